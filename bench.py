@@ -7,6 +7,12 @@ One process per GPU (torch.distributed, backend nccl = RCCL); weak scaling, 8 cl
 per GPU.  One "step" = H2D of the int32 codes + int64 targets (prefetched) + forward on the loader-layout one-hot of
 those codes (not materialised: gather / scatter in the causal layer) + CrossEntropy-on-probabilities + backward +
 gradient all-reduce (N > 1) + Adam, i.e. wavenet/train.py:171-182 of the reference.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the headline (samples/s, ms_per_step, per-step statistics).
+`--full` adds everything else the line used to carry: the phase table, roofline and MFMA figures (HIP events inside the
+timed region and untimed steps of their own), the host's enqueue rate, the per-kernel split, the config-4 / config-5 /
+shipped-parameter sub-benchmarks and the CPU baseline.  `--dump-outputs DIR` writes what the last timed step handed its
+caller (loss, flat gradient, parameters after Adam) as .npy files, so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -491,6 +497,22 @@ def measured_copy_gbs():
     return 2.0 * n * 4 / (best * 1e-3) / 1e9
 
 
+DUMP_LIMIT = 64 << 20      # bytes, all --dump-outputs files together
+
+
+def dump_outputs(d, loss, eng):
+    """--dump-outputs: what the timed path hands its caller after its last step - the loss, the gradient (flat, state_dict
+    order, after the all-reduce when N > 1) and the parameters Adam left (flat, same order) - as DIR/<name>.npy."""
+    arrays = {"loss": loss.detach().to(torch.float64).reshape(1).cpu().numpy(),
+              "grad": eng.flat_grad.detach().to(torch.float32).cpu().numpy(),
+              "params": eng.flat.detach().to(torch.float32).cpu().numpy()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, "outputs of %d bytes exceed the dump limit" % total
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -498,13 +520,20 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--settle", type=int, default=60, help="discarded steps before the warm-up (one-time costs of a fresh box)")
     ap.add_argument("--dump-steps", action="store_true", help="every timed step's GPU time in the line (ms_per_step_stats.all_in_order)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's loss, gradient and parameters to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also the phase table, roofline / MFMA / per-kernel figures, sub-benchmarks and the CPU baseline")
     ap.add_argument("--precision", default="f16x3,bf16x3")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the config-4 / config-5 sub-benchmarks")
-    ap.add_argument("--phases", action="store_true", help="print the per-phase GPU time table to stderr")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="(--full) skip the config-4 / config-5 sub-benchmarks")
+    ap.add_argument("--phases", action="store_true", help="(--full) print the per-phase GPU time table to stderr")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch plumbing only (CPU, gloo): every rank joins the group, rank 0 prints the world size")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.phases and not args.full:
+        ap.error("--phases needs --full (the phase table takes steps of its own)")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -615,9 +644,10 @@ def main():
     # tenth step (code-object loads, workspace allocation, the first timing events of the sampled marks, the copy stream's
     # first transfers: 25-step windows read 5.3-5.7, then 4.24 ms from the second window on, tools/settle_probe.py), and
     # the metric is STEADY-STATE throughput.  The settle steps run the timed loop's own code path, sampled
-    # marks included, and are discarded; the contract's W untimed + K timed steps follow unchanged.
-    state["sampled"], state["k0"] = [], state["k"]
-    eng.mark_only = {"step_begin", "causal_fwd", "stack_fwd", "epilogue_bwd", "stack_bwd"}
+    # marks included (--full), and are discarded; the contract's W untimed + K timed steps follow unchanged.
+    sampled_marks = {"step_begin", "causal_fwd", "stack_fwd", "epilogue_bwd", "stack_bwd"} if args.full else None
+    state["sampled"], state["k0"] = ([] if args.full else None), state["k"]
+    eng.mark_only = sampled_marks
     # ... but the one-time cost stays visible: the first window of the process (min(25, settle) steps, wall clock) is reported
     first_n = min(25, args.settle)
     first_ms = None
@@ -644,9 +674,9 @@ def main():
     # inside the timed region only the events the roofline figures need (the two ends of the forward and of the backward
     # stack), and only on every MARK_EVERY-th step: a timing event is a marker packet between two dependent kernels, and
     # five of them per step cost 0.12-0.17 ms of a 4.6 ms step (same-box A/B).  The full phase table comes from 3 untimed
-    # steps afterwards.
-    state["sampled"], state["k0"] = [], state["k"]
-    eng.mark_only = {"step_begin", "causal_fwd", "stack_fwd", "epilogue_bwd", "stack_bwd"}
+    # steps afterwards.  A plain run (no --full) records none of them.
+    state["sampled"], state["k0"] = ([] if args.full else None), state["k"]
+    eng.mark_only = sampled_marks
     # one event per step end (enable_timing): median / min / max of the per-step GPU time
     t0 = time.perf_counter()
     step_ev[0].record()
@@ -672,6 +702,54 @@ def main():
         dt_ranks = [float(t.item()) for t in tg]
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = tt.item()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, eng)            # before any untimed step of --full moves the parameters on
+
+    x3 = args.precision == "f16x3,bf16x3"
+    out = {
+        "metric": "audio samples/sec trained (whole node), 30-layer WaveNet @16kHz",
+        "value": world * B_LOCAL * T * args.steps / dt,
+        "unit": "samples/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "settle_steps": args.settle, "full": args.full,
+        "ms_per_step": dt / args.steps * 1e3,
+        "ms_per_step_stats": {"median": per_step[len(per_step) // 2], "min": per_step[0], "max": per_step[-1],
+                              "p90": per_step[min(len(per_step) - 1, (len(per_step) * 9) // 10)], "first_10_in_order": per_step_order[:10], **({"all_in_order": per_step_order, "host_enqueued_at_ms": [round((t - t0) * 1e3, 2) for t in host_t]} if args.dump_steps else {}),
+                              "note": "GPU time between the end-of-step HIP events of consecutive timed steps (rank 0); the interpreter's garbage collector runs before the timed region, not inside it"} if per_step else None,
+        "ms_per_step_ranks": {"min": min(dt_ranks) / args.steps * 1e3, "max": max(dt_ranks) / args.steps * 1e3,
+                              "all": [round(v / args.steps * 1e3, 4) for v in dt_ranks],
+                              "note": "each rank's wall time over the K timed steps / K; ms_per_step is the max (the contract)"},
+        "host_threads": {"torch_intra_op": torch.get_num_threads(), "OMP_NUM_THREADS": os.environ.get("OMP_NUM_THREADS"),
+                         "local_world_size": int(os.environ.get("LOCAL_WORLD_SIZE", "1"))},
+        "first_window": {"steps": first_n, "ms_per_step": first_ms,
+                         "note": "the first steps of this process (one-time costs included), before the settle / warm-up steps are discarded"},
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32 (forward + recompute: f16 2-term split operands, 2^-22 per element; backward products: bf16 2-term split, 2^-17 per element, f32 range; 3 MFMA per product, f32 accumulate)" if x3 else args.precision,
+        "data": "synthetic",
+        "rccl_ranks": world if (use_dist and dist.get_backend() == "nccl") else 0, "backend": (dist.get_backend() if use_dist else "none"),
+        "config": {"workload": "BASELINE configs[1]: 30-layer (3x dilations 1..512) WaveNet, 64 res/dil, 256 skip, "
+                               "batch 8x16000 per GPU, full train step (H2D of codes and targets, prefetched one step ahead on a copy stream, + fwd on the loader-layout one-hot of the codes (never materialised) + CE + bwd + all-reduce + Adam)",
+                   "global_batch": world * B_LOCAL, "seq_len": T, "parallelism": "dp%d" % world,
+                   "precision": args.precision, "final_loss": float(loss.item()),
+                   # (the median of the K timed steps beside the mean in ms_per_step - the device has bursts of 6 ms steps on
+                   # some boxes, profiles/r06_gemm_tiles.md section 3)
+                   "ms_per_step_median": per_step[len(per_step) // 2] if per_step else None,
+                   "ms_per_step_p90": per_step[min(len(per_step) - 1, (len(per_step) * 9) // 10)] if per_step else None,
+                   "slow_steps_over_1p15_median": sum(1 for v in per_step if v > 1.15 * per_step[len(per_step) // 2]) if per_step else None},
+        # the same run as predicted samples/s (x W/T)
+        "predicted_samples_per_s": world * B_LOCAL * W * args.steps / dt,
+    }
+
+    def emit(out):
+        if use_dist:
+            dist.destroy_process_group()
+        sys.stdout.flush()
+        os.dup2(stdout_fd, 1)
+        os.close(stdout_fd)
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+    if not args.full:
+        emit(out)
+        return
 
     # per-phase GPU time from the HIP events recorded on the launch stream inside the timed region
     phase, phase_all = {}, {}
@@ -796,7 +874,6 @@ def main():
         "epilogue_bwd": 3 * B * 2 * (fl["skip"] + fl["post"]),
         "causal_fwd": 3 * B * fl["causal"],
     }
-    x3 = args.precision == "f16x3,bf16x3"
     mfma = {"peak_TFLOPs": MFMA_PEAK / 1e12, "unit": "fraction of the dense 16-bit MFMA peak",
             "note": "issued MFMA FLOPs = 3 x algorithmic (2-term operand split) / phase time / peak" if x3 else
                     "issued MFMA FLOPs = algorithmic / phase time / peak"}
@@ -810,36 +887,8 @@ def main():
     mfma["issued_TFLOP_per_step"] = tot_fl / 1e12
 
     bwd_launch_ms = bwd_ms / n_layers
-    out = {
-        "metric": "audio samples/sec trained (whole node), 30-layer WaveNet @16kHz",
-        "value": world * B_LOCAL * T * args.steps / dt,
-        "unit": "samples/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "settle_steps": args.settle,
-        "ms_per_step": dt / args.steps * 1e3,
-        "ms_per_step_stats": {"median": per_step[len(per_step) // 2], "min": per_step[0], "max": per_step[-1],
-                              "p90": per_step[min(len(per_step) - 1, (len(per_step) * 9) // 10)], "first_10_in_order": per_step_order[:10], **({"all_in_order": per_step_order, "host_enqueued_at_ms": [round((t - t0) * 1e3, 2) for t in host_t]} if args.dump_steps else {}),
-                              "note": "GPU time between the end-of-step HIP events of consecutive timed steps (rank 0); the interpreter's garbage collector runs before the timed region, not inside it"} if per_step else None,
-        "ms_per_step_ranks": {"min": min(dt_ranks) / args.steps * 1e3, "max": max(dt_ranks) / args.steps * 1e3,
-                              "all": [round(v / args.steps * 1e3, 4) for v in dt_ranks],
-                              "note": "each rank's wall time over the K timed steps / K; ms_per_step is the max (the contract)"},
+    out.update({
         "host_enqueue_ms_per_step": host_enqueue_ms,
-        "host_threads": {"torch_intra_op": torch.get_num_threads(), "OMP_NUM_THREADS": os.environ.get("OMP_NUM_THREADS"),
-                         "local_world_size": int(os.environ.get("LOCAL_WORLD_SIZE", "1"))},
-        "first_window": {"steps": first_n, "ms_per_step": first_ms,
-                         "note": "the first steps of this process (one-time costs included), before the settle / warm-up steps are discarded"},
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32 (forward + recompute: f16 2-term split operands, 2^-22 per element; backward products: bf16 2-term split, 2^-17 per element, f32 range; 3 MFMA per product, f32 accumulate)" if x3 else args.precision,
-        "data": "synthetic",
-        "rccl_ranks": world if (use_dist and dist.get_backend() == "nccl") else 0, "backend": (dist.get_backend() if use_dist else "none"),
-        "config": {"workload": "BASELINE configs[1]: 30-layer (3x dilations 1..512) WaveNet, 64 res/dil, 256 skip, "
-                               "batch 8x16000 per GPU, full train step (H2D of codes and targets, prefetched one step ahead on a copy stream, + fwd on the loader-layout one-hot of the codes (never materialised) + CE + bwd + all-reduce + Adam)",
-                   "global_batch": world * B_LOCAL, "seq_len": T, "parallelism": "dp%d" % world,
-                   "precision": args.precision, "final_loss": float(loss.item()),
-                   # (the driver's record keeps `config`: the median of the K timed steps beside the mean in ms_per_step - the device has
-                   # bursts of 6 ms steps on some boxes, profiles/r06_gemm_tiles.md section 3)
-                   "ms_per_step_median": per_step[len(per_step) // 2] if per_step else None,
-                   "ms_per_step_p90": per_step[min(len(per_step) - 1, (len(per_step) * 9) // 10)] if per_step else None,
-                   "slow_steps_over_1p15_median": sum(1 for v in per_step if v > 1.15 * per_step[len(per_step) // 2]) if per_step else None},
         # the time-dominant kernels: one residual block's backward (SURVEY 8d A_b per block; duration = the HIP-event
         # time of the backward stack inside the timed region / its 30 blocks)
         "roofline": roof(bwd_b / n_layers, bwd_launch_ms,
@@ -863,8 +912,7 @@ def main():
         "roofline_stack_bwd": roof(bwd_b, bwd_ms, algorithmic_bytes_per_step=bwd_b),
         "roofline_stack_fwd_bwd": roof(fwd_b + bwd_b, fwd_ms + bwd_ms, algorithmic_bytes_per_step=fwd_b + bwd_b),
         "mfma_util": mfma,
-        # the same run as predicted samples/s (x W/T), and the dilated-conv stack alone (forward, forward + backward)
-        "predicted_samples_per_s": world * B_LOCAL * W * args.steps / dt,
+        # the dilated-conv stack alone (forward, forward + backward)
         "stack_only": {"fwd_ms": fwd_ms, "fwd_bwd_ms": fwd_ms + bwd_ms,
                        "fwd_bwd_input_samples_per_s_per_gpu": B_LOCAL * T / ((fwd_ms + bwd_ms) * 1e-3) if fwd_ms == fwd_ms else None,
                        "target_fwd_bwd_ms_at_40pct_of_hbm": (fwd_b + bwd_b) / (0.4 * HBM_PEAK) * 1e3},
@@ -873,7 +921,7 @@ def main():
         "timed_region_ms_per_step": {k: (round(v, 4) if v is not None else None) for k, v in timed.items()},
         "timed_region_events": "HIP events on the launch stream around the forward and the backward stack, on every %d-th of the "
                                "timed steps (%d of %d); means over those steps" % (MARK_EVERY, n_sampled, args.steps),
-    }
+    })
     if kern:
         out["kernels"] = kern
     # the side measurements must never cost the headline line: a failure is recorded in place of the figure
@@ -922,13 +970,7 @@ def main():
             "shipped_autoencoder_ms_per_step": dig(ex, "shipped_params", "autoencoder", "ms_per_step"),
             "cpu_baseline_samples_per_s": dig(out, "cpu_baseline", "value"),
         }
-    if use_dist:
-        dist.destroy_process_group()
-    sys.stdout.flush()
-    os.dup2(stdout_fd, 1)
-    os.close(stdout_fd)
-    if rank == 0:
-        print(json.dumps(out), flush=True)
+    emit(out)
 
 
 if __name__ == "__main__":

@@ -192,3 +192,14 @@ def test_bench_self_launches_its_ranks():
         if n > 1:
             from music_amd import _lib
             assert out["omp_num_threads"] == str(min(8, _lib.thread_budget(_lib.cpu_quota(), n))), out
+
+
+def test_bench_rejects_arguments_it_cannot_honour():
+    """No timed step (`--steps 0`) and the phase table without `--full` (it takes untimed steps of its own) are refused
+    while the arguments are parsed, before anything touches a GPU."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    for extra, word in ((["--steps", "0"], "--steps"), (["--phases"], "--full")):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + extra, env=env,
+                           capture_output=True, text=True, timeout=300)
+        assert r.returncode == 2 and word in r.stderr, r.stderr[-2000:]
+        assert r.stdout.strip() == ""

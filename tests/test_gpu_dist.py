@@ -92,7 +92,7 @@ def test_bench_two_ranks_on_this_box(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     if torch.cuda.device_count() < 2:
         env["WN_DIST_BACKEND"] = "gloo"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"], env=env,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"], env=env,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = r.stdout.strip().split("\n")
@@ -125,7 +125,7 @@ def test_bench_eight_ranks_on_this_box():
     n_gpu = torch.cuda.device_count()
     if n_gpu < 8:
         env["WN_DIST_BACKEND"] = "gloo"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--settle", "2"], env=env,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--settle", "2", "--full"], env=env,
                        capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = r.stdout.strip().split("\n")
@@ -151,13 +151,45 @@ def test_bench_under_launcher_prints_one_json_line_with_rccl():
     # the DRIVER's launch form, verbatim (explicit master address and port)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-           "--no-cpu-baseline", "--no-extras"]
+           "--full", "--no-cpu-baseline", "--no-extras"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = r.stdout.strip().split("\n")
     assert len(lines) == 1 and lines[0].startswith("{"), r.stdout
     out = json.loads(lines[0])
     assert out["n_gpus"] == 1 and out["rccl_ranks"] == 1 and out["backend"] == "nccl" and "allreduce" in out["phase_ms_per_step"]
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """`python bench.py --gpus 1` without --full: ONE line with the headline alone (no phase table, roofline, sub-benchmarks or
+    CPU baseline), exactly --steps timed steps, and --dump-outputs writes what the last timed step handed its caller - the
+    loss, the flat gradient and the parameters after Adam - the same arrays from two runs with the same arguments."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    runs = []
+    for i in range(2):
+        d = tmp_path / ("run%d" % i)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--settle", "2",
+                            "--dump-steps", "--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        lines = r.stdout.strip().split("\n")
+        assert len(lines) == 1 and lines[0].startswith("{"), r.stdout
+        out = json.loads(lines[0])
+        assert out["steps"] == 3 and out["full"] is False and len(out["ms_per_step_stats"]["all_in_order"]) == 3
+        assert out["unit"] == "samples/s" and out["higher_is_better"] is True and out["dtype"].startswith("f32")
+        assert abs(out["value"] - 8 * 16000 / (out["ms_per_step"] * 1e-3)) < 1e-6 * out["value"]
+        assert not set(out) & {"phase_ms_per_step", "roofline", "mfma_util", "host_enqueue_ms_per_step", "kernels", "extra",
+                               "cpu_baseline", "summary"}
+        a = {n: np.load(str(d / (n + ".npy"))) for n in ("loss", "grad", "params")}
+        assert a["loss"].dtype == np.float64 and a["loss"].shape == (1,)
+        assert abs(a["loss"][0] - out["config"]["final_loss"]) <= 1e-6 * abs(out["config"]["final_loss"])
+        assert a["grad"].dtype == a["params"].dtype == np.float32 and a["grad"].ndim == 1 and a["grad"].shape == a["params"].shape
+        assert np.isfinite(a["grad"]).all() and np.isfinite(a["params"]).all() and np.abs(a["grad"]).max() > 0
+        assert sum(v.nbytes for v in a.values()) <= 64 << 20
+        runs.append(a)
+    for n in ("loss", "grad", "params"):
+        x, y = runs[0][n].astype(np.float64), runs[1][n].astype(np.float64)
+        assert np.abs(x - y).max() <= 1e-5 * np.abs(x).max(), n
 
 
 def test_allreduce_flat_through_the_c_abi_one_rank():

@@ -7,7 +7,7 @@ timeout 300 python tools/gemm_bench.py --rounds 3 2>/dev/null | grep fused
 for r in 1 2 3; do
 for v in "old:WN_EPI_FUSED_BWD=0 WN_EPI_FUSED=0 WN_GEMM_BST=0" "new:"; do
   n=${v%%:*}; e=${v#*:}
-  env $e python bench.py --no-cpu-baseline --no-extras --steps 200 --dump-steps > $O/$n.$r.json 2> $O/$n.$r.err
+  env $e python bench.py --full --no-cpu-baseline --no-extras --steps 200 --dump-steps > $O/$n.$r.json 2> $O/$n.$r.err
   python - <<PY
 import json
 d=json.load(open("$O/$n.$r.json"))
