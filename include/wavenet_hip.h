@@ -42,7 +42,7 @@ extern "C" {
 
 typedef void* wn_stream_t;                 /* hipStream_t */
 enum { WN_F16X3 = 0, WN_F16X1 = 1, WN_BF16X3 = 2, WN_BF16X1 = 3 };
-#define WN_ABI_VERSION 5
+#define WN_ABI_VERSION 6
 #define WN_CE_NUM_PARTIALS 1024
 
 int wn_version(void);
@@ -428,6 +428,26 @@ int64_t wn_decode_sync_granules(int n_layers, int D, int S);
 int wn_decode_batch_pk(int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host, const int64_t* q_off_host,
                        float* queues, const float* w_causal, const float* b_causal, const float* w_layers,
                        int64_t layer_stride, const float* b_layers, const float* w_p1, const float* b_p1,
+                       const float* w_p2, const float* b_p2, const float* note0, const float* prev0, float* note_out,
+                       float* prev_out, const int32_t* forced, int32_t* codes_out, float* probs_out, int64_t step0,
+                       int n_steps, int push_input, uint64_t* sync, int n_utt, int64_t queues_ustride, float temperature,
+                       uint64_t seed, const uint16_t* pk, int64_t pk_fg0, int64_t pk_d0, int64_t pk_lstride, int64_t pk_skip,
+                       int64_t pk_p1, int64_t pk_p2, wn_stream_t stream);
+/* wn_decode_batch_pk for any filter width k = filter_width >= 1 (ABI 6).  Block i reads its input at t, t - d_i, ..,
+ * t - (k-1) d_i: its queue is a ring of L_i = (k-1) d_i columns [L_i][R] (time-major) at float offset q_off[i]; at global
+ * step g tap j (0 <= j <= k-2) reads slot (g + j d_i) mod L_i, and slot g mod L_i - the oldest, tap 0 - is then overwritten
+ * with the block's INPUT (k = 1: no rings).  The causal layer keeps k - 1 previous input columns: prev0 / prev_out hold
+ * (k-1) * Q floats per utterance, oldest column first (utterance u at + u*(k-1)*Q; may be NULL when k = 1).  fp32 weights:
+ * w_causal [R][kQ] (k = tap 0 q | tap 1 q | .. | tap k-1 q); per block Wfg [2D][kR] with k = tap k-1 r (current input) |
+ * tap k-2 r | .. | tap 0 r, then Wd [R][D], Ws [S][D] at layer_stride floats per block.  Any Q from 1 to 1024 (probs_out
+ * rows hold Q floats).  k = 2 is wn_decode_batch_pk, same results.  The matrix-core kernels serve k = 2, 3 and 4 (pk with
+ * fg fragments [2 x 64][64 k] per block in natural k order; k = 3 / 4 need the tap-0-ahead form); other widths run the
+ * fp32 kernel and ignore pk.  Returns -4 (wn_last_error says why) for filter_width < 1, push_input = 0 with
+ * k != 2 (the as-written recurrence is only defined for k = 2), NULL required pointers, and a layout that does not fit
+ * the kernel's LDS. */
+int wn_decode_batch_fw(int filter_width, int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host,
+                       const int64_t* q_off_host, float* queues, const float* w_causal, const float* b_causal,
+                       const float* w_layers, int64_t layer_stride, const float* b_layers, const float* w_p1, const float* b_p1,
                        const float* w_p2, const float* b_p2, const float* note0, const float* prev0, float* note_out,
                        float* prev_out, const int32_t* forced, int32_t* codes_out, float* probs_out, int64_t step0,
                        int n_steps, int push_input, uint64_t* sync, int n_utt, int64_t queues_ustride, float temperature,

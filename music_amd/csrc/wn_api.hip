@@ -450,7 +450,7 @@ static int decode_impl(int n_layers, int R, int D, int S, int Q, const int32_t* 
                        float* prev_out, const int32_t* forced, int32_t* codes_out, float* probs_out, int64_t step0,
                        int n_steps, int push_input, uint64_t* sync, int64_t sync_ustride, int n_utt, int64_t queues_ustride,
                        float temperature, uint64_t seed, const uint16_t* pk, int64_t pk_fg0, int64_t pk_d0, int64_t pk_lstride,
-                       int64_t pk_skip, int64_t pk_p1, int64_t pk_p2, wn_stream_t stream);
+                       int64_t pk_skip, int64_t pk_p1, int64_t pk_p2, int fw, wn_stream_t stream);
 extern "C" {
 int64_t wn_decode_sync_granules(int n_layers, int D, int S);
 int wn_decode_batch(int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host, const int64_t* q_off_host,
@@ -490,7 +490,7 @@ int wn_decode_batch(int n_layers, int R, int D, int S, int Q, const int32_t* dil
     return decode_impl(n_layers, R, D, S, Q, dilations_host, q_off_host, queues, w_causal, b_causal, w_layers, layer_stride,
                        b_layers, w_p1, b_p1, w_p2, b_p2, note0, prev0, note_out, prev_out, forced, codes_out, probs_out,
                        step0, n_steps, push_input, sync, (int64_t)n_layers * D + 2, n_utt, queues_ustride, temperature, seed,
-                       nullptr, 0, 0, 0, -1, -1, -1, stream);
+                       nullptr, 0, 0, 0, -1, -1, -1, 2, stream);
 }
 
 int64_t wn_decode_sync_granules(int n_layers, int D, int S) {
@@ -508,7 +508,30 @@ int wn_decode_batch_pk(int n_layers, int R, int D, int S, int Q, const int32_t* 
     return decode_impl(n_layers, R, D, S, Q, dilations_host, q_off_host, queues, w_causal, b_causal, w_layers, layer_stride,
                        b_layers, w_p1, b_p1, w_p2, b_p2, note0, prev0, note_out, prev_out, forced, codes_out, probs_out,
                        step0, n_steps, push_input, sync, wn_decode_sync_granules(n_layers, D, S), n_utt, queues_ustride,
-                       temperature, seed, pk, pk_fg0, pk_d0, pk_lstride, pk_skip, pk_p1, pk_p2, stream);
+                       temperature, seed, pk, pk_fg0, pk_d0, pk_lstride, pk_skip, pk_p1, pk_p2, 2, stream);
+}
+
+int wn_decode_batch_fw(int filter_width, int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host,
+                       const int64_t* q_off_host, float* queues, const float* w_causal, const float* b_causal,
+                       const float* w_layers, int64_t layer_stride, const float* b_layers, const float* w_p1, const float* b_p1,
+                       const float* w_p2, const float* b_p2, const float* note0, const float* prev0, float* note_out,
+                       float* prev_out, const int32_t* forced, int32_t* codes_out, float* probs_out, int64_t step0,
+                       int n_steps, int push_input, uint64_t* sync, int n_utt, int64_t queues_ustride, float temperature,
+                       uint64_t seed, const uint16_t* pk, int64_t pk_fg0, int64_t pk_d0, int64_t pk_lstride, int64_t pk_skip,
+                       int64_t pk_p1, int64_t pk_p2, wn_stream_t stream) {
+    if (filter_width < 1) return wn_set_error_msg(-4, "wn_decode_batch_fw: filter_width must be >= 1");
+    if (filter_width != 2 && !push_input)
+        return wn_set_error_msg(-4, "wn_decode_batch_fw: the as-written queue push (push_input = 0) exists for filter_width 2 "
+                                    "only; pass push_input = 1 (the corrected recurrence)");
+    if (Q < 1 || Q > WN_DEC_MAX_Q) return wn_set_error_msg(-4, "wn_decode_batch_fw: 1 <= Q <= 1024 quantisation channels");
+    if (n_utt > 0 && n_steps > 0) {
+        WN_REQUIRE("wn_decode_batch_fw", note0, note_out, codes_out);
+        if (filter_width > 1) WN_REQUIRE("wn_decode_batch_fw", prev0, prev_out);
+    }
+    return decode_impl(n_layers, R, D, S, Q, dilations_host, q_off_host, queues, w_causal, b_causal, w_layers, layer_stride,
+                       b_layers, w_p1, b_p1, w_p2, b_p2, note0, prev0, note_out, prev_out, forced, codes_out, probs_out,
+                       step0, n_steps, push_input, sync, wn_decode_sync_granules(n_layers, D, S), n_utt, queues_ustride,
+                       temperature, seed, pk, pk_fg0, pk_d0, pk_lstride, pk_skip, pk_p1, pk_p2, filter_width, stream);
 }
 
 }  // extern "C"
@@ -520,14 +543,14 @@ static int decode_impl(int n_layers, int R, int D, int S, int Q, const int32_t* 
                        float* prev_out, const int32_t* forced, int32_t* codes_out, float* probs_out, int64_t step0,
                        int n_steps, int push_input, uint64_t* sync, int64_t sync_ustride, int n_utt, int64_t queues_ustride,
                        float temperature, uint64_t seed, const uint16_t* pk, int64_t pk_fg0, int64_t pk_d0, int64_t pk_lstride,
-                       int64_t pk_skip, int64_t pk_p1, int64_t pk_p2, wn_stream_t stream) {
+                       int64_t pk_skip, int64_t pk_p1, int64_t pk_p2, int fw, wn_stream_t stream) {
     if (n_utt <= 0) return 0;
     if (n_layers > WN_DEC_MAX_LAYERS || n_layers <= 0) return wn_set_error_msg(-4, "wn_decode: 1..64 layers supported");
     WN_REQUIRE("wn_decode", dilations_host, q_off_host);              // (host arrays, read right here)
     if (n_steps > 0) WN_REQUIRE("wn_decode", queues, w_causal, w_layers, w_p1, w_p2, sync);
     WnDecodeArgs a;
     memset(&a, 0, sizeof(a));
-    a.n_layers = n_layers; a.R = R; a.D = D; a.S = S; a.Q = Q;
+    a.n_layers = n_layers; a.R = R; a.D = D; a.S = S; a.Q = Q; a.fw = fw;
     for (int i = 0; i < n_layers; ++i) { a.dil[i] = dilations_host[i]; a.q_off[i] = q_off_host[i]; }
     a.queues = queues; a.w_causal = w_causal; a.b_causal = b_causal; a.w_layers = w_layers; a.layer_stride = layer_stride;
     a.b_layers = b_layers; a.w_p1 = w_p1; a.b_p1 = b_p1; a.w_p2 = w_p2; a.b_p2 = b_p2;

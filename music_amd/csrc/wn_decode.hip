@@ -45,23 +45,27 @@ __device__ __forceinline__ void dec_matvec(const float* __restrict__ W, int ldw,
 }
 
 
-// Next code from the 256 pre-softmax logits (one wave, lane l owns entries 4l..4l+3): probabilities =
-// softmax(logit * inv_temp) (written to probs_dst if given), then either the first-index argmax (the
-// reference's greedy topk(1), fast_generate.py:139) or - SURVEY 8f2 - a draw from that distribution by
-// inverse CDF with the uniform number u in [0,1).  The result is valid in every lane.
-__device__ __forceinline__ int dec_choose(const float* logit, int lane, float* probs_dst, float inv_temp, bool sample, float u) {
-    float v[4], m = -INFINITY;
-    for (int e = 0; e < 4; ++e) { v[e] = logit[lane * 4 + e]; m = fmaxf(m, v[e]); }
+// Next code from the Q pre-softmax logits (one wave, lane l owns entries NE*l .. NE*l + NE-1, entries >= Q are -inf padding
+// and never read or written; NE = 4 for the usual 256): probabilities = softmax(logit * inv_temp) (written to probs_dst
+// if given), then either the first-index argmax (the reference's greedy topk(1), fast_generate.py:139) or - SURVEY 8f2 -
+// a draw from that distribution by inverse CDF with the uniform number u in [0,1).  The result is valid in every lane.
+template <int NE>
+__device__ __forceinline__ int dec_choose(const float* logit, int Q, int lane, float* probs_dst, float inv_temp, bool sample, float u) {
+    float v[NE], m = -INFINITY;
+    for (int e = 0; e < NE; ++e) { const int i = lane * NE + e; v[e] = i < Q ? logit[i] : -INFINITY; m = fmaxf(m, v[e]); }
     for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
     float s = 0.f;
-    for (int e = 0; e < 4; ++e) { v[e] = expf((v[e] - m) * inv_temp); s += v[e]; }
+    for (int e = 0; e < NE; ++e) { v[e] = expf((v[e] - m) * inv_temp); s += v[e]; }
     for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
     const float inv = 1.0f / s;
     float best = -1.f; int bi = 0;
-    for (int e = 0; e < 4; ++e) {
+    for (int e = 0; e < NE; ++e) {
+        const int i = lane * NE + e;
         v[e] *= inv;
-        if (probs_dst) probs_dst[lane * 4 + e] = v[e];
-        if (v[e] > best) { best = v[e]; bi = lane * 4 + e; }
+        if (i < Q) {
+            if (probs_dst) probs_dst[i] = v[e];
+            if (v[e] > best) { best = v[e]; bi = i; }
+        }
     }
     if (!sample) {
         for (int off = 32; off > 0; off >>= 1) {
@@ -71,8 +75,13 @@ __device__ __forceinline__ int dec_choose(const float* logit, int lane, float* p
         }
         return bi;
     }
-    // inclusive scan of the lane sums, then the first entry whose cumulative probability exceeds u
-    const float mine = (v[0] + v[1]) + (v[2] + v[3]);
+    // inclusive scan of the lane sums (pairwise: (v0 + v1) + (v2 + v3) for NE = 4), then the first entry whose
+    // cumulative probability exceeds u
+    float t[NE];
+    for (int e = 0; e < NE; ++e) t[e] = v[e];
+    for (int w = 1; w < NE; w <<= 1)
+        for (int e = 0; e + w < NE; e += 2 * w) t[e] += t[e + w];
+    const float mine = t[0];
     float incl = mine;
     for (int off = 1; off < 64; off <<= 1) {
         const float o = __shfl_up(incl, off, 64);
@@ -80,12 +89,20 @@ __device__ __forceinline__ int dec_choose(const float* logit, int lane, float* p
     }
     float c = incl - mine;
     int pick = 1 << 20;
-    for (int e = 0; e < 4; ++e) {
+    for (int e = 0; e < NE; ++e) {
         c += v[e];
-        if (pick == (1 << 20) && c > u) pick = lane * 4 + e;
+        if (pick == (1 << 20) && c > u) pick = lane * NE + e;
     }
     for (int off = 32; off > 0; off >>= 1) pick = min(pick, __shfl_xor(pick, off, 64));
-    return pick < 256 ? pick : 255;                 // (u above the rounded total: last entry)
+    return pick < Q ? pick : Q - 1;                 // (u above the rounded total: last entry)
+}
+// any Q up to WN_DEC_MAX_Q: the smallest power-of-two entry count per lane that covers it
+__device__ __forceinline__ int dec_choose_any(const float* logit, int Q, int lane, float* probs_dst, float inv_temp, bool sample, float u) {
+    if (Q <= 64) return dec_choose<1>(logit, Q, lane, probs_dst, inv_temp, sample, u);
+    if (Q <= 128) return dec_choose<2>(logit, Q, lane, probs_dst, inv_temp, sample, u);
+    if (Q <= 256) return dec_choose<4>(logit, Q, lane, probs_dst, inv_temp, sample, u);
+    if (Q <= 512) return dec_choose<8>(logit, Q, lane, probs_dst, inv_temp, sample, u);
+    return dec_choose<16>(logit, Q, lane, probs_dst, inv_temp, sample, u);
 }
 
 // Uniform number in [0,1) for (seed, global step, utterance): splitmix64 finaliser, 24 random bits.
@@ -97,65 +114,77 @@ __device__ __forceinline__ float dec_uniform(unsigned long long seed, unsigned l
     return (float)(z >> 40) * (1.0f / 16777216.0f);
 }
 
+// filter width k = a.fw >= 1: the causal layer reads the k - 1 previous input columns and the current one; block i reads
+// its input at t, t - d, .., t - (k-1) d from a ring of L = (k-1) d columns (tap j, 0 <= j <= k-2, at slot (g + j d) mod L
+// of global step g; slot g mod L is the oldest: read as tap 0, then overwritten).  For k = 2 this is the loop above,
+// with the same arithmetic in the same order.
+// FW = 2: the filter width fixed at compile time (the arithmetic and schedule of the two-tap loop); FW = 0: any width a.fw
+template <int FW>
 __global__ __launch_bounds__(DEC_THREADS) void decode_k(WnDecodeArgs a) {
     // utterance of a batched launch: per-utterance pointers as LOCALS (the argument struct itself must stay
     // untouched: a modified copy would be moved to scratch and every dil[] / q_off[] lookup with it)
+    const int fw = FW ? FW : a.fw;
+    const int K1 = fw - 1;                                      // history columns (taps before the current one)
     const size_t utt = blockIdx.x;
     float* const u_queues = a.queues + utt * a.queues_ustride;
     const float* const u_note0 = a.note0 + utt * a.Q;
-    const float* const u_prev0 = a.prev0 + utt * a.Q;
+    const float* const u_prev0 = a.prev0 ? a.prev0 + utt * (size_t)K1 * a.Q : nullptr;
     float* const u_note_out = a.note_out + utt * a.Q;
-    float* const u_prev_out = a.prev_out + utt * a.Q;
+    float* const u_prev_out = a.prev_out ? a.prev_out + utt * (size_t)K1 * a.Q : nullptr;
     const int32_t* const u_forced = a.forced ? a.forced + utt * a.n_steps : nullptr;
     int32_t* const u_codes_out = a.codes_out + utt * a.n_steps;
     float* const u_probs_out = a.probs_out ? a.probs_out + utt * (size_t)a.n_steps * a.Q : nullptr;
-    unsigned long long* const u_sync = a.sync ? a.sync + utt * (size_t)a.sync_ustride : nullptr;
     extern __shared__ float sm[];
-    float* prev = sm;                       // [Q] previous input column (the causal layer's queue)
-    float* note = prev + a.Q;               // [Q] current input column (dense); [prev|note] is contiguous
+    float* prev = sm;                       // [k-1][Q] previous input columns, oldest first (the causal layer's queue)
+    float* note = prev + K1 * a.Q;          // [Q] current input column (dense); [prev|note] is contiguous
     float* cur = note + a.Q;                // [R] residual stream at this sample
-    float* old = cur + a.R;                 // [R] oldest queue column of the current block
-    float* fg = old + a.R;                  // [2D]
+    float* old = cur + a.R;                 // [k-1][R] queue columns of the current block: tap k-2 first, tap 0 last
+    float* fg = old + K1 * a.R;             // [2D]
     float* z = fg + 2 * a.D;                // [D]
     float* nxt = z + a.D;                   // [R]
     float* skip = nxt + a.R;                // [S]
     float* h1 = skip + a.S;                 // [S]
     float* logit = h1 + a.S;                // [Q]
-    float* red = logit + a.Q;               // [64]
     __shared__ int s_arg;
     const int tid = threadIdx.x;
 
-    for (int i = tid; i < a.Q; i += DEC_THREADS) { note[i] = u_note0[i]; prev[i] = u_prev0[i]; }
+    for (int i = tid; i < a.Q; i += DEC_THREADS) note[i] = u_note0[i];
+    for (int i = tid; i < K1 * a.Q; i += DEC_THREADS) prev[i] = u_prev0[i];
     __syncthreads();
 
     for (int step = 0; step < a.n_steps; ++step) {
         const long gstep = a.step0 + step;                      // global step index: ring positions
-        // ---- causal layer: cur = Wc[:, 0:Q] prev + Wc[:, Q:2Q] note
-        dec_matvec(a.w_causal, 2 * a.Q, prev /* note follows prev in LDS */, a.R, 2 * a.Q, a.b_causal,
+        // ---- causal layer: cur = sum_j Wc[:, jQ:(j+1)Q] col_j over [prev_0 .. prev_{k-2} | note]
+        dec_matvec(a.w_causal, fw * a.Q, prev /* note follows prev in LDS */, a.R, fw * a.Q, a.b_causal,
                    [&](int o, float v) { cur[o] = v; });
         for (int i = tid; i < a.S; i += DEC_THREADS) skip[i] = 0.f;
         __syncthreads();
         for (int l = 0; l < a.n_layers; ++l) {
             const int d = a.dil[l];
+            const long L = (long)K1 * d;
             float* q = u_queues + a.q_off[l];
-            const int slot = (int)(gstep % d);                  // oldest column == the one replaced now
-            for (int i = tid; i < a.R; i += DEC_THREADS) old[i] = q[(size_t)slot * a.R + i];
+            const int slot = L ? (int)(gstep % L) : 0;          // oldest column == the one replaced now
+            // tap j at slot (g + j d) mod L, staged at old[(k-2-j) R]
+            for (int jj = 0; jj < K1; ++jj) {
+                const float* qj = q + (size_t)((gstep + (long)(K1 - 1 - jj) * d) % L) * a.R;
+                for (int i = tid; i < a.R; i += DEC_THREADS) old[jj * a.R + i] = qj[i];
+            }
             __syncthreads();
             const float* wl = a.w_layers + (size_t)l * a.layer_stride;
             const float* bl = a.b_layers ? a.b_layers + (size_t)l * (2 * a.D + a.R + a.S) : nullptr;
-            // [f;g] = Wfg [cur; old]: the decode pack orders k as [tap-1 weights (cur) | tap-0 weights (old)]
-            // because cur and old are adjacent in LDS in that order
-            dec_matvec(wl, 2 * a.R, cur, 2 * a.D, 2 * a.R, bl, [&](int o, float v) { fg[o] = v; });
+            // [f;g] = Wfg [cur; old]: the decode pack orders k as [tap k-1 weights (cur) | tap k-2 | .. | tap 0]
+            // because cur and the staged columns are adjacent in LDS in that order
+            dec_matvec(wl, fw * a.R, cur, 2 * a.D, fw * a.R, bl, [&](int o, float v) { fg[o] = v; });
             __syncthreads();
             for (int i = tid; i < a.D; i += DEC_THREADS) z[i] = tanhf(fg[i]) * (1.0f / (1.0f + expf(-fg[a.D + i])));
             __syncthreads();
-            const float* wd = wl + (size_t)2 * a.D * 2 * a.R;
+            const float* wd = wl + (size_t)2 * a.D * fw * a.R;
             const float* wsk = wd + (size_t)a.R * a.D;
             dec_matvec(wd, a.D, z, a.R, a.D, bl ? bl + 2 * a.D : nullptr, [&](int o, float v) { nxt[o] = v + cur[o]; });
             dec_matvec(wsk, a.D, z, a.S, a.D, bl ? bl + 2 * a.D + a.R : nullptr, [&](int o, float v) { skip[o] += v; });
             __syncthreads();
             for (int i = tid; i < a.R; i += DEC_THREADS) {
-                q[(size_t)slot * a.R + i] = a.push_input ? cur[i] : nxt[i];     // Q5: output by default
+                if (L) q[(size_t)slot * a.R + i] = a.push_input ? cur[i] : nxt[i];     // Q5: output by default (k = 2 only)
                 cur[i] = nxt[i];
             }
             __syncthreads();
@@ -167,22 +196,26 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_k(WnDecodeArgs a) {
         __syncthreads();
         dec_matvec(a.w_p2, a.S, h1, a.Q, a.S, a.b_p2, [&](int o, float v) { logit[o] = v; });
         __syncthreads();
-        // softmax over the Q (=256) logits and first-index argmax of the PROBABILITIES, wave 0
+        // softmax over the Q logits and first-index argmax of the PROBABILITIES, wave 0
         if (tid < 64) {
             const float ur = a.sample ? dec_uniform(a.seed, (unsigned long long)(a.step0 + step), utt) : 0.f;
-            const int bi = dec_choose(logit, tid, u_probs_out ? u_probs_out + (size_t)step * a.Q : nullptr, a.inv_temp, a.sample != 0, ur);
+            const int bi = (FW == 2 && a.Q == 256) ? dec_choose<4>(logit, 256, tid, u_probs_out ? u_probs_out + (size_t)step * a.Q : nullptr, a.inv_temp, a.sample != 0, ur)
+                                                   : dec_choose_any(logit, a.Q, tid, u_probs_out ? u_probs_out + (size_t)step * a.Q : nullptr, a.inv_temp, a.sample != 0, ur);
             if (tid == 0) { s_arg = bi; u_codes_out[step] = bi; }
         }
         __syncthreads();
-        // next input column: the forced code if given (teacher forcing), else the prediction
+        // next input column: the forced code if given (teacher forcing), else the prediction; the causal queue moves up
         const int nextc = u_forced ? u_forced[step] : s_arg;
-        for (int i = tid; i < a.Q; i += DEC_THREADS) { prev[i] = note[i]; }
-        __syncthreads();
+        for (int j = 0; j < K1; ++j) {
+            for (int i = tid; i < a.Q; i += DEC_THREADS) { prev[j * a.Q + i] = prev[(j + 1) * a.Q + i]; }     // (j = k-2: note)
+            __syncthreads();
+        }
         for (int i = tid; i < a.Q; i += DEC_THREADS) note[i] = (i == nextc) ? 1.0f : 0.0f;
         __syncthreads();
     }
-    // hand the two input columns back (prev = causal queue, note = next input)
-    for (int i = tid; i < a.Q; i += DEC_THREADS) { u_prev_out[i] = prev[i]; u_note_out[i] = note[i]; }
+    // hand the input columns back (prev = causal queue, note = next input)
+    for (int i = tid; i < a.Q; i += DEC_THREADS) u_note_out[i] = note[i];
+    for (int i = tid; i < K1 * a.Q; i += DEC_THREADS) u_prev_out[i] = prev[i];
 }
 
 // Workgroup barrier that only drains LDS traffic.  __syncthreads() also waits for every outstanding
@@ -325,9 +358,17 @@ __device__ __forceinline__ bool dec_poll2(const unsigned long long* p, unsigned 
 // REGISTERS for the whole launch (2 x 128) - so the tail behind the last block has no weight traffic at all.  The S-vectors
 // (skip sum, post_process_1 output) are exchanged between the parts as tagged granules like z (all-gather: every part
 // publishes its 64 rows and polls the others'), the logits go to part 0, which chooses the codes.
-template <bool BIAS, int T0, int S = 256, int KS = 1>
+//
+// KT = filter width (2, 3 or 4; KT > 2 needs T0 and the corrected recurrence): every history tap j = 0 .. KT-2 depends only on the
+// queues, so the sample-ahead pass sums W_tap_j x(t + 1 - (KT-1-j) d) of all of them into the same per-block partial sums (one pass
+// per tap through the same staging area: the LDS budget does not grow with KT), and the chain's critical path keeps the current tap
+// only.  The fg fragments are [2 x 64][64 KT] in natural k order (tap 0 first); the causal layer's KT-1 history columns are codes
+// (one-hot: a gather) or, until the first KT steps have passed, the dense columns of prev0 / note0 read from global memory.
+template <bool BIAS, int T0, int S = 256, int KS = 1, int KT = 2>
 __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
     constexpr int NU = 8, R = 64, D = 64, Q = 256, MS = S / 64;
+    static_assert(KT == 2 || ((KT == 3 || KT == 4) && T0 > 0), "history taps are summed a sample ahead");
+    constexpr int KF = 2 * KT, KO = 2 * (KT - 2);         // k-steps of an fg row tile; first k-step of the current tap
     static_assert(KS == 1 || KS == S / 64, "one row tile per wave in the split form");
     // LDS strides between utterances (halfs): the eight utterances of a 16-lane group read 16-byte pieces at the same offset of
     // their own vectors - with the natural strides (256 B, 1 KB) all of them in the same banks.  +16 B per utterance spreads the
@@ -343,6 +384,7 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
     const int u = c >> 1, h = c & 1;                       // this lane's utterance of the eight and its half (hi / lo columns)
     extern __shared__ __attribute__((aligned(16))) float sm[];
     __shared__ int s_code[NU], s_pc[NU], s_nc[NU];
+    __shared__ int s_src[NU][KT];                          // KT > 2: causal input columns, oldest first: code, or -1 - (dense column)
     __shared__ int slots[WN_DEC_MAX_LAYERS];
     // hand-off area of an utterance (8-byte granules): z [n_layers][D] | skip vector [S] | post_process_1 output [S] | logits [Q] |
     // (first utterance of a pair, T0 = 2: tap-0 table [n_layers][256] x 16 bytes) | code | error flag
@@ -368,9 +410,12 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
         uint16_t* oldh = zh + NU * VS;                   // [n_layers][NU][hi R | lo R] queue columns of this sample (T0: of DEC_T0_CHUNK blocks)
         // T0: [n_layers][256] tap-0 partial sums (f0, f1, g0, g1): in LDS (T0 = 1) or in the pair's hand-off area (T0 = 2)
         f32x4* part = T0 == 2 ? reinterpret_cast<f32x4*>(lg_of(0) + Q) : reinterpret_cast<f32x4*>(oldh + (size_t)DEC_T0_CHUNK * NU * VS);
-        for (int i = tid; i < NU * Q; i += 256) { const int uu = i / Q, e = i - uu * Q; note[i] = a.note0[ux(uu) * Q + e]; prev[i] = a.prev0[ux(uu) * Q + e]; }
+        if (KT == 2) for (int i = tid; i < NU * Q; i += 256) { const int uu = i / Q, e = i - uu * Q; note[i] = a.note0[ux(uu) * Q + e]; prev[i] = a.prev0[ux(uu) * Q + e]; }
+        // KT > 2: dense column c of utterance uu's start state (c < KT-1: prev0, oldest first; KT-1: note0)
+        auto dense_col = [&](int uu, int c) { return c < KT - 1 ? a.prev0 + (ux(uu) * (KT - 1) + c) * (size_t)Q : a.note0 + ux(uu) * (size_t)Q; };
+        if (KT > 2 && tid < NU) for (int c = 0; c < KT; ++c) s_src[tid][c] = -1 - c;
         if (BIAS && a.b_layers && !T0) for (int i = tid; i < a.n_layers * BL; i += 256) { const int l = i / BL, e = i - l * BL; bias[i] = a.b_layers[(size_t)l * (BL + S) + e]; }
-        if (tid < a.n_layers) slots[tid] = (int)(a.step0 % a.dil[tid]);
+        if (tid < a.n_layers) slots[tid] = (int)(a.step0 % ((KT - 1) * a.dil[tid]));
         if (tid < NU) { s_pc[tid] = -1; s_nc[tid] = -1; }
         dec_sync();
         const uint16_t* fgb = a.pk + a.pk_fg0;
@@ -403,13 +448,19 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
         };
         // T0: queue columns of DEC_T0_CHUNK blocks at a time -> halfs in LDS -> this wave's 16 rows of W_tap0 x for f and g of each
         // block -> part[l][tid].  (Same two-column products and pair sums as the block itself runs for its tap-1 half.)
-        auto tap0_ahead = [&]() {
+        // slot of history tap `tap` of block l (tap 0: slots[l], the oldest column); the ring holds (KT-1) d columns
+        auto tap_slot = [&](int l, int tap) {
+            int sl = slots[l];
+            if (KT > 2 && tap) { const int L = (KT - 1) * a.dil[l]; sl += tap * a.dil[l]; if (sl >= L) sl -= L; }
+            return sl;
+        };
+        auto tap0_ahead = [&](const int tap) {
             const uint16_t* fgw = a.pk + a.pk_fg0;
             Frag<F16> tf[2][2], tg[2][2];                   // [set][k-step 0, 1] of block l (set l & 1), re-armed one block ahead
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                load_a<F16, 3>(tf[0][ks], fgw, w * 4 + ks, lane);
-                load_a<F16, 3>(tg[0][ks], fgw, (4 + w) * 4 + ks, lane);
+                load_a<F16, 3>(tf[0][ks], fgw, w * KF + 2 * tap + ks, lane);
+                load_a<F16, 3>(tg[0][ks], fgw, (4 + w) * KF + 2 * tap + ks, lane);
             }
             // the f / g biases of this thread's two rows, fetched one block ahead like the weights (a load issued where it is used
             // would put an L2 round trip per block into this window)
@@ -432,7 +483,7 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
                     l = l < a.n_layers ? l : a.n_layers - 1;
                     const int uu = (e >> 4) & (NU - 1), r4 = e & 15;
                     qv[j] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(
-                        a.queues + ux(uu) * (size_t)a.queues_ustride + a.q_off[l] + (size_t)slots[l] * R + 4 * r4));
+                        a.queues + ux(uu) * (size_t)a.queues_ustride + a.q_off[l] + (size_t)tap_slot(l, tap) * R + 4 * r4));
                 }
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
@@ -452,8 +503,8 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
                         Frag<F16> (&ng)[2] = tg[(lc + 1) & 1];
 #pragma unroll
                         for (int ks = 0; ks < 2; ++ks) {
-                            load_a<F16, 3>(nf[ks], fgn, w * 4 + ks, lane);
-                            load_a<F16, 3>(ng[ks], fgn, (4 + w) * 4 + ks, lane);
+                            load_a<F16, 3>(nf[ks], fgn, w * KF + 2 * tap + ks, lane);
+                            load_a<F16, 3>(ng[ks], fgn, (4 + w) * KF + 2 * tap + ks, lane);
                         }
                         const f32x4 bnext = bias4(ln);
                         const uint16_t* ob = oldh + ((size_t)lc * NU + u) * VS + h * R;
@@ -467,7 +518,8 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
                         for (int ks = 0; ks < 2; ++ks) { pf[ks] = F16::mfma(cf[ks].lo, bx[ks], pf[ks]); pg[ks] = F16::mfma(cg[ks].lo, bx[ks], pg[ks]); }
                         const f32x4 af = dec_pairsum(pf[0] + pf[1]), ag = dec_pairsum(pg[0] + pg[1]);
                         f32x4 pv = {h ? af[2] : af[0], h ? af[3] : af[1], h ? ag[2] : ag[0], h ? ag[3] : ag[1]};
-                        pv += bcur;                          // the block's f / g biases ride along
+                        if (tap == 0) pv += bcur;            // the block's f / g biases ride along (with tap 0)
+                        else pv += part[(size_t)l * 256 + tid];   // (KT > 2: the sums of the earlier history taps)
                         bcur = bnext;
                         part[(size_t)l * 256 + tid] = pv;
                     }
@@ -479,7 +531,10 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
                 dec_sync();
             }
         };
-        if (T0) tap0_ahead();
+        auto history_ahead = [&]() {
+            for (int tap = 0; tap < KT - 1; ++tap) tap0_ahead(tap);
+        };
+        if (T0) history_ahead();
         else load_queues();
         float bdn0 = 0.f, bdn1 = 0.f;                        // T0: the next block's dense bias (two rows of this thread)
         f32x4 t0n = {0.f, 0.f, 0.f, 0.f};                    // T0 = 2: the next block's partial sums, fetched a block ahead (L2 round trip)
@@ -491,10 +546,10 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
             const size_t lb1 = a.n_layers > 1 ? (size_t)a.pk_lstride : 0;
 #pragma unroll
             for (int s2 = T0 ? 2 : 0; s2 < 4; ++s2) {             // T0: the tap-0 k-steps (0, 1) were multiplied a sample ahead
-                load_a<F16, 3>(wfA[s2], fgb, w * 4 + s2, lane);
-                load_a<F16, 3>(wgA[s2], fgb, (4 + w) * 4 + s2, lane);
-                load_a<F16, 3>(wfB[s2], fgb + lb1, w * 4 + s2, lane);
-                load_a<F16, 3>(wgB[s2], fgb + lb1, (4 + w) * 4 + s2, lane);
+                load_a<F16, 3>(wfA[s2], fgb, w * KF + KO + s2, lane);
+                load_a<F16, 3>(wgA[s2], fgb, (4 + w) * KF + KO + s2, lane);
+                load_a<F16, 3>(wfB[s2], fgb + lb1, w * KF + KO + s2, lane);
+                load_a<F16, 3>(wgB[s2], fgb + lb1, (4 + w) * KF + KO + s2, lane);
             }
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
@@ -503,18 +558,33 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
             }
             {   // causal layer, 2 rows of one utterance per thread: x0 = Wc[:, tap0] prev + Wc[:, tap1] note (one-hot: a gather)
                 const int uu = tid >> 5, o0 = (tid & 31) * 2;
-                const int pc = s_pc[uu], nc = s_nc[uu];
                 float sv[2];
+                if constexpr (KT == 2) {
+                    const int pc = s_pc[uu], nc = s_nc[uu];
+    #pragma unroll
+                    for (int e = 0; e < 2; ++e) {
+                        const float* wrow = a.w_causal + (size_t)(o0 + e) * 2 * Q;
+                        float t = 0.f;
+                        if (pc >= 0) t += wrow[pc];
+                        else for (int kk = 0; kk < Q; ++kk) t = fmaf(wrow[kk], prev[uu * Q + kk], t);
+                        if (nc >= 0) t += wrow[Q + nc];
+                        else for (int kk = 0; kk < Q; ++kk) t = fmaf(wrow[Q + kk], note[uu * Q + kk], t);
+                        if (BIAS && a.b_causal) t += a.b_causal[o0 + e];
+                        sv[e] = t;
+                    }
+} else {
 #pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    const float* wrow = a.w_causal + (size_t)(o0 + e) * 2 * Q;
-                    float t = 0.f;
-                    if (pc >= 0) t += wrow[pc];
-                    else for (int kk = 0; kk < Q; ++kk) t = fmaf(wrow[kk], prev[uu * Q + kk], t);
-                    if (nc >= 0) t += wrow[Q + nc];
-                    else for (int kk = 0; kk < Q; ++kk) t = fmaf(wrow[Q + kk], note[uu * Q + kk], t);
-                    if (BIAS && a.b_causal) t += a.b_causal[o0 + e];
-                    sv[e] = t;
+                    for (int e = 0; e < 2; ++e) {
+                        const float* wrow = a.w_causal + (size_t)(o0 + e) * KT * Q;
+                        float t = 0.f;
+                        for (int c = 0; c < KT; ++c) {
+                            const int src = s_src[uu][c];
+                            if (src >= 0) t += wrow[c * Q + src];
+                            else { const float* col = dense_col(uu, -1 - src); for (int kk = 0; kk < Q; ++kk) t = fmaf(wrow[c * Q + kk], col[kk], t); }
+                        }
+                        if (BIAS && a.b_causal) t += a.b_causal[o0 + e];
+                        sv[e] = t;
+                    }
                 }
                 xc0[uu * R + o0] = sv[0]; xc0[uu * R + o0 + 1] = sv[1];
                 dec_put2(xh0 + uu * VS, R, o0, sv[0], sv[1]);
@@ -543,8 +613,8 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
                 for (int ks = T0 ? 2 : 0; ks < 4; ++ks) { pf[ks] = F16::mfma(wf[ks].lo, bx[ks], pf[ks]); pg[ks] = F16::mfma(wg[ks].lo, bx[ks], pg[ks]); }
 #pragma unroll
                 for (int ks = T0 ? 2 : 0; ks < 4; ++ks) {
-                    load_a<F16, 3>(wf[ks], fgn, w * 4 + ks, lane);
-                    load_a<F16, 3>(wg[ks], fgn, (4 + w) * 4 + ks, lane);
+                    load_a<F16, 3>(wf[ks], fgn, w * KF + KO + ks, lane);
+                    load_a<F16, 3>(wg[ks], fgn, (4 + w) * KF + KO + ks, lane);
                 }
                 float f0, f1, g0, g1;
                 if (T0) {
@@ -608,9 +678,9 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
                 if (l + 1 < a.n_layers) blk(l + 1, wfB, wgB, wdB);
             }
             __syncthreads();                       // all queue stores of this sample are complete (dilation 1 reads them back next)
-            if (tid < a.n_layers) { int sl = slots[tid] + 1; slots[tid] = sl == a.dil[tid] ? 0 : sl; }
+            if (tid < a.n_layers) { int sl = slots[tid] + 1; slots[tid] = sl == (KT - 1) * a.dil[tid] ? 0 : sl; }
             dec_sync();
-            if (step + 1 < a.n_steps) { if (T0) tap0_ahead(); else load_queues(); }
+            if (step + 1 < a.n_steps) { if (T0) history_ahead(); else load_queues(); }
             if (tid < NU) {
                 float cv = 0.f;
                 dec_poll(cg_of(tid), tag, cv, cg_of(tid) + 1);
@@ -619,11 +689,21 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
             dec_sync();
             for (int i = tid; i < NU * Q; i += 256) prev[i] = note[i];
             if (tid < NU) { s_pc[tid] = s_nc[tid]; s_nc[tid] = s_code[tid]; }
+            if (KT > 2 && tid < NU) { for (int c = 0; c + 1 < KT; ++c) s_src[tid][c] = s_src[tid][c + 1]; s_src[tid][KT - 1] = s_code[tid]; }
             dec_sync();
             for (int i = tid; i < NU * Q; i += 256) note[i] = ((i & (Q - 1)) == s_code[i / Q]) ? 1.0f : 0.0f;
             dec_sync();
         }
-        for (int i = tid; i < NU * Q; i += 256) { const int uu = i / Q, e = i - uu * Q; a.prev_out[ux(uu) * Q + e] = prev[i]; a.note_out[ux(uu) * Q + e] = note[i]; }
+        if (KT == 2) {
+            for (int i = tid; i < NU * Q; i += 256) { const int uu = i / Q, e = i - uu * Q; a.prev_out[ux(uu) * Q + e] = prev[i]; a.note_out[ux(uu) * Q + e] = note[i]; }
+        } else {
+            for (int i = tid; i < NU * KT * Q; i += 256) {
+                const int uu = i / (KT * Q), c = (i - uu * KT * Q) / Q, e = i - uu * KT * Q - c * Q, src = s_src[uu][c];
+                const float v = src >= 0 ? (e == src ? 1.0f : 0.0f) : dense_col(uu, -1 - src)[e];
+                float* dst = c < KT - 1 ? a.prev_out + (ux(uu) * (KT - 1) + c) * (size_t)Q : a.note_out + ux(uu) * (size_t)Q;
+                dst[e] = v;
+            }
+        }
     } else if (KS > 1) {
         // ------------------------------------------------------------------ skip sum + post-processing, part j of KS: one row tile per wave
         constexpr int KP = S / 32;                           // k-steps of a product over an S-vector
@@ -765,7 +845,7 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
                     const size_t ug = ux(uu);
                     const float ur = a.sample ? dec_uniform(a.seed, (unsigned long long)(a.step0 + step), ug) : 0.f;
                     float* pdst = a.probs_out ? a.probs_out + (ug * (size_t)a.n_steps + step) * Q : nullptr;
-                    const int bi = dec_choose(logit + uu * Q, lane, pdst, a.inv_temp, a.sample != 0, ur);
+                    const int bi = dec_choose<4>(logit + uu * Q, Q, lane, pdst, a.inv_temp, a.sample != 0, ur);
                     if (lane == 0) {
                         a.codes_out[ug * a.n_steps + step] = bi;
                         __hip_atomic_store(cg_of(uu), dec_pack((float)bi, tag), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -893,7 +973,7 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
                 const size_t ug = ux(uu);
                 const float ur = a.sample ? dec_uniform(a.seed, (unsigned long long)(a.step0 + step), ug) : 0.f;
                 float* pdst = a.probs_out ? a.probs_out + (ug * (size_t)a.n_steps + step) * Q : nullptr;
-                const int bi = dec_choose(logit + uu * Q, lane, pdst, a.inv_temp, a.sample != 0, ur);
+                const int bi = dec_choose<4>(logit + uu * Q, Q, lane, pdst, a.inv_temp, a.sample != 0, ur);
                 if (lane == 0) {
                     a.codes_out[ug * a.n_steps + step] = bi;
                     __hip_atomic_store(cg_of(uu), dec_pack((float)bi, tag), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -915,6 +995,12 @@ long wn_decode_granules(int n_layers, int D, int S) {
     return (long)n_layers * D + 2 * (long)S + 256 + (dec_t0_fits_lds(n_layers) ? 0 : (long)n_layers * 512) + 2;
 }
 
+// LDS bytes of decode_k: [k-1][Q] history + [Q] note, cur [R] + [k-1][R] queue columns, fg [2D], z [D], nxt [R], skip and
+// post_process_1 [S] each, logits [Q] (k = 2: 3Q + 3R + 3D + 2S + 64 floats, as before)
+size_t dec_k_lds_bytes(const WnDecodeArgs& a) {
+    return sizeof(float) * (size_t)((a.fw + 1) * (size_t)a.Q + (a.fw + 1) * (size_t)a.R + 3 * (size_t)a.D + 2 * (size_t)a.S + 64);
+}
+
 int wn_launch_decode(const WnDecodeArgs& a, hipStream_t st) {
     if (a.n_steps <= 0) return 0;
     if (a.n_layers > WN_DEC_MAX_LAYERS) return wn_set_error_msg(-4, "decode: too many layers");
@@ -925,7 +1011,14 @@ int wn_launch_decode(const WnDecodeArgs& a, hipStream_t st) {
     // 1024 utterances per launch.  Everything else (other channel counts, fewer than 4 steps) runs on decode_k: one
     // workgroup per utterance, fp32 FMA.
     const bool any_bias = a.b_layers || a.b_causal || a.b_p1 || a.b_p2;
-    const bool mf = a.pk && a.pk_skip >= 0 && a.sync && a.n_steps >= 4 && !(a.dbg & 31) && (a.S == 256 || a.S == 512);
+    static int t0_env = -1, ks_env = -2;
+    if (t0_env < 0) { const char* e = getenv("WN_DEC_T0"); t0_env = e ? atoi(e) : 1; }
+    if (ks_env < -1) { const char* e = getenv("WN_DEC_KS"); ks_env = e ? atoi(e) : -1; }
+    // filter widths 3 and 4 need the history taps summed a sample ahead (tap-0 table in LDS or in the hand-off area); other
+    // widths, and these with WN_DEC_T0=0, run decode_k
+    const bool t0_room = dec_t0_fits_lds(a.n_layers) || a.sync_ustride >= wn_decode_granules(a.n_layers, a.D, a.S);
+    const bool mf_taps = a.fw == 2 || ((a.fw == 3 || a.fw == 4) && t0_env != 0 && t0_room);
+    const bool mf = mf_taps && a.pk && a.pk_skip >= 0 && a.sync && a.n_steps >= 4 && !(a.dbg & 31) && (a.S == 256 || a.S == 512);
     if (nu > (mf ? 1024 : 128)) return wn_set_error_msg(-4, "decode: at most 128 utterances per launch (1024 on the matrix-core path)");
     if (mf) {
         const size_t nsync = (size_t)a.sync_ustride * sizeof(unsigned long long) * (size_t)nu;
@@ -938,9 +1031,6 @@ int wn_launch_decode(const WnDecodeArgs& a, hipStream_t st) {
         const size_t s80_t0 = dec_t0_lds_bytes(a.n_layers);
         const size_t ws_h = 2 * ((size_t)a.S + 64) + 8;               // halfs of one utterance's split S-vector (the kernel's WS)
         const size_t s81 = sizeof(uint16_t) * (size_t)(2 * 8 * 136 + 2 * 8 * ws_h) + sizeof(float) * (size_t)(8 * a.Q + 2 * a.S + a.Q);
-        static int t0_env = -1, ks_env = -2;
-        if (t0_env < 0) { const char* e = getenv("WN_DEC_T0"); t0_env = e ? atoi(e) : 1; }
-        if (ks_env < -1) { const char* e = getenv("WN_DEC_KS"); ks_env = e ? atoi(e) : -1; }
         // tap-0 table: in LDS when it fits (<= 31 blocks), else in the pair's hand-off area (wn_decode_sync_granules leaves room)
         const long need_tab = wn_decode_granules(a.n_layers, a.D, a.S);
         const int t0 = !t0_env ? 0 : (dec_t0_fits_lds(a.n_layers) ? 1 : (a.sync_ustride >= need_tab ? 2 : 0));
@@ -958,16 +1048,19 @@ int wn_launch_decode(const WnDecodeArgs& a, hipStream_t st) {
         const size_t s_chain = t0 == 1 ? s80_t0 : (t0 == 2 ? s80_t2 : s80);
         const size_t sh = s_chain > s81 ? s_chain : s81;
         if (sh + 1024 > 160 * 1024) return wn_set_error_msg(-4, "decode: this many blocks do not fit the matrix-core kernel's LDS");
-        if (getenv("WN_DEC_VERBOSE")) fprintf(stderr, "[wn_decode] matrix-core, 8 utterances per pair: %d utterances, %d steps, %d skip channels, biases %d, tap-0 ahead %d, skip parts %d\n", nu, a.n_steps, a.S, any_bias ? 1 : 0, t0, ks);
+        if (getenv("WN_DEC_VERBOSE")) fprintf(stderr, "[wn_decode] matrix-core, 8 utterances per pair: filter width %d, %d utterances, %d steps, %d skip channels, biases %d, tap-0 ahead %d, skip parts %d\n", a.fw, nu, a.n_steps, a.S, any_bias ? 1 : 0, t0, ks);
         int dev = 0;
         (void)hipGetDevice(&dev);
         const int mx = 160 * 1024 - 1024;           // (the kernel also has ~350 bytes of static LDS)
         const dim3 gr((1 + ks) * pairs), bl(DEC_MT);
-#define DEC_GO3(BB, TT, SS, KK) do { \
+#define DEC_GO3(BB, TT, SS, KK, KT) do { \
         static WnDevOnce done_; \
-        if (done_.need(dev)) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&decode_duo_mfma8_k<BB, TT, SS, KK>), hipFuncAttributeMaxDynamicSharedMemorySize, mx); done_.done(dev); } \
-        hipLaunchKernelGGL((decode_duo_mfma8_k<BB, TT, SS, KK>), gr, bl, sh, st, a); } while (0)
-#define DEC_GO2(BB, SS, KK) do { if (t0 == 2) DEC_GO3(BB, 2, SS, KK); else if (t0 == 1) DEC_GO3(BB, 1, SS, KK); else DEC_GO3(BB, 0, SS, KK); } while (0)
+        if (done_.need(dev)) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&decode_duo_mfma8_k<BB, TT, SS, KK, KT>), hipFuncAttributeMaxDynamicSharedMemorySize, mx); done_.done(dev); } \
+        hipLaunchKernelGGL((decode_duo_mfma8_k<BB, TT, SS, KK, KT>), gr, bl, sh, st, a); } while (0)
+#define DEC_GO2(BB, SS, KK) do { \
+        if (a.fw == 3) { if (t0 == 2) DEC_GO3(BB, 2, SS, KK, 3); else DEC_GO3(BB, 1, SS, KK, 3); } \
+        else if (a.fw == 4) { if (t0 == 2) DEC_GO3(BB, 2, SS, KK, 4); else DEC_GO3(BB, 1, SS, KK, 4); } \
+        else if (t0 == 2) DEC_GO3(BB, 2, SS, KK, 2); else if (t0 == 1) DEC_GO3(BB, 1, SS, KK, 2); else DEC_GO3(BB, 0, SS, KK, 2); } while (0)
 #define DEC_GO(SS, KK) do { if (any_bias) DEC_GO2(true, SS, KK); else DEC_GO2(false, SS, KK); } while (0)
         if (a.S == 512 && ks > 1) DEC_GO(512, 8);
         else if (a.S == 512) DEC_GO(512, 1);
@@ -978,8 +1071,18 @@ int wn_launch_decode(const WnDecodeArgs& a, hipStream_t st) {
 #undef DEC_GO3
     } else {
         if (getenv("WN_DEC_VERBOSE")) fprintf(stderr, "[wn_decode] generic fp32 kernel: %d utterances, %d steps\n", nu, a.n_steps);
-        size_t sh = sizeof(float) * (size_t)(3 * a.Q + 3 * a.R + 3 * a.D + 2 * a.S + 64);
-        hipLaunchKernelGGL(decode_k, dim3(nu), dim3(DEC_THREADS), sh, st, a);
+        const size_t sh = dec_k_lds_bytes(a);
+        if (sh + 1024 > 160 * 1024) return wn_set_error_msg(-4, "decode: the fp32 kernel's LDS layout does not fit (too many channels for this filter width)");
+        if (sh > 64 * 1024) {                       // (above the default dynamic-LDS limit: raise it once per device)
+            static WnDevOnce done_k2, done_k0;
+            int dev = 0;
+            (void)hipGetDevice(&dev);
+            WnDevOnce& once = a.fw == 2 ? done_k2 : done_k0;
+            const void* fn = a.fw == 2 ? reinterpret_cast<const void*>(&decode_k<2>) : reinterpret_cast<const void*>(&decode_k<0>);
+            if (once.need(dev)) { (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024); once.done(dev); }
+        }
+        if (a.fw == 2) hipLaunchKernelGGL(decode_k<2>, dim3(nu), dim3(DEC_THREADS), sh, st, a);
+        else hipLaunchKernelGGL(decode_k<0>, dim3(nu), dim3(DEC_THREADS), sh, st, a);
     }
     WN_CHECK_LAUNCH();
     return 0;

@@ -269,8 +269,14 @@ struct WnDecodeArgs {
     // ("fg<l>" natural k order, "d<l>" chained k order), offsets in halfs: fragment base of block l = pk + pk_*0 + l * pk_lstride
     const uint16_t* pk; long pk_fg0, pk_d0, pk_lstride;
     long pk_skip, pk_p1, pk_p2;          // "skip" ([S/16][n_layers*D/32]), "p1" ([S/16][S/32]), "p2" ([Q/16][S/32]) fragment bases, natural k order (S = Q = 256)
+    // filter width k >= 1 (2 for every entry point before wn_decode_batch_fw): prev0 / prev_out hold k - 1 columns [k-1][Q] per
+    // utterance (oldest first), block ring i holds (k-1) d_i columns; fp32 weights w_causal [R][kQ] (k = tap 0 q | .. | tap k-1 q),
+    // Wfg [2D][kR] (k = tap k-1 r | tap k-2 r | .. | tap 0 r)
+    int fw;
 };
 int wn_launch_decode(const WnDecodeArgs& a, hipStream_t st);
+size_t dec_k_lds_bytes(const WnDecodeArgs& a);            // dynamic LDS of the fp32 decode kernel (decode_k)
+#define WN_DEC_MAX_Q 1024                                  // quantisation channels the fp32 decode kernel's sampler covers
 long wn_decode_granules(int n_layers, int D, int S);      // 8-byte granules of one utterance's hand-off area (matrix-core kernels)
 
 // wn_coll.hip

@@ -11,6 +11,10 @@ As WRITTEN in the reference each block pushes its OUTPUT into its own queue inst
 (fast_generate.py:128-129), so fast generation differs from naive generation; that
 recurrence is reproduced by default.  ``correct_queue=True`` selects the fast-wavenet recurrence.
 
+Any filter width k >= 1: block i keeps the last (k-1) d_i columns of its input ('block_i' -> (1, R, (k-1) d_i)) and the
+causal layer the last k-1 input columns ('causal_layer' -> (1, Q, k-1)).  The as-written push is undefined for k != 2 (its
+``[state | note]`` input is too short for k >= 3): there only ``correct_queue=True`` exists, ``False`` raises ValueError.
+
 ``generate()`` (fast_generate.py:144-179) runs the whole greedy loop as ONE persistent kernel launch
 (``wn_decode``) instead of one Python iteration per sample, and writes the wav with scipy (librosa,
 which the reference uses for that, is not a dependency here).  Unlike the reference module this one
@@ -48,9 +52,17 @@ def _mfma_decode(eng):
     a switch flipped inside a process must not make them disagree)."""
     v = getattr(eng, "_dec_mfma", None)
     if v is None:
-        v = eng._dec_mfma = bool(os.environ.get("WN_DEC_MFMA", "1") == "1" and getattr(eng, "k", 2) == 2 and eng.R <= 64 and
-                                 eng.D <= 64 and eng.S in (256, 512) and eng.Q == 256 and eng.mode_fwd == _lib.F16X3 and
-                                 "fg0" in getattr(eng, "pk_f_off", {}))
+        k = getattr(eng, "k", 2)
+        if k == 2:
+            v = bool(os.environ.get("WN_DEC_MFMA", "1") == "1" and eng.R <= 64 and
+                     eng.D <= 64 and eng.S in (256, 512) and eng.Q == 256 and eng.mode_fwd == _lib.F16X3 and
+                     "fg0" in getattr(eng, "pk_f_off", {}))
+        else:
+            # filter widths 3 / 4 (general-plan engines; _DecodePack builds the [2 x 64][64 k] fg packs itself): the history
+            # taps are summed a sample ahead, so the tap-0-ahead form is required (WN_DEC_T0=0: the fp32 kernel)
+            v = bool(os.environ.get("WN_DEC_MFMA", "1") == "1" and os.environ.get("WN_DEC_T0", "1") != "0" and k in (3, 4) and
+                     eng.R <= 64 and eng.D <= 64 and eng.S in (256, 512) and eng.Q == 256 and eng.mode_fwd == _lib.F16X3)
+        eng._dec_mfma = v
     return v
 
 
@@ -66,11 +78,7 @@ class _DecodePack:
 
     def __init__(self, eng):
         sp, R, D, S, Q, N = eng.spec, eng.R, eng.D, eng.S, eng.Q, eng.N
-        if getattr(eng, "k", 2) != 2:
-            # the reference's own cached-queue decoder keeps d_i columns per block and convolves [queue | note] once
-            # (wavenet/fast_generate.py:73-90): it only exists for filter_width 2
-            raise NotImplementedError("fast_generate implements the reference's cached-queue recurrence, which is defined for "
-                                      "filter_width == 2 only (wavenet/fast_generate.py:73-90)")
+        k = self.k = getattr(eng, "k", 2)
         self.mfma = _mfma_decode(eng)
         Rp = Dp = self.Rp = self.Dp = 64 if self.mfma else None
         if not self.mfma:
@@ -86,22 +94,22 @@ class _DecodePack:
             out[:len(v)] = v
             return out
         parts, mats = [], {}
-        wc = sp.conv("causal_layer.weight")                                 # [R,Q,2]
+        wc = sp.conv("causal_layer.weight")                                 # [R,Q,k]
         self.o_causal = 0
-        parts.append(pad(np.concatenate([wc[:, :, 0], wc[:, :, 1]], 1), Rp, 2 * Q).reshape(-1))
-        self.layer_stride = 2 * Dp * 2 * Rp + Rp * Dp + S * Dp
+        parts.append(pad(np.concatenate([wc[:, :, j] for j in range(k)], 1), Rp, k * Q).reshape(-1))     # k = [tap0 | .. | tap k-1]
+        self.layer_stride = 2 * Dp * k * Rp + Rp * Dp + S * Dp
         self.o_layers = sum(len(p) for p in parts)
         for i in range(N):
-            wf = sp.conv("dilation_layer_stack.%d.weight" % (4 * i))        # [D,R,2]
+            wf = sp.conv("dilation_layer_stack.%d.weight" % (4 * i))        # [D,R,k]
             wg = sp.conv("dilation_layer_stack.%d.weight" % (4 * i + 1))
             wd = sp.conv("dilation_layer_stack.%d.weight" % (4 * i + 2))[:, :, 0]
             ws = sp.conv("dilation_layer_stack.%d.weight" % (4 * i + 3))[:, :, 0]
-            blk = lambda a, b: np.concatenate([pad(a, Dp, Rp), pad(b, Dp, Rp)], 1)
-            fg = np.concatenate([blk(wf[:, :, 1], wf[:, :, 0]),                      # k = [tap1 (cur) | tap0 (old)]
-                                 blk(wg[:, :, 1], wg[:, :, 0])], 0)
+            blk = lambda w, taps: np.concatenate([pad(w[:, :, j], Dp, Rp) for j in taps], 1)
+            fg = np.concatenate([blk(wf, range(k - 1, -1, -1)),                        # k = [tap k-1 (cur) | tap k-2 | .. | tap0 (oldest)]
+                                 blk(wg, range(k - 1, -1, -1))], 0)
             parts += [fg.reshape(-1), pad(wd, Rp, Dp).reshape(-1), pad(ws, S, Dp).reshape(-1)]
-            # the packed forms: [f; g] rows, K = [tap0 | tap1] in natural order; dense in chained order (as wn_resblock_fwd)
-            mats["fg%d" % i] = (np.concatenate([blk(wf[:, :, 0], wf[:, :, 1]), blk(wg[:, :, 0], wg[:, :, 1])], 0), False)
+            # the packed forms: [f; g] rows, K = [tap0 | tap1 | ..] in natural order; dense in chained order (as wn_resblock_fwd)
+            mats["fg%d" % i] = (np.concatenate([blk(wf, range(k)), blk(wg, range(k))], 0), False)
             mats["d%d" % i] = (pad(wd, Rp, Dp), True)
             mats.setdefault("skip_cols", []).append(pad(ws, S, Dp))
         self.o_p1 = sum(len(p) for p in parts)
@@ -160,30 +168,60 @@ class _DecodePack:
         return ptr(self.pk), o["fg0"], o["d0"], self.pk_stride, o["skip"], o["p1"], o["p2"]
 
 
+def _taps(eng):
+    """k - 1: the previous input columns every layer keeps (filter_width - 1)."""
+    return getattr(eng, "k", 2) - 1
+
+
+def _check_recurrence(eng, correct_queue):
+    if _taps(eng) != 1 and not correct_queue:
+        raise ValueError("the reference's as-written queue push (wavenet/fast_generate.py:128-129) is defined for filter_width "
+                         "== 2 only; pass correct_queue=True for filter_width %d" % (_taps(eng) + 1))
+
+
+def _ptr_or_none(t):
+    """Device pointer, or None for an empty tensor (filter_width 1: no previous input columns)."""
+    return ptr(t) if t is not None and t.numel() else None
+
+
+def _queue_buffer(rings):
+    """filter_width 1 keeps no queues, but the entry point wants a queue buffer: one unused float then."""
+    return rings if rings.numel() else torch.zeros(1, dtype=torch.float32, device=rings.device)
+
+
+def _queue_offsets(eng, rw):
+    """Float offset of every block's ring: (k-1) d_i columns of rw floats each."""
+    return np.cumsum([0] + [_taps(eng) * d * rw for d in eng.dil[:-1]]).astype(np.int64)
+
+
 class DecodeState(OrderedDict):
-    """The per-layer FIFO queues of the decoder.  Internally every block's queue is a ring buffer in
-    time-major layout on the device; indexing by the reference's keys materialises the
-    time-ordered ``(1, C, d)`` tensor the reference would hold."""
+    """The per-layer FIFO queues of the decoder.  Internally every block's queue is a ring buffer of (k-1) d_i columns in
+    time-major layout on the device (k = filter_width); indexing by the reference's keys materialises the
+    time-ordered ``(1, C, (k-1) d)`` tensor (``'causal_layer'``: ``(1, Q, k-1)``), oldest column first."""
 
     def __init__(self, eng, rings, prev, steps=0):
         super().__init__()
         self.eng, self.rings, self.prev, self.steps = eng, rings, prev, steps
         self.rw = _ring_width(eng)                # floats per queue column (64 on the matrix-core kernels, zeros beyond eng.R)
-        self.q_off = np.cumsum([0] + [d * self.rw for d in eng.dil[:-1]]).astype(np.int64)
+        self.q_off = _queue_offsets(eng, self.rw)
         for k in ["causal_layer"] + ["block_%d" % (i + 1) for i in range(eng.N)]:
             OrderedDict.__setitem__(self, k, None)
 
     def _ring(self, i):
-        d = self.eng.dil[i]
-        return self.rings[self.q_off[i]:self.q_off[i] + d * self.rw].view(d, self.rw)[:, :self.eng.R]
+        L = _taps(self.eng) * self.eng.dil[i]
+        return self.rings[self.q_off[i]:self.q_off[i] + L * self.rw].view(L, self.rw)[:, :self.eng.R]
 
     def __getitem__(self, key):
+        K1 = _taps(self.eng)
         if key == "causal_layer":
-            return self.prev.view(1, -1, 1).clone()
+            Q = self.eng.Q
+            return self.prev.view(K1, Q).t().contiguous().view(1, Q, K1).clone()
         i = int(key.split("_")[1]) - 1
-        d = self.eng.dil[i]
-        ring = torch.roll(self._ring(i), -(self.steps % d), 0)        # oldest column first
-        return ring.t().contiguous().view(1, self.eng.R, d)
+        L = K1 * self.eng.dil[i]
+        ring = self._ring(i)
+        if L:
+            ring = torch.roll(ring, -(self.steps % L), 0)              # oldest column first
+        return ring.t().contiguous().view(1, self.eng.R, L)
 
     def items(self):
         return [(k, self[k]) for k in self.keys()]
@@ -194,15 +232,16 @@ class DecodeState(OrderedDict):
     @staticmethod
     def from_tensors(eng, queue):
         """Build the ring form from reference-style tensors (time-ordered, oldest first)."""
-        rw = _ring_width(eng)
-        rings = torch.cat([torch.nn.functional.pad(queue["block_%d" % (i + 1)].to(eng.device).float().reshape(eng.R, eng.dil[i]).t(),
+        rw, K1 = _ring_width(eng), _taps(eng)
+        rings = torch.cat([torch.nn.functional.pad(queue["block_%d" % (i + 1)].to(eng.device).float().reshape(eng.R, K1 * eng.dil[i]).t(),
                                                    (0, rw - eng.R)).reshape(-1) for i in range(eng.N)])
-        prev = queue["causal_layer"].to(eng.device).float().reshape(-1).clone()
+        prev = queue["causal_layer"].to(eng.device).float().reshape(eng.Q, K1).t().contiguous().reshape(-1)
         return DecodeState(eng, rings.contiguous(), prev, 0)
 
 
 def _decode(net, state, note0, n_steps, forced=None, want_probs=False, correct_queue=False, temperature=None, seed=0):
     eng = state.eng
+    _check_recurrence(eng, correct_queue)
     pack = getattr(net, "_decode_pack", None)
     if pack is None or pack.eng is not eng:
         pack = net._decode_pack = _DecodePack(eng)
@@ -214,7 +253,7 @@ def _decode(net, state, note0, n_steps, forced=None, want_probs=False, correct_q
     codes = torch.empty(n_steps, dtype=torch.int32, device=dev)
     probs = torch.empty(n_steps, eng.Q, dtype=torch.float32, device=dev) if want_probs else None
     note_out = torch.empty(eng.Q, dtype=torch.float32, device=dev)
-    prev_out = torch.empty(eng.Q, dtype=torch.float32, device=dev)
+    prev_out = torch.empty(pack.k - 1, eng.Q, dtype=torch.float32, device=dev).view(-1)
     dil = (ctypes.c_int32 * eng.N)(*eng.dil)
     qoff = (ctypes.c_int64 * eng.N)(*[int(v) for v in state.q_off])
     forced_t = forced.to(device=dev, dtype=torch.int32).contiguous() if forced is not None else None
@@ -224,11 +263,12 @@ def _decode(net, state, note0, n_steps, forced=None, want_probs=False, correct_q
         sync = net._decode_sync = torch.zeros(n_sync, dtype=torch.int64, device=dev)
     bias = pack.o_bias is not None
     pk = pack.chain()
-    call("wn_decode_batch_pk", eng.N, pack.Rp, pack.Dp, eng.S, eng.Q, ctypes.cast(dil, ctypes.c_void_p), ctypes.cast(qoff, ctypes.c_void_p),
-         ptr(state.rings), pack.p(pack.o_causal), pack.p(pack.ob_causal) if bias else None,
+    qbuf = _queue_buffer(state.rings)
+    call("wn_decode_batch_fw", pack.k, eng.N, pack.Rp, pack.Dp, eng.S, eng.Q, ctypes.cast(dil, ctypes.c_void_p),
+         ctypes.cast(qoff, ctypes.c_void_p), ptr(qbuf), pack.p(pack.o_causal), pack.p(pack.ob_causal) if bias else None,
          pack.p(pack.o_layers), pack.layer_stride, pack.p(pack.ob_layers) if bias else None,
          pack.p(pack.o_p1), pack.p(pack.ob_p1) if bias else None, pack.p(pack.o_p2), pack.p(pack.ob_p2) if bias else None,
-         ptr(note0), ptr(state.prev), ptr(note_out), ptr(prev_out), ptr(forced_t), ptr(codes), ptr(probs),
+         ptr(note0), _ptr_or_none(state.prev), ptr(note_out), _ptr_or_none(prev_out), ptr(forced_t), ptr(codes), ptr(probs),
          state.steps, n_steps, 1 if correct_queue else 0, ptr(sync), 1, 0,
          float(temperature) if temperature else 0.0, int(seed), pk[0], pk[1], pk[2], pk[3], pk[4], pk[5], pk[6], _lib.stream())
     if n_steps >= 4 and int(sync[-1].item()) != 0:
@@ -250,11 +290,12 @@ def predict_next(net, note, state_queue=None, correct_queue=False):
         ws = eng.workspace(1, x.size(2))
         T, pitch, CH, R = x.size(2), ws["pitch"], eng.CH, eng.R
         X = ws["X"][SLACK:SLACK + (eng.N + 1) * CH * pitch].view(eng.N + 1, CH, pitch)
-        # queue of block i = the last d_i columns of that block's INPUT (fast_generate.py:42-47)
-        rw = _ring_width(eng)
-        rings = torch.cat([torch.nn.functional.pad(X[i, :R, T - d:T].t(), (0, rw - R)).reshape(-1)
+        # queue of block i = the last (k-1) d_i columns of that block's INPUT (fast_generate.py:42-47 for k = 2); the causal
+        # layer's = the last k-1 input columns
+        rw, K1 = _ring_width(eng), _taps(eng)
+        rings = torch.cat([torch.nn.functional.pad(X[i, :R, T - K1 * d:T].t(), (0, rw - R)).reshape(-1)
                            for i, d in enumerate(eng.dil)]).contiguous()
-        state = DecodeState(eng, rings, x[0, :, -1].clone(), 0)
+        state = DecodeState(eng, rings, x[0, :, T - K1:T].t().contiguous().view(-1), 0)
         _, predict = torch.topk(probs.view(-1), 1)
         return predict.to(note.device), state
     assert note.size()[2] == 1
@@ -299,13 +340,14 @@ def generate_codes_batch(net, start_pieces, note_num, correct_queue=False, tempe
     ws = eng.workspace(U, x.size(2))
     T, pitch, CH, R, N, Q = x.size(2), ws["pitch"], eng.CH, eng.R, eng.N, eng.Q
     X = ws["X"][SLACK:SLACK + (N + 1) * U * CH * pitch].view(N + 1, U, CH, pitch)
-    # ring of block i of utterance u = the last d_i columns of that block's input, time-major
-    rw = _ring_width(eng)
-    rings = torch.cat([torch.nn.functional.pad(X[i, :, :R, T - d:T].transpose(1, 2), (0, rw - R)).reshape(U, d * rw)
+    # ring of block i of utterance u = the last (k-1) d_i columns of that block's input, time-major
+    rw, K1 = _ring_width(eng), _taps(eng)
+    rings = torch.cat([torch.nn.functional.pad(X[i, :, :R, T - K1 * d:T].transpose(1, 2), (0, rw - R)).reshape(U, K1 * d * rw)
                        for i, d in enumerate(eng.dil)], 1).contiguous()
     first = probs.view(U, Q).argmax(1)
     if note_num <= 1:
         return first.view(U, 1)[:, :note_num]
+    _check_recurrence(eng, correct_queue)
     pack = getattr(net, "_decode_pack", None)
     if pack is None or pack.eng is not eng:
         pack = net._decode_pack = _DecodePack(eng)
@@ -313,21 +355,22 @@ def generate_codes_batch(net, start_pieces, note_num, correct_queue=False, tempe
     n_steps = note_num - 1
     note0 = torch.zeros(U, Q, dtype=torch.float32, device=dev)
     note0[torch.arange(U, device=dev), first] = 1.0
-    prev0 = x[:, :, -1].contiguous()
+    prev0 = x[:, :, T - K1:T].transpose(1, 2).contiguous()         # [U][k-1][Q], oldest column first
     codes = torch.empty(U, n_steps, dtype=torch.int32, device=dev)
     note_out = torch.empty(U, Q, dtype=torch.float32, device=dev)
-    prev_out = torch.empty(U, Q, dtype=torch.float32, device=dev)
+    prev_out = torch.empty(U, K1, Q, dtype=torch.float32, device=dev)
     sync = torch.zeros(U * _lib.decode_sync_granules(N, pack.Dp, eng.S), dtype=torch.int64, device=dev)
     dil = (ctypes.c_int32 * N)(*eng.dil)
-    q_off = np.cumsum([0] + [d * rw for d in eng.dil[:-1]]).astype(np.int64)
+    q_off = _queue_offsets(eng, rw)
     qoff = (ctypes.c_int64 * N)(*[int(v) for v in q_off])
     bias = pack.o_bias is not None
     pk = pack.chain()
-    call("wn_decode_batch_pk", N, pack.Rp, pack.Dp, eng.S, Q, ctypes.cast(dil, ctypes.c_void_p), ctypes.cast(qoff, ctypes.c_void_p),
-         ptr(rings), pack.p(pack.o_causal), pack.p(pack.ob_causal) if bias else None,
+    qbuf = _queue_buffer(rings)
+    call("wn_decode_batch_fw", pack.k, N, pack.Rp, pack.Dp, eng.S, Q, ctypes.cast(dil, ctypes.c_void_p),
+         ctypes.cast(qoff, ctypes.c_void_p), ptr(qbuf), pack.p(pack.o_causal), pack.p(pack.ob_causal) if bias else None,
          pack.p(pack.o_layers), pack.layer_stride, pack.p(pack.ob_layers) if bias else None,
          pack.p(pack.o_p1), pack.p(pack.ob_p1) if bias else None, pack.p(pack.o_p2), pack.p(pack.ob_p2) if bias else None,
-         ptr(note0), ptr(prev0), ptr(note_out), ptr(prev_out), None, ptr(codes), None,
+         ptr(note0), _ptr_or_none(prev0), ptr(note_out), _ptr_or_none(prev_out), None, ptr(codes), None,
          0, n_steps, 1 if correct_queue else 0, ptr(sync), U, rings.size(1),
          float(temperature) if temperature else 0.0, int(seed), pk[0], pk[1], pk[2], pk[3], pk[4], pk[5], pk[6], _lib.stream())
     if n_steps >= 4:
@@ -349,9 +392,11 @@ def generate(model_path, model_name, generate_path, generate_name, start_piece=N
         raise FileNotFoundError(model_path + model_name)
     net = net.cuda()
     if start_piece is None:
-        start_piece = torch.zeros(1, 256, net.receptive_field)
-        start_piece[:, 128, :] = 1.0
-    generated_piece = generate_codes(net, start_piece.cuda(), duration * sr)
+        Q = net.quantization_channels
+        start_piece = torch.zeros(1, Q, net.receptive_field)
+        start_piece[:, Q // 2, :] = 1.0
+    # the as-written queue push exists for filter_width 2 only; every other width runs the corrected recurrence
+    generated_piece = generate_codes(net, start_piece.cuda(), duration * sr, correct_queue=net.filter_width != 2)
     print(generated_piece.tolist()[:32], "...")
     audio = mu_law_decode(generated_piece, net.quantization_channels).cpu().numpy()
     from scipy.io import wavfile
