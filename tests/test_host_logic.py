@@ -216,6 +216,36 @@ def test_generic_engine_index_maps_cover_every_parameter_once():
     assert g[wf[2, 7, 2]] == go2 + 2 * cols2 + 7
 
 
+def test_generic_autoencoder_index_maps_cover_every_parameter_once():
+    """music_amd/ae_generic.py, built on the CPU with biases and filter width 3: the same three coverage properties as the
+    WaveNet plan above - every weight exactly once in the forward packs, exactly once in the backward packs, and the
+    gradient gather map a bijection from the parameters (weights and biases) into the gradient matrices."""
+    import numpy as np
+    import torch
+    from music_amd.ae_generic import GenericAutoencoderEngine
+    from music_amd.model1 import wavenet_autoencoder
+    net = wavenet_autoencoder(filter_width=3, quantization_channel=48, dilations=[1, 2, 4], en_residual_channel=20,
+                              en_dilation_channel=24, en_bottleneck_width=6, en_pool_kernel_size=10, de_residual_channel=40,
+                              de_dilation_channel=28, de_skip_channel=36, use_bias=True)
+    eng = GenericAutoencoderEngine(net, torch.device("cpu"))
+    assert eng.rf == 2 * (7 + 1) + 1 and eng.off == [2, 4, 8, 16] and eng.pairs == [(0, 1), (2, None)]
+    n_w = sum(int(np.prod(eng.spec.shape[n])) for n in eng.param_names if n.endswith(".weight"))
+    assert n_w < eng.spec.total                              # (the biases are parameters too)
+    fidx = eng.pk_f_idx.numpy()
+    seen = fidx[fidx >= 0]
+    assert len(seen) == n_w and len(np.unique(seen)) == n_w
+    bidx = eng.pk_b_idx.numpy()
+    seen_b = bidx[bidx >= 0]
+    assert len(seen_b) == n_w and len(np.unique(seen_b)) == n_w
+    is_w = np.zeros(eng.spec.total, dtype=bool)
+    for n in eng.param_names:
+        if n.endswith(".weight"):
+            is_w[eng.spec.off[n]:eng.spec.off[n] + int(np.prod(eng.spec.shape[n]))] = True
+    assert is_w[seen].all() and is_w[seen_b].all()
+    g = eng.gidx.numpy()
+    assert len(g) == eng.spec.total and len(np.unique(g)) == eng.spec.total and g.min() >= 0 and g.max() < eng.gpack.numel()
+
+
 def test_workspace_pool_semantics_without_a_gpu():
     """WorkspacePool / WorkspaceHold (music_amd/engine.py): get() hands out the first workspace no pending backward holds,
     a held one is never reused or evicted, peek() is what the last forward used, shapes are evicted one at a time (LRU),
