@@ -42,7 +42,7 @@ extern "C" {
 
 typedef void* wn_stream_t;                 /* hipStream_t */
 enum { WN_F16X3 = 0, WN_F16X1 = 1, WN_BF16X3 = 2, WN_BF16X1 = 3 };
-#define WN_ABI_VERSION 6
+#define WN_ABI_VERSION 7
 #define WN_CE_NUM_PARTIALS 1024
 
 int wn_version(void);
@@ -453,6 +453,37 @@ int wn_decode_batch_fw(int filter_width, int n_layers, int R, int D, int S, int 
                        int n_steps, int push_input, uint64_t* sync, int n_utt, int64_t queues_ustride, float temperature,
                        uint64_t seed, const uint16_t* pk, int64_t pk_fg0, int64_t pk_d0, int64_t pk_lstride, int64_t pk_skip,
                        int64_t pk_p1, int64_t pk_p2, wn_stream_t stream);
+
+/* wn_decode_batch_fw with a PER-UTTERANCE, TIME-VARYING conditioning table under every block's [f; g] and under
+ * post_process_1's output (ABI 7): the autoencoder's decoder (wavenet_autoencoder/model1.py:158-247) as a cached-queue
+ * recurrence, so an encoding of any number of pooled frames can be decoded, and the utterances of a launch decode
+ * different encodings.  cond_fg: float [n_utt][n_layers][le][2D] (utterance u at + u*cond_fg_ustride), rows f then g - the
+ * decode layout, the reference's "gate = first half" order is swapped by the caller; cond_p1: float [n_utt][le][S]
+ * (+ u*cond_p1_ustride).  The tables stay in global memory, le is not capped.
+ * The SCHEDULE (host arrays of n_layers + 1 ints, blocks first, post-processing last; shared by the launch) says which
+ * column a stage reads: step s of the launch is output position j = pos0 + s, stage i's column is c = j + c_shift[i]
+ * (c_shift[i] = L_{i+1} - W: length of the stage's output in the forward over the whole clip minus the forward's output
+ * width) and its table column is  c / c_q[i]  when c_q[i] > 0 (the stretch branch of _conditon),  c mod le  when c_q[i] == 0
+ * (the tile branch).  c < 0 reads column 0 (pos0 may be negative: priming steps before the first output position); a
+ * stretch column past the end reads the last one, le - 1; the tile branch is periodic and has no end.
+ * Either table may be NULL (that stage is then unconditioned); with both NULL the call is wn_decode_batch_fw bit for bit.
+ * The fp32 kernel serves every shape it serves unconditioned; the matrix-core kernels serve the tap-0-ahead forms (filter
+ * widths 2, 3, 4; 256 or 512 skip channels, one-workgroup and split skip stage): the f / g term of sample t + 1 is added
+ * to the tap-0 partial sums in the sample-ahead pass, the cond_p1 column is staged per sample by the skip workgroups while
+ * they wait for the chain.  A launch the matrix-core kernels do not serve conditioned (tap-0-ahead switched off) runs the
+ * fp32 kernel; nothing is ever decoded silently unconditioned.
+ * Returns -4 (wn_last_error says why) for le < 1, a NULL schedule array with a non-NULL table, c_q[i] < 0, push_input == 0
+ * (conditioned decode exists for the corrected recurrence only) and everything wn_decode_batch_fw refuses. */
+int wn_decode_batch_cond(int filter_width, int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host,
+                         const int64_t* q_off_host, float* queues, const float* w_causal, const float* b_causal,
+                         const float* w_layers, int64_t layer_stride, const float* b_layers, const float* w_p1, const float* b_p1,
+                         const float* w_p2, const float* b_p2, const float* note0, const float* prev0, float* note_out,
+                         float* prev_out, const int32_t* forced, int32_t* codes_out, float* probs_out, int64_t step0,
+                         int n_steps, int push_input, uint64_t* sync, int n_utt, int64_t queues_ustride, float temperature,
+                         uint64_t seed, const uint16_t* pk, int64_t pk_fg0, int64_t pk_d0, int64_t pk_lstride, int64_t pk_skip,
+                         int64_t pk_p1, int64_t pk_p2, const float* cond_fg, int64_t cond_fg_ustride, const float* cond_p1,
+                         int64_t cond_p1_ustride, const int32_t* c_shift_host, const int32_t* c_q_host, int le, int64_t pos0,
+                         wn_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -16,7 +16,12 @@ different algorithm from the reference's, not a faster form of it: the reference
 and re-draws its 31 random projections for every generated sample (generate.py:13-19, model1.py:178-217).
 With a time-constant encoding (one pooled frame: the reference's window of receptive_field + 512 samples and
 pool 512 give exactly one) the conditioning is a constant per-channel bias, so the conditioned decoder IS a
-plain WaveNet with effective biases, and the existing decode kernel runs it unchanged."""
+plain WaveNet with effective biases, and the existing decode kernel runs it unchanged.
+
+``resynthesize`` is the same idea for an encoding of ANY number of pooled frames (encode a clip, regenerate audio from the
+encoding): the projections of the encoding become per-clip TABLES with one column per frame, and the conditioned decode
+kernel (``wn_decode_batch_cond``) adds, at every step, the column the reference's ``_conditon`` (model1.py:227-247) would
+have added at that position of the forward over the whole clip - ``cond_schedule`` says which."""
 import json
 import os
 
@@ -40,29 +45,25 @@ def predict_next(net, input_wav, quantization_channel=256):
     return int(torch.topk(out[-1, :].view(-1), 1)[1])
 
 
-def cached_decoder(net, encoding, cond):
-    """The autoencoder's conditioned decoder (model1.py:158-225) for ONE pooled frame of encoding
-    ``(1, bottleneck, 1)`` and fixed conditioning projections ``cond`` (N+1 (weight (C, bottleneck, 1), bias (C,))
-    pairs, gate rows first, the last one for the post-processing stage) as a ``music_amd.model.wavenet``:
-    filter / gate = second / first half of ``filter_gate`` (model1.py:188-190), conditioning folded into the
-    biases.  Its forward and its cached-queue decoder (``fast_generate``) then reproduce the decoder exactly."""
+def _decoder_wavenet(net, proj=None):
+    """The autoencoder's decoder as a ``music_amd.model.wavenet`` on the device: filter / gate = second / first half of
+    ``filter_gate`` (model1.py:188-190), the autoencoder's own biases (zeros without ``use_bias``) plus, if given, the N + 1
+    constant conditioning vectors ``proj`` (reference row order, gate rows first)."""
     try:
         from .model import wavenet
     except ImportError:
         from music_amd.model import wavenet
-    if encoding.dim() != 3 or encoding.size(0) != 1 or encoding.size(2) != 1:
-        raise ValueError("cached_decoder needs a single pooled frame of encoding, got %s" % (tuple(encoding.shape),))
     N, Dd = len(net.dilations), net.de_dilation_channel
     sd = {k: v.detach().float().cpu() for k, v in net.state_dict().items()}
-    enc = encoding.detach().float().cpu()[0, :, 0]
-    proj = [w.detach().float().cpu()[:, :, 0] @ enc + b.detach().float().cpu() for w, b in cond]
     zeros = lambda n: torch.zeros(n)
     bias = lambda name, n: sd[name + ".bias"] if net.use_bias else zeros(n)
     out = {"causal_layer.weight": sd["de_causal_layer.weight"],
            "causal_layer.bias": bias("de_causal_layer", net.de_residual_channel)}
     for i in range(N):
         fg, dn, sk = ("de_dilation_layer_stack.%d" % (3 * i + k) for k in range(3))
-        w, b = sd[fg + ".weight"], bias(fg, 2 * Dd) + proj[i]
+        w, b = sd[fg + ".weight"], bias(fg, 2 * Dd)
+        if proj is not None:
+            b = b + proj[i]
         out["dilation_layer_stack.%d.weight" % (4 * i)], out["dilation_layer_stack.%d.bias" % (4 * i)] = w[Dd:], b[Dd:]
         out["dilation_layer_stack.%d.weight" % (4 * i + 1)], out["dilation_layer_stack.%d.bias" % (4 * i + 1)] = w[:Dd], b[:Dd]
         out["dilation_layer_stack.%d.weight" % (4 * i + 2)] = sd[dn + ".weight"]
@@ -70,7 +71,7 @@ def cached_decoder(net, encoding, cond):
         out["dilation_layer_stack.%d.weight" % (4 * i + 3)] = sd[sk + ".weight"]
         out["dilation_layer_stack.%d.bias" % (4 * i + 3)] = bias(sk, net.de_skip_channel)
     out["post_process_1.weight"] = sd["connection_1.weight"]
-    out["post_process_1.bias"] = bias("connection_1", net.de_skip_channel) + proj[N]
+    out["post_process_1.bias"] = bias("connection_1", net.de_skip_channel) + (proj[N] if proj is not None else 0)
     out["post_process_2.weight"] = sd["connection_2.weight"]
     out["post_process_2.bias"] = bias("connection_2", net.quantization_channel)
     wnet = wavenet(filter_width=net.filter_width, dilations=list(net.dilations), dilation_channels=Dd,
@@ -78,6 +79,122 @@ def cached_decoder(net, encoding, cond):
                    quantization_channels=net.quantization_channel, use_bias=True)
     wnet.load_state_dict({k: v.contiguous() for k, v in out.items()})
     return wnet.cuda()
+
+
+def cached_decoder(net, encoding, cond):
+    """The autoencoder's conditioned decoder (model1.py:158-225) for ONE pooled frame of encoding
+    ``(1, bottleneck, 1)`` and fixed conditioning projections ``cond`` (N+1 (weight (C, bottleneck, 1), bias (C,))
+    pairs, gate rows first, the last one for the post-processing stage) as a ``music_amd.model.wavenet``:
+    filter / gate = second / first half of ``filter_gate`` (model1.py:188-190), conditioning folded into the
+    biases.  Its forward and its cached-queue decoder (``fast_generate``) then reproduce the decoder exactly."""
+    if encoding.dim() != 3 or encoding.size(0) != 1 or encoding.size(2) != 1:
+        raise ValueError("cached_decoder needs a single pooled frame of encoding, got %s" % (tuple(encoding.shape),))
+    enc = encoding.detach().float().cpu()[0, :, 0]
+    proj = [w.detach().float().cpu()[:, :, 0] @ enc + b.detach().float().cpu() for w, b in cond]
+    return _decoder_wavenet(net, proj)
+
+
+def cond_schedule(net_or_geometry, W, Le):
+    """The conditioning schedule of a forward with ``W`` output rows and ``Le`` pooled frames: per stage i = 0..N (the N
+    decoder blocks, then the post-processing stage) the triple ``(shift_i, q_i, Le)``.  Block i's output in that forward has
+    L_{i+1} columns (L_N = W; the post-processing stage W) and ``_conditon`` (model1.py:227-247) adds frame
+    ``c // (L_{i+1} / Le)`` at its column c when Le divides L_{i+1} (stretch: q_i = L_{i+1} / Le > 0), frame ``c % Le``
+    otherwise (tile: q_i = 0).  Output position j is column j + shift_i, shift_i = L_{i+1} - W.  The schedule depends on W as
+    the reference's forward does.  ``net_or_geometry``: anything with ``filter_width`` and ``dilations``, or that pair.
+    Pure host arithmetic."""
+    if isinstance(net_or_geometry, (tuple, list)):
+        k, dil = net_or_geometry
+    else:
+        k, dil = net_or_geometry.filter_width, net_or_geometry.dilations
+    k, dil, W, Le = int(k), [int(d) for d in dil], int(W), int(Le)
+    if k < 1 or W < 1 or Le < 1:
+        raise ValueError("cond_schedule: filter_width, W and Le must be >= 1")
+    out = []
+    for i in range(len(dil) + 1):
+        L = W + (k - 1) * sum(dil[i + 1:]) if i < len(dil) else W         # L_{i+1}: what the blocks behind block i still consume
+        out.append((L - W, L // Le if L % Le == 0 else 0, Le))
+    return out
+
+
+def conditioned_decoder(net, cond):
+    """The autoencoder's decoder as a ``music_amd.model.wavenet`` with the autoencoder's OWN biases only (no conditioning
+    folded in), and the N + 1 conditioning projections ``cond`` as device matrices in the decode layout:
+    ``[(weight (C, bottleneck), bias (C,))]`` with the blocks' rows ordered filter first, gate second (the reference draws
+    them gate first, model1.py:188-190), the last pair for the post-processing stage.  A table column is
+    ``weight @ encoding[:, frame] + bias``."""
+    Dd = net.de_dilation_channel
+    wnet = _decoder_wavenet(net)
+    dev = next(wnet.parameters()).device
+    N = len(net.dilations)
+    proj = []
+    for i, (w, b) in enumerate(cond):
+        w, b = w.detach().float()[:, :, 0], b.detach().float()
+        if i < N:
+            w, b = torch.cat([w[Dd:], w[:Dd]]), torch.cat([b[Dd:], b[:Dd]])
+        proj.append((w.contiguous().to(dev), b.contiguous().to(dev)))
+    return wnet, proj
+
+
+def resynthesize(net, clips, cond=None, teacher_forced=False, want_probs=False, temperature=None, seed=0):
+    """Encode ``clips`` (B, Q, T) one-hot, T >= receptive_field with at least one pooled frame, and regenerate them from the
+    encoding with the cached-queue decoder: the encoder runs ONCE, the conditioning projections are drawn ONCE (or taken
+    from ``cond``), the per-clip tables (one column per pooled frame and stage) are built on the device, the queues are
+    primed by teacher-forced decode steps over the first receptive_field - 1 samples from zero queues (output positions
+    -(rf - 1) .. -1: their conditioning columns clamp to frame 0 and nothing of them reaches a valid position), and the
+    W = T - rf + 1 output positions are decoded in one persistent launch, every clip with its own tables.
+    ``teacher_forced``: the clip's own codes are fed (the probabilities are then the forward's, row for row); otherwise the
+    model's own codes are fed back after the clip's first receptive_field samples.  ``temperature``: sample instead of
+    argmax, reproducibly for ``seed``.  Returns (codes int64 (B, W), probabilities (B, W, Q) or None, encodings (B, Bw, Le))."""
+    try:
+        from . import fast_generate as fg
+    except ImportError:
+        from music_amd import fast_generate as fg
+    if clips.dim() != 3 or clips.size(1) != net.quantization_channel:
+        raise ValueError("resynthesize: clips must be (B, %d, T)" % net.quantization_channel)
+    x = clips.detach().cuda().float().contiguous()
+    B, Q, T = x.shape
+    rf = net.receptive_field
+    W = T - rf + 1
+    if W < 1:
+        raise ValueError("wave sample not long enough")
+    if cond is None:
+        cond = net._draw_conditioning()
+    eng = net._engine_for(x.device)
+    with torch.no_grad():
+        _, enc, _ = eng.forward(x, cond, want_probs=False)            # (raises when the clip pools to no frame)
+    enc = net.last_encoding = enc.clone()
+    Le = enc.size(2)
+    wnet, proj = conditioned_decoder(net, cond)
+    deng = wnet._engine_for(x.device)
+    if not hasattr(wnet, "_decode_pack") or wnet._decode_pack.eng is not deng:
+        wnet._decode_pack = fg._DecodePack(deng)
+    pack = wnet._decode_pack
+    N, Dd, Dp, S, K1 = len(net.dilations), net.de_dilation_channel, pack.Dp, net.de_skip_channel, net.filter_width - 1
+    # tables: column e of stage i = proj_i(enc[:, e]); blocks [B][N][Le][f Dp | g Dp] (zero rows beyond Dd), post-processing [B][Le][S]
+    cw = torch.stack([p[0] for p in proj[:N]])                        # (N, 2 Dd, Bw), rows [f | g]
+    cb = torch.stack([p[1] for p in proj[:N]])
+    en = torch.einsum("nck,bkl->bnlc", cw, enc) + cb[None, :, None, :]
+    cond_fg = torch.zeros(B, N, Le, 2 * Dp, dtype=torch.float32, device=x.device)
+    cond_fg[..., :Dd] = en[..., :Dd]
+    cond_fg[..., Dp:Dp + Dd] = en[..., Dd:]
+    cond_p1 = (torch.einsum("ck,bkl->blc", proj[N][0], enc) + proj[N][1]).contiguous()
+    sched = cond_schedule(net, W, Le)
+    rw = fg._ring_width(deng)
+    rings = torch.zeros(B, max(1, sum(K1 * d * rw for d in deng.dil)), dtype=torch.float32, device=x.device)
+    codes_in = x.argmax(1).to(torch.int32)                            # (B, T)
+    note = x[:, :, 0].contiguous()
+    prev = torch.zeros(B, K1, Q, dtype=torch.float32, device=x.device)
+    tabs = dict(cond_fg=cond_fg, cond_p1=cond_p1, schedule=sched)
+    if rf > 1:
+        # priming: step s takes the clip's sample s and is forced to continue with sample s + 1
+        _, _, note, prev = fg.decode_batch_cond(wnet, rings, prev, note, rf - 1, step0=0, pos0=-(rf - 1),
+                                                forced=codes_in[:, 1:rf], **tabs)
+    forced = None
+    if teacher_forced:
+        forced = torch.cat([codes_in[:, rf:], torch.zeros(B, 1, dtype=torch.int32, device=x.device)], 1)
+    codes, probs, _, _ = fg.decode_batch_cond(wnet, rings, prev, note, W, step0=rf - 1, pos0=0, forced=forced,
+                                              want_probs=want_probs, temperature=temperature, seed=seed, **tabs)
+    return codes.to(torch.int64), probs, enc
 
 
 def generate_cached(net, start_piece, note_num, cond=None, temperature=None, seed=0):

@@ -450,7 +450,10 @@ static int decode_impl(int n_layers, int R, int D, int S, int Q, const int32_t* 
                        float* prev_out, const int32_t* forced, int32_t* codes_out, float* probs_out, int64_t step0,
                        int n_steps, int push_input, uint64_t* sync, int64_t sync_ustride, int n_utt, int64_t queues_ustride,
                        float temperature, uint64_t seed, const uint16_t* pk, int64_t pk_fg0, int64_t pk_d0, int64_t pk_lstride,
-                       int64_t pk_skip, int64_t pk_p1, int64_t pk_p2, int fw, wn_stream_t stream);
+                       int64_t pk_skip, int64_t pk_p1, int64_t pk_p2, int fw, wn_stream_t stream,
+                       const float* cond_fg = nullptr, int64_t cond_fg_ustride = 0, const float* cond_p1 = nullptr,
+                       int64_t cond_p1_ustride = 0, const int32_t* c_shift = nullptr, const int32_t* c_q = nullptr, int le = 1,
+                       int64_t pos0 = 0);
 extern "C" {
 int64_t wn_decode_sync_granules(int n_layers, int D, int S);
 int wn_decode_batch(int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host, const int64_t* q_off_host,
@@ -534,6 +537,41 @@ int wn_decode_batch_fw(int filter_width, int n_layers, int R, int D, int S, int 
                        temperature, seed, pk, pk_fg0, pk_d0, pk_lstride, pk_skip, pk_p1, pk_p2, filter_width, stream);
 }
 
+int wn_decode_batch_cond(int filter_width, int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host,
+                         const int64_t* q_off_host, float* queues, const float* w_causal, const float* b_causal,
+                         const float* w_layers, int64_t layer_stride, const float* b_layers, const float* w_p1, const float* b_p1,
+                         const float* w_p2, const float* b_p2, const float* note0, const float* prev0, float* note_out,
+                         float* prev_out, const int32_t* forced, int32_t* codes_out, float* probs_out, int64_t step0,
+                         int n_steps, int push_input, uint64_t* sync, int n_utt, int64_t queues_ustride, float temperature,
+                         uint64_t seed, const uint16_t* pk, int64_t pk_fg0, int64_t pk_d0, int64_t pk_lstride, int64_t pk_skip,
+                         int64_t pk_p1, int64_t pk_p2, const float* cond_fg, int64_t cond_fg_ustride, const float* cond_p1,
+                         int64_t cond_p1_ustride, const int32_t* c_shift_host, const int32_t* c_q_host, int le, int64_t pos0,
+                         wn_stream_t stream) {
+    if (filter_width < 1) return wn_set_error_msg(-4, "wn_decode_batch_cond: filter_width must be >= 1");
+    if (!push_input)
+        return wn_set_error_msg(-4, "wn_decode_batch_cond: conditioned decode exists for the corrected recurrence only; pass "
+                                    "push_input = 1");
+    if (le < 1) return wn_set_error_msg(-4, "wn_decode_batch_cond: le (columns of a conditioning table) must be >= 1");
+    if (Q < 1 || Q > WN_DEC_MAX_Q) return wn_set_error_msg(-4, "wn_decode_batch_cond: 1 <= Q <= 1024 quantisation channels");
+    if (n_layers > WN_DEC_MAX_LAYERS || n_layers <= 0) return wn_set_error_msg(-4, "wn_decode_batch_cond: 1..64 layers supported");
+    if (cond_fg || cond_p1) {
+        if (!c_shift_host || !c_q_host)
+            return wn_set_error_msg(-4, "wn_decode_batch_cond: a conditioning table needs the schedule arrays 'c_shift_host' and "
+                                        "'c_q_host' (n_layers + 1 entries each)");
+        for (int i = 0; i <= n_layers; ++i)
+            if (c_q_host[i] < 0) return wn_set_error_msg(-4, "wn_decode_batch_cond: c_q[i] must be >= 0 (stretch factor, or 0 = tile)");
+    }
+    if (n_utt > 0 && n_steps > 0) {
+        WN_REQUIRE("wn_decode_batch_cond", note0, note_out, codes_out);
+        if (filter_width > 1) WN_REQUIRE("wn_decode_batch_cond", prev0, prev_out);
+    }
+    return decode_impl(n_layers, R, D, S, Q, dilations_host, q_off_host, queues, w_causal, b_causal, w_layers, layer_stride,
+                       b_layers, w_p1, b_p1, w_p2, b_p2, note0, prev0, note_out, prev_out, forced, codes_out, probs_out,
+                       step0, n_steps, push_input, sync, wn_decode_sync_granules(n_layers, D, S), n_utt, queues_ustride,
+                       temperature, seed, pk, pk_fg0, pk_d0, pk_lstride, pk_skip, pk_p1, pk_p2, filter_width, stream,
+                       cond_fg, cond_fg_ustride, cond_p1, cond_p1_ustride, c_shift_host, c_q_host, le, pos0);
+}
+
 }  // extern "C"
 
 static int decode_impl(int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host, const int64_t* q_off_host,
@@ -543,7 +581,9 @@ static int decode_impl(int n_layers, int R, int D, int S, int Q, const int32_t* 
                        float* prev_out, const int32_t* forced, int32_t* codes_out, float* probs_out, int64_t step0,
                        int n_steps, int push_input, uint64_t* sync, int64_t sync_ustride, int n_utt, int64_t queues_ustride,
                        float temperature, uint64_t seed, const uint16_t* pk, int64_t pk_fg0, int64_t pk_d0, int64_t pk_lstride,
-                       int64_t pk_skip, int64_t pk_p1, int64_t pk_p2, int fw, wn_stream_t stream) {
+                       int64_t pk_skip, int64_t pk_p1, int64_t pk_p2, int fw, wn_stream_t stream,
+                       const float* cond_fg, int64_t cond_fg_ustride, const float* cond_p1, int64_t cond_p1_ustride,
+                       const int32_t* c_shift, const int32_t* c_q, int le, int64_t pos0) {
     if (n_utt <= 0) return 0;
     if (n_layers > WN_DEC_MAX_LAYERS || n_layers <= 0) return wn_set_error_msg(-4, "wn_decode: 1..64 layers supported");
     WN_REQUIRE("wn_decode", dilations_host, q_off_host);              // (host arrays, read right here)
@@ -562,6 +602,10 @@ static int decode_impl(int n_layers, int R, int D, int S, int Q, const int32_t* 
     a.n_utt = n_utt; a.queues_ustride = queues_ustride;
     a.sample = temperature > 0.0f ? 1 : 0; a.inv_temp = temperature > 0.0f ? 1.0f / temperature : 1.0f; a.seed = seed;
     a.pk_skip = -1;
+    a.cond_fg = cond_fg; a.cond_fg_ustride = cond_fg_ustride; a.cond_p1 = cond_p1; a.cond_p1_ustride = cond_p1_ustride;
+    a.le = le; a.pos0 = pos0;
+    if (cond_fg || cond_p1)
+        for (int i = 0; i <= n_layers; ++i) { a.c_shift[i] = c_shift[i]; a.c_q[i] = c_q[i]; }
     // the matrix-core kernel needs all of pk (chain, skip, post-processing: 64 / 64 / 256 / 256 channels); biases are fine
     const bool any_bias = b_layers || b_causal || b_p1 || b_p2;
     const bool post_pk = (S == 256 || S == 512) && Q == 256 && pk_skip >= 0 && pk_p1 >= 0 && pk_p2 >= 0;

@@ -134,6 +134,9 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_k(WnDecodeArgs a) {
     const int32_t* const u_forced = a.forced ? a.forced + utt * a.n_steps : nullptr;
     int32_t* const u_codes_out = a.codes_out + utt * a.n_steps;
     float* const u_probs_out = a.probs_out ? a.probs_out + utt * (size_t)a.n_steps * a.Q : nullptr;
+    // conditioned decode: this utterance's tables (null: that stage is unconditioned)
+    const float* const u_cfg = a.cond_fg ? a.cond_fg + utt * a.cond_fg_ustride : nullptr;
+    const float* const u_cp1 = a.cond_p1 ? a.cond_p1 + utt * a.cond_p1_ustride : nullptr;
     extern __shared__ float sm[];
     float* prev = sm;                       // [k-1][Q] previous input columns, oldest first (the causal layer's queue)
     float* note = prev + K1 * a.Q;          // [Q] current input column (dense); [prev|note] is contiguous
@@ -154,6 +157,7 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_k(WnDecodeArgs a) {
 
     for (int step = 0; step < a.n_steps; ++step) {
         const long gstep = a.step0 + step;                      // global step index: ring positions
+        const int pos = (int)(a.pos0 + step);                   // output position: conditioning columns
         // ---- causal layer: cur = sum_j Wc[:, jQ:(j+1)Q] col_j over [prev_0 .. prev_{k-2} | note]
         dec_matvec(a.w_causal, fw * a.Q, prev /* note follows prev in LDS */, a.R, fw * a.Q, a.b_causal,
                    [&](int o, float v) { cur[o] = v; });
@@ -174,7 +178,9 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_k(WnDecodeArgs a) {
             const float* bl = a.b_layers ? a.b_layers + (size_t)l * (2 * a.D + a.R + a.S) : nullptr;
             // [f;g] = Wfg [cur; old]: the decode pack orders k as [tap k-1 weights (cur) | tap k-2 | .. | tap 0]
             // because cur and the staged columns are adjacent in LDS in that order
-            dec_matvec(wl, fw * a.R, cur, 2 * a.D, fw * a.R, bl, [&](int o, float v) { fg[o] = v; });
+            // conditioning: column idx_l(pos + shift_l) of this block's table under [f; g]
+            const float* cfg = u_cfg ? u_cfg + ((size_t)l * a.le + wn_dec_cond_idx(pos + a.c_shift[l], a.c_q[l], a.le)) * 2 * a.D : nullptr;
+            dec_matvec(wl, fw * a.R, cur, 2 * a.D, fw * a.R, bl, [&](int o, float v) { fg[o] = cfg ? v + cfg[o] : v; });
             __syncthreads();
             for (int i = tid; i < a.D; i += DEC_THREADS) z[i] = tanhf(fg[i]) * (1.0f / (1.0f + expf(-fg[a.D + i])));
             __syncthreads();
@@ -192,7 +198,8 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_k(WnDecodeArgs a) {
         // ---- post-processing: relu -> P1 -> relu -> P2 -> softmax -> argmax
         for (int i = tid; i < a.S; i += DEC_THREADS) skip[i] = fmaxf(skip[i], 0.f);
         __syncthreads();
-        dec_matvec(a.w_p1, a.S, skip, a.S, a.S, a.b_p1, [&](int o, float v) { h1[o] = fmaxf(v, 0.f); });
+        const float* cp1 = u_cp1 ? u_cp1 + (size_t)wn_dec_cond_idx(pos + a.c_shift[a.n_layers], a.c_q[a.n_layers], a.le) * a.S : nullptr;
+        dec_matvec(a.w_p1, a.S, skip, a.S, a.S, a.b_p1, [&](int o, float v) { h1[o] = fmaxf(cp1 ? v + cp1[o] : v, 0.f); });
         __syncthreads();
         dec_matvec(a.w_p2, a.S, h1, a.Q, a.S, a.b_p2, [&](int o, float v) { logit[o] = v; });
         __syncthreads();
@@ -386,6 +393,7 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
     __shared__ int s_code[NU], s_pc[NU], s_nc[NU];
     __shared__ int s_src[NU][KT];                          // KT > 2: causal input columns, oldest first: code, or -1 - (dense column)
     __shared__ int slots[WN_DEC_MAX_LAYERS];
+    __shared__ int s_cidx[WN_DEC_MAX_LAYERS];              // conditioned decode: every block's table column for the sample AHEAD
     // hand-off area of an utterance (8-byte granules): z [n_layers][D] | skip vector [S] | post_process_1 output [S] | logits [Q] |
     // (first utterance of a pair, T0 = 2: tap-0 table [n_layers][256] x 16 bytes) | code | error flag
     auto zg_of = [&](int uu) { return a.sync + ux(uu) * (size_t)a.sync_ustride; };
@@ -416,11 +424,14 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
         if (KT > 2 && tid < NU) for (int c = 0; c < KT; ++c) s_src[tid][c] = -1 - c;
         if (BIAS && a.b_layers && !T0) for (int i = tid; i < a.n_layers * BL; i += 256) { const int l = i / BL, e = i - l * BL; bias[i] = a.b_layers[(size_t)l * (BL + S) + e]; }
         if (tid < a.n_layers) slots[tid] = (int)(a.step0 % ((KT - 1) * a.dil[tid]));
+        if (BIAS && a.cond_fg && tid < a.n_layers) s_cidx[tid] = wn_dec_cond_idx((int)a.pos0 + a.c_shift[tid], a.c_q[tid], a.le);
         if (tid < NU) { s_pc[tid] = -1; s_nc[tid] = -1; }
         dec_sync();
         const uint16_t* fgb = a.pk + a.pk_fg0;
         const uint16_t* db = a.pk + a.pk_d0;
         float* const uq = a.queues + ux(u) * (size_t)a.queues_ustride;       // this lane's utterance
+        // conditioned decode (T0 only): this lane's utterance's [n_layers][le][2D] table
+        const float* const ucf = BIAS && a.cond_fg ? a.cond_fg + ux(u) * (size_t)a.cond_fg_ustride : nullptr;
         const int ra = 16 * w + 4 * q + 2 * h;                                       // its two rows: ra, ra + 1
         // the queue columns x(t - d) of ALL blocks for one sample, split into halfs: a batch of 32 loads per thread in flight
         // (hand-off-scope loads go out to memory: ~1 us alone, 2-3 us on a busy chip), then the splits.  Called for sample
@@ -454,7 +465,7 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
             if (KT > 2 && tap) { const int L = (KT - 1) * a.dil[l]; sl += tap * a.dil[l]; if (sl >= L) sl -= L; }
             return sl;
         };
-        auto tap0_ahead = [&](const int tap) {
+        auto tap0_ahead = [&](const int tap) __attribute__((always_inline)) {
             const uint16_t* fgw = a.pk + a.pk_fg0;
             Frag<F16> tf[2][2], tg[2][2];                   // [set][k-step 0, 1] of block l (set l & 1), re-armed one block ahead
 #pragma unroll
@@ -464,11 +475,17 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
             }
             // the f / g biases of this thread's two rows, fetched one block ahead like the weights (a load issued where it is used
             // would put an L2 round trip per block into this window)
-            auto bias4 = [&](int l) {
+            auto bias4 = [&](int l) __attribute__((always_inline)) {
                 f32x4 b = {0.f, 0.f, 0.f, 0.f};
                 if (BIAS && a.b_layers) {
                     const float* bl = a.b_layers + (size_t)l * (BL + S);
                     b = f32x4{bl[ra], bl[ra + 1], bl[D + ra], bl[D + ra + 1]};
+                }
+                // conditioning of the sample ahead: depends on the table and the position only, so it rides in the partial sums
+                // like the biases (fetched here, a block ahead, in the wait window: nothing of it on the chain's critical path)
+                if (ucf) {
+                    const float* ct = ucf + ((size_t)l * a.le + s_cidx[l]) * (2 * D);
+                    b += f32x4{ct[ra], ct[ra + 1], ct[D + ra], ct[D + ra + 1]};
                 }
                 return b;
             };
@@ -531,7 +548,7 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
                 dec_sync();
             }
         };
-        auto history_ahead = [&]() {
+        auto history_ahead = [&]() __attribute__((always_inline)) {
             for (int tap = 0; tap < KT - 1; ++tap) tap0_ahead(tap);
         };
         if (T0) history_ahead();
@@ -679,6 +696,7 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
             }
             __syncthreads();                       // all queue stores of this sample are complete (dilation 1 reads them back next)
             if (tid < a.n_layers) { int sl = slots[tid] + 1; slots[tid] = sl == (KT - 1) * a.dil[tid] ? 0 : sl; }
+            if (BIAS && a.cond_fg && tid < a.n_layers) s_cidx[tid] = wn_dec_cond_idx((int)a.pos0 + step + 1 + a.c_shift[tid], a.c_q[tid], a.le);
             dec_sync();
             if (step + 1 < a.n_steps) { if (T0) history_ahead(); else load_queues(); }
             if (tid < NU) {
@@ -724,6 +742,10 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
         }
         if (BIAS && a.b_p1) for (int r = tid; r < S; r += 256) bsk[S + r] = a.b_p1[r];
         if (BIAS && a.b_p2) bsk[2 * S + tid] = a.b_p2[tid];
+        // conditioned decode: [NU][64] post_process_1 bias + this sample's cond_p1 column, this part's 64 rows of every utterance,
+        // re-staged at the top of every sample (while this workgroup waits for the chain's first z of the sample)
+        float* cp1 = bsk + 2 * S + Q;
+        const float* const ucp = BIAS && a.cond_p1 ? a.cond_p1 + ux(tid >> 5) * (size_t)a.cond_p1_ustride + 64 * jpart + 2 * (tid & 31) : nullptr;
         dec_sync();
         const int KSS = a.n_layers * D / 32;
         const uint16_t* skb = a.pk + a.pk_skip;
@@ -776,6 +798,13 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
             const unsigned tag = (unsigned)step + 1u;
             f32x4 acc2[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
             Frag<F16> ws[2];
+            if (ucp) {
+                const float* cc = ucp + (size_t)wn_dec_cond_idx((int)a.pos0 + step + a.c_shift[a.n_layers], a.c_q[a.n_layers], a.le) * S;
+                const int r = 64 * jpart + 2 * (tid & 31);
+                float c0 = cc[0], c1 = cc[1];
+                if (a.b_p1) { c0 += bsk[S + r]; c1 += bsk[S + r + 1]; }
+                cp1[(tid >> 5) * 64 + 2 * (tid & 31)] = c0; cp1[(tid >> 5) * 64 + 2 * (tid & 31) + 1] = c1;
+            }
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) load_a<F16, 3>(ws[s2], skb, tile * KSS + s2, lane);
             for (int l = 0; l < a.n_layers; ++l) {
@@ -818,7 +847,8 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
                 }
                 const f32x4 t = dec_pairsum(acc[0] + acc[1]);
                 float v0 = h ? t[2] : t[0], v1 = h ? t[3] : t[1];
-                if (BIAS && a.b_p1) { v0 += bsk[S + row]; v1 += bsk[S + row + 1]; }
+                if (BIAS && a.cond_p1) { v0 += cp1[u * 64 + row - 64 * jpart]; v1 += cp1[u * 64 + row - 64 * jpart + 1]; }
+                else if (BIAS && a.b_p1) { v0 += bsk[S + row]; v1 += bsk[S + row + 1]; }
                 dec_send2(hv_of(u) + row, fmaxf(v0, 0.f), fmaxf(v1, 0.f), tag);
             }
             gather_rows(hv_of(tid >> 5), S, h1, nullptr, tag, errp);
@@ -870,6 +900,10 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
         }
         if (BIAS && a.b_p1) for (int r = tid; r < S; r += 256) bsk[S + r] = a.b_p1[r];
         if (BIAS && a.b_p2) bsk[2 * S + tid] = a.b_p2[tid];
+        // conditioned decode: [NU][S] post_process_1 bias + this sample's cond_p1 column of every utterance, re-staged at the top
+        // of every sample (while this workgroup waits for the chain's first z of the sample)
+        float* cp1 = bsk + 2 * S + Q;
+        const float* const ucp = BIAS && a.cond_p1 ? a.cond_p1 + ux(tid >> 5) * (size_t)a.cond_p1_ustride : nullptr;
         dec_sync();
         const int KSS = a.n_layers * D / 32;
         const uint16_t* skb = a.pk + a.pk_skip;
@@ -915,6 +949,21 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
         unsigned long long pa = 0, pb = 0;                                               // prefetched pair (tag 0 = nothing yet)
         for (int step = 0; step < a.n_steps; ++step) {
             const unsigned tag = (unsigned)step + 1u;
+            if (ucp) {
+                const float* cc = ucp + (size_t)wn_dec_cond_idx((int)a.pos0 + step + a.c_shift[a.n_layers], a.c_q[a.n_layers], a.le) * S;
+                // (eight loads in flight at a time: all S / 32 at once push the 512-channel form over its 512 registers)
+#pragma unroll 1
+                for (int k0 = 0; k0 < S / 32; k0 += 8) {
+                    float cv[8];
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) cv[k] = cc[(tid & 31) + 32 * (k0 + k)];
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) {
+                        const int r = (tid & 31) + 32 * (k0 + k);
+                        cp1[(tid >> 5) * S + r] = a.b_p1 ? cv[k] + bsk[S + r] : cv[k];
+                    }
+                }
+            }
             f32x4 acc2[2][MS];
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2)
@@ -963,7 +1012,7 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
                 dec_put2(skip + u * WS, WLO, row, fmaxf(v0, 0.f), fmaxf(v1, 0.f));
             }
             dec_sync();
-            post(S / 256, p1b, skip, h1, nullptr, BIAS && a.b_p1 ? bsk + S : nullptr);
+            post(S / 256, p1b, skip, h1, nullptr, BIAS && a.cond_p1 ? cp1 + u * S : (BIAS && a.b_p1 ? bsk + S : nullptr));
             dec_sync();
             post(Q / 256, p2b, h1, nullptr, logit, BIAS && a.b_p2 ? bsk + 2 * S : nullptr);
             dec_sync();
@@ -1010,7 +1059,9 @@ int wn_launch_decode(const WnDecodeArgs& a, hipStream_t st) {
     // The two workgroups of a pair spin on each other's hand-offs, so every pair must be resident at once: 128 pairs =
     // 1024 utterances per launch.  Everything else (other channel counts, fewer than 4 steps) runs on decode_k: one
     // workgroup per utterance, fp32 FMA.
-    const bool any_bias = a.b_layers || a.b_causal || a.b_p1 || a.b_p2;
+    // (a conditioning table is a bias that moves: the BIAS forms of the matrix-core kernel carry it)
+    const bool cond = a.cond_fg || a.cond_p1;
+    const bool any_bias = a.b_layers || a.b_causal || a.b_p1 || a.b_p2 || cond;
     static int t0_env = -1, ks_env = -2;
     if (t0_env < 0) { const char* e = getenv("WN_DEC_T0"); t0_env = e ? atoi(e) : 1; }
     if (ks_env < -1) { const char* e = getenv("WN_DEC_KS"); ks_env = e ? atoi(e) : -1; }
@@ -1018,7 +1069,10 @@ int wn_launch_decode(const WnDecodeArgs& a, hipStream_t st) {
     // widths, and these with WN_DEC_T0=0, run decode_k
     const bool t0_room = dec_t0_fits_lds(a.n_layers) || a.sync_ustride >= wn_decode_granules(a.n_layers, a.D, a.S);
     const bool mf_taps = a.fw == 2 || ((a.fw == 3 || a.fw == 4) && t0_env != 0 && t0_room);
-    const bool mf = mf_taps && a.pk && a.pk_skip >= 0 && a.sync && a.n_steps >= 4 && !(a.dbg & 31) && (a.S == 256 || a.S == 512);
+    // conditioned: the f / g term of a sample is added to the tap-0 partial sums a sample ahead, so the matrix-core kernel serves
+    // it in the tap-0-ahead forms only; without them (WN_DEC_T0=0, no room for the table) the launch runs decode_k
+    const bool cond_ok = !cond || (t0_env != 0 && t0_room);
+    const bool mf = mf_taps && cond_ok && a.pk && a.pk_skip >= 0 && a.sync && a.n_steps >= 4 && !(a.dbg & 31) && (a.S == 256 || a.S == 512);
     if (nu > (mf ? 1024 : 128)) return wn_set_error_msg(-4, "decode: at most 128 utterances per launch (1024 on the matrix-core path)");
     if (mf) {
         const size_t nsync = (size_t)a.sync_ustride * sizeof(unsigned long long) * (size_t)nu;
@@ -1030,7 +1084,8 @@ int wn_launch_decode(const WnDecodeArgs& a, hipStream_t st) {
         const size_t s80_t2 = sizeof(float) * (size_t)(16 * a.Q + 16 * a.R) + sizeof(uint16_t) * (size_t)(8 * 136 * (3 + DEC_T0_CHUNK));
         const size_t s80_t0 = dec_t0_lds_bytes(a.n_layers);
         const size_t ws_h = 2 * ((size_t)a.S + 64) + 8;               // halfs of one utterance's split S-vector (the kernel's WS)
-        const size_t s81 = sizeof(uint16_t) * (size_t)(2 * 8 * 136 + 2 * 8 * ws_h) + sizeof(float) * (size_t)(8 * a.Q + 2 * a.S + a.Q);
+        const size_t s81 = sizeof(uint16_t) * (size_t)(2 * 8 * 136 + 2 * 8 * ws_h) + sizeof(float) * (size_t)(8 * a.Q + 2 * a.S + a.Q)
+                           + (a.cond_p1 ? sizeof(float) * (size_t)(8 * a.S) : 0);      // + the staged cond_p1 columns [8][S]
         // tap-0 table: in LDS when it fits (<= 31 blocks), else in the pair's hand-off area (wn_decode_sync_granules leaves room)
         const long need_tab = wn_decode_granules(a.n_layers, a.D, a.S);
         const int t0 = !t0_env ? 0 : (dec_t0_fits_lds(a.n_layers) ? 1 : (a.sync_ustride >= need_tab ? 2 : 0));
@@ -1048,7 +1103,7 @@ int wn_launch_decode(const WnDecodeArgs& a, hipStream_t st) {
         const size_t s_chain = t0 == 1 ? s80_t0 : (t0 == 2 ? s80_t2 : s80);
         const size_t sh = s_chain > s81 ? s_chain : s81;
         if (sh + 1024 > 160 * 1024) return wn_set_error_msg(-4, "decode: this many blocks do not fit the matrix-core kernel's LDS");
-        if (getenv("WN_DEC_VERBOSE")) fprintf(stderr, "[wn_decode] matrix-core, 8 utterances per pair: filter width %d, %d utterances, %d steps, %d skip channels, biases %d, tap-0 ahead %d, skip parts %d\n", a.fw, nu, a.n_steps, a.S, any_bias ? 1 : 0, t0, ks);
+        if (getenv("WN_DEC_VERBOSE")) fprintf(stderr, "[wn_decode] matrix-core, 8 utterances per pair: filter width %d, %d utterances, %d steps, %d skip channels, biases %d, tap-0 ahead %d, skip parts %d, conditioned %d (%d columns)\n", a.fw, nu, a.n_steps, a.S, any_bias ? 1 : 0, t0, ks, cond ? 1 : 0, cond ? a.le : 0);
         int dev = 0;
         (void)hipGetDevice(&dev);
         const int mx = 160 * 1024 - 1024;           // (the kernel also has ~350 bytes of static LDS)
@@ -1070,7 +1125,7 @@ int wn_launch_decode(const WnDecodeArgs& a, hipStream_t st) {
 #undef DEC_GO2
 #undef DEC_GO3
     } else {
-        if (getenv("WN_DEC_VERBOSE")) fprintf(stderr, "[wn_decode] generic fp32 kernel: %d utterances, %d steps\n", nu, a.n_steps);
+        if (getenv("WN_DEC_VERBOSE")) fprintf(stderr, "[wn_decode] generic fp32 kernel: %d utterances, %d steps, conditioned %d\n", nu, a.n_steps, cond ? 1 : 0);
         const size_t sh = dec_k_lds_bytes(a);
         if (sh + 1024 > 160 * 1024) return wn_set_error_msg(-4, "decode: the fp32 kernel's LDS layout does not fit (too many channels for this filter width)");
         if (sh > 64 * 1024) {                       // (above the default dynamic-LDS limit: raise it once per device)

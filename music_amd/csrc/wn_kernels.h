@@ -273,7 +273,20 @@ struct WnDecodeArgs {
     // utterance (oldest first), block ring i holds (k-1) d_i columns; fp32 weights w_causal [R][kQ] (k = tap 0 q | .. | tap k-1 q),
     // Wfg [2D][kR] (k = tap k-1 r | tap k-2 r | .. | tap 0 r)
     int fw;
+    // conditioned decode (wn_decode_batch_cond; the autoencoder's _conditon, model1.py:227-247): per-utterance tables, stage i adds
+    // column idx_i(pos0 + step + c_shift[i]) of its table - c_q[i] > 0: stretch, idx = c / c_q[i]; 0: tile, idx = c mod le; c < 0
+    // reads column 0, a stretch column past the end the last one.  Either table may be null (that stage is unconditioned).
+    const float* cond_fg; long cond_fg_ustride;          // [n_utt][n_layers][le][2D] rows f then g, added to the blocks' [f; g]
+    const float* cond_p1; long cond_p1_ustride;          // [n_utt][le][S], added to post_process_1's output before its relu
+    int c_shift[WN_DEC_MAX_LAYERS + 1], c_q[WN_DEC_MAX_LAYERS + 1];      // blocks 0 .. n_layers-1, then post-processing at [n_layers]
+    int le; long pos0;
 };
+// column of a conditioning table for output column c (see WnDecodeArgs::c_shift)
+__host__ __device__ inline int wn_dec_cond_idx(int c, int q, int le) {
+    if (c < 0) return 0;
+    if (q > 0) { const int i = c / q; return i < le ? i : le - 1; }
+    return c % le;
+}
 int wn_launch_decode(const WnDecodeArgs& a, hipStream_t st);
 size_t dec_k_lds_bytes(const WnDecodeArgs& a);            // dynamic LDS of the fp32 decode kernel (decode_k)
 #define WN_DEC_MAX_Q 1024                                  // quantisation channels the fp32 decode kernel's sampler covers

@@ -380,6 +380,69 @@ def generate_codes_batch(net, start_pieces, note_num, correct_queue=False, tempe
     return torch.cat([first.view(U, 1).to(torch.int64), codes.to(torch.int64)], 1)
 
 
+last_error_flags = None        # the error flag word of every utterance of the last decode_batch_cond launch (device tensor)
+
+
+def decode_batch_cond(net, rings, prev0, note0, n_steps, step0=0, pos0=0, forced=None, want_probs=False, temperature=None,
+                      seed=0, cond_fg=None, cond_p1=None, schedule=None):
+    """One persistent launch of wn_decode_batch_cond (corrected recurrence) for U utterances from explicit state: ``rings``
+    (U, ring floats) is advanced in place, ``prev0`` (U, k-1, Q) / ``note0`` (U, Q) are the causal layer's history and the
+    first input column.  ``cond_fg`` (U, N, Le, 2 Dp) rows [f | g] and ``cond_p1`` (U, Le, S) are the per-utterance
+    conditioning tables (Dp = the decode pack's dilation width), ``schedule`` the N + 1 (shift, q, Le) triples of
+    ``ae_generate.cond_schedule``; step s is output position pos0 + s.  ``forced`` (U, n_steps): the next input codes.
+    Returns (codes int32 (U, n_steps), probabilities (U, n_steps, Q) or None, note_out, prev_out)."""
+    eng = net._engine_for(rings.device)
+    pack = getattr(net, "_decode_pack", None)
+    if pack is None or pack.eng is not eng:
+        pack = net._decode_pack = _DecodePack(eng)
+    pack.refresh()
+    dev, N, Q, K1, U = eng.device, eng.N, eng.Q, _taps(eng), rings.size(0)
+    rw = _ring_width(eng)
+    q_off = _queue_offsets(eng, rw)
+    if rings.dim() != 2 or rings.size(1) != max(1, sum(K1 * d * rw for d in eng.dil)) or not rings.is_contiguous():
+        raise ValueError("decode_batch_cond: rings must be (U, %d) contiguous floats" % max(1, sum(K1 * d * rw for d in eng.dil)))
+    if U > (1024 if pack.mfma else 128):
+        raise ValueError("at most 1024 utterances per launch (128 off the matrix-core path)")
+    le = 1
+    shift = qs = None
+    if cond_fg is not None or cond_p1 is not None:
+        if schedule is None or len(schedule) != N + 1:
+            raise ValueError("decode_batch_cond: conditioning tables need a schedule of N + 1 (shift, q, Le) triples")
+        le = int(schedule[0][2])
+        if cond_fg is not None and (tuple(cond_fg.shape) != (U, N, le, 2 * pack.Dp) or not cond_fg.is_contiguous()):
+            raise ValueError("decode_batch_cond: cond_fg must be (U, N, Le, %d) contiguous" % (2 * pack.Dp))
+        if cond_p1 is not None and (tuple(cond_p1.shape) != (U, le, eng.S) or not cond_p1.is_contiguous()):
+            raise ValueError("decode_batch_cond: cond_p1 must be (U, Le, S) contiguous")
+        shift = (ctypes.c_int32 * (N + 1))(*[int(t[0]) for t in schedule])
+        qs = (ctypes.c_int32 * (N + 1))(*[int(t[1]) for t in schedule])
+    codes = torch.empty(U, n_steps, dtype=torch.int32, device=dev)
+    probs = torch.empty(U, n_steps, Q, dtype=torch.float32, device=dev) if want_probs else None
+    note_out = torch.empty(U, Q, dtype=torch.float32, device=dev)
+    prev_out = torch.empty(U, K1, Q, dtype=torch.float32, device=dev)
+    forced_t = forced.to(device=dev, dtype=torch.int32).contiguous() if forced is not None else None
+    assert forced_t is None or tuple(forced_t.shape) == (U, n_steps)
+    sync = torch.zeros(U * _lib.decode_sync_granules(N, pack.Dp, eng.S), dtype=torch.int64, device=dev)
+    dil = (ctypes.c_int32 * N)(*eng.dil)
+    qoff = (ctypes.c_int64 * N)(*[int(v) for v in q_off])
+    bias = pack.o_bias is not None
+    pk = pack.chain()
+    call("wn_decode_batch_cond", pack.k, N, pack.Rp, pack.Dp, eng.S, Q, ctypes.cast(dil, ctypes.c_void_p),
+         ctypes.cast(qoff, ctypes.c_void_p), ptr(rings), pack.p(pack.o_causal), pack.p(pack.ob_causal) if bias else None,
+         pack.p(pack.o_layers), pack.layer_stride, pack.p(pack.ob_layers) if bias else None,
+         pack.p(pack.o_p1), pack.p(pack.ob_p1) if bias else None, pack.p(pack.o_p2), pack.p(pack.ob_p2) if bias else None,
+         ptr(note0), _ptr_or_none(prev0), ptr(note_out), _ptr_or_none(prev_out), ptr(forced_t), ptr(codes), ptr(probs),
+         step0, n_steps, 1, ptr(sync), U, rings.size(1), float(temperature) if temperature else 0.0, int(seed),
+         pk[0], pk[1], pk[2], pk[3], pk[4], pk[5], pk[6],
+         ptr(cond_fg), cond_fg[0].numel() if cond_fg is not None else 0, ptr(cond_p1), cond_p1[0].numel() if cond_p1 is not None else 0,
+         ctypes.cast(shift, ctypes.c_void_p) if shift is not None else None, ctypes.cast(qs, ctypes.c_void_p) if qs is not None else None,
+         le, int(pos0), _lib.stream())
+    global last_error_flags
+    flags = last_error_flags = sync.view(U, -1)[:, -1]      # the error flag word of every utterance
+    if int(flags.abs().max().item()) != 0:
+        raise _lib.WavenetHipError("wn_decode_batch_cond: a hand-off between two decode workgroups timed out")
+    return codes, probs, note_out, prev_out
+
+
 def generate(model_path, model_name, generate_path, generate_name, start_piece=None, sr=16000, duration=10):
     """wavenet/fast_generate.py:144-179."""
     if os.path.exists(generate_path) is False:

@@ -2,7 +2,9 @@
 """Developer tool (GPU): cached-queue decode speed of the config-5 model (30 blocks, 64 / 64 / 256 / 256), one stream and
 batches, as bench.py's extra.c5_decode measures it; honours the WN_DEC_* switches.  `--bias`: a biased model (the
 autoencoder's cached decoder is one).  `--filter-width K`: the same shape with K taps (K != 2 runs the corrected queue
-recurrence, the only one defined there)."""
+recurrence, the only one defined there).  `--cond-frames N`: the same decoder CONDITIONED (wn_decode_batch_cond) on per-utterance
+tables of N frames with the schedule of a 16000-sample clip (config 4: N = 25), biased, corrected recurrence, from zero queues -
+to be compared with `--bias` (the unconditioned biased decoder of the same shape)."""
 import os
 import sys
 import time
@@ -18,7 +20,43 @@ def filter_width():
     return int(sys.argv[sys.argv.index("--filter-width") + 1]) if "--filter-width" in sys.argv else 2
 
 
+def cond_frames():
+    return int(sys.argv[sys.argv.index("--cond-frames") + 1]) if "--cond-frames" in sys.argv else 0
+
+
+def main_cond(le):
+    """conditioned decode of the config-4 decoder shape: one stream x 12930 positions, 128 utterances x 2000"""
+    from music_amd import ae_generate as ag
+    from music_amd import fast_generate as fg
+    from music_amd.model import wavenet
+    torch.manual_seed(0)
+    cfg = dict(bench.CFG, use_bias=True, filter_width=2)
+    net = wavenet(**cfg).cuda()
+    dev = torch.device("cuda", 0)
+    eng = net._engine_for(dev)
+    N, rf = len(cfg["dilations"]), net.receptive_field
+    W = 16000 - rf + 1
+    sched = ag.cond_schedule((2, cfg["dilations"]), W, le)
+    rw = fg._ring_width(eng)
+    for U, n in ((1, W), (128, 2000)):
+        tabs = dict(cond_fg=0.1 * torch.randn(U, N, le, 2 * 64, device=dev), cond_p1=0.1 * torch.randn(U, le, cfg["skip_channels"], device=dev),
+                    schedule=sched)
+        note = torch.zeros(U, 256, device=dev)
+        note[torch.arange(U), (128 + torch.arange(U)) % 256] = 1.0
+        for rep in range(3):
+            rings = torch.zeros(U, sum(d * rw for d in eng.dil), device=dev)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            codes, _, _, _ = fg.decode_batch_cond(net, rings, note.clone().view(U, 1, 256), note, n, step0=0, pos0=0, **tabs)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            print("conditioned (%d frames), %d utterance(s) x %d samples, run %d: %.3f s = %.1f k samples/s (%d distinct codes)"
+                  % (le, U, n, rep, dt, U * n / dt / 1e3, int(torch.unique(codes).numel())))
+
+
 def main():
+    if cond_frames():
+        return main_cond(cond_frames())
     from music_amd import fast_generate as fg
     from music_amd.model import wavenet
     torch.manual_seed(0)

@@ -15,6 +15,10 @@ if [ "$STAGE" = "all" ] || [ "$STAGE" = "tests" ]; then
   case $rc in 124|134|137|139) echo "stopping: see $LOGS/block_kernels.log" | tee -a $LOGS/summary.txt; exit $rc ;; esac
   timeout 1200 python -m pytest tests/test_gpu_parity.py -m gpu -q -s -p no:cacheprovider > $LOGS/parity.log 2>&1
   echo "parity exit $?" | tee -a $LOGS/summary.txt
+  timeout -k 10 900 python -m pytest tests/test_gpu_decode_cond.py -m gpu -q -s -p no:cacheprovider > $LOGS/decode_cond.log 2>&1
+  rc=$?
+  echo "conditioned decode exit $rc" | tee -a $LOGS/summary.txt
+  case $rc in 124|134|137|139) echo "stopping: see $LOGS/decode_cond.log" | tee -a $LOGS/summary.txt; exit $rc ;; esac
   timeout 600 python __graft_entry__.py smoke > $LOGS/smoke.log 2>&1
   echo "smoke exit $?" | tee -a $LOGS/summary.txt
 fi
