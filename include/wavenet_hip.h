@@ -266,7 +266,9 @@ int wn_shift_add(const float* p, const float* q, float* out, int64_t bstride, in
  * dimension ldc) with plain stores into slab number b*nchunks + j at c + slab*c_slab_stride.
  * wn_wgrad_slabs() returns the number of slabs a call writes; wn_reduce_slabs() sums them in slab
  * order (bit-reproducible, no float atomics).  Replaces the weight half of autograd's conv
- * backward (wavenet/train.py:181). */
+ * backward (wavenet/train.py:181).
+ * Operand values outside the window - columns other than [t_lo + shift, t_hi + shift) of a row - do not enter the result,
+ * NaN included (the engines' workspaces hold stale data there); operand columns below 0 read as zero. */
 int wn_wgrad(const float* a, int64_t a_bstride, int a_pitch, int a_shift, int a_cols,
              const float* b0, const float* b1, int64_t b_bstride, int b_pitch, int b_shift0,
              int b_shift1, int b_cols, int nt_per_tap, int mt, int relu_b, float* c, int ldc,
@@ -294,7 +296,9 @@ int wn_causal_fwd_codes(const int32_t* codes, int scrambled, const float* wt, co
 int wn_reduce_slabs(const int64_t* desc, int n_ops, int64_t total_vec, const float* slab, float* out,
                     wn_stream_t stream);
 
-/* out[row] = sum_{b,t} a[b][row][t+a_shift]  (bias gradients, use_bias=true) */
+/* out[row] = sum_{b, t in [t_lo,t_hi)} a[b][row][t+a_shift]  (bias gradients, use_bias=true).
+ * Values of a outside the window [t_lo + a_shift, t_hi + a_shift) of a row do not enter the result, NaN included.
+ * No clips, rows or columns: returns 0 and writes nothing. */
 int wn_bias_grad(const float* a, int64_t a_bstride, int a_pitch, int a_shift, int rows, int t_lo,
                  int t_hi, int batch, float* out, wn_stream_t stream);
 

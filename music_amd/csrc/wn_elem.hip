@@ -388,7 +388,7 @@ __global__ __launch_bounds__(256) void bias_grad_k(const float* __restrict__ a, 
 }
 int wn_launch_bias_grad(const float* a, long a_bstride, int a_pitch, int a_shift, int rows, int t_lo,
                         int t_hi, int batch, float* out, hipStream_t st) {
-    if (rows <= 0) return 0;
+    if (rows <= 0 || batch <= 0 || t_hi <= t_lo) return 0;      // no work: nothing is launched, `out` (not required then) is left alone
     hipLaunchKernelGGL(bias_grad_k, dim3(rows), dim3(256), 0, st, a, a_bstride, a_pitch, a_shift, t_lo, t_hi, batch, out);
     WN_CHECK_LAUNCH();
     return 0;

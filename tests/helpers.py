@@ -42,6 +42,18 @@ def nonvacuous(p_ref, what, floor=0.05):
     return m
 
 
+def nan_rows(win, pitch, col0, slack, tail=512):
+    """The NaN-surrounded operand of the kernel-level tests: a flat float32 CPU buffer of slack + b * rows * pitch + tail
+    floats, NaN everywhere except columns [col0, col0 + w) of every row, which hold win[b][row][:] (the part of a window
+    that would start below column 0 is not stored: such columns do not exist)."""
+    b, rows, w = win.shape
+    first = max(0, -col0)
+    assert col0 + w <= pitch
+    t = torch.full((slack + b * rows * pitch + tail,), float("nan"), dtype=torch.float32)
+    t[slack:slack + b * rows * pitch].view(b, rows, pitch)[:, :, col0 + first:col0 + w] = win[:, :, first:]
+    return t
+
+
 def g1_input(d, meta):
     if meta["kind"] == "randn":
         return torch.from_numpy(d["x"])

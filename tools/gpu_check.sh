@@ -13,6 +13,10 @@ if [ "$STAGE" = "all" ] || [ "$STAGE" = "tests" ]; then
   echo "block kernels exit $rc" | tee -a $LOGS/summary.txt
   # a time limit, an abort or a segmentation fault in a kernel test: nothing more is started on this card
   case $rc in 124|134|137|139) echo "stopping: see $LOGS/block_kernels.log" | tee -a $LOGS/summary.txt; exit $rc ;; esac
+  timeout -k 10 600 python -m pytest tests/test_gpu_wgrad_kernels.py -m gpu -q -s -p no:cacheprovider > $LOGS/wgrad_kernels.log 2>&1
+  rc=$?
+  echo "wgrad kernels exit $rc" | tee -a $LOGS/summary.txt
+  case $rc in 124|134|137|139) echo "stopping: see $LOGS/wgrad_kernels.log" | tee -a $LOGS/summary.txt; exit $rc ;; esac
   timeout 1200 python -m pytest tests/test_gpu_parity.py -m gpu -q -s -p no:cacheprovider > $LOGS/parity.log 2>&1
   echo "parity exit $?" | tee -a $LOGS/summary.txt
   timeout -k 10 900 python -m pytest tests/test_gpu_decode_cond.py -m gpu -q -s -p no:cacheprovider > $LOGS/decode_cond.log 2>&1
@@ -26,7 +30,7 @@ if [ "$STAGE" = "all" ] || [ "$STAGE" = "bench" ]; then
   timeout 900 python bench.py --steps 10 --warmup 3 --full --phases > $LOGS/bench.log 2> $LOGS/bench.err
   echo "bench exit $?" | tee -a $LOGS/summary.txt
 fi
-tail -n 60 $LOGS/kernels.log $LOGS/block_kernels.log $LOGS/parity.log $LOGS/smoke.log $LOGS/bench.log $LOGS/bench.err 2>/dev/null | tail -n 150
+tail -n 60 $LOGS/kernels.log $LOGS/block_kernels.log $LOGS/wgrad_kernels.log $LOGS/parity.log $LOGS/smoke.log $LOGS/bench.log $LOGS/bench.err 2>/dev/null | tail -n 150
 if [ "$STAGE" = "all" ] || [ "$STAGE" = "prof" ]; then
   REPO=$(pwd)
   case $LOGS in /*) L=$LOGS ;; *) L=$REPO/$LOGS ;; esac
