@@ -42,7 +42,7 @@ extern "C" {
 
 typedef void* wn_stream_t;                 /* hipStream_t */
 enum { WN_F16X3 = 0, WN_F16X1 = 1, WN_BF16X3 = 2, WN_BF16X1 = 3 };
-#define WN_ABI_VERSION 7
+#define WN_ABI_VERSION 8
 #define WN_CE_NUM_PARTIALS 1024
 
 int wn_version(void);
@@ -488,6 +488,47 @@ int wn_decode_batch_cond(int filter_width, int n_layers, int R, int D, int S, in
                          int64_t pk_p1, int64_t pk_p2, const float* cond_fg, int64_t cond_fg_ustride, const float* cond_p1,
                          int64_t cond_p1_ustride, const int32_t* c_shift_host, const int32_t* c_q_host, int le, int64_t pos0,
                          wn_stream_t stream);
+
+/* Sampling settings of one utterance of a decode launch, or of one row of wn_sample_logits (ABI 8), 24 bytes.
+ * temperature <= 0: greedy first-index argmax (the filters are ignored).  top_k <= 0 or >= Q: no top-k filter; top_p <= 0 or
+ * >= 1: no nucleus filter.  The uniform number of step s is dec_uniform(seed, s, stream) (splitmix64 finaliser, 24 bits). */
+typedef struct { float temperature; float top_p; int32_t top_k; uint32_t stream; uint64_t seed; } wn_sampling;
+
+/* wn_decode_batch_cond with TRUNCATED sampling and PER-UTTERANCE settings (ABI 8).  The rule, per row of Q logits l with
+ * temperature T > 0 and a uniform number u in [0, 1), is decided on the LOGITS, so the kept set is exact:
+ *   1. top-k (0 < top_k < Q): K = { i : l_i >= the top_k-th largest logit } - ties at the boundary are kept; else K = all.
+ *   2. p_i = exp((l_i - max l) / T) / sum over K on K, 0 elsewhere.
+ *   3. top-p (0 < top_p < 1): tau = the largest logit value v in K with sum_{K, l_i >= v} p_i >= top_p, N = { i in K :
+ *      l_i >= tau } (ties kept); else N = K.
+ *   4. r = p / sum over N on N, 0 elsewhere: probs_out receives r (exact zeros outside N); the code is the first index whose
+ *      inclusive cumulative r exceeds u, and the LARGEST INDEX IN N when none does (u above the rounded total).
+ *   5. T <= 0: greedy first-index argmax, probs_out is the plain softmax.
+ * samp == NULL: the scalar temperature / seed / top_k / top_p apply to every utterance and utterance u draws from stream u;
+ * with top_k = 0 and top_p = 1 that is wn_decode_batch_cond bit for bit.  samp != NULL: a DEVICE array [n_utt]; utterance
+ * u takes everything from samp[u] (read once, before the first sample) and the scalars are ignored.  Row u of a launch with
+ * a table equals the single-utterance launch with samp[u] - bit for bit when both run the same kernel form (at 256 skip
+ * channels one pair's skip stage is split over four workgroups by default, several pairs' are not, and the two forms round
+ * the logits differently: WN_DEC_KS holds the form fixed).
+ * Returns -4 (wn_last_error names the argument) for a scalar top_p that is NaN or negative, a scalar top_k < 0, and
+ * everything wn_decode_batch_cond refuses. */
+int wn_decode_batch_samp(int filter_width, int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host,
+                         const int64_t* q_off_host, float* queues, const float* w_causal, const float* b_causal,
+                         const float* w_layers, int64_t layer_stride, const float* b_layers, const float* w_p1, const float* b_p1,
+                         const float* w_p2, const float* b_p2, const float* note0, const float* prev0, float* note_out,
+                         float* prev_out, const int32_t* forced, int32_t* codes_out, float* probs_out, int64_t step0,
+                         int n_steps, int push_input, uint64_t* sync, int n_utt, int64_t queues_ustride, float temperature,
+                         uint64_t seed, const uint16_t* pk, int64_t pk_fg0, int64_t pk_d0, int64_t pk_lstride, int64_t pk_skip,
+                         int64_t pk_p1, int64_t pk_p2, const float* cond_fg, int64_t cond_fg_ustride, const float* cond_p1,
+                         int64_t cond_p1_ustride, const int32_t* c_shift_host, const int32_t* c_q_host, int le, int64_t pos0,
+                         const wn_sampling* samp, int top_k, float top_p, wn_stream_t stream);
+
+/* The decoder's sampler (the same device function) on a logits matrix: row i of logits [n][Q] (row stride ld >= Q floats)
+ * is "step" step0 + i.  samp: optional DEVICE table [n], one entry per row; NULL: the scalars apply to every row and the
+ * stream id is 0.  u: optional DEVICE array [n] of explicit uniform numbers in [0, 1) that replace the generated ones.
+ * codes [n] receives the codes, probs [n][Q] (optional) the distribution drawn from.  1 <= Q <= 1024; n == 0 launches
+ * nothing.  Returns -4 for Q out of range, n < 0, ld < Q, NULL logits / codes, and a scalar top_p / top_k as above. */
+int wn_sample_logits(const float* logits, int64_t n, int Q, int64_t ld, const wn_sampling* samp, float temperature, uint64_t seed,
+                     int top_k, float top_p, int64_t step0, const float* u, int32_t* codes, float* probs, wn_stream_t stream);
 
 #ifdef __cplusplus
 }

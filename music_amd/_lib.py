@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get("WAVENET_HIP_LIB") or os.path.join(_HERE, "libwavenet_
 F16X3, F16X1, BF16X3, BF16X1 = 0, 1, 2, 3
 MODE_NAMES = {"f16x3": F16X3, "f16x1": F16X1, "bf16x3": BF16X3, "bf16x1": BF16X1}
 CE_NUM_PARTIALS = 1024
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 _p = ctypes.c_void_p
 _i = ctypes.c_int
@@ -97,7 +97,18 @@ SIGNATURES = {
     # wn_decode_batch_fw + cond_fg, its utterance stride, cond_p1, its utterance stride, c_shift, c_q, le, pos0 (before the stream)
     "wn_decode_batch_cond": [_i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
                              _l, _i, _i, _p, _i, _l, _f, _l, _p, _l, _l, _l, _l, _l, _l, _p, _l, _p, _l, _p, _p, _i, _l, _p],
+    # wn_decode_batch_cond + the per-utterance wn_sampling table, top_k, top_p (before the stream)
+    "wn_decode_batch_samp": [_i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
+                             _l, _i, _i, _p, _i, _l, _f, _l, _p, _l, _l, _l, _l, _l, _l, _p, _l, _p, _l, _p, _p, _i, _l,
+                             _p, _i, _f, _p],
+    "wn_sample_logits": [_p, _l, _i, _l, _p, _f, _l, _i, _f, _l, _p, _p, _p, _p],
 }
+
+
+class Sampling(ctypes.Structure):
+    """wn_sampling (include/wavenet_hip.h): one utterance's / one row's sampling settings, 24 bytes."""
+    _fields_ = [("temperature", ctypes.c_float), ("top_p", ctypes.c_float), ("top_k", ctypes.c_int32),
+                ("stream", ctypes.c_uint32), ("seed", ctypes.c_uint64)]
 
 _lib = None
 

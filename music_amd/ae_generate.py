@@ -38,10 +38,18 @@ except ImportError:
     from music_amd.train import load_model
 
 
-def predict_next(net, input_wav, quantization_channel=256):
-    """generate.py:13-19 — argmax over the last chunk-row of the forward output."""
+def predict_next(net, input_wav, quantization_channel=256, temperature=None, top_k=None, top_p=None, seed=0, step=0):
+    """generate.py:13-19 — argmax over the last chunk-row of the forward output.  ``temperature`` > 0: the code is drawn by
+    the decoder's sampler (``fast_generate.sample_logits`` on the log of that row: the softmax only shifts the logits) as
+    step ``step`` of ``seed``, truncated by ``top_k`` / ``top_p``."""
     with torch.no_grad():
         out = net(input_wav).view(-1, quantization_channel)
+    if temperature is not None and temperature > 0:
+        try:
+            from . import fast_generate as fg
+        except ImportError:
+            from music_amd import fast_generate as fg
+        return int(fg.sample_logits(torch.log(out[-1:, :].float()), temperature, top_k, top_p, seed=seed, step0=step)[0])
     return int(torch.topk(out[-1, :].view(-1), 1)[1])
 
 
@@ -135,7 +143,8 @@ def conditioned_decoder(net, cond):
     return wnet, proj
 
 
-def resynthesize(net, clips, cond=None, teacher_forced=False, want_probs=False, temperature=None, seed=0):
+def resynthesize(net, clips, cond=None, teacher_forced=False, want_probs=False, temperature=None, seed=0, top_k=None, top_p=None,
+                 streams=None):
     """Encode ``clips`` (B, Q, T) one-hot, T >= receptive_field with at least one pooled frame, and regenerate them from the
     encoding with the cached-queue decoder: the encoder runs ONCE, the conditioning projections are drawn ONCE (or taken
     from ``cond``), the per-clip tables (one column per pooled frame and stage) are built on the device, the queues are
@@ -144,7 +153,8 @@ def resynthesize(net, clips, cond=None, teacher_forced=False, want_probs=False, 
     W = T - rf + 1 output positions are decoded in one persistent launch, every clip with its own tables.
     ``teacher_forced``: the clip's own codes are fed (the probabilities are then the forward's, row for row); otherwise the
     model's own codes are fed back after the clip's first receptive_field samples.  ``temperature``: sample instead of
-    argmax, reproducibly for ``seed``.  Returns (codes int64 (B, W), probabilities (B, W, Q) or None, encodings (B, Bw, Le))."""
+    argmax, reproducibly for ``seed``; ``top_k`` / ``top_p`` truncate the distribution first; each of the four may be one value per clip
+    (``streams``: the clips' random-number stream ids, default their index).  Returns (codes int64 (B, W), probabilities (B, W, Q) or None, encodings (B, Bw, Le))."""
     try:
         from . import fast_generate as fg
     except ImportError:
@@ -193,11 +203,12 @@ def resynthesize(net, clips, cond=None, teacher_forced=False, want_probs=False, 
     if teacher_forced:
         forced = torch.cat([codes_in[:, rf:], torch.zeros(B, 1, dtype=torch.int32, device=x.device)], 1)
     codes, probs, _, _ = fg.decode_batch_cond(wnet, rings, prev, note, W, step0=rf - 1, pos0=0, forced=forced,
-                                              want_probs=want_probs, temperature=temperature, seed=seed, **tabs)
+                                              want_probs=want_probs, temperature=temperature, seed=seed, top_k=top_k, top_p=top_p,
+                                              streams=streams, **tabs)
     return codes.to(torch.int64), probs, enc
 
 
-def generate_cached(net, start_piece, note_num, cond=None, temperature=None, seed=0):
+def generate_cached(net, start_piece, note_num, cond=None, temperature=None, seed=0, top_k=None, top_p=None):
     """encode ``start_piece`` (1, Q, >= receptive_field) once, draw the conditioning projections once
     (or take ``cond``), then generate ``note_num`` codes with the persistent cached-queue decoder (corrected queue
     recurrence).  Returns (codes int64 on the device, the wavenet-form decoder, the encoding)."""
@@ -215,22 +226,25 @@ def generate_cached(net, start_piece, note_num, cond=None, temperature=None, see
         cond = net._draw_conditioning()
     wnet = cached_decoder(net, enc, cond)
     codes = fg.generate_codes(wnet, start_piece[:, :, -wnet.receptive_field:].cuda(), note_num, correct_queue=True,
-                              temperature=temperature, seed=seed)
+                              temperature=temperature, seed=seed, top_k=top_k, top_p=top_p)
     return codes, wnet, enc
 
 
-def generate_codes_naive(net, start_piece, note_num, sliding_window=False, window=None, seed=None):
+def generate_codes_naive(net, start_piece, note_num, sliding_window=False, window=None, seed=None, temperature=None, top_k=None,
+                         top_p=None):
     """The loop of generate.py:44-55: one full forward (encoder + conditioned decoder, fresh random conditioning
     projections) per generated code.  ``sliding_window`` False = as written (growing window), True = the last
     ``window - 1`` samples + the new one (``window`` defaults to receptive_field + 512).  ``seed``: torch.manual_seed(seed + i)
-    before step i (the projections are drawn from the global RNG), for reproducible runs and the golden tests."""
+    before step i (the projections are drawn from the global RNG), for reproducible runs and the golden tests.
+    ``temperature`` / ``top_k`` / ``top_p``: draw each code with the decoder's sampler instead of the argmax (``predict_next``)."""
     win = window if window is not None else net.receptive_field + 512
     input_wav = start_piece.cuda()
     generated = []
     for i in range(note_num):
         if seed is not None:
             torch.manual_seed(int(seed) + i)
-        code = predict_next(net, input_wav, net.quantization_channel)
+        code = predict_next(net, input_wav, net.quantization_channel, temperature=temperature, top_k=top_k, top_p=top_p,
+                            seed=seed or 0, step=i)
         generated.append(code)
         note = torch.zeros(1, net.quantization_channel, 1, device=input_wav.device)
         note[0, code, 0] = 1.0
@@ -240,7 +254,7 @@ def generate_codes_naive(net, start_piece, note_num, sliding_window=False, windo
 
 
 def generate(model_path, model_name, generate_path, generate_name, start_piece=None, sr=16000, duration=10,
-             sliding_window=False, seed=None):
+             sliding_window=False, seed=None, temperature=None, top_k=None, top_p=None):
     if os.path.exists(generate_path) is False:
         os.makedirs(generate_path)
     with open('./params/model_params.json') as f:
@@ -254,7 +268,7 @@ def generate(model_path, model_name, generate_path, generate_name, start_piece=N
         start_piece = torch.zeros(1, 256, net.receptive_field + 512)
         start_piece[:, 128, :] = 1.0
     generated = generate_codes_naive(net, start_piece, int(duration * sr), sliding_window=sliding_window,
-                                     window=start_piece.size(2), seed=seed)
+                                     window=start_piece.size(2), seed=seed, temperature=temperature, top_k=top_k, top_p=top_p)
     audio = mu_law_decode(torch.tensor(generated, dtype=torch.int64), net.quantization_channel).cpu().numpy()
     from scipy.io import wavfile
     wavfile.write(generate_path + generate_name, sr, audio.astype(np.float32))

@@ -453,7 +453,7 @@ static int decode_impl(int n_layers, int R, int D, int S, int Q, const int32_t* 
                        int64_t pk_skip, int64_t pk_p1, int64_t pk_p2, int fw, wn_stream_t stream,
                        const float* cond_fg = nullptr, int64_t cond_fg_ustride = 0, const float* cond_p1 = nullptr,
                        int64_t cond_p1_ustride = 0, const int32_t* c_shift = nullptr, const int32_t* c_q = nullptr, int le = 1,
-                       int64_t pos0 = 0);
+                       int64_t pos0 = 0, const wn_sampling* samp = nullptr, int top_k = 0, float top_p = 1.0f);
 extern "C" {
 int64_t wn_decode_sync_granules(int n_layers, int D, int S);
 int wn_decode_batch(int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host, const int64_t* q_off_host,
@@ -537,6 +537,41 @@ int wn_decode_batch_fw(int filter_width, int n_layers, int R, int D, int S, int 
                        temperature, seed, pk, pk_fg0, pk_d0, pk_lstride, pk_skip, pk_p1, pk_p2, filter_width, stream);
 }
 
+static int decode_cond_checked(const char* fn, int filter_width, int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host,
+                         const int64_t* q_off_host, float* queues, const float* w_causal, const float* b_causal,
+                         const float* w_layers, int64_t layer_stride, const float* b_layers, const float* w_p1, const float* b_p1,
+                         const float* w_p2, const float* b_p2, const float* note0, const float* prev0, float* note_out,
+                         float* prev_out, const int32_t* forced, int32_t* codes_out, float* probs_out, int64_t step0,
+                         int n_steps, int push_input, uint64_t* sync, int n_utt, int64_t queues_ustride, float temperature,
+                         uint64_t seed, const uint16_t* pk, int64_t pk_fg0, int64_t pk_d0, int64_t pk_lstride, int64_t pk_skip,
+                         int64_t pk_p1, int64_t pk_p2, const float* cond_fg, int64_t cond_fg_ustride, const float* cond_p1,
+                         int64_t cond_p1_ustride, const int32_t* c_shift_host, const int32_t* c_q_host, int le, int64_t pos0,
+                         const wn_sampling* samp, int top_k, float top_p, wn_stream_t stream) {
+    char msg[256];
+#define DEC_REFUSE(text) do { snprintf(msg, sizeof(msg), "%s: " text, fn); return wn_set_error_msg(-4, msg); } while (0)
+    if (filter_width < 1) DEC_REFUSE("filter_width must be >= 1");
+    if (!push_input) DEC_REFUSE("conditioned decode exists for the corrected recurrence only; pass push_input = 1");
+    if (le < 1) DEC_REFUSE("le (columns of a conditioning table) must be >= 1");
+    if (Q < 1 || Q > WN_DEC_MAX_Q) DEC_REFUSE("1 <= Q <= 1024 quantisation channels");
+    if (n_layers > WN_DEC_MAX_LAYERS || n_layers <= 0) DEC_REFUSE("1..64 layers supported");
+    if (cond_fg || cond_p1) {
+        if (!c_shift_host || !c_q_host)
+            DEC_REFUSE("a conditioning table needs the schedule arrays 'c_shift_host' and 'c_q_host' (n_layers + 1 entries each)");
+        for (int i = 0; i <= n_layers; ++i)
+            if (c_q_host[i] < 0) DEC_REFUSE("c_q[i] must be >= 0 (stretch factor, or 0 = tile)");
+    }
+    if (n_utt > 0 && n_steps > 0) {
+        WN_REQUIRE(fn, note0, note_out, codes_out);
+        if (filter_width > 1) WN_REQUIRE(fn, prev0, prev_out);
+    }
+    return decode_impl(n_layers, R, D, S, Q, dilations_host, q_off_host, queues, w_causal, b_causal, w_layers, layer_stride,
+                       b_layers, w_p1, b_p1, w_p2, b_p2, note0, prev0, note_out, prev_out, forced, codes_out, probs_out,
+                       step0, n_steps, push_input, sync, wn_decode_sync_granules(n_layers, D, S), n_utt, queues_ustride,
+                       temperature, seed, pk, pk_fg0, pk_d0, pk_lstride, pk_skip, pk_p1, pk_p2, filter_width, stream,
+                       cond_fg, cond_fg_ustride, cond_p1, cond_p1_ustride, c_shift_host, c_q_host, le, pos0, samp, top_k, top_p);
+#undef DEC_REFUSE
+}
+
 int wn_decode_batch_cond(int filter_width, int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host,
                          const int64_t* q_off_host, float* queues, const float* w_causal, const float* b_causal,
                          const float* w_layers, int64_t layer_stride, const float* b_layers, const float* w_p1, const float* b_p1,
@@ -547,29 +582,47 @@ int wn_decode_batch_cond(int filter_width, int n_layers, int R, int D, int S, in
                          int64_t pk_p1, int64_t pk_p2, const float* cond_fg, int64_t cond_fg_ustride, const float* cond_p1,
                          int64_t cond_p1_ustride, const int32_t* c_shift_host, const int32_t* c_q_host, int le, int64_t pos0,
                          wn_stream_t stream) {
-    if (filter_width < 1) return wn_set_error_msg(-4, "wn_decode_batch_cond: filter_width must be >= 1");
-    if (!push_input)
-        return wn_set_error_msg(-4, "wn_decode_batch_cond: conditioned decode exists for the corrected recurrence only; pass "
-                                    "push_input = 1");
-    if (le < 1) return wn_set_error_msg(-4, "wn_decode_batch_cond: le (columns of a conditioning table) must be >= 1");
-    if (Q < 1 || Q > WN_DEC_MAX_Q) return wn_set_error_msg(-4, "wn_decode_batch_cond: 1 <= Q <= 1024 quantisation channels");
-    if (n_layers > WN_DEC_MAX_LAYERS || n_layers <= 0) return wn_set_error_msg(-4, "wn_decode_batch_cond: 1..64 layers supported");
-    if (cond_fg || cond_p1) {
-        if (!c_shift_host || !c_q_host)
-            return wn_set_error_msg(-4, "wn_decode_batch_cond: a conditioning table needs the schedule arrays 'c_shift_host' and "
-                                        "'c_q_host' (n_layers + 1 entries each)");
-        for (int i = 0; i <= n_layers; ++i)
-            if (c_q_host[i] < 0) return wn_set_error_msg(-4, "wn_decode_batch_cond: c_q[i] must be >= 0 (stretch factor, or 0 = tile)");
+    return decode_cond_checked("wn_decode_batch_cond", filter_width, n_layers, R, D, S, Q, dilations_host, q_off_host, queues, w_causal, b_causal, w_layers,
+                               layer_stride, b_layers, w_p1, b_p1, w_p2, b_p2, note0, prev0, note_out, prev_out, forced, codes_out,
+                               probs_out, step0, n_steps, push_input, sync, n_utt, queues_ustride, temperature, seed, pk, pk_fg0,
+                               pk_d0, pk_lstride, pk_skip, pk_p1, pk_p2, cond_fg, cond_fg_ustride, cond_p1, cond_p1_ustride,
+                               c_shift_host, c_q_host, le, pos0, nullptr, 0, 1.0f, stream);
+}
+
+int wn_decode_batch_samp(int filter_width, int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host,
+                         const int64_t* q_off_host, float* queues, const float* w_causal, const float* b_causal,
+                         const float* w_layers, int64_t layer_stride, const float* b_layers, const float* w_p1, const float* b_p1,
+                         const float* w_p2, const float* b_p2, const float* note0, const float* prev0, float* note_out,
+                         float* prev_out, const int32_t* forced, int32_t* codes_out, float* probs_out, int64_t step0,
+                         int n_steps, int push_input, uint64_t* sync, int n_utt, int64_t queues_ustride, float temperature,
+                         uint64_t seed, const uint16_t* pk, int64_t pk_fg0, int64_t pk_d0, int64_t pk_lstride, int64_t pk_skip,
+                         int64_t pk_p1, int64_t pk_p2, const float* cond_fg, int64_t cond_fg_ustride, const float* cond_p1,
+                         int64_t cond_p1_ustride, const int32_t* c_shift_host, const int32_t* c_q_host, int le, int64_t pos0,
+                         const wn_sampling* samp, int top_k, float top_p, wn_stream_t stream) {
+    if (!samp) {        // the scalar form's filters (a table's entries are normalised on the device: out of range = filter off)
+        if (!(top_p >= 0.0f)) return wn_set_error_msg(-4, "wn_decode_batch_samp: 'top_p' must be a number >= 0 (0 or >= 1: no nucleus filter)");
+        if (top_k < 0) return wn_set_error_msg(-4, "wn_decode_batch_samp: 'top_k' must be >= 0 (0 or >= Q: no top-k filter)");
     }
-    if (n_utt > 0 && n_steps > 0) {
-        WN_REQUIRE("wn_decode_batch_cond", note0, note_out, codes_out);
-        if (filter_width > 1) WN_REQUIRE("wn_decode_batch_cond", prev0, prev_out);
+    return decode_cond_checked("wn_decode_batch_samp", filter_width, n_layers, R, D, S, Q, dilations_host, q_off_host, queues, w_causal, b_causal, w_layers,
+                               layer_stride, b_layers, w_p1, b_p1, w_p2, b_p2, note0, prev0, note_out, prev_out, forced, codes_out,
+                               probs_out, step0, n_steps, push_input, sync, n_utt, queues_ustride, temperature, seed, pk, pk_fg0,
+                               pk_d0, pk_lstride, pk_skip, pk_p1, pk_p2, cond_fg, cond_fg_ustride, cond_p1, cond_p1_ustride,
+                               c_shift_host, c_q_host, le, pos0, samp, top_k, top_p, stream);
+}
+
+int wn_sample_logits(const float* logits, int64_t n, int Q, int64_t ld, const wn_sampling* samp, float temperature, uint64_t seed,
+                     int top_k, float top_p, int64_t step0, const float* u, int32_t* codes, float* probs, wn_stream_t stream) {
+    if (Q < 1 || Q > WN_DEC_MAX_Q) return wn_set_error_msg(-4, "wn_sample_logits: 1 <= 'Q' <= 1024 entries per row");
+    if (n < 0) return wn_set_error_msg(-4, "wn_sample_logits: 'n' (rows) must be >= 0");
+    if (ld < Q) return wn_set_error_msg(-4, "wn_sample_logits: 'ld' (row stride) must be >= Q");
+    if (!samp) {
+        if (!(top_p >= 0.0f)) return wn_set_error_msg(-4, "wn_sample_logits: 'top_p' must be a number >= 0 (0 or >= 1: no nucleus filter)");
+        if (top_k < 0) return wn_set_error_msg(-4, "wn_sample_logits: 'top_k' must be >= 0 (0 or >= Q: no top-k filter)");
     }
-    return decode_impl(n_layers, R, D, S, Q, dilations_host, q_off_host, queues, w_causal, b_causal, w_layers, layer_stride,
-                       b_layers, w_p1, b_p1, w_p2, b_p2, note0, prev0, note_out, prev_out, forced, codes_out, probs_out,
-                       step0, n_steps, push_input, sync, wn_decode_sync_granules(n_layers, D, S), n_utt, queues_ustride,
-                       temperature, seed, pk, pk_fg0, pk_d0, pk_lstride, pk_skip, pk_p1, pk_p2, filter_width, stream,
-                       cond_fg, cond_fg_ustride, cond_p1, cond_p1_ustride, c_shift_host, c_q_host, le, pos0);
+    if (n == 0) return 0;
+    WN_REQUIRE("wn_sample_logits", logits, codes);
+    return wn_launch_sample_logits(logits, (long)n, Q, (long)ld, reinterpret_cast<const WnSampling*>(samp), temperature, seed, top_k,
+                                   top_p, (long)step0, u, codes, probs, (hipStream_t)stream);
 }
 
 }  // extern "C"
@@ -583,7 +636,8 @@ static int decode_impl(int n_layers, int R, int D, int S, int Q, const int32_t* 
                        float temperature, uint64_t seed, const uint16_t* pk, int64_t pk_fg0, int64_t pk_d0, int64_t pk_lstride,
                        int64_t pk_skip, int64_t pk_p1, int64_t pk_p2, int fw, wn_stream_t stream,
                        const float* cond_fg, int64_t cond_fg_ustride, const float* cond_p1, int64_t cond_p1_ustride,
-                       const int32_t* c_shift, const int32_t* c_q, int le, int64_t pos0) {
+                       const int32_t* c_shift, const int32_t* c_q, int le, int64_t pos0, const wn_sampling* samp, int top_k,
+                       float top_p) {
     if (n_utt <= 0) return 0;
     if (n_layers > WN_DEC_MAX_LAYERS || n_layers <= 0) return wn_set_error_msg(-4, "wn_decode: 1..64 layers supported");
     WN_REQUIRE("wn_decode", dilations_host, q_off_host);              // (host arrays, read right here)
@@ -601,6 +655,7 @@ static int decode_impl(int n_layers, int R, int D, int S, int Q, const int32_t* 
     a.sync_ustride = sync_ustride;
     a.n_utt = n_utt; a.queues_ustride = queues_ustride;
     a.sample = temperature > 0.0f ? 1 : 0; a.inv_temp = temperature > 0.0f ? 1.0f / temperature : 1.0f; a.seed = seed;
+    a.samp = reinterpret_cast<const WnSampling*>(samp); a.top_k = top_k; a.top_p = top_p;
     a.pk_skip = -1;
     a.cond_fg = cond_fg; a.cond_fg_ustride = cond_fg_ustride; a.cond_p1 = cond_p1; a.cond_p1_ustride = cond_p1_ustride;
     a.le = le; a.pos0 = pos0;

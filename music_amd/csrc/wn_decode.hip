@@ -45,6 +45,30 @@ __device__ __forceinline__ void dec_matvec(const float* __restrict__ W, int ldw,
 }
 
 
+// Inverse CDF over the wave's NE x 64 probabilities: inclusive scan of the lane sums (pairwise: (v0 + v1) + (v2 + v3) for
+// NE = 4), then the first entry whose cumulative probability exceeds u; 1 << 20 when none does.  Valid in every lane.
+template <int NE>
+__device__ __forceinline__ int dec_draw(const float (&v)[NE], int lane, float u) {
+    float t[NE];
+    for (int e = 0; e < NE; ++e) t[e] = v[e];
+    for (int w = 1; w < NE; w <<= 1)
+        for (int e = 0; e + w < NE; e += 2 * w) t[e] += t[e + w];
+    const float mine = t[0];
+    float incl = mine;
+    for (int off = 1; off < 64; off <<= 1) {
+        const float o = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += o;
+    }
+    float c = incl - mine;
+    int pick = 1 << 20;
+    for (int e = 0; e < NE; ++e) {
+        c += v[e];
+        if (pick == (1 << 20) && c > u) pick = lane * NE + e;
+    }
+    for (int off = 32; off > 0; off >>= 1) pick = min(pick, __shfl_xor(pick, off, 64));
+    return pick;
+}
+
 // Next code from the Q pre-softmax logits (one wave, lane l owns entries NE*l .. NE*l + NE-1, entries >= Q are -inf padding
 // and never read or written; NE = 4 for the usual 256): probabilities = softmax(logit * inv_temp) (written to probs_dst
 // if given), then either the first-index argmax (the reference's greedy topk(1), fast_generate.py:139) or - SURVEY 8f2 -
@@ -75,43 +99,208 @@ __device__ __forceinline__ int dec_choose(const float* logit, int Q, int lane, f
         }
         return bi;
     }
-    // inclusive scan of the lane sums (pairwise: (v0 + v1) + (v2 + v3) for NE = 4), then the first entry whose
-    // cumulative probability exceeds u
-    float t[NE];
-    for (int e = 0; e < NE; ++e) t[e] = v[e];
-    for (int w = 1; w < NE; w <<= 1)
-        for (int e = 0; e + w < NE; e += 2 * w) t[e] += t[e + w];
-    const float mine = t[0];
-    float incl = mine;
-    for (int off = 1; off < 64; off <<= 1) {
-        const float o = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += o;
-    }
-    float c = incl - mine;
-    int pick = 1 << 20;
-    for (int e = 0; e < NE; ++e) {
-        c += v[e];
-        if (pick == (1 << 20) && c > u) pick = lane * NE + e;
-    }
-    for (int off = 32; off > 0; off >>= 1) pick = min(pick, __shfl_xor(pick, off, 64));
+    const int pick = dec_draw<NE>(v, lane, u);
     return pick < Q ? pick : Q - 1;                 // (u above the rounded total: last entry)
 }
-// any Q up to WN_DEC_MAX_Q: the smallest power-of-two entry count per lane that covers it
-__device__ __forceinline__ int dec_choose_any(const float* logit, int Q, int lane, float* probs_dst, float inv_temp, bool sample, float u) {
-    if (Q <= 64) return dec_choose<1>(logit, Q, lane, probs_dst, inv_temp, sample, u);
-    if (Q <= 128) return dec_choose<2>(logit, Q, lane, probs_dst, inv_temp, sample, u);
-    if (Q <= 256) return dec_choose<4>(logit, Q, lane, probs_dst, inv_temp, sample, u);
-    if (Q <= 512) return dec_choose<8>(logit, Q, lane, probs_dst, inv_temp, sample, u);
-    return dec_choose<16>(logit, Q, lane, probs_dst, inv_temp, sample, u);
-}
-
-// Uniform number in [0,1) for (seed, global step, utterance): splitmix64 finaliser, 24 random bits.
+// Uniform number in [0,1) for (seed, global step, utterance or stream id): splitmix64 finaliser, 24 random bits.
 __device__ __forceinline__ float dec_uniform(unsigned long long seed, unsigned long long step, unsigned long long utt) {
     unsigned long long z = seed + 0x9E3779B97F4A7C15ull * (step + 1) + 0xD1B54A32D192ED03ull * (utt + 1);
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     z ^= z >> 31;
     return (float)(z >> 40) * (1.0f / 16777216.0f);
+}
+
+// ---- truncated sampling (top-k / nucleus) ----------------------------------------------------------------------------
+// Wave-wide reductions on DPP moves (row shifts within 16 lanes, then the two row broadcasts): six dependent VALU
+// instructions and one v_readlane, no trip through the LDS crossbar.  Masked-out lanes read 0, the identity of both
+// operations on the values used here (sums of non-negative floats, maxima of unsigned integers); lane 63 holds the total.
+// The tree is FIXED, so a sum over a subset of non-negative terms never exceeds the sum over a superset (every fp32 add is
+// monotone in its operands): the threshold search below relies on that.
+#define DEC_DPP(x, ctrl, rows, banks) __builtin_amdgcn_update_dpp(0, (x), (ctrl), (rows), (banks), false)
+__device__ __forceinline__ float dec_wave_sum(float x) {
+    x += __int_as_float(DEC_DPP(__float_as_int(x), 0x111, 0xf, 0xf));       // row_shr:1
+    x += __int_as_float(DEC_DPP(__float_as_int(x), 0x112, 0xf, 0xf));       // row_shr:2
+    x += __int_as_float(DEC_DPP(__float_as_int(x), 0x114, 0xf, 0xe));       // row_shr:4, banks 1 - 3
+    x += __int_as_float(DEC_DPP(__float_as_int(x), 0x118, 0xf, 0xc));       // row_shr:8, banks 2 - 3
+    x += __int_as_float(DEC_DPP(__float_as_int(x), 0x142, 0xa, 0xf));       // row_bcast:15 into rows 1 and 3
+    x += __int_as_float(DEC_DPP(__float_as_int(x), 0x143, 0xc, 0xf));       // row_bcast:31 into rows 2 and 3
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 63));
+}
+__device__ __forceinline__ unsigned dec_wave_umax(unsigned x) {
+    x = max(x, (unsigned)DEC_DPP((int)x, 0x111, 0xf, 0xf));
+    x = max(x, (unsigned)DEC_DPP((int)x, 0x112, 0xf, 0xf));
+    x = max(x, (unsigned)DEC_DPP((int)x, 0x114, 0xf, 0xe));
+    x = max(x, (unsigned)DEC_DPP((int)x, 0x118, 0xf, 0xc));
+    x = max(x, (unsigned)DEC_DPP((int)x, 0x142, 0xa, 0xf));
+    x = max(x, (unsigned)DEC_DPP((int)x, 0x143, 0xc, 0xf));
+    return (unsigned)__builtin_amdgcn_readlane((int)x, 63);
+}
+#undef DEC_DPP
+// order-preserving image of an fp32 value in the unsigned integers (a < b  <=>  key(a) < key(b); -0 is folded into +0 by
+// the caller): the kept sets are decided on these, exactly, never on rounded exponentials
+__device__ __forceinline__ unsigned dec_key(float x) {
+    const unsigned b = __float_as_uint(x);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+// dec_choose's sampled path with the distribution truncated first (same layout: one wave, NE entries per lane).
+//   top_k > 0 (the caller passes 0 unless 0 < top_k < Q): K = the entries >= the top_k-th largest logit, ties kept;
+//   p = exp((logit - max) * inv_temp) / sum over K;
+//   top_p < 1 (the caller passes 1 unless 0 < top_p < 1): N = the entries of K >= tau, tau the largest logit whose head
+//   mass sum_{K, logit >= tau} p reaches top_p, ties kept;
+//   r = p / sum over N goes to probs_dst (exact zeros outside N) and is drawn from by inverse CDF; when u lies above the
+//   rounded total the code is the LARGEST INDEX IN N.
+// Both thresholds are the result of a bitwise select on the keys, most significant bit first: "how many keys >= candidate"
+// is one v_cmp + s_bcnt1 per register (top-k: counts only), "how much mass" one DPP reduction per bit.  The top-p search
+// skips the leading bits the largest and the smallest kept key share and stops as soon as ONE key is left between the
+// bounds (it is tau), so distinct logits cost about a dozen reductions, not 32.
+template <int NE>
+__device__ __forceinline__ int dec_choose_trunc(const float* logit, int Q, int lane, float* probs_dst, float inv_temp, int top_k,
+                                                float top_p, float u) {
+    float v[NE], m = -INFINITY;
+    unsigned key[NE];
+    for (int e = 0; e < NE; ++e) {
+        const int i = lane * NE + e;
+        v[e] = i < Q ? logit[i] + 0.0f : -INFINITY;             // (+ 0: -0 becomes +0, one key per value)
+        key[e] = i < Q ? dec_key(v[e]) : 0u;                    // padding: below every real key (key(-inf) = 0x007fffff)
+        m = fmaxf(m, v[e]);
+    }
+    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+    // ---- top-k: the largest c with #{key >= c} >= top_k is the top_k-th largest key
+    unsigned thr = 0u;
+    int n_kept = Q;
+    if (top_k > 0) {
+        for (int bit = 31; bit >= 0; --bit) {
+            const unsigned cand = thr | (1u << bit);
+            int cnt = 0;
+            for (int e = 0; e < NE; ++e) cnt += __popcll(__ballot(key[e] >= cand));
+            if (cnt >= top_k) {
+                thr = cand; n_kept = cnt;
+                if (cnt == top_k) break;                        // exactly top_k keys above: the set is final
+            }
+        }
+    }
+    float part = 0.f;
+    for (int e = 0; e < NE; ++e) { v[e] = key[e] >= thr ? expf((v[e] - m) * inv_temp) : 0.f; part += v[e]; }
+    float s = dec_wave_sum(part);
+    // ---- top-p on the unnormalised masses: the largest c with mass{key >= c} >= top_p * s is tau's key
+    if (top_p < 1.0f) {
+        const float need = top_p * s;                           // (<= s, and the mass of all of K is s itself: some c qualifies)
+        unsigned lo = thr;
+        if (top_k <= 0) {                                       // smallest real key
+            unsigned inv = 0u;
+            for (int e = 0; e < NE; ++e) inv = max(inv, lane * NE + e < Q ? ~key[e] : 0u);
+            lo = ~dec_wave_umax(inv);
+        }
+        const unsigned hi = dec_key(m);
+        if (hi != lo) {
+            int bit = 31 - __clz((int)(hi ^ lo));               // first bit in which kept keys differ
+            unsigned pre = bit == 31 ? 0u : (hi >> (bit + 1)) << (bit + 1);
+            int c_lo = n_kept, c_hi = 0;                        // keys >= pre (kept ones), keys >= pre + 2^(bit+1)
+            for (; bit >= 0; --bit) {
+                const unsigned cand = pre | (1u << bit);
+                int cnt = 0;
+                float ms = 0.f;
+                for (int e = 0; e < NE; ++e) {
+                    const bool in = key[e] >= cand;
+                    cnt += __popcll(__ballot(in));
+                    ms += in ? v[e] : 0.f;
+                }
+                if (dec_wave_sum(ms) >= need) { pre = cand; c_lo = cnt; }
+                else c_hi = cnt;
+                if (c_lo - c_hi == 1) break;                    // one key in [pre, pre + 2^bit'): it is tau
+            }
+            if (pre > thr) thr = pre;
+            part = 0.f;
+            for (int e = 0; e < NE; ++e) { v[e] = key[e] >= thr ? v[e] : 0.f; part += v[e]; }
+            s = dec_wave_sum(part);
+        }
+    }
+    const float inv = 1.0f / s;
+    for (int e = 0; e < NE; ++e) {
+        const int i = lane * NE + e;
+        v[e] *= inv;
+        if (i < Q && probs_dst) probs_dst[i] = v[e];
+    }
+    const int pick = dec_draw<NE>(v, lane, u);
+    if (pick < Q) return pick;
+    unsigned last = 0u;                                         // u above the rounded total: the largest index in N
+    for (int e = 0; e < NE; ++e) { const int i = lane * NE + e; if (i < Q && key[e] >= thr) last = (unsigned)i; }
+    return (int)dec_wave_umax(last);
+}
+
+// One utterance's (one row's) sampling settings, read ONCE before the sample loop and kept in five scalar registers.
+struct DecSamp {
+    float inv_temp, top_p;                  // top_p == 1: nucleus filter off
+    int top_k;                              // -1: greedy (no draw at all), 0: top-k filter off
+    unsigned long long key;                 // seed + 0xD1B5.. * (stream + 1): the step-independent part of dec_uniform's counter
+    __device__ __forceinline__ bool sample() const { return top_k >= 0; }
+    __device__ __forceinline__ bool trunc() const { return top_k > 0 || top_p < 1.0f; }
+    // dec_uniform(seed, step, stream): the same 64-bit sum, associated differently
+    __device__ __forceinline__ float uniform(unsigned long long step) const { return top_k >= 0 ? dec_uniform(key, step, ~0ull) : 0.f; }
+};
+__device__ __forceinline__ float dec_sgpr(float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); }
+__device__ __forceinline__ int dec_sgpr(int x) { return __builtin_amdgcn_readfirstlane(x); }
+__device__ __forceinline__ unsigned long long dec_sgpr(unsigned long long x) {
+    return ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(x >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)x);
+}
+// `row` (wave-uniform) indexes the table; without a table the launch's scalars apply and `row` is the stream id
+__device__ __forceinline__ DecSamp dec_samp_of(const WnSampling* tab, size_t row, int Q, int sample, float inv_temp, int top_k,
+                                               float top_p, unsigned long long seed) {
+    DecSamp s;
+    if (tab) {
+        const WnSampling e = tab[row];
+        sample = e.temperature > 0.0f ? 1 : 0;
+        inv_temp = e.temperature > 0.0f ? 1.0f / e.temperature : 1.0f;
+        top_k = e.top_k; top_p = e.top_p; seed = e.seed; row = e.stream;
+    }
+    s.inv_temp = dec_sgpr(inv_temp);
+    s.top_k = dec_sgpr(!sample ? -1 : (top_k > 0 && top_k < Q ? top_k : 0));
+    s.top_p = dec_sgpr(sample && top_p > 0.0f && top_p < 1.0f ? top_p : 1.0f);
+    s.key = dec_sgpr(seed + 0xD1B54A32D192ED03ull * ((unsigned long long)row + 1));
+    return s;
+}
+__device__ __forceinline__ DecSamp dec_samp_of(const WnDecodeArgs& a, size_t utt, int Q) {
+    return dec_samp_of(a.samp, utt, Q, a.sample, a.inv_temp, a.top_k, a.top_p, a.seed);
+}
+// the code of one row: greedy / plain temperature exactly as before (dec_choose), truncated only when a filter is on
+template <int NE>
+__device__ __forceinline__ int dec_pick(const float* logit, int Q, int lane, float* probs_dst, const DecSamp& s, float u) {
+    if (s.trunc()) return dec_choose_trunc<NE>(logit, Q, lane, probs_dst, s.inv_temp, s.top_k, s.top_p, u);
+    return dec_choose<NE>(logit, Q, lane, probs_dst, s.inv_temp, s.sample(), u);
+}
+__device__ __forceinline__ int dec_pick_any(const float* logit, int Q, int lane, float* probs_dst, const DecSamp& s, float u) {
+    if (Q <= 64) return dec_pick<1>(logit, Q, lane, probs_dst, s, u);
+    if (Q <= 128) return dec_pick<2>(logit, Q, lane, probs_dst, s, u);
+    if (Q <= 256) return dec_pick<4>(logit, Q, lane, probs_dst, s, u);
+    if (Q <= 512) return dec_pick<8>(logit, Q, lane, probs_dst, s, u);
+    return dec_pick<16>(logit, Q, lane, probs_dst, s, u);
+}
+
+// The sampler alone: one wave per row of logits [n][Q] (row stride ld), four rows per workgroup.  Row i is "step" step0 + i
+// of stream samp[i].stream (no table: stream 0); u, when given, replaces the generated uniform numbers.
+__global__ __launch_bounds__(256) void sample_logits_k(const float* __restrict__ logits, long n, int Q, long ld, const WnSampling* __restrict__ samp,
+                                                       int sample, float inv_temp, unsigned long long seed, int top_k, float top_p, long step0,
+                                                       const float* __restrict__ u, int32_t* __restrict__ codes, float* __restrict__ probs) {
+    const int lane = threadIdx.x & 63;
+    const long row = (long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (row >= n) return;
+    const DecSamp s = dec_samp_of(samp, samp ? (size_t)row : 0, Q, sample, inv_temp, top_k, top_p, seed);
+    const float ur = u ? u[row] : s.uniform((unsigned long long)(step0 + row));
+    const int bi = dec_pick_any(logits + row * ld, Q, lane, probs ? probs + row * (long)Q : nullptr, s, ur);
+    if (lane == 0) codes[row] = bi;
+}
+int wn_launch_sample_logits(const float* logits, long n, int Q, long ld, const WnSampling* samp, float temperature,
+                            unsigned long long seed, int top_k, float top_p, long step0, const float* u, int32_t* codes,
+                            float* probs, hipStream_t st) {
+    if (n <= 0) return 0;
+    const long blocks = (n + 3) / 4;
+    if (blocks > 0x7fffffffL) return wn_set_error_msg(-4, "wn_sample_logits: 'n' is too many rows for one launch");
+    hipLaunchKernelGGL(sample_logits_k, dim3((unsigned)blocks), dim3(256), 0, st, logits, n, Q, ld, samp, temperature > 0.0f ? 1 : 0,
+                       temperature > 0.0f ? 1.0f / temperature : 1.0f, seed, top_k, top_p, step0, u, codes, probs);
+    WN_CHECK_LAUNCH();
+    return 0;
 }
 
 // filter width k = a.fw >= 1: the causal layer reads the k - 1 previous input columns and the current one; block i reads
@@ -151,6 +340,7 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_k(WnDecodeArgs a) {
     __shared__ int s_arg;
     const int tid = threadIdx.x;
 
+    const DecSamp smp = dec_samp_of(a, utt, a.Q);               // this utterance's sampling settings, in scalar registers
     for (int i = tid; i < a.Q; i += DEC_THREADS) note[i] = u_note0[i];
     for (int i = tid; i < K1 * a.Q; i += DEC_THREADS) prev[i] = u_prev0[i];
     __syncthreads();
@@ -205,9 +395,9 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_k(WnDecodeArgs a) {
         __syncthreads();
         // softmax over the Q logits and first-index argmax of the PROBABILITIES, wave 0
         if (tid < 64) {
-            const float ur = a.sample ? dec_uniform(a.seed, (unsigned long long)(a.step0 + step), utt) : 0.f;
-            const int bi = (FW == 2 && a.Q == 256) ? dec_choose<4>(logit, 256, tid, u_probs_out ? u_probs_out + (size_t)step * a.Q : nullptr, a.inv_temp, a.sample != 0, ur)
-                                                   : dec_choose_any(logit, a.Q, tid, u_probs_out ? u_probs_out + (size_t)step * a.Q : nullptr, a.inv_temp, a.sample != 0, ur);
+            const float ur = smp.uniform((unsigned long long)(a.step0 + step));
+            const int bi = (FW == 2 && a.Q == 256) ? dec_pick<4>(logit, 256, tid, u_probs_out ? u_probs_out + (size_t)step * a.Q : nullptr, smp, ur)
+                                                   : dec_pick_any(logit, a.Q, tid, u_probs_out ? u_probs_out + (size_t)step * a.Q : nullptr, smp, ur);
             if (tid == 0) { s_arg = bi; u_codes_out[step] = bi; }
         }
         __syncthreads();
@@ -791,6 +981,9 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
                 }
             }
         };
+        // sampling settings of the two utterances this wave chooses for (2w, 2w + 1), read once, in scalar registers
+        const int wv = __builtin_amdgcn_readfirstlane(w);
+        const DecSamp smp0 = dec_samp_of(a, ux(2 * wv), Q), smp1 = dec_samp_of(a, ux(2 * wv + 1), Q);
         const unsigned long long* const zmine = zg_of(tid >> 5) + (tid & 31) * 2;       // this thread's two granules of block 0
         unsigned long long* const errp = cg_of(tid >> 5) + 1;
         unsigned long long pa = 0, pb = 0;                                               // prefetched pair (tag 0 = nothing yet)
@@ -873,9 +1066,10 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
                 for (int e = 0; e < 2; ++e) {          // wave w chooses for utterances 2w and 2w + 1
                     const int uu = 2 * w + e;
                     const size_t ug = ux(uu);
-                    const float ur = a.sample ? dec_uniform(a.seed, (unsigned long long)(a.step0 + step), ug) : 0.f;
+                    const DecSamp& sp = e ? smp1 : smp0;
+                    const float ur = sp.uniform((unsigned long long)(a.step0 + step));
                     float* pdst = a.probs_out ? a.probs_out + (ug * (size_t)a.n_steps + step) * Q : nullptr;
-                    const int bi = dec_choose<4>(logit + uu * Q, Q, lane, pdst, a.inv_temp, a.sample != 0, ur);
+                    const int bi = dec_pick<4>(logit + uu * Q, Q, lane, pdst, sp, ur);
                     if (lane == 0) {
                         a.codes_out[ug * a.n_steps + step] = bi;
                         __hip_atomic_store(cg_of(uu), dec_pack((float)bi, tag), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -945,6 +1139,9 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
                 }
             }
         };
+        // sampling settings of the two utterances this wave chooses for (2w, 2w + 1), read once, in scalar registers
+        const int wv = __builtin_amdgcn_readfirstlane(w);
+        const DecSamp smp0 = dec_samp_of(a, ux(2 * wv), Q), smp1 = dec_samp_of(a, ux(2 * wv + 1), Q);
         const unsigned long long* const zmine = zg_of(tid >> 5) + (tid & 31) * 2;       // this thread's two granules of block 0
         unsigned long long pa = 0, pb = 0;                                               // prefetched pair (tag 0 = nothing yet)
         for (int step = 0; step < a.n_steps; ++step) {
@@ -1020,9 +1217,10 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
             for (int e = 0; e < 2; ++e) {          // wave w chooses for utterances 2w and 2w + 1
                 const int uu = 2 * w + e;
                 const size_t ug = ux(uu);
-                const float ur = a.sample ? dec_uniform(a.seed, (unsigned long long)(a.step0 + step), ug) : 0.f;
+                const DecSamp& sp = e ? smp1 : smp0;
+                const float ur = sp.uniform((unsigned long long)(a.step0 + step));
                 float* pdst = a.probs_out ? a.probs_out + (ug * (size_t)a.n_steps + step) * Q : nullptr;
-                const int bi = dec_choose<4>(logit + uu * Q, Q, lane, pdst, a.inv_temp, a.sample != 0, ur);
+                const int bi = dec_pick<4>(logit + uu * Q, Q, lane, pdst, sp, ur);
                 if (lane == 0) {
                     a.codes_out[ug * a.n_steps + step] = bi;
                     __hip_atomic_store(cg_of(uu), dec_pack((float)bi, tag), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -242,6 +242,9 @@ int wn_launch_softmaxq_ce(const float* x, const int64_t* target, float* probs, f
                           float inv_n, hipStream_t st);
 
 #define WN_DEC_MAX_LAYERS 64
+// one utterance's (or one row's) sampling settings: the layout of wn_sampling (include/wavenet_hip.h), 24 bytes
+struct WnSampling { float temperature; float top_p; int32_t top_k; uint32_t stream; uint64_t seed; };
+static_assert(sizeof(WnSampling) == 24, "wn_sampling is 24 bytes");
 struct WnDecodeArgs {
     int n_layers, R, D, S, Q;
     int dil[WN_DEC_MAX_LAYERS];
@@ -280,6 +283,10 @@ struct WnDecodeArgs {
     const float* cond_p1; long cond_p1_ustride;          // [n_utt][le][S], added to post_process_1's output before its relu
     int c_shift[WN_DEC_MAX_LAYERS + 1], c_q[WN_DEC_MAX_LAYERS + 1];      // blocks 0 .. n_layers-1, then post-processing at [n_layers]
     int le; long pos0;
+    // truncated sampling (wn_decode_batch_samp): top_k in (0, Q) keeps the k largest logits (ties kept), top_p in (0, 1) the
+    // smallest head of the sorted distribution whose mass reaches it; samp != null: utterance u takes ALL its settings
+    // (temperature, filters, seed, random-number stream id) from samp[u] and the scalars above are ignored
+    const WnSampling* samp; int top_k; float top_p;
 };
 // column of a conditioning table for output column c (see WnDecodeArgs::c_shift)
 __host__ __device__ inline int wn_dec_cond_idx(int c, int q, int le) {
@@ -291,6 +298,10 @@ int wn_launch_decode(const WnDecodeArgs& a, hipStream_t st);
 size_t dec_k_lds_bytes(const WnDecodeArgs& a);            // dynamic LDS of the fp32 decode kernel (decode_k)
 #define WN_DEC_MAX_Q 1024                                  // quantisation channels the fp32 decode kernel's sampler covers
 long wn_decode_granules(int n_layers, int D, int S);      // 8-byte granules of one utterance's hand-off area (matrix-core kernels)
+// the decoder's sampler on an arbitrary [n][Q] logits matrix (row stride ld), one wave per row: row i is step step0 + i
+int wn_launch_sample_logits(const float* logits, long n, int Q, long ld, const WnSampling* samp, float temperature,
+                            unsigned long long seed, int top_k, float top_p, long step0, const float* u, int32_t* codes,
+                            float* probs, hipStream_t st);
 
 // wn_coll.hip
 int wn_coll_loaded();

@@ -239,9 +239,76 @@ class DecodeState(OrderedDict):
         return DecodeState(eng, rings.contiguous(), prev, 0)
 
 
-def _decode(net, state, note0, n_steps, forced=None, want_probs=False, correct_queue=False, temperature=None, seed=0):
+class _Sampling:
+    """The sampling arguments of one decode launch of U utterances (or of ``sample_logits`` over U rows).  ``temperature``,
+    ``top_k``, ``top_p`` and ``seed`` may each be a scalar or a length-U sequence / tensor; ``streams`` are the random-number
+    stream ids (default ``arange(U)``: the utterance index, today's key).  Scalars travel as the entry point's scalar
+    arguments; the device table of ``wn_sampling`` entries is built only when something is per-utterance.
+    ``plain``: nothing here needs ``wn_decode_batch_samp`` (no filter, no table)."""
+
+    def __init__(self, U, temperature, top_k, top_p, seed, streams, dev, default_stream=None):
+        def seq(v):
+            if isinstance(v, torch.Tensor):
+                v = v.detach().cpu().tolist()
+            if isinstance(v, np.ndarray):
+                v = v.tolist()
+            if isinstance(v, (list, tuple)):
+                if len(v) != U:
+                    raise ValueError("per-utterance sampling settings must have one entry per utterance (%d), got %d" % (U, len(v)))
+                return list(v)
+            return None
+        per = {"temperature": seq(temperature), "top_k": seq(top_k), "top_p": seq(top_p), "seed": seq(seed)}
+        st = seq(streams)
+        if streams is not None and st is None:
+            raise ValueError("streams must be a sequence of one stream id per utterance")
+        if st is not None and default_stream is None and [int(v) for v in st] == list(range(U)):
+            st = None                                     # the default key
+        val = lambda name, v: per[name] if per[name] is not None else [v] * U
+        T = [0.0 if t is None else float(t) for t in val("temperature", temperature)]
+        K = [0 if k is None else int(k) for k in val("top_k", top_k)]
+        P = [1.0 if q is None else float(q) for q in val("top_p", top_p)]
+        for k in K:
+            if k < 0:
+                raise ValueError("top_k must be >= 0 (0 / None: no top-k filter), got %d" % k)
+        for q in P:
+            if not (0.0 < q <= 1.0):
+                raise ValueError("top_p must lie in (0, 1] (1 / None: no nucleus filter), got %r" % (q,))
+        self.table = None
+        if st is not None or any(v is not None for v in per.values()):
+            sd = [int(v) for v in val("seed", seed)]
+            if st is None:
+                st = [default_stream] * U if default_stream is not None else list(range(U))
+            tab = np.zeros(U, dtype=np.dtype([("temperature", "<f4"), ("top_p", "<f4"), ("top_k", "<i4"), ("stream", "<u4"), ("seed", "<u8")]))
+            assert tab.dtype.itemsize == ctypes.sizeof(_lib.Sampling)
+            tab["temperature"], tab["top_p"], tab["top_k"], tab["stream"] = T, P, K, [int(v) for v in st]
+            tab["seed"] = [v & 0xFFFFFFFFFFFFFFFF for v in sd]
+            self.table = torch.from_numpy(tab.view(np.uint8).copy()).to(dev)
+            self.temperature, self.top_k, self.top_p, self.seed = 0.0, 0, 1.0, 0
+        else:
+            self.temperature, self.top_k, self.top_p, self.seed = T[0] if T[0] > 0 else 0.0, K[0], P[0], int(seed)
+        self.filtered = any(k > 0 for k in K) or any(q < 1.0 for q in P)
+        self.plain = self.table is None and not self.filtered
+
+    def tail(self):
+        """The arguments wn_decode_batch_samp takes behind wn_decode_batch_cond's (before the stream)."""
+        return ptr(self.table), int(self.top_k), float(self.top_p)
+
+
+_NO_COND = (None, 0, None, 0, None, None, 1, 0)       # wn_decode_batch_cond's table arguments of an unconditioned launch
+
+
+def _need_corrected(smp, correct_queue):
+    if not smp.plain and not correct_queue:
+        raise ValueError("top_k / top_p and per-utterance sampling settings run on the corrected recurrence only "
+                         "(wn_decode_batch_samp): pass correct_queue=True")
+
+
+def _decode(net, state, note0, n_steps, forced=None, want_probs=False, correct_queue=False, temperature=None, seed=0,
+            top_k=None, top_p=None):
     eng = state.eng
     _check_recurrence(eng, correct_queue)
+    smp = _Sampling(1, temperature, top_k, top_p, seed, None, eng.device)
+    _need_corrected(smp, correct_queue)
     pack = getattr(net, "_decode_pack", None)
     if pack is None or pack.eng is not eng:
         pack = net._decode_pack = _DecodePack(eng)
@@ -264,13 +331,17 @@ def _decode(net, state, note0, n_steps, forced=None, want_probs=False, correct_q
     bias = pack.o_bias is not None
     pk = pack.chain()
     qbuf = _queue_buffer(state.rings)
-    call("wn_decode_batch_fw", pack.k, eng.N, pack.Rp, pack.Dp, eng.S, eng.Q, ctypes.cast(dil, ctypes.c_void_p),
-         ctypes.cast(qoff, ctypes.c_void_p), ptr(qbuf), pack.p(pack.o_causal), pack.p(pack.ob_causal) if bias else None,
-         pack.p(pack.o_layers), pack.layer_stride, pack.p(pack.ob_layers) if bias else None,
-         pack.p(pack.o_p1), pack.p(pack.ob_p1) if bias else None, pack.p(pack.o_p2), pack.p(pack.ob_p2) if bias else None,
-         ptr(note0), _ptr_or_none(state.prev), ptr(note_out), _ptr_or_none(prev_out), ptr(forced_t), ptr(codes), ptr(probs),
-         state.steps, n_steps, 1 if correct_queue else 0, ptr(sync), 1, 0,
-         float(temperature) if temperature else 0.0, int(seed), pk[0], pk[1], pk[2], pk[3], pk[4], pk[5], pk[6], _lib.stream())
+    args = (pack.k, eng.N, pack.Rp, pack.Dp, eng.S, eng.Q, ctypes.cast(dil, ctypes.c_void_p),
+            ctypes.cast(qoff, ctypes.c_void_p), ptr(qbuf), pack.p(pack.o_causal), pack.p(pack.ob_causal) if bias else None,
+            pack.p(pack.o_layers), pack.layer_stride, pack.p(pack.ob_layers) if bias else None,
+            pack.p(pack.o_p1), pack.p(pack.ob_p1) if bias else None, pack.p(pack.o_p2), pack.p(pack.ob_p2) if bias else None,
+            ptr(note0), _ptr_or_none(state.prev), ptr(note_out), _ptr_or_none(prev_out), ptr(forced_t), ptr(codes), ptr(probs),
+            state.steps, n_steps, 1 if correct_queue else 0, ptr(sync), 1, 0,
+            smp.temperature, smp.seed, pk[0], pk[1], pk[2], pk[3], pk[4], pk[5], pk[6])
+    if smp.plain:
+        call("wn_decode_batch_fw", *args, _lib.stream())
+    else:
+        call("wn_decode_batch_samp", *args, *_NO_COND, *smp.tail(), _lib.stream())
     if n_steps >= 4 and int(sync[-1].item()) != 0:
         raise _lib.WavenetHipError("wn_decode: a hand-off between the two decode workgroups timed out")
     state.prev = prev_out
@@ -307,27 +378,35 @@ def predict_next(net, note, state_queue=None, correct_queue=False):
     return codes.to(torch.int64).to(note.device), state_queue
 
 
-def generate_codes(net, start_piece, note_num, correct_queue=False, temperature=None, seed=0):
+def generate_codes(net, start_piece, note_num, correct_queue=False, temperature=None, seed=0, top_k=None, top_p=None):
     """The greedy loop of fast_generate.py:162-172 as one init forward + ONE persistent launch.
     Returns the note_num generated codes (int64, on the device).
     ``temperature`` (the reference is greedy only): if given and > 0, every code after the
-    first is SAMPLED from softmax(logits / temperature), reproducibly for a given ``seed``."""
+    first is SAMPLED from softmax(logits / temperature), reproducibly for a given ``seed``.
+    ``top_k`` / ``top_p``: the distribution is truncated first (include/wavenet_hip.h, wn_decode_batch_samp: the top_k largest
+    logits, then the smallest head whose mass reaches top_p, ties kept); corrected recurrence only."""
     with torch.no_grad():
         first, state = predict_next(net, start_piece, None)
     if note_num <= 1:
         return first.to(state.eng.device)[:note_num]
     note0 = torch.zeros(net.quantization_channels, dtype=torch.float32, device=state.eng.device)
     note0[int(first[0])] = 1.0
-    codes, _, _ = _decode(net, state, note0, note_num - 1, correct_queue=correct_queue, temperature=temperature, seed=seed)
+    codes, _, _ = _decode(net, state, note0, note_num - 1, correct_queue=correct_queue, temperature=temperature, seed=seed,
+                          top_k=top_k, top_p=top_p)
     return torch.cat([first.to(codes.device).to(torch.int64), codes.to(torch.int64)])
 
 
-def generate_codes_batch(net, start_pieces, note_num, correct_queue=False, temperature=None, seed=0):
+def generate_codes_batch(net, start_pieces, note_num, correct_queue=False, temperature=None, seed=0, top_k=None, top_p=None,
+                         streams=None):
     """SURVEY 8f2 (batched utterances; the reference generates one at a time): greedy generation of
     ``note_num`` codes for U independent start pieces ``(U, Q, receptive_field)`` in ONE persistent
     launch - on the matrix-core path eight utterances to a workgroup pair, one pair of MFMA result columns each (else one
     pair per utterance), the weights are shared.  Returns int64
-    ``(U, note_num)`` on the device; row u equals ``generate_codes(net, start_pieces[u:u+1], note_num)``."""
+    ``(U, note_num)`` on the device; row u equals ``generate_codes(net, start_pieces[u:u+1], note_num)``.
+    ``temperature``, ``top_k``, ``top_p`` and ``seed`` may each be a scalar or one value per utterance (a sweep of settings
+    over one prompt, N takes of one prompt); ``streams``: the random-number stream id of every utterance (default: its
+    index; row u is then the single-utterance launch with ``streams=[u]``, bit for bit when both run the same kernel form,
+    see WN_DEC_KS).  Truncation and per-utterance settings run on the corrected recurrence only."""
     assert start_pieces.dim() == 3 and start_pieces.size(2) == net.receptive_field
     U = start_pieces.size(0)
     if U > 1024:
@@ -348,6 +427,8 @@ def generate_codes_batch(net, start_pieces, note_num, correct_queue=False, tempe
     if note_num <= 1:
         return first.view(U, 1)[:, :note_num]
     _check_recurrence(eng, correct_queue)
+    smp = _Sampling(U, temperature, top_k, top_p, seed, streams, dev)
+    _need_corrected(smp, correct_queue)
     pack = getattr(net, "_decode_pack", None)
     if pack is None or pack.eng is not eng:
         pack = net._decode_pack = _DecodePack(eng)
@@ -366,13 +447,17 @@ def generate_codes_batch(net, start_pieces, note_num, correct_queue=False, tempe
     bias = pack.o_bias is not None
     pk = pack.chain()
     qbuf = _queue_buffer(rings)
-    call("wn_decode_batch_fw", pack.k, N, pack.Rp, pack.Dp, eng.S, Q, ctypes.cast(dil, ctypes.c_void_p),
-         ctypes.cast(qoff, ctypes.c_void_p), ptr(qbuf), pack.p(pack.o_causal), pack.p(pack.ob_causal) if bias else None,
-         pack.p(pack.o_layers), pack.layer_stride, pack.p(pack.ob_layers) if bias else None,
-         pack.p(pack.o_p1), pack.p(pack.ob_p1) if bias else None, pack.p(pack.o_p2), pack.p(pack.ob_p2) if bias else None,
-         ptr(note0), _ptr_or_none(prev0), ptr(note_out), _ptr_or_none(prev_out), None, ptr(codes), None,
-         0, n_steps, 1 if correct_queue else 0, ptr(sync), U, rings.size(1),
-         float(temperature) if temperature else 0.0, int(seed), pk[0], pk[1], pk[2], pk[3], pk[4], pk[5], pk[6], _lib.stream())
+    args = (pack.k, N, pack.Rp, pack.Dp, eng.S, Q, ctypes.cast(dil, ctypes.c_void_p),
+            ctypes.cast(qoff, ctypes.c_void_p), ptr(qbuf), pack.p(pack.o_causal), pack.p(pack.ob_causal) if bias else None,
+            pack.p(pack.o_layers), pack.layer_stride, pack.p(pack.ob_layers) if bias else None,
+            pack.p(pack.o_p1), pack.p(pack.ob_p1) if bias else None, pack.p(pack.o_p2), pack.p(pack.ob_p2) if bias else None,
+            ptr(note0), _ptr_or_none(prev0), ptr(note_out), _ptr_or_none(prev_out), None, ptr(codes), None,
+            0, n_steps, 1 if correct_queue else 0, ptr(sync), U, rings.size(1),
+            smp.temperature, smp.seed, pk[0], pk[1], pk[2], pk[3], pk[4], pk[5], pk[6])
+    if smp.plain:
+        call("wn_decode_batch_fw", *args, _lib.stream())
+    else:
+        call("wn_decode_batch_samp", *args, *_NO_COND, *smp.tail(), _lib.stream())
     if n_steps >= 4:
         flags = sync.view(U, -1)[:, -1]
         if int(flags.abs().max().item()) != 0:
@@ -384,12 +469,14 @@ last_error_flags = None        # the error flag word of every utterance of the l
 
 
 def decode_batch_cond(net, rings, prev0, note0, n_steps, step0=0, pos0=0, forced=None, want_probs=False, temperature=None,
-                      seed=0, cond_fg=None, cond_p1=None, schedule=None):
+                      seed=0, cond_fg=None, cond_p1=None, schedule=None, top_k=None, top_p=None, streams=None):
     """One persistent launch of wn_decode_batch_cond (corrected recurrence) for U utterances from explicit state: ``rings``
     (U, ring floats) is advanced in place, ``prev0`` (U, k-1, Q) / ``note0`` (U, Q) are the causal layer's history and the
     first input column.  ``cond_fg`` (U, N, Le, 2 Dp) rows [f | g] and ``cond_p1`` (U, Le, S) are the per-utterance
     conditioning tables (Dp = the decode pack's dilation width), ``schedule`` the N + 1 (shift, q, Le) triples of
     ``ae_generate.cond_schedule``; step s is output position pos0 + s.  ``forced`` (U, n_steps): the next input codes.
+    ``temperature`` / ``top_k`` / ``top_p`` / ``seed``: scalars or one value per utterance, ``streams`` the random-number stream
+    ids (default: the utterance index); anything beyond a scalar temperature and seed goes through wn_decode_batch_samp.
     Returns (codes int32 (U, n_steps), probabilities (U, n_steps, Q) or None, note_out, prev_out)."""
     eng = net._engine_for(rings.device)
     pack = getattr(net, "_decode_pack", None)
@@ -403,6 +490,7 @@ def decode_batch_cond(net, rings, prev0, note0, n_steps, step0=0, pos0=0, forced
         raise ValueError("decode_batch_cond: rings must be (U, %d) contiguous floats" % max(1, sum(K1 * d * rw for d in eng.dil)))
     if U > (1024 if pack.mfma else 128):
         raise ValueError("at most 1024 utterances per launch (128 off the matrix-core path)")
+    smp = _Sampling(U, temperature, top_k, top_p, seed, streams, dev)
     le = 1
     shift = qs = None
     if cond_fg is not None or cond_p1 is not None:
@@ -426,16 +514,20 @@ def decode_batch_cond(net, rings, prev0, note0, n_steps, step0=0, pos0=0, forced
     qoff = (ctypes.c_int64 * N)(*[int(v) for v in q_off])
     bias = pack.o_bias is not None
     pk = pack.chain()
-    call("wn_decode_batch_cond", pack.k, N, pack.Rp, pack.Dp, eng.S, Q, ctypes.cast(dil, ctypes.c_void_p),
-         ctypes.cast(qoff, ctypes.c_void_p), ptr(rings), pack.p(pack.o_causal), pack.p(pack.ob_causal) if bias else None,
-         pack.p(pack.o_layers), pack.layer_stride, pack.p(pack.ob_layers) if bias else None,
-         pack.p(pack.o_p1), pack.p(pack.ob_p1) if bias else None, pack.p(pack.o_p2), pack.p(pack.ob_p2) if bias else None,
-         ptr(note0), _ptr_or_none(prev0), ptr(note_out), _ptr_or_none(prev_out), ptr(forced_t), ptr(codes), ptr(probs),
-         step0, n_steps, 1, ptr(sync), U, rings.size(1), float(temperature) if temperature else 0.0, int(seed),
-         pk[0], pk[1], pk[2], pk[3], pk[4], pk[5], pk[6],
-         ptr(cond_fg), cond_fg[0].numel() if cond_fg is not None else 0, ptr(cond_p1), cond_p1[0].numel() if cond_p1 is not None else 0,
-         ctypes.cast(shift, ctypes.c_void_p) if shift is not None else None, ctypes.cast(qs, ctypes.c_void_p) if qs is not None else None,
-         le, int(pos0), _lib.stream())
+    args = (pack.k, N, pack.Rp, pack.Dp, eng.S, Q, ctypes.cast(dil, ctypes.c_void_p),
+            ctypes.cast(qoff, ctypes.c_void_p), ptr(rings), pack.p(pack.o_causal), pack.p(pack.ob_causal) if bias else None,
+            pack.p(pack.o_layers), pack.layer_stride, pack.p(pack.ob_layers) if bias else None,
+            pack.p(pack.o_p1), pack.p(pack.ob_p1) if bias else None, pack.p(pack.o_p2), pack.p(pack.ob_p2) if bias else None,
+            ptr(note0), _ptr_or_none(prev0), ptr(note_out), _ptr_or_none(prev_out), ptr(forced_t), ptr(codes), ptr(probs),
+            step0, n_steps, 1, ptr(sync), U, rings.size(1), smp.temperature, smp.seed,
+            pk[0], pk[1], pk[2], pk[3], pk[4], pk[5], pk[6],
+            ptr(cond_fg), cond_fg[0].numel() if cond_fg is not None else 0, ptr(cond_p1), cond_p1[0].numel() if cond_p1 is not None else 0,
+            ctypes.cast(shift, ctypes.c_void_p) if shift is not None else None, ctypes.cast(qs, ctypes.c_void_p) if qs is not None else None,
+            le, int(pos0))
+    if smp.plain:
+        call("wn_decode_batch_cond", *args, _lib.stream())
+    else:
+        call("wn_decode_batch_samp", *args, *smp.tail(), _lib.stream())
     global last_error_flags
     flags = last_error_flags = sync.view(U, -1)[:, -1]      # the error flag word of every utterance
     if int(flags.abs().max().item()) != 0:
@@ -443,8 +535,38 @@ def decode_batch_cond(net, rings, prev0, note0, n_steps, step0=0, pos0=0, forced
     return codes, probs, note_out, prev_out
 
 
-def generate(model_path, model_name, generate_path, generate_name, start_piece=None, sr=16000, duration=10):
-    """wavenet/fast_generate.py:144-179."""
+def sample_logits(logits, temperature=1.0, top_k=None, top_p=None, seed=0, step0=0, u=None, want_probs=False, streams=None):
+    """The decoder's sampler (the same device function, wn_sample_logits) on a matrix of pre-softmax logits ``(n, Q)``,
+    Q <= 1024: row i is drawn as "step" ``step0 + i``.  ``temperature`` (<= 0 / None: greedy argmax), ``top_k``, ``top_p`` and
+    ``seed`` may each be a scalar or one value per row (``streams``: the rows' random-number stream ids, default 0);
+    ``u`` (n,) replaces the generated uniform numbers.  Returns the codes (int64, on the device), with ``want_probs`` also the
+    distributions drawn from ``(n, Q)``.  This is what a one-forward-per-sample generator calls on the forward's logits."""
+    if logits.dim() != 2 or not logits.is_cuda:
+        raise ValueError("sample_logits: logits must be a (n, Q) device tensor")
+    x = logits.detach().float()
+    if x.size(1) > 0 and x.stride(1) != 1:
+        x = x.contiguous()
+    n, Q = x.shape
+    if not 1 <= Q <= 1024:
+        raise ValueError("sample_logits: 1 <= Q <= 1024")
+    smp = _Sampling(n, temperature, top_k, top_p, seed, streams, x.device, default_stream=0)
+    u_t = None
+    if u is not None:
+        u_t = torch.as_tensor(u, dtype=torch.float32).to(x.device).contiguous()
+        if tuple(u_t.shape) != (n,):
+            raise ValueError("sample_logits: u must hold one number per row")
+    codes = torch.empty(n, dtype=torch.int32, device=x.device)
+    probs = torch.empty(n, Q, dtype=torch.float32, device=x.device) if want_probs else None
+    call("wn_sample_logits", ptr(x), n, Q, x.stride(0) if n > 1 else max(Q, x.stride(0)), ptr(smp.table), smp.temperature, smp.seed,
+         int(smp.top_k), float(smp.top_p), int(step0), ptr(u_t), ptr(codes), ptr(probs), _lib.stream())
+    codes = codes.to(torch.int64)
+    return (codes, probs) if want_probs else codes
+
+
+def generate(model_path, model_name, generate_path, generate_name, start_piece=None, sr=16000, duration=10, temperature=None,
+             seed=0, top_k=None, top_p=None):
+    """wavenet/fast_generate.py:144-179.  ``temperature`` / ``top_k`` / ``top_p`` / ``seed``: sample instead of the greedy
+    argmax; a filter selects the corrected queue recurrence (the only one truncated sampling runs on)."""
     if os.path.exists(generate_path) is False:
         os.makedirs(generate_path)
     with open('./params/wavenet_params.json', 'r') as f:
@@ -459,7 +581,9 @@ def generate(model_path, model_name, generate_path, generate_name, start_piece=N
         start_piece = torch.zeros(1, Q, net.receptive_field)
         start_piece[:, Q // 2, :] = 1.0
     # the as-written queue push exists for filter_width 2 only; every other width runs the corrected recurrence
-    generated_piece = generate_codes(net, start_piece.cuda(), duration * sr, correct_queue=net.filter_width != 2)
+    generated_piece = generate_codes(net, start_piece.cuda(), duration * sr,
+                                     correct_queue=net.filter_width != 2 or top_k is not None or top_p is not None,
+                                     temperature=temperature, seed=seed, top_k=top_k, top_p=top_p)
     print(generated_piece.tolist()[:32], "...")
     audio = mu_law_decode(generated_piece, net.quantization_channels).cpu().numpy()
     from scipy.io import wavfile

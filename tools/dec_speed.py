@@ -4,7 +4,9 @@ batches, as bench.py's extra.c5_decode measures it; honours the WN_DEC_* switche
 autoencoder's cached decoder is one).  `--filter-width K`: the same shape with K taps (K != 2 runs the corrected queue
 recurrence, the only one defined there).  `--cond-frames N`: the same decoder CONDITIONED (wn_decode_batch_cond) on per-utterance
 tables of N frames with the schedule of a 16000-sample clip (config 4: N = 25), biased, corrected recurrence, from zero queues -
-to be compared with `--bias` (the unconditioned biased decoder of the same shape)."""
+to be compared with `--bias` (the unconditioned biased decoder of the same shape).
+`--temperature T`: sample instead of the greedy argmax; `--top-k K` / `--top-p P`: truncate the distribution first
+(wn_decode_batch_samp; corrected recurrence, temperature 1 unless given); `--runs N`: repeat the whole measurement."""
 import os
 import sys
 import time
@@ -22,6 +24,21 @@ def filter_width():
 
 def cond_frames():
     return int(sys.argv[sys.argv.index("--cond-frames") + 1]) if "--cond-frames" in sys.argv else 0
+
+
+def _opt(name, conv, default=None):
+    return conv(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default
+
+
+def sampling():
+    """generate_codes' sampling arguments from the command line, and whether they need the corrected recurrence"""
+    top_k, top_p = _opt("--top-k", int), _opt("--top-p", float)
+    filtered = top_k is not None or top_p is not None
+    T = _opt("--temperature", float, 1.0 if filtered else None)
+    kw = dict(temperature=T, seed=1)
+    if filtered:
+        kw.update(top_k=top_k, top_p=top_p)
+    return kw, filtered
 
 
 def main_cond(le):
@@ -67,23 +84,28 @@ def main():
     start = torch.zeros(1, 256, net.receptive_field, device=dev)
     start[0, 128, :] = 1.0
     n = 16000
-    for rep in range(2):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        seq = fg.generate_codes(net, start, n, correct_queue=k != 2)
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
-    print("one stream: %d samples in %.3f s = %.1f k samples/s (%d distinct codes)" % (n, dt, n / dt / 1e3, int(torch.unique(seq).numel())))
-    for U in ((128, 1024) if fg._mfma_decode(net._engine) else (128,)):          # (the fp32 kernel: at most 128 per launch)
-        st = torch.zeros(U, 256, net.receptive_field, device=dev)
-        for uu in range(U):
-            st[uu, (128 + uu) % 256, :] = 1.0
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        out = fg.generate_codes_batch(net, st, 2001, correct_queue=k != 2)
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
-        print("%d utterances x 2000 samples: %.3f s = %.2f M samples/s" % (U, dt, U * 2000 / dt / 1e6))
+    kw, filtered = sampling()
+    correct = k != 2 or filtered
+    what = ", ".join("%s %s" % kv for kv in kw.items() if kv[1] is not None and kv[0] != "seed") or "greedy"
+    for run in range(_opt("--runs", int, 1)):
+        for rep in range(2):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            seq = fg.generate_codes(net, start, n, correct_queue=correct, **kw)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+        print("one stream (%s): %d samples in %.3f s = %.1f k samples/s = %.2f us per sample (%d distinct codes)"
+              % (what, n, dt, n / dt / 1e3, dt / n * 1e6, int(torch.unique(seq).numel())))
+        for U in ((128, 1024) if fg._mfma_decode(net._engine) else (128,)):          # (the fp32 kernel: at most 128 per launch)
+            st = torch.zeros(U, 256, net.receptive_field, device=dev)
+            for uu in range(U):
+                st[uu, (128 + uu) % 256, :] = 1.0
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = fg.generate_codes_batch(net, st, 2001, correct_queue=correct, **kw)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            print("%d utterances x 2000 samples (%s): %.3f s = %.2f M samples/s" % (U, what, dt, U * 2000 / dt / 1e6))
 
 
 if __name__ == "__main__":
