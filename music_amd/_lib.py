@@ -18,6 +18,12 @@ _p = ctypes.c_void_p
 _i = ctypes.c_int
 _l = ctypes.c_int64
 _f = ctypes.c_float
+# the decode entries share one argument list (include/wavenet_hip.h): each takes the one before it plus a tail, the stream last
+_DEC_HEAD = [_i] * 5 + [_p] * 6 + [_l] + [_p] * 12 + [_l, _i, _i, _p]    # n_layers .. sync
+_DEC_BATCH = [_i, _l, _f, _l]                          # n_utt, queues_ustride, temperature, seed
+_DEC_PK = [_p] + [_l] * 6                              # pk, pk_fg0, pk_d0, pk_lstride, pk_skip, pk_p1, pk_p2
+_DEC_COND = [_p, _l, _p, _l, _p, _p, _i, _l]           # cond_fg + stride, cond_p1 + stride, c_shift, c_q, le, pos0
+_DEC_SAMP = [_p, _i, _f]                               # the per-utterance wn_sampling table, top_k, top_p
 
 # name -> argtypes  (every function returns int status except wn_last_error)
 SIGNATURES = {
@@ -85,22 +91,13 @@ SIGNATURES = {
     "wn_mulaw_decode_lut": [_p, _p, _p, _l, _p],
     "wn_mulaw_encode_q": [_p, _p, _i, _p, _l, _p],
     "wn_mulaw_decode_q": [_p, _p, _i, _p, _l, _p],
-    "wn_decode": [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _l,
-                  _i, _i, _p, _p],
-    "wn_decode_batch": [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _l,
-                        _i, _i, _p, _i, _l, _f, _l, _p],
+    "wn_decode": _DEC_HEAD + [_p],
+    "wn_decode_batch": _DEC_HEAD + _DEC_BATCH + [_p],
     "wn_decode_sync_granules": [_i, _i, _i],
-    "wn_decode_batch_pk": [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _l,
-                           _i, _i, _p, _i, _l, _f, _l, _p, _l, _l, _l, _l, _l, _l, _p],
-    "wn_decode_batch_fw": [_i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
-                           _l, _i, _i, _p, _i, _l, _f, _l, _p, _l, _l, _l, _l, _l, _l, _p],
-    # wn_decode_batch_fw + cond_fg, its utterance stride, cond_p1, its utterance stride, c_shift, c_q, le, pos0 (before the stream)
-    "wn_decode_batch_cond": [_i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
-                             _l, _i, _i, _p, _i, _l, _f, _l, _p, _l, _l, _l, _l, _l, _l, _p, _l, _p, _l, _p, _p, _i, _l, _p],
-    # wn_decode_batch_cond + the per-utterance wn_sampling table, top_k, top_p (before the stream)
-    "wn_decode_batch_samp": [_i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
-                             _l, _i, _i, _p, _i, _l, _f, _l, _p, _l, _l, _l, _l, _l, _l, _p, _l, _p, _l, _p, _p, _i, _l,
-                             _p, _i, _f, _p],
+    "wn_decode_batch_pk": _DEC_HEAD + _DEC_BATCH + _DEC_PK + [_p],
+    "wn_decode_batch_fw": [_i] + _DEC_HEAD + _DEC_BATCH + _DEC_PK + [_p],              # filter_width first
+    "wn_decode_batch_cond": [_i] + _DEC_HEAD + _DEC_BATCH + _DEC_PK + _DEC_COND + [_p],
+    "wn_decode_batch_samp": [_i] + _DEC_HEAD + _DEC_BATCH + _DEC_PK + _DEC_COND + _DEC_SAMP + [_p],
     "wn_sample_logits": [_p, _l, _i, _l, _p, _f, _l, _i, _f, _l, _p, _p, _p, _p],
 }
 

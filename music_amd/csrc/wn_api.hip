@@ -57,6 +57,93 @@ static_assert(WN_F16X3 == WN_MODE_F16X3 && WN_F16X1 == WN_MODE_F16X1 && WN_BF16X
               WN_BF16X1 == WN_MODE_BF16X1, "mode enums out of sync");
 static_assert(WN_CE_NUM_PARTIALS == WN_CE_PARTIALS, "partials out of sync");
 
+// ---- cached-queue decode: the ONE call path behind the six exported decode entries -------------------------------------------
+// Every entry forwards its arguments (and the defaults of those it does not take) to decode_checked with the checks it applies:
+enum : unsigned {
+    DEC_FW = 1,       // takes filter_width: it, Q and the note / history pointers are checked, under the entry's own name
+    DEC_COND = 2,     // takes conditioning tables: corrected recurrence only; le, n_layers and the schedule arrays are checked
+    DEC_SAMP = 4,     // takes top_k / top_p: the scalar form's filters are checked
+};
+
+static int decode_refuse(const char* fn, const char* text) {
+    snprintf(g_err, sizeof(g_err), "%s: %s", fn, text);
+    return -4;
+}
+
+// Makes every refusal of a decode call, in the one order all entries share, then fills WnDecodeArgs and launches.  `fn`: the calling
+// entry; `sync_ustride`: uint64 words of hand-off scratch per utterance.  The checks every entry applies report as "wn_decode".
+static int decode_checked(const char* fn, unsigned checks, int64_t sync_ustride, int filter_width, int n_layers, int R, int D, int S,
+                          int Q, const int32_t* dilations_host, const int64_t* q_off_host, float* queues, const float* w_causal,
+                          const float* b_causal, const float* w_layers, int64_t layer_stride, const float* b_layers,
+                          const float* w_p1, const float* b_p1, const float* w_p2, const float* b_p2, const float* note0,
+                          const float* prev0, float* note_out, float* prev_out, const int32_t* forced, int32_t* codes_out,
+                          float* probs_out, int64_t step0, int n_steps, int push_input, uint64_t* sync, int n_utt,
+                          int64_t queues_ustride, float temperature, uint64_t seed, const uint16_t* pk, int64_t pk_fg0,
+                          int64_t pk_d0, int64_t pk_lstride, int64_t pk_skip, int64_t pk_p1, int64_t pk_p2, const float* cond_fg,
+                          int64_t cond_fg_ustride, const float* cond_p1, int64_t cond_p1_ustride, const int32_t* c_shift_host,
+                          const int32_t* c_q_host, int le, int64_t pos0, const wn_sampling* samp, int top_k, float top_p,
+                          wn_stream_t stream) {
+    const bool layers_ok = n_layers >= 1 && n_layers <= WN_DEC_MAX_LAYERS;
+    if ((checks & DEC_SAMP) && !samp) {   // (a table's entries are normalised on the device: out of range = filter off)
+        if (!(top_p >= 0.0f)) return decode_refuse(fn, "'top_p' must be a number >= 0 (0 or >= 1: no nucleus filter)");
+        if (top_k < 0) return decode_refuse(fn, "'top_k' must be >= 0 (0 or >= Q: no top-k filter)");
+    }
+    if ((checks & DEC_FW) && filter_width < 1) return decode_refuse(fn, "filter_width must be >= 1");
+    if (!push_input) {
+        if (checks & DEC_COND) return decode_refuse(fn, "conditioned decode exists for the corrected recurrence only; pass push_input = 1");
+        if ((checks & DEC_FW) && filter_width != 2)
+            return decode_refuse(fn, "the as-written queue push (push_input = 0) exists for filter_width 2 only; pass push_input = 1 "
+                                     "(the corrected recurrence)");
+    }
+    if ((checks & DEC_COND) && le < 1) return decode_refuse(fn, "le (columns of a conditioning table) must be >= 1");
+    if ((checks & DEC_FW) && (Q < 1 || Q > WN_DEC_MAX_Q)) return decode_refuse(fn, "1 <= Q <= 1024 quantisation channels");
+    if (checks & DEC_COND) {              // (the schedule arrays hold n_layers + 1 entries: the layer count is checked first)
+        if (!layers_ok) return decode_refuse(fn, "1..64 layers supported");
+        if (cond_fg || cond_p1) {
+            if (!c_shift_host || !c_q_host)
+                return decode_refuse(fn, "a conditioning table needs the schedule arrays 'c_shift_host' and 'c_q_host' (n_layers + 1 "
+                                         "entries each)");
+            for (int i = 0; i <= n_layers; ++i)
+                if (c_q_host[i] < 0) return decode_refuse(fn, "c_q[i] must be >= 0 (stretch factor, or 0 = tile)");
+        }
+    }
+    if ((checks & DEC_FW) && n_utt > 0 && n_steps > 0) {
+        WN_REQUIRE(fn, note0, note_out, codes_out);
+        if (filter_width > 1) WN_REQUIRE(fn, prev0, prev_out);
+    }
+    if (n_utt <= 0) return 0;
+    if (!layers_ok) return decode_refuse("wn_decode", "1..64 layers supported");
+    WN_REQUIRE("wn_decode", dilations_host, q_off_host);              // (host arrays, read right here)
+    if (n_steps > 0) WN_REQUIRE("wn_decode", queues, w_causal, w_layers, w_p1, w_p2, sync);
+    WnDecodeArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n_layers = n_layers; a.R = R; a.D = D; a.S = S; a.Q = Q; a.fw = filter_width;
+    for (int i = 0; i < n_layers; ++i) { a.dil[i] = dilations_host[i]; a.q_off[i] = q_off_host[i]; }
+    a.queues = queues; a.w_causal = w_causal; a.b_causal = b_causal; a.w_layers = w_layers; a.layer_stride = layer_stride;
+    a.b_layers = b_layers; a.w_p1 = w_p1; a.b_p1 = b_p1; a.w_p2 = w_p2; a.b_p2 = b_p2;
+    a.note0 = note0; a.prev0 = prev0; a.note_out = note_out; a.prev_out = prev_out; a.forced = forced;
+    a.codes_out = codes_out; a.probs_out = probs_out; a.step0 = step0; a.n_steps = n_steps; a.push_input = push_input;
+    a.dbg = 0;
+    a.sync = reinterpret_cast<unsigned long long*>(sync);
+    a.sync_ustride = sync_ustride;
+    a.n_utt = n_utt; a.queues_ustride = queues_ustride;
+    a.sample = temperature > 0.0f ? 1 : 0; a.inv_temp = temperature > 0.0f ? 1.0f / temperature : 1.0f; a.seed = seed;
+    a.samp = reinterpret_cast<const WnSampling*>(samp); a.top_k = top_k; a.top_p = top_p;
+    a.pk_skip = -1;
+    a.cond_fg = cond_fg; a.cond_fg_ustride = cond_fg_ustride; a.cond_p1 = cond_p1; a.cond_p1_ustride = cond_p1_ustride;
+    a.le = le; a.pos0 = pos0;
+    if (cond_fg || cond_p1)
+        for (int i = 0; i <= n_layers; ++i) { a.c_shift[i] = c_shift_host[i]; a.c_q[i] = c_q_host[i]; }
+    // the matrix-core kernel needs all of pk (chain, skip, post-processing: 64 / 64 / 256 / 256 channels); biases are fine
+    const bool any_bias = b_layers || b_causal || b_p1 || b_p2;
+    const bool post_pk = (S == 256 || S == 512) && Q == 256 && pk_skip >= 0 && pk_p1 >= 0 && pk_p2 >= 0;
+    if (pk && R == 64 && D == 64 && (post_pk || !any_bias)) {
+        a.pk = pk; a.pk_fg0 = pk_fg0; a.pk_d0 = pk_d0; a.pk_lstride = pk_lstride;
+        if (post_pk) { a.pk_skip = pk_skip; a.pk_p1 = pk_p1; a.pk_p2 = pk_p2; }
+    }
+    return wn_launch_decode(a, (hipStream_t)stream);
+}
+
 extern "C" {
 
 int wn_version(void) { return WN_ABI_VERSION; }
@@ -442,35 +529,9 @@ int wn_avgpool(const float* in, int64_t in_bstride, int in_pitch, int t0, int po
                              (hipStream_t)stream);
 }
 
-}  // extern "C"
-static int decode_impl(int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host, const int64_t* q_off_host,
-                       float* queues, const float* w_causal, const float* b_causal, const float* w_layers,
-                       int64_t layer_stride, const float* b_layers, const float* w_p1, const float* b_p1,
-                       const float* w_p2, const float* b_p2, const float* note0, const float* prev0, float* note_out,
-                       float* prev_out, const int32_t* forced, int32_t* codes_out, float* probs_out, int64_t step0,
-                       int n_steps, int push_input, uint64_t* sync, int64_t sync_ustride, int n_utt, int64_t queues_ustride,
-                       float temperature, uint64_t seed, const uint16_t* pk, int64_t pk_fg0, int64_t pk_d0, int64_t pk_lstride,
-                       int64_t pk_skip, int64_t pk_p1, int64_t pk_p2, int fw, wn_stream_t stream,
-                       const float* cond_fg = nullptr, int64_t cond_fg_ustride = 0, const float* cond_p1 = nullptr,
-                       int64_t cond_p1_ustride = 0, const int32_t* c_shift = nullptr, const int32_t* c_q = nullptr, int le = 1,
-                       int64_t pos0 = 0, const wn_sampling* samp = nullptr, int top_k = 0, float top_p = 1.0f);
-extern "C" {
-int64_t wn_decode_sync_granules(int n_layers, int D, int S);
-int wn_decode_batch(int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host, const int64_t* q_off_host,
-                    float* queues, const float* w_causal, const float* b_causal, const float* w_layers,
-                    int64_t layer_stride, const float* b_layers, const float* w_p1, const float* b_p1,
-                    const float* w_p2, const float* b_p2, const float* note0, const float* prev0, float* note_out,
-                    float* prev_out, const int32_t* forced, int32_t* codes_out, float* probs_out, int64_t step0,
-                    int n_steps, int push_input, uint64_t* sync, int n_utt, int64_t queues_ustride, float temperature,
-                    uint64_t seed, wn_stream_t stream);
-int wn_decode_batch_pk(int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host, const int64_t* q_off_host,
-                       float* queues, const float* w_causal, const float* b_causal, const float* w_layers,
-                       int64_t layer_stride, const float* b_layers, const float* w_p1, const float* b_p1,
-                       const float* w_p2, const float* b_p2, const float* note0, const float* prev0, float* note_out,
-                       float* prev_out, const int32_t* forced, int32_t* codes_out, float* probs_out, int64_t step0,
-                       int n_steps, int push_input, uint64_t* sync, int n_utt, int64_t queues_ustride, float temperature,
-                       uint64_t seed, const uint16_t* pk, int64_t pk_fg0, int64_t pk_d0, int64_t pk_lstride, int64_t pk_skip,
-                       int64_t pk_p1, int64_t pk_p2, wn_stream_t stream);
+int64_t wn_decode_sync_granules(int n_layers, int D, int S) {
+    return (int64_t)wn_decode_granules(n_layers, D, S);      // z of every block, the split form's vectors, the tap-0 table, code, error flag
+}
 
 int wn_decode(int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host, const int64_t* q_off_host,
               float* queues, const float* w_causal, const float* b_causal, const float* w_layers,
@@ -478,9 +539,10 @@ int wn_decode(int n_layers, int R, int D, int S, int Q, const int32_t* dilations
               const float* w_p2, const float* b_p2, const float* note0, const float* prev0, float* note_out,
               float* prev_out, const int32_t* forced, int32_t* codes_out, float* probs_out, int64_t step0,
               int n_steps, int push_input, uint64_t* sync, wn_stream_t stream) {
-    return wn_decode_batch(n_layers, R, D, S, Q, dilations_host, q_off_host, queues, w_causal, b_causal, w_layers, layer_stride,
-                           b_layers, w_p1, b_p1, w_p2, b_p2, note0, prev0, note_out, prev_out, forced, codes_out, probs_out,
-                           step0, n_steps, push_input, sync, 1, 0, 0.0f, 0, stream);
+    return decode_checked("wn_decode", 0, (int64_t)n_layers * D + 2, 2, n_layers, R, D, S, Q, dilations_host, q_off_host, queues,
+                          w_causal, b_causal, w_layers, layer_stride, b_layers, w_p1, b_p1, w_p2, b_p2, note0, prev0, note_out,
+                          prev_out, forced, codes_out, probs_out, step0, n_steps, push_input, sync, 1, 0, 0.0f, 0,
+                          nullptr, 0, 0, 0, -1, -1, -1, nullptr, 0, nullptr, 0, nullptr, nullptr, 1, 0, nullptr, 0, 1.0f, stream);
 }
 
 int wn_decode_batch(int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host, const int64_t* q_off_host,
@@ -490,14 +552,11 @@ int wn_decode_batch(int n_layers, int R, int D, int S, int Q, const int32_t* dil
                     float* prev_out, const int32_t* forced, int32_t* codes_out, float* probs_out, int64_t step0,
                     int n_steps, int push_input, uint64_t* sync, int n_utt, int64_t queues_ustride, float temperature,
                     uint64_t seed, wn_stream_t stream) {
-    return decode_impl(n_layers, R, D, S, Q, dilations_host, q_off_host, queues, w_causal, b_causal, w_layers, layer_stride,
-                       b_layers, w_p1, b_p1, w_p2, b_p2, note0, prev0, note_out, prev_out, forced, codes_out, probs_out,
-                       step0, n_steps, push_input, sync, (int64_t)n_layers * D + 2, n_utt, queues_ustride, temperature, seed,
-                       nullptr, 0, 0, 0, -1, -1, -1, 2, stream);
-}
-
-int64_t wn_decode_sync_granules(int n_layers, int D, int S) {
-    return (int64_t)wn_decode_granules(n_layers, D, S);      // z of every block, the split form's vectors, the tap-0 table, code, error flag
+    return decode_checked("wn_decode_batch", 0, (int64_t)n_layers * D + 2, 2, n_layers, R, D, S, Q, dilations_host, q_off_host,
+                          queues, w_causal, b_causal, w_layers, layer_stride, b_layers, w_p1, b_p1, w_p2, b_p2, note0, prev0,
+                          note_out, prev_out, forced, codes_out, probs_out, step0, n_steps, push_input, sync, n_utt, queues_ustride,
+                          temperature, seed, nullptr, 0, 0, 0, -1, -1, -1, nullptr, 0, nullptr, 0, nullptr, nullptr, 1, 0,
+                          nullptr, 0, 1.0f, stream);
 }
 
 int wn_decode_batch_pk(int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host, const int64_t* q_off_host,
@@ -508,10 +567,11 @@ int wn_decode_batch_pk(int n_layers, int R, int D, int S, int Q, const int32_t* 
                        int n_steps, int push_input, uint64_t* sync, int n_utt, int64_t queues_ustride, float temperature,
                        uint64_t seed, const uint16_t* pk, int64_t pk_fg0, int64_t pk_d0, int64_t pk_lstride, int64_t pk_skip,
                        int64_t pk_p1, int64_t pk_p2, wn_stream_t stream) {
-    return decode_impl(n_layers, R, D, S, Q, dilations_host, q_off_host, queues, w_causal, b_causal, w_layers, layer_stride,
-                       b_layers, w_p1, b_p1, w_p2, b_p2, note0, prev0, note_out, prev_out, forced, codes_out, probs_out,
-                       step0, n_steps, push_input, sync, wn_decode_sync_granules(n_layers, D, S), n_utt, queues_ustride,
-                       temperature, seed, pk, pk_fg0, pk_d0, pk_lstride, pk_skip, pk_p1, pk_p2, 2, stream);
+    return decode_checked("wn_decode_batch_pk", 0, wn_decode_sync_granules(n_layers, D, S), 2, n_layers, R, D, S, Q, dilations_host,
+                          q_off_host, queues, w_causal, b_causal, w_layers, layer_stride, b_layers, w_p1, b_p1, w_p2, b_p2, note0,
+                          prev0, note_out, prev_out, forced, codes_out, probs_out, step0, n_steps, push_input, sync, n_utt,
+                          queues_ustride, temperature, seed, pk, pk_fg0, pk_d0, pk_lstride, pk_skip, pk_p1, pk_p2,
+                          nullptr, 0, nullptr, 0, nullptr, nullptr, 1, 0, nullptr, 0, 1.0f, stream);
 }
 
 int wn_decode_batch_fw(int filter_width, int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host,
@@ -522,54 +582,11 @@ int wn_decode_batch_fw(int filter_width, int n_layers, int R, int D, int S, int 
                        int n_steps, int push_input, uint64_t* sync, int n_utt, int64_t queues_ustride, float temperature,
                        uint64_t seed, const uint16_t* pk, int64_t pk_fg0, int64_t pk_d0, int64_t pk_lstride, int64_t pk_skip,
                        int64_t pk_p1, int64_t pk_p2, wn_stream_t stream) {
-    if (filter_width < 1) return wn_set_error_msg(-4, "wn_decode_batch_fw: filter_width must be >= 1");
-    if (filter_width != 2 && !push_input)
-        return wn_set_error_msg(-4, "wn_decode_batch_fw: the as-written queue push (push_input = 0) exists for filter_width 2 "
-                                    "only; pass push_input = 1 (the corrected recurrence)");
-    if (Q < 1 || Q > WN_DEC_MAX_Q) return wn_set_error_msg(-4, "wn_decode_batch_fw: 1 <= Q <= 1024 quantisation channels");
-    if (n_utt > 0 && n_steps > 0) {
-        WN_REQUIRE("wn_decode_batch_fw", note0, note_out, codes_out);
-        if (filter_width > 1) WN_REQUIRE("wn_decode_batch_fw", prev0, prev_out);
-    }
-    return decode_impl(n_layers, R, D, S, Q, dilations_host, q_off_host, queues, w_causal, b_causal, w_layers, layer_stride,
-                       b_layers, w_p1, b_p1, w_p2, b_p2, note0, prev0, note_out, prev_out, forced, codes_out, probs_out,
-                       step0, n_steps, push_input, sync, wn_decode_sync_granules(n_layers, D, S), n_utt, queues_ustride,
-                       temperature, seed, pk, pk_fg0, pk_d0, pk_lstride, pk_skip, pk_p1, pk_p2, filter_width, stream);
-}
-
-static int decode_cond_checked(const char* fn, int filter_width, int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host,
-                         const int64_t* q_off_host, float* queues, const float* w_causal, const float* b_causal,
-                         const float* w_layers, int64_t layer_stride, const float* b_layers, const float* w_p1, const float* b_p1,
-                         const float* w_p2, const float* b_p2, const float* note0, const float* prev0, float* note_out,
-                         float* prev_out, const int32_t* forced, int32_t* codes_out, float* probs_out, int64_t step0,
-                         int n_steps, int push_input, uint64_t* sync, int n_utt, int64_t queues_ustride, float temperature,
-                         uint64_t seed, const uint16_t* pk, int64_t pk_fg0, int64_t pk_d0, int64_t pk_lstride, int64_t pk_skip,
-                         int64_t pk_p1, int64_t pk_p2, const float* cond_fg, int64_t cond_fg_ustride, const float* cond_p1,
-                         int64_t cond_p1_ustride, const int32_t* c_shift_host, const int32_t* c_q_host, int le, int64_t pos0,
-                         const wn_sampling* samp, int top_k, float top_p, wn_stream_t stream) {
-    char msg[256];
-#define DEC_REFUSE(text) do { snprintf(msg, sizeof(msg), "%s: " text, fn); return wn_set_error_msg(-4, msg); } while (0)
-    if (filter_width < 1) DEC_REFUSE("filter_width must be >= 1");
-    if (!push_input) DEC_REFUSE("conditioned decode exists for the corrected recurrence only; pass push_input = 1");
-    if (le < 1) DEC_REFUSE("le (columns of a conditioning table) must be >= 1");
-    if (Q < 1 || Q > WN_DEC_MAX_Q) DEC_REFUSE("1 <= Q <= 1024 quantisation channels");
-    if (n_layers > WN_DEC_MAX_LAYERS || n_layers <= 0) DEC_REFUSE("1..64 layers supported");
-    if (cond_fg || cond_p1) {
-        if (!c_shift_host || !c_q_host)
-            DEC_REFUSE("a conditioning table needs the schedule arrays 'c_shift_host' and 'c_q_host' (n_layers + 1 entries each)");
-        for (int i = 0; i <= n_layers; ++i)
-            if (c_q_host[i] < 0) DEC_REFUSE("c_q[i] must be >= 0 (stretch factor, or 0 = tile)");
-    }
-    if (n_utt > 0 && n_steps > 0) {
-        WN_REQUIRE(fn, note0, note_out, codes_out);
-        if (filter_width > 1) WN_REQUIRE(fn, prev0, prev_out);
-    }
-    return decode_impl(n_layers, R, D, S, Q, dilations_host, q_off_host, queues, w_causal, b_causal, w_layers, layer_stride,
-                       b_layers, w_p1, b_p1, w_p2, b_p2, note0, prev0, note_out, prev_out, forced, codes_out, probs_out,
-                       step0, n_steps, push_input, sync, wn_decode_sync_granules(n_layers, D, S), n_utt, queues_ustride,
-                       temperature, seed, pk, pk_fg0, pk_d0, pk_lstride, pk_skip, pk_p1, pk_p2, filter_width, stream,
-                       cond_fg, cond_fg_ustride, cond_p1, cond_p1_ustride, c_shift_host, c_q_host, le, pos0, samp, top_k, top_p);
-#undef DEC_REFUSE
+    return decode_checked("wn_decode_batch_fw", DEC_FW, wn_decode_sync_granules(n_layers, D, S), filter_width, n_layers, R, D, S, Q,
+                          dilations_host, q_off_host, queues, w_causal, b_causal, w_layers, layer_stride, b_layers, w_p1, b_p1, w_p2,
+                          b_p2, note0, prev0, note_out, prev_out, forced, codes_out, probs_out, step0, n_steps, push_input, sync,
+                          n_utt, queues_ustride, temperature, seed, pk, pk_fg0, pk_d0, pk_lstride, pk_skip, pk_p1, pk_p2,
+                          nullptr, 0, nullptr, 0, nullptr, nullptr, 1, 0, nullptr, 0, 1.0f, stream);
 }
 
 int wn_decode_batch_cond(int filter_width, int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host,
@@ -582,11 +599,12 @@ int wn_decode_batch_cond(int filter_width, int n_layers, int R, int D, int S, in
                          int64_t pk_p1, int64_t pk_p2, const float* cond_fg, int64_t cond_fg_ustride, const float* cond_p1,
                          int64_t cond_p1_ustride, const int32_t* c_shift_host, const int32_t* c_q_host, int le, int64_t pos0,
                          wn_stream_t stream) {
-    return decode_cond_checked("wn_decode_batch_cond", filter_width, n_layers, R, D, S, Q, dilations_host, q_off_host, queues, w_causal, b_causal, w_layers,
-                               layer_stride, b_layers, w_p1, b_p1, w_p2, b_p2, note0, prev0, note_out, prev_out, forced, codes_out,
-                               probs_out, step0, n_steps, push_input, sync, n_utt, queues_ustride, temperature, seed, pk, pk_fg0,
-                               pk_d0, pk_lstride, pk_skip, pk_p1, pk_p2, cond_fg, cond_fg_ustride, cond_p1, cond_p1_ustride,
-                               c_shift_host, c_q_host, le, pos0, nullptr, 0, 1.0f, stream);
+    return decode_checked("wn_decode_batch_cond", DEC_FW | DEC_COND, wn_decode_sync_granules(n_layers, D, S), filter_width, n_layers,
+                          R, D, S, Q, dilations_host, q_off_host, queues, w_causal, b_causal, w_layers, layer_stride, b_layers, w_p1,
+                          b_p1, w_p2, b_p2, note0, prev0, note_out, prev_out, forced, codes_out, probs_out, step0, n_steps,
+                          push_input, sync, n_utt, queues_ustride, temperature, seed, pk, pk_fg0, pk_d0, pk_lstride, pk_skip, pk_p1,
+                          pk_p2, cond_fg, cond_fg_ustride, cond_p1, cond_p1_ustride, c_shift_host, c_q_host, le, pos0,
+                          nullptr, 0, 1.0f, stream);
 }
 
 int wn_decode_batch_samp(int filter_width, int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host,
@@ -599,15 +617,12 @@ int wn_decode_batch_samp(int filter_width, int n_layers, int R, int D, int S, in
                          int64_t pk_p1, int64_t pk_p2, const float* cond_fg, int64_t cond_fg_ustride, const float* cond_p1,
                          int64_t cond_p1_ustride, const int32_t* c_shift_host, const int32_t* c_q_host, int le, int64_t pos0,
                          const wn_sampling* samp, int top_k, float top_p, wn_stream_t stream) {
-    if (!samp) {        // the scalar form's filters (a table's entries are normalised on the device: out of range = filter off)
-        if (!(top_p >= 0.0f)) return wn_set_error_msg(-4, "wn_decode_batch_samp: 'top_p' must be a number >= 0 (0 or >= 1: no nucleus filter)");
-        if (top_k < 0) return wn_set_error_msg(-4, "wn_decode_batch_samp: 'top_k' must be >= 0 (0 or >= Q: no top-k filter)");
-    }
-    return decode_cond_checked("wn_decode_batch_samp", filter_width, n_layers, R, D, S, Q, dilations_host, q_off_host, queues, w_causal, b_causal, w_layers,
-                               layer_stride, b_layers, w_p1, b_p1, w_p2, b_p2, note0, prev0, note_out, prev_out, forced, codes_out,
-                               probs_out, step0, n_steps, push_input, sync, n_utt, queues_ustride, temperature, seed, pk, pk_fg0,
-                               pk_d0, pk_lstride, pk_skip, pk_p1, pk_p2, cond_fg, cond_fg_ustride, cond_p1, cond_p1_ustride,
-                               c_shift_host, c_q_host, le, pos0, samp, top_k, top_p, stream);
+    return decode_checked("wn_decode_batch_samp", DEC_FW | DEC_COND | DEC_SAMP, wn_decode_sync_granules(n_layers, D, S), filter_width,
+                          n_layers, R, D, S, Q, dilations_host, q_off_host, queues, w_causal, b_causal, w_layers, layer_stride,
+                          b_layers, w_p1, b_p1, w_p2, b_p2, note0, prev0, note_out, prev_out, forced, codes_out, probs_out, step0,
+                          n_steps, push_input, sync, n_utt, queues_ustride, temperature, seed, pk, pk_fg0, pk_d0, pk_lstride, pk_skip,
+                          pk_p1, pk_p2, cond_fg, cond_fg_ustride, cond_p1, cond_p1_ustride, c_shift_host, c_q_host, le, pos0, samp,
+                          top_k, top_p, stream);
 }
 
 int wn_sample_logits(const float* logits, int64_t n, int Q, int64_t ld, const wn_sampling* samp, float temperature, uint64_t seed,
@@ -626,47 +641,3 @@ int wn_sample_logits(const float* logits, int64_t n, int Q, int64_t ld, const wn
 }
 
 }  // extern "C"
-
-static int decode_impl(int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host, const int64_t* q_off_host,
-                       float* queues, const float* w_causal, const float* b_causal, const float* w_layers,
-                       int64_t layer_stride, const float* b_layers, const float* w_p1, const float* b_p1,
-                       const float* w_p2, const float* b_p2, const float* note0, const float* prev0, float* note_out,
-                       float* prev_out, const int32_t* forced, int32_t* codes_out, float* probs_out, int64_t step0,
-                       int n_steps, int push_input, uint64_t* sync, int64_t sync_ustride, int n_utt, int64_t queues_ustride,
-                       float temperature, uint64_t seed, const uint16_t* pk, int64_t pk_fg0, int64_t pk_d0, int64_t pk_lstride,
-                       int64_t pk_skip, int64_t pk_p1, int64_t pk_p2, int fw, wn_stream_t stream,
-                       const float* cond_fg, int64_t cond_fg_ustride, const float* cond_p1, int64_t cond_p1_ustride,
-                       const int32_t* c_shift, const int32_t* c_q, int le, int64_t pos0, const wn_sampling* samp, int top_k,
-                       float top_p) {
-    if (n_utt <= 0) return 0;
-    if (n_layers > WN_DEC_MAX_LAYERS || n_layers <= 0) return wn_set_error_msg(-4, "wn_decode: 1..64 layers supported");
-    WN_REQUIRE("wn_decode", dilations_host, q_off_host);              // (host arrays, read right here)
-    if (n_steps > 0) WN_REQUIRE("wn_decode", queues, w_causal, w_layers, w_p1, w_p2, sync);
-    WnDecodeArgs a;
-    memset(&a, 0, sizeof(a));
-    a.n_layers = n_layers; a.R = R; a.D = D; a.S = S; a.Q = Q; a.fw = fw;
-    for (int i = 0; i < n_layers; ++i) { a.dil[i] = dilations_host[i]; a.q_off[i] = q_off_host[i]; }
-    a.queues = queues; a.w_causal = w_causal; a.b_causal = b_causal; a.w_layers = w_layers; a.layer_stride = layer_stride;
-    a.b_layers = b_layers; a.w_p1 = w_p1; a.b_p1 = b_p1; a.w_p2 = w_p2; a.b_p2 = b_p2;
-    a.note0 = note0; a.prev0 = prev0; a.note_out = note_out; a.prev_out = prev_out; a.forced = forced;
-    a.codes_out = codes_out; a.probs_out = probs_out; a.step0 = step0; a.n_steps = n_steps; a.push_input = push_input;
-    a.dbg = 0;
-    a.sync = reinterpret_cast<unsigned long long*>(sync);
-    a.sync_ustride = sync_ustride;
-    a.n_utt = n_utt; a.queues_ustride = queues_ustride;
-    a.sample = temperature > 0.0f ? 1 : 0; a.inv_temp = temperature > 0.0f ? 1.0f / temperature : 1.0f; a.seed = seed;
-    a.samp = reinterpret_cast<const WnSampling*>(samp); a.top_k = top_k; a.top_p = top_p;
-    a.pk_skip = -1;
-    a.cond_fg = cond_fg; a.cond_fg_ustride = cond_fg_ustride; a.cond_p1 = cond_p1; a.cond_p1_ustride = cond_p1_ustride;
-    a.le = le; a.pos0 = pos0;
-    if (cond_fg || cond_p1)
-        for (int i = 0; i <= n_layers; ++i) { a.c_shift[i] = c_shift[i]; a.c_q[i] = c_q[i]; }
-    // the matrix-core kernel needs all of pk (chain, skip, post-processing: 64 / 64 / 256 / 256 channels); biases are fine
-    const bool any_bias = b_layers || b_causal || b_p1 || b_p2;
-    const bool post_pk = (S == 256 || S == 512) && Q == 256 && pk_skip >= 0 && pk_p1 >= 0 && pk_p2 >= 0;
-    if (pk && R == 64 && D == 64 && (post_pk || !any_bias)) {
-        a.pk = pk; a.pk_fg0 = pk_fg0; a.pk_d0 = pk_d0; a.pk_lstride = pk_lstride;
-        if (post_pk) { a.pk_skip = pk_skip; a.pk_p1 = pk_p1; a.pk_p2 = pk_p2; }
-    }
-    return wn_launch_decode(a, (hipStream_t)stream);
-}

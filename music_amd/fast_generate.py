@@ -160,6 +160,12 @@ class _DecodePack:
     def p(self, off):
         return None if off is None else ptr(self.buf, off)
 
+    def weights(self):
+        """(w_causal, b_causal, w_layers, layer stride, b_layers, w_p1, b_p1, w_p2, b_p2) as every decode entry takes them."""
+        ob = (self.ob_causal, self.ob_layers, self.ob_p1, self.ob_p2) if self.o_bias is not None else (None,) * 4
+        return (self.p(self.o_causal), self.p(ob[0]), self.p(self.o_layers), self.layer_stride, self.p(ob[1]),
+                self.p(self.o_p1), self.p(ob[2]), self.p(self.o_p2), self.p(ob[3]))
+
     def chain(self):
         """(pk pointer, fg offset, d offset, per-block stride, skip, p1, p2 offsets) for wn_decode_batch_pk, or Nones / -1."""
         if self.pk is None:
@@ -295,6 +301,7 @@ class _Sampling:
 
 
 _NO_COND = (None, 0, None, 0, None, None, 1, 0)       # wn_decode_batch_cond's table arguments of an unconditioned launch
+last_error_flags = None        # the error flag word of every utterance of the last decode_batch_cond launch (device tensor)
 
 
 def _need_corrected(smp, correct_queue):
@@ -303,50 +310,95 @@ def _need_corrected(smp, correct_queue):
                          "(wn_decode_batch_samp): pass correct_queue=True")
 
 
+def _pack_for(net, eng):
+    """The decode weight pack of `eng`, kept on the net (built on first use; refreshed by the launcher)."""
+    pack = getattr(net, "_decode_pack", None)
+    if pack is None or pack.eng is not eng:
+        pack = net._decode_pack = _DecodePack(eng)
+    return pack
+
+
+def _decode_call(shape, dil, qoff, queues, weights, io, step0, n_steps, push_input, sync, U, queues_ustride, smp, pk, cond=None):
+    """(entry point, its arguments without the stream) of one decode launch: THE place the argument list is written and the
+    entry chosen.  Plain values and pointers only (no device work).  ``shape``: (filter_width, N, Rp, Dp, S, Q); ``weights``:
+    ``_DecodePack.weights()``; ``io``: note0, prev0, note_out, prev_out, forced, codes, probs; ``pk``: ``_DecodePack.chain()``;
+    ``cond``: the eight table arguments of wn_decode_batch_cond when the launch came in through ``decode_batch_cond``."""
+    args = (*shape, dil, qoff, queues, *weights, *io, step0, n_steps, push_input, sync, U, queues_ustride,
+            smp.temperature, smp.seed, *pk)
+    if smp.plain and cond is None:
+        return "wn_decode_batch_fw", args
+    args += _NO_COND if cond is None else tuple(cond)
+    if smp.plain:
+        return "wn_decode_batch_cond", args
+    return "wn_decode_batch_samp", args + smp.tail()
+
+
+def _launch_decode(net, eng, smp, rings, note0, prev0, U, n_steps, step0, push_input, timeout_msg, check=True, forced=None,
+                   want_probs=False, sync=None, cond=None):
+    """One persistent decode launch of U utterances: ``rings`` ((U, ring floats), or 1-D for one utterance) is advanced in
+    place.  ``sync``: the hand-off scratch (default: fresh and zeroed); ``check``: read the error flags back and raise
+    ``timeout_msg`` if one is set.  Returns (codes int32 (U, n_steps), probabilities (U, n_steps, Q) or None, note_out (U, Q),
+    prev_out (U, k-1, Q))."""
+    global last_error_flags
+    pack = _pack_for(net, eng)
+    pack.refresh()
+    dev, N, Q, K1 = eng.device, eng.N, eng.Q, pack.k - 1
+    dil = (ctypes.c_int32 * N)(*eng.dil)
+    qoff = (ctypes.c_int64 * N)(*[int(v) for v in _queue_offsets(eng, pack.Rp)])
+    forced_t = forced.to(device=dev, dtype=torch.int32).contiguous() if forced is not None else None
+    codes = torch.empty(U, n_steps, dtype=torch.int32, device=dev)
+    probs = torch.empty(U, n_steps, Q, dtype=torch.float32, device=dev) if want_probs else None
+    note_out = torch.empty(U, Q, dtype=torch.float32, device=dev)
+    prev_out = torch.empty(U, K1, Q, dtype=torch.float32, device=dev)
+    if sync is None:
+        sync = torch.zeros(U * _lib.decode_sync_granules(N, pack.Dp, eng.S), dtype=torch.int64, device=dev)
+    qbuf = _queue_buffer(rings)
+    name, args = _decode_call((pack.k, N, pack.Rp, pack.Dp, eng.S, Q), ctypes.cast(dil, ctypes.c_void_p),
+                              ctypes.cast(qoff, ctypes.c_void_p), ptr(qbuf), pack.weights(),
+                              (ptr(note0), _ptr_or_none(prev0), ptr(note_out), _ptr_or_none(prev_out), ptr(forced_t), ptr(codes),
+                               ptr(probs)), int(step0), n_steps, push_input, ptr(sync), U, rings.size(1) if rings.dim() == 2 else 0,
+                              smp, pack.chain(), cond)
+    call(name, *args, _lib.stream())
+    flags = sync.view(U, -1)[:, -1]                          # the error flag word of every utterance
+    if cond is not None:
+        last_error_flags = flags
+    if check and int(flags.abs().max().item()) != 0:
+        raise _lib.WavenetHipError(timeout_msg)
+    return codes, probs, note_out, prev_out
+
+
 def _decode(net, state, note0, n_steps, forced=None, want_probs=False, correct_queue=False, temperature=None, seed=0,
             top_k=None, top_p=None):
     eng = state.eng
     _check_recurrence(eng, correct_queue)
     smp = _Sampling(1, temperature, top_k, top_p, seed, None, eng.device)
     _need_corrected(smp, correct_queue)
-    pack = getattr(net, "_decode_pack", None)
-    if pack is None or pack.eng is not eng:
-        pack = net._decode_pack = _DecodePack(eng)
+    pack = _pack_for(net, eng)
     if state.rw != pack.Rp:
         raise RuntimeError("music_amd.fast_generate: this DecodeState holds %d floats per queue column, the weight pack is laid "
                            "out for %d (built for another engine or decode kernel form)" % (state.rw, pack.Rp))
-    pack.refresh()
-    dev = eng.device
-    codes = torch.empty(n_steps, dtype=torch.int32, device=dev)
-    probs = torch.empty(n_steps, eng.Q, dtype=torch.float32, device=dev) if want_probs else None
-    note_out = torch.empty(eng.Q, dtype=torch.float32, device=dev)
-    prev_out = torch.empty(pack.k - 1, eng.Q, dtype=torch.float32, device=dev).view(-1)
-    dil = (ctypes.c_int32 * eng.N)(*eng.dil)
-    qoff = (ctypes.c_int64 * eng.N)(*[int(v) for v in state.q_off])
-    forced_t = forced.to(device=dev, dtype=torch.int32).contiguous() if forced is not None else None
     sync = getattr(net, "_decode_sync", None)
     n_sync = _lib.decode_sync_granules(eng.N, pack.Dp, eng.S)
-    if sync is None or sync.device != dev or sync.numel() != n_sync:
-        sync = net._decode_sync = torch.zeros(n_sync, dtype=torch.int64, device=dev)
-    bias = pack.o_bias is not None
-    pk = pack.chain()
-    qbuf = _queue_buffer(state.rings)
-    args = (pack.k, eng.N, pack.Rp, pack.Dp, eng.S, eng.Q, ctypes.cast(dil, ctypes.c_void_p),
-            ctypes.cast(qoff, ctypes.c_void_p), ptr(qbuf), pack.p(pack.o_causal), pack.p(pack.ob_causal) if bias else None,
-            pack.p(pack.o_layers), pack.layer_stride, pack.p(pack.ob_layers) if bias else None,
-            pack.p(pack.o_p1), pack.p(pack.ob_p1) if bias else None, pack.p(pack.o_p2), pack.p(pack.ob_p2) if bias else None,
-            ptr(note0), _ptr_or_none(state.prev), ptr(note_out), _ptr_or_none(prev_out), ptr(forced_t), ptr(codes), ptr(probs),
-            state.steps, n_steps, 1 if correct_queue else 0, ptr(sync), 1, 0,
-            smp.temperature, smp.seed, pk[0], pk[1], pk[2], pk[3], pk[4], pk[5], pk[6])
-    if smp.plain:
-        call("wn_decode_batch_fw", *args, _lib.stream())
-    else:
-        call("wn_decode_batch_samp", *args, *_NO_COND, *smp.tail(), _lib.stream())
-    if n_steps >= 4 and int(sync[-1].item()) != 0:
-        raise _lib.WavenetHipError("wn_decode: a hand-off between the two decode workgroups timed out")
-    state.prev = prev_out
+    if sync is None or sync.device != eng.device or sync.numel() != n_sync:
+        sync = net._decode_sync = torch.zeros(n_sync, dtype=torch.int64, device=eng.device)
+    codes, probs, note_out, prev_out = _launch_decode(
+        net, eng, smp, state.rings, note0, state.prev, 1, n_steps, state.steps, 1 if correct_queue else 0,
+        "wn_decode: a hand-off between the two decode workgroups timed out", check=n_steps >= 4, forced=forced,
+        want_probs=want_probs, sync=sync)
+    state.prev = prev_out.view(-1)
     state.steps += n_steps
-    return codes, probs, note_out
+    return codes[0], probs[0] if want_probs else None, note_out[0]
+
+
+def _rings_from_workspace(eng, U, T):
+    """(U, ring floats) from the workspace of the forward just run over (U, Q, T): the ring of block i of utterance u = the
+    last (k-1) d_i columns of that block's INPUT (fast_generate.py:42-47 for k = 2), time-major."""
+    ws = eng.workspace(U, T)
+    pitch, CH, R, N = ws["pitch"], eng.CH, eng.R, eng.N
+    X = ws["X"][SLACK:SLACK + (N + 1) * U * CH * pitch].view(N + 1, U, CH, pitch)
+    rw, K1 = _ring_width(eng), _taps(eng)
+    return torch.cat([torch.nn.functional.pad(X[i, :, :R, T - K1 * d:T].transpose(1, 2), (0, rw - R)).reshape(U, K1 * d * rw)
+                      for i, d in enumerate(eng.dil)], 1).contiguous()
 
 
 def predict_next(net, note, state_queue=None, correct_queue=False):
@@ -357,16 +409,9 @@ def predict_next(net, note, state_queue=None, correct_queue=False):
         x = note.detach().to(dev).float().contiguous()
         with torch.no_grad():
             probs = net(x)                                        # (1, Q): W == 1
-        eng = net._engine
-        ws = eng.workspace(1, x.size(2))
-        T, pitch, CH, R = x.size(2), ws["pitch"], eng.CH, eng.R
-        X = ws["X"][SLACK:SLACK + (eng.N + 1) * CH * pitch].view(eng.N + 1, CH, pitch)
-        # queue of block i = the last (k-1) d_i columns of that block's INPUT (fast_generate.py:42-47 for k = 2); the causal
-        # layer's = the last k-1 input columns
-        rw, K1 = _ring_width(eng), _taps(eng)
-        rings = torch.cat([torch.nn.functional.pad(X[i, :R, T - K1 * d:T].t(), (0, rw - R)).reshape(-1)
-                           for i, d in enumerate(eng.dil)]).contiguous()
-        state = DecodeState(eng, rings, x[0, :, T - K1:T].t().contiguous().view(-1), 0)
+        eng, T, K1 = net._engine, x.size(2), _taps(net._engine)
+        # the causal layer's queue = the last k-1 input columns
+        state = DecodeState(eng, _rings_from_workspace(eng, 1, T)[0], x[0, :, T - K1:T].t().contiguous().view(-1), 0)
         _, predict = torch.topk(probs.view(-1), 1)
         return predict.to(note.device), state
     assert note.size()[2] == 1
@@ -416,56 +461,20 @@ def generate_codes_batch(net, start_pieces, note_num, correct_queue=False, tempe
     with torch.no_grad():
         probs = net(x)                                            # (U, Q): W == 1
     eng = net._engine
-    ws = eng.workspace(U, x.size(2))
-    T, pitch, CH, R, N, Q = x.size(2), ws["pitch"], eng.CH, eng.R, eng.N, eng.Q
-    X = ws["X"][SLACK:SLACK + (N + 1) * U * CH * pitch].view(N + 1, U, CH, pitch)
-    # ring of block i of utterance u = the last (k-1) d_i columns of that block's input, time-major
-    rw, K1 = _ring_width(eng), _taps(eng)
-    rings = torch.cat([torch.nn.functional.pad(X[i, :, :R, T - K1 * d:T].transpose(1, 2), (0, rw - R)).reshape(U, K1 * d * rw)
-                       for i, d in enumerate(eng.dil)], 1).contiguous()
+    T, Q, K1 = x.size(2), eng.Q, _taps(eng)
+    rings = _rings_from_workspace(eng, U, T)
     first = probs.view(U, Q).argmax(1)
     if note_num <= 1:
         return first.view(U, 1)[:, :note_num]
     _check_recurrence(eng, correct_queue)
     smp = _Sampling(U, temperature, top_k, top_p, seed, streams, dev)
     _need_corrected(smp, correct_queue)
-    pack = getattr(net, "_decode_pack", None)
-    if pack is None or pack.eng is not eng:
-        pack = net._decode_pack = _DecodePack(eng)
-    pack.refresh()
-    n_steps = note_num - 1
     note0 = torch.zeros(U, Q, dtype=torch.float32, device=dev)
     note0[torch.arange(U, device=dev), first] = 1.0
     prev0 = x[:, :, T - K1:T].transpose(1, 2).contiguous()         # [U][k-1][Q], oldest column first
-    codes = torch.empty(U, n_steps, dtype=torch.int32, device=dev)
-    note_out = torch.empty(U, Q, dtype=torch.float32, device=dev)
-    prev_out = torch.empty(U, K1, Q, dtype=torch.float32, device=dev)
-    sync = torch.zeros(U * _lib.decode_sync_granules(N, pack.Dp, eng.S), dtype=torch.int64, device=dev)
-    dil = (ctypes.c_int32 * N)(*eng.dil)
-    q_off = _queue_offsets(eng, rw)
-    qoff = (ctypes.c_int64 * N)(*[int(v) for v in q_off])
-    bias = pack.o_bias is not None
-    pk = pack.chain()
-    qbuf = _queue_buffer(rings)
-    args = (pack.k, N, pack.Rp, pack.Dp, eng.S, Q, ctypes.cast(dil, ctypes.c_void_p),
-            ctypes.cast(qoff, ctypes.c_void_p), ptr(qbuf), pack.p(pack.o_causal), pack.p(pack.ob_causal) if bias else None,
-            pack.p(pack.o_layers), pack.layer_stride, pack.p(pack.ob_layers) if bias else None,
-            pack.p(pack.o_p1), pack.p(pack.ob_p1) if bias else None, pack.p(pack.o_p2), pack.p(pack.ob_p2) if bias else None,
-            ptr(note0), _ptr_or_none(prev0), ptr(note_out), _ptr_or_none(prev_out), None, ptr(codes), None,
-            0, n_steps, 1 if correct_queue else 0, ptr(sync), U, rings.size(1),
-            smp.temperature, smp.seed, pk[0], pk[1], pk[2], pk[3], pk[4], pk[5], pk[6])
-    if smp.plain:
-        call("wn_decode_batch_fw", *args, _lib.stream())
-    else:
-        call("wn_decode_batch_samp", *args, *_NO_COND, *smp.tail(), _lib.stream())
-    if n_steps >= 4:
-        flags = sync.view(U, -1)[:, -1]
-        if int(flags.abs().max().item()) != 0:
-            raise _lib.WavenetHipError("wn_decode_batch: a hand-off between two decode workgroups timed out")
+    codes, _, _, _ = _launch_decode(net, eng, smp, rings, note0, prev0, U, note_num - 1, 0, 1 if correct_queue else 0,
+                                    "wn_decode_batch: a hand-off between two decode workgroups timed out", check=note_num - 1 >= 4)
     return torch.cat([first.view(U, 1).to(torch.int64), codes.to(torch.int64)], 1)
-
-
-last_error_flags = None        # the error flag word of every utterance of the last decode_batch_cond launch (device tensor)
 
 
 def decode_batch_cond(net, rings, prev0, note0, n_steps, step0=0, pos0=0, forced=None, want_probs=False, temperature=None,
@@ -479,15 +488,11 @@ def decode_batch_cond(net, rings, prev0, note0, n_steps, step0=0, pos0=0, forced
     ids (default: the utterance index); anything beyond a scalar temperature and seed goes through wn_decode_batch_samp.
     Returns (codes int32 (U, n_steps), probabilities (U, n_steps, Q) or None, note_out, prev_out)."""
     eng = net._engine_for(rings.device)
-    pack = getattr(net, "_decode_pack", None)
-    if pack is None or pack.eng is not eng:
-        pack = net._decode_pack = _DecodePack(eng)
-    pack.refresh()
-    dev, N, Q, K1, U = eng.device, eng.N, eng.Q, _taps(eng), rings.size(0)
-    rw = _ring_width(eng)
-    q_off = _queue_offsets(eng, rw)
-    if rings.dim() != 2 or rings.size(1) != max(1, sum(K1 * d * rw for d in eng.dil)) or not rings.is_contiguous():
-        raise ValueError("decode_batch_cond: rings must be (U, %d) contiguous floats" % max(1, sum(K1 * d * rw for d in eng.dil)))
+    pack = _pack_for(net, eng)
+    dev, N, K1, U = eng.device, eng.N, _taps(eng), rings.size(0)
+    n_ring = max(1, sum(K1 * d * pack.Rp for d in eng.dil))
+    if rings.dim() != 2 or rings.size(1) != n_ring or not rings.is_contiguous():
+        raise ValueError("decode_batch_cond: rings must be (U, %d) contiguous floats" % n_ring)
     if U > (1024 if pack.mfma else 128):
         raise ValueError("at most 1024 utterances per launch (128 off the matrix-core path)")
     smp = _Sampling(U, temperature, top_k, top_p, seed, streams, dev)
@@ -501,38 +506,14 @@ def decode_batch_cond(net, rings, prev0, note0, n_steps, step0=0, pos0=0, forced
             raise ValueError("decode_batch_cond: cond_fg must be (U, N, Le, %d) contiguous" % (2 * pack.Dp))
         if cond_p1 is not None and (tuple(cond_p1.shape) != (U, le, eng.S) or not cond_p1.is_contiguous()):
             raise ValueError("decode_batch_cond: cond_p1 must be (U, Le, S) contiguous")
-        shift = (ctypes.c_int32 * (N + 1))(*[int(t[0]) for t in schedule])
-        qs = (ctypes.c_int32 * (N + 1))(*[int(t[1]) for t in schedule])
-    codes = torch.empty(U, n_steps, dtype=torch.int32, device=dev)
-    probs = torch.empty(U, n_steps, Q, dtype=torch.float32, device=dev) if want_probs else None
-    note_out = torch.empty(U, Q, dtype=torch.float32, device=dev)
-    prev_out = torch.empty(U, K1, Q, dtype=torch.float32, device=dev)
-    forced_t = forced.to(device=dev, dtype=torch.int32).contiguous() if forced is not None else None
-    assert forced_t is None or tuple(forced_t.shape) == (U, n_steps)
-    sync = torch.zeros(U * _lib.decode_sync_granules(N, pack.Dp, eng.S), dtype=torch.int64, device=dev)
-    dil = (ctypes.c_int32 * N)(*eng.dil)
-    qoff = (ctypes.c_int64 * N)(*[int(v) for v in q_off])
-    bias = pack.o_bias is not None
-    pk = pack.chain()
-    args = (pack.k, N, pack.Rp, pack.Dp, eng.S, Q, ctypes.cast(dil, ctypes.c_void_p),
-            ctypes.cast(qoff, ctypes.c_void_p), ptr(rings), pack.p(pack.o_causal), pack.p(pack.ob_causal) if bias else None,
-            pack.p(pack.o_layers), pack.layer_stride, pack.p(pack.ob_layers) if bias else None,
-            pack.p(pack.o_p1), pack.p(pack.ob_p1) if bias else None, pack.p(pack.o_p2), pack.p(pack.ob_p2) if bias else None,
-            ptr(note0), _ptr_or_none(prev0), ptr(note_out), _ptr_or_none(prev_out), ptr(forced_t), ptr(codes), ptr(probs),
-            step0, n_steps, 1, ptr(sync), U, rings.size(1), smp.temperature, smp.seed,
-            pk[0], pk[1], pk[2], pk[3], pk[4], pk[5], pk[6],
-            ptr(cond_fg), cond_fg[0].numel() if cond_fg is not None else 0, ptr(cond_p1), cond_p1[0].numel() if cond_p1 is not None else 0,
-            ctypes.cast(shift, ctypes.c_void_p) if shift is not None else None, ctypes.cast(qs, ctypes.c_void_p) if qs is not None else None,
-            le, int(pos0))
-    if smp.plain:
-        call("wn_decode_batch_cond", *args, _lib.stream())
-    else:
-        call("wn_decode_batch_samp", *args, *smp.tail(), _lib.stream())
-    global last_error_flags
-    flags = last_error_flags = sync.view(U, -1)[:, -1]      # the error flag word of every utterance
-    if int(flags.abs().max().item()) != 0:
-        raise _lib.WavenetHipError("wn_decode_batch_cond: a hand-off between two decode workgroups timed out")
-    return codes, probs, note_out, prev_out
+        shift = ctypes.cast((ctypes.c_int32 * (N + 1))(*[int(t[0]) for t in schedule]), ctypes.c_void_p)
+        qs = ctypes.cast((ctypes.c_int32 * (N + 1))(*[int(t[1]) for t in schedule]), ctypes.c_void_p)
+    assert forced is None or tuple(forced.shape) == (U, n_steps)
+    cond = (ptr(cond_fg), cond_fg[0].numel() if cond_fg is not None else 0, ptr(cond_p1),
+            cond_p1[0].numel() if cond_p1 is not None else 0, shift, qs, le, int(pos0))
+    return _launch_decode(net, eng, smp, rings, note0, prev0, U, n_steps, step0, 1,
+                          "wn_decode_batch_cond: a hand-off between two decode workgroups timed out", forced=forced,
+                          want_probs=want_probs, cond=cond)
 
 
 def sample_logits(logits, temperature=1.0, top_k=None, top_p=None, seed=0, step0=0, u=None, want_probs=False, streams=None):

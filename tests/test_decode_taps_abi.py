@@ -2,8 +2,7 @@
 with a wn_last_error message before anything is launched, so no device is needed.  Pointers below are never dereferenced."""
 import ctypes
 
-P = 1 << 20            # "some non-NULL address"
-_KEEP = []             # the host arrays of the last argument list stay alive
+from tests.decode_args import decode_args
 
 
 def _lib():
@@ -15,16 +14,7 @@ def _lib():
 
 
 def _args(lib, **over):
-    dil = (ctypes.c_int32 * 2)(1, 2)
-    qoff = (ctypes.c_int64 * 2)(0, 64)
-    _KEEP[:] = [dil, qoff]
-    a = dict(filter_width=3, n_layers=2, R=32, D=32, S=64, Q=256, dil=ctypes.cast(dil, ctypes.c_void_p),
-             qoff=ctypes.cast(qoff, ctypes.c_void_p), queues=P, w_causal=P, b_causal=None, w_layers=P, layer_stride=4096,
-             b_layers=None, w_p1=P, b_p1=None, w_p2=P, b_p2=None, note0=P, prev0=P, note_out=P, prev_out=P, forced=None,
-             codes_out=P, probs_out=None, step0=0, n_steps=4, push_input=1, sync=P, n_utt=1, queues_ustride=0,
-             temperature=0.0, seed=0, pk=None, pk_fg0=0, pk_d0=0, pk_lstride=0, pk_skip=-1, pk_p1=-1, pk_p2=-1, stream=None)
-    a.update(over)
-    return list(a.values())
+    return decode_args("wn_decode_batch_fw", **{"filter_width": 3, **over})
 
 
 def _refused(lib, what, **over):
