@@ -42,8 +42,11 @@ extern "C" {
 
 typedef void* wn_stream_t;                 /* hipStream_t */
 enum { WN_F16X3 = 0, WN_F16X1 = 1, WN_BF16X3 = 2, WN_BF16X1 = 3 };
-#define WN_ABI_VERSION 8
+#define WN_ABI_VERSION 9
 #define WN_CE_NUM_PARTIALS 1024
+#define WN_GUARD_NUM_PARTIALS 256           /* workgroups of wn_grad_guard's first launch = entries of its partials */
+#define WN_GUARD_PARTIALS_BYTES (WN_GUARD_NUM_PARTIALS * 12)   /* bytes of `partials`: a double and a uint32 per workgroup */
+#define WN_GUARD_STATE_BYTES 48             /* sizeof(wn_guard_state) */
 
 int wn_version(void);
 const char* wn_last_error(void);
@@ -326,6 +329,50 @@ int wn_sgd_flat(float* p, const float* g, float* momentum_buf, int64_t n, float 
                 int first_step, wn_stream_t stream);
 int wn_rmsprop_flat(float* p, const float* g, float* square_avg, float* momentum_buf, int64_t n, float lr, float alpha,
                     float eps, float momentum, float gscale, wn_stream_t stream);
+/* ---- Guarded optimizer step (ABI 9): global-norm clipping and the skipping of a non-finite step, decided ON THE DEVICE.
+ * Replaces torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm) followed by the optimizer's step (wavenet/train.py:28-42,
+ * 182 - the reference has neither the clip nor a guard; a NaN gradient there ends the run), with no host read-back between the
+ * backward and the update, so a host that runs ahead of the device keeps doing so and every call is legal under stream capture.
+ *
+ * wn_guard_state: the device-resident block one optimizer owns (WN_GUARD_STATE_BYTES bytes, 8-byte aligned, zeroed by the caller
+ * before the first step; wn_grad_guard rewrites the first four fields at every call and advances the rest). */
+typedef struct wn_guard_state {
+    float norm;          /* L2 norm of gscale * g over the whole buffer at the last call (summed in float64) */
+    float coef;          /* factor the guarded update applies to gscale * g: 1, or max_norm / (norm + 1e-6) when that is below 1
+                          * (clip_grad_norm_'s rule); NaN when the gradient held a non-finite element or its norm is not finite */
+    uint32_t nonfinite;  /* elements of the last gradient for which the float32 value gscale * g is NaN or +-inf */
+    uint32_t skip;       /* 1: the guarded update that follows returns without touching anything; else 0 */
+    uint64_t n_taken;    /* steps applied so far - Adam's t, and SGD's "first step" is n_taken == 1.  The caller may seed it
+                          * (a restored run) while no step is in flight */
+    uint64_t n_clipped;  /* of those, steps with coef < 1 */
+    uint64_t n_skipped;  /* steps skipped so far */
+    float bc1;           /* 1 - beta1^n_taken, in float64 from the device's counter, written at every step taken */
+    float bc2;           /* 1 - beta2^n_taken */
+} wn_guard_state;
+/* One pass over g (n floats, ANY 4-byte aligned address) and the decision, two launches on `stream`, no allocation, no
+ * synchronisation, no atomics (the result is a pure function of g, n, gscale, the arguments and the state before):
+ *   nonfinite, norm as above; broken = nonfinite > 0 or norm not finite;
+ *   skip = skip_nonfinite != 0 and broken;
+ *   coef = NaN when broken (an unskipped non-finite step turns the parameters into NaN at once, as the unguarded step does);
+ *          else 1 when max_norm <= 0 (no clipping); else min(1, max_norm / (norm + 1e-6));
+ *   a skipped step adds 1 to n_skipped and leaves n_taken, n_clipped, bc1, bc2 as they are - Adam's bias correction does not
+ *   advance; any other step adds 1 to n_taken, 1 to n_clipped when coef < 1, and rewrites bc1 / bc2 from beta1 / beta2 (pass 0
+ *   for an optimizer that has none).
+ * partials: WN_GUARD_PARTIALS_BYTES bytes of device scratch, 8-byte aligned.  n == 0 is legal (g may be NULL): norm 0, coef 1, a
+ * step taken.  NULL partials / state, or NULL g with n > 0: -4, the argument named in wn_last_error. */
+int wn_grad_guard(const float* g, int64_t n, float gscale, float max_norm, int skip_nonfinite, float beta1, float beta2,
+                  void* partials, wn_guard_state* state, wn_stream_t stream);
+/* wn_adam_flat / wn_sgd_flat / wn_rmsprop_flat after a wn_grad_guard of the same g, n, gscale on the same stream: the same
+ * arithmetic with gscale * coef * g as the gradient; with state->skip set they write nothing (parameters, moments and momentum
+ * buffers stay bit for bit).  Adam takes its bias corrections from the state block (no bias_corr arguments); SGD's first step -
+ * the momentum buffer is SET to the gradient - is the first step TAKEN (state->n_taken == 1; no first_step argument).
+ * NULL rules as for the unguarded entries, plus `state`; n == 0 returns 0. */
+int wn_adam_flat_guarded(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                         float gscale, const wn_guard_state* state, wn_stream_t stream);
+int wn_sgd_flat_guarded(float* p, const float* g, float* momentum_buf, int64_t n, float lr, float momentum, float gscale,
+                        const wn_guard_state* state, wn_stream_t stream);
+int wn_rmsprop_flat_guarded(float* p, const float* g, float* square_avg, float* momentum_buf, int64_t n, float lr, float alpha,
+                            float eps, float momentum, float gscale, const wn_guard_state* state, wn_stream_t stream);
 /* The reference's nn.DataParallel gradient reduction (wavenet/train.py:116-122) as ONE in-place sum over the ranks of the flat
  * fp32 gradient buffer: ncclAllReduce(buf, buf, n, ncclFloat32, ncclSum, comm, stream) on the caller's RCCL communicator
  * (`comm` = an ncclComm_t).  The 1 / world_size of the mean goes into wn_adam_flat's gscale.  Returns -5 when RCCL is neither

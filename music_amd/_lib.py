@@ -12,7 +12,9 @@ LIB_PATH = os.environ.get("WAVENET_HIP_LIB") or os.path.join(_HERE, "libwavenet_
 F16X3, F16X1, BF16X3, BF16X1 = 0, 1, 2, 3
 MODE_NAMES = {"f16x3": F16X3, "f16x1": F16X1, "bf16x3": BF16X3, "bf16x1": BF16X1}
 CE_NUM_PARTIALS = 1024
-ABI_VERSION = 8
+ABI_VERSION = 9
+GUARD_NUM_PARTIALS = 256       # include/wavenet_hip.h WN_GUARD_NUM_PARTIALS
+GUARD_PARTIALS_BYTES = GUARD_NUM_PARTIALS * 12
 
 _p = ctypes.c_void_p
 _i = ctypes.c_int
@@ -79,6 +81,10 @@ SIGNATURES = {
     "wn_adam_flat": [_p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _f, _f, _p],
     "wn_sgd_flat": [_p, _p, _p, _l, _f, _f, _f, _i, _p],
     "wn_rmsprop_flat": [_p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _p],
+    "wn_grad_guard": [_p, _l, _f, _f, _i, _f, _f, _p, _p, _p],
+    "wn_adam_flat_guarded": [_p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _p, _p],
+    "wn_sgd_flat_guarded": [_p, _p, _p, _l, _f, _f, _f, _p, _p],
+    "wn_rmsprop_flat_guarded": [_p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _p, _p],
     "wn_coll_available": [],
     "wn_comm_unique_id": [_p],
     "wn_comm_create": [_i, _i, _p, _p],
@@ -106,6 +112,14 @@ class Sampling(ctypes.Structure):
     """wn_sampling (include/wavenet_hip.h): one utterance's / one row's sampling settings, 24 bytes."""
     _fields_ = [("temperature", ctypes.c_float), ("top_p", ctypes.c_float), ("top_k", ctypes.c_int32),
                 ("stream", ctypes.c_uint32), ("seed", ctypes.c_uint64)]
+
+
+class GuardState(ctypes.Structure):
+    """wn_guard_state (include/wavenet_hip.h): the device-resident block of one guarded optimizer, 48 bytes."""
+    _fields_ = [("norm", ctypes.c_float), ("coef", ctypes.c_float), ("nonfinite", ctypes.c_uint32), ("skip", ctypes.c_uint32),
+                ("n_taken", ctypes.c_uint64), ("n_clipped", ctypes.c_uint64), ("n_skipped", ctypes.c_uint64),
+                ("bc1", ctypes.c_float), ("bc2", ctypes.c_float)]
+
 
 _lib = None
 

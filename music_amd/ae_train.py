@@ -16,7 +16,9 @@ of a loss line that does not contain it (:110-116: ``int("is")``), is the number
     train()      reads ./params/train_params.json, ./params/model_params.json, ./params/dataset_params.json
 
 Optional key in train_params.json (as in music_amd/train.py): ``"fused_step"`` (bool, Adam only) - the whole step runs
-as forward + one softmax/CE/backward kernel + backward + flat Adam on the engine, without autograd.
+as forward + one softmax/CE/backward kernel + backward + flat Adam on the engine, without autograd.  ``"max_grad_norm"``
+(float) and ``"skip_nonfinite"`` (bool): global-norm clipping of the gradient and the skipping of a non-finite step
+(music_amd/guard.py; on the device for the fused step), with a line per ``print_every`` in ``guard_log.log``.
 """
 import glob
 import os
@@ -27,11 +29,13 @@ import torch.optim as optim
 
 try:
     from . import dist as wdist
+    from . import guard
     from .faster_audio_data import audio_data_loader
     from .model1 import wavenet_autoencoder
     from .train import get_params, load_model
 except ImportError:
     from music_amd import dist as wdist
+    from music_amd import guard
     from music_amd.faster_audio_data import audio_data_loader
     from music_amd.model1 import wavenet_autoencoder
     from music_amd.train import get_params, load_model
@@ -44,8 +48,39 @@ def get_arguments():
             get_params('./params/dataset_params.json'))
 
 
-def get_optimizer(model, optimizer_type, learning_rate, momentum1=False):
-    """wavenet_autoencoder/train.py:26-34 (with ``optim.sgd`` spelled ``optim.SGD``)."""
+def _host_guarded(cls):
+    """`cls` (a torch optimizer class) with the guard's rule applied on the host before every step (music_amd/guard.py): the step of
+    this harness is torch's own per-tensor path, where a read-back per step is already the rule."""
+    class Guarded(guard.GuardedOptimizer, cls):
+        def __init__(self, params, max_grad_norm, skip_nonfinite, **kw):
+            super().__init__(params, **kw)
+            self._guard_setup(max_grad_norm, skip_nonfinite)
+
+        def load_state_dict(self, state_dict):
+            super().load_state_dict(state_dict)
+            self._guard_reseed()
+
+        def step(self, closure=None):
+            return self._torch_step(closure)
+    Guarded.__name__ = Guarded.__qualname__ = "Guarded" + cls.__name__
+    return Guarded
+
+
+def get_optimizer(model, optimizer_type, learning_rate, momentum1=False, max_grad_norm=None, skip_nonfinite=False):
+    """wavenet_autoencoder/train.py:26-34 (with ``optim.sgd`` spelled ``optim.SGD``).  max_grad_norm / skip_nonfinite: the same
+    optimizer with its gradient clipped to that global norm / a non-finite step not applied (not for 'lbfgs', whose closure is
+    evaluated many times per step)."""
+    if guard.enabled(max_grad_norm, skip_nonfinite):
+        kw = dict(max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, lr=learning_rate)
+        if optimizer_type == 'sgd':
+            return _host_guarded(optim.SGD)(model.parameters(), momentum=momentum1 or 0, **kw)
+        if optimizer_type == 'RMSprop':
+            return _host_guarded(optim.RMSprop)(model.parameters(), momentum=momentum1 or 0, **kw)
+        if optimizer_type == 'Adam':
+            return _host_guarded(optim.Adam)(model.parameters(), **kw)
+        if optimizer_type == 'lbfgs':
+            raise ValueError("max_grad_norm / skip_nonfinite do not apply to the 'lbfgs' optimizer")
+        return None
     if optimizer_type == 'sgd':
         return optim.SGD(model.parameters(), lr=learning_rate, momentum=momentum1 or 0)
     if optimizer_type == 'RMSprop':
@@ -109,8 +144,10 @@ def train():
     if cuda_available:
         net = net.cuda()
     wdist.broadcast_parameters(list(net.parameters()))
+    max_gn, skip_nf = guard.guard_options(train_params)
     optimizer = get_optimizer(net, train_params.get("optimizer_type", train_params.get("optimizer", "Adam")),
-                              train_params["learning_rate"], train_params.get("momentum", False))
+                              train_params["learning_rate"], train_params.get("momentum", False), max_grad_norm=max_gn,
+                              skip_nonfinite=skip_nf)
     loss_func = nn.CrossEntropyLoss()
     is_writer = rank == 0
     loss_log_file = store_log_file = None
@@ -130,7 +167,13 @@ def train():
     engine = None
     if fused:
         engine = net._engine_for(device)
-        engine.adam_init(lr=train_params["learning_rate"])
+        engine.adam_init(lr=train_params["learning_rate"], max_grad_norm=max_gn, skip_nonfinite=skip_nf)
+    guard_log = None
+    if guard.enabled(max_gn, skip_nf) and is_writer:
+        guard_log = guard.GuardLog(
+            train_params["log_dir"] + 'guard_log.log',
+            lambda: engine.guard_report() if fused else optimizer.guard_report(),
+            lambda: guard.engine_named_grads(engine) if fused else [(n, p.grad) for n, p in net.named_parameters()])
     for epoch in range(train_params["num_epochs"]):
         for i_batch, sampled_batch in enumerate(dataloader):
             piece, target = sampled_batch["audio_piece"], sampled_batch["audio_target"]
@@ -171,6 +214,8 @@ def train():
                 if is_writer:
                     loss_log_file.writelines('Average loss is ' + str(total_loss.item() / train_params["print_every"]) + '\n')
                     loss_log_file.flush()
+                if guard_log is not None:
+                    guard_log.tick(num_trained)
                 total_loss.zero_()
         if (epoch + 1) % train_params["check_point_every"] == 0 and is_writer:
             stored = glob.glob(train_params["restore_dir"] + "*.model")

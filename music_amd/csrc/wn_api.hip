@@ -327,6 +327,34 @@ int wn_rmsprop_flat(float* p, const float* g, float* square_avg, float* momentum
     if (n > 0) WN_REQUIRE("wn_rmsprop_flat", p, g);
     return wn_launch_rmsprop(p, g, square_avg, momentum_buf, n, lr, alpha, eps, momentum, gscale, (hipStream_t)stream);
 }
+
+// ---- guarded step (wn_guard.hip) ----
+int wn_grad_guard(const float* g, int64_t n, float gscale, float max_norm, int skip_nonfinite, float beta1, float beta2, void* partials,
+                  wn_guard_state* state, wn_stream_t stream) {
+    WN_REQUIRE("wn_grad_guard", partials, state);
+    if (n > 0) WN_REQUIRE("wn_grad_guard", g);
+    if (n < 0) return wn_set_error_msg(-4, "wn_grad_guard: n is negative");
+    if (((uintptr_t)g & 3) || ((uintptr_t)partials & 7) || ((uintptr_t)state & 7))
+        return wn_set_error_msg(-4, "wn_grad_guard: g needs 4-byte, partials and state 8-byte alignment");
+    return wn_launch_grad_guard(g, n, gscale, max_norm, skip_nonfinite, beta1, beta2, partials, state, (hipStream_t)stream);
+}
+int wn_adam_flat_guarded(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                         float gscale, const wn_guard_state* state, wn_stream_t stream) {
+    if (n > 0) WN_REQUIRE("wn_adam_flat_guarded", p, g, m, v, state);
+    return wn_launch_adam_guarded(p, g, m, v, n, lr, beta1, beta2, eps, gscale, state, (hipStream_t)stream);
+}
+int wn_sgd_flat_guarded(float* p, const float* g, float* momentum_buf, int64_t n, float lr, float momentum, float gscale,
+                        const wn_guard_state* state, wn_stream_t stream) {
+    if (momentum != 0.f && !momentum_buf) return wn_set_error_msg(-4, "wn_sgd_flat_guarded: momentum needs its buffer");
+    if (n > 0) WN_REQUIRE("wn_sgd_flat_guarded", p, g, state);
+    return wn_launch_sgd_guarded(p, g, momentum_buf, n, lr, momentum, gscale, state, (hipStream_t)stream);
+}
+int wn_rmsprop_flat_guarded(float* p, const float* g, float* square_avg, float* momentum_buf, int64_t n, float lr, float alpha, float eps,
+                            float momentum, float gscale, const wn_guard_state* state, wn_stream_t stream) {
+    if (!square_avg || (momentum > 0.f && !momentum_buf)) return wn_set_error_msg(-4, "wn_rmsprop_flat_guarded: missing state buffer");
+    if (n > 0) WN_REQUIRE("wn_rmsprop_flat_guarded", p, g, state);
+    return wn_launch_rmsprop_guarded(p, g, square_avg, momentum_buf, n, lr, alpha, eps, momentum, gscale, state, (hipStream_t)stream);
+}
 int wn_coll_available(void) { return wn_coll_loaded(); }
 int wn_comm_unique_id(char* id128) { return wn_coll_unique_id(id128); }
 int wn_comm_create(int nranks, int rank, const char* id128, void** comm) { return wn_coll_create(nranks, rank, id128, comm); }

@@ -4,6 +4,7 @@
 // (wavenet/faster_audio_data.py:62-83), and mu-law (wavenet/audio_func.py:5-39).
 #include "wn_common.h"
 #include "wn_kernels.h"
+#include "wn_optim.h"
 
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
@@ -160,15 +161,7 @@ __global__ void adam_k(float* __restrict__ p, const float* __restrict__ g, float
                        float bc2, float gscale) {
     long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const long stride = (long)gridDim.x * blockDim.x;
-    const float step = lr / bc1, rs = 1.0f / sqrtf(bc2);
-    for (; i < n; i += stride) {
-        float gi = g[i] * gscale;
-        float mi = b1 * m[i] + (1.0f - b1) * gi;
-        float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
-        m[i] = mi;
-        v[i] = vi;
-        p[i] -= step * mi / (sqrtf(vi) * rs + eps);
-    }
+    wn_adam_body<false>(p, g, m, v, i, stride, n, lr, b1, b2, eps, bc1, bc2, gscale, 1.0f);          // the arithmetic: wn_optim.h
 }
 int wn_launch_adam(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2,
                    float eps, float bc1, float bc2, float gscale, hipStream_t st) {
@@ -190,14 +183,7 @@ __global__ void sgd_k(float* __restrict__ p, const float* __restrict__ g, float*
                       float gscale, int first) {
     long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const long stride = (long)gridDim.x * blockDim.x;
-    for (; i < n; i += stride) {
-        float gi = g[i] * gscale;
-        if (momentum != 0.f) {
-            gi = first ? gi : buf[i] * momentum + gi;
-            buf[i] = gi;
-        }
-        p[i] += -lr * gi;
-    }
+    wn_sgd_body<false>(p, g, buf, i, stride, n, lr, momentum, gscale, first, 1.0f);
 }
 int wn_launch_sgd(float* p, const float* g, float* buf, long n, float lr, float momentum, float gscale, int first, hipStream_t st) {
     if (n <= 0) return 0;
@@ -211,19 +197,7 @@ __global__ void rmsprop_k(float* __restrict__ p, const float* __restrict__ g, fl
                           float lr, float alpha, float eps, float momentum, float gscale) {
     long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const long stride = (long)gridDim.x * blockDim.x;
-    for (; i < n; i += stride) {
-        const float gi = g[i] * gscale;
-        const float s = sq[i] * alpha + ((1.0f - alpha) * gi) * gi;
-        sq[i] = s;
-        const float avg = sqrtf(s) + eps;
-        if (momentum > 0.f) {
-            const float b = buf[i] * momentum + gi / avg;
-            buf[i] = b;
-            p[i] += -lr * b;
-        } else {
-            p[i] += -lr * (gi / avg);
-        }
-    }
+    wn_rmsprop_body<false>(p, g, sq, buf, i, stride, n, lr, alpha, eps, momentum, gscale, 1.0f);
 }
 int wn_launch_rmsprop(float* p, const float* g, float* sq, float* buf, long n, float lr, float alpha, float eps, float momentum,
                       float gscale, hipStream_t st) {

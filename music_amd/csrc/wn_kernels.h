@@ -212,6 +212,16 @@ int wn_launch_adam(float* p, const float* g, float* m, float* v, long n, float l
 int wn_launch_sgd(float* p, const float* g, float* buf, long n, float lr, float momentum, float gscale, int first, hipStream_t st);
 int wn_launch_rmsprop(float* p, const float* g, float* sq, float* buf, long n, float lr, float alpha, float eps, float momentum,
                       float gscale, hipStream_t st);
+// wn_guard.hip: gradient statistics + decision (two launches), and the three updates reading the decision
+struct wn_guard_state;                      // include/wavenet_hip.h
+int wn_launch_grad_guard(const float* g, long n, float gscale, float max_norm, int skip_nonfinite, float beta1, float beta2,
+                         void* partials, wn_guard_state* state, hipStream_t st);
+int wn_launch_adam_guarded(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps, float gscale,
+                           const wn_guard_state* state, hipStream_t st);
+int wn_launch_sgd_guarded(float* p, const float* g, float* buf, long n, float lr, float momentum, float gscale,
+                          const wn_guard_state* state, hipStream_t st);
+int wn_launch_rmsprop_guarded(float* p, const float* g, float* sq, float* buf, long n, float lr, float alpha, float eps, float momentum,
+                              float gscale, const wn_guard_state* state, hipStream_t st);
 int wn_launch_gather_grads(const float* packed, const int32_t* idx, float* flat_grad, int n, hipStream_t st);
 int wn_launch_gather_grads2(const float* packed, const int32_t* idx, const int32_t* idx2, float* flat_grad, int n, hipStream_t st);
 int wn_launch_onehot(const int32_t* idx, float* out, int batch, int q, int t, int scrambled, hipStream_t st);

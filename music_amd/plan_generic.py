@@ -15,7 +15,7 @@ conditioning) arrives as data.  PyTorch is used for device memory and streams on
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, guard
 from ._lib import call, ptr
 from .engine import SLACK, PAD_BACK, WorkspacePool, _pad, pack_index
 
@@ -323,12 +323,22 @@ class GeneralPlan:
         self._throttle.leave()
         return loss
 
-    def adam_init(self, lr=1e-4, betas=(0.9, 0.999), eps=1e-8):
+    def adam_init(self, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, skip_nonfinite=False):
+        """max_grad_norm / skip_nonfinite: the guarded step (music_amd/guard.py) - the gradient is clipped to that global L2 norm and
+        a non-finite one is skipped, both decided on the device; unset, adam_step is the one wn_adam_flat launch."""
         self.adam_state = dict(m=torch.zeros_like(self.flat), v=torch.zeros_like(self.flat), t=0,
                                lr=lr, b1=betas[0], b2=betas[1], eps=eps)
+        guard.adam_init_guard(self.adam_state, self.flat.device, max_grad_norm, skip_nonfinite)
+
+    def guard_report(self):
+        """The guard's state block read back (the only sync of the guarded step): norm / coef / taken / clipped / skipped /
+        nonfinite, adam_state["t"] set to the steps taken; None without a guard."""
+        return guard.engine_guard_report(self)
 
     def adam_step(self, gscale=1.0):
         s = self.adam_state
+        if s.get("guard") is not None:
+            return guard.adam_step_guarded(self, gscale)
         s["t"] += 1
         call("wn_adam_flat", ptr(self.flat), ptr(self.flat_grad), ptr(s["m"]), ptr(s["v"]), self.spec.total,
              s["lr"], s["b1"], s["b2"], s["eps"], 1.0 - s["b1"] ** s["t"], 1.0 - s["b2"] ** s["t"], gscale, _lib.stream())

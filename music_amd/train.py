@@ -15,7 +15,15 @@ Differences, all additive:
     whole step runs as forward+CE+backward+flat-Adam kernels without autograd), ``"save_optimizer_state"``
     (bool, SURVEY 8f4: the reference drops the optimizer state at every checkpoint, so a resumed Adam /
     momentum run restarts cold; with this key ``wavenet{N}.opt`` is written next to ``wavenet{N}.model``
-    and read back when that model is restored — the .model file itself stays the reference's format).
+    and read back when that model is restored — the .model file itself stays the reference's format),
+    ``"max_grad_norm"`` (float: the gradient is clipped to that global L2 norm, torch.nn.utils.clip_grad_norm_'s rule) and
+    ``"skip_nonfinite"`` (bool: a step whose gradient holds a NaN or an inf is not applied) — both decided on the device
+    (music_amd/guard.py), after the all-reduce under data parallelism so that every rank takes the same decision; rank 0 then
+    appends a line per ``print_every`` to ``guard_log.log`` and warns once on stderr when a step was skipped (the tensors it
+    names are those non-finite in the gradient current at that ``print_every``: best effort, nothing is read back per step).
+    Scaling under data parallelism: a ragged shard's ``dp_scale`` differs per rank and has to multiply the local buffer before
+    the sum; the 1 / world of the mean is folded into the guard's ``gscale`` on the fused step, while the autograd path keeps
+    it in ``allreduce_gradients`` (the gradients are the optimizer's ``.grad`` tensors there, which torch's own step reads too).
 """
 from collections import OrderedDict
 from functools import cmp_to_key
@@ -29,10 +37,12 @@ import torch.optim as optim
 
 try:
     from . import dist as wdist
+    from . import guard
     from .faster_audio_data import audio_data_loader
     from .model import wavenet
 except ImportError:                                  # run as a script / bare modules from the CWD
     from music_amd import dist as wdist
+    from music_amd import guard
     from music_amd.faster_audio_data import audio_data_loader
     from music_amd.model import wavenet
 
@@ -48,7 +58,7 @@ def get_arguments():
             get_params('./params/dataset_params.json'))
 
 
-class FlatAdam(optim.Adam):
+class FlatAdam(guard.GuardedOptimizer, optim.Adam):
     """``torch.optim.Adam`` whose ``step()`` is ONE ``wn_adam_flat`` launch when it can be.
 
     The module's parameters are views of one flat buffer (music_amd/engine.py) and the gradients autograd hands to them
@@ -59,9 +69,10 @@ class FlatAdam(optim.Adam):
     does not cover (parameters not on the flat buffer yet, gradients that are not one flat tensor, weight decay /
     amsgrad / maximize / closures, several parameter groups) falls through to ``torch.optim.Adam.step`` on the same state."""
 
-    def __init__(self, model, lr):
+    def __init__(self, model, lr, max_grad_norm=None, skip_nonfinite=False):
         super().__init__(model.parameters(), lr=lr)
         self._model = model
+        self._guard_setup(max_grad_norm, skip_nonfinite)
         self._flat = None            # (engine, m, v, steps): flat moments of that engine's flat parameter buffer
 
     def _fast_state(self):
@@ -101,6 +112,7 @@ class FlatAdam(optim.Adam):
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
         self._flat = None                                 # re-adopt the loaded tensors at the next step
+        self._guard_reseed()
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -117,13 +129,19 @@ class FlatAdam(optim.Adam):
             if ok:
                 from music_amd import _lib
                 grp = self.param_groups[0]
+                if self._guard_opts is not None:          # guard + guarded update; the step counters follow the device's (state_dict())
+                    gd = self._guard_get(eng.flat.device)
+                    gd.run(gbase, eng.spec.total)
+                    _lib.call("wn_adam_flat_guarded", eng.flat.data_ptr(), gbase, m.data_ptr(), v.data_ptr(), eng.spec.total,
+                              float(grp["lr"]), grp["betas"][0], grp["betas"][1], grp["eps"], 1.0, gd.state_ptr(), _lib.stream())
+                    return None
                 torch._foreach_add_(steps, 1.0)
                 t = float(steps[0])
                 b1, b2 = grp["betas"]
                 _lib.call("wn_adam_flat", eng.flat.data_ptr(), gbase, m.data_ptr(), v.data_ptr(), eng.spec.total,
                           float(grp["lr"]), b1, b2, grp["eps"], 1.0 - b1 ** t, 1.0 - b2 ** t, 1.0, _lib.stream())
                 return None
-        return super().step(closure)
+        return self._torch_step(closure)
 
 
 def _flat_layout(opt, model, plain_group):
@@ -177,19 +195,26 @@ def _flat_views(opt, eng, params, key, cache):
     return flat, had
 
 
-class FlatSGD(optim.SGD):
+class FlatSGD(guard.GuardedOptimizer, optim.SGD):
     """``torch.optim.SGD(model.parameters(), lr, momentum)`` (wavenet/train.py:28-31) whose ``step()`` is ONE ``wn_sgd_flat``
     launch when it can be (see FlatAdam): same state (``momentum_buffer`` per parameter, views of one flat buffer), same
     ``state_dict``; anything the kernel does not cover (dampening, Nesterov, weight decay, maximize, closures, parameters or
     gradients off the flat buffers, parameters with and without a momentum buffer mixed) falls through to torch's own step."""
 
-    def __init__(self, model, lr, momentum):
+    def __init__(self, model, lr, momentum, max_grad_norm=None, skip_nonfinite=False):
         super().__init__(model.parameters(), lr=lr, momentum=momentum)
         self._model, self._cache = model, {}
+        self._guard_setup(max_grad_norm, skip_nonfinite)
+
+    def _guard_seed(self):
+        # torch's SGD keeps no step counter: existing momentum buffers mean "not the first step" (one step the guard did not see)
+        have = any(st.get("momentum_buffer") is not None for st in self.state.values())
+        return (1, 1) if have else (0, 0)
 
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
         self._cache = {}
+        self._guard_reseed()
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -205,27 +230,35 @@ class FlatSGD(optim.SGD):
             if mom != 0.0:
                 have = sum(1 for p in params if self.state[p].get("momentum_buffer") is not None)
                 if have not in (0, len(params)):
-                    return super().step(closure)
+                    return self._torch_step(closure)
                 flat, _ = _flat_views(self, eng, params, "momentum_buffer", self._cache)
                 buf, first = flat.data_ptr(), 1 if have == 0 else 0
             from music_amd import _lib
+            if self._guard_opts is not None:              # "first step" is the device's: the first step TAKEN
+                gd = self._guard_get(eng.flat.device)
+                gd.run(gbase, eng.spec.total)
+                _lib.call("wn_sgd_flat_guarded", eng.flat.data_ptr(), gbase, buf, eng.spec.total, float(grp["lr"]), mom, 1.0, gd.state_ptr(),
+                          _lib.stream())
+                return None
             _lib.call("wn_sgd_flat", eng.flat.data_ptr(), gbase, buf, eng.spec.total, float(grp["lr"]), mom, 1.0, first, _lib.stream())
             return None
-        return super().step(closure)
+        return self._torch_step(closure)
 
 
-class FlatRMSprop(optim.RMSprop):
+class FlatRMSprop(guard.GuardedOptimizer, optim.RMSprop):
     """``torch.optim.RMSprop(model.parameters(), lr, momentum=momentum)`` (wavenet/train.py:32-37) whose ``step()`` is ONE
     ``wn_rmsprop_flat`` launch when it can be (see FlatAdam): torch's own state (``step``, ``square_avg``, ``momentum_buffer``; the
     tensors are views of flat buffers), same ``state_dict``; centered / weight decay / maximize / closures fall through to torch."""
 
-    def __init__(self, model, lr, momentum):
+    def __init__(self, model, lr, momentum, max_grad_norm=None, skip_nonfinite=False):
         super().__init__(model.parameters(), lr=lr, momentum=momentum)
         self._model, self._cache = model, {}
+        self._guard_setup(max_grad_norm, skip_nonfinite)
 
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
         self._cache = {}
+        self._guard_reseed()
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -251,23 +284,31 @@ class FlatRMSprop(optim.RMSprop):
                                   torch.as_tensor(step, dtype=torch.float32).detach().cpu().reshape(()).clone())
                     steps.append(st["step"])
                 self._cache["step"] = steps
-            torch._foreach_add_(steps, 1.0)
             from music_amd import _lib
+            if self._guard_opts is not None:              # the step counters follow the device's count (state_dict())
+                gd = self._guard_get(eng.flat.device)
+                gd.run(gbase, eng.spec.total)
+                _lib.call("wn_rmsprop_flat_guarded", eng.flat.data_ptr(), gbase, sq.data_ptr(), buf, eng.spec.total, float(grp["lr"]),
+                          float(grp["alpha"]), float(grp["eps"]), mom, 1.0, gd.state_ptr(), _lib.stream())
+                return None
+            torch._foreach_add_(steps, 1.0)
             _lib.call("wn_rmsprop_flat", eng.flat.data_ptr(), gbase, sq.data_ptr(), buf, eng.spec.total, float(grp["lr"]), float(grp["alpha"]),
                       float(grp["eps"]), mom, 1.0, _lib.stream())
             return None
-        return super().step(closure)
+        return self._torch_step(closure)
 
 
-def get_optimizer(model, optimizer_type, learning_rate, momentum):
+def get_optimizer(model, optimizer_type, learning_rate, momentum, max_grad_norm=None, skip_nonfinite=False):
     """wavenet/train.py:28-42 — 'sgd' / 'rmsprop' (with momentum) / 'adam'; anything else -> None.  Each is torch's own optimizer class
-    (same hyper-parameters, same state_dict) whose step() is one launch on the module's flat buffers when it can be."""
+    (same hyper-parameters, same state_dict) whose step() is one launch on the module's flat buffers when it can be.  max_grad_norm / skip_nonfinite: the guarded
+    step (music_amd/guard.py) - that launch becomes wn_grad_guard + the guarded update."""
+    kw = dict(max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
     if optimizer_type == 'sgd':
-        return FlatSGD(model, lr=learning_rate, momentum=momentum)
+        return FlatSGD(model, lr=learning_rate, momentum=momentum, **kw)
     if optimizer_type == 'rmsprop':
-        return FlatRMSprop(model, lr=learning_rate, momentum=momentum)
+        return FlatRMSprop(model, lr=learning_rate, momentum=momentum, **kw)
     if optimizer_type == 'adam':
-        return FlatAdam(model, lr=learning_rate)          # an optim.Adam (same state_dict); one launch per step on the flat buffers
+        return FlatAdam(model, lr=learning_rate, **kw)          # an optim.Adam (same state_dict); one launch per step on the flat buffers
 
 
 def save_model(model, num_iter, path):
@@ -310,6 +351,7 @@ def _rotate_checkpoints(restore_dir, max_check_points):
 def _optimizer_state(optimizer, engine):
     """What wavenet{N}.opt holds: the torch optimizer's state_dict, or the flat Adam buffers of the fused step."""
     if engine is not None and engine.adam_state is not None:
+        engine.guard_report()                             # guarded: "t" = the steps the device took
         st = engine.adam_state
         return {"kind": "fused_adam", "m": st["m"].detach().cpu().clone(), "v": st["v"].detach().cpu().clone(), "t": int(st["t"])}
     return {"kind": "torch", "state": optimizer.state_dict()}
@@ -327,6 +369,8 @@ def _restore_optimizer_state(path, optimizer, engine_factory):
         engine.adam_state["m"].copy_(blob["m"])
         engine.adam_state["v"].copy_(blob["v"])
         engine.adam_state["t"] = int(blob["t"])
+        if engine.adam_state.get("guard") is not None:
+            engine.adam_state["guard"].seed_taken(int(blob["t"]))
         return engine
     if blob.get("kind") == "torch" and optimizer is not None:
         optimizer.load_state_dict(blob["state"])
@@ -378,8 +422,10 @@ def train():
     print("Writing logging information to ", "{}".format(train_params["log_dir"]))
     print("Models are saved in {}".format(train_params["restore_dir"]))
 
+    max_gn, skip_nf = guard.guard_options(train_params)
+    guarded = guard.enabled(max_gn, skip_nf)
     optimizer = get_optimizer(net, train_params["optimizer"], train_params["learning_rate"],
-                              train_params["momentum"])
+                              train_params["momentum"], max_grad_norm=max_gn, skip_nonfinite=skip_nf)
     loss_func = nn.CrossEntropyLoss()
     if cuda_available:
         loss_func = loss_func.cuda()
@@ -405,9 +451,15 @@ def train():
             if not fused:
                 return None
             e = net._engine_for(device)
-            e.adam_init(lr=train_params["learning_rate"])
+            e.adam_init(lr=train_params["learning_rate"], max_grad_norm=max_gn, skip_nonfinite=skip_nf)
             return e
         engine = _restore_optimizer_state(restored_from[:-len(".model")] + ".opt", optimizer, _fused_engine)
+    guard_log = None
+    if guarded and is_writer:
+        guard_log = guard.GuardLog(
+            train_params["log_dir"] + 'guard_log.log',
+            lambda: (engine.guard_report() if engine is not None else None) if fused else optimizer.guard_report(),
+            lambda: guard.engine_named_grads(engine) if fused else [(n, p.grad) for n, p in net.named_parameters()])
     for epoch in range(train_params["num_epochs"]):
         for i_batch, sampled_batch in enumerate(dataloader):
             piece = sampled_batch["audio_piece"]
@@ -423,13 +475,17 @@ def train():
             if fused:
                 if engine is None:
                     engine = net._engine_for(device)
-                    engine.adam_init(lr=train_params["learning_rate"])
+                    engine.adam_init(lr=train_params["learning_rate"], max_grad_norm=max_gn, skip_nonfinite=skip_nf)
                 if piece is not None:
                     loss = engine.loss_and_grad(piece.contiguous(), target)
                 else:
                     engine.flat_grad.zero_()
-                wdist.allreduce_flat_(engine.flat_grad, average=True, scale=dp_scale)
-                engine.adam_step()
+                if guarded:                               # the sum alone; 1 / world rides in the guard's and the update's gscale
+                    wdist.allreduce_flat_(engine.flat_grad, average=False, scale=dp_scale)
+                    engine.adam_step(gscale=1.0 / world)
+                else:
+                    wdist.allreduce_flat_(engine.flat_grad, average=True, scale=dp_scale)
+                    engine.adam_step()
             else:
                 optimizer.zero_grad()
                 if piece is not None:
@@ -450,6 +506,8 @@ def train():
                     loss_log_file.writelines("Trained over " + str(num_trained) + " pieces," +
                                              "Average loss is " + str(avg_loss) + "\n")
                     loss_log_file.flush()
+                if guard_log is not None:
+                    guard_log.tick(num_trained)
                 total_loss.zero_()
 
         if (epoch + 1) % train_params["check_point_every"] == 0 and is_writer:

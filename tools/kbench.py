@@ -157,6 +157,50 @@ def main():
         fg.generate_codes(netb, start, 8000)
         torch.cuda.synchronize()
         res["decode_bias_samples_per_s"] = round(8000 / (time.perf_counter() - t0), 1)
+    if args.what == "guard":
+        # the guarded optimizer step on config 2's flat buffers: wn_grad_guard (two launches) and the guarded Adam against the plain
+        # one, by HIP events over `reps` back-to-back calls; then the whole fused step guarded / unguarded, alternated
+        import time
+        from music_amd.guard import GradGuard
+        n = eng.spec.total
+        eng.loss_and_grad(x, target)
+        gd = GradGuard(eng.flat.device, 1.0, True, (0.9, 0.999))
+        m, v = torch.zeros_like(eng.flat), torch.zeros_like(eng.flat)
+        p = eng.flat.clone()
+
+        def timed(fn):
+            fn()
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            ev[0].record()
+            for _ in range(args.reps * 20):
+                fn()
+            ev[1].record()
+            torch.cuda.synchronize()
+            return round(ev[0].elapsed_time(ev[1]) / (args.reps * 20) * 1e3, 2)
+        res["guard_floats"] = n
+        res["grad_guard_us"] = timed(lambda: gd.run(ptr(eng.flat_grad), n, 1.0))
+        res["adam_guarded_us"] = timed(lambda: call("wn_adam_flat_guarded", ptr(p), ptr(eng.flat_grad), ptr(m), ptr(v), n, 1e-4, 0.9, 0.999,
+                                                    1e-8, 1.0, gd.state_ptr(), st))
+        res["adam_plain_us"] = timed(lambda: call("wn_adam_flat", ptr(p), ptr(eng.flat_grad), ptr(m), ptr(v), n, 1e-4, 0.9, 0.999, 1e-8,
+                                                  0.1, 0.001, 1.0, st))
+        steps = {"unguarded": [], "guarded": []}
+        for rnd in range(6):                               # alternated, as tools/ab_vars.py does
+            for label in ("unguarded", "guarded"):
+                eng.adam_init(lr=1e-4, max_grad_norm=1.0 if label == "guarded" else None, skip_nonfinite=label == "guarded")
+                for _ in range(3):
+                    eng.loss_and_grad(x, target)
+                    eng.adam_step()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(args.reps * 4):
+                    eng.loss_and_grad(x, target)
+                    eng.adam_step()
+                torch.cuda.synchronize()
+                steps[label].append((time.perf_counter() - t0) / (args.reps * 4) * 1e3)
+        for label, vals in steps.items():
+            res["fused_step_%s_ms" % label] = round(float(np.median(vals)), 4)
+            res["fused_step_%s_ms_all" % label] = [round(t, 4) for t in vals]
+        res["guard_report"] = eng.guard_report()
     if args.what in ("ae", "all"):
         # BASELINE config 4: autoencoder, 30+30 blocks, 64 ch, skip 256, bottleneck 64, pool 512, batch 8 x 16000:
         # forward + CE + backward (fresh conditioning projections every forward, as in the reference)
