@@ -30,7 +30,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from ._lib import call, ptr
-from .engine import SLACK, _Spec, _pad
+from .engine_base import SLACK, _Spec, _pad
 from .plan_generic import NONE3, NONE4, GeneralPlan, PackBuilder, Pass
 
 
@@ -192,12 +192,15 @@ class GenericAutoencoderEngine(GeneralPlan):
         return probs, enc, ws
 
     # ------------------------------------------------------------------ backward
-    def _bwd_buffers(self, buf):
+    def _bwd_buffers(self, buf, add):
         N, lo = self.N, self.rf - 1
-        bw = dict(dR1=buf(self.SP), dU=buf(self.SP), dZ=buf(N * self.DdP), dXd=[buf(self.RdP), buf(self.RdP)], dz=buf(self.DdP),
-                  dfg=buf(2 * self.DdP), dE=buf(self.BwP), dXe=[buf(self.ReP), buf(self.ReP)], dHe=buf(self.DeP))
-        return bw, ([("c2", lo, 1024), ("c1", lo, 1024), ("skip", lo, 2048)] + self._stack_ops("de_fg%d", "de_d%d", "de_causal", N - 1) +
-                    [("bottleneck", lo, 512)] + self._stack_ops("en_dil%d", "en_dense%d", "en_causal", N))
+        for name, chunk in (("c2", 1024), ("c1", 1024), ("skip", 2048)):
+            add(name, lo, chunk)
+        self._add_stack(add, "de_fg%d", "de_d%d", "de_causal", N - 1)
+        add("bottleneck", lo, 512)
+        self._add_stack(add, "en_dil%d", "en_dense%d", "en_causal", N)
+        return dict(dR1=buf(self.SP), dU=buf(self.SP), dZ=buf(N * self.DdP), dXd=[buf(self.RdP), buf(self.RdP)], dz=buf(self.DdP),
+                    dfg=buf(2 * self.DdP), dE=buf(self.BwP), dXe=[buf(self.ReP), buf(self.ReP)], dHe=buf(self.DeP))
 
     def input_grad(self, ws):
         """Gradient of the last backward w.r.t. the module's INPUT (the encoder's and the decoder's causal conv, model1.py:137,158)."""
@@ -272,4 +275,4 @@ class GenericAutoencoderEngine(GeneralPlan):
 
     # ------------------------------------------------------------------ fused training step (wavenet_autoencoder/train.py:146-160)
     def loss_and_grad(self, x, target, cond):
-        return self._fused_step(lambda: self.forward(x, cond, want_probs=False)[2], target)
+        return self._throttled(lambda: self._fused_tail(self.forward(x, cond, want_probs=False)[2], target))

@@ -15,16 +15,9 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, guard
+from . import _lib
 from ._lib import call, ptr
-
-SLACK = 64          # floats in front of every activation buffer
-PAD_BACK = 2048     # floats behind
-
-
-def _pad(n, m):
-    return (n + m - 1) // m * m
-
+from .engine_base import SLACK, PAD_BACK, EngineBase, SlabPlan, WorkspaceHold, WorkspacePool, _Spec, _pad  # noqa: F401 (re-exported)
 
 def pack_positions(mt, ks, chained):
     """Logical A-fragment order -> (row, k) of the effective weight matrix.
@@ -47,103 +40,7 @@ def pack_index(weff, chained=False):
     return weff[row, k].astype(np.int32)
 
 
-class WorkspacePool:
-    """(B, T) -> workspaces of that shape.  A workspace whose activations a pending autograd node still needs is HELD
-    (hold() in the Function's forward, release() after its backward or when the graph dies): the next forward of the
-    same shape then gets ANOTHER workspace instead of overwriting it, so a module can have several forwards in flight
-    (gradient accumulation over micro-batches, the reference's autograd semantics, wavenet/model.py:86-145).  Shapes are
-    evicted one at a time, least recently used first, never one that is held."""
-    MAX_SHAPES = 4
-    MAX_PER_SHAPE = 4
-
-    def __init__(self, make):
-        from collections import OrderedDict
-        self._make = make
-        self._d = OrderedDict()
-        self._last = {}
-
-    def peek(self, B, T):
-        """The workspace the LAST forward of this shape used (held or not) - what a caller inspects after a step; a
-        fresh one if there has been none."""
-        ws = self._last.get((B, T))
-        return ws if ws is not None else self.get(B, T)
-
-    def get(self, B, T):
-        """A workspace for the NEXT forward of this shape: the first one no pending backward holds, else a new one."""
-        key = (B, T)
-        lst = self._d.get(key)
-        if lst is None:
-            if len(self._d) >= self.MAX_SHAPES:
-                for k, wl in self._d.items():
-                    if not any(w.get("held") for w in wl):
-                        del self._d[k]
-                        self._last.pop(k, None)
-                        break
-            lst = self._d[key] = []
-        self._d.move_to_end(key)
-        for ws in lst:
-            if not ws.get("held"):
-                self._last[key] = ws
-                return ws
-        if len(lst) >= self.MAX_PER_SHAPE:
-            # the reference never runs out (autograd just keeps allocating): take the OLDEST waiting forward's workspace over, say
-            # so once, and let a backward that still arrives for it fail loudly (its generation no longer matches)
-            import warnings
-            warnings.warn("music_amd: %d forwards of shape %s are waiting for their backward; the oldest one's activations are "
-                          "reused (run backward(), drop the outputs, or use torch.no_grad() for inference)" % (len(lst), key))
-            ws = min(lst, key=lambda w: w.get("gen", 0))
-            ws["held"] = False
-            self._last[key] = ws
-            return ws
-        ws = self._make(B, T)
-        lst.append(ws)
-        self._last[key] = ws
-        return ws
-
-    def clear(self):
-        self._d.clear()
-        self._last.clear()
-
-    def __len__(self):
-        return sum(len(v) for v in self._d.values())
-
-
-class WorkspaceHold:
-    """Keeps a workspace out of the pool's hands while an autograd node needs it; released explicitly after backward or
-    by garbage collection of the node (an output that was dropped without a backward)."""
-
-    def __init__(self, ws):
-        self.ws, self.gen = ws, ws["gen"]
-        ws["held"] = True
-
-    def release(self):
-        if self.ws is not None and self.ws.get("gen") == self.gen:
-            self.ws["held"] = False
-        self.ws = None
-
-    def __del__(self):
-        self.release()
-
-
-class _Spec:
-    """Offsets of every reference parameter inside the flat buffer (state_dict order)."""
-
-    def __init__(self, named_shapes):
-        self.off, self.shape = {}, {}
-        o = 0
-        for name, shape in named_shapes:
-            self.off[name] = o
-            self.shape[name] = tuple(shape)
-            o += int(np.prod(shape))
-        self.total = o
-
-    def conv(self, name):
-        """int64 array [O, I, k] of flat offsets of a Conv1d weight."""
-        shp = self.shape[name]
-        return self.off[name] + np.arange(int(np.prod(shp)), dtype=np.int64).reshape(shp)
-
-
-class WaveNetEngine:
+class WaveNetEngine(EngineBase):
     def __init__(self, dilations, residual_channels, dilation_channels, skip_channels,
                  quantization_channels=256, filter_width=2, use_bias=False,
                  mode_fwd="f16x3", mode_bwd="bf16x3", device=None):
@@ -176,11 +73,7 @@ class WaveNetEngine:
         _lib.load()
         self._build_spec()
         self._build_packs()
-        self._ws = WorkspacePool(self._make_workspace)
-        self._gen = 0
-        self.adam_state = None
-        self.marks = None            # list of (name, torch.cuda.Event) when profiling is on
-        self.mark_only = None        # optional set of mark names to keep
+        self._init_state()
         # weight-gradient launches that only feed the final slab reduction run on a second HIP stream: the
         # epilogue's three (2 rounds of workgroups at 80 % fill each) then pack into the data-gradient GEMMs'
         # idle CUs (epilogue backward 1.25 -> 1.00 ms)
@@ -191,7 +84,6 @@ class WaveNetEngine:
         # ... or all three in ONE launch per 128-column tile (wn_skip_epilogue_fwd, round 6; 256 skip / 256 quantisation channels, x3
         # modes; WN_EPI_FUSED=0 = the three launches above)
         self.epi_fused = os.environ.get("WN_EPI_FUSED", "1") == "1"
-        self._throttle = _lib.StepThrottle()
         self.epi_fused_bwd = os.environ.get("WN_EPI_FUSED_BWD", "1") == "1"
         # Channel-split backward block with both weight gradients in the launch (wn_resblock_bwd_ms):
         # 64 padded channels, (f16x3, bf16x3) only; None = whenever it applies (WN_MS_BWD=0 turns it off)
@@ -200,14 +92,6 @@ class WaveNetEngine:
         self.fine_marks = False
         # the unfused backward reads the forward's z (stored on the full valid range) for dWd
         self.z_from_fwd = True
-
-    def mark(self, name):
-        """Record a timing event on the current stream (only when self.marks is a list; self.mark_only, if set, limits
-        the events to those names - every event costs a marker packet between two kernels)."""
-        if self.marks is not None and (self.mark_only is None or name in self.mark_only):
-            ev = torch.cuda.Event(enable_timing=True)
-            ev.record()
-            self.marks.append((name, ev))
 
     def fmark(self, name):
         """Per-kernel timing marks of the epilogue (tools/kbench.py epi); off unless self.fine_marks."""
@@ -444,22 +328,13 @@ class WaveNetEngine:
         call("wn_pack_weights", ptr(self.flat), ptr(self.pk_b_idx), ptr(self.pk_b), self.pk_b_idx.numel(), self.mode_bwd, st)
 
     # ------------------------------------------------------------------ workspace
-    def workspace(self, B, T):
-        """The workspace the last forward of this shape used (what callers inspect after a step; WorkspacePool.peek).  A
-        forward takes its own through WorkspacePool.get: the first one no pending backward holds."""
-        return self._ws.peek(B, T)
-
     def _make_workspace(self, B, T):
         dev = self.device
         pitch = _pad(T, 256) + 512        # tiles of 512 columns may overhang T by < 512
         W = T - self.rf + 1
-
-        def buf(rows):
-            t = torch.zeros(SLACK + B * rows * pitch + PAD_BACK, dtype=torch.float32, device=dev)
-            return t
-
+        buf = lambda rows: self.act_buf(B, rows, pitch)
         ws = dict(B=B, T=T, W=W, pitch=pitch)
-        ws["X"] = torch.zeros(SLACK + (self.N + 1) * B * self.CH * pitch + PAD_BACK, dtype=torch.float32, device=dev)
+        ws["X"] = buf((self.N + 1) * self.CH)
         ws["Z"] = buf(self.N * self.CH)
         ws["U"] = buf(self.SP)
         ws["H"] = buf(self.SP)
@@ -479,16 +354,11 @@ class WaveNetEngine:
         if ws["bwd"] is not None:
             return ws["bwd"]
         B, pitch, W, dev = ws["B"], ws["pitch"], ws["W"], self.device
-
-        def buf(rows):
-            return torch.zeros(SLACK + B * rows * pitch + PAD_BACK, dtype=torch.float32, device=dev)
-
+        buf = lambda rows: self.act_buf(B, rows, pitch)
         bw = dict(dO=torch.zeros(B * self.Q * W + PAD_BACK, dtype=torch.float32, device=dev),
                   dH=buf(self.SP), dU=buf(self.SP), dZ=buf(self.N * self.CH),
                   dX=[buf(self.CH), buf(self.CH)], dfg=[buf(2 * self.CH), buf(2 * self.CH)],
                   zs=[buf(self.CH), buf(self.CH)])
-        # weight-gradient slabs: every wgrad workgroup writes its partial C with plain stores,
-        # one batched kernel then sums the slabs of all ops in a fixed order (deterministic)
         T, lo = ws["T"], self.rf - 1
         ms = ws["ms"]
         bw["ms"] = ms
@@ -511,53 +381,31 @@ class WaveNetEngine:
                 n = -(-span // c)                      # chunks per clip
                 return -(-(-(-span // n)) // 32) * 32    # their common length, a multiple of the 32-sample k-step
             ck = [even(c) for c in ck]
-        ops = [("p2", lo, T, ck[0]), ("p1", lo, T, ck[1]), ("skip", lo, T, ck[2])]
+        plan = SlabPlan(self.gp_off)
+        for name, c in zip(("p2", "p1", "skip"), ck):
+            plan.add(name, _lib.wgrad_slabs(lo, T, c, B), c)
         # one-launch blocks whose dilation is a multiple of 32 hand dx on WHOLE (chain form of wn_resblock_bwd_pq: the Q rows
         # of an item are the carry of the next item of its chain); decided here, once per workspace, with the slab counts
         Bp = B // 2 if pair else B
         want = os.environ.get("WN_PQ_CHAIN", "1") == "1"       # 0: every block hands the (P, Q) pair on (round 3's form)
         bw["chain"] = [want and bool(bw["pq"] or pair) and _lib.pq_chain_ok(self.off[i + 1], T, Bp, self.dil[i]) for i in range(self.N)]
+        sfx = "2_" if pair else ""                            # pair mode: the block-diagonal gradient matrices of B / 2 clip pairs
         for i in range(self.N):
-            if pair:                                          # the 64-channel one-launch block on B / 2 clip pairs
-                ops.append(("fg2_%d" % i, self.off[i + 1], T, (-3, i)))
-                if i < self.N - 1:
-                    ops.append(("d2_%d" % i, self.off[i + 1], T, (-3, i)))
-                continue
-            kind = (-3, i) if bw["pq"] else (-1 if ms else 512)
-            ops.append(("fg%d" % i, self.off[i + 1], T, kind))
+            t_lo = self.off[i + 1]
+            if bw["pq"] or pair:                              # one-launch block (on clips or clip pairs): one slab per workgroup of ITS plan
+                ns, chunk = _lib.pq_slabs(t_lo, T, Bp, self.dil[i], bw["chain"][i]), None
+            elif ms:                                          # channel-split block: one slab per workgroup
+                ns, chunk = _lib.ms_slabs(t_lo, T, B), None
+            else:
+                ns, chunk = _lib.wgrad_slabs(t_lo, T, 512, B), 512
+            plan.add("fg%s%d" % (sfx, i), ns, chunk)
             if i < self.N - 1:
-                ops.append(("d%d" % i, self.off[i + 1], T, kind))
-        ops.append(("causal", 1, T, 512))
+                plan.add("d%s%d" % (sfx, i), ns, chunk)
+        plan.add("causal", _lib.wgrad_slabs(1, T, 512, B), 512)
         # the same gradient from integer codes (wn_causal_wgrad_codes) when the input is a one-hot this engine / the
         # loader built: its own slab region and its own reduction table (only the last row differs)
-        ops.append(("causal_codes", 1, T, None))
-        plan, desc, so, vs = {}, [], 0, 0
-        nslab = {}
-        for name, t_lo, t_hi, chunk in ops:
-            if isinstance(chunk, tuple):
-                nslab[name] = _lib.pq_slabs(t_lo, t_hi, Bp, self.dil[chunk[1]], bw["chain"][chunk[1]])
-        for name, t_lo, t_hi, chunk in ops:
-            go, r, c = self.gp_off["causal" if name == "causal_codes" else name]
-            n = r * c
-            if chunk is None:
-                ns = _lib.causal_codes_slabs(T, B)
-            elif isinstance(chunk, tuple):                    # one-launch block (on clips or clip pairs): one slab per workgroup of ITS plan
-                ns = nslab[name]
-            elif chunk > 0:
-                ns = _lib.wgrad_slabs(t_lo, t_hi, chunk, B)
-            else:                                             # channel-split block: one slab per workgroup
-                ns = _lib.ms_slabs(t_lo, t_hi, B)
-            plan[name] = (so, n, chunk, ns, go)
-            if name == "causal_codes":
-                desc_codes = desc[:-1] + [[desc[-1][0], so, ns, n, go, n]]
-            else:
-                desc.append([vs, so, ns, n, go, n])
-                vs += (n + 3) // 4
-            so += ns * n
-        bw["slab"] = torch.empty(so, dtype=torch.float32, device=dev)
-        bw["slab_plan"], bw["slab_vec"], bw["slab_nops"] = plan, vs, len(desc)
-        bw["slab_desc"] = torch.tensor(desc, dtype=torch.int64, device=dev)
-        bw["slab_desc_codes"] = torch.tensor(desc_codes, dtype=torch.int64, device=dev)
+        plan.add_alternative("causal", "causal_codes", _lib.causal_codes_slabs(T, B))
+        bw.update(plan.finish(dev))
         ws["bwd"] = bw
         return bw
 
@@ -612,7 +460,8 @@ class WaveNetEngine:
                     tuple(codes.shape) == (B, T)):
                 ws["x_codes"] = (codes, scrambled)
         # what the backward re-checks: the causal layer's weight gradient is formed later from these same tensors
-        ws["x_ver"] = (None if x is None else x._version, None if ws["x_codes"] is None else ws["x_codes"][0]._version)
+        ws["x_ver"] = None if x is None else x._version
+        ws["codes_ver"] = None if ws["x_codes"] is None else ws["x_codes"][0]._version
         # causal conv (wavenet/model.py:104): x0[t] = W0 in[t-1] + W1 in[t], t in [1,T)
         if ws["x_codes"] is not None:
             # the input is the one-hot of known codes: a gather of weight columns (the dense tensor is not read)
@@ -717,13 +566,13 @@ class WaveNetEngine:
         fr = lambda name: ptr(self.pk_f, self.pk_f_off[name])
         lo = self.rf - 1
         xb, zb, sb = CH * pitch, N * CH * pitch, SP * pitch
-        plan = bw["slab_plan"]
+        plan = bw["plan"]
 
         def wgrad(name, *args):
             """args = everything of wn_wgrad up to and including relu_b, then ldc, t_lo, t_hi"""
-            so, n, chunk = plan[name][:3]
+            op = plan[name]
             head, (ldc, t_lo, t_hi) = args[:-3], args[-3:]
-            call("wn_wgrad", *head, ptr(bw["slab"], so), ldc, n, t_lo, t_hi, chunk, B, mb, st)
+            call("wn_wgrad", *head, ptr(bw["slab"], op.so), ldc, op.n, t_lo, t_hi, op.chunk, B, mb, st)
         dO, dH, dU, dZ = ptr(bw["dO"]), ptr(bw["dH"], SLACK), ptr(bw["dU"], SLACK), ptr(bw["dZ"], SLACK)
         U, H, Z = ptr(ws["U"], SLACK), ptr(ws["H"], SLACK), ptr(ws["Z"], SLACK)
         main = torch.cuda.current_stream()
@@ -745,9 +594,9 @@ class WaveNetEngine:
                 fn(_lib.stream())
 
         def wgrad_s(name, *args):
-            so, n, chunk = plan[name][:3]
+            op = plan[name]
             head, (ldc, t_lo, t_hi) = args[:-3], args[-3:]
-            on_side(lambda s2: call("wn_wgrad", *head, ptr(bw["slab"], so), ldc, n, t_lo, t_hi, chunk, B, mb, s2))
+            on_side(lambda s2: call("wn_wgrad", *head, ptr(bw["slab"], op.so), ldc, op.n, t_lo, t_hi, op.chunk, B, mb, s2))
 
         # weight gradients of the epilogue run on the side stream as soon as their operands exist
         wgrad_s("p2", dO, Q * W, W, -lo, W, H, None, sb, pitch, 0, 0, pitch, SP // 16, Q // 16, 1, SP, lo, T)
@@ -841,12 +690,12 @@ class WaveNetEngine:
                     # clip pairs on the 64-channel block: block-diagonal packs, the second clip's dz rows in its own slice
                     call("wn_resblock_bwd_pq", self._x(ws, i), p_in, q_in, dn, p_lo, ptr(bw["dZ"], SLACK + i * CH * pitch),
                          p_out, q_out, 2 * xb, 2 * zb, pitch, fr("fg2_%d" % i), br("dT2_%d" % i), br("pq2_%d" % i), 64, d, t_lo, T, lo,
-                         ptr(bw["slab"], plan["fg2_%d" % i][0]), ptr(bw["slab"], plan["d2_%d" % i][0]) if i < N - 1 else None,
+                         ptr(bw["slab"], plan["fg2_%d" % i].so), ptr(bw["slab"], plan["d2_%d" % i].so) if i < N - 1 else None,
                          None, 0, 0, 0, None, None, zb, chain, B // 2, mf, mb, st)
                 else:
                     call("wn_resblock_bwd_pq", self._x(ws, i), p_in, q_in, dn, p_lo, ptr(bw["dZ"], SLACK + i * CH * pitch),
                          p_out, q_out, xb, zb, pitch, fr("fg%d" % i), br("dT%d" % i), br("pq%d" % i), CH, d, t_lo, T, lo,
-                         ptr(bw["slab"], plan["fg%d" % i][0]), ptr(bw["slab"], plan["d%d" % i][0]) if i < N - 1 else None,
+                         ptr(bw["slab"], plan["fg%d" % i].so), ptr(bw["slab"], plan["d%d" % i].so) if i < N - 1 else None,
                          None, 0, 0, 0, None, None, 0, chain, B, mf, mb, st)
                 self.fmark("b_block")
                 if i == 0 and not chain:
@@ -857,8 +706,8 @@ class WaveNetEngine:
             if bw["ms"]:
                 call("wn_resblock_bwd_ms", self._x(ws, i), dy, ptr(bw["dZ"], SLACK + i * CH * pitch), dfg, xb, zb, 2 * CH * pitch,
                      pitch, fr("fg%d" % i), br("dT%d" % i), self._bias_ptr(bn % (4 * i)), self._bias_ptr(bn % (4 * i + 1)),
-                     self.D, CH, d, t_lo, T, lo, ptr(bw["slab"], plan["fg%d" % i][0]),
-                     ptr(bw["slab"], plan["d%d" % i][0]) if i < N - 1 else None, None, 0, 0, 0, 0, 0, B, mf, mb, st)
+                     self.D, CH, d, t_lo, T, lo, ptr(bw["slab"], plan["fg%d" % i].so),
+                     ptr(bw["slab"], plan["d%d" % i].so) if i < N - 1 else None, None, 0, 0, 0, 0, 0, B, mf, mb, st)
                 self.fmark("b_block")
                 if self.use_bias:
                     bo = self.gp_bias_off
@@ -887,14 +736,14 @@ class WaveNetEngine:
                 side.wait_event(ev_r)
             with torch.cuda.stream(side):
                 st2 = _lib.stream()
-                so, n, chunk = plan["fg%d" % i][:3]
+                op = plan["fg%d" % i]
                 call("wn_wgrad", dfg, 2 * CH * pitch, pitch, 0, pitch, self._x(ws, i), self._x(ws, i), xb, pitch, -d, 0, pitch,
-                     CH // 16, 2 * CH // 16, 0, ptr(bw["slab"], so), 2 * CH, n, t_lo, T, chunk, B, mb, st2)
+                     CH // 16, 2 * CH // 16, 0, ptr(bw["slab"], op.so), 2 * CH, op.n, t_lo, T, op.chunk, B, mb, st2)
                 if i < N - 1:
-                    so, n, chunk = plan["d%d" % i][:3]
+                    op = plan["d%d" % i]
                     zsrc, zstr = (ptr(ws["Z"], SLACK + i * CH * pitch), zb) if self.z_from_fwd else (zs, xb)
                     call("wn_wgrad", dy, xb, pitch, 0, pitch, zsrc, None, zstr, pitch, 0, 0, pitch, CH // 16, CH // 16, 0,
-                         ptr(bw["slab"], so), CH, n, t_lo, T, chunk, B, mb, st2)
+                         ptr(bw["slab"], op.so), CH, op.n, t_lo, T, op.chunk, B, mb, st2)
                 if self.use_bias:
                     bo = self.gp_bias_off
                     call("wn_bias_grad", dfg, 2 * CH * pitch, pitch, 0, self.D, t_lo, T, B, ptr(self.gpack, bo[bn % (4 * i)]), st2)
@@ -924,14 +773,11 @@ class WaveNetEngine:
         # causal weight gradient: dWc[r][q][tap] = sum dx0[r][t] in[q][t-1+tap]
         x = ws["x_in"]
         dx0 = ptr(bw["dX"][0], SLACK)
-        desc = bw["slab_desc"]
-        # the input (and the codes it was built from) must still be what the forward saw: in-place writes that bump the
-        # version counter are caught here (autograd's own rule for saved tensors); writes that do not (x.data.zero_(), a
-        # raw-pointer kernel) cannot be - onehot() documents the tensor as immutable while tagged
-        xv, cv = ws.get("x_ver", (None, None))
-        if x is not None and xv is not None and x._version != xv:
-            raise RuntimeError("music_amd: the input of this forward was modified in place before backward()")
-        x_codes = ws.get("x_codes")
+        desc = bw["desc"]
+        # the input and the codes it was built from must still be what the forward saw (_check_input_unchanged; onehot() documents
+        # the tensor as immutable while tagged)
+        self._check_input_unchanged(ws)
+        x_codes, cv = ws.get("x_codes"), ws.get("codes_ver")
         if x_codes is not None and cv is not None and x_codes[0]._version != cv:
             if x is None:
                 raise RuntimeError("music_amd: the integer codes of this forward were modified in place before backward()")
@@ -939,14 +785,14 @@ class WaveNetEngine:
         if x_codes is not None:
             codes, scrambled = x_codes
             call("wn_causal_wgrad_codes", ptr(codes), 1 if scrambled else 0, dx0, None, 0, 0, xb, pitch, CH, Q, T, B,
-                 ptr(bw["slab"], plan["causal_codes"][0]), st)
-            desc = bw["slab_desc_codes"]
+                 ptr(bw["slab"], plan["causal_codes"].so), st)
+            desc = bw["desc_codes"]
         else:
             wgrad("causal", dx0, xb, pitch, 0, pitch, ptr(x), ptr(x), Q * T, T, -1, 0, T, Q // 16, CH // 16, 0, 2 * Q, 1, T)
         if self.use_bias:
             call("wn_bias_grad", dx0, xb, pitch, 0, self.R, 1, T, B, ptr(self.gpack, self.gp_bias_off["causal_layer.bias"]), st)
         self.mark("causal_bwd")
-        call("wn_reduce_slabs", ptr(desc), bw["slab_nops"], bw["slab_vec"], ptr(bw["slab"]), ptr(self.gpack), st)
+        call("wn_reduce_slabs", ptr(desc), bw["nops"], bw["vec"], ptr(bw["slab"]), ptr(self.gpack), st)
         if bw["pair"]:
             call("wn_gather_grads2", ptr(self.gpack), ptr(self.gidx_pa), ptr(self.gidx_pb), ptr(self.flat_grad), self.spec.total, st)
         else:
@@ -985,52 +831,19 @@ class WaveNetEngine:
     def loss_and_grad(self, x, target, want_probs=False, codes=None):
         """forward + CrossEntropyLoss(probs, target) + backward (wavenet/train.py:178-181).
         Returns the loss as a 0-d device tensor; gradients land in self.flat_grad."""
-        self._throttle.enter()                 # at most WN_MAX_STEPS_IN_FLIGHT fused steps in flight (_lib.StepThrottle)
-        self.mark("begin")
-        self.pack_weights()
-        self.mark("pack")
-        ws = self.forward_logits(x, codes=codes)
-        bw = self._bwd_workspace(ws)
-        B, W = ws["B"], ws["W"]
-        n = B * W
-        target = target.reshape(-1)
-        assert target.numel() == n and target.dtype == torch.int64 and target.is_cuda
-        if "loss_part" not in ws:
-            ws["loss_part"] = torch.zeros(_lib.CE_NUM_PARTIALS, dtype=torch.float32, device=self.device)
-        probs = None
-        if want_probs:
-            probs = torch.empty(n, self.Q, dtype=torch.float32, device=self.device)
-            ws["probs"] = probs
-        call("wn_chunk_softmax256_ce", ptr(ws["O"]), ptr(target), ptr(probs), ptr(bw["dO"]), ptr(ws["loss_part"]),
-             n, 1.0 / n, _lib.stream())
+        def step():
+            self.mark("begin")
+            self.pack_weights()
+            self.mark("pack")
+            return self._fused_tail(self.forward_logits(x, codes=codes), target, want_probs)
+        return self._throttled(step)
+
+    def softmax_ce(self, *args):
+        super().softmax_ce(*args)
         self.mark("softmax_ce")
-        self.backward_from_dlogits(ws)
-        loss = ws["loss_part"].sum()
-        self._throttle.leave()
-        return loss
-
-    def adam_init(self, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, skip_nonfinite=False):
-        """max_grad_norm / skip_nonfinite: the guarded step (music_amd/guard.py) - the gradient is clipped to that global L2 norm and
-        a non-finite one is skipped, both decided on the device; unset, adam_step is the one wn_adam_flat launch."""
-        self.adam_state = dict(m=torch.zeros_like(self.flat), v=torch.zeros_like(self.flat), t=0,
-                               lr=lr, b1=betas[0], b2=betas[1], eps=eps)
-        guard.adam_init_guard(self.adam_state, self.flat.device, max_grad_norm, skip_nonfinite)
-
-    def guard_report(self):
-        """The guard's state block read back (the only sync of the guarded step): norm / coef / taken / clipped / skipped /
-        nonfinite, adam_state["t"] set to the steps taken; None without a guard."""
-        return guard.engine_guard_report(self)
 
     def adam_step(self, gscale=1.0):
-        s = self.adam_state
-        if s.get("guard") is not None:
-            guard.adam_step_guarded(self, gscale)
-            return self.mark("adam")
-        s["t"] += 1
-        bc1 = 1.0 - s["b1"] ** s["t"]
-        bc2 = 1.0 - s["b2"] ** s["t"]
-        call("wn_adam_flat", ptr(self.flat), ptr(self.flat_grad), ptr(s["m"]), ptr(s["v"]), self.spec.total,
-             s["lr"], s["b1"], s["b2"], s["eps"], bc1, bc2, gscale, _lib.stream())
+        super().adam_step(gscale)
         self.mark("adam")
 
     def onehot(self, codes, scrambled=True):

@@ -24,7 +24,7 @@ import torch
 
 from . import _lib
 from ._lib import call, ptr
-from .engine import SLACK, _Spec, _pad
+from .engine_base import SLACK, _Spec, _pad
 from .plan_generic import GeneralPlan, PackBuilder, Pass
 
 
@@ -150,10 +150,12 @@ class GenericWaveNetEngine(GeneralPlan):
         return probs, ws
 
     # ------------------------------------------------------------------ backward
-    def _bwd_buffers(self, buf):
+    def _bwd_buffers(self, buf, add):
         N, RP, DP, SP, lo = self.N, self.RP, self.DP, self.SP, self.rf - 1
-        bw = dict(dH=buf(SP), dU=buf(SP), dZ=buf(N * DP), dX=[buf(RP), buf(RP)], dz=buf(DP), dfg=buf(2 * DP))
-        return bw, [("p2", lo, 1024), ("p1", lo, 1024), ("skip", lo, 2048)] + self._stack_ops("fg%d", "d%d", "causal", N - 1)
+        for name, chunk in (("p2", 1024), ("p1", 1024), ("skip", 2048)):
+            add(name, lo, chunk)
+        self._add_stack(add, "fg%d", "d%d", "causal", N - 1)
+        return dict(dH=buf(SP), dU=buf(SP), dZ=buf(N * DP), dX=[buf(RP), buf(RP)], dz=buf(DP), dfg=buf(2 * DP))
 
     def backward_from_dlogits(self, ws):
         """ws['bwd']['dO'] holds d loss / d pre-softmax (B, Q, W).  Fills self.flat_grad."""
@@ -193,7 +195,7 @@ class GenericWaveNetEngine(GeneralPlan):
         return self.forward_logits(x)
 
     def loss_and_grad(self, x, target, want_probs=False):
-        return self._fused_step(lambda: self._step_forward(x), target, want_probs)
+        return self._throttled(lambda: self._fused_tail(self._step_forward(x), target, want_probs))
 
     def loss_and_grad_codes(self, codes, target, scrambled=True, want_probs=False):
         """the fast engine's entry point on integer codes; here the one-hot is built (wn_onehot) and the dense path runs"""

@@ -27,16 +27,18 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 try:
-    from . import _lib, _losshook, guard
+    from . import _lib, _losshook
     from ._lib import call, ptr
-    from .engine import SLACK, PAD_BACK, _Spec, _pad, pack_index, pack_positions, WorkspacePool, WorkspaceHold
+    from .engine import pack_index, pack_positions
+    from .engine_base import SLACK, PAD_BACK, EngineBase, SlabPlan, WorkspaceHold, _Spec, _pad
 except ImportError:
-    from music_amd import _lib, _losshook, guard
+    from music_amd import _lib, _losshook
     from music_amd._lib import call, ptr
-    from music_amd.engine import SLACK, PAD_BACK, _Spec, _pad, pack_index, pack_positions, WorkspacePool, WorkspaceHold
+    from music_amd.engine import pack_index, pack_positions
+    from music_amd.engine_base import SLACK, PAD_BACK, EngineBase, SlabPlan, WorkspaceHold, _Spec, _pad
 
 
-class _AutoencoderEngine:
+class _AutoencoderEngine(EngineBase):
     """Host-side plan of the autoencoder on one MI355X: flat parameters, packed-weight index maps,
     workspaces, forward (model1.py:256-268) and backward (autograd of it)."""
 
@@ -80,17 +82,9 @@ class _AutoencoderEngine:
                 view.copy_(p.data)
                 p.data = view
         self._build_packs()
-        self._ws = WorkspacePool(self._make_workspace)
-        self._gen = 0
-        self.marks = None            # list of (name, torch.cuda.Event) when phase timing is on (bench.py)
+        self._init_state()
         self._side = None            # second HIP stream for the epilogue's weight gradients (as music_amd/engine.py)
         self.overlap_wgrad = True
-
-    def mark(self, name):
-        if self.marks is not None:
-            ev = torch.cuda.Event(enable_timing=True)
-            ev.record()
-            self.marks.append((name, ev))
 
     def _stage_cond(self, cond):
         """cond (N+1 CPU (weight, bias) pairs) -> device tensors cw (N, 2Dd, Bw), cb (N, 2Dd), cfw (Sd, Bw, 1), cfb (Sd) through one
@@ -277,18 +271,12 @@ class _AutoencoderEngine:
             self.gidx_pa = torch.from_numpy(ga.astype(np.int32)).to(self.device)
             self.gidx_pb = torch.from_numpy(gb.astype(np.int32)).to(self.device)
 
-    def workspace(self, B, T):
-        return self._ws.peek(B, T)
-
     def _make_workspace(self, B, T):
         dev = self.device
         pitch = _pad(T, 256) + 512
         W = T - self.rf + 1
         N = self.N
-
-        def buf(rows):
-            return torch.zeros(SLACK + B * rows * pitch + PAD_BACK, dtype=torch.float32, device=dev)
-
+        buf = lambda rows: self.act_buf(B, rows, pitch)
         ws = dict(B=B, T=T, W=W, pitch=pitch, Xe=buf((N + 1) * self.CHe), He=buf(N * self.CHe), E=buf(self.BwP),
                   Xd=buf((N + 1) * self.CHd), Z=buf(N * self.CHd), U=buf(self.SP), R1=buf(self.SP),
                   C1=buf(self.SP), O=torch.zeros(B * self.Q * W + PAD_BACK, dtype=torch.float32, device=dev), bwd=None)
@@ -297,12 +285,6 @@ class _AutoencoderEngine:
     # layer i of a stacked [(N+1) or N][B][CH][pitch] buffer
     def _lay(self, t, i, ch, ws):
         return ptr(t, SLACK + i * ws["B"] * ch * ws["pitch"])
-
-    def _gemm(self, st, B, mode, pack_ptr, in0, in1, in_bs, in_pitch, in_lo, in_hi, s0, s1, ks0, ks1, mt, mvalid, out, out_bs,
-              out_pitch, out_shift, bias, resid, mask, t_lo, t_hi, relu_in):
-        call("wn_chan_gemm", in0, in1, in_bs, in_pitch, in_lo, in_hi, s0, s1, ks0, ks1, pack_ptr, mt, mvalid,
-             out, out_bs, out_pitch, out_shift, bias, resid[0], resid[1], resid[2], resid[3] if len(resid) > 3 else 0,
-             mask[0], mask[1], mask[2], t_lo, t_hi, relu_in, B, mode, st)
 
     def forward(self, x, cond, want_probs=True):
         """cond: list of N+1 (weight (C,Bw,1), bias (C,)) CPU tensors (see wavenet_autoencoder.forward).
@@ -500,17 +482,16 @@ class _AutoencoderEngine:
         if ws["bwd"] is not None:
             return ws["bwd"]
         B, T, W, pitch, dev, N = ws["B"], ws["T"], ws["W"], ws["pitch"], self.device, self.N
-
-        def buf(rows):
-            return torch.zeros(SLACK + B * rows * pitch + PAD_BACK, dtype=torch.float32, device=dev)
-
+        buf = lambda rows: self.act_buf(B, rows, pitch)
         bw = dict(dO=torch.zeros(B * self.Q * W + PAD_BACK, dtype=torch.float32, device=dev),
                   dR1=buf(self.SP), dU=buf(self.SP), dZ=buf(N * self.CHd), dXd=[buf(self.CHd), buf(self.CHd)],
                   dE=buf(self.BwP), dXe=[buf(self.CHe), buf(self.CHe)],
                   dHe=buf(self.CHe))
         lo = self.rf - 1
-        ops = [("c2", lo, T, 1024), ("c1", lo, T, 1024), ("skip", lo, T, 2048), ("bottleneck", lo, T, 512),
-               ("de_causal", 1, T, 512), ("en_causal", 1, T, 512)]
+        plan = SlabPlan(self.gp_off)
+        for name, t_lo, chunk in (("c2", lo, 1024), ("c1", lo, 1024), ("skip", lo, 2048), ("bottleneck", lo, 512),
+                                  ("de_causal", 1, 512), ("en_causal", 1, 512)):
+            plan.add(name, _lib.wgrad_slabs(t_lo, T, chunk, B), chunk)
         # decoder blocks: the channel-split block kernel (both weight gradients inside the block launch)
         # where it applies, else resblock_bwd + two wgrad launches
         pair = bw["pair"] = ws.get("pair", False)            # both stacks as clip pairs on the 64-channel one-launch blocks
@@ -533,47 +514,31 @@ class _AutoencoderEngine:
         if bw["enc_pq"]:
             bw["PQe"] = (bw["PQ"] if bw["pq"] and self.CHe == self.CHd else     # the decoder's pairs are free again by then
                          [(buf(self.CHe), buf(self.CHe)), (buf(self.CHe), buf(self.CHe))])
-        sfx = "2_" if pair else ""                            # pair mode: the block-diagonal gradient matrices, B / 2 "clips"
+        Bp, sfx = (B // 2, "2_") if pair else (B, "")         # pair mode: the block-diagonal gradient matrices, B / 2 "clips"
         # one-launch encoder blocks whose dilation is a multiple of 32 hand dx on WHOLE (chain form of wn_enc_resblock_bwd_pq, as
         # wn_resblock_bwd_pq's in music_amd/engine.py): 4 activation tensors per block instead of 6 - the launch is bound by its bytes
         # ... and those with d < 32 too (form 2: adjacent items walked downwards, the Q rows cross from item to item through LDS)
         want_chain = bw["enc_pq"] and os.environ.get("WN_PQ_CHAIN", "1") == "1"
         want_lch = want_chain and os.environ.get("WN_ENC_LCH", "1") == "1"
-        bw["enc_chain"] = [(1 if want_chain and _lib.pq_chain_ok(self.off[i + 1], T, B // 2 if pair else B, self.dil[i]) else
+        bw["enc_chain"] = [(1 if want_chain and _lib.pq_chain_ok(self.off[i + 1], T, Bp, self.dil[i]) else
                             2 if want_lch and self.dil[i] < 32 else 0) for i in range(N)]
         for i in range(N):
-            ench = (-3 - i if bw["enc_chain"][i] else -2) if enc_fused else 512      # -3 - i: layer i in chain form (its own slab count)
-            ops += [("de_fg%s%d" % (sfx, i), self.off[i + 1], T, -1 if ms else 512), ("en_dil%s%d" % (sfx, i), self.off[i + 1], T, ench),
-                    ("en_dense%s%d" % (sfx, i), self.off[i + 1], T, ench)]
+            t_lo, ch = self.off[i + 1], bw["enc_chain"][i]
+            # (slabs, wn_wgrad's chunk) of the decoder block's and of the encoder block's two gradients, by the kernel that writes them
+            de = (_lib.ms_slabs(t_lo, T, Bp), None) if ms else (_lib.wgrad_slabs(t_lo, T, 512, B), 512)
+            en = ((_lib.wgrad_slabs(t_lo, T, 512, B), 512) if not enc_fused else
+                  (_lib.pq_slabs(t_lo, T, Bp, self.dil[i] if ch == 1 else 32, True), None) if ch else      # chain form: its own slab count
+                  (_lib.enc_slabs(t_lo, T, Bp), None))
+            plan.add("de_fg%s%d" % (sfx, i), *de)
+            plan.add("en_dil%s%d" % (sfx, i), *en)
+            plan.add("en_dense%s%d" % (sfx, i), *en)
             if i < N - 1:
-                ops.append(("de_d%s%d" % (sfx, i), self.off[i + 1], T, -1 if ms else 512))
-        plan, desc, so, vs = {}, [], 0, 0
-        row_of = {}
-        for name, t_lo, t_hi, chunk in ops:
-            go, r, c = self.gp_off[name]
-            n = r * c
-            Bs = B // 2 if pair and chunk < 0 else B
-            ns = (_lib.wgrad_slabs(t_lo, t_hi, chunk, B) if chunk > 0 else
-                  _lib.ms_slabs(t_lo, t_hi, Bs) if chunk == -1 else _lib.enc_slabs(t_lo, t_hi, Bs) if chunk == -2 else
-                  _lib.pq_slabs(t_lo, t_hi, Bs, self.dil[-3 - chunk] if bw["enc_chain"][-3 - chunk] == 1 else 32, True))
-            plan[name] = (so, n, chunk)
-            row_of[name] = len(desc)
-            desc.append([vs, so, ns, n, go, n])
-            so += ns * n
-            vs += (n + 3) // 4
+                plan.add("de_d%s%d" % (sfx, i), *de)
         # the causal layers' weight gradients from codes (wn_causal_wgrad_codes): their own slab regions, and a second
         # reduction table in which only those two rows differ
-        desc_codes = [list(r) for r in desc]
         for name in ("de_causal", "en_causal"):
-            go, r, c = self.gp_off[name]
-            ns = _lib.causal_codes_slabs(T, B)
-            plan[name + "_codes"] = (so, r * c, None)
-            desc_codes[row_of[name]][1:3] = [so, ns]
-            so += ns * r * c
-        bw["slab"] = torch.empty(so, dtype=torch.float32, device=dev)
-        bw["plan"], bw["vec"], bw["nops"] = plan, vs, len(desc)
-        bw["desc"] = torch.tensor(desc, dtype=torch.int64, device=dev)
-        bw["desc_codes"] = torch.tensor(desc_codes, dtype=torch.int64, device=dev)
+            plan.add_alternative(name, name + "_codes", _lib.causal_codes_slabs(T, B))
+        bw.update(plan.finish(dev))
         ws["bwd"] = bw
         return bw
 
@@ -581,43 +546,7 @@ class _AutoencoderEngine:
         """Fused training step body (the autoencoder counterpart of engine.loss_and_grad): forward to the logits, ONE
         kernel for chunk softmax + CrossEntropyLoss on the probabilities (wavenet_autoencoder/train.py:146-160) + both
         backward steps, then the backward.  Returns the loss (0-d device tensor); gradients land in self.flat_grad."""
-        if getattr(self, "_throttle", None) is None:
-            self._throttle = _lib.StepThrottle()   # at most WN_MAX_STEPS_IN_FLIGHT fused steps in flight (music_amd/_lib.py)
-        self._throttle.enter()
-        _, enc, ws = self.forward(x, cond, want_probs=False)
-        bw = self._bwd_workspace(ws)
-        n = ws["B"] * ws["W"]
-        target = target.reshape(-1)
-        assert target.numel() == n and target.dtype == torch.int64 and target.is_cuda
-        if "loss_part" not in ws:
-            ws["loss_part"] = torch.zeros(_lib.CE_NUM_PARTIALS, dtype=torch.float32, device=self.device)
-        call("wn_chunk_softmax256_ce", ptr(ws["O"]), ptr(target), None, ptr(bw["dO"]), ptr(ws["loss_part"]), n, 1.0 / n,
-             _lib.stream())
-        self.backward(ws, None)
-        loss = ws["loss_part"].sum()
-        self._throttle.leave()
-        return loss
-
-    def adam_init(self, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, skip_nonfinite=False):
-        """max_grad_norm / skip_nonfinite: the guarded step (music_amd/guard.py) - the gradient is clipped to that global L2 norm and
-        a non-finite one is skipped, both decided on the device; unset, adam_step is the one wn_adam_flat launch."""
-        self.adam_state = dict(m=torch.zeros_like(self.flat), v=torch.zeros_like(self.flat), t=0,
-                               lr=lr, b1=betas[0], b2=betas[1], eps=eps)
-        guard.adam_init_guard(self.adam_state, self.flat.device, max_grad_norm, skip_nonfinite)
-
-    def guard_report(self):
-        """The guard's state block read back (the only sync of the guarded step): norm / coef / taken / clipped / skipped /
-        nonfinite, adam_state["t"] set to the steps taken; None without a guard."""
-        return guard.engine_guard_report(self)
-
-    def adam_step(self, gscale=1.0):
-        """torch.optim.Adam semantics on the flat parameter buffer (the nn.Parameters are views of it)."""
-        s = self.adam_state
-        if s.get("guard") is not None:
-            return guard.adam_step_guarded(self, gscale)
-        s["t"] += 1
-        call("wn_adam_flat", ptr(self.flat), ptr(self.flat_grad), ptr(s["m"]), ptr(s["v"]), self.spec.total,
-             s["lr"], s["b1"], s["b2"], s["eps"], 1.0 - s["b1"] ** s["t"], 1.0 - s["b2"] ** s["t"], gscale, _lib.stream())
+        return self._throttled(lambda: self._fused_tail(self.forward(x, cond, want_probs=False)[2], target))
 
     def backward_from_dlogits(self, ws):
         self.backward(ws, None)
@@ -675,9 +604,9 @@ class _AutoencoderEngine:
         plan = bw["plan"]
 
         def wgrad(name, *args):
-            so, n, chunk = plan[name]
+            op = plan[name]
             head, (ldc, t_lo, t_hi) = args[:-3], args[-3:]
-            call("wn_wgrad", *head, ptr(bw["slab"], so), ldc, n, t_lo, t_hi, chunk, B, mb, st)
+            call("wn_wgrad", *head, ptr(bw["slab"], op.so), ldc, op.n, t_lo, t_hi, op.chunk, B, mb, st)
 
         # the decoder epilogue's three weight gradients only feed the slab reduction at the very end: on a second
         # (high-priority = own hardware queue) stream their half-empty last rounds of workgroups pack into the
@@ -691,13 +620,13 @@ class _AutoencoderEngine:
         def wgrad_s(name, *args):
             if not overlap:
                 return wgrad(name, *args)
-            so, n, chunk = plan[name]
+            op = plan[name]
             head, (ldc, t_lo, t_hi) = args[:-3], args[-3:]
             ev = torch.cuda.Event()
             ev.record(main)
             side.wait_event(ev)
             with torch.cuda.stream(side):
-                call("wn_wgrad", *head, ptr(bw["slab"], so), ldc, n, t_lo, t_hi, chunk, B, mb, _lib.stream())
+                call("wn_wgrad", *head, ptr(bw["slab"], op.so), ldc, op.n, t_lo, t_hi, op.chunk, B, mb, _lib.stream())
 
         if dprobs is not None:
             dprobs = dprobs.contiguous()
@@ -780,12 +709,12 @@ class _AutoencoderEngine:
                 if pair:
                     call("wn_resblock_bwd_pq", xd(i), p_in, q_in, dn, p_lo, ptr(bw["dZ"], SLACK + i * CHd * pitch), p_out, q_out,
                          2 * db, 2 * zb, pitch, fr("de_fg2_%d" % i), br("de_dT2_%d" % i), br("de_pq2_%d" % i), 64, d, t_lo, T, lo,
-                         ptr(bw["slab"], plan["de_fg2_%d" % i][0]), ptr(bw["slab"], plan["de_d2_%d" % i][0]) if i < N - 1 else None,
+                         ptr(bw["slab"], plan["de_fg2_%d" % i].so), ptr(bw["slab"], plan["de_d2_%d" % i].so) if i < N - 1 else None,
                          ptr(ws["tab"][i]), 4 * CHd * Le, Le, Le, ptr(ws["cidx"][i]), ptr(bw["cslab"], bw["cs_off"][i]), zb, 0, Bp, mf, mb, st)
                 else:
                     call("wn_resblock_bwd_pq", xd(i), p_in, q_in, dn, p_lo, ptr(bw["dZ"], SLACK + i * CHd * pitch), p_out, q_out,
                          db, zb, pitch, fr("de_fg%d" % i), br("de_dT%d" % i), br("de_pq%d" % i), CHd, d, t_lo, T, lo,
-                         ptr(bw["slab"], plan["de_fg%d" % i][0]), ptr(bw["slab"], plan["de_d%d" % i][0]) if i < N - 1 else None,
+                         ptr(bw["slab"], plan["de_fg%d" % i].so), ptr(bw["slab"], plan["de_d%d" % i].so) if i < N - 1 else None,
                          ptr(ws["tab"][i]), 2 * CHd * Le, Le, Le, ptr(ws["cidx"][i]), ptr(bw["cslab"], bw["cs_off"][i]), 0, 0, B, mf, mb, st)
                 if i == 0:
                     call("wn_shift_add", p_out, q_out, ptr(bw["dXd"][0], SLACK), db, pitch, CHd, d, t_lo, self.off[0], T, B, st)
@@ -793,7 +722,7 @@ class _AutoencoderEngine:
             if bw["ms"]:
                 call("wn_resblock_bwd_ms", xd(i), dy, ptr(bw["dZ"], SLACK + i * CHd * pitch), dfg, db, zb, 2 * CHd * pitch, pitch,
                      fr("de_fg%d" % i), br("de_dT%d" % i), bf, bias_fg, Dd, CHd, d, t_lo, T, lo,
-                     ptr(bw["slab"], plan["de_fg%d" % i][0]), ptr(bw["slab"], plan["de_d%d" % i][0]) if i < N - 1 else None,
+                     ptr(bw["slab"], plan["de_fg%d" % i].so), ptr(bw["slab"], plan["de_d%d" % i].so) if i < N - 1 else None,
                      ptr(ws["tab"][i]), 2 * CHd * Le, Le, mode_c, Le, max(q, 1), B, mf, mb, st)
                 call("wn_cond_grad", dfg, 2 * CHd * pitch, pitch, 2 * CHd, t_lo, T, mode_c, Le, max(q, 1),
                      ptr(d_tab[i]), 2 * CHd * Le, Le, B, st)
@@ -828,7 +757,7 @@ class _AutoencoderEngine:
             if codes_path:
                 codes, scrambled = ws["x_codes"]
                 call("wn_causal_wgrad_codes", ptr(codes), 1 if scrambled else 0, dx0, None, 0, 0, bs, pitch, ch, Q, T, B,
-                     ptr(bw["slab"], plan[name + "_codes"][0]), st)
+                     ptr(bw["slab"], plan[name + "_codes"].so), st)
             else:
                 wgrad(name, dx0, bs, pitch, 0, pitch, ptr(x), ptr(x), Q * T, T, -1, 0, T, Q // 16, ch // 16, 0, 2 * Q, 1, T)
         causal_wgrad("de_causal", ptr(bw["dXd"][0], SLACK), db, CHd)
@@ -868,19 +797,19 @@ class _AutoencoderEngine:
                     p_in, q_in, dn, p_lo = dy, None, 0, y_lo
                 if pair:
                     call("wn_enc_resblock_bwd_pq", xe(i), p_in, q_in, dn, p_lo, he(i), p_out, q_out, 2 * eb, 2 * eb, pitch,
-                         br("en_denseT2_%d" % i), br("en_pq2_%d" % i), 64, d, t_lo, T, ptr(bw["slab"], plan["en_dil2_%d" % i][0]),
-                         ptr(bw["slab"], plan["en_dense2_%d" % i][0]), chain, Bp, mb, st)
+                         br("en_denseT2_%d" % i), br("en_pq2_%d" % i), 64, d, t_lo, T, ptr(bw["slab"], plan["en_dil2_%d" % i].so),
+                         ptr(bw["slab"], plan["en_dense2_%d" % i].so), chain, Bp, mb, st)
                 else:
                     call("wn_enc_resblock_bwd_pq", xe(i), p_in, q_in, dn, p_lo, he(i), p_out, q_out, eb, eb, pitch,
-                         br("en_denseT%d" % i), br("en_pq%d" % i), CHe, d, t_lo, T, ptr(bw["slab"], plan["en_dil%d" % i][0]),
-                         ptr(bw["slab"], plan["en_dense%d" % i][0]), chain, B, mb, st)
+                         br("en_denseT%d" % i), br("en_pq%d" % i), CHe, d, t_lo, T, ptr(bw["slab"], plan["en_dil%d" % i].so),
+                         ptr(bw["slab"], plan["en_dense%d" % i].so), chain, B, mb, st)
                 if i == 0 and not chain:
                     call("wn_shift_add", p_out, q_out, dxe[0], eb, pitch, CHe, d, t_lo, self.off[0], T, B, st)
                 continue
             if bw["enc_fused"]:
                 # dh, dW1 = sum dy relu(h)^T and dWdil = sum dh [relu x(t-d) | relu x(t)]^T in one launch
                 call("wn_enc_resblock_bwd", xe(i), dy, he(i), dHe, eb, eb, eb, pitch, br("en_denseT%d" % i), CHe, d, t_lo, T, y_lo,
-                     ptr(bw["slab"], plan["en_dil%d" % i][0]), ptr(bw["slab"], plan["en_dense%d" % i][0]), B, mb, st)
+                     ptr(bw["slab"], plan["en_dil%d" % i].so), ptr(bw["slab"], plan["en_dense%d" % i].so), B, mb, st)
                 bias_grad("en_dense_layer_stack.%d" % i, dy, eb, pitch, 0, Re, y_lo, T)
                 bias_grad("en_dilation_layer_stack.%d" % i, dHe, eb, pitch, 0, De, t_lo, T)
                 gemm("en_dilT%d" % i, dHe, dHe, eb, pitch, t_lo, T, 0, d, CHe // 32, CHe // 32, CHe // 16, Re, dxe[i % 2], eb, pitch, 0,

@@ -3,8 +3,8 @@
 The autoencoder's decoder with its conditioning folded away IS a wavenet (wavenet_autoencoder/model1.py:158-225 against
 wavenet/model.py:104-144), so both plans are sequences of the same few layers, one product per launch:
 
-    GeneralPlan   the host side every general plan has: geometry of a k-tap dilated stack (`k`, `rf`, `off`, `pairs`), weight
-                  packing, workspaces and their slab plan, the padded input copy, the chunk softmax by Q, the fused step, Adam
+    GeneralPlan   the host side every general plan has on top of engine_base.EngineBase: geometry of a k-tap dilated stack (`k`,
+                  `rf`, `off`, `pairs`), weight packing, workspaces and their slab plan, the padded input copy, the chunk softmax by Q
     PackBuilder   flat-parameter offsets -> forward packs, transposed backward packs, gradient matrices and the gather map
     Pass          the launches of ONE forward or backward pass: k-tap conv, gated block, epilogue, each forward and backward,
                   with an optional conditioning table (None = the WaveNet plan)
@@ -15,9 +15,10 @@ conditioning) arrives as data.  PyTorch is used for device memory and streams on
 import numpy as np
 import torch
 
-from . import _lib, guard
+from . import _lib
 from ._lib import call, ptr
-from .engine import SLACK, PAD_BACK, WorkspacePool, _pad, pack_index
+from .engine import pack_index
+from .engine_base import SLACK, PAD_BACK, EngineBase, SlabPlan, _pad
 
 NONE4, NONE3 = (None, 0, 0, 0), (None, 0, 0)
 
@@ -111,7 +112,7 @@ class PackBuilder:
         return offs, idx_all, torch.zeros(o * hpf // 512, dtype=torch.int16, device=dev)
 
 
-class GeneralPlan:
+class GeneralPlan(EngineBase):
     """Host side common to the general plans.  A plan sets `dil`, `k`, `Q`, `QP`, `use_bias`, `mode_fwd`, `mode_bwd`, `device`,
     `spec`, `param_names`, `flat`, `flat_grad`, then calls _geometry(), _finish_packs() and _init_state(); it provides
     _make_workspace(), _bwd_buffers(), backward_from_dlogits() and its own forward."""
@@ -127,19 +128,6 @@ class GeneralPlan:
         assert self.off[-1] == self.rf - 1
         self.pairs = [(j, j + 1 if j + 1 < self.k else None) for j in range(0, self.k, 2)]
 
-    def _init_state(self):
-        self._ws = WorkspacePool(self._make_workspace)
-        self._gen = 0
-        self.adam_state = None
-        self.marks = None
-        self.mark_only = None
-
-    def mark(self, name):
-        if self.marks is not None and (self.mark_only is None or name in self.mark_only):
-            ev = torch.cuda.Event(enable_timing=True)
-            ev.record()
-            self.marks.append((name, ev))
-
     def _bias_ptr(self, name):
         return ptr(self.flat, self.spec.off[name]) if self.use_bias else None
 
@@ -147,12 +135,6 @@ class GeneralPlan:
         """(shift of tap j0, shift of tap j1 or 0, 1 if there is a second tap): input column = t - (k-1-j) d"""
         j0, j1 = pair
         return -(self.k - 1 - j0) * d, (-(self.k - 1 - j1) * d if j1 is not None else 0), (1 if j1 is not None else 0)
-
-    def _gemm(self, st, B, mode, wpack, in0, in1, in_bs, in_pitch, in_lo, in_hi, s0, s1, ks0, ks1, mt, m_valid, out, out_bs,
-              out_pitch, out_shift, bias, resid, mask, t_lo, t_hi, relu_in):
-        call("wn_chan_gemm", in0, in1, in_bs, in_pitch, in_lo, in_hi, s0, s1, ks0, ks1, wpack, mt, m_valid,
-             out, out_bs, out_pitch, out_shift, bias, resid[0], resid[1], resid[2], resid[3],
-             mask[0], mask[1], mask[2], t_lo, t_hi, relu_in, B, mode, st)
 
     # ------------------------------------------------------------------ packs
     def _finish_packs(self, pb, gate_bias, gate_rows_p):
@@ -177,17 +159,12 @@ class GeneralPlan:
             call("wn_gather_grads", ptr(self.flat), ptr(self.bfg_idx), ptr(self.bfg), self.bfg.numel(), st)
 
     # ------------------------------------------------------------------ workspaces
-    def workspace(self, B, T):
-        return self._ws.peek(B, T)
-
     def _new_workspace(self, B, T):
         """(workspace with what every plan has, allocator of a [clip][rows][pitch] activation buffer)"""
         dev, Q = self.device, self.Q
         pitch = _pad(T, 256) + 512
         W = T - self.rf + 1
-
-        def buf(rows):
-            return torch.zeros(SLACK + B * rows * pitch + PAD_BACK, dtype=torch.float32, device=dev)
+        buf = lambda rows: self.act_buf(B, rows, pitch)
         ws = dict(B=B, T=T, W=W, pitch=pitch, bwd=None)
         # the compact (B, Q, W) logits; rows Q .. QP-1 of the LAST clip are read (against zero weights) by the products that
         # take this tensor as an operand, so QP - Q rows of finite slack follow it
@@ -215,40 +192,30 @@ class GeneralPlan:
         return ws["xin"]
 
     def _bwd_workspace(self, ws):
-        """Backward buffers of the plan plus the slab plan of its weight gradients: `ops` = (gradient matrix, t_lo, chunk) of
-        every wn_wgrad call -> where its slabs go (`plan`) and what wn_reduce_slabs sums into the gradient pack (`desc`)."""
+        """Backward buffers of the plan plus the slab plan of its weight gradients: the plan's _bwd_buffers() calls add(gradient
+        matrix, t_lo, chunk) for every wn_wgrad call, in the order the backward launches them."""
         if ws["bwd"] is not None:
             return ws["bwd"]
         B, T, W, pitch, dev = ws["B"], ws["T"], ws["W"], ws["pitch"], self.device
-
-        def buf(rows):
-            return torch.zeros(SLACK + B * rows * pitch + PAD_BACK, dtype=torch.float32, device=dev)
-        bw, ops = self._bwd_buffers(buf)
+        plan = SlabPlan(self.gp_off)
+        bw = self._bwd_buffers(lambda rows: self.act_buf(B, rows, pitch),
+                               lambda name, t_lo, chunk: plan.add(name, _lib.wgrad_slabs(t_lo, T, chunk, B), chunk))
         bw["dO"] = torch.zeros(B * self.Q * W + 32 * W + PAD_BACK, dtype=torch.float32, device=dev)
-        plan, desc, so, vs = {}, [], 0, 0
-        for name, t_lo, chunk in ops:
-            go, r, c = self.gp_off[name]
-            n = r * c
-            ns = _lib.wgrad_slabs(t_lo, T, chunk, B)
-            plan[name] = (so, n, chunk)
-            desc.append([vs, so, ns, n, go, n])
-            vs += (n + 3) // 4
-            so += ns * n
-        bw["slab"] = torch.empty(so, dtype=torch.float32, device=dev)
-        bw["plan"], bw["vec"], bw["nops"] = plan, vs, len(desc)
-        bw["desc"] = torch.tensor(desc, dtype=torch.int64, device=dev)
+        bw.update(plan.finish(dev))
         ws["bwd"] = bw
         return bw
 
-    def _stack_ops(self, fg, dense, causal, n_dense):
+    def _add_stack(self, add, fg, dense, causal, n_dense):
         """Slab-plan entries of a stack: per block the k-tap conv's pairs then its 1x1 (the first n_dense blocks), then the
         causal layer's pairs - the order the backward launches them in."""
-        ops, np_ = [], len(self.pairs)
+        np_ = len(self.pairs)
         for i in range(self.N):
-            ops += [(fg % i + "_%d" % p, self.off[i + 1], 512) for p in range(np_)]
+            for p in range(np_):
+                add(fg % i + "_%d" % p, self.off[i + 1], 512)
             if i < n_dense:
-                ops.append((dense % i, self.off[i + 1], 512))
-        return ops + [(causal + "_%d" % p, self.k - 1, 512) for p in range(np_)]
+                add(dense % i, self.off[i + 1], 512)
+        for p in range(np_):
+            add(causal + "_%d" % p, self.k - 1, 512)
 
     # ------------------------------------------------------------------ chunk softmax: the 256-wide kernels or the any-Q ones
     def _softmax(self, what, ptrs, n, tail=()):
@@ -264,14 +231,9 @@ class GeneralPlan:
         self._softmax("bwd", (ptr(probs), ptr(dprobs), ptr(dlogits)), n)
 
     def softmax_ce(self, logits, target, probs, dlogits, loss_part, n):
-        """loss partials and d loss / d logits of the MEAN cross entropy over n rows (probs None: not wanted)"""
         self._softmax("ce", (ptr(logits), ptr(target), ptr(probs), ptr(dlogits), ptr(loss_part)), n, (1.0 / n,))
 
     # ------------------------------------------------------------------ backward entry points
-    def _check_input_unchanged(self, ws):
-        if ws.get("x_ver") is not None and ws["x_in"]._version != ws["x_ver"]:
-            raise RuntimeError("music_amd: the input of this forward was modified in place before backward()")
-
     def backward(self, ws, dprobs):
         """Fills self.flat_grad from d loss / d probabilities (B*W, Q), the gradient w.r.t. what forward() returned; dprobs None =
         bw["dO"] already holds d loss / d logits."""
@@ -300,49 +262,6 @@ class GeneralPlan:
             din.add_(o)
         return din
 
-    # ------------------------------------------------------------------ fused training step
-    def _fused_step(self, forward, target, want_probs=False):
-        """forward() -> workspace holding the logits; then softmax + cross entropy and the backward, throttled."""
-        if getattr(self, "_throttle", None) is None:
-            self._throttle = _lib.StepThrottle()   # at most WN_MAX_STEPS_IN_FLIGHT fused steps in flight (music_amd/_lib.py)
-        self._throttle.enter()
-        ws = forward()
-        bw = self._bwd_workspace(ws)
-        n = ws["B"] * ws["W"]
-        target = target.reshape(-1)
-        assert target.numel() == n and target.dtype == torch.int64 and target.is_cuda
-        if "loss_part" not in ws:
-            ws["loss_part"] = torch.zeros(_lib.CE_NUM_PARTIALS, dtype=torch.float32, device=self.device)
-        probs = None
-        if want_probs:
-            probs = torch.empty(n, self.Q, dtype=torch.float32, device=self.device)
-            ws["probs"] = probs
-        self.softmax_ce(ws["O"], target, probs, bw["dO"], ws["loss_part"], n)
-        self.backward_from_dlogits(ws)
-        loss = ws["loss_part"].sum()
-        self._throttle.leave()
-        return loss
-
-    def adam_init(self, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, skip_nonfinite=False):
-        """max_grad_norm / skip_nonfinite: the guarded step (music_amd/guard.py) - the gradient is clipped to that global L2 norm and
-        a non-finite one is skipped, both decided on the device; unset, adam_step is the one wn_adam_flat launch."""
-        self.adam_state = dict(m=torch.zeros_like(self.flat), v=torch.zeros_like(self.flat), t=0,
-                               lr=lr, b1=betas[0], b2=betas[1], eps=eps)
-        guard.adam_init_guard(self.adam_state, self.flat.device, max_grad_norm, skip_nonfinite)
-
-    def guard_report(self):
-        """The guard's state block read back (the only sync of the guarded step): norm / coef / taken / clipped / skipped /
-        nonfinite, adam_state["t"] set to the steps taken; None without a guard."""
-        return guard.engine_guard_report(self)
-
-    def adam_step(self, gscale=1.0):
-        s = self.adam_state
-        if s.get("guard") is not None:
-            return guard.adam_step_guarded(self, gscale)
-        s["t"] += 1
-        call("wn_adam_flat", ptr(self.flat), ptr(self.flat_grad), ptr(s["m"]), ptr(s["v"]), self.spec.total,
-             s["lr"], s["b1"], s["b2"], s["eps"], 1.0 - s["b1"] ** s["t"], 1.0 - s["b2"] ** s["t"], gscale, _lib.stream())
-
 
 class Pass:
     """The launches of one forward (bw None: forward packs, forward arithmetic) or backward pass over a workspace.  Activation
@@ -360,9 +279,9 @@ class Pass:
 
     def wgrad(self, name, *args):
         """args = wn_wgrad's arguments up to relu_b, then ldc, t_lo, t_hi"""
-        so, n, chunk = self.bw["plan"][name]
+        op = self.bw["plan"][name]
         head, (ldc, t_lo, t_hi) = args[:-3], args[-3:]
-        call("wn_wgrad", *head, ptr(self.bw["slab"], so), ldc, n, t_lo, t_hi, chunk, self.B, self.mode, self.st)
+        call("wn_wgrad", *head, ptr(self.bw["slab"], op.so), ldc, op.n, t_lo, t_hi, op.chunk, self.B, self.mode, self.st)
 
     def bias_grad(self, name, a, a_bs, a_pitch, a_shift, rows, t_lo):
         eng = self.eng
