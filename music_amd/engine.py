@@ -18,6 +18,7 @@ import torch
 from . import _lib
 from ._lib import call, ptr
 from .engine_base import SLACK, PAD_BACK, EngineBase, SlabPlan, WorkspaceHold, WorkspacePool, _Spec, _pad  # noqa: F401 (re-exported)
+from .stack import GatedStack, diag, finish, full
 
 def pack_positions(mt, ks, chained):
     """Logical A-fragment order -> (row, k) of the effective weight matrix.
@@ -74,10 +75,8 @@ class WaveNetEngine(EngineBase):
         self._build_spec()
         self._build_packs()
         self._init_state()
-        # weight-gradient launches that only feed the final slab reduction run on a second HIP stream: the
-        # epilogue's three (2 rounds of workgroups at 80 % fill each) then pack into the data-gradient GEMMs'
-        # idle CUs (epilogue backward 1.25 -> 1.00 ms)
-        self.overlap_wgrad = True
+        # (overlap_wgrad, on the side stream: the epilogue's three weight gradients - 2 rounds of workgroups at 80 % fill each - pack
+        # into the data-gradient GEMMs' idle CUs, epilogue backward 1.25 -> 1.00 ms)
         # the forward epilogue's three products as this many per-clip-group chains, every second one on the side stream (1 = one
         # chain on the main stream; bit-identical results: tests/test_gpu_switches.py)
         self.epi_chains = 2
@@ -88,10 +87,13 @@ class WaveNetEngine(EngineBase):
         # Channel-split backward block with both weight gradients in the launch (wn_resblock_bwd_ms):
         # 64 padded channels, (f16x3, bf16x3) only; None = whenever it applies (WN_MS_BWD=0 turns it off)
         self.ms_bwd = None
-        self._side = None
         self.fine_marks = False
         # the unfused backward reads the forward's z (stored on the full valid range) for dWd
         self.z_from_fwd = True
+        bn = "dilation_layer_stack.%d.bias"
+        self.stack = GatedStack(self, "", self.CH, self.R, self.D, self._fr, self._br,
+                                lambda i: (self._bias_ptr(bn % (4 * i)), self._bias_ptr(bn % (4 * i + 1)), self._bias_ptr(bn % (4 * i + 2))),
+                                self.mode_fwd, self.mode_bwd, fmark=self.fmark, side_wgrad=True, zero_tail=True)
 
     def fmark(self, name):
         """Per-kernel timing marks of the epilogue (tools/kbench.py epi); off unless self.fine_marks."""
@@ -135,14 +137,17 @@ class WaveNetEngine(EngineBase):
             return None
         return ptr(self.flat, self.spec.off[name])
 
+    def _fr(self, name):
+        return ptr(self.pk_f, self.pk_f_off[name])
+
+    def _br(self, name):
+        return ptr(self.pk_b, self.pk_b_off[name])
+
     # ------------------------------------------------------------------ packs
     def _build_packs(self):
         sp, CH, N, R, D, S, Q, SP = self.spec, self.CH, self.N, self.R, self.D, self.S, self.Q, self.SP
         fwd, bwd = [], []            # lists of (name, idx array)
         gp = []                      # gradient C matrices: (name, rows, cols)
-
-        def full(m, k):
-            return np.full((m, k), -1, dtype=np.int64)
 
         # 1. causal: rows R, K = [tap0 Q | tap1 Q]
         wc = sp.conv("causal_layer.weight")                 # [R,Q,2]
@@ -190,15 +195,6 @@ class WaveNetEngine(EngineBase):
             if self.pair_ok:
                 # 12. the same four matrices block-diagonal for two clips side by side (rows / columns of a 32-block: clip A
                 #     then clip B) - what the 64-channel block kernels multiply in pair mode
-                def diag(m32, rb, cb):
-                    """m32: [rb*32][cb*32] blocks of 32 x 32 -> [rb*64][cb*64] with every block doubled on the diagonal"""
-                    out = full(rb * 64, cb * 64)
-                    for a_ in range(rb):
-                        for b_ in range(cb):
-                            blk = m32[a_ * 32:(a_ + 1) * 32, b_ * 32:(b_ + 1) * 32]
-                            for c_ in range(2):
-                                out[a_ * 64 + c_ * 32:a_ * 64 + (c_ + 1) * 32, b_ * 64 + c_ * 32:b_ * 64 + (c_ + 1) * 32] = blk
-                    return out
                 wfg32 = full(2 * CH, 2 * CH)
                 for h, src in enumerate((wf, wg)):
                     wfg32[h * CH:h * CH + D, 0:R] = src[:, :, 0]
@@ -238,19 +234,8 @@ class WaveNetEngine(EngineBase):
         bwd.append(("p2T", pack_index(np.ascontiguousarray(w.T))))        # rows SP, K = Q
 
         dev = self.device
-
-        def finish(lst, mode):
-            halfs_per_frag = 1024 if mode in (_lib.F16X3, _lib.BF16X3) else 512
-            offs, o = {}, 0
-            for name, idx in lst:
-                offs[name] = o * halfs_per_frag // 512          # offset in halfs of the packed buffer
-                o += len(idx)
-            idx_all = torch.from_numpy(np.concatenate([i for _, i in lst]).astype(np.int32)).to(dev)
-            buf = torch.zeros(o * halfs_per_frag // 512, dtype=torch.int16, device=dev)
-            return offs, idx_all, buf
-
-        self.pk_f_off, self.pk_f_idx, self.pk_f = finish(fwd, self.mode_fwd)
-        self.pk_b_off, self.pk_b_idx, self.pk_b = finish(bwd, self.mode_bwd)
+        self.pk_f_off, self.pk_f_idx, self.pk_f = finish(fwd, self.mode_fwd, dev)
+        self.pk_b_off, self.pk_b_idx, self.pk_b = finish(bwd, self.mode_bwd, dev)
 
         # gradient matrices + gather map (flat parameter element -> offset in gpack)
         self.gp_off, o = {}, 0
@@ -444,35 +429,19 @@ class WaveNetEngine(EngineBase):
         ws = ws or self._ws.get(B, T)
         st = _lib.stream()
         CH, N, SP, pitch, mf = self.CH, self.N, self.SP, ws["pitch"], self.mode_fwd
-        fr = lambda name: ptr(self.pk_f, self.pk_f_off[name])
-        xb = CH * pitch
+        fr = self._fr
         self._gen += 1
         ws["gen"] = self._gen
         ws["x_in"] = x
         # a one-hot built from integer codes by onehot() / the loader carries them along: the backward then forms the
         # causal layer's weight gradient by scatter instead of streaming the dense tensor (still valid only while the
         # tensor has not been written to since)
-        tag = getattr(x, "_wn_codes", None) if x is not None else None
-        ws["x_codes"] = (codes[0], bool(codes[1])) if x is None else None
-        if tag is not None:
-            codes, scrambled, version, cversion = tag
-            if (x._version == version and codes._version == cversion and codes.is_cuda and codes.dtype == torch.int32 and codes.is_contiguous() and
-                    tuple(codes.shape) == (B, T)):
-                ws["x_codes"] = (codes, scrambled)
+        ws["x_codes"] = (codes[0], bool(codes[1])) if x is None else self.tagged_codes(x, B, T)
         # what the backward re-checks: the causal layer's weight gradient is formed later from these same tensors
         ws["x_ver"] = None if x is None else x._version
         ws["codes_ver"] = None if ws["x_codes"] is None else ws["x_codes"][0]._version
         # causal conv (wavenet/model.py:104): x0[t] = W0 in[t-1] + W1 in[t], t in [1,T)
-        if ws["x_codes"] is not None:
-            # the input is the one-hot of known codes: a gather of weight columns (the dense tensor is not read)
-            codes, scrambled = ws["x_codes"]
-            call("wn_gather_grads", ptr(self.flat), ptr(self.wt_idx), ptr(self.wt), self.wt.numel(), st)
-            call("wn_causal_fwd_codes", ptr(codes), 1 if scrambled else 0, ptr(self.wt), self._bias_ptr("causal_layer.bias"),
-                 self.R, self._x(ws, 0), xb, pitch, CH, Q, T, B, st)
-        else:
-            call("wn_chan_gemm", ptr(x), ptr(x), Q * T, T, 0, T, -1, 0, Q // 32, Q // 32, fr("causal"), CH // 16, self.R,
-                 self._x(ws, 0), xb, pitch, 0, self._bias_ptr("causal_layer.bias"),
-                 None, 0, 0, 0, None, 0, 0, 1, T, 0, B, mf, st)
+        self.causal_fwd(ws, x, self.wt_idx, self.wt, fr("causal"), self._bias_ptr("causal_layer.bias"), self.R, CH, self._x(ws, 0), st, mf)
         zb = N * CH * pitch
         self.mark("causal_fwd")
         # z: the skip product needs it on the crop [rf-1, T) only, and the two-role / one-launch backward blocks recompute
@@ -480,19 +449,7 @@ class WaveNetEngine(EngineBase):
         # forward's z for dWd on the block's whole valid range [off_{i+1}, T) (19 % more z; it saves that path a second
         # copy written by its recompute kernel).
         z_whole = self.z_from_fwd and not ws["ms"] and not ws["pair"]      # (pair: the one-launch backward recomputes z)
-        for i, d in enumerate(self.dil):
-            bn = "dilation_layer_stack.%d.bias"
-            if ws["pair_fwd"]:
-                # two clips per 64-row tensor, block-diagonal packs; the second clip's z rows go to its own slice (z_half = zb)
-                call("wn_resblock_fwd", self._x(ws, i), self._x(ws, i + 1), ptr(ws["Z"], SLACK + i * CH * pitch), 2 * xb, 2 * zb,
-                     pitch, fr("fg2_%d" % i), fr("d2_%d" % i), None, None, None, 64, 64, 64, d, self.off[i + 1], T, self.rf - 1,
-                     1 if i < N - 1 else 0, None, 0, 0, 0, 0, 0, None, 0, None, zb, B // 2, mf, st)
-                continue
-            call("wn_resblock_fwd", self._x(ws, i), self._x(ws, i + 1), ptr(ws["Z"], SLACK + i * CH * pitch), xb, zb, pitch,
-                 fr("fg%d" % i), fr("d%d" % i), self._bias_ptr(bn % (4 * i)), self._bias_ptr(bn % (4 * i + 1)),
-                 self._bias_ptr(bn % (4 * i + 2)), self.D, self.R, CH, d, self.off[i + 1], T,
-                 self.off[i + 1] if z_whole else self.rf - 1,
-                 1 if i < N - 1 else 0, None, 0, 0, 0, 0, 0, None, 0, None, 0, B, mf, st)
+        self.stack.forward(B, T, pitch, ws["X"], ws["Z"], z_whole, st, pair=ws["pair_fwd"])
         self.mark("stack_fwd")
         lo = self.rf - 1
         bias_s = None
@@ -522,10 +479,7 @@ class WaveNetEngine(EngineBase):
             # the three products of each part of the clips as a chain of its own, every second chain on the side stream: a
             # product's half-empty last round of workgroups (408 tiles of 256 columns on 256 CUs) then packs into the other
             # chain's launches (0.435-0.445 vs 0.466-0.469 ms with two chains)
-            main = torch.cuda.current_stream()
-            if self._side is None:
-                self._side = _lib.side_stream(self.device)
-            side = self._side
+            main, side = torch.cuda.current_stream(), self._side_stream()
             ev = torch.cuda.Event()
             ev.record(main)
             side.wait_event(ev)
@@ -561,43 +515,13 @@ class WaveNetEngine(EngineBase):
         bw = self._bwd_workspace(ws)
         st = _lib.stream()
         B, T, W, pitch = ws["B"], ws["T"], ws["W"], ws["pitch"]
-        CH, N, SP, Q, mb, mf = self.CH, self.N, self.SP, self.Q, self.mode_bwd, self.mode_fwd
-        br = lambda name: ptr(self.pk_b, self.pk_b_off[name])
-        fr = lambda name: ptr(self.pk_f, self.pk_f_off[name])
-        lo = self.rf - 1
-        xb, zb, sb = CH * pitch, N * CH * pitch, SP * pitch
-        plan = bw["plan"]
-
-        def wgrad(name, *args):
-            """args = everything of wn_wgrad up to and including relu_b, then ldc, t_lo, t_hi"""
-            op = plan[name]
-            head, (ldc, t_lo, t_hi) = args[:-3], args[-3:]
-            call("wn_wgrad", *head, ptr(bw["slab"], op.so), ldc, op.n, t_lo, t_hi, op.chunk, B, mb, st)
+        CH, N, SP, Q, mb = self.CH, self.N, self.SP, self.Q, self.mode_bwd
+        br, lo = self._br, self.rf - 1
+        zb, sb = N * CH * pitch, SP * pitch
+        wgrad = lambda name, *args: self.wgrad(bw, B, mb, st, name, *args)
+        wgrad_s = lambda name, *args: self.wgrad_s(bw, B, mb, name, *args)
         dO, dH, dU, dZ = ptr(bw["dO"]), ptr(bw["dH"], SLACK), ptr(bw["dU"], SLACK), ptr(bw["dZ"], SLACK)
         U, H, Z = ptr(ws["U"], SLACK), ptr(ws["H"], SLACK), ptr(ws["Z"], SLACK)
-        main = torch.cuda.current_stream()
-        overlap = self.overlap_wgrad
-        if overlap and self._side is None:
-            # HIGH priority = its own hardware queue.  A default-priority stream is dealt one of a few hardware
-            # queues round-robin; once RCCL has created its streams (torchrun) the side stream landed on the
-            # MAIN stream's queue and the overlap silently disappeared (epilogue_bwd 0.99 -> 1.26 ms).
-            self._side = _lib.side_stream(self.device)
-        side = self._side if overlap else main
-
-        def on_side(fn):
-            """Run fn on the side stream after everything enqueued so far on the main stream."""
-            if overlap:
-                ev = torch.cuda.Event()
-                ev.record(main)
-                side.wait_event(ev)
-            with torch.cuda.stream(side):
-                fn(_lib.stream())
-
-        def wgrad_s(name, *args):
-            op = plan[name]
-            head, (ldc, t_lo, t_hi) = args[:-3], args[-3:]
-            on_side(lambda s2: call("wn_wgrad", *head, ptr(bw["slab"], op.so), ldc, op.n, t_lo, t_hi, op.chunk, B, mb, s2))
-
         # weight gradients of the epilogue run on the side stream as soon as their operands exist
         wgrad_s("p2", dO, Q * W, W, -lo, W, H, None, sb, pitch, 0, 0, pitch, SP // 16, Q // 16, 1, SP, lo, T)
         self.fmark("b_wgrad_p2")
@@ -618,12 +542,10 @@ class WaveNetEngine(EngineBase):
                 wgrad("skip", dU, sb, pitch, 0, pitch, Z, None, zb, pitch, 0, 0, pitch, N * CH // 16, SP // 16, 0, N * CH, lo, T)
             else:
                 wgrad_s("skip", dU, sb, pitch, 0, pitch, Z, None, zb, pitch, 0, 0, pitch, N * CH // 16, SP // 16, 0, N * CH, lo, T)
-            if order == "1" and overlap:
-                ev = torch.cuda.Event()
-                ev.record(side)
-                main.wait_event(ev)
+            if order == "1":
+                self.join_side()
             self.mark("epilogue_bwd")
-            return self._backward_stack(ws, bw, st, main, side, overlap, plan, wgrad)
+            return self._backward_stack(ws, bw, st)
         # dH = (P2^T dO) * [H > 0]
         call("wn_chan_gemm", dO, None, Q * W, W, 0, W, -lo, 0, Q // 32, 0, br("p2T"), SP // 16, self.S,
              dH, sb, pitch, 0, None, None, 0, 0, 0, H, sb, pitch, lo, T, 0, B, mb, st)
@@ -647,156 +569,38 @@ class WaveNetEngine(EngineBase):
                 call("wn_bias_grad", dU, sb, pitch, 0, self.S, lo, T, B,
                      ptr(self.gpack, bo["dilation_layer_stack.%d.bias" % (4 * i + 3)]), st)
         self.mark("epilogue_bwd")
-        return self._backward_stack(ws, bw, st, main, side, overlap, plan, wgrad)
+        return self._backward_stack(ws, bw, st)
 
-    def _backward_stack(self, ws, bw, st, main, side, overlap, plan, wgrad):
+    def _backward_stack(self, ws, bw, st):
         """The residual stack's backward, the causal layer's weight gradient and the slab reduction (second half of backward_from_dlogits)."""
-        B, T, W, pitch = ws["B"], ws["T"], ws["W"], ws["pitch"]
-        CH, N, SP, Q, mb, mf = self.CH, self.N, self.SP, self.Q, self.mode_bwd, self.mode_fwd
-        br = lambda name: ptr(self.pk_b, self.pk_b_off[name])
-        fr = lambda name: ptr(self.pk_f, self.pk_f_off[name])
-        lo = self.rf - 1
-        xb, zb, sb = CH * pitch, N * CH * pitch, SP * pitch
-        # The per-layer weight-gradient products only feed the slab reduction at the very end, so
-        # they run on a second HIP stream next to the data-gradient chain
-        # (resblock_bwd -> dx product -> next block); dfg / z scratch is double-buffered for that.
-        ev_w = [None, None]          # side-stream completion of the wgrads that read scratch buffer k
-        ev_prev = None               # ... of the previous layer's wgrads (they read dX[(i+1)%2])
-        for i in range(N - 1, -1, -1):
-            d = self.dil[i]
-            t_lo = self.off[i + 1]
-            k = i % 2
-            dfg, zs = ptr(bw["dfg"][k], SLACK), ptr(bw["zs"][k], SLACK)
-            dy = ptr(bw["dX"][(i + 1) % 2], SLACK) if i < N - 1 else None
-            bn = "dilation_layer_stack.%d.bias"
-            if overlap and ev_w[k] is not None:
-                main.wait_event(ev_w[k])
-            if bw["pq"] or bw["pair"]:
-                p_out, q_out = (ptr(t, SLACK) for t in bw["PQ"][i % 2])
-                chain = 1 if bw["chain"][i] else 0
-                if i == 0 and chain:
-                    # a first block in chain form (d_0 a multiple of 32) hands dx_0 on WHOLE: straight into the buffer the causal
-                    # layer's weight gradient reads (same layout and stride as the (P, Q) buffers)
-                    p_out = ptr(bw["dX"][0], SLACK)
-                if i < N - 1:
-                    p_in, q_in = (ptr(t, SLACK) for t in bw["PQ"][(i + 1) % 2])
-                    dn, p_lo = self.dil[i + 1], self.off[i + 2]
-                    if bw["chain"][i + 1]:                    # the block above handed dx on whole (valid from ITS t_lo - d = this t_lo)
-                        q_in, dn, p_lo = None, 0, t_lo
-                else:
-                    p_in = q_in = None
-                    dn = p_lo = 0
-                if bw["pair"]:
-                    # clip pairs on the 64-channel block: block-diagonal packs, the second clip's dz rows in its own slice
-                    call("wn_resblock_bwd_pq", self._x(ws, i), p_in, q_in, dn, p_lo, ptr(bw["dZ"], SLACK + i * CH * pitch),
-                         p_out, q_out, 2 * xb, 2 * zb, pitch, fr("fg2_%d" % i), br("dT2_%d" % i), br("pq2_%d" % i), 64, d, t_lo, T, lo,
-                         ptr(bw["slab"], plan["fg2_%d" % i].so), ptr(bw["slab"], plan["d2_%d" % i].so) if i < N - 1 else None,
-                         None, 0, 0, 0, None, None, zb, chain, B // 2, mf, mb, st)
-                else:
-                    call("wn_resblock_bwd_pq", self._x(ws, i), p_in, q_in, dn, p_lo, ptr(bw["dZ"], SLACK + i * CH * pitch),
-                         p_out, q_out, xb, zb, pitch, fr("fg%d" % i), br("dT%d" % i), br("pq%d" % i), CH, d, t_lo, T, lo,
-                         ptr(bw["slab"], plan["fg%d" % i].so), ptr(bw["slab"], plan["d%d" % i].so) if i < N - 1 else None,
-                         None, 0, 0, 0, None, None, 0, chain, B, mf, mb, st)
-                self.fmark("b_block")
-                if i == 0 and not chain:
-                    # dx_0 for the causal layer: the pair made whole once (19 us; the scatter from codes can also take the
-                    # pair as it is - wn_causal_wgrad_codes(dx_q) - but its doubled, masked tile loads cost the same 20 us)
-                    call("wn_shift_add", p_out, q_out, ptr(bw["dX"][0], SLACK), xb, pitch, CH, d, t_lo, self.off[0], T, B, st)
-                continue
-            if bw["ms"]:
-                call("wn_resblock_bwd_ms", self._x(ws, i), dy, ptr(bw["dZ"], SLACK + i * CH * pitch), dfg, xb, zb, 2 * CH * pitch,
-                     pitch, fr("fg%d" % i), br("dT%d" % i), self._bias_ptr(bn % (4 * i)), self._bias_ptr(bn % (4 * i + 1)),
-                     self.D, CH, d, t_lo, T, lo, ptr(bw["slab"], plan["fg%d" % i].so),
-                     ptr(bw["slab"], plan["d%d" % i].so) if i < N - 1 else None, None, 0, 0, 0, 0, 0, B, mf, mb, st)
-                self.fmark("b_block")
-                if self.use_bias:
-                    bo = self.gp_bias_off
-                    call("wn_bias_grad", dfg, 2 * CH * pitch, pitch, 0, self.D, t_lo, T, B, ptr(self.gpack, bo[bn % (4 * i)]), st)
-                    call("wn_bias_grad", ptr(bw["dfg"][k], SLACK + CH * pitch), 2 * CH * pitch, pitch, 0, self.D, t_lo, T, B,
-                         ptr(self.gpack, bo[bn % (4 * i + 1)]), st)
-                    if i < N - 1:
-                        call("wn_bias_grad", dy, xb, pitch, 0, self.R, t_lo, T, B, ptr(self.gpack, bo[bn % (4 * i + 2)]), st)
-                # input range [t_lo, pitch): the [df;dg] scratch holds zeros beyond T (never written: every store is
-                # masked to t < T, and pitch >= T + 512 >= T + d), so the waves at the end of a clip need not take
-                # the guarded-load path for the shifted tap.  (Below t_lo the guard IS needed: dx exists on
-                # [t_lo - d, T) and the unshifted tap must read zeros there, not another layer's stale rows.)
-                call("wn_chan_gemm", dfg, dfg, 2 * CH * pitch, pitch, t_lo, pitch, 0, d, 2 * CH // 32, 2 * CH // 32, br("fgT%d" % i),
-                     CH // 16, self.R, ptr(bw["dX"][i % 2], SLACK), xb, pitch, 0, None,
-                     dy, xb, pitch, t_lo, None, 0, 0, self.off[i], T, 0, B, mb, st)
-                self.fmark("b_dx")
-                continue
-            zs = None if self.z_from_fwd else zs
-            call("wn_resblock_bwd", self._x(ws, i), dy, ptr(bw["dZ"], SLACK + i * CH * pitch), dfg, zs,
-                 xb, zb, 2 * CH * pitch, xb, pitch, fr("fg%d" % i), br("dT%d" % i),
-                 self._bias_ptr(bn % (4 * i)), self._bias_ptr(bn % (4 * i + 1)), self.D, CH, d, t_lo, T, lo,
-                 None, 0, 0, 0, 0, 0, B, mf, mb, st)
-            if overlap:
-                ev_r = torch.cuda.Event()
-                ev_r.record(main)
-                side.wait_event(ev_r)
-            with torch.cuda.stream(side):
-                st2 = _lib.stream()
-                op = plan["fg%d" % i]
-                call("wn_wgrad", dfg, 2 * CH * pitch, pitch, 0, pitch, self._x(ws, i), self._x(ws, i), xb, pitch, -d, 0, pitch,
-                     CH // 16, 2 * CH // 16, 0, ptr(bw["slab"], op.so), 2 * CH, op.n, t_lo, T, op.chunk, B, mb, st2)
-                if i < N - 1:
-                    op = plan["d%d" % i]
-                    zsrc, zstr = (ptr(ws["Z"], SLACK + i * CH * pitch), zb) if self.z_from_fwd else (zs, xb)
-                    call("wn_wgrad", dy, xb, pitch, 0, pitch, zsrc, None, zstr, pitch, 0, 0, pitch, CH // 16, CH // 16, 0,
-                         ptr(bw["slab"], op.so), CH, op.n, t_lo, T, op.chunk, B, mb, st2)
-                if self.use_bias:
-                    bo = self.gp_bias_off
-                    call("wn_bias_grad", dfg, 2 * CH * pitch, pitch, 0, self.D, t_lo, T, B, ptr(self.gpack, bo[bn % (4 * i)]), st2)
-                    call("wn_bias_grad", ptr(bw["dfg"][k], SLACK + CH * pitch), 2 * CH * pitch, pitch, 0, self.D, t_lo, T, B,
-                         ptr(self.gpack, bo[bn % (4 * i + 1)]), st2)
-                    if i < N - 1:
-                        call("wn_bias_grad", dy, xb, pitch, 0, self.R, t_lo, T, B, ptr(self.gpack, bo[bn % (4 * i + 2)]), st2)
-                if overlap:
-                    ev_w[k] = torch.cuda.Event()
-                    ev_w[k].record(side)
-            # dx_i[t] = W1^T dfg[t] + W0^T dfg[t+d] + dy[t]        on [off_i, T)
-            # (writes dX[i%2], which the PREVIOUS layer's weight gradients may still be reading)
-            if overlap and ev_prev is not None:
-                main.wait_event(ev_prev)
-            call("wn_chan_gemm", dfg, dfg, 2 * CH * pitch, pitch, t_lo, pitch, 0, d, 2 * CH // 32, 2 * CH // 32, br("fgT%d" % i),
-                 CH // 16, self.R, ptr(bw["dX"][i % 2], SLACK), xb, pitch, 0, None,
-                 dy, xb, pitch, t_lo, None, 0, 0, self.off[i], T, 0, B, mb, st)
-            ev_prev = ev_w[k]
-        if overlap:
-            for e in ev_w:
-                if e is not None:
-                    main.wait_event(e)
-            ev_join = torch.cuda.Event()          # everything on the side stream (epilogue weight gradients)
-            ev_join.record(side)
-            main.wait_event(ev_join)
+        B, T, pitch, CH = ws["B"], ws["T"], ws["pitch"], self.CH
+
+        def bias_grads(i, dfg, dy, t_lo, s_):
+            """row sums of [df;dg] and of dy: the gradients of block i's three biases"""
+            if self.use_bias:
+                bo, bn = self.gp_bias_off, "dilation_layer_stack.%d.bias"
+                call("wn_bias_grad", dfg, 2 * CH * pitch, pitch, 0, self.D, t_lo, T, B, ptr(self.gpack, bo[bn % (4 * i)]), s_)
+                call("wn_bias_grad", dfg + 4 * CH * pitch, 2 * CH * pitch, pitch, 0, self.D, t_lo, T, B, ptr(self.gpack, bo[bn % (4 * i + 1)]), s_)
+                if dy is not None:
+                    call("wn_bias_grad", dy, CH * pitch, pitch, 0, self.R, t_lo, T, B, ptr(self.gpack, bo[bn % (4 * i + 2)]), s_)
+        # The per-layer weight-gradient products of the fallback form only feed the slab reduction at the very end, so they run on the
+        # side stream next to the data-gradient chain (resblock_bwd -> dx product -> next block); dfg / z scratch is double-buffered for that.
+        form = "pq" if bw["pq"] or bw["pair"] else "ms" if bw["ms"] else "rw"
+        self.stack.backward(form, B, T, pitch, ws["X"], ws["Z"], bw, bw["dX"], st, chain=bw["chain"], dfg=bw["dfg"],
+                            zs=None if self.z_from_fwd else bw["zs"], pair=bw["pair"], hook=bias_grads)
+        self.join_side()              # everything on the side stream (epilogue weight gradients)
         self.mark("stack_bwd")
         # causal weight gradient: dWc[r][q][tap] = sum dx0[r][t] in[q][t-1+tap]
-        x = ws["x_in"]
         dx0 = ptr(bw["dX"][0], SLACK)
-        desc = bw["desc"]
         # the input and the codes it was built from must still be what the forward saw (_check_input_unchanged; onehot() documents
         # the tensor as immutable while tagged)
         self._check_input_unchanged(ws)
-        x_codes, cv = ws.get("x_codes"), ws.get("codes_ver")
-        if x_codes is not None and cv is not None and x_codes[0]._version != cv:
-            if x is None:
-                raise RuntimeError("music_amd: the integer codes of this forward were modified in place before backward()")
-            x_codes = None                  # the dense tensor is intact: the dense weight-gradient product
-        if x_codes is not None:
-            codes, scrambled = x_codes
-            call("wn_causal_wgrad_codes", ptr(codes), 1 if scrambled else 0, dx0, None, 0, 0, xb, pitch, CH, Q, T, B,
-                 ptr(bw["slab"], plan["causal_codes"].so), st)
-            desc = bw["desc_codes"]
-        else:
-            wgrad("causal", dx0, xb, pitch, 0, pitch, ptr(x), ptr(x), Q * T, T, -1, 0, T, Q // 16, CH // 16, 0, 2 * Q, 1, T)
+        x_codes = self.codes_for_backward(ws)
+        self.causal_wgrad(ws, bw, x_codes, "causal", dx0, CH, st, self.mode_bwd)
         if self.use_bias:
-            call("wn_bias_grad", dx0, xb, pitch, 0, self.R, 1, T, B, ptr(self.gpack, self.gp_bias_off["causal_layer.bias"]), st)
+            call("wn_bias_grad", dx0, CH * pitch, pitch, 0, self.R, 1, T, B, ptr(self.gpack, self.gp_bias_off["causal_layer.bias"]), st)
         self.mark("causal_bwd")
-        call("wn_reduce_slabs", ptr(desc), bw["nops"], bw["vec"], ptr(bw["slab"]), ptr(self.gpack), st)
-        if bw["pair"]:
-            call("wn_gather_grads2", ptr(self.gpack), ptr(self.gidx_pa), ptr(self.gidx_pb), ptr(self.flat_grad), self.spec.total, st)
-        else:
-            call("wn_gather_grads", ptr(self.gpack), ptr(self.gidx), ptr(self.flat_grad), self.spec.total, st)
+        self.reduce_and_gather(bw, x_codes is not None, st)
         self.mark("slab_reduce")
 
     def input_grad(self, ws):
@@ -806,12 +610,7 @@ class WaveNetEngine(EngineBase):
         bw = ws["bwd"]
         if bw is None:
             raise RuntimeError("music_amd: input_grad() needs the backward of this forward to have run")
-        B, T, pitch, CH, Q = ws["B"], ws["T"], ws["pitch"], self.CH, self.Q
-        din = torch.empty(B, Q, T, dtype=torch.float32, device=self.device)
-        dx0 = ptr(bw["dX"][0], SLACK)
-        call("wn_chan_gemm", dx0, dx0, CH * pitch, pitch, 1, T, 0, 1, CH // 32, CH // 32, ptr(self.pk_b, self.pk_b_off["causalT"]), Q // 16, Q,
-             ptr(din), Q * T, T, 0, None, None, 0, 0, 0, None, 0, 0, 0, T, 0, B, self.mode_bwd, _lib.stream())
-        return din
+        return self.causal_input_grad(ws, bw["dX"][0], self.CH, self._br("causalT"), self.mode_bwd)
 
     def backward(self, ws, dprobs):
         """dprobs: (B*W, Q) gradient w.r.t. the probabilities returned by forward()."""

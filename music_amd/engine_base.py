@@ -175,6 +175,10 @@ class EngineBase:
         self.marks = None            # list of (name, torch.cuda.Event) when profiling is on
         self.mark_only = None        # optional set of mark names to keep
         self._throttle = _lib.StepThrottle()   # at most WN_MAX_STEPS_IN_FLIGHT fused steps in flight
+        # weight-gradient launches that only feed the final slab reduction run on a second HIP stream (on_side): their half-empty
+        # last rounds of workgroups pack into the data-gradient launches beside them
+        self._side = None
+        self.overlap_wgrad = True
 
     def mark(self, name):
         """Record a timing event on the current stream (only when self.marks is a list; self.mark_only, if set, limits
@@ -205,6 +209,102 @@ class EngineBase:
         (autograd's own rule for saved tensors); writes that do not (x.data.zero_(), a raw-pointer kernel) cannot be."""
         if ws.get("x_ver") is not None and ws["x_in"]._version != ws["x_ver"]:
             raise RuntimeError("music_amd: the input of this forward was modified in place before backward()")
+
+    # ------------------------------------------------------------------ the second stream
+    def _side_stream(self):
+        """THE side stream of this device (_lib.side_stream: high priority = a hardware queue of its own), created at first use."""
+        if self._side is None:
+            self._side = _lib.side_stream(self.device)
+        return self._side
+
+    def on_side(self, fn):
+        """fn(stream) on the side stream, behind everything enqueued so far on the main stream; overlap_wgrad off: on the main stream."""
+        if not self.overlap_wgrad:
+            return fn(_lib.stream())
+        side, ev = self._side_stream(), torch.cuda.Event()
+        ev.record(torch.cuda.current_stream())
+        side.wait_event(ev)
+        with torch.cuda.stream(side):
+            fn(_lib.stream())
+
+    def join_side(self):
+        """The main stream waits for everything enqueued so far on the side stream."""
+        if self.overlap_wgrad:
+            ev = torch.cuda.Event()
+            ev.record(self._side_stream())
+            torch.cuda.current_stream().wait_event(ev)
+
+    # ------------------------------------------------------------------ weight gradients: slabs, reduction, gather
+    def wgrad(self, bw, B, mode, st, name, *args):
+        """wn_wgrad into the slabs of op `name` of bw["plan"]; args = everything of wn_wgrad up to and including relu_b, then ldc, t_lo, t_hi"""
+        op = bw["plan"][name]
+        head, (ldc, t_lo, t_hi) = args[:-3], args[-3:]
+        call("wn_wgrad", *head, ptr(bw["slab"], op.so), ldc, op.n, t_lo, t_hi, op.chunk, B, mode, st)
+
+    def wgrad_s(self, bw, B, mode, name, *args):
+        """... on the side stream, as soon as its operands exist"""
+        self.on_side(lambda s2: self.wgrad(bw, B, mode, s2, name, *args))
+
+    def reduce_and_gather(self, bw, from_codes, st):
+        """slabs -> gradient pack (one batched sum in a fixed order; the second table where a causal layer's gradient came from codes) ->
+        flat_grad (pair mode: a stack weight's gradient is the sum of its two copies in the block-diagonal matrix)"""
+        call("wn_reduce_slabs", ptr(bw["desc_codes"] if from_codes else bw["desc"]), bw["nops"], bw["vec"], ptr(bw["slab"]), ptr(self.gpack), st)
+        if bw["pair"]:
+            call("wn_gather_grads2", ptr(self.gpack), ptr(self.gidx_pa), ptr(self.gidx_pb), ptr(self.flat_grad), self.spec.total, st)
+        else:
+            call("wn_gather_grads", ptr(self.gpack), ptr(self.gidx), ptr(self.flat_grad), self.spec.total, st)
+
+    # ------------------------------------------------------------------ the causal layer(s): from integer codes, else dense
+    @staticmethod
+    def tagged_codes(x, B, T):
+        """(codes, scrambled) of a one-hot that onehot() / the loader built from integer codes and that still is what it was then (the
+        tensor and the codes are immutable while tagged: an in-place op that bumps a version counter drops the tag's fast path), else None"""
+        tag = getattr(x, "_wn_codes", None) if x is not None else None
+        if tag is not None:
+            codes, scrambled, version, cversion = tag
+            if (x._version == version and codes._version == cversion and codes.is_cuda and codes.dtype == torch.int32 and
+                    codes.is_contiguous() and tuple(codes.shape) == (B, T)):
+                return codes, scrambled
+        return None
+
+    def causal_fwd(self, ws, x, wt_idx, wt, wpack, bias, R, CH, out, st, mode):
+        """x0[t] = W0 in[t-1] + W1 in[t] on [1, T): a gather of weight columns where the input is the one-hot of known codes
+        (ws["x_codes"]; the dense tensor is not read), else the channel product over the dense input"""
+        B, T, pitch, Q = ws["B"], ws["T"], ws["pitch"], self.Q
+        if ws["x_codes"] is None:
+            return call("wn_chan_gemm", ptr(x), ptr(x), Q * T, T, 0, T, -1, 0, Q // 32, Q // 32, wpack, CH // 16, R, out, CH * pitch, pitch, 0, bias,
+                        None, 0, 0, 0, None, 0, 0, 1, T, 0, B, mode, st)
+        codes, scrambled = ws["x_codes"]
+        call("wn_gather_grads", ptr(self.flat), ptr(wt_idx), ptr(wt), wt.numel(), st)
+        call("wn_causal_fwd_codes", ptr(codes), 1 if scrambled else 0, ptr(wt), bias, R, out, CH * pitch, pitch, CH, Q, T, B, st)
+
+    def codes_for_backward(self, ws):
+        """ws["x_codes"] if the codes are still what the forward saw (where it noted their version); changed codes beside an intact dense
+        input: None, the dense weight-gradient product"""
+        x_codes, cv = ws.get("x_codes"), ws.get("codes_ver")
+        if x_codes is not None and cv is not None and x_codes[0]._version != cv:
+            if ws["x_in"] is None:
+                raise RuntimeError("music_amd: the integer codes of this forward were modified in place before backward()")
+            return None
+        return x_codes
+
+    def causal_wgrad(self, ws, bw, x_codes, name, dx0, CH, st, mode):
+        """dWc[r][q][tap] = sum dx0[r][t] in[q][t-1+tap] into the slabs of `name`: a scatter from the codes (slabs `name`_codes), else dense"""
+        B, T, pitch, Q, x = ws["B"], ws["T"], ws["pitch"], self.Q, ws["x_in"]
+        if x_codes is not None:
+            return call("wn_causal_wgrad_codes", ptr(x_codes[0]), 1 if x_codes[1] else 0, dx0, None, 0, 0, CH * pitch, pitch, CH, Q, T, B,
+                        ptr(bw["slab"], bw["plan"][name + "_codes"].so), st)
+        self.wgrad(bw, B, mode, st, name, dx0, CH * pitch, pitch, 0, pitch, ptr(x), ptr(x), Q * T, T, -1, 0, T, Q // 16, CH // 16, 0, 2 * Q, 1, T)
+
+    def causal_input_grad(self, ws, dx0, CH, wpackT, mode):
+        """din[q][s] = sum_r W[r][q][1] dx0[r][s] + W[r][q][0] dx0[r][s + 1], dx0 (the first block's data gradient, which the backward
+        leaves in its workspace) living on [1, T): one channel product with the transposed causal weight"""
+        B, T, pitch, Q = ws["B"], ws["T"], ws["pitch"], self.Q
+        din = torch.empty(B, Q, T, dtype=torch.float32, device=self.device)
+        dx0 = ptr(dx0, SLACK)
+        call("wn_chan_gemm", dx0, dx0, CH * pitch, pitch, 1, T, 0, 1, CH // 32, CH // 32, wpackT, Q // 16, Q,
+             ptr(din), Q * T, T, 0, None, None, 0, 0, 0, None, 0, 0, 0, T, 0, B, mode, _lib.stream())
+        return din
 
     # ------------------------------------------------------------------ fused training step
     def softmax_ce(self, logits, target, probs, dlogits, loss_part, n):

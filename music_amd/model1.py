@@ -31,11 +31,13 @@ try:
     from ._lib import call, ptr
     from .engine import pack_index, pack_positions
     from .engine_base import SLACK, PAD_BACK, EngineBase, SlabPlan, WorkspaceHold, _Spec, _pad
+    from .stack import Cond, GatedStack, diag, enc_resblock_bwd_pq, enc_resblock_fwd, finish, full, hand_over
 except ImportError:
     from music_amd import _lib, _losshook
     from music_amd._lib import call, ptr
     from music_amd.engine import pack_index, pack_positions
     from music_amd.engine_base import SLACK, PAD_BACK, EngineBase, SlabPlan, WorkspaceHold, _Spec, _pad
+    from music_amd.stack import Cond, GatedStack, diag, enc_resblock_bwd_pq, enc_resblock_fwd, finish, full, hand_over
 
 
 class _AutoencoderEngine(EngineBase):
@@ -83,8 +85,13 @@ class _AutoencoderEngine(EngineBase):
                 p.data = view
         self._build_packs()
         self._init_state()
-        self._side = None            # second HIP stream for the epilogue's weight gradients (as music_amd/engine.py)
-        self.overlap_wgrad = True
+
+        def de_bias(i):
+            """the filter_gate bias is one tensor, gate rows first"""
+            bias_fg = self._bias("de_dilation_layer_stack.%d" % (3 * i))
+            return bias_fg + 4 * self.Dd if bias_fg is not None else None, bias_fg, self._bias("de_dilation_layer_stack.%d" % (3 * i + 1))
+        # the decoder stack: its weight gradients stay on the main stream, its blocks never chain (conditioned blocks hand the pair on)
+        self.decoder = GatedStack(self, "de_", self.CHd, self.Rd, self.Dd, self._fr, self._br, de_bias, self.mode, self.mode_b)
 
     def _stage_cond(self, cond):
         """cond (N+1 CPU (weight, bias) pairs) -> device tensors cw (N, 2Dd, Bw), cb (N, 2Dd), cfw (Sd, Bw, 1), cfb (Sd) through one
@@ -119,6 +126,12 @@ class _AutoencoderEngine(EngineBase):
     def _bias(self, name):
         return ptr(self.flat, self.spec.off[name + ".bias"]) if self.use_bias else None
 
+    def _fr(self, name):
+        return ptr(self.pk, self.pk_off[name])
+
+    def _br(self, name):
+        return ptr(self.pkb, self.pkb_off[name])
+
     def _build_packs(self):
         sp, Q, N = self.spec, self.Q, self.N
         CHe, CHd, SP, BwP = self.CHe, self.CHd, self.SP, self.BwP
@@ -126,9 +139,6 @@ class _AutoencoderEngine(EngineBase):
         fwd, bwd, gp = [], [], []
         gidx = np.full(self.spec.total, -1, dtype=np.int64)
         gsize = [0]
-
-        def full(m, k):
-            return np.full((m, k), -1, dtype=np.int64)
 
         def add(name, w, chained=False, grad=True):
             """forward pack of the effective matrix w (entries = flat parameter offsets) + its
@@ -142,16 +152,6 @@ class _AutoencoderEngine(EngineBase):
                 gsize[0] += w.size
 
         pa, pb = {}, {}                                      # pair mode: parameter offset -> its two places in a block-diagonal gradient
-
-        def diag(m32, rb, cb):
-            """[rb*32][cb*32] blocks of 32 x 32 -> [rb*64][cb*64], every block doubled on the diagonal (clip A, clip B)"""
-            out = full(rb * 64, cb * 64)
-            for a_ in range(rb):
-                for b_ in range(cb):
-                    blk = m32[a_ * 32:(a_ + 1) * 32, b_ * 32:(b_ + 1) * 32]
-                    for c_ in range(2):
-                        out[a_ * 64 + c_ * 32:a_ * 64 + (c_ + 1) * 32, b_ * 64 + c_ * 32:b_ * 64 + (c_ + 1) * 32] = blk
-            return out
 
         def add2(name, w32, rb, cb, chained=False):
             """pair-mode forward pack + gradient matrix of the block-diagonal form of w32, and where each parameter's two
@@ -250,17 +250,8 @@ class _AutoencoderEngine(EngineBase):
         add("c2", w)
         bwd.append(("c2T", pack_index(np.ascontiguousarray(w.T))))
 
-        def finish(lst, mode):
-            hp = 1024 if mode in (_lib.F16X3, _lib.BF16X3) else 512
-            offs, o = {}, 0
-            for name, idx in lst:
-                offs[name] = o * hp // 512
-                o += len(idx)
-            idx_all = torch.from_numpy(np.concatenate([i for _, i in lst]).astype(np.int32)).to(self.device)
-            return offs, idx_all, torch.zeros(o * hp // 512, dtype=torch.int16, device=self.device)
-
-        self.pk_off, self.pk_idx, self.pk = finish(fwd, self.mode)
-        self.pkb_off, self.pkb_idx, self.pkb = finish(bwd, self.mode_b)
+        self.pk_off, self.pk_idx, self.pk = finish(fwd, self.mode, self.device)
+        self.pkb_off, self.pkb_idx, self.pkb = finish(bwd, self.mode_b, self.device)
         self.gp_off = {name: (o, r, c) for name, o, r, c in gp}
         self.gpack = torch.zeros(gsize[0], dtype=torch.float32, device=self.device)
         self.gidx = torch.from_numpy(gidx.astype(np.int32)).to(self.device)   # -1 (biases) -> zero gradient
@@ -302,13 +293,7 @@ class _AutoencoderEngine(EngineBase):
         pair_f = pair and (B // 2) * ((T + 511) // 512) >= 200
         # a one-hot built from integer codes (engine.onehot / the loader) carries them: both causal layers then run on the
         # codes (gather forward, scatter backward), as in music_amd/engine.py
-        ws["x_codes"] = None
-        tag = getattr(x, "_wn_codes", None)
-        if tag is not None:
-            codes, scrambled, version, cversion = tag
-            if (x._version == version and codes._version == cversion and codes.is_cuda and codes.dtype == torch.int32 and
-                    codes.is_contiguous() and tuple(codes.shape) == (B, T)):
-                ws["x_codes"] = (codes, scrambled)
+        ws["x_codes"] = self.tagged_codes(x, B, T)
         st = _lib.stream()
         m, pitch, N, CHe, CHd, SP, BwP = self.mode, ws["pitch"], self.N, self.CHe, self.CHd, self.SP, self.BwP
         # the 31 conditioning projections (drawn on the CPU, model1.py:178,216) go to the device FIRST, in one asynchronous copy
@@ -316,8 +301,7 @@ class _AutoencoderEngine(EngineBase):
         # stack and the decoder start from an empty queue (0.35 ms for this phase at config 4)
         cw, cb, cfw, cfb = self._stage_cond(cond)
         call("wn_pack_weights", ptr(self.flat), ptr(self.pk_idx), ptr(self.pk), self.pk_idx.numel(), m, st)
-        fr = lambda name: ptr(self.pk, self.pk_off[name])
-        lo = self.rf - 1
+        fr, lo = self._fr, self.rf - 1
         NONE3 = (None, 0, 0)
         gemm = lambda pack, *a: self._gemm(st, B, m, fr(pack), *a)
 
@@ -326,29 +310,17 @@ class _AutoencoderEngine(EngineBase):
         he = lambda i: self._lay(ws["He"], i, CHe, ws)
         E = ptr(ws["E"], SLACK)
         eb = CHe * pitch
-        def causal(name, ch, rows, out, obs, bias):
-            if ws["x_codes"] is None:
-                gemm(name, ptr(x), ptr(x), Q * T, T, 0, T, -1, 0, Q // 32, Q // 32, ch // 16, rows, out, obs, pitch, 0, bias,
-                     NONE3, NONE3, 1, T, 0)
-                return
-            codes, scrambled = ws["x_codes"]
-            call("wn_gather_grads", ptr(self.flat), ptr(self.wt_idx[name]), ptr(self.wt[name]), self.wt[name].numel(), st)
-            call("wn_causal_fwd_codes", ptr(codes), 1 if scrambled else 0, ptr(self.wt[name]), bias, rows, out, obs, pitch, ch, Q, T,
-                 B, st)
+        causal = lambda name, ch, rows, out: self.causal_fwd(ws, x, self.wt_idx[name], self.wt[name], fr(name), self._bias(name + "_layer"),
+                                                             rows, ch, out, st, m)
         self.mark("begin")
-        causal("en_causal", CHe, self.Re, xe(0), eb, self._bias("en_causal_layer"))
+        causal("en_causal", CHe, self.Re, xe(0))
         self.mark("en_causal_fwd")
         for i, d in enumerate(self.dil):
             t_lo = self.off[i + 1]
             # h = dilated_conv(relu(x));   x' = dense(relu(h)) + x[tail]
-            if pair_f:                       # two clips per 64-row tensor, block-diagonal packs
-                call("wn_enc_resblock_fwd", xe(i), xe(i + 1), he(i), 2 * eb, 2 * eb, pitch, fr("en_dil2_%d" % i), fr("en_dense2_%d" % i),
-                     None, None, 64, 64, 64, d, t_lo, T, B // 2, m, st)
-                continue
-            if self.fused_encoder:
-                call("wn_enc_resblock_fwd", xe(i), xe(i + 1), he(i), eb, eb, pitch, fr("en_dil%d" % i), fr("en_dense_c%d" % i),
-                     self._bias("en_dilation_layer_stack.%d" % i), self._bias("en_dense_layer_stack.%d" % i), self.De, self.Re,
-                     CHe, d, t_lo, T, B, m, st)
+            if pair_f or self.fused_encoder:     # (pair: two clips per 64-row tensor, block-diagonal packs)
+                enc_resblock_fwd(fr, i, xe(i), xe(i + 1), he(i), eb, pitch, (self._bias("en_dilation_layer_stack.%d" % i),
+                                 self._bias("en_dense_layer_stack.%d" % i)), self.De, self.Re, CHe, d, t_lo, T, B, m, st, pair=pair_f)
                 continue
             gemm("en_dil%d" % i, xe(i), xe(i), eb, pitch, self.off[i], T, -d, 0, CHe // 32, CHe // 32, CHe // 16, self.De,
                  he(i), eb, pitch, 0, self._bias("en_dilation_layer_stack.%d" % i), NONE3, NONE3, t_lo, T, 1)
@@ -371,8 +343,8 @@ class _AutoencoderEngine(EngineBase):
 
         # ---------------- decoder (model1.py:158-225)
         xd = lambda i: self._lay(ws["Xd"], i, CHd, ws)
-        db, zb = CHd * pitch, N * CHd * pitch
-        causal("de_causal", CHd, self.Rd, xd(0), db, self._bias("de_causal_layer"))
+        zb = N * CHd * pitch
+        causal("de_causal", CHd, self.Rd, xd(0))
         self.mark("bottleneck_cond_de_causal")
         bn = "de_dilation_layer_stack.%d"
         cmodes = []
@@ -409,22 +381,11 @@ class _AutoencoderEngine(EngineBase):
                 call("wn_pack_weights", ptr(tab), ptr(ws["ctab_idx"]), ptr(ws["ctab_pk"]), ws["ctab_idx"].numel(), m, st)
                 cpk, cix = ws["ctab_pk"], ws["cidx"]
         cpb = 2 * CHp * 32 * 2                          # halfs of one clip's packed table (hi + lo planes)
-        for i, d in enumerate(self.dil):
-            t_lo = self.off[i + 1]
-            mode_c, q = cmodes[i]
-            if pair_f:
-                call("wn_resblock_fwd", xd(i), xd(i + 1), ptr(ws["Z"], SLACK + i * CHd * pitch), 2 * db, 2 * zb, pitch,
-                     fr("de_fg2_%d" % i), fr("de_d2_%d" % i), None, None, None, 64, 64, 64, d,
-                     t_lo, T, t_lo, 1 if i < N - 1 else 0, ptr(tab[i]), 4 * CHd * Le, Le, mode_c, Le, q,
-                     ptr(cpk, i * Bp * cpb), cpb, ptr(cix[i]), zb, Bp, m, st)
-                continue
-            bias_fg = self._bias(bn % (3 * i))
-            bf = bias_fg + 4 * Dd if bias_fg is not None else None      # filter_gate bias: gate rows first
-            call("wn_resblock_fwd", xd(i), xd(i + 1), ptr(ws["Z"], SLACK + i * CHd * pitch), db, zb, pitch,
-                 fr("de_fg%d" % i), fr("de_d%d" % i), bf, bias_fg, self._bias(bn % (3 * i + 1)), Dd, self.Rd, CHd, d,
-                 t_lo, T, t_lo, 1 if i < N - 1 else 0, ptr(tab_c[i]), 2 * CHd * Le, Le, mode_c, Le, q,
-                 ptr(cpk, i * B * cpb) if cpk is not None else None, cpb, ptr(cix[i]) if cix is not None else None,
-                 0, B, m, st)   # z on the whole valid range: the backward's dWd reads it
+        tab_f, n_f = (tab, Bp) if pair_f else (tab_c, B)    # the 64-row pair tables, or per clip
+        cond_f = lambda i: Cond(ptr(tab_f[i]), tab_f.shape[2] * Le, Le, *cmodes[i], ptr(cpk, i * n_f * cpb) if cpk is not None else None, cpb,
+                                ptr(cix[i]) if cix is not None else None)
+        # z on the whole valid range: the backward's dWd reads it
+        self.decoder.forward(B, T, pitch, ws["Xd"], ws["Z"], True, st, cond=cond_f, pair=pair_f)
         self.mark("dec_stack_fwd")
         U, R1, C1 = ptr(ws["U"], SLACK), ptr(ws["R1"], SLACK), ptr(ws["C1"], SLACK)
         sb = SP * pitch
@@ -453,10 +414,7 @@ class _AutoencoderEngine(EngineBase):
         # the other chain's launches (music_amd/engine.py epi_chains; bit-identical results)
         nsplit = min(2, B)
         if nsplit >= 2 and self.overlap_wgrad:
-            main = torch.cuda.current_stream()
-            if self._side is None:
-                self._side = _lib.side_stream(self.device)
-            side = self._side
+            main, side = torch.cuda.current_stream(), self._side_stream()
             ev = torch.cuda.Event()
             ev.record(main)
             side.wait_event(ev)
@@ -557,14 +515,8 @@ class _AutoencoderEngine(EngineBase):
         bw = ws["bwd"]
         if bw is None:
             raise RuntimeError("music_amd: input_grad() needs the backward of this forward to have run")
-        B, T, pitch, Q = ws["B"], ws["T"], ws["pitch"], self.Q
-        parts = []
-        for name, ch, key in (("de_causalT", self.CHd, "dXd"), ("en_causalT", self.CHe, "dXe")):
-            out = torch.empty(B, Q, T, dtype=torch.float32, device=self.device)
-            dx0 = ptr(bw[key][0], SLACK)
-            call("wn_chan_gemm", dx0, dx0, ch * pitch, pitch, 1, T, 0, 1, ch // 32, ch // 32, ptr(self.pkb, self.pkb_off[name]), Q // 16, Q,
-                 ptr(out), Q * T, T, 0, None, None, 0, 0, 0, None, 0, 0, 0, T, 0, B, self.mode_b, _lib.stream())
-            parts.append(out)
+        parts = [self.causal_input_grad(ws, bw[key][0], ch, self._br(name), self.mode_b)
+                 for name, ch, key in (("de_causalT", self.CHd, "dXd"), ("en_causalT", self.CHe, "dXe"))]
         return parts[0].add_(parts[1])
 
     def backward(self, ws, dprobs):
@@ -594,40 +546,17 @@ class _AutoencoderEngine(EngineBase):
         B, T, W, pitch, Le = ws["B"], ws["T"], ws["W"], ws["pitch"], ws["Le"]
         N, CHe, CHd, SP, BwP, Q = self.N, self.CHe, self.CHd, self.SP, self.BwP, self.Q
         Dd, Sd, Rd, Re, De, Bw = self.Dd, self.Sd, self.Rd, self.Re, self.De, self.Bw
-        mf, mb = self.mode, self.mode_b
-        lo = self.rf - 1
+        mb, lo = self.mode_b, self.rf - 1
         call("wn_pack_weights", ptr(self.flat), ptr(self.pkb_idx), ptr(self.pkb), self.pkb_idx.numel(), mb, st)
-        br = lambda name: ptr(self.pkb, self.pkb_off[name])
-        fr = lambda name: ptr(self.pk, self.pk_off[name])
+        br = self._br
         NONE3 = (None, 0, 0)
         gemm = lambda pack, *a: self._gemm(st, B, mb, br(pack), *a)
         plan = bw["plan"]
-
-        def wgrad(name, *args):
-            op = plan[name]
-            head, (ldc, t_lo, t_hi) = args[:-3], args[-3:]
-            call("wn_wgrad", *head, ptr(bw["slab"], op.so), ldc, op.n, t_lo, t_hi, op.chunk, B, mb, st)
-
-        # the decoder epilogue's three weight gradients only feed the slab reduction at the very end: on a second
-        # (high-priority = own hardware queue) stream their half-empty last rounds of workgroups pack into the
-        # data-gradient GEMMs beside them, as in music_amd/engine.py (config 4: 1.30 -> ~1.0 ms for this phase)
-        main = torch.cuda.current_stream()
-        overlap = self.overlap_wgrad
-        if overlap and self._side is None:
-            self._side = _lib.side_stream(self.device)
-        side = self._side if overlap else main
-
-        def wgrad_s(name, *args):
-            if not overlap:
-                return wgrad(name, *args)
-            op = plan[name]
-            head, (ldc, t_lo, t_hi) = args[:-3], args[-3:]
-            ev = torch.cuda.Event()
-            ev.record(main)
-            side.wait_event(ev)
-            with torch.cuda.stream(side):
-                call("wn_wgrad", *head, ptr(bw["slab"], op.so), ldc, op.n, t_lo, t_hi, op.chunk, B, mb, _lib.stream())
-
+        # the decoder epilogue's three weight gradients only feed the slab reduction at the very end: on the side stream their
+        # half-empty last rounds of workgroups pack into the data-gradient GEMMs beside them, as in music_amd/engine.py
+        # (config 4: 1.30 -> ~1.0 ms for this phase)
+        wgrad = lambda name, *args: self.wgrad(bw, B, mb, st, name, *args)
+        wgrad_s = lambda name, *args: self.wgrad_s(bw, B, mb, name, *args)
         if dprobs is not None:
             dprobs = dprobs.contiguous()
             call("wn_chunk_softmax256_bwd", ptr(ws["probs"]), ptr(dprobs), ptr(bw["dO"]), B * W, st)
@@ -648,10 +577,7 @@ class _AutoencoderEngine(EngineBase):
             call("wn_cond_grad", dR1, sb, pitch, Sd, lo, T, cmode, Le, max(cq, 1), ptr(d_enf), Sd * Le, Le, B, st)
             wgrad_s("c1", dR1, sb, pitch, 0, pitch, U, None, sb, pitch, 0, 0, pitch, SP // 16, SP // 16, 1, SP, lo, T)
             wgrad("skip", dU, sb, pitch, 0, pitch, Z, None, zb, pitch, 0, 0, pitch, N * CHd // 16, SP // 16, 0, N * CHd, lo, T)
-            if overlap:
-                ev = torch.cuda.Event()
-                ev.record(side)
-                main.wait_event(ev)
+            self.join_side()
         else:
             gemm("c2T", dO, None, Q * W, W, 0, W, -lo, 0, Q // 32, 0, SP // 16, Sd, dR1, sb, pitch, 0, None, NONE3,
                  (R1, sb, pitch), lo, T, 0)
@@ -669,11 +595,9 @@ class _AutoencoderEngine(EngineBase):
                  NONE3, lo, T, 0)
         self.mark("ce_epilogue_bwd")
         # ---- decoder stack
-        xd = lambda i: self._lay(ws["Xd"], i, CHd, ws)
-        dfg = ptr(bw["dfg"], SLACK) if "dfg" in bw else None
         d_tab = torch.zeros(N, B, 2 * CHd, Le, dtype=torch.float32, device=self.device)
         pair = bw["pair"]
-        Bp, sfx = (B // 2, "2_") if pair else (B, "")
+        Bp, rows = (B // 2, 4 * CHd) if pair else (B, 2 * CHd)
         if pair:
             d_tab = torch.zeros(N, Bp, 4 * CHd, Le, dtype=torch.float32, device=self.device)     # rows [f: A B | g: A B]
         if bw["pq"] and "cslab" not in bw:
@@ -683,84 +607,34 @@ class _AutoencoderEngine(EngineBase):
             bw["cs_off"] = (ctypes.c_int64 * N)(*np.concatenate([[0], np.cumsum(fl)[:-1]]).tolist())
             bw["cs_tlo"] = (ctypes.c_int * N)(*[self.off[i + 1] for i in range(N)])
             bw["cslab"] = torch.empty(sum(fl), dtype=torch.float32, device=self.device)
-        for i in range(N - 1, -1, -1):
-            d, t_lo = self.dil[i], self.off[i + 1]
-            dy = ptr(bw["dXd"][(i + 1) % 2], SLACK) if i < N - 1 else None
-            mode_c, q = ws["cmodes"][i]
-            bias_fg = self._bias("de_dilation_layer_stack.%d" % (3 * i))
-            bf = bias_fg + 4 * Dd if bias_fg is not None else None      # filter_gate bias: gate rows first
 
-            def block_bias_grads():
-                if not self.use_bias:
-                    return
+        def cond(i):
+            """block i's table; the one-launch block gathers by bucket bytes and leaves bucket sums of [df;dg] in its region of cslab"""
+            mode_c, q = ws["cmodes"][i]
+            mc = dict(cidx=ptr(ws["cidx"][i]), cslab=ptr(bw["cslab"], bw["cs_off"][i])) if bw["pq"] else {}
+            return Cond(ptr(ws["tab"][i]), rows * Le, Le, mode_c, max(q, 1), **mc)
+
+        def dfg_grads(i, dfg, dy, t_lo, s_):
+            """behind a block that wrote [df;dg]: the conditioning gradient (sums over each pooled frame's samples) and the bias gradients"""
+            mode_c, q = ws["cmodes"][i]
+            call("wn_cond_grad", dfg, 2 * CHd * pitch, pitch, 2 * CHd, t_lo, T, mode_c, Le, max(q, 1), ptr(d_tab[i]), 2 * CHd * Le, Le, B, s_)
+            if self.use_bias:
                 nm = "de_dilation_layer_stack.%d" % (3 * i)
                 bias_grad(nm, dfg + 4 * CHd * pitch, 2 * CHd * pitch, pitch, 0, Dd, t_lo, T)          # gate rows = dg
                 bias_grad(nm, dfg, 2 * CHd * pitch, pitch, 0, Dd, t_lo, T, dst=Dd)                    # filter rows = df
                 if dy is not None:
                     bias_grad("de_dilation_layer_stack.%d" % (3 * i + 1), dy, db, pitch, 0, Rd, t_lo, T)
-            if bw["pq"]:
-                p_out, q_out = (ptr(t, SLACK) for t in bw["PQ"][i % 2])
-                if i < N - 1:
-                    p_in, q_in = (ptr(t, SLACK) for t in bw["PQ"][(i + 1) % 2])
-                    dn, p_lo = self.dil[i + 1], self.off[i + 2]
-                else:
-                    p_in = q_in = None
-                    dn = p_lo = 0
-                if pair:
-                    call("wn_resblock_bwd_pq", xd(i), p_in, q_in, dn, p_lo, ptr(bw["dZ"], SLACK + i * CHd * pitch), p_out, q_out,
-                         2 * db, 2 * zb, pitch, fr("de_fg2_%d" % i), br("de_dT2_%d" % i), br("de_pq2_%d" % i), 64, d, t_lo, T, lo,
-                         ptr(bw["slab"], plan["de_fg2_%d" % i].so), ptr(bw["slab"], plan["de_d2_%d" % i].so) if i < N - 1 else None,
-                         ptr(ws["tab"][i]), 4 * CHd * Le, Le, Le, ptr(ws["cidx"][i]), ptr(bw["cslab"], bw["cs_off"][i]), zb, 0, Bp, mf, mb, st)
-                else:
-                    call("wn_resblock_bwd_pq", xd(i), p_in, q_in, dn, p_lo, ptr(bw["dZ"], SLACK + i * CHd * pitch), p_out, q_out,
-                         db, zb, pitch, fr("de_fg%d" % i), br("de_dT%d" % i), br("de_pq%d" % i), CHd, d, t_lo, T, lo,
-                         ptr(bw["slab"], plan["de_fg%d" % i].so), ptr(bw["slab"], plan["de_d%d" % i].so) if i < N - 1 else None,
-                         ptr(ws["tab"][i]), 2 * CHd * Le, Le, Le, ptr(ws["cidx"][i]), ptr(bw["cslab"], bw["cs_off"][i]), 0, 0, B, mf, mb, st)
-                if i == 0:
-                    call("wn_shift_add", p_out, q_out, ptr(bw["dXd"][0], SLACK), db, pitch, CHd, d, t_lo, self.off[0], T, B, st)
-                continue
-            if bw["ms"]:
-                call("wn_resblock_bwd_ms", xd(i), dy, ptr(bw["dZ"], SLACK + i * CHd * pitch), dfg, db, zb, 2 * CHd * pitch, pitch,
-                     fr("de_fg%d" % i), br("de_dT%d" % i), bf, bias_fg, Dd, CHd, d, t_lo, T, lo,
-                     ptr(bw["slab"], plan["de_fg%d" % i].so), ptr(bw["slab"], plan["de_d%d" % i].so) if i < N - 1 else None,
-                     ptr(ws["tab"][i]), 2 * CHd * Le, Le, mode_c, Le, max(q, 1), B, mf, mb, st)
-                call("wn_cond_grad", dfg, 2 * CHd * pitch, pitch, 2 * CHd, t_lo, T, mode_c, Le, max(q, 1),
-                     ptr(d_tab[i]), 2 * CHd * Le, Le, B, st)
-                block_bias_grads()
-                gemm("de_fgT%d" % i, dfg, dfg, 2 * CHd * pitch, pitch, t_lo, T, 0, d, 2 * CHd // 32, 2 * CHd // 32, CHd // 16, Rd,
-                     ptr(bw["dXd"][i % 2], SLACK), db, pitch, 0, None, (dy, db, pitch, t_lo) if dy else NONE3, NONE3, self.off[i], T, 0)
-                continue
-            call("wn_resblock_bwd", xd(i), dy, ptr(bw["dZ"], SLACK + i * CHd * pitch), dfg, None,
-                 db, zb, 2 * CHd * pitch, db, pitch, fr("de_fg%d" % i), br("de_dT%d" % i), bf, bias_fg, Dd, CHd, d, t_lo, T, lo,
-                 ptr(ws["tab"][i]), 2 * CHd * Le, Le, mode_c, Le, max(q, 1), B, mf, mb, st)
-            call("wn_cond_grad", dfg, 2 * CHd * pitch, pitch, 2 * CHd, t_lo, T, mode_c, Le, max(q, 1),
-                 ptr(d_tab[i]), 2 * CHd * Le, Le, B, st)
-            block_bias_grads()
-            wgrad("de_fg%d" % i, dfg, 2 * CHd * pitch, pitch, 0, pitch, xd(i), xd(i), db, pitch, -d, 0, pitch,
-                  CHd // 16, 2 * CHd // 16, 0, 2 * CHd, t_lo, T)
-            if i < N - 1:
-                wgrad("de_d%d" % i, dy, db, pitch, 0, pitch, ptr(ws["Z"], SLACK + i * CHd * pitch), None, zb, pitch, 0, 0, pitch,
-                      CHd // 16, CHd // 16, 0, CHd, t_lo, T)
-            gemm("de_fgT%d" % i, dfg, dfg, 2 * CHd * pitch, pitch, t_lo, T, 0, d, 2 * CHd // 32, 2 * CHd // 32, CHd // 16, Rd,
-                 ptr(bw["dXd"][i % 2], SLACK), db, pitch, 0, None, (dy, db, pitch, t_lo) if dy else NONE3, NONE3, self.off[i], T, 0)
+        self.decoder.backward("pq" if bw["pq"] else "ms" if bw["ms"] else "rw", B, T, pitch, ws["Xd"], ws["Z"], bw, bw["dXd"], st,
+                              chain=[False] * N, dfg=[bw["dfg"]] if "dfg" in bw else None, cond=cond, pair=pair, hook=dfg_grads)
         if bw["pq"]:
-            rows = 4 * CHd if pair else 2 * CHd
             call("wn_resblock_bwd_pq_cond_reduce", ptr(bw["cslab"]), bw["cs_off"], bw["cs_tlo"], N, T, Bp, Le, ptr(d_tab),
                  Bp * rows * Le, rows * Le, Le, st)
             if pair:                                    # back to per-clip tables, rows [f | g]
                 d_tab = d_tab.view(N, Bp, 2, 2, CHd, Le).permute(0, 1, 3, 2, 4, 5).reshape(N, B, 2 * CHd, Le)
         self.mark("dec_stack_bwd")
-        x = ws["x_in"]
-        codes_path = ws.get("x_codes") is not None
-
-        def causal_wgrad(name, dx0, bs, ch):
-            if codes_path:
-                codes, scrambled = ws["x_codes"]
-                call("wn_causal_wgrad_codes", ptr(codes), 1 if scrambled else 0, dx0, None, 0, 0, bs, pitch, ch, Q, T, B,
-                     ptr(bw["slab"], plan[name + "_codes"].so), st)
-            else:
-                wgrad(name, dx0, bs, pitch, 0, pitch, ptr(x), ptr(x), Q * T, T, -1, 0, T, Q // 16, ch // 16, 0, 2 * Q, 1, T)
-        causal_wgrad("de_causal", ptr(bw["dXd"][0], SLACK), db, CHd)
+        x_codes = self.codes_for_backward(ws)
+        causal_wgrad = lambda name, dx0, ch: self.causal_wgrad(ws, bw, x_codes, name, dx0, ch, st, mb)
+        causal_wgrad("de_causal", ptr(bw["dXd"][0], SLACK), CHd)
         bias_grad("de_causal_layer", ptr(bw["dXd"][0], SLACK), db, pitch, 0, Rd, 1, T)
         # ---- conditioning: en_i = cw_i enc + b (rows in the reference order: gate first), enf = cfw enc + b
         d_en = torch.cat([d_tab[:, :, CHd:CHd + Dd], d_tab[:, :, :Dd]], 2)            # (N,B,2Dd,Le) reference row order
@@ -784,27 +658,13 @@ class _AutoencoderEngine(EngineBase):
             dy = dxe[(i + 1) % 2]
             if bw["enc_pq"]:
                 # the whole backward of the block in one launch; dx travels as the unshifted pair (P, Q)
-                p_out, q_out = (ptr(t, SLACK) for t in bw["PQe"][i % 2])
-                chain = bw["enc_chain"][i]
-                if i == 0 and chain:
-                    p_out = dxe[0]                                # a first block in chain form hands dx_0 on whole: straight to the causal layer's buffer
-                if i < N - 1:
-                    p_in, q_in = (ptr(t, SLACK) for t in bw["PQe"][(i + 1) % 2])
-                    dn, p_lo = self.dil[i + 1], self.off[i + 2]
-                    if bw["enc_chain"][i + 1]:                    # the block above handed dx on whole (valid from ITS t_lo - d = this t_lo)
-                        q_in, dn, p_lo = None, 0, t_lo
-                else:
-                    p_in, q_in, dn, p_lo = dy, None, 0, y_lo
-                if pair:
-                    call("wn_enc_resblock_bwd_pq", xe(i), p_in, q_in, dn, p_lo, he(i), p_out, q_out, 2 * eb, 2 * eb, pitch,
-                         br("en_denseT2_%d" % i), br("en_pq2_%d" % i), 64, d, t_lo, T, ptr(bw["slab"], plan["en_dil2_%d" % i].so),
-                         ptr(bw["slab"], plan["en_dense2_%d" % i].so), chain, Bp, mb, st)
-                else:
-                    call("wn_enc_resblock_bwd_pq", xe(i), p_in, q_in, dn, p_lo, he(i), p_out, q_out, eb, eb, pitch,
-                         br("en_denseT%d" % i), br("en_pq%d" % i), CHe, d, t_lo, T, ptr(bw["slab"], plan["en_dil%d" % i].so),
-                         ptr(bw["slab"], plan["en_dense%d" % i].so), chain, B, mb, st)
+                hand, chain = hand_over(i, N, bw["enc_chain"], bw["PQe"], bw["dXe"][0], self.dil, self.off), bw["enc_chain"][i]
+                q_out = ptr(bw["PQe"][i % 2][1], SLACK)
+                if i == N - 1:
+                    hand = (dy, None, 0, y_lo, hand[4])           # the top block takes the bottleneck's data gradient, whole, on the crop
+                enc_resblock_bwd_pq(br, plan, bw["slab"], i, xe(i), hand, he(i), q_out, eb, pitch, CHe, d, t_lo, T, chain, B, mb, st, pair=pair)
                 if i == 0 and not chain:
-                    call("wn_shift_add", p_out, q_out, dxe[0], eb, pitch, CHe, d, t_lo, self.off[0], T, B, st)
+                    call("wn_shift_add", hand[4], q_out, dxe[0], eb, pitch, CHe, d, t_lo, self.off[0], T, B, st)
                 continue
             if bw["enc_fused"]:
                 # dh, dW1 = sum dy relu(h)^T and dWdil = sum dh [relu x(t-d) | relu x(t)]^T in one launch
@@ -827,18 +687,10 @@ class _AutoencoderEngine(EngineBase):
             gemm("en_dilT%d" % i, dHe, dHe, eb, pitch, t_lo, T, 0, d, CHe // 32, CHe // 32, CHe // 16, Re, dxe[i % 2], eb, pitch, 0,
                  None, (dy, eb, pitch, y_lo), (xe(i), eb, pitch), self.off[i], T, 0)
         self.mark("enc_stack_bwd")
-        causal_wgrad("en_causal", dxe[0], eb, CHe)
+        causal_wgrad("en_causal", dxe[0], CHe)
         bias_grad("en_causal_layer", dxe[0], eb, pitch, 0, Re, 1, T)
-        if overlap:
-            ev_join = torch.cuda.Event()
-            ev_join.record(side)
-            main.wait_event(ev_join)
-        call("wn_reduce_slabs", ptr(bw["desc_codes"] if codes_path else bw["desc"]), bw["nops"], bw["vec"], ptr(bw["slab"]),
-             ptr(self.gpack), st)
-        if pair:
-            call("wn_gather_grads2", ptr(self.gpack), ptr(self.gidx_pa), ptr(self.gidx_pb), ptr(self.flat_grad), self.spec.total, st)
-        else:
-            call("wn_gather_grads", ptr(self.gpack), ptr(self.gidx), ptr(self.flat_grad), self.spec.total, st)
+        self.join_side()
+        self.reduce_and_gather(bw, x_codes is not None, st)
         if self.use_bias:
             self.flat_grad.index_copy_(0, b_idx, b_grad)
         self.mark("en_causal_slab_reduce")
