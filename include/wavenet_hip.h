@@ -373,6 +373,21 @@ int wn_sgd_flat_guarded(float* p, const float* g, float* momentum_buf, int64_t n
                         const wn_guard_state* state, wn_stream_t stream);
 int wn_rmsprop_flat_guarded(float* p, const float* g, float* square_avg, float* momentum_buf, int64_t n, float lr, float alpha,
                             float eps, float momentum, float gscale, const wn_guard_state* state, wn_stream_t stream);
+/* EMA shadow of the parameters - the weights every WaveNet recipe samples from (tf.train.ExponentialMovingAverage(decay,
+ * num_updates) in the NSynth code; torch.optim.swa_utils.get_ema_avg_fn's lerp rule).  The reference keeps none.  One launch on
+ * `stream` behind the optimizer's update: no allocation, no synchronisation, no atomics, legal under stream capture.  Per element,
+ * in float32 (an fma may form the sum):
+ *   d_eff = warmup ? min(decay, (1 + T) / (10 + T)) : decay     (in double from the float `decay`, rounded once to float)
+ *   w = 1.0f - d_eff;   ema[i] = ema[i] + w * (p[i] - ema[i])
+ * state == NULL: T = t, the caller's count of updates including this one (t >= 1).
+ * state != NULL: the block a wn_grad_guard on the same stream wrote for this step.  With state->skip set nothing is written (the
+ *   shadow stays bit for bit); else T = state->n_taken + t, where t is an OFFSET: 0 in a fresh run, set by a host that restored a
+ *   run whose device counter was seeded differently (a T below 1 counts as 1).
+ * ema and p: n floats each at ANY 4-byte aligned addresses (not necessarily alike); p is never written, nothing outside [0, n) is
+ * touched.  n == 0 returns 0 (NULLs allowed).  -4, the argument named in wn_last_error: n < 0; NULL ema or p with n > 0; a
+ * misaligned pointer (state: 8 bytes); decay outside [0, 1) or NaN; t < 1 with state == NULL. */
+int wn_ema_flat(float* ema, const float* p, int64_t n, float decay, int warmup, int64_t t, const wn_guard_state* state,
+                wn_stream_t stream);
 /* The reference's nn.DataParallel gradient reduction (wavenet/train.py:116-122) as ONE in-place sum over the ranks of the flat
  * fp32 gradient buffer: ncclAllReduce(buf, buf, n, ncclFloat32, ncclSum, comm, stream) on the caller's RCCL communicator
  * (`comm` = an ncclComm_t).  The 1 / world_size of the mean goes into wn_adam_flat's gscale.  Returns -5 when RCCL is neither

@@ -85,6 +85,7 @@ SIGNATURES = {
     "wn_adam_flat_guarded": [_p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _p, _p],
     "wn_sgd_flat_guarded": [_p, _p, _p, _l, _f, _f, _f, _p, _p],
     "wn_rmsprop_flat_guarded": [_p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _p, _p],
+    "wn_ema_flat": [_p, _p, _l, _f, _i, _l, _p, _p],
     "wn_coll_available": [],
     "wn_comm_unique_id": [_p],
     "wn_comm_create": [_i, _i, _p, _p],
@@ -221,7 +222,11 @@ def load():
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
     for name, args in SIGNATURES.items():
-        fn = getattr(lib, name)            # AttributeError here = header/library out of sync
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:             # header / library out of sync: a libwavenet_hip.so built from older sources
+            raise WavenetHipError("%s does not export %s: it was built from older sources - rebuild it (`make -C music_amd/csrc`)"
+                                  % (LIB_PATH, name)) from None
         fn.argtypes = args
         fn.restype = ctypes.c_int
     lib.wn_decode_sync_granules.restype = ctypes.c_int64

@@ -18,7 +18,10 @@ of a loss line that does not contain it (:110-116: ``int("is")``), is the number
 Optional key in train_params.json (as in music_amd/train.py): ``"fused_step"`` (bool, Adam only) - the whole step runs
 as forward + one softmax/CE/backward kernel + backward + flat Adam on the engine, without autograd.  ``"max_grad_norm"``
 (float) and ``"skip_nonfinite"`` (bool): global-norm clipping of the gradient and the skipping of a non-finite step
-(music_amd/guard.py; on the device for the fused step), with a line per ``print_every`` in ``guard_log.log``.
+(music_amd/guard.py; on the device for the fused step), with a line per ``print_every`` in ``guard_log.log``.  ``"ema_decay"``
+(float) and ``"ema_warmup"`` (bool): the EMA shadow of the parameters (music_amd/ema.py; on the device for the fused step),
+written as ``wavenet_autoencoder{N}.ema`` next to every checkpoint in the checkpoint's own format and read back when that
+checkpoint is restored.
 """
 import glob
 import os
@@ -29,12 +32,14 @@ import torch.optim as optim
 
 try:
     from . import dist as wdist
+    from . import ema
     from . import guard
     from .faster_audio_data import audio_data_loader
     from .model1 import wavenet_autoencoder
     from .train import get_params, load_model
 except ImportError:
     from music_amd import dist as wdist
+    from music_amd import ema
     from music_amd import guard
     from music_amd.faster_audio_data import audio_data_loader
     from music_amd.model1 import wavenet_autoencoder
@@ -50,11 +55,13 @@ def get_arguments():
 
 def _host_guarded(cls):
     """`cls` (a torch optimizer class) with the guard's rule applied on the host before every step (music_amd/guard.py): the step of
-    this harness is torch's own per-tensor path, where a read-back per step is already the rule."""
+    this harness is torch's own per-tensor path, where a read-back per step is already the rule.  With `ema` (ema_decay set) every
+    step ends with the shadow's update (music_amd/ema.py), guarded or not."""
     class Guarded(guard.GuardedOptimizer, cls):
-        def __init__(self, params, max_grad_norm, skip_nonfinite, **kw):
-            super().__init__(params, **kw)
+        def __init__(self, model, max_grad_norm, skip_nonfinite, ema_decay=None, ema_warmup=False, **kw):
+            super().__init__(model.parameters(), **kw)
             self._guard_setup(max_grad_norm, skip_nonfinite)
+            self._ema_setup(model.named_parameters(), ema_decay, ema_warmup)
 
         def load_state_dict(self, state_dict):
             super().load_state_dict(state_dict)
@@ -66,20 +73,22 @@ def _host_guarded(cls):
     return Guarded
 
 
-def get_optimizer(model, optimizer_type, learning_rate, momentum1=False, max_grad_norm=None, skip_nonfinite=False):
+def get_optimizer(model, optimizer_type, learning_rate, momentum1=False, max_grad_norm=None, skip_nonfinite=False, ema_decay=None,
+                  ema_warmup=False):
     """wavenet_autoencoder/train.py:26-34 (with ``optim.sgd`` spelled ``optim.SGD``).  max_grad_norm / skip_nonfinite: the same
-    optimizer with its gradient clipped to that global norm / a non-finite step not applied (not for 'lbfgs', whose closure is
-    evaluated many times per step)."""
-    if guard.enabled(max_grad_norm, skip_nonfinite):
-        kw = dict(max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, lr=learning_rate)
+    optimizer with its gradient clipped to that global norm / a non-finite step not applied; ema_decay / ema_warmup: with `ema`,
+    the EMA shadow of the parameters, updated behind every step (neither for 'lbfgs', whose closure is evaluated many times per
+    step).  All unset: torch's own class."""
+    if guard.enabled(max_grad_norm, skip_nonfinite) or ema_decay is not None:
+        kw = dict(max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, ema_decay=ema_decay, ema_warmup=ema_warmup, lr=learning_rate)
         if optimizer_type == 'sgd':
-            return _host_guarded(optim.SGD)(model.parameters(), momentum=momentum1 or 0, **kw)
+            return _host_guarded(optim.SGD)(model, momentum=momentum1 or 0, **kw)
         if optimizer_type == 'RMSprop':
-            return _host_guarded(optim.RMSprop)(model.parameters(), momentum=momentum1 or 0, **kw)
+            return _host_guarded(optim.RMSprop)(model, momentum=momentum1 or 0, **kw)
         if optimizer_type == 'Adam':
-            return _host_guarded(optim.Adam)(model.parameters(), **kw)
+            return _host_guarded(optim.Adam)(model, **kw)
         if optimizer_type == 'lbfgs':
-            raise ValueError("max_grad_norm / skip_nonfinite do not apply to the 'lbfgs' optimizer")
+            raise ValueError("max_grad_norm / skip_nonfinite / ema_decay do not apply to the 'lbfgs' optimizer")
         return None
     if optimizer_type == 'sgd':
         return optim.SGD(model.parameters(), lr=learning_rate, momentum=momentum1 or 0)
@@ -119,6 +128,15 @@ def _epoch_of(name):
     return int(os.path.basename(name).split('.')[0][len(PREFIX):])
 
 
+def _rotate_checkpoints(stored, max_check_points):
+    """Delete the numerically oldest of the `stored` .model files once max_check_points exist, and its .ema with it."""
+    if len(stored) == max_check_points:
+        oldest = sorted(stored, key=_epoch_of)[0]
+        os.remove(oldest)
+        if os.path.exists(oldest[:-len(".model")] + ".ema"):
+            os.remove(oldest[:-len(".model")] + ".ema")
+
+
 def train():
     cuda_available = torch.cuda.is_available()
     train_params, model_params, dataset_params = get_arguments()
@@ -129,12 +147,14 @@ def train():
         torch.manual_seed(int(train_params["seed"]))
     net = wavenet_autoencoder(**model_params)
     epoch_trained = 0
+    restored_from = None
     if train_params["restore_model"]:
         restored = load_model(net, train_params["restore_dir"], train_params["restore_model"])
         if restored is None:
             print("Initialize network and train from scratch.")
         else:
             epoch_trained = _epoch_of(train_params["restore_model"])
+            restored_from = train_params["restore_dir"] + train_params["restore_model"]
     if cuda_available is False and train_params["device_ids"] is not None:
         raise ValueError("Cuda is not avalable,", " can not train model using multi-gpu.")
     if world > 1:
@@ -145,9 +165,12 @@ def train():
         net = net.cuda()
     wdist.broadcast_parameters(list(net.parameters()))
     max_gn, skip_nf = guard.guard_options(train_params)
+    ema_decay, ema_warmup = ema.ema_options(train_params)
+    fused = (bool(train_params.get("fused_step")) and cuda_available and
+             str(train_params.get("optimizer_type", train_params.get("optimizer", "Adam"))).lower() == "adam")
     optimizer = get_optimizer(net, train_params.get("optimizer_type", train_params.get("optimizer", "Adam")),
                               train_params["learning_rate"], train_params.get("momentum", False), max_grad_norm=max_gn,
-                              skip_nonfinite=skip_nf)
+                              skip_nonfinite=skip_nf, ema_decay=None if fused else ema_decay, ema_warmup=ema_warmup)
     loss_func = nn.CrossEntropyLoss()
     is_writer = rank == 0
     loss_log_file = store_log_file = None
@@ -162,12 +185,16 @@ def train():
     device = next(net.parameters()).device
     total_loss = torch.zeros((), dtype=torch.float64, device=device)
     step_seed = int(train_params.get("seed") or 0)
-    fused = (bool(train_params.get("fused_step")) and cuda_available and
-             str(train_params.get("optimizer_type", train_params.get("optimizer", "Adam"))).lower() == "adam")
     engine = None
     if fused:
         engine = net._engine_for(device)
-        engine.adam_init(lr=train_params["learning_rate"], max_grad_norm=max_gn, skip_nonfinite=skip_nf)
+        engine.adam_init(lr=train_params["learning_rate"], max_grad_norm=max_gn, skip_nonfinite=skip_nf, ema_decay=ema_decay,
+                         ema_warmup=ema_warmup)
+    # the EMA shadow (music_amd/ema.py); no optimizer state is kept by this harness, so a resumed run's warm-up counts as finished
+    shadow = engine.ema if fused else getattr(optimizer, "ema", None)
+    if shadow is not None and restored_from is not None:
+        ema.restore_shadow(shadow, restored_from[:-len(".model")] + ".ema", None,
+                           engine.adam_state.get("guard") if fused else optimizer._guard)
     guard_log = None
     if guard.enabled(max_gn, skip_nf) and is_writer:
         guard_log = guard.GuardLog(
@@ -219,9 +246,10 @@ def train():
                 total_loss.zero_()
         if (epoch + 1) % train_params["check_point_every"] == 0 and is_writer:
             stored = glob.glob(train_params["restore_dir"] + "*.model")
-            if len(stored) == train_params["max_check_points"]:
-                os.remove(sorted(stored, key=_epoch_of)[0])
+            _rotate_checkpoints(stored, train_params["max_check_points"])
             save_model(net, epoch_trained + epoch + 1, train_params["restore_dir"])
+            if shadow is not None:
+                ema.save_shadow(shadow, train_params["restore_dir"] + PREFIX + str(epoch_trained + epoch + 1) + ".ema")
             store_log_file.writelines('Epoch' + str(epoch_trained + epoch + 1) + 'model saved!')
             store_log_file.flush()
     if is_writer:

@@ -355,6 +355,19 @@ int wn_rmsprop_flat_guarded(float* p, const float* g, float* square_avg, float* 
     if (n > 0) WN_REQUIRE("wn_rmsprop_flat_guarded", p, g, state);
     return wn_launch_rmsprop_guarded(p, g, square_avg, momentum_buf, n, lr, alpha, eps, momentum, gscale, state, (hipStream_t)stream);
 }
+// ---- EMA shadow of the parameters (wn_guard.hip) ----
+int wn_ema_flat(float* ema, const float* p, int64_t n, float decay, int warmup, int64_t t, const wn_guard_state* state,
+                wn_stream_t stream) {
+    if (n < 0) return wn_set_error_msg(-4, "wn_ema_flat: n is negative");
+    if (n == 0) return 0;
+    WN_REQUIRE("wn_ema_flat", ema, p);
+    if ((uintptr_t)ema % 4 != 0) return wn_set_error_msg(-4, "wn_ema_flat: argument 'ema' needs 4-byte alignment");
+    if ((uintptr_t)p % 4 != 0) return wn_set_error_msg(-4, "wn_ema_flat: argument 'p' needs 4-byte alignment");
+    if ((uintptr_t)state % 8 != 0) return wn_set_error_msg(-4, "wn_ema_flat: argument 'state' needs 8-byte alignment");
+    if (!(decay >= 0.f && decay < 1.f)) return wn_set_error_msg(-4, "wn_ema_flat: argument 'decay' must lie in [0, 1)");
+    if (!state && t < 1) return wn_set_error_msg(-4, "wn_ema_flat: argument 't' counts the updates from 1 when state is NULL");
+    return wn_launch_ema(ema, p, n, decay, warmup ? 1 : 0, t, state, (hipStream_t)stream);
+}
 int wn_coll_available(void) { return wn_coll_loaded(); }
 int wn_comm_unique_id(char* id128) { return wn_coll_unique_id(id128); }
 int wn_comm_create(int nranks, int rank, const char* id128, void** comm) { return wn_coll_create(nranks, rank, id128, comm); }

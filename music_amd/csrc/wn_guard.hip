@@ -179,3 +179,24 @@ int wn_launch_rmsprop_guarded(float* p, const float* g, float* sq, float* buf, l
     WN_CHECK_LAUNCH();
     return 0;
 }
+
+// EMA shadow of the parameters, behind any of the six updates above and in wn_elem.hip (the arithmetic: wn_optim.h).  state NULL:
+// T = t, the caller's count of updates.  Else the decision of the wn_grad_guard before it on the stream: a skipped step leaves the
+// shadow bit for bit, a taken one is update number n_taken + t.  Element-wise on 4-byte accesses: ema and p need no common alignment.
+__global__ void ema_k(float* __restrict__ ema, const float* __restrict__ p, long n, float decay, int warmup, long t,
+                      const wn_guard_state* __restrict__ state) {
+    long T = t;
+    if (state) {
+        if (state->skip) return;
+        T = (long)state->n_taken + t;
+    }
+    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long stride = (long)gridDim.x * blockDim.x;
+    wn_ema_body(ema, p, i, stride, n, wn_ema_weight(decay, warmup, T));
+}
+int wn_launch_ema(float* ema, const float* p, long n, float decay, int warmup, long t, const wn_guard_state* state, hipStream_t st) {
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(ema_k, dim3(guard_update_grid(n)), dim3(256), 0, st, ema, p, n, decay, warmup, t, state);
+    WN_CHECK_LAUNCH();
+    return 0;
+}

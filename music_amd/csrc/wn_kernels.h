@@ -222,6 +222,8 @@ int wn_launch_sgd_guarded(float* p, const float* g, float* buf, long n, float lr
                           const wn_guard_state* state, hipStream_t st);
 int wn_launch_rmsprop_guarded(float* p, const float* g, float* sq, float* buf, long n, float lr, float alpha, float eps, float momentum,
                               float gscale, const wn_guard_state* state, hipStream_t st);
+// EMA shadow of the parameters (state NULL: unguarded, T = t; else T = state->n_taken + t and a skipped step writes nothing)
+int wn_launch_ema(float* ema, const float* p, long n, float decay, int warmup, long t, const wn_guard_state* state, hipStream_t st);
 int wn_launch_gather_grads(const float* packed, const int32_t* idx, float* flat_grad, int n, hipStream_t st);
 int wn_launch_gather_grads2(const float* packed, const int32_t* idx, const int32_t* idx2, float* flat_grad, int n, hipStream_t st);
 int wn_launch_onehot(const int32_t* idx, float* out, int batch, int q, int t, int scrambled, hipStream_t st);

@@ -1,7 +1,8 @@
 // The ONE copy of the flat optimizers' arithmetic, shared by the plain kernels (wn_elem.hip: adam_k, sgd_k, rmsprop_k) and the
 // guarded ones (wn_guard.hip).  GUARDED only adds the clip coefficient to the gradient's scale; with GUARDED false the bodies are
 // the plain kernels' loops as they always were (coef is not read).  i / stride: the calling kernel's first element and grid stride
-// (taken in the kernel itself, where the compiler knows the workgroup size is uniform).
+// (taken in the kernel itself, where the compiler knows the workgroup size is uniform).  Below the optimizers: the exponential moving
+// average of the parameters (wn_ema_flat, wn_guard.hip) that follows any of them.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -56,5 +57,24 @@ __device__ __forceinline__ void wn_rmsprop_body(float* __restrict__ p, const flo
         } else {
             p[i] += -lr * (gi / avg);
         }
+    }
+}
+
+// EMA shadow weights: torch.optim.swa_utils.get_ema_avg_fn's lerp rule, ema += (1 - d_eff) * (p - ema), with TensorFlow's
+// num_updates warm-up d_eff = min(decay, (1 + T) / (10 + T)).  The weight is formed in double from the float decay and rounded
+// once (T below 1 counts as 1: an offset that went wrong must not divide by zero).
+__device__ __forceinline__ float wn_ema_weight(float decay, int warmup, long T) {
+    double d = (double)decay;
+    if (warmup) {
+        const double tt = (double)(T < 1 ? 1 : T);
+        const double wu = (1.0 + tt) / (10.0 + tt);
+        d = wu < d ? wu : d;
+    }
+    return 1.0f - (float)d;
+}
+__device__ __forceinline__ void wn_ema_body(float* __restrict__ ema, const float* __restrict__ p, long i, long stride, long n, float w) {
+    for (; i < n; i += stride) {
+        const float e = ema[i];
+        ema[i] = e + w * (p[i] - e);
     }
 }

@@ -336,12 +336,23 @@ class EngineBase:
         return ws["loss_part"].sum()
 
     # ------------------------------------------------------------------ optimizer
-    def adam_init(self, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, skip_nonfinite=False):
+    def adam_init(self, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, skip_nonfinite=False, ema_decay=None,
+                  ema_warmup=False):
         """max_grad_norm / skip_nonfinite: the guarded step (music_amd/guard.py) - the gradient is clipped to that global L2 norm and
-        a non-finite one is skipped, both decided on the device; unset, adam_step is the one wn_adam_flat launch."""
+        a non-finite one is skipped, both decided on the device; unset, adam_step is the one wn_adam_flat launch.  ema_decay /
+        ema_warmup: the step ends with the wn_ema_flat launch on a shadow of the flat buffer taken here (music_amd/ema.py, `ema`)."""
+        from . import ema
         self.adam_state = dict(m=torch.zeros_like(self.flat), v=torch.zeros_like(self.flat), t=0,
                                lr=lr, b1=betas[0], b2=betas[1], eps=eps)
         guard.adam_init_guard(self.adam_state, self.flat.device, max_grad_norm, skip_nonfinite)
+        shadow = self.adam_state["ema"] = ema.make(ema_decay, ema_warmup)
+        if shadow is not None:
+            shadow.bind_engine(self)
+
+    @property
+    def ema(self):
+        """The ShadowParams of the fused step (adam_init(ema_decay=...)), else None."""
+        return None if self.adam_state is None else self.adam_state.get("ema")
 
     def guard_report(self):
         """The guard's state block read back (the only sync of the guarded step): norm / coef / taken / clipped / skipped /
@@ -351,8 +362,13 @@ class EngineBase:
     def adam_step(self, gscale=1.0):
         """torch.optim.Adam semantics on the flat parameter buffer."""
         s = self.adam_state
+        shadow = s.get("ema")
+        if shadow is not None:
+            shadow.check_step()
         if s.get("guard") is not None:
             return guard.adam_step_guarded(self, gscale)
         s["t"] += 1
         call("wn_adam_flat", ptr(self.flat), ptr(self.flat_grad), ptr(s["m"]), ptr(s["v"]), self.spec.total,
              s["lr"], s["b1"], s["b2"], s["eps"], 1.0 - s["b1"] ** s["t"], 1.0 - s["b2"] ** s["t"], gscale, _lib.stream())
+        if shadow is not None:
+            shadow.update(self)

@@ -78,14 +78,17 @@ def adam_init_guard(state, device, max_grad_norm, skip_nonfinite):
 
 
 def adam_step_guarded(eng, gscale):
-    """wn_grad_guard + wn_adam_flat_guarded on the engine's flat buffers.  adam_state["t"] counts the steps ISSUED until
-    guard_report() replaces it by the device's count of steps taken."""
+    """wn_grad_guard + wn_adam_flat_guarded on the engine's flat buffers (+ wn_ema_flat reading the same decision, with
+    adam_init(ema_decay=...)).  adam_state["t"] counts the steps ISSUED until guard_report() replaces it by the device's count of
+    steps taken."""
     s = eng.adam_state
     gd = s["guard"]
     s["t"] += 1
     gd.run(_lib.ptr(eng.flat_grad), eng.spec.total, gscale)
     _lib.call("wn_adam_flat_guarded", _lib.ptr(eng.flat), _lib.ptr(eng.flat_grad), _lib.ptr(s["m"]), _lib.ptr(s["v"]), eng.spec.total,
               s["lr"], s["b1"], s["b2"], s["eps"], gscale, gd.state_ptr(), _lib.stream())
+    if s.get("ema") is not None:
+        s["ema"].update(eng, gd)
 
 
 def engine_guard_report(eng):
@@ -113,9 +116,26 @@ class GuardedOptimizer:
     device's count of steps TAKEN wherever torch reads them (state_dict(), a step on torch's own path), and the host form of the
     rule for such a step."""
 
+    ema = None                   # the ShadowParams of music_amd/ema.py when ema_decay is set (_ema_setup), else None
+
     def _guard_setup(self, max_grad_norm, skip_nonfinite):
         self._guard_opts = (max_grad_norm, bool(skip_nonfinite)) if enabled(max_grad_norm, skip_nonfinite) else None
         self._guard = None
+
+    def _ema_setup(self, named_params, ema_decay, ema_warmup):
+        """ema_decay set: `ema`, the shadow of the parameters, taken here; every step ends with its update."""
+        from . import ema
+        self.ema = ema.make(ema_decay, ema_warmup)
+        if self.ema is not None:
+            self.ema.bind(named_params)
+
+    def _guard_seed_device(self, running):
+        """Start the device's count from torch's step counters; the shadow's update number continues (its offset absorbs the
+        difference; `running`: the count so far is read back from the device first)."""
+        t, base = self._guard_seed()
+        if self.ema is not None:
+            self.ema.continue_from(self.ema.updates(self._guard if running else None), t)
+        self._guard.seed_taken(t, base)
 
     def _guard_seed(self):
         """(count of taken steps to start the device from, how many of them are not this optimizer's): torch's step counters."""
@@ -125,12 +145,12 @@ class GuardedOptimizer:
     def _guard_get(self, device):
         if self._guard is None:
             self._guard = GradGuard(device, self._guard_opts[0], self._guard_opts[1], self.param_groups[0].get("betas", (0.0, 0.0)))
-            self._guard.seed_taken(*self._guard_seed())
+            self._guard_seed_device(False)
         return self._guard
 
     def _guard_reseed(self):
         if self._guard is not None:
-            self._guard.seed_taken(*self._guard_seed())
+            self._guard_seed_device(True)
 
     def _guard_sync_steps(self):
         if self._guard is None:
@@ -152,18 +172,27 @@ class GuardedOptimizer:
         return None if self._guard is None else self._guard.report()
 
     def _torch_step(self, closure=None):
-        """torch's own step; guarded: the same rule on the host first (clip_grad_norm_, and a non-finite gradient is not applied)."""
+        """torch's own step; guarded: the same rule on the host first (clip_grad_norm_, and a non-finite gradient is not applied).
+        With `ema`, the shadow's update in plain torch follows a step that was taken."""
+        params = [p for grp in self.param_groups for p in grp["params"]]
+        if self.ema is not None:
+            self.ema.check_step()
         if self._guard_opts is None:
-            return super().step(closure)
+            loss = super().step(closure)
+            if self.ema is not None:
+                self.ema.host_update(params)
+            return loss
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        params = [p for grp in self.param_groups for p in grp["params"]]
         gd = self._guard_get(params[0].device)
         self._guard_sync_steps()
-        if gd.host_rule(params):
+        taken = gd.host_rule(params)
+        if taken:
             super().step()
+        if self.ema is not None:
+            self.ema.host_update(params, taken, gd)
         return loss
 
 

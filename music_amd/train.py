@@ -24,6 +24,11 @@ Differences, all additive:
     Scaling under data parallelism: a ragged shard's ``dp_scale`` differs per rank and has to multiply the local buffer before
     the sum; the 1 / world of the mean is folded into the guard's ``gscale`` on the fused step, while the autograd path keeps
     it in ``allreduce_gradients`` (the gradients are the optimizer's ``.grad`` tensors there, which torch's own step reads too).
+    ``"ema_decay"`` (float) and ``"ema_warmup"`` (bool): an exponential moving average of the parameters is kept on the device
+    (music_amd/ema.py: one launch behind every optimizer step; under the guard a skipped step leaves it alone and the warm-up
+    counts the steps taken) and written as ``wavenet{N}.ema`` next to every ``wavenet{N}.model``, in the same format - so
+    ``load_model(net, dir, "wavenet{N}.ema")`` and ``fast_generate.generate(dir, "wavenet{N}.ema", ...)`` sample from it.  A
+    resumed run reads it back (with ``"save_optimizer_state"`` also the count of updates, ``"ema_updates"`` in the ``.opt`` blob).
 """
 from collections import OrderedDict
 from functools import cmp_to_key
@@ -37,11 +42,13 @@ import torch.optim as optim
 
 try:
     from . import dist as wdist
+    from . import ema
     from . import guard
     from .faster_audio_data import audio_data_loader
     from .model import wavenet
 except ImportError:                                  # run as a script / bare modules from the CWD
     from music_amd import dist as wdist
+    from music_amd import ema
     from music_amd import guard
     from music_amd.faster_audio_data import audio_data_loader
     from music_amd.model import wavenet
@@ -69,10 +76,11 @@ class FlatAdam(guard.GuardedOptimizer, optim.Adam):
     does not cover (parameters not on the flat buffer yet, gradients that are not one flat tensor, weight decay /
     amsgrad / maximize / closures, several parameter groups) falls through to ``torch.optim.Adam.step`` on the same state."""
 
-    def __init__(self, model, lr, max_grad_norm=None, skip_nonfinite=False):
+    def __init__(self, model, lr, max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=False):
         super().__init__(model.parameters(), lr=lr)
         self._model = model
         self._guard_setup(max_grad_norm, skip_nonfinite)
+        self._ema_setup(model.named_parameters(), ema_decay, ema_warmup)
         self._flat = None            # (engine, m, v, steps): flat moments of that engine's flat parameter buffer
 
     def _fast_state(self):
@@ -116,6 +124,8 @@ class FlatAdam(guard.GuardedOptimizer, optim.Adam):
 
     @torch.no_grad()
     def step(self, closure=None):
+        if self.ema is not None:
+            self.ema.check_step()
         fast = self._fast_state() if closure is None else None
         if fast is not None:
             eng, m, v, steps = fast
@@ -134,12 +144,16 @@ class FlatAdam(guard.GuardedOptimizer, optim.Adam):
                     gd.run(gbase, eng.spec.total)
                     _lib.call("wn_adam_flat_guarded", eng.flat.data_ptr(), gbase, m.data_ptr(), v.data_ptr(), eng.spec.total,
                               float(grp["lr"]), grp["betas"][0], grp["betas"][1], grp["eps"], 1.0, gd.state_ptr(), _lib.stream())
+                    if self.ema is not None:
+                        self.ema.update(eng, gd)
                     return None
                 torch._foreach_add_(steps, 1.0)
                 t = float(steps[0])
                 b1, b2 = grp["betas"]
                 _lib.call("wn_adam_flat", eng.flat.data_ptr(), gbase, m.data_ptr(), v.data_ptr(), eng.spec.total,
                           float(grp["lr"]), b1, b2, grp["eps"], 1.0 - b1 ** t, 1.0 - b2 ** t, 1.0, _lib.stream())
+                if self.ema is not None:
+                    self.ema.update(eng)
                 return None
         return self._torch_step(closure)
 
@@ -201,10 +215,11 @@ class FlatSGD(guard.GuardedOptimizer, optim.SGD):
     ``state_dict``; anything the kernel does not cover (dampening, Nesterov, weight decay, maximize, closures, parameters or
     gradients off the flat buffers, parameters with and without a momentum buffer mixed) falls through to torch's own step."""
 
-    def __init__(self, model, lr, momentum, max_grad_norm=None, skip_nonfinite=False):
+    def __init__(self, model, lr, momentum, max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=False):
         super().__init__(model.parameters(), lr=lr, momentum=momentum)
         self._model, self._cache = model, {}
         self._guard_setup(max_grad_norm, skip_nonfinite)
+        self._ema_setup(model.named_parameters(), ema_decay, ema_warmup)
 
     def _guard_seed(self):
         # torch's SGD keeps no step counter: existing momentum buffers mean "not the first step" (one step the guard did not see)
@@ -218,6 +233,8 @@ class FlatSGD(guard.GuardedOptimizer, optim.SGD):
 
     @torch.no_grad()
     def step(self, closure=None):
+        if self.ema is not None:
+            self.ema.check_step()
         lay = None
         if closure is None:
             lay = _flat_layout(self, self._model, lambda g: (g.get("dampening", 0) == 0 and not g.get("nesterov") and g.get("weight_decay", 0) == 0
@@ -239,8 +256,12 @@ class FlatSGD(guard.GuardedOptimizer, optim.SGD):
                 gd.run(gbase, eng.spec.total)
                 _lib.call("wn_sgd_flat_guarded", eng.flat.data_ptr(), gbase, buf, eng.spec.total, float(grp["lr"]), mom, 1.0, gd.state_ptr(),
                           _lib.stream())
+                if self.ema is not None:
+                    self.ema.update(eng, gd)
                 return None
             _lib.call("wn_sgd_flat", eng.flat.data_ptr(), gbase, buf, eng.spec.total, float(grp["lr"]), mom, 1.0, first, _lib.stream())
+            if self.ema is not None:
+                self.ema.update(eng)
             return None
         return self._torch_step(closure)
 
@@ -250,10 +271,11 @@ class FlatRMSprop(guard.GuardedOptimizer, optim.RMSprop):
     ``wn_rmsprop_flat`` launch when it can be (see FlatAdam): torch's own state (``step``, ``square_avg``, ``momentum_buffer``; the
     tensors are views of flat buffers), same ``state_dict``; centered / weight decay / maximize / closures fall through to torch."""
 
-    def __init__(self, model, lr, momentum, max_grad_norm=None, skip_nonfinite=False):
+    def __init__(self, model, lr, momentum, max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=False):
         super().__init__(model.parameters(), lr=lr, momentum=momentum)
         self._model, self._cache = model, {}
         self._guard_setup(max_grad_norm, skip_nonfinite)
+        self._ema_setup(model.named_parameters(), ema_decay, ema_warmup)
 
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
@@ -262,6 +284,8 @@ class FlatRMSprop(guard.GuardedOptimizer, optim.RMSprop):
 
     @torch.no_grad()
     def step(self, closure=None):
+        if self.ema is not None:
+            self.ema.check_step()
         lay = None
         if closure is None:
             lay = _flat_layout(self, self._model, lambda g: (not g.get("centered") and g.get("weight_decay", 0) == 0 and not g.get("maximize")
@@ -290,19 +314,26 @@ class FlatRMSprop(guard.GuardedOptimizer, optim.RMSprop):
                 gd.run(gbase, eng.spec.total)
                 _lib.call("wn_rmsprop_flat_guarded", eng.flat.data_ptr(), gbase, sq.data_ptr(), buf, eng.spec.total, float(grp["lr"]),
                           float(grp["alpha"]), float(grp["eps"]), mom, 1.0, gd.state_ptr(), _lib.stream())
+                if self.ema is not None:
+                    self.ema.update(eng, gd)
                 return None
             torch._foreach_add_(steps, 1.0)
             _lib.call("wn_rmsprop_flat", eng.flat.data_ptr(), gbase, sq.data_ptr(), buf, eng.spec.total, float(grp["lr"]), float(grp["alpha"]),
                       float(grp["eps"]), mom, 1.0, _lib.stream())
+            if self.ema is not None:
+                self.ema.update(eng)
             return None
         return self._torch_step(closure)
 
 
-def get_optimizer(model, optimizer_type, learning_rate, momentum, max_grad_norm=None, skip_nonfinite=False):
+def get_optimizer(model, optimizer_type, learning_rate, momentum, max_grad_norm=None, skip_nonfinite=False, ema_decay=None,
+                  ema_warmup=False):
     """wavenet/train.py:28-42 — 'sgd' / 'rmsprop' (with momentum) / 'adam'; anything else -> None.  Each is torch's own optimizer class
     (same hyper-parameters, same state_dict) whose step() is one launch on the module's flat buffers when it can be.  max_grad_norm / skip_nonfinite: the guarded
-    step (music_amd/guard.py) - that launch becomes wn_grad_guard + the guarded update."""
-    kw = dict(max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+    step (music_amd/guard.py) - that launch becomes wn_grad_guard + the guarded update.  ema_decay / ema_warmup: `opt.ema`, the EMA
+    shadow of the parameters (music_amd/ema.py; None when unset) - every step ends with its one wn_ema_flat launch; the shadow is
+    not part of state_dict()."""
+    kw = dict(max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, ema_decay=ema_decay, ema_warmup=ema_warmup)
     if optimizer_type == 'sgd':
         return FlatSGD(model, lr=learning_rate, momentum=momentum, **kw)
     if optimizer_type == 'rmsprop':
@@ -344,8 +375,9 @@ def _rotate_checkpoints(restore_dir, max_check_points):
             return int(p.split('/')[-1].split('.')[0][7:])
         stored = sorted(stored, key=cmp_to_key(lambda a, b: number(a) - number(b)))
         os.remove(stored[0])
-        if os.path.exists(stored[0][:-len(".model")] + ".opt"):       # its optimizer state, if one was written
-            os.remove(stored[0][:-len(".model")] + ".opt")
+        for suffix in (".opt", ".ema"):                               # its optimizer state and EMA shadow, if they were written
+            if os.path.exists(stored[0][:-len(".model")] + suffix):
+                os.remove(stored[0][:-len(".model")] + suffix)
 
 
 def _optimizer_state(optimizer, engine):
@@ -375,6 +407,13 @@ def _restore_optimizer_state(path, optimizer, engine_factory):
     if blob.get("kind") == "torch" and optimizer is not None:
         optimizer.load_state_dict(blob["state"])
     return None
+
+
+def _saved_ema_updates(path):
+    """"ema_updates" of wavenet{N}.opt: the count of EMA updates at that checkpoint, or None (no file, or one without a shadow)."""
+    if not os.path.exists(path):
+        return None
+    return torch.load(path, map_location="cpu").get("ema_updates")
 
 
 def _resume_counter(log_dir):
@@ -424,12 +463,14 @@ def train():
 
     max_gn, skip_nf = guard.guard_options(train_params)
     guarded = guard.enabled(max_gn, skip_nf)
+    ema_decay, ema_warmup = ema.ema_options(train_params)
+    fused = bool(train_params.get("fused_step")) and train_params["optimizer"] == 'adam' and cuda_available
     optimizer = get_optimizer(net, train_params["optimizer"], train_params["learning_rate"],
-                              train_params["momentum"], max_grad_norm=max_gn, skip_nonfinite=skip_nf)
+                              train_params["momentum"], max_grad_norm=max_gn, skip_nonfinite=skip_nf,
+                              ema_decay=None if fused else ema_decay, ema_warmup=ema_warmup)     # (fused: the engine keeps the shadow)
     loss_func = nn.CrossEntropyLoss()
     if cuda_available:
         loss_func = loss_func.cuda()
-    fused = bool(train_params.get("fused_step")) and train_params["optimizer"] == 'adam' and cuda_available
     is_writer = rank == 0
     loss_log_file = store_log_file = None
     if is_writer:
@@ -445,15 +486,27 @@ def train():
     total_loss = torch.zeros((), dtype=torch.float64, device=device)     # summed without host syncs
     engine = None
     keep_opt = bool(train_params.get("save_optimizer_state"))
-    if keep_opt and restored_from is not None:
 
-        def _fused_engine():
-            if not fused:
-                return None
-            e = net._engine_for(device)
-            e.adam_init(lr=train_params["learning_rate"], max_grad_norm=max_gn, skip_nonfinite=skip_nf)
-            return e
+    def _fused_engine():
+        if not fused:
+            return None
+        e = net._engine_for(device)
+        e.adam_init(lr=train_params["learning_rate"], max_grad_norm=max_gn, skip_nonfinite=skip_nf, ema_decay=ema_decay,
+                    ema_warmup=ema_warmup)
+        return e
+
+    def _shadow():
+        """(the EMA shadow of this run or None, the GradGuard its updates follow or None)"""
+        if fused:
+            return (None, None) if engine is None else (engine.ema, engine.adam_state.get("guard"))
+        return (None, None) if optimizer is None else (optimizer.ema, optimizer._guard)
+    if keep_opt and restored_from is not None:
         engine = _restore_optimizer_state(restored_from[:-len(".model")] + ".opt", optimizer, _fused_engine)
+    if ema_decay is not None and restored_from is not None:
+        if fused and engine is None:
+            engine = _fused_engine()
+        ema.restore_shadow(_shadow()[0], restored_from[:-len(".model")] + ".ema",
+                           _saved_ema_updates(restored_from[:-len(".model")] + ".opt") if keep_opt else None, _shadow()[1])
     guard_log = None
     if guarded and is_writer:
         guard_log = guard.GuardLog(
@@ -474,8 +527,7 @@ def train():
             loss = torch.zeros((), device=device)
             if fused:
                 if engine is None:
-                    engine = net._engine_for(device)
-                    engine.adam_init(lr=train_params["learning_rate"], max_grad_norm=max_gn, skip_nonfinite=skip_nf)
+                    engine = _fused_engine()
                 if piece is not None:
                     loss = engine.loss_and_grad(piece.contiguous(), target)
                 else:
@@ -513,9 +565,14 @@ def train():
         if (epoch + 1) % train_params["check_point_every"] == 0 and is_writer:
             _rotate_checkpoints(train_params["restore_dir"], train_params["max_check_points"])
             save_model(net, epoch_trained + epoch + 1, train_params["restore_dir"])
+            shadow, shadow_guard = _shadow()
+            if shadow is not None:
+                ema.save_shadow(shadow, train_params["restore_dir"] + "wavenet" + str(epoch_trained + epoch + 1) + ".ema")
             if keep_opt:
-                torch.save(_optimizer_state(optimizer, engine),
-                           train_params["restore_dir"] + "wavenet" + str(epoch_trained + epoch + 1) + ".opt")
+                blob = _optimizer_state(optimizer, engine)
+                if shadow is not None:
+                    blob["ema_updates"] = shadow.updates(shadow_guard)
+                torch.save(blob, train_params["restore_dir"] + "wavenet" + str(epoch_trained + epoch + 1) + ".opt")
             store_log_file.writelines("Epoch " + str(epoch_trained + epoch + 1) + ", model saved!\n")
             store_log_file.flush()
     if is_writer:

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of single kernels of the hot path at BASELINE config-2 shapes (GPU only).
 
-    python tools/kbench.py [fwd|bwd|all] [--reps N] [--precision f16x3,bf16x3]
+    python tools/kbench.py [fwd|bwd|epi|dx|skip|decode|ae|guard|ema|all] [--reps N] [--precision f16x3,bf16x3]
 
 Prints per-phase / per-layer kernel times measured with HIP events on the launch stream.
 """
@@ -201,6 +201,52 @@ def main():
             res["fused_step_%s_ms" % label] = round(float(np.median(vals)), 4)
             res["fused_step_%s_ms_all" % label] = [round(t, 4) for t in vals]
         res["guard_report"] = eng.guard_report()
+    if args.what == "ema":
+        # the EMA shadow update on config 2's flat buffer: wn_ema_flat plain and behind a guard's state block, by HIP events over
+        # `reps` back-to-back calls; then the whole fused step with / without EMA, alternated; written to profiles/ema_kbench.json
+        import time
+        from music_amd.guard import GradGuard
+        n = eng.spec.total
+        eng.loss_and_grad(x, target)
+        gd = GradGuard(eng.flat.device, 1.0, True, (0.9, 0.999))
+        gd.run(ptr(eng.flat_grad), n, 1.0)
+        shadow = eng.flat.clone()
+
+        def timed(fn):
+            fn()
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            ev[0].record()
+            for _ in range(args.reps * 20):
+                fn()
+            ev[1].record()
+            torch.cuda.synchronize()
+            return round(ev[0].elapsed_time(ev[1]) / (args.reps * 20) * 1e3, 2)
+        res["ema_floats"] = n
+        res["ema_plain_us"] = timed(lambda: call("wn_ema_flat", ptr(shadow), ptr(eng.flat), n, 0.9999, 1, 1000, None, st))
+        res["ema_guarded_us"] = timed(lambda: call("wn_ema_flat", ptr(shadow), ptr(eng.flat), n, 0.9999, 1, 0, gd.state_ptr(), st))
+        steps = {"without_ema": [], "with_ema": []}
+        for rnd in range(6):                               # alternated, as the guard leg does
+            for label in ("without_ema", "with_ema"):
+                eng.adam_init(lr=1e-4, ema_decay=0.9999 if label == "with_ema" else None, ema_warmup=True)
+                for _ in range(3):
+                    eng.loss_and_grad(x, target)
+                    eng.adam_step()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(args.reps * 4):
+                    eng.loss_and_grad(x, target)
+                    eng.adam_step()
+                torch.cuda.synchronize()
+                steps[label].append((time.perf_counter() - t0) / (args.reps * 4) * 1e3)
+        for label, vals in steps.items():
+            res["fused_step_%s_ms" % label] = round(float(np.median(vals)), 4)
+            res["fused_step_%s_ms_all" % label] = [round(t, 4) for t in vals]
+        res["fused_step_ema_delta_ms"] = round(res["fused_step_with_ema_ms"] - res["fused_step_without_ema_ms"], 4)
+        res["fused_step_spread_ms"] = {k: round(max(v) - min(v), 4) for k, v in steps.items()}
+        os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+        with open(os.path.join(ROOT, "profiles", "ema_kbench.json"), "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
     if args.what in ("ae", "all"):
         # BASELINE config 4: autoencoder, 30+30 blocks, 64 ch, skip 256, bottleneck 64, pool 512, batch 8 x 16000:
         # forward + CE + backward (fresh conditioning projections every forward, as in the reference)
