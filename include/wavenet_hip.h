@@ -388,6 +388,28 @@ int wn_rmsprop_flat_guarded(float* p, const float* g, float* square_avg, float* 
  * misaligned pointer (state: 8 bytes); decay outside [0, 1) or NaN; t < 1 with state == NULL. */
 int wn_ema_flat(float* ema, const float* p, int64_t n, float decay, int warmup, int64_t t, const wn_guard_state* state,
                 wn_stream_t stream);
+/* ---- The PER-TIMESTEP softmax and the true negative log-likelihood: the distribution the decoder samples from (the softmax over the
+ * q channels of ONE output column), as an objective.  Nothing of the reference's loss is reproduced here: no second log-softmax
+ * (SURVEY Q1), no softmax over time.  x holds logits as [batch][q][x_pitch] with clip stride x_bstride (floats): the
+ * channel axis has stride x_pitch, time is contiguous - the layout the epilogue leaves and the backward consumes.  For clip b and
+ * column c < w, over the q values x[b * x_bstride + k * x_pitch + c], with y = target[b * w + c]:
+ *   m = max_k x_k;  S = sum_k exp(x_k - m);  p_k = exp(x_k - m) / S;  nll = log S + m - x_y
+ *   probs[(b * w + c) * q + k] = p_k                    row-major per time step, the shape of the module's output
+ *   dx[b * dx_bstride + k * dx_pitch + c] = (p_k - [k == y]) * inv_n
+ *   row_nll[b * w + c] = nll;   row_hit[b * w + c] = (the FIRST index of max_k x_k == y)
+ *   loss_part: WN_CE_NUM_PARTIALS floats, ALL rewritten at every call; their sum is inv_n * sum of nll over all columns
+ * dx, probs, row_nll and row_hit may each be NULL (not wanted).  A target outside [0, q) turns the loss, that column's dx and its
+ * row_nll into NaN and its row_hit into 0; other columns are untouched (the rule of wn_chunk_softmax256_ce).  Columns c >= w of a
+ * row are never read or written, in x and in dx; any w and any 4-byte aligned bases are valid.  One launch on `stream`: no
+ * allocation, no synchronisation, no float atomics (the result is a pure function of the inputs: the same bits at every launch),
+ * legal under stream capture.  q == 256 has a kernel of its own; 1 <= q <= 1024.
+ * batch == 0 or w == 0: returns 0 and writes nothing, except that wn_step_nll zeroes loss_part when it is given (NULLs allowed).
+ * -4, the argument named in wn_last_error: batch < 0 or w < 0; q < 1 or q > 1024; x_pitch < w; x_bstride < q * x_pitch; with dx
+ * given, dx_pitch < w or dx_bstride < q * dx_pitch; with work to do, NULL x, target or loss_part (wn_step_softmax: x or probs). */
+int wn_step_softmax(const float* x, int64_t x_bstride, int x_pitch, float* probs, int w, int q, int batch, wn_stream_t stream);
+int wn_step_nll(const float* x, int64_t x_bstride, int x_pitch, const int64_t* target, float* dx, int64_t dx_bstride, int dx_pitch,
+                float* probs, float* row_nll, int32_t* row_hit, float* loss_part, int w, int q, int batch, float inv_n,
+                wn_stream_t stream);
 /* The reference's nn.DataParallel gradient reduction (wavenet/train.py:116-122) as ONE in-place sum over the ranks of the flat
  * fp32 gradient buffer: ncclAllReduce(buf, buf, n, ncclFloat32, ncclSum, comm, stream) on the caller's RCCL communicator
  * (`comm` = an ncclComm_t).  The 1 / world_size of the mean goes into wn_adam_flat's gscale.  Returns -5 when RCCL is neither

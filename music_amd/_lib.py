@@ -86,6 +86,8 @@ SIGNATURES = {
     "wn_sgd_flat_guarded": [_p, _p, _p, _l, _f, _f, _f, _p, _p],
     "wn_rmsprop_flat_guarded": [_p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _p, _p],
     "wn_ema_flat": [_p, _p, _l, _f, _i, _l, _p, _p],
+    "wn_step_softmax": [_p, _l, _i, _p, _i, _i, _i, _p],
+    "wn_step_nll": [_p, _l, _i, _p, _p, _l, _i, _p, _p, _p, _p, _i, _i, _i, _f, _p],
     "wn_coll_available": [],
     "wn_comm_unique_id": [_p],
     "wn_comm_create": [_i, _i, _p, _p],

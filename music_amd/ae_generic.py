@@ -274,5 +274,6 @@ class GenericAutoencoderEngine(GeneralPlan):
         ps.reduce_grads()
 
     # ------------------------------------------------------------------ fused training step (wavenet_autoencoder/train.py:146-160)
-    def loss_and_grad(self, x, target, cond):
-        return self._throttled(lambda: self._fused_tail(self.forward(x, cond, want_probs=False)[2], target))
+    def loss_and_grad(self, x, target, cond, objective=None):
+        """objective: None = self.objective (EngineBase)"""
+        return self._throttled(lambda: self._fused_tail(self.forward(x, cond, want_probs=False)[2], target, objective=objective))

@@ -34,6 +34,7 @@ try:
     from . import dist as wdist
     from . import ema
     from . import guard
+    from . import objective as wobjective
     from .faster_audio_data import audio_data_loader
     from .model1 import wavenet_autoencoder
     from .train import get_params, load_model
@@ -41,6 +42,7 @@ except ImportError:
     from music_amd import dist as wdist
     from music_amd import ema
     from music_amd import guard
+    from music_amd import objective as wobjective
     from music_amd.faster_audio_data import audio_data_loader
     from music_amd.model1 import wavenet_autoencoder
     from music_amd.train import get_params, load_model
@@ -157,6 +159,9 @@ def train():
             restored_from = train_params["restore_dir"] + train_params["restore_model"]
     if cuda_available is False and train_params["device_ids"] is not None:
         raise ValueError("Cuda is not avalable,", " can not train model using multi-gpu.")
+    # optional keys "objective", "valid_audio_path", "validate_every": as in music_amd/train.py (music_amd/objective.py)
+    objective = wobjective.objective_option(train_params)
+    validation = wobjective.Validation.make(train_params, dataset_params) if rank == 0 else None
     if world > 1:
         assert dataset_params["batch_size"] % world == 0
         dataset_params = dict(dataset_params, shard=(rank, world))
@@ -188,6 +193,7 @@ def train():
     engine = None
     if fused:
         engine = net._engine_for(device)
+        engine.objective = objective
         engine.adam_init(lr=train_params["learning_rate"], max_grad_norm=max_gn, skip_nonfinite=skip_nf, ema_decay=ema_decay,
                          ema_warmup=ema_warmup)
     # the EMA shadow (music_amd/ema.py); no optimizer state is kept by this harness, so a resumed run's warm-up counts as finished
@@ -215,7 +221,7 @@ def train():
                 optimizer.zero_grad()
                 loss = torch.zeros((), device=device)
                 if piece is not None:
-                    loss = loss_func(net(piece), target)
+                    loss = wobjective.nll_loss(net, piece, target) if objective == "nll" else loss_func(net(piece), target)
                     loss.backward()
                 wdist.allreduce_gradients(net.parameters(), average=True, scale=dp_scale)
                 return loss
@@ -244,6 +250,8 @@ def train():
                 if guard_log is not None:
                     guard_log.tick(num_trained)
                 total_loss.zero_()
+            if validation is not None:
+                validation.tick(net, num_trained, shadow)
         if (epoch + 1) % train_params["check_point_every"] == 0 and is_writer:
             stored = glob.glob(train_params["restore_dir"] + "*.model")
             _rotate_checkpoints(stored, train_params["max_check_points"])

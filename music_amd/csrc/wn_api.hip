@@ -368,6 +368,40 @@ int wn_ema_flat(float* ema, const float* p, int64_t n, float decay, int warmup, 
     if (!state && t < 1) return wn_set_error_msg(-4, "wn_ema_flat: argument 't' counts the updates from 1 when state is NULL");
     return wn_launch_ema(ema, p, n, decay, warmup ? 1 : 0, t, state, (hipStream_t)stream);
 }
+// ---- per-timestep softmax and negative log-likelihood (wn_nll.hip) ----
+// the refusals both entries share: shapes first (they need no pointer), then the pointers of a call that has work to do
+static int step_checked(const char* fn, const void* x, int64_t x_bstride, int x_pitch, int w, int q, int batch) {
+    char msg[160];
+    const char* bad = nullptr;
+    if (batch < 0) bad = "'batch' must be >= 0";
+    else if (w < 0) bad = "'w' must be >= 0";
+    else if (q < 1 || q > 1024) bad = "'q' must lie in [1, 1024]";
+    else if (x_pitch < w) bad = "'x_pitch' must be >= w";
+    else if (x_bstride < (int64_t)q * x_pitch) bad = "'x_bstride' must be >= q * x_pitch";
+    if (bad) {
+        snprintf(msg, sizeof(msg), "%s: argument %s", fn, bad);
+        return wn_set_error_msg(-4, msg);
+    }
+    if (batch > 0 && w > 0) WN_REQUIRE(fn, x);
+    return 0;
+}
+int wn_step_softmax(const float* x, int64_t x_bstride, int x_pitch, float* probs, int w, int q, int batch, wn_stream_t stream) {
+    if (int rc = step_checked("wn_step_softmax", x, x_bstride, x_pitch, w, q, batch)) return rc;
+    if (batch == 0 || w == 0) return 0;
+    WN_REQUIRE("wn_step_softmax", probs);
+    return wn_launch_step_nll(x, (long)x_bstride, x_pitch, nullptr, nullptr, 0, 0, probs, nullptr, nullptr, nullptr, w, q, batch, 0.f,
+                              (hipStream_t)stream);
+}
+int wn_step_nll(const float* x, int64_t x_bstride, int x_pitch, const int64_t* target, float* dx, int64_t dx_bstride, int dx_pitch,
+                float* probs, float* row_nll, int32_t* row_hit, float* loss_part, int w, int q, int batch, float inv_n,
+                wn_stream_t stream) {
+    if (int rc = step_checked("wn_step_nll", x, x_bstride, x_pitch, w, q, batch)) return rc;
+    if (dx && dx_pitch < w) return wn_set_error_msg(-4, "wn_step_nll: argument 'dx_pitch' must be >= w");
+    if (dx && dx_bstride < (int64_t)q * dx_pitch) return wn_set_error_msg(-4, "wn_step_nll: argument 'dx_bstride' must be >= q * dx_pitch");
+    if (batch > 0 && w > 0) WN_REQUIRE("wn_step_nll", target, loss_part);
+    return wn_launch_step_nll(x, (long)x_bstride, x_pitch, target, dx, (long)dx_bstride, dx_pitch, probs, row_nll, row_hit, loss_part, w, q,
+                              batch, inv_n, (hipStream_t)stream);
+}
 int wn_coll_available(void) { return wn_coll_loaded(); }
 int wn_comm_unique_id(char* id128) { return wn_coll_unique_id(id128); }
 int wn_comm_create(int nranks, int rank, const char* id128, void** comm) { return wn_coll_create(nranks, rank, id128, comm); }

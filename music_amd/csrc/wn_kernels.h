@@ -243,6 +243,9 @@ int wn_launch_avgpool_bwd(const float* denc, long denc_bstride, int denc_pitch, 
 int wn_launch_avgpool(const float* in, long in_bstride, int in_pitch, int t0, int pool, int n_out, int rows,
                       float* out, long out_bstride, int out_pitch, int batch, hipStream_t st);
 
+// per-timestep softmax + negative log-likelihood over the channel axis of [B][Q][pitch] logits (wn_nll.hip); target NULL: softmax only
+int wn_launch_step_nll(const float* x, long x_bs, int x_pitch, const int64_t* target, float* dx, long dx_bs, int dx_pitch, float* probs,
+                       float* row_nll, int32_t* row_hit, float* loss_part, int w, int q, int batch, float inv_n, hipStream_t st);
 // general path (wn_generic.hip): gate and chunk softmax for any shape
 int wn_launch_gate_fwd(const float* fg, long fg_bstride, int dp, int rows, float* z, long z_bstride, int pitch, int t_lo, int t_hi,
                        int batch, hipStream_t st);

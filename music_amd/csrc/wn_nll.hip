@@ -1,0 +1,155 @@
+// The PER-TIMESTEP softmax and the true negative log-likelihood over the channel axis of the compact [B][Q][W] logits (wn_step_softmax,
+// wn_step_nll in include/wavenet_hip.h): the distribution the decoder samples from, as a training and scoring objective.  The chunk
+// softmax of wn_elem.hip / wn_generic.hip runs over 256 consecutive floats of that buffer, i.e. over time, and its loss
+// applies a second log-softmax to the probabilities; nothing of either is reproduced here.
+//
+// The channel axis has stride `pitch` and time is contiguous, so a workgroup owns a tile of 64 columns of one clip: lane = column
+// (every global access of a wave is 64 consecutive floats of one channel row), the waves split the q rows RPW apiece and keep them in
+// registers, the column max / argmax / target logit and the column sum cross the waves through LDS.  x is read once, dx written once.
+// Any W: a clip's base is only 4-byte aligned, so every access is a scalar dword per lane and the last tile of a clip is masked.
+// No float atomics: block i sums its tiles in a fixed order into loss_part[i]; the same bits come back on every launch.
+#include "wn_common.h"
+#include "wn_kernels.h"
+
+// probabilities go out row-major per time step ([column][q]): a wave turns TR of its rows at a time through a [64][TR + 1] LDS tile
+// of its own and writes segments of TR consecutive floats
+// Q256: q is 256 and the block has 4 waves of 64 rows (120 registers, no scratch: four blocks per CU, so a grid of up to 1024 blocks
+// is resident at once); else q is a run-time value, the block has ceil(q / 64) <= MAXT / 64 waves and rows >= q are masked.
+template <int RPW, int TR, bool Q256, int MAXT>
+__global__ __launch_bounds__(MAXT) void step_nll_k(
+        const float* __restrict__ x, long x_bs, int x_pitch, const int64_t* __restrict__ target, float* __restrict__ dx, long dx_bs,
+        int dx_pitch, float* __restrict__ probs, float* __restrict__ row_nll, int32_t* __restrict__ row_hit,
+        float* __restrict__ loss_part, int w, int q_rt, int tiles_per_clip, long ntiles, float inv_n) {
+    constexpr int MAXW = MAXT / 64;
+    constexpr int TP = TR + 1;
+    __shared__ float s_max[MAXW][64], s_sum[MAXW][64], s_xy[64];
+    __shared__ int s_arg[MAXW][64];
+    __shared__ float s_t[MAXW][64 * TP];
+    const int q = Q256 ? 256 : q_rt;
+    // (the wave index through readfirstlane: row offsets are then wave-uniform, a scalar base + the lane's column per access)
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
+    const int k0 = wave * RPW;
+    const float nan = __builtin_nanf("");
+    float lacc = 0.f;
+    for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int b = (int)(tile / tiles_per_clip);
+        const int c0 = (int)(tile - (long)b * tiles_per_clip) * 64, c = c0 + lane;
+        const bool cv = c < w;                                   // columns >= w are neither read nor written
+        const long col = (long)b * w + c;
+        long y = -1;
+        if (cv && target) y = target[col];
+        const bool bad = (unsigned long)y >= (unsigned long)q;
+        const float* xr = x + b * x_bs + (long)k0 * x_pitch + c0;       // row k0 of this tile, wave-uniform
+        float v[RPW];
+#pragma unroll
+        for (int j = 0; j < RPW; ++j) {
+            const int k = k0 + j;
+            v[j] = (Q256 || k < q) ? (cv ? xr[lane] : 0.f) : -INFINITY;
+            xr += x_pitch;
+        }
+        // this wave's max, its first index, and the target's logit if it is one of these rows
+        float m = v[0], xy = 0.f;
+        int a = 0;
+#pragma unroll
+        for (int j = 1; j < RPW; ++j)
+            if (v[j] > m) { m = v[j]; a = j; }
+        int yj = bad ? -1 : (int)y - k0;                          // the target's row among this wave's, if in [0, RPW)
+#pragma unroll
+        for (int j = 0; j < RPW; ++j)
+            if (j == yj) xy = v[j];
+        s_max[wave][lane] = m;
+        s_arg[wave][lane] = k0 + a;
+        if (yj >= 0 && yj < RPW) s_xy[lane] = xy;
+        // (hides yj's value from the optimiser: it would otherwise keep the RPW compare masks above alive in scalar registers for
+        // the gradient loop below, and spill them)
+        asm volatile("" : "+v"(yj));
+        __syncthreads();
+        float M = s_max[0][lane];
+        int A = s_arg[0][lane];
+        for (int i = 1; i < nw; ++i) {                           // rows ascend with the wave: '>' keeps the first index of a tie
+            const float mi = s_max[i][lane];
+            if (mi > M) { M = mi; A = s_arg[i][lane]; }
+        }
+        xy = s_xy[lane];                                         // (never written for a bad target: replaced by NaN below)
+        float s4[4] = {0.f, 0.f, 0.f, 0.f};                      // four short chains: less rounding than one of RPW terms
+#pragma unroll
+        for (int j = 0; j < RPW; ++j) {
+            v[j] = expf(v[j] - M);
+            s4[j & 3] += v[j];
+        }
+        s_sum[wave][lane] = (s4[0] + s4[1]) + (s4[2] + s4[3]);
+        __syncthreads();
+        float S = 0.f;
+        for (int i = 0; i < nw; ++i) S += s_sum[i][lane];       // the same order in every wave: one S per column
+        const float inv = 1.0f / S;
+        if (wave == 0 && cv && target) {
+            const float nll = bad ? nan : logf(S) + (M - xy);
+            if (row_nll) row_nll[col] = nll;
+            if (row_hit) row_hit[col] = (!bad && A == (int)y) ? 1 : 0;
+            lacc += nll;
+        }
+        if (dx && cv) {
+            float* dr = dx + b * dx_bs + (long)k0 * dx_pitch + c0;
+#pragma unroll
+            for (int j = 0; j < RPW; ++j) {
+                const int k = k0 + j;
+                if (Q256 || k < q) dr[lane] = bad ? nan : (v[j] * inv - (j == yj ? 1.f : 0.f)) * inv_n;
+                dr += dx_pitch;
+            }
+        }
+        if (probs) {                                             // (a kernel argument: every wave takes this branch or none)
+            float* t = s_t[wave];
+            const int tc = lane / TR, tr = lane % TR;
+#pragma unroll
+            for (int p = 0; p < RPW / TR; ++p) {
+#pragma unroll
+                for (int r = 0; r < TR; ++r) t[lane * TP + r] = v[p * TR + r] * inv;
+                __syncthreads();
+                const int k = k0 + p * TR + tr;
+#pragma unroll
+                for (int i = 0; i < TR; ++i) {
+                    const int cc = i * (64 / TR) + tc;
+                    if (c0 + cc < w && (Q256 || k < q)) probs[((long)b * w + c0 + cc) * q + k] = t[cc * TP + tr];
+                }
+                __syncthreads();
+            }
+        }
+    }
+    if (wave == 0 && loss_part) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) lacc += __shfl_xor(lacc, o, 64);
+        if (lane == 0) {
+            loss_part[blockIdx.x] = lacc * inv_n;
+            for (int i = blockIdx.x + gridDim.x; i < WN_CE_PARTIALS; i += gridDim.x) loss_part[i] = 0.f;   // all slots, every call
+        }
+    }
+}
+
+// target NULL: the softmax alone (wn_step_softmax; nothing but probs is written).  The caller has checked the arguments.
+int wn_launch_step_nll(const float* x, long x_bs, int x_pitch, const int64_t* target, float* dx, long dx_bs, int dx_pitch, float* probs,
+                       float* row_nll, int32_t* row_hit, float* loss_part, int w, int q, int batch, float inv_n, hipStream_t st) {
+    if (batch <= 0 || w <= 0) {
+        if (loss_part) {
+            hipError_t e = hipMemsetAsync(loss_part, 0, WN_CE_PARTIALS * sizeof(float), st);
+            if (e != hipSuccess) return wn_set_error(e, __FILE__, __LINE__);
+        }
+        return 0;
+    }
+    const int tiles_per_clip = (w + 63) / 64;
+    const long ntiles = (long)batch * tiles_per_clip;
+    // a bounded grid whose blocks all take the same number of tiles (+-1), one loss partial per block
+    const long rounds = (ntiles + WN_CE_PARTIALS - 1) / WN_CE_PARTIALS;
+    const int grid = (int)((ntiles + rounds - 1) / rounds);
+    const dim3 block(64 * ((q + 63) / 64));
+    if (q == 256)
+        hipLaunchKernelGGL((step_nll_k<64, 8, true, 256>), dim3(grid), block, 0, st, x, x_bs, x_pitch, target, dx, dx_bs, dx_pitch, probs,
+                           row_nll, row_hit, loss_part, w, q, tiles_per_clip, ntiles, inv_n);
+    else if (q <= 512)
+        hipLaunchKernelGGL((step_nll_k<64, 8, false, 512>), dim3(grid), block, 0, st, x, x_bs, x_pitch, target, dx, dx_bs, dx_pitch, probs,
+                           row_nll, row_hit, loss_part, w, q, tiles_per_clip, ntiles, inv_n);
+    else          // (16 waves of 64 rows leave 128 registers a lane: this instantiation alone keeps part of its rows in scratch)
+        hipLaunchKernelGGL((step_nll_k<64, 8, false, 1024>), dim3(grid), block, 0, st, x, x_bs, x_pitch, target, dx, dx_bs, dx_pitch, probs,
+                           row_nll, row_hit, loss_part, w, q, tiles_per_clip, ntiles, inv_n);
+    WN_CHECK_LAUNCH();
+    return 0;
+}

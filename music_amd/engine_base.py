@@ -116,6 +116,9 @@ class _Spec:
         return self.off[name] + np.arange(int(np.prod(shp)), dtype=np.int64).reshape(shp)
 
 
+OBJECTIVES = ("reference", "nll")     # what a fused step minimises: the reference's loss, or the true NLL per sample
+
+
 SlabOp = namedtuple("SlabOp", "so n chunk ns")      # first slab element, elements per slab, wn_wgrad's chunk (or None), slabs
 
 
@@ -167,6 +170,10 @@ class SlabPlan:
 class EngineBase:
     """Host state and the steps every engine runs the same way.  An engine sets `device`, `Q`, `spec`, `flat`, `flat_grad`, calls
     _init_state(), and provides _make_workspace(), _bwd_workspace() and backward_from_dlogits()."""
+
+    # the loss of loss_and_grad(..., objective=None): "reference" = chunk softmax + CrossEntropyLoss on the probabilities, as the
+    # reference trains (SURVEY Q1, Q2); "nll" = the negative log-likelihood under the per-timestep softmax the decoder samples from
+    objective = "reference"
 
     def _init_state(self):
         self._ws = WorkspacePool(self._make_workspace)
@@ -311,6 +318,42 @@ class EngineBase:
         """loss partials and d loss / d logits of the MEAN cross entropy over n rows of 256 (probs None: not wanted)"""
         call("wn_chunk_softmax256_ce", ptr(logits), ptr(target), ptr(probs), ptr(dlogits), ptr(loss_part), n, 1.0 / n, _lib.stream())
 
+    def _resolve_objective(self, objective):
+        objective = self.objective if objective is None else objective
+        if objective not in OBJECTIVES:
+            raise ValueError("music_amd: objective must be one of %s, not %r" % (", ".join(OBJECTIVES), objective))
+        return objective
+
+    def step_nll(self, ws, target, dlogits=None, probs=None, row_nll=None, row_hit=None):
+        """wn_step_nll on the compact logits ws["O"] (pitch W, clip stride Q W): loss partials of the MEAN negative log-likelihood under
+        the per-timestep softmax into ws["loss_part"]; d loss / d logits in the logits' own layout, the (B W, Q) probabilities, the
+        per-column nll and hit flags where a tensor is given"""
+        B, W, Q = ws["B"], ws["W"], self.Q
+        if "loss_part" not in ws:
+            ws["loss_part"] = torch.zeros(_lib.CE_NUM_PARTIALS, dtype=torch.float32, device=self.device)
+        call("wn_step_nll", ptr(ws["O"]), Q * W, W, ptr(target), ptr(dlogits), Q * W, W, ptr(probs), ptr(row_nll), ptr(row_hit),
+             ptr(ws["loss_part"]), W, Q, B, 1.0 / (B * W), _lib.stream())
+        self.mark("step_nll")
+
+    def score_logits(self, ws, target):
+        """(row_nll float32 (B W,), row_hit int32 (B W,)) of the logits a forward left in ws["O"]: nats of every target sample under
+        the per-timestep softmax, and whether the first-index argmax is the target.  Forward only: no gradient is formed."""
+        n = ws["B"] * ws["W"]
+        target = target.reshape(-1)
+        assert target.numel() == n and target.dtype == torch.int64 and target.is_cuda
+        row_nll = torch.empty(n, dtype=torch.float32, device=self.device)
+        row_hit = torch.empty(n, dtype=torch.int32, device=self.device)
+        self.step_nll(ws, target, row_nll=row_nll, row_hit=row_hit)
+        return row_nll, row_hit
+
+    def step_probs(self, ws):
+        """(B W, Q) per-timestep probabilities of the logits in ws["O"] (wn_step_softmax): row b W + w is the distribution the
+        decoder draws sample w of clip b from"""
+        B, W, Q = ws["B"], ws["W"], self.Q
+        probs = torch.empty(B * W, Q, dtype=torch.float32, device=self.device)
+        call("wn_step_softmax", ptr(ws["O"]), Q * W, W, ptr(probs), W, Q, B, _lib.stream())
+        return probs
+
     def _throttled(self, step):
         """step() between the throttle's enter and leave (_lib.StepThrottle)."""
         self._throttle.enter()
@@ -318,9 +361,11 @@ class EngineBase:
         self._throttle.leave()
         return out
 
-    def _fused_tail(self, ws, target, want_probs=False):
+    def _fused_tail(self, ws, target, want_probs=False, objective=None):
         """Everything of a fused step behind the forward that left the logits in ws["O"]: softmax + CrossEntropyLoss on the
-        probabilities in one kernel, the backward, the loss as a 0-d device tensor.  Gradients land in self.flat_grad."""
+        probabilities in one kernel (objective "nll": the per-timestep softmax and its negative log-likelihood, step_nll), the
+        backward, the loss as a 0-d device tensor.  Gradients land in self.flat_grad."""
+        objective = self._resolve_objective(objective)
         bw = self._bwd_workspace(ws)
         n = ws["B"] * ws["W"]
         target = target.reshape(-1)
@@ -331,7 +376,10 @@ class EngineBase:
         if want_probs:
             probs = torch.empty(n, self.Q, dtype=torch.float32, device=self.device)
             ws["probs"] = probs
-        self.softmax_ce(ws["O"], target, probs, bw["dO"], ws["loss_part"], n)
+        if objective == "nll":
+            self.step_nll(ws, target, bw["dO"], probs)
+        else:
+            self.softmax_ce(ws["O"], target, probs, bw["dO"], ws["loss_part"], n)
         self.backward_from_dlogits(ws)
         return ws["loss_part"].sum()
 

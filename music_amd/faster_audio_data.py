@@ -126,10 +126,14 @@ class _Stager:
         return dev
 
 
+ONE_HOT_LAYOUTS = ("scrambled", "canonical")
+
+
 class _Collate:
-    def __init__(self, q, shard=None):
+    def __init__(self, q, shard=None, scrambled=True):
         self.q = q
         self.shard = shard
+        self.scrambled = bool(scrambled)
         self.stager = _Stager()
 
     def __call__(self, items):
@@ -153,19 +157,23 @@ class _Collate:
             codes = torch.stack([it['audio_piece'] for it in items]).to(torch.int32)
             target = torch.stack([it['audio_target'] for it in items])
             target = target.cuda(non_blocking=True) if torch.cuda.is_available() else target
-        batch = {"audio_piece": onehot_device(codes, self.q), "audio_target": target}
+        batch = {"audio_piece": onehot_device(codes, self.q, scrambled=self.scrambled), "audio_target": target}
         if self.shard is not None:
             batch["dp_scale"] = scale
         return batch
 
 
-def audio_data_loader(batch_size, shuffle, num_workers, pin_memory, shard=None, **kwargs):
+def audio_data_loader(batch_size, shuffle, num_workers, pin_memory, shard=None, one_hot="scrambled", **kwargs):
     """faster_audio_data.py:51-59.  Yields {"audio_piece": float32 (B,256,T) on the device,
     "audio_target": int64 (B,win) on the device}.  Shuffling is torch's own RandomSampler, i.e. the
     same permutation stream as the reference under the same seed.  ``shard=(rank, world)`` (set by
     train.py under torchrun) makes this process build only its contiguous chunk of every global
-    batch; all ranks must share the torch seed so they draw the same permutation."""
+    batch; all ranks must share the torch seed so they draw the same permutation.  ``one_hot`` (the optional key "one_hot" of
+    dataset_params.json): "scrambled" is the reference's reshape-not-transpose layout, "canonical" the true one-hot
+    x[b][code[t]][t] = 1 - what a model trained on the true likelihood (music_amd/objective.py) and the decoder see."""
+    if one_hot not in ONE_HOT_LAYOUTS:
+        raise ValueError("one_hot must be one of %s, not %r" % (", ".join(ONE_HOT_LAYOUTS), one_hot))
     audioDataset = audio_dataset(**kwargs)
     print("{} pieces in total".format(len(audioDataset)))
     return DataLoader(audioDataset, batch_size=batch_size, shuffle=shuffle, num_workers=0,
-                      pin_memory=False, collate_fn=_Collate(audioDataset.quantization_channels, shard))
+                      pin_memory=False, collate_fn=_Collate(audioDataset.quantization_channels, shard, scrambled=one_hot == "scrambled"))

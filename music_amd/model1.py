@@ -500,11 +500,12 @@ class _AutoencoderEngine(EngineBase):
         ws["bwd"] = bw
         return bw
 
-    def loss_and_grad(self, x, target, cond):
+    def loss_and_grad(self, x, target, cond, objective=None):
         """Fused training step body (the autoencoder counterpart of engine.loss_and_grad): forward to the logits, ONE
         kernel for chunk softmax + CrossEntropyLoss on the probabilities (wavenet_autoencoder/train.py:146-160) + both
-        backward steps, then the backward.  Returns the loss (0-d device tensor); gradients land in self.flat_grad."""
-        return self._throttled(lambda: self._fused_tail(self.forward(x, cond, want_probs=False)[2], target))
+        backward steps, then the backward.  Returns the loss (0-d device tensor); gradients land in self.flat_grad.
+        objective: None = self.objective (EngineBase)."""
+        return self._throttled(lambda: self._fused_tail(self.forward(x, cond, want_probs=False)[2], target, objective=objective))
 
     def backward_from_dlogits(self, ws):
         self.backward(ws, None)

@@ -1,0 +1,183 @@
+"""The objective of the model the decoder samples from: the negative log-likelihood of every sample under the softmax over the Q
+channels of ITS output column (``wn_step_nll`` / ``wn_step_softmax``, music_amd/csrc/wn_nll.hip).
+
+The reference trains something else on purpose-reproduced quirks: cross entropy applied to probabilities of a softmax
+that runs over time, on a scrambled one-hot.  Nothing of that changes here; this module is the opt-in
+alternative, for ``wavenet`` and ``wavenet_autoencoder`` alike:
+
+``nll_loss(net, x, target)``   mean nats per sample as a 0-d tensor attached to autograd (training)
+``step_probs(net, x)``         (B W, Q) per-timestep probabilities, the distribution the decoder draws from
+``score(net, x, target)``      per-clip nats, bits and accuracy of a checkpoint on held-out audio, no gradient
+
+There is no CPU path: the arithmetic runs through libwavenet_hip.so only.
+"""
+from contextlib import nullcontext
+import math
+
+import numpy as np
+import torch
+
+try:
+    from . import faster_audio_data
+    from .engine_base import OBJECTIVES, WorkspaceHold
+except ImportError:                      # imported as a bare module
+    from music_amd import faster_audio_data
+    from music_amd.engine_base import OBJECTIVES, WorkspaceHold
+
+
+def _dense_input(wave_sample):
+    """float32 contiguous view of the input; a one-hot built from codes keeps its tag (music_amd/model.py)"""
+    x = wave_sample.detach()
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        return x.float().contiguous()
+    tag = getattr(wave_sample, "_wn_codes", None)
+    if tag is not None and wave_sample._version == tag[2]:
+        x._wn_codes = (tag[0], tag[1], x._version, tag[3])
+    return x
+
+
+def _forward_logits(net, wave_sample):
+    """The module's forward up to the pre-softmax logits: (engine, workspace with the logits in ws["O"]).  The autoencoder draws its
+    per-forward conditioning convs from the global RNG, as its own forward does."""
+    if wave_sample.dim() != 3:
+        raise ValueError("music_amd.objective: the input is a (B, Q, T) one-hot, got shape %s" % (tuple(wave_sample.shape),))
+    if wave_sample.shape[2] - net.receptive_field + 1 <= 0:
+        raise ValueError("wave sample not long enough")
+    eng = net._engine_for(wave_sample.device)
+    x = _dense_input(wave_sample)
+    if hasattr(net, "_draw_conditioning"):
+        _, enc, ws = eng.forward(x, net._draw_conditioning(), want_probs=False)
+        net.last_encoding = enc
+    else:
+        eng.pack_weights()
+        ws = eng.forward_logits(x)
+    return eng, ws
+
+
+def _flat_target(target, ws):
+    target = target.reshape(-1)
+    if target.numel() != ws["B"] * ws["W"]:
+        raise ValueError("music_amd.objective: %d targets for %d clips of %d samples" % (target.numel(), ws["B"], ws["W"]))
+    return target.to(device=ws["O"].device, dtype=torch.int64).contiguous()
+
+
+class _NLLFunction(torch.autograd.Function):
+    """forward_logits + wn_step_nll; the kernel leaves d loss / d logits in the backward workspace, so the backward is the engine's
+    backward_from_dlogits scaled by the upstream scalar."""
+
+    @staticmethod
+    def forward(ctx, net, grad_on, wave_sample, target, *params):
+        eng, ws = _forward_logits(net, wave_sample)
+        need = grad_on and any(ctx.needs_input_grad)
+        eng.step_nll(ws, _flat_target(target, ws), eng._bwd_workspace(ws)["dO"] if need else None)
+        ctx.eng, ctx.ws, ctx.gen = eng, ws, ws["gen"]
+        ctx.hold = WorkspaceHold(ws) if need else None          # see music_amd/model.py
+        return ws["loss_part"].sum()
+
+    @staticmethod
+    def backward(ctx, dloss):
+        eng, ws = ctx.eng, ctx.ws
+        if ws.get("gen") != ctx.gen:
+            raise RuntimeError("music_amd.objective: the activations of this forward were overwritten by a later forward of the "
+                               "same module before backward() ran")
+        eng.backward_from_dlogits(ws)
+        if ctx.hold is not None:
+            ctx.hold.release()
+        g = eng.flat_grad * dloss
+        grads = []
+        for name in eng.param_names:
+            o, shp = eng.spec.off[name], eng.spec.shape[name]
+            grads.append(g[o:o + int(np.prod(shp))].view(shp))
+        din = eng.input_grad(ws) * dloss if ctx.needs_input_grad[2] else None
+        return (None, None, din, None) + tuple(grads)
+
+
+def _params(net):
+    """the module's parameters in its engine's order (music_amd/model.py, music_amd/model1.py)"""
+    return [p for _, p in net._named_ref_params()] if hasattr(net, "_named_ref_params") else list(net.parameters())
+
+
+def nll_loss(net, x, target):
+    """Mean negative log-likelihood (nats per sample) of `target` (B, W) or (B W,) int64 under the per-timestep softmax of
+    net's logits for the one-hot x (B, Q, T): a 0-d tensor whose backward() gives the parameter gradients (and the input's, when it
+    requires grad).  A target outside [0, Q) makes the loss NaN."""
+    return _NLLFunction.apply(net, torch.is_grad_enabled(), x, target, *_params(net))
+
+
+def step_probs(net, x):
+    """(B W, Q) probabilities: row b W + w is softmax over the Q logits of output column w of clip b - what the decoder samples
+    from (the module's own forward returns the reference's chunk softmax instead)."""
+    with torch.no_grad():
+        eng, ws = _forward_logits(net, x)
+        return eng.step_probs(ws)
+
+
+def score(net, x_or_codes, target, scrambled=False):
+    """Held-out figures of net on one batch, forward only.  x_or_codes: the one-hot (B, Q, T) float, or the integer codes (B, T) -
+    then the one-hot is laid out canonical, or as the loader scrambles it with `scrambled`.  Returns device tensors of
+    shape (B,), float64: "nll" (mean nats per sample of each clip), "bits" (nll / ln 2) and "accuracy" (share of samples whose
+    first-index argmax is the target); the per-clip means are taken on the device, nothing is read back."""
+    with torch.no_grad():
+        x = x_or_codes
+        if x.dim() == 2:
+            q = getattr(net, "quantization_channels", None) or net.quantization_channel
+            x = faster_audio_data.onehot_device(x, q, scrambled)
+        eng, ws = _forward_logits(net, x)
+        row_nll, row_hit = eng.score_logits(ws, _flat_target(target, ws))
+        B, W = ws["B"], ws["W"]
+        nll = row_nll.view(B, W).double().mean(1)
+        return {"nll": nll, "bits": nll / math.log(2.0), "accuracy": row_hit.view(B, W).double().mean(1)}
+
+
+# ---------------------------------------------------------------- train() / ae_train: the JSON keys
+def objective_option(train_params):
+    """The optional key "objective" of train_params.json: "reference" (default) or "nll"."""
+    objective = train_params.get("objective", "reference")
+    if objective not in OBJECTIVES:
+        raise ValueError('train_params.json: "objective" must be one of %s, not %r' % (", ".join(OBJECTIVES), objective))
+    return objective
+
+
+class Validation:
+    """Held-out scoring during training: every `validate_every` steps, `score` over the loader of "valid_audio_path" - under the
+    EMA shadow's weights when there is one - and one line in valid_log.log.  make() returns None when the keys are unset: nothing
+    is built and nothing is launched then."""
+
+    @classmethod
+    def make(cls, train_params, dataset_params):
+        path, every = train_params.get("valid_audio_path"), int(train_params.get("validate_every") or 0)
+        if not path or every <= 0:
+            return None
+        return cls(path, every, dataset_params, train_params["log_dir"])
+
+    def __init__(self, audio_path, every, dataset_params, log_dir):
+        params = {k: v for k, v in dataset_params.items() if k != "shard"}
+        params.update(audio_path=audio_path, shuffle=False)
+        self.every = every
+        self.loader = faster_audio_data.audio_data_loader(**params)
+        self.log_path = log_dir + "valid_log.log"
+
+    def run(self, net, shadow=None):
+        """(nll, bits per sample, accuracy) over the held-out loader, as Python floats (the one read-back of a validation)"""
+        total, clips = None, 0
+        with (shadow.swapped(net) if shadow is not None else nullcontext()):
+            for batch in self.loader:
+                if batch["audio_piece"] is None:
+                    continue
+                r = score(net, batch["audio_piece"], batch["audio_target"])
+                part = torch.stack([r["nll"].sum(), r["bits"].sum(), r["accuracy"].sum()])
+                total = part if total is None else total + part
+                clips += r["nll"].numel()
+        if total is None:
+            raise ValueError("music_amd.objective: the validation set holds no piece")
+        return tuple((total / clips).tolist())
+
+    def tick(self, net, num_trained, shadow=None):
+        """after training step `num_trained`: validate and log when it is due"""
+        if num_trained % self.every != 0:
+            return None
+        nll, bits, acc = self.run(net, shadow)
+        with open(self.log_path, "a") as f:
+            f.write("Trained over " + str(num_trained) + " pieces,Validation nll is " + str(nll) + ", bits per sample " + str(bits) +
+                    ", accuracy " + str(acc) + "\n")
+        return nll, bits, acc

@@ -44,12 +44,14 @@ try:
     from . import dist as wdist
     from . import ema
     from . import guard
+    from . import objective as wobjective
     from .faster_audio_data import audio_data_loader
     from .model import wavenet
 except ImportError:                                  # run as a script / bare modules from the CWD
     from music_amd import dist as wdist
     from music_amd import ema
     from music_amd import guard
+    from music_amd import objective as wobjective
     from music_amd.faster_audio_data import audio_data_loader
     from music_amd.model import wavenet
 
@@ -448,6 +450,10 @@ def train():
 
     if cuda_available is False and train_params["device_ids"] is not None:
         raise ValueError("Cuda is not avalable,", " can not train model using multi-gpu.")
+    # optional keys: "objective": "nll" trains the negative log-likelihood under the per-timestep softmax instead of the reference's
+    # loss; "valid_audio_path" + "validate_every" (steps) score held-out audio on rank 0 into valid_log.log (music_amd/objective.py)
+    objective = wobjective.objective_option(train_params)
+    validation = wobjective.Validation.make(train_params, dataset_params) if rank == 0 else None
     if world > 1:
         # DataParallel semantics: the JSON batch_size is the GLOBAL batch, split evenly
         assert dataset_params["batch_size"] % world == 0
@@ -491,6 +497,7 @@ def train():
         if not fused:
             return None
         e = net._engine_for(device)
+        e.objective = objective
         e.adam_init(lr=train_params["learning_rate"], max_grad_norm=max_gn, skip_nonfinite=skip_nf, ema_decay=ema_decay,
                     ema_warmup=ema_warmup)
         return e
@@ -540,7 +547,10 @@ def train():
                     engine.adam_step()
             else:
                 optimizer.zero_grad()
-                if piece is not None:
+                if piece is not None and objective == "nll":
+                    loss = wobjective.nll_loss(net, piece, target)
+                    loss.backward()
+                elif piece is not None:
                     logits = net(piece)            # probabilities, named as in the reference (Q1)
                     loss = loss_func(logits, target)
                     loss.backward()
@@ -561,6 +571,8 @@ def train():
                 if guard_log is not None:
                     guard_log.tick(num_trained)
                 total_loss.zero_()
+            if validation is not None:
+                validation.tick(net, num_trained, _shadow()[0])
 
         if (epoch + 1) % train_params["check_point_every"] == 0 and is_writer:
             _rotate_checkpoints(train_params["restore_dir"], train_params["max_check_points"])

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of single kernels of the hot path at BASELINE config-2 shapes (GPU only).
 
-    python tools/kbench.py [fwd|bwd|epi|dx|skip|decode|ae|guard|ema|all] [--reps N] [--precision f16x3,bf16x3]
+    python tools/kbench.py [fwd|bwd|epi|dx|skip|decode|ae|guard|ema|nll|all] [--reps N] [--precision f16x3,bf16x3]
 
 Prints per-phase / per-layer kernel times measured with HIP events on the launch stream.
 """
@@ -245,6 +245,74 @@ def main():
         res["fused_step_spread_ms"] = {k: round(max(v) - min(v), 4) for k, v in steps.items()}
         os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
         with open(os.path.join(ROOT, "profiles", "ema_kbench.json"), "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+    if args.what == "nll":
+        # the per-timestep softmax + NLL kernel (wn_step_nll) against the chunk softmax + CE kernel of the reference's loss
+        # (wn_chunk_softmax256_ce) on config 2's logits (8 x 256 x 12930), alternated on one box, by HIP events over `reps * 20`
+        # back-to-back calls; both read the logits once and write d loss / d logits once (2 B Q W 4 bytes).  Then the whole fused
+        # step under both objectives, alternated.  Written to profiles/nll_kbench.json
+        import time
+        eng.loss_and_grad(x, target)
+        bw = ws["bwd"]
+        B, W, Q = B_LOCAL, ws["W"], eng.Q
+        n = B * W
+        part = ws["loss_part"]
+        row_nll = torch.empty(n, dtype=torch.float32, device="cuda")
+        row_hit = torch.empty(n, dtype=torch.int32, device="cuda")
+
+        def timed(fn):
+            fn()
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            ev[0].record()
+            for _ in range(args.reps * 20):
+                fn()
+            ev[1].record()
+            torch.cuda.synchronize()
+            return ev[0].elapsed_time(ev[1]) / (args.reps * 20) * 1e3
+        legs = {
+            "chunk_softmax256_ce": lambda: call("wn_chunk_softmax256_ce", ptr(ws["O"]), ptr(target), None, ptr(bw["dO"]), ptr(part), n,
+                                                1.0 / n, st),
+            "step_nll": lambda: call("wn_step_nll", ptr(ws["O"]), Q * W, W, ptr(target), ptr(bw["dO"]), Q * W, W, None, None, None,
+                                     ptr(part), W, Q, B, 1.0 / n, st),
+            "step_nll_score": lambda: call("wn_step_nll", ptr(ws["O"]), Q * W, W, ptr(target), None, 0, 0, None, ptr(row_nll),
+                                           ptr(row_hit), ptr(part), W, Q, B, 1.0 / n, st),
+        }
+        us = {k: [] for k in legs}
+        for rnd in range(6):
+            for k, fn in legs.items():
+                us[k].append(timed(fn))
+        nbytes = 2 * B * Q * W * 4
+        res["nll_shape"] = [B, Q, W]
+        res["nll_algorithmic_bytes"] = nbytes
+        for k, vals in us.items():
+            res[k + "_us"] = round(float(np.median(vals)), 2)
+            res[k + "_us_all"] = [round(v, 2) for v in vals]
+        res["step_nll_over_chunk_ce"] = round(res["step_nll_us"] / res["chunk_softmax256_ce_us"], 3)
+        for k in ("chunk_softmax256_ce", "step_nll"):
+            res[k + "_TBps"] = round(nbytes / (res[k + "_us"] * 1e-6) / 1e12, 3)
+            res[k + "_share_of_8TBps"] = round(res[k + "_TBps"] / 8.0, 3)
+        steps = {"reference": [], "nll": []}
+        eng.adam_init(lr=1e-4)
+        for rnd in range(6):                               # alternated, as the guard and ema legs do
+            for label in steps:
+                for _ in range(3):
+                    eng.loss_and_grad(x, target, objective=label)
+                    eng.adam_step()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(args.reps * 4):
+                    eng.loss_and_grad(x, target, objective=label)
+                    eng.adam_step()
+                torch.cuda.synchronize()
+                steps[label].append((time.perf_counter() - t0) / (args.reps * 4) * 1e3)
+        for label, vals in steps.items():
+            res["fused_step_%s_ms" % label] = round(float(np.median(vals)), 4)
+            res["fused_step_%s_ms_all" % label] = [round(t, 4) for t in vals]
+        res["fused_step_nll_delta_ms"] = round(res["fused_step_nll_ms"] - res["fused_step_reference_ms"], 4)
+        res["fused_step_spread_ms"] = {k: round(max(v) - min(v), 4) for k, v in steps.items()}
+        os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+        with open(os.path.join(ROOT, "profiles", "nll_kbench.json"), "w") as f:
             json.dump(res, f, indent=1)
             f.write("\n")
     if args.what in ("ae", "all"):
