@@ -410,6 +410,30 @@ int wn_step_softmax(const float* x, int64_t x_bstride, int x_pitch, float* probs
 int wn_step_nll(const float* x, int64_t x_bstride, int x_pitch, const int64_t* target, float* dx, int64_t dx_bstride, int dx_pitch,
                 float* probs, float* row_nll, int32_t* row_hit, float* loss_part, int w, int q, int batch, float inv_n,
                 wn_stream_t stream);
+/* ---- LEARNED conditioning projections of the autoencoder: the N + 1 1x1 convs of the pooled encoding enc [batch][bw][le]
+ * (wavenet_autoencoder/model1.py:178-179, 216-217 draws them afresh per forward; here they are parameters), read from and
+ * differentiated into the flat buffers.  Offsets count floats from `flat` (and from `flat_grad`): stage i < n_stages has its weight
+ * [2 dd][bw] at w_off + i * stage_stride and its bias [2 dd] at b_off + i * stage_stride, rows in the reference's order (gate rows
+ * [0, dd), filter rows [dd, 2 dd)); the final stage has [sd][bw] at wf_off and [sd] at bf_off.
+ *   en_i[b][c][l] = bias_i[c] + sum_k W_i[c][k] enc[b][k][l]        enf[b][c][l] likewise with the final stage, [batch][sd][le]
+ * Block tables hold en_i in the layouts the block kernels read, [n_stages][tensors][rows][le], ch = dd padded to 32:
+ *   per clip (tab, d_tab with pair = 0):   tensor b,      filter row c -> c - dd,               gate row c -> ch + c,       rows 2 ch
+ *   clip pairs (tab_pair, pair = 1):       tensor b >> 1, filter row c -> (b & 1) ch + c - dd,  gate row c -> 2 ch + (b & 1) ch + c,  rows 4 ch
+ * wn_cond_proj_fwd writes every table it is given (tab, tab_pair: at least one) WHOLE, padding rows as zeros, and enf, in one launch.
+ * wn_cond_proj_bwd takes d_tab in the layout `pair` names and d_enf [batch][sd][le] and writes, in two launches,
+ *   d_enc[b][k][l] = sum_i sum_c W_i[c][k] d_en_i[b][c][l] + sum_c W_f[c][k] d_enf[b][c][l]         [batch][bw][le]
+ *   flat_grad:  dW_i[c][k] = sum_b sum_l d_en_i[b][c][l] enc[b][k][l],  db_i[c] = sum_b sum_l d_en_i[b][c][l]  (final stage alike)
+ * at the parameters' offsets, overwriting; nothing else of flat_grad is touched.  fp32 FMA arithmetic in a fixed order, no atomics:
+ * the same bits at every launch.  On `stream`, no allocation, nothing retained.  Any bw, le, dd, sd, n_stages >= 1.
+ * batch == 0 returns 0 (NULLs allowed).  -4, function and argument named in wn_last_error: batch < 0; n_stages, dd, sd, bw or le < 1;
+ * ch < dd or ch not a multiple of 32; a pair table with an odd batch; a negative offset; stage_stride < 2 dd bw with more than one
+ * stage; with work to do, a NULL required pointer. */
+int wn_cond_proj_fwd(const float* enc, const float* flat, int64_t w_off, int64_t b_off, int64_t stage_stride, int64_t wf_off,
+                     int64_t bf_off, float* tab, float* tab_pair, float* enf, int n_stages, int dd, int ch, int sd, int bw, int le,
+                     int batch, wn_stream_t stream);
+int wn_cond_proj_bwd(const float* d_tab, int pair, const float* d_enf, const float* enc, const float* flat, int64_t w_off,
+                     int64_t b_off, int64_t stage_stride, int64_t wf_off, int64_t bf_off, float* d_enc, float* flat_grad,
+                     int n_stages, int dd, int ch, int sd, int bw, int le, int batch, wn_stream_t stream);
 /* The reference's nn.DataParallel gradient reduction (wavenet/train.py:116-122) as ONE in-place sum over the ranks of the flat
  * fp32 gradient buffer: ncclAllReduce(buf, buf, n, ncclFloat32, ncclSum, comm, stream) on the caller's RCCL communicator
  * (`comm` = an ncclComm_t).  The 1 / world_size of the mean goes into wn_adam_flat's gscale.  Returns -5 when RCCL is neither

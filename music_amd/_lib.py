@@ -88,6 +88,8 @@ SIGNATURES = {
     "wn_ema_flat": [_p, _p, _l, _f, _i, _l, _p, _p],
     "wn_step_softmax": [_p, _l, _i, _p, _i, _i, _i, _p],
     "wn_step_nll": [_p, _l, _i, _p, _p, _l, _i, _p, _p, _p, _p, _i, _i, _i, _f, _p],
+    "wn_cond_proj_fwd": [_p, _p, _l, _l, _l, _l, _l, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
+    "wn_cond_proj_bwd": [_p, _i, _p, _p, _p, _l, _l, _l, _l, _l, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
     "wn_coll_available": [],
     "wn_comm_unique_id": [_p],
     "wn_comm_create": [_i, _i, _p, _p],

@@ -167,11 +167,11 @@ def resynthesize(net, clips, cond=None, teacher_forced=False, want_probs=False, 
     W = T - rf + 1
     if W < 1:
         raise ValueError("wave sample not long enough")
-    if cond is None:
-        cond = net._draw_conditioning()
+    eng_cond = net.engine_cond(cond)                                  # (learned conditioning: None, and a given `cond` is refused)
+    cond = eng_cond if eng_cond is not None else net.conditioning_projections()
     eng = net._engine_for(x.device)
     with torch.no_grad():
-        _, enc, _ = eng.forward(x, cond, want_probs=False)            # (raises when the clip pools to no frame)
+        _, enc, _ = eng.forward(x, eng_cond, want_probs=False)            # (raises when the clip pools to no frame)
     enc = net.last_encoding = enc.clone()
     Le = enc.size(2)
     wnet, proj = conditioned_decoder(net, cond)
@@ -216,6 +216,8 @@ def generate_cached(net, start_piece, note_num, cond=None, temperature=None, see
         from . import fast_generate as fg
     except ImportError:
         from music_amd import fast_generate as fg
+    if cond is not None:
+        net.engine_cond(cond)                                # (learned conditioning: a given `cond` is refused, as in resynthesize)
     with torch.no_grad():
         net(start_piece.cuda())                              # sets net.last_encoding (model1.py:256-268)
     enc = net.last_encoding
@@ -223,7 +225,7 @@ def generate_cached(net, start_piece, note_num, cond=None, temperature=None, see
         raise ValueError("the start piece pools to %d frames; the cached decoder needs exactly one "
                          "(receptive_field + pool .. receptive_field + 2*pool - 1 samples)" % enc.size(2))
     if cond is None:
-        cond = net._draw_conditioning()
+        cond = net.conditioning_projections()
     wnet = cached_decoder(net, enc, cond)
     codes = fg.generate_codes(wnet, start_piece[:, :, -wnet.receptive_field:].cuda(), note_num, correct_queue=True,
                               temperature=temperature, seed=seed, top_k=top_k, top_p=top_p)

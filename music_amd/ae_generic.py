@@ -60,6 +60,7 @@ class GenericAutoencoderEngine(GeneralPlan):
                 view = self.flat[o:o + p.numel()].view(p.shape)
                 view.copy_(p.data)
                 p.data = view                                # the module's parameters now ARE the flat buffer
+        self._plan_cond(net)
         self._build_packs()
         self._init_state()
 
@@ -88,7 +89,8 @@ class GenericAutoencoderEngine(GeneralPlan):
         pb.conv_1("connection_2.weight", "c2", Q, QP, Sd, SP)
         if self.use_bias:
             # filter_gate bias: its gradient rows come in the pack's [f | g] order, each half apart
-            pb.bias_rows([n for n in self.param_names if n.endswith(".bias")],
+            # (not the learned conditioning projections': wn_cond_proj_bwd writes theirs)
+            pb.bias_rows([n for n in self.gathered_param_names if n.endswith(".bias")],
                          {dn % (3 * i) + ".bias": (self.fg_rows, 2 * DdP) for i in range(N)})
         # the filter_gate biases of every block in the pack's padded [f | g] row order, gathered from the flat buffer
         self._finish_packs(pb, [[(dn % (3 * i) + ".bias", self.fg_rows)] for i in range(N)], 2 * DdP)
@@ -113,7 +115,9 @@ class GenericAutoencoderEngine(GeneralPlan):
         return out
 
     # ------------------------------------------------------------------ forward (model1.py:256-268)
-    def forward(self, x, cond, want_probs=True):
+    def forward(self, x, cond=None, want_probs=True):
+        """cond: the N + 1 drawn (weight, bias) pairs; None with learned conditioning (parameters of the flat buffer)"""
+        self._check_cond(cond)
         B, Q, T = x.shape
         assert Q == self.Q and x.is_contiguous() and x.dtype == torch.float32 and x.is_cuda
         W = T - self.rf + 1
@@ -126,9 +130,10 @@ class GenericAutoencoderEngine(GeneralPlan):
         ws["Le"] = Le
         N, pitch, dev = self.N, ws["pitch"], self.device
         ReP, DeP, BwP, RdP, DdP, SP, QP = self.ReP, self.DeP, self.BwP, self.RdP, self.DdP, self.SP, self.QP
-        cw = torch.stack([c[0][:, :, 0] for c in cond[:N]]).to(dev)          # (N, 2Dd, Bw) reference row order [gate | filter]
-        cb = torch.stack([c[1] for c in cond[:N]]).to(dev)
-        cfw, cfb = cond[N][0].to(dev), cond[N][1].to(dev)
+        if not self.learned:
+            cw = torch.stack([c[0][:, :, 0] for c in cond[:N]]).to(dev)      # (N, 2Dd, Bw) reference row order [gate | filter]
+            cb = torch.stack([c[1] for c in cond[:N]]).to(dev)
+            cfw, cfb = cond[N][0].to(dev), cond[N][1].to(dev)
         self.pack_weights()
         lo, k0 = self.rf - 1, self.k - 1
         xin_p, xin_bs = self._stage_input(ws, x)
@@ -155,13 +160,19 @@ class GenericAutoencoderEngine(GeneralPlan):
 
         # ---------------- conditioning tables en_i = Conv1d_rand(enc) (model1.py:178-179, 216-217), rows in the pack's [f | g] order
         Dd, Sd = self.Dd, self.Sd
-        en = torch.einsum("nck,bkl->nbcl", cw, enc) + cb[:, None, :, None]             # (N, B, 2Dd, Le)
-        tab = torch.zeros(N, B, 2 * DdP, Le, dtype=torch.float32, device=dev)
-        tab[:, :, :Dd] = en[:, :, Dd:]
-        tab[:, :, DdP:DdP + Dd] = en[:, :, :Dd]
-        enf = F.conv1d(enc, cfw, cfb).contiguous()                                     # (B, Sd, Le)
         cmodes = self._cond_modes(T, Le)
-        ws.update(enc=enc, cw=cw, cfw=cfw, cmodes=cmodes)
+        if self.learned:                                                               # the learned projections: one launch, every table
+            tab = torch.empty(N, B, 2 * DdP, Le, dtype=torch.float32, device=dev)
+            enf = torch.empty(B, Sd, Le, dtype=torch.float32, device=dev)
+            self.cond_proj_fwd(enc, tab, None, enf, DdP, st)
+            ws.update(enc=enc, cmodes=cmodes)
+        else:
+            en = torch.einsum("nck,bkl->nbcl", cw, enc) + cb[:, None, :, None]         # (N, B, 2Dd, Le)
+            tab = torch.zeros(N, B, 2 * DdP, Le, dtype=torch.float32, device=dev)
+            tab[:, :, :Dd] = en[:, :, Dd:]
+            tab[:, :, DdP:DdP + Dd] = en[:, :, :Dd]
+            enf = F.conv1d(enc, cfw, cfb).contiguous()                                 # (B, Sd, Le)
+            ws.update(enc=enc, cw=cw, cfw=cfw, cmodes=cmodes)
 
         # ---------------- decoder: the WaveNet stack and epilogue with a conditioning table under every [f; g] and under r1
         zb = N * DdP * pitch
@@ -241,8 +252,12 @@ class GenericAutoencoderEngine(GeneralPlan):
         ps.conv_k_bwd("de_causal", dxd[0], RdP * pitch, RdP, 1, k0, xin_p, xin_bs, T, QP)
         ps.bias_grad("de_causal_layer.bias", dxd[0], RdP * pitch, pitch, 0, self.Rd, k0)
         # ---- conditioning projections (unregistered, no gradient of their own): d enc = sum_i cw_i^T d en_i + cfw^T d enf
-        d_en = torch.cat([d_tab[:, :, DdP:DdP + Dd], d_tab[:, :, :Dd]], 2)             # reference row order [gate | filter]
-        d_enc = (torch.einsum("nck,nbcl->bkl", ws["cw"], d_en) + torch.einsum("ck,bcl->bkl", ws["cfw"][:, :, 0], d_enf)).contiguous()
+        if self.learned:                     # ... parameters of their own: d enc, dW and db (flat_grad's tail) in wn_cond_proj_bwd
+            d_enc = torch.empty(B, Bw, Le, dtype=torch.float32, device=dev)
+            self.cond_proj_bwd(d_tab, False, d_enf, ws["enc"], d_enc, DdP, st)
+        else:
+            d_en = torch.cat([d_tab[:, :, DdP:DdP + Dd], d_tab[:, :, :Dd]], 2)         # reference row order [gate | filter]
+            d_enc = (torch.einsum("nck,nbcl->bkl", ws["cw"], d_en) + torch.einsum("ck,bcl->bkl", ws["cfw"][:, :, 0], d_enf)).contiguous()
         # ---- encoder: avgpool -> bottleneck -> N blocks -> causal
         dE = ptr(bw["dE"], SLACK)
         call("wn_avgpool_bwd", ptr(d_enc), Bw * Le, Le, lo, self.pool, Le, Bw, dE, BwP * pitch, pitch, T, B, st)
@@ -274,6 +289,6 @@ class GenericAutoencoderEngine(GeneralPlan):
         ps.reduce_grads()
 
     # ------------------------------------------------------------------ fused training step (wavenet_autoencoder/train.py:146-160)
-    def loss_and_grad(self, x, target, cond, objective=None):
+    def loss_and_grad(self, x, target, cond=None, objective=None):
         """objective: None = self.objective (EngineBase)"""
         return self._throttled(lambda: self._fused_tail(self.forward(x, cond, want_probs=False)[2], target, objective=objective))

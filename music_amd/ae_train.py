@@ -22,6 +22,10 @@ as forward + one softmax/CE/backward kernel + backward + flat Adam on the engine
 (float) and ``"ema_warmup"`` (bool): the EMA shadow of the parameters (music_amd/ema.py; on the device for the fused step),
 written as ``wavenet_autoencoder{N}.ema`` next to every checkpoint in the checkpoint's own format and read back when that
 checkpoint is restored.
+
+Optional key in model_params.json: ``"conditioning"`` (``"random"``, the default and the reference's behaviour: the decoder's N + 1
+conditioning projections are drawn afresh in every forward; ``"learned"``: they are parameters of the model, trained, saved and
+restored with it - music_amd/model1.py).  A checkpoint only loads into a model built with the mode it was saved with.
 """
 import glob
 import os
@@ -213,8 +217,8 @@ def train():
             dp_scale = float(sampled_batch.get("dp_scale", 1.0))      # ragged last batch, see faster_audio_data._Collate
             if piece is not None:
                 target = target.view(-1)
-            if world > 1:
-                # every replica must draw the SAME per-forward conditioning projections
+            if world > 1 and net.conditioning != "learned":
+                # every replica must draw the SAME per-forward conditioning projections; learned ones are parameters
                 torch.manual_seed(step_seed + num_trained)
 
             def closure():
@@ -228,7 +232,7 @@ def train():
             if fused:
                 loss = torch.zeros((), device=device)
                 if piece is not None:
-                    loss = engine.loss_and_grad(piece.to(device).float().contiguous(), target.to(device), net._draw_conditioning())
+                    loss = engine.loss_and_grad(piece.to(device).float().contiguous(), target.to(device), net.engine_cond())
                 else:
                     engine.flat_grad.zero_()
                 wdist.allreduce_flat_(engine.flat_grad, average=False, scale=dp_scale)

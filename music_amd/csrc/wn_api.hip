@@ -402,6 +402,61 @@ int wn_step_nll(const float* x, int64_t x_bstride, int x_pitch, const int64_t* t
     return wn_launch_step_nll(x, (long)x_bstride, x_pitch, target, dx, (long)dx_bstride, dx_pitch, probs, row_nll, row_hit, loss_part, w, q,
                               batch, inv_n, (hipStream_t)stream);
 }
+// ---- learned conditioning projections (wn_condproj.hip) ----
+// the refusals both entries share: shapes, offsets and strides first (they need no pointer)
+static int cond_proj_checked(const char* fn, int64_t w_off, int64_t b_off, int64_t stage_stride, int64_t wf_off, int64_t bf_off, int pair,
+                             int n_stages, int dd, int ch, int sd, int bw, int le, int batch) {
+    char msg[200];
+    const char* bad = nullptr;
+    if (batch < 0) bad = "'batch' must be >= 0";
+    else if (n_stages < 1) bad = "'n_stages' must be >= 1";
+    else if (dd < 1) bad = "'dd' must be >= 1";
+    else if (sd < 1) bad = "'sd' must be >= 1";
+    else if (bw < 1) bad = "'bw' must be >= 1";
+    else if (le < 1) bad = "'le' must be >= 1";
+    else if (ch < dd || ch % 32 != 0) bad = "'ch' must be a multiple of 32 and >= dd";
+    else if (w_off < 0) bad = "'w_off' must be >= 0";
+    else if (b_off < 0) bad = "'b_off' must be >= 0";
+    else if (wf_off < 0) bad = "'wf_off' must be >= 0";
+    else if (bf_off < 0) bad = "'bf_off' must be >= 0";
+    else if (n_stages > 1 && stage_stride < (int64_t)2 * dd * bw) bad = "'stage_stride' must be >= 2 * dd * bw (the stages' weights overlap)";
+    else if (pair && batch % 2 != 0) bad = "'batch' must be even for a table of clip pairs";
+    if (bad) {
+        snprintf(msg, sizeof(msg), "%s: argument %s", fn, bad);
+        return wn_set_error_msg(-4, msg);
+    }
+    return 0;
+}
+int wn_cond_proj_fwd(const float* enc, const float* flat, int64_t w_off, int64_t b_off, int64_t stage_stride, int64_t wf_off,
+                     int64_t bf_off, float* tab, float* tab_pair, float* enf, int n_stages, int dd, int ch, int sd, int bw, int le,
+                     int batch, wn_stream_t stream) {
+    if (int rc = cond_proj_checked("wn_cond_proj_fwd", w_off, b_off, stage_stride, wf_off, bf_off, tab_pair != nullptr, n_stages, dd, ch,
+                                   sd, bw, le, batch)) return rc;
+    if (batch == 0) return 0;
+    WN_REQUIRE("wn_cond_proj_fwd", enc, flat, enf);
+    if (!tab && !tab_pair) return wn_set_error_msg(-4, "wn_cond_proj_fwd: argument 'tab' or 'tab_pair' must not be NULL");
+    WnCondProj p;
+    memset(&p, 0, sizeof(p));
+    p.enc = enc; p.flat = flat; p.w_off = (long)w_off; p.b_off = (long)b_off; p.stage_stride = (long)stage_stride;
+    p.wf_off = (long)wf_off; p.bf_off = (long)bf_off; p.tab = tab; p.tab_pair = tab_pair; p.enf = enf;
+    p.n_stages = n_stages; p.dd = dd; p.ch = ch; p.sd = sd; p.bw = bw; p.le = le; p.batch = batch;
+    return wn_launch_cond_proj_fwd(p, (hipStream_t)stream);
+}
+int wn_cond_proj_bwd(const float* d_tab, int pair, const float* d_enf, const float* enc, const float* flat, int64_t w_off,
+                     int64_t b_off, int64_t stage_stride, int64_t wf_off, int64_t bf_off, float* d_enc, float* flat_grad,
+                     int n_stages, int dd, int ch, int sd, int bw, int le, int batch, wn_stream_t stream) {
+    if (int rc = cond_proj_checked("wn_cond_proj_bwd", w_off, b_off, stage_stride, wf_off, bf_off, pair, n_stages, dd, ch, sd, bw, le,
+                                   batch)) return rc;
+    if (batch == 0) return 0;
+    WN_REQUIRE("wn_cond_proj_bwd", d_tab, d_enf, enc, flat, d_enc, flat_grad);
+    WnCondProj p;
+    memset(&p, 0, sizeof(p));
+    p.enc = enc; p.flat = flat; p.w_off = (long)w_off; p.b_off = (long)b_off; p.stage_stride = (long)stage_stride;
+    p.wf_off = (long)wf_off; p.bf_off = (long)bf_off; p.d_tab = d_tab; p.d_pair = pair ? 1 : 0; p.d_enf = d_enf; p.d_enc = d_enc;
+    p.flat_grad = flat_grad;
+    p.n_stages = n_stages; p.dd = dd; p.ch = ch; p.sd = sd; p.bw = bw; p.le = le; p.batch = batch;
+    return wn_launch_cond_proj_bwd(p, (hipStream_t)stream);
+}
 int wn_coll_available(void) { return wn_coll_loaded(); }
 int wn_comm_unique_id(char* id128) { return wn_coll_unique_id(id128); }
 int wn_comm_create(int nranks, int rank, const char* id128, void** comm) { return wn_coll_create(nranks, rank, id128, comm); }

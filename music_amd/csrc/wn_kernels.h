@@ -243,6 +243,18 @@ int wn_launch_avgpool_bwd(const float* denc, long denc_bstride, int denc_pitch, 
 int wn_launch_avgpool(const float* in, long in_bstride, int in_pitch, int t0, int pool, int n_out, int rows,
                       float* out, long out_bstride, int out_pitch, int batch, hipStream_t st);
 
+// learned conditioning projections (wn_condproj.hip): the N + 1 1x1 convs of the pooled encoding out of / into the flat buffers.
+// Offsets are floats into flat / flat_grad; stage i's weight [2 dd][bw] sits at w_off + i * stage_stride, its bias at b_off + i *
+// stage_stride, the final stage's [sd][bw] / [sd] at wf_off / bf_off.  tab / tab_pair / d_tab: the block tables, per clip or as pairs.
+struct WnCondProj {
+    const float* enc; const float* flat;
+    long w_off, b_off, stage_stride, wf_off, bf_off;
+    float* tab; float* tab_pair; float* enf;                                          // forward outputs (a table may be NULL)
+    const float* d_tab; int d_pair; const float* d_enf; float* d_enc; float* flat_grad;  // backward
+    int n_stages, dd, ch, sd, bw, le, batch;
+};
+int wn_launch_cond_proj_fwd(const WnCondProj& p, hipStream_t st);
+int wn_launch_cond_proj_bwd(const WnCondProj& p, hipStream_t st);
 // per-timestep softmax + negative log-likelihood over the channel axis of [B][Q][pitch] logits (wn_nll.hip); target NULL: softmax only
 int wn_launch_step_nll(const float* x, long x_bs, int x_pitch, const int64_t* target, float* dx, long dx_bs, int dx_pitch, float* probs,
                        float* row_nll, int32_t* row_hit, float* loss_part, int w, int q, int batch, float inv_n, hipStream_t st);

@@ -217,6 +217,55 @@ class EngineBase:
         if ws.get("x_ver") is not None and ws["x_in"]._version != ws["x_ver"]:
             raise RuntimeError("music_amd: the input of this forward was modified in place before backward()")
 
+    # ------------------------------------------------------------------ learned conditioning projections (the autoencoder's engines)
+    learned = False              # net.conditioning == "learned": the N + 1 projections are parameters at the END of the flat buffer
+    n_cond = 0                   # their floats: wn_cond_proj_bwd writes that tail of flat_grad, the gather everything in front of it
+
+    @property
+    def n_gather(self):
+        """Leading elements of flat_grad that the gather of the gradient pack fills."""
+        return self.spec.total - self.n_cond
+
+    @property
+    def gathered_param_names(self):
+        """The parameters whose gradients come out of the gradient pack: all but the learned projections' 2 (N + 1), the last ones."""
+        return self.param_names[:len(self.param_names) - (2 * (len(self.dil) + 1) if self.learned else 0)]
+
+    def _plan_cond(self, net):
+        """Learned mode: where wn_cond_proj_fwd / wn_cond_proj_bwd find the projections in the flat buffers."""
+        self.learned = getattr(net, "conditioning", "random") == "learned"
+        if not self.learned:
+            return
+        o, N = self.spec.off, len(self.dil)
+        w0, b0 = o["de_cond_layer_stack.0.weight"], o["de_cond_layer_stack.0.bias"]
+        stride = 2 * self.Dd * self.Bw + 2 * self.Dd
+        wf, bf = o["connection_cond.weight"], o["connection_cond.bias"]
+        # registered last, in stage order (weight, bias per stage): one constant stage stride, and nothing behind them
+        assert all(o["de_cond_layer_stack.%d.weight" % i] == w0 + i * stride and o["de_cond_layer_stack.%d.bias" % i] == b0 + i * stride
+                   for i in range(N)) and wf == w0 + N * stride and bf + self.Sd == self.spec.total
+        self.cond_off = (w0, b0, stride, wf, bf)
+        self.n_cond = self.spec.total - w0
+
+    def _check_cond(self, cond):
+        """`cond` of forward / loss_and_grad: the drawn projections in random mode, None in learned mode - nothing is ignored silently."""
+        if self.learned and cond is not None:
+            raise ValueError('music_amd: conditioning="learned": the projections are the model\'s parameters, pass cond=None')
+        if not self.learned and cond is None:
+            raise ValueError('music_amd: conditioning="random": pass the drawn projections (net.conditioning_projections()) as cond')
+
+    def cond_proj_fwd(self, enc, tab, tab_pair, enf, ch, st):
+        """All N + 1 projections of enc (B, Bw, Le) out of the flat buffer in one launch: the block tables (per clip and / or as clip
+        pairs, padding rows included) and the final table enf (B, Sd, Le)."""
+        B, _, Le = enc.shape
+        call("wn_cond_proj_fwd", ptr(enc), ptr(self.flat), *self.cond_off, ptr(tab), ptr(tab_pair), ptr(enf), len(self.dil), self.Dd, ch,
+             self.Sd, self.Bw, Le, B, st)
+
+    def cond_proj_bwd(self, d_tab, pair, d_enf, enc, d_enc, ch, st):
+        """d enc and the projections' own gradients (into the tail of flat_grad) from the block tables' and the final table's gradients."""
+        B, _, Le = enc.shape
+        call("wn_cond_proj_bwd", ptr(d_tab), 1 if pair else 0, ptr(d_enf), ptr(enc), ptr(self.flat), *self.cond_off, ptr(d_enc),
+             ptr(self.flat_grad), len(self.dil), self.Dd, ch, self.Sd, self.Bw, Le, B, st)
+
     # ------------------------------------------------------------------ the second stream
     def _side_stream(self):
         """THE side stream of this device (_lib.side_stream: high priority = a hardware queue of its own), created at first use."""
@@ -257,9 +306,9 @@ class EngineBase:
         flat_grad (pair mode: a stack weight's gradient is the sum of its two copies in the block-diagonal matrix)"""
         call("wn_reduce_slabs", ptr(bw["desc_codes"] if from_codes else bw["desc"]), bw["nops"], bw["vec"], ptr(bw["slab"]), ptr(self.gpack), st)
         if bw["pair"]:
-            call("wn_gather_grads2", ptr(self.gpack), ptr(self.gidx_pa), ptr(self.gidx_pb), ptr(self.flat_grad), self.spec.total, st)
+            call("wn_gather_grads2", ptr(self.gpack), ptr(self.gidx_pa), ptr(self.gidx_pb), ptr(self.flat_grad), self.n_gather, st)
         else:
-            call("wn_gather_grads", ptr(self.gpack), ptr(self.gidx), ptr(self.flat_grad), self.spec.total, st)
+            call("wn_gather_grads", ptr(self.gpack), ptr(self.gidx), ptr(self.flat_grad), self.n_gather, st)
 
     # ------------------------------------------------------------------ the causal layer(s): from integer codes, else dense
     @staticmethod

@@ -83,6 +83,7 @@ class _AutoencoderEngine(EngineBase):
                 view = self.flat[o:o + p.numel()].view(p.shape)
                 view.copy_(p.data)
                 p.data = view
+        self._plan_cond(net)
         self._build_packs()
         self._init_state()
 
@@ -277,9 +278,11 @@ class _AutoencoderEngine(EngineBase):
     def _lay(self, t, i, ch, ws):
         return ptr(t, SLACK + i * ws["B"] * ch * ws["pitch"])
 
-    def forward(self, x, cond, want_probs=True):
-        """cond: list of N+1 (weight (C,Bw,1), bias (C,)) CPU tensors (see wavenet_autoencoder.forward).
+    def forward(self, x, cond=None, want_probs=True):
+        """cond: list of N+1 (weight (C,Bw,1), bias (C,)) CPU tensors (see wavenet_autoencoder.forward); None with learned
+        conditioning, whose projections are parameters of the flat buffer.
         want_probs=False stops at the pre-softmax logits in ws["O"] (the fused training step)."""
+        self._check_cond(cond)
         B, Q, T = x.shape
         W = T - self.rf + 1
         Le = W // self.pool
@@ -299,7 +302,8 @@ class _AutoencoderEngine(EngineBase):
         # the 31 conditioning projections (drawn on the CPU, model1.py:178,216) go to the device FIRST, in one asynchronous copy
         # from pinned memory: as four pageable .to(device) copies behind the encoder they made the host wait for the encoder
         # stack and the decoder start from an empty queue (0.35 ms for this phase at config 4)
-        cw, cb, cfw, cfb = self._stage_cond(cond)
+        if not self.learned:
+            cw, cb, cfw, cfb = self._stage_cond(cond)
         call("wn_pack_weights", ptr(self.flat), ptr(self.pk_idx), ptr(self.pk), self.pk_idx.numel(), m, st)
         fr, lo = self._fr, self.rf - 1
         NONE3 = (None, 0, 0)
@@ -334,12 +338,22 @@ class _AutoencoderEngine(EngineBase):
 
         # ---------------- conditioning tables: en = Conv1d_rand(enc)  (model1.py:178-179, 216-217)
         Dd, Sd = self.Dd, self.Sd
-        en = torch.einsum("nck,bkl->nbcl", cw, enc) + cb[:, None, :, None]             # (N, B, 2Dd, Le)
-        tab = torch.zeros(N, B, 2 * CHd, Le, dtype=torch.float32, device=self.device)
-        tab[:, :, :Dd] = en[:, :, Dd:]                                                 # my rows: filter first
-        tab[:, :, CHd:CHd + Dd] = en[:, :, :Dd]
-        enf = F.conv1d(enc, cfw, cfb)                                                  # (B, Sd, Le)
-        ws.update(enc=enc, tab=tab, cw=cw, cfw=cfw)
+        if self.learned:
+            # the learned projections: every table straight in the layout its reader wants, in one launch (wn_cond_proj_fwd) - per
+            # clip for a 32-channel or unpaired forward, as clip pairs for the pair blocks (forward if pair_f, backward always)
+            empty = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=self.device)
+            tab_c = empty(N, B, 2 * CHd, Le) if not pair_f else None
+            tab = empty(N, B // 2, 4 * CHd, Le) if pair else tab_c
+            enf = empty(B, Sd, Le)
+            self.cond_proj_fwd(enc, tab_c, tab if pair else None, enf, CHd, st)
+            ws.update(enc=enc, tab=tab)
+        else:
+            en = torch.einsum("nck,bkl->nbcl", cw, enc) + cb[:, None, :, None]             # (N, B, 2Dd, Le)
+            tab = torch.zeros(N, B, 2 * CHd, Le, dtype=torch.float32, device=self.device)
+            tab[:, :, :Dd] = en[:, :, Dd:]                                                 # my rows: filter first
+            tab[:, :, CHd:CHd + Dd] = en[:, :, :Dd]
+            enf = F.conv1d(enc, cfw, cfb)                                                  # (B, Sd, Le)
+            ws.update(enc=enc, tab=tab, cw=cw, cfw=cfw)
 
         # ---------------- decoder (model1.py:158-225)
         xd = lambda i: self._lay(ws["Xd"], i, CHd, ws)
@@ -354,8 +368,9 @@ class _AutoencoderEngine(EngineBase):
         ws["cmodes"] = cmodes
         cpk = cix = None
         CHp, Bp = (64, B // 2) if pair else (CHd, B)         # pair mode: 64-row tensors of two clips, rows [f: A B | g: A B]
-        tab_c = tab                                         # per clip, rows [f | g]: what the 32-channel forward block gathers from
-        if pair:
+        if not self.learned:
+            tab_c = tab                                     # per clip, rows [f | g]: what the 32-channel forward block gathers from
+        if pair and not self.learned:
             tab = tab.view(N, Bp, 2, 2, CHd, Le).permute(0, 1, 3, 2, 4, 5).reshape(N, Bp, 4 * CHd, Le).contiguous()
             ws["tab"] = tab
         if Le <= 32 and CHp == 64 and m == _lib.F16X3 and (pair or os.environ.get("WN_AE_COND_MFMA", "1") == "1"):
@@ -397,7 +412,8 @@ class _AutoencoderEngine(EngineBase):
             bias_s = ptr(bsum)
         # final conditioning expanded over time (stretch / tile rule on the length-W sequence)
         ws["cf_mode"] = (1, W // Le) if W % Le == 0 else (2, 0)
-        enf = enf.contiguous()
+        if not self.learned:
+            enf = enf.contiguous()
         call("wn_cond_expand", ptr(enf), Sd * Le, Le, Sd, lo, T, ws["cf_mode"][0], Le, max(ws["cf_mode"][1], 1), C1, sb, pitch, B, st)
 
         def chain(b0, nb, s_):
@@ -500,7 +516,7 @@ class _AutoencoderEngine(EngineBase):
         ws["bwd"] = bw
         return bw
 
-    def loss_and_grad(self, x, target, cond, objective=None):
+    def loss_and_grad(self, x, target, cond=None, objective=None):
         """Fused training step body (the autoencoder counterpart of engine.loss_and_grad): forward to the logits, ONE
         kernel for chunk softmax + CrossEntropyLoss on the probabilities (wavenet_autoencoder/train.py:146-160) + both
         backward steps, then the backward.  Returns the loss (0-d device tensor); gradients land in self.flat_grad.
@@ -528,7 +544,7 @@ class _AutoencoderEngine(EngineBase):
         # bias gradients (use_bias=True): row sums of the matching output gradient, collected in one small buffer
         # and copied to their flat-parameter positions after the weight gradients were gathered
         if self.use_bias and getattr(self, "_bias_plan", None) is None:
-            names = [n for n in self.param_names if n.endswith(".bias")]
+            names = [n for n in self.gathered_param_names if n.endswith(".bias")]
             off, o = {}, 0
             for n in names:
                 off[n[:-5]] = o
@@ -630,7 +646,7 @@ class _AutoencoderEngine(EngineBase):
         if bw["pq"]:
             call("wn_resblock_bwd_pq_cond_reduce", ptr(bw["cslab"]), bw["cs_off"], bw["cs_tlo"], N, T, Bp, Le, ptr(d_tab),
                  Bp * rows * Le, rows * Le, Le, st)
-            if pair:                                    # back to per-clip tables, rows [f | g]
+            if pair and not self.learned:               # back to per-clip tables, rows [f | g]
                 d_tab = d_tab.view(N, Bp, 2, 2, CHd, Le).permute(0, 1, 3, 2, 4, 5).reshape(N, B, 2 * CHd, Le)
         self.mark("dec_stack_bwd")
         x_codes = self.codes_for_backward(ws)
@@ -638,9 +654,14 @@ class _AutoencoderEngine(EngineBase):
         causal_wgrad("de_causal", ptr(bw["dXd"][0], SLACK), CHd)
         bias_grad("de_causal_layer", ptr(bw["dXd"][0], SLACK), db, pitch, 0, Rd, 1, T)
         # ---- conditioning: en_i = cw_i enc + b (rows in the reference order: gate first), enf = cfw enc + b
-        d_en = torch.cat([d_tab[:, :, CHd:CHd + Dd], d_tab[:, :, :Dd]], 2)            # (N,B,2Dd,Le) reference row order
-        d_enc = torch.einsum("nck,nbcl->bkl", ws["cw"], d_en) + torch.einsum("ck,bcl->bkl", ws["cfw"][:, :, 0], d_enf)
-        d_enc = d_enc.contiguous()
+        if self.learned:
+            # ... and they are parameters: d enc, dW and db (into flat_grad's tail) straight from the block tables' layout
+            d_enc = torch.empty(B, Bw, Le, dtype=torch.float32, device=self.device)
+            self.cond_proj_bwd(d_tab, pair, d_enf, ws["enc"], d_enc, CHd, st)
+        else:
+            d_en = torch.cat([d_tab[:, :, CHd:CHd + Dd], d_tab[:, :, :Dd]], 2)            # (N,B,2Dd,Le) reference row order
+            d_enc = torch.einsum("nck,nbcl->bkl", ws["cw"], d_en) + torch.einsum("ck,bcl->bkl", ws["cfw"][:, :, 0], d_enf)
+            d_enc = d_enc.contiguous()
         # ---- encoder: avgpool -> bottleneck -> N blocks -> causal
         dE = ptr(bw["dE"], SLACK)
         call("wn_avgpool_bwd", ptr(d_enc), Bw * Le, Le, lo, self.pool, Le, Bw, dE, BwP * pitch, pitch, T, B, st)
@@ -697,6 +718,9 @@ class _AutoencoderEngine(EngineBase):
         self.mark("en_causal_slab_reduce")
 
 
+CONDITIONING = ("random", "learned")     # the decoder's conditioning projections: drawn afresh per forward (the reference), or parameters
+
+
 class _AutoencoderFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, net, grad_on, wave_sample, cond, *params):
@@ -737,8 +761,12 @@ class wavenet_autoencoder(nn.Module):
 
     def __init__(self, filter_width, quantization_channel, dilations, en_residual_channel, en_dilation_channel,
                  en_bottleneck_width, en_pool_kernel_size, de_residual_channel, de_dilation_channel,
-                 de_skip_channel, use_bias):
+                 de_skip_channel, use_bias, conditioning="random"):
         super(wavenet_autoencoder, self).__init__()
+        if conditioning not in CONDITIONING:
+            raise ValueError("music_amd.wavenet_autoencoder: conditioning must be one of %s, not %r"
+                             % (", ".join('"%s"' % c for c in CONDITIONING), conditioning))
+        self.conditioning = conditioning
         self.filter_width = filter_width
         self.quantization_channel = quantization_channel
         self.dilations = dilations
@@ -779,6 +807,45 @@ class wavenet_autoencoder(nn.Module):
         # (forward, backward) arithmetic of the matrix-core products, as on `wavenet`; ("bf16x3", "bf16x3") gives the forward float32's exponent range
         # (an un-normalised ReLU encoder can leave f16's: DESIGN section 5) at 2^-17 instead of 2^-22 per product
         self.precision = ("f16x3", "bf16x3")
+        if conditioning == "learned":
+            # the N + 1 conditioning projections as parameters (the reference draws them afresh in every forward): registered
+            # AFTER every reference submodule, so a seed gives the reference's parameters the same values in both modes and these sit at
+            # the end of the flat buffer; always with a bias, rows in the reference's order (gate first), like the drawn convs
+            self.de_cond_layer_stack = nn.ModuleList(nn.Conv1d(en_bottleneck_width, 2 * de_dilation_channel, 1) for _ in dilations)
+            self.connection_cond = nn.Conv1d(en_bottleneck_width, de_skip_channel, 1)
+
+    def __setstate__(self, state):
+        super(wavenet_autoencoder, self).__setstate__(state)
+        self.__dict__.setdefault("conditioning", "random")       # (a module pickled before the attribute existed)
+
+    def _cond_modules(self):
+        return list(self.de_cond_layer_stack) + [self.connection_cond]
+
+    def conditioning_projections(self):
+        """The N + 1 (weight (C, Bw, 1), bias (C,)) pairs a forward conditions the decoder on: the (detached) parameters with learned
+        conditioning - no RNG is consumed -, a fresh draw from the global RNG (_draw_conditioning) with random conditioning."""
+        if getattr(self, "conditioning", "random") == "learned":
+            return [(m.weight.detach(), m.bias.detach()) for m in self._cond_modules()]
+        return self._draw_conditioning()
+
+    def engine_cond(self, cond=None):
+        """What the engine's forward / loss_and_grad take as `cond`: None with learned conditioning (a given list is refused there),
+        else `cond` or a fresh draw."""
+        if getattr(self, "conditioning", "random") == "learned":
+            if cond is not None:
+                raise ValueError('music_amd.wavenet_autoencoder: conditioning="learned": the projections are parameters, cond must be None')
+            return None
+        return cond if cond is not None else self._draw_conditioning()
+
+    def load_state_dict(self, state_dict, *args, **kwargs):
+        # a checkpoint of the other conditioning mode: refused whole, by name, before anything is copied
+        has = any(k.startswith(("de_cond_layer_stack.", "connection_cond.")) for k in state_dict.keys())
+        mine = getattr(self, "conditioning", "random")
+        if has != (mine == "learned"):
+            raise RuntimeError('music_amd.wavenet_autoencoder: the checkpoint was saved with conditioning="%s" but this model was built '
+                               'with conditioning="%s" (the "conditioning" key of model_params.json); nothing was loaded'
+                               % ("learned" if has else "random", mine))
+        return super(wavenet_autoencoder, self).load_state_dict(state_dict, *args, **kwargs)
 
     def __getstate__(self):
         # copy.deepcopy / pickle / torch.save(module): the engine (HIP streams, workspaces, ctypes plans) stays behind and is rebuilt
@@ -846,7 +913,7 @@ class wavenet_autoencoder(nn.Module):
         if output_width <= 0:
             raise ValueError("wave sample not long enough")
         self._engine_for(wave_sample.device)
-        cond = self._draw_conditioning()
+        cond = self.engine_cond()
         self._last_hook = None
         out = _AutoencoderFunction.apply(self, torch.is_grad_enabled(), wave_sample, cond, *list(self.parameters()))
         hook, self._last_hook = self._last_hook, None

@@ -38,15 +38,15 @@ def _dense_input(wave_sample):
 
 def _forward_logits(net, wave_sample):
     """The module's forward up to the pre-softmax logits: (engine, workspace with the logits in ws["O"]).  The autoencoder draws its
-    per-forward conditioning convs from the global RNG, as its own forward does."""
+    per-forward conditioning convs from the global RNG, as its own forward does (learned ones are parameters: nothing is drawn)."""
     if wave_sample.dim() != 3:
         raise ValueError("music_amd.objective: the input is a (B, Q, T) one-hot, got shape %s" % (tuple(wave_sample.shape),))
     if wave_sample.shape[2] - net.receptive_field + 1 <= 0:
         raise ValueError("wave sample not long enough")
     eng = net._engine_for(wave_sample.device)
     x = _dense_input(wave_sample)
-    if hasattr(net, "_draw_conditioning"):
-        _, enc, ws = eng.forward(x, net._draw_conditioning(), want_probs=False)
+    if hasattr(net, "engine_cond"):
+        _, enc, ws = eng.forward(x, net.engine_cond(), want_probs=False)
         net.last_encoding = enc
     else:
         eng.pack_weights()

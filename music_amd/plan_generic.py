@@ -140,7 +140,7 @@ class GeneralPlan(EngineBase):
     def _finish_packs(self, pb, gate_bias, gate_rows_p):
         """pb: the plan's PackBuilder, every weight and bias placed.  gate_bias: per block, the biases of the [f | g] product as
         [(name, pack row of bias row r)] - gathered into `bfg` in the product's padded row order by pack_weights()."""
-        assert (pb.gidx >= 0).all()
+        assert (pb.gidx[:self.n_gather] >= 0).all()          # (learned conditioning projections: wn_cond_proj_bwd writes theirs)
         dev = self.device
         self.gp_off, self.gp_bias_off = pb.gp_off, pb.gp_bias_off
         self.gpack = torch.zeros(pb.go, dtype=torch.float32, device=dev)
@@ -292,7 +292,7 @@ class Pass:
         """slabs -> gradient pack -> flat_grad (fixed summation order: bit-reproducible)"""
         eng, bw = self.eng, self.bw
         call("wn_reduce_slabs", ptr(bw["desc"]), bw["nops"], bw["vec"], ptr(bw["slab"]), ptr(eng.gpack), self.st)
-        call("wn_gather_grads", ptr(eng.gpack), ptr(eng.gidx), ptr(eng.flat_grad), eng.spec.total, self.st)
+        call("wn_gather_grads", ptr(eng.gpack), ptr(eng.gidx), ptr(eng.flat_grad), eng.n_gather, self.st)
         eng.mark("slab_reduce")
 
     def cond_expand(self, cond, t_lo, out, out_bs):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of single kernels of the hot path at BASELINE config-2 shapes (GPU only).
 
-    python tools/kbench.py [fwd|bwd|epi|dx|skip|decode|ae|guard|ema|nll|all] [--reps N] [--precision f16x3,bf16x3]
+    python tools/kbench.py [fwd|bwd|epi|dx|skip|decode|ae|guard|ema|nll|cond|all] [--reps N] [--precision f16x3,bf16x3]
 
 Prints per-phase / per-layer kernel times measured with HIP events on the launch stream.
 """
@@ -313,6 +313,79 @@ def main():
         res["fused_step_spread_ms"] = {k: round(max(v) - min(v), 4) for k, v in steps.items()}
         os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
         with open(os.path.join(ROOT, "profiles", "nll_kbench.json"), "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+    if args.what == "cond":
+        # the learned conditioning projections (wn_cond_proj_fwd: one launch; wn_cond_proj_bwd: two) alone at config 4's shape and at
+        # the shipped autoencoder's, by HIP events over `reps * 20` back-to-back calls, six alternations; then the fused config-4
+        # step with conditioning="learned" against "random" on one box, alternated.  Written to profiles/cond_kbench.json
+        import time
+        from music_amd.model1 import wavenet_autoencoder
+
+        def timed(fn):
+            fn()
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            ev[0].record()
+            for _ in range(args.reps * 20):
+                fn()
+            ev[1].record()
+            torch.cuda.synchronize()
+            return ev[0].elapsed_time(ev[1]) / (args.reps * 20) * 1e3
+        shapes = {"config4": dict(N=30, Dd=64, CH=64, Sd=256, Bw=64, Le=25, B=8, pair=False),
+                  "shipped": dict(N=40, Dd=32, CH=32, Sd=512, Bw=512, Le=32, B=4, pair=True)}
+        for tag, g in shapes.items():
+            N, Dd, CH, Sd, Bw, Le, B, pair = (g[k] for k in ("N", "Dd", "CH", "Sd", "Bw", "Le", "B", "pair"))
+            rnd = lambda *shape: torch.randn(*shape, device="cuda")
+            stride = 2 * Dd * Bw + 2 * Dd
+            n = N * stride + Sd * Bw + Sd
+            flat, grad, enc = rnd(n) * 0.1, torch.empty(n, device="cuda"), rnd(B, Bw, Le)
+            offs = (0, 2 * Dd * Bw, stride, N * stride, N * stride + Sd * Bw)
+            dims = (N, Dd, CH, Sd, Bw, Le, B)
+            tab, tabp, enf = rnd(N, B, 2 * CH, Le), (rnd(N, B // 2, 4 * CH, Le) if pair else None), rnd(B, Sd, Le)
+            d_enc = torch.empty(B, Bw, Le, device="cuda")
+            legs = {"fwd": lambda: call("wn_cond_proj_fwd", ptr(enc), ptr(flat), *offs, ptr(tab), ptr(tabp), ptr(enf), *dims, st),
+                    "bwd": lambda: call("wn_cond_proj_bwd", ptr(tabp if pair else tab), 1 if pair else 0, ptr(enf), ptr(enc), ptr(flat), *offs,
+                                        ptr(d_enc), ptr(grad), *dims, st)}
+            us = {k: [] for k in legs}
+            for _ in range(6):
+                for k, fn in legs.items():
+                    us[k].append(timed(fn))
+            R, C = N * 2 * Dd + Sd, B * Le
+            res["cond_%s_shape" % tag] = g
+            res["cond_%s_flop" % tag] = {"fwd": 2 * R * C * Bw, "bwd": 4 * R * C * Bw}
+            for k, vals in us.items():
+                res["cond_%s_%s_us" % (tag, k)] = round(float(np.median(vals)), 2)
+                res["cond_%s_%s_us_all" % (tag, k)] = [round(v, 2) for v in vals]
+        steps, engines = {"random": [], "learned": []}, {}
+        for label in steps:
+            torch.manual_seed(0)
+            ae = wavenet_autoencoder(filter_width=2, quantization_channel=256, dilations=CFG["dilations"], en_residual_channel=64,
+                                     en_dilation_channel=64, en_bottleneck_width=64, en_pool_kernel_size=512, de_residual_channel=64,
+                                     de_dilation_channel=64, de_skip_channel=256, use_bias=False, conditioning=label).cuda()
+            engines[label] = (ae, ae._engine_for(x.device))
+            engines[label][1].adam_init(lr=1e-4)
+
+        def fused(label):
+            ae, aeng = engines[label]
+            aeng.loss_and_grad(x, target, ae.engine_cond())
+            aeng.adam_step()
+        for rnd_ in range(6):
+            for label in steps:
+                for _ in range(3):
+                    fused(label)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(args.reps * 4):
+                    fused(label)
+                torch.cuda.synchronize()
+                steps[label].append((time.perf_counter() - t0) / (args.reps * 4) * 1e3)
+        for label, vals in steps.items():
+            res["fused_c4_step_%s_ms" % label] = round(float(np.median(vals)), 4)
+            res["fused_c4_step_%s_ms_all" % label] = [round(t, 4) for t in vals]
+        res["fused_c4_step_learned_delta_ms"] = round(res["fused_c4_step_learned_ms"] - res["fused_c4_step_random_ms"], 4)
+        res["fused_c4_step_spread_ms"] = {k: round(max(v) - min(v), 4) for k, v in steps.items()}
+        os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+        with open(os.path.join(ROOT, "profiles", "cond_kbench.json"), "w") as f:
             json.dump(res, f, indent=1)
             f.write("\n")
     if args.what in ("ae", "all"):
