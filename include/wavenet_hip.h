@@ -75,7 +75,9 @@ int wn_chan_gemm(const float* in0, const float* in1, int64_t in_bstride, int in_
 
 /* Fused gated residual block, forward (wavenet/model.py:111-129 for one dilation d):
  *   [f;g] = Wfg [x(t-d); x(t)] ; z = tanh f * sigmoid g ; x_out = Wd z + x(t) on [t_lo,t_hi);
- *   z is stored on [z_lo, t_hi) (the crop the skip product needs).  ch = padded channels (32|64).
+ *   z is stored on [z_lo, t_hi) (the crop the skip product needs).  ch = padded channels (32|64).  All ch rows of z and
+ *   (write_x != 0) of x_out are written on their windows, the padded rows - zero weights, no bias (rows >= n_f / n_d), zero
+ *   table rows - as exact zeros; nothing else is touched, and with write_x == 0 x_out is not touched at all.
  * Optional conditioning of the autoencoder's decoder (wavenet_autoencoder/model1.py:175-192,
  * 227-247): [f;g][row][t] += cond[b][row][idx(t)], cond = [B][2*ch][cond_pitch] (rows f then g),
  * idx = (t - t_lo) / cond_q when cond_mode == 1 ("stretch"), (t - t_lo) % cond_le when 2 ("tile");

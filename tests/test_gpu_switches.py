@@ -180,8 +180,9 @@ def test_fused_epilogue_equals_the_three_launches(monkeypatch):
     direction (wn_skip_epilogue_fwd / _bwd, engine.epi_fused / epi_fused_bwd; round 6); WN_EPI_FUSED=0 / WN_EPI_FUSED_BWD=0 are the three
     wn_chan_gemm launches each (dZ then on the B-stationary product, and with WN_GEMM_BST=0 on chan_gemm_wide2_k).  Same products, the
     intermediate tiles in the chained k order: probabilities within 2e-6, loss within 1e-6, every gradient within 2e-5 of its max-abs;
-    a second run of the fused form reproduces its bits.  Ragged batch of 3 (a partly filled last round: tiles dealt out by dZ passes
-    is exercised at the bench geometry by tests/test_gpu_fullsize.py)."""
+    a second run of the fused form reproduces its bits.  Ragged batch of 3 (a partly filled last round - tiles dealt out by dZ passes -
+    needs more tiles than compute units: tests/test_gpu_fwd_kernels.py launches it on its own, one tile more than a round, against
+    float64 and bit for bit against whole tiles; tests/test_gpu_fullsize.py runs it at the bench geometry)."""
     import numpy as np
     import torch
     from music_amd.model import wavenet
