@@ -18,27 +18,8 @@ import torch
 from . import _lib
 from ._lib import call, ptr
 from .engine_base import SLACK, PAD_BACK, EngineBase, SlabPlan, WorkspaceHold, WorkspacePool, _Spec, _pad  # noqa: F401 (re-exported)
-from .stack import GatedStack, diag, finish, full
-
-def pack_positions(mt, ks, chained):
-    """Logical A-fragment order -> (row, k) of the effective weight matrix.
-    p = ((m*ks + s)*64 + lane)*8 + j ; row = 16m + (lane&15) ; k = kmap(s, lane>>4, j)."""
-    m, s, lane, j = np.indices((mt, ks, 64, 8))
-    row = 16 * m + (lane & 15)
-    q = lane >> 4
-    if chained:
-        k = 32 * s + 16 * (j >> 2) + 4 * q + (j & 3)
-    else:
-        k = 32 * s + 8 * q + j
-    return row.reshape(-1), k.reshape(-1)
-
-
-def pack_index(weff, chained=False):
-    """weff: int32 [Mp, Kp] of flat-parameter offsets (-1 = zero).  Returns idx[p] (int32)."""
-    mp, kp = weff.shape
-    assert mp % 16 == 0 and kp % 32 == 0
-    row, k = pack_positions(mp // 16, kp // 32, chained)
-    return weff[row, k].astype(np.int32)
+from .packs import PackSet, causal_mats, epilogue_mats, gated_mats, pack_index, pack_positions, pair_mats  # noqa: F401 (pack_* re-exported)
+from .stack import EpiBias, GatedStack, SkipEpilogue
 
 
 class WaveNetEngine(EngineBase):
@@ -94,6 +75,12 @@ class WaveNetEngine(EngineBase):
         self.stack = GatedStack(self, "", self.CH, self.R, self.D, self._fr, self._br,
                                 lambda i: (self._bias_ptr(bn % (4 * i)), self._bias_ptr(bn % (4 * i + 1)), self._bias_ptr(bn % (4 * i + 2))),
                                 self.mode_fwd, self.mode_bwd, fmark=self.fmark, side_wgrad=True, zero_tail=True)
+        # the bias gradients are rows of the gradient pack, behind the data-gradient products
+        bias = EpiBias([bn % (4 * i + 3) for i in range(self.N)], "post_process_1.bias", "post_process_2.bias", self._bias_ptr,
+                       lambda name: ptr(self.gpack, self.gp_bias_off[name]),
+                       [self.spec.off[bn % (4 * i + 3)] for i in range(self.N)]) if self.use_bias else None
+        self.epilogue = SkipEpilogue(self, ("skip", "p1", "p2"), ("U", "H", None, "dH"), self.CH, self.S, self.SP, self._fr, self._br,
+                                     self.mode_fwd, self.mode_bwd, bias=bias, fmark=self.fmark)
 
     def fmark(self, name):
         """Per-kernel timing marks of the epilogue (tools/kbench.py epi); off unless self.fine_marks."""
@@ -145,167 +132,46 @@ class WaveNetEngine(EngineBase):
 
     # ------------------------------------------------------------------ packs
     def _build_packs(self):
-        sp, CH, N, R, D, S, Q, SP = self.spec, self.CH, self.N, self.R, self.D, self.S, self.Q, self.SP
-        fwd, bwd = [], []            # lists of (name, idx array)
-        gp = []                      # gradient C matrices: (name, rows, cols)
-
-        # 1. causal: rows R, K = [tap0 Q | tap1 Q]
-        wc = sp.conv("causal_layer.weight")                 # [R,Q,2]
-        w = full(CH, 2 * Q)
-        w[:R, :Q] = wc[:, :, 0]
-        w[:R, Q:] = wc[:, :, 1]
-        fwd.append(("causal", pack_index(w)))
-        gp.append(("causal", CH, 2 * Q))
-        # 1b. its transpose for the gradient w.r.t. the INPUT (input_grad): rows Q, K = [tap1^T over dx0[t] | tap0^T over dx0[t+1]]
-        w = full(Q, 2 * CH)
-        w[:, :R] = wc[:, :, 1].T
-        w[:, CH:CH + R] = wc[:, :, 0].T
-        bwd.append(("causalT", pack_index(w)))
+        sp, CH, N, dev = self.spec, self.CH, self.N, self.device
+        wn = "dilation_layer_stack.%d.weight"
+        pk = PackSet(sp.total)
+        causal = causal_mats(sp.conv("causal_layer.weight"), CH)
+        pk.fwd("causal", causal.w)
+        pk.bwd("causalT", causal.wT)
         for i in range(N):
-            wf = sp.conv("dilation_layer_stack.%d.weight" % (4 * i))       # [D,R,2]
-            wg = sp.conv("dilation_layer_stack.%d.weight" % (4 * i + 1))
-            wd = sp.conv("dilation_layer_stack.%d.weight" % (4 * i + 2))   # [R,D,1]
-            # 2. fg: rows [f(D) pad CH | g(D) pad CH], K = [tap0 CH | tap1 CH]
-            w = full(2 * CH, 2 * CH)
-            for h, src in enumerate((wf, wg)):
-                w[h * CH:h * CH + D, 0:R] = src[:, :, 0]
-                w[h * CH:h * CH + D, CH:CH + R] = src[:, :, 1]
-            fwd.append(("fg%d" % i, pack_index(w)))
-            gp.append(("fg%d" % i, 2 * CH, 2 * CH))
-            # 3. dense (chained k order: B fragments come from the z accumulators)
-            w = full(CH, CH)
-            w[:R, :D] = wd[:, :, 0]
-            fwd.append(("d%d" % i, pack_index(w, chained=True)))
-            gp.append(("d%d" % i, CH, CH))
-            # 10. Wd^T (rows D, K = R)
-            bwd.append(("dT%d" % i, pack_index(np.ascontiguousarray(w.T))))
-            # 11. data gradient of fg: rows R, K = [W1^T over (df|dg) | W0^T over (df|dg)]
-            w = full(CH, 4 * CH)
-            for h, src in enumerate((wf, wg)):
-                w[:R, h * CH:h * CH + D] = src[:, :, 1].T
-                w[:R, 2 * CH + h * CH:2 * CH + h * CH + D] = src[:, :, 0].T
-            bwd.append(("fgT%d" % i, pack_index(w)))
-            # 11b. the same weights as two UNSHIFTED row blocks for the one-launch backward block (wn_resblock_bwd_pq):
-            #      rows [0,CH) = W1^T (-> P), rows [CH,2CH) = W0^T (-> Q), K = (df | dg)
-            w = full(2 * CH, 2 * CH)
-            for h, src in enumerate((wf, wg)):
-                w[:R, h * CH:h * CH + D] = src[:, :, 1].T
-                w[CH:CH + R, h * CH:h * CH + D] = src[:, :, 0].T
-            bwd.append(("pq%d" % i, pack_index(w)))
+            g = gated_mats(sp.conv(wn % (4 * i)), sp.conv(wn % (4 * i + 1)), sp.conv(wn % (4 * i + 2))[:, :, 0], CH)
+            pk.fwd("fg%d" % i, g.fg)
+            pk.fwd("d%d" % i, g.d, chained=True)
+            pk.bwd("dT%d" % i, g.dT)
+            pk.bwd("fgT%d" % i, g.fgT)
+            pk.bwd("pq%d" % i, g.pq)
             if self.pair_ok:
-                # 12. the same four matrices block-diagonal for two clips side by side (rows / columns of a 32-block: clip A
-                #     then clip B) - what the 64-channel block kernels multiply in pair mode
-                wfg32 = full(2 * CH, 2 * CH)
-                for h, src in enumerate((wf, wg)):
-                    wfg32[h * CH:h * CH + D, 0:R] = src[:, :, 0]
-                    wfg32[h * CH:h * CH + D, CH:CH + R] = src[:, :, 1]
-                wd32 = full(CH, CH)
-                wd32[:R, :D] = wd[:, :, 0]
-                fwd.append(("fg2_%d" % i, pack_index(diag(wfg32, 2, 2))))
-                fwd.append(("d2_%d" % i, pack_index(diag(wd32, 1, 1), chained=True)))
-                bwd.append(("dT2_%d" % i, pack_index(diag(np.ascontiguousarray(wd32.T), 1, 1))))
-                bwd.append(("pq2_%d" % i, pack_index(diag(w, 2, 2))))
-                gp.append(("fg2_%d" % i, 4 * CH, 4 * CH))
-                gp.append(("d2_%d" % i, 2 * CH, 2 * CH))
-        # 4. skip over the concatenated z-crops: rows S, K = N*CH
-        w = full(SP, N * CH)
-        for i in range(N):
-            ws = sp.conv("dilation_layer_stack.%d.weight" % (4 * i + 3))   # [S,D,1]
-            w[:S, i * CH:i * CH + D] = ws[:, :, 0]
-        fwd.append(("skip", pack_index(w)))
-        gp.append(("skip", SP, N * CH))
-        bwd.append(("skipT", pack_index(np.ascontiguousarray(w.T))))      # rows N*CH, K = SP
-        bwd.append(("skipTc", pack_index(np.ascontiguousarray(w.T), chained=True)))     # chained k order: the fused backward epilogue
-        # 5/6. post-process
-        p1 = sp.conv("post_process_1.weight")[:, :, 0]
-        p2 = sp.conv("post_process_2.weight")[:, :, 0]
-        w = full(SP, SP)
-        w[:S, :S] = p1
-        fwd.append(("p1", pack_index(w)))
-        fwd.append(("p1c", pack_index(w, chained=True)))     # chained k order: the fused forward epilogue takes relu(U) out of the accumulators
-        gp.append(("p1", SP, SP))
-        bwd.append(("p1T", pack_index(np.ascontiguousarray(w.T))))
-        bwd.append(("p1Tc", pack_index(np.ascontiguousarray(w.T), chained=True)))
-        w = full(Q, SP)
-        w[:, :S] = p2
-        fwd.append(("p2", pack_index(w)))
-        fwd.append(("p2c", pack_index(w, chained=True)))
-        gp.append(("p2", Q, SP))
-        bwd.append(("p2T", pack_index(np.ascontiguousarray(w.T))))        # rows SP, K = Q
-
-        dev = self.device
-        self.pk_f_off, self.pk_f_idx, self.pk_f = finish(fwd, self.mode_fwd, dev)
-        self.pk_b_off, self.pk_b_idx, self.pk_b = finish(bwd, self.mode_bwd, dev)
-
+                g2 = pair_mats(g)
+                pk.fwd("fg2_%d" % i, g2.fg, pair=True)
+                pk.fwd("d2_%d" % i, g2.d, chained=True, pair=True)
+                pk.bwd("dT2_%d" % i, g2.dT)
+                pk.bwd("pq2_%d" % i, g2.pq)
+        pk.epilogue(epilogue_mats([sp.conv(wn % (4 * i + 3))[:, :, 0] for i in range(N)], sp.conv("post_process_1.weight")[:, :, 0],
+                                  sp.conv("post_process_2.weight")[:, :, 0], CH, self.SP), "skip", "p1", "p2", chained_fwd=True)
+        # the bias gradients: rows of the gradient pack behind the matrices (wn_bias_grad writes them)
+        for name in self.param_names if self.use_bias else ():
+            if name.endswith(".bias"):
+                pk.bias(name, sp.off[name], sp.shape[name][0])
+        self.pk_f_off, self.pk_f_idx, self.pk_f = pk.finish(pk.f, self.mode_fwd, dev)
+        self.pk_b_off, self.pk_b_idx, self.pk_b = pk.finish(pk.b, self.mode_bwd, dev)
         # gradient matrices + gather map (flat parameter element -> offset in gpack)
-        self.gp_off, o = {}, 0
-        for name, r, c in gp:
-            self.gp_off[name] = (o, r, c)
-            o += r * c
-        bias_rows = {}
-        if self.use_bias:
-            for name in self.param_names:
-                if name.endswith(".bias"):
-                    bias_rows[name] = o
-                    o += _pad(self.spec.shape[name][0], 4)
-        self.gp_bias_off = bias_rows
-        self.gpack = torch.zeros(o, dtype=torch.float32, device=dev)
-        gidx = np.full(self.spec.total, -1, dtype=np.int64)
-
-        def put(pname, mat_off):
-            """mat_off: int array with the same shape as the parameter holding gpack offsets."""
-            po = self.spec.off[pname]
-            gidx[po:po + mat_off.size] = mat_off.reshape(-1)
-
-        o0, r, c = self.gp_off["causal"]
-        rows = np.arange(R)[:, None, None]
-        put("causal_layer.weight", o0 + rows * c + (np.arange(2)[None, None, :] * Q + np.arange(Q)[None, :, None]))
-        for i in range(N):
-            o0, r, c = self.gp_off["fg%d" % i]
-            for h in range(2):
-                put("dilation_layer_stack.%d.weight" % (4 * i + h),
-                    o0 + (h * CH + np.arange(D)[:, None, None]) * c +
-                    (np.arange(2)[None, None, :] * CH + np.arange(R)[None, :, None]))
-            o0, r, c = self.gp_off["d%d" % i]
-            put("dilation_layer_stack.%d.weight" % (4 * i + 2),
-                o0 + np.arange(R)[:, None, None] * c + np.arange(D)[None, :, None])
-            o0, r, c = self.gp_off["skip"]
-            put("dilation_layer_stack.%d.weight" % (4 * i + 3),
-                o0 + np.arange(S)[:, None, None] * c + (i * CH + np.arange(D)[None, :, None]))
-        o0, r, c = self.gp_off["p1"]
-        put("post_process_1.weight", o0 + np.arange(S)[:, None, None] * c + np.arange(S)[None, :, None])
-        o0, r, c = self.gp_off["p2"]
-        put("post_process_2.weight", o0 + np.arange(Q)[:, None, None] * c + np.arange(S)[None, :, None])
-        for name, bo in bias_rows.items():
-            put(name, bo + np.arange(self.spec.shape[name][0]))
+        self.gp_off, self.gp_bias_off = pk.gp_off, pk.gp_bias_off
+        self.gpack = torch.zeros(pk.go, dtype=torch.float32, device=dev)
+        gidx, ga, gb = pk.gather_maps()
         assert (gidx >= 0).all()
         self.gidx = torch.from_numpy(gidx.astype(np.int32)).to(dev)
         if self.pair_ok:
             # pair mode: the stack's weight gradients come out of the 64-channel block kernels as block-diagonal matrices -
             # a weight's gradient is the sum of its two copies (wn_gather_grads2); everything else as above
-            ga, gb = gidx.copy(), np.full(self.spec.total, -1, dtype=np.int64)
-
-            def put2(pname, off_a, off_b):
-                po = self.spec.off[pname]
-                ga[po:po + off_a.size] = off_a.reshape(-1)
-                gb[po:po + off_b.size] = off_b.reshape(-1)
-            for i in range(N):
-                o0, r, c = self.gp_off["fg2_%d" % i]
-                for h in range(2):
-                    rows = h * 64 + np.arange(D)[:, None, None]
-                    cols = np.arange(2)[None, None, :] * 64 + np.arange(R)[None, :, None]
-                    put2("dilation_layer_stack.%d.weight" % (4 * i + h), o0 + rows * c + cols, o0 + (rows + 32) * c + cols + 32)
-                o0, r, c = self.gp_off["d2_%d" % i]
-                rows, cols = np.arange(R)[:, None, None], np.arange(D)[None, :, None]
-                put2("dilation_layer_stack.%d.weight" % (4 * i + 2), o0 + rows * c + cols, o0 + (rows + 32) * c + cols + 32)
             self.gidx_pa = torch.from_numpy(ga.astype(np.int32)).to(dev)
             self.gidx_pb = torch.from_numpy(gb.astype(np.int32)).to(dev)
-        # causal weight re-laid as [tap][q][ch] for the forward from codes (wn_causal_fwd_codes): a gather map over the
-        # flat parameter buffer (-1 = padded channel, reads as 0)
-        wt = np.full((2, Q, CH), -1, dtype=np.int64)
-        wt[:, :, :R] = wc.transpose(2, 1, 0)
-        self.wt_idx = torch.from_numpy(wt.reshape(-1).astype(np.int32)).to(dev)
-        self.wt = torch.zeros(2 * Q * CH, dtype=torch.float32, device=dev)
+        self.wt_idx = torch.from_numpy(causal.taps).to(dev)
+        self.wt = torch.zeros(causal.taps.size, dtype=torch.float32, device=dev)
 
     def pack_weights(self):
         st = _lib.stream()
@@ -428,8 +294,7 @@ class WaveNetEngine(EngineBase):
             raise ValueError("wave sample not long enough")          # wavenet/model.py:100-101
         ws = ws or self._ws.get(B, T)
         st = _lib.stream()
-        CH, N, SP, pitch, mf = self.CH, self.N, self.SP, ws["pitch"], self.mode_fwd
-        fr = self._fr
+        CH, pitch, mf = self.CH, ws["pitch"], self.mode_fwd
         self._gen += 1
         ws["gen"] = self._gen
         ws["x_in"] = x
@@ -441,8 +306,7 @@ class WaveNetEngine(EngineBase):
         ws["x_ver"] = None if x is None else x._version
         ws["codes_ver"] = None if ws["x_codes"] is None else ws["x_codes"][0]._version
         # causal conv (wavenet/model.py:104): x0[t] = W0 in[t-1] + W1 in[t], t in [1,T)
-        self.causal_fwd(ws, x, self.wt_idx, self.wt, fr("causal"), self._bias_ptr("causal_layer.bias"), self.R, CH, self._x(ws, 0), st, mf)
-        zb = N * CH * pitch
+        self.causal_fwd(ws, x, self.wt_idx, self.wt, self._fr("causal"), self._bias_ptr("causal_layer.bias"), self.R, CH, self._x(ws, 0), st, mf)
         self.mark("causal_fwd")
         # z: the skip product needs it on the crop [rf-1, T) only, and the two-role / one-launch backward blocks recompute
         # it on the CU.  Only the fallback backward (resblock_bwd_k + wgrad_k: 32 padded channels, x1 modes) reads the
@@ -451,51 +315,7 @@ class WaveNetEngine(EngineBase):
         z_whole = self.z_from_fwd and not ws["ms"] and not ws["pair"]      # (pair: the one-launch backward recomputes z)
         self.stack.forward(B, T, pitch, ws["X"], ws["Z"], z_whole, st, pair=ws["pair_fwd"])
         self.mark("stack_fwd")
-        lo = self.rf - 1
-        bias_s = None
-        if self.use_bias:
-            bs = sum(self.param_view("dilation_layer_stack.%d.bias" % (4 * i + 3)) for i in range(N))
-            ws["bias_skip"] = bs.contiguous()
-            bias_s = ptr(ws["bias_skip"])
-        def chain(b0, nb, s_):
-            """skip product -> post-processing 1 -> 2 for clips b0 .. b0 + nb - 1 on stream s_"""
-            call("wn_chan_gemm", ptr(ws["Z"], SLACK + b0 * zb), None, zb, pitch, lo, T, 0, 0, N * CH // 32, 0, fr("skip"), SP // 16, self.S,
-                 ptr(ws["U"], SLACK + b0 * SP * pitch), SP * pitch, pitch, 0, bias_s, None, 0, 0, 0, None, 0, 0, lo, T, 0, nb, mf, s_)
-            self.fmark("f_skip")
-            call("wn_chan_gemm", ptr(ws["U"], SLACK + b0 * SP * pitch), None, SP * pitch, pitch, lo, T, 0, 0, SP // 32, 0, fr("p1"), SP // 16, self.S,
-                 ptr(ws["H"], SLACK + b0 * SP * pitch), SP * pitch, pitch, 0, self._bias_ptr("post_process_1.bias"),
-                 None, 0, 0, 0, None, 0, 0, lo, T, 1, nb, mf, s_)
-            self.fmark("f_p1")
-            call("wn_chan_gemm", ptr(ws["H"], SLACK + b0 * SP * pitch), None, SP * pitch, pitch, lo, T, 0, 0, SP // 32, 0, fr("p2"), Q // 16, Q,
-                 ptr(ws["O"], b0 * Q * W), Q * W, W, -lo, self._bias_ptr("post_process_2.bias"),
-                 None, 0, 0, 0, None, 0, 0, lo, T, 1, nb, mf, s_)
-        nsplit = min(int(self.epi_chains), B)
-        if self.epi_fused and SP == 256 and Q == 256 and (N * CH // 32) % 2 == 0 and mf in (_lib.F16X3, _lib.BF16X3):
-            # the three products in ONE launch per 128-column tile, U and H handed on chip (wn_skip_epilogue_fwd, ABI v5)
-            call("wn_skip_epilogue_fwd", ptr(ws["Z"], SLACK), zb, pitch, N * CH // 32, fr("skip"), bias_s,
-                 ptr(ws["U"], SLACK), ptr(ws["H"], SLACK), SP * pitch, fr("p1c"), self._bias_ptr("post_process_1.bias"),
-                 fr("p2c"), self._bias_ptr("post_process_2.bias"), ptr(ws["O"]), Q * W, W, self.S, Q, lo, T, B, mf, st)
-        elif nsplit >= 2:
-            # the three products of each part of the clips as a chain of its own, every second chain on the side stream: a
-            # product's half-empty last round of workgroups (408 tiles of 256 columns on 256 CUs) then packs into the other
-            # chain's launches (0.435-0.445 vs 0.466-0.469 ms with two chains)
-            main, side = torch.cuda.current_stream(), self._side_stream()
-            ev = torch.cuda.Event()
-            ev.record(main)
-            side.wait_event(ev)
-            bounds = [B * k // nsplit for k in range(nsplit + 1)]
-            for k in range(nsplit):
-                b0, nb = bounds[k], bounds[k + 1] - bounds[k]
-                if k % 2 == 1:
-                    with torch.cuda.stream(side):
-                        chain(b0, nb, _lib.stream())
-                else:
-                    chain(b0, nb, st)
-            ev2 = torch.cuda.Event()
-            ev2.record(side)
-            main.wait_event(ev2)
-        else:
-            chain(0, B, st)
+        self.epilogue.forward(ws, self.epilogue.skip_bias(ws), st, self.epi_fused, int(self.epi_chains))
         self.mark("epilogue_fwd")
         return ws
 
@@ -514,60 +334,9 @@ class WaveNetEngine(EngineBase):
         """ws['bwd']['dO'] holds d loss / d pre-softmax (B,Q,W).  Fills self.flat_grad."""
         bw = self._bwd_workspace(ws)
         st = _lib.stream()
-        B, T, W, pitch = ws["B"], ws["T"], ws["W"], ws["pitch"]
-        CH, N, SP, Q, mb = self.CH, self.N, self.SP, self.Q, self.mode_bwd
-        br, lo = self._br, self.rf - 1
-        zb, sb = N * CH * pitch, SP * pitch
-        wgrad = lambda name, *args: self.wgrad(bw, B, mb, st, name, *args)
-        wgrad_s = lambda name, *args: self.wgrad_s(bw, B, mb, name, *args)
-        dO, dH, dU, dZ = ptr(bw["dO"]), ptr(bw["dH"], SLACK), ptr(bw["dU"], SLACK), ptr(bw["dZ"], SLACK)
-        U, H, Z = ptr(ws["U"], SLACK), ptr(ws["H"], SLACK), ptr(ws["Z"], SLACK)
-        # weight gradients of the epilogue run on the side stream as soon as their operands exist
-        wgrad_s("p2", dO, Q * W, W, -lo, W, H, None, sb, pitch, 0, 0, pitch, SP // 16, Q // 16, 1, SP, lo, T)
-        self.fmark("b_wgrad_p2")
-        if (self.epi_fused_bwd and SP == 256 and Q == 256 and (N * CH // 16) % 3 == 0 and mb in (_lib.F16X3, _lib.BF16X3)
-                and not self.use_bias):
-            # dH, dU and dZ in ONE launch per 128-column tile (wn_skip_epilogue_bwd, ABI v5); the two weight gradients that read
-            # dH / dU follow on the side stream
-            call("wn_skip_epilogue_bwd", dO, Q * W, W, H, U, sb, pitch, dH, dU, dZ, zb, br("p2T"), br("p1Tc"), br("skipTc"),
-                 N * CH // 16, N * CH, self.S, lo, T, B, mb, st)
-            self.fmark("b_fused")
-            wgrad_s("p1", dH, sb, pitch, 0, pitch, U, None, sb, pitch, 0, 0, pitch, SP // 16, SP // 16, 1, SP, lo, T)
-            # the skip weight gradient on the MAIN stream, beside post_process_1's on the side stream, and the stack starts when both are
-            # done: left to run beside the stack (WN_EPI_BWD_ORDER=0) they stretch every backward-block launch - a block launch wants all
-            # 256 CUs at once - for the same total (bench A/B on one box: 0.95 + 2.0 against 0.52 + 2.6 ms), and the stack's own time
-            # (what `roofline` is computed from) would read 40 % high
-            order = os.environ.get("WN_EPI_BWD_ORDER", "1")
-            if order == "1":
-                wgrad("skip", dU, sb, pitch, 0, pitch, Z, None, zb, pitch, 0, 0, pitch, N * CH // 16, SP // 16, 0, N * CH, lo, T)
-            else:
-                wgrad_s("skip", dU, sb, pitch, 0, pitch, Z, None, zb, pitch, 0, 0, pitch, N * CH // 16, SP // 16, 0, N * CH, lo, T)
-            if order == "1":
-                self.join_side()
-            self.mark("epilogue_bwd")
-            return self._backward_stack(ws, bw, st)
-        # dH = (P2^T dO) * [H > 0]
-        call("wn_chan_gemm", dO, None, Q * W, W, 0, W, -lo, 0, Q // 32, 0, br("p2T"), SP // 16, self.S,
-             dH, sb, pitch, 0, None, None, 0, 0, 0, H, sb, pitch, lo, T, 0, B, mb, st)
-        self.fmark("b_p2T")
-        wgrad_s("p1", dH, sb, pitch, 0, pitch, U, None, sb, pitch, 0, 0, pitch, SP // 16, SP // 16, 1, SP, lo, T)
-        self.fmark("b_wgrad_p1")
-        # dU = (P1^T dH) * [U > 0]
-        call("wn_chan_gemm", dH, None, sb, pitch, lo, T, 0, 0, SP // 32, 0, br("p1T"), SP // 16, self.S,
-             dU, sb, pitch, 0, None, None, 0, 0, 0, U, sb, pitch, lo, T, 0, B, mb, st)
-        self.fmark("b_p1T")
-        wgrad_s("skip", dU, sb, pitch, 0, pitch, Z, None, zb, pitch, 0, 0, pitch, N * CH // 16, SP // 16, 0, N * CH, lo, T)
-        self.fmark("b_wgrad_skip")
-        # dZ = Ws^T dU   (all N crops at once)
-        call("wn_chan_gemm", dU, None, sb, pitch, lo, T, 0, 0, SP // 32, 0, br("skipT"), N * CH // 16, N * CH,
-             dZ, zb, pitch, 0, None, None, 0, 0, 0, None, 0, 0, lo, T, 0, B, mb, st)
-        if self.use_bias:
-            bo = self.gp_bias_off
-            call("wn_bias_grad", dO, Q * W, W, -lo, Q, lo, T, B, ptr(self.gpack, bo["post_process_2.bias"]), st)
-            call("wn_bias_grad", dH, sb, pitch, 0, self.S, lo, T, B, ptr(self.gpack, bo["post_process_1.bias"]), st)
-            for i in range(N):
-                call("wn_bias_grad", dU, sb, pitch, 0, self.S, lo, T, B,
-                     ptr(self.gpack, bo["dilation_layer_stack.%d.bias" % (4 * i + 3)]), st)
+        # (WN_EPI_BWD_ORDER=0: the skip weight gradient beside the stack, on the side stream)
+        self.epilogue.backward(self.epilogue.begin_backward(ws, bw), st, self.epi_fused_bwd and not self.use_bias,
+                               side_skip=os.environ.get("WN_EPI_BWD_ORDER", "1") != "1")
         self.mark("epilogue_bwd")
         return self._backward_stack(ws, bw, st)
 

@@ -29,15 +29,15 @@ import torch.nn.functional as F
 try:
     from . import _lib, _losshook
     from ._lib import call, ptr
-    from .engine import pack_index, pack_positions
     from .engine_base import SLACK, PAD_BACK, EngineBase, SlabPlan, WorkspaceHold, _Spec, _pad
-    from .stack import Cond, GatedStack, diag, enc_resblock_bwd_pq, enc_resblock_fwd, finish, full, hand_over
+    from .packs import PackSet, causal_mats, diag, epilogue_mats, full, gated_mats, pack_positions, pair_mats, transposed
+    from .stack import Cond, EpiBias, GatedStack, SkipEpilogue, enc_resblock_bwd_pq, enc_resblock_fwd, hand_over
 except ImportError:
     from music_amd import _lib, _losshook
     from music_amd._lib import call, ptr
-    from music_amd.engine import pack_index, pack_positions
     from music_amd.engine_base import SLACK, PAD_BACK, EngineBase, SlabPlan, WorkspaceHold, _Spec, _pad
-    from music_amd.stack import Cond, GatedStack, diag, enc_resblock_bwd_pq, enc_resblock_fwd, finish, full, hand_over
+    from music_amd.packs import PackSet, causal_mats, diag, epilogue_mats, full, gated_mats, pack_positions, pair_mats, transposed
+    from music_amd.stack import Cond, EpiBias, GatedStack, SkipEpilogue, enc_resblock_bwd_pq, enc_resblock_fwd, hand_over
 
 
 class _AutoencoderEngine(EngineBase):
@@ -93,6 +93,13 @@ class _AutoencoderEngine(EngineBase):
             return bias_fg + 4 * self.Dd if bias_fg is not None else None, bias_fg, self._bias("de_dilation_layer_stack.%d" % (3 * i + 1))
         # the decoder stack: its weight gradients stay on the main stream, its blocks never chain (conditioned blocks hand the pair on)
         self.decoder = GatedStack(self, "de_", self.CHd, self.Rd, self.Dd, self._fr, self._br, de_bias, self.mode, self.mode_b)
+        # ... and its epilogue: o = c2(relu(r)), r = c1(relu(u)) + cond_f (the expanded final conditioning C1), u = skip(z).  The bias
+        # gradients go to the small buffer of backward()'s _bias_plan, as soon as dR1 and dU exist
+        skips = ["de_dilation_layer_stack.%d" % (3 * i + 2) for i in range(self.N)]
+        bias = EpiBias(skips, "connection_1", "connection_2", self._bias, lambda name: ptr(self._bias_plan[2], self._bias_plan[0][name]),
+                       [self.spec.off[n + ".bias"] for n in skips]) if self.use_bias else None
+        self.epilogue = SkipEpilogue(self, ("skip", "c1", "c2"), ("U", "R1", "C1", "dR1"), self.CHd, self.Sd, self.SP, self._fr, self._br,
+                                     self.mode, self.mode_b, bias=bias, bias_early=True)
 
     def _stage_cond(self, cond):
         """cond (N+1 CPU (weight, bias) pairs) -> device tensors cw (N, 2Dd, Bw), cb (N, 2Dd), cfw (Sd, Bw, 1), cfb (Sd) through one
@@ -134,134 +141,64 @@ class _AutoencoderEngine(EngineBase):
         return ptr(self.pkb, self.pkb_off[name])
 
     def _build_packs(self):
-        sp, Q, N = self.spec, self.Q, self.N
-        CHe, CHd, SP, BwP = self.CHe, self.CHd, self.SP, self.BwP
-        Re, De, Rd, Dd, Sd, Bw = self.Re, self.De, self.Rd, self.Dd, self.Sd, self.Bw
-        fwd, bwd, gp = [], [], []
-        gidx = np.full(self.spec.total, -1, dtype=np.int64)
-        gsize = [0]
-
-        def add(name, w, chained=False, grad=True):
-            """forward pack of the effective matrix w (entries = flat parameter offsets) + its
-            gradient matrix (same shape) + the gather map back to the parameters"""
-            fwd.append((name, pack_index(w, chained)))
-            if grad:
-                o = gsize[0]
-                gp.append((name, o, w.shape[0], w.shape[1]))
-                r, c = np.nonzero(w >= 0)
-                gidx[w[r, c]] = o + r * w.shape[1] + c
-                gsize[0] += w.size
-
-        pa, pb = {}, {}                                      # pair mode: parameter offset -> its two places in a block-diagonal gradient
-
-        def add2(name, w32, rb, cb, chained=False):
-            """pair-mode forward pack + gradient matrix of the block-diagonal form of w32, and where each parameter's two
-            gradient copies sit in it"""
-            fwd.append((name, pack_index(diag(w32, rb, cb), chained)))
-            o, cols = gsize[0], cb * 64
-            gp.append((name, o, rb * 64, cols))
-            r, c = np.nonzero(w32 >= 0)
-            base = o + ((r // 32) * 64 + r % 32) * cols + (c // 32) * 64 + c % 32
-            for par, pos in zip(w32[r, c], base):
-                pa[int(par)], pb[int(par)] = int(pos), int(pos) + 32 * cols + 32
-            gsize[0] += rb * 64 * cols
-
+        sp, N, dev = self.spec, self.N, self.device
+        CHe, CHd, Re, De, Dd, Bw = self.CHe, self.CHd, self.Re, self.De, self.Dd, self.Bw
+        pk = PackSet(sp.total)
         self.wt_idx, self.wt = {}, {}
-        for name, ch, r in (("en_causal", CHe, Re), ("de_causal", CHd, Rd)):
-            wc = sp.conv(name + "_layer.weight")
-            w = full(ch, 2 * Q)
-            w[:r, :Q], w[:r, Q:] = wc[:, :, 0], wc[:, :, 1]
-            add(name, w)
-            wT = full(Q, 2 * ch)                          # its transpose for the gradient w.r.t. the input (input_grad): K = [tap1^T | tap0^T]
-            wT[:, :r], wT[:, ch:ch + r] = wc[:, :, 1].T, wc[:, :, 0].T
-            bwd.append((name + "T", pack_index(wT)))
-            # the same weight as [tap][q][ch] for the forward from codes (wn_causal_fwd_codes), a gather map
-            wt = np.full((2, Q, ch), -1, dtype=np.int64)
-            wt[:, :, :r] = wc.transpose(2, 1, 0)
-            self.wt_idx[name] = torch.from_numpy(wt.reshape(-1).astype(np.int32)).to(self.device)
-            self.wt[name] = torch.zeros(2 * Q * ch, dtype=torch.float32, device=self.device)
+        for name, ch in (("en_causal", CHe), ("de_causal", CHd)):
+            causal = causal_mats(sp.conv(name + "_layer.weight"), ch)
+            pk.fwd(name, causal.w)
+            pk.bwd(name + "T", causal.wT)
+            self.wt_idx[name] = torch.from_numpy(causal.taps).to(dev)
+            self.wt[name] = torch.zeros(causal.taps.size, dtype=torch.float32, device=dev)
+        dn = "de_dilation_layer_stack.%d.weight"
         for i in range(N):
             wd = sp.conv("en_dilation_layer_stack.%d.weight" % i)              # [De,Re,2]
-            w = full(CHe, 2 * CHe)
+            w = pk.fwd("en_dil%d" % i, full(CHe, 2 * CHe))
             w[:De, :Re], w[:De, CHe:CHe + Re] = wd[:, :, 0], wd[:, :, 1]
-            add("en_dil%d" % i, w)
-            wt = full(CHe, 2 * CHe)                                            # dx: rows Re, K = [tap1^T | tap0^T] over De
+            wt = pk.bwd("en_dilT%d" % i, full(CHe, 2 * CHe))                    # dx: rows Re, K = [tap1^T | tap0^T] over De
             wt[:Re, :De], wt[:Re, CHe:CHe + De] = wd[:, :, 1].T, wd[:, :, 0].T
-            bwd.append(("en_dilT%d" % i, pack_index(wt)))
-            wq = full(2 * CHe, CHe)                     # [W1^T; W0^T] over dh: the one-launch backward block of the encoder
-            wq[:CHe], wq[CHe:] = wt[:, :CHe], wt[:, CHe:]
-            bwd.append(("en_pq%d" % i, pack_index(wq)))
+            # [W1^T; W0^T] over dh: the one-launch backward block of the encoder
+            wq = pk.bwd("en_pq%d" % i, np.concatenate([wt[:, :CHe], wt[:, CHe:]]))
             if self.pair_ok:
-                wdil32 = full(CHe, 2 * CHe)
-                wdil32[:De, :Re], wdil32[:De, CHe:CHe + Re] = wd[:, :, 0], wd[:, :, 1]
-                add2("en_dil2_%d" % i, wdil32, 1, 2)
-                bwd.append(("en_pq2_%d" % i, pack_index(diag(wq, 2, 1))))
-            w = full(CHe, CHe)
+                pk.fwd("en_dil2_%d" % i, diag(w, 1, 2), pair=True)
+                pk.bwd("en_pq2_%d" % i, diag(wq, 2, 1))
+            w = pk.fwd("en_dense%d" % i, full(CHe, CHe))
             w[:Re, :De] = sp.conv("en_dense_layer_stack.%d.weight" % i)[:, :, 0]
-            add("en_dense%d" % i, w)
-            fwd.append(("en_dense_c%d" % i, pack_index(w, True)))               # chained k order: the fused encoder block
-            bwd.append(("en_denseT%d" % i, pack_index(np.ascontiguousarray(w.T))))
+            pk.fwd("en_dense_c%d" % i, w, chained=True, grad=False)             # chained k order: the fused encoder block
+            pk.bwd("en_denseT%d" % i, transposed(w))
             if self.pair_ok:
-                add2("en_dense2_%d" % i, w, 1, 1, chained=True)                 # (its pack doubles as "en_dense_c2")
-                bwd.append(("en_denseT2_%d" % i, pack_index(diag(np.ascontiguousarray(w.T), 1, 1))))
-            wfg = sp.conv("de_dilation_layer_stack.%d.weight" % (3 * i))       # [2Dd,Rd,2], gate rows first
-            w = full(2 * CHd, 2 * CHd)
-            wx = full(CHd, 4 * CHd)
-            for h, rows in enumerate((slice(Dd, 2 * Dd), slice(0, Dd))):        # my rows: filter then gate
-                w[h * CHd:h * CHd + Dd, :Rd] = wfg[rows, :, 0]
-                w[h * CHd:h * CHd + Dd, CHd:CHd + Rd] = wfg[rows, :, 1]
-                wx[:Rd, h * CHd:h * CHd + Dd] = wfg[rows, :, 1].T
-                wx[:Rd, 2 * CHd + h * CHd:2 * CHd + h * CHd + Dd] = wfg[rows, :, 0].T
-            add("de_fg%d" % i, w)
-            bwd.append(("de_fgT%d" % i, pack_index(wx)))
-            wq = full(2 * CHd, 2 * CHd)                 # [W1^T; W0^T] over (df | dg): the one-launch backward block
-            wq[:CHd], wq[CHd:] = wx[:, :2 * CHd], wx[:, 2 * CHd:]
-            bwd.append(("de_pq%d" % i, pack_index(wq)))
+                pk.fwd("en_dense2_%d" % i, diag(w, 1, 1), chained=True, pair=True)     # (its pack doubles as "en_dense_c2")
+                pk.bwd("en_denseT2_%d" % i, diag(transposed(w), 1, 1))
+            wfg = sp.conv(dn % (3 * i))                                        # [2Dd,Rd,2], gate rows first: my rows are filter then gate
+            g = gated_mats(wfg[Dd:], wfg[:Dd], sp.conv(dn % (3 * i + 1))[:, :, 0], CHd)
+            g2 = pair_mats(g) if self.pair_ok else None
+            pk.fwd("de_fg%d" % i, g.fg)
+            pk.bwd("de_fgT%d" % i, g.fgT)
+            pk.bwd("de_pq%d" % i, g.pq)
             if self.pair_ok:
-                wfg32 = full(2 * CHd, 2 * CHd)
-                for h, rows in enumerate((slice(Dd, 2 * Dd), slice(0, Dd))):
-                    wfg32[h * CHd:h * CHd + Dd, :Rd] = wfg[rows, :, 0]
-                    wfg32[h * CHd:h * CHd + Dd, CHd:CHd + Rd] = wfg[rows, :, 1]
-                add2("de_fg2_%d" % i, wfg32, 2, 2)
-                bwd.append(("de_pq2_%d" % i, pack_index(diag(wq, 2, 2))))
-            w = full(CHd, CHd)
-            w[:Rd, :Dd] = sp.conv("de_dilation_layer_stack.%d.weight" % (3 * i + 1))[:, :, 0]
-            add("de_d%d" % i, w, chained=True)
-            bwd.append(("de_dT%d" % i, pack_index(np.ascontiguousarray(w.T))))
+                pk.fwd("de_fg2_%d" % i, g2.fg, pair=True)
+                pk.bwd("de_pq2_%d" % i, g2.pq)
+            pk.fwd("de_d%d" % i, g.d, chained=True)
+            pk.bwd("de_dT%d" % i, g.dT)
             if self.pair_ok:
-                add2("de_d2_%d" % i, w, 1, 1, chained=True)
-                bwd.append(("de_dT2_%d" % i, pack_index(diag(np.ascontiguousarray(w.T), 1, 1))))
-        w = full(BwP, CHe)
+                pk.fwd("de_d2_%d" % i, g2.d, chained=True, pair=True)
+                pk.bwd("de_dT2_%d" % i, g2.dT)
+        w = pk.fwd("bottleneck", full(self.BwP, CHe))
         w[:Bw, :Re] = sp.conv("bottleneck_layer.weight")[:, :, 0]
-        add("bottleneck", w)
-        bwd.append(("bottleneckT", pack_index(np.ascontiguousarray(w.T))))
-        w = full(SP, N * CHd)
-        for i in range(N):
-            w[:Sd, i * CHd:i * CHd + Dd] = sp.conv("de_dilation_layer_stack.%d.weight" % (3 * i + 2))[:, :, 0]
-        add("skip", w)
-        bwd.append(("skipT", pack_index(np.ascontiguousarray(w.T))))
-        bwd.append(("skipTc", pack_index(np.ascontiguousarray(w.T), chained=True)))     # chained k order: wn_skip_epilogue_bwd
-        w = full(SP, SP)
-        w[:Sd, :Sd] = sp.conv("connection_1.weight")[:, :, 0]
-        add("c1", w)
-        bwd.append(("c1T", pack_index(np.ascontiguousarray(w.T))))
-        bwd.append(("c1Tc", pack_index(np.ascontiguousarray(w.T), chained=True)))
-        w = full(Q, SP)
-        w[:, :Sd] = sp.conv("connection_2.weight")[:, :, 0]
-        add("c2", w)
-        bwd.append(("c2T", pack_index(np.ascontiguousarray(w.T))))
-
-        self.pk_off, self.pk_idx, self.pk = finish(fwd, self.mode, self.device)
-        self.pkb_off, self.pkb_idx, self.pkb = finish(bwd, self.mode_b, self.device)
-        self.gp_off = {name: (o, r, c) for name, o, r, c in gp}
-        self.gpack = torch.zeros(gsize[0], dtype=torch.float32, device=self.device)
-        self.gidx = torch.from_numpy(gidx.astype(np.int32)).to(self.device)   # -1 (biases) -> zero gradient
+        pk.bwd("bottleneckT", transposed(w))
+        # (no chained forward forms: the decoder's forward epilogue is the three products)
+        pk.epilogue(epilogue_mats([sp.conv(dn % (3 * i + 2))[:, :, 0] for i in range(N)], sp.conv("connection_1.weight")[:, :, 0],
+                                  sp.conv("connection_2.weight")[:, :, 0], CHd, self.SP), "skip", "c1", "c2", chained_fwd=False)
+        self.pk_off, self.pk_idx, self.pk = pk.finish(pk.f, self.mode, dev)
+        self.pkb_off, self.pkb_idx, self.pkb = pk.finish(pk.b, self.mode_b, dev)
+        self.gp_off = pk.gp_off
+        self.gpack = torch.zeros(pk.go, dtype=torch.float32, device=dev)
+        gidx, ga, gb = pk.gather_maps()
+        self.gidx = torch.from_numpy(gidx.astype(np.int32)).to(dev)          # -1 (biases) -> zero gradient
         if self.pair_ok:                                  # pair mode: a stack weight's gradient = the sum of its two copies
-            ga, gb = gidx.copy(), np.full(self.spec.total, -1, dtype=np.int64)
-            for par, pos in pa.items():
-                ga[par], gb[par] = pos, pb[par]
-            self.gidx_pa = torch.from_numpy(ga.astype(np.int32)).to(self.device)
-            self.gidx_pb = torch.from_numpy(gb.astype(np.int32)).to(self.device)
+            self.gidx_pa = torch.from_numpy(ga.astype(np.int32)).to(dev)
+            self.gidx_pb = torch.from_numpy(gb.astype(np.int32)).to(dev)
 
     def _make_workspace(self, B, T):
         dev = self.device
@@ -357,10 +294,8 @@ class _AutoencoderEngine(EngineBase):
 
         # ---------------- decoder (model1.py:158-225)
         xd = lambda i: self._lay(ws["Xd"], i, CHd, ws)
-        zb = N * CHd * pitch
         causal("de_causal", CHd, self.Rd, xd(0))
         self.mark("bottleneck_cond_de_causal")
-        bn = "de_dilation_layer_stack.%d"
         cmodes = []
         for i in range(N):
             L = T - self.off[i + 1]
@@ -402,47 +337,15 @@ class _AutoencoderEngine(EngineBase):
         # z on the whole valid range: the backward's dWd reads it
         self.decoder.forward(B, T, pitch, ws["Xd"], ws["Z"], True, st, cond=cond_f, pair=pair_f)
         self.mark("dec_stack_fwd")
-        U, R1, C1 = ptr(ws["U"], SLACK), ptr(ws["R1"], SLACK), ptr(ws["C1"], SLACK)
-        sb = SP * pitch
-        bias_s = None
-        if self.use_bias:
-            o = self.spec.off
-            bsum = sum(self.flat[o[bn % (3 * i + 2) + ".bias"]:o[bn % (3 * i + 2) + ".bias"] + Sd] for i in range(N)).contiguous()
-            ws["bias_skip"] = bsum
-            bias_s = ptr(bsum)
+        bias_s = self.epilogue.skip_bias(ws)
         # final conditioning expanded over time (stretch / tile rule on the length-W sequence)
         ws["cf_mode"] = (1, W // Le) if W % Le == 0 else (2, 0)
         if not self.learned:
             enf = enf.contiguous()
-        call("wn_cond_expand", ptr(enf), Sd * Le, Le, Sd, lo, T, ws["cf_mode"][0], Le, max(ws["cf_mode"][1], 1), C1, sb, pitch, B, st)
-
-        def chain(b0, nb, s_):
-            """skip product -> connection_1 (+ conditioning) -> connection_2 for clips b0 .. b0 + nb - 1 on stream s_"""
-            g_ = lambda pack, *a: self._gemm(s_, nb, m, fr(pack), *a)
-            o = b0 * sb
-            g_("skip", ptr(ws["Z"], SLACK + b0 * zb), None, zb, pitch, lo, T, 0, 0, N * CHd // 32, 0, SP // 16, Sd,
-               ptr(ws["U"], SLACK + o), sb, pitch, 0, bias_s, NONE3, NONE3, lo, T, 0)
-            g_("c1", ptr(ws["U"], SLACK + o), None, sb, pitch, lo, T, 0, 0, SP // 32, 0, SP // 16, Sd,
-               ptr(ws["R1"], SLACK + o), sb, pitch, 0, self._bias("connection_1"), (ptr(ws["C1"], SLACK + o), sb, pitch, lo), NONE3, lo, T, 1)
-            g_("c2", ptr(ws["R1"], SLACK + o), None, sb, pitch, lo, T, 0, 0, SP // 32, 0, Q // 16, Q,
-               ptr(ws["O"], b0 * Q * W), Q * W, W, -lo, self._bias("connection_2"), NONE3, NONE3, lo, T, 1)
-        # two per-clip-group chains, the second on the side stream: a product's half-empty last round of workgroups packs into
-        # the other chain's launches (music_amd/engine.py epi_chains; bit-identical results)
-        nsplit = min(2, B)
-        if nsplit >= 2 and self.overlap_wgrad:
-            main, side = torch.cuda.current_stream(), self._side_stream()
-            ev = torch.cuda.Event()
-            ev.record(main)
-            side.wait_event(ev)
-            half = B // 2
-            chain(0, half, st)
-            with torch.cuda.stream(side):
-                chain(half, B - half, _lib.stream())
-            ev2 = torch.cuda.Event()
-            ev2.record(side)
-            main.wait_event(ev2)
-        else:
-            chain(0, B, st)
+        call("wn_cond_expand", ptr(enf), Sd * Le, Le, Sd, lo, T, ws["cf_mode"][0], Le, max(ws["cf_mode"][1], 1), ptr(ws["C1"], SLACK),
+             SP * pitch, pitch, B, st)
+        # two per-clip-group chains, the second on the side stream (stack.SkipEpilogue.forward), where the side stream is in use
+        self.epilogue.forward(ws, bias_s, st, False, 2 if self.overlap_wgrad else 1)
         probs = None
         if want_probs:
             probs = torch.empty(B * W, Q, dtype=torch.float32, device=self.device)
@@ -561,7 +464,7 @@ class _AutoencoderEngine(EngineBase):
             def bias_grad(*a, **k):
                 pass
         B, T, W, pitch, Le = ws["B"], ws["T"], ws["W"], ws["pitch"], ws["Le"]
-        N, CHe, CHd, SP, BwP, Q = self.N, self.CHe, self.CHd, self.SP, self.BwP, self.Q
+        N, CHe, CHd, SP, BwP = self.N, self.CHe, self.CHd, self.SP, self.BwP
         Dd, Sd, Rd, Re, De, Bw = self.Dd, self.Sd, self.Rd, self.Re, self.De, self.Bw
         mb, lo = self.mode_b, self.rf - 1
         call("wn_pack_weights", ptr(self.flat), ptr(self.pkb_idx), ptr(self.pkb), self.pkb_idx.numel(), mb, st)
@@ -569,47 +472,19 @@ class _AutoencoderEngine(EngineBase):
         NONE3 = (None, 0, 0)
         gemm = lambda pack, *a: self._gemm(st, B, mb, br(pack), *a)
         plan = bw["plan"]
-        # the decoder epilogue's three weight gradients only feed the slab reduction at the very end: on the side stream their
-        # half-empty last rounds of workgroups pack into the data-gradient GEMMs beside them, as in music_amd/engine.py
-        # (config 4: 1.30 -> ~1.0 ms for this phase)
         wgrad = lambda name, *args: self.wgrad(bw, B, mb, st, name, *args)
-        wgrad_s = lambda name, *args: self.wgrad_s(bw, B, mb, name, *args)
         if dprobs is not None:
             dprobs = dprobs.contiguous()
             call("wn_chunk_softmax256_bwd", ptr(ws["probs"]), ptr(dprobs), ptr(bw["dO"]), B * W, st)
-        dO, dR1, dU, dZ = ptr(bw["dO"]), ptr(bw["dR1"], SLACK), ptr(bw["dU"], SLACK), ptr(bw["dZ"], SLACK)
-        U, R1, Z = ptr(ws["U"], SLACK), ptr(ws["R1"], SLACK), ptr(ws["Z"], SLACK)
-        sb, db, zb, eb = SP * pitch, CHd * pitch, N * CHd * pitch, CHe * pitch
-        # ---- decoder epilogue: o = c2(relu(r)), r = c1(relu(u)) + cond_f, u = skip(z)
-        wgrad_s("c2", dO, Q * W, W, -lo, W, R1, None, sb, pitch, 0, 0, pitch, SP // 16, Q // 16, 1, SP, lo, T)
+        sb, db, eb = SP * pitch, CHd * pitch, CHe * pitch
+        # ---- decoder epilogue (its three weight gradients on the side stream as in music_amd/engine.py: config 4, 1.30 -> ~1.0 ms
+        # for this phase); in the fused form connection_1's weight gradient runs on the side stream, the skip convs' on the main
+        # stream, and the stack starts behind both
+        epi = self.epilogue.begin_backward(ws, bw)
         cmode, cq = ws["cf_mode"]
         d_enf = torch.zeros(B, Sd, Le, dtype=torch.float32, device=self.device)
-        fused = (os.environ.get("WN_EPI_FUSED_BWD", "1") == "1" and SP == 256 and Q == 256 and (N * CHd // 16) % 3 == 0
-                 and mb in (_lib.F16X3, _lib.BF16X3))
-        if fused:
-            # dR1, dU and dZ in ONE launch per 128-column tile (wn_skip_epilogue_bwd, music_amd/engine.py); the weight gradients that read
-            # dR1 / dU follow - connection_1's on the side stream, the skip convs' on the main stream - and the stack starts behind both
-            call("wn_skip_epilogue_bwd", dO, Q * W, W, R1, U, sb, pitch, dR1, dU, dZ, zb, br("c2T"), br("c1Tc"), br("skipTc"),
-                 N * CHd // 16, N * CHd, Sd, lo, T, B, mb, st)
-            call("wn_cond_grad", dR1, sb, pitch, Sd, lo, T, cmode, Le, max(cq, 1), ptr(d_enf), Sd * Le, Le, B, st)
-            wgrad_s("c1", dR1, sb, pitch, 0, pitch, U, None, sb, pitch, 0, 0, pitch, SP // 16, SP // 16, 1, SP, lo, T)
-            wgrad("skip", dU, sb, pitch, 0, pitch, Z, None, zb, pitch, 0, 0, pitch, N * CHd // 16, SP // 16, 0, N * CHd, lo, T)
-            self.join_side()
-        else:
-            gemm("c2T", dO, None, Q * W, W, 0, W, -lo, 0, Q // 32, 0, SP // 16, Sd, dR1, sb, pitch, 0, None, NONE3,
-                 (R1, sb, pitch), lo, T, 0)
-            call("wn_cond_grad", dR1, sb, pitch, Sd, lo, T, cmode, Le, max(cq, 1), ptr(d_enf), Sd * Le, Le, B, st)
-            wgrad_s("c1", dR1, sb, pitch, 0, pitch, U, None, sb, pitch, 0, 0, pitch, SP // 16, SP // 16, 1, SP, lo, T)
-            gemm("c1T", dR1, None, sb, pitch, lo, T, 0, 0, SP // 32, 0, SP // 16, Sd, dU, sb, pitch, 0, None, NONE3,
-                 (U, sb, pitch), lo, T, 0)
-        bias_grad("connection_2", dO, Q * W, W, -lo, Q, lo, T)
-        bias_grad("connection_1", dR1, sb, pitch, 0, Sd, lo, T)
-        for i in range(N if self.use_bias else 0):
-            bias_grad("de_dilation_layer_stack.%d" % (3 * i + 2), dU, sb, pitch, 0, Sd, lo, T)
-        if not fused:
-            wgrad_s("skip", dU, sb, pitch, 0, pitch, Z, None, zb, pitch, 0, 0, pitch, N * CHd // 16, SP // 16, 0, N * CHd, lo, T)
-            gemm("skipT", dU, None, sb, pitch, lo, T, 0, 0, SP // 32, 0, N * CHd // 16, N * CHd, dZ, zb, pitch, 0, None, NONE3,
-                 NONE3, lo, T, 0)
+        self.epilogue.backward(epi, st, os.environ.get("WN_EPI_FUSED_BWD", "1") == "1", after_dh=lambda: call(
+            "wn_cond_grad", epi.dH, sb, pitch, Sd, lo, T, cmode, Le, max(cq, 1), ptr(d_enf), Sd * Le, Le, B, st))
         self.mark("ce_epilogue_bwd")
         # ---- decoder stack
         d_tab = torch.zeros(N, B, 2 * CHd, Le, dtype=torch.float32, device=self.device)

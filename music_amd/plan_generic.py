@@ -5,7 +5,8 @@ wavenet/model.py:104-144), so both plans are sequences of the same few layers, o
 
     GeneralPlan   the host side every general plan has on top of engine_base.EngineBase: geometry of a k-tap dilated stack (`k`,
                   `rf`, `off`, `pairs`), weight packing, workspaces and their slab plan, the padded input copy, the chunk softmax by Q
-    PackBuilder   flat-parameter offsets -> forward packs, transposed backward packs, gradient matrices and the gather map
+    PackBuilder   places the weights' flat-parameter offsets into the matrices of a packs.PackSet (forward packs, transposed
+                  backward packs, gradient matrices; the gather map is derived from them)
     Pass          the launches of ONE forward or backward pass: k-tap conv, gated block, epilogue, each forward and backward,
                   with an optional conditioning table (None = the WaveNet plan)
 
@@ -17,80 +18,50 @@ import torch
 
 from . import _lib
 from ._lib import call, ptr
-from .engine import pack_index
 from .engine_base import SLACK, PAD_BACK, EngineBase, SlabPlan, _pad
+from .packs import PackSet, transposed
 
 NONE4, NONE3 = (None, 0, 0, 0), (None, 0, 0)
 
 
-class PackBuilder:
-    """Collects the weight matrices of a plan as arrays of flat-parameter offsets (-1 = zero): `fwd` / `bwd` hold the packs in
-    launch-pack order, `gp_off` the gradient matrices wn_wgrad writes (same layout as the forward pack of that name), `gidx`
-    where in those every parameter's gradient is found.  Several weights may share one matrix (same tag, different rows)."""
+class PackBuilder(PackSet):
+    """The weight matrices of a general plan (packs.PackSet: forward packs, transposed backward packs, gradient matrices, gather map),
+    placed weight by weight.  Several weights may share one matrix (same tag, different rows)."""
 
     def __init__(self, spec, k, pairs):
+        super().__init__(spec.total)
         self.sp, self.k, self.pairs = spec, k, pairs
-        self.fwd, self.bwd, self.gp_off, self.gp_bias_off = {}, {}, {}, {}
-        self.gidx = np.full(spec.total, -1, dtype=np.int64)
-        self.go = 0                                          # running offset into the gradient pack
-
-    @staticmethod
-    def _full(packs, name, m, kk):
-        return packs.setdefault(name, np.full((m, kk), -1, dtype=np.int64))
-
-    def _add_gp(self, name, rows, cols):
-        if name not in self.gp_off:
-            self.gp_off[name] = (self.go, rows, cols)
-            self.go += rows * cols
-        return self.gp_off[name][0]
-
-    def _put(self, pname, mat_off):
-        po = self.sp.off[pname]
-        self.gidx[po:po + mat_off.size] = mat_off.reshape(-1)
 
     def conv_k(self, pname, tag, rows, rows_p, cols, cols_p, row_map=None, tagT=None):
-        """A k-tap conv weight [rows][cols][k] as per-pair forward packs "<tag>_<p>" (rows_p x taps * cols_p), their transposes
-        "<tagT>_<p>" (cols_p x taps * rows_p; tagT defaults to <tag>T) and the gradient map of every tap.  row_map: pack row
-        of weight row r (a second weight with the same tag and other rows lands in the same matrices)."""
+        """A k-tap conv weight [rows][cols][k] as per-pair forward packs "<tag>_<p>" (rows_p x taps * cols_p) and their transposes
+        "<tagT>_<p>" (cols_p x taps * rows_p; tagT defaults to <tag>T).  row_map: pack row of weight row r (a second weight with
+        the same tag and other rows lands in the same matrices)."""
         w3 = self.sp.conv(pname)
         rm = np.arange(rows) if row_map is None else row_map
-        gm = np.zeros((rows, cols, self.k), dtype=np.int64)
         for p, pair in enumerate(self.pairs):
             tp = [j for j in pair if j is not None]
-            name = "%s_%d" % (tag, p)
-            w = self._full(self.fwd, name, rows_p, len(tp) * cols_p)
-            wt = self._full(self.bwd, "%s_%d" % (tagT or tag + "T", p), cols_p, len(tp) * rows_p)
-            o0 = self._add_gp(name, rows_p, len(tp) * cols_p)
+            w = self.matrix(self.f, "%s_%d" % (tag, p), rows_p, len(tp) * cols_p)
+            wt = self.matrix(self.b, "%s_%d" % (tagT or tag + "T", p), cols_p, len(tp) * rows_p)
             for tl, j in enumerate(tp):
                 w[rm, tl * cols_p:tl * cols_p + cols] = w3[:, :, j]
                 wt[:cols, tl * rows_p + rm] = w3[:, :, j].T
-                gm[:, :, j] = o0 + rm[:, None] * (len(tp) * cols_p) + tl * cols_p + np.arange(cols)[None, :]
-        self._put(pname, gm)
 
     def stacked_1x1(self, pnames, tag, rows, rows_p, cols, cols_p, tagT=None):
         """1x1 conv weights [rows][cols][1] side by side on the K axis of one forward pack "<tag>" (rows_p x len(pnames) * cols_p)
         and its transpose "<tagT>": the skip convs of all blocks are one product."""
-        n = len(pnames)
-        w = self._full(self.fwd, tag, rows_p, n * cols_p)
-        o0 = self._add_gp(tag, rows_p, n * cols_p)
+        w = self.matrix(self.f, tag, rows_p, len(pnames) * cols_p)
         for i, pname in enumerate(pnames):
             w[:rows, i * cols_p:i * cols_p + cols] = self.sp.conv(pname)[:, :, 0]
-            self._put(pname, o0 + np.arange(rows)[:, None] * (n * cols_p) + i * cols_p + np.arange(cols)[None, :])
-        self.bwd[tagT or tag + "T"] = np.ascontiguousarray(w.T)
+        self.bwd(tagT or tag + "T", transposed(w))
 
     def conv_1(self, pname, tag, rows, rows_p, cols, cols_p, tagT=None):
         self.stacked_1x1([pname], tag, rows, rows_p, cols, cols_p, tagT)
 
     def bias_rows(self, names, row_maps):
-        """Rows of the gradient pack for every bias in `names` (padded to 4).  row_maps[name] = (gradient row of bias row r,
-        rows reserved): a bias whose gradient wn_bias_grad writes in another row order than the parameter's."""
+        """Rows of the gradient pack for every bias in `names`.  row_maps[name] = (gradient row of bias row r, rows reserved): a bias
+        whose gradient wn_bias_grad writes in another row order than the parameter's."""
         for name in names:
-            self.gp_bias_off[name] = self.go
-            rm, n = row_maps.get(name, (None, 0))
-            if rm is None:
-                rm, n = np.arange(self.sp.shape[name][0]), _pad(self.sp.shape[name][0], 4)
-            self._put(name, self.go + rm)
-            self.go += n
+            self.bias(name, self.sp.off[name], self.sp.shape[name][0], *row_maps.get(name, ()))
 
     def gather_rows(self, layers, rows_p):
         """Gather map flat buffer -> one padded column of rows_p rows per layer; layers[i] = [(bias name, pack row of its row r)]."""
@@ -99,17 +70,6 @@ class PackBuilder:
             for name, rm in lst:
                 bi[i, rm] = self.sp.off[name] + np.arange(len(rm))
         return bi.reshape(-1).astype(np.int32)
-
-    def finish(self, packs, mode, dev):
-        """(offset of every pack in halfs, the gather map of all of them, the packed buffer) for one direction."""
-        hpf = 1024 if mode in (_lib.F16X3, _lib.BF16X3) else 512
-        offs, idx, o = {}, [], 0
-        for name, w in packs.items():
-            offs[name] = o * hpf // 512
-            idx.append(pack_index(w))
-            o += len(idx[-1])
-        idx_all = torch.from_numpy(np.concatenate(idx).astype(np.int32)).to(dev)
-        return offs, idx_all, torch.zeros(o * hpf // 512, dtype=torch.int16, device=dev)
 
 
 class GeneralPlan(EngineBase):
@@ -140,13 +100,14 @@ class GeneralPlan(EngineBase):
     def _finish_packs(self, pb, gate_bias, gate_rows_p):
         """pb: the plan's PackBuilder, every weight and bias placed.  gate_bias: per block, the biases of the [f | g] product as
         [(name, pack row of bias row r)] - gathered into `bfg` in the product's padded row order by pack_weights()."""
-        assert (pb.gidx[:self.n_gather] >= 0).all()          # (learned conditioning projections: wn_cond_proj_bwd writes theirs)
+        gidx = pb.gather_maps()[0]
+        assert (gidx[:self.n_gather] >= 0).all()             # (learned conditioning projections: wn_cond_proj_bwd writes theirs)
         dev = self.device
         self.gp_off, self.gp_bias_off = pb.gp_off, pb.gp_bias_off
         self.gpack = torch.zeros(pb.go, dtype=torch.float32, device=dev)
-        self.gidx = torch.from_numpy(pb.gidx.astype(np.int32)).to(dev)
-        self.pk_f_off, self.pk_f_idx, self.pk_f = pb.finish(pb.fwd, self.mode_fwd, dev)
-        self.pk_b_off, self.pk_b_idx, self.pk_b = pb.finish(pb.bwd, self.mode_bwd, dev)
+        self.gidx = torch.from_numpy(gidx.astype(np.int32)).to(dev)
+        self.pk_f_off, self.pk_f_idx, self.pk_f = pb.finish(pb.f, self.mode_fwd, dev)
+        self.pk_b_off, self.pk_b_idx, self.pk_b = pb.finish(pb.b, self.mode_bwd, dev)
         if self.use_bias:
             self.bfg_idx = torch.from_numpy(pb.gather_rows(gate_bias, gate_rows_p)).to(dev)
             self.bfg = torch.zeros(self.N * gate_rows_p, dtype=torch.float32, device=dev)

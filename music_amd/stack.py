@@ -1,5 +1,5 @@
-"""The gated residual stack of the two fast engines (engine.WaveNetEngine, the decoder of model1._AutoencoderEngine) on the block
-kernels, the autoencoder's encoder block calls, and the weight-pack helpers of both _build_packs.
+"""The gated residual stack and the skip epilogue of the two fast engines (engine.WaveNetEngine, the decoder of
+model1._AutoencoderEngine) on the block and epilogue kernels, and the autoencoder's encoder block calls.
 
 Every block entry point has ONE writer here: the only place its positional argument list is composed.  "No conditioning" is the
 default of one argument (`Cond`); "pair" is one flag: two clips side by side as one 64-row tensor on the 64-channel kernels -
@@ -9,41 +9,11 @@ PyTorch is used for device memory and streams only.  Nothing here imports oracle
 """
 from collections import namedtuple
 
-import numpy as np
 import torch
 
 from . import _lib
 from ._lib import call, ptr
 from .engine_base import SLACK
-
-
-# ---------------------------------------------------------------------- weight packs
-def full(m, k):
-    """An [m][k] map of flat-parameter offsets, all -1 (= zero)"""
-    return np.full((m, k), -1, dtype=np.int64)
-
-
-def diag(m32, rb, cb):
-    """m32: [rb*32][cb*32] blocks of 32 x 32 -> [rb*64][cb*64] with every block doubled on the diagonal (clip A, clip B): what the
-    64-channel block kernels multiply in pair mode"""
-    out = full(rb * 64, cb * 64)
-    for a_ in range(rb):
-        for b_ in range(cb):
-            blk = m32[a_ * 32:(a_ + 1) * 32, b_ * 32:(b_ + 1) * 32]
-            for c_ in range(2):
-                out[a_ * 64 + c_ * 32:a_ * 64 + (c_ + 1) * 32, b_ * 64 + c_ * 32:b_ * 64 + (c_ + 1) * 32] = blk
-    return out
-
-
-def finish(lst, mode, device):
-    """[(name, idx array)] -> (offset of every pack in halfs of the packed buffer, all index maps as one tensor, the packed buffer)"""
-    halfs_per_frag = 1024 if mode in (_lib.F16X3, _lib.BF16X3) else 512
-    offs, o = {}, 0
-    for name, idx in lst:
-        offs[name] = o * halfs_per_frag // 512
-        o += len(idx)
-    idx_all = torch.from_numpy(np.concatenate([i for _, i in lst]).astype(np.int32)).to(device)
-    return offs, idx_all, torch.zeros(o * halfs_per_frag // 512, dtype=torch.int16, device=device)
 
 
 # ---------------------------------------------------------------------- the (P, Q) hand-over of the one-launch blocks
@@ -225,3 +195,179 @@ class GatedStack:
         for e in ev_w:
             if e is not None:
                 main.wait_event(e)
+
+
+# ---------------------------------------------------------------------- the skip epilogue
+# What the engine's bias=True adds to an epilogue: the names of the N skip biases and of the two products' (the engine's own), src:
+# name -> pointer of the bias in the flat buffer, dst: name -> where wn_bias_grad leaves its gradient, and the flat-buffer offsets
+# of the skip biases (their sum is the skip product's bias)
+EpiBias = namedtuple("EpiBias", "skips b1 b2 src dst skip_offs")
+# One backward pass: the shape, the clip strides of the S-row and of the z tensors, and every pointer
+_EpiBwd = namedtuple("_EpiBwd", "bw B T W pitch sb zb dO dH dU dZ U H Z")
+
+
+class SkipEpilogue:
+    """u = sum_i Ws_i z_i;  h = W1 relu(u) (+ c);  o = W2 relu(h), written compact (B, Q, W) - on the crop [rf - 1, T), forward and
+    backward, in one launch each where the fused kernels apply (256 skip / 256 quantisation channels, x3 modes, whole tile groups of
+    the skip product's K / rows), else in three.  What differs between its users is handed in: `eng` (an EngineBase: side stream,
+    wgrad), the names of the three packs (= gradient matrices = slab ops; "<name>T", "<name>c", "<name>Tc": packs.PackSet.epilogue),
+    `keys` = the workspace keys of u, h and of c (the residual of the second product, None: none) and the backward workspace's key of
+    dh, the channel counts, `fr` / `br` (pack name -> pointer), `bias` (an EpiBias, None without biases), `fmark` (fine timing
+    marks), and where the bias gradients go in the three-launch backward (bias_early: as soon as dh and du exist, else last)."""
+
+    def __init__(self, eng, names, keys, CH, S, SP, fr, br, mode_f, mode_b, bias=None, fmark=lambda name: None, bias_early=False):
+        self.eng, self.names, self.keys, self.CH, self.S, self.SP, self.fr, self.br = eng, names, keys, CH, S, SP, fr, br
+        self.mode_f, self.mode_b, self.bias, self.fmark, self.bias_early = mode_f, mode_b, bias, fmark, bias_early
+        self.N, self.Q, self.lo, self.K = eng.N, eng.Q, eng.rf - 1, eng.N * CH
+        x3 = (_lib.F16X3, _lib.BF16X3)
+        self.fused_fwd_ok = SP == 256 and self.Q == 256 and (self.K // 32) % 2 == 0 and mode_f in x3 and keys[2] is None
+        self.fused_bwd_ok = SP == 256 and self.Q == 256 and (self.K // 16) % 3 == 0 and mode_b in x3
+
+    # ------------------------------------------------------------------ one writer per entry point
+    def fused_fwd(self, ws, bias_s, st):
+        """the three products in ONE launch per 128-column tile, U and H handed on chip (wn_skip_epilogue_fwd, ABI v5)"""
+        (skip, p1, p2), (kU, kH, _, _), b, pitch, W, Q = self.names, self.keys, self.bias, ws["pitch"], ws["W"], self.Q
+        call("wn_skip_epilogue_fwd", ptr(ws["Z"], SLACK), self.K * pitch, pitch, self.K // 32, self.fr(skip), bias_s,
+             ptr(ws[kU], SLACK), ptr(ws[kH], SLACK), self.SP * pitch, self.fr(p1 + "c"), b.src(b.b1) if b else None,
+             self.fr(p2 + "c"), b.src(b.b2) if b else None, ptr(ws["O"]), Q * W, W, self.S, Q, self.lo, ws["T"], ws["B"], self.mode_f, st)
+
+    def products_fwd(self, ws, bias_s, b0, nb, s_):
+        """skip product -> second product (+ c) -> third product for clips b0 .. b0 + nb - 1 on stream s_"""
+        (skip, p1, p2), (kU, kH, kC, _), b, fr = self.names, self.keys, self.bias, self.fr
+        pitch, T, W, lo, SP, S, Q, K, mf = ws["pitch"], ws["T"], ws["W"], self.lo, self.SP, self.S, self.Q, self.K, self.mode_f
+        sb, zb = SP * pitch, K * pitch
+        U, H = ptr(ws[kU], SLACK + b0 * sb), ptr(ws[kH], SLACK + b0 * sb)
+        call("wn_chan_gemm", ptr(ws["Z"], SLACK + b0 * zb), None, zb, pitch, lo, T, 0, 0, K // 32, 0, fr(skip), SP // 16, S,
+             U, sb, pitch, 0, bias_s, None, 0, 0, 0, None, 0, 0, lo, T, 0, nb, mf, s_)
+        self.fmark("f_skip")
+        call("wn_chan_gemm", U, None, sb, pitch, lo, T, 0, 0, SP // 32, 0, fr(p1), SP // 16, S, H, sb, pitch, 0, b.src(b.b1) if b else None,
+             *((ptr(ws[kC], SLACK + b0 * sb), sb, pitch, lo) if kC else (None, 0, 0, 0)), None, 0, 0, lo, T, 1, nb, mf, s_)
+        self.fmark("f_p1")
+        call("wn_chan_gemm", H, None, sb, pitch, lo, T, 0, 0, SP // 32, 0, fr(p2), Q // 16, Q, ptr(ws["O"], b0 * Q * W), Q * W, W, -lo,
+             b.src(b.b2) if b else None, None, 0, 0, 0, None, 0, 0, lo, T, 1, nb, mf, s_)
+
+    def fused_bwd(self, a, st):
+        """dH, dU and dZ in ONE launch per 128-column tile (wn_skip_epilogue_bwd, ABI v5)"""
+        skip, p1, p2 = self.names
+        call("wn_skip_epilogue_bwd", a.dO, self.Q * a.W, a.W, a.H, a.U, a.sb, a.pitch, a.dH, a.dU, a.dZ, a.zb, self.br(p2 + "T"),
+             self.br(p1 + "Tc"), self.br(skip + "Tc"), self.K // 16, self.K, self.S, self.lo, a.T, a.B, self.mode_b, st)
+
+    def wgrad(self, k, a, st):
+        """Weight gradient of product k (0: the skip convs', from dU and Z; 1: from dH and relu(U); 2: from dO and relu(H)) on stream
+        st; None: on the side stream, as soon as its operands exist"""
+        SP, Q, K, lo, pitch = self.SP, self.Q, self.K, self.lo, a.pitch
+        args = ((a.dU, a.sb, pitch, 0, pitch, a.Z, None, a.zb, pitch, 0, 0, pitch, K // 16, SP // 16, 0, K, lo, a.T) if k == 0 else
+                (a.dH, a.sb, pitch, 0, pitch, a.U, None, a.sb, pitch, 0, 0, pitch, SP // 16, SP // 16, 1, SP, lo, a.T) if k == 1 else
+                (a.dO, Q * a.W, a.W, -lo, a.W, a.H, None, a.sb, pitch, 0, 0, pitch, SP // 16, Q // 16, 1, SP, lo, a.T))
+        if st is None:
+            self.eng.wgrad_s(a.bw, a.B, self.mode_b, self.names[k], *args)
+        else:
+            self.eng.wgrad(a.bw, a.B, self.mode_b, st, self.names[k], *args)
+
+    def data_grad(self, k, a, st):
+        """dH = (W2^T dO) * [H > 0] (k = 2);  dU = (W1^T dH) * [U > 0] (1);  dZ = Ws^T dU, all N crops at once (0)"""
+        SP, S, Q, K, lo, pitch, T, sb, br = self.SP, self.S, self.Q, self.K, self.lo, a.pitch, a.T, a.sb, self.br(self.names[k] + "T")
+        if k == 2:
+            call("wn_chan_gemm", a.dO, None, Q * a.W, a.W, 0, a.W, -lo, 0, Q // 32, 0, br, SP // 16, S,
+                 a.dH, sb, pitch, 0, None, None, 0, 0, 0, a.H, sb, pitch, lo, T, 0, a.B, self.mode_b, st)
+        elif k == 1:
+            call("wn_chan_gemm", a.dH, None, sb, pitch, lo, T, 0, 0, SP // 32, 0, br, SP // 16, S,
+                 a.dU, sb, pitch, 0, None, None, 0, 0, 0, a.U, sb, pitch, lo, T, 0, a.B, self.mode_b, st)
+        else:
+            call("wn_chan_gemm", a.dU, None, sb, pitch, lo, T, 0, 0, SP // 32, 0, br, K // 16, K,
+                 a.dZ, a.zb, pitch, 0, None, None, 0, 0, 0, None, 0, 0, lo, T, 0, a.B, self.mode_b, st)
+
+    def bias_grads(self, a, st):
+        """row sums of dO, dH and (for every block's skip conv alike) dU"""
+        b, lo = self.bias, self.lo
+        if b:
+            call("wn_bias_grad", a.dO, self.Q * a.W, a.W, -lo, self.Q, lo, a.T, a.B, b.dst(b.b2), st)
+            call("wn_bias_grad", a.dH, a.sb, a.pitch, 0, self.S, lo, a.T, a.B, b.dst(b.b1), st)
+            for name in b.skips:
+                call("wn_bias_grad", a.dU, a.sb, a.pitch, 0, self.S, lo, a.T, a.B, b.dst(name), st)
+
+    # ------------------------------------------------------------------ the epilogue
+    def skip_bias(self, ws):
+        """The skip product's bias, the sum of the N skip convs' (None without biases): a torch sum of its own on the current stream"""
+        if not self.bias:
+            return None
+        flat = self.eng.flat
+        ws["bias_skip"] = sum(flat[o:o + self.S] for o in self.bias.skip_offs).contiguous()
+        return ptr(ws["bias_skip"])
+
+    def forward(self, ws, bias_s, st, fused, chains):
+        """From ws["Z"] to the logits in ws["O"]; bias_s = skip_bias(ws).  fused: the one launch, where it applies; else `chains`
+        per-clip-group chains of the three products, every second one on the side stream (1 = one chain on the main stream;
+        bit-identical results: tests/test_gpu_switches.py)"""
+        B = ws["B"]
+        nsplit = min(chains, B)
+        if fused and self.fused_fwd_ok:
+            self.fused_fwd(ws, bias_s, st)
+        elif nsplit >= 2:
+            # the three products of each part of the clips as a chain of its own, every second chain on the side stream: a
+            # product's half-empty last round of workgroups (408 tiles of 256 columns on 256 CUs) then packs into the other
+            # chain's launches (0.435-0.445 vs 0.466-0.469 ms with two chains)
+            main, side = torch.cuda.current_stream(), self.eng._side_stream()
+            ev = torch.cuda.Event()
+            ev.record(main)
+            side.wait_event(ev)
+            bounds = [B * k // nsplit for k in range(nsplit + 1)]
+            for k in range(nsplit):
+                b0, nb = bounds[k], bounds[k + 1] - bounds[k]
+                if k % 2 == 1:
+                    with torch.cuda.stream(side):
+                        self.products_fwd(ws, bias_s, b0, nb, _lib.stream())
+                else:
+                    self.products_fwd(ws, bias_s, b0, nb, st)
+            ev2 = torch.cuda.Event()
+            ev2.record(side)
+            main.wait_event(ev2)
+        else:
+            self.products_fwd(ws, bias_s, 0, B, st)
+
+    def begin_backward(self, ws, bw):
+        """The pass's pointers, and the first launch of the backward: the last product's weight gradient, on the side stream.  (On
+        its own for a user with launches of its own between this one and the data gradients.)"""
+        pitch, (kU, kH, _, kdH) = ws["pitch"], self.keys
+        a = _EpiBwd(bw, ws["B"], ws["T"], ws["W"], pitch, self.SP * pitch, self.K * pitch, ptr(bw["dO"]), ptr(bw[kdH], SLACK),
+                    ptr(bw["dU"], SLACK), ptr(bw["dZ"], SLACK), ptr(ws[kU], SLACK), ptr(ws[kH], SLACK), ptr(ws["Z"], SLACK))
+        self.wgrad(2, a, None)
+        self.fmark("b_wgrad_p2")
+        return a
+
+    def backward(self, a, st, fused, side_skip=False, after_dh=lambda: None):
+        """a = begin_backward(ws, bw).  From bw["dO"] (B, Q, W) to dz of every block in bw["dZ"], the three weight gradients into
+        their slabs, the bias gradients.  The weight gradients only feed the slab reduction at the very end: they run on the side
+        stream as soon as their operands exist, where their half-empty last rounds of workgroups pack into the data-gradient launches
+        beside them.  fused: the one launch for the data gradients, where it applies; side_skip: its skip weight gradient on the
+        side stream too, nothing joined; after_dh(): the user's launches on dh (the gradient of c), directly behind the launch that
+        produces it."""
+        if fused and self.fused_bwd_ok:
+            # the two weight gradients that read dH / dU follow the fused launch
+            self.fused_bwd(a, st)
+            self.fmark("b_fused")
+            after_dh()
+            self.wgrad(1, a, None)
+            # the skip weight gradient on the MAIN stream, beside the second product's on the side stream, and the stack starts when both
+            # are done: left to run beside the stack (side_skip, WN_EPI_BWD_ORDER=0) they stretch every backward-block launch - a block
+            # launch wants all 256 CUs at once - for the same total (bench A/B on one box: 0.95 + 2.0 against 0.52 + 2.6 ms), and the
+            # stack's own time (what `roofline` is computed from) would read 40 % high
+            self.wgrad(0, a, None if side_skip else st)
+            if not side_skip:
+                self.eng.join_side()
+            self.bias_grads(a, st)
+            return
+        self.data_grad(2, a, st)
+        self.fmark("b_p2T")
+        after_dh()
+        self.wgrad(1, a, None)
+        self.fmark("b_wgrad_p1")
+        self.data_grad(1, a, st)
+        self.fmark("b_p1T")
+        if self.bias_early:
+            self.bias_grads(a, st)
+        self.wgrad(0, a, None)
+        self.fmark("b_wgrad_skip")
+        self.data_grad(0, a, st)
+        if not self.bias_early:
+            self.bias_grads(a, st)

@@ -1,5 +1,6 @@
 """The complete launch trace of a fast engine's step, recorded on the CPU (tests/test_launch_trace.py compares it with
-tests/golden/launch_traces.json; tools/record_launch_trace.py writes that file and dumps the trace of any checkout).
+tests/golden/launch_traces.json and, for the forms of the skip epilogue that file does not reach, launch_traces_epilogue.json;
+tools/record_launch_trace.py writes those files and dumps the trace of any checkout).
 
 Nothing is launched and no device is touched: the engines are built on device="cpu" with `call` replaced
 (test_engine_base.patch_calls), `ptr` replaced by a marker that remembers its tensor, and the streams, events, the step throttle
@@ -27,6 +28,7 @@ from tests.test_engine_base import CASES, _ae_net, patch_calls
 SWITCHES = ("WN_PQ_BWD", "WN_MS_BWD", "WN_PAIR32", "WN_PQ_CHAIN", "WN_ENC_LCH", "WN_AE_ENC_PQ", "WN_AE_FUSED_ENC", "WN_EPI_WGRAD_CHUNKS",
             "WN_EPI_FUSED", "WN_EPI_FUSED_BWD", "WN_EPI_BWD_ORDER", "WN_AE_COND_MFMA", "WN_MAX_STEPS_IN_FLIGHT")
 WN_DIL, WN_T, AE_T = [1, 2, 4, 32, 64], 1200, 400
+SIX, AE_SIX = WN_DIL + [1], [1, 2, 32, 33, 1, 2]
 
 
 class OnDevice(torch.Tensor):
@@ -165,7 +167,11 @@ def canonical(trace, eng, ws):
     return out
 
 
-def pack_maps(eng):
+PACK_KEYS = r"pk\w*_(idx|off)|gp_off|gidx\w*|wt_idx"
+PACK_KEYS_ALL = PACK_KEYS + r"|bfg_idx|gp_bias_off"       # the second file's: the bias maps too
+
+
+def pack_maps(eng, keys=PACK_KEYS):
     """SHA-256 of every index map _build_packs produces (pk*_idx, pk*_off, gp_off, gidx*, wt_idx)."""
     def plain(v):
         if isinstance(v, torch.Tensor):
@@ -174,14 +180,14 @@ def pack_maps(eng):
         if isinstance(v, dict):
             return {str(k): plain(v[k]) for k in sorted(v)}
         return v
-    maps = {k: plain(v) for k, v in sorted(vars(eng).items()) if re.fullmatch(r"pk\w*_(idx|off)|gp_off|gidx\w*|wt_idx", k)}
+    maps = {k: plain(v) for k, v in sorted(vars(eng).items()) if re.fullmatch(keys, k)}
     return {k: hashlib.sha256(json.dumps(v, sort_keys=True).encode()).hexdigest() for k, v in maps.items()}
 
 
 # ---------------------------------------------------------------- the cases
-def _wn(ch, **kw):
+def _wn(ch, dil=WN_DIL, **kw):
     from music_amd.engine import WaveNetEngine
-    return WaveNetEngine(WN_DIL, ch, ch, 256, device="cpu", **kw)
+    return WaveNetEngine(dil, ch, ch, 256, device="cpu", **kw)
 
 
 def _ae(en, de, **kw):
@@ -189,7 +195,15 @@ def _ae(en, de, **kw):
     net = _ae_net(en, de, **kw)
     eng = _AutoencoderEngine(net, torch.device("cpu"))
     torch.manual_seed(3)
-    eng.cond = [tuple(c) for c in net._draw_conditioning()]
+    eng.cond = None if eng.learned else [tuple(c) for c in net._draw_conditioning()]
+    return eng
+
+
+def _with(eng, **attrs):
+    """the engine with the switches a test or tool sets as attributes"""
+    for k, v in attrs.items():
+        assert hasattr(eng, k), k
+        setattr(eng, k, v)
     return eng
 
 
@@ -271,10 +285,46 @@ TRACE_CASES = {
     "wavenet64_onehot_tag": ({}, lambda: _wn(64), _wn_step(2, "tagged")),
 }
 
+# The forms of the skip epilogue (and learned conditioning) that none of the cases above runs, same shapes: recorded into
+# tests/golden/launch_traces_epilogue.json, with every pack map hashed (PACK_KEYS_ALL)
+EPILOGUE_CASES = {
+    "wavenet64_epi3": ({"WN_EPI_FUSED": "0"}, lambda: _wn(64), _wn_step(2)),                       # two chains on two streams
+    "wavenet64_epi3_one_chain": ({"WN_EPI_FUSED": "0"}, lambda: _with(_wn(64), epi_chains=1), _wn_step(2)),
+    "wavenet64_bias_epi3": ({"WN_EPI_FUSED": "0"}, lambda: _wn(64, use_bias=True), _wn_step(2)),   # the summed skip bias enters the chain
+    "wavenet64_epi_bwd3": ({"WN_EPI_FUSED_BWD": "0"}, lambda: _wn(64), _wn_step(2)),
+    "wavenet64_epi_bwd_order0": ({"WN_EPI_BWD_ORDER": "0"}, lambda: _wn(64), _wn_step(2)),
+    "autoencoder64_epi_bwd3": ({"WN_EPI_FUSED_BWD": "0"}, lambda: _ae(64, 64), _ae_step(2)),
+    "autoencoder64_bias_epi_bwd3": ({"WN_EPI_FUSED_BWD": "0"}, lambda: _ae(64, 64, use_bias=True), _ae_step(2)),
+    "autoencoder64_no_overlap": ({}, lambda: _with(_ae(64, 64), overlap_wgrad=False), _ae_step(2)),   # one forward chain, all on main
+    "autoencoder64_learned": ({}, lambda: _ae(64, 64, conditioning="learned"), _ae_step(2)),
+    # wn_skip_epilogue_bwd takes the skip product's 16-row tiles three at a time: five (or the autoencoder's four) blocks of 64
+    # channels never reach it, whatever the switches say - the four cases above with WN_EPI_FUSED_BWD / WN_EPI_BWD_ORDER run the
+    # three launches.  Six blocks do, the autoencoder with 256 skip channels
+    "wavenet64_six_blocks": ({}, lambda: _wn(64, SIX), _wn_step(2)),
+    "wavenet64_six_blocks_bwd_order0": ({"WN_EPI_BWD_ORDER": "0"}, lambda: _wn(64, SIX), _wn_step(2)),
+    "wavenet64_six_blocks_epi_bwd3": ({"WN_EPI_FUSED_BWD": "0"}, lambda: _wn(64, SIX), _wn_step(2)),
+    "autoencoder64_six_blocks": ({}, lambda: _ae(64, 64, dilations=AE_SIX, de_skip_channel=256), _ae_step(2)),
+    "autoencoder64_six_blocks_bias": ({}, lambda: _ae(64, 64, dilations=AE_SIX, de_skip_channel=256, use_bias=True), _ae_step(2)),
+    "autoencoder64_six_blocks_epi_bwd3": ({"WN_EPI_FUSED_BWD": "0"}, lambda: _ae(64, 64, dilations=AE_SIX, de_skip_channel=256), _ae_step(2)),
+}
+# ... and of the two general engines the pack maps alone (they are built from the same pack builder): name -> builder of (engine, _)
+PACK_CASES = {name: CASES[name] for name in ("general_wavenet", "general_autoencoder")}
+
+
+def record_packs(name, monkeypatch):
+    """-> pack-map hashes (PACK_KEYS_ALL) of one general engine."""
+    env, build = PACK_CASES[name]
+    for k in SWITCHES:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    patch_calls(monkeypatch)
+    return pack_maps(build()[0], PACK_KEYS_ALL)
+
 
 def record(name, monkeypatch):
     """-> (canonical trace, pack-map hashes, forms of the workspace) of one case."""
-    env, build, run = TRACE_CASES[name]
+    env, build, run = TRACE_CASES[name] if name in TRACE_CASES else EPILOGUE_CASES[name]
     for k in SWITCHES:
         monkeypatch.delenv(k, raising=False)
     for k, v in env.items():
@@ -289,7 +339,7 @@ def record(name, monkeypatch):
     forms = {k: v for k, v in list(ws.items()) + list(bw.items())
              if k in ("pair", "pair_fwd", "ms", "pq", "chain", "enc_chain", "enc_pq", "enc_fused")}
     forms["cidx"] = "cidx" in ws
-    return canonical(trace, eng, ws), pack_maps(eng), forms
+    return canonical(trace, eng, ws), pack_maps(eng, PACK_KEYS if name in TRACE_CASES else PACK_KEYS_ALL), forms
 
 
 def digest(trace):

@@ -3,6 +3,10 @@ and music_amd/model1.py - entry point, argument values, stream, position in the 
 every timing mark, compared with the trace recorded at the commit named in tests/golden/launch_traces.json (written once by
 tools/record_launch_trace.py --write, never regenerated), and the index maps _build_packs produces compared by hash.
 
+A second file, tests/golden/launch_traces_epilogue.json (tools/record_launch_trace.py --write --set epilogue, at the commit it names),
+pins the forms of the skip epilogue the first one does not reach - the three-launch forward, one chain, the fused backward and its
+switches, learned conditioning - and the pack maps of the two general engines.
+
 The recording itself (what is stubbed, how pointers are named) is tests/launch_trace.py.  No device is touched."""
 import json
 import os
@@ -12,12 +16,28 @@ import pytest
 from tests import launch_trace as lt
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "launch_traces.json")
+GOLDEN_EPILOGUE = os.path.join(os.path.dirname(GOLDEN), "launch_traces_epilogue.json")
 
 
 @pytest.fixture(scope="module")
 def golden():
     with open(GOLDEN) as f:
         return json.load(f)
+
+
+@pytest.fixture(scope="module")
+def golden_epilogue():
+    with open(GOLDEN_EPILOGUE) as f:
+        return json.load(f)
+
+
+def _same(want, trace, packs, forms):
+    trace = json.loads(json.dumps(trace))
+    assert forms == want["forms"]
+    assert packs == want["packs"]
+    for k, (got, exp) in enumerate(zip(trace, want["trace"])):
+        assert got == exp, "item %d of %d" % (k, len(want["trace"]))
+    assert len(trace) == len(want["trace"])
 
 
 def test_the_recorded_cases_are_the_cases(golden):
@@ -50,3 +70,45 @@ def test_launch_trace_is_the_recorded_one(name, golden, monkeypatch):
     for k, (got, exp) in enumerate(zip(trace, want["trace"])):
         assert got == exp, "item %d of %d" % (k, len(want["trace"]))
     assert len(trace) == len(want["trace"])
+
+
+def test_the_recorded_epilogue_cases_are_the_cases(golden_epilogue):
+    g = golden_epilogue
+    assert len(g["recorded_at"]) == 40 and sorted(g["cases"]) == sorted(lt.EPILOGUE_CASES) and sorted(g["packs_only"]) == sorted(lt.PACK_CASES)
+    assert all("gp_bias_off" in p and "gidx" in p for p in g["packs_only"].values())
+    items = lambda name: g["cases"][name]["trace"]
+    calls = lambda name, entry=None: [i for i in items(name) if i[0] == "call" and entry in (None, i[1])]
+    on = lambda name, entry: [i[2] for i in calls(name, entry)]
+    # the three-launch forward: two chains on two streams, one chain on the main stream, the summed skip bias as the first product's bias
+    for name in ("wavenet64_epi3", "wavenet64_epi3_one_chain", "wavenet64_bias_epi3"):
+        assert not calls(name, "wn_skip_epilogue_fwd")
+    fwd3 = lambda name: [i for i in calls(name, "wn_chan_gemm") if i[3][10][0] in ("eng.pk_f", "eng.pk")][-6:]
+    assert [i[2] for i in fwd3("wavenet64_epi3")] == ["main"] * 3 + ["side"] * 3
+    assert [i[2] for i in fwd3("wavenet64_epi3_one_chain")][-3:] == ["main"] * 3 and "side" not in on("wavenet64_epi3_one_chain", "wn_chan_gemm")
+    assert fwd3("wavenet64_bias_epi3")[0][3][17][0] == "ws.bias_skip" and fwd3("wavenet64_epi3")[0][3][17] is None
+    # five blocks of 64 channels never take the fused backward; six do, and the autoencoder with 256 skip channels, biases or not
+    for name in ("wavenet64_epi_bwd3", "wavenet64_epi_bwd_order0", "autoencoder64_epi_bwd3", "autoencoder64_bias_epi_bwd3",
+                 "wavenet64_six_blocks_epi_bwd3", "autoencoder64_six_blocks_epi_bwd3"):
+        assert not calls(name, "wn_skip_epilogue_bwd")
+    for name in ("wavenet64_six_blocks", "wavenet64_six_blocks_bwd_order0", "autoencoder64_six_blocks", "autoencoder64_six_blocks_bias"):
+        assert len(calls(name, "wn_skip_epilogue_bwd")) == 1
+    assert on("wavenet64_six_blocks", "wn_wgrad")[:3] == ["side", "side", "main"]
+    assert on("wavenet64_six_blocks_bwd_order0", "wn_wgrad")[:3] == ["side", "side", "side"]
+    # the conditioning gradient directly behind the launch that produces dR1, in both forms
+    for name, entry in (("autoencoder64_six_blocks", "wn_skip_epilogue_bwd"), ("autoencoder64_six_blocks_epi_bwd3", "wn_chan_gemm")):
+        seq = [i[1] for i in calls(name)]
+        k = seq.index("wn_cond_grad")
+        assert seq[k - 1] == entry
+    assert calls("autoencoder64_bias_epi_bwd3", "wn_bias_grad") and calls("autoencoder64_six_blocks_bias", "wn_bias_grad")
+    assert "side" not in [i[2] for i in calls("autoencoder64_no_overlap")] and not [i for i in items("autoencoder64_no_overlap") if i[0] != "call" and i[0] != "mark"]
+    assert len(calls("autoencoder64_learned", "wn_cond_proj_fwd")) == 1 and len(calls("autoencoder64_learned", "wn_cond_proj_bwd")) == 1
+
+
+@pytest.mark.parametrize("name", list(lt.EPILOGUE_CASES))
+def test_epilogue_launch_trace_is_the_recorded_one(name, golden_epilogue, monkeypatch):
+    _same(golden_epilogue["cases"][name], *lt.record(name, monkeypatch))
+
+
+@pytest.mark.parametrize("name", list(lt.PACK_CASES))
+def test_general_engine_pack_maps_are_the_recorded_ones(name, golden_epilogue, monkeypatch):
+    assert lt.record_packs(name, monkeypatch) == golden_epilogue["packs_only"][name]
