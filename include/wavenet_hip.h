@@ -436,6 +436,34 @@ int wn_cond_proj_fwd(const float* enc, const float* flat, int64_t w_off, int64_t
 int wn_cond_proj_bwd(const float* d_tab, int pair, const float* d_enf, const float* enc, const float* flat, int64_t w_off,
                      int64_t b_off, int64_t stage_stride, int64_t wf_off, int64_t bf_off, float* d_enc, float* flat_grad,
                      int n_stages, int dd, int ch, int sd, int bw, int le, int batch, wn_stream_t stream);
+/* ---- VECTOR-QUANTISED bottleneck of the autoencoder (VQ-VAE, van den Oord et al. 2017; the reference has none): every pooled frame
+ * e = enc[b][:][l] of enc [batch][bw][le] is replaced by its nearest row of the codebook c [K][bw], which sits at flat + cb_off
+ * (its gradient at flat_grad + cb_off; offsets count floats).  C = batch * le frames.  Everything in float32:
+ *   dist(b, l, k) = sum_j (e_j - c_kj)^2          the difference form (exact on multiples of 1/8), not |c|^2 - 2 e.c
+ *   idx[b][l]     = argmin_k dist, ties to the SMALLEST k;          q[b][:][l] = c[idx[b][l]], the layout of enc
+ *   mse           = sum (q - e)^2 / (C bw);       the model's vq_loss = (1 + beta) mse (codebook term + beta x commitment term)
+ * wn_vq_fwd writes q_out, idx (int32 [batch][le]), counts (int32 [K], frames per code; may be NULL) and loss_part:
+ * WN_VQ_NUM_PARTIALS floats, ALL rewritten at every call, their sum is mse.  One kernel launch (and a memset node for counts).
+ * wn_vq_bwd, with s = 2 / (C bw) and g_scale the upstream scalar on vq_loss, writes in one launch
+ *   d_enc[b][j][l] = d_q[b][j][l] + g_scale beta s (e - q)          straight-through + commitment; d_enc may alias d_q
+ *   flat_grad + cb_off: d_c[k] = g_scale s sum_{frames with idx = k, in ascending frame order} (c_k - e)
+ * OVERWRITING all K rows - a code no frame chose gets exactly 0 - and touching nothing else of flat_grad; an idx outside [0, K)
+ * turns that frame's d_enc into NaN and is not dereferenced.
+ * wn_vq_lookup writes q_out = c[idx] from given codes (decoding): an idx outside [0, K) is never dereferenced - that frame of
+ * q_out becomes NaN and *bad (int32 on the device, cleared by the call; may be NULL) becomes 1.
+ * On `stream`, no allocation, nothing retained, legal under stream capture; no float atomics and a fixed summation order: the same
+ * bits at every launch.  2 <= K <= WN_VQ_MAX_CODES, 1 <= bw <= WN_VQ_MAX_WIDTH, any le >= 1.  batch == 0 returns 0 and writes
+ * nothing (NULLs allowed).  -4, function and argument named in wn_last_error, before anything is launched: batch < 0; K < 2 or
+ * K > 1024; bw < 1 or bw > 512; le < 1; cb_off < 0; with work to do, a NULL required pointer (all but counts and bad). */
+#define WN_VQ_NUM_PARTIALS 256
+#define WN_VQ_MAX_CODES 1024                /* = WN_DEC_MAX_Q: what a prior over the codes, wn_step_nll and the samplers accept */
+#define WN_VQ_MAX_WIDTH 512
+int wn_vq_fwd(const float* enc, const float* flat, int64_t cb_off, float* q_out, int32_t* idx, int32_t* counts, float* loss_part, int K,
+              int bw, int le, int batch, wn_stream_t stream);
+int wn_vq_bwd(const float* enc, const int32_t* idx, const float* d_q, const float* flat, int64_t cb_off, float beta, float g_scale,
+              float* d_enc, float* flat_grad, int K, int bw, int le, int batch, wn_stream_t stream);
+int wn_vq_lookup(const int32_t* idx, const float* flat, int64_t cb_off, float* q_out, int32_t* bad, int K, int bw, int le, int batch,
+                 wn_stream_t stream);
 /* The reference's nn.DataParallel gradient reduction (wavenet/train.py:116-122) as ONE in-place sum over the ranks of the flat
  * fp32 gradient buffer: ncclAllReduce(buf, buf, n, ncclFloat32, ncclSum, comm, stream) on the caller's RCCL communicator
  * (`comm` = an ncclComm_t).  The 1 / world_size of the mean goes into wn_adam_flat's gscale.  Returns -5 when RCCL is neither

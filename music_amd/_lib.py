@@ -15,6 +15,8 @@ CE_NUM_PARTIALS = 1024
 ABI_VERSION = 9
 GUARD_NUM_PARTIALS = 256       # include/wavenet_hip.h WN_GUARD_NUM_PARTIALS
 GUARD_PARTIALS_BYTES = GUARD_NUM_PARTIALS * 12
+VQ_NUM_PARTIALS = 256          # include/wavenet_hip.h WN_VQ_NUM_PARTIALS
+VQ_MAX_CODES, VQ_MAX_WIDTH = 1024, 512
 
 _p = ctypes.c_void_p
 _i = ctypes.c_int
@@ -90,6 +92,9 @@ SIGNATURES = {
     "wn_step_nll": [_p, _l, _i, _p, _p, _l, _i, _p, _p, _p, _p, _i, _i, _i, _f, _p],
     "wn_cond_proj_fwd": [_p, _p, _l, _l, _l, _l, _l, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
     "wn_cond_proj_bwd": [_p, _i, _p, _p, _p, _l, _l, _l, _l, _l, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
+    "wn_vq_fwd": [_p, _p, _l, _p, _p, _p, _p, _i, _i, _i, _i, _p],
+    "wn_vq_bwd": [_p, _p, _p, _p, _l, _f, _f, _p, _p, _i, _i, _i, _i, _p],
+    "wn_vq_lookup": [_p, _p, _l, _p, _p, _i, _i, _i, _i, _p],
     "wn_coll_available": [],
     "wn_comm_unique_id": [_p],
     "wn_comm_create": [_i, _i, _p, _p],

@@ -161,7 +161,11 @@ def backward(hook, eng, ws, dprobs):
                   None, n, 1.0 / n, _lib.stream())
         hook.do_valid = True
     tok = _zero_token(dprobs)
-    if dprobs.data_ptr() == tok.data_ptr() and not any(dprobs.stride()):
+    if dprobs.data_ptr() == tok.data_ptr() and not any(dprobs.stride()) and getattr(eng, "vq", False):
+        # a vq bottleneck's backward is not linear in the loss's upstream gradient alone (vq_loss has its own, ws["vq_g"]): scale
+        # d loss / d pre-softmax instead of the result
+        eng.vq_backward_scaled(ws, hook.dloss, ws.get("vq_g", 0.0))
+    elif dprobs.data_ptr() == tok.data_ptr() and not any(dprobs.stride()):
         eng.backward_from_dlogits(ws)                       # d loss / d pre-softmax is in the workspace (for an upstream gradient of 1)
         eng.flat_grad.mul_(hook.dloss)
     else:                                                   # the probabilities are used elsewhere in the loss too

@@ -143,6 +143,54 @@ def conditioned_decoder(net, cond):
     return wnet, proj
 
 
+def _decode_from_encoding(net, enc, cond, W, first, prime, forced, free_step=False, want_probs=False, temperature=None, seed=0,
+                          top_k=None, top_p=None, streams=None):
+    """What ``resynthesize`` and ``decode_codes`` share: from an encoding ``enc`` (B, Bw, Le) on the device and the conditioning
+    projections ``cond``, build the per-clip tables and the schedule of a forward with ``W`` output rows, prime the queues from
+    zero with the input samples ``first`` (B,) then ``prime`` (B, n) - teacher-forced steps at output positions -(rf - 1) .. -
+    and decode the W output positions in one persistent conditioned launch, fed ``forced`` (B, W) or its own codes.
+    ``free_step``: ``prime`` holds rf - 2 samples only and the sample in front of output position 0 is the model's own.
+    Returns (codes int32 (B, W), probabilities (B, W, Q) or None)."""
+    try:
+        from . import fast_generate as fg
+    except ImportError:
+        from music_amd import fast_generate as fg
+    dev = enc.device
+    B, Le = enc.size(0), enc.size(2)
+    Q, rf = net.quantization_channel, net.receptive_field
+    wnet, proj = conditioned_decoder(net, cond)
+    deng = wnet._engine_for(dev)
+    if not hasattr(wnet, "_decode_pack") or wnet._decode_pack.eng is not deng:
+        wnet._decode_pack = fg._DecodePack(deng)
+    pack = wnet._decode_pack
+    N, Dd, Dp, S, K1 = len(net.dilations), net.de_dilation_channel, pack.Dp, net.de_skip_channel, net.filter_width - 1
+    # tables: column e of stage i = proj_i(enc[:, e]); blocks [B][N][Le][f Dp | g Dp] (zero rows beyond Dd), post-processing [B][Le][S]
+    cw = torch.stack([p[0] for p in proj[:N]])                        # (N, 2 Dd, Bw), rows [f | g]
+    cb = torch.stack([p[1] for p in proj[:N]])
+    en = torch.einsum("nck,bkl->bnlc", cw, enc) + cb[None, :, None, :]
+    cond_fg = torch.zeros(B, N, Le, 2 * Dp, dtype=torch.float32, device=dev)
+    cond_fg[..., :Dd] = en[..., :Dd]
+    cond_fg[..., Dp:Dp + Dd] = en[..., Dd:]
+    cond_p1 = (torch.einsum("ck,bkl->blc", proj[N][0], enc) + proj[N][1]).contiguous()
+    sched = cond_schedule(net, W, Le)
+    rw = fg._ring_width(deng)
+    rings = torch.zeros(B, max(1, sum(K1 * d * rw for d in deng.dil)), dtype=torch.float32, device=dev)
+    note = first
+    prev = torch.zeros(B, K1, Q, dtype=torch.float32, device=dev)
+    tabs = dict(cond_fg=cond_fg, cond_p1=cond_p1, schedule=sched)
+    n = prime.size(1)
+    if n > 0:
+        # priming: step s takes sample s and is forced to continue with sample s + 1
+        _, _, note, prev = fg.decode_batch_cond(wnet, rings, prev, note, n, step0=0, pos0=-(rf - 1), forced=prime, **tabs)
+    if free_step:
+        _, _, note, prev = fg.decode_batch_cond(wnet, rings, prev, note, 1, step0=n, pos0=n - (rf - 1), temperature=temperature, seed=seed,
+                                                top_k=top_k, top_p=top_p, streams=streams, **tabs)
+    codes, probs, _, _ = fg.decode_batch_cond(wnet, rings, prev, note, W, step0=rf - 1, pos0=0, forced=forced,
+                                              want_probs=want_probs, temperature=temperature, seed=seed, top_k=top_k, top_p=top_p,
+                                              streams=streams, **tabs)
+    return codes, probs
+
+
 def resynthesize(net, clips, cond=None, teacher_forced=False, want_probs=False, temperature=None, seed=0, top_k=None, top_p=None,
                  streams=None):
     """Encode ``clips`` (B, Q, T) one-hot, T >= receptive_field with at least one pooled frame, and regenerate them from the
@@ -154,11 +202,9 @@ def resynthesize(net, clips, cond=None, teacher_forced=False, want_probs=False, 
     ``teacher_forced``: the clip's own codes are fed (the probabilities are then the forward's, row for row); otherwise the
     model's own codes are fed back after the clip's first receptive_field samples.  ``temperature``: sample instead of
     argmax, reproducibly for ``seed``; ``top_k`` / ``top_p`` truncate the distribution first; each of the four may be one value per clip
-    (``streams``: the clips' random-number stream ids, default their index).  Returns (codes int64 (B, W), probabilities (B, W, Q) or None, encodings (B, Bw, Le))."""
-    try:
-        from . import fast_generate as fg
-    except ImportError:
-        from music_amd import fast_generate as fg
+    (``streams``: the clips' random-number stream ids, default their index).  Returns (codes int64 (B, W), probabilities (B, W, Q) or None, encodings (B, Bw, Le)).
+    With a vq bottleneck the encoding is the quantised one, and ``net.vq_codes`` (B, Le) / ``net.last_encoding_pre`` hold the
+    frames' codes and the encoding in front of the quantiser."""
     if clips.dim() != 3 or clips.size(1) != net.quantization_channel:
         raise ValueError("resynthesize: clips must be (B, %d, T)" % net.quantization_channel)
     x = clips.detach().cuda().float().contiguous()
@@ -171,41 +217,84 @@ def resynthesize(net, clips, cond=None, teacher_forced=False, want_probs=False, 
     cond = eng_cond if eng_cond is not None else net.conditioning_projections()
     eng = net._engine_for(x.device)
     with torch.no_grad():
-        _, enc, _ = eng.forward(x, eng_cond, want_probs=False)            # (raises when the clip pools to no frame)
+        _, enc, ws = eng.forward(x, eng_cond, want_probs=False)           # (raises when the clip pools to no frame)
     enc = net.last_encoding = enc.clone()
-    Le = enc.size(2)
-    wnet, proj = conditioned_decoder(net, cond)
-    deng = wnet._engine_for(x.device)
-    if not hasattr(wnet, "_decode_pack") or wnet._decode_pack.eng is not deng:
-        wnet._decode_pack = fg._DecodePack(deng)
-    pack = wnet._decode_pack
-    N, Dd, Dp, S, K1 = len(net.dilations), net.de_dilation_channel, pack.Dp, net.de_skip_channel, net.filter_width - 1
-    # tables: column e of stage i = proj_i(enc[:, e]); blocks [B][N][Le][f Dp | g Dp] (zero rows beyond Dd), post-processing [B][Le][S]
-    cw = torch.stack([p[0] for p in proj[:N]])                        # (N, 2 Dd, Bw), rows [f | g]
-    cb = torch.stack([p[1] for p in proj[:N]])
-    en = torch.einsum("nck,bkl->bnlc", cw, enc) + cb[None, :, None, :]
-    cond_fg = torch.zeros(B, N, Le, 2 * Dp, dtype=torch.float32, device=x.device)
-    cond_fg[..., :Dd] = en[..., :Dd]
-    cond_fg[..., Dp:Dp + Dd] = en[..., Dd:]
-    cond_p1 = (torch.einsum("ck,bkl->blc", proj[N][0], enc) + proj[N][1]).contiguous()
-    sched = cond_schedule(net, W, Le)
-    rw = fg._ring_width(deng)
-    rings = torch.zeros(B, max(1, sum(K1 * d * rw for d in deng.dil)), dtype=torch.float32, device=x.device)
+    if eng.vq:
+        net.vq_codes, net.last_encoding_pre = ws["vq_idx"].to(torch.int64), ws["enc_pre"]
     codes_in = x.argmax(1).to(torch.int32)                            # (B, T)
-    note = x[:, :, 0].contiguous()
-    prev = torch.zeros(B, K1, Q, dtype=torch.float32, device=x.device)
-    tabs = dict(cond_fg=cond_fg, cond_p1=cond_p1, schedule=sched)
-    if rf > 1:
-        # priming: step s takes the clip's sample s and is forced to continue with sample s + 1
-        _, _, note, prev = fg.decode_batch_cond(wnet, rings, prev, note, rf - 1, step0=0, pos0=-(rf - 1),
-                                                forced=codes_in[:, 1:rf], **tabs)
     forced = None
     if teacher_forced:
         forced = torch.cat([codes_in[:, rf:], torch.zeros(B, 1, dtype=torch.int32, device=x.device)], 1)
-    codes, probs, _, _ = fg.decode_batch_cond(wnet, rings, prev, note, W, step0=rf - 1, pos0=0, forced=forced,
-                                              want_probs=want_probs, temperature=temperature, seed=seed, top_k=top_k, top_p=top_p,
-                                              streams=streams, **tabs)
+    codes, probs = _decode_from_encoding(net, enc, cond, W, x[:, :, 0].contiguous(), codes_in[:, 1:rf], forced, want_probs=want_probs,
+                                         temperature=temperature, seed=seed, top_k=top_k, top_p=top_p, streams=streams)
     return codes.to(torch.int64), probs, enc
+
+
+def _vq_engine(net, what):
+    if getattr(net, "bottleneck", "continuous") != "vq":
+        raise ValueError('music_amd.ae_generate.%s needs a model with bottleneck="vq"' % what)
+    return net._engine_for(next(net.parameters()).device)
+
+
+def encode_codes(net, clips):
+    """The codes of ``clips`` (B, Q, T) one-hot under a vq model: (B, Le) int64, Le = (T - rf + 1) // pool frames per clip.
+    Runs the encoder, the pool and the quantiser (wn_vq_fwd) only."""
+    eng = _vq_engine(net, "encode_codes")
+    if clips.dim() != 3 or clips.size(1) != net.quantization_channel:
+        raise ValueError("encode_codes: clips must be (B, %d, T)" % net.quantization_channel)
+    if clips.size(2) - net.receptive_field + 1 < 1:
+        raise ValueError("wave sample not long enough")
+    x = clips.detach().to(eng.device).float().contiguous()
+    with torch.no_grad():
+        _, _, ws = eng.forward(x, None, want_probs=False, encode_only=True)
+    return ws["vq_idx"].to(torch.int64)
+
+
+def decode_codes(net, codes, W, start=None, teacher_forced=None, want_probs=False, temperature=None, top_k=None, top_p=None, seed=0,
+                 streams=None):
+    """Audio codes from bottleneck codes: ``codes`` (B, Le) integers in [0, K) are looked up in the codebook (wn_vq_lookup; a code
+    out of range raises) and the encoding is decoded as ``resynthesize`` decodes one - the same tables, schedule
+    (``cond_schedule(net, W, Le)``), priming and persistent conditioned launch - into ``W`` samples per clip.
+    The rf = receptive_field samples in front of output position 0: ``start`` (B, rf - 1) codes are the first rf - 1 of them and
+    the last is the model's own continuation; ``start=None`` primes with the mid code Q / 2 throughout, as
+    ``fast_generate.generate`` does.  ``teacher_forced``: the codes (B, rf - 1 + W) of whole clips - they are fed instead of the
+    model's own (the probabilities are then those of a forward over the clip whose encoding these codes are), ``start``
+    defaults to their first rf - 1.  ``temperature`` / ``top_k`` / ``top_p`` / ``seed`` / ``streams``: as in ``resynthesize``.
+    Returns (codes int64 (B, W), probabilities (B, W, Q) or None)."""
+    eng = _vq_engine(net, "decode_codes")
+    dev = eng.device
+    Q, rf, W = net.quantization_channel, net.receptive_field, int(W)
+    if codes.dim() != 2 or W < 1:
+        raise ValueError("decode_codes: codes must be (B, Le) and W >= 1")
+    B = codes.size(0)
+    enc = eng.vq_lookup(codes)
+    as_codes = lambda t, n, what: _checked_codes(t, B, n, Q, dev, what)
+    forced = last = None
+    if teacher_forced is not None:
+        tf = as_codes(teacher_forced, rf - 1 + W, "teacher_forced")
+        start = tf[:, :rf - 1] if start is None else start
+        last = tf[:, rf - 1:rf]
+        forced = torch.cat([tf[:, rf:], torch.zeros(B, 1, dtype=torch.int32, device=dev)], 1)
+    if start is None:
+        start = torch.full((B, rf - 1), Q // 2, dtype=torch.int32, device=dev)
+        last = start[:, :1]
+    start = as_codes(start, rf - 1, "start")
+    seq = start if last is None else torch.cat([start, last], 1)
+    first = torch.zeros(B, Q, dtype=torch.float32, device=dev)
+    first.scatter_(1, seq[:, :1].to(torch.int64), 1.0)
+    out, probs = _decode_from_encoding(net, enc, net.conditioning_projections(), W, first, seq[:, 1:].contiguous(), forced,
+                                       free_step=last is None, want_probs=want_probs, temperature=temperature, seed=seed, top_k=top_k,
+                                       top_p=top_p, streams=streams)
+    return out.to(torch.int64), probs
+
+
+def _checked_codes(t, B, n, Q, dev, what):
+    t = torch.as_tensor(t)
+    if t.dim() != 2 or tuple(t.shape) != (B, n):
+        raise ValueError("decode_codes: %s must be (%d, %d) codes, got %s" % (what, B, n, tuple(t.shape)))
+    if t.is_floating_point() or int(t.min()) < 0 or int(t.max()) >= Q:
+        raise ValueError("decode_codes: %s must hold integer codes in [0, %d)" % (what, Q))
+    return t.to(device=dev, dtype=torch.int32).contiguous()
 
 
 def generate_cached(net, start_piece, note_num, cond=None, temperature=None, seed=0, top_k=None, top_p=None):

@@ -115,8 +115,9 @@ class GenericAutoencoderEngine(GeneralPlan):
         return out
 
     # ------------------------------------------------------------------ forward (model1.py:256-268)
-    def forward(self, x, cond=None, want_probs=True):
-        """cond: the N + 1 drawn (weight, bias) pairs; None with learned conditioning (parameters of the flat buffer)"""
+    def forward(self, x, cond=None, want_probs=True, encode_only=False):
+        """cond: the N + 1 drawn (weight, bias) pairs; None with learned conditioning (parameters of the flat buffer);
+        encode_only=True stops behind the pooled (and, with a vq bottleneck, quantised) encoding: (None, enc, ws)"""
         self._check_cond(cond)
         B, Q, T = x.shape
         assert Q == self.Q and x.is_contiguous() and x.dtype == torch.float32 and x.is_cuda
@@ -157,6 +158,10 @@ class GenericAutoencoderEngine(GeneralPlan):
                 self._bias_ptr("bottleneck_layer.bias"), NONE4, NONE3, lo, T, 0)
         enc = torch.empty(B, self.Bw, Le, dtype=torch.float32, device=dev)
         call("wn_avgpool", E, BwP * pitch, pitch, lo, self.pool, Le, self.Bw, ptr(enc), self.Bw * Le, Le, B, st)
+        if self.vq:                                           # every frame -> its nearest codebook row: the decoder sees q
+            enc = self.vq_fwd(ws, enc, st)
+        if encode_only:
+            return None, enc, ws
 
         # ---------------- conditioning tables en_i = Conv1d_rand(enc) (model1.py:178-179, 216-217), rows in the pack's [f | g] order
         Dd, Sd = self.Dd, self.Sd
@@ -255,6 +260,8 @@ class GenericAutoencoderEngine(GeneralPlan):
         if self.learned:                     # ... parameters of their own: d enc, dW and db (flat_grad's tail) in wn_cond_proj_bwd
             d_enc = torch.empty(B, Bw, Le, dtype=torch.float32, device=dev)
             self.cond_proj_bwd(d_tab, False, d_enf, ws["enc"], d_enc, DdP, st)
+            if self.vq:                                       # straight through to e, + the commitment term; the codebook's gradient
+                self.vq_bwd(ws, d_enc, st)
         else:
             d_en = torch.cat([d_tab[:, :, DdP:DdP + Dd], d_tab[:, :, :Dd]], 2)         # reference row order [gate | filter]
             d_enc = (torch.einsum("nck,nbcl->bkl", ws["cw"], d_en) + torch.einsum("ck,bcl->bkl", ws["cfw"][:, :, 0], d_enf)).contiguous()

@@ -26,6 +26,12 @@ checkpoint is restored.
 Optional key in model_params.json: ``"conditioning"`` (``"random"``, the default and the reference's behaviour: the decoder's N + 1
 conditioning projections are drawn afresh in every forward; ``"learned"``: they are parameters of the model, trained, saved and
 restored with it - music_amd/model1.py).  A checkpoint only loads into a model built with the mode it was saved with.
+``"bottleneck"`` (``"continuous"``, the default; ``"vq"``: every pooled frame is replaced by its nearest row of a learned codebook,
+VQ-VAE - needs ``"conditioning": "learned"``), ``"vq_codes"`` (codebook rows, 2 .. 1024, default 512) and ``"vq_beta"`` (weight of the
+commitment term, default 0.25).  With it the loss of every step is the reconstruction loss plus ``vq_loss``, one line per
+``print_every`` goes to ``vq_log.log`` (mse, perplexity of the code usage, codes used), and the optional train_params.json key
+``"vq_init"`` (``"uniform"``, the default, or ``"data"``) initialises the codebook from the first batch's pre-quantisation
+encoding (``net.init_codebook``) when training starts from scratch.
 """
 import glob
 import os
@@ -211,12 +217,29 @@ def train():
             train_params["log_dir"] + 'guard_log.log',
             lambda: engine.guard_report() if fused else optimizer.guard_report(),
             lambda: guard.engine_named_grads(engine) if fused else [(n, p.grad) for n, p in net.named_parameters()])
+    is_vq = getattr(net, "bottleneck", "continuous") == "vq"
+    vq_init = train_params.get("vq_init", "uniform")
+    if vq_init not in ("uniform", "data"):
+        raise ValueError('train_params.json: "vq_init" must be "uniform" or "data", not %r' % (vq_init,))
+    vq_init_pending = is_vq and vq_init == "data" and restored_from is None
+    vq_log_file = open(train_params["log_dir"] + 'vq_log.log', 'a') if is_vq and is_writer else None
     for epoch in range(train_params["num_epochs"]):
         for i_batch, sampled_batch in enumerate(dataloader):
             piece, target = sampled_batch["audio_piece"], sampled_batch["audio_target"]
             dp_scale = float(sampled_batch.get("dp_scale", 1.0))      # ragged last batch, see faster_audio_data._Collate
             if piece is not None:
                 target = target.view(-1)
+            if vq_init_pending and piece is not None:
+                # the codebook starts as K frames of the first batch's encoding in front of the quantiser (every replica from the
+                # same frames: rank 0's, broadcast)
+                vq_init_pending = False
+                with torch.no_grad():
+                    _, _, ws0 = net._engine_for(device).forward(piece.to(device).float().contiguous(), None, want_probs=False,
+                                                                encode_only=True)
+                net.init_codebook(ws0["enc_pre"], seed=step_seed)
+                wdist.broadcast_parameters([net.vq_codebook.weight])
+                if shadow is not None and "vq_codebook.weight" in (getattr(shadow, "tensors", None) or {}):
+                    shadow.tensors["vq_codebook.weight"].copy_(net.vq_codebook.weight.detach())      # the shadow was taken before
             if world > 1 and net.conditioning != "learned":
                 # every replica must draw the SAME per-forward conditioning projections; learned ones are parameters
                 torch.manual_seed(step_seed + num_trained)
@@ -226,6 +249,8 @@ def train():
                 loss = torch.zeros((), device=device)
                 if piece is not None:
                     loss = wobjective.nll_loss(net, piece, target) if objective == "nll" else loss_func(net(piece), target)
+                    if is_vq:
+                        loss = loss + net.vq_loss
                     loss.backward()
                 wdist.allreduce_gradients(net.parameters(), average=True, scale=dp_scale)
                 return loss
@@ -253,6 +278,11 @@ def train():
                     loss_log_file.flush()
                 if guard_log is not None:
                     guard_log.tick(num_trained)
+                stats = (engine.last_vq if fused else net.last_vq) if vq_log_file is not None else None
+                if stats is not None:                         # (the last step's figures, read back where the loss is)
+                    vq_log_file.writelines('Trained over %d pieces, vq mse %s, perplexity %s, codes used %d\n'
+                                           % (num_trained, stats.mse.item(), stats.perplexity.item(), int(stats.codes_used.item())))
+                    vq_log_file.flush()
                 total_loss.zero_()
             if validation is not None:
                 validation.tick(net, num_trained, shadow)
@@ -267,6 +297,8 @@ def train():
     if is_writer:
         loss_log_file.close()
         store_log_file.close()
+        if vq_log_file is not None:
+            vq_log_file.close()
 
 
 if __name__ == '__main__':

@@ -56,6 +56,7 @@ static int wn_null_error(const char* fn, const char* names, int which) {
 static_assert(WN_F16X3 == WN_MODE_F16X3 && WN_F16X1 == WN_MODE_F16X1 && WN_BF16X3 == WN_MODE_BF16X3 &&
               WN_BF16X1 == WN_MODE_BF16X1, "mode enums out of sync");
 static_assert(WN_CE_NUM_PARTIALS == WN_CE_PARTIALS, "partials out of sync");
+static_assert(WN_VQ_NUM_PARTIALS == WN_VQ_PARTIALS && WN_VQ_MAX_CODES == WN_DEC_MAX_Q, "vq constants out of sync");
 
 // ---- cached-queue decode: the ONE call path behind the six exported decode entries -------------------------------------------
 // Every entry forwards its arguments (and the defaults of those it does not take) to decode_checked with the checks it applies:
@@ -456,6 +457,52 @@ int wn_cond_proj_bwd(const float* d_tab, int pair, const float* d_enf, const flo
     p.flat_grad = flat_grad;
     p.n_stages = n_stages; p.dd = dd; p.ch = ch; p.sd = sd; p.bw = bw; p.le = le; p.batch = batch;
     return wn_launch_cond_proj_bwd(p, (hipStream_t)stream);
+}
+// ---- vector-quantised bottleneck (wn_vq.hip) ----
+// the refusals the three entries share: shapes and the offset first (they need no pointer)
+static int vq_checked(const char* fn, int64_t cb_off, int K, int bw, int le, int batch) {
+    char msg[200];
+    const char* bad = nullptr;
+    if (batch < 0) bad = "'batch' must be >= 0";
+    else if (K < 2 || K > WN_VQ_MAX_CODES) bad = "'K' must lie in [2, 1024]";
+    else if (bw < 1 || bw > WN_VQ_MAX_WIDTH) bad = "'bw' must lie in [1, 512]";
+    else if (le < 1) bad = "'le' must be >= 1";
+    else if (cb_off < 0) bad = "'cb_off' must be >= 0";
+    else if ((int64_t)batch * le > 0x7fffffffLL - 64) bad = "'batch' * le frames do not fit 31 bits";
+    if (bad) {
+        snprintf(msg, sizeof(msg), "%s: argument %s", fn, bad);
+        return wn_set_error_msg(-4, msg);
+    }
+    return 0;
+}
+int wn_vq_fwd(const float* enc, const float* flat, int64_t cb_off, float* q_out, int32_t* idx, int32_t* counts, float* loss_part, int K,
+              int bw, int le, int batch, wn_stream_t stream) {
+    if (int rc = vq_checked("wn_vq_fwd", cb_off, K, bw, le, batch)) return rc;
+    if (batch == 0) return 0;
+    WN_REQUIRE("wn_vq_fwd", enc, flat, q_out, idx, loss_part);
+    WnVq p;
+    memset(&p, 0, sizeof(p));
+    p.enc = enc; p.flat = flat; p.cb_off = (long)cb_off; p.q_out = q_out; p.idx = idx; p.counts = counts; p.loss_part = loss_part;
+    p.K = K; p.bw = bw; p.le = le; p.batch = batch;
+    return wn_launch_vq_fwd(p, (hipStream_t)stream);
+}
+int wn_vq_bwd(const float* enc, const int32_t* idx, const float* d_q, const float* flat, int64_t cb_off, float beta, float g_scale,
+              float* d_enc, float* flat_grad, int K, int bw, int le, int batch, wn_stream_t stream) {
+    if (int rc = vq_checked("wn_vq_bwd", cb_off, K, bw, le, batch)) return rc;
+    if (batch == 0) return 0;
+    WN_REQUIRE("wn_vq_bwd", enc, idx, d_q, flat, d_enc, flat_grad);
+    WnVq p;
+    memset(&p, 0, sizeof(p));
+    p.enc = enc; p.flat = flat; p.cb_off = (long)cb_off; p.idx = const_cast<int32_t*>(idx); p.d_q = d_q; p.d_enc = d_enc;
+    p.flat_grad = flat_grad; p.K = K; p.bw = bw; p.le = le; p.batch = batch;
+    return wn_launch_vq_bwd(p, beta, g_scale, (hipStream_t)stream);
+}
+int wn_vq_lookup(const int32_t* idx, const float* flat, int64_t cb_off, float* q_out, int32_t* bad, int K, int bw, int le, int batch,
+                 wn_stream_t stream) {
+    if (int rc = vq_checked("wn_vq_lookup", cb_off, K, bw, le, batch)) return rc;
+    if (batch == 0) return 0;
+    WN_REQUIRE("wn_vq_lookup", idx, flat, q_out);
+    return wn_launch_vq_lookup(idx, flat, (long)cb_off, q_out, bad, K, bw, le, batch, (hipStream_t)stream);
 }
 int wn_coll_available(void) { return wn_coll_loaded(); }
 int wn_comm_unique_id(char* id128) { return wn_coll_unique_id(id128); }

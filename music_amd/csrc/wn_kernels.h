@@ -255,6 +255,18 @@ struct WnCondProj {
 };
 int wn_launch_cond_proj_fwd(const WnCondProj& p, hipStream_t st);
 int wn_launch_cond_proj_bwd(const WnCondProj& p, hipStream_t st);
+// vector-quantised bottleneck (wn_vq.hip): the codebook [K][bw] sits at flat + cb_off (its gradient at flat_grad + cb_off)
+#define WN_VQ_PARTIALS 256
+struct WnVq {
+    const float* enc; const float* flat; long cb_off;
+    float* q_out; int32_t* idx; int32_t* counts; float* loss_part;       // forward outputs (counts may be NULL); idx: the backward's input
+    const float* d_q; float* d_enc; float* flat_grad;                    // backward
+    int K, bw, le, batch;
+};
+int wn_launch_vq_fwd(const WnVq& p, hipStream_t st);
+int wn_launch_vq_bwd(const WnVq& p, float beta, float g_scale, hipStream_t st);
+int wn_launch_vq_lookup(const int32_t* idx, const float* flat, long cb_off, float* q_out, int32_t* bad, int K, int bw, int le, int batch,
+                        hipStream_t st);
 // per-timestep softmax + negative log-likelihood over the channel axis of [B][Q][pitch] logits (wn_nll.hip); target NULL: softmax only
 int wn_launch_step_nll(const float* x, long x_bs, int x_pitch, const int64_t* target, float* dx, long dx_bs, int dx_pitch, float* probs,
                        float* row_nll, int32_t* row_hit, float* loss_part, int w, int q, int batch, float inv_n, hipStream_t st);

@@ -1,0 +1,236 @@
+// The vector-quantised bottleneck of the autoencoder (wn_vq_fwd / wn_vq_bwd / wn_vq_lookup in include/wavenet_hip.h): every pooled
+// frame e[b][:, l] of enc [B][Bw][Le] is replaced by its nearest row of the codebook c [K][Bw], a parameter of the flat buffer.
+//
+//   forward   dist(frame, k) = sum_j (e_j - c_kj)^2 (the difference form: no cancellation), idx = the FIRST argmin over k,
+//             q = c[idx] in enc's layout, counts[k] = frames of code k, loss_part = per-workgroup sums of the best distances / (C Bw)
+//   backward  d_e = d_q + c_enc (e - q)   (straight-through + commitment),   d_c[k] = c_cb sum_{frames of k, ascending} (c_k - e)
+//   lookup    q = c[idx] from given codes; an index outside [0, K) gives a NaN frame and raises *bad, it is never dereferenced
+//
+// The work is small and sits between encoder and decoder (C K Bw = 200 x 512 x 64 at config 4): few launches, every codebook row
+// read once per workgroup and coalesced.  Forward: a workgroup stages FT frames in LDS, its NWV waves deal the codes out round-robin
+// (ascending inside a wave, four per pass), lanes run along j; the FT per-lane sums of a code are folded over the wave by a transposing butterfly
+// (7 exchanges for 4 sums instead of 24) that leaves frame f's distance in lanes [16 f, 16 f + 16); a strict < keeps the first
+// minimum of a wave, and the waves' (distance, index) pairs are merged through LDS in wave order, lexicographically - the tie rule.
+// Backward: one launch; the leading workgroups own 4 codes each (a wave per code walks idx in ascending frame order, 64 frames
+// per ballot, and adds the matching frames: no scatter, no atomics), the others form d_e elementwise.  fp32, a fixed summation
+// order, no float atomics: the same bits at every launch.  counts uses integer atomics on a buffer cleared by a memset node.
+#include <limits>
+#include "wn_common.h"
+#include "wn_kernels.h"
+
+namespace {
+
+constexpr int FT = 4;              // frames per tile of vq_fwd_k (the butterfly below is written for 4)
+constexpr int NWV = 8;             // its waves per workgroup
+constexpr int CU = 4;              // codes a wave takes per pass
+constexpr int MAXW = 512;          // bw <= 512: 8 values of j per lane
+constexpr int NJ = MAXW / 64;
+constexpr int CWV = 4;             // vq_bwd_k: waves = codes per workgroup
+
+// frame fr = (clip b, pooled frame l): the offset of its element j = 0 in [B][Bw][Le]; element j sits j * le floats behind it
+__device__ __forceinline__ long frame_base(int fr, int bw, int le) {
+    const int b = fr / le;
+    return (long)b * bw * le + (fr - b * le);
+}
+
+// v0..v3: this lane's partial sums of frames 0..3 -> the sum over all 64 lanes of frame (lane >> 4), in every lane of that group
+__device__ __forceinline__ float fold4(float v0, float v1, float v2, float v3, int lane) {
+    const bool up = lane & 32;
+    const float a = (up ? v2 : v0) + __shfl_xor(up ? v0 : v2, 32);     // lower half: frames 0, 1; upper half: frames 2, 3
+    const float b = (up ? v3 : v1) + __shfl_xor(up ? v1 : v3, 32);
+    const bool odd = lane & 16;
+    float c = (odd ? b : a) + __shfl_xor(odd ? a : b, 16);
+    c += __shfl_xor(c, 8);
+    c += __shfl_xor(c, 4);
+    c += __shfl_xor(c, 2);
+    c += __shfl_xor(c, 1);
+    return c;
+}
+
+__global__ __launch_bounds__(64 * NWV) void vq_fwd_k(WnVq p, float inv_n) {
+    __shared__ float s_e[FT][MAXW];
+    __shared__ float s_bd[NWV][FT];
+    __shared__ int s_bi[NWV][FT];
+    const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int C = p.batch * p.le, tiles = (C + FT - 1) / FT, nj = (p.bw + 63) >> 6;
+    const float* cb = p.flat + p.cb_off;
+    float loss = 0.f;                                      // thread 0: this workgroup's best distances, in frame order
+    for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const int f0 = tile * FT;
+        // (frame fastest: neighbouring threads touch neighbouring l of one row of enc / q_out)
+        for (int o = t; o < FT * p.bw; o += 64 * NWV) {
+            const int j = o / FT, f = o % FT;
+            s_e[f][j] = f0 + f < C ? p.enc[frame_base(f0 + f, p.bw, p.le) + (long)j * p.le] : 0.f;
+        }
+        __syncthreads();
+        float bd = std::numeric_limits<float>::infinity();    // of frame lane >> 4, over this wave's codes
+        int bi = 0;
+        // CU codes per pass, so that their loads and their (dependent) butterflies overlap; a code behind the last one reads row
+        // K - 1 and is left out of the comparison
+        for (int k0 = wave; k0 < p.K; k0 += CU * NWV) {
+            const float* row[CU];
+            float v[CU][FT];
+#pragma unroll
+            for (int u = 0; u < CU; ++u) {
+                row[u] = cb + (long)min(k0 + u * NWV, p.K - 1) * p.bw;
+#pragma unroll
+                for (int f = 0; f < FT; ++f) v[u][f] = 0.f;
+            }
+            for (int i = 0; i < nj; ++i) {
+                const int j = i * 64 + lane;
+                if (j < p.bw) {
+                    const float e0 = s_e[0][j], e1 = s_e[1][j], e2 = s_e[2][j], e3 = s_e[3][j];
+#pragma unroll
+                    for (int u = 0; u < CU; ++u) {
+                        const float c = row[u][j];
+                        const float d0 = e0 - c, d1 = e1 - c, d2 = e2 - c, d3 = e3 - c;
+                        v[u][0] = fmaf(d0, d0, v[u][0]); v[u][1] = fmaf(d1, d1, v[u][1]);
+                        v[u][2] = fmaf(d2, d2, v[u][2]); v[u][3] = fmaf(d3, d3, v[u][3]);
+                    }
+                }
+            }
+            float d[CU];
+#pragma unroll
+            for (int u = 0; u < CU; ++u) d[u] = fold4(v[u][0], v[u][1], v[u][2], v[u][3], lane);
+#pragma unroll
+            for (int u = 0; u < CU; ++u) {                 // codes ascend inside a wave: the first minimum stays
+                const int k = k0 + u * NWV;
+                if (k < p.K && d[u] < bd) { bd = d[u]; bi = k; }
+            }
+        }
+        if ((lane & 15) == 0) { s_bd[wave][lane >> 4] = bd; s_bi[wave][lane >> 4] = bi; }
+        __syncthreads();
+        if (t < FT) {
+            float d = s_bd[0][t];
+            int ix = s_bi[0][t];
+            for (int w = 1; w < NWV; ++w) {
+                const float dw = s_bd[w][t];
+                const int iw = s_bi[w][t];
+                if (dw < d || (dw == d && iw < ix)) { d = dw; ix = iw; }
+            }
+            s_bd[0][t] = d;
+            s_bi[0][t] = ix;
+            if (f0 + t < C) {
+                p.idx[f0 + t] = ix;
+                if (p.counts) atomicAdd(&p.counts[ix], 1);
+            }
+        }
+        __syncthreads();
+        if (t == 0)
+            for (int f = 0; f < FT; ++f)
+                if (f0 + f < C) loss += s_bd[0][f];
+        for (int o = t; o < FT * p.bw; o += 64 * NWV) {
+            const int j = o / FT, f = o % FT;
+            if (f0 + f < C) p.q_out[frame_base(f0 + f, p.bw, p.le) + (long)j * p.le] = cb[(long)s_bi[0][f] * p.bw + j];
+        }
+        __syncthreads();                                   // the next tile overwrites s_e, s_bd and s_bi
+    }
+    if (t == 0) p.loss_part[blockIdx.x] = loss * inv_n;    // every partial is rewritten at every call (a workgroup without a tile: 0)
+}
+
+// element o of [B][Bw][Le] -> its frame (b * le + l) and its j
+__device__ __forceinline__ void elem_of(long o, int bw, int le, int& fr, int& j) {
+    const long bj = o / le;
+    const int l = (int)(o - bj * le), b = (int)(bj / bw);
+    j = (int)(bj - (long)b * bw);
+    fr = b * le + l;
+}
+
+__global__ __launch_bounds__(64 * CWV) void vq_bwd_k(WnVq p, float c_enc, float c_cb, int code_blocks) {
+    const int C = p.batch * p.le;
+    const float* cb = p.flat + p.cb_off;
+    if ((int)blockIdx.x >= code_blocks) {
+        // d_e = d_q + c_enc (e - q): every element is read and then written by one thread (d_enc may be d_q)
+        const long total = (long)C * p.bw, step = (long)(gridDim.x - code_blocks) * (64 * CWV);
+        for (long o = (long)(blockIdx.x - code_blocks) * (64 * CWV) + threadIdx.x; o < total; o += step) {
+            int fr, j;
+            elem_of(o, p.bw, p.le, fr, j);
+            const int ix = p.idx[fr];
+            const float q = (unsigned)ix < (unsigned)p.K ? cb[(long)ix * p.bw + j] : std::numeric_limits<float>::quiet_NaN();
+            p.d_enc[o] = fmaf(c_enc, p.enc[o] - q, p.d_q[o]);
+        }
+        return;
+    }
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int k = blockIdx.x * CWV + wave;
+    if (k >= p.K) return;
+    float ck[NJ], acc[NJ];
+#pragma unroll
+    for (int i = 0; i < NJ; ++i) {
+        const int j = i * 64 + lane;
+        ck[i] = j < p.bw ? cb[(long)k * p.bw + j] : 0.f;
+        acc[i] = 0.f;
+    }
+    for (int c0 = 0; c0 < C; c0 += 64) {
+        const int ix = c0 + lane < C ? p.idx[c0 + lane] : -1;
+        unsigned long long m = __ballot(ix == k);
+        while (m) {                                        // the matching frames of these 64, in ascending order
+            const int f = c0 + __ffsll(m) - 1;
+            m &= m - 1;
+            const float* e = p.enc + frame_base(f, p.bw, p.le);
+#pragma unroll
+            for (int i = 0; i < NJ; ++i) {
+                const int j = i * 64 + lane;
+                if (i * 64 < p.bw && j < p.bw) acc[i] += ck[i] - e[(long)j * p.le];
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < NJ; ++i) {
+        const int j = i * 64 + lane;
+        if (j < p.bw) p.flat_grad[p.cb_off + (long)k * p.bw + j] = c_cb * acc[i];      // a code no frame chose: exactly 0
+    }
+}
+
+__global__ __launch_bounds__(256) void vq_lookup_k(const int32_t* idx, const float* cb, float* q_out, int32_t* bad, int K, int bw, int le,
+                                                   long total) {
+    for (long o = (long)blockIdx.x * 256 + threadIdx.x; o < total; o += (long)gridDim.x * 256) {
+        int fr, j;
+        elem_of(o, bw, le, fr, j);
+        const int ix = idx[fr];
+        const bool ok = (unsigned)ix < (unsigned)K;
+        q_out[o] = ok ? cb[(long)ix * bw + j] : std::numeric_limits<float>::quiet_NaN();
+        if (!ok && bad) *bad = 1;                          // (every writer stores the same value)
+    }
+}
+
+}  // namespace
+
+// The callers (wn_api.hip) have checked the arguments.
+int wn_launch_vq_fwd(const WnVq& p, hipStream_t st) {
+    if (p.batch <= 0) return 0;
+    if (p.counts) {
+        hipError_t e = hipMemsetAsync(p.counts, 0, sizeof(int32_t) * p.K, st);
+        if (e != hipSuccess) return wn_set_error(e, __FILE__, __LINE__);
+    }
+    const double n = (double)p.batch * p.le * p.bw;
+    hipLaunchKernelGGL(vq_fwd_k, dim3(WN_VQ_PARTIALS), dim3(64 * NWV), 0, st, p, (float)(1.0 / n));
+    WN_CHECK_LAUNCH();
+    return 0;
+}
+
+int wn_launch_vq_bwd(const WnVq& p, float beta, float g_scale, hipStream_t st) {
+    if (p.batch <= 0) return 0;
+    const double s = 2.0 / ((double)p.batch * p.le * p.bw);
+    const int code_blocks = (p.K + CWV - 1) / CWV;
+    const long total = (long)p.batch * p.le * p.bw;
+    const int elem_blocks = (int)std::min<long>((total + 64 * CWV - 1) / (64 * CWV), 256);
+    hipLaunchKernelGGL(vq_bwd_k, dim3(code_blocks + elem_blocks), dim3(64 * CWV), 0, st, p, (float)((double)g_scale * beta * s),
+                       (float)((double)g_scale * s), code_blocks);
+    WN_CHECK_LAUNCH();
+    return 0;
+}
+
+int wn_launch_vq_lookup(const int32_t* idx, const float* flat, long cb_off, float* q_out, int32_t* bad, int K, int bw, int le, int batch,
+                        hipStream_t st) {
+    if (batch <= 0) return 0;
+    if (bad) {
+        hipError_t e = hipMemsetAsync(bad, 0, sizeof(int32_t), st);
+        if (e != hipSuccess) return wn_set_error(e, __FILE__, __LINE__);
+    }
+    const long total = (long)batch * le * bw;
+    hipLaunchKernelGGL(vq_lookup_k, dim3((unsigned)std::min<long>((total + 255) / 256, 1024)), dim3(256), 0, st, idx, flat + cb_off, q_out, bad,
+                       K, bw, le, total);
+    WN_CHECK_LAUNCH();
+    return 0;
+}

@@ -167,6 +167,31 @@ class SlabPlan:
         return out
 
 
+class VqStats:
+    """What one forward's wn_vq_fwd left on the device, read on demand (nothing here runs in the step): `mse` and `perplexity` are
+    0-d device tensors, `vq_loss` = (1 + beta) mse, `codes_used` the number of codes at least one frame chose."""
+
+    def __init__(self, part, counts, frames, beta):
+        self.part, self.counts, self.frames, self.beta = part, counts, frames, beta
+
+    @property
+    def mse(self):
+        return self.part.sum()
+
+    @property
+    def vq_loss(self):
+        return self.part.sum() * (1.0 + self.beta)
+
+    @property
+    def perplexity(self):
+        p = self.counts.to(torch.float64) / self.frames
+        return torch.exp(-(p * torch.log(p.clamp_min(1e-300))).sum()).float()
+
+    @property
+    def codes_used(self):
+        return (self.counts > 0).sum()
+
+
 class EngineBase:
     """Host state and the steps every engine runs the same way.  An engine sets `device`, `Q`, `spec`, `flat`, `flat_grad`, calls
     _init_state(), and provides _make_workspace(), _bwd_workspace() and backward_from_dlogits()."""
@@ -221,30 +246,92 @@ class EngineBase:
     learned = False              # net.conditioning == "learned": the N + 1 projections are parameters at the END of the flat buffer
     n_cond = 0                   # their floats: wn_cond_proj_bwd writes that tail of flat_grad, the gather everything in front of it
 
+    vq = False                   # net.bottleneck == "vq": the codebook (K, Bw) is the LAST parameter of the flat buffer, behind the projections
+    n_vq = 0                     # its floats: wn_vq_bwd writes that tail of flat_grad
+    last_vq = None               # VqStats of the last forward (vq only)
+
     @property
     def n_gather(self):
         """Leading elements of flat_grad that the gather of the gradient pack fills."""
-        return self.spec.total - self.n_cond
+        return self.spec.total - self.n_cond - self.n_vq
 
     @property
     def gathered_param_names(self):
-        """The parameters whose gradients come out of the gradient pack: all but the learned projections' 2 (N + 1), the last ones."""
-        return self.param_names[:len(self.param_names) - (2 * (len(self.dil) + 1) if self.learned else 0)]
+        """The parameters whose gradients come out of the gradient pack: all but the learned projections' 2 (N + 1) and the codebook,
+        the last ones."""
+        return self.param_names[:len(self.param_names) - (2 * (len(self.dil) + 1) if self.learned else 0) - (1 if self.vq else 0)]
 
     def _plan_cond(self, net):
-        """Learned mode: where wn_cond_proj_fwd / wn_cond_proj_bwd find the projections in the flat buffers."""
+        """Learned mode: where wn_cond_proj_fwd / wn_cond_proj_bwd find the projections in the flat buffers; the vq bottleneck's
+        codebook behind them."""
         self.learned = getattr(net, "conditioning", "random") == "learned"
+        self.vq = getattr(net, "bottleneck", "continuous") == "vq"
+        if self.vq:
+            if not self.learned:
+                raise ValueError('music_amd: bottleneck="vq" requires conditioning="learned"')
+            self.vq_K, self.vq_beta = int(net.vq_codebook.num_embeddings), float(net.vq_beta)
+            self.vq_off = self.spec.off["vq_codebook.weight"]
+            self.n_vq = self.vq_K * self.Bw
+            assert self.spec.shape["vq_codebook.weight"] == (self.vq_K, self.Bw) and self.vq_off + self.n_vq == self.spec.total
         if not self.learned:
             return
         o, N = self.spec.off, len(self.dil)
         w0, b0 = o["de_cond_layer_stack.0.weight"], o["de_cond_layer_stack.0.bias"]
         stride = 2 * self.Dd * self.Bw + 2 * self.Dd
         wf, bf = o["connection_cond.weight"], o["connection_cond.bias"]
-        # registered last, in stage order (weight, bias per stage): one constant stage stride, and nothing behind them
+        # registered last (the codebook alone behind them), in stage order (weight, bias per stage): one constant stage stride
         assert all(o["de_cond_layer_stack.%d.weight" % i] == w0 + i * stride and o["de_cond_layer_stack.%d.bias" % i] == b0 + i * stride
-                   for i in range(N)) and wf == w0 + N * stride and bf + self.Sd == self.spec.total
+                   for i in range(N)) and wf == w0 + N * stride and bf + self.Sd == self.spec.total - self.n_vq
         self.cond_off = (w0, b0, stride, wf, bf)
-        self.n_cond = self.spec.total - w0
+        self.n_cond = self.spec.total - self.n_vq - w0
+
+    # ------------------------------------------------------------------ vector-quantised bottleneck (the autoencoder's engines)
+    def vq_fwd(self, ws, enc, st):
+        """The pooled encoding e (B, Bw, Le) -> q, every frame its nearest codebook row (wn_vq_fwd, one launch); ws keeps enc_pre = e,
+        vq_idx, vq_counts and the loss partials (fresh tensors per forward: the module hands them out), self.last_vq reads them."""
+        B, _, Le = enc.shape
+        dev = self.device
+        q = torch.empty_like(enc)
+        idx = torch.empty(B, Le, dtype=torch.int32, device=dev)
+        counts = torch.empty(self.vq_K, dtype=torch.int32, device=dev)
+        part = torch.empty(_lib.VQ_NUM_PARTIALS, dtype=torch.float32, device=dev)
+        call("wn_vq_fwd", ptr(enc), ptr(self.flat), self.vq_off, ptr(q), ptr(idx), ptr(counts), ptr(part), self.vq_K, self.Bw, Le, B, st)
+        ws.update(enc_pre=enc, vq_idx=idx, vq_counts=counts, vq_part=part, vq_g=1.0)
+        self.last_vq = VqStats(part, counts, B * Le, self.vq_beta)
+        return q
+
+    def vq_bwd(self, ws, d_q, st):
+        """d_q (what wn_cond_proj_bwd wrote as d enc) -> d e in place, and the codebook's gradient into the tail of flat_grad (wn_vq_bwd,
+        one launch); ws["vq_g"]: the upstream scalar on vq_loss (1 in the fused step, autograd's in the module's backward)."""
+        B, _, Le = d_q.shape
+        call("wn_vq_bwd", ptr(ws["enc_pre"]), ptr(ws["vq_idx"]), ptr(d_q), ptr(self.flat), self.vq_off, self.vq_beta, float(ws.get("vq_g", 1.0)),
+             ptr(d_q), ptr(self.flat_grad), self.vq_K, self.Bw, Le, B, st)
+
+    def vq_backward_scaled(self, ws, dloss, dvq):
+        """backward_from_dlogits of a vq model for upstream gradients `dloss` (0-d device tensor or None) on the reconstruction loss whose
+        d loss / d logits the workspace holds, and `dvq` (likewise) on vq_loss.  The backward is not linear in dloss alone, so
+        d loss / d logits is scaled (and restored behind the backward) rather than the result; dvq reaches wn_vq_bwd as a host float -
+        one read-back, only where vq_loss is part of the loss."""
+        ws["vq_g"] = 0.0 if dvq is None else float(dvq)
+        d_o = self._bwd_workspace(ws)["dO"][:ws["B"] * ws["W"] * self.Q]
+        keep = d_o.clone()
+        if dloss is None:
+            d_o.zero_()
+        else:
+            d_o.mul_(dloss)
+        self.backward_from_dlogits(ws)
+        d_o.copy_(keep)
+
+    def vq_lookup(self, codes):
+        """codes (B, Le) integer -> q (B, Bw, Le) out of the codebook (wn_vq_lookup); a code outside [0, K) raises."""
+        codes = codes.to(device=self.device, dtype=torch.int32).contiguous()
+        B, Le = codes.shape
+        q = torch.empty(B, self.Bw, Le, dtype=torch.float32, device=self.device)
+        bad = torch.zeros(1, dtype=torch.int32, device=self.device)
+        call("wn_vq_lookup", ptr(codes), ptr(self.flat), self.vq_off, ptr(q), ptr(bad), self.vq_K, self.Bw, Le, B, _lib.stream())
+        if int(bad.item()):
+            raise ValueError("music_amd: a code lies outside [0, %d)" % self.vq_K)
+        return q
 
     def _check_cond(self, cond):
         """`cond` of forward / loss_and_grad: the drawn projections in random mode, None in learned mode - nothing is ignored silently."""
@@ -429,6 +516,10 @@ class EngineBase:
             self.step_nll(ws, target, bw["dO"], probs)
         else:
             self.softmax_ce(ws["O"], target, probs, bw["dO"], ws["loss_part"], n)
+        if self.vq:                         # reconstruction loss + vq_loss, under either objective; its upstream scalar is 1
+            ws["vq_g"] = 1.0
+            self.backward_from_dlogits(ws)
+            return torch.add(ws["loss_part"].sum(), ws["vq_part"].sum(), alpha=1.0 + self.vq_beta)
         self.backward_from_dlogits(ws)
         return ws["loss_part"].sum()
 

@@ -215,10 +215,11 @@ class _AutoencoderEngine(EngineBase):
     def _lay(self, t, i, ch, ws):
         return ptr(t, SLACK + i * ws["B"] * ch * ws["pitch"])
 
-    def forward(self, x, cond=None, want_probs=True):
+    def forward(self, x, cond=None, want_probs=True, encode_only=False):
         """cond: list of N+1 (weight (C,Bw,1), bias (C,)) CPU tensors (see wavenet_autoencoder.forward); None with learned
         conditioning, whose projections are parameters of the flat buffer.
-        want_probs=False stops at the pre-softmax logits in ws["O"] (the fused training step)."""
+        want_probs=False stops at the pre-softmax logits in ws["O"] (the fused training step); encode_only=True behind the pooled
+        (and, with a vq bottleneck, quantised) encoding: (None, enc, ws), nothing of the decoder runs."""
         self._check_cond(cond)
         B, Q, T = x.shape
         W = T - self.rf + 1
@@ -272,6 +273,10 @@ class _AutoencoderEngine(EngineBase):
              E, BwP * pitch, pitch, 0, self._bias("bottleneck_layer"), NONE3, NONE3, lo, T, 0)
         enc = torch.empty(B, self.Bw, Le, dtype=torch.float32, device=self.device)
         call("wn_avgpool", E, BwP * pitch, pitch, lo, self.pool, Le, self.Bw, ptr(enc), self.Bw * Le, Le, B, st)
+        if self.vq:                                           # every frame -> its nearest codebook row: the decoder sees q
+            enc = self.vq_fwd(ws, enc, st)
+        if encode_only:
+            return None, enc, ws
 
         # ---------------- conditioning tables: en = Conv1d_rand(enc)  (model1.py:178-179, 216-217)
         Dd, Sd = self.Dd, self.Sd
@@ -533,6 +538,8 @@ class _AutoencoderEngine(EngineBase):
             # ... and they are parameters: d enc, dW and db (into flat_grad's tail) straight from the block tables' layout
             d_enc = torch.empty(B, Bw, Le, dtype=torch.float32, device=self.device)
             self.cond_proj_bwd(d_tab, pair, d_enf, ws["enc"], d_enc, CHd, st)
+            if self.vq:                                       # straight through to e, + the commitment term; the codebook's gradient
+                self.vq_bwd(ws, d_enc, st)
         else:
             d_en = torch.cat([d_tab[:, :, CHd:CHd + Dd], d_tab[:, :, :Dd]], 2)            # (N,B,2Dd,Le) reference row order
             d_enc = torch.einsum("nck,nbcl->bkl", ws["cw"], d_en) + torch.einsum("ck,bcl->bkl", ws["cfw"][:, :, 0], d_enf)
@@ -593,6 +600,7 @@ class _AutoencoderEngine(EngineBase):
         self.mark("en_causal_slab_reduce")
 
 
+BOTTLENECKS = ("continuous", "vq")       # the pooled encoding as it is, or every frame replaced by its nearest codebook row (VQ-VAE)
 CONDITIONING = ("random", "learned")     # the decoder's conditioning projections: drawn afresh per forward (the reference), or parameters
 
 
@@ -612,13 +620,24 @@ class _AutoencoderFunction(torch.autograd.Function):
         ctx.eng, ctx.ws, ctx.gen = eng, ws, ws["gen"]
         ctx.loss_hook = net._last_hook = _losshook.make(eng, ws, grad_on)
         ctx.hold = WorkspaceHold(ws) if (grad_on and any(ctx.needs_input_grad)) else None      # see music_amd/model.py
+        if eng.vq:
+            # the quantised bottleneck: q went to the decoder (net.last_encoding); vq_loss = (1 + beta) mse is a SECOND output of this
+            # node - left out of the user's loss, its upstream gradient is None and neither the codebook nor the commitment term gets any
+            net.last_encoding_pre, net.vq_codes, net.last_vq = ws["enc_pre"], ws["vq_idx"].to(torch.int64), eng.last_vq
+            ctx.set_materialize_grads(False)
+            return probs.detach(), eng.last_vq.vq_loss
         return probs.detach()            # (an alias: the workspace's own reference must not carry the autograd node)
 
     @staticmethod
-    def backward(ctx, dprobs):
+    def backward(ctx, dprobs, dvq=None):
         eng, ws = ctx.eng, ctx.ws
         if ws.get("gen") != ctx.gen:
             raise RuntimeError("music_amd.wavenet_autoencoder: activations were overwritten by a later forward")
+        if eng.vq:
+            # the upstream scalar on vq_loss goes to wn_vq_bwd as a host float (one read-back, only where vq_loss is in the loss)
+            ws["vq_g"] = 0.0 if dvq is None else float(dvq)
+            if dprobs is None:                                  # vq_loss alone was differentiated
+                dprobs = torch.zeros(ws["B"] * ws["W"], eng.Q, dtype=torch.float32, device=eng.device)
         if not _losshook.backward(ctx.loss_hook, eng, ws, dprobs):          # (the loss ran fused: see _losshook.py)
             eng.backward(ws, dprobs)
         if ctx.hold is not None:
@@ -636,12 +655,27 @@ class wavenet_autoencoder(nn.Module):
 
     def __init__(self, filter_width, quantization_channel, dilations, en_residual_channel, en_dilation_channel,
                  en_bottleneck_width, en_pool_kernel_size, de_residual_channel, de_dilation_channel,
-                 de_skip_channel, use_bias, conditioning="random"):
+                 de_skip_channel, use_bias, conditioning="random", bottleneck="continuous", vq_codes=512, vq_beta=0.25):
         super(wavenet_autoencoder, self).__init__()
         if conditioning not in CONDITIONING:
             raise ValueError("music_amd.wavenet_autoencoder: conditioning must be one of %s, not %r"
                              % (", ".join('"%s"' % c for c in CONDITIONING), conditioning))
+        if bottleneck not in BOTTLENECKS:
+            raise ValueError("music_amd.wavenet_autoencoder: bottleneck must be one of %s, not %r"
+                             % (", ".join('"%s"' % c for c in BOTTLENECKS), bottleneck))
+        if bottleneck == "vq":
+            if conditioning != "learned":
+                raise ValueError('music_amd.wavenet_autoencoder: bottleneck="vq" requires conditioning="learned" (with projections drawn '
+                                 'afresh in every forward a codebook means nothing)')
+            if not 2 <= int(vq_codes) <= _lib.VQ_MAX_CODES:
+                raise ValueError("music_amd.wavenet_autoencoder: vq_codes must lie in [2, %d], not %r" % (_lib.VQ_MAX_CODES, vq_codes))
+            if not 1 <= int(en_bottleneck_width) <= _lib.VQ_MAX_WIDTH:
+                raise ValueError('music_amd.wavenet_autoencoder: bottleneck="vq" needs en_bottleneck_width in [1, %d], not %r'
+                                 % (_lib.VQ_MAX_WIDTH, en_bottleneck_width))
+            if not float(vq_beta) >= 0.0:
+                raise ValueError("music_amd.wavenet_autoencoder: vq_beta must be >= 0, not %r" % (vq_beta,))
         self.conditioning = conditioning
+        self.bottleneck, self.vq_num_codes, self.vq_beta = bottleneck, int(vq_codes), float(vq_beta)
         self.filter_width = filter_width
         self.quantization_channel = quantization_channel
         self.dilations = dilations
@@ -688,10 +722,38 @@ class wavenet_autoencoder(nn.Module):
             # the end of the flat buffer; always with a bias, rows in the reference's order (gate first), like the drawn convs
             self.de_cond_layer_stack = nn.ModuleList(nn.Conv1d(en_bottleneck_width, 2 * de_dilation_channel, 1) for _ in dilations)
             self.connection_cond = nn.Conv1d(en_bottleneck_width, de_skip_channel, 1)
+        # after a forward of a vq model: vq_loss (0-d, attached to autograd: add it to the loss), vq_codes (B, Le) int64,
+        # last_encoding = q, last_encoding_pre = e, last_vq = the engine's VqStats
+        self.vq_loss = self.vq_codes = self.last_encoding_pre = self.last_vq = None
+        if bottleneck == "vq":
+            # the codebook (K, Bw), registered BEHIND the learned projections: a seed gives every earlier parameter the continuous
+            # model's values, and it is the last block of the flat buffer; uniform(-1/K, 1/K) (van den Oord et al. 2017)
+            self.vq_codebook = nn.Embedding(self.vq_num_codes, en_bottleneck_width)
+            with torch.no_grad():
+                self.vq_codebook.weight.uniform_(-1.0 / self.vq_num_codes, 1.0 / self.vq_num_codes)
 
     def __setstate__(self, state):
         super(wavenet_autoencoder, self).__setstate__(state)
         self.__dict__.setdefault("conditioning", "random")       # (a module pickled before the attribute existed)
+        self.__dict__.setdefault("bottleneck", "continuous")
+        for k in ("vq_loss", "vq_codes", "last_encoding_pre", "last_vq"):
+            self.__dict__.setdefault(k, None)
+
+    def init_codebook(self, encodings, seed=0):
+        """Data-dependent initialisation: K frames of `encodings` (B, Bw, Le) - pre-quantisation encodings, net.last_encoding_pre -
+        become the codebook, drawn without replacement by a generator seeded with `seed`; fewer than K frames are cycled through."""
+        if getattr(self, "bottleneck", "continuous") != "vq":
+            raise ValueError('music_amd.wavenet_autoencoder: init_codebook needs bottleneck="vq"')
+        w = self.vq_codebook.weight
+        frames = encodings.detach().to(torch.float32).permute(0, 2, 1).reshape(-1, encodings.size(1))
+        if frames.size(1) != w.size(1) or frames.size(0) < 1:
+            raise ValueError("music_amd.wavenet_autoencoder: init_codebook wants (B, %d, Le) encodings, got %s"
+                             % (w.size(1), tuple(encodings.shape)))
+        gen = torch.Generator().manual_seed(int(seed))
+        order = torch.randperm(frames.size(0), generator=gen)
+        pick = order[torch.arange(w.size(0)) % frames.size(0)]
+        with torch.no_grad():
+            w.copy_(frames[pick.to(frames.device)].to(w.device))          # (in place: the parameter may be a view of the flat buffer)
 
     def _cond_modules(self):
         return list(self.de_cond_layer_stack) + [self.connection_cond]
@@ -720,6 +782,12 @@ class wavenet_autoencoder(nn.Module):
             raise RuntimeError('music_amd.wavenet_autoencoder: the checkpoint was saved with conditioning="%s" but this model was built '
                                'with conditioning="%s" (the "conditioning" key of model_params.json); nothing was loaded'
                                % ("learned" if has else "random", mine))
+        has_vq = any(k.startswith("vq_codebook.") for k in state_dict.keys())
+        mine_vq = getattr(self, "bottleneck", "continuous")
+        if has_vq != (mine_vq == "vq"):
+            raise RuntimeError('music_amd.wavenet_autoencoder: the checkpoint was saved with bottleneck="%s" but this model was built '
+                               'with bottleneck="%s" (the "bottleneck" key of model_params.json); nothing was loaded'
+                               % ("vq" if has_vq else "continuous", mine_vq))
         return super(wavenet_autoencoder, self).load_state_dict(state_dict, *args, **kwargs)
 
     def __getstate__(self):
@@ -728,6 +796,7 @@ class wavenet_autoencoder(nn.Module):
         state = self.__dict__.copy()
         state["_engine"] = None
         state["_last_hook"] = None
+        state["vq_loss"] = state["last_vq"] = None           # (an autograd output and the engine's buffers of the last forward)
         return state
 
     def _calc_receptive_field(self):
@@ -791,5 +860,7 @@ class wavenet_autoencoder(nn.Module):
         cond = self.engine_cond()
         self._last_hook = None
         out = _AutoencoderFunction.apply(self, torch.is_grad_enabled(), wave_sample, cond, *list(self.parameters()))
+        if getattr(self, "bottleneck", "continuous") == "vq":
+            out, self.vq_loss = out
         hook, self._last_hook = self._last_hook, None
         return _losshook.wrap(out, hook) if self.fuse_loss else out

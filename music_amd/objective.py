@@ -72,15 +72,25 @@ class _NLLFunction(torch.autograd.Function):
         eng.step_nll(ws, _flat_target(target, ws), eng._bwd_workspace(ws)["dO"] if need else None)
         ctx.eng, ctx.ws, ctx.gen = eng, ws, ws["gen"]
         ctx.hold = WorkspaceHold(ws) if need else None          # see music_amd/model.py
+        if getattr(eng, "vq", False):
+            # a vq autoencoder: vq_loss is a second output of this node, which nll_loss leaves in net.vq_loss for the caller to add
+            net.last_encoding_pre, net.vq_codes, net.last_vq = ws["enc_pre"], ws["vq_idx"].to(torch.int64), eng.last_vq
+            ctx.set_materialize_grads(False)
+            return ws["loss_part"].sum(), eng.last_vq.vq_loss
         return ws["loss_part"].sum()
 
     @staticmethod
-    def backward(ctx, dloss):
+    def backward(ctx, dloss, dvq=None):
         eng, ws = ctx.eng, ctx.ws
         if ws.get("gen") != ctx.gen:
             raise RuntimeError("music_amd.objective: the activations of this forward were overwritten by a later forward of the "
                                "same module before backward() ran")
-        eng.backward_from_dlogits(ws)
+        vq = getattr(eng, "vq", False)
+        if vq:
+            eng.vq_backward_scaled(ws, dloss, dvq)
+            dloss = 1.0
+        else:
+            eng.backward_from_dlogits(ws)
         if ctx.hold is not None:
             ctx.hold.release()
         g = eng.flat_grad * dloss
@@ -101,7 +111,10 @@ def nll_loss(net, x, target):
     """Mean negative log-likelihood (nats per sample) of `target` (B, W) or (B W,) int64 under the per-timestep softmax of
     net's logits for the one-hot x (B, Q, T): a 0-d tensor whose backward() gives the parameter gradients (and the input's, when it
     requires grad).  A target outside [0, Q) makes the loss NaN."""
-    return _NLLFunction.apply(net, torch.is_grad_enabled(), x, target, *_params(net))
+    out = _NLLFunction.apply(net, torch.is_grad_enabled(), x, target, *_params(net))
+    if isinstance(out, tuple):                                  # a vq autoencoder: the caller adds net.vq_loss
+        out, net.vq_loss = out
+    return out
 
 
 def step_probs(net, x):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of single kernels of the hot path at BASELINE config-2 shapes (GPU only).
 
-    python tools/kbench.py [fwd|bwd|epi|dx|skip|decode|ae|guard|ema|nll|cond|all] [--reps N] [--precision f16x3,bf16x3]
+    python tools/kbench.py [fwd|bwd|epi|dx|skip|decode|ae|guard|ema|nll|cond|vq|all] [--reps N] [--precision f16x3,bf16x3]
 
 Prints per-phase / per-layer kernel times measured with HIP events on the launch stream.
 """
@@ -18,6 +18,103 @@ sys.path.insert(0, ROOT)
 from bench import CFG, B_LOCAL, T  # noqa: E402
 
 
+def _median_spread(v):
+    v = sorted(v)
+    return round(float(np.median(v)), 3), round(v[-1] - v[0], 3)
+
+
+def vq_bench(reps, alternations=6):
+    """`vq`: the vector-quantised bottleneck.  (a) wn_vq_fwd and wn_vq_bwd alone at config 4's shape (B 8, Bw 64, Le 25, K 512) and at
+    the shipped autoencoder's (B 4, Bw 512, Le 32, K 512), HIP events around `reps` launches; (b) the fused config-4 step (forward,
+    loss, backward, flat Adam) of a vq model against the continuous model, both with learned conditioning.  Everything is
+    alternated `alternations` times on one device: medians and spreads (largest - smallest) over the alternations."""
+    import time
+    from music_amd import _lib
+    from music_amd._lib import call, ptr
+    from music_amd.model1 import wavenet_autoencoder
+    st = _lib.stream()
+    res = {"alternations": alternations}
+    rng = np.random.default_rng(0)
+    shapes = {"config4": (8, 64, 25, 512), "shipped": (4, 512, 32, 512)}
+    bufs = {}
+    for name, (B, Bw, Le, K) in shapes.items():
+        enc = torch.from_numpy(rng.standard_normal((B, Bw, Le)).astype(np.float32)).cuda()
+        flat = torch.from_numpy(rng.standard_normal(K * Bw).astype(np.float32)).cuda()
+        bufs[name] = dict(enc=enc, flat=flat, q=torch.empty_like(enc), idx=torch.empty(B, Le, dtype=torch.int32, device="cuda"),
+                          counts=torch.empty(K, dtype=torch.int32, device="cuda"),
+                          part=torch.empty(_lib.VQ_NUM_PARTIALS, dtype=torch.float32, device="cuda"), d=torch.randn_like(enc),
+                          grad=torch.empty_like(flat))
+
+    def launches(name, which, n):
+        B, Bw, Le, K = shapes[name]
+        b = bufs[name]
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        torch.cuda.synchronize()
+        ev[0].record()
+        for _ in range(n):
+            if which == "fwd":
+                call("wn_vq_fwd", ptr(b["enc"]), ptr(b["flat"]), 0, ptr(b["q"]), ptr(b["idx"]), ptr(b["counts"]), ptr(b["part"]), K, Bw, Le, B, st)
+            else:
+                call("wn_vq_bwd", ptr(b["enc"]), ptr(b["idx"]), ptr(b["d"]), ptr(b["flat"]), 0, 0.25, 1.0, ptr(b["d"]), ptr(b["grad"]), K, Bw,
+                     Le, B, st)
+        ev[1].record()
+        torch.cuda.synchronize()
+        return ev[0].elapsed_time(ev[1]) / n * 1e3
+    times = {(n, w): [] for n in shapes for w in ("fwd", "bwd")}
+    for key in times:
+        launches(*key, 20)                                                    # warm
+    for _ in range(alternations):
+        for key in times:
+            times[key].append(launches(*key, max(reps, 100)))
+    for (n, w), v in times.items():
+        res["wn_vq_%s_%s_us" % (w, n)], res["wn_vq_%s_%s_us_spread" % (w, n)] = _median_spread(v)
+    # ---- the fused config-4 step
+    cfg = dict(filter_width=2, quantization_channel=256, dilations=CFG["dilations"], en_residual_channel=64, en_dilation_channel=64,
+               en_bottleneck_width=64, en_pool_kernel_size=512, de_residual_channel=64, de_dilation_channel=64, de_skip_channel=256,
+               use_bias=False, conditioning="learned")
+    codes = torch.from_numpy(rng.integers(0, 256, size=(B_LOCAL, T)).astype(np.int32)).cuda()
+    engs = {}
+    for mode in ("continuous", "vq"):
+        torch.manual_seed(0)
+        net = wavenet_autoencoder(bottleneck=mode, vq_codes=512, **cfg).cuda()
+        eng = net._engine_for(torch.device("cuda", 0))
+        eng.adam_init(lr=1e-4)
+        engs[mode] = (net, eng)
+    from music_amd.faster_audio_data import onehot_device
+    x = onehot_device(codes, 256, True)
+    W = T - engs["vq"][0].receptive_field + 1
+    target = torch.from_numpy(rng.integers(0, 256, size=(B_LOCAL * W,)).astype(np.int64)).cuda()
+    with torch.no_grad():
+        _, _, ws0 = engs["vq"][1].forward(x, None, want_probs=False, encode_only=True)
+    engs["vq"][0].init_codebook(ws0["enc_pre"], seed=0)                       # (codes in use, as in a trained model)
+
+    def steps(mode, n):
+        eng = engs[mode][1]
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            loss = eng.loss_and_grad(x, target, None)
+            eng.adam_step()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / n * 1e3, float(loss)
+    for mode in engs:
+        steps(mode, 5)
+    step_ms = {m: [] for m in engs}
+    for _ in range(alternations):
+        for mode in engs:
+            ms, loss = steps(mode, max(reps, 20))
+            step_ms[mode].append(ms)
+            res["fused_step_loss_" + mode] = round(loss, 5)
+    for mode, v in step_ms.items():
+        res["fused_step_ms_" + mode], res["fused_step_ms_%s_spread" % mode] = _median_spread(v)
+    res["fused_step_ms_vq_minus_continuous"] = round(res["fused_step_ms_vq"] - res["fused_step_ms_continuous"], 3)
+    res["fused_step_ms_by_alternation"] = {m: [round(t, 3) for t in v] for m, v in step_ms.items()}
+    stats = engs["vq"][1].last_vq
+    res["vq_codes_used"], res["vq_perplexity"] = int(stats.codes_used), round(float(stats.perplexity), 2)
+    res["shape_config4_step"] = dict(B=B_LOCAL, T=T, frames=B_LOCAL * (W // 512), Bw=64, K=512)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", nargs="?", default="all")
@@ -25,6 +122,8 @@ def main():
     ap.add_argument("--precision", default="f16x3,bf16x3")
     ap.add_argument("--overlap", type=int, default=1)
     args = ap.parse_args()
+    if args.what == "vq":
+        return vq_bench(args.reps)
     from music_amd.model import wavenet
     from music_amd import _lib
     from music_amd._lib import call, ptr
