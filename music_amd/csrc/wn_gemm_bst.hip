@@ -1,6 +1,6 @@
 // B-stationary form of the wide channel-mixing product (time on the MFMA lanes) for SHORT reductions and MANY rows:
 //
-//   out[m][t + out_shift] = mask( bias[m] + sum_k W[m][k] * pre(in[k][t + shift0]) ),   K = 32 ks0 <= 256, one tap
+//   out[m][t + out_shift] = mask( bias[m] + sum_k W[m][k] * pre(in[k][t + shift0]) ),   K = 32 ks0 = 256 (ks0 == 8 only), one tap, no residual
 //
 // i.e. every "weights transposed" data-gradient product of the epilogue whose K is a skip-channel count - above all
 // dZ = Ws^T dU (wavenet/model.py:127-134 backward: 30 x 64 = 1920 rows against K = 256, 795 MB of output at config 2).

@@ -88,18 +88,22 @@ __global__ __launch_bounds__(GR_THREADS, 2) void chan_gemm_rw_k(WnGemmArgs a, Gr
         for (int it = 0; it < n_items; ++it) {
             const Pos ps = pos_k(it);
             const int tl = ps.t0 + 2 * c;
-            // residual rows of this item (consumed after the products)
+            // residual rows of this item (consumed after the products).  Without a residual / a mask the loads stay (unconditional,
+            // as the L waves') but go to the ONE address the L waves use for dead loads, a.in0 + a.in_lo with row stride 0: inside
+            // the input window (the launcher wants it >= 2 columns wide), whatever rows and slack the input has
             f32x2 rr[4];
-            const float* rp = (a.resid ? a.resid : a.in0) + (size_t)ps.b * (a.resid ? a.resid_bstride : a.in_bstride) +
-                              (size_t)(16 * g + 4 * q) * (a.resid ? a.resid_pitch : a.in_pitch) + tl;
+            const float* rp = a.resid ? a.resid + (size_t)ps.b * a.resid_bstride + (size_t)(16 * g + 4 * q) * a.resid_pitch + tl
+                                      : a.in0 + a.in_lo;
+            const size_t rs = a.resid ? (size_t)a.resid_pitch : 0;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) rr[i] = gr_ld2u(rp + (size_t)i * (a.resid ? a.resid_pitch : a.in_pitch));
+            for (int i = 0; i < 4; ++i) rr[i] = gr_ld2u(rp + i * rs);
             // mask rows (keep where > 0; applied before the residual, as chan_gemm_k does)
             f32x2 mk[4];
-            const float* mp = (a.mask ? a.mask : a.in0) + (size_t)ps.b * (a.mask ? a.mask_bstride : a.in_bstride) +
-                              (size_t)(16 * g + 4 * q) * (a.mask ? a.mask_pitch : a.in_pitch) + tl;
+            const float* mp = a.mask ? a.mask + (size_t)ps.b * a.mask_bstride + (size_t)(16 * g + 4 * q) * a.mask_pitch + tl
+                                     : a.in0 + a.in_lo;
+            const size_t ms = a.mask ? (size_t)a.mask_pitch : 0;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) mk[i] = gr_ld2u(mp + (size_t)i * (a.mask ? a.mask_pitch : a.in_pitch));
+            for (int i = 0; i < 4; ++i) mk[i] = gr_ld2u(mp + i * ms);
 
             const uint16_t* st = lds + (size_t)(it & 1) * STAGE;
             f32x4 acc[2];
