@@ -464,6 +464,34 @@ int wn_vq_bwd(const float* enc, const int32_t* idx, const float* d_q, const floa
               float* d_enc, float* flat_grad, int K, int bw, int le, int batch, wn_stream_t stream);
 int wn_vq_lookup(const int32_t* idx, const float* flat, int64_t cb_off, float* q_out, int32_t* bad, int K, int bw, int le, int batch,
                  wn_stream_t stream);
+/* ---- EMA codebook updates for the bottleneck above (van den Oord et al. 2017, appendix A.1) and the restart of dead codes: the codebook
+ * follows the running mean of the frames assigned to its rows instead of a gradient.  stat and state share ONE layout, K (bw + 1)
+ * floats: K counts, then K rows of bw sums.  stat = [n | s]: n_k the frames with idx = k (as a float), s_k their sum in ascending
+ * frame order.  state = [N | m]: running usage and running sums; m / N is the codebook, [1 | c] the initial state.
+ * wn_vq_bwd_stats takes the place of wn_vq_bwd, in ONE launch: d_enc exactly as there (the same formula and bits; d_enc may alias
+ * d_q; an idx outside [0, K) is compared, never dereferenced, and turns that frame's d_enc into NaN), ALL K (bw + 1) entries of
+ * stat, and exactly 0 into all K codebook rows of flat_grad (nothing else of flat_grad is touched): vq_loss = beta mse here.
+ * wn_vq_ema_update, with g = decay, updates state and the codebook rows of flat IN PLACE, in two launches:
+ *   N'_k = g N_k + (1 - g) n_k      m'_k = g m_k + (1 - g) s_k      tot = sum_k N'_k      Nhat_k = (N'_k + eps) / (tot + K eps) tot
+ *   c'_k = m'_k / Nhat_k
+ *   restart > 0: the dead codes (N'_k < restart), in ascending index, are paired with the donors (not dead, n_k >= 2 in THIS stat)
+ *   in the order of n_k descending, ties to the smaller index; the d-th dead code j takes the d-th donor k: c'_j = m'_j = s_k / n_k
+ *   (the donor's batch mean), N'_j = 1; the donor is unchanged; a dead code without a donor stays as the plain update left it.
+ * A pure function of stat, state and the scalars: replicas holding the same stat stay bit-identical.  The first launch (one
+ * workgroup) reads the old N and stat and writes only `work`, WN_VQ_EMA_WORK_BYTES of device scratch; in the second every
+ * workgroup reads and writes only its own codes' rows of state and flat (and reads work and stat).  info (int32[2] on the device,
+ * may be NULL): info[0] += the codes restarted by this call, info[1] = the dead codes left without a donor.  guard_state (may be
+ * NULL): the wn_guard_state of the wn_grad_guard before it on the stream; with its skip set NOTHING is written - codebook, state
+ * and info stay bit for bit.
+ * On `stream`, no allocation, no synchronisation, no float atomics, fp32 in a fixed order: the same bits at every launch.  Limits and
+ * refusals (-4, function and argument named, before any launch) as for wn_vq_bwd; wn_vq_bwd_stats with batch == 0 returns 0 and
+ * writes nothing (NULLs allowed).  wn_vq_ema_update refuses: K < 2 or K > 1024; bw < 1 or bw > 512; cb_off < 0; decay outside
+ * (0, 1); eps < 0; restart < 0 (or a NaN for any of the three); NULL flat, stat, state or work; a guard_state off 8-byte alignment. */
+#define WN_VQ_EMA_WORK_BYTES 4112
+int wn_vq_bwd_stats(const float* enc, const int32_t* idx, const float* d_q, const float* flat, int64_t cb_off, float beta, float g_scale,
+                    float* d_enc, float* flat_grad, float* stat, int K, int bw, int le, int batch, wn_stream_t stream);
+int wn_vq_ema_update(float* flat, int64_t cb_off, const float* stat, float* state, void* work, int32_t* info, int K, int bw,
+                     float decay, float eps, float restart, const wn_guard_state* guard_state, wn_stream_t stream);
 /* The reference's nn.DataParallel gradient reduction (wavenet/train.py:116-122) as ONE in-place sum over the ranks of the flat
  * fp32 gradient buffer: ncclAllReduce(buf, buf, n, ncclFloat32, ncclSum, comm, stream) on the caller's RCCL communicator
  * (`comm` = an ncclComm_t).  The 1 / world_size of the mean goes into wn_adam_flat's gscale.  Returns -5 when RCCL is neither

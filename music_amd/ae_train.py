@@ -32,6 +32,14 @@ commitment term, default 0.25).  With it the loss of every step is the reconstru
 ``print_every`` goes to ``vq_log.log`` (mse, perplexity of the code usage, codes used), and the optional train_params.json key
 ``"vq_init"`` (``"uniform"``, the default, or ``"data"``) initialises the codebook from the first batch's pre-quantisation
 encoding (``net.init_codebook``) when training starts from scratch.
+``"vq_update"`` (``"gradient"``, the default: the codebook is trained by its loss term; ``"ema"``: every row follows the
+exponential moving average of the frames assigned to it, van den Oord et al. 2017 appendix A.1 - no learning rate, no optimizer
+state, ``vq_loss`` is the commitment term alone), with ``"vq_decay"`` (in (0, 1), default 0.99), ``"vq_eps"`` (smoothing of the
+usage, default 1e-5) and ``"vq_restart"`` (default 0 = off: a code whose running usage falls below it restarts from the batch mean
+of one of the most used codes' frames).  The update runs on the device behind every optimizer step (a step the guard skips leaves it
+alone); under data parallelism the per-code counts and sums are summed over the ranks first, so every replica makes the same update.
+The ``vq_log.log`` line then ends with ``, restarted N``, the codes restarted since the line before.  A checkpoint carries the running
+state (``vq_ema_state``) and only loads into a model built with the same ``"vq_update"``.
 """
 import glob
 import os
@@ -72,6 +80,7 @@ def _host_guarded(cls):
     class Guarded(guard.GuardedOptimizer, cls):
         def __init__(self, model, max_grad_norm, skip_nonfinite, ema_decay=None, ema_warmup=False, **kw):
             super().__init__(model.parameters(), **kw)
+            self._model = model
             self._guard_setup(max_grad_norm, skip_nonfinite)
             self._ema_setup(model.named_parameters(), ema_decay, ema_warmup)
 
@@ -178,7 +187,7 @@ def train():
     dataloader = audio_data_loader(**dataset_params)
     if cuda_available:
         net = net.cuda()
-    wdist.broadcast_parameters(list(net.parameters()))
+    wdist.broadcast_parameters(list(net.parameters()) + list(net.buffers()))      # (buffers: the running state of an EMA-updated codebook)
     max_gn, skip_nf = guard.guard_options(train_params)
     ema_decay, ema_warmup = ema.ema_options(train_params)
     fused = (bool(train_params.get("fused_step")) and cuda_available and
@@ -218,6 +227,7 @@ def train():
             lambda: engine.guard_report() if fused else optimizer.guard_report(),
             lambda: guard.engine_named_grads(engine) if fused else [(n, p.grad) for n, p in net.named_parameters()])
     is_vq = getattr(net, "bottleneck", "continuous") == "vq"
+    is_vq_ema = is_vq and getattr(net, "vq_update", "gradient") == "ema"
     vq_init = train_params.get("vq_init", "uniform")
     if vq_init not in ("uniform", "data"):
         raise ValueError('train_params.json: "vq_init" must be "uniform" or "data", not %r' % (vq_init,))
@@ -238,6 +248,7 @@ def train():
                                                                 encode_only=True)
                 net.init_codebook(ws0["enc_pre"], seed=step_seed)
                 wdist.broadcast_parameters([net.vq_codebook.weight])
+                net.reset_vq_ema_state()                      # (from the broadcast rows: the same running state on every replica)
                 if shadow is not None and "vq_codebook.weight" in (getattr(shadow, "tensors", None) or {}):
                     shadow.tensors["vq_codebook.weight"].copy_(net.vq_codebook.weight.detach())      # the shadow was taken before
             if world > 1 and net.conditioning != "learned":
@@ -260,12 +271,23 @@ def train():
                     loss = engine.loss_and_grad(piece.to(device).float().contiguous(), target.to(device), net.engine_cond())
                 else:
                     engine.flat_grad.zero_()
+                    if is_vq_ema:
+                        engine.vq_stat.zero_()                # an empty shard: no frames
                 wdist.allreduce_flat_(engine.flat_grad, average=False, scale=dp_scale)
+                if is_vq_ema:                                 # counts and sums of ALL ranks' frames: sums, so no dp_scale
+                    wdist.allreduce_flat_(engine.vq_stat, average=False, scale=1.0)
                 engine.adam_step(gscale=1.0 / wdist.world())
             else:
                 loss = optimizer.step(closure) if isinstance(optimizer, optim.LBFGS) else closure()
+                if is_vq_ema:
+                    eng = net._engine_for(device)
+                    if piece is None:
+                        eng.vq_stat.zero_()
+                    wdist.allreduce_flat_(eng.vq_stat, average=False, scale=1.0)
                 if not isinstance(optimizer, optim.LBFGS):
                     optimizer.step()
+                    if is_vq_ema and not isinstance(optimizer, guard.GuardedOptimizer):
+                        eng.vq_ema_step()                     # (a GuardedOptimizer's step ends with it itself)
             loss = loss.detach() * dp_scale
             total_loss += loss.detach().double()
             num_trained += 1
@@ -280,8 +302,9 @@ def train():
                     guard_log.tick(num_trained)
                 stats = (engine.last_vq if fused else net.last_vq) if vq_log_file is not None else None
                 if stats is not None:                         # (the last step's figures, read back where the loss is)
-                    vq_log_file.writelines('Trained over %d pieces, vq mse %s, perplexity %s, codes used %d\n'
-                                           % (num_trained, stats.mse.item(), stats.perplexity.item(), int(stats.codes_used.item())))
+                    vq_log_file.writelines('Trained over %d pieces, vq mse %s, perplexity %s, codes used %d%s\n'
+                                           % (num_trained, stats.mse.item(), stats.perplexity.item(), int(stats.codes_used.item()),
+                                              ", restarted %d" % net._engine_for(device).vq_restarted() if is_vq_ema else ""))
                     vq_log_file.flush()
                 total_loss.zero_()
             if validation is not None:
@@ -291,7 +314,7 @@ def train():
             _rotate_checkpoints(stored, train_params["max_check_points"])
             save_model(net, epoch_trained + epoch + 1, train_params["restore_dir"])
             if shadow is not None:
-                ema.save_shadow(shadow, train_params["restore_dir"] + PREFIX + str(epoch_trained + epoch + 1) + ".ema")
+                ema.save_shadow(shadow, train_params["restore_dir"] + PREFIX + str(epoch_trained + epoch + 1) + ".ema", net)
             store_log_file.writelines('Epoch' + str(epoch_trained + epoch + 1) + 'model saved!')
             store_log_file.flush()
     if is_writer:

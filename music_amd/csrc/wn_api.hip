@@ -57,6 +57,7 @@ static_assert(WN_F16X3 == WN_MODE_F16X3 && WN_F16X1 == WN_MODE_F16X1 && WN_BF16X
               WN_BF16X1 == WN_MODE_BF16X1, "mode enums out of sync");
 static_assert(WN_CE_NUM_PARTIALS == WN_CE_PARTIALS, "partials out of sync");
 static_assert(WN_VQ_NUM_PARTIALS == WN_VQ_PARTIALS && WN_VQ_MAX_CODES == WN_DEC_MAX_Q, "vq constants out of sync");
+static_assert(WN_VQ_MAX_CODES == WN_VQ_MAX_K && WN_VQ_EMA_WORK_BYTES == WN_VQ_EMA_WORK, "vq ema constants out of sync");
 
 // ---- cached-queue decode: the ONE call path behind the six exported decode entries -------------------------------------------
 // Every entry forwards its arguments (and the defaults of those it does not take) to decode_checked with the checks it applies:
@@ -503,6 +504,28 @@ int wn_vq_lookup(const int32_t* idx, const float* flat, int64_t cb_off, float* q
     if (batch == 0) return 0;
     WN_REQUIRE("wn_vq_lookup", idx, flat, q_out);
     return wn_launch_vq_lookup(idx, flat, (long)cb_off, q_out, bad, K, bw, le, batch, (hipStream_t)stream);
+}
+int wn_vq_bwd_stats(const float* enc, const int32_t* idx, const float* d_q, const float* flat, int64_t cb_off, float beta, float g_scale,
+                    float* d_enc, float* flat_grad, float* stat, int K, int bw, int le, int batch, wn_stream_t stream) {
+    if (int rc = vq_checked("wn_vq_bwd_stats", cb_off, K, bw, le, batch)) return rc;
+    if (batch == 0) return 0;
+    WN_REQUIRE("wn_vq_bwd_stats", enc, idx, d_q, flat, d_enc, flat_grad, stat);
+    WnVq p;
+    memset(&p, 0, sizeof(p));
+    p.enc = enc; p.flat = flat; p.cb_off = (long)cb_off; p.idx = const_cast<int32_t*>(idx); p.d_q = d_q; p.d_enc = d_enc;
+    p.flat_grad = flat_grad; p.K = K; p.bw = bw; p.le = le; p.batch = batch;
+    return wn_launch_vq_bwd_stats(p, beta, g_scale, stat, (hipStream_t)stream);
+}
+int wn_vq_ema_update(float* flat, int64_t cb_off, const float* stat, float* state, void* work, int32_t* info, int K, int bw,
+                     float decay, float eps, float restart, const wn_guard_state* guard_state, wn_stream_t stream) {
+    if (int rc = vq_checked("wn_vq_ema_update", cb_off, K, bw, 1, 1)) return rc;
+    if (!(decay > 0.f && decay < 1.f)) return wn_set_error_msg(-4, "wn_vq_ema_update: argument 'decay' must lie in (0, 1)");
+    if (!(eps >= 0.f)) return wn_set_error_msg(-4, "wn_vq_ema_update: argument 'eps' must be >= 0");
+    if (!(restart >= 0.f)) return wn_set_error_msg(-4, "wn_vq_ema_update: argument 'restart' must be >= 0");
+    WN_REQUIRE("wn_vq_ema_update", flat, stat, state, work);
+    if ((uintptr_t)guard_state % 8 != 0) return wn_set_error_msg(-4, "wn_vq_ema_update: argument 'guard_state' needs 8-byte alignment");
+    return wn_launch_vq_ema_update(flat, (long)cb_off, stat, state, work, info, K, bw, decay, eps, restart, guard_state,
+                                   (hipStream_t)stream);
 }
 int wn_coll_available(void) { return wn_coll_loaded(); }
 int wn_comm_unique_id(char* id128) { return wn_coll_unique_id(id128); }

@@ -267,6 +267,12 @@ int wn_launch_vq_fwd(const WnVq& p, hipStream_t st);
 int wn_launch_vq_bwd(const WnVq& p, float beta, float g_scale, hipStream_t st);
 int wn_launch_vq_lookup(const int32_t* idx, const float* flat, long cb_off, float* q_out, int32_t* bad, int K, int bw, int le, int batch,
                         hipStream_t st);
+// EMA mode: stat = [n | s] and state = [N | m], K counts then K rows of bw; work: WN_VQ_EMA_WORK bytes of device scratch
+#define WN_VQ_MAX_K 1024
+#define WN_VQ_EMA_WORK (16 + 4 * WN_VQ_MAX_K)
+int wn_launch_vq_bwd_stats(const WnVq& p, float beta, float g_scale, float* stat, hipStream_t st);
+int wn_launch_vq_ema_update(float* flat, long cb_off, const float* stat, float* state, void* work, int32_t* info, int K, int bw,
+                            float decay, float eps, float restart, const wn_guard_state* guard, hipStream_t st);
 // per-timestep softmax + negative log-likelihood over the channel axis of [B][Q][pitch] logits (wn_nll.hip); target NULL: softmax only
 int wn_launch_step_nll(const float* x, long x_bs, int x_pitch, const int64_t* target, float* dx, long dx_bs, int dx_pitch, float* probs,
                        float* row_nll, int32_t* row_hit, float* loss_part, int w, int q, int batch, float inv_n, hipStream_t st);

@@ -14,7 +14,16 @@
 // Backward: one launch; the leading workgroups own 4 codes each (a wave per code walks idx in ascending frame order, 64 frames
 // per ballot, and adds the matching frames: no scatter, no atomics), the others form d_e elementwise.  fp32, a fixed summation
 // order, no float atomics: the same bits at every launch.  counts uses integer atomics on a buffer cleared by a memset node.
+//
+// EMA mode (wn_vq_bwd_stats / wn_vq_ema_update): the codebook follows the running mean of its frames instead of a gradient.
+//   stats     the backward's launch with the code workgroups adding e instead of c_k - e: stat = [n | s], the frames per code (as
+//             floats) and their sums in ascending frame order; the codebook's rows of flat_grad become exactly 0
+//   update    N' = g N + (1 - g) n, m' = g m + (1 - g) s, c' = m' / Nhat with the usage smoothed by eps; a code whose N' fell
+//             below `restart` takes the batch mean s / n of a donor (the d-th dead code, ascending, the d-th code by n descending).
+// Two launches: ONE workgroup ranks the K codes (counting ranks over LDS) and writes only the scratch `work`; then a wave per code
+// rewrites its own rows of state and codebook from them - no workgroup reads what another writes, so the update is in place.
 #include <limits>
+#include "../../include/wavenet_hip.h"
 #include "wn_common.h"
 #include "wn_kernels.h"
 
@@ -136,21 +145,24 @@ __device__ __forceinline__ void elem_of(long o, int bw, int le, int& fr, int& j)
     fr = b * le + l;
 }
 
+// the element workgroups of the backward launches (blocks [code_blocks, gridDim.x)): d_e = d_q + c_enc (e - q); every element is read
+// and then written by one thread (d_enc may be d_q)
+__device__ __forceinline__ void vq_bwd_elems(const WnVq& p, float c_enc, int code_blocks) {
+    const float* cb = p.flat + p.cb_off;
+    const long total = (long)p.batch * p.le * p.bw, step = (long)(gridDim.x - code_blocks) * (64 * CWV);
+    for (long o = (long)(blockIdx.x - code_blocks) * (64 * CWV) + threadIdx.x; o < total; o += step) {
+        int fr, j;
+        elem_of(o, p.bw, p.le, fr, j);
+        const int ix = p.idx[fr];
+        const float q = (unsigned)ix < (unsigned)p.K ? cb[(long)ix * p.bw + j] : std::numeric_limits<float>::quiet_NaN();
+        p.d_enc[o] = fmaf(c_enc, p.enc[o] - q, p.d_q[o]);
+    }
+}
+
 __global__ __launch_bounds__(64 * CWV) void vq_bwd_k(WnVq p, float c_enc, float c_cb, int code_blocks) {
     const int C = p.batch * p.le;
     const float* cb = p.flat + p.cb_off;
-    if ((int)blockIdx.x >= code_blocks) {
-        // d_e = d_q + c_enc (e - q): every element is read and then written by one thread (d_enc may be d_q)
-        const long total = (long)C * p.bw, step = (long)(gridDim.x - code_blocks) * (64 * CWV);
-        for (long o = (long)(blockIdx.x - code_blocks) * (64 * CWV) + threadIdx.x; o < total; o += step) {
-            int fr, j;
-            elem_of(o, p.bw, p.le, fr, j);
-            const int ix = p.idx[fr];
-            const float q = (unsigned)ix < (unsigned)p.K ? cb[(long)ix * p.bw + j] : std::numeric_limits<float>::quiet_NaN();
-            p.d_enc[o] = fmaf(c_enc, p.enc[o] - q, p.d_q[o]);
-        }
-        return;
-    }
+    if ((int)blockIdx.x >= code_blocks) return vq_bwd_elems(p, c_enc, code_blocks);
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int k = blockIdx.x * CWV + wave;
     if (k >= p.K) return;
@@ -180,6 +192,154 @@ __global__ __launch_bounds__(64 * CWV) void vq_bwd_k(WnVq p, float c_enc, float 
         const int j = i * 64 + lane;
         if (j < p.bw) p.flat_grad[p.cb_off + (long)k * p.bw + j] = c_cb * acc[i];      // a code no frame chose: exactly 0
     }
+}
+
+// EMA mode's backward: the element workgroups of vq_bwd_k as they are; a code's wave adds its frames e (ascending, as there) and counts
+// them: stat = [n (K floats) | s (K rows of bw)], every entry written; the codebook's rows of flat_grad: exactly 0
+__global__ __launch_bounds__(64 * CWV) void vq_bwd_stats_k(WnVq p, float c_enc, int code_blocks, float* __restrict__ stat) {
+    const int C = p.batch * p.le;
+    if ((int)blockIdx.x >= code_blocks) return vq_bwd_elems(p, c_enc, code_blocks);
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int k = blockIdx.x * CWV + wave;
+    if (k >= p.K) return;
+    float acc[NJ];
+#pragma unroll
+    for (int i = 0; i < NJ; ++i) acc[i] = 0.f;
+    int n = 0;
+    for (int c0 = 0; c0 < C; c0 += 64) {
+        const int ix = c0 + lane < C ? p.idx[c0 + lane] : -1;
+        unsigned long long m = __ballot(ix == k);
+        n += __popcll(m);
+        while (m) {                                        // the matching frames of these 64, in ascending order
+            const int f = c0 + __ffsll(m) - 1;
+            m &= m - 1;
+            const float* e = p.enc + frame_base(f, p.bw, p.le);
+#pragma unroll
+            for (int i = 0; i < NJ; ++i) {
+                const int j = i * 64 + lane;
+                if (i * 64 < p.bw && j < p.bw) acc[i] += e[(long)j * p.le];
+            }
+        }
+    }
+    if (lane == 0) stat[k] = (float)n;
+#pragma unroll
+    for (int i = 0; i < NJ; ++i) {
+        const int j = i * 64 + lane;
+        if (j < p.bw) {
+            stat[p.K + (long)k * p.bw + j] = acc[i];
+            p.flat_grad[p.cb_off + (long)k * p.bw + j] = 0.f;
+        }
+    }
+}
+
+// ---- the EMA update.  Both launches form N' with THIS expression, so a code's N' has the same bits in either
+__device__ __forceinline__ float ema_mix(float g, float omg, float old, float fresh) { return fmaf(omg, fresh, g * old); }
+
+// the scratch of wn_vq_ema_update (WN_VQ_EMA_WORK_BYTES): what the ranking launch hands the row launch
+struct VqEmaWork {
+    float tot;                     // sum of N' (per wave by butterfly, the waves in ascending order)
+    int32_t restarted, left;       // dead codes that found a donor / that did not
+    int32_t pad;
+    int32_t donor[WN_VQ_MAX_K];    // per code: the code whose batch mean it takes, or -1
+};
+static_assert(sizeof(VqEmaWork) == WN_VQ_EMA_WORK, "the scratch's documented size");
+
+// ONE workgroup, thread k = code k.  Reads the old N and stat, writes only `work`.  Dead codes (N' < restart) rank by index: a prefix
+// count over ballots.  Donors (not dead, n_k >= 2) rank by (n descending, index ascending): key[k] = n_k (an integer below 2^32) above
+// the 10 bits of 1023 - k, 0 for every other code - no two donors share a key, so a donor's rank is the number of larger keys: a
+// counting rank, every donor walks the K keys in LDS two at a time (all lanes read one address: a broadcast; the keys behind K are 0).
+__global__ __launch_bounds__(WN_VQ_MAX_K) void vq_ema_rank_k(const float* __restrict__ stat, const float* __restrict__ state,
+                                                             VqEmaWork* __restrict__ work, int K, float g, float omg, float restart,
+                                                             const wn_guard_state* __restrict__ guard) {
+    __shared__ __attribute__((aligned(16))) unsigned long long s_key[WN_VQ_MAX_K];
+    __shared__ int s_donor[WN_VQ_MAX_K];
+    __shared__ float s_tot[WN_VQ_MAX_K / 64];
+    __shared__ int s_dead[WN_VQ_MAX_K / 64], s_don[WN_VQ_MAX_K / 64];
+    if (guard && guard->skip) return;
+    const int k = threadIdx.x, lane = k & 63, wave = k >> 6;
+    float n = 0.f, N1 = 0.f;
+    bool dead = false, don = false;
+    if (k < K) {
+        n = stat[k];
+        N1 = ema_mix(g, omg, state[k], n);
+        dead = restart > 0.f && N1 < restart;
+        don = !dead && n >= 2.f;
+    }
+    const unsigned long long key = don ? ((unsigned long long)(unsigned)fminf(n, 4294967040.f) << 10) | (unsigned)(WN_VQ_MAX_K - 1 - k) : 0ull;
+    s_key[k] = key;
+    float t = N1;
+    for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+    const unsigned long long b_dead = __ballot(dead), b_don = __ballot(don);
+    if (lane == 0) {
+        s_tot[wave] = t;
+        s_dead[wave] = __popcll(b_dead);
+        s_don[wave] = __popcll(b_don);
+    }
+    __syncthreads();
+    int n_dead = 0, n_donor = 0, rank = 0;                 // the sizes of the two kinds; this code's rank among its kind
+    for (int w = 0; w < WN_VQ_MAX_K / 64; ++w) {
+        n_dead += s_dead[w];
+        n_donor += s_don[w];
+        if (w < wave) rank += s_dead[w];
+    }
+    rank += __popcll(b_dead & ((1ull << lane) - 1ull));
+    if (don) {
+        rank = 0;
+        const ulonglong2* key2 = (const ulonglong2*)s_key;
+#pragma unroll 8
+        for (int j2 = 0; j2 < (K + 1) >> 1; ++j2) {
+            const ulonglong2 v = key2[j2];
+            rank += (v.x > key) + (v.y > key);
+        }
+        s_donor[rank] = k;
+    }
+    __syncthreads();
+    if (k < K) work->donor[k] = (dead && rank < n_donor) ? s_donor[rank] : -1;
+    if (k == 0) {
+        float tot = s_tot[0];
+        for (int w = 1; w < (K + 63) / 64; ++w) tot += s_tot[w];
+        const int r = n_dead < n_donor ? n_dead : n_donor;
+        work->tot = tot;
+        work->restarted = r;
+        work->left = n_dead - r;
+    }
+}
+
+// A wave per code, lanes along j: its own N and m row of state and its own codebook row, rewritten in place; work and stat are read only
+__global__ __launch_bounds__(64 * CWV) void vq_ema_rows_k(float* __restrict__ cb, const float* __restrict__ stat, float* __restrict__ state,
+                                                          const VqEmaWork* __restrict__ work, int32_t* __restrict__ info, int K, int bw,
+                                                          float g, float omg, float eps, const wn_guard_state* __restrict__ guard) {
+    if (guard && guard->skip) return;
+    if (info && blockIdx.x == 0 && threadIdx.x == 0) {
+        info[0] += work->restarted;
+        info[1] = work->left;
+    }
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int k = blockIdx.x * CWV + wave;
+    if (k >= K) return;
+    const int donor = work->donor[k];
+    float* m = state + K + (long)k * bw;
+    if ((unsigned)donor < (unsigned)K) {                   // restarted: the donor's batch mean, with usage 1
+        const float nd = stat[donor];
+        const float* sd = stat + K + (long)donor * bw;
+        for (int j = lane; j < bw; j += 64) {
+            const float c = sd[j] / nd;
+            m[j] = c;
+            cb[(long)k * bw + j] = c;
+        }
+        if (lane == 0) state[k] = 1.f;
+        return;
+    }
+    const float N1 = ema_mix(g, omg, state[k], stat[k]);
+    const float tot = work->tot;
+    const float nhat = (N1 + eps) / (tot + (float)K * eps) * tot;
+    const float* s = stat + K + (long)k * bw;
+    for (int j = lane; j < bw; j += 64) {
+        const float m1 = ema_mix(g, omg, m[j], s[j]);
+        m[j] = m1;
+        cb[(long)k * bw + j] = m1 / nhat;
+    }
+    if (lane == 0) state[k] = N1;                          // (behind the wave's reads of it: one wave, program order)
 }
 
 __global__ __launch_bounds__(256) void vq_lookup_k(const int32_t* idx, const float* cb, float* q_out, int32_t* bad, int K, int bw, int le,
@@ -217,6 +377,29 @@ int wn_launch_vq_bwd(const WnVq& p, float beta, float g_scale, hipStream_t st) {
     const int elem_blocks = (int)std::min<long>((total + 64 * CWV - 1) / (64 * CWV), 256);
     hipLaunchKernelGGL(vq_bwd_k, dim3(code_blocks + elem_blocks), dim3(64 * CWV), 0, st, p, (float)((double)g_scale * beta * s),
                        (float)((double)g_scale * s), code_blocks);
+    WN_CHECK_LAUNCH();
+    return 0;
+}
+
+int wn_launch_vq_bwd_stats(const WnVq& p, float beta, float g_scale, float* stat, hipStream_t st) {
+    if (p.batch <= 0) return 0;
+    const double s = 2.0 / ((double)p.batch * p.le * p.bw);
+    const int code_blocks = (p.K + CWV - 1) / CWV;
+    const long total = (long)p.batch * p.le * p.bw;
+    const int elem_blocks = (int)std::min<long>((total + 64 * CWV - 1) / (64 * CWV), 256);
+    hipLaunchKernelGGL(vq_bwd_stats_k, dim3(code_blocks + elem_blocks), dim3(64 * CWV), 0, st, p, (float)((double)g_scale * beta * s),
+                       code_blocks, stat);
+    WN_CHECK_LAUNCH();
+    return 0;
+}
+
+int wn_launch_vq_ema_update(float* flat, long cb_off, const float* stat, float* state, void* work, int32_t* info, int K, int bw,
+                            float decay, float eps, float restart, const wn_guard_state* guard, hipStream_t st) {
+    const float omg = (float)(1.0 - (double)decay);
+    hipLaunchKernelGGL(vq_ema_rank_k, dim3(1), dim3(WN_VQ_MAX_K), 0, st, stat, state, (VqEmaWork*)work, K, decay, omg, restart, guard);
+    WN_CHECK_LAUNCH();
+    hipLaunchKernelGGL(vq_ema_rows_k, dim3((K + CWV - 1) / CWV), dim3(64 * CWV), 0, st, flat + cb_off, stat, state,
+                       (const VqEmaWork*)work, info, K, bw, decay, omg, eps, guard);
     WN_CHECK_LAUNCH();
     return 0;
 }

@@ -179,9 +179,19 @@ class ShadowParams:
 
 
 # ---------------------------------------------------------------- train() / ae_train: the .ema file beside every .model
-def save_shadow(shadow, path):
-    """The shadow in the .model format (a bare state_dict pickle on the CPU): train.load_model(net, dir, "wavenet5.ema") reads it."""
-    torch.save(OrderedDict((k, v.detach().cpu().clone()) for k, v in shadow.state_dict().items()), path)
+BUFFER_KEYS = ("vq_ema_state",)     # a module's buffers that an .ema file carries beside the shadow (there is no average of them)
+
+
+def save_shadow(shadow, path, model=None):
+    """The shadow in the .model format (a bare state_dict pickle on the CPU): train.load_model(net, dir, "wavenet5.ema") reads it.
+    `model`: its buffers named in BUFFER_KEYS (the running state of an EMA-updated vq codebook) are written behind the shadow as
+    they are, so that the file loads into a model of the same mode."""
+    sd = OrderedDict((k, v.detach().cpu().clone()) for k, v in shadow.state_dict().items())
+    if model is not None:
+        for k, v in model.named_buffers():
+            if k in BUFFER_KEYS:
+                sd[k] = v.detach().cpu().clone()
+    torch.save(sd, path)
 
 
 def restore_shadow(shadow, path, n_updates, guard=None):
@@ -190,7 +200,7 @@ def restore_shadow(shadow, path, n_updates, guard=None):
     `guard`: the (already seeded) GradGuard of the step, so that T continues from the count."""
     import os
     if os.path.exists(path):
-        shadow.load_state_dict(torch.load(path, map_location="cpu"))
+        shadow.load_state_dict(OrderedDict((k, v) for k, v in torch.load(path, map_location="cpu").items() if k not in BUFFER_KEYS))
     else:
         print("No EMA shadow found at {}, it starts from the restored weights.".format(path))
     n = warmup_done(shadow.decay) if n_updates is None else int(n_updates)

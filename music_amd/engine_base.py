@@ -4,6 +4,7 @@ the workspace pool, the flat-parameter spec, `EngineBase` (state, timing marks, 
 
 PyTorch is used for device memory and streams only.  Nothing here imports oracle/.
 """
+import weakref
 from collections import namedtuple
 
 import numpy as np
@@ -169,10 +170,12 @@ class SlabPlan:
 
 class VqStats:
     """What one forward's wn_vq_fwd left on the device, read on demand (nothing here runs in the step): `mse` and `perplexity` are
-    0-d device tensors, `vq_loss` = (1 + beta) mse, `codes_used` the number of codes at least one frame chose."""
+    0-d device tensors, `vq_loss` = (1 + beta) mse - beta mse with EMA codebook updates, where the codebook term is gone (`coef`) -,
+    `codes_used` the number of codes at least one frame chose."""
 
-    def __init__(self, part, counts, frames, beta):
+    def __init__(self, part, counts, frames, beta, coef=None):
         self.part, self.counts, self.frames, self.beta = part, counts, frames, beta
+        self.coef = 1.0 + beta if coef is None else coef
 
     @property
     def mse(self):
@@ -180,7 +183,7 @@ class VqStats:
 
     @property
     def vq_loss(self):
-        return self.part.sum() * (1.0 + self.beta)
+        return self.part.sum() * self.coef
 
     @property
     def perplexity(self):
@@ -249,6 +252,7 @@ class EngineBase:
     vq = False                   # net.bottleneck == "vq": the codebook (K, Bw) is the LAST parameter of the flat buffer, behind the projections
     n_vq = 0                     # its floats: wn_vq_bwd writes that tail of flat_grad
     last_vq = None               # VqStats of the last forward (vq only)
+    vq_ema = False               # net.vq_update == "ema": wn_vq_bwd_stats in place of wn_vq_bwd, wn_vq_ema_update behind the optimizer
 
     @property
     def n_gather(self):
@@ -273,6 +277,14 @@ class EngineBase:
             self.vq_off = self.spec.off["vq_codebook.weight"]
             self.n_vq = self.vq_K * self.Bw
             assert self.spec.shape["vq_codebook.weight"] == (self.vq_K, self.Bw) and self.vq_off + self.n_vq == self.spec.total
+            self.vq_ema = getattr(net, "vq_update", "gradient") == "ema"
+            if self.vq_ema:
+                # [n | s] of the last backward, the update's scratch and its restart counters; the running state is the MODULE's buffer
+                self.vq_decay, self.vq_eps, self.vq_restart = float(net.vq_decay), float(net.vq_eps), float(net.vq_restart)
+                self.vq_stat = torch.zeros(self.vq_K * (self.Bw + 1), dtype=torch.float32, device=self.device)
+                self.vq_ema_work = torch.zeros(_lib.VQ_EMA_WORK_BYTES // 4, dtype=torch.int32, device=self.device)
+                self.vq_ema_info = torch.zeros(2, dtype=torch.int32, device=self.device)
+                self._vq_net = weakref.ref(net)
         if not self.learned:
             return
         o, N = self.spec.off, len(self.dil)
@@ -297,15 +309,45 @@ class EngineBase:
         part = torch.empty(_lib.VQ_NUM_PARTIALS, dtype=torch.float32, device=dev)
         call("wn_vq_fwd", ptr(enc), ptr(self.flat), self.vq_off, ptr(q), ptr(idx), ptr(counts), ptr(part), self.vq_K, self.Bw, Le, B, st)
         ws.update(enc_pre=enc, vq_idx=idx, vq_counts=counts, vq_part=part, vq_g=1.0)
-        self.last_vq = VqStats(part, counts, B * Le, self.vq_beta)
+        self.last_vq = VqStats(part, counts, B * Le, self.vq_beta, self.vq_loss_coef)
         return q
 
     def vq_bwd(self, ws, d_q, st):
         """d_q (what wn_cond_proj_bwd wrote as d enc) -> d e in place, and the codebook's gradient into the tail of flat_grad (wn_vq_bwd,
         one launch); ws["vq_g"]: the upstream scalar on vq_loss (1 in the fused step, autograd's in the module's backward)."""
         B, _, Le = d_q.shape
+        if self.vq_ema:                     # the same d e; the frames' counts and sums per code into vq_stat, zeros as the codebook's gradient
+            return call("wn_vq_bwd_stats", ptr(ws["enc_pre"]), ptr(ws["vq_idx"]), ptr(d_q), ptr(self.flat), self.vq_off, self.vq_beta,
+                        float(ws.get("vq_g", 1.0)), ptr(d_q), ptr(self.flat_grad), ptr(self.vq_stat), self.vq_K, self.Bw, Le, B, st)
         call("wn_vq_bwd", ptr(ws["enc_pre"]), ptr(ws["vq_idx"]), ptr(d_q), ptr(self.flat), self.vq_off, self.vq_beta, float(ws.get("vq_g", 1.0)),
              ptr(d_q), ptr(self.flat_grad), self.vq_K, self.Bw, Le, B, st)
+
+    @property
+    def vq_loss_coef(self):
+        """vq_loss / mse: codebook term + beta x commitment term; the commitment term alone where the codebook follows its frames' mean."""
+        return self.vq_beta if self.vq_ema else 1.0 + self.vq_beta
+
+    def vq_ema_state(self):
+        """The module's running state [N | m] (its `vq_ema_state` buffer, which checkpoints carry), on this engine's device."""
+        net = self._vq_net()
+        state = None if net is None else getattr(net, "vq_ema_state", None)
+        if state is None or state.device != self.flat.device or state.dtype != torch.float32 or state.numel() != self.vq_stat.numel():
+            raise RuntimeError("music_amd: the model's vq_ema_state buffer is gone, or not where its parameters are")
+        return state
+
+    def vq_ema_step(self, guard=None):
+        """wn_vq_ema_update (two launches) on the stats of the last backward: the module's running state and the codebook's rows of
+        the flat buffer, in place.  Behind the optimizer's update - which leaves those rows alone, their gradient being 0 - and in
+        front of the EMA shadow's.  `guard`: the GradGuard that decided the step; a skipped step changes nothing."""
+        call("wn_vq_ema_update", ptr(self.flat), self.vq_off, ptr(self.vq_stat), ptr(self.vq_ema_state()), ptr(self.vq_ema_work),
+             ptr(self.vq_ema_info), self.vq_K, self.Bw, self.vq_decay, self.vq_eps, self.vq_restart,
+             None if guard is None else guard.state_ptr(), _lib.stream())
+
+    def vq_restarted(self):
+        """Codes restarted since the last call (reads the device's counter back and zeroes it)."""
+        n = int(self.vq_ema_info[0].item())
+        self.vq_ema_info[0] = 0
+        return n
 
     def vq_backward_scaled(self, ws, dloss, dvq):
         """backward_from_dlogits of a vq model for upstream gradients `dloss` (0-d device tensor or None) on the reconstruction loss whose
@@ -519,7 +561,7 @@ class EngineBase:
         if self.vq:                         # reconstruction loss + vq_loss, under either objective; its upstream scalar is 1
             ws["vq_g"] = 1.0
             self.backward_from_dlogits(ws)
-            return torch.add(ws["loss_part"].sum(), ws["vq_part"].sum(), alpha=1.0 + self.vq_beta)
+            return torch.add(ws["loss_part"].sum(), ws["vq_part"].sum(), alpha=self.vq_loss_coef)
         self.backward_from_dlogits(ws)
         return ws["loss_part"].sum()
 
@@ -558,5 +600,7 @@ class EngineBase:
         s["t"] += 1
         call("wn_adam_flat", ptr(self.flat), ptr(self.flat_grad), ptr(s["m"]), ptr(s["v"]), self.spec.total,
              s["lr"], s["b1"], s["b2"], s["eps"], 1.0 - s["b1"] ** s["t"], 1.0 - s["b2"] ** s["t"], gscale, _lib.stream())
+        if self.vq_ema:
+            self.vq_ema_step()
         if shadow is not None:
             shadow.update(self)

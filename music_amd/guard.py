@@ -87,6 +87,8 @@ def adam_step_guarded(eng, gscale):
     gd.run(_lib.ptr(eng.flat_grad), eng.spec.total, gscale)
     _lib.call("wn_adam_flat_guarded", _lib.ptr(eng.flat), _lib.ptr(eng.flat_grad), _lib.ptr(s["m"]), _lib.ptr(s["v"]), eng.spec.total,
               s["lr"], s["b1"], s["b2"], s["eps"], gscale, gd.state_ptr(), _lib.stream())
+    if getattr(eng, "vq_ema", False):
+        eng.vq_ema_step(gd)
     if s.get("ema") is not None:
         s["ema"].update(eng, gd)
 
@@ -117,6 +119,14 @@ class GuardedOptimizer:
     rule for such a step."""
 
     ema = None                   # the ShadowParams of music_amd/ema.py when ema_decay is set (_ema_setup), else None
+    _model = None                # the module whose parameters these are, where the optimizer was given it
+
+    def _vq_ema_step(self, eng=None, gd=None, taken=True):
+        """A model whose vq codebook follows EMA updates: its engine's wn_vq_ema_update, behind the step's parameter update and in
+        front of the shadow's.  `gd`: the GradGuard whose decision the device reads; `taken`: the host's decision on torch's path."""
+        eng = eng if eng is not None else getattr(self._model, "_engine", None)
+        if taken and eng is not None and getattr(eng, "vq_ema", False):
+            eng.vq_ema_step(gd)
 
     def _guard_setup(self, max_grad_norm, skip_nonfinite):
         self._guard_opts = (max_grad_norm, bool(skip_nonfinite)) if enabled(max_grad_norm, skip_nonfinite) else None
@@ -179,6 +189,7 @@ class GuardedOptimizer:
             self.ema.check_step()
         if self._guard_opts is None:
             loss = super().step(closure)
+            self._vq_ema_step()
             if self.ema is not None:
                 self.ema.host_update(params)
             return loss
@@ -191,6 +202,7 @@ class GuardedOptimizer:
         taken = gd.host_rule(params)
         if taken:
             super().step()
+        self._vq_ema_step(taken=taken)
         if self.ema is not None:
             self.ema.host_update(params, taken, gd)
         return loss

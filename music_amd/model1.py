@@ -601,6 +601,7 @@ class _AutoencoderEngine(EngineBase):
 
 
 BOTTLENECKS = ("continuous", "vq")       # the pooled encoding as it is, or every frame replaced by its nearest codebook row (VQ-VAE)
+VQ_UPDATES = ("gradient", "ema")         # what trains the codebook: its loss term's gradient, or the running mean of its frames (+ restarts)
 CONDITIONING = ("random", "learned")     # the decoder's conditioning projections: drawn afresh per forward (the reference), or parameters
 
 
@@ -655,7 +656,8 @@ class wavenet_autoencoder(nn.Module):
 
     def __init__(self, filter_width, quantization_channel, dilations, en_residual_channel, en_dilation_channel,
                  en_bottleneck_width, en_pool_kernel_size, de_residual_channel, de_dilation_channel,
-                 de_skip_channel, use_bias, conditioning="random", bottleneck="continuous", vq_codes=512, vq_beta=0.25):
+                 de_skip_channel, use_bias, conditioning="random", bottleneck="continuous", vq_codes=512, vq_beta=0.25,
+                 vq_update="gradient", vq_decay=0.99, vq_eps=1e-5, vq_restart=0.0):
         super(wavenet_autoencoder, self).__init__()
         if conditioning not in CONDITIONING:
             raise ValueError("music_amd.wavenet_autoencoder: conditioning must be one of %s, not %r"
@@ -674,8 +676,21 @@ class wavenet_autoencoder(nn.Module):
                                  % (_lib.VQ_MAX_WIDTH, en_bottleneck_width))
             if not float(vq_beta) >= 0.0:
                 raise ValueError("music_amd.wavenet_autoencoder: vq_beta must be >= 0, not %r" % (vq_beta,))
+        if vq_update not in VQ_UPDATES:
+            raise ValueError("music_amd.wavenet_autoencoder: vq_update must be one of %s, not %r"
+                             % (", ".join('"%s"' % c for c in VQ_UPDATES), vq_update))
+        if vq_update == "ema":
+            if bottleneck != "vq":
+                raise ValueError('music_amd.wavenet_autoencoder: vq_update="ema" requires bottleneck="vq"')
+            if not 0.0 < float(vq_decay) < 1.0:
+                raise ValueError("music_amd.wavenet_autoencoder: vq_decay must lie in (0, 1), not %r" % (vq_decay,))
+            if not float(vq_eps) >= 0.0:
+                raise ValueError("music_amd.wavenet_autoencoder: vq_eps must be >= 0, not %r" % (vq_eps,))
+            if not float(vq_restart) >= 0.0:
+                raise ValueError("music_amd.wavenet_autoencoder: vq_restart must be >= 0, not %r" % (vq_restart,))
         self.conditioning = conditioning
         self.bottleneck, self.vq_num_codes, self.vq_beta = bottleneck, int(vq_codes), float(vq_beta)
+        self.vq_update, self.vq_decay, self.vq_eps, self.vq_restart = vq_update, float(vq_decay), float(vq_eps), float(vq_restart)
         self.filter_width = filter_width
         self.quantization_channel = quantization_channel
         self.dilations = dilations
@@ -731,11 +746,18 @@ class wavenet_autoencoder(nn.Module):
             self.vq_codebook = nn.Embedding(self.vq_num_codes, en_bottleneck_width)
             with torch.no_grad():
                 self.vq_codebook.weight.uniform_(-1.0 / self.vq_num_codes, 1.0 / self.vq_num_codes)
+            if vq_update == "ema":
+                # the running usage N (K) and running sums m (K, Bw) of wn_vq_ema_update, [N | m] in one vector; m / N is the
+                # codebook.  A buffer: it travels with state_dict() (as the LAST key) and the module's moves, no optimizer sees it
+                self.register_buffer("vq_ema_state", torch.empty(self.vq_num_codes * (en_bottleneck_width + 1)))
+                self.reset_vq_ema_state()
 
     def __setstate__(self, state):
         super(wavenet_autoencoder, self).__setstate__(state)
         self.__dict__.setdefault("conditioning", "random")       # (a module pickled before the attribute existed)
         self.__dict__.setdefault("bottleneck", "continuous")
+        for k, v in (("vq_update", "gradient"), ("vq_decay", 0.99), ("vq_eps", 1e-5), ("vq_restart", 0.0)):
+            self.__dict__.setdefault(k, v)
         for k in ("vq_loss", "vq_codes", "last_encoding_pre", "last_vq"):
             self.__dict__.setdefault(k, None)
 
@@ -754,6 +776,24 @@ class wavenet_autoencoder(nn.Module):
         pick = order[torch.arange(w.size(0)) % frames.size(0)]
         with torch.no_grad():
             w.copy_(frames[pick.to(frames.device)].to(w.device))          # (in place: the parameter may be a view of the flat buffer)
+        self.reset_vq_ema_state()
+
+    def reset_vq_ema_state(self):
+        """vq_update="ema": the running state back to [1 | codebook] - usage 1 per code, sums = the rows as they are now (after the
+        codebook was set by hand, init_codebook does it itself).  In place; nothing to do in gradient mode."""
+        if getattr(self, "vq_update", "gradient") != "ema":
+            return
+        K = self.vq_num_codes
+        with torch.no_grad():
+            self.vq_ema_state[:K].fill_(1.0)
+            self.vq_ema_state[K:].copy_(self.vq_codebook.weight.detach().reshape(-1))
+
+    def state_dict(self, *args, **kwargs):
+        sd = super(wavenet_autoencoder, self).state_dict(*args, **kwargs)
+        key = kwargs.get("prefix", "") + "vq_ema_state"       # the module's own buffer is listed first: it goes BEHIND everything else
+        if key in sd:
+            sd.move_to_end(key)
+        return sd
 
     def _cond_modules(self):
         return list(self.de_cond_layer_stack) + [self.connection_cond]
@@ -788,6 +828,12 @@ class wavenet_autoencoder(nn.Module):
             raise RuntimeError('music_amd.wavenet_autoencoder: the checkpoint was saved with bottleneck="%s" but this model was built '
                                'with bottleneck="%s" (the "bottleneck" key of model_params.json); nothing was loaded'
                                % ("vq" if has_vq else "continuous", mine_vq))
+        has_ema = "vq_ema_state" in state_dict.keys()
+        mine_ema = getattr(self, "vq_update", "gradient")
+        if has_ema != (mine_ema == "ema"):
+            raise RuntimeError('music_amd.wavenet_autoencoder: the checkpoint was saved with vq_update="%s" but this model was built '
+                               'with vq_update="%s" (the "vq_update" key of model_params.json); nothing was loaded'
+                               % ("ema" if has_ema else "gradient", mine_ema))
         return super(wavenet_autoencoder, self).load_state_dict(state_dict, *args, **kwargs)
 
     def __getstate__(self):

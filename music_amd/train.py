@@ -146,6 +146,7 @@ class FlatAdam(guard.GuardedOptimizer, optim.Adam):
                     gd.run(gbase, eng.spec.total)
                     _lib.call("wn_adam_flat_guarded", eng.flat.data_ptr(), gbase, m.data_ptr(), v.data_ptr(), eng.spec.total,
                               float(grp["lr"]), grp["betas"][0], grp["betas"][1], grp["eps"], 1.0, gd.state_ptr(), _lib.stream())
+                    self._vq_ema_step(eng, gd)
                     if self.ema is not None:
                         self.ema.update(eng, gd)
                     return None
@@ -154,6 +155,7 @@ class FlatAdam(guard.GuardedOptimizer, optim.Adam):
                 b1, b2 = grp["betas"]
                 _lib.call("wn_adam_flat", eng.flat.data_ptr(), gbase, m.data_ptr(), v.data_ptr(), eng.spec.total,
                           float(grp["lr"]), b1, b2, grp["eps"], 1.0 - b1 ** t, 1.0 - b2 ** t, 1.0, _lib.stream())
+                self._vq_ema_step(eng)
                 if self.ema is not None:
                     self.ema.update(eng)
                 return None
@@ -258,10 +260,12 @@ class FlatSGD(guard.GuardedOptimizer, optim.SGD):
                 gd.run(gbase, eng.spec.total)
                 _lib.call("wn_sgd_flat_guarded", eng.flat.data_ptr(), gbase, buf, eng.spec.total, float(grp["lr"]), mom, 1.0, gd.state_ptr(),
                           _lib.stream())
+                self._vq_ema_step(eng, gd)
                 if self.ema is not None:
                     self.ema.update(eng, gd)
                 return None
             _lib.call("wn_sgd_flat", eng.flat.data_ptr(), gbase, buf, eng.spec.total, float(grp["lr"]), mom, 1.0, first, _lib.stream())
+            self._vq_ema_step(eng)
             if self.ema is not None:
                 self.ema.update(eng)
             return None
@@ -316,12 +320,14 @@ class FlatRMSprop(guard.GuardedOptimizer, optim.RMSprop):
                 gd.run(gbase, eng.spec.total)
                 _lib.call("wn_rmsprop_flat_guarded", eng.flat.data_ptr(), gbase, sq.data_ptr(), buf, eng.spec.total, float(grp["lr"]),
                           float(grp["alpha"]), float(grp["eps"]), mom, 1.0, gd.state_ptr(), _lib.stream())
+                self._vq_ema_step(eng, gd)
                 if self.ema is not None:
                     self.ema.update(eng, gd)
                 return None
             torch._foreach_add_(steps, 1.0)
             _lib.call("wn_rmsprop_flat", eng.flat.data_ptr(), gbase, sq.data_ptr(), buf, eng.spec.total, float(grp["lr"]), float(grp["alpha"]),
                       float(grp["eps"]), mom, 1.0, _lib.stream())
+            self._vq_ema_step(eng)
             if self.ema is not None:
                 self.ema.update(eng)
             return None

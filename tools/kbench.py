@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of single kernels of the hot path at BASELINE config-2 shapes (GPU only).
 
-    python tools/kbench.py [fwd|bwd|epi|dx|skip|decode|ae|guard|ema|nll|cond|vq|all] [--reps N] [--precision f16x3,bf16x3]
+    python tools/kbench.py [fwd|bwd|epi|dx|skip|decode|ae|guard|ema|nll|cond|vq|vq_ema|all] [--reps N] [--precision f16x3,bf16x3]
 
 Prints per-phase / per-layer kernel times measured with HIP events on the launch stream.
 """
@@ -115,6 +115,115 @@ def vq_bench(reps, alternations=6):
     print(json.dumps(res))
 
 
+def vq_ema_bench(reps, alternations=6):
+    """`vq_ema`: EMA codebook updates.  (a) wn_vq_bwd_stats (beside wn_vq_bwd, whose place it takes) and the two launches of
+    wn_vq_ema_update alone at config 4's shape (B 8, Bw 64, Le 25, K 512) and at the shipped autoencoder's (B 4, Bw 512, Le 32,
+    K 512), HIP events around `reps` calls; (b) the fused config-4 step of an ema model against the gradient model, both started from
+    a data-drawn codebook; everything alternated `alternations` times on one device, medians and spreads (largest - smallest);
+    (c) the collapse the mode exists for: perplexity and codes in use on the bench batch from the constructor's codebook after the
+    warm-up steps and after 100 more, with vq_restart off and on.  Written to profiles/vq_ema_kbench.json."""
+    import time
+    from music_amd import _lib
+    from music_amd._lib import call, ptr
+    from music_amd.model1 import wavenet_autoencoder
+    st = _lib.stream()
+    res = {"alternations": alternations}
+    rng = np.random.default_rng(0)
+    shapes = {"config4": (8, 64, 25, 512), "shipped": (4, 512, 32, 512)}
+    bufs = {}
+    for name, (B, Bw, Le, K) in shapes.items():
+        enc = torch.from_numpy(rng.standard_normal((B, Bw, Le)).astype(np.float32)).cuda()
+        flat = torch.from_numpy(rng.standard_normal(K * Bw).astype(np.float32)).cuda()
+        idx = torch.from_numpy(rng.integers(0, K, size=(B, Le)).astype(np.int32)).cuda()
+        bufs[name] = dict(enc=enc, flat=flat, idx=idx, d=torch.randn_like(enc), grad=torch.empty_like(flat),
+                          stat=torch.zeros(K * (Bw + 1), device="cuda"), state=torch.cat([torch.ones(K, device="cuda"), flat]),
+                          work=torch.zeros(_lib.VQ_EMA_WORK_BYTES // 4, dtype=torch.int32, device="cuda"),
+                          info=torch.zeros(2, dtype=torch.int32, device="cuda"))
+
+    def launches(name, which, n):
+        B, Bw, Le, K = shapes[name]
+        b = bufs[name]
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        torch.cuda.synchronize()
+        ev[0].record()
+        for _ in range(n):
+            if which == "bwd":
+                call("wn_vq_bwd", ptr(b["enc"]), ptr(b["idx"]), ptr(b["d"]), ptr(b["flat"]), 0, 0.25, 1.0, ptr(b["d"]), ptr(b["grad"]), K, Bw,
+                     Le, B, st)
+            elif which == "bwd_stats":
+                call("wn_vq_bwd_stats", ptr(b["enc"]), ptr(b["idx"]), ptr(b["d"]), ptr(b["flat"]), 0, 0.25, 1.0, ptr(b["d"]), ptr(b["grad"]),
+                     ptr(b["stat"]), K, Bw, Le, B, st)
+            else:                                                               # (its two launches; restarts on: a used code's N' stays >= 1)
+                call("wn_vq_ema_update", ptr(b["flat"]), 0, ptr(b["stat"]), ptr(b["state"]), ptr(b["work"]), ptr(b["info"]), K, Bw, 0.99, 1e-5,
+                     0.995, None, st)
+        ev[1].record()
+        torch.cuda.synchronize()
+        return ev[0].elapsed_time(ev[1]) / n * 1e3
+    times = {(n, w): [] for n in shapes for w in ("bwd", "bwd_stats", "ema_update")}
+    for key in times:
+        launches(*key, 20)                                                    # warm (and the stats the update reads exist)
+    for _ in range(alternations):
+        for key in times:
+            times[key].append(launches(*key, max(reps, 100)))
+    for (n, w), v in times.items():
+        res["wn_vq_%s_%s_us" % (w, n)], res["wn_vq_%s_%s_us_spread" % (w, n)] = _median_spread(v)
+    # ---- the fused config-4 step
+    cfg = dict(filter_width=2, quantization_channel=256, dilations=CFG["dilations"], en_residual_channel=64, en_dilation_channel=64,
+               en_bottleneck_width=64, en_pool_kernel_size=512, de_residual_channel=64, de_dilation_channel=64, de_skip_channel=256,
+               use_bias=False, conditioning="learned", bottleneck="vq", vq_codes=512)
+    codes = torch.from_numpy(rng.integers(0, 256, size=(B_LOCAL, T)).astype(np.int32)).cuda()
+    from music_amd.faster_audio_data import onehot_device
+    x = onehot_device(codes, 256, True)
+
+    def model(**kw):
+        torch.manual_seed(0)
+        net = wavenet_autoencoder(**dict(cfg, **kw)).cuda()
+        eng = net._engine_for(torch.device("cuda", 0))
+        eng.adam_init(lr=1e-4)
+        return net, eng
+    engs = {"gradient": model(), "ema": model(vq_update="ema", vq_restart=0.995)}
+    W = T - engs["ema"][0].receptive_field + 1
+    target = torch.from_numpy(rng.integers(0, 256, size=(B_LOCAL * W,)).astype(np.int64)).cuda()
+    with torch.no_grad():
+        _, _, ws0 = engs["ema"][1].forward(x, None, want_probs=False, encode_only=True)
+    for net, _ in engs.values():
+        net.init_codebook(ws0["enc_pre"], seed=0)                             # (codes in use, as in a trained model)
+
+    def steps(eng, n):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            loss = eng.loss_and_grad(x, target, None)
+            eng.adam_step()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / n * 1e3, float(loss)
+    for mode in engs:
+        steps(engs[mode][1], 5)
+    step_ms = {m: [] for m in engs}
+    for _ in range(alternations):
+        for mode in engs:
+            ms, loss = steps(engs[mode][1], max(reps, 20))
+            step_ms[mode].append(ms)
+            res["fused_step_loss_" + mode] = round(loss, 5)
+    for mode, v in step_ms.items():
+        res["fused_step_ms_" + mode], res["fused_step_ms_%s_spread" % mode] = _median_spread(v)
+    res["fused_step_ms_ema_minus_gradient"] = round(res["fused_step_ms_ema"] - res["fused_step_ms_gradient"], 3)
+    res["fused_step_ms_by_alternation"] = {m: [round(t, 3) for t in v] for m, v in step_ms.items()}
+    res["ema_update_restarted_in_timed_steps"] = engs["ema"][1].vq_restarted()
+    res["shape_config4_step"] = dict(B=B_LOCAL, T=T, frames=B_LOCAL * (W // 512), Bw=64, K=512)
+    # ---- the collapse: the constructor's codebook on the bench batch
+    for label, kw in (("gradient", {}), ("ema_restart_off", dict(vq_update="ema")), ("ema_restart_on", dict(vq_update="ema", vq_restart=0.995))):
+        net, eng = model(**kw)
+        for n_steps, when in ((5, "after_warmup"), (100, "after_105_steps")):
+            steps(eng, n_steps)
+            eng.loss_and_grad(x, target, None)
+            s = eng.last_vq
+            res["collapse_%s_%s" % (label, when)] = dict(codes_used=int(s.codes_used), perplexity=round(float(s.perplexity), 2))
+        if eng.vq_ema:
+            res["collapse_%s_restarted" % label] = eng.vq_restarted()
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", nargs="?", default="all")
@@ -124,6 +233,8 @@ def main():
     args = ap.parse_args()
     if args.what == "vq":
         return vq_bench(args.reps)
+    if args.what == "vq_ema":
+        return vq_ema_bench(args.reps)
     from music_amd.model import wavenet
     from music_amd import _lib
     from music_amd._lib import call, ptr
