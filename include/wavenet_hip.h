@@ -436,6 +436,33 @@ int wn_cond_proj_fwd(const float* enc, const float* flat, int64_t w_off, int64_t
 int wn_cond_proj_bwd(const float* d_tab, int pair, const float* d_enf, const float* enc, const float* flat, int64_t w_off,
                      int64_t b_off, int64_t stage_stride, int64_t wf_off, int64_t bf_off, float* d_enc, float* flat_grad,
                      int n_stages, int dd, int ch, int sd, int bw, int le, int batch, wn_stream_t stream);
+/* ---- the same projections with a GLOBAL CLASS term (VQ-VAE's speaker id, NSynth's instrument): clip b has a class cls[b] (int32
+ * [batch], on the device) whose embedding row emb[cls[b]] [ge] is projected into every stage, constant over the clip's frames:
+ *   en_i[b][c][l] = (bias_i[c] + sum_k W_i[c][k] enc[b][k][l]) + sum_e G_i[c][e] emb[cls[b]][e]           (the final stage alike)
+ * - the bracket is wn_cond_proj_fwd's value to the bit, the global product a second reduction added to it.  In flat (flat_grad),
+ * counted in floats: stage i's G_i [2 dd][ge] at gw_off + i * gstage_stride, rows in the reference's order like W_i; the final
+ * stage's G_f [sd][ge] at gwf_off; the embedding [n_cls][ge] at emb_off.  All other arguments are wn_cond_proj_fwd / _bwd's.
+ * wn_gcond_proj_fwd writes every table it is given WHOLE, padding rows as zeros, and enf, in ONE launch.
+ * wn_gcond_proj_bwd writes, in THREE launches (wn_cond_proj_bwd's two, the first with dG's tiles behind dW's, and d_emb's),
+ *   d_enc, dW_i, db_i:  what wn_cond_proj_bwd writes from the same inputs, the same bits
+ *   dG_i[c][e]  = sum_b sum_l d_en_i[b][c][l] emb[cls[b]][e]                                               (the final stage alike)
+ *   d_emb[m][e] = sum_{b: cls[b] == m, in ascending b} sum_r G[r][e] (sum_l d[r][b][l])    over all n_stages * 2 dd + sd rows r
+ * at the parameters' offsets, OVERWRITING all n_cls rows of d_emb - a class no clip has gets exactly 0; nothing else of flat_grad is
+ * touched.  A cls[b] outside [0, n_cls) is never used as an index: the forward turns that clip's columns of every table and of enf
+ * into NaN, the backward its share of dG (d_emb has no row for it).  fp32 FMA arithmetic in a fixed order, no float atomics: the
+ * same bits at every launch.  On `stream`, no allocation, nothing retained, legal under stream capture.
+ * batch == 0 returns 0 (NULLs allowed).  -4, function and argument named in wn_last_error: every case of wn_cond_proj_fwd / _bwd;
+ * ge < 1 or ge > WN_GCOND_MAX_CHANNELS; n_cls < 1; a negative gw_off, gwf_off or emb_off; gstage_stride < 2 dd ge with more than one
+ * stage; with work to do, a NULL cls. */
+#define WN_GCOND_MAX_CHANNELS 512
+int wn_gcond_proj_fwd(const float* enc, const float* flat, int64_t w_off, int64_t b_off, int64_t stage_stride, int64_t wf_off,
+                      int64_t bf_off, float* tab, float* tab_pair, float* enf, int n_stages, int dd, int ch, int sd, int bw, int le,
+                      int batch, const int32_t* cls, int64_t gw_off, int64_t gstage_stride, int64_t gwf_off, int64_t emb_off, int ge,
+                      int n_cls, wn_stream_t stream);
+int wn_gcond_proj_bwd(const float* d_tab, int pair, const float* d_enf, const float* enc, const float* flat, int64_t w_off,
+                      int64_t b_off, int64_t stage_stride, int64_t wf_off, int64_t bf_off, float* d_enc, float* flat_grad,
+                      int n_stages, int dd, int ch, int sd, int bw, int le, int batch, const int32_t* cls, int64_t gw_off,
+                      int64_t gstage_stride, int64_t gwf_off, int64_t emb_off, int ge, int n_cls, wn_stream_t stream);
 /* ---- VECTOR-QUANTISED bottleneck of the autoencoder (VQ-VAE, van den Oord et al. 2017; the reference has none): every pooled frame
  * e = enc[b][:][l] of enc [batch][bw][le] is replaced by its nearest row of the codebook c [K][bw], which sits at flat + cb_off
  * (its gradient at flat_grad + cb_off; offsets count floats).  C = batch * le frames.  Everything in float32:

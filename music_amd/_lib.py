@@ -18,6 +18,7 @@ GUARD_PARTIALS_BYTES = GUARD_NUM_PARTIALS * 12
 VQ_NUM_PARTIALS = 256          # include/wavenet_hip.h WN_VQ_NUM_PARTIALS
 VQ_MAX_CODES, VQ_MAX_WIDTH = 1024, 512
 VQ_EMA_WORK_BYTES = 16 + 4 * VQ_MAX_CODES      # include/wavenet_hip.h WN_VQ_EMA_WORK_BYTES
+GCOND_MAX_CHANNELS = 512       # include/wavenet_hip.h WN_GCOND_MAX_CHANNELS
 
 _p = ctypes.c_void_p
 _i = ctypes.c_int
@@ -93,6 +94,8 @@ SIGNATURES = {
     "wn_step_nll": [_p, _l, _i, _p, _p, _l, _i, _p, _p, _p, _p, _i, _i, _i, _f, _p],
     "wn_cond_proj_fwd": [_p, _p, _l, _l, _l, _l, _l, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
     "wn_cond_proj_bwd": [_p, _i, _p, _p, _p, _l, _l, _l, _l, _l, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
+    "wn_gcond_proj_fwd": [_p, _p, _l, _l, _l, _l, _l, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _l, _l, _l, _l, _i, _i, _p],
+    "wn_gcond_proj_bwd": [_p, _i, _p, _p, _p, _l, _l, _l, _l, _l, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _l, _l, _l, _l, _i, _i, _p],
     "wn_vq_fwd": [_p, _p, _l, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     "wn_vq_bwd": [_p, _p, _p, _p, _l, _f, _f, _p, _p, _i, _i, _i, _i, _p],
     "wn_vq_lookup": [_p, _p, _l, _p, _p, _i, _i, _i, _i, _p],

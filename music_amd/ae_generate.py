@@ -38,12 +38,12 @@ except ImportError:
     from music_amd.train import load_model
 
 
-def predict_next(net, input_wav, quantization_channel=256, temperature=None, top_k=None, top_p=None, seed=0, step=0):
+def predict_next(net, input_wav, quantization_channel=256, temperature=None, top_k=None, top_p=None, seed=0, step=0, classes=None):
     """generate.py:13-19 — argmax over the last chunk-row of the forward output.  ``temperature`` > 0: the code is drawn by
     the decoder's sampler (``fast_generate.sample_logits`` on the log of that row: the softmax only shifts the logits) as
-    step ``step`` of ``seed``, truncated by ``top_k`` / ``top_p``."""
+    step ``step`` of ``seed``, truncated by ``top_k`` / ``top_p``.  ``classes``: the clip's class, for a model with global class conditioning."""
     with torch.no_grad():
-        out = net(input_wav).view(-1, quantization_channel)
+        out = (net(input_wav) if classes is None else net(input_wav, classes)).view(-1, quantization_channel)
     if temperature is not None and temperature > 0:
         try:
             from . import fast_generate as fg
@@ -89,16 +89,45 @@ def _decoder_wavenet(net, proj=None):
     return wnet.cuda()
 
 
-def cached_decoder(net, encoding, cond):
+def global_term(net, B, classes=None, global_vectors=None, what="decode"):
+    """The clip-level input of a decode: None for a model without global class conditioning (both arguments are refused there),
+    else the (B, E) float32 vectors on the model's device - the embedding rows of ``classes`` (B integers in [0, global_classes))
+    or ``global_vectors`` as given (a row may mix two embedding rows: timbre morphing).  Exactly one of the two is wanted."""
+    n = getattr(net, "global_classes", 0)
+    if not n:
+        if classes is not None or global_vectors is not None:
+            raise ValueError("music_amd.ae_generate.%s: the model has no global class conditioning (global_classes is 0): classes "
+                             "and global_vectors must be None" % what)
+        return None
+    if (classes is None) == (global_vectors is None):
+        raise ValueError("music_amd.ae_generate.%s: global_classes = %d: pass classes (one integer per clip) or global_vectors "
+                         "((B, %d) floats), never both" % (what, n, net.global_channels))
+    dev = net.global_embedding.weight.device
+    if classes is not None:
+        cls = torch.as_tensor(classes)
+        if cls.dim() != 1 or cls.numel() != B or cls.is_floating_point():
+            raise ValueError("music_amd.ae_generate.%s: classes must be %d integers, one per clip" % (what, B))
+        return net.global_vectors(cls).float()
+    gv = torch.as_tensor(global_vectors)
+    if gv.dim() != 2 or tuple(gv.shape) != (B, net.global_channels) or not gv.is_floating_point():
+        raise ValueError("music_amd.ae_generate.%s: global_vectors must be (%d, %d) floats, got %s %s"
+                         % (what, B, net.global_channels, gv.dtype, tuple(gv.shape)))
+    return gv.detach().to(device=dev, dtype=torch.float32)
+
+
+def cached_decoder(net, encoding, cond, gvec=None):
     """The autoencoder's conditioned decoder (model1.py:158-225) for ONE pooled frame of encoding
     ``(1, bottleneck, 1)`` and fixed conditioning projections ``cond`` (N+1 (weight (C, bottleneck, 1), bias (C,))
     pairs, gate rows first, the last one for the post-processing stage) as a ``music_amd.model.wavenet``:
     filter / gate = second / first half of ``filter_gate`` (model1.py:188-190), conditioning folded into the
-    biases.  Its forward and its cached-queue decoder (``fast_generate``) then reproduce the decoder exactly."""
+    biases.  Its forward and its cached-queue decoder (``fast_generate``) then reproduce the decoder exactly.
+    ``gvec`` (1, E): the clip's global vector (``global_term``), folded in as G_i gvec."""
     if encoding.dim() != 3 or encoding.size(0) != 1 or encoding.size(2) != 1:
         raise ValueError("cached_decoder needs a single pooled frame of encoding, got %s" % (tuple(encoding.shape),))
     enc = encoding.detach().float().cpu()[0, :, 0]
     proj = [w.detach().float().cpu()[:, :, 0] @ enc + b.detach().float().cpu() for w, b in cond]
+    if gvec is not None:
+        proj = [p + g.float().cpu() @ gvec.detach().float().cpu()[0] for p, g in zip(proj, net.global_projections())]
     return _decoder_wavenet(net, proj)
 
 
@@ -144,12 +173,13 @@ def conditioned_decoder(net, cond):
 
 
 def _decode_from_encoding(net, enc, cond, W, first, prime, forced, free_step=False, want_probs=False, temperature=None, seed=0,
-                          top_k=None, top_p=None, streams=None):
+                          top_k=None, top_p=None, streams=None, gvec=None):
     """What ``resynthesize`` and ``decode_codes`` share: from an encoding ``enc`` (B, Bw, Le) on the device and the conditioning
     projections ``cond``, build the per-clip tables and the schedule of a forward with ``W`` output rows, prime the queues from
     zero with the input samples ``first`` (B,) then ``prime`` (B, n) - teacher-forced steps at output positions -(rf - 1) .. -
     and decode the W output positions in one persistent conditioned launch, fed ``forced`` (B, W) or its own codes.
     ``free_step``: ``prime`` holds rf - 2 samples only and the sample in front of output position 0 is the model's own.
+    ``gvec`` (B, E): the clips' global vectors (``global_term``) - every column of clip b's tables gains G_i gvec[b].
     Returns (codes int32 (B, W), probabilities (B, W, Q) or None)."""
     try:
         from . import fast_generate as fg
@@ -172,6 +202,13 @@ def _decode_from_encoding(net, enc, cond, W, first, prime, forced, free_step=Fal
     cond_fg[..., :Dd] = en[..., :Dd]
     cond_fg[..., Dp:Dp + Dd] = en[..., Dd:]
     cond_p1 = (torch.einsum("ck,bkl->blc", proj[N][0], enc) + proj[N][1]).contiguous()
+    if gvec is not None:
+        # the per-clip term, constant over the frames: G_i gvec[b], the blocks' rows filter first like proj's
+        G = [g.float().to(dev) for g in net.global_projections()]
+        gfg = torch.einsum("nce,be->bnc", torch.stack([torch.cat([g[Dd:], g[:Dd]]) for g in G[:N]]), gvec.to(dev))
+        cond_fg[..., :Dd] += gfg[:, :, None, :Dd]
+        cond_fg[..., Dp:Dp + Dd] += gfg[:, :, None, Dd:]
+        cond_p1 += (gvec.to(dev) @ G[N].t())[:, None, :]
     sched = cond_schedule(net, W, Le)
     rw = fg._ring_width(deng)
     rings = torch.zeros(B, max(1, sum(K1 * d * rw for d in deng.dil)), dtype=torch.float32, device=dev)
@@ -192,7 +229,7 @@ def _decode_from_encoding(net, enc, cond, W, first, prime, forced, free_step=Fal
 
 
 def resynthesize(net, clips, cond=None, teacher_forced=False, want_probs=False, temperature=None, seed=0, top_k=None, top_p=None,
-                 streams=None):
+                 streams=None, classes=None, global_vectors=None):
     """Encode ``clips`` (B, Q, T) one-hot, T >= receptive_field with at least one pooled frame, and regenerate them from the
     encoding with the cached-queue decoder: the encoder runs ONCE, the conditioning projections are drawn ONCE (or taken
     from ``cond``), the per-clip tables (one column per pooled frame and stage) are built on the device, the queues are
@@ -204,7 +241,10 @@ def resynthesize(net, clips, cond=None, teacher_forced=False, want_probs=False, 
     argmax, reproducibly for ``seed``; ``top_k`` / ``top_p`` truncate the distribution first; each of the four may be one value per clip
     (``streams``: the clips' random-number stream ids, default their index).  Returns (codes int64 (B, W), probabilities (B, W, Q) or None, encodings (B, Bw, Le)).
     With a vq bottleneck the encoding is the quantised one, and ``net.vq_codes`` (B, Le) / ``net.last_encoding_pre`` hold the
-    frames' codes and the encoding in front of the quantiser."""
+    frames' codes and the encoding in front of the quantiser.
+    A model with global class conditioning wants ``classes`` (one integer per clip) or ``global_vectors`` ((B, E) floats, e.g. a
+    mix of two rows of ``net.global_vectors``), never both: the clips are decoded AS that class - their own for a reconstruction,
+    another for a conversion (the encoder takes no class)."""
     if clips.dim() != 3 or clips.size(1) != net.quantization_channel:
         raise ValueError("resynthesize: clips must be (B, %d, T)" % net.quantization_channel)
     x = clips.detach().cuda().float().contiguous()
@@ -215,9 +255,11 @@ def resynthesize(net, clips, cond=None, teacher_forced=False, want_probs=False, 
         raise ValueError("wave sample not long enough")
     eng_cond = net.engine_cond(cond)                                  # (learned conditioning: None, and a given `cond` is refused)
     cond = eng_cond if eng_cond is not None else net.conditioning_projections()
+    gvec = global_term(net, B, classes, global_vectors, "resynthesize")
     eng = net._engine_for(x.device)
     with torch.no_grad():
-        _, enc, ws = eng.forward(x, eng_cond, want_probs=False)           # (raises when the clip pools to no frame)
+        # (raises when the clip pools to no frame; with a global term the encoder alone runs: the decoder's class is the caller's)
+        _, enc, ws = eng.forward(x, eng_cond, want_probs=False, encode_only=gvec is not None)
     enc = net.last_encoding = enc.clone()
     if eng.vq:
         net.vq_codes, net.last_encoding_pre = ws["vq_idx"].to(torch.int64), ws["enc_pre"]
@@ -226,7 +268,7 @@ def resynthesize(net, clips, cond=None, teacher_forced=False, want_probs=False, 
     if teacher_forced:
         forced = torch.cat([codes_in[:, rf:], torch.zeros(B, 1, dtype=torch.int32, device=x.device)], 1)
     codes, probs = _decode_from_encoding(net, enc, cond, W, x[:, :, 0].contiguous(), codes_in[:, 1:rf], forced, want_probs=want_probs,
-                                         temperature=temperature, seed=seed, top_k=top_k, top_p=top_p, streams=streams)
+                                         temperature=temperature, seed=seed, top_k=top_k, top_p=top_p, streams=streams, gvec=gvec)
     return codes.to(torch.int64), probs, enc
 
 
@@ -251,7 +293,7 @@ def encode_codes(net, clips):
 
 
 def decode_codes(net, codes, W, start=None, teacher_forced=None, want_probs=False, temperature=None, top_k=None, top_p=None, seed=0,
-                 streams=None):
+                 streams=None, classes=None, global_vectors=None):
     """Audio codes from bottleneck codes: ``codes`` (B, Le) integers in [0, K) are looked up in the codebook (wn_vq_lookup; a code
     out of range raises) and the encoding is decoded as ``resynthesize`` decodes one - the same tables, schedule
     (``cond_schedule(net, W, Le)``), priming and persistent conditioned launch - into ``W`` samples per clip.
@@ -259,7 +301,8 @@ def decode_codes(net, codes, W, start=None, teacher_forced=None, want_probs=Fals
     the last is the model's own continuation; ``start=None`` primes with the mid code Q / 2 throughout, as
     ``fast_generate.generate`` does.  ``teacher_forced``: the codes (B, rf - 1 + W) of whole clips - they are fed instead of the
     model's own (the probabilities are then those of a forward over the clip whose encoding these codes are), ``start``
-    defaults to their first rf - 1.  ``temperature`` / ``top_k`` / ``top_p`` / ``seed`` / ``streams``: as in ``resynthesize``.
+    defaults to their first rf - 1.  ``temperature`` / ``top_k`` / ``top_p`` / ``seed`` / ``streams``: as in ``resynthesize``,
+    and so are ``classes`` / ``global_vectors`` (the same codes as another class: the conversion of VQ-VAE).
     Returns (codes int64 (B, W), probabilities (B, W, Q) or None)."""
     eng = _vq_engine(net, "decode_codes")
     dev = eng.device
@@ -267,6 +310,7 @@ def decode_codes(net, codes, W, start=None, teacher_forced=None, want_probs=Fals
     if codes.dim() != 2 or W < 1:
         raise ValueError("decode_codes: codes must be (B, Le) and W >= 1")
     B = codes.size(0)
+    gvec = global_term(net, B, classes, global_vectors, "decode_codes")
     enc = eng.vq_lookup(codes)
     as_codes = lambda t, n, what: _checked_codes(t, B, n, Q, dev, what)
     forced = last = None
@@ -284,7 +328,7 @@ def decode_codes(net, codes, W, start=None, teacher_forced=None, want_probs=Fals
     first.scatter_(1, seq[:, :1].to(torch.int64), 1.0)
     out, probs = _decode_from_encoding(net, enc, net.conditioning_projections(), W, first, seq[:, 1:].contiguous(), forced,
                                        free_step=last is None, want_probs=want_probs, temperature=temperature, seed=seed, top_k=top_k,
-                                       top_p=top_p, streams=streams)
+                                       top_p=top_p, streams=streams, gvec=gvec)
     return out.to(torch.int64), probs
 
 
@@ -297,37 +341,45 @@ def _checked_codes(t, B, n, Q, dev, what):
     return t.to(device=dev, dtype=torch.int32).contiguous()
 
 
-def generate_cached(net, start_piece, note_num, cond=None, temperature=None, seed=0, top_k=None, top_p=None):
+def generate_cached(net, start_piece, note_num, cond=None, temperature=None, seed=0, top_k=None, top_p=None, classes=None,
+                    global_vectors=None):
     """encode ``start_piece`` (1, Q, >= receptive_field) once, draw the conditioning projections once
     (or take ``cond``), then generate ``note_num`` codes with the persistent cached-queue decoder (corrected queue
-    recurrence).  Returns (codes int64 on the device, the wavenet-form decoder, the encoding)."""
+    recurrence).  Returns (codes int64 on the device, the wavenet-form decoder, the encoding).
+    ``classes`` ([c]) / ``global_vectors`` ((1, E)): the class to generate as, for a model with global class conditioning."""
     try:
         from . import fast_generate as fg
     except ImportError:
         from music_amd import fast_generate as fg
     if cond is not None:
         net.engine_cond(cond)                                # (learned conditioning: a given `cond` is refused, as in resynthesize)
+    gvec = global_term(net, start_piece.size(0), classes, global_vectors, "generate_cached")
     with torch.no_grad():
-        net(start_piece.cuda())                              # sets net.last_encoding (model1.py:256-268)
+        if gvec is None:
+            net(start_piece.cuda())                          # sets net.last_encoding (model1.py:256-268)
+        else:                                                # (the encoder alone: it takes no class)
+            x = start_piece.detach().cuda().float().contiguous()
+            net.last_encoding = net._engine_for(x.device).forward(x, None, want_probs=False, encode_only=True)[1].clone()
     enc = net.last_encoding
     if enc.size(2) != 1:
         raise ValueError("the start piece pools to %d frames; the cached decoder needs exactly one "
                          "(receptive_field + pool .. receptive_field + 2*pool - 1 samples)" % enc.size(2))
     if cond is None:
         cond = net.conditioning_projections()
-    wnet = cached_decoder(net, enc, cond)
+    wnet = cached_decoder(net, enc, cond) if gvec is None else cached_decoder(net, enc, cond, gvec)
     codes = fg.generate_codes(wnet, start_piece[:, :, -wnet.receptive_field:].cuda(), note_num, correct_queue=True,
                               temperature=temperature, seed=seed, top_k=top_k, top_p=top_p)
     return codes, wnet, enc
 
 
 def generate_codes_naive(net, start_piece, note_num, sliding_window=False, window=None, seed=None, temperature=None, top_k=None,
-                         top_p=None):
+                         top_p=None, classes=None):
     """The loop of generate.py:44-55: one full forward (encoder + conditioned decoder, fresh random conditioning
     projections) per generated code.  ``sliding_window`` False = as written (growing window), True = the last
     ``window - 1`` samples + the new one (``window`` defaults to receptive_field + 512).  ``seed``: torch.manual_seed(seed + i)
     before step i (the projections are drawn from the global RNG), for reproducible runs and the golden tests.
-    ``temperature`` / ``top_k`` / ``top_p``: draw each code with the decoder's sampler instead of the argmax (``predict_next``)."""
+    ``temperature`` / ``top_k`` / ``top_p``: draw each code with the decoder's sampler instead of the argmax (``predict_next``).
+    ``classes`` ([c]): the clip's class, for a model with global class conditioning (every step is the model's own forward)."""
     win = window if window is not None else net.receptive_field + 512
     input_wav = start_piece.cuda()
     generated = []
@@ -335,7 +387,7 @@ def generate_codes_naive(net, start_piece, note_num, sliding_window=False, windo
         if seed is not None:
             torch.manual_seed(int(seed) + i)
         code = predict_next(net, input_wav, net.quantization_channel, temperature=temperature, top_k=top_k, top_p=top_p,
-                            seed=seed or 0, step=i)
+                            seed=seed or 0, step=i, **({} if classes is None else {"classes": classes}))
         generated.append(code)
         note = torch.zeros(1, net.quantization_channel, 1, device=input_wav.device)
         note[0, code, 0] = 1.0
@@ -345,7 +397,13 @@ def generate_codes_naive(net, start_piece, note_num, sliding_window=False, windo
 
 
 def generate(model_path, model_name, generate_path, generate_name, start_piece=None, sr=16000, duration=10,
-             sliding_window=False, seed=None, temperature=None, top_k=None, top_p=None):
+             sliding_window=False, seed=None, temperature=None, top_k=None, top_p=None, classes=None, global_vectors=None):
+    """``classes`` ([c]) for a model with global class conditioning: the class to generate as.  ``global_vectors`` is refused here -
+    this loop runs the model's own forward, which takes class ids; ``generate_cached`` / ``resynthesize`` / ``decode_codes`` decode
+    from a vector."""
+    if global_vectors is not None:
+        raise ValueError("music_amd.ae_generate.generate runs the model's own forward per code, which takes classes; decode from "
+                         "global_vectors with generate_cached, resynthesize or decode_codes")
     if os.path.exists(generate_path) is False:
         os.makedirs(generate_path)
     with open('./params/model_params.json') as f:
@@ -359,7 +417,8 @@ def generate(model_path, model_name, generate_path, generate_name, start_piece=N
         start_piece = torch.zeros(1, 256, net.receptive_field + 512)
         start_piece[:, 128, :] = 1.0
     generated = generate_codes_naive(net, start_piece, int(duration * sr), sliding_window=sliding_window,
-                                     window=start_piece.size(2), seed=seed, temperature=temperature, top_k=top_k, top_p=top_p)
+                                     window=start_piece.size(2), seed=seed, temperature=temperature, top_k=top_k, top_p=top_p,
+                                     classes=classes)
     audio = mu_law_decode(torch.tensor(generated, dtype=torch.int64), net.quantization_channel).cpu().numpy()
     from scipy.io import wavfile
     wavfile.write(generate_path + generate_name, sr, audio.astype(np.float32))

@@ -115,11 +115,13 @@ class GenericAutoencoderEngine(GeneralPlan):
         return out
 
     # ------------------------------------------------------------------ forward (model1.py:256-268)
-    def forward(self, x, cond=None, want_probs=True, encode_only=False):
+    def forward(self, x, cond=None, want_probs=True, encode_only=False, classes=None):
         """cond: the N + 1 drawn (weight, bias) pairs; None with learned conditioning (parameters of the flat buffer);
+        classes: one integer per clip with global class conditioning, else None;
         encode_only=True stops behind the pooled (and, with a vq bottleneck, quantised) encoding: (None, enc, ws)"""
         self._check_cond(cond)
         B, Q, T = x.shape
+        cls = None if encode_only and classes is None else self.stage_classes(classes, B)      # (the encoder takes no classes)
         assert Q == self.Q and x.is_contiguous() and x.dtype == torch.float32 and x.is_cuda
         W = T - self.rf + 1
         if W <= 0:
@@ -128,7 +130,7 @@ class GenericAutoencoderEngine(GeneralPlan):
         if Le < 1:
             raise RuntimeError("Output size is too small: %d samples of encoding cannot be pooled by %d" % (W, self.pool))
         ws = self._ws.get(B, T)
-        ws["Le"] = Le
+        ws["Le"], ws["cls"] = Le, cls
         N, pitch, dev = self.N, ws["pitch"], self.device
         ReP, DeP, BwP, RdP, DdP, SP, QP = self.ReP, self.DeP, self.BwP, self.RdP, self.DdP, self.SP, self.QP
         if not self.learned:
@@ -169,7 +171,7 @@ class GenericAutoencoderEngine(GeneralPlan):
         if self.learned:                                                               # the learned projections: one launch, every table
             tab = torch.empty(N, B, 2 * DdP, Le, dtype=torch.float32, device=dev)
             enf = torch.empty(B, Sd, Le, dtype=torch.float32, device=dev)
-            self.cond_proj_fwd(enc, tab, None, enf, DdP, st)
+            self.cond_proj_fwd(enc, tab, None, enf, DdP, st, cls)
             ws.update(enc=enc, cmodes=cmodes)
         else:
             en = torch.einsum("nck,bkl->nbcl", cw, enc) + cb[:, None, :, None]         # (N, B, 2Dd, Le)
@@ -259,7 +261,7 @@ class GenericAutoencoderEngine(GeneralPlan):
         # ---- conditioning projections (unregistered, no gradient of their own): d enc = sum_i cw_i^T d en_i + cfw^T d enf
         if self.learned:                     # ... parameters of their own: d enc, dW and db (flat_grad's tail) in wn_cond_proj_bwd
             d_enc = torch.empty(B, Bw, Le, dtype=torch.float32, device=dev)
-            self.cond_proj_bwd(d_tab, False, d_enf, ws["enc"], d_enc, DdP, st)
+            self.cond_proj_bwd(d_tab, False, d_enf, ws["enc"], d_enc, DdP, st, ws["cls"])
             if self.vq:                                       # straight through to e, + the commitment term; the codebook's gradient
                 self.vq_bwd(ws, d_enc, st)
         else:
@@ -296,6 +298,7 @@ class GenericAutoencoderEngine(GeneralPlan):
         ps.reduce_grads()
 
     # ------------------------------------------------------------------ fused training step (wavenet_autoencoder/train.py:146-160)
-    def loss_and_grad(self, x, target, cond=None, objective=None):
+    def loss_and_grad(self, x, target, cond=None, objective=None, classes=None):
         """objective: None = self.objective (EngineBase)"""
-        return self._throttled(lambda: self._fused_tail(self.forward(x, cond, want_probs=False)[2], target, objective=objective))
+        return self._throttled(lambda: self._fused_tail(self.forward(x, cond, want_probs=False, classes=classes)[2], target,
+                                                       objective=objective))

@@ -40,6 +40,12 @@ of one of the most used codes' frames).  The update runs on the device behind ev
 alone); under data parallelism the per-code counts and sums are summed over the ranks first, so every replica makes the same update.
 The ``vq_log.log`` line then ends with ``, restarted N``, the codes restarted since the line before.  A checkpoint carries the running
 state (``vq_ema_state``) and only loads into a model built with the same ``"vq_update"``.
+``"global_classes"`` and ``"global_channels"`` (both 0, the default: off; both >= 1 together, ``"conditioning": "learned"`` required):
+global class conditioning of the decoder - every clip has a class (speaker, instrument) whose learned embedding is projected into
+every conditioning table (music_amd/model1.py).  The classes come from the optional dataset_params.json key ``"labels_path"``, a
+JSON list of integers in [0, global_classes), one per item of the audio pickle (``"valid_labels_path"`` in train_params.json for the
+held-out set); a model with the mode on and no ``"labels_path"`` is refused at start, as are labels without the mode.  A checkpoint
+only loads into a model built with the same two values.
 """
 import glob
 import os
@@ -180,6 +186,19 @@ def train():
         raise ValueError("Cuda is not avalable,", " can not train model using multi-gpu.")
     # optional keys "objective", "valid_audio_path", "validate_every": as in music_amd/train.py (music_amd/objective.py)
     objective = wobjective.objective_option(train_params)
+    n_global = getattr(net, "global_classes", 0)
+    if n_global and not dataset_params.get("labels_path"):
+        raise ValueError('model_params.json sets "global_classes": %d, so dataset_params.json must name the clips\' classes with '
+                         '"labels_path" (a JSON list of integers, one per item of the audio pickle)' % n_global)
+    if dataset_params.get("labels_path"):
+        if not n_global:
+            raise ValueError('dataset_params.json has "labels_path" but model_params.json leaves "global_classes" at 0: nothing would '
+                             'read the labels')
+        dataset_params = dict(dataset_params, n_classes=n_global)         # a label outside [0, global_classes) raises at load
+        if train_params.get("valid_audio_path") and int(train_params.get("validate_every") or 0) > 0 \
+                and not train_params.get("valid_labels_path"):
+            raise ValueError('train_params.json: validating a model with "global_classes" needs "valid_labels_path", the classes of the '
+                             'items of "valid_audio_path"')
     validation = wobjective.Validation.make(train_params, dataset_params) if rank == 0 else None
     if world > 1:
         assert dataset_params["batch_size"] % world == 0
@@ -236,6 +255,9 @@ def train():
     for epoch in range(train_params["num_epochs"]):
         for i_batch, sampled_batch in enumerate(dataloader):
             piece, target = sampled_batch["audio_piece"], sampled_batch["audio_target"]
+            # global class conditioning: the clips' classes, (B,) on the host, as ONE more keyword of the calls below - without it they
+            # are made as they always were
+            kw = {"classes": sampled_batch["audio_class"]} if "audio_class" in sampled_batch else {}
             dp_scale = float(sampled_batch.get("dp_scale", 1.0))      # ragged last batch, see faster_audio_data._Collate
             if piece is not None:
                 target = target.view(-1)
@@ -259,7 +281,7 @@ def train():
                 optimizer.zero_grad()
                 loss = torch.zeros((), device=device)
                 if piece is not None:
-                    loss = wobjective.nll_loss(net, piece, target) if objective == "nll" else loss_func(net(piece), target)
+                    loss = wobjective.nll_loss(net, piece, target, **kw) if objective == "nll" else loss_func(net(piece, **kw), target)
                     if is_vq:
                         loss = loss + net.vq_loss
                     loss.backward()
@@ -268,7 +290,7 @@ def train():
             if fused:
                 loss = torch.zeros((), device=device)
                 if piece is not None:
-                    loss = engine.loss_and_grad(piece.to(device).float().contiguous(), target.to(device), net.engine_cond())
+                    loss = engine.loss_and_grad(piece.to(device).float().contiguous(), target.to(device), net.engine_cond(), **kw)
                 else:
                     engine.flat_grad.zero_()
                     if is_vq_ema:

@@ -459,6 +459,65 @@ int wn_cond_proj_bwd(const float* d_tab, int pair, const float* d_enf, const flo
     p.n_stages = n_stages; p.dd = dd; p.ch = ch; p.sd = sd; p.bw = bw; p.le = le; p.batch = batch;
     return wn_launch_cond_proj_bwd(p, (hipStream_t)stream);
 }
+// ---- learned conditioning projections with a global class term (wn_gcond.hip) ----
+static_assert(WN_GCOND_MAX_E == WN_GCOND_MAX_CHANNELS, "wn_kernels.h and wavenet_hip.h disagree");
+// the refusals of cond_proj_checked, then the new arguments' (they need no pointer either)
+static int gcond_checked(const char* fn, int64_t w_off, int64_t b_off, int64_t stage_stride, int64_t wf_off, int64_t bf_off, int pair,
+                         int n_stages, int dd, int ch, int sd, int bw, int le, int batch, int64_t gw_off, int64_t gstage_stride,
+                         int64_t gwf_off, int64_t emb_off, int ge, int n_cls) {
+    if (int rc = cond_proj_checked(fn, w_off, b_off, stage_stride, wf_off, bf_off, pair, n_stages, dd, ch, sd, bw, le, batch)) return rc;
+    char msg[200];
+    const char* bad = nullptr;
+    if (ge < 1 || ge > WN_GCOND_MAX_CHANNELS) bad = "'ge' must lie in [1, 512]";
+    else if (n_cls < 1) bad = "'n_cls' must be >= 1";
+    else if (gw_off < 0) bad = "'gw_off' must be >= 0";
+    else if (gwf_off < 0) bad = "'gwf_off' must be >= 0";
+    else if (emb_off < 0) bad = "'emb_off' must be >= 0";
+    else if (n_stages > 1 && gstage_stride < (int64_t)2 * dd * ge) bad = "'gstage_stride' must be >= 2 * dd * ge (the stages' weights overlap)";
+    if (bad) {
+        snprintf(msg, sizeof(msg), "%s: argument %s", fn, bad);
+        return wn_set_error_msg(-4, msg);
+    }
+    return 0;
+}
+static WnGcond gcond_args(const int32_t* cls, int64_t gw_off, int64_t gstage_stride, int64_t gwf_off, int64_t emb_off, int ge, int n_cls) {
+    WnGcond g;
+    g.cls = cls; g.gw_off = (long)gw_off; g.gstage_stride = (long)gstage_stride; g.gwf_off = (long)gwf_off; g.emb_off = (long)emb_off;
+    g.ge = ge; g.n_cls = n_cls;
+    return g;
+}
+int wn_gcond_proj_fwd(const float* enc, const float* flat, int64_t w_off, int64_t b_off, int64_t stage_stride, int64_t wf_off,
+                      int64_t bf_off, float* tab, float* tab_pair, float* enf, int n_stages, int dd, int ch, int sd, int bw, int le,
+                      int batch, const int32_t* cls, int64_t gw_off, int64_t gstage_stride, int64_t gwf_off, int64_t emb_off, int ge,
+                      int n_cls, wn_stream_t stream) {
+    if (int rc = gcond_checked("wn_gcond_proj_fwd", w_off, b_off, stage_stride, wf_off, bf_off, tab_pair != nullptr, n_stages, dd, ch, sd,
+                               bw, le, batch, gw_off, gstage_stride, gwf_off, emb_off, ge, n_cls)) return rc;
+    if (batch == 0) return 0;
+    WN_REQUIRE("wn_gcond_proj_fwd", enc, flat, enf, cls);
+    if (!tab && !tab_pair) return wn_set_error_msg(-4, "wn_gcond_proj_fwd: argument 'tab' or 'tab_pair' must not be NULL");
+    WnCondProj p;
+    memset(&p, 0, sizeof(p));
+    p.enc = enc; p.flat = flat; p.w_off = (long)w_off; p.b_off = (long)b_off; p.stage_stride = (long)stage_stride;
+    p.wf_off = (long)wf_off; p.bf_off = (long)bf_off; p.tab = tab; p.tab_pair = tab_pair; p.enf = enf;
+    p.n_stages = n_stages; p.dd = dd; p.ch = ch; p.sd = sd; p.bw = bw; p.le = le; p.batch = batch;
+    return wn_launch_gcond_proj_fwd(p, gcond_args(cls, gw_off, gstage_stride, gwf_off, emb_off, ge, n_cls), (hipStream_t)stream);
+}
+int wn_gcond_proj_bwd(const float* d_tab, int pair, const float* d_enf, const float* enc, const float* flat, int64_t w_off,
+                      int64_t b_off, int64_t stage_stride, int64_t wf_off, int64_t bf_off, float* d_enc, float* flat_grad,
+                      int n_stages, int dd, int ch, int sd, int bw, int le, int batch, const int32_t* cls, int64_t gw_off,
+                      int64_t gstage_stride, int64_t gwf_off, int64_t emb_off, int ge, int n_cls, wn_stream_t stream) {
+    if (int rc = gcond_checked("wn_gcond_proj_bwd", w_off, b_off, stage_stride, wf_off, bf_off, pair, n_stages, dd, ch, sd, bw, le, batch,
+                               gw_off, gstage_stride, gwf_off, emb_off, ge, n_cls)) return rc;
+    if (batch == 0) return 0;
+    WN_REQUIRE("wn_gcond_proj_bwd", d_tab, d_enf, enc, flat, d_enc, flat_grad, cls);
+    WnCondProj p;
+    memset(&p, 0, sizeof(p));
+    p.enc = enc; p.flat = flat; p.w_off = (long)w_off; p.b_off = (long)b_off; p.stage_stride = (long)stage_stride;
+    p.wf_off = (long)wf_off; p.bf_off = (long)bf_off; p.d_tab = d_tab; p.d_pair = pair ? 1 : 0; p.d_enf = d_enf; p.d_enc = d_enc;
+    p.flat_grad = flat_grad;
+    p.n_stages = n_stages; p.dd = dd; p.ch = ch; p.sd = sd; p.bw = bw; p.le = le; p.batch = batch;
+    return wn_launch_gcond_proj_bwd(p, gcond_args(cls, gw_off, gstage_stride, gwf_off, emb_off, ge, n_cls), (hipStream_t)stream);
+}
 // ---- vector-quantised bottleneck (wn_vq.hip) ----
 // the refusals the three entries share: shapes and the offset first (they need no pointer)
 static int vq_checked(const char* fn, int64_t cb_off, int K, int bw, int le, int batch) {

@@ -255,6 +255,18 @@ struct WnCondProj {
 };
 int wn_launch_cond_proj_fwd(const WnCondProj& p, hipStream_t st);
 int wn_launch_cond_proj_bwd(const WnCondProj& p, hipStream_t st);
+bool wn_cond_denc_fits(const WnCondProj& p);                   // d enc's grid of this shape is one the device takes
+int wn_launch_cond_denc(const WnCondProj& p, hipStream_t st);  // d enc alone (the caller has checked wn_cond_denc_fits)
+// the same with a global class term (wn_gcond.hip): clip b's tables gain G_i emb[cls[b]], constant over its frames.  Stage i's G
+// [2 dd][ge] sits at gw_off + i * gstage_stride, the final stage's [sd][ge] at gwf_off, the embedding [n_cls][ge] at emb_off.
+#define WN_GCOND_MAX_E 512
+struct WnGcond {
+    const int32_t* cls;
+    long gw_off, gstage_stride, gwf_off, emb_off;
+    int ge, n_cls;
+};
+int wn_launch_gcond_proj_fwd(const WnCondProj& p, const WnGcond& g, hipStream_t st);
+int wn_launch_gcond_proj_bwd(const WnCondProj& p, const WnGcond& g, hipStream_t st);
 // vector-quantised bottleneck (wn_vq.hip): the codebook [K][bw] sits at flat + cb_off (its gradient at flat_grad + cb_off)
 #define WN_VQ_PARTIALS 256
 struct WnVq {

@@ -253,30 +253,47 @@ class EngineBase:
     n_vq = 0                     # its floats: wn_vq_bwd writes that tail of flat_grad
     last_vq = None               # VqStats of the last forward (vq only)
     vq_ema = False               # net.vq_update == "ema": wn_vq_bwd_stats in place of wn_vq_bwd, wn_vq_ema_update behind the optimizer
+    gcond = False                # net.global_classes > 0: the global block [G_0 .. G_N-1 | G_f | embedding] ends the flat buffer, behind the codebook
+    n_gcond = 0                  # its floats: wn_gcond_proj_bwd writes that tail of flat_grad (and the projections' in front of the codebook)
 
     @property
     def n_gather(self):
         """Leading elements of flat_grad that the gather of the gradient pack fills."""
-        return self.spec.total - self.n_cond - self.n_vq
+        return self.spec.total - self.n_cond - self.n_vq - self.n_gcond
 
     @property
     def gathered_param_names(self):
-        """The parameters whose gradients come out of the gradient pack: all but the learned projections' 2 (N + 1) and the codebook,
-        the last ones."""
-        return self.param_names[:len(self.param_names) - (2 * (len(self.dil) + 1) if self.learned else 0) - (1 if self.vq else 0)]
+        """The parameters whose gradients come out of the gradient pack: all but the learned projections' 2 (N + 1), the codebook and
+        the global block's N + 2, the last ones."""
+        N = len(self.dil)
+        return self.param_names[:len(self.param_names) - (2 * (N + 1) if self.learned else 0) - (1 if self.vq else 0) - (N + 2 if self.gcond else 0)]
 
     def _plan_cond(self, net):
         """Learned mode: where wn_cond_proj_fwd / wn_cond_proj_bwd find the projections in the flat buffers; the vq bottleneck's
-        codebook behind them."""
+        codebook behind them, the global class conditioning's block behind that: the tail of flat / flat_grad is
+        [projections | codebook | global block]."""
         self.learned = getattr(net, "conditioning", "random") == "learned"
         self.vq = getattr(net, "bottleneck", "continuous") == "vq"
+        self.gcond = int(getattr(net, "global_classes", 0)) > 0
+        if self.gcond:
+            if not self.learned:
+                raise ValueError('music_amd: global_classes > 0 requires conditioning="learned"')
+            o, N = self.spec.off, len(self.dil)
+            E, n = self.g_E, self.g_n = int(net.global_channels), int(net.global_classes)
+            gw0, gwf, emb = o["de_gcond_layer_stack.0.weight"], o["connection_gcond.weight"], o["global_embedding.weight"]
+            gstride = 2 * self.Dd * E
+            # registered last, in stage order: one constant stage stride, the final stage's G and the embedding behind the stages'
+            assert all(o["de_gcond_layer_stack.%d.weight" % i] == gw0 + i * gstride for i in range(N)) and gwf == gw0 + N * gstride \
+                and emb == gwf + self.Sd * E and emb + n * E == self.spec.total
+            self.gcond_off = (gw0, gstride, gwf, emb)
+            self.n_gcond = self.spec.total - gw0
         if self.vq:
             if not self.learned:
                 raise ValueError('music_amd: bottleneck="vq" requires conditioning="learned"')
             self.vq_K, self.vq_beta = int(net.vq_codebook.num_embeddings), float(net.vq_beta)
             self.vq_off = self.spec.off["vq_codebook.weight"]
             self.n_vq = self.vq_K * self.Bw
-            assert self.spec.shape["vq_codebook.weight"] == (self.vq_K, self.Bw) and self.vq_off + self.n_vq == self.spec.total
+            assert self.spec.shape["vq_codebook.weight"] == (self.vq_K, self.Bw) and self.vq_off + self.n_vq == self.spec.total - self.n_gcond
             self.vq_ema = getattr(net, "vq_update", "gradient") == "ema"
             if self.vq_ema:
                 # [n | s] of the last backward, the update's scratch and its restart counters; the running state is the MODULE's buffer
@@ -291,11 +308,11 @@ class EngineBase:
         w0, b0 = o["de_cond_layer_stack.0.weight"], o["de_cond_layer_stack.0.bias"]
         stride = 2 * self.Dd * self.Bw + 2 * self.Dd
         wf, bf = o["connection_cond.weight"], o["connection_cond.bias"]
-        # registered last (the codebook alone behind them), in stage order (weight, bias per stage): one constant stage stride
+        # registered last (the codebook and the global block alone behind them), in stage order (weight, bias per stage): one constant stage stride
         assert all(o["de_cond_layer_stack.%d.weight" % i] == w0 + i * stride and o["de_cond_layer_stack.%d.bias" % i] == b0 + i * stride
-                   for i in range(N)) and wf == w0 + N * stride and bf + self.Sd == self.spec.total - self.n_vq
+                   for i in range(N)) and wf == w0 + N * stride and bf + self.Sd == self.spec.total - self.n_vq - self.n_gcond
         self.cond_off = (w0, b0, stride, wf, bf)
-        self.n_cond = self.spec.total - self.n_vq - w0
+        self.n_cond = self.spec.total - self.n_vq - self.n_gcond - w0
 
     # ------------------------------------------------------------------ vector-quantised bottleneck (the autoencoder's engines)
     def vq_fwd(self, ws, enc, st):
@@ -382,18 +399,46 @@ class EngineBase:
         if not self.learned and cond is None:
             raise ValueError('music_amd: conditioning="random": pass the drawn projections (net.conditioning_projections()) as cond')
 
-    def cond_proj_fwd(self, enc, tab, tab_pair, enf, ch, st):
-        """All N + 1 projections of enc (B, Bw, Le) out of the flat buffer in one launch: the block tables (per clip and / or as clip
-        pairs, padding rows included) and the final table enf (B, Sd, Le)."""
-        B, _, Le = enc.shape
-        call("wn_cond_proj_fwd", ptr(enc), ptr(self.flat), *self.cond_off, ptr(tab), ptr(tab_pair), ptr(enf), len(self.dil), self.Dd, ch,
-             self.Sd, self.Bw, Le, B, st)
+    def stage_classes(self, classes, B):
+        """`classes` of forward / loss_and_grad -> what the workspace keeps as ws["cls"]: None with the mode off (a given vector is
+        refused), else the (B,) int32 class vector on the device - ONE copy per step; values that are still on the host are checked
+        against [0, n) here, before anything is launched (a device tensor's are the kernel's to turn into NaN)."""
+        if not self.gcond:
+            if classes is not None:
+                raise ValueError("music_amd: global_classes is 0: this model takes no classes, pass classes=None")
+            return None
+        if classes is None:
+            raise ValueError("music_amd: global_classes = %d: pass classes, one integer in [0, %d) per clip" % (self.g_n, self.g_n))
+        cls = classes if torch.is_tensor(classes) else torch.as_tensor(list(classes))
+        if cls.dim() != 1 or cls.numel() != B or cls.is_floating_point() or cls.is_complex() or cls.dtype == torch.bool:
+            raise ValueError("music_amd: classes must be %d integers, one per clip, not %s of shape %s" % (B, cls.dtype, tuple(cls.shape)))
+        if cls.device.type == "cpu" and B and not (0 <= int(cls.min()) and int(cls.max()) < self.g_n):
+            raise ValueError("music_amd: a class lies outside [0, %d) (global_classes)" % self.g_n)
+        return cls.to(device=self.device, dtype=torch.int32, non_blocking=True).contiguous()
 
-    def cond_proj_bwd(self, d_tab, pair, d_enf, enc, d_enc, ch, st):
-        """d enc and the projections' own gradients (into the tail of flat_grad) from the block tables' and the final table's gradients."""
+    def _gcond_args(self, cls):
+        return (ptr(cls),) + self.gcond_off + (self.g_E, self.g_n)
+
+    def cond_proj_fwd(self, enc, tab, tab_pair, enf, ch, st, cls=None):
+        """All N + 1 projections of enc (B, Bw, Le) out of the flat buffer in one launch: the block tables (per clip and / or as clip
+        pairs, padding rows included) and the final table enf (B, Sd, Le); with global class conditioning plus every clip's
+        G emb[cls[b]] (wn_gcond_proj_fwd, `cls` = stage_classes' vector)."""
         B, _, Le = enc.shape
-        call("wn_cond_proj_bwd", ptr(d_tab), 1 if pair else 0, ptr(d_enf), ptr(enc), ptr(self.flat), *self.cond_off, ptr(d_enc),
-             ptr(self.flat_grad), len(self.dil), self.Dd, ch, self.Sd, self.Bw, Le, B, st)
+        args = (ptr(enc), ptr(self.flat)) + self.cond_off + (ptr(tab), ptr(tab_pair), ptr(enf), len(self.dil), self.Dd, ch, self.Sd, self.Bw,
+                                                            Le, B)
+        if self.gcond:
+            return call("wn_gcond_proj_fwd", *args, *self._gcond_args(cls), st)
+        call("wn_cond_proj_fwd", *args, st)
+
+    def cond_proj_bwd(self, d_tab, pair, d_enf, enc, d_enc, ch, st, cls=None):
+        """d enc and the projections' own gradients (into the tail of flat_grad) from the block tables' and the final table's gradients;
+        with global class conditioning the global block's too (wn_gcond_proj_bwd)."""
+        B, _, Le = enc.shape
+        args = (ptr(d_tab), 1 if pair else 0, ptr(d_enf), ptr(enc), ptr(self.flat)) + self.cond_off + (
+            ptr(d_enc), ptr(self.flat_grad), len(self.dil), self.Dd, ch, self.Sd, self.Bw, Le, B)
+        if self.gcond:
+            return call("wn_gcond_proj_bwd", *args, *self._gcond_args(cls), st)
+        call("wn_cond_proj_bwd", *args, st)
 
     # ------------------------------------------------------------------ the second stream
     def _side_stream(self):

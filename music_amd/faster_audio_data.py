@@ -7,6 +7,7 @@ keeps the int32 codes, a batch crosses PCIe as B x T int32 (128 KB at 8 x 16000)
 B x 256 x T float32 (131 MB), and the one-hot is written directly in HBM by ``wn_onehot``.
 ``num_workers`` is accepted and ignored (there is no per-item CPU work left to parallelise).
 """
+import json
 import pickle
 
 import torch
@@ -21,35 +22,59 @@ except ImportError:
 class audio_dataset(Dataset):
 
     def __init__(self, audio_path, receptive_field, window_length, cuda_available=False,
-                 quantization_channels=256):
+                 quantization_channels=256, labels_path=None, n_classes=None):
+        """labels_path (the optional key "labels_path" of dataset_params.json): a JSON list of integers, one class per item of the
+        audio pickle (global class conditioning of the autoencoder); every piece then carries 'audio_class', the label of the item
+        it was cut from.  n_classes: the model's global_classes - a label outside [0, n_classes) raises here."""
         self.audio_path = audio_path
+        self.labels_path = labels_path
         self.receptive_field = receptive_field
         self.window_length = window_length
         self.cuda_available = cuda_available
         self.quantization_channels = quantization_channels
         with open(self.audio_path, 'rb') as f:
             data = pickle.load(f)
-        self.data = self._make_data_pieces(data)
+        self.data = self._make_data_pieces(data, self._load_labels(len(data), n_classes))
 
-    def _make_data_pieces(self, data):
+    def _load_labels(self, n_items, n_classes):
+        if self.labels_path is None:
+            return None
+        with open(self.labels_path) as f:
+            labels = json.load(f)
+        if not isinstance(labels, list) or any(isinstance(v, bool) or not isinstance(v, int) for v in labels):
+            raise ValueError("labels_path %s: a JSON list of integers is wanted" % self.labels_path)
+        if len(labels) != n_items:
+            raise ValueError("labels_path %s: %d labels for %d items of %s" % (self.labels_path, len(labels), n_items, self.audio_path))
+        hi = n_classes if n_classes is not None else float("inf")
+        bad = [v for v in labels if not 0 <= v < hi]
+        if bad:
+            raise ValueError("labels_path %s: label %d lies outside [0, %s) (global_classes)"
+                             % (self.labels_path, bad[0], n_classes if n_classes is not None else "inf"))
+        return labels
+
+    def _make_data_pieces(self, data, labels=None):
         """faster_audio_data.py:24-40.  A remainder longer than rf but shorter than rf+window
         advances by rf and appends the PREVIOUS piece/target again (the reference's `else` branch
         assigns nothing new); a first item that short raises NameError, as the reference does."""
         rf, win = self.receptive_field, self.window_length
         pieces = []
-        piece = target = None
-        for item in data:
+        piece = target = label = None
+        for n, item in enumerate(data):
             item = torch.from_numpy(item)
             while len(item) > rf:
                 if len(item) >= rf + win:
                     piece = item[:rf + win - 1]
                     target = item[rf:rf + win].long()
+                    label = labels[n] if labels is not None else None
                     item = item[win:]
                 else:
                     item = item[rf:]
                 if target is None:
                     raise NameError("name 'target' is not defined")
-                pieces.append({'audio_piece': piece, 'audio_target': target})
+                # (a re-appended piece keeps the label of the item its samples came from - the previous item's, where a short item
+                # repeats that one's last piece)
+                pieces.append({'audio_piece': piece, 'audio_target': target} if labels is None else
+                              {'audio_piece': piece, 'audio_target': target, 'audio_class': label})
         return pieces
 
     def __len__(self):
@@ -158,6 +183,8 @@ class _Collate:
             target = torch.stack([it['audio_target'] for it in items])
             target = target.cuda(non_blocking=True) if torch.cuda.is_available() else target
         batch = {"audio_piece": onehot_device(codes, self.q, scrambled=self.scrambled), "audio_target": target}
+        if "audio_class" in items[0]:                # (labels_path: this shard's classes, on the host - the engine checks and copies them)
+            batch["audio_class"] = torch.tensor([it["audio_class"] for it in items], dtype=torch.int64)
         if self.shard is not None:
             batch["dp_scale"] = scale
         return batch
@@ -170,7 +197,8 @@ def audio_data_loader(batch_size, shuffle, num_workers, pin_memory, shard=None, 
     train.py under torchrun) makes this process build only its contiguous chunk of every global
     batch; all ranks must share the torch seed so they draw the same permutation.  ``one_hot`` (the optional key "one_hot" of
     dataset_params.json): "scrambled" is the reference's reshape-not-transpose layout, "canonical" the true one-hot
-    x[b][code[t]][t] = 1 - what a model trained on the true likelihood (music_amd/objective.py) and the decoder see."""
+    x[b][code[t]][t] = 1 - what a model trained on the true likelihood (music_amd/objective.py) and the decoder see.
+    With ``labels_path`` (audio_dataset) a batch also has "audio_class": int64 (B,) on the HOST, the classes of this process's clips."""
     if one_hot not in ONE_HOT_LAYOUTS:
         raise ValueError("one_hot must be one of %s, not %r" % (", ".join(ONE_HOT_LAYOUTS), one_hot))
     audioDataset = audio_dataset(**kwargs)

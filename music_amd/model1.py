@@ -215,20 +215,22 @@ class _AutoencoderEngine(EngineBase):
     def _lay(self, t, i, ch, ws):
         return ptr(t, SLACK + i * ws["B"] * ch * ws["pitch"])
 
-    def forward(self, x, cond=None, want_probs=True, encode_only=False):
+    def forward(self, x, cond=None, want_probs=True, encode_only=False, classes=None):
         """cond: list of N+1 (weight (C,Bw,1), bias (C,)) CPU tensors (see wavenet_autoencoder.forward); None with learned
         conditioning, whose projections are parameters of the flat buffer.
+        classes: one integer per clip with global class conditioning (EngineBase.stage_classes), else None.
         want_probs=False stops at the pre-softmax logits in ws["O"] (the fused training step); encode_only=True behind the pooled
         (and, with a vq bottleneck, quantised) encoding: (None, enc, ws), nothing of the decoder runs."""
         self._check_cond(cond)
         B, Q, T = x.shape
+        cls = None if encode_only and classes is None else self.stage_classes(classes, B)      # (the encoder takes no classes)
         W = T - self.rf + 1
         Le = W // self.pool
         if Le < 1:
             raise RuntimeError("Output size is too small: %d samples of encoding cannot be pooled by %d" % (W, self.pool))
         ws = self._ws.get(B, T)
         self._gen += 1
-        ws["gen"], ws["x_in"], ws["Le"] = self._gen, x, Le
+        ws["gen"], ws["x_in"], ws["Le"], ws["cls"] = self._gen, x, Le, cls
         pair = ws["pair"] = self.pair_ok and B % 2 == 0 and Le <= 32      # decided per workspace shape (B, T fix Le)
         # the forward blocks pair only when that fills the chip (music_amd/engine.py); the backward blocks always
         pair_f = pair and (B // 2) * ((T + 511) // 512) >= 200
@@ -287,7 +289,7 @@ class _AutoencoderEngine(EngineBase):
             tab_c = empty(N, B, 2 * CHd, Le) if not pair_f else None
             tab = empty(N, B // 2, 4 * CHd, Le) if pair else tab_c
             enf = empty(B, Sd, Le)
-            self.cond_proj_fwd(enc, tab_c, tab if pair else None, enf, CHd, st)
+            self.cond_proj_fwd(enc, tab_c, tab if pair else None, enf, CHd, st, cls)
             ws.update(enc=enc, tab=tab)
         else:
             en = torch.einsum("nck,bkl->nbcl", cw, enc) + cb[:, None, :, None]             # (N, B, 2Dd, Le)
@@ -424,12 +426,13 @@ class _AutoencoderEngine(EngineBase):
         ws["bwd"] = bw
         return bw
 
-    def loss_and_grad(self, x, target, cond=None, objective=None):
+    def loss_and_grad(self, x, target, cond=None, objective=None, classes=None):
         """Fused training step body (the autoencoder counterpart of engine.loss_and_grad): forward to the logits, ONE
         kernel for chunk softmax + CrossEntropyLoss on the probabilities (wavenet_autoencoder/train.py:146-160) + both
         backward steps, then the backward.  Returns the loss (0-d device tensor); gradients land in self.flat_grad.
         objective: None = self.objective (EngineBase)."""
-        return self._throttled(lambda: self._fused_tail(self.forward(x, cond, want_probs=False)[2], target, objective=objective))
+        return self._throttled(lambda: self._fused_tail(self.forward(x, cond, want_probs=False, classes=classes)[2], target,
+                                                       objective=objective))
 
     def backward_from_dlogits(self, ws):
         self.backward(ws, None)
@@ -537,7 +540,7 @@ class _AutoencoderEngine(EngineBase):
         if self.learned:
             # ... and they are parameters: d enc, dW and db (into flat_grad's tail) straight from the block tables' layout
             d_enc = torch.empty(B, Bw, Le, dtype=torch.float32, device=self.device)
-            self.cond_proj_bwd(d_tab, pair, d_enf, ws["enc"], d_enc, CHd, st)
+            self.cond_proj_bwd(d_tab, pair, d_enf, ws["enc"], d_enc, CHd, st, ws["cls"])
             if self.vq:                                       # straight through to e, + the commitment term; the codebook's gradient
                 self.vq_bwd(ws, d_enc, st)
         else:
@@ -607,7 +610,7 @@ CONDITIONING = ("random", "learned")     # the decoder's conditioning projection
 
 class _AutoencoderFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, net, grad_on, wave_sample, cond, *params):
+    def forward(ctx, net, grad_on, wave_sample, cond, classes, *params):
         eng = net._engine_for(wave_sample.device)
         x = wave_sample.detach()
         if x.dtype != torch.float32 or not x.is_contiguous():
@@ -616,7 +619,7 @@ class _AutoencoderFunction(torch.autograd.Function):
             tag = getattr(wave_sample, "_wn_codes", None)        # one-hot built from codes (see _AutoencoderEngine.forward)
             if tag is not None and wave_sample._version == tag[2]:
                 x._wn_codes = (tag[0], tag[1], x._version, tag[3])
-        probs, enc, ws = eng.forward(x, cond)
+        probs, enc, ws = eng.forward(x, cond, classes=classes)
         net.last_encoding = enc
         ctx.eng, ctx.ws, ctx.gen = eng, ws, ws["gen"]
         ctx.loss_hook = net._last_hook = _losshook.make(eng, ws, grad_on)
@@ -649,7 +652,7 @@ class _AutoencoderFunction(torch.autograd.Function):
             o, shp = eng.spec.off[name], eng.spec.shape[name]
             grads.append(g[o:o + int(np.prod(shp))].view(shp))
         din = eng.input_grad(ws) if ctx.needs_input_grad[2] else None       # (the reference's two causal nn.Conv1d give it, model1.py:137,158)
-        return (None, None, din, None) + tuple(grads)
+        return (None, None, din, None, None) + tuple(grads)
 
 
 class wavenet_autoencoder(nn.Module):
@@ -657,8 +660,20 @@ class wavenet_autoencoder(nn.Module):
     def __init__(self, filter_width, quantization_channel, dilations, en_residual_channel, en_dilation_channel,
                  en_bottleneck_width, en_pool_kernel_size, de_residual_channel, de_dilation_channel,
                  de_skip_channel, use_bias, conditioning="random", bottleneck="continuous", vq_codes=512, vq_beta=0.25,
-                 vq_update="gradient", vq_decay=0.99, vq_eps=1e-5, vq_restart=0.0):
+                 vq_update="gradient", vq_decay=0.99, vq_eps=1e-5, vq_restart=0.0, global_classes=0, global_channels=0):
         super(wavenet_autoencoder, self).__init__()
+        for key, val in (("global_classes", global_classes), ("global_channels", global_channels)):
+            if isinstance(val, bool) or not isinstance(val, int) or val < 0:
+                raise ValueError("music_amd.wavenet_autoencoder: %s must be an integer >= 0, not %r" % (key, val))
+        if (global_classes > 0) != (global_channels > 0):
+            raise ValueError("music_amd.wavenet_autoencoder: global_classes and global_channels must both be 0 (off) or both >= 1, "
+                             "not %r and %r" % (global_classes, global_channels))
+        if global_channels > _lib.GCOND_MAX_CHANNELS:
+            raise ValueError("music_amd.wavenet_autoencoder: global_channels must lie in [1, %d], not %r"
+                             % (_lib.GCOND_MAX_CHANNELS, global_channels))
+        if global_classes > 0 and conditioning != "learned":
+            raise ValueError('music_amd.wavenet_autoencoder: global_classes > 0 requires conditioning="learned" (the class term is one '
+                             'more term of the learned projections\' tables)')
         if conditioning not in CONDITIONING:
             raise ValueError("music_amd.wavenet_autoencoder: conditioning must be one of %s, not %r"
                              % (", ".join('"%s"' % c for c in CONDITIONING), conditioning))
@@ -691,6 +706,7 @@ class wavenet_autoencoder(nn.Module):
         self.conditioning = conditioning
         self.bottleneck, self.vq_num_codes, self.vq_beta = bottleneck, int(vq_codes), float(vq_beta)
         self.vq_update, self.vq_decay, self.vq_eps, self.vq_restart = vq_update, float(vq_decay), float(vq_eps), float(vq_restart)
+        self.global_classes, self.global_channels = global_classes, global_channels
         self.filter_width = filter_width
         self.quantization_channel = quantization_channel
         self.dilations = dilations
@@ -751,6 +767,13 @@ class wavenet_autoencoder(nn.Module):
                 # codebook.  A buffer: it travels with state_dict() (as the LAST key) and the module's moves, no optimizer sees it
                 self.register_buffer("vq_ema_state", torch.empty(self.vq_num_codes * (en_bottleneck_width + 1)))
                 self.reset_vq_ema_state()
+        if global_classes > 0:
+            # global class conditioning (VQ-VAE's speaker id, NSynth's instrument): en_i[b] = W_i enc[b] + b_i + G_i emb[cls[b]].  The
+            # G_i (gate rows first, like de_cond_layer_stack), G_f and the embedding are registered - and drawn - BEHIND everything the
+            # model has without them, the codebook included: a seed gives every earlier parameter the same value and flat offset
+            self.de_gcond_layer_stack = nn.ModuleList(nn.Conv1d(global_channels, 2 * de_dilation_channel, 1, bias=False) for _ in dilations)
+            self.connection_gcond = nn.Conv1d(global_channels, de_skip_channel, 1, bias=False)
+            self.global_embedding = nn.Embedding(global_classes, global_channels)
 
     def __setstate__(self, state):
         super(wavenet_autoencoder, self).__setstate__(state)
@@ -760,6 +783,8 @@ class wavenet_autoencoder(nn.Module):
             self.__dict__.setdefault(k, v)
         for k in ("vq_loss", "vq_codes", "last_encoding_pre", "last_vq"):
             self.__dict__.setdefault(k, None)
+        self.__dict__.setdefault("global_classes", 0)
+        self.__dict__.setdefault("global_channels", 0)
 
     def init_codebook(self, encodings, seed=0):
         """Data-dependent initialisation: K frames of `encodings` (B, Bw, Le) - pre-quantisation encodings, net.last_encoding_pre -
@@ -805,6 +830,26 @@ class wavenet_autoencoder(nn.Module):
             return [(m.weight.detach(), m.bias.detach()) for m in self._cond_modules()]
         return self._draw_conditioning()
 
+    def global_projections(self):
+        """The N + 1 (detached) matrices G_i (2 Dd, E) - rows in the reference's order, gate first - and G_f (Sd, E) that project a
+        clip's global vector into the conditioning tables."""
+        self._need_global("global_projections")
+        return [m.weight.detach()[:, :, 0] for m in list(self.de_gcond_layer_stack) + [self.connection_gcond]]
+
+    def global_vectors(self, classes):
+        """The (detached) embedding rows (B, E) of `classes`, B integers in [0, global_classes): what decoding takes as
+        ``global_vectors=`` (a mix of two rows morphs between their classes)."""
+        self._need_global("global_vectors")
+        w = self.global_embedding.weight.detach()
+        cls = torch.as_tensor(classes, dtype=torch.int64).reshape(-1)
+        if cls.numel() and not (0 <= int(cls.min()) and int(cls.max()) < self.global_classes):
+            raise ValueError("music_amd.wavenet_autoencoder: a class lies outside [0, %d) (global_classes)" % self.global_classes)
+        return w[cls.to(w.device)]
+
+    def _need_global(self, what):
+        if not getattr(self, "global_classes", 0):
+            raise ValueError("music_amd.wavenet_autoencoder: %s needs global_classes > 0" % what)
+
     def engine_cond(self, cond=None):
         """What the engine's forward / loss_and_grad take as `cond`: None with learned conditioning (a given list is refused there),
         else `cond` or a fresh draw."""
@@ -834,6 +879,13 @@ class wavenet_autoencoder(nn.Module):
             raise RuntimeError('music_amd.wavenet_autoencoder: the checkpoint was saved with vq_update="%s" but this model was built '
                                'with vq_update="%s" (the "vq_update" key of model_params.json); nothing was loaded'
                                % ("ema" if has_ema else "gradient", mine_ema))
+        emb = state_dict.get("global_embedding.weight", state_dict.get("module.global_embedding.weight"))
+        saved = tuple(emb.shape) if emb is not None and emb.dim() == 2 else (0, 0)
+        mine_g = (getattr(self, "global_classes", 0), getattr(self, "global_channels", 0))
+        if saved != mine_g:
+            raise RuntimeError("music_amd.wavenet_autoencoder: the checkpoint was saved with global_classes=%d, global_channels=%d but "
+                               "this model was built with global_classes=%d, global_channels=%d (the keys of model_params.json); "
+                               "nothing was loaded" % (saved + mine_g))
         return super(wavenet_autoencoder, self).load_state_dict(state_dict, *args, **kwargs)
 
     def __getstate__(self):
@@ -897,15 +949,18 @@ class wavenet_autoencoder(nn.Module):
             self._engine = eng
         return eng
 
-    def forward(self, wave_sample):
+    def forward(self, wave_sample, classes=None):
         batch_size, original_channels, seq_len = wave_sample.size()
         output_width = seq_len - self.receptive_field + 1
         if output_width <= 0:
             raise ValueError("wave sample not long enough")
+        if (classes is None) == bool(getattr(self, "global_classes", 0)):      # (before the engine is built and anything is drawn)
+            raise ValueError("music_amd.wavenet_autoencoder: global_classes = %d: classes must be %s"
+                             % (getattr(self, "global_classes", 0), "None" if classes is not None else "given, one integer per clip"))
         self._engine_for(wave_sample.device)
         cond = self.engine_cond()
         self._last_hook = None
-        out = _AutoencoderFunction.apply(self, torch.is_grad_enabled(), wave_sample, cond, *list(self.parameters()))
+        out = _AutoencoderFunction.apply(self, torch.is_grad_enabled(), wave_sample, cond, classes, *list(self.parameters()))
         if getattr(self, "bottleneck", "continuous") == "vq":
             out, self.vq_loss = out
         hook, self._last_hook = self._last_hook, None

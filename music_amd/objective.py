@@ -36,7 +36,7 @@ def _dense_input(wave_sample):
     return x
 
 
-def _forward_logits(net, wave_sample):
+def _forward_logits(net, wave_sample, classes=None):
     """The module's forward up to the pre-softmax logits: (engine, workspace with the logits in ws["O"]).  The autoencoder draws its
     per-forward conditioning convs from the global RNG, as its own forward does (learned ones are parameters: nothing is drawn)."""
     if wave_sample.dim() != 3:
@@ -46,7 +46,7 @@ def _forward_logits(net, wave_sample):
     eng = net._engine_for(wave_sample.device)
     x = _dense_input(wave_sample)
     if hasattr(net, "engine_cond"):
-        _, enc, ws = eng.forward(x, net.engine_cond(), want_probs=False)
+        _, enc, ws = eng.forward(x, net.engine_cond(), want_probs=False, classes=classes)
         net.last_encoding = enc
     else:
         eng.pack_weights()
@@ -66,8 +66,8 @@ class _NLLFunction(torch.autograd.Function):
     backward_from_dlogits scaled by the upstream scalar."""
 
     @staticmethod
-    def forward(ctx, net, grad_on, wave_sample, target, *params):
-        eng, ws = _forward_logits(net, wave_sample)
+    def forward(ctx, net, grad_on, wave_sample, target, classes, *params):
+        eng, ws = _forward_logits(net, wave_sample, classes)
         need = grad_on and any(ctx.needs_input_grad)
         eng.step_nll(ws, _flat_target(target, ws), eng._bwd_workspace(ws)["dO"] if need else None)
         ctx.eng, ctx.ws, ctx.gen = eng, ws, ws["gen"]
@@ -99,7 +99,7 @@ class _NLLFunction(torch.autograd.Function):
             o, shp = eng.spec.off[name], eng.spec.shape[name]
             grads.append(g[o:o + int(np.prod(shp))].view(shp))
         din = eng.input_grad(ws) * dloss if ctx.needs_input_grad[2] else None
-        return (None, None, din, None) + tuple(grads)
+        return (None, None, din, None, None) + tuple(grads)
 
 
 def _params(net):
@@ -107,25 +107,28 @@ def _params(net):
     return [p for _, p in net._named_ref_params()] if hasattr(net, "_named_ref_params") else list(net.parameters())
 
 
-def nll_loss(net, x, target):
+def nll_loss(net, x, target, classes=None):
     """Mean negative log-likelihood (nats per sample) of `target` (B, W) or (B W,) int64 under the per-timestep softmax of
     net's logits for the one-hot x (B, Q, T): a 0-d tensor whose backward() gives the parameter gradients (and the input's, when it
-    requires grad).  A target outside [0, Q) makes the loss NaN."""
-    out = _NLLFunction.apply(net, torch.is_grad_enabled(), x, target, *_params(net))
+    requires grad).  A target outside [0, Q) makes the loss NaN.  classes: one integer per clip for an autoencoder with global class
+    conditioning (required there, refused elsewhere)."""
+    if classes is not None and not hasattr(net, "engine_cond"):
+        raise ValueError("music_amd.objective: classes are the autoencoder's (global class conditioning)")
+    out = _NLLFunction.apply(net, torch.is_grad_enabled(), x, target, classes, *_params(net))
     if isinstance(out, tuple):                                  # a vq autoencoder: the caller adds net.vq_loss
         out, net.vq_loss = out
     return out
 
 
-def step_probs(net, x):
+def step_probs(net, x, classes=None):
     """(B W, Q) probabilities: row b W + w is softmax over the Q logits of output column w of clip b - what the decoder samples
     from (the module's own forward returns the reference's chunk softmax instead)."""
     with torch.no_grad():
-        eng, ws = _forward_logits(net, x)
+        eng, ws = _forward_logits(net, x, classes)
         return eng.step_probs(ws)
 
 
-def score(net, x_or_codes, target, scrambled=False):
+def score(net, x_or_codes, target, scrambled=False, classes=None):
     """Held-out figures of net on one batch, forward only.  x_or_codes: the one-hot (B, Q, T) float, or the integer codes (B, T) -
     then the one-hot is laid out canonical, or as the loader scrambles it with `scrambled`.  Returns device tensors of
     shape (B,), float64: "nll" (mean nats per sample of each clip), "bits" (nll / ln 2) and "accuracy" (share of samples whose
@@ -135,7 +138,7 @@ def score(net, x_or_codes, target, scrambled=False):
         if x.dim() == 2:
             q = getattr(net, "quantization_channels", None) or net.quantization_channel
             x = faster_audio_data.onehot_device(x, q, scrambled)
-        eng, ws = _forward_logits(net, x)
+        eng, ws = _forward_logits(net, x, classes)
         row_nll, row_hit = eng.score_logits(ws, _flat_target(target, ws))
         B, W = ws["B"], ws["W"]
         nll = row_nll.view(B, W).double().mean(1)
@@ -161,11 +164,14 @@ class Validation:
         path, every = train_params.get("valid_audio_path"), int(train_params.get("validate_every") or 0)
         if not path or every <= 0:
             return None
-        return cls(path, every, dataset_params, train_params["log_dir"])
+        return cls(path, every, dataset_params, train_params["log_dir"], train_params.get("valid_labels_path"))
 
-    def __init__(self, audio_path, every, dataset_params, log_dir):
-        params = {k: v for k, v in dataset_params.items() if k != "shard"}
+    def __init__(self, audio_path, every, dataset_params, log_dir, labels_path=None):
+        # (the training set's labels name the training pickle's items: the held-out set's come from "valid_labels_path")
+        params = {k: v for k, v in dataset_params.items() if k not in ("shard", "labels_path")}
         params.update(audio_path=audio_path, shuffle=False)
+        if labels_path:
+            params.update(labels_path=labels_path)
         self.every = every
         self.loader = faster_audio_data.audio_data_loader(**params)
         self.log_path = log_dir + "valid_log.log"
@@ -177,7 +183,8 @@ class Validation:
             for batch in self.loader:
                 if batch["audio_piece"] is None:
                     continue
-                r = score(net, batch["audio_piece"], batch["audio_target"])
+                kw = {"classes": batch["audio_class"]} if "audio_class" in batch else {}       # (global class conditioning)
+                r = score(net, batch["audio_piece"], batch["audio_target"], **kw)
                 part = torch.stack([r["nll"].sum(), r["bits"].sum(), r["accuracy"].sum()])
                 total = part if total is None else total + part
                 clips += r["nll"].numel()

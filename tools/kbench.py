@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of single kernels of the hot path at BASELINE config-2 shapes (GPU only).
 
-    python tools/kbench.py [fwd|bwd|epi|dx|skip|decode|ae|guard|ema|nll|cond|vq|vq_ema|all] [--reps N] [--precision f16x3,bf16x3]
+    python tools/kbench.py [fwd|bwd|epi|dx|skip|decode|ae|guard|ema|nll|cond|vq|vq_ema|gcond|all] [--reps N] [--precision f16x3,bf16x3]
 
 Prints per-phase / per-layer kernel times measured with HIP events on the launch stream.
 """
@@ -224,13 +224,145 @@ def vq_ema_bench(reps, alternations=6):
     print(json.dumps(res))
 
 
+def _write_profile(name, res):
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", name), "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+
+
+def bench_unset(parent, alternations=6):
+    """bench.py of this tree (the new keys unset: the feature launches nothing there) against a built checkout of the parent commit at
+    `parent`, alternated `alternations` times, each run a process of its own.  Called before this process touches the device."""
+    import subprocess
+    runs = {"parent": [], "tree": []}
+    for _ in range(alternations):
+        for label, root in (("parent", parent), ("tree", ROOT)):
+            out = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "60", "--warmup", "20"], cwd=root, check=True,
+                                 stdout=subprocess.PIPE, timeout=300).stdout.decode()
+            line = json.loads([ln for ln in out.splitlines() if ln.startswith("{")][-1])
+            runs[label].append({k: line[k] for k in ("ms_per_step", "value") if k in line})
+    res = {"what": "bench.py --gpus 1 --steps 60 --warmup 20 with global_classes / global_channels unset, parent commit and this tree "
+                   "alternating on one MI355X, %d pairs, parent first" % alternations}
+    res.update(runs)
+    for label, v in runs.items():
+        ms = [r["ms_per_step"] for r in v if "ms_per_step" in r]
+        if ms:
+            res[label + "_ms_per_step_median"], res[label + "_ms_per_step_spread"] = _median_spread(ms)
+    _write_profile("gcond_bench_unset.json", res)
+    print(json.dumps(res))
+
+
+def gcond_bench(reps, alternations=6, E=64, n_cls=8):
+    """`gcond`: global class conditioning.  (a) wn_gcond_proj_fwd / _bwd beside wn_cond_proj_fwd / _bwd, whose place they take, alone
+    at config 4's shape and at the shipped autoencoder's with E = 64 channels, HIP events around `reps` calls; (b) the fused config-4
+    step of a global model against the learned model; everything alternated `alternations` times on one device, medians and spreads
+    (largest - smallest).  Written to profiles/gcond_kbench.json."""
+    import time
+    from music_amd import _lib
+    from music_amd._lib import call, ptr
+    from music_amd.model1 import wavenet_autoencoder
+    st = _lib.stream()
+    res = {"alternations": alternations, "E": E, "n_cls": n_cls}
+    rng = np.random.default_rng(0)
+    shapes = {"config4": dict(N=30, Dd=64, CH=64, Sd=256, Bw=64, Le=25, B=8, pair=False),
+              "shipped": dict(N=40, Dd=32, CH=32, Sd=512, Bw=512, Le=32, B=4, pair=True)}
+    legs = {}
+    for tag, g in shapes.items():
+        N, Dd, CH, Sd, Bw, Le, B, pair = (g[k] for k in ("N", "Dd", "CH", "Sd", "Bw", "Le", "B", "pair"))
+        rnd = lambda *shape: torch.randn(*shape, device="cuda")
+        stride = 2 * Dd * Bw + 2 * Dd
+        n_l = N * stride + Sd * Bw + Sd
+        n = n_l + N * 2 * Dd * E + Sd * E + n_cls * E
+        flat, grad, enc = rnd(n) * 0.1, torch.empty(n, device="cuda"), rnd(B, Bw, Le)
+        offs = (0, 2 * Dd * Bw, stride, N * stride, N * stride + Sd * Bw)
+        goffs = (n_l, 2 * Dd * E, n_l + N * 2 * Dd * E, n_l + N * 2 * Dd * E + Sd * E, E, n_cls)
+        dims = (N, Dd, CH, Sd, Bw, Le, B)
+        tab, tabp, enf = rnd(N, B, 2 * CH, Le), (rnd(N, B // 2, 4 * CH, Le) if pair else None), rnd(B, Sd, Le)
+        d_enc = torch.empty(B, Bw, Le, device="cuda")
+        cls = torch.from_numpy((np.arange(B) % n_cls).astype(np.int32)).cuda()
+        fwd = (ptr(enc), ptr(flat)) + offs + (ptr(tab), ptr(tabp), ptr(enf)) + dims
+        bwd = (ptr(tabp if pair else tab), 1 if pair else 0, ptr(enf), ptr(enc), ptr(flat)) + offs + (ptr(d_enc), ptr(grad)) + dims
+        keep = (flat, grad, enc, tab, tabp, enf, d_enc, cls)
+        legs[(tag, "cond_fwd")] = (lambda a=fwd, k=keep: call("wn_cond_proj_fwd", *a, st))
+        legs[(tag, "cond_bwd")] = (lambda a=bwd, k=keep: call("wn_cond_proj_bwd", *a, st))
+        legs[(tag, "gcond_fwd")] = (lambda a=fwd + (ptr(cls),) + goffs, k=keep: call("wn_gcond_proj_fwd", *a, st))
+        legs[(tag, "gcond_bwd")] = (lambda a=bwd + (ptr(cls),) + goffs, k=keep: call("wn_gcond_proj_bwd", *a, st))
+        res["shape_" + tag] = g
+
+    def launches(fn, n):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        torch.cuda.synchronize()
+        ev[0].record()
+        for _ in range(n):
+            fn()
+        ev[1].record()
+        torch.cuda.synchronize()
+        return ev[0].elapsed_time(ev[1]) / n * 1e3
+    times = {key: [] for key in legs}
+    for key, fn in legs.items():
+        launches(fn, 20)                                                      # warm
+    for _ in range(alternations):
+        for key, fn in legs.items():
+            times[key].append(launches(fn, max(reps, 100)))
+    for (tag, leg), v in times.items():
+        res["wn_%s_%s_us" % (leg.replace("_", "_proj_"), tag)], res["wn_%s_%s_us_spread" % (leg.replace("_", "_proj_"), tag)] = _median_spread(v)
+    # ---- the fused config-4 step
+    cfg = dict(filter_width=2, quantization_channel=256, dilations=CFG["dilations"], en_residual_channel=64, en_dilation_channel=64,
+               en_bottleneck_width=64, en_pool_kernel_size=512, de_residual_channel=64, de_dilation_channel=64, de_skip_channel=256,
+               use_bias=False, conditioning="learned")
+    codes = torch.from_numpy(rng.integers(0, 256, size=(B_LOCAL, T)).astype(np.int32)).cuda()
+    from music_amd.faster_audio_data import onehot_device
+    x = onehot_device(codes, 256, True)
+    engs = {}
+    for mode, kw in (("learned", {}), ("global", dict(global_classes=n_cls, global_channels=E))):
+        torch.manual_seed(0)
+        net = wavenet_autoencoder(**dict(cfg, **kw)).cuda()
+        eng = net._engine_for(torch.device("cuda", 0))
+        eng.adam_init(lr=1e-4)
+        engs[mode] = eng
+    W = T - engs["global"].rf + 1
+    target = torch.from_numpy(rng.integers(0, 256, size=(B_LOCAL * W,)).astype(np.int64)).cuda()
+    classes = torch.arange(B_LOCAL, dtype=torch.int64) % n_cls               # on the host, as the loader hands them on
+
+    def steps(mode, n):
+        eng = engs[mode]
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            loss = eng.loss_and_grad(x, target, None, classes=classes if mode == "global" else None)
+            eng.adam_step()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / n * 1e3, float(loss)
+    for mode in engs:
+        steps(mode, 5)
+    step_ms = {m: [] for m in engs}
+    for _ in range(alternations):
+        for mode in engs:
+            ms, loss = steps(mode, max(reps, 20))
+            step_ms[mode].append(ms)
+            res["fused_step_loss_" + mode] = round(loss, 5)
+    for mode, v in step_ms.items():
+        res["fused_step_ms_" + mode], res["fused_step_ms_%s_spread" % mode] = _median_spread(v)
+    res["fused_step_ms_global_minus_learned"] = round(res["fused_step_ms_global"] - res["fused_step_ms_learned"], 3)
+    res["fused_step_ms_by_alternation"] = {m: [round(t, 3) for t in v] for m, v in step_ms.items()}
+    res["shape_config4_step"] = dict(B=B_LOCAL, T=T, Le=W // 512, Bw=64, E=E, n_cls=n_cls)
+    _write_profile("gcond_kbench.json", res)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", nargs="?", default="all")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--precision", default="f16x3,bf16x3")
     ap.add_argument("--overlap", type=int, default=1)
+    ap.add_argument("--parent", default=None, help="gcond: a built checkout of the parent commit, for profiles/gcond_bench_unset.json")
     args = ap.parse_args()
+    if args.what == "gcond":
+        if args.parent:
+            bench_unset(os.path.abspath(args.parent))
+        return gcond_bench(args.reps)
     if args.what == "vq":
         return vq_bench(args.reps)
     if args.what == "vq_ema":
