@@ -519,6 +519,40 @@ int wn_vq_bwd_stats(const float* enc, const int32_t* idx, const float* d_q, cons
                     float* d_enc, float* flat_grad, float* stat, int K, int bw, int le, int batch, wn_stream_t stream);
 int wn_vq_ema_update(float* flat, int64_t cb_off, const float* stat, float* state, void* work, int32_t* info, int K, int bw,
                      float decay, float eps, float restart, const wn_guard_state* guard_state, wn_stream_t stream);
+/* ---- RESIDUAL vector quantisation of the same bottleneck (SoundStream, EnCodec): S codebooks of K rows, stage s owns rows
+ * [s K, (s + 1) K) of the (S K, bw) block at flat + cb_off.  With r_0 = e, for s = 0 .. S-1, everything in float32:
+ *   idx_s = argmin_k sum_j (r_s,j - c_s,kj)^2 (wn_vq_fwd's rule: the difference form, ties to the smallest k);   q_s = c_s[idx_s]
+ *   r_s+1 = r_s - q_s;          q = (..(q_0 + q_1) + ..) + q_S-1 (ascending, NOT e - r_S: a lookup from the codes gives the same bits)
+ *   mse_s = sum (r_s - q_s)^2 / (C bw);          the model's vq_loss = coef sum_s mse_s
+ * The frames are independent, so the chain is one launch per direction.  wn_rvq_fwd (one launch and the memset node for counts)
+ * writes q_out, idx (int32 [S][batch][le]), counts (int32 [S][K]; may be NULL), res ([S][batch][bw][le], res[s] = r_s+1: the
+ * backward reads it) and loss_part ([S][WN_VQ_NUM_PARTIALS], ALL rewritten at every call, row s sums to mse_s).
+ * wn_rvq_bwd, one launch, the residual passing between the stages detached (s = 2 / (C bw), g_scale the scalar on vq_loss):
+ *   d_enc = d_q + g_scale beta s (r_1 + r_2 + .. + r_S)      the sum in ascending order, then ONE fma onto d_q; d_enc may alias d_q
+ *   d_c_s[k] = g_scale s sum_{frames with idx_s = k, ascending} (c_s,k - r_s)      all S K rows overwritten, 0 for an unused row
+ * wn_rvq_bwd_stats in its place (EMA mode): the same d_enc, stat = S blocks of [n | sums of r_s] (K (bw + 1) floats each, all
+ * written) and exact zeros into all S K codebook rows of flat_grad.  An idx outside [0, K), in any stage, is compared and never
+ * dereferenced: that frame's d_enc becomes NaN.
+ * wn_rvq_ema_update: wn_vq_ema_update's rule and its two launches for all stages at once (the stage is a second grid dimension), each
+ * stage on its own block of stat and state - dead codes and donors are ranked within the stage.  work: S x WN_VQ_EMA_WORK_BYTES,
+ * info: int32 [S][2] (may be NULL), guard_state as there.
+ * wn_rvq_lookup: q_out = the sum of the first `stages` (1 .. S) stages' rows, in stage order, from idx [stages][batch][le] - a prefix of
+ * the stages is the coarser code; an idx outside [0, K) gives a NaN frame and sets *bad (cleared by the call; may be NULL).
+ * On `stream`, no allocation, no float atomics, a fixed order: the same bits at every launch, and at S = 1 the bits of the wn_vq_*
+ * entry.  Limits and refusals (-4, function and argument named, before any launch) as for wn_vq_*, and: S outside
+ * [1, WN_RVQ_MAX_STAGES]; stages outside [1, S]; a NULL res.  batch == 0 returns 0 and writes nothing. */
+#define WN_RVQ_MAX_STAGES 8
+int wn_rvq_fwd(const float* enc, const float* flat, int64_t cb_off, float* q_out, int32_t* idx, int32_t* counts, float* res,
+               float* loss_part, int S, int K, int bw, int le, int batch, wn_stream_t stream);
+int wn_rvq_bwd(const float* enc, const int32_t* idx, const float* res, const float* d_q, const float* flat, int64_t cb_off, float beta,
+               float g_scale, float* d_enc, float* flat_grad, int S, int K, int bw, int le, int batch, wn_stream_t stream);
+int wn_rvq_bwd_stats(const float* enc, const int32_t* idx, const float* res, const float* d_q, const float* flat, int64_t cb_off, float beta,
+                     float g_scale, float* d_enc, float* flat_grad, float* stat, int S, int K, int bw, int le, int batch,
+                     wn_stream_t stream);
+int wn_rvq_ema_update(float* flat, int64_t cb_off, const float* stat, float* state, void* work, int32_t* info, int S, int K, int bw,
+                      float decay, float eps, float restart, const wn_guard_state* guard_state, wn_stream_t stream);
+int wn_rvq_lookup(const int32_t* idx, const float* flat, int64_t cb_off, float* q_out, int32_t* bad, int S, int stages, int K, int bw,
+                  int le, int batch, wn_stream_t stream);
 /* The reference's nn.DataParallel gradient reduction (wavenet/train.py:116-122) as ONE in-place sum over the ranks of the flat
  * fp32 gradient buffer: ncclAllReduce(buf, buf, n, ncclFloat32, ncclSum, comm, stream) on the caller's RCCL communicator
  * (`comm` = an ncclComm_t).  The 1 / world_size of the mean goes into wn_adam_flat's gscale.  Returns -5 when RCCL is neither

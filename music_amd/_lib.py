@@ -18,6 +18,7 @@ GUARD_PARTIALS_BYTES = GUARD_NUM_PARTIALS * 12
 VQ_NUM_PARTIALS = 256          # include/wavenet_hip.h WN_VQ_NUM_PARTIALS
 VQ_MAX_CODES, VQ_MAX_WIDTH = 1024, 512
 VQ_EMA_WORK_BYTES = 16 + 4 * VQ_MAX_CODES      # include/wavenet_hip.h WN_VQ_EMA_WORK_BYTES
+RVQ_MAX_STAGES = 8             # include/wavenet_hip.h WN_RVQ_MAX_STAGES
 GCOND_MAX_CHANNELS = 512       # include/wavenet_hip.h WN_GCOND_MAX_CHANNELS
 
 _p = ctypes.c_void_p
@@ -101,6 +102,11 @@ SIGNATURES = {
     "wn_vq_lookup": [_p, _p, _l, _p, _p, _i, _i, _i, _i, _p],
     "wn_vq_bwd_stats": [_p, _p, _p, _p, _l, _f, _f, _p, _p, _p, _i, _i, _i, _i, _p],
     "wn_vq_ema_update": [_p, _l, _p, _p, _p, _p, _i, _i, _f, _f, _f, _p, _p],
+    "wn_rvq_fwd": [_p, _p, _l, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
+    "wn_rvq_bwd": [_p, _p, _p, _p, _p, _l, _f, _f, _p, _p, _i, _i, _i, _i, _i, _p],
+    "wn_rvq_bwd_stats": [_p, _p, _p, _p, _p, _l, _f, _f, _p, _p, _p, _i, _i, _i, _i, _i, _p],
+    "wn_rvq_ema_update": [_p, _l, _p, _p, _p, _p, _i, _i, _i, _f, _f, _f, _p, _p],
+    "wn_rvq_lookup": [_p, _p, _l, _p, _p, _i, _i, _i, _i, _i, _i, _p],
     "wn_coll_available": [],
     "wn_comm_unique_id": [_p],
     "wn_comm_create": [_i, _i, _p, _p],

@@ -240,7 +240,7 @@ def resynthesize(net, clips, cond=None, teacher_forced=False, want_probs=False, 
     model's own codes are fed back after the clip's first receptive_field samples.  ``temperature``: sample instead of
     argmax, reproducibly for ``seed``; ``top_k`` / ``top_p`` truncate the distribution first; each of the four may be one value per clip
     (``streams``: the clips' random-number stream ids, default their index).  Returns (codes int64 (B, W), probabilities (B, W, Q) or None, encodings (B, Bw, Le)).
-    With a vq bottleneck the encoding is the quantised one, and ``net.vq_codes`` (B, Le) / ``net.last_encoding_pre`` hold the
+    With a vq bottleneck the encoding is the quantised one, and ``net.vq_codes`` (B, Le; (B, S, Le) with ``vq_stages`` = S > 1) / ``net.last_encoding_pre`` hold the
     frames' codes and the encoding in front of the quantiser.
     A model with global class conditioning wants ``classes`` (one integer per clip) or ``global_vectors`` ((B, E) floats, e.g. a
     mix of two rows of ``net.global_vectors``), never both: the clips are decoded AS that class - their own for a reconstruction,
@@ -262,7 +262,7 @@ def resynthesize(net, clips, cond=None, teacher_forced=False, want_probs=False, 
         _, enc, ws = eng.forward(x, eng_cond, want_probs=False, encode_only=gvec is not None)
     enc = net.last_encoding = enc.clone()
     if eng.vq:
-        net.vq_codes, net.last_encoding_pre = ws["vq_idx"].to(torch.int64), ws["enc_pre"]
+        net.vq_codes, net.last_encoding_pre = eng.vq_codes_of(ws), ws["enc_pre"]
     codes_in = x.argmax(1).to(torch.int32)                            # (B, T)
     forced = None
     if teacher_forced:
@@ -279,8 +279,8 @@ def _vq_engine(net, what):
 
 
 def encode_codes(net, clips):
-    """The codes of ``clips`` (B, Q, T) one-hot under a vq model: (B, Le) int64, Le = (T - rf + 1) // pool frames per clip.
-    Runs the encoder, the pool and the quantiser (wn_vq_fwd) only."""
+    """The codes of ``clips`` (B, Q, T) one-hot under a vq model: (B, Le) int64, Le = (T - rf + 1) // pool frames per clip;
+    (B, S, Le) with ``vq_stages`` = S > 1, stage s in [:, s].  Runs the encoder, the pool and the quantiser (wn_vq_fwd / wn_rvq_fwd) only."""
     eng = _vq_engine(net, "encode_codes")
     if clips.dim() != 3 or clips.size(1) != net.quantization_channel:
         raise ValueError("encode_codes: clips must be (B, %d, T)" % net.quantization_channel)
@@ -289,7 +289,7 @@ def encode_codes(net, clips):
     x = clips.detach().to(eng.device).float().contiguous()
     with torch.no_grad():
         _, _, ws = eng.forward(x, None, want_probs=False, encode_only=True)
-    return ws["vq_idx"].to(torch.int64)
+    return eng.vq_codes_of(ws)
 
 
 def decode_codes(net, codes, W, start=None, teacher_forced=None, want_probs=False, temperature=None, top_k=None, top_p=None, seed=0,
@@ -303,11 +303,16 @@ def decode_codes(net, codes, W, start=None, teacher_forced=None, want_probs=Fals
     model's own (the probabilities are then those of a forward over the clip whose encoding these codes are), ``start``
     defaults to their first rf - 1.  ``temperature`` / ``top_k`` / ``top_p`` / ``seed`` / ``streams``: as in ``resynthesize``,
     and so are ``classes`` / ``global_vectors`` (the same codes as another class: the conversion of VQ-VAE).
+    With ``vq_stages`` = S > 1: ``codes`` (B, n, Le), 1 <= n <= S, the first n stages' codes; the encoding is the sum of their rows in
+    stage order (wn_rvq_lookup) - all S give the encoding the forward decoded, a prefix the coarser code.
     Returns (codes int64 (B, W), probabilities (B, W, Q) or None)."""
     eng = _vq_engine(net, "decode_codes")
     dev = eng.device
     Q, rf, W = net.quantization_channel, net.receptive_field, int(W)
-    if codes.dim() != 2 or W < 1:
+    if eng.vq_S > 1:
+        if codes.dim() != 3 or not 1 <= codes.size(1) <= eng.vq_S or W < 1:
+            raise ValueError("decode_codes: vq_stages = %d: codes must be (B, n, Le) with 1 <= n <= %d, and W >= 1" % (eng.vq_S, eng.vq_S))
+    elif codes.dim() != 2 or W < 1:
         raise ValueError("decode_codes: codes must be (B, Le) and W >= 1")
     B = codes.size(0)
     gvec = global_term(net, B, classes, global_vectors, "decode_codes")
@@ -330,6 +335,30 @@ def decode_codes(net, codes, W, start=None, teacher_forced=None, want_probs=Fals
                                        free_step=last is None, want_probs=want_probs, temperature=temperature, seed=seed, top_k=top_k,
                                        top_p=top_p, streams=streams, gvec=gvec)
     return out.to(torch.int64), probs
+
+
+def split_code_stream(tokens, stages, K):
+    """The interleaved token stream of tools/vq_codes_dataset.py back into codes: ``tokens`` (B, Le * stages) or (Le * stages,)
+    integers, frame-major (l0s0, l0s1, .., l1s0, ..) with token = s * K + code, -> (B, stages, Le) int64 codes in [0, K), what
+    ``decode_codes`` takes.  Raises on a length that is no multiple of ``stages`` and on a token outside its position's stage range
+    (a prior over the S K alphabet is free to emit one)."""
+    t = torch.as_tensor(tokens)
+    stages, K = int(stages), int(K)
+    if stages < 1 or K < 1:
+        raise ValueError("split_code_stream: stages and K must be >= 1")
+    if t.is_floating_point() or t.dim() not in (1, 2):
+        raise ValueError("split_code_stream: tokens must be integers, (B, Le * stages) or (Le * stages,)")
+    t = t.reshape(1, -1) if t.dim() == 1 else t
+    if t.size(1) % stages:
+        raise ValueError("split_code_stream: %d tokens per clip are not a multiple of %d stages" % (t.size(1), stages))
+    t = t.to(torch.int64).reshape(t.size(0), -1, stages)                              # (B, Le, S)
+    codes = t - torch.arange(stages, dtype=torch.int64, device=t.device) * K
+    wrong = (codes < 0) | (codes >= K)
+    if bool(wrong.any()):
+        b, l, s = (int(v) for v in wrong.nonzero()[0])
+        raise ValueError("split_code_stream: token %d of clip %d at frame %d, stage %d lies outside that stage's range [%d, %d)"
+                         % (int(t[b, l, s]), b, l, s, s * K, (s + 1) * K))
+    return codes.permute(0, 2, 1).contiguous()
 
 
 def _checked_codes(t, B, n, Q, dev, what):

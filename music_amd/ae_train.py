@@ -40,6 +40,11 @@ of one of the most used codes' frames).  The update runs on the device behind ev
 alone); under data parallelism the per-code counts and sums are summed over the ranks first, so every replica makes the same update.
 The ``vq_log.log`` line then ends with ``, restarted N``, the codes restarted since the line before.  A checkpoint carries the running
 state (``vq_ema_state``) and only loads into a model built with the same ``"vq_update"``.
+``"vq_stages"`` (1 .. 8, default 1; needs ``"bottleneck": "vq"``): residual vector quantisation - S codebooks of ``"vq_codes"`` rows,
+stage s quantises what the stages before it left over and the decoder sees the sum of the S rows (S log2 K bits per frame; a prefix
+of the stages is a coarser code).  ``vq_loss`` sums the stages' terms, every stage keeps its own EMA state and restarts, ``"vq_init":
+"data"`` fills the stages in order from the residuals, the ``vq_log.log`` line reports the last stage's mse (q against e) and ends with
+the per-stage figures, ``restarted`` sums the stages; a checkpoint only loads into a model of the same stage count.
 ``"global_classes"`` and ``"global_channels"`` (both 0, the default: off; both >= 1 together, ``"conditioning": "learned"`` required):
 global class conditioning of the decoder - every clip has a class (speaker, instrument) whose learned embedding is projected into
 every conditioning table (music_amd/model1.py).  The classes come from the optional dataset_params.json key ``"labels_path"``, a
@@ -72,6 +77,13 @@ except ImportError:
     from music_amd.train import get_params, load_model
 
 PREFIX = "wavenet_autoencoder"
+
+
+def vq_stage_fields(stats):
+    """The tail of a vq_log.log line with "vq_stages" > 1: every stage's mse, perplexity and codes used, behind the fields of stage 1."""
+    fmt = lambda v: "[" + ", ".join("%.6g" % x for x in v.tolist()) + "]"
+    return ", stage mse %s, stage perplexity %s, stage codes used %s" % (
+        fmt(stats.stage_mse), fmt(stats.stage_perplexity), [int(v) for v in stats.stage_codes_used.tolist()])
 
 
 def get_arguments():
@@ -324,9 +336,10 @@ def train():
                     guard_log.tick(num_trained)
                 stats = (engine.last_vq if fused else net.last_vq) if vq_log_file is not None else None
                 if stats is not None:                         # (the last step's figures, read back where the loss is)
-                    vq_log_file.writelines('Trained over %d pieces, vq mse %s, perplexity %s, codes used %d%s\n'
+                    vq_log_file.writelines('Trained over %d pieces, vq mse %s, perplexity %s, codes used %d%s%s\n'
                                            % (num_trained, stats.mse.item(), stats.perplexity.item(), int(stats.codes_used.item()),
-                                              ", restarted %d" % net._engine_for(device).vq_restarted() if is_vq_ema else ""))
+                                              ", restarted %d" % net._engine_for(device).vq_restarted() if is_vq_ema else "",
+                                              vq_stage_fields(stats) if getattr(net, "vq_stages", 1) > 1 else ""))
                     vq_log_file.flush()
                 total_loss.zero_()
             if validation is not None:

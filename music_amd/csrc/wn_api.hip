@@ -58,6 +58,7 @@ static_assert(WN_F16X3 == WN_MODE_F16X3 && WN_F16X1 == WN_MODE_F16X1 && WN_BF16X
 static_assert(WN_CE_NUM_PARTIALS == WN_CE_PARTIALS, "partials out of sync");
 static_assert(WN_VQ_NUM_PARTIALS == WN_VQ_PARTIALS && WN_VQ_MAX_CODES == WN_DEC_MAX_Q, "vq constants out of sync");
 static_assert(WN_VQ_MAX_CODES == WN_VQ_MAX_K && WN_VQ_EMA_WORK_BYTES == WN_VQ_EMA_WORK, "vq ema constants out of sync");
+static_assert(WN_RVQ_MAX_STAGES == WN_RVQ_MAX_S, "rvq constants out of sync");
 
 // ---- cached-queue decode: the ONE call path behind the six exported decode entries -------------------------------------------
 // Every entry forwards its arguments (and the defaults of those it does not take) to decode_checked with the checks it applies:
@@ -562,7 +563,7 @@ int wn_vq_lookup(const int32_t* idx, const float* flat, int64_t cb_off, float* q
     if (int rc = vq_checked("wn_vq_lookup", cb_off, K, bw, le, batch)) return rc;
     if (batch == 0) return 0;
     WN_REQUIRE("wn_vq_lookup", idx, flat, q_out);
-    return wn_launch_vq_lookup(idx, flat, (long)cb_off, q_out, bad, K, bw, le, batch, (hipStream_t)stream);
+    return wn_launch_vq_lookup(idx, flat, (long)cb_off, q_out, bad, 1, K, bw, le, batch, (hipStream_t)stream);
 }
 int wn_vq_bwd_stats(const float* enc, const int32_t* idx, const float* d_q, const float* flat, int64_t cb_off, float beta, float g_scale,
                     float* d_enc, float* flat_grad, float* stat, int K, int bw, int le, int batch, wn_stream_t stream) {
@@ -583,8 +584,72 @@ int wn_vq_ema_update(float* flat, int64_t cb_off, const float* stat, float* stat
     if (!(restart >= 0.f)) return wn_set_error_msg(-4, "wn_vq_ema_update: argument 'restart' must be >= 0");
     WN_REQUIRE("wn_vq_ema_update", flat, stat, state, work);
     if ((uintptr_t)guard_state % 8 != 0) return wn_set_error_msg(-4, "wn_vq_ema_update: argument 'guard_state' needs 8-byte alignment");
-    return wn_launch_vq_ema_update(flat, (long)cb_off, stat, state, work, info, K, bw, decay, eps, restart, guard_state,
+    return wn_launch_vq_ema_update(flat, (long)cb_off, stat, state, work, info, 1, K, bw, decay, eps, restart, guard_state,
                                    (hipStream_t)stream);
+}
+// ---- the residual chain over S codebooks (wn_vq.hip): the refusals of the entries above, and the stage count
+static int rvq_checked(const char* fn, int S, int64_t cb_off, int K, int bw, int le, int batch) {
+    if (S < 1 || S > WN_RVQ_MAX_STAGES) {
+        char msg[200];
+        snprintf(msg, sizeof(msg), "%s: argument 'S' must lie in [1, 8]", fn);
+        return wn_set_error_msg(-4, msg);
+    }
+    return vq_checked(fn, cb_off, K, bw, le, batch);
+}
+static WnVq rvq_args(const float* enc, const float* flat, int64_t cb_off, const int32_t* idx, const float* res, int S, int K, int bw, int le,
+                     int batch) {
+    WnVq p;
+    memset(&p, 0, sizeof(p));
+    p.enc = enc; p.flat = flat; p.cb_off = (long)cb_off; p.idx = const_cast<int32_t*>(idx); p.res = const_cast<float*>(res);
+    p.S = S; p.K = K; p.bw = bw; p.le = le; p.batch = batch;
+    return p;
+}
+int wn_rvq_fwd(const float* enc, const float* flat, int64_t cb_off, float* q_out, int32_t* idx, int32_t* counts, float* res,
+               float* loss_part, int S, int K, int bw, int le, int batch, wn_stream_t stream) {
+    if (int rc = rvq_checked("wn_rvq_fwd", S, cb_off, K, bw, le, batch)) return rc;
+    if (batch == 0) return 0;
+    WN_REQUIRE("wn_rvq_fwd", enc, flat, q_out, idx, res, loss_part);
+    WnVq p = rvq_args(enc, flat, cb_off, idx, res, S, K, bw, le, batch);
+    p.q_out = q_out; p.counts = counts; p.loss_part = loss_part;
+    return wn_launch_rvq_fwd(p, (hipStream_t)stream);
+}
+int wn_rvq_bwd(const float* enc, const int32_t* idx, const float* res, const float* d_q, const float* flat, int64_t cb_off, float beta,
+               float g_scale, float* d_enc, float* flat_grad, int S, int K, int bw, int le, int batch, wn_stream_t stream) {
+    if (int rc = rvq_checked("wn_rvq_bwd", S, cb_off, K, bw, le, batch)) return rc;
+    if (batch == 0) return 0;
+    WN_REQUIRE("wn_rvq_bwd", enc, idx, res, d_q, flat, d_enc, flat_grad);
+    WnVq p = rvq_args(enc, flat, cb_off, idx, res, S, K, bw, le, batch);
+    p.d_q = d_q; p.d_enc = d_enc; p.flat_grad = flat_grad;
+    return wn_launch_rvq_bwd(p, beta, g_scale, nullptr, (hipStream_t)stream);
+}
+int wn_rvq_bwd_stats(const float* enc, const int32_t* idx, const float* res, const float* d_q, const float* flat, int64_t cb_off, float beta,
+                     float g_scale, float* d_enc, float* flat_grad, float* stat, int S, int K, int bw, int le, int batch,
+                     wn_stream_t stream) {
+    if (int rc = rvq_checked("wn_rvq_bwd_stats", S, cb_off, K, bw, le, batch)) return rc;
+    if (batch == 0) return 0;
+    WN_REQUIRE("wn_rvq_bwd_stats", enc, idx, res, d_q, flat, d_enc, flat_grad, stat);
+    WnVq p = rvq_args(enc, flat, cb_off, idx, res, S, K, bw, le, batch);
+    p.d_q = d_q; p.d_enc = d_enc; p.flat_grad = flat_grad;
+    return wn_launch_rvq_bwd(p, beta, g_scale, stat, (hipStream_t)stream);
+}
+int wn_rvq_ema_update(float* flat, int64_t cb_off, const float* stat, float* state, void* work, int32_t* info, int S, int K, int bw,
+                      float decay, float eps, float restart, const wn_guard_state* guard_state, wn_stream_t stream) {
+    if (int rc = rvq_checked("wn_rvq_ema_update", S, cb_off, K, bw, 1, 1)) return rc;
+    if (!(decay > 0.f && decay < 1.f)) return wn_set_error_msg(-4, "wn_rvq_ema_update: argument 'decay' must lie in (0, 1)");
+    if (!(eps >= 0.f)) return wn_set_error_msg(-4, "wn_rvq_ema_update: argument 'eps' must be >= 0");
+    if (!(restart >= 0.f)) return wn_set_error_msg(-4, "wn_rvq_ema_update: argument 'restart' must be >= 0");
+    WN_REQUIRE("wn_rvq_ema_update", flat, stat, state, work);
+    if ((uintptr_t)guard_state % 8 != 0) return wn_set_error_msg(-4, "wn_rvq_ema_update: argument 'guard_state' needs 8-byte alignment");
+    return wn_launch_vq_ema_update(flat, (long)cb_off, stat, state, work, info, S, K, bw, decay, eps, restart, guard_state,
+                                   (hipStream_t)stream);
+}
+int wn_rvq_lookup(const int32_t* idx, const float* flat, int64_t cb_off, float* q_out, int32_t* bad, int S, int stages, int K, int bw, int le,
+                  int batch, wn_stream_t stream) {
+    if (int rc = rvq_checked("wn_rvq_lookup", S, cb_off, K, bw, le, batch)) return rc;
+    if (stages < 1 || stages > S) return wn_set_error_msg(-4, "wn_rvq_lookup: argument 'stages' must lie in [1, S]");
+    if (batch == 0) return 0;
+    WN_REQUIRE("wn_rvq_lookup", idx, flat, q_out);
+    return wn_launch_vq_lookup(idx, flat, (long)cb_off, q_out, bad, stages, K, bw, le, batch, (hipStream_t)stream);
 }
 int wn_coll_available(void) { return wn_coll_loaded(); }
 int wn_comm_unique_id(char* id128) { return wn_coll_unique_id(id128); }

@@ -274,16 +274,24 @@ struct WnVq {
     float* q_out; int32_t* idx; int32_t* counts; float* loss_part;       // forward outputs (counts may be NULL); idx: the backward's input
     const float* d_q; float* d_enc; float* flat_grad;                    // backward
     int K, bw, le, batch;
+    // the residual chain (wn_rvq_*) alone: S stages of K rows each; res [S][B][Bw][Le], res[s] = what stage s left over (the forward
+    // writes it, the backward reads it); idx is [S][B][Le], counts [S][K] and loss_part [S][WN_VQ_PARTIALS] there
+    int S; float* res;
 };
+#define WN_RVQ_MAX_S 8
 int wn_launch_vq_fwd(const WnVq& p, hipStream_t st);
 int wn_launch_vq_bwd(const WnVq& p, float beta, float g_scale, hipStream_t st);
-int wn_launch_vq_lookup(const int32_t* idx, const float* flat, long cb_off, float* q_out, int32_t* bad, int K, int bw, int le, int batch,
-                        hipStream_t st);
+// q = the sum of the first `stages` stages' rows (1: the plain lookup); idx [stages][batch][le]
+int wn_launch_vq_lookup(const int32_t* idx, const float* flat, long cb_off, float* q_out, int32_t* bad, int stages, int K, int bw, int le,
+                        int batch, hipStream_t st);
+int wn_launch_rvq_fwd(const WnVq& p, hipStream_t st);
+int wn_launch_rvq_bwd(const WnVq& p, float beta, float g_scale, float* stat, hipStream_t st);       // stat != NULL: the stats form
 // EMA mode: stat = [n | s] and state = [N | m], K counts then K rows of bw; work: WN_VQ_EMA_WORK bytes of device scratch
 #define WN_VQ_MAX_K 1024
 #define WN_VQ_EMA_WORK (16 + 4 * WN_VQ_MAX_K)
 int wn_launch_vq_bwd_stats(const WnVq& p, float beta, float g_scale, float* stat, hipStream_t st);
-int wn_launch_vq_ema_update(float* flat, long cb_off, const float* stat, float* state, void* work, int32_t* info, int K, int bw,
+// S stages (1: wn_vq_ema_update): S blocks of stat, state, work and info[2], S x K codebook rows
+int wn_launch_vq_ema_update(float* flat, long cb_off, const float* stat, float* state, void* work, int32_t* info, int S, int K, int bw,
                             float decay, float eps, float restart, const wn_guard_state* guard, hipStream_t st);
 // per-timestep softmax + negative log-likelihood over the channel axis of [B][Q][pitch] logits (wn_nll.hip); target NULL: softmax only
 int wn_launch_step_nll(const float* x, long x_bs, int x_pitch, const int64_t* target, float* dx, long dx_bs, int dx_pitch, float* probs,

@@ -171,15 +171,32 @@ class SlabPlan:
 class VqStats:
     """What one forward's wn_vq_fwd left on the device, read on demand (nothing here runs in the step): `mse` and `perplexity` are
     0-d device tensors, `vq_loss` = (1 + beta) mse - beta mse with EMA codebook updates, where the codebook term is gone (`coef`) -,
-    `codes_used` the number of codes at least one frame chose."""
+    `codes_used` the number of codes at least one frame chose.
+
+    With a residual chain of S > 1 stages (wn_rvq_fwd) `part` is (S, partials) and `counts` (S, K): `stage_mse` (S,) holds every
+    stage's sum (r_s - q_s)^2 / (C Bw), `mse` is the LAST stage's - the error of q against e -, `vq_loss` = coef x their sum, and
+    `stage_perplexity` / `stage_codes_used` (S,) stand beside `perplexity` / `codes_used`, which describe stage 0."""
 
     def __init__(self, part, counts, frames, beta, coef=None):
         self.part, self.counts, self.frames, self.beta = part, counts, frames, beta
         self.coef = 1.0 + beta if coef is None else coef
 
     @property
+    def stage_mse(self):
+        return self.part.reshape(-1, self.part.shape[-1]).sum(dim=1)
+
+    @property
+    def stage_perplexity(self):
+        p = self.counts.reshape(-1, self.counts.shape[-1]).to(torch.float64) / self.frames
+        return torch.exp(-(p * torch.log(p.clamp_min(1e-300))).sum(dim=1)).float()
+
+    @property
+    def stage_codes_used(self):
+        return (self.counts.reshape(-1, self.counts.shape[-1]) > 0).sum(dim=1)
+
+    @property
     def mse(self):
-        return self.part.sum()
+        return self.part.sum() if self.part.dim() == 1 else self.part[-1].sum()
 
     @property
     def vq_loss(self):
@@ -187,12 +204,12 @@ class VqStats:
 
     @property
     def perplexity(self):
-        p = self.counts.to(torch.float64) / self.frames
+        p = (self.counts if self.counts.dim() == 1 else self.counts[0]).to(torch.float64) / self.frames
         return torch.exp(-(p * torch.log(p.clamp_min(1e-300))).sum()).float()
 
     @property
     def codes_used(self):
-        return (self.counts > 0).sum()
+        return ((self.counts if self.counts.dim() == 1 else self.counts[0]) > 0).sum()
 
 
 class EngineBase:
@@ -252,6 +269,7 @@ class EngineBase:
     vq = False                   # net.bottleneck == "vq": the codebook (K, Bw) is the LAST parameter of the flat buffer, behind the projections
     n_vq = 0                     # its floats: wn_vq_bwd writes that tail of flat_grad
     last_vq = None               # VqStats of the last forward (vq only)
+    vq_S = 1                     # net.vq_stages: S > 1 = a residual chain, the codebook is (S K, Bw) and the wn_rvq_* entries run it
     vq_ema = False               # net.vq_update == "ema": wn_vq_bwd_stats in place of wn_vq_bwd, wn_vq_ema_update behind the optimizer
     gcond = False                # net.global_classes > 0: the global block [G_0 .. G_N-1 | G_f | embedding] ends the flat buffer, behind the codebook
     n_gcond = 0                  # its floats: wn_gcond_proj_bwd writes that tail of flat_grad (and the projections' in front of the codebook)
@@ -290,17 +308,19 @@ class EngineBase:
         if self.vq:
             if not self.learned:
                 raise ValueError('music_amd: bottleneck="vq" requires conditioning="learned"')
-            self.vq_K, self.vq_beta = int(net.vq_codebook.num_embeddings), float(net.vq_beta)
+            S = self.vq_S = int(getattr(net, "vq_stages", 1))
+            self.vq_K, self.vq_beta = int(net.vq_codebook.num_embeddings) // S, float(net.vq_beta)
             self.vq_off = self.spec.off["vq_codebook.weight"]
-            self.n_vq = self.vq_K * self.Bw
-            assert self.spec.shape["vq_codebook.weight"] == (self.vq_K, self.Bw) and self.vq_off + self.n_vq == self.spec.total - self.n_gcond
+            self.n_vq = S * self.vq_K * self.Bw
+            assert self.spec.shape["vq_codebook.weight"] == (S * self.vq_K, self.Bw) and self.vq_off + self.n_vq == self.spec.total - self.n_gcond
             self.vq_ema = getattr(net, "vq_update", "gradient") == "ema"
             if self.vq_ema:
                 # [n | s] of the last backward, the update's scratch and its restart counters; the running state is the MODULE's buffer
                 self.vq_decay, self.vq_eps, self.vq_restart = float(net.vq_decay), float(net.vq_eps), float(net.vq_restart)
-                self.vq_stat = torch.zeros(self.vq_K * (self.Bw + 1), dtype=torch.float32, device=self.device)
-                self.vq_ema_work = torch.zeros(_lib.VQ_EMA_WORK_BYTES // 4, dtype=torch.int32, device=self.device)
-                self.vq_ema_info = torch.zeros(2, dtype=torch.int32, device=self.device)
+                # (one block of each per stage, the stats of all stages in ONE tensor: a data-parallel run reduces it in one call)
+                self.vq_stat = torch.zeros(S * self.vq_K * (self.Bw + 1), dtype=torch.float32, device=self.device)
+                self.vq_ema_work = torch.zeros(S * _lib.VQ_EMA_WORK_BYTES // 4, dtype=torch.int32, device=self.device)
+                self.vq_ema_info = torch.zeros(2 * S, dtype=torch.int32, device=self.device)
                 self._vq_net = weakref.ref(net)
         if not self.learned:
             return
@@ -321,6 +341,19 @@ class EngineBase:
         B, _, Le = enc.shape
         dev = self.device
         q = torch.empty_like(enc)
+        if self.vq_S > 1:
+            # the residual chain, still one launch: idx (S, B, Le), counts (S, K), the loss partials per stage, and res[s] = what
+            # stage s left over, which the backward reads
+            S = self.vq_S
+            idx = torch.empty(S, B, Le, dtype=torch.int32, device=dev)
+            counts = torch.empty(S, self.vq_K, dtype=torch.int32, device=dev)
+            part = torch.empty(S, _lib.VQ_NUM_PARTIALS, dtype=torch.float32, device=dev)
+            res = torch.empty((S,) + tuple(enc.shape), dtype=torch.float32, device=dev)
+            call("wn_rvq_fwd", ptr(enc), ptr(self.flat), self.vq_off, ptr(q), ptr(idx), ptr(counts), ptr(res), ptr(part), S, self.vq_K,
+                 self.Bw, Le, B, st)
+            ws.update(enc_pre=enc, vq_idx=idx, vq_counts=counts, vq_part=part, vq_res=res, vq_g=1.0)
+            self.last_vq = VqStats(part, counts, B * Le, self.vq_beta, self.vq_loss_coef)
+            return q
         idx = torch.empty(B, Le, dtype=torch.int32, device=dev)
         counts = torch.empty(self.vq_K, dtype=torch.int32, device=dev)
         part = torch.empty(_lib.VQ_NUM_PARTIALS, dtype=torch.float32, device=dev)
@@ -333,6 +366,12 @@ class EngineBase:
         """d_q (what wn_cond_proj_bwd wrote as d enc) -> d e in place, and the codebook's gradient into the tail of flat_grad (wn_vq_bwd,
         one launch); ws["vq_g"]: the upstream scalar on vq_loss (1 in the fused step, autograd's in the module's backward)."""
         B, _, Le = d_q.shape
+        if self.vq_S > 1:
+            head = (ptr(ws["enc_pre"]), ptr(ws["vq_idx"]), ptr(ws["vq_res"]), ptr(d_q), ptr(self.flat), self.vq_off, self.vq_beta,
+                    float(ws.get("vq_g", 1.0)), ptr(d_q), ptr(self.flat_grad))
+            if self.vq_ema:
+                return call("wn_rvq_bwd_stats", *head, ptr(self.vq_stat), self.vq_S, self.vq_K, self.Bw, Le, B, st)
+            return call("wn_rvq_bwd", *head, self.vq_S, self.vq_K, self.Bw, Le, B, st)
         if self.vq_ema:                     # the same d e; the frames' counts and sums per code into vq_stat, zeros as the codebook's gradient
             return call("wn_vq_bwd_stats", ptr(ws["enc_pre"]), ptr(ws["vq_idx"]), ptr(d_q), ptr(self.flat), self.vq_off, self.vq_beta,
                         float(ws.get("vq_g", 1.0)), ptr(d_q), ptr(self.flat_grad), ptr(self.vq_stat), self.vq_K, self.Bw, Le, B, st)
@@ -343,6 +382,11 @@ class EngineBase:
     def vq_loss_coef(self):
         """vq_loss / mse: codebook term + beta x commitment term; the commitment term alone where the codebook follows its frames' mean."""
         return self.vq_beta if self.vq_ema else 1.0 + self.vq_beta
+
+    def vq_codes_of(self, ws):
+        """The codes of a forward's workspace as the module hands them out: (B, Le) int64, (B, S, Le) with S > 1 stages."""
+        idx = ws["vq_idx"].to(torch.int64)
+        return idx if self.vq_S == 1 else idx.permute(1, 0, 2)
 
     def vq_ema_state(self):
         """The module's running state [N | m] (its `vq_ema_state` buffer, which checkpoints carry), on this engine's device."""
@@ -356,14 +400,16 @@ class EngineBase:
         """wn_vq_ema_update (two launches) on the stats of the last backward: the module's running state and the codebook's rows of
         the flat buffer, in place.  Behind the optimizer's update - which leaves those rows alone, their gradient being 0 - and in
         front of the EMA shadow's.  `guard`: the GradGuard that decided the step; a skipped step changes nothing."""
-        call("wn_vq_ema_update", ptr(self.flat), self.vq_off, ptr(self.vq_stat), ptr(self.vq_ema_state()), ptr(self.vq_ema_work),
-             ptr(self.vq_ema_info), self.vq_K, self.Bw, self.vq_decay, self.vq_eps, self.vq_restart,
-             None if guard is None else guard.state_ptr(), _lib.stream())
+        tail = (self.vq_K, self.Bw, self.vq_decay, self.vq_eps, self.vq_restart, None if guard is None else guard.state_ptr(), _lib.stream())
+        head = (ptr(self.flat), self.vq_off, ptr(self.vq_stat), ptr(self.vq_ema_state()), ptr(self.vq_ema_work), ptr(self.vq_ema_info))
+        if self.vq_S > 1:                   # every stage on its own block of stat, state, work and info; still two launches
+            return call("wn_rvq_ema_update", *head, self.vq_S, *tail)
+        call("wn_vq_ema_update", *head, *tail)
 
     def vq_restarted(self):
         """Codes restarted since the last call (reads the device's counter back and zeroes it)."""
-        n = int(self.vq_ema_info[0].item())
-        self.vq_ema_info[0] = 0
+        n = int(self.vq_ema_info[0::2].sum().item())                   # (info is [S][2]: the stages' counters)
+        self.vq_ema_info[0::2] = 0
         return n
 
     def vq_backward_scaled(self, ws, dloss, dvq):
@@ -382,7 +428,23 @@ class EngineBase:
         d_o.copy_(keep)
 
     def vq_lookup(self, codes):
-        """codes (B, Le) integer -> q (B, Bw, Le) out of the codebook (wn_vq_lookup); a code outside [0, K) raises."""
+        """codes (B, Le) integer -> q (B, Bw, Le) out of the codebook (wn_vq_lookup); a code outside [0, K) raises.  With S > 1 stages:
+        codes (B, n, Le), 1 <= n <= S, the first n stages' codes -> the sum of their rows in stage order (wn_rvq_lookup)."""
+        if self.vq_S > 1:
+            if codes.dim() != 3 or not 1 <= codes.shape[1] <= self.vq_S:
+                raise ValueError("music_amd: vq_stages = %d: codes must be (B, n, Le) with 1 <= n <= %d, not %s"
+                                 % (self.vq_S, self.vq_S, tuple(codes.shape)))
+            codes = codes.to(device=self.device, dtype=torch.int32).permute(1, 0, 2).contiguous()
+            n, B, Le = codes.shape
+            q = torch.empty(B, self.Bw, Le, dtype=torch.float32, device=self.device)
+            bad = torch.zeros(1, dtype=torch.int32, device=self.device)
+            call("wn_rvq_lookup", ptr(codes), ptr(self.flat), self.vq_off, ptr(q), ptr(bad), self.vq_S, n, self.vq_K, self.Bw, Le, B,
+                 _lib.stream())
+            if int(bad.item()):
+                raise ValueError("music_amd: a code lies outside [0, %d)" % self.vq_K)
+            return q
+        if codes.dim() != 2:
+            raise ValueError("music_amd: codes must be (B, Le), not %s" % (tuple(codes.shape),))
         codes = codes.to(device=self.device, dtype=torch.int32).contiguous()
         B, Le = codes.shape
         q = torch.empty(B, self.Bw, Le, dtype=torch.float32, device=self.device)

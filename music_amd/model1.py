@@ -627,7 +627,7 @@ class _AutoencoderFunction(torch.autograd.Function):
         if eng.vq:
             # the quantised bottleneck: q went to the decoder (net.last_encoding); vq_loss = (1 + beta) mse is a SECOND output of this
             # node - left out of the user's loss, its upstream gradient is None and neither the codebook nor the commitment term gets any
-            net.last_encoding_pre, net.vq_codes, net.last_vq = ws["enc_pre"], ws["vq_idx"].to(torch.int64), eng.last_vq
+            net.last_encoding_pre, net.vq_codes, net.last_vq = ws["enc_pre"], eng.vq_codes_of(ws), eng.last_vq
             ctx.set_materialize_grads(False)
             return probs.detach(), eng.last_vq.vq_loss
         return probs.detach()            # (an alias: the workspace's own reference must not carry the autograd node)
@@ -660,8 +660,13 @@ class wavenet_autoencoder(nn.Module):
     def __init__(self, filter_width, quantization_channel, dilations, en_residual_channel, en_dilation_channel,
                  en_bottleneck_width, en_pool_kernel_size, de_residual_channel, de_dilation_channel,
                  de_skip_channel, use_bias, conditioning="random", bottleneck="continuous", vq_codes=512, vq_beta=0.25,
-                 vq_update="gradient", vq_decay=0.99, vq_eps=1e-5, vq_restart=0.0, global_classes=0, global_channels=0):
+                 vq_update="gradient", vq_decay=0.99, vq_eps=1e-5, vq_restart=0.0, global_classes=0, global_channels=0, vq_stages=1):
         super(wavenet_autoencoder, self).__init__()
+        if isinstance(vq_stages, bool) or not isinstance(vq_stages, int) or not 1 <= vq_stages <= _lib.RVQ_MAX_STAGES:
+            raise ValueError("music_amd.wavenet_autoencoder: vq_stages must be an integer in [1, %d], not %r"
+                             % (_lib.RVQ_MAX_STAGES, vq_stages))
+        if vq_stages > 1 and bottleneck != "vq":
+            raise ValueError('music_amd.wavenet_autoencoder: vq_stages > 1 requires bottleneck="vq"')
         for key, val in (("global_classes", global_classes), ("global_channels", global_channels)):
             if isinstance(val, bool) or not isinstance(val, int) or val < 0:
                 raise ValueError("music_amd.wavenet_autoencoder: %s must be an integer >= 0, not %r" % (key, val))
@@ -705,6 +710,7 @@ class wavenet_autoencoder(nn.Module):
                 raise ValueError("music_amd.wavenet_autoencoder: vq_restart must be >= 0, not %r" % (vq_restart,))
         self.conditioning = conditioning
         self.bottleneck, self.vq_num_codes, self.vq_beta = bottleneck, int(vq_codes), float(vq_beta)
+        self.vq_stages = vq_stages       # residual quantisation: stage s quantises what the stages before it left over, with rows [sK, (s+1)K)
         self.vq_update, self.vq_decay, self.vq_eps, self.vq_restart = vq_update, float(vq_decay), float(vq_eps), float(vq_restart)
         self.global_classes, self.global_channels = global_classes, global_channels
         self.filter_width = filter_width
@@ -753,19 +759,21 @@ class wavenet_autoencoder(nn.Module):
             # the end of the flat buffer; always with a bias, rows in the reference's order (gate first), like the drawn convs
             self.de_cond_layer_stack = nn.ModuleList(nn.Conv1d(en_bottleneck_width, 2 * de_dilation_channel, 1) for _ in dilations)
             self.connection_cond = nn.Conv1d(en_bottleneck_width, de_skip_channel, 1)
-        # after a forward of a vq model: vq_loss (0-d, attached to autograd: add it to the loss), vq_codes (B, Le) int64,
-        # last_encoding = q, last_encoding_pre = e, last_vq = the engine's VqStats
+        # after a forward of a vq model: vq_loss (0-d, attached to autograd: add it to the loss), vq_codes (B, Le) int64 - (B, S, Le) with
+        # vq_stages = S > 1 -, last_encoding = q, last_encoding_pre = e, last_vq = the engine's VqStats
         self.vq_loss = self.vq_codes = self.last_encoding_pre = self.last_vq = None
         if bottleneck == "vq":
             # the codebook (K, Bw), registered BEHIND the learned projections: a seed gives every earlier parameter the continuous
             # model's values, and it is the last block of the flat buffer; uniform(-1/K, 1/K) (van den Oord et al. 2017)
-            self.vq_codebook = nn.Embedding(self.vq_num_codes, en_bottleneck_width)
+            # (S K, Bw) with vq_stages = S: stage s owns rows [sK, (s+1)K), every row uniform(-1/K, 1/K)
+            self.vq_codebook = nn.Embedding(vq_stages * self.vq_num_codes, en_bottleneck_width)
             with torch.no_grad():
                 self.vq_codebook.weight.uniform_(-1.0 / self.vq_num_codes, 1.0 / self.vq_num_codes)
             if vq_update == "ema":
                 # the running usage N (K) and running sums m (K, Bw) of wn_vq_ema_update, [N | m] in one vector; m / N is the
-                # codebook.  A buffer: it travels with state_dict() (as the LAST key) and the module's moves, no optimizer sees it
-                self.register_buffer("vq_ema_state", torch.empty(self.vq_num_codes * (en_bottleneck_width + 1)))
+                # codebook.  A buffer: it travels with state_dict() (as the LAST key) and the module's moves, no optimizer sees it.
+                # One [N | m] block per stage
+                self.register_buffer("vq_ema_state", torch.empty(vq_stages * self.vq_num_codes * (en_bottleneck_width + 1)))
                 self.reset_vq_ema_state()
         if global_classes > 0:
             # global class conditioning (VQ-VAE's speaker id, NSynth's instrument): en_i[b] = W_i enc[b] + b_i + G_i emb[cls[b]].  The
@@ -779,6 +787,7 @@ class wavenet_autoencoder(nn.Module):
         super(wavenet_autoencoder, self).__setstate__(state)
         self.__dict__.setdefault("conditioning", "random")       # (a module pickled before the attribute existed)
         self.__dict__.setdefault("bottleneck", "continuous")
+        self.__dict__.setdefault("vq_stages", 1)
         for k, v in (("vq_update", "gradient"), ("vq_decay", 0.99), ("vq_eps", 1e-5), ("vq_restart", 0.0)):
             self.__dict__.setdefault(k, v)
         for k in ("vq_loss", "vq_codes", "last_encoding_pre", "last_vq"):
@@ -788,7 +797,10 @@ class wavenet_autoencoder(nn.Module):
 
     def init_codebook(self, encodings, seed=0):
         """Data-dependent initialisation: K frames of `encodings` (B, Bw, Le) - pre-quantisation encodings, net.last_encoding_pre -
-        become the codebook, drawn without replacement by a generator seeded with `seed`; fewer than K frames are cycled through."""
+        become the codebook, drawn without replacement by a generator seeded with `seed`; fewer than K frames are cycled through.
+        With vq_stages > 1 the stages are filled in order: stage s draws its rows (generator `seed` + s) from the residuals that the
+        stages before it leave on these frames (nearest row) - of the frames no earlier stage took: a frame that BECAME a row leaves
+        nothing over, and all such frames share their later residuals, rows that would tie.  Give at least S K frames."""
         if getattr(self, "bottleneck", "continuous") != "vq":
             raise ValueError('music_amd.wavenet_autoencoder: init_codebook needs bottleneck="vq"')
         w = self.vq_codebook.weight
@@ -796,11 +808,19 @@ class wavenet_autoencoder(nn.Module):
         if frames.size(1) != w.size(1) or frames.size(0) < 1:
             raise ValueError("music_amd.wavenet_autoencoder: init_codebook wants (B, %d, Le) encodings, got %s"
                              % (w.size(1), tuple(encodings.shape)))
-        gen = torch.Generator().manual_seed(int(seed))
-        order = torch.randperm(frames.size(0), generator=gen)
-        pick = order[torch.arange(w.size(0)) % frames.size(0)]
+        K = self.vq_num_codes
+        fresh = torch.ones(frames.size(0), dtype=torch.bool)               # frames no stage has taken as a row yet
         with torch.no_grad():
-            w.copy_(frames[pick.to(frames.device)].to(w.device))          # (in place: the parameter may be a view of the flat buffer)
+            for s in range(getattr(self, "vq_stages", 1)):
+                gen = torch.Generator().manual_seed(int(seed) + s)
+                pool = fresh.nonzero()[:, 0] if bool(fresh.any()) else torch.arange(frames.size(0))
+                order = torch.randperm(pool.numel(), generator=gen)
+                pick = pool[order[torch.arange(K) % pool.numel()]]
+                fresh[pick] = False
+                rows = frames[pick.to(frames.device)]
+                w[s * K:(s + 1) * K].copy_(rows.to(w.device))            # (in place: the parameter may be a view of the flat buffer)
+                if s + 1 < getattr(self, "vq_stages", 1):
+                    frames = frames - rows[torch.cdist(frames, rows).argmin(dim=1)]
         self.reset_vq_ema_state()
 
     def reset_vq_ema_state(self):
@@ -808,10 +828,11 @@ class wavenet_autoencoder(nn.Module):
         codebook was set by hand, init_codebook does it itself).  In place; nothing to do in gradient mode."""
         if getattr(self, "vq_update", "gradient") != "ema":
             return
-        K = self.vq_num_codes
+        K, S = self.vq_num_codes, getattr(self, "vq_stages", 1)
         with torch.no_grad():
-            self.vq_ema_state[:K].fill_(1.0)
-            self.vq_ema_state[K:].copy_(self.vq_codebook.weight.detach().reshape(-1))
+            state = self.vq_ema_state.view(S, -1)                      # per stage: [N | m]
+            state[:, :K].fill_(1.0)
+            state[:, K:].copy_(self.vq_codebook.weight.detach().reshape(S, -1))
 
     def state_dict(self, *args, **kwargs):
         sd = super(wavenet_autoencoder, self).state_dict(*args, **kwargs)
@@ -879,6 +900,14 @@ class wavenet_autoencoder(nn.Module):
             raise RuntimeError('music_amd.wavenet_autoencoder: the checkpoint was saved with vq_update="%s" but this model was built '
                                'with vq_update="%s" (the "vq_update" key of model_params.json); nothing was loaded'
                                % ("ema" if has_ema else "gradient", mine_ema))
+        if mine_vq == "vq":
+            cb = state_dict.get("vq_codebook.weight", state_dict.get("module.vq_codebook.weight"))
+            rows = cb.shape[0] if cb is not None and cb.dim() == 2 else 0
+            mine_s = getattr(self, "vq_stages", 1)
+            if rows != mine_s * self.vq_num_codes and rows % self.vq_num_codes == 0:
+                raise RuntimeError("music_amd.wavenet_autoencoder: the checkpoint was saved with vq_stages=%d but this model was built "
+                                   'with vq_stages=%d (the "vq_stages" key of model_params.json); nothing was loaded'
+                                   % (rows // self.vq_num_codes, mine_s))
         emb = state_dict.get("global_embedding.weight", state_dict.get("module.global_embedding.weight"))
         saved = tuple(emb.shape) if emb is not None and emb.dim() == 2 else (0, 0)
         mine_g = (getattr(self, "global_classes", 0), getattr(self, "global_channels", 0))

@@ -74,7 +74,7 @@ class _NLLFunction(torch.autograd.Function):
         ctx.hold = WorkspaceHold(ws) if need else None          # see music_amd/model.py
         if getattr(eng, "vq", False):
             # a vq autoencoder: vq_loss is a second output of this node, which nll_loss leaves in net.vq_loss for the caller to add
-            net.last_encoding_pre, net.vq_codes, net.last_vq = ws["enc_pre"], ws["vq_idx"].to(torch.int64), eng.last_vq
+            net.last_encoding_pre, net.vq_codes, net.last_vq = ws["enc_pre"], eng.vq_codes_of(ws), eng.last_vq
             ctx.set_materialize_grads(False)
             return ws["loss_part"].sum(), eng.last_vq.vq_loss
         return ws["loss_part"].sum()

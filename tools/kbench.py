@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of single kernels of the hot path at BASELINE config-2 shapes (GPU only).
 
-    python tools/kbench.py [fwd|bwd|epi|dx|skip|decode|ae|guard|ema|nll|cond|vq|vq_ema|gcond|all] [--reps N] [--precision f16x3,bf16x3]
+    python tools/kbench.py [fwd|bwd|epi|dx|skip|decode|ae|guard|ema|nll|cond|vq|vq_ema|gcond|rvq|all] [--reps N] [--precision f16x3,bf16x3]
 
 Prints per-phase / per-layer kernel times measured with HIP events on the launch stream.
 """
@@ -231,7 +231,7 @@ def _write_profile(name, res):
         f.write("\n")
 
 
-def bench_unset(parent, alternations=6):
+def bench_unset(parent, alternations=6, profile="gcond_bench_unset.json", keys="global_classes / global_channels"):
     """bench.py of this tree (the new keys unset: the feature launches nothing there) against a built checkout of the parent commit at
     `parent`, alternated `alternations` times, each run a process of its own.  Called before this process touches the device."""
     import subprocess
@@ -242,14 +242,145 @@ def bench_unset(parent, alternations=6):
                                  stdout=subprocess.PIPE, timeout=300).stdout.decode()
             line = json.loads([ln for ln in out.splitlines() if ln.startswith("{")][-1])
             runs[label].append({k: line[k] for k in ("ms_per_step", "value") if k in line})
-    res = {"what": "bench.py --gpus 1 --steps 60 --warmup 20 with global_classes / global_channels unset, parent commit and this tree "
-                   "alternating on one MI355X, %d pairs, parent first" % alternations}
+    res = {"what": "bench.py --gpus 1 --steps 60 --warmup 20 with %s unset, parent commit and this tree "
+                   "alternating on one MI355X, %d pairs, parent first" % (keys, alternations)}
     res.update(runs)
     for label, v in runs.items():
         ms = [r["ms_per_step"] for r in v if "ms_per_step" in r]
         if ms:
             res[label + "_ms_per_step_median"], res[label + "_ms_per_step_spread"] = _median_spread(ms)
-    _write_profile("gcond_bench_unset.json", res)
+    _write_profile(profile, res)
+    print(json.dumps(res))
+
+
+def rvq_bench(reps, alternations=6):
+    """`rvq`: residual vector quantisation.  (a) wn_rvq_fwd / wn_rvq_bwd / wn_rvq_ema_update at S = 2, 4, 8 against the composition they
+    replace, built from the one-stage entries: S wn_vq_fwd launches with the torch subtractions and additions between them, S
+    wn_vq_bwd launches, S wn_vq_ema_update calls - at config 4's shape (B 8, Bw 64, Le 25, K 512) and the shipped autoencoder's
+    (B 4, Bw 512, Le 32, K 512), HIP events around `reps` rounds; (b) the fused config-4 step at S = 4 against S = 1, both learned.
+    Everything alternated `alternations` times on one device: medians and spreads.  Written to profiles/rvq_kbench.json."""
+    import time
+    from music_amd import _lib
+    from music_amd._lib import call, ptr
+    from music_amd.model1 import wavenet_autoencoder
+    st = _lib.stream()
+    res = {"alternations": alternations}
+    rng = np.random.default_rng(0)
+    shapes = {"config4": (8, 64, 25, 512), "shipped": (4, 512, 32, 512)}
+    stages = (2, 4, 8)
+    f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device="cuda")
+    i32 = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device="cuda")
+    bufs = {}
+    for name, (B, Bw, Le, K) in shapes.items():
+        for S in stages:
+            enc = torch.from_numpy(rng.standard_normal((B, Bw, Le)).astype(np.float32)).cuda()
+            flat = torch.from_numpy(np.concatenate([rng.standard_normal(K * Bw) * 0.8 ** s for s in range(S)]).astype(np.float32)).cuda()
+            b = bufs[name, S] = dict(enc=enc, flat=flat, q=f32(B, Bw, Le), idx=i32(S, B, Le), counts=i32(S, K), res=f32(S, B, Bw, Le),
+                                     part=f32(S, _lib.VQ_NUM_PARTIALS), d=torch.randn_like(enc), d_out=f32(B, Bw, Le), grad=torch.empty_like(flat),
+                                     stat=f32(S, K * (Bw + 1)), state=f32(S, K * (Bw + 1)), work=i32(S, _lib.VQ_EMA_WORK_BYTES // 4), info=i32(S, 2))
+            call("wn_rvq_fwd", ptr(enc), ptr(flat), 0, ptr(b["q"]), ptr(b["idx"]), ptr(b["counts"]), ptr(b["res"]), ptr(b["part"]), S, K, Bw, Le, B, st)
+            call("wn_rvq_bwd_stats", ptr(enc), ptr(b["idx"]), ptr(b["res"]), ptr(b["d"]), ptr(flat), 0, 0.25, 1.0, ptr(b["d_out"]), ptr(b["grad"]),
+                 ptr(b["stat"]), S, K, Bw, Le, B, st)
+            b["state"].view(S, -1)[:, :K] = 1.0
+            b["state"].view(S, -1)[:, K:] = flat.view(S, -1)
+            b["state0"], b["flat0"] = b["state"].clone(), flat.clone()
+
+    def one(name, S, which, fused):
+        B, Bw, Le, K = shapes[name]
+        b = bufs[name, S]
+        n, kb = B * Bw * Le, K * Bw
+        if which == "fwd" and fused:
+            call("wn_rvq_fwd", ptr(b["enc"]), ptr(b["flat"]), 0, ptr(b["q"]), ptr(b["idx"]), ptr(b["counts"]), ptr(b["res"]), ptr(b["part"]), S, K,
+                 Bw, Le, B, st)
+        elif which == "fwd":                                                # S launches; r -= q_s and q += q_s in torch between them
+            r, q = b["enc"], None
+            for s in range(S):
+                call("wn_vq_fwd", ptr(r), ptr(b["flat"]), s * kb, ptr(b["d_out"]), ptr(b["idx"], s * B * Le), ptr(b["counts"], s * K),
+                     ptr(b["part"], s * _lib.VQ_NUM_PARTIALS), K, Bw, Le, B, st)
+                r = torch.sub(r, b["d_out"], out=b["res"][s])
+                q = b["q"].copy_(b["d_out"]) if q is None else q.add_(b["d_out"])
+        elif which == "bwd" and fused:
+            call("wn_rvq_bwd", ptr(b["enc"]), ptr(b["idx"]), ptr(b["res"]), ptr(b["d"]), ptr(b["flat"]), 0, 0.25, 1.0, ptr(b["d_out"]),
+                 ptr(b["grad"]), S, K, Bw, Le, B, st)
+        elif which == "bwd":                                                # S launches, each stage on its own input, d_enc handed on
+            for s in range(S):
+                call("wn_vq_bwd", ptr(b["enc"]) if s == 0 else ptr(b["res"], (s - 1) * n), ptr(b["idx"], s * B * Le),
+                     ptr(b["d"]) if s == 0 else ptr(b["d_out"]), ptr(b["flat"]), s * kb, 0.25, 1.0, ptr(b["d_out"]), ptr(b["grad"]), K, Bw, Le, B, st)
+        elif fused:
+            call("wn_rvq_ema_update", ptr(b["flat"]), 0, ptr(b["stat"]), ptr(b["state"]), ptr(b["work"]), ptr(b["info"]), S, K, Bw, 0.99, 1e-5,
+                 0.5, None, st)
+        else:
+            w = _lib.VQ_EMA_WORK_BYTES // 4
+            for s in range(S):
+                call("wn_vq_ema_update", ptr(b["flat"]), s * kb, ptr(b["stat"], s * K * (Bw + 1)), ptr(b["state"], s * K * (Bw + 1)),
+                     ptr(b["work"], s * w), ptr(b["info"], 2 * s), K, Bw, 0.99, 1e-5, 0.5, None, st)
+
+    def rounds(key, n):
+        name, S, which, fused = key
+        b = bufs[name, S]
+        b["state"].copy_(b["state0"])
+        b["flat"].copy_(b["flat0"])
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        torch.cuda.synchronize()
+        ev[0].record()
+        for _ in range(n):
+            one(*key)
+        ev[1].record()
+        torch.cuda.synchronize()
+        return ev[0].elapsed_time(ev[1]) / n * 1e3
+    times = {(n, S, w, f): [] for n in shapes for S in stages for w in ("fwd", "bwd", "ema") for f in (True, False)}
+    for key in times:
+        rounds(key, 10)                                                       # warm
+    for _ in range(alternations):
+        for key in times:
+            times[key].append(rounds(key, max(reps, 50)))
+    for (n, S, w, f), v in times.items():
+        label = "%s_%s_s%d_%s_us" % ("wn_rvq" if f else "composed", w, S, n)
+        res[label], res[label + "_spread"] = _median_spread(v)
+    # ---- the fused config-4 step, S = 4 against S = 1
+    cfg = dict(filter_width=2, quantization_channel=256, dilations=CFG["dilations"], en_residual_channel=64, en_dilation_channel=64,
+               en_bottleneck_width=64, en_pool_kernel_size=512, de_residual_channel=64, de_dilation_channel=64, de_skip_channel=256,
+               use_bias=False, conditioning="learned", bottleneck="vq", vq_codes=512)
+    from music_amd.faster_audio_data import onehot_device
+    x = onehot_device(torch.from_numpy(rng.integers(0, 256, size=(B_LOCAL, T)).astype(np.int32)).cuda(), 256, True)
+    engs = {}
+    for S in (1, 4):
+        torch.manual_seed(0)
+        net = wavenet_autoencoder(vq_stages=S, **cfg).cuda()
+        eng = net._engine_for(torch.device("cuda", 0))
+        eng.adam_init(lr=1e-4)
+        with torch.no_grad():
+            _, _, ws0 = eng.forward(x, None, want_probs=False, encode_only=True)
+        net.init_codebook(ws0["enc_pre"], seed=0)                             # (codes in use, as in a trained model)
+        engs[S] = (net, eng)
+    W = T - engs[1][0].receptive_field + 1
+    target = torch.from_numpy(rng.integers(0, 256, size=(B_LOCAL * W,)).astype(np.int64)).cuda()
+
+    def steps(S, n):
+        eng = engs[S][1]
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            loss = eng.loss_and_grad(x, target, None)
+            eng.adam_step()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / n * 1e3, float(loss)
+    for S in engs:
+        steps(S, 5)
+    step_ms = {S: [] for S in engs}
+    for _ in range(alternations):
+        for S in engs:
+            ms, loss = steps(S, max(reps, 20))
+            step_ms[S].append(ms)
+            res["fused_step_loss_s%d" % S] = round(loss, 5)
+    for S, v in step_ms.items():
+        res["fused_step_ms_s%d" % S], res["fused_step_ms_s%d_spread" % S] = _median_spread(v)
+    res["fused_step_ms_s4_minus_s1"] = round(res["fused_step_ms_s4"] - res["fused_step_ms_s1"], 3)
+    res["fused_step_ms_by_alternation"] = {"s%d" % S: [round(t, 3) for t in v] for S, v in step_ms.items()}
+    stats = engs[4][1].last_vq
+    res["stage_mse_s4"] = [round(float(v), 6) for v in stats.stage_mse.tolist()]
+    res["stage_codes_used_s4"] = [int(v) for v in stats.stage_codes_used.tolist()]
+    _write_profile("rvq_kbench.json", res)
     print(json.dumps(res))
 
 
@@ -357,12 +488,16 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--precision", default="f16x3,bf16x3")
     ap.add_argument("--overlap", type=int, default=1)
-    ap.add_argument("--parent", default=None, help="gcond: a built checkout of the parent commit, for profiles/gcond_bench_unset.json")
+    ap.add_argument("--parent", default=None, help="gcond / rvq: a built checkout of the parent commit, for profiles/<what>_bench_unset.json")
     args = ap.parse_args()
     if args.what == "gcond":
         if args.parent:
             bench_unset(os.path.abspath(args.parent))
         return gcond_bench(args.reps)
+    if args.what == "rvq":
+        if args.parent:
+            bench_unset(os.path.abspath(args.parent), profile="rvq_bench_unset.json", keys="vq_stages")
+        return rvq_bench(args.reps)
     if args.what == "vq":
         return vq_bench(args.reps)
     if args.what == "vq_ema":

@@ -14,7 +14,12 @@ music_amd.ae_generate.decode_codes.
 
 The checkpoint is read under its EMA shadow when `<checkpoint minus .model>.ema` exists (--no-ema: the raw weights).  A piece is
 encoded in windows of --frames pooled frames (rf - 1 samples of overlap, so every frame sees what it sees in the whole piece),
---batch windows per forward; only the encoder, the pool and the quantiser run (music_amd.ae_generate.encode_codes)."""
+--batch windows per forward; only the encoder, the pool and the quantiser run (music_amd.ae_generate.encode_codes).
+
+A model with "vq_stages": S > 1 gives S codes per frame.  A piece is still ONE array, frame-major - l0s0, l0s1, .., l1s0, .. - of
+TOKENS s * K + code, so the prior's alphabet ("quantization_channels") is S * K and a position's stage is readable from its
+token; S * K > 1024, the decoder's sampler limit, is refused.  music_amd.ae_generate.split_code_stream turns a sampled stream back
+into the (B, S, Le) codes that decode_codes takes."""
 import argparse
 import json
 import os
@@ -36,6 +41,8 @@ def encode_pieces(net, pieces, frames=32, batch=8, one_hot="scrambled"):
     if one_hot not in ("scrambled", "canonical"):
         raise ValueError('one_hot must be "scrambled" or "canonical", not %r' % (one_hot,))
     Q, rf, pool = net.quantization_channel, net.receptive_field, net.en_pool_kernel_size
+    S, K = getattr(net, "vq_stages", 1), net.vq_num_codes
+    check_alphabet(S, K)
     dev = next(net.parameters()).device
     out = []
     for piece in pieces:
@@ -45,7 +52,7 @@ def encode_pieces(net, pieces, frames=32, batch=8, one_hot="scrambled"):
         if piece.size and (int(piece.min()) < 0 or int(piece.max()) >= Q):
             raise ValueError("a piece holds codes outside [0, %d)" % Q)
         n_frames = max(0, (piece.size - rf + 1) // pool)
-        codes = np.empty(n_frames, dtype=np.int32)
+        codes = np.empty((n_frames, S), dtype=np.int32)            # tokens: s * K + code, frame-major
         # windows of `frames` frames (the last one shorter), full ones `batch` at a time
         starts = list(range(0, n_frames, frames))
         full = [f0 for f0 in starts if f0 + frames <= n_frames]
@@ -54,12 +61,21 @@ def encode_pieces(net, pieces, frames=32, batch=8, one_hot="scrambled"):
             nf = min(frames, n_frames - group[0])
             win = np.stack([piece[f0 * pool:f0 * pool + rf - 1 + nf * pool] for f0 in group]).astype(np.int32)
             x = faster_audio_data.onehot_device(torch.from_numpy(win).to(dev), Q, one_hot == "scrambled")
-            got = encode_codes(net, x).cpu().numpy().astype(np.int32)
-            assert got.shape == (len(group), nf)
+            got = encode_codes(net, x).cpu().numpy().astype(np.int32).reshape(len(group), S, -1)
+            assert got.shape == (len(group), S, nf)
             for row, f0 in zip(got, group):
-                codes[f0:f0 + nf] = row
-        out.append(codes)
+                codes[f0:f0 + nf] = row.T + np.arange(S, dtype=np.int32) * K
+        out.append(codes.reshape(-1))
     return out
+
+
+def check_alphabet(stages, K):
+    """The prior's alphabet is stages * K tokens; the decoder's samplers take at most 1024."""
+    from music_amd import _lib
+    if stages * K > _lib.VQ_MAX_CODES:
+        raise ValueError('"vq_stages" x "vq_codes" = %d x %d = %d tokens: a prior over the interleaved stream would need more than the '
+                         "%d classes the decoder's samplers take - use fewer stages or a smaller codebook"
+                         % (stages, K, stages * K, _lib.VQ_MAX_CODES))
 
 
 def load_vq_model(model_params, checkpoint, use_ema=True):
