@@ -553,6 +553,32 @@ int wn_rvq_ema_update(float* flat, int64_t cb_off, const float* stat, float* sta
                       float decay, float eps, float restart, const wn_guard_state* guard_state, wn_stream_t stream);
 int wn_rvq_lookup(const int32_t* idx, const float* flat, int64_t cb_off, float* q_out, int32_t* bad, int S, int stages, int K, int bw,
                   int le, int batch, wn_stream_t stream);
+/* ---- QUANTISER DROPOUT for the residual chain (SoundStream, EnCodec, DAC): every clip b has its own stage count n_b, frame fr of
+ * clip b is ACTIVE in stage s iff s < n_b.  nstage: `batch` int32 on the device, required; wn_rvq_fwd_n / _bwd_n / _bwd_stats_n clamp
+ * a value outside [1, S] to [1, S] before any use (the host validates before it uploads), it is never a bound unchecked.
+ * wn_rvq_fwd_n (one launch and the memset node for counts, as wn_rvq_fwd): per frame and stage an active frame gets exactly what
+ * wn_rvq_fwd computes; for an inactive one idx_s = -1, the residual and the running q stay as they are (no arithmetic on them),
+ * res[s] = the carried r_n_b (no uninitialised floats), and nothing goes into counts[s] or stage s's loss partial.  q_out = the sum of
+ * the first n_b winning rows in stage order.  loss_part[s] keeps the FIXED denominator: sum over the ACTIVE frames of the best
+ * distance / (C bw), so the model's vq_loss is the batch expectation.  A tile's stage loop ends at the largest n of its frames.
+ * wn_rvq_bwd_n / wn_rvq_bwd_stats_n: wn_rvq_bwd / wn_rvq_bwd_stats with
+ *   d_enc = d_q + g_scale beta s (r_1 + .. + r_n_b)     the ACTIVE stages, ascending; NaN iff an active stage's idx lies outside [0, K)
+ * and d_c_s[k] / stat's [n | sums] over the active frames of stage s alone (idx = -1 matches no code): a stage nobody used gets exact
+ * zeros.  Inactive indices are not looked at.  wn_rvq_ema_update takes the stats as they are.
+ * wn_rvq_lookup_n: q_out = the sum of the first n_b stages' rows from idx [S][batch][le]; an ACTIVE idx outside [0, K), or an n_b
+ * outside [1, S] (NOT clamped here), gives a NaN frame and sets *bad (cleared by the call; may be NULL) - never dereferenced.
+ * With every n_b = S every output of the four has the bits of the entry without _n.  On `stream`, no allocation, no float atomics, a
+ * fixed order.  Limits and refusals as for wn_rvq_*, and a NULL nstage; batch == 0 returns 0 and writes nothing (NULLs allowed). */
+int wn_rvq_fwd_n(const float* enc, const float* flat, int64_t cb_off, const int32_t* nstage, float* q_out, int32_t* idx, int32_t* counts,
+                 float* res, float* loss_part, int S, int K, int bw, int le, int batch, wn_stream_t stream);
+int wn_rvq_bwd_n(const float* enc, const int32_t* idx, const float* res, const int32_t* nstage, const float* d_q, const float* flat,
+                 int64_t cb_off, float beta, float g_scale, float* d_enc, float* flat_grad, int S, int K, int bw, int le, int batch,
+                 wn_stream_t stream);
+int wn_rvq_bwd_stats_n(const float* enc, const int32_t* idx, const float* res, const int32_t* nstage, const float* d_q, const float* flat,
+                       int64_t cb_off, float beta, float g_scale, float* d_enc, float* flat_grad, float* stat, int S, int K, int bw, int le,
+                       int batch, wn_stream_t stream);
+int wn_rvq_lookup_n(const int32_t* idx, const int32_t* nstage, const float* flat, int64_t cb_off, float* q_out, int32_t* bad, int S, int K,
+                    int bw, int le, int batch, wn_stream_t stream);
 /* The reference's nn.DataParallel gradient reduction (wavenet/train.py:116-122) as ONE in-place sum over the ranks of the flat
  * fp32 gradient buffer: ncclAllReduce(buf, buf, n, ncclFloat32, ncclSum, comm, stream) on the caller's RCCL communicator
  * (`comm` = an ncclComm_t).  The 1 / world_size of the mean goes into wn_adam_flat's gscale.  Returns -5 when RCCL is neither

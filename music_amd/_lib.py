@@ -107,6 +107,10 @@ SIGNATURES = {
     "wn_rvq_bwd_stats": [_p, _p, _p, _p, _p, _l, _f, _f, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     "wn_rvq_ema_update": [_p, _l, _p, _p, _p, _p, _i, _i, _i, _f, _f, _f, _p, _p],
     "wn_rvq_lookup": [_p, _p, _l, _p, _p, _i, _i, _i, _i, _i, _i, _p],
+    "wn_rvq_fwd_n": [_p, _p, _l, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
+    "wn_rvq_bwd_n": [_p, _p, _p, _p, _p, _p, _l, _f, _f, _p, _p, _i, _i, _i, _i, _i, _p],
+    "wn_rvq_bwd_stats_n": [_p, _p, _p, _p, _p, _p, _l, _f, _f, _p, _p, _p, _i, _i, _i, _i, _i, _p],
+    "wn_rvq_lookup_n": [_p, _p, _p, _l, _p, _p, _i, _i, _i, _i, _i, _p],
     "wn_coll_available": [],
     "wn_comm_unique_id": [_p],
     "wn_comm_create": [_i, _i, _p, _p],

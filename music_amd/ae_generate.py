@@ -23,6 +23,7 @@ encoding): the projections of the encoding become per-clip TABLES with one colum
 kernel (``wn_decode_batch_cond``) adds, at every step, the column the reference's ``_conditon`` (model1.py:227-247) would
 have added at that position of the forward over the whole clip - ``cond_schedule`` says which."""
 import json
+import math
 import os
 
 import numpy as np
@@ -229,7 +230,7 @@ def _decode_from_encoding(net, enc, cond, W, first, prime, forced, free_step=Fal
 
 
 def resynthesize(net, clips, cond=None, teacher_forced=False, want_probs=False, temperature=None, seed=0, top_k=None, top_p=None,
-                 streams=None, classes=None, global_vectors=None):
+                 streams=None, classes=None, global_vectors=None, stages=None):
     """Encode ``clips`` (B, Q, T) one-hot, T >= receptive_field with at least one pooled frame, and regenerate them from the
     encoding with the cached-queue decoder: the encoder runs ONCE, the conditioning projections are drawn ONCE (or taken
     from ``cond``), the per-clip tables (one column per pooled frame and stage) are built on the device, the queues are
@@ -244,7 +245,9 @@ def resynthesize(net, clips, cond=None, teacher_forced=False, want_probs=False, 
     frames' codes and the encoding in front of the quantiser.
     A model with global class conditioning wants ``classes`` (one integer per clip) or ``global_vectors`` ((B, E) floats, e.g. a
     mix of two rows of ``net.global_vectors``), never both: the clips are decoded AS that class - their own for a reconstruction,
-    another for a conversion (the encoder takes no class)."""
+    another for a conversion (the encoder takes no class).
+    ``stages`` (a residual vq bottleneck): None, an int n or one int per clip in [1, vq_stages] - every clip is quantised with its
+    first n stages (wn_rvq_fwd_n) and decoded from that coarser encoding; ``net.vq_codes`` then holds -1 in the absent stages."""
     if clips.dim() != 3 or clips.size(1) != net.quantization_channel:
         raise ValueError("resynthesize: clips must be (B, %d, T)" % net.quantization_channel)
     x = clips.detach().cuda().float().contiguous()
@@ -259,7 +262,7 @@ def resynthesize(net, clips, cond=None, teacher_forced=False, want_probs=False, 
     eng = net._engine_for(x.device)
     with torch.no_grad():
         # (raises when the clip pools to no frame; with a global term the encoder alone runs: the decoder's class is the caller's)
-        _, enc, ws = eng.forward(x, eng_cond, want_probs=False, encode_only=gvec is not None)
+        _, enc, ws = eng.forward(x, eng_cond, want_probs=False, encode_only=gvec is not None, **({} if stages is None else {"stages": stages}))
     enc = net.last_encoding = enc.clone()
     if eng.vq:
         net.vq_codes, net.last_encoding_pre = eng.vq_codes_of(ws), ws["enc_pre"]
@@ -278,9 +281,11 @@ def _vq_engine(net, what):
     return net._engine_for(next(net.parameters()).device)
 
 
-def encode_codes(net, clips):
+def encode_codes(net, clips, stages=None):
     """The codes of ``clips`` (B, Q, T) one-hot under a vq model: (B, Le) int64, Le = (T - rf + 1) // pool frames per clip;
-    (B, S, Le) with ``vq_stages`` = S > 1, stage s in [:, s].  Runs the encoder, the pool and the quantiser (wn_vq_fwd / wn_rvq_fwd) only."""
+    (B, S, Le) with ``vq_stages`` = S > 1, stage s in [:, s].  Runs the encoder, the pool and the quantiser (wn_vq_fwd / wn_rvq_fwd) only.
+    ``stages``: None, an int n or one int per clip in [1, S] - the codes of the first n stages, still (B, S, Le), with -1 in the absent
+    stages (wn_rvq_fwd_n); ``decode_codes`` takes them as they are."""
     eng = _vq_engine(net, "encode_codes")
     if clips.dim() != 3 or clips.size(1) != net.quantization_channel:
         raise ValueError("encode_codes: clips must be (B, %d, T)" % net.quantization_channel)
@@ -288,7 +293,7 @@ def encode_codes(net, clips):
         raise ValueError("wave sample not long enough")
     x = clips.detach().to(eng.device).float().contiguous()
     with torch.no_grad():
-        _, _, ws = eng.forward(x, None, want_probs=False, encode_only=True)
+        _, _, ws = eng.forward(x, None, want_probs=False, encode_only=True, **({} if stages is None else {"stages": stages}))
     return eng.vq_codes_of(ws)
 
 
@@ -304,7 +309,9 @@ def decode_codes(net, codes, W, start=None, teacher_forced=None, want_probs=Fals
     defaults to their first rf - 1.  ``temperature`` / ``top_k`` / ``top_p`` / ``seed`` / ``streams``: as in ``resynthesize``,
     and so are ``classes`` / ``global_vectors`` (the same codes as another class: the conversion of VQ-VAE).
     With ``vq_stages`` = S > 1: ``codes`` (B, n, Le), 1 <= n <= S, the first n stages' codes; the encoding is the sum of their rows in
-    stage order (wn_rvq_lookup) - all S give the encoding the forward decoded, a prefix the coarser code.
+    stage order (wn_rvq_lookup) - all S give the encoding the forward decoded, a prefix the coarser code.  Codes with -1 in a clip's
+    absent stages (``encode_codes(..., stages=)``) give every clip the sum of ITS stages' rows (wn_rvq_lookup_n); a clip's -1 entries
+    must form a stage suffix, identical over its frames, and never include stage 0 (ValueError otherwise, before any launch).
     Returns (codes int64 (B, W), probabilities (B, W, Q) or None)."""
     eng = _vq_engine(net, "decode_codes")
     dev = eng.device
@@ -335,6 +342,39 @@ def decode_codes(net, codes, W, start=None, teacher_forced=None, want_probs=Fals
                                        free_step=last is None, want_probs=want_probs, temperature=temperature, seed=seed, top_k=top_k,
                                        top_p=top_p, streams=streams, gvec=gvec)
     return out.to(torch.int64), probs
+
+
+def rate_distortion(net, clips, classes=None):
+    """What every prefix of the stages costs and gives on ``clips`` (B, Q, T) canonical one-hot, as ``resynthesize`` takes them: for
+    n = 1 .. S one forward in eval mode over the first T - 1 samples with ``stages=n``, scored against the clips' own next samples
+    (output column w predicts sample rf + w).  Returns a list of S dicts:
+    ``stages`` n, ``bits_per_frame`` n log2 K, ``mse`` (the encoding's error against e: the last active stage's) and ``nll``
+    (nats per sample, the mean over the clips of ``objective.score``).  The model's mode is restored.  On a chain whose codebooks were
+    not fitted the mse may GROW with n: a stage refines a frame only where one of its rows is nearer to the residual than 0 is."""
+    eng = _vq_engine(net, "rate_distortion")
+    if clips.dim() != 3 or clips.size(1) != net.quantization_channel:
+        raise ValueError("rate_distortion: clips must be (B, %d, T)" % net.quantization_channel)
+    try:
+        from . import objective
+    except ImportError:
+        from music_amd import objective
+    if clips.size(2) - net.receptive_field < 1:
+        raise ValueError("wave sample not long enough")
+    full = clips.detach().to(eng.device).float()
+    x = full[:, :, :-1].contiguous()
+    target = full[:, :, net.receptive_field:].argmax(1)                # (B, T - rf)
+    was_training = net.training
+    net.eval()
+    rows = []
+    try:
+        for n in range(1, eng.vq_S + 1):
+            s = objective.score(net, x, target, classes=classes, stages=n if eng.vq_S > 1 else None)
+            st = eng.last_vq
+            mse = st.stage_mse[n - 1] if eng.vq_S > 1 else st.mse
+            rows.append({"stages": n, "bits_per_frame": n * math.log2(eng.vq_K), "mse": float(mse), "nll": float(s["nll"].mean())})
+    finally:
+        net.train(was_training)
+    return rows
 
 
 def split_code_stream(tokens, stages, K):

@@ -115,13 +115,15 @@ class GenericAutoencoderEngine(GeneralPlan):
         return out
 
     # ------------------------------------------------------------------ forward (model1.py:256-268)
-    def forward(self, x, cond=None, want_probs=True, encode_only=False, classes=None):
+    def forward(self, x, cond=None, want_probs=True, encode_only=False, classes=None, stages=None):
         """cond: the N + 1 drawn (weight, bias) pairs; None with learned conditioning (parameters of the flat buffer);
         classes: one integer per clip with global class conditioning, else None;
+        stages: quantiser dropout of a residual vq bottleneck (EngineBase.vq_stage_counts): None, an int or one int per clip;
         encode_only=True stops behind the pooled (and, with a vq bottleneck, quantised) encoding: (None, enc, ws)"""
         self._check_cond(cond)
         B, Q, T = x.shape
         cls = None if encode_only and classes is None else self.stage_classes(classes, B)      # (the encoder takes no classes)
+        nstage = self.vq_stage_counts(stages, B)
         assert Q == self.Q and x.is_contiguous() and x.dtype == torch.float32 and x.is_cuda
         W = T - self.rf + 1
         if W <= 0:
@@ -161,7 +163,7 @@ class GenericAutoencoderEngine(GeneralPlan):
         enc = torch.empty(B, self.Bw, Le, dtype=torch.float32, device=dev)
         call("wn_avgpool", E, BwP * pitch, pitch, lo, self.pool, Le, self.Bw, ptr(enc), self.Bw * Le, Le, B, st)
         if self.vq:                                           # every frame -> its nearest codebook row: the decoder sees q
-            enc = self.vq_fwd(ws, enc, st)
+            enc = self.vq_fwd(ws, enc, st, nstage)
         if encode_only:
             return None, enc, ws
 
@@ -298,7 +300,7 @@ class GenericAutoencoderEngine(GeneralPlan):
         ps.reduce_grads()
 
     # ------------------------------------------------------------------ fused training step (wavenet_autoencoder/train.py:146-160)
-    def loss_and_grad(self, x, target, cond=None, objective=None, classes=None):
-        """objective: None = self.objective (EngineBase)"""
-        return self._throttled(lambda: self._fused_tail(self.forward(x, cond, want_probs=False, classes=classes)[2], target,
+    def loss_and_grad(self, x, target, cond=None, objective=None, classes=None, stages=None):
+        """objective: None = self.objective (EngineBase); stages: as in forward"""
+        return self._throttled(lambda: self._fused_tail(self.forward(x, cond, want_probs=False, classes=classes, stages=stages)[2], target,
                                                        objective=objective))

@@ -45,6 +45,15 @@ stage s quantises what the stages before it left over and the decoder sees the s
 of the stages is a coarser code).  ``vq_loss`` sums the stages' terms, every stage keeps its own EMA state and restarts, ``"vq_init":
 "data"`` fills the stages in order from the residuals, the ``vq_log.log`` line reports the last stage's mse (q against e) and ends with
 the per-stage figures, ``restarted`` sums the stages; a checkpoint only loads into a model of the same stage count.
+``"vq_stage_dropout"`` (p in [0, 1], default 0 = off; needs ``"vq_stages"`` > 1): quantiser dropout (SoundStream, EnCodec, DAC) - in
+every step a share p of the clips draws its own stage count n uniformly from 1 .. S and is quantised, scored and counted with its
+first n stages only, the others use all S (p = 1 is SoundStream's rule, p = 0.5 DAC's): one model then serves every bitrate n log2 K,
+and ``decode_codes`` of a prefix of the stages runs through tables that were trained on it.  The draw is a counter hash of the
+optional train_params.json key ``"vq_dropout_seed"`` (default 0), the global step and the clip's index in the GLOBAL batch
+(music_amd/vq_dropout.py): no RNG state, a resumed run and any data-parallel layout draw the same n for the same clip.  It adds no
+parameter and no buffer, checkpoints load both ways.  ``"vq_init": "data"`` fills the stages from all-active residuals, as without it.
+Only with p > 0 the ``vq_log.log`` line ends with ``, active f0/f1/..``, the frames that took part in each stage.  Later stages see
+fewer frames (stage s a share 1 - p s / S), so with ``"vq_update": "ema"`` a ``"vq_restart"`` threshold bites them sooner.
 ``"global_classes"`` and ``"global_channels"`` (both 0, the default: off; both >= 1 together, ``"conditioning": "learned"`` required):
 global class conditioning of the decoder - every clip has a class (speaker, instrument) whose learned embedding is projected into
 every conditioning table (music_amd/model1.py).  The classes come from the optional dataset_params.json key ``"labels_path"``, a
@@ -259,6 +268,9 @@ def train():
             lambda: guard.engine_named_grads(engine) if fused else [(n, p.grad) for n, p in net.named_parameters()])
     is_vq = getattr(net, "bottleneck", "continuous") == "vq"
     is_vq_ema = is_vq and getattr(net, "vq_update", "gradient") == "ema"
+    vq_drop = is_vq and getattr(net, "vq_stage_dropout", 0.0) > 0
+    if vq_drop:
+        net.vq_dropout_seed = int(train_params.get("vq_dropout_seed", 0))
     vq_init = train_params.get("vq_init", "uniform")
     if vq_init not in ("uniform", "data"):
         raise ValueError('train_params.json: "vq_init" must be "uniform" or "data", not %r' % (vq_init,))
@@ -270,6 +282,9 @@ def train():
             # global class conditioning: the clips' classes, (B,) on the host, as ONE more keyword of the calls below - without it they
             # are made as they always were
             kw = {"classes": sampled_batch["audio_class"]} if "audio_class" in sampled_batch else {}
+            if vq_drop and piece is not None:
+                # quantiser dropout: the clips' stage counts from (seed, global step, global clip index), ONE more keyword as well
+                kw["stages"] = net.draw_stages(piece.shape[0], step=num_trained, first_clip=int(sampled_batch.get("first_clip", 0)))
             dp_scale = float(sampled_batch.get("dp_scale", 1.0))      # ragged last batch, see faster_audio_data._Collate
             if piece is not None:
                 target = target.view(-1)
@@ -336,10 +351,11 @@ def train():
                     guard_log.tick(num_trained)
                 stats = (engine.last_vq if fused else net.last_vq) if vq_log_file is not None else None
                 if stats is not None:                         # (the last step's figures, read back where the loss is)
-                    vq_log_file.writelines('Trained over %d pieces, vq mse %s, perplexity %s, codes used %d%s%s\n'
+                    vq_log_file.writelines('Trained over %d pieces, vq mse %s, perplexity %s, codes used %d%s%s%s\n'
                                            % (num_trained, stats.mse.item(), stats.perplexity.item(), int(stats.codes_used.item()),
                                               ", restarted %d" % net._engine_for(device).vq_restarted() if is_vq_ema else "",
-                                              vq_stage_fields(stats) if getattr(net, "vq_stages", 1) > 1 else ""))
+                                              vq_stage_fields(stats) if getattr(net, "vq_stages", 1) > 1 else "",
+                                              ", active " + "/".join("%d" % v for v in stats.stage_frames.tolist()) if vq_drop else ""))
                     vq_log_file.flush()
                 total_loss.zero_()
             if validation is not None:

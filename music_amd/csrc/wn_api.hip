@@ -651,6 +651,43 @@ int wn_rvq_lookup(const int32_t* idx, const float* flat, int64_t cb_off, float* 
     WN_REQUIRE("wn_rvq_lookup", idx, flat, q_out);
     return wn_launch_vq_lookup(idx, flat, (long)cb_off, q_out, bad, stages, K, bw, le, batch, (hipStream_t)stream);
 }
+// ---- quantiser dropout: the chain with a stage count per clip (nstage, batch int32 on the device; required)
+int wn_rvq_fwd_n(const float* enc, const float* flat, int64_t cb_off, const int32_t* nstage, float* q_out, int32_t* idx, int32_t* counts,
+                 float* res, float* loss_part, int S, int K, int bw, int le, int batch, wn_stream_t stream) {
+    if (int rc = rvq_checked("wn_rvq_fwd_n", S, cb_off, K, bw, le, batch)) return rc;
+    if (batch == 0) return 0;
+    WN_REQUIRE("wn_rvq_fwd_n", enc, flat, nstage, q_out, idx, res, loss_part);
+    WnVq p = rvq_args(enc, flat, cb_off, idx, res, S, K, bw, le, batch);
+    p.q_out = q_out; p.counts = counts; p.loss_part = loss_part;
+    return wn_launch_rvq_fwd_n(p, nstage, (hipStream_t)stream);
+}
+int wn_rvq_bwd_n(const float* enc, const int32_t* idx, const float* res, const int32_t* nstage, const float* d_q, const float* flat,
+                 int64_t cb_off, float beta, float g_scale, float* d_enc, float* flat_grad, int S, int K, int bw, int le, int batch,
+                 wn_stream_t stream) {
+    if (int rc = rvq_checked("wn_rvq_bwd_n", S, cb_off, K, bw, le, batch)) return rc;
+    if (batch == 0) return 0;
+    WN_REQUIRE("wn_rvq_bwd_n", enc, idx, res, nstage, d_q, flat, d_enc, flat_grad);
+    WnVq p = rvq_args(enc, flat, cb_off, idx, res, S, K, bw, le, batch);
+    p.d_q = d_q; p.d_enc = d_enc; p.flat_grad = flat_grad;
+    return wn_launch_rvq_bwd_n(p, nstage, beta, g_scale, nullptr, (hipStream_t)stream);
+}
+int wn_rvq_bwd_stats_n(const float* enc, const int32_t* idx, const float* res, const int32_t* nstage, const float* d_q, const float* flat,
+                       int64_t cb_off, float beta, float g_scale, float* d_enc, float* flat_grad, float* stat, int S, int K, int bw, int le,
+                       int batch, wn_stream_t stream) {
+    if (int rc = rvq_checked("wn_rvq_bwd_stats_n", S, cb_off, K, bw, le, batch)) return rc;
+    if (batch == 0) return 0;
+    WN_REQUIRE("wn_rvq_bwd_stats_n", enc, idx, res, nstage, d_q, flat, d_enc, flat_grad, stat);
+    WnVq p = rvq_args(enc, flat, cb_off, idx, res, S, K, bw, le, batch);
+    p.d_q = d_q; p.d_enc = d_enc; p.flat_grad = flat_grad;
+    return wn_launch_rvq_bwd_n(p, nstage, beta, g_scale, stat, (hipStream_t)stream);
+}
+int wn_rvq_lookup_n(const int32_t* idx, const int32_t* nstage, const float* flat, int64_t cb_off, float* q_out, int32_t* bad, int S, int K,
+                    int bw, int le, int batch, wn_stream_t stream) {
+    if (int rc = rvq_checked("wn_rvq_lookup_n", S, cb_off, K, bw, le, batch)) return rc;
+    if (batch == 0) return 0;
+    WN_REQUIRE("wn_rvq_lookup_n", idx, nstage, flat, q_out);
+    return wn_launch_vq_lookup_n(idx, nstage, flat, (long)cb_off, q_out, bad, S, K, bw, le, batch, (hipStream_t)stream);
+}
 int wn_coll_available(void) { return wn_coll_loaded(); }
 int wn_comm_unique_id(char* id128) { return wn_coll_unique_id(id128); }
 int wn_comm_create(int nranks, int rank, const char* id128, void** comm) { return wn_coll_create(nranks, rank, id128, comm); }

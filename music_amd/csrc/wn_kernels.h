@@ -286,6 +286,12 @@ int wn_launch_vq_lookup(const int32_t* idx, const float* flat, long cb_off, floa
                         int batch, hipStream_t st);
 int wn_launch_rvq_fwd(const WnVq& p, hipStream_t st);
 int wn_launch_rvq_bwd(const WnVq& p, float beta, float g_scale, float* stat, hipStream_t st);       // stat != NULL: the stats form
+// quantiser dropout (wn_rvq_*_n): nstage = batch int32 stage counts on the device, clamped to [1, S] there; frame fr of clip b is active
+// in stage s iff s < nstage[b].  wn_launch_vq_lookup_n does not clamp: an n outside [1, S] gives a NaN frame and *bad
+int wn_launch_rvq_fwd_n(const WnVq& p, const int32_t* nstage, hipStream_t st);
+int wn_launch_rvq_bwd_n(const WnVq& p, const int32_t* nstage, float beta, float g_scale, float* stat, hipStream_t st);
+int wn_launch_vq_lookup_n(const int32_t* idx, const int32_t* nstage, const float* flat, long cb_off, float* q_out, int32_t* bad, int S, int K,
+                          int bw, int le, int batch, hipStream_t st);
 // EMA mode: stat = [n | s] and state = [N | m], K counts then K rows of bw; work: WN_VQ_EMA_WORK bytes of device scratch
 #define WN_VQ_MAX_K 1024
 #define WN_VQ_EMA_WORK (16 + 4 * WN_VQ_MAX_K)

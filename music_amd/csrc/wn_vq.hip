@@ -28,6 +28,15 @@
 // over a staged tile with the search and merge of vq_fwd_k, rvq_bwd_k / rvq_bwd_stats_k give every (stage, code) a wave with the walk
 // of vq_bwd_k, and the EMA update's two launches take the stage as a second grid dimension.  The device functions are shared, so at
 // S = 1 every output has the bits of the wn_vq_* entry.
+//
+// Quantiser dropout (wn_rvq_fwd_n / wn_rvq_bwd_n / wn_rvq_bwd_stats_n / wn_rvq_lookup_n): a stage count n_b per clip, frame fr of clip b is
+// active in stage s iff s < n_b (clamped to [1, S] on the device).  Clips of different n share a 4-frame tile whenever Le % 4 != 0, so
+// the stage count is a property of the FRAME inside rvq_fwd_n_k: the tile's stage loop runs to the largest n of its frames (read from
+// LDS behind a barrier: the same bound in every thread, the barriers inside the loop stay uniform), an inactive frame keeps its
+// residual and running q untouched, gets idx = -1 and adds nothing to counts or the stage's loss partial, whose denominator stays
+// C Bw.  The backward needs new element workgroups only (the sum over the ACTIVE stages' residuals): idx = -1 matches no code in
+// vq_code_walk, so the (stage, code) waves cover exactly the active frames as they are.  With every n = S the statements are the
+// chain's: the same bits in every output.
 #include <limits>
 #include "../../include/wavenet_hip.h"
 #include "wn_common.h"
@@ -222,6 +231,83 @@ __global__ __launch_bounds__(64 * NWV) void rvq_fwd_k(WnVq p, float inv_n) {
     if (t < p.S) p.loss_part[t * WN_VQ_PARTIALS + blockIdx.x] = s_loss[t] * inv_n;
 }
 
+// a clip's stage count as the _n kernels use it: whatever the array holds, a value of [1, S] - never a bound unchecked
+__device__ __forceinline__ int nstage_of(const int32_t* nstage, int b, int S) { return min(max(nstage[b], 1), S); }
+
+// Quantiser dropout (wn_rvq_fwd_n): rvq_fwd_k with a stage count per clip, frame fr of clip b is ACTIVE in stage s iff s < n_b.  An
+// active frame gets rvq_fwd_k's arithmetic, an inactive one idx = -1, no count, no loss, and its residual and running q stay as they
+// are (res[s] = the carried r_n, so the buffer holds no uninitialised floats); q_out is written behind the frame's last active stage.
+// The stage loop runs to the maximum n of the tile's frames - s_n is read behind a barrier, so every thread forms the same bound and
+// the barriers inside the loop stay uniform -; the stages behind it only hand out -1 and the carried residual.  A frame behind C has
+// n = 0.  With every n = S each statement below is rvq_fwd_k's: the same bits in every output.
+__global__ __launch_bounds__(64 * NWV) void rvq_fwd_n_k(WnVq p, const int32_t* __restrict__ nstage, float inv_n) {
+    __shared__ float s_e[FT][MAXW];                        // the residual r_s
+    __shared__ float s_q[FT][MAXW];                        // q_0 + ... + q_s
+    __shared__ float s_bd[NWV][FT];
+    __shared__ int s_bi[NWV][FT];
+    __shared__ int s_n[FT];                                // the stage counts of the tile's frames
+    __shared__ float s_loss[WN_RVQ_MAX_S];
+    const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int C = p.batch * p.le, tiles = (C + FT - 1) / FT, nj = (p.bw + 63) >> 6;
+    const long total = (long)C * p.bw, rows = (long)p.K * p.bw;
+    if (t < WN_RVQ_MAX_S) s_loss[t] = 0.f;
+    for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const int f0 = tile * FT;
+        vq_tile_stage(p, f0, C, s_e, t);
+        if (t < FT) s_n[t] = f0 + t < C ? nstage_of(nstage, (f0 + t) / p.le, p.S) : 0;
+        __syncthreads();
+        const int n_max = max(max(s_n[0], s_n[1]), max(s_n[2], s_n[3]));
+        for (int s = 0; s < n_max; ++s) {
+            const float* cb = p.flat + p.cb_off + s * rows;
+            float bd;
+            int bi;
+            vq_tile_search(cb, p.K, p.bw, nj, s_e, lane, wave, bd, bi);
+            if ((lane & 15) == 0) { s_bd[wave][lane >> 4] = bd; s_bi[wave][lane >> 4] = bi; }
+            __syncthreads();
+            if (t < FT) {
+                const int ix = vq_tile_merge(s_bd, s_bi, t);
+                if (f0 + t < C) {
+                    const bool on = s < s_n[t];
+                    p.idx[(long)s * C + f0 + t] = on ? ix : -1;
+                    if (on && p.counts) atomicAdd(&p.counts[s * p.K + ix], 1);
+                }
+            }
+            __syncthreads();
+            if (t == 0) {
+                float loss = s_loss[s];
+                for (int f = 0; f < FT; ++f)
+                    if (s < s_n[f]) loss += s_bd[0][f];
+                s_loss[s] = loss;
+            }
+            for (int o = t; o < FT * p.bw; o += 64 * NWV) {
+                const int j = o / FT, f = o % FT, n = s_n[f];
+                float r = s_e[f][j];
+                if (s < n) {
+                    const float c = cb[(long)s_bi[0][f] * p.bw + j];
+                    r -= c;
+                    const float q = s ? s_q[f][j] + c : c;
+                    s_e[f][j] = r;
+                    s_q[f][j] = q;
+                    if (s == n - 1) p.q_out[frame_base(f0 + f, p.bw, p.le) + (long)j * p.le] = q;
+                }
+                if (f0 + f < C) p.res[s * total + frame_base(f0 + f, p.bw, p.le) + (long)j * p.le] = r;
+            }
+            __syncthreads();                               // the next stage reads s_e and overwrites s_bd and s_bi; so does the next tile
+        }
+        if (n_max < p.S) {                                 // the stages no frame of this tile takes part in
+            for (int s = n_max; s < p.S; ++s) {
+                if (t < FT && f0 + t < C) p.idx[(long)s * C + f0 + t] = -1;
+                for (int o = t; o < FT * p.bw; o += 64 * NWV) {
+                    const int j = o / FT, f = o % FT;
+                    if (f0 + f < C) p.res[s * total + frame_base(f0 + f, p.bw, p.le) + (long)j * p.le] = s_e[f][j];
+                }
+            }
+            __syncthreads();                               // the next tile overwrites s_e and s_n
+        }
+    }
+    if (t < p.S) p.loss_part[t * WN_VQ_PARTIALS + blockIdx.x] = s_loss[t] * inv_n;
+}
+
 // element o of [B][Bw][Le] -> its frame (b * le + l) and its j
 __device__ __forceinline__ void elem_of(long o, int bw, int le, int& fr, int& j) {
     const long bj = o / le;
@@ -371,6 +457,49 @@ __global__ __launch_bounds__(64 * CWV) void rvq_bwd_stats_k(WnVq p, float c_enc,
                   p.bw, p.le, threadIdx.x & 63);
 }
 
+// ---- quantiser dropout's backward (wn_rvq_bwd_n / wn_rvq_bwd_stats_n).  The code waves are the ones above: an inactive frame's idx is
+// -1, which vq_code_walk matches with no code, so a stage's rows cover exactly its active frames.  The element workgroups sum the
+// ACTIVE stages only, d_e = d_q + c_enc (r_1 + ... + r_n), ascending - rvq_bwd_elems' expressions, so n = S gives its bits -, NaN iff
+// an active stage's idx lies outside [0, K); an inactive idx is not looked at
+__device__ __forceinline__ void rvq_bwd_elems_n(const WnVq& p, const int32_t* nstage, float c_enc, int first_block) {
+    const int C = p.batch * p.le;
+    const long total = (long)C * p.bw, step = (long)(gridDim.x - first_block) * (64 * CWV);
+    for (long o = (long)(blockIdx.x - first_block) * (64 * CWV) + threadIdx.x; o < total; o += step) {
+        int fr, j;
+        elem_of(o, p.bw, p.le, fr, j);
+        const int n = nstage_of(nstage, fr / p.le, p.S);
+        bool ok = true;
+        float sum = 0.f;
+        for (int s = 0; s < n; ++s) {
+            ok = ok && (unsigned)p.idx[(long)s * C + fr] < (unsigned)p.K;
+            const float r = p.res[s * total + o];
+            sum = s ? sum + r : r;
+        }
+        p.d_enc[o] = fmaf(c_enc, ok ? sum : std::numeric_limits<float>::quiet_NaN(), p.d_q[o]);
+    }
+}
+
+__global__ __launch_bounds__(64 * CWV) void rvq_bwd_n_k(WnVq p, const int32_t* __restrict__ nstage, float c_enc, float c_cb, int code_blocks) {
+    if ((int)blockIdx.x >= p.S * code_blocks) return rvq_bwd_elems_n(p, nstage, c_enc, p.S * code_blocks);
+    int s, k;
+    const float* src;
+    if (!rvq_code_of(p, code_blocks, s, k, src)) return;
+    const long at = p.cb_off + (long)s * p.K * p.bw;
+    const int C = p.batch * p.le;
+    vq_code_grad(p.idx + (long)s * C, src, p.flat + at, p.flat_grad + at, c_cb, k, C, p.bw, p.le, threadIdx.x & 63);
+}
+
+__global__ __launch_bounds__(64 * CWV) void rvq_bwd_stats_n_k(WnVq p, const int32_t* __restrict__ nstage, float c_enc, int code_blocks,
+                                                              float* __restrict__ stat) {
+    if ((int)blockIdx.x >= p.S * code_blocks) return rvq_bwd_elems_n(p, nstage, c_enc, p.S * code_blocks);
+    int s, k;
+    const float* src;
+    if (!rvq_code_of(p, code_blocks, s, k, src)) return;
+    const int C = p.batch * p.le;
+    vq_code_stats(p.idx + (long)s * C, src, stat + (long)s * p.K * (p.bw + 1), p.flat_grad + p.cb_off + (long)s * p.K * p.bw, k, p.K, C,
+                  p.bw, p.le, threadIdx.x & 63);
+}
+
 // ---- the EMA update.  Both launches form N' with THIS expression, so a code's N' has the same bits in either
 __device__ __forceinline__ float ema_mix(float g, float omg, float old, float fresh) { return fmaf(omg, fresh, g * old); }
 
@@ -512,6 +641,29 @@ __global__ __launch_bounds__(256) void vq_lookup_k(const int32_t* idx, const flo
     }
 }
 
+// per-clip stage counts (wn_rvq_lookup_n): q = the sum of the first n_b stages' rows, ascending; idx [S][frames].  An n_b outside [1, S]
+// or an ACTIVE idx outside [0, K): a NaN frame and *bad, nothing dereferenced; an inactive idx is not looked at
+__global__ __launch_bounds__(256) void vq_lookup_n_k(const int32_t* idx, const int32_t* nstage, const float* cb, float* q_out, int32_t* bad,
+                                                     int S, int K, int bw, int le, long total, long frames) {
+    for (long o = (long)blockIdx.x * 256 + threadIdx.x; o < total; o += (long)gridDim.x * 256) {
+        int fr, j;
+        elem_of(o, bw, le, fr, j);
+        const int n_raw = nstage[fr / le];
+        bool ok = n_raw >= 1 && n_raw <= S;
+        const int n = ok ? n_raw : 0;
+        float q = 0.f;
+        for (int s = 0; s < n; ++s) {
+            const int ix = idx[s * frames + fr];
+            const bool in = (unsigned)ix < (unsigned)K;
+            const float c = in ? cb[((long)s * K + ix) * bw + j] : 0.f;
+            q = s ? q + c : c;
+            ok = ok && in;
+        }
+        q_out[o] = ok ? q : std::numeric_limits<float>::quiet_NaN();
+        if (!ok && bad) *bad = 1;                          // (every writer stores the same value)
+    }
+}
+
 }  // namespace
 
 // The callers (wn_api.hip) have checked the arguments.
@@ -603,6 +755,49 @@ int wn_launch_rvq_bwd(const WnVq& p, float beta, float g_scale, float* stat, hip
         hipLaunchKernelGGL(rvq_bwd_stats_k, grid, dim3(64 * CWV), 0, st, p, c_enc, code_blocks, stat);
     else
         hipLaunchKernelGGL(rvq_bwd_k, grid, dim3(64 * CWV), 0, st, p, c_enc, (float)((double)g_scale * s), code_blocks);
+    WN_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---- quantiser dropout (nstage: batch int32 stage counts on the device): the launches above with the _n kernels, the same grids
+int wn_launch_rvq_fwd_n(const WnVq& p, const int32_t* nstage, hipStream_t st) {
+    if (p.batch <= 0) return 0;
+    if (p.counts) {
+        hipError_t e = hipMemsetAsync(p.counts, 0, sizeof(int32_t) * p.S * p.K, st);
+        if (e != hipSuccess) return wn_set_error(e, __FILE__, __LINE__);
+    }
+    const double n = (double)p.batch * p.le * p.bw;        // the FIXED denominator: vq_loss is the batch expectation
+    hipLaunchKernelGGL(rvq_fwd_n_k, dim3(WN_VQ_PARTIALS), dim3(64 * NWV), 0, st, p, nstage, (float)(1.0 / n));
+    WN_CHECK_LAUNCH();
+    return 0;
+}
+
+int wn_launch_rvq_bwd_n(const WnVq& p, const int32_t* nstage, float beta, float g_scale, float* stat, hipStream_t st) {
+    if (p.batch <= 0) return 0;
+    const double s = 2.0 / ((double)p.batch * p.le * p.bw);
+    const int code_blocks = (p.K + CWV - 1) / CWV;
+    const long total = (long)p.batch * p.le * p.bw;
+    const int elem_blocks = (int)std::min<long>((total + 64 * CWV - 1) / (64 * CWV), 256);
+    const dim3 grid(p.S * code_blocks + elem_blocks);
+    const float c_enc = (float)((double)g_scale * beta * s);
+    if (stat)
+        hipLaunchKernelGGL(rvq_bwd_stats_n_k, grid, dim3(64 * CWV), 0, st, p, nstage, c_enc, code_blocks, stat);
+    else
+        hipLaunchKernelGGL(rvq_bwd_n_k, grid, dim3(64 * CWV), 0, st, p, nstage, c_enc, (float)((double)g_scale * s), code_blocks);
+    WN_CHECK_LAUNCH();
+    return 0;
+}
+
+int wn_launch_vq_lookup_n(const int32_t* idx, const int32_t* nstage, const float* flat, long cb_off, float* q_out, int32_t* bad, int S, int K,
+                          int bw, int le, int batch, hipStream_t st) {
+    if (batch <= 0) return 0;
+    if (bad) {
+        hipError_t e = hipMemsetAsync(bad, 0, sizeof(int32_t), st);
+        if (e != hipSuccess) return wn_set_error(e, __FILE__, __LINE__);
+    }
+    const long total = (long)batch * le * bw;
+    hipLaunchKernelGGL(vq_lookup_n_k, dim3((unsigned)std::min<long>((total + 255) / 256, 1024)), dim3(256), 0, st, idx, nstage, flat + cb_off,
+                       q_out, bad, S, K, bw, le, total, (long)batch * le);
     WN_CHECK_LAUNCH();
     return 0;
 }

@@ -10,7 +10,7 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from . import _lib, guard
+from . import _lib, guard, vq_dropout
 from ._lib import call, ptr
 
 SLACK = 64          # floats in front of every activation buffer
@@ -175,11 +175,27 @@ class VqStats:
 
     With a residual chain of S > 1 stages (wn_rvq_fwd) `part` is (S, partials) and `counts` (S, K): `stage_mse` (S,) holds every
     stage's sum (r_s - q_s)^2 / (C Bw), `mse` is the LAST stage's - the error of q against e -, `vq_loss` = coef x their sum, and
-    `stage_perplexity` / `stage_codes_used` (S,) stand beside `perplexity` / `codes_used`, which describe stage 0."""
+    `stage_perplexity` / `stage_codes_used` (S,) stand beside `perplexity` / `codes_used`, which describe stage 0.
 
-    def __init__(self, part, counts, frames, beta, coef=None):
+    `stage_frames` (S,) = counts.sum(1), the frames that took part in each stage: all of them without quantiser dropout, the ACTIVE
+    ones of a forward with stage counts (wn_rvq_fwd_n, `final_res` given).  There `stage_mse` keeps the fixed denominator C Bw (its
+    sum x coef is vq_loss, the batch expectation), `stage_mse_active` = stage_mse C / stage_frames is the stage's error per frame it
+    saw (0 where it saw none), `stage_perplexity` is taken over the stage's own active frames, and `mse` - q against e - comes from
+    `final_res`, every frame's residual behind ITS last active stage."""
+
+    def __init__(self, part, counts, frames, beta, coef=None, final_res=None):
         self.part, self.counts, self.frames, self.beta = part, counts, frames, beta
         self.coef = 1.0 + beta if coef is None else coef
+        self.final_res = final_res
+
+    @property
+    def stage_frames(self):
+        return self.counts.reshape(-1, self.counts.shape[-1]).sum(dim=1)
+
+    @property
+    def stage_mse_active(self):
+        n = self.stage_frames.to(torch.float32)
+        return torch.where(n > 0, self.stage_mse * float(self.frames) / n.clamp_min(1.0), torch.zeros_like(n))
 
     @property
     def stage_mse(self):
@@ -187,6 +203,9 @@ class VqStats:
 
     @property
     def stage_perplexity(self):
+        if self.final_res is not None:                        # quantiser dropout: every stage over the frames it saw
+            p = self.counts.to(torch.float64) / self.stage_frames.clamp_min(1).to(torch.float64)[:, None]
+            return torch.exp(-(p * torch.log(p.clamp_min(1e-300))).sum(dim=1)).float()
         p = self.counts.reshape(-1, self.counts.shape[-1]).to(torch.float64) / self.frames
         return torch.exp(-(p * torch.log(p.clamp_min(1e-300))).sum(dim=1)).float()
 
@@ -196,6 +215,8 @@ class VqStats:
 
     @property
     def mse(self):
+        if self.final_res is not None:
+            return self.final_res.square().sum() / self.final_res.numel()
         return self.part.sum() if self.part.dim() == 1 else self.part[-1].sum()
 
     @property
@@ -335,9 +356,17 @@ class EngineBase:
         self.n_cond = self.spec.total - self.n_vq - self.n_gcond - w0
 
     # ------------------------------------------------------------------ vector-quantised bottleneck (the autoencoder's engines)
-    def vq_fwd(self, ws, enc, st):
+    def vq_stage_counts(self, stages, B):
+        """`stages` of forward / loss_and_grad -> None (the launches without dropout) or the clips' stage counts as (B,) int32 on the
+        device (music_amd/vq_dropout.py: stage_counts validates on the host, a ValueError before any launch)."""
+        n = vq_dropout.stage_counts(stages, B, self.vq_S if self.vq else 1)
+        return None if n is None else torch.from_numpy(n).to(self.device, non_blocking=True)      # (ONE small copy per step, as stage_classes')
+
+    def vq_fwd(self, ws, enc, st, nstage=None):
         """The pooled encoding e (B, Bw, Le) -> q, every frame its nearest codebook row (wn_vq_fwd, one launch); ws keeps enc_pre = e,
-        vq_idx, vq_counts and the loss partials (fresh tensors per forward: the module hands them out), self.last_vq reads them."""
+        vq_idx, vq_counts and the loss partials (fresh tensors per forward: the module hands them out), self.last_vq reads them.
+        nstage (vq_stage_counts; S > 1 only): quantiser dropout, clip b takes part in its first nstage[b] stages (wn_rvq_fwd_n, still
+        one launch); ws keeps it for the backward, vq_idx holds -1 where a clip took no part."""
         B, _, Le = enc.shape
         dev = self.device
         q = torch.empty_like(enc)
@@ -349,9 +378,15 @@ class EngineBase:
             counts = torch.empty(S, self.vq_K, dtype=torch.int32, device=dev)
             part = torch.empty(S, _lib.VQ_NUM_PARTIALS, dtype=torch.float32, device=dev)
             res = torch.empty((S,) + tuple(enc.shape), dtype=torch.float32, device=dev)
+            if nstage is not None:
+                call("wn_rvq_fwd_n", ptr(enc), ptr(self.flat), self.vq_off, ptr(nstage), ptr(q), ptr(idx), ptr(counts), ptr(res), ptr(part),
+                     S, self.vq_K, self.Bw, Le, B, st)
+                ws.update(enc_pre=enc, vq_idx=idx, vq_counts=counts, vq_part=part, vq_res=res, vq_g=1.0, vq_nstage=nstage)
+                self.last_vq = VqStats(part, counts, B * Le, self.vq_beta, self.vq_loss_coef, final_res=res[S - 1])
+                return q
             call("wn_rvq_fwd", ptr(enc), ptr(self.flat), self.vq_off, ptr(q), ptr(idx), ptr(counts), ptr(res), ptr(part), S, self.vq_K,
                  self.Bw, Le, B, st)
-            ws.update(enc_pre=enc, vq_idx=idx, vq_counts=counts, vq_part=part, vq_res=res, vq_g=1.0)
+            ws.update(enc_pre=enc, vq_idx=idx, vq_counts=counts, vq_part=part, vq_res=res, vq_g=1.0, vq_nstage=None)
             self.last_vq = VqStats(part, counts, B * Le, self.vq_beta, self.vq_loss_coef)
             return q
         idx = torch.empty(B, Le, dtype=torch.int32, device=dev)
@@ -366,6 +401,13 @@ class EngineBase:
         """d_q (what wn_cond_proj_bwd wrote as d enc) -> d e in place, and the codebook's gradient into the tail of flat_grad (wn_vq_bwd,
         one launch); ws["vq_g"]: the upstream scalar on vq_loss (1 in the fused step, autograd's in the module's backward)."""
         B, _, Le = d_q.shape
+        if self.vq_S > 1 and ws.get("vq_nstage") is not None:
+            # the forward ran with stage counts: the same launch over the ACTIVE stages of every frame (idx = -1 matches no code)
+            head = (ptr(ws["enc_pre"]), ptr(ws["vq_idx"]), ptr(ws["vq_res"]), ptr(ws["vq_nstage"]), ptr(d_q), ptr(self.flat), self.vq_off,
+                    self.vq_beta, float(ws.get("vq_g", 1.0)), ptr(d_q), ptr(self.flat_grad))
+            if self.vq_ema:
+                return call("wn_rvq_bwd_stats_n", *head, ptr(self.vq_stat), self.vq_S, self.vq_K, self.Bw, Le, B, st)
+            return call("wn_rvq_bwd_n", *head, self.vq_S, self.vq_K, self.Bw, Le, B, st)
         if self.vq_S > 1:
             head = (ptr(ws["enc_pre"]), ptr(ws["vq_idx"]), ptr(ws["vq_res"]), ptr(d_q), ptr(self.flat), self.vq_off, self.vq_beta,
                     float(ws.get("vq_g", 1.0)), ptr(d_q), ptr(self.flat_grad))
@@ -384,7 +426,8 @@ class EngineBase:
         return self.vq_beta if self.vq_ema else 1.0 + self.vq_beta
 
     def vq_codes_of(self, ws):
-        """The codes of a forward's workspace as the module hands them out: (B, Le) int64, (B, S, Le) with S > 1 stages."""
+        """The codes of a forward's workspace as the module hands them out: (B, Le) int64, (B, S, Le) with S > 1 stages - with -1
+        where a forward with stage counts left a clip out of a stage, as they are."""
         idx = ws["vq_idx"].to(torch.int64)
         return idx if self.vq_S == 1 else idx.permute(1, 0, 2)
 
@@ -429,11 +472,26 @@ class EngineBase:
 
     def vq_lookup(self, codes):
         """codes (B, Le) integer -> q (B, Bw, Le) out of the codebook (wn_vq_lookup); a code outside [0, K) raises.  With S > 1 stages:
-        codes (B, n, Le), 1 <= n <= S, the first n stages' codes -> the sum of their rows in stage order (wn_rvq_lookup)."""
+        codes (B, n, Le), 1 <= n <= S, the first n stages' codes -> the sum of their rows in stage order (wn_rvq_lookup).  Codes with
+        -1 in a clip's absent stages (what a forward with stage counts hands out; vq_dropout.counts_of_codes checks the pattern on the
+        host) -> every clip the sum of ITS stages' rows (wn_rvq_lookup_n)."""
         if self.vq_S > 1:
             if codes.dim() != 3 or not 1 <= codes.shape[1] <= self.vq_S:
                 raise ValueError("music_amd: vq_stages = %d: codes must be (B, n, Le) with 1 <= n <= %d, not %s"
                                  % (self.vq_S, self.vq_S, tuple(codes.shape)))
+            nstage = None if codes.is_floating_point() else vq_dropout.counts_of_codes(codes, self.vq_S)
+            if nstage is not None:
+                B, n, Le = codes.shape
+                full = torch.full((self.vq_S, B, Le), -1, dtype=torch.int32, device=self.device)
+                full[:n] = codes.to(device=self.device, dtype=torch.int32).permute(1, 0, 2)
+                q = torch.empty(B, self.Bw, Le, dtype=torch.float32, device=self.device)
+                bad = torch.zeros(1, dtype=torch.int32, device=self.device)
+                nstage = torch.from_numpy(nstage).to(self.device)
+                call("wn_rvq_lookup_n", ptr(full), ptr(nstage), ptr(self.flat), self.vq_off, ptr(q), ptr(bad), self.vq_S, self.vq_K, self.Bw, Le,
+                     B, _lib.stream())
+                if int(bad.item()):
+                    raise ValueError("music_amd: a code lies outside [0, %d)" % self.vq_K)
+                return q
             codes = codes.to(device=self.device, dtype=torch.int32).permute(1, 0, 2).contiguous()
             n, B, Le = codes.shape
             q = torch.empty(B, self.Bw, Le, dtype=torch.float32, device=self.device)

@@ -187,6 +187,7 @@ class _Collate:
             batch["audio_class"] = torch.tensor([it["audio_class"] for it in items], dtype=torch.int64)
         if self.shard is not None:
             batch["dp_scale"] = scale
+            batch["first_clip"] = lo             # this shard's first clip in the global batch (quantiser dropout draws per GLOBAL clip)
         return batch
 
 

@@ -27,13 +27,13 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 try:
-    from . import _lib, _losshook
+    from . import _lib, _losshook, vq_dropout
     from ._lib import call, ptr
     from .engine_base import SLACK, PAD_BACK, EngineBase, SlabPlan, WorkspaceHold, _Spec, _pad
     from .packs import PackSet, causal_mats, diag, epilogue_mats, full, gated_mats, pack_positions, pair_mats, transposed
     from .stack import Cond, EpiBias, GatedStack, SkipEpilogue, enc_resblock_bwd_pq, enc_resblock_fwd, hand_over
 except ImportError:
-    from music_amd import _lib, _losshook
+    from music_amd import _lib, _losshook, vq_dropout
     from music_amd._lib import call, ptr
     from music_amd.engine_base import SLACK, PAD_BACK, EngineBase, SlabPlan, WorkspaceHold, _Spec, _pad
     from music_amd.packs import PackSet, causal_mats, diag, epilogue_mats, full, gated_mats, pack_positions, pair_mats, transposed
@@ -215,15 +215,18 @@ class _AutoencoderEngine(EngineBase):
     def _lay(self, t, i, ch, ws):
         return ptr(t, SLACK + i * ws["B"] * ch * ws["pitch"])
 
-    def forward(self, x, cond=None, want_probs=True, encode_only=False, classes=None):
+    def forward(self, x, cond=None, want_probs=True, encode_only=False, classes=None, stages=None):
         """cond: list of N+1 (weight (C,Bw,1), bias (C,)) CPU tensors (see wavenet_autoencoder.forward); None with learned
         conditioning, whose projections are parameters of the flat buffer.
         classes: one integer per clip with global class conditioning (EngineBase.stage_classes), else None.
+        stages: quantiser dropout of a residual vq bottleneck - None, an int or one int per clip in [1, vq_stages]
+        (EngineBase.vq_stage_counts); not None: every clip is quantised with its first n stages (wn_rvq_fwd_n).
         want_probs=False stops at the pre-softmax logits in ws["O"] (the fused training step); encode_only=True behind the pooled
         (and, with a vq bottleneck, quantised) encoding: (None, enc, ws), nothing of the decoder runs."""
         self._check_cond(cond)
         B, Q, T = x.shape
         cls = None if encode_only and classes is None else self.stage_classes(classes, B)      # (the encoder takes no classes)
+        nstage = self.vq_stage_counts(stages, B)
         W = T - self.rf + 1
         Le = W // self.pool
         if Le < 1:
@@ -276,7 +279,7 @@ class _AutoencoderEngine(EngineBase):
         enc = torch.empty(B, self.Bw, Le, dtype=torch.float32, device=self.device)
         call("wn_avgpool", E, BwP * pitch, pitch, lo, self.pool, Le, self.Bw, ptr(enc), self.Bw * Le, Le, B, st)
         if self.vq:                                           # every frame -> its nearest codebook row: the decoder sees q
-            enc = self.vq_fwd(ws, enc, st)
+            enc = self.vq_fwd(ws, enc, st, nstage)
         if encode_only:
             return None, enc, ws
 
@@ -426,12 +429,12 @@ class _AutoencoderEngine(EngineBase):
         ws["bwd"] = bw
         return bw
 
-    def loss_and_grad(self, x, target, cond=None, objective=None, classes=None):
+    def loss_and_grad(self, x, target, cond=None, objective=None, classes=None, stages=None):
         """Fused training step body (the autoencoder counterpart of engine.loss_and_grad): forward to the logits, ONE
         kernel for chunk softmax + CrossEntropyLoss on the probabilities (wavenet_autoencoder/train.py:146-160) + both
         backward steps, then the backward.  Returns the loss (0-d device tensor); gradients land in self.flat_grad.
-        objective: None = self.objective (EngineBase)."""
-        return self._throttled(lambda: self._fused_tail(self.forward(x, cond, want_probs=False, classes=classes)[2], target,
+        objective: None = self.objective (EngineBase).  stages: as in forward (the backward then runs wn_rvq_bwd_n / _bwd_stats_n)."""
+        return self._throttled(lambda: self._fused_tail(self.forward(x, cond, want_probs=False, classes=classes, stages=stages)[2], target,
                                                        objective=objective))
 
     def backward_from_dlogits(self, ws):
@@ -610,7 +613,7 @@ CONDITIONING = ("random", "learned")     # the decoder's conditioning projection
 
 class _AutoencoderFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, net, grad_on, wave_sample, cond, classes, *params):
+    def forward(ctx, net, grad_on, wave_sample, cond, classes, stages, *params):
         eng = net._engine_for(wave_sample.device)
         x = wave_sample.detach()
         if x.dtype != torch.float32 or not x.is_contiguous():
@@ -619,7 +622,7 @@ class _AutoencoderFunction(torch.autograd.Function):
             tag = getattr(wave_sample, "_wn_codes", None)        # one-hot built from codes (see _AutoencoderEngine.forward)
             if tag is not None and wave_sample._version == tag[2]:
                 x._wn_codes = (tag[0], tag[1], x._version, tag[3])
-        probs, enc, ws = eng.forward(x, cond, classes=classes)
+        probs, enc, ws = eng.forward(x, cond, classes=classes) if stages is None else eng.forward(x, cond, classes=classes, stages=stages)
         net.last_encoding = enc
         ctx.eng, ctx.ws, ctx.gen = eng, ws, ws["gen"]
         ctx.loss_hook = net._last_hook = _losshook.make(eng, ws, grad_on)
@@ -652,7 +655,7 @@ class _AutoencoderFunction(torch.autograd.Function):
             o, shp = eng.spec.off[name], eng.spec.shape[name]
             grads.append(g[o:o + int(np.prod(shp))].view(shp))
         din = eng.input_grad(ws) if ctx.needs_input_grad[2] else None       # (the reference's two causal nn.Conv1d give it, model1.py:137,158)
-        return (None, None, din, None, None) + tuple(grads)
+        return (None, None, din, None, None, None) + tuple(grads)
 
 
 class wavenet_autoencoder(nn.Module):
@@ -660,8 +663,13 @@ class wavenet_autoencoder(nn.Module):
     def __init__(self, filter_width, quantization_channel, dilations, en_residual_channel, en_dilation_channel,
                  en_bottleneck_width, en_pool_kernel_size, de_residual_channel, de_dilation_channel,
                  de_skip_channel, use_bias, conditioning="random", bottleneck="continuous", vq_codes=512, vq_beta=0.25,
-                 vq_update="gradient", vq_decay=0.99, vq_eps=1e-5, vq_restart=0.0, global_classes=0, global_channels=0, vq_stages=1):
+                 vq_update="gradient", vq_decay=0.99, vq_eps=1e-5, vq_restart=0.0, global_classes=0, global_channels=0, vq_stages=1,
+                 vq_stage_dropout=0.0):
         super(wavenet_autoencoder, self).__init__()
+        if isinstance(vq_stage_dropout, bool) or not isinstance(vq_stage_dropout, (int, float)) or not 0.0 <= vq_stage_dropout <= 1.0:
+            raise ValueError("music_amd.wavenet_autoencoder: vq_stage_dropout must be a number in [0, 1], not %r" % (vq_stage_dropout,))
+        if vq_stage_dropout > 0 and not (isinstance(vq_stages, int) and not isinstance(vq_stages, bool) and vq_stages > 1):
+            raise ValueError("music_amd.wavenet_autoencoder: vq_stage_dropout > 0 requires vq_stages > 1 (there is no stage to drop)")
         if isinstance(vq_stages, bool) or not isinstance(vq_stages, int) or not 1 <= vq_stages <= _lib.RVQ_MAX_STAGES:
             raise ValueError("music_amd.wavenet_autoencoder: vq_stages must be an integer in [1, %d], not %r"
                              % (_lib.RVQ_MAX_STAGES, vq_stages))
@@ -711,6 +719,12 @@ class wavenet_autoencoder(nn.Module):
         self.conditioning = conditioning
         self.bottleneck, self.vq_num_codes, self.vq_beta = bottleneck, int(vq_codes), float(vq_beta)
         self.vq_stages = vq_stages       # residual quantisation: stage s quantises what the stages before it left over, with rows [sK, (s+1)K)
+        # quantiser dropout (music_amd/vq_dropout.py): in training mode a share p of the clips draws its stage count from 1 .. S.  No
+        # parameter, no buffer: state_dict is unchanged.  The draw hashes (vq_dropout_seed, the module's call counter, the clip's index);
+        # a training loop that knows its global step and clip offset passes stages= itself (ae_train)
+        self.vq_stage_dropout = float(vq_stage_dropout)
+        self.vq_dropout_seed = 0
+        self.vq_dropout_calls = 0
         self.vq_update, self.vq_decay, self.vq_eps, self.vq_restart = vq_update, float(vq_decay), float(vq_eps), float(vq_restart)
         self.global_classes, self.global_channels = global_classes, global_channels
         self.filter_width = filter_width
@@ -788,6 +802,8 @@ class wavenet_autoencoder(nn.Module):
         self.__dict__.setdefault("conditioning", "random")       # (a module pickled before the attribute existed)
         self.__dict__.setdefault("bottleneck", "continuous")
         self.__dict__.setdefault("vq_stages", 1)
+        for k, v in (("vq_stage_dropout", 0.0), ("vq_dropout_seed", 0), ("vq_dropout_calls", 0)):
+            self.__dict__.setdefault(k, v)
         for k, v in (("vq_update", "gradient"), ("vq_decay", 0.99), ("vq_eps", 1e-5), ("vq_restart", 0.0)):
             self.__dict__.setdefault(k, v)
         for k in ("vq_loss", "vq_codes", "last_encoding_pre", "last_vq"):
@@ -978,7 +994,21 @@ class wavenet_autoencoder(nn.Module):
             self._engine = eng
         return eng
 
-    def forward(self, wave_sample, classes=None):
+    def draw_stages(self, batch_size, step=None, first_clip=0):
+        """The stage counts quantiser dropout gives `batch_size` clips (music_amd/vq_dropout.py: draw_stages with this module's
+        vq_dropout_seed and vq_stage_dropout), or None where it is off.  step=None: the module's own call counter, which then advances."""
+        p = getattr(self, "vq_stage_dropout", 0.0)
+        if not p > 0:
+            return None
+        if step is None:
+            step = self.vq_dropout_calls
+            self.vq_dropout_calls += 1
+        return vq_dropout.draw_stages(getattr(self, "vq_dropout_seed", 0), step, first_clip, batch_size, self.vq_stages, p)
+
+    def forward(self, wave_sample, classes=None, stages=None):
+        """stages: quantiser dropout of a residual vq bottleneck - None, an int n (every clip is quantised with its first n stages) or
+        one int per clip, each in [1, vq_stages].  None in training mode with vq_stage_dropout > 0: the module draws them (draw_stages);
+        None otherwise, eval mode included: all stages."""
         batch_size, original_channels, seq_len = wave_sample.size()
         output_width = seq_len - self.receptive_field + 1
         if output_width <= 0:
@@ -986,10 +1016,14 @@ class wavenet_autoencoder(nn.Module):
         if (classes is None) == bool(getattr(self, "global_classes", 0)):      # (before the engine is built and anything is drawn)
             raise ValueError("music_amd.wavenet_autoencoder: global_classes = %d: classes must be %s"
                              % (getattr(self, "global_classes", 0), "None" if classes is not None else "given, one integer per clip"))
+        if stages is None and self.training:
+            stages = self.draw_stages(batch_size)
+        # (refused here, before the engine is built: a bool, a float, a wrong length, a value outside [1, vq_stages])
+        stages = vq_dropout.stage_counts(stages, batch_size, getattr(self, "vq_stages", 1))
         self._engine_for(wave_sample.device)
         cond = self.engine_cond()
         self._last_hook = None
-        out = _AutoencoderFunction.apply(self, torch.is_grad_enabled(), wave_sample, cond, classes, *list(self.parameters()))
+        out = _AutoencoderFunction.apply(self, torch.is_grad_enabled(), wave_sample, cond, classes, stages, *list(self.parameters()))
         if getattr(self, "bottleneck", "continuous") == "vq":
             out, self.vq_loss = out
         hook, self._last_hook = self._last_hook, None

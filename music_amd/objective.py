@@ -36,7 +36,7 @@ def _dense_input(wave_sample):
     return x
 
 
-def _forward_logits(net, wave_sample, classes=None):
+def _forward_logits(net, wave_sample, classes=None, stages=None):
     """The module's forward up to the pre-softmax logits: (engine, workspace with the logits in ws["O"]).  The autoencoder draws its
     per-forward conditioning convs from the global RNG, as its own forward does (learned ones are parameters: nothing is drawn)."""
     if wave_sample.dim() != 3:
@@ -46,9 +46,12 @@ def _forward_logits(net, wave_sample, classes=None):
     eng = net._engine_for(wave_sample.device)
     x = _dense_input(wave_sample)
     if hasattr(net, "engine_cond"):
-        _, enc, ws = eng.forward(x, net.engine_cond(), want_probs=False, classes=classes)
+        kw = {} if stages is None else {"stages": stages}       # (quantiser dropout of a residual vq bottleneck: music_amd/vq_dropout.py)
+        _, enc, ws = eng.forward(x, net.engine_cond(), want_probs=False, classes=classes, **kw)
         net.last_encoding = enc
     else:
+        if stages is not None:
+            raise ValueError("music_amd.objective: stages are the autoencoder's (quantiser dropout)")
         eng.pack_weights()
         ws = eng.forward_logits(x)
     return eng, ws
@@ -66,8 +69,8 @@ class _NLLFunction(torch.autograd.Function):
     backward_from_dlogits scaled by the upstream scalar."""
 
     @staticmethod
-    def forward(ctx, net, grad_on, wave_sample, target, classes, *params):
-        eng, ws = _forward_logits(net, wave_sample, classes)
+    def forward(ctx, net, grad_on, wave_sample, target, classes, stages, *params):
+        eng, ws = _forward_logits(net, wave_sample, classes, stages)
         need = grad_on and any(ctx.needs_input_grad)
         eng.step_nll(ws, _flat_target(target, ws), eng._bwd_workspace(ws)["dO"] if need else None)
         ctx.eng, ctx.ws, ctx.gen = eng, ws, ws["gen"]
@@ -99,7 +102,7 @@ class _NLLFunction(torch.autograd.Function):
             o, shp = eng.spec.off[name], eng.spec.shape[name]
             grads.append(g[o:o + int(np.prod(shp))].view(shp))
         din = eng.input_grad(ws) * dloss if ctx.needs_input_grad[2] else None
-        return (None, None, din, None, None) + tuple(grads)
+        return (None, None, din, None, None, None) + tuple(grads)
 
 
 def _params(net):
@@ -107,14 +110,15 @@ def _params(net):
     return [p for _, p in net._named_ref_params()] if hasattr(net, "_named_ref_params") else list(net.parameters())
 
 
-def nll_loss(net, x, target, classes=None):
+def nll_loss(net, x, target, classes=None, stages=None):
     """Mean negative log-likelihood (nats per sample) of `target` (B, W) or (B W,) int64 under the per-timestep softmax of
     net's logits for the one-hot x (B, Q, T): a 0-d tensor whose backward() gives the parameter gradients (and the input's, when it
     requires grad).  A target outside [0, Q) makes the loss NaN.  classes: one integer per clip for an autoencoder with global class
-    conditioning (required there, refused elsewhere)."""
+    conditioning (required there, refused elsewhere).  stages: the clips' stage counts under quantiser dropout, as the autoencoder's
+    forward takes them (None: all stages - this function draws nothing)."""
     if classes is not None and not hasattr(net, "engine_cond"):
         raise ValueError("music_amd.objective: classes are the autoencoder's (global class conditioning)")
-    out = _NLLFunction.apply(net, torch.is_grad_enabled(), x, target, classes, *_params(net))
+    out = _NLLFunction.apply(net, torch.is_grad_enabled(), x, target, classes, stages, *_params(net))
     if isinstance(out, tuple):                                  # a vq autoencoder: the caller adds net.vq_loss
         out, net.vq_loss = out
     return out
@@ -128,17 +132,18 @@ def step_probs(net, x, classes=None):
         return eng.step_probs(ws)
 
 
-def score(net, x_or_codes, target, scrambled=False, classes=None):
+def score(net, x_or_codes, target, scrambled=False, classes=None, stages=None):
     """Held-out figures of net on one batch, forward only.  x_or_codes: the one-hot (B, Q, T) float, or the integer codes (B, T) -
     then the one-hot is laid out canonical, or as the loader scrambles it with `scrambled`.  Returns device tensors of
     shape (B,), float64: "nll" (mean nats per sample of each clip), "bits" (nll / ln 2) and "accuracy" (share of samples whose
-    first-index argmax is the target); the per-clip means are taken on the device, nothing is read back."""
+    first-index argmax is the target); the per-clip means are taken on the device, nothing is read back.  stages: score a residual vq
+    autoencoder with the first n stages (an int, or one per clip) - the coarser code's figures."""
     with torch.no_grad():
         x = x_or_codes
         if x.dim() == 2:
             q = getattr(net, "quantization_channels", None) or net.quantization_channel
             x = faster_audio_data.onehot_device(x, q, scrambled)
-        eng, ws = _forward_logits(net, x, classes)
+        eng, ws = _forward_logits(net, x, classes, stages)
         row_nll, row_hit = eng.score_logits(ws, _flat_target(target, ws))
         B, W = ws["B"], ws["W"]
         nll = row_nll.view(B, W).double().mean(1)

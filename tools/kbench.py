@@ -384,6 +384,127 @@ def rvq_bench(reps, alternations=6):
     print(json.dumps(res))
 
 
+def rvq_drop_bench(reps, alternations=6):
+    """`rvq_drop`: quantiser dropout.  (a) wn_rvq_fwd_n / wn_rvq_bwd_n with every clip on all S stages against wn_rvq_fwd / wn_rvq_bwd, and
+    with the stage counts of a p = 1 draw (uniform over 1 .. S), at config 4's shape (B 8, Bw 64, Le 25, K 512) and the shipped
+    autoencoder's (B 4, Bw 512, Le 32, K 512), S = 4 and 8, HIP events around `reps` rounds; (b) the fused config-4 step at S = 4 with
+    vq_stage_dropout = 0.5 (fresh draws every step, as ae_train makes them) against 0.  Everything alternated `alternations` times on
+    one device: medians and spreads.  Written to profiles/rvq_drop_kbench.json."""
+    import time
+    from music_amd import _lib, vq_dropout
+    from music_amd._lib import call, ptr
+    from music_amd.model1 import wavenet_autoencoder
+    st = _lib.stream()
+    res = {"alternations": alternations}
+    rng = np.random.default_rng(0)
+    shapes = {"config4": (8, 64, 25, 512), "shipped": (4, 512, 32, 512)}
+    stages = (4, 8)
+    f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device="cuda")
+    i32 = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device="cuda")
+    bufs = {}
+    for name, (B, Bw, Le, K) in shapes.items():
+        for S in stages:
+            enc = torch.from_numpy(rng.standard_normal((B, Bw, Le)).astype(np.float32)).cuda()
+            flat = torch.from_numpy(np.concatenate([rng.standard_normal(K * Bw) * 0.8 ** s for s in range(S)]).astype(np.float32)).cuda()
+            drawn = vq_dropout.draw_stages(0, 0, 0, B, S, 1.0)
+            bufs[name, S] = dict(enc=enc, flat=flat, q=f32(B, Bw, Le), idx=i32(S, B, Le), counts=i32(S, K), res=f32(S, B, Bw, Le),
+                                 part=f32(S, _lib.VQ_NUM_PARTIALS), d=torch.randn_like(enc), d_out=f32(B, Bw, Le), grad=torch.empty_like(flat),
+                                 n_all=torch.full((B,), S, dtype=torch.int32, device="cuda"), n_drawn=torch.from_numpy(drawn).cuda())
+            res["drawn_counts_%s_s%d" % (name, S)] = drawn.tolist()
+
+    def one(name, S, which, form):
+        B, Bw, Le, K = shapes[name]
+        b = bufs[name, S]
+        n = None if form == "plain" else b["n_all" if form == "all" else "n_drawn"]
+        if which == "fwd" and n is None:
+            call("wn_rvq_fwd", ptr(b["enc"]), ptr(b["flat"]), 0, ptr(b["q"]), ptr(b["idx"]), ptr(b["counts"]), ptr(b["res"]), ptr(b["part"]), S, K,
+                 Bw, Le, B, st)
+        elif which == "fwd":
+            call("wn_rvq_fwd_n", ptr(b["enc"]), ptr(b["flat"]), 0, ptr(n), ptr(b["q"]), ptr(b["idx"]), ptr(b["counts"]), ptr(b["res"]),
+                 ptr(b["part"]), S, K, Bw, Le, B, st)
+        elif n is None:
+            call("wn_rvq_bwd", ptr(b["enc"]), ptr(b["idx"]), ptr(b["res"]), ptr(b["d"]), ptr(b["flat"]), 0, 0.25, 1.0, ptr(b["d_out"]),
+                 ptr(b["grad"]), S, K, Bw, Le, B, st)
+        else:
+            call("wn_rvq_bwd_n", ptr(b["enc"]), ptr(b["idx"]), ptr(b["res"]), ptr(n), ptr(b["d"]), ptr(b["flat"]), 0, 0.25, 1.0, ptr(b["d_out"]),
+                 ptr(b["grad"]), S, K, Bw, Le, B, st)
+
+    def rounds(key, n):
+        name, S, which, form = key
+        if which == "bwd":                                                    # the backward reads the idx and res of ITS forward
+            one(name, S, "fwd", form)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        torch.cuda.synchronize()
+        ev[0].record()
+        for _ in range(n):
+            one(*key)
+        ev[1].record()
+        torch.cuda.synchronize()
+        return ev[0].elapsed_time(ev[1]) / n * 1e3
+    times = {(n, S, w, f): [] for n in shapes for S in stages for w in ("fwd", "bwd") for f in ("plain", "all", "drawn")}
+    for key in times:
+        rounds(key, 10)                                                       # warm
+    for _ in range(alternations):
+        for key in times:
+            times[key].append(rounds(key, max(reps, 50)))
+    for (n, S, w, f), v in times.items():
+        label = "%s_%s_s%d_%s_us" % ({"plain": "wn_rvq", "all": "wn_rvq_n_all", "drawn": "wn_rvq_n_drawn"}[f], w, S, n)
+        res[label], res[label + "_spread"] = _median_spread(v)
+    for n in shapes:
+        for S in stages:
+            for w in ("fwd", "bwd"):
+                plain = res["wn_rvq_%s_s%d_%s_us" % (w, S, n)]
+                for f in ("all", "drawn"):
+                    res["ratio_n_%s_over_plain_%s_s%d_%s" % (f, w, S, n)] = round(res["wn_rvq_n_%s_%s_s%d_%s_us" % (f, w, S, n)] / plain, 4)
+    # ---- the fused config-4 step at S = 4, p = 0.5 against p = 0
+    cfg = dict(filter_width=2, quantization_channel=256, dilations=CFG["dilations"], en_residual_channel=64, en_dilation_channel=64,
+               en_bottleneck_width=64, en_pool_kernel_size=512, de_residual_channel=64, de_dilation_channel=64, de_skip_channel=256,
+               use_bias=False, conditioning="learned", bottleneck="vq", vq_codes=512, vq_stages=4)
+    from music_amd.faster_audio_data import onehot_device
+    x = onehot_device(torch.from_numpy(rng.integers(0, 256, size=(B_LOCAL, T)).astype(np.int32)).cuda(), 256, True)
+    engs = {}
+    for p in (0.0, 0.5):
+        torch.manual_seed(0)
+        net = wavenet_autoencoder(vq_stage_dropout=p, **cfg).cuda()
+        eng = net._engine_for(torch.device("cuda", 0))
+        eng.adam_init(lr=1e-4)
+        with torch.no_grad():
+            _, _, ws0 = eng.forward(x, None, want_probs=False, encode_only=True)
+        net.init_codebook(ws0["enc_pre"], seed=0)                             # (codes in use, as in a trained model)
+        engs[p] = (net, eng)
+    W = T - engs[0.0][0].receptive_field + 1
+    target = torch.from_numpy(rng.integers(0, 256, size=(B_LOCAL * W,)).astype(np.int64)).cuda()
+    step_no = {p: 0 for p in engs}
+
+    def steps(p, n):
+        net, eng = engs[p]
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            drawn = net.draw_stages(B_LOCAL, step=step_no[p])                 # None at p = 0: the launches without dropout
+            step_no[p] += 1
+            loss = eng.loss_and_grad(x, target, None, stages=drawn)
+            eng.adam_step()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / n * 1e3, float(loss)
+    for p in engs:
+        steps(p, 5)
+    step_ms = {p: [] for p in engs}
+    for _ in range(alternations):
+        for p in engs:
+            ms, loss = steps(p, max(reps, 20))
+            step_ms[p].append(ms)
+            res["fused_step_loss_p%g" % p] = round(loss, 5)
+    for p, v in step_ms.items():
+        res["fused_step_ms_p%g" % p], res["fused_step_ms_p%g_spread" % p] = _median_spread(v)
+    res["fused_step_ms_p0.5_minus_p0"] = round(res["fused_step_ms_p0.5"] - res["fused_step_ms_p0"], 3)
+    res["fused_step_ms_by_alternation"] = {"p%g" % p: [round(t, 3) for t in v] for p, v in step_ms.items()}
+    stats = engs[0.5][1].last_vq
+    res["stage_frames_last_step_p0.5"] = [int(v) for v in stats.stage_frames.tolist()]
+    _write_profile("rvq_drop_kbench.json", res)
+    print(json.dumps(res))
+
+
 def gcond_bench(reps, alternations=6, E=64, n_cls=8):
     """`gcond`: global class conditioning.  (a) wn_gcond_proj_fwd / _bwd beside wn_cond_proj_fwd / _bwd, whose place they take, alone
     at config 4's shape and at the shipped autoencoder's with E = 64 channels, HIP events around `reps` calls; (b) the fused config-4
@@ -488,7 +609,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--precision", default="f16x3,bf16x3")
     ap.add_argument("--overlap", type=int, default=1)
-    ap.add_argument("--parent", default=None, help="gcond / rvq: a built checkout of the parent commit, for profiles/<what>_bench_unset.json")
+    ap.add_argument("--parent", default=None, help="gcond / rvq / rvq_drop: a built checkout of the parent commit, for profiles/<what>_bench_unset.json")
     args = ap.parse_args()
     if args.what == "gcond":
         if args.parent:
@@ -498,6 +619,10 @@ def main():
         if args.parent:
             bench_unset(os.path.abspath(args.parent), profile="rvq_bench_unset.json", keys="vq_stages")
         return rvq_bench(args.reps)
+    if args.what == "rvq_drop":
+        if args.parent:
+            bench_unset(os.path.abspath(args.parent), profile="rvq_drop_bench_unset.json", keys="vq_stage_dropout")
+        return rvq_drop_bench(args.reps)
     if args.what == "vq":
         return vq_bench(args.reps)
     if args.what == "vq_ema":
