@@ -101,8 +101,17 @@ int wn_resblock_fwd(const float* x_in, float* x_out, float* z_out, int64_t x_bst
 /* Fused gated residual block, backward recompute half (autograd of model.py:118-124, SURVEY
  * Appendix B): recomputes f,g,z from x_in; dz = Wd^T dy (+ dz_crop on t >= z_lo);
  * writes dfg = [df; dg] (2*ch rows) and z (ch rows) on [t_lo,t_hi).  dy may be NULL; z may be NULL
- * (the caller kept the forward's z, stored with z_lo = t_lo).
- * cond*: the conditioning table of wn_resblock_fwd (the recompute adds it as well); NULL = none. */
+ * (the caller kept the forward's z, stored with z_lo = t_lo): dfg then has the same bits and z is not touched.
+ * cond*: the conditioning table of wn_resblock_fwd (the recompute adds it as well); NULL = none.
+ * dy has x_in's layout: its clip stride is x_bstride as well.  All 2*ch rows of dfg and all ch rows of z are written on the
+ * window, the padded rows (zero weights, no bias at rows >= n_f, zero table rows) as exact zeros; nothing else is touched.
+ * Supported (mode_fwd, mode_bwd): (f16x3, bf16x3), (f16x1, bf16x1), (bf16x3, bf16x3), (bf16x1, bf16x1), else -2; ch other than
+ * 32 | 64: -3; pitch no multiple of 4: -4; t_hi <= t_lo or batch <= 0: returns 0 and writes nothing.
+ * The launch tiles the columns from t_lo & ~63 in steps of 512 and READS the rows of x_in (also d columns in front of each
+ * tile, so up to 63 floats in front of the first row when t_lo - d < 64: the activation layout's front slack), dy and dz over
+ * whole tiles, so the tiles must lie inside the row pitch.  Values that do not count are ignored, NaN included: x_in at columns
+ * < t_lo - d and >= t_hi, dy outside [t_lo, t_hi), dz at columns < z_lo and >= t_hi (all of it when z_lo >= t_hi), bias
+ * entries at rows >= n_f, table columns >= cond_le (stretch: buckets beyond cond_le - 1 clamp to the last one). */
 int wn_resblock_bwd(const float* x_in, const float* dy, const float* dz, float* dfg, float* z,
                     int64_t x_bstride, int64_t dz_bstride, int64_t dfg_bstride, int64_t z_bstride,
                     int pitch, const uint16_t* wfg, const uint16_t* wdT, const float* bias_f,
@@ -284,7 +293,12 @@ int wn_wgrad_slabs(int t_lo, int t_hi, int chunk, int batch);
  * in[b][q][s-1+tap] becomes a scatter of dx columns - dx (ch rows) is read once, the 4*q*t bytes per clip of dense
  * one-hot are not read at all.  Writes wn_causal_wgrad_codes_slabs(t, batch) slabs [ch][2q] (columns = tap 0 rows |
  * tap 1 rows, the layout wn_wgrad gives the same product); sum them with wn_reduce_slabs.  Bit-reproducible.
- * dx_q != NULL: the data gradient comes as the unshifted pair wn_resblock_bwd_pq writes, dx[s] (s >= p_lo) + dx_q[s + dn].
+ * dx_q != NULL: the data gradient comes as the unshifted pair wn_resblock_bwd_pq writes, dx[s] (s >= p_lo) + dx_q[s + dn]
+ * (s + dn < t); the same bits as the plain form on the float32 sum of the pair.
+ * s runs over [1, t): dx at column 0 and at columns >= t does not count (NaN included), nor do dx below p_lo and dx_q at
+ * columns < 1 + dn or >= t in the pair form.  A code outside [0, q) sets no one (wn_onehot's rule) and contributes nothing.
+ * Every element of every slab is written, zeros included (t == 1: the slabs are all zeros); q other than 256: -4, ch other
+ * than 32 | 64: -3; t <= 0 or batch <= 0: returns 0 and writes nothing.
  * Arbitrary float inputs (faster_audio_data.py hands the model a dense tensor) keep using wn_wgrad. */
 int wn_causal_wgrad_codes(const int32_t* codes, int scrambled, const float* dx, const float* dx_q, int dn, int p_lo,
                           int64_t dx_bstride, int pitch, int ch, int q, int t, int batch, float* slab, wn_stream_t stream);
@@ -292,7 +306,10 @@ int wn_causal_wgrad_codes_slabs(int t, int batch);
 /* Forward of the causal layer (wavenet/model.py:104) from the same codes, without the one-hot tensor:
  * x0[b][r][s] = bias[r] + sum over the ones (q, s-1) of W[r][q][0] + sum over the ones (q, s) of W[r][q][1], s in [1, t).
  * wt = the layer's weight re-laid as [tap][q][ch] floats (ch contiguous, zero-padded to ch); n_rows = real channel count;
- * bias may be NULL.  Sums of exact fp32 weights in a fixed order (bit-reproducible). */
+ * bias may be NULL.  Sums of exact fp32 weights in a fixed order (bit-reproducible).
+ * Only rows < n_rows x columns [1, t) of every clip are written (the padded rows are NOT touched).  A code outside [0, q)
+ * sets no one and contributes nothing; in the scrambled layout a column holds as many ones as the reshape puts there.
+ * q other than 256: -4, ch other than 32 | 64: -3; t <= 1 or batch <= 0: returns 0 and writes nothing. */
 int wn_causal_fwd_codes(const int32_t* codes, int scrambled, const float* wt, const float* bias, int n_rows, float* x0,
                         int64_t x_bstride, int pitch, int ch, int q, int t, int batch, wn_stream_t stream);
 /* desc[op] = {vec_start, slab_off, n_slabs, stride, out_off, n} (int64, device memory):
