@@ -520,9 +520,13 @@ int wn_gcond_proj_bwd(const float* d_tab, int pair, const float* d_enf, const fl
     return wn_launch_gcond_proj_bwd(p, gcond_args(cls, gw_off, gstage_stride, gwf_off, emb_off, ge, n_cls), (hipStream_t)stream);
 }
 // ---- vector-quantised bottleneck (wn_vq.hip) ----
-// the refusals the three entries share: shapes and the offset first (they need no pointer)
-static int vq_checked(const char* fn, int64_t cb_off, int K, int bw, int le, int batch) {
+static int vq_refused(const char* fn, const char* what) {
     char msg[200];
+    snprintf(msg, sizeof(msg), "%s: argument %s", fn, what);
+    return wn_set_error_msg(-4, msg);
+}
+// the refusals the entries share: shapes and the offset first (they need no pointer)
+static int vq_checked(const char* fn, int64_t cb_off, int K, int bw, int le, int batch) {
     const char* bad = nullptr;
     if (batch < 0) bad = "'batch' must be >= 0";
     else if (K < 2 || K > WN_VQ_MAX_CODES) bad = "'K' must lie in [2, 1024]";
@@ -530,97 +534,93 @@ static int vq_checked(const char* fn, int64_t cb_off, int K, int bw, int le, int
     else if (le < 1) bad = "'le' must be >= 1";
     else if (cb_off < 0) bad = "'cb_off' must be >= 0";
     else if ((int64_t)batch * le > 0x7fffffffLL - 64) bad = "'batch' * le frames do not fit 31 bits";
-    if (bad) {
-        snprintf(msg, sizeof(msg), "%s: argument %s", fn, bad);
-        return wn_set_error_msg(-4, msg);
-    }
-    return 0;
+    return bad ? vq_refused(fn, bad) : 0;
 }
+// the residual chain over S codebooks (wn_rvq_*): the stage count, then the refusals above
+static int rvq_checked(const char* fn, int S, int64_t cb_off, int K, int bw, int le, int batch) {
+    if (S < 1 || S > WN_RVQ_MAX_STAGES) return vq_refused(fn, "'S' must lie in [1, 8]");
+    return vq_checked(fn, cb_off, K, bw, le, batch);
+}
+// What every forward and backward entry hands its launcher.  res NULL: one stage (wn_vq_*; S is not read); else the chain over S stages,
+// wn_rvq_* at S = 1 included.  nstage NULL: no stage counts
+static WnVq rvq_args(const float* enc, const float* flat, int64_t cb_off, const int32_t* idx, const float* res, const int32_t* nstage, int S,
+                     int K, int bw, int le, int batch) {
+    WnVq p;
+    memset(&p, 0, sizeof(p));
+    p.enc = enc; p.flat = flat; p.cb_off = (long)cb_off; p.idx = const_cast<int32_t*>(idx); p.res = const_cast<float*>(res);
+    p.nstage = nstage; p.S = S; p.K = K; p.bw = bw; p.le = le; p.batch = batch;
+    return p;
+}
+static int vq_fwd_run(WnVq p, float* q_out, int32_t* counts, float* loss_part, wn_stream_t stream) {
+    p.q_out = q_out; p.counts = counts; p.loss_part = loss_part;
+    return wn_launch_vq_fwd(p, (hipStream_t)stream);
+}
+static int vq_bwd_run(WnVq p, const float* d_q, float beta, float g_scale, float* d_enc, float* flat_grad, float* stat, wn_stream_t stream) {
+    p.d_q = d_q; p.d_enc = d_enc; p.flat_grad = flat_grad;
+    return wn_launch_vq_bwd(p, beta, g_scale, stat, (hipStream_t)stream);
+}
+// wn_vq_ema_update (S = 1) and wn_rvq_ema_update
+static int vq_ema_update_run(const char* fn, float* flat, int64_t cb_off, const float* stat, float* state, void* work, int32_t* info, int S,
+                             int K, int bw, float decay, float eps, float restart, const wn_guard_state* guard_state, wn_stream_t stream) {
+    if (int rc = rvq_checked(fn, S, cb_off, K, bw, 1, 1)) return rc;
+    if (!(decay > 0.f && decay < 1.f)) return vq_refused(fn, "'decay' must lie in (0, 1)");
+    if (!(eps >= 0.f)) return vq_refused(fn, "'eps' must be >= 0");
+    if (!(restart >= 0.f)) return vq_refused(fn, "'restart' must be >= 0");
+    WN_REQUIRE(fn, flat, stat, state, work);
+    if ((uintptr_t)guard_state % 8 != 0) return vq_refused(fn, "'guard_state' needs 8-byte alignment");
+    return wn_launch_vq_ema_update(flat, (long)cb_off, stat, state, work, info, S, K, bw, decay, eps, restart, guard_state,
+                                   (hipStream_t)stream);
+}
+
 int wn_vq_fwd(const float* enc, const float* flat, int64_t cb_off, float* q_out, int32_t* idx, int32_t* counts, float* loss_part, int K,
               int bw, int le, int batch, wn_stream_t stream) {
     if (int rc = vq_checked("wn_vq_fwd", cb_off, K, bw, le, batch)) return rc;
     if (batch == 0) return 0;
     WN_REQUIRE("wn_vq_fwd", enc, flat, q_out, idx, loss_part);
-    WnVq p;
-    memset(&p, 0, sizeof(p));
-    p.enc = enc; p.flat = flat; p.cb_off = (long)cb_off; p.q_out = q_out; p.idx = idx; p.counts = counts; p.loss_part = loss_part;
-    p.K = K; p.bw = bw; p.le = le; p.batch = batch;
-    return wn_launch_vq_fwd(p, (hipStream_t)stream);
+    return vq_fwd_run(rvq_args(enc, flat, cb_off, idx, nullptr, nullptr, 1, K, bw, le, batch), q_out, counts, loss_part, stream);
 }
 int wn_vq_bwd(const float* enc, const int32_t* idx, const float* d_q, const float* flat, int64_t cb_off, float beta, float g_scale,
               float* d_enc, float* flat_grad, int K, int bw, int le, int batch, wn_stream_t stream) {
     if (int rc = vq_checked("wn_vq_bwd", cb_off, K, bw, le, batch)) return rc;
     if (batch == 0) return 0;
     WN_REQUIRE("wn_vq_bwd", enc, idx, d_q, flat, d_enc, flat_grad);
-    WnVq p;
-    memset(&p, 0, sizeof(p));
-    p.enc = enc; p.flat = flat; p.cb_off = (long)cb_off; p.idx = const_cast<int32_t*>(idx); p.d_q = d_q; p.d_enc = d_enc;
-    p.flat_grad = flat_grad; p.K = K; p.bw = bw; p.le = le; p.batch = batch;
-    return wn_launch_vq_bwd(p, beta, g_scale, (hipStream_t)stream);
+    return vq_bwd_run(rvq_args(enc, flat, cb_off, idx, nullptr, nullptr, 1, K, bw, le, batch), d_q, beta, g_scale, d_enc, flat_grad, nullptr,
+                      stream);
 }
 int wn_vq_lookup(const int32_t* idx, const float* flat, int64_t cb_off, float* q_out, int32_t* bad, int K, int bw, int le, int batch,
                  wn_stream_t stream) {
     if (int rc = vq_checked("wn_vq_lookup", cb_off, K, bw, le, batch)) return rc;
     if (batch == 0) return 0;
     WN_REQUIRE("wn_vq_lookup", idx, flat, q_out);
-    return wn_launch_vq_lookup(idx, flat, (long)cb_off, q_out, bad, 1, K, bw, le, batch, (hipStream_t)stream);
+    return wn_launch_vq_lookup(idx, nullptr, flat, (long)cb_off, q_out, bad, 1, K, bw, le, batch, (hipStream_t)stream);
 }
 int wn_vq_bwd_stats(const float* enc, const int32_t* idx, const float* d_q, const float* flat, int64_t cb_off, float beta, float g_scale,
                     float* d_enc, float* flat_grad, float* stat, int K, int bw, int le, int batch, wn_stream_t stream) {
     if (int rc = vq_checked("wn_vq_bwd_stats", cb_off, K, bw, le, batch)) return rc;
     if (batch == 0) return 0;
     WN_REQUIRE("wn_vq_bwd_stats", enc, idx, d_q, flat, d_enc, flat_grad, stat);
-    WnVq p;
-    memset(&p, 0, sizeof(p));
-    p.enc = enc; p.flat = flat; p.cb_off = (long)cb_off; p.idx = const_cast<int32_t*>(idx); p.d_q = d_q; p.d_enc = d_enc;
-    p.flat_grad = flat_grad; p.K = K; p.bw = bw; p.le = le; p.batch = batch;
-    return wn_launch_vq_bwd_stats(p, beta, g_scale, stat, (hipStream_t)stream);
+    return vq_bwd_run(rvq_args(enc, flat, cb_off, idx, nullptr, nullptr, 1, K, bw, le, batch), d_q, beta, g_scale, d_enc, flat_grad, stat,
+                      stream);
 }
 int wn_vq_ema_update(float* flat, int64_t cb_off, const float* stat, float* state, void* work, int32_t* info, int K, int bw,
                      float decay, float eps, float restart, const wn_guard_state* guard_state, wn_stream_t stream) {
-    if (int rc = vq_checked("wn_vq_ema_update", cb_off, K, bw, 1, 1)) return rc;
-    if (!(decay > 0.f && decay < 1.f)) return wn_set_error_msg(-4, "wn_vq_ema_update: argument 'decay' must lie in (0, 1)");
-    if (!(eps >= 0.f)) return wn_set_error_msg(-4, "wn_vq_ema_update: argument 'eps' must be >= 0");
-    if (!(restart >= 0.f)) return wn_set_error_msg(-4, "wn_vq_ema_update: argument 'restart' must be >= 0");
-    WN_REQUIRE("wn_vq_ema_update", flat, stat, state, work);
-    if ((uintptr_t)guard_state % 8 != 0) return wn_set_error_msg(-4, "wn_vq_ema_update: argument 'guard_state' needs 8-byte alignment");
-    return wn_launch_vq_ema_update(flat, (long)cb_off, stat, state, work, info, 1, K, bw, decay, eps, restart, guard_state,
-                                   (hipStream_t)stream);
+    return vq_ema_update_run("wn_vq_ema_update", flat, cb_off, stat, state, work, info, 1, K, bw, decay, eps, restart, guard_state, stream);
 }
-// ---- the residual chain over S codebooks (wn_vq.hip): the refusals of the entries above, and the stage count
-static int rvq_checked(const char* fn, int S, int64_t cb_off, int K, int bw, int le, int batch) {
-    if (S < 1 || S > WN_RVQ_MAX_STAGES) {
-        char msg[200];
-        snprintf(msg, sizeof(msg), "%s: argument 'S' must lie in [1, 8]", fn);
-        return wn_set_error_msg(-4, msg);
-    }
-    return vq_checked(fn, cb_off, K, bw, le, batch);
-}
-static WnVq rvq_args(const float* enc, const float* flat, int64_t cb_off, const int32_t* idx, const float* res, int S, int K, int bw, int le,
-                     int batch) {
-    WnVq p;
-    memset(&p, 0, sizeof(p));
-    p.enc = enc; p.flat = flat; p.cb_off = (long)cb_off; p.idx = const_cast<int32_t*>(idx); p.res = const_cast<float*>(res);
-    p.S = S; p.K = K; p.bw = bw; p.le = le; p.batch = batch;
-    return p;
-}
+// ---- the residual chain over S codebooks
 int wn_rvq_fwd(const float* enc, const float* flat, int64_t cb_off, float* q_out, int32_t* idx, int32_t* counts, float* res,
                float* loss_part, int S, int K, int bw, int le, int batch, wn_stream_t stream) {
     if (int rc = rvq_checked("wn_rvq_fwd", S, cb_off, K, bw, le, batch)) return rc;
     if (batch == 0) return 0;
     WN_REQUIRE("wn_rvq_fwd", enc, flat, q_out, idx, res, loss_part);
-    WnVq p = rvq_args(enc, flat, cb_off, idx, res, S, K, bw, le, batch);
-    p.q_out = q_out; p.counts = counts; p.loss_part = loss_part;
-    return wn_launch_rvq_fwd(p, (hipStream_t)stream);
+    return vq_fwd_run(rvq_args(enc, flat, cb_off, idx, res, nullptr, S, K, bw, le, batch), q_out, counts, loss_part, stream);
 }
 int wn_rvq_bwd(const float* enc, const int32_t* idx, const float* res, const float* d_q, const float* flat, int64_t cb_off, float beta,
                float g_scale, float* d_enc, float* flat_grad, int S, int K, int bw, int le, int batch, wn_stream_t stream) {
     if (int rc = rvq_checked("wn_rvq_bwd", S, cb_off, K, bw, le, batch)) return rc;
     if (batch == 0) return 0;
     WN_REQUIRE("wn_rvq_bwd", enc, idx, res, d_q, flat, d_enc, flat_grad);
-    WnVq p = rvq_args(enc, flat, cb_off, idx, res, S, K, bw, le, batch);
-    p.d_q = d_q; p.d_enc = d_enc; p.flat_grad = flat_grad;
-    return wn_launch_rvq_bwd(p, beta, g_scale, nullptr, (hipStream_t)stream);
+    return vq_bwd_run(rvq_args(enc, flat, cb_off, idx, res, nullptr, S, K, bw, le, batch), d_q, beta, g_scale, d_enc, flat_grad, nullptr,
+                      stream);
 }
 int wn_rvq_bwd_stats(const float* enc, const int32_t* idx, const float* res, const float* d_q, const float* flat, int64_t cb_off, float beta,
                      float g_scale, float* d_enc, float* flat_grad, float* stat, int S, int K, int bw, int le, int batch,
@@ -628,20 +628,11 @@ int wn_rvq_bwd_stats(const float* enc, const int32_t* idx, const float* res, con
     if (int rc = rvq_checked("wn_rvq_bwd_stats", S, cb_off, K, bw, le, batch)) return rc;
     if (batch == 0) return 0;
     WN_REQUIRE("wn_rvq_bwd_stats", enc, idx, res, d_q, flat, d_enc, flat_grad, stat);
-    WnVq p = rvq_args(enc, flat, cb_off, idx, res, S, K, bw, le, batch);
-    p.d_q = d_q; p.d_enc = d_enc; p.flat_grad = flat_grad;
-    return wn_launch_rvq_bwd(p, beta, g_scale, stat, (hipStream_t)stream);
+    return vq_bwd_run(rvq_args(enc, flat, cb_off, idx, res, nullptr, S, K, bw, le, batch), d_q, beta, g_scale, d_enc, flat_grad, stat, stream);
 }
 int wn_rvq_ema_update(float* flat, int64_t cb_off, const float* stat, float* state, void* work, int32_t* info, int S, int K, int bw,
                       float decay, float eps, float restart, const wn_guard_state* guard_state, wn_stream_t stream) {
-    if (int rc = rvq_checked("wn_rvq_ema_update", S, cb_off, K, bw, 1, 1)) return rc;
-    if (!(decay > 0.f && decay < 1.f)) return wn_set_error_msg(-4, "wn_rvq_ema_update: argument 'decay' must lie in (0, 1)");
-    if (!(eps >= 0.f)) return wn_set_error_msg(-4, "wn_rvq_ema_update: argument 'eps' must be >= 0");
-    if (!(restart >= 0.f)) return wn_set_error_msg(-4, "wn_rvq_ema_update: argument 'restart' must be >= 0");
-    WN_REQUIRE("wn_rvq_ema_update", flat, stat, state, work);
-    if ((uintptr_t)guard_state % 8 != 0) return wn_set_error_msg(-4, "wn_rvq_ema_update: argument 'guard_state' needs 8-byte alignment");
-    return wn_launch_vq_ema_update(flat, (long)cb_off, stat, state, work, info, S, K, bw, decay, eps, restart, guard_state,
-                                   (hipStream_t)stream);
+    return vq_ema_update_run("wn_rvq_ema_update", flat, cb_off, stat, state, work, info, S, K, bw, decay, eps, restart, guard_state, stream);
 }
 int wn_rvq_lookup(const int32_t* idx, const float* flat, int64_t cb_off, float* q_out, int32_t* bad, int S, int stages, int K, int bw, int le,
                   int batch, wn_stream_t stream) {
@@ -649,7 +640,7 @@ int wn_rvq_lookup(const int32_t* idx, const float* flat, int64_t cb_off, float* 
     if (stages < 1 || stages > S) return wn_set_error_msg(-4, "wn_rvq_lookup: argument 'stages' must lie in [1, S]");
     if (batch == 0) return 0;
     WN_REQUIRE("wn_rvq_lookup", idx, flat, q_out);
-    return wn_launch_vq_lookup(idx, flat, (long)cb_off, q_out, bad, stages, K, bw, le, batch, (hipStream_t)stream);
+    return wn_launch_vq_lookup(idx, nullptr, flat, (long)cb_off, q_out, bad, stages, K, bw, le, batch, (hipStream_t)stream);
 }
 // ---- quantiser dropout: the chain with a stage count per clip (nstage, batch int32 on the device; required)
 int wn_rvq_fwd_n(const float* enc, const float* flat, int64_t cb_off, const int32_t* nstage, float* q_out, int32_t* idx, int32_t* counts,
@@ -657,9 +648,7 @@ int wn_rvq_fwd_n(const float* enc, const float* flat, int64_t cb_off, const int3
     if (int rc = rvq_checked("wn_rvq_fwd_n", S, cb_off, K, bw, le, batch)) return rc;
     if (batch == 0) return 0;
     WN_REQUIRE("wn_rvq_fwd_n", enc, flat, nstage, q_out, idx, res, loss_part);
-    WnVq p = rvq_args(enc, flat, cb_off, idx, res, S, K, bw, le, batch);
-    p.q_out = q_out; p.counts = counts; p.loss_part = loss_part;
-    return wn_launch_rvq_fwd_n(p, nstage, (hipStream_t)stream);
+    return vq_fwd_run(rvq_args(enc, flat, cb_off, idx, res, nstage, S, K, bw, le, batch), q_out, counts, loss_part, stream);
 }
 int wn_rvq_bwd_n(const float* enc, const int32_t* idx, const float* res, const int32_t* nstage, const float* d_q, const float* flat,
                  int64_t cb_off, float beta, float g_scale, float* d_enc, float* flat_grad, int S, int K, int bw, int le, int batch,
@@ -667,9 +656,7 @@ int wn_rvq_bwd_n(const float* enc, const int32_t* idx, const float* res, const i
     if (int rc = rvq_checked("wn_rvq_bwd_n", S, cb_off, K, bw, le, batch)) return rc;
     if (batch == 0) return 0;
     WN_REQUIRE("wn_rvq_bwd_n", enc, idx, res, nstage, d_q, flat, d_enc, flat_grad);
-    WnVq p = rvq_args(enc, flat, cb_off, idx, res, S, K, bw, le, batch);
-    p.d_q = d_q; p.d_enc = d_enc; p.flat_grad = flat_grad;
-    return wn_launch_rvq_bwd_n(p, nstage, beta, g_scale, nullptr, (hipStream_t)stream);
+    return vq_bwd_run(rvq_args(enc, flat, cb_off, idx, res, nstage, S, K, bw, le, batch), d_q, beta, g_scale, d_enc, flat_grad, nullptr, stream);
 }
 int wn_rvq_bwd_stats_n(const float* enc, const int32_t* idx, const float* res, const int32_t* nstage, const float* d_q, const float* flat,
                        int64_t cb_off, float beta, float g_scale, float* d_enc, float* flat_grad, float* stat, int S, int K, int bw, int le,
@@ -677,16 +664,14 @@ int wn_rvq_bwd_stats_n(const float* enc, const int32_t* idx, const float* res, c
     if (int rc = rvq_checked("wn_rvq_bwd_stats_n", S, cb_off, K, bw, le, batch)) return rc;
     if (batch == 0) return 0;
     WN_REQUIRE("wn_rvq_bwd_stats_n", enc, idx, res, nstage, d_q, flat, d_enc, flat_grad, stat);
-    WnVq p = rvq_args(enc, flat, cb_off, idx, res, S, K, bw, le, batch);
-    p.d_q = d_q; p.d_enc = d_enc; p.flat_grad = flat_grad;
-    return wn_launch_rvq_bwd_n(p, nstage, beta, g_scale, stat, (hipStream_t)stream);
+    return vq_bwd_run(rvq_args(enc, flat, cb_off, idx, res, nstage, S, K, bw, le, batch), d_q, beta, g_scale, d_enc, flat_grad, stat, stream);
 }
 int wn_rvq_lookup_n(const int32_t* idx, const int32_t* nstage, const float* flat, int64_t cb_off, float* q_out, int32_t* bad, int S, int K,
                     int bw, int le, int batch, wn_stream_t stream) {
     if (int rc = rvq_checked("wn_rvq_lookup_n", S, cb_off, K, bw, le, batch)) return rc;
     if (batch == 0) return 0;
     WN_REQUIRE("wn_rvq_lookup_n", idx, nstage, flat, q_out);
-    return wn_launch_vq_lookup_n(idx, nstage, flat, (long)cb_off, q_out, bad, S, K, bw, le, batch, (hipStream_t)stream);
+    return wn_launch_vq_lookup(idx, nstage, flat, (long)cb_off, q_out, bad, S, K, bw, le, batch, (hipStream_t)stream);
 }
 int wn_coll_available(void) { return wn_coll_loaded(); }
 int wn_comm_unique_id(char* id128) { return wn_coll_unique_id(id128); }

@@ -269,33 +269,29 @@ int wn_launch_gcond_proj_fwd(const WnCondProj& p, const WnGcond& g, hipStream_t 
 int wn_launch_gcond_proj_bwd(const WnCondProj& p, const WnGcond& g, hipStream_t st);
 // vector-quantised bottleneck (wn_vq.hip): the codebook [K][bw] sits at flat + cb_off (its gradient at flat_grad + cb_off)
 #define WN_VQ_PARTIALS 256
+#define WN_RVQ_MAX_S 8
 struct WnVq {
     const float* enc; const float* flat; long cb_off;
     float* q_out; int32_t* idx; int32_t* counts; float* loss_part;       // forward outputs (counts may be NULL); idx: the backward's input
     const float* d_q; float* d_enc; float* flat_grad;                    // backward
     int K, bw, le, batch;
-    // the residual chain (wn_rvq_*) alone: S stages of K rows each; res [S][B][Bw][Le], res[s] = what stage s left over (the forward
-    // writes it, the backward reads it); idx is [S][B][Le], counts [S][K] and loss_part [S][WN_VQ_PARTIALS] there
+    // res != NULL: the residual chain (wn_rvq_*), S stages of K rows each; res [S][B][Bw][Le], res[s] = what stage s left over (the
+    // forward writes it, the backward reads it); idx is [S][B][Le], counts [S][K] and loss_part [S][WN_VQ_PARTIALS] there.  NULL: one
+    // stage (wn_vq_*), S is not read
     int S; float* res;
+    // != NULL (the chain alone): quantiser dropout (wn_rvq_*_n), batch int32 stage counts on the device, clamped to [1, S] there; frame
+    // fr of clip b is active in stage s iff s < nstage[b]
+    const int32_t* nstage;
 };
-#define WN_RVQ_MAX_S 8
 int wn_launch_vq_fwd(const WnVq& p, hipStream_t st);
-int wn_launch_vq_bwd(const WnVq& p, float beta, float g_scale, hipStream_t st);
-// q = the sum of the first `stages` stages' rows (1: the plain lookup); idx [stages][batch][le]
-int wn_launch_vq_lookup(const int32_t* idx, const float* flat, long cb_off, float* q_out, int32_t* bad, int stages, int K, int bw, int le,
-                        int batch, hipStream_t st);
-int wn_launch_rvq_fwd(const WnVq& p, hipStream_t st);
-int wn_launch_rvq_bwd(const WnVq& p, float beta, float g_scale, float* stat, hipStream_t st);       // stat != NULL: the stats form
-// quantiser dropout (wn_rvq_*_n): nstage = batch int32 stage counts on the device, clamped to [1, S] there; frame fr of clip b is active
-// in stage s iff s < nstage[b].  wn_launch_vq_lookup_n does not clamp: an n outside [1, S] gives a NaN frame and *bad
-int wn_launch_rvq_fwd_n(const WnVq& p, const int32_t* nstage, hipStream_t st);
-int wn_launch_rvq_bwd_n(const WnVq& p, const int32_t* nstage, float beta, float g_scale, float* stat, hipStream_t st);
-int wn_launch_vq_lookup_n(const int32_t* idx, const int32_t* nstage, const float* flat, long cb_off, float* q_out, int32_t* bad, int S, int K,
-                          int bw, int le, int batch, hipStream_t st);
+int wn_launch_vq_bwd(const WnVq& p, float beta, float g_scale, float* stat, hipStream_t st);        // stat != NULL: the stats form
+// q = the sum of the first `stages` stages' rows (1: the plain lookup); idx [stages][batch][le].  nstage != NULL: `stages` = S, idx
+// [S][batch][le] and clip b takes its first nstage[b]; NOT clamped: an n outside [1, S] gives a NaN frame and *bad
+int wn_launch_vq_lookup(const int32_t* idx, const int32_t* nstage, const float* flat, long cb_off, float* q_out, int32_t* bad, int stages,
+                        int K, int bw, int le, int batch, hipStream_t st);
 // EMA mode: stat = [n | s] and state = [N | m], K counts then K rows of bw; work: WN_VQ_EMA_WORK bytes of device scratch
 #define WN_VQ_MAX_K 1024
 #define WN_VQ_EMA_WORK (16 + 4 * WN_VQ_MAX_K)
-int wn_launch_vq_bwd_stats(const WnVq& p, float beta, float g_scale, float* stat, hipStream_t st);
 // S stages (1: wn_vq_ema_update): S blocks of stat, state, work and info[2], S x K codebook rows
 int wn_launch_vq_ema_update(float* flat, long cb_off, const float* stat, float* state, void* work, int32_t* info, int S, int K, int bw,
                             float decay, float eps, float restart, const wn_guard_state* guard, hipStream_t st);

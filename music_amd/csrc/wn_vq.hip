@@ -1,5 +1,7 @@
-// The vector-quantised bottleneck of the autoencoder (wn_vq_fwd / wn_vq_bwd / wn_vq_lookup in include/wavenet_hip.h): every pooled
-// frame e[b][:, l] of enc [B][Bw][Le] is replaced by its nearest row of the codebook c [K][Bw], a parameter of the flat buffer.
+// The vector-quantised bottleneck of the autoencoder (the wn_vq_* and wn_rvq_* entries of include/wavenet_hip.h): every pooled frame
+// e[b][:, l] of enc [B][Bw][Le] is replaced by its nearest row of a codebook c [K][Bw], a parameter of the flat buffer - or, in a
+// residual chain, by the sum of S such rows.  ONE kernel family: a forward, a backward and a lookup template, the EMA update's two
+// kernels, four launchers.
 //
 //   forward   dist(frame, k) = sum_j (e_j - c_kj)^2 (the difference form: no cancellation), idx = the FIRST argmin over k,
 //             q = c[idx] in enc's layout, counts[k] = frames of code k, loss_part = per-workgroup sums of the best distances / (C Bw)
@@ -15,28 +17,28 @@
 // per ballot, and adds the matching frames: no scatter, no atomics), the others form d_e elementwise.  fp32, a fixed summation
 // order, no float atomics: the same bits at every launch.  counts uses integer atomics on a buffer cleared by a memset node.
 //
-// EMA mode (wn_vq_bwd_stats / wn_vq_ema_update): the codebook follows the running mean of its frames instead of a gradient.
-//   stats     the backward's launch with the code workgroups adding e instead of c_k - e: stat = [n | s], the frames per code (as
-//             floats) and their sums in ascending frame order; the codebook's rows of flat_grad become exactly 0
-//   update    N' = g N + (1 - g) n, m' = g m + (1 - g) s, c' = m' / Nhat with the usage smoothed by eps; a code whose N' fell
-//             below `restart` takes the batch mean s / n of a donor (the d-th dead code, ascending, the d-th code by n descending).
-// Two launches: ONE workgroup ranks the K codes (counting ranks over LDS) and writes only the scratch `work`; then a wave per code
+// The templates' parameters (compile-time: the forms do not cost the same registers and LDS, tools/kres.sh shows each instantiation):
+//   CHAIN   the residual chain (wn_rvq_*, chosen by WnVq::res != NULL, at S = 1 too): S codebooks of K rows, stage s quantises what the
+//           stages before it left over (r_0 = e, r_s+1 = r_s - q_s), the decoder sees q_0 + ... + q_S-1.  Frames are independent, so the
+//           chain is still ONE launch per direction: the forward loops the stages over its staged tile, the backward gives every
+//           (stage, code) a wave, the EMA update's two launches take the stage as a second grid dimension.  Without it (wn_vq_*) there
+//           is one stage, no res, no running q; the statements are shared, so at S = 1 the chain has the one-stage entries' bits.
+//   NST     quantiser dropout (wn_rvq_*_n, WnVq::nstage != NULL; the chain only): a stage count n_b per clip, frame fr of clip b is
+//           active in stage s iff s < n_b (clamped to [1, S] on the device; the lookup does not clamp, it flags).  Clips of different n
+//           share a 4-frame tile whenever Le % 4 != 0, so the stage count is a property of the FRAME in the forward: the tile's stage
+//           loop runs to the largest n of its frames (read from LDS behind a barrier: the same bound in every thread, the barriers
+//           inside the loop stay uniform), an inactive frame keeps its residual and running q untouched, gets idx = -1 and adds
+//           nothing to counts or the stage's loss partial, whose denominator stays C Bw.  The backward's element workgroups sum the
+//           ACTIVE stages' residuals; idx = -1 matches no code in vq_code_walk, so the (stage, code) waves cover exactly the active
+//           frames as they are.  With every n = S the statements are the chain's: the same bits in every output.
+//   STATS   (backward) EMA mode, wn_*_bwd_stats* / wn_*_ema_update: the codebook follows the running mean of its frames instead of a
+//           gradient.  The code workgroups add e instead of c_k - e: stat = [n | s], the frames per code (as floats) and their sums in
+//           ascending frame order; the codebook's rows of flat_grad become exactly 0.
+//
+// The EMA update: N' = g N + (1 - g) n, m' = g m + (1 - g) s, c' = m' / Nhat with the usage smoothed by eps; a code whose N' fell
+// below `restart` takes the batch mean s / n of a donor (the d-th dead code, ascending, the d-th code by n descending).  Two launches:
+// ONE workgroup per stage ranks the K codes (counting ranks over LDS) and writes only the scratch `work`; then a wave per code
 // rewrites its own rows of state and codebook from them - no workgroup reads what another writes, so the update is in place.
-//
-// Residual chain (wn_rvq_*): S codebooks of K rows, stage s quantises what the stages before it left over (r_0 = e, r_s+1 = r_s - q_s),
-// the decoder sees q_0 + ... + q_S-1.  Frames are independent, so the chain is ONE launch per direction: rvq_fwd_k loops the stages
-// over a staged tile with the search and merge of vq_fwd_k, rvq_bwd_k / rvq_bwd_stats_k give every (stage, code) a wave with the walk
-// of vq_bwd_k, and the EMA update's two launches take the stage as a second grid dimension.  The device functions are shared, so at
-// S = 1 every output has the bits of the wn_vq_* entry.
-//
-// Quantiser dropout (wn_rvq_fwd_n / wn_rvq_bwd_n / wn_rvq_bwd_stats_n / wn_rvq_lookup_n): a stage count n_b per clip, frame fr of clip b is
-// active in stage s iff s < n_b (clamped to [1, S] on the device).  Clips of different n share a 4-frame tile whenever Le % 4 != 0, so
-// the stage count is a property of the FRAME inside rvq_fwd_n_k: the tile's stage loop runs to the largest n of its frames (read from
-// LDS behind a barrier: the same bound in every thread, the barriers inside the loop stay uniform), an inactive frame keeps its
-// residual and running q untouched, gets idx = -1 and adds nothing to counts or the stage's loss partial, whose denominator stays
-// C Bw.  The backward needs new element workgroups only (the sum over the ACTIVE stages' residuals): idx = -1 matches no code in
-// vq_code_walk, so the (stage, code) waves cover exactly the active frames as they are.  With every n = S the statements are the
-// chain's: the same bits in every output.
 #include <limits>
 #include "../../include/wavenet_hip.h"
 #include "wn_common.h"
@@ -44,12 +46,12 @@
 
 namespace {
 
-constexpr int FT = 4;              // frames per tile of vq_fwd_k (the butterfly below is written for 4)
+constexpr int FT = 4;              // frames per tile of the forward (the butterfly below is written for 4)
 constexpr int NWV = 8;             // its waves per workgroup
 constexpr int CU = 4;              // codes a wave takes per pass
 constexpr int MAXW = 512;          // bw <= 512: 8 values of j per lane
 constexpr int NJ = MAXW / 64;
-constexpr int CWV = 4;             // vq_bwd_k: waves = codes per workgroup
+constexpr int CWV = 4;             // the backward: waves = codes per workgroup
 
 // frame fr = (clip b, pooled frame l): the offset of its element j = 0 in [B][Bw][Le]; element j sits j * le floats behind it
 __device__ __forceinline__ long frame_base(int fr, int bw, int le) {
@@ -135,131 +137,52 @@ __device__ __forceinline__ void vq_tile_stage(const WnVq& p, int f0, int C, floa
     }
 }
 
-__global__ __launch_bounds__(64 * NWV) void vq_fwd_k(WnVq p, float inv_n) {
-    __shared__ float s_e[FT][MAXW];
-    __shared__ float s_bd[NWV][FT];
-    __shared__ int s_bi[NWV][FT];
-    const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
-    const int C = p.batch * p.le, tiles = (C + FT - 1) / FT, nj = (p.bw + 63) >> 6;
-    const float* cb = p.flat + p.cb_off;
-    float loss = 0.f;                                      // thread 0: this workgroup's best distances, in frame order
-    for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const int f0 = tile * FT;
-        vq_tile_stage(p, f0, C, s_e, t);
-        __syncthreads();
-        float bd;                                          // of frame lane >> 4, over this wave's codes
-        int bi;
-        vq_tile_search(cb, p.K, p.bw, nj, s_e, lane, wave, bd, bi);
-        if ((lane & 15) == 0) { s_bd[wave][lane >> 4] = bd; s_bi[wave][lane >> 4] = bi; }
-        __syncthreads();
-        if (t < FT) {
-            const int ix = vq_tile_merge(s_bd, s_bi, t);
-            if (f0 + t < C) {
-                p.idx[f0 + t] = ix;
-                if (p.counts) atomicAdd(&p.counts[ix], 1);
-            }
-        }
-        __syncthreads();
-        if (t == 0)
-            for (int f = 0; f < FT; ++f)
-                if (f0 + f < C) loss += s_bd[0][f];
-        for (int o = t; o < FT * p.bw; o += 64 * NWV) {
-            const int j = o / FT, f = o % FT;
-            if (f0 + f < C) p.q_out[frame_base(f0 + f, p.bw, p.le) + (long)j * p.le] = cb[(long)s_bi[0][f] * p.bw + j];
-        }
-        __syncthreads();                                   // the next tile overwrites s_e, s_bd and s_bi
-    }
-    if (t == 0) p.loss_part[blockIdx.x] = loss * inv_n;    // every partial is rewritten at every call (a workgroup without a tile: 0)
-}
-
-// The residual chain (wn_rvq_fwd): the tile is staged once, the S stages loop inside the workgroup.  Stage s searches ITS K rows for the
-// staged residual r_s with vq_fwd_k's search and merge, then every thread subtracts the winning row from the residual in place
-// (r_s+1 = r_s - q_s, handed to the backward as res[s]) and adds it onto the running q (q_0 + q_1 + ..., ascending).  idx [S][C],
-// counts [S][K], loss_part [S][WN_VQ_PARTIALS].  A frame behind C is staged as zeros and chooses some row of [0, K): nothing of it is written.
-__global__ __launch_bounds__(64 * NWV) void rvq_fwd_k(WnVq p, float inv_n) {
-    __shared__ float s_e[FT][MAXW];                        // the residual r_s
-    __shared__ float s_q[FT][MAXW];                        // q_0 + ... + q_s
-    __shared__ float s_bd[NWV][FT];
-    __shared__ int s_bi[NWV][FT];
-    __shared__ float s_loss[WN_RVQ_MAX_S];                 // thread 0: per stage, this workgroup's best distances in frame order
-    const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
-    const int C = p.batch * p.le, tiles = (C + FT - 1) / FT, nj = (p.bw + 63) >> 6;
-    const long total = (long)C * p.bw, rows = (long)p.K * p.bw;
-    if (t < WN_RVQ_MAX_S) s_loss[t] = 0.f;
-    for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const int f0 = tile * FT;
-        vq_tile_stage(p, f0, C, s_e, t);
-        __syncthreads();
-        for (int s = 0; s < p.S; ++s) {
-            const float* cb = p.flat + p.cb_off + s * rows;
-            float bd;
-            int bi;
-            vq_tile_search(cb, p.K, p.bw, nj, s_e, lane, wave, bd, bi);
-            if ((lane & 15) == 0) { s_bd[wave][lane >> 4] = bd; s_bi[wave][lane >> 4] = bi; }
-            __syncthreads();
-            if (t < FT) {
-                const int ix = vq_tile_merge(s_bd, s_bi, t);
-                if (f0 + t < C) {
-                    p.idx[(long)s * C + f0 + t] = ix;
-                    if (p.counts) atomicAdd(&p.counts[s * p.K + ix], 1);
-                }
-            }
-            __syncthreads();
-            if (t == 0) {
-                float loss = s_loss[s];
-                for (int f = 0; f < FT; ++f)
-                    if (f0 + f < C) loss += s_bd[0][f];
-                s_loss[s] = loss;
-            }
-            const bool last = s == p.S - 1;
-            for (int o = t; o < FT * p.bw; o += 64 * NWV) {
-                const int j = o / FT, f = o % FT;
-                const float c = cb[(long)s_bi[0][f] * p.bw + j];
-                const float r = s_e[f][j] - c;
-                const float q = s ? s_q[f][j] + c : c;
-                s_e[f][j] = r;
-                s_q[f][j] = q;
-                if (f0 + f < C) {
-                    const long at = frame_base(f0 + f, p.bw, p.le) + (long)j * p.le;
-                    p.res[s * total + at] = r;
-                    if (last) p.q_out[at] = q;
-                }
-            }
-            __syncthreads();                               // the next stage reads s_e and overwrites s_bd and s_bi; so does the next tile
-        }
-    }
-    if (t < p.S) p.loss_part[t * WN_VQ_PARTIALS + blockIdx.x] = s_loss[t] * inv_n;
-}
-
-// a clip's stage count as the _n kernels use it: whatever the array holds, a value of [1, S] - never a bound unchecked
+// a clip's stage count as the forward and the backward use it: whatever the array holds, a value of [1, S] - never a bound unchecked
 __device__ __forceinline__ int nstage_of(const int32_t* nstage, int b, int S) { return min(max(nstage[b], 1), S); }
 
-// Quantiser dropout (wn_rvq_fwd_n): rvq_fwd_k with a stage count per clip, frame fr of clip b is ACTIVE in stage s iff s < n_b.  An
-// active frame gets rvq_fwd_k's arithmetic, an inactive one idx = -1, no count, no loss, and its residual and running q stay as they
-// are (res[s] = the carried r_n, so the buffer holds no uninitialised floats); q_out is written behind the frame's last active stage.
-// The stage loop runs to the maximum n of the tile's frames - s_n is read behind a barrier, so every thread forms the same bound and
-// the barriers inside the loop stay uniform -; the stages behind it only hand out -1 and the carried residual.  A frame behind C has
-// n = 0.  With every n = S each statement below is rvq_fwd_k's: the same bits in every output.
-__global__ __launch_bounds__(64 * NWV) void rvq_fwd_n_k(WnVq p, const int32_t* __restrict__ nstage, float inv_n) {
-    __shared__ float s_e[FT][MAXW];                        // the residual r_s
-    __shared__ float s_q[FT][MAXW];                        // q_0 + ... + q_s
+// The forward of every entry: a tile of FT frames is staged once, then per stage: search, publish, merge, loss, write back.
+//   <false, false>  wn_vq_fwd: one stage (p.S is not read), q_out = the winning rows; no s_q / s_loss / s_n, no res
+//   <true, false>   wn_rvq_fwd: stage s searches ITS K rows for the staged residual r_s, then every thread subtracts the winning row from
+//                   the residual in place (r_s+1 = r_s - q_s, handed to the backward as res[s]) and adds it onto the running q (q_0 +
+//                   q_1 + ..., ascending).  idx [S][C], counts [S][K], loss_part [S][WN_VQ_PARTIALS]
+//   <true, true>    wn_rvq_fwd_n: frame fr of clip b is ACTIVE in stage s iff s < n_b.  An active frame gets the chain's arithmetic, an
+//                   inactive one idx = -1, no count, no loss, and its residual and running q stay as they are (res[s] = the carried
+//                   r_n, so the buffer holds no uninitialised floats); q_out is written behind the frame's last active stage.  The
+//                   stage loop runs to the maximum n of the tile's frames - s_n is read behind a barrier, so every thread forms the
+//                   same bound and the barriers inside the loop stay uniform -; the stages behind it only hand out -1 and the carried
+//                   residual.  A frame behind C has n = 0.  With every n = S each statement is the chain's: the same bits everywhere.
+// A frame behind C is staged as zeros and chooses some row of [0, K): nothing of it is written.
+template <bool CHAIN, bool NST>
+__global__ __launch_bounds__(64 * NWV) void vq_fwd_k(WnVq p, float inv_n) {
+    static_assert(CHAIN || !NST, "stage counts belong to the chain");
+    __shared__ float s_e[FT][MAXW];                        // the frames; in a chain the residual r_s
+    __shared__ float s_q[FT][MAXW];                        // CHAIN: q_0 + ... + q_s
     __shared__ float s_bd[NWV][FT];
     __shared__ int s_bi[NWV][FT];
-    __shared__ int s_n[FT];                                // the stage counts of the tile's frames
-    __shared__ float s_loss[WN_RVQ_MAX_S];
+    __shared__ int s_n[FT];                                // NST: the stage counts of the tile's frames
+    __shared__ float s_loss[WN_RVQ_MAX_S];                 // CHAIN, thread 0: per stage, this workgroup's best distances in frame order
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int C = p.batch * p.le, tiles = (C + FT - 1) / FT, nj = (p.bw + 63) >> 6;
+    const int S = CHAIN ? p.S : 1;
     const long total = (long)C * p.bw, rows = (long)p.K * p.bw;
-    if (t < WN_RVQ_MAX_S) s_loss[t] = 0.f;
+    // (formed out here, not beside its use: the one-stage form sits at 72 VGPRs, the last count with 7 waves per SIMD, and with the base
+    // formed inside the tile loop, or a 64-bit sum as its idx offset, the compiler gives up the search's four loads in flight to stay
+    // there - 1.2x to 1.75x the time.  tools/kres.sh: 72 VGPRs is the good schedule, 66 the serialised one)
+    const float* const cb0 = p.flat + p.cb_off;
+    float loss = 0.f;                                      // !CHAIN, thread 0: what s_loss[0] would hold
+    if constexpr (CHAIN)
+        if (t < WN_RVQ_MAX_S) s_loss[t] = 0.f;
     for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         const int f0 = tile * FT;
         vq_tile_stage(p, f0, C, s_e, t);
-        if (t < FT) s_n[t] = f0 + t < C ? nstage_of(nstage, (f0 + t) / p.le, p.S) : 0;
+        if constexpr (NST)
+            if (t < FT) s_n[t] = f0 + t < C ? nstage_of(p.nstage, (f0 + t) / p.le, S) : 0;
         __syncthreads();
-        const int n_max = max(max(s_n[0], s_n[1]), max(s_n[2], s_n[3]));
+        int n_max = S;
+        if constexpr (NST) n_max = max(max(s_n[0], s_n[1]), max(s_n[2], s_n[3]));
         for (int s = 0; s < n_max; ++s) {
-            const float* cb = p.flat + p.cb_off + s * rows;
-            float bd;
+            const float* cb = cb0 + s * rows;
+            float bd;                                      // of frame lane >> 4, over this wave's codes
             int bi;
             vq_tile_search(cb, p.K, p.bw, nj, s_e, lane, wave, bd, bi);
             if ((lane & 15) == 0) { s_bd[wave][lane >> 4] = bd; s_bi[wave][lane >> 4] = bi; }
@@ -267,45 +190,68 @@ __global__ __launch_bounds__(64 * NWV) void rvq_fwd_n_k(WnVq p, const int32_t* _
             if (t < FT) {
                 const int ix = vq_tile_merge(s_bd, s_bi, t);
                 if (f0 + t < C) {
-                    const bool on = s < s_n[t];
-                    p.idx[(long)s * C + f0 + t] = on ? ix : -1;
+                    bool on = true;
+                    if constexpr (NST) on = s < s_n[t];
+                    p.idx[CHAIN ? (long)s * C + f0 + t : f0 + t] = on ? ix : -1;          // (one stage: a 32-bit sum, see cb0)
                     if (on && p.counts) atomicAdd(&p.counts[s * p.K + ix], 1);
                 }
             }
             __syncthreads();
             if (t == 0) {
-                float loss = s_loss[s];
-                for (int f = 0; f < FT; ++f)
-                    if (s < s_n[f]) loss += s_bd[0][f];
-                s_loss[s] = loss;
+                if constexpr (CHAIN) loss = s_loss[s];
+                for (int f = 0; f < FT; ++f) {
+                    bool on = f0 + f < C;
+                    if constexpr (NST) on = s < s_n[f];
+                    if (on) loss += s_bd[0][f];
+                }
+                if constexpr (CHAIN) s_loss[s] = loss;
             }
             for (int o = t; o < FT * p.bw; o += 64 * NWV) {
-                const int j = o / FT, f = o % FT, n = s_n[f];
-                float r = s_e[f][j];
-                if (s < n) {
-                    const float c = cb[(long)s_bi[0][f] * p.bw + j];
-                    r -= c;
-                    const float q = s ? s_q[f][j] + c : c;
-                    s_e[f][j] = r;
-                    s_q[f][j] = q;
-                    if (s == n - 1) p.q_out[frame_base(f0 + f, p.bw, p.le) + (long)j * p.le] = q;
+                const int j = o / FT, f = o % FT;
+                if constexpr (!CHAIN) {
+                    if (f0 + f < C) p.q_out[frame_base(f0 + f, p.bw, p.le) + (long)j * p.le] = cb[(long)s_bi[0][f] * p.bw + j];
+                } else {
+                    int n = S;
+                    if constexpr (NST) n = s_n[f];
+                    float r = s_e[f][j], q = 0.f;
+                    if (s < n) {
+                        const float c = cb[(long)s_bi[0][f] * p.bw + j];
+                        r -= c;
+                        q = s ? s_q[f][j] + c : c;
+                        s_e[f][j] = r;
+                        s_q[f][j] = q;
+                        if constexpr (NST)                 // (s < n: a frame in front of C)
+                            if (s == n - 1) p.q_out[frame_base(f0 + f, p.bw, p.le) + (long)j * p.le] = q;
+                    }
+                    if (f0 + f < C) {
+                        const long at = frame_base(f0 + f, p.bw, p.le) + (long)j * p.le;
+                        p.res[s * total + at] = r;
+                        if constexpr (!NST)
+                            if (s == S - 1) p.q_out[at] = q;
+                    }
                 }
-                if (f0 + f < C) p.res[s * total + frame_base(f0 + f, p.bw, p.le) + (long)j * p.le] = r;
             }
             __syncthreads();                               // the next stage reads s_e and overwrites s_bd and s_bi; so does the next tile
         }
-        if (n_max < p.S) {                                 // the stages no frame of this tile takes part in
-            for (int s = n_max; s < p.S; ++s) {
-                if (t < FT && f0 + t < C) p.idx[(long)s * C + f0 + t] = -1;
-                for (int o = t; o < FT * p.bw; o += 64 * NWV) {
-                    const int j = o / FT, f = o % FT;
-                    if (f0 + f < C) p.res[s * total + frame_base(f0 + f, p.bw, p.le) + (long)j * p.le] = s_e[f][j];
+        if constexpr (NST) {
+            if (n_max < S) {                               // the stages no frame of this tile takes part in
+                for (int s = n_max; s < S; ++s) {
+                    if (t < FT && f0 + t < C) p.idx[(long)s * C + f0 + t] = -1;
+                    for (int o = t; o < FT * p.bw; o += 64 * NWV) {
+                        const int j = o / FT, f = o % FT;
+                        if (f0 + f < C) p.res[s * total + frame_base(f0 + f, p.bw, p.le) + (long)j * p.le] = s_e[f][j];
+                    }
                 }
+                __syncthreads();                           // the next tile overwrites s_e and s_n
             }
-            __syncthreads();                               // the next tile overwrites s_e and s_n
         }
     }
-    if (t < p.S) p.loss_part[t * WN_VQ_PARTIALS + blockIdx.x] = s_loss[t] * inv_n;
+    // every partial is rewritten at every call (a workgroup without a tile: 0)
+    if constexpr (CHAIN) {
+        if (t < S) p.loss_part[t * WN_VQ_PARTIALS + blockIdx.x] = s_loss[t] * inv_n;
+    } else {
+        if (t == 0) p.loss_part[blockIdx.x] = loss * inv_n;
+    }
 }
 
 // element o of [B][Bw][Le] -> its frame (b * le + l) and its j
@@ -391,83 +337,18 @@ __device__ __forceinline__ void vq_code_stats(const int32_t* idx, const float* s
     }
 }
 
-__global__ __launch_bounds__(64 * CWV) void vq_bwd_k(WnVq p, float c_enc, float c_cb, int code_blocks) {
-    if ((int)blockIdx.x >= code_blocks) return vq_bwd_elems(p, c_enc, code_blocks);
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int k = blockIdx.x * CWV + wave;
-    if (k >= p.K) return;
-    vq_code_grad(p.idx, p.enc, p.flat + p.cb_off, p.flat_grad + p.cb_off, c_cb, k, p.batch * p.le, p.bw, p.le, lane);
-}
-
-// EMA mode's backward: the element workgroups of vq_bwd_k as they are; a code's wave adds its frames e (ascending, as there) and counts them
-__global__ __launch_bounds__(64 * CWV) void vq_bwd_stats_k(WnVq p, float c_enc, int code_blocks, float* __restrict__ stat) {
-    if ((int)blockIdx.x >= code_blocks) return vq_bwd_elems(p, c_enc, code_blocks);
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int k = blockIdx.x * CWV + wave;
-    if (k >= p.K) return;
-    vq_code_stats(p.idx, p.enc, stat, p.flat_grad + p.cb_off, k, p.K, p.batch * p.le, p.bw, p.le, lane);
-}
-
-// ---- the residual chain's backward (wn_rvq_bwd / wn_rvq_bwd_stats): S x code_blocks leading workgroups, a wave per (stage, code) on that
-// stage's idx and its input r_s (enc for stage 0, res[s - 1] behind it); the element workgroups form d_e = d_q + c_enc (r_1 + ... + r_S),
-// the sum in ascending stage order (at S = 1: e - q, vq_bwd_elems' expression); an idx outside [0, K) in any stage: NaN, never dereferenced
+// the chain's element workgroups: d_e = d_q + c_enc (r_1 + ... + r_n), the residuals of the frame's n stages in ascending order (at
+// S = 1: e - q, vq_bwd_elems' expression), n = S, with NST the clip's stage count: the ACTIVE stages only, so n = S gives the chain's
+// bits.  An idx outside [0, K) in one of those stages: NaN, never dereferenced; an inactive idx is not looked at
+template <bool NST>
 __device__ __forceinline__ void rvq_bwd_elems(const WnVq& p, float c_enc, int first_block) {
     const int C = p.batch * p.le;
     const long total = (long)C * p.bw, step = (long)(gridDim.x - first_block) * (64 * CWV);
     for (long o = (long)(blockIdx.x - first_block) * (64 * CWV) + threadIdx.x; o < total; o += step) {
         int fr, j;
         elem_of(o, p.bw, p.le, fr, j);
-        bool ok = true;
-        float sum = 0.f;
-        for (int s = 0; s < p.S; ++s) {
-            ok = ok && (unsigned)p.idx[(long)s * C + fr] < (unsigned)p.K;
-            const float r = p.res[s * total + o];
-            sum = s ? sum + r : r;
-        }
-        p.d_enc[o] = fmaf(c_enc, ok ? sum : std::numeric_limits<float>::quiet_NaN(), p.d_q[o]);
-    }
-}
-
-// the (stage, code) of a leading workgroup's wave: false where the wave has no code
-__device__ __forceinline__ bool rvq_code_of(const WnVq& p, int code_blocks, int& s, int& k, const float*& src) {
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    s = blockIdx.x / code_blocks;
-    k = (blockIdx.x - s * code_blocks) * CWV + wave;
-    src = s ? p.res + (s - 1) * ((long)p.batch * p.le * p.bw) : p.enc;
-    return k < p.K;
-}
-
-__global__ __launch_bounds__(64 * CWV) void rvq_bwd_k(WnVq p, float c_enc, float c_cb, int code_blocks) {
-    if ((int)blockIdx.x >= p.S * code_blocks) return rvq_bwd_elems(p, c_enc, p.S * code_blocks);
-    int s, k;
-    const float* src;
-    if (!rvq_code_of(p, code_blocks, s, k, src)) return;
-    const long at = p.cb_off + (long)s * p.K * p.bw;
-    const int C = p.batch * p.le;
-    vq_code_grad(p.idx + (long)s * C, src, p.flat + at, p.flat_grad + at, c_cb, k, C, p.bw, p.le, threadIdx.x & 63);
-}
-
-__global__ __launch_bounds__(64 * CWV) void rvq_bwd_stats_k(WnVq p, float c_enc, int code_blocks, float* __restrict__ stat) {
-    if ((int)blockIdx.x >= p.S * code_blocks) return rvq_bwd_elems(p, c_enc, p.S * code_blocks);
-    int s, k;
-    const float* src;
-    if (!rvq_code_of(p, code_blocks, s, k, src)) return;
-    const int C = p.batch * p.le;
-    vq_code_stats(p.idx + (long)s * C, src, stat + (long)s * p.K * (p.bw + 1), p.flat_grad + p.cb_off + (long)s * p.K * p.bw, k, p.K, C,
-                  p.bw, p.le, threadIdx.x & 63);
-}
-
-// ---- quantiser dropout's backward (wn_rvq_bwd_n / wn_rvq_bwd_stats_n).  The code waves are the ones above: an inactive frame's idx is
-// -1, which vq_code_walk matches with no code, so a stage's rows cover exactly its active frames.  The element workgroups sum the
-// ACTIVE stages only, d_e = d_q + c_enc (r_1 + ... + r_n), ascending - rvq_bwd_elems' expressions, so n = S gives its bits -, NaN iff
-// an active stage's idx lies outside [0, K); an inactive idx is not looked at
-__device__ __forceinline__ void rvq_bwd_elems_n(const WnVq& p, const int32_t* nstage, float c_enc, int first_block) {
-    const int C = p.batch * p.le;
-    const long total = (long)C * p.bw, step = (long)(gridDim.x - first_block) * (64 * CWV);
-    for (long o = (long)(blockIdx.x - first_block) * (64 * CWV) + threadIdx.x; o < total; o += step) {
-        int fr, j;
-        elem_of(o, p.bw, p.le, fr, j);
-        const int n = nstage_of(nstage, fr / p.le, p.S);
+        int n = p.S;
+        if constexpr (NST) n = nstage_of(p.nstage, fr / p.le, p.S);
         bool ok = true;
         float sum = 0.f;
         for (int s = 0; s < n; ++s) {
@@ -479,25 +360,38 @@ __device__ __forceinline__ void rvq_bwd_elems_n(const WnVq& p, const int32_t* ns
     }
 }
 
-__global__ __launch_bounds__(64 * CWV) void rvq_bwd_n_k(WnVq p, const int32_t* __restrict__ nstage, float c_enc, float c_cb, int code_blocks) {
-    if ((int)blockIdx.x >= p.S * code_blocks) return rvq_bwd_elems_n(p, nstage, c_enc, p.S * code_blocks);
-    int s, k;
-    const float* src;
-    if (!rvq_code_of(p, code_blocks, s, k, src)) return;
-    const long at = p.cb_off + (long)s * p.K * p.bw;
-    const int C = p.batch * p.le;
-    vq_code_grad(p.idx + (long)s * C, src, p.flat + at, p.flat_grad + at, c_cb, k, C, p.bw, p.le, threadIdx.x & 63);
+// the (stage, code) of a leading workgroup's wave and the stage's input r_s (enc for stage 0, res[s - 1] behind it): false where the
+// wave has no code
+template <bool CHAIN>
+__device__ __forceinline__ bool rvq_code_of(const WnVq& p, int code_blocks, int& s, int& k, const float*& src) {
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    s = CHAIN ? blockIdx.x / code_blocks : 0;
+    k = (blockIdx.x - s * code_blocks) * CWV + wave;
+    src = s ? p.res + (s - 1) * ((long)p.batch * p.le * p.bw) : p.enc;
+    return k < p.K;
 }
 
-__global__ __launch_bounds__(64 * CWV) void rvq_bwd_stats_n_k(WnVq p, const int32_t* __restrict__ nstage, float c_enc, int code_blocks,
-                                                              float* __restrict__ stat) {
-    if ((int)blockIdx.x >= p.S * code_blocks) return rvq_bwd_elems_n(p, nstage, c_enc, p.S * code_blocks);
+// The backward of every entry, one launch: S x code_blocks leading workgroups (S = 1 without CHAIN: wn_vq_bwd*, where p.S and p.res are
+// not read), a wave per (stage, code) on that stage's idx and its input; the workgroups behind them form d_e elementwise.  STATS (EMA
+// mode, `stat` [S][K (bw + 1)]): a code's wave adds its frames and counts them, the codebook's rows of flat_grad become 0.  NST
+// (quantiser dropout) changes the element workgroups alone: an inactive frame's idx is -1, which vq_code_walk matches with no code, so
+// a stage's rows cover exactly its active frames as they are.
+template <bool CHAIN, bool NST, bool STATS>
+__global__ __launch_bounds__(64 * CWV) void vq_bwd_k(WnVq p, float c_enc, float c_cb, int code_blocks, float* __restrict__ stat) {
+    static_assert(CHAIN || !NST, "stage counts belong to the chain");
+    const int first_elem = CHAIN ? p.S * code_blocks : code_blocks;
+    if ((int)blockIdx.x >= first_elem) {
+        if constexpr (CHAIN) return rvq_bwd_elems<NST>(p, c_enc, first_elem);
+        else return vq_bwd_elems(p, c_enc, first_elem);
+    }
     int s, k;
     const float* src;
-    if (!rvq_code_of(p, code_blocks, s, k, src)) return;
-    const int C = p.batch * p.le;
-    vq_code_stats(p.idx + (long)s * C, src, stat + (long)s * p.K * (p.bw + 1), p.flat_grad + p.cb_off + (long)s * p.K * p.bw, k, p.K, C,
-                  p.bw, p.le, threadIdx.x & 63);
+    if (!rvq_code_of<CHAIN>(p, code_blocks, s, k, src)) return;
+    const long at = p.cb_off + (long)s * p.K * p.bw;
+    const int C = p.batch * p.le, lane = threadIdx.x & 63;
+    const int32_t* idx = p.idx + (long)s * C;
+    if constexpr (STATS) vq_code_stats(idx, src, stat + (long)s * p.K * (p.bw + 1), p.flat_grad + at, k, p.K, C, p.bw, p.le, lane);
+    else vq_code_grad(idx, src, p.flat + at, p.flat_grad + at, c_cb, k, C, p.bw, p.le, lane);
 }
 
 // ---- the EMA update.  Both launches form N' with THIS expression, so a code's N' has the same bits in either
@@ -621,36 +515,22 @@ __global__ __launch_bounds__(64 * CWV) void vq_ema_rows_k(float* __restrict__ cb
     if (lane == 0) state[k] = N1;                          // (behind the wave's reads of it: one wave, program order)
 }
 
-// q = c_0[idx_0] + c_1[idx_1] + ... over the first `stages` stages, ascending (one stage: wn_vq_lookup); idx [stages][frames], cb: K rows per stage
-__global__ __launch_bounds__(256) void vq_lookup_k(const int32_t* idx, const float* cb, float* q_out, int32_t* bad, int K, int bw, int le,
-                                                   long total, int stages, long frames) {
+// q = c_0[idx_0] + c_1[idx_1] + ... over the first n stages, ascending; idx [.][frames], cb: K rows per stage.  n = `stages` (1:
+// wn_vq_lookup); with NST (wn_rvq_lookup_n) the clip's stage count, which is NOT clamped: an n_b outside [1, stages] gives a NaN frame and
+// *bad, as does an ACTIVE idx outside [0, K) in either form; nothing of it is dereferenced, an inactive idx is not looked at
+template <bool NST>
+__global__ __launch_bounds__(256) void vq_lookup_k(const int32_t* idx, const int32_t* nstage, const float* cb, float* q_out, int32_t* bad,
+                                                   int stages, int K, int bw, int le, long total, long frames) {
     for (long o = (long)blockIdx.x * 256 + threadIdx.x; o < total; o += (long)gridDim.x * 256) {
         int fr, j;
         elem_of(o, bw, le, fr, j);
         bool ok = true;
-        float q = 0.f;
-        for (int s = 0; s < stages; ++s) {
-            const int ix = idx[s * frames + fr];
-            const bool in = (unsigned)ix < (unsigned)K;
-            const float c = in ? cb[((long)s * K + ix) * bw + j] : 0.f;
-            q = s ? q + c : c;
-            ok = ok && in;
+        int n = stages;
+        if constexpr (NST) {
+            const int n_raw = nstage[fr / le];
+            ok = n_raw >= 1 && n_raw <= stages;
+            n = ok ? n_raw : 0;
         }
-        q_out[o] = ok ? q : std::numeric_limits<float>::quiet_NaN();
-        if (!ok && bad) *bad = 1;                          // (every writer stores the same value)
-    }
-}
-
-// per-clip stage counts (wn_rvq_lookup_n): q = the sum of the first n_b stages' rows, ascending; idx [S][frames].  An n_b outside [1, S]
-// or an ACTIVE idx outside [0, K): a NaN frame and *bad, nothing dereferenced; an inactive idx is not looked at
-__global__ __launch_bounds__(256) void vq_lookup_n_k(const int32_t* idx, const int32_t* nstage, const float* cb, float* q_out, int32_t* bad,
-                                                     int S, int K, int bw, int le, long total, long frames) {
-    for (long o = (long)blockIdx.x * 256 + threadIdx.x; o < total; o += (long)gridDim.x * 256) {
-        int fr, j;
-        elem_of(o, bw, le, fr, j);
-        const int n_raw = nstage[fr / le];
-        bool ok = n_raw >= 1 && n_raw <= S;
-        const int n = ok ? n_raw : 0;
         float q = 0.f;
         for (int s = 0; s < n; ++s) {
             const int ix = idx[s * frames + fr];
@@ -666,39 +546,37 @@ __global__ __launch_bounds__(256) void vq_lookup_n_k(const int32_t* idx, const i
 
 }  // namespace
 
-// The callers (wn_api.hip) have checked the arguments.
+// The callers (wn_api.hip) have checked the arguments.  p.res != NULL: the residual chain over p.S stages (an entry's choice - wn_rvq_*
+// at S = 1 is the chain); NULL: one stage, p.S is not read.  p.nstage != NULL (the chain alone): stage counts per clip.
+static int vq_stages(const WnVq& p) { return p.res ? p.S : 1; }
+
 int wn_launch_vq_fwd(const WnVq& p, hipStream_t st) {
     if (p.batch <= 0) return 0;
     if (p.counts) {
-        hipError_t e = hipMemsetAsync(p.counts, 0, sizeof(int32_t) * p.K, st);
+        hipError_t e = hipMemsetAsync(p.counts, 0, sizeof(int32_t) * vq_stages(p) * p.K, st);
         if (e != hipSuccess) return wn_set_error(e, __FILE__, __LINE__);
     }
-    const double n = (double)p.batch * p.le * p.bw;
-    hipLaunchKernelGGL(vq_fwd_k, dim3(WN_VQ_PARTIALS), dim3(64 * NWV), 0, st, p, (float)(1.0 / n));
+    const double n = (double)p.batch * p.le * p.bw;        // with stage counts too, the FIXED denominator: vq_loss is the batch expectation
+    const auto k = !p.res ? vq_fwd_k<false, false> : p.nstage ? vq_fwd_k<true, true> : vq_fwd_k<true, false>;
+    hipLaunchKernelGGL(k, dim3(WN_VQ_PARTIALS), dim3(64 * NWV), 0, st, p, (float)(1.0 / n));
     WN_CHECK_LAUNCH();
     return 0;
 }
 
-int wn_launch_vq_bwd(const WnVq& p, float beta, float g_scale, hipStream_t st) {
-    if (p.batch <= 0) return 0;
-    const double s = 2.0 / ((double)p.batch * p.le * p.bw);
-    const int code_blocks = (p.K + CWV - 1) / CWV;
-    const long total = (long)p.batch * p.le * p.bw;
-    const int elem_blocks = (int)std::min<long>((total + 64 * CWV - 1) / (64 * CWV), 256);
-    hipLaunchKernelGGL(vq_bwd_k, dim3(code_blocks + elem_blocks), dim3(64 * CWV), 0, st, p, (float)((double)g_scale * beta * s),
-                       (float)((double)g_scale * s), code_blocks);
-    WN_CHECK_LAUNCH();
-    return 0;
+template <bool STATS>
+static auto vq_bwd_kernel(const WnVq& p) {
+    return !p.res ? vq_bwd_k<false, false, STATS> : p.nstage ? vq_bwd_k<true, true, STATS> : vq_bwd_k<true, false, STATS>;
 }
 
-int wn_launch_vq_bwd_stats(const WnVq& p, float beta, float g_scale, float* stat, hipStream_t st) {
+// stat != NULL: the stats form (EMA mode)
+int wn_launch_vq_bwd(const WnVq& p, float beta, float g_scale, float* stat, hipStream_t st) {
     if (p.batch <= 0) return 0;
-    const double s = 2.0 / ((double)p.batch * p.le * p.bw);
-    const int code_blocks = (p.K + CWV - 1) / CWV;
     const long total = (long)p.batch * p.le * p.bw;
+    const double s = 2.0 / (double)total;
+    const int code_blocks = (p.K + CWV - 1) / CWV;
     const int elem_blocks = (int)std::min<long>((total + 64 * CWV - 1) / (64 * CWV), 256);
-    hipLaunchKernelGGL(vq_bwd_stats_k, dim3(code_blocks + elem_blocks), dim3(64 * CWV), 0, st, p, (float)((double)g_scale * beta * s),
-                       code_blocks, stat);
+    hipLaunchKernelGGL(stat ? vq_bwd_kernel<true>(p) : vq_bwd_kernel<false>(p), dim3(vq_stages(p) * code_blocks + elem_blocks), dim3(64 * CWV),
+                       0, st, p, (float)((double)g_scale * beta * s), (float)((double)g_scale * s), code_blocks, stat);
     WN_CHECK_LAUNCH();
     return 0;
 }
@@ -715,89 +593,18 @@ int wn_launch_vq_ema_update(float* flat, long cb_off, const float* stat, float* 
     return 0;
 }
 
-int wn_launch_vq_lookup(const int32_t* idx, const float* flat, long cb_off, float* q_out, int32_t* bad, int stages, int K, int bw, int le,
-                        int batch, hipStream_t st) {
+// nstage NULL: q = the sum of the first `stages` stages' rows (1: the plain lookup); else `stages` = S and every clip takes its own count
+int wn_launch_vq_lookup(const int32_t* idx, const int32_t* nstage, const float* flat, long cb_off, float* q_out, int32_t* bad, int stages,
+                        int K, int bw, int le, int batch, hipStream_t st) {
     if (batch <= 0) return 0;
     if (bad) {
         hipError_t e = hipMemsetAsync(bad, 0, sizeof(int32_t), st);
         if (e != hipSuccess) return wn_set_error(e, __FILE__, __LINE__);
     }
     const long total = (long)batch * le * bw;
-    hipLaunchKernelGGL(vq_lookup_k, dim3((unsigned)std::min<long>((total + 255) / 256, 1024)), dim3(256), 0, st, idx, flat + cb_off, q_out, bad,
-                       K, bw, le, total, stages, (long)batch * le);
+    hipLaunchKernelGGL(nstage ? vq_lookup_k<true> : vq_lookup_k<false>, dim3((unsigned)std::min<long>((total + 255) / 256, 1024)), dim3(256), 0,
+                       st, idx, nstage, flat + cb_off, q_out, bad, stages, K, bw, le, total, (long)batch * le);
     WN_CHECK_LAUNCH();
     return 0;
 }
 
-// ---- the residual chain (p.S stages; p.idx [S][C], p.counts [S][K], p.res [S][B][Bw][Le], p.loss_part [S][WN_VQ_PARTIALS])
-int wn_launch_rvq_fwd(const WnVq& p, hipStream_t st) {
-    if (p.batch <= 0) return 0;
-    if (p.counts) {
-        hipError_t e = hipMemsetAsync(p.counts, 0, sizeof(int32_t) * p.S * p.K, st);
-        if (e != hipSuccess) return wn_set_error(e, __FILE__, __LINE__);
-    }
-    const double n = (double)p.batch * p.le * p.bw;
-    hipLaunchKernelGGL(rvq_fwd_k, dim3(WN_VQ_PARTIALS), dim3(64 * NWV), 0, st, p, (float)(1.0 / n));
-    WN_CHECK_LAUNCH();
-    return 0;
-}
-
-// (the scalars and the element workgroups' count: as wn_launch_vq_bwd forms them)
-int wn_launch_rvq_bwd(const WnVq& p, float beta, float g_scale, float* stat, hipStream_t st) {
-    if (p.batch <= 0) return 0;
-    const double s = 2.0 / ((double)p.batch * p.le * p.bw);
-    const int code_blocks = (p.K + CWV - 1) / CWV;
-    const long total = (long)p.batch * p.le * p.bw;
-    const int elem_blocks = (int)std::min<long>((total + 64 * CWV - 1) / (64 * CWV), 256);
-    const dim3 grid(p.S * code_blocks + elem_blocks);
-    const float c_enc = (float)((double)g_scale * beta * s);
-    if (stat)
-        hipLaunchKernelGGL(rvq_bwd_stats_k, grid, dim3(64 * CWV), 0, st, p, c_enc, code_blocks, stat);
-    else
-        hipLaunchKernelGGL(rvq_bwd_k, grid, dim3(64 * CWV), 0, st, p, c_enc, (float)((double)g_scale * s), code_blocks);
-    WN_CHECK_LAUNCH();
-    return 0;
-}
-
-// ---- quantiser dropout (nstage: batch int32 stage counts on the device): the launches above with the _n kernels, the same grids
-int wn_launch_rvq_fwd_n(const WnVq& p, const int32_t* nstage, hipStream_t st) {
-    if (p.batch <= 0) return 0;
-    if (p.counts) {
-        hipError_t e = hipMemsetAsync(p.counts, 0, sizeof(int32_t) * p.S * p.K, st);
-        if (e != hipSuccess) return wn_set_error(e, __FILE__, __LINE__);
-    }
-    const double n = (double)p.batch * p.le * p.bw;        // the FIXED denominator: vq_loss is the batch expectation
-    hipLaunchKernelGGL(rvq_fwd_n_k, dim3(WN_VQ_PARTIALS), dim3(64 * NWV), 0, st, p, nstage, (float)(1.0 / n));
-    WN_CHECK_LAUNCH();
-    return 0;
-}
-
-int wn_launch_rvq_bwd_n(const WnVq& p, const int32_t* nstage, float beta, float g_scale, float* stat, hipStream_t st) {
-    if (p.batch <= 0) return 0;
-    const double s = 2.0 / ((double)p.batch * p.le * p.bw);
-    const int code_blocks = (p.K + CWV - 1) / CWV;
-    const long total = (long)p.batch * p.le * p.bw;
-    const int elem_blocks = (int)std::min<long>((total + 64 * CWV - 1) / (64 * CWV), 256);
-    const dim3 grid(p.S * code_blocks + elem_blocks);
-    const float c_enc = (float)((double)g_scale * beta * s);
-    if (stat)
-        hipLaunchKernelGGL(rvq_bwd_stats_n_k, grid, dim3(64 * CWV), 0, st, p, nstage, c_enc, code_blocks, stat);
-    else
-        hipLaunchKernelGGL(rvq_bwd_n_k, grid, dim3(64 * CWV), 0, st, p, nstage, c_enc, (float)((double)g_scale * s), code_blocks);
-    WN_CHECK_LAUNCH();
-    return 0;
-}
-
-int wn_launch_vq_lookup_n(const int32_t* idx, const int32_t* nstage, const float* flat, long cb_off, float* q_out, int32_t* bad, int S, int K,
-                          int bw, int le, int batch, hipStream_t st) {
-    if (batch <= 0) return 0;
-    if (bad) {
-        hipError_t e = hipMemsetAsync(bad, 0, sizeof(int32_t), st);
-        if (e != hipSuccess) return wn_set_error(e, __FILE__, __LINE__);
-    }
-    const long total = (long)batch * le * bw;
-    hipLaunchKernelGGL(vq_lookup_n_k, dim3((unsigned)std::min<long>((total + 255) / 256, 1024)), dim3(256), 0, st, idx, nstage, flat + cb_off,
-                       q_out, bad, S, K, bw, le, total, (long)batch * le);
-    WN_CHECK_LAUNCH();
-    return 0;
-}

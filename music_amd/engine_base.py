@@ -369,56 +369,36 @@ class EngineBase:
         one launch); ws keeps it for the backward, vq_idx holds -1 where a clip took no part."""
         B, _, Le = enc.shape
         dev = self.device
+        # S > 1: the residual chain, still one launch: idx (S, B, Le), counts (S, K), the loss partials per stage, and res[s] = what
+        # stage s left over, which the backward reads.  S = 1: the one-stage entry, no stage axis, no res, no stage counts
+        S, chain = self.vq_S, self.vq_S > 1
+        lead = (S,) if chain else ()
+        nstage = nstage if chain else None
         q = torch.empty_like(enc)
-        if self.vq_S > 1:
-            # the residual chain, still one launch: idx (S, B, Le), counts (S, K), the loss partials per stage, and res[s] = what
-            # stage s left over, which the backward reads
-            S = self.vq_S
-            idx = torch.empty(S, B, Le, dtype=torch.int32, device=dev)
-            counts = torch.empty(S, self.vq_K, dtype=torch.int32, device=dev)
-            part = torch.empty(S, _lib.VQ_NUM_PARTIALS, dtype=torch.float32, device=dev)
-            res = torch.empty((S,) + tuple(enc.shape), dtype=torch.float32, device=dev)
-            if nstage is not None:
-                call("wn_rvq_fwd_n", ptr(enc), ptr(self.flat), self.vq_off, ptr(nstage), ptr(q), ptr(idx), ptr(counts), ptr(res), ptr(part),
-                     S, self.vq_K, self.Bw, Le, B, st)
-                ws.update(enc_pre=enc, vq_idx=idx, vq_counts=counts, vq_part=part, vq_res=res, vq_g=1.0, vq_nstage=nstage)
-                self.last_vq = VqStats(part, counts, B * Le, self.vq_beta, self.vq_loss_coef, final_res=res[S - 1])
-                return q
-            call("wn_rvq_fwd", ptr(enc), ptr(self.flat), self.vq_off, ptr(q), ptr(idx), ptr(counts), ptr(res), ptr(part), S, self.vq_K,
-                 self.Bw, Le, B, st)
-            ws.update(enc_pre=enc, vq_idx=idx, vq_counts=counts, vq_part=part, vq_res=res, vq_g=1.0, vq_nstage=None)
-            self.last_vq = VqStats(part, counts, B * Le, self.vq_beta, self.vq_loss_coef)
-            return q
-        idx = torch.empty(B, Le, dtype=torch.int32, device=dev)
-        counts = torch.empty(self.vq_K, dtype=torch.int32, device=dev)
-        part = torch.empty(_lib.VQ_NUM_PARTIALS, dtype=torch.float32, device=dev)
-        call("wn_vq_fwd", ptr(enc), ptr(self.flat), self.vq_off, ptr(q), ptr(idx), ptr(counts), ptr(part), self.vq_K, self.Bw, Le, B, st)
-        ws.update(enc_pre=enc, vq_idx=idx, vq_counts=counts, vq_part=part, vq_g=1.0)
-        self.last_vq = VqStats(part, counts, B * Le, self.vq_beta, self.vq_loss_coef)
+        idx = torch.empty(lead + (B, Le), dtype=torch.int32, device=dev)
+        counts = torch.empty(lead + (self.vq_K,), dtype=torch.int32, device=dev)
+        part = torch.empty(lead + (_lib.VQ_NUM_PARTIALS,), dtype=torch.float32, device=dev)
+        res = torch.empty(lead + tuple(enc.shape), dtype=torch.float32, device=dev) if chain else None
+        call("wn_vq_fwd" if not chain else "wn_rvq_fwd" if nstage is None else "wn_rvq_fwd_n",
+             ptr(enc), ptr(self.flat), self.vq_off, *([ptr(nstage)] if nstage is not None else []), ptr(q), ptr(idx), ptr(counts),
+             *([ptr(res)] if chain else []), ptr(part), *([S] if chain else []), self.vq_K, self.Bw, Le, B, st)
+        ws.update(enc_pre=enc, vq_idx=idx, vq_counts=counts, vq_part=part, vq_g=1.0, **(dict(vq_res=res, vq_nstage=nstage) if chain else {}))
+        self.last_vq = VqStats(part, counts, B * Le, self.vq_beta, self.vq_loss_coef, final_res=None if nstage is None else res[S - 1])
         return q
 
     def vq_bwd(self, ws, d_q, st):
         """d_q (what wn_cond_proj_bwd wrote as d enc) -> d e in place, and the codebook's gradient into the tail of flat_grad (wn_vq_bwd,
         one launch); ws["vq_g"]: the upstream scalar on vq_loss (1 in the fused step, autograd's in the module's backward)."""
         B, _, Le = d_q.shape
-        if self.vq_S > 1 and ws.get("vq_nstage") is not None:
-            # the forward ran with stage counts: the same launch over the ACTIVE stages of every frame (idx = -1 matches no code)
-            head = (ptr(ws["enc_pre"]), ptr(ws["vq_idx"]), ptr(ws["vq_res"]), ptr(ws["vq_nstage"]), ptr(d_q), ptr(self.flat), self.vq_off,
-                    self.vq_beta, float(ws.get("vq_g", 1.0)), ptr(d_q), ptr(self.flat_grad))
-            if self.vq_ema:
-                return call("wn_rvq_bwd_stats_n", *head, ptr(self.vq_stat), self.vq_S, self.vq_K, self.Bw, Le, B, st)
-            return call("wn_rvq_bwd_n", *head, self.vq_S, self.vq_K, self.Bw, Le, B, st)
-        if self.vq_S > 1:
-            head = (ptr(ws["enc_pre"]), ptr(ws["vq_idx"]), ptr(ws["vq_res"]), ptr(d_q), ptr(self.flat), self.vq_off, self.vq_beta,
-                    float(ws.get("vq_g", 1.0)), ptr(d_q), ptr(self.flat_grad))
-            if self.vq_ema:
-                return call("wn_rvq_bwd_stats", *head, ptr(self.vq_stat), self.vq_S, self.vq_K, self.Bw, Le, B, st)
-            return call("wn_rvq_bwd", *head, self.vq_S, self.vq_K, self.Bw, Le, B, st)
-        if self.vq_ema:                     # the same d e; the frames' counts and sums per code into vq_stat, zeros as the codebook's gradient
-            return call("wn_vq_bwd_stats", ptr(ws["enc_pre"]), ptr(ws["vq_idx"]), ptr(d_q), ptr(self.flat), self.vq_off, self.vq_beta,
-                        float(ws.get("vq_g", 1.0)), ptr(d_q), ptr(self.flat_grad), ptr(self.vq_stat), self.vq_K, self.Bw, Le, B, st)
-        call("wn_vq_bwd", ptr(ws["enc_pre"]), ptr(ws["vq_idx"]), ptr(d_q), ptr(self.flat), self.vq_off, self.vq_beta, float(ws.get("vq_g", 1.0)),
-             ptr(d_q), ptr(self.flat_grad), self.vq_K, self.Bw, Le, B, st)
+        # a chain hands over res and S; a forward that ran with stage counts the counts: the same launch over the ACTIVE stages of every
+        # frame (idx = -1 matches no code); EMA mode: the same d e, the frames' counts and sums per code into vq_stat, zeros as the
+        # codebook's gradient
+        chain = self.vq_S > 1
+        nstage = ws.get("vq_nstage") if chain else None
+        call(("wn_rvq_bwd" if chain else "wn_vq_bwd") + ("_stats" if self.vq_ema else "") + ("_n" if nstage is not None else ""),
+             ptr(ws["enc_pre"]), ptr(ws["vq_idx"]), *([ptr(ws["vq_res"])] if chain else []), *([ptr(nstage)] if nstage is not None else []),
+             ptr(d_q), ptr(self.flat), self.vq_off, self.vq_beta, float(ws.get("vq_g", 1.0)), ptr(d_q), ptr(self.flat_grad),
+             *([ptr(self.vq_stat)] if self.vq_ema else []), *([self.vq_S] if chain else []), self.vq_K, self.Bw, Le, B, st)
 
     @property
     def vq_loss_coef(self):
@@ -443,11 +423,10 @@ class EngineBase:
         """wn_vq_ema_update (two launches) on the stats of the last backward: the module's running state and the codebook's rows of
         the flat buffer, in place.  Behind the optimizer's update - which leaves those rows alone, their gradient being 0 - and in
         front of the EMA shadow's.  `guard`: the GradGuard that decided the step; a skipped step changes nothing."""
-        tail = (self.vq_K, self.Bw, self.vq_decay, self.vq_eps, self.vq_restart, None if guard is None else guard.state_ptr(), _lib.stream())
-        head = (ptr(self.flat), self.vq_off, ptr(self.vq_stat), ptr(self.vq_ema_state()), ptr(self.vq_ema_work), ptr(self.vq_ema_info))
-        if self.vq_S > 1:                   # every stage on its own block of stat, state, work and info; still two launches
-            return call("wn_rvq_ema_update", *head, self.vq_S, *tail)
-        call("wn_vq_ema_update", *head, *tail)
+        chain = self.vq_S > 1               # every stage on its own block of stat, state, work and info; still two launches
+        call("wn_rvq_ema_update" if chain else "wn_vq_ema_update", ptr(self.flat), self.vq_off, ptr(self.vq_stat), ptr(self.vq_ema_state()),
+             ptr(self.vq_ema_work), ptr(self.vq_ema_info), *([self.vq_S] if chain else []), self.vq_K, self.Bw, self.vq_decay, self.vq_eps,
+             self.vq_restart, None if guard is None else guard.state_ptr(), _lib.stream())
 
     def vq_restarted(self):
         """Codes restarted since the last call (reads the device's counter back and zeroes it)."""
@@ -475,39 +454,29 @@ class EngineBase:
         codes (B, n, Le), 1 <= n <= S, the first n stages' codes -> the sum of their rows in stage order (wn_rvq_lookup).  Codes with
         -1 in a clip's absent stages (what a forward with stage counts hands out; vq_dropout.counts_of_codes checks the pattern on the
         host) -> every clip the sum of ITS stages' rows (wn_rvq_lookup_n)."""
-        if self.vq_S > 1:
-            if codes.dim() != 3 or not 1 <= codes.shape[1] <= self.vq_S:
-                raise ValueError("music_amd: vq_stages = %d: codes must be (B, n, Le) with 1 <= n <= %d, not %s"
-                                 % (self.vq_S, self.vq_S, tuple(codes.shape)))
-            nstage = None if codes.is_floating_point() else vq_dropout.counts_of_codes(codes, self.vq_S)
-            if nstage is not None:
-                B, n, Le = codes.shape
-                full = torch.full((self.vq_S, B, Le), -1, dtype=torch.int32, device=self.device)
-                full[:n] = codes.to(device=self.device, dtype=torch.int32).permute(1, 0, 2)
-                q = torch.empty(B, self.Bw, Le, dtype=torch.float32, device=self.device)
-                bad = torch.zeros(1, dtype=torch.int32, device=self.device)
-                nstage = torch.from_numpy(nstage).to(self.device)
-                call("wn_rvq_lookup_n", ptr(full), ptr(nstage), ptr(self.flat), self.vq_off, ptr(q), ptr(bad), self.vq_S, self.vq_K, self.Bw, Le,
-                     B, _lib.stream())
-                if int(bad.item()):
-                    raise ValueError("music_amd: a code lies outside [0, %d)" % self.vq_K)
-                return q
-            codes = codes.to(device=self.device, dtype=torch.int32).permute(1, 0, 2).contiguous()
-            n, B, Le = codes.shape
-            q = torch.empty(B, self.Bw, Le, dtype=torch.float32, device=self.device)
-            bad = torch.zeros(1, dtype=torch.int32, device=self.device)
-            call("wn_rvq_lookup", ptr(codes), ptr(self.flat), self.vq_off, ptr(q), ptr(bad), self.vq_S, n, self.vq_K, self.Bw, Le, B,
-                 _lib.stream())
-            if int(bad.item()):
-                raise ValueError("music_amd: a code lies outside [0, %d)" % self.vq_K)
-            return q
-        if codes.dim() != 2:
+        S, chain, dev = self.vq_S, self.vq_S > 1, self.device
+        nstage = None
+        if chain:
+            if codes.dim() != 3 or not 1 <= codes.shape[1] <= S:
+                raise ValueError("music_amd: vq_stages = %d: codes must be (B, n, Le) with 1 <= n <= %d, not %s" % (S, S, tuple(codes.shape)))
+            nstage = None if codes.is_floating_point() else vq_dropout.counts_of_codes(codes, S)
+        elif codes.dim() != 2:
             raise ValueError("music_amd: codes must be (B, Le), not %s" % (tuple(codes.shape),))
-        codes = codes.to(device=self.device, dtype=torch.int32).contiguous()
-        B, Le = codes.shape
-        q = torch.empty(B, self.Bw, Le, dtype=torch.float32, device=self.device)
-        bad = torch.zeros(1, dtype=torch.int32, device=self.device)
-        call("wn_vq_lookup", ptr(codes), ptr(self.flat), self.vq_off, ptr(q), ptr(bad), self.vq_K, self.Bw, Le, B, _lib.stream())
+        idx = codes.to(device=dev, dtype=torch.int32)
+        if chain:
+            idx = idx.permute(1, 0, 2)                                     # (n, B, Le): the stage in front, as the forward's vq_idx
+        n = idx.shape[0] if chain else 1
+        if nstage is not None:                                             # all S stages, -1 behind the n given ones
+            full = torch.full((S,) + tuple(idx.shape[1:]), -1, dtype=torch.int32, device=dev)
+            full[:n] = idx
+            idx, nstage = full, torch.from_numpy(nstage).to(dev)
+        idx = idx.contiguous()
+        B, Le = idx.shape[-2:]
+        q = torch.empty(B, self.Bw, Le, dtype=torch.float32, device=dev)
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        call("wn_vq_lookup" if not chain else "wn_rvq_lookup" if nstage is None else "wn_rvq_lookup_n",
+             ptr(idx), *([ptr(nstage)] if nstage is not None else []), ptr(self.flat), self.vq_off, ptr(q), ptr(bad), *([S] if chain else []),
+             *([n] if chain and nstage is None else []), self.vq_K, self.Bw, Le, B, _lib.stream())
         if int(bad.item()):
             raise ValueError("music_amd: a code lies outside [0, %d)" % self.vq_K)
         return q
