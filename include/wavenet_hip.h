@@ -621,7 +621,13 @@ int wn_cond_expand(const float* tab, int64_t tab_bstride, int tab_pitch, int row
                    float* out, int64_t out_bstride, int out_pitch, int batch, wn_stream_t stream);
 /* Gradient of the conditioning table: out[b][row][j] = sum over t in [t_lo,t_hi) with idx(t) == j of
  * in[b][row][t]; idx as in wn_resblock_fwd (mode 1 stretch by q, mode 2 tile modulo le)
- * (autograd of wavenet_autoencoder/model1.py:227-247). */
+ * (autograd of wavenet_autoencoder/model1.py:227-247).  Only out[b][row][0 .. le) is written (out_pitch may be larger; what lies
+ * behind column le stays).  Values of `in` outside [t_lo, t_hi) do not count and are not read, NaN included.  An empty window
+ * (t_hi <= t_lo) with valid pointers writes le zeros per row - the sum over nothing; callers hand in a window, not a promise that
+ * it is non-empty.  `in` and `out` are required exactly when something is launched, that is whenever rows, batch and le are all
+ * > 0 (NULL: -4, nothing launched); rows, batch or le <= 0 returns 0 and writes nothing.  Refused with -4 and a message, as by
+ * wn_cond_expand: a mode outside {1, 2}, q <= 0 under mode 1 (a negative q would start the last bucket in front of the row), and
+ * le > 1024.  Under mode 2 q is ignored, whatever its value.  Fixed summation order: the same inputs give the same bits. */
 int wn_cond_grad(const float* in, int64_t in_bstride, int in_pitch, int rows, int t_lo, int t_hi, int mode, int le,
                  int q, float* out, int64_t out_bstride, int out_pitch, int batch, wn_stream_t stream);
 /* Backward of AvgPool1d: out[b][c][t0 + j*pool + k] = denc[b][c][j] / pool (j < n_out), 0 up to t_hi. */
@@ -635,7 +641,10 @@ int wn_avgpool(const float* in, int64_t in_bstride, int in_pitch, int t0, int po
 
 /* One-hot input on device from int32 codes (B,T) -> float32 (B,Q,T).  scrambled=1 reproduces
  * faster_audio_data.one_hot_encode's reshape (wavenet/faster_audio_data.py:77-81);
- * scrambled=0 is the textbook layout fast_generate.py:159-160 builds. */
+ * scrambled=0 is the textbook layout fast_generate.py:159-160 builds.  Scrambled: sample s of a clip puts its one at flat offset
+ * s*q + code of that clip's q*t floats; textbook: out[b][code][s] = 1.  Every other element of the batch*q*t floats is set to 0,
+ * nothing behind them is touched.  A code outside [0, q) sets no one (its sample stays all zero).  batch, q or t <= 0 returns 0 and
+ * writes nothing (NULL pointers accepted). */
 int wn_onehot(const int32_t* codes, float* out, int batch, int q, int t, int scrambled, wn_stream_t stream);
 
 /* mu-law (wavenet/audio_func.py:5-39): encode through the 255-entry float32 threshold table of the

@@ -689,7 +689,8 @@ int wn_gather_grads2(const float* packed, const int32_t* idx, const int32_t* idx
     return wn_launch_gather_grads2(packed, idx, idx2, flat_grad, n, (hipStream_t)stream);
 }
 int wn_onehot(const int32_t* codes, float* out, int batch, int q, int t, int scrambled, wn_stream_t stream) {
-    if (batch > 0 && q > 0 && t > 0) WN_REQUIRE("wn_onehot", codes, out);
+    if (batch <= 0 || q <= 0 || t <= 0) return 0;                // no work: nothing is written, no pointer is required
+    WN_REQUIRE("wn_onehot", codes, out);
     return wn_launch_onehot(codes, out, batch, q, t, scrambled, (hipStream_t)stream);
 }
 int wn_mulaw_encode_tbl(const float* audio, const float* thresholds, uint8_t* codes, int64_t n, wn_stream_t stream) {
@@ -850,7 +851,10 @@ int wn_causal_fwd_codes(const int32_t* codes, int scrambled, const float* wt, co
 
 int wn_cond_grad(const float* in, int64_t in_bstride, int in_pitch, int rows, int t_lo, int t_hi, int mode, int le,
                  int q, float* out, int64_t out_bstride, int out_pitch, int batch, wn_stream_t stream) {
-    if (batch > 0 && rows > 0 && t_hi > t_lo) WN_REQUIRE("wn_cond_grad", in, out);
+    if ((mode != 1 && mode != 2) || (mode == 1 && q <= 0))
+        return wn_set_error_msg(-4, "wn_cond_grad: mode must be 1 (stretch, q > 0) or 2 (tile)");
+    // the launcher launches whenever rows, batch, le > 0 - an empty window too, which stores le zeros per row through `out`
+    if (batch > 0 && rows > 0 && le > 0) WN_REQUIRE("wn_cond_grad", in, out);
     return wn_launch_cond_grad(in, in_bstride, in_pitch, rows, t_lo, t_hi, mode, le, q, out, out_bstride, out_pitch, batch,
                                (hipStream_t)stream);
 }

@@ -253,8 +253,8 @@ __global__ void onehot_k(const int32_t* __restrict__ idx, float* __restrict__ ou
     out[b * (long)q * t + pos] = 1.0f;
 }
 int wn_launch_onehot(const int32_t* idx, float* out, int batch, int q, int t, int scrambled, hipStream_t st) {
+    if (batch <= 0 || q <= 0 || t <= 0) return 0;               // no work (q <= 0 too: the memset below would take a huge size)
     long total = (long)batch * t;
-    if (total <= 0) return 0;
     hipError_t e = hipMemsetAsync(out, 0, (size_t)total * q * sizeof(float), st);
     if (e != hipSuccess) return wn_set_error(e, __FILE__, __LINE__);
     hipLaunchKernelGGL(onehot_k, dim3((int)((total + 255) / 256)), dim3(256), 0, st, idx, out, q, t, scrambled, total);

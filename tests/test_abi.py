@@ -232,3 +232,27 @@ def test_null_required_pointers_are_reported_not_dereferenced():
         a = list(dec)
         a[i] = None
         bad("wn_decode", arg, *a)
+
+
+def test_cond_grad_and_onehot_guards_agree_with_their_launchers():
+    """wn_cond_grad launches whenever rows, batch and le are > 0 - an empty window too, which stores le zeros per row - so that is
+    when `in` and `out` are required; mode and q are checked as wn_cond_expand checks them; wn_onehot with q <= 0 has no work.
+    Every case here is refused or empty before a launch: no device is needed."""
+    from music_amd import _lib
+    lib = _lib.load()
+    P = 1 << 20
+    cg = lambda in_, out, rows=4, t_lo=8, t_hi=8, mode=2, le=5, q=1, batch=2: lib.wn_cond_grad(
+        in_, 64 * 64, 64, rows, t_lo, t_hi, mode, le, q, out, 64, 8, batch, None)
+    for t_hi in (8, 7, 40):                                  # an empty window, a reversed one, a real one: NULL is refused alike
+        assert cg(P, None, t_hi=t_hi) == -4 and "wn_cond_grad" in lib.wn_last_error().decode() and "'out'" in lib.wn_last_error().decode()
+        assert cg(None, P, t_hi=t_hi) == -4 and "'in'" in lib.wn_last_error().decode()
+    for kw in (dict(rows=0), dict(batch=0), dict(le=0), dict(le=-1)):  # nothing would be launched: NULLs are fine
+        assert cg(None, None, t_hi=40, **kw) == 0
+    for kw in (dict(mode=0), dict(mode=3), dict(mode=-1), dict(mode=1, q=0), dict(mode=1, q=-1), dict(le=1025), dict(mode=1, q=3, le=1025)):
+        assert cg(P, P, t_hi=40, **kw) == -4, kw
+        assert "cond_grad" in lib.wn_last_error().decode()
+    for q in (0, -1, -(1 << 31), 1 << 20):
+        assert lib.wn_onehot(None, None, 3, q, 16, 1, None) == (0 if q <= 0 else -4)
+        if q <= 0:
+            assert lib.wn_onehot(P, P, 3, q, 16, 0, None) == 0
+    assert lib.wn_onehot(None, None, 0, 4, 16, 0, None) == 0 and lib.wn_onehot(None, None, 3, 4, 0, 0, None) == 0
