@@ -809,6 +809,47 @@ int wn_decode_batch_samp(int filter_width, int n_layers, int R, int D, int S, in
 int wn_sample_logits(const float* logits, int64_t n, int Q, int64_t ld, const wn_sampling* samp, float temperature, uint64_t seed,
                      int top_k, float top_p, int64_t step0, const float* u, int32_t* codes, float* probs, wn_stream_t stream);
 
+/* POSITION-WINDOWED sampling (ABI 9 still: new entries only).  A code stream that interleaves several alphabets - the residual
+ * quantiser's frame-major stream l0s0, l0s1, .., l1s0, .. with token = s K + code - allows at stream position p only the tokens
+ * of stage p mod S.  A launch carries a WINDOW TABLE of `period` pairs (lo_j, hi_j), 0 <= lo_j < hi_j <= Q, and a position
+ * win_pos0 >= 0; step s of the launch (row s of a logits matrix) uses pair j = (win_pos0 + s) mod period.  The rule:
+ *   - The window is applied FIRST: the row is the hi - lo logits l[lo .. hi), and steps 1-5 of wn_decode_batch_samp's rule apply
+ *     to it as if Q were hi - lo.  The maximum, every sum, the top-k count, the nucleus search and the smallest real key are taken
+ *     over the window only; top_k >= hi - lo means no top-k filter AT THAT POSITION (widths may differ between positions).
+ *   - Entries outside the window are never part of the result: their probability in probs_out is an exact 0 and their values
+ *     influence nothing - not a NaN, not a value far above every logit inside.
+ *   - Codes are reported in the full alphabet, lo + index.  Greedy (temperature <= 0) is the first-index argmax inside the window,
+ *     its probs_out the plain softmax over the window.
+ *   - The code lies in [lo, hi) whatever the logits hold: with u above the rounded total it is the largest index of the kept set
+ *     inside the window (hi - 1 without filters); on a row whose logits inside the window are all -inf or NaN the probabilities
+ *     are unspecified and the code is still inside the window (greedy: lo).
+ *   - period == 0 (win_host may be NULL): no table, the launch is wn_decode_batch_samp / wn_sample_logits bit for bit; so is a
+ *     table whose every pair is (0, Q) - the window is the validity predicate lo <= i < hi where those test i < Q.
+ * The table travels in the kernel arguments (at most 16 pairs), shared by the utterances of a launch.
+ *
+ * wn_win_decode_batch: wn_decode_batch_samp's arguments up to top_p, then win_host - a HOST array of 2 * win_period int32
+ * lo0, hi0, lo1, hi1, .., read during the call - win_period and win_pos0.  A teacher-forced step still reports the windowed
+ * code and probabilities.  Returns -4 (wn_last_error names the entry and the argument) before any launch for win_period < 0 or
+ * > 16, win_period > 0 with NULL win_host, a pair with lo < 0, hi > Q or lo >= hi, win_pos0 < 0, and everything
+ * wn_decode_batch_samp refuses (so: the corrected recurrence only).  n_steps == 0 or n_utt == 0 launch nothing and return 0. */
+int wn_win_decode_batch(int filter_width, int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host,
+                        const int64_t* q_off_host, float* queues, const float* w_causal, const float* b_causal,
+                        const float* w_layers, int64_t layer_stride, const float* b_layers, const float* w_p1, const float* b_p1,
+                        const float* w_p2, const float* b_p2, const float* note0, const float* prev0, float* note_out,
+                        float* prev_out, const int32_t* forced, int32_t* codes_out, float* probs_out, int64_t step0,
+                        int n_steps, int push_input, uint64_t* sync, int n_utt, int64_t queues_ustride, float temperature,
+                        uint64_t seed, const uint16_t* pk, int64_t pk_fg0, int64_t pk_d0, int64_t pk_lstride, int64_t pk_skip,
+                        int64_t pk_p1, int64_t pk_p2, const float* cond_fg, int64_t cond_fg_ustride, const float* cond_p1,
+                        int64_t cond_p1_ustride, const int32_t* c_shift_host, const int32_t* c_q_host, int le, int64_t pos0,
+                        const wn_sampling* samp, int top_k, float top_p, const int32_t* win_host, int win_period,
+                        int64_t win_pos0, wn_stream_t stream);
+/* wn_sample_logits under a window table: row i uses pair (win_pos0 + i) mod win_period (independent of step0, which still
+ * numbers the generated uniforms).  Same refusals for the three new arguments, plus everything wn_sample_logits refuses; n == 0
+ * launches nothing. */
+int wn_win_sample_logits(const float* logits, int64_t n, int Q, int64_t ld, const wn_sampling* samp, float temperature, uint64_t seed,
+                         int top_k, float top_p, int64_t step0, const float* u, int32_t* codes, float* probs,
+                         const int32_t* win_host, int win_period, int64_t win_pos0, wn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

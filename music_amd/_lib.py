@@ -31,6 +31,8 @@ _DEC_BATCH = [_i, _l, _f, _l]                          # n_utt, queues_ustride, 
 _DEC_PK = [_p] + [_l] * 6                              # pk, pk_fg0, pk_d0, pk_lstride, pk_skip, pk_p1, pk_p2
 _DEC_COND = [_p, _l, _p, _l, _p, _p, _i, _l]           # cond_fg + stride, cond_p1 + stride, c_shift, c_q, le, pos0
 _DEC_SAMP = [_p, _i, _f]                               # the per-utterance wn_sampling table, top_k, top_p
+_DEC_WIN = [_p, _i, _l]                                # the host window table (lo, hi pairs), its period, the first stream position
+_SAMPLE_LOGITS = [_p, _l, _i, _l, _p, _f, _l, _i, _f, _l, _p, _p, _p]     # logits .. probs
 
 # name -> argtypes  (every function returns int status except wn_last_error)
 SIGNATURES = {
@@ -130,7 +132,10 @@ SIGNATURES = {
     "wn_decode_batch_fw": [_i] + _DEC_HEAD + _DEC_BATCH + _DEC_PK + [_p],              # filter_width first
     "wn_decode_batch_cond": [_i] + _DEC_HEAD + _DEC_BATCH + _DEC_PK + _DEC_COND + [_p],
     "wn_decode_batch_samp": [_i] + _DEC_HEAD + _DEC_BATCH + _DEC_PK + _DEC_COND + _DEC_SAMP + [_p],
-    "wn_sample_logits": [_p, _l, _i, _l, _p, _f, _l, _i, _f, _l, _p, _p, _p, _p],
+    "wn_sample_logits": _SAMPLE_LOGITS + [_p],
+    # position-windowed sampling: the entries above with the window tail (named outside the wn_decode* family on purpose)
+    "wn_win_decode_batch": [_i] + _DEC_HEAD + _DEC_BATCH + _DEC_PK + _DEC_COND + _DEC_SAMP + _DEC_WIN + [_p],
+    "wn_win_sample_logits": _SAMPLE_LOGITS + _DEC_WIN + [_p],
 }
 
 

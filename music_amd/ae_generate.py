@@ -380,8 +380,9 @@ def rate_distortion(net, clips, classes=None):
 def split_code_stream(tokens, stages, K):
     """The interleaved token stream of tools/vq_codes_dataset.py back into codes: ``tokens`` (B, Le * stages) or (Le * stages,)
     integers, frame-major (l0s0, l0s1, .., l1s0, ..) with token = s * K + code, -> (B, stages, Le) int64 codes in [0, K), what
-    ``decode_codes`` takes.  Raises on a length that is no multiple of ``stages`` and on a token outside its position's stage range
-    (a prior over the S K alphabet is free to emit one)."""
+    ``decode_codes`` takes.  Raises on a length that is no multiple of ``stages`` and on a token outside its position's stage range.
+    A prior over the S K alphabet sampled freely may emit one; ``sample_code_stream`` samples it under the decoder's position
+    windows (``fast_generate.stage_windows``), which keep every token inside its position's range, so its streams always split."""
     t = torch.as_tensor(tokens)
     stages, K = int(stages), int(K)
     if stages < 1 or K < 1:
@@ -399,6 +400,42 @@ def split_code_stream(tokens, stages, K):
         raise ValueError("split_code_stream: token %d of clip %d at frame %d, stage %d lies outside that stage's range [%d, %d)"
                          % (int(t[b, l, s]), b, l, s, s * K, (s + 1) * K))
     return codes.permute(0, 2, 1).contiguous()
+
+
+def sample_code_stream(prior, stages, K, frames, start_tokens, start_pos=0, temperature=None, top_k=None, top_p=None, seed=0,
+                       streams=None):
+    """New bottleneck codes from a prior over the interleaved token stream (a ``wavenet`` with ``quantization_channels`` >= stages
+    * K trained on tools/vq_codes_dataset.py's output): ``start_tokens`` (U, n0 >= receptive_field) are tokens of a real stream
+    whose first token sits at stream position ``start_pos``; their last receptive_field tokens (canonical one-hot) prime the
+    prior, and ``frames * stages`` tokens are generated in ONE ``fast_generate.generate_codes_batch`` launch (corrected
+    recurrence) under ``stage_windows(stages, K)``: the token at stream position p is drawn among stage p mod stages' K tokens
+    only, renormalised there, so no token can leave its range.  ``(start_pos + n0) % stages`` must be 0: generation starts on a
+    frame boundary.  ``temperature`` / ``top_k`` / ``top_p`` / ``seed`` / ``streams``: as in ``generate_codes_batch``.
+    Returns ``split_code_stream`` of the generated tokens: (U, stages, frames) int64 codes in [0, K), what ``decode_codes`` takes."""
+    try:
+        from . import fast_generate as fg
+    except ImportError:
+        from music_amd import fast_generate as fg
+    stages, K, frames, start_pos = int(stages), int(K), int(frames), int(start_pos)
+    rf, Q = prior.receptive_field, prior.quantization_channels
+    if stages < 1 or K < 1 or frames < 1:
+        raise ValueError("sample_code_stream: stages, K and frames must be >= 1")
+    if stages * K > Q:
+        raise ValueError("sample_code_stream: %d stages x %d codes = %d tokens, the prior's alphabet holds %d" % (stages, K, stages * K, Q))
+    t = torch.as_tensor(start_tokens)
+    if t.is_floating_point() or t.dim() != 2 or t.size(1) < rf:
+        raise ValueError("sample_code_stream: start_tokens must be (U, n0 >= %d) integer tokens" % rf)
+    if start_pos < 0 or (start_pos + t.size(1)) % stages:
+        raise ValueError("sample_code_stream: generation must start on a frame boundary: start_pos + n0 = %d + %d is no multiple of "
+                         "%d stages (start_pos >= 0)" % (start_pos, t.size(1), stages))
+    if int(t.min()) < 0 or int(t.max()) >= Q:
+        raise ValueError("sample_code_stream: start_tokens must hold tokens in [0, %d)" % Q)
+    dev = next(prior.parameters()).device
+    x = torch.nn.functional.one_hot(t[:, -rf:].to(device=dev, dtype=torch.int64), Q).transpose(1, 2).float().contiguous()
+    tokens = fg.generate_codes_batch(prior, x, frames * stages, correct_queue=True, temperature=temperature, seed=seed, top_k=top_k,
+                                     top_p=top_p, streams=streams, windows=fg.stage_windows(stages, K),
+                                     window_pos=start_pos + t.size(1))
+    return split_code_stream(tokens, stages, K)
 
 
 def _checked_codes(t, B, n, Q, dev, what):

@@ -60,17 +60,38 @@ static_assert(WN_VQ_NUM_PARTIALS == WN_VQ_PARTIALS && WN_VQ_MAX_CODES == WN_DEC_
 static_assert(WN_VQ_MAX_CODES == WN_VQ_MAX_K && WN_VQ_EMA_WORK_BYTES == WN_VQ_EMA_WORK, "vq ema constants out of sync");
 static_assert(WN_RVQ_MAX_STAGES == WN_RVQ_MAX_S, "rvq constants out of sync");
 
-// ---- cached-queue decode: the ONE call path behind the six exported decode entries -------------------------------------------
+// ---- cached-queue decode: the ONE call path behind the seven exported decode entries (wn_decode .. wn_decode_batch_samp and
+// wn_win_decode_batch) -----------------------------------------------------------------------------------------------------------
 // Every entry forwards its arguments (and the defaults of those it does not take) to decode_checked with the checks it applies:
 enum : unsigned {
     DEC_FW = 1,       // takes filter_width: it, Q and the note / history pointers are checked, under the entry's own name
     DEC_COND = 2,     // takes conditioning tables: corrected recurrence only; le, n_layers and the schedule arrays are checked
     DEC_SAMP = 4,     // takes top_k / top_p: the scalar form's filters are checked
+    DEC_WIN = 8,      // takes a sampling-window table: its period, pairs and position are checked against Q
 };
 
 static int decode_refuse(const char* fn, const char* text) {
     snprintf(g_err, sizeof(g_err), "%s: %s", fn, text);
     return -4;
+}
+
+// A host window table (lo0, hi0, lo1, hi1, ..: win_period pairs) and the stream position of the call's first step or row, checked
+// under the entry's name `fn` and copied into the kernel-argument form: the position arrives reduced mod the period.
+static int win_checked(const char* fn, const int32_t* win_host, int win_period, int64_t win_pos0, int Q, int& period, int& pos0,
+                       int (&lo)[WN_WIN_MAX], int (&hi)[WN_WIN_MAX]) {
+    if (win_period < 0 || win_period > WN_WIN_MAX) return decode_refuse(fn, "'win_period' must be 0 (no windows) .. 16 pairs");
+    if (win_period > 0 && !win_host) return decode_refuse(fn, "'win_host' is NULL with win_period > 0");
+    for (int j = 0; j < win_period; ++j)
+        if (win_host[2 * j] < 0 || win_host[2 * j + 1] > Q || win_host[2 * j] >= win_host[2 * j + 1]) {
+            snprintf(g_err, sizeof(g_err), "%s: 'win_host' pair %d is (%d, %d): every window needs 0 <= lo < hi <= Q", fn, j,
+                     (int)win_host[2 * j], (int)win_host[2 * j + 1]);
+            return -4;
+        }
+    if (win_pos0 < 0) return decode_refuse(fn, "'win_pos0' (stream position of the first step) must be >= 0");
+    period = win_period;
+    pos0 = win_period > 0 ? (int)(win_pos0 % win_period) : 0;
+    for (int j = 0; j < win_period; ++j) { lo[j] = win_host[2 * j]; hi[j] = win_host[2 * j + 1]; }
+    return 0;
 }
 
 // Makes every refusal of a decode call, in the one order all entries share, then fills WnDecodeArgs and launches.  `fn`: the calling
@@ -85,7 +106,7 @@ static int decode_checked(const char* fn, unsigned checks, int64_t sync_ustride,
                           int64_t pk_d0, int64_t pk_lstride, int64_t pk_skip, int64_t pk_p1, int64_t pk_p2, const float* cond_fg,
                           int64_t cond_fg_ustride, const float* cond_p1, int64_t cond_p1_ustride, const int32_t* c_shift_host,
                           const int32_t* c_q_host, int le, int64_t pos0, const wn_sampling* samp, int top_k, float top_p,
-                          wn_stream_t stream) {
+                          const int32_t* win_host, int win_period, int64_t win_pos0, wn_stream_t stream) {
     const bool layers_ok = n_layers >= 1 && n_layers <= WN_DEC_MAX_LAYERS;
     if ((checks & DEC_SAMP) && !samp) {   // (a table's entries are normalised on the device: out of range = filter off)
         if (!(top_p >= 0.0f)) return decode_refuse(fn, "'top_p' must be a number >= 0 (0 or >= 1: no nucleus filter)");
@@ -114,12 +135,16 @@ static int decode_checked(const char* fn, unsigned checks, int64_t sync_ustride,
         WN_REQUIRE(fn, note0, note_out, codes_out);
         if (filter_width > 1) WN_REQUIRE(fn, prev0, prev_out);
     }
+    WnDecodeArgs a;
+    memset(&a, 0, sizeof(a));
+    if (checks & DEC_WIN) {               // (Q is in range here: DEC_WIN comes with DEC_FW)
+        const int rc = win_checked(fn, win_host, win_period, win_pos0, Q, a.win_period, a.win_pos0, a.win_lo, a.win_hi);
+        if (rc) return rc;
+    }
     if (n_utt <= 0) return 0;
     if (!layers_ok) return decode_refuse("wn_decode", "1..64 layers supported");
     WN_REQUIRE("wn_decode", dilations_host, q_off_host);              // (host arrays, read right here)
     if (n_steps > 0) WN_REQUIRE("wn_decode", queues, w_causal, w_layers, w_p1, w_p2, sync);
-    WnDecodeArgs a;
-    memset(&a, 0, sizeof(a));
     a.n_layers = n_layers; a.R = R; a.D = D; a.S = S; a.Q = Q; a.fw = filter_width;
     for (int i = 0; i < n_layers; ++i) { a.dil[i] = dilations_host[i]; a.q_off[i] = q_off_host[i]; }
     a.queues = queues; a.w_causal = w_causal; a.b_causal = b_causal; a.w_layers = w_layers; a.layer_stride = layer_stride;
@@ -145,6 +170,29 @@ static int decode_checked(const char* fn, unsigned checks, int64_t sync_ustride,
         if (post_pk) { a.pk_skip = pk_skip; a.pk_p1 = pk_p1; a.pk_p2 = pk_p2; }
     }
     return wn_launch_decode(a, (hipStream_t)stream);
+}
+
+// The two sampler entries' one body: the refusals under the entry's name `fn`, then the launch (`win`: the entry takes a table).
+static int sample_checked(const char* fn, bool win, const float* logits, int64_t n, int Q, int64_t ld, const wn_sampling* samp,
+                          float temperature, uint64_t seed, int top_k, float top_p, int64_t step0, const float* u, int32_t* codes,
+                          float* probs, const int32_t* win_host, int win_period, int64_t win_pos0, wn_stream_t stream) {
+    if (Q < 1 || Q > WN_DEC_MAX_Q) return decode_refuse(fn, "1 <= 'Q' <= 1024 entries per row");
+    if (n < 0) return decode_refuse(fn, "'n' (rows) must be >= 0");
+    if (ld < Q) return decode_refuse(fn, "'ld' (row stride) must be >= Q");
+    if (!samp) {
+        if (!(top_p >= 0.0f)) return decode_refuse(fn, "'top_p' must be a number >= 0 (0 or >= 1: no nucleus filter)");
+        if (top_k < 0) return decode_refuse(fn, "'top_k' must be >= 0 (0 or >= Q: no top-k filter)");
+    }
+    WnWin w;
+    memset(&w, 0, sizeof(w));
+    if (win) {
+        const int rc = win_checked(fn, win_host, win_period, win_pos0, Q, w.period, w.pos0, w.lo, w.hi);
+        if (rc) return rc;
+    }
+    if (n == 0) return 0;
+    WN_REQUIRE(fn, logits, codes);
+    return wn_launch_sample_logits(logits, (long)n, Q, (long)ld, reinterpret_cast<const WnSampling*>(samp), temperature, seed, top_k,
+                                   top_p, (long)step0, u, codes, probs, w, (hipStream_t)stream);
 }
 
 extern "C" {
@@ -892,7 +940,7 @@ int wn_decode(int n_layers, int R, int D, int S, int Q, const int32_t* dilations
     return decode_checked("wn_decode", 0, (int64_t)n_layers * D + 2, 2, n_layers, R, D, S, Q, dilations_host, q_off_host, queues,
                           w_causal, b_causal, w_layers, layer_stride, b_layers, w_p1, b_p1, w_p2, b_p2, note0, prev0, note_out,
                           prev_out, forced, codes_out, probs_out, step0, n_steps, push_input, sync, 1, 0, 0.0f, 0,
-                          nullptr, 0, 0, 0, -1, -1, -1, nullptr, 0, nullptr, 0, nullptr, nullptr, 1, 0, nullptr, 0, 1.0f, stream);
+                          nullptr, 0, 0, 0, -1, -1, -1, nullptr, 0, nullptr, 0, nullptr, nullptr, 1, 0, nullptr, 0, 1.0f, nullptr, 0, 0, stream);
 }
 
 int wn_decode_batch(int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host, const int64_t* q_off_host,
@@ -906,7 +954,7 @@ int wn_decode_batch(int n_layers, int R, int D, int S, int Q, const int32_t* dil
                           queues, w_causal, b_causal, w_layers, layer_stride, b_layers, w_p1, b_p1, w_p2, b_p2, note0, prev0,
                           note_out, prev_out, forced, codes_out, probs_out, step0, n_steps, push_input, sync, n_utt, queues_ustride,
                           temperature, seed, nullptr, 0, 0, 0, -1, -1, -1, nullptr, 0, nullptr, 0, nullptr, nullptr, 1, 0,
-                          nullptr, 0, 1.0f, stream);
+                          nullptr, 0, 1.0f, nullptr, 0, 0, stream);
 }
 
 int wn_decode_batch_pk(int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host, const int64_t* q_off_host,
@@ -921,7 +969,7 @@ int wn_decode_batch_pk(int n_layers, int R, int D, int S, int Q, const int32_t* 
                           q_off_host, queues, w_causal, b_causal, w_layers, layer_stride, b_layers, w_p1, b_p1, w_p2, b_p2, note0,
                           prev0, note_out, prev_out, forced, codes_out, probs_out, step0, n_steps, push_input, sync, n_utt,
                           queues_ustride, temperature, seed, pk, pk_fg0, pk_d0, pk_lstride, pk_skip, pk_p1, pk_p2,
-                          nullptr, 0, nullptr, 0, nullptr, nullptr, 1, 0, nullptr, 0, 1.0f, stream);
+                          nullptr, 0, nullptr, 0, nullptr, nullptr, 1, 0, nullptr, 0, 1.0f, nullptr, 0, 0, stream);
 }
 
 int wn_decode_batch_fw(int filter_width, int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host,
@@ -936,7 +984,7 @@ int wn_decode_batch_fw(int filter_width, int n_layers, int R, int D, int S, int 
                           dilations_host, q_off_host, queues, w_causal, b_causal, w_layers, layer_stride, b_layers, w_p1, b_p1, w_p2,
                           b_p2, note0, prev0, note_out, prev_out, forced, codes_out, probs_out, step0, n_steps, push_input, sync,
                           n_utt, queues_ustride, temperature, seed, pk, pk_fg0, pk_d0, pk_lstride, pk_skip, pk_p1, pk_p2,
-                          nullptr, 0, nullptr, 0, nullptr, nullptr, 1, 0, nullptr, 0, 1.0f, stream);
+                          nullptr, 0, nullptr, 0, nullptr, nullptr, 1, 0, nullptr, 0, 1.0f, nullptr, 0, 0, stream);
 }
 
 int wn_decode_batch_cond(int filter_width, int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host,
@@ -954,7 +1002,7 @@ int wn_decode_batch_cond(int filter_width, int n_layers, int R, int D, int S, in
                           b_p1, w_p2, b_p2, note0, prev0, note_out, prev_out, forced, codes_out, probs_out, step0, n_steps,
                           push_input, sync, n_utt, queues_ustride, temperature, seed, pk, pk_fg0, pk_d0, pk_lstride, pk_skip, pk_p1,
                           pk_p2, cond_fg, cond_fg_ustride, cond_p1, cond_p1_ustride, c_shift_host, c_q_host, le, pos0,
-                          nullptr, 0, 1.0f, stream);
+                          nullptr, 0, 1.0f, nullptr, 0, 0, stream);
 }
 
 int wn_decode_batch_samp(int filter_width, int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host,
@@ -972,22 +1020,39 @@ int wn_decode_batch_samp(int filter_width, int n_layers, int R, int D, int S, in
                           b_layers, w_p1, b_p1, w_p2, b_p2, note0, prev0, note_out, prev_out, forced, codes_out, probs_out, step0,
                           n_steps, push_input, sync, n_utt, queues_ustride, temperature, seed, pk, pk_fg0, pk_d0, pk_lstride, pk_skip,
                           pk_p1, pk_p2, cond_fg, cond_fg_ustride, cond_p1, cond_p1_ustride, c_shift_host, c_q_host, le, pos0, samp,
-                          top_k, top_p, stream);
+                          top_k, top_p, nullptr, 0, 0, stream);
+}
+
+int wn_win_decode_batch(int filter_width, int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host,
+                        const int64_t* q_off_host, float* queues, const float* w_causal, const float* b_causal,
+                        const float* w_layers, int64_t layer_stride, const float* b_layers, const float* w_p1, const float* b_p1,
+                        const float* w_p2, const float* b_p2, const float* note0, const float* prev0, float* note_out,
+                        float* prev_out, const int32_t* forced, int32_t* codes_out, float* probs_out, int64_t step0,
+                        int n_steps, int push_input, uint64_t* sync, int n_utt, int64_t queues_ustride, float temperature,
+                        uint64_t seed, const uint16_t* pk, int64_t pk_fg0, int64_t pk_d0, int64_t pk_lstride, int64_t pk_skip,
+                        int64_t pk_p1, int64_t pk_p2, const float* cond_fg, int64_t cond_fg_ustride, const float* cond_p1,
+                        int64_t cond_p1_ustride, const int32_t* c_shift_host, const int32_t* c_q_host, int le, int64_t pos0,
+                        const wn_sampling* samp, int top_k, float top_p, const int32_t* win_host, int win_period,
+                        int64_t win_pos0, wn_stream_t stream) {
+    return decode_checked("wn_win_decode_batch", DEC_FW | DEC_COND | DEC_SAMP | DEC_WIN, wn_decode_sync_granules(n_layers, D, S),
+                          filter_width, n_layers, R, D, S, Q, dilations_host, q_off_host, queues, w_causal, b_causal, w_layers,
+                          layer_stride, b_layers, w_p1, b_p1, w_p2, b_p2, note0, prev0, note_out, prev_out, forced, codes_out,
+                          probs_out, step0, n_steps, push_input, sync, n_utt, queues_ustride, temperature, seed, pk, pk_fg0, pk_d0,
+                          pk_lstride, pk_skip, pk_p1, pk_p2, cond_fg, cond_fg_ustride, cond_p1, cond_p1_ustride, c_shift_host,
+                          c_q_host, le, pos0, samp, top_k, top_p, win_host, win_period, win_pos0, stream);
 }
 
 int wn_sample_logits(const float* logits, int64_t n, int Q, int64_t ld, const wn_sampling* samp, float temperature, uint64_t seed,
                      int top_k, float top_p, int64_t step0, const float* u, int32_t* codes, float* probs, wn_stream_t stream) {
-    if (Q < 1 || Q > WN_DEC_MAX_Q) return wn_set_error_msg(-4, "wn_sample_logits: 1 <= 'Q' <= 1024 entries per row");
-    if (n < 0) return wn_set_error_msg(-4, "wn_sample_logits: 'n' (rows) must be >= 0");
-    if (ld < Q) return wn_set_error_msg(-4, "wn_sample_logits: 'ld' (row stride) must be >= Q");
-    if (!samp) {
-        if (!(top_p >= 0.0f)) return wn_set_error_msg(-4, "wn_sample_logits: 'top_p' must be a number >= 0 (0 or >= 1: no nucleus filter)");
-        if (top_k < 0) return wn_set_error_msg(-4, "wn_sample_logits: 'top_k' must be >= 0 (0 or >= Q: no top-k filter)");
-    }
-    if (n == 0) return 0;
-    WN_REQUIRE("wn_sample_logits", logits, codes);
-    return wn_launch_sample_logits(logits, (long)n, Q, (long)ld, reinterpret_cast<const WnSampling*>(samp), temperature, seed, top_k,
-                                   top_p, (long)step0, u, codes, probs, (hipStream_t)stream);
+    return sample_checked("wn_sample_logits", false, logits, n, Q, ld, samp, temperature, seed, top_k, top_p, step0, u, codes, probs,
+                          nullptr, 0, 0, stream);
+}
+
+int wn_win_sample_logits(const float* logits, int64_t n, int Q, int64_t ld, const wn_sampling* samp, float temperature, uint64_t seed,
+                         int top_k, float top_p, int64_t step0, const float* u, int32_t* codes, float* probs,
+                         const int32_t* win_host, int win_period, int64_t win_pos0, wn_stream_t stream) {
+    return sample_checked("wn_win_sample_logits", true, logits, n, Q, ld, samp, temperature, seed, top_k, top_p, step0, u, codes, probs,
+                          win_host, win_period, win_pos0, stream);
 }
 
 }  // extern "C"

@@ -46,9 +46,12 @@ __device__ __forceinline__ void dec_matvec(const float* __restrict__ W, int ldw,
 
 
 // Inverse CDF over the wave's NE x 64 probabilities: inclusive scan of the lane sums (pairwise: (v0 + v1) + (v2 + v3) for
-// NE = 4), then the first entry whose cumulative probability exceeds u; 1 << 20 when none does.  Valid in every lane.
+// NE = 4), then the first entry of the window [lo, hi) whose cumulative probability exceeds u; 1 << 20 when none does.  Valid
+// in every lane.  Only an entry of POSITIVE probability is ever the answer: a lane's running sum starts from the scan, the lane
+// before it ended on its own sequential sum, and where the two round differently around u (u = 1 - 2^-24 against a total of
+// 1 - 2^-24 | 1) the first entry of the later lane would otherwise be taken whatever its probability - a filtered-out entry.
 template <int NE>
-__device__ __forceinline__ int dec_draw(const float (&v)[NE], int lane, float u) {
+__device__ __forceinline__ int dec_draw(const float (&v)[NE], int lo, int hi, int lane, float u) {
     float t[NE];
     for (int e = 0; e < NE; ++e) t[e] = v[e];
     for (int w = 1; w < NE; w <<= 1)
@@ -62,8 +65,9 @@ __device__ __forceinline__ int dec_draw(const float (&v)[NE], int lane, float u)
     float c = incl - mine;
     int pick = 1 << 20;
     for (int e = 0; e < NE; ++e) {
+        const int i = lane * NE + e;
         c += v[e];
-        if (pick == (1 << 20) && c > u) pick = lane * NE + e;
+        if (pick == (1 << 20) && c > u && v[e] > 0.f && i >= lo && i < hi) pick = i;
     }
     for (int off = 32; off > 0; off >>= 1) pick = min(pick, __shfl_xor(pick, off, 64));
     return pick;
@@ -73,23 +77,26 @@ __device__ __forceinline__ int dec_draw(const float (&v)[NE], int lane, float u)
 // and never read or written; NE = 4 for the usual 256): probabilities = softmax(logit * inv_temp) (written to probs_dst
 // if given), then either the first-index argmax (the reference's greedy topk(1), fast_generate.py:139) or - SURVEY 8f2 -
 // a draw from that distribution by inverse CDF with the uniform number u in [0,1).  The result is valid in every lane.
+// The step's window [lo, hi), 0 <= lo < hi <= Q and wave-uniform, is the VALIDITY PREDICATE of an entry: entries outside it
+// are padding like those >= Q - never read, never part of a maximum, a sum or a count - except that probs_dst receives an
+// exact 0 for them.  The code lies in [lo, hi) whatever the logits hold; (0, Q) is the sampler without a window, bit for bit.
 template <int NE>
-__device__ __forceinline__ int dec_choose(const float* logit, int Q, int lane, float* probs_dst, float inv_temp, bool sample, float u) {
+__device__ __forceinline__ int dec_choose(const float* logit, int Q, int lo, int hi, int lane, float* probs_dst, float inv_temp, bool sample, float u) {
     float v[NE], m = -INFINITY;
-    for (int e = 0; e < NE; ++e) { const int i = lane * NE + e; v[e] = i < Q ? logit[i] : -INFINITY; m = fmaxf(m, v[e]); }
+    for (int e = 0; e < NE; ++e) { const int i = lane * NE + e; v[e] = (i >= lo && i < hi) ? logit[i] : -INFINITY; m = fmaxf(m, v[e]); }
     for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
     float s = 0.f;
     for (int e = 0; e < NE; ++e) { v[e] = expf((v[e] - m) * inv_temp); s += v[e]; }
     for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
     const float inv = 1.0f / s;
-    float best = -1.f; int bi = 0;
+    float best = -1.f; int bi = lo;
     for (int e = 0; e < NE; ++e) {
         const int i = lane * NE + e;
         v[e] *= inv;
-        if (i < Q) {
+        if (i >= lo && i < hi) {
             if (probs_dst) probs_dst[i] = v[e];
             if (v[e] > best) { best = v[e]; bi = i; }
-        }
+        } else if (i < Q && probs_dst) probs_dst[i] = 0.f;
     }
     if (!sample) {
         for (int off = 32; off > 0; off >>= 1) {
@@ -99,8 +106,8 @@ __device__ __forceinline__ int dec_choose(const float* logit, int Q, int lane, f
         }
         return bi;
     }
-    const int pick = dec_draw<NE>(v, lane, u);
-    return pick < Q ? pick : Q - 1;                 // (u above the rounded total: last entry)
+    const int pick = dec_draw<NE>(v, lo, hi, lane, u);
+    return pick < Q ? pick : hi - 1;                // (u above the rounded total: last entry of the window)
 }
 // Uniform number in [0,1) for (seed, global step, utterance or stream id): splitmix64 finaliser, 24 random bits.
 __device__ __forceinline__ float dec_uniform(unsigned long long seed, unsigned long long step, unsigned long long utt) {
@@ -155,21 +162,24 @@ __device__ __forceinline__ unsigned dec_key(float x) {
 // is one v_cmp + s_bcnt1 per register (top-k: counts only), "how much mass" one DPP reduction per bit.  The top-p search
 // skips the leading bits the largest and the smallest kept key share and stops as soon as ONE key is left between the
 // bounds (it is tau), so distinct logits cost about a dozen reductions, not 32.
+// [lo, hi) is the step's window as in dec_choose: the rule runs on the hi - lo entries inside it (the caller passes top_k = 0
+// unless 0 < top_k < hi - lo), everything outside is padding with an exact 0 in probs_dst.
 template <int NE>
-__device__ __forceinline__ int dec_choose_trunc(const float* logit, int Q, int lane, float* probs_dst, float inv_temp, int top_k,
-                                                float top_p, float u) {
+__device__ __forceinline__ int dec_choose_trunc(const float* logit, int Q, int lo, int hi, int lane, float* probs_dst, float inv_temp,
+                                                int top_k, float top_p, float u) {
     float v[NE], m = -INFINITY;
     unsigned key[NE];
     for (int e = 0; e < NE; ++e) {
         const int i = lane * NE + e;
-        v[e] = i < Q ? logit[i] + 0.0f : -INFINITY;             // (+ 0: -0 becomes +0, one key per value)
-        key[e] = i < Q ? dec_key(v[e]) : 0u;                    // padding: below every real key (key(-inf) = 0x007fffff)
+        const bool in = i >= lo && i < hi;
+        v[e] = in ? logit[i] + 0.0f : -INFINITY;                // (+ 0: -0 becomes +0, one key per value)
+        key[e] = in ? dec_key(v[e]) : 0u;                       // padding: below every real key (key(-inf) = 0x007fffff)
         m = fmaxf(m, v[e]);
     }
     for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
     // ---- top-k: the largest c with #{key >= c} >= top_k is the top_k-th largest key
     unsigned thr = 0u;
-    int n_kept = Q;
+    int n_kept = hi - lo;
     if (top_k > 0) {
         for (int bit = 31; bit >= 0; --bit) {
             const unsigned cand = thr | (1u << bit);
@@ -187,16 +197,16 @@ __device__ __forceinline__ int dec_choose_trunc(const float* logit, int Q, int l
     // ---- top-p on the unnormalised masses: the largest c with mass{key >= c} >= top_p * s is tau's key
     if (top_p < 1.0f) {
         const float need = top_p * s;                           // (<= s, and the mass of all of K is s itself: some c qualifies)
-        unsigned lo = thr;
+        unsigned klo = thr;
         if (top_k <= 0) {                                       // smallest real key
             unsigned inv = 0u;
-            for (int e = 0; e < NE; ++e) inv = max(inv, lane * NE + e < Q ? ~key[e] : 0u);
-            lo = ~dec_wave_umax(inv);
+            for (int e = 0; e < NE; ++e) { const int i = lane * NE + e; inv = max(inv, (i >= lo && i < hi) ? ~key[e] : 0u); }
+            klo = ~dec_wave_umax(inv);
         }
-        const unsigned hi = dec_key(m);
-        if (hi != lo) {
-            int bit = 31 - __clz((int)(hi ^ lo));               // first bit in which kept keys differ
-            unsigned pre = bit == 31 ? 0u : (hi >> (bit + 1)) << (bit + 1);
+        const unsigned khi = dec_key(m);
+        if (khi != klo) {
+            int bit = 31 - __clz((int)(khi ^ klo));             // first bit in which kept keys differ
+            unsigned pre = bit == 31 ? 0u : (khi >> (bit + 1)) << (bit + 1);
             int c_lo = n_kept, c_hi = 0;                        // keys >= pre (kept ones), keys >= pre + 2^(bit+1)
             for (; bit >= 0; --bit) {
                 const unsigned cand = pre | (1u << bit);
@@ -221,12 +231,12 @@ __device__ __forceinline__ int dec_choose_trunc(const float* logit, int Q, int l
     for (int e = 0; e < NE; ++e) {
         const int i = lane * NE + e;
         v[e] *= inv;
-        if (i < Q && probs_dst) probs_dst[i] = v[e];
+        if (i < Q && probs_dst) probs_dst[i] = (i >= lo && i < hi) ? v[e] : 0.f;
     }
-    const int pick = dec_draw<NE>(v, lane, u);
+    const int pick = dec_draw<NE>(v, lo, hi, lane, u);
     if (pick < Q) return pick;
-    unsigned last = 0u;                                         // u above the rounded total: the largest index in N
-    for (int e = 0; e < NE; ++e) { const int i = lane * NE + e; if (i < Q && key[e] >= thr) last = (unsigned)i; }
+    unsigned last = (unsigned)lo;                               // u above the rounded total: the largest index in N
+    for (int e = 0; e < NE; ++e) { const int i = lane * NE + e; if (i >= lo && i < hi && key[e] >= thr) last = (unsigned)i; }
     return (int)dec_wave_umax(last);
 }
 
@@ -236,7 +246,6 @@ struct DecSamp {
     int top_k;                              // -1: greedy (no draw at all), 0: top-k filter off
     unsigned long long key;                 // seed + 0xD1B5.. * (stream + 1): the step-independent part of dec_uniform's counter
     __device__ __forceinline__ bool sample() const { return top_k >= 0; }
-    __device__ __forceinline__ bool trunc() const { return top_k > 0 || top_p < 1.0f; }
     // dec_uniform(seed, step, stream): the same 64-bit sum, associated differently
     __device__ __forceinline__ float uniform(unsigned long long step) const { return top_k >= 0 ? dec_uniform(key, step, ~0ull) : 0.f; }
 };
@@ -264,41 +273,56 @@ __device__ __forceinline__ DecSamp dec_samp_of(const WnSampling* tab, size_t row
 __device__ __forceinline__ DecSamp dec_samp_of(const WnDecodeArgs& a, size_t utt, int Q) {
     return dec_samp_of(a.samp, utt, Q, a.sample, a.inv_temp, a.top_k, a.top_p, a.seed);
 }
-// the code of one row: greedy / plain temperature exactly as before (dec_choose), truncated only when a filter is on
-template <int NE>
-__device__ __forceinline__ int dec_pick(const float* logit, int Q, int lane, float* probs_dst, const DecSamp& s, float u) {
-    if (s.trunc()) return dec_choose_trunc<NE>(logit, Q, lane, probs_dst, s.inv_temp, s.top_k, s.top_p, u);
-    return dec_choose<NE>(logit, Q, lane, probs_dst, s.inv_temp, s.sample(), u);
+// The window of launch-local step j (a row of a logits matrix alike) as two wave-uniform scalars: pair j of the table, which
+// travels in the kernel arguments (scalar loads); no table: the whole alphabet.
+struct DecWin { int lo, hi; };
+__device__ __forceinline__ DecWin dec_win_of(int period, const int (&tlo)[WN_WIN_MAX], const int (&thi)[WN_WIN_MAX], int j, int Q) {
+    DecWin w = {0, Q};
+    if (period > 0) { w.lo = dec_sgpr(tlo[j]); w.hi = dec_sgpr(thi[j]); }
+    return w;
 }
-__device__ __forceinline__ int dec_pick_any(const float* logit, int Q, int lane, float* probs_dst, const DecSamp& s, float u) {
-    if (Q <= 64) return dec_pick<1>(logit, Q, lane, probs_dst, s, u);
-    if (Q <= 128) return dec_pick<2>(logit, Q, lane, probs_dst, s, u);
-    if (Q <= 256) return dec_pick<4>(logit, Q, lane, probs_dst, s, u);
-    if (Q <= 512) return dec_pick<8>(logit, Q, lane, probs_dst, s, u);
-    return dec_pick<16>(logit, Q, lane, probs_dst, s, u);
+// the pair after pair j
+__device__ __forceinline__ int dec_win_next(int period, int j) { return j + 1 < period ? j + 1 : 0; }
+// the code of one row: greedy / plain temperature exactly as before (dec_choose), truncated only when a filter is on.  The
+// launch-wide normalisation of top_k against Q (dec_samp_of) is repeated against the window's width, which may differ per step
+template <int NE>
+__device__ __forceinline__ int dec_pick(const float* logit, int Q, const DecWin& w, int lane, float* probs_dst, const DecSamp& s, float u) {
+    const int top_k = s.top_k < w.hi - w.lo ? s.top_k : 0;
+    if (top_k > 0 || s.top_p < 1.0f) return dec_choose_trunc<NE>(logit, Q, w.lo, w.hi, lane, probs_dst, s.inv_temp, top_k, s.top_p, u);
+    return dec_choose<NE>(logit, Q, w.lo, w.hi, lane, probs_dst, s.inv_temp, s.sample(), u);
+}
+__device__ __forceinline__ int dec_pick_any(const float* logit, int Q, const DecWin& w, int lane, float* probs_dst, const DecSamp& s, float u) {
+    if (Q <= 64) return dec_pick<1>(logit, Q, w, lane, probs_dst, s, u);
+    if (Q <= 128) return dec_pick<2>(logit, Q, w, lane, probs_dst, s, u);
+    if (Q <= 256) return dec_pick<4>(logit, Q, w, lane, probs_dst, s, u);
+    if (Q <= 512) return dec_pick<8>(logit, Q, w, lane, probs_dst, s, u);
+    return dec_pick<16>(logit, Q, w, lane, probs_dst, s, u);
 }
 
 // The sampler alone: one wave per row of logits [n][Q] (row stride ld), four rows per workgroup.  Row i is "step" step0 + i
-// of stream samp[i].stream (no table: stream 0); u, when given, replaces the generated uniform numbers.
+// of stream samp[i].stream (no table: stream 0); u, when given, replaces the generated uniform numbers.  Row i samples inside
+// pair (win.pos0 + i) mod win.period of the window table (period 0: the whole alphabet).
 __global__ __launch_bounds__(256) void sample_logits_k(const float* __restrict__ logits, long n, int Q, long ld, const WnSampling* __restrict__ samp,
                                                        int sample, float inv_temp, unsigned long long seed, int top_k, float top_p, long step0,
-                                                       const float* __restrict__ u, int32_t* __restrict__ codes, float* __restrict__ probs) {
+                                                       const float* __restrict__ u, int32_t* __restrict__ codes, float* __restrict__ probs,
+                                                       WnWin win) {
     const int lane = threadIdx.x & 63;
     const long row = (long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (row >= n) return;
     const DecSamp s = dec_samp_of(samp, samp ? (size_t)row : 0, Q, sample, inv_temp, top_k, top_p, seed);
     const float ur = u ? u[row] : s.uniform((unsigned long long)(step0 + row));
-    const int bi = dec_pick_any(logits + row * ld, Q, lane, probs ? probs + row * (long)Q : nullptr, s, ur);
+    const DecWin w = dec_win_of(win.period, win.lo, win.hi, win.period > 0 ? (int)((win.pos0 + row) % win.period) : 0, Q);
+    const int bi = dec_pick_any(logits + row * ld, Q, w, lane, probs ? probs + row * (long)Q : nullptr, s, ur);
     if (lane == 0) codes[row] = bi;
 }
 int wn_launch_sample_logits(const float* logits, long n, int Q, long ld, const WnSampling* samp, float temperature,
                             unsigned long long seed, int top_k, float top_p, long step0, const float* u, int32_t* codes,
-                            float* probs, hipStream_t st) {
+                            float* probs, const WnWin& win, hipStream_t st) {
     if (n <= 0) return 0;
     const long blocks = (n + 3) / 4;
     if (blocks > 0x7fffffffL) return wn_set_error_msg(-4, "wn_sample_logits: 'n' is too many rows for one launch");
     hipLaunchKernelGGL(sample_logits_k, dim3((unsigned)blocks), dim3(256), 0, st, logits, n, Q, ld, samp, temperature > 0.0f ? 1 : 0,
-                       temperature > 0.0f ? 1.0f / temperature : 1.0f, seed, top_k, top_p, step0, u, codes, probs);
+                       temperature > 0.0f ? 1.0f / temperature : 1.0f, seed, top_k, top_p, step0, u, codes, probs, win);
     WN_CHECK_LAUNCH();
     return 0;
 }
@@ -345,6 +369,7 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_k(WnDecodeArgs a) {
     for (int i = tid; i < K1 * a.Q; i += DEC_THREADS) prev[i] = u_prev0[i];
     __syncthreads();
 
+    int wj = a.win_pos0;                                        // this step's pair of the window table
     for (int step = 0; step < a.n_steps; ++step) {
         const long gstep = a.step0 + step;                      // global step index: ring positions
         const int pos = (int)(a.pos0 + step);                   // output position: conditioning columns
@@ -396,10 +421,12 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_k(WnDecodeArgs a) {
         // softmax over the Q logits and first-index argmax of the PROBABILITIES, wave 0
         if (tid < 64) {
             const float ur = smp.uniform((unsigned long long)(a.step0 + step));
-            const int bi = (FW == 2 && a.Q == 256) ? dec_pick<4>(logit, 256, tid, u_probs_out ? u_probs_out + (size_t)step * a.Q : nullptr, smp, ur)
-                                                   : dec_pick_any(logit, a.Q, tid, u_probs_out ? u_probs_out + (size_t)step * a.Q : nullptr, smp, ur);
+            const DecWin win = dec_win_of(a.win_period, a.win_lo, a.win_hi, wj, a.Q);
+            const int bi = (FW == 2 && a.Q == 256) ? dec_pick<4>(logit, 256, win, tid, u_probs_out ? u_probs_out + (size_t)step * a.Q : nullptr, smp, ur)
+                                                   : dec_pick_any(logit, a.Q, win, tid, u_probs_out ? u_probs_out + (size_t)step * a.Q : nullptr, smp, ur);
             if (tid == 0) { s_arg = bi; u_codes_out[step] = bi; }
         }
+        wj = dec_win_next(a.win_period, wj);
         __syncthreads();
         // next input column: the forced code if given (teacher forcing), else the prediction; the causal queue moves up
         const int nextc = u_forced ? u_forced[step] : s_arg;
@@ -987,6 +1014,7 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
         const unsigned long long* const zmine = zg_of(tid >> 5) + (tid & 31) * 2;       // this thread's two granules of block 0
         unsigned long long* const errp = cg_of(tid >> 5) + 1;
         unsigned long long pa = 0, pb = 0;                                               // prefetched pair (tag 0 = nothing yet)
+        int wj = a.win_pos0;                                                             // this step's pair of the window table
         for (int step = 0; step < a.n_steps; ++step) {
             const unsigned tag = (unsigned)step + 1u;
             f32x4 acc2[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
@@ -1062,6 +1090,7 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
             if (jpart == 0) {   // part 0 chooses: the logits of all parts, then as the one-workgroup form
                 gather_rows(lg_of(tid >> 5), Q, nullptr, logit, tag, errp);
                 dec_sync();
+                const DecWin win = dec_win_of(a.win_period, a.win_lo, a.win_hi, wj, Q);
 #pragma unroll
                 for (int e = 0; e < 2; ++e) {          // wave w chooses for utterances 2w and 2w + 1
                     const int uu = 2 * w + e;
@@ -1069,13 +1098,14 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
                     const DecSamp& sp = e ? smp1 : smp0;
                     const float ur = sp.uniform((unsigned long long)(a.step0 + step));
                     float* pdst = a.probs_out ? a.probs_out + (ug * (size_t)a.n_steps + step) * Q : nullptr;
-                    const int bi = dec_pick<4>(logit + uu * Q, Q, lane, pdst, sp, ur);
+                    const int bi = dec_pick<4>(logit + uu * Q, Q, win, lane, pdst, sp, ur);
                     if (lane == 0) {
                         a.codes_out[ug * a.n_steps + step] = bi;
                         __hip_atomic_store(cg_of(uu), dec_pack((float)bi, tag), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     }
                 }
             }
+            wj = dec_win_next(a.win_period, wj);
             dec_sync();
         }
     } else {
@@ -1144,6 +1174,7 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
         const DecSamp smp0 = dec_samp_of(a, ux(2 * wv), Q), smp1 = dec_samp_of(a, ux(2 * wv + 1), Q);
         const unsigned long long* const zmine = zg_of(tid >> 5) + (tid & 31) * 2;       // this thread's two granules of block 0
         unsigned long long pa = 0, pb = 0;                                               // prefetched pair (tag 0 = nothing yet)
+        int wj = a.win_pos0;                                                             // this step's pair of the window table
         for (int step = 0; step < a.n_steps; ++step) {
             const unsigned tag = (unsigned)step + 1u;
             if (ucp) {
@@ -1213,6 +1244,7 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
             dec_sync();
             post(Q / 256, p2b, h1, nullptr, logit, BIAS && a.b_p2 ? bsk + 2 * S : nullptr);
             dec_sync();
+            const DecWin win = dec_win_of(a.win_period, a.win_lo, a.win_hi, wj, Q);
 #pragma unroll
             for (int e = 0; e < 2; ++e) {          // wave w chooses for utterances 2w and 2w + 1
                 const int uu = 2 * w + e;
@@ -1220,12 +1252,13 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
                 const DecSamp& sp = e ? smp1 : smp0;
                 const float ur = sp.uniform((unsigned long long)(a.step0 + step));
                 float* pdst = a.probs_out ? a.probs_out + (ug * (size_t)a.n_steps + step) * Q : nullptr;
-                const int bi = dec_pick<4>(logit + uu * Q, Q, lane, pdst, sp, ur);
+                const int bi = dec_pick<4>(logit + uu * Q, Q, win, lane, pdst, sp, ur);
                 if (lane == 0) {
                     a.codes_out[ug * a.n_steps + step] = bi;
                     __hip_atomic_store(cg_of(uu), dec_pack((float)bi, tag), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
             }
+            wj = dec_win_next(a.win_period, wj);
             dec_sync();
         }
     }

@@ -309,6 +309,7 @@ int wn_launch_softmaxq_ce(const float* x, const int64_t* target, float* probs, f
                           float inv_n, hipStream_t st);
 
 #define WN_DEC_MAX_LAYERS 64
+#define WN_WIN_MAX 16                                      // pairs of a sampling-window table
 // one utterance's (or one row's) sampling settings: the layout of wn_sampling (include/wavenet_hip.h), 24 bytes
 struct WnSampling { float temperature; float top_p; int32_t top_k; uint32_t stream; uint64_t seed; };
 static_assert(sizeof(WnSampling) == 24, "wn_sampling is 24 bytes");
@@ -354,6 +355,11 @@ struct WnDecodeArgs {
     // smallest head of the sorted distribution whose mass reaches it; samp != null: utterance u takes ALL its settings
     // (temperature, filters, seed, random-number stream id) from samp[u] and the scalars above are ignored
     const WnSampling* samp; int top_k; float top_p;
+    // position-windowed sampling (wn_win_decode_batch): step s of the launch samples inside [win_lo[j], win_hi[j]) of the alphabet,
+    // j = (win_pos0 + s) mod win_period; win_period == 0: no table, every step takes the whole alphabet.  win_pos0 is the launch's
+    // stream position already reduced mod win_period by the host.  Read with scalar loads, like dil[] and c_shift[]
+    int win_period, win_pos0;
+    int win_lo[WN_WIN_MAX], win_hi[WN_WIN_MAX];
 };
 // column of a conditioning table for output column c (see WnDecodeArgs::c_shift)
 __host__ __device__ inline int wn_dec_cond_idx(int c, int q, int le) {
@@ -366,9 +372,11 @@ size_t dec_k_lds_bytes(const WnDecodeArgs& a);            // dynamic LDS of the 
 #define WN_DEC_MAX_Q 1024                                  // quantisation channels the fp32 decode kernel's sampler covers
 long wn_decode_granules(int n_layers, int D, int S);      // 8-byte granules of one utterance's hand-off area (matrix-core kernels)
 // the decoder's sampler on an arbitrary [n][Q] logits matrix (row stride ld), one wave per row: row i is step step0 + i
+// win: the window table of the rows (row i takes pair (pos0 + i) mod period; period == 0: none), passed in the kernel arguments
+struct WnWin { int period, pos0; int lo[WN_WIN_MAX], hi[WN_WIN_MAX]; };
 int wn_launch_sample_logits(const float* logits, long n, int Q, long ld, const WnSampling* samp, float temperature,
                             unsigned long long seed, int top_k, float top_p, long step0, const float* u, int32_t* codes,
-                            float* probs, hipStream_t st);
+                            float* probs, const WnWin& win, hipStream_t st);
 
 // wn_coll.hip
 int wn_coll_loaded();

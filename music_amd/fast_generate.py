@@ -310,6 +310,62 @@ def _need_corrected(smp, correct_queue):
                          "(wn_decode_batch_samp): pass correct_queue=True")
 
 
+def stage_windows(stages, K):
+    """The window table of a residual quantiser's frame-major token stream (tools/vq_codes_dataset.py: token = s K + code at
+    stream position p with s = p mod stages): ``[(s K, (s + 1) K) for s in range(stages)]``."""
+    return [(s * int(K), (s + 1) * int(K)) for s in range(int(stages))]
+
+
+class _Windows:
+    """The position windows of one launch (include/wavenet_hip.h, wn_win_decode_batch): ``windows``, a sequence of 1..16
+    ``(lo, hi)`` pairs with 0 <= lo < hi <= Q, and ``pos``, the stream position of the launch's first step (row); step s
+    samples inside pair ``(pos + s) % len(windows)``.  ``_windows_of`` gives None for ``windows=None``."""
+
+    def __init__(self, windows, pos, Q):
+        try:
+            pairs = [(int(lo), int(hi)) for lo, hi in windows]
+        except (TypeError, ValueError):
+            raise ValueError("windows must be a sequence of (lo, hi) pairs") from None
+        if not 1 <= len(pairs) <= 16:
+            raise ValueError("windows must hold 1..16 (lo, hi) pairs, got %d" % len(pairs))
+        for lo, hi in pairs:
+            if not 0 <= lo < hi <= Q:
+                raise ValueError("every window needs 0 <= lo < hi <= Q = %d, got (%d, %d)" % (Q, lo, hi))
+        if int(pos) < 0:
+            raise ValueError("window_pos (the stream position of the first code) must be >= 0, got %d" % int(pos))
+        self.pairs, self.pos = pairs, int(pos)
+        self.host = (ctypes.c_int32 * (2 * len(pairs)))(*[v for pr in pairs for v in pr])
+
+    def at(self, pos):
+        """The pair of stream position ``pos``."""
+        return self.pairs[pos % len(self.pairs)]
+
+    def tail(self, ahead=0):
+        """The arguments wn_win_decode_batch / wn_win_sample_logits take behind the entry they extend (before the stream), for a
+        launch whose first step sits ``ahead`` positions behind ``pos``."""
+        return ctypes.cast(self.host, ctypes.c_void_p), len(self.pairs), self.pos + ahead
+
+
+def _windows_of(windows, window_pos, Q):
+    if windows is None:
+        if window_pos:
+            raise ValueError("window_pos is the position inside a window table: pass windows= with it")
+        return None
+    return _Windows(windows, window_pos, Q)
+
+
+def _need_corrected_win(win, correct_queue):
+    if win is not None and not correct_queue:
+        raise ValueError("position windows run on the corrected recurrence only (wn_win_decode_batch): pass correct_queue=True")
+
+
+def _first_in_window(probs, win):
+    """First-index argmax of every row of the init forward's probabilities (U, Q) inside the window of position ``win.pos``,
+    taken on the host; reported in the full alphabet."""
+    lo, hi = win.at(win.pos)
+    return torch.from_numpy(lo + np.argmax(probs.detach().float().cpu().numpy()[:, lo:hi], axis=1)).to(probs.device)
+
+
 def _pack_for(net, eng):
     """The decode weight pack of `eng`, kept on the net (built on first use; refreshed by the launcher)."""
     pack = getattr(net, "_decode_pack", None)
@@ -318,13 +374,17 @@ def _pack_for(net, eng):
     return pack
 
 
-def _decode_call(shape, dil, qoff, queues, weights, io, step0, n_steps, push_input, sync, U, queues_ustride, smp, pk, cond=None):
+def _decode_call(shape, dil, qoff, queues, weights, io, step0, n_steps, push_input, sync, U, queues_ustride, smp, pk, cond=None,
+                 win=None):
     """(entry point, its arguments without the stream) of one decode launch: THE place the argument list is written and the
     entry chosen.  Plain values and pointers only (no device work).  ``shape``: (filter_width, N, Rp, Dp, S, Q); ``weights``:
     ``_DecodePack.weights()``; ``io``: note0, prev0, note_out, prev_out, forced, codes, probs; ``pk``: ``_DecodePack.chain()``;
-    ``cond``: the eight table arguments of wn_decode_batch_cond when the launch came in through ``decode_batch_cond``."""
+    ``cond``: the eight table arguments of wn_decode_batch_cond when the launch came in through ``decode_batch_cond``;
+    ``win``: the three window arguments (``_Windows.tail``) - only then is the entry wn_win_decode_batch, whatever the sampling."""
     args = (*shape, dil, qoff, queues, *weights, *io, step0, n_steps, push_input, sync, U, queues_ustride,
             smp.temperature, smp.seed, *pk)
+    if win is not None:
+        return "wn_win_decode_batch", args + (_NO_COND if cond is None else tuple(cond)) + smp.tail() + tuple(win)
     if smp.plain and cond is None:
         return "wn_decode_batch_fw", args
     args += _NO_COND if cond is None else tuple(cond)
@@ -334,9 +394,9 @@ def _decode_call(shape, dil, qoff, queues, weights, io, step0, n_steps, push_inp
 
 
 def _launch_decode(net, eng, smp, rings, note0, prev0, U, n_steps, step0, push_input, timeout_msg, check=True, forced=None,
-                   want_probs=False, sync=None, cond=None):
+                   want_probs=False, sync=None, cond=None, win=None):
     """One persistent decode launch of U utterances: ``rings`` ((U, ring floats), or 1-D for one utterance) is advanced in
-    place.  ``sync``: the hand-off scratch (default: fresh and zeroed); ``check``: read the error flags back and raise
+    place.  ``win``: the window arguments of the launch's first step (``_Windows.tail``), or None.  ``sync``: the hand-off scratch (default: fresh and zeroed); ``check``: read the error flags back and raise
     ``timeout_msg`` if one is set.  Returns (codes int32 (U, n_steps), probabilities (U, n_steps, Q) or None, note_out (U, Q),
     prev_out (U, k-1, Q))."""
     global last_error_flags
@@ -357,7 +417,7 @@ def _launch_decode(net, eng, smp, rings, note0, prev0, U, n_steps, step0, push_i
                               ctypes.cast(qoff, ctypes.c_void_p), ptr(qbuf), pack.weights(),
                               (ptr(note0), _ptr_or_none(prev0), ptr(note_out), _ptr_or_none(prev_out), ptr(forced_t), ptr(codes),
                                ptr(probs)), int(step0), n_steps, push_input, ptr(sync), U, rings.size(1) if rings.dim() == 2 else 0,
-                              smp, pack.chain(), cond)
+                              smp, pack.chain(), cond, win)
     call(name, *args, _lib.stream())
     flags = sync.view(U, -1)[:, -1]                          # the error flag word of every utterance
     if cond is not None:
@@ -368,7 +428,7 @@ def _launch_decode(net, eng, smp, rings, note0, prev0, U, n_steps, step0, push_i
 
 
 def _decode(net, state, note0, n_steps, forced=None, want_probs=False, correct_queue=False, temperature=None, seed=0,
-            top_k=None, top_p=None):
+            top_k=None, top_p=None, win=None):
     eng = state.eng
     _check_recurrence(eng, correct_queue)
     smp = _Sampling(1, temperature, top_k, top_p, seed, None, eng.device)
@@ -384,7 +444,7 @@ def _decode(net, state, note0, n_steps, forced=None, want_probs=False, correct_q
     codes, probs, note_out, prev_out = _launch_decode(
         net, eng, smp, state.rings, note0, state.prev, 1, n_steps, state.steps, 1 if correct_queue else 0,
         "wn_decode: a hand-off between the two decode workgroups timed out", check=n_steps >= 4, forced=forced,
-        want_probs=want_probs, sync=sync)
+        want_probs=want_probs, sync=sync, win=win)
     state.prev = prev_out.view(-1)
     state.steps += n_steps
     return codes[0], probs[0] if want_probs else None, note_out[0]
@@ -401,17 +461,22 @@ def _rings_from_workspace(eng, U, T):
                       for i, d in enumerate(eng.dil)], 1).contiguous()
 
 
+def _init_forward(net, note):
+    """The full forward over a ``(1, Q, receptive_field)`` piece: (probabilities (1, Q), the queues it leaves)."""
+    assert note.size()[2] == net.receptive_field
+    dev = note.device if note.is_cuda else torch.device("cuda")
+    x = note.detach().to(dev).float().contiguous()
+    with torch.no_grad():
+        probs = net(x)                                            # (1, Q): W == 1
+    eng, T, K1 = net._engine, x.size(2), _taps(net._engine)
+    # the causal layer's queue = the last k-1 input columns
+    return probs, DecodeState(eng, _rings_from_workspace(eng, 1, T)[0], x[0, :, T - K1:T].t().contiguous().view(-1), 0)
+
+
 def predict_next(net, note, state_queue=None, correct_queue=False):
     """wavenet/fast_generate.py:13-141."""
     if state_queue is None:
-        assert note.size()[2] == net.receptive_field
-        dev = note.device if note.is_cuda else torch.device("cuda")
-        x = note.detach().to(dev).float().contiguous()
-        with torch.no_grad():
-            probs = net(x)                                        # (1, Q): W == 1
-        eng, T, K1 = net._engine, x.size(2), _taps(net._engine)
-        # the causal layer's queue = the last k-1 input columns
-        state = DecodeState(eng, _rings_from_workspace(eng, 1, T)[0], x[0, :, T - K1:T].t().contiguous().view(-1), 0)
+        probs, state = _init_forward(net, note)
         _, predict = torch.topk(probs.view(-1), 1)
         return predict.to(note.device), state
     assert note.size()[2] == 1
@@ -423,26 +488,37 @@ def predict_next(net, note, state_queue=None, correct_queue=False):
     return codes.to(torch.int64).to(note.device), state_queue
 
 
-def generate_codes(net, start_piece, note_num, correct_queue=False, temperature=None, seed=0, top_k=None, top_p=None):
+def generate_codes(net, start_piece, note_num, correct_queue=False, temperature=None, seed=0, top_k=None, top_p=None,
+                   windows=None, window_pos=0):
     """The greedy loop of fast_generate.py:162-172 as one init forward + ONE persistent launch.
     Returns the note_num generated codes (int64, on the device).
     ``temperature`` (the reference is greedy only): if given and > 0, every code after the
     first is SAMPLED from softmax(logits / temperature), reproducibly for a given ``seed``.
     ``top_k`` / ``top_p``: the distribution is truncated first (include/wavenet_hip.h, wn_decode_batch_samp: the top_k largest
-    logits, then the smallest head whose mass reaches top_p, ties kept); corrected recurrence only."""
+    logits, then the smallest head whose mass reaches top_p, ties kept); corrected recurrence only.
+    ``windows`` / ``window_pos``: 1..16 ``(lo, hi)`` pairs and the stream position of the first code returned; the code at
+    position p is chosen inside pair ``p % len(windows)`` only, renormalised there (include/wavenet_hip.h,
+    wn_win_decode_batch; ``stage_windows`` for a residual quantiser's token stream).  The first code is the first-index argmax
+    of the init forward inside its window.  Corrected recurrence only."""
+    win = _windows_of(windows, window_pos, net.quantization_channels)
+    _need_corrected_win(win, correct_queue)
     with torch.no_grad():
-        first, state = predict_next(net, start_piece, None)
+        if win is None:
+            first, state = predict_next(net, start_piece, None)
+        else:
+            probs, state = _init_forward(net, start_piece)
+            first = _first_in_window(probs.view(1, -1), win)
     if note_num <= 1:
         return first.to(state.eng.device)[:note_num]
     note0 = torch.zeros(net.quantization_channels, dtype=torch.float32, device=state.eng.device)
     note0[int(first[0])] = 1.0
     codes, _, _ = _decode(net, state, note0, note_num - 1, correct_queue=correct_queue, temperature=temperature, seed=seed,
-                          top_k=top_k, top_p=top_p)
+                          top_k=top_k, top_p=top_p, win=win.tail(1) if win is not None else None)
     return torch.cat([first.to(codes.device).to(torch.int64), codes.to(torch.int64)])
 
 
 def generate_codes_batch(net, start_pieces, note_num, correct_queue=False, temperature=None, seed=0, top_k=None, top_p=None,
-                         streams=None):
+                         streams=None, windows=None, window_pos=0):
     """SURVEY 8f2 (batched utterances; the reference generates one at a time): greedy generation of
     ``note_num`` codes for U independent start pieces ``(U, Q, receptive_field)`` in ONE persistent
     launch - on the matrix-core path eight utterances to a workgroup pair, one pair of MFMA result columns each (else one
@@ -451,8 +527,11 @@ def generate_codes_batch(net, start_pieces, note_num, correct_queue=False, tempe
     ``temperature``, ``top_k``, ``top_p`` and ``seed`` may each be a scalar or one value per utterance (a sweep of settings
     over one prompt, N takes of one prompt); ``streams``: the random-number stream id of every utterance (default: its
     index; row u is then the single-utterance launch with ``streams=[u]``, bit for bit when both run the same kernel form,
-    see WN_DEC_KS).  Truncation and per-utterance settings run on the corrected recurrence only."""
+    see WN_DEC_KS).  Truncation and per-utterance settings run on the corrected recurrence only.
+    ``windows`` / ``window_pos``: as in ``generate_codes``; one table and one position for the whole launch."""
     assert start_pieces.dim() == 3 and start_pieces.size(2) == net.receptive_field
+    win = _windows_of(windows, window_pos, net.quantization_channels)
+    _need_corrected_win(win, correct_queue)
     U = start_pieces.size(0)
     if U > 1024:
         raise ValueError("at most 1024 utterances per launch (128 off the matrix-core path)")
@@ -463,7 +542,7 @@ def generate_codes_batch(net, start_pieces, note_num, correct_queue=False, tempe
     eng = net._engine
     T, Q, K1 = x.size(2), eng.Q, _taps(eng)
     rings = _rings_from_workspace(eng, U, T)
-    first = probs.view(U, Q).argmax(1)
+    first = probs.view(U, Q).argmax(1) if win is None else _first_in_window(probs.view(U, Q), win)
     if note_num <= 1:
         return first.view(U, 1)[:, :note_num]
     _check_recurrence(eng, correct_queue)
@@ -473,12 +552,14 @@ def generate_codes_batch(net, start_pieces, note_num, correct_queue=False, tempe
     note0[torch.arange(U, device=dev), first] = 1.0
     prev0 = x[:, :, T - K1:T].transpose(1, 2).contiguous()         # [U][k-1][Q], oldest column first
     codes, _, _, _ = _launch_decode(net, eng, smp, rings, note0, prev0, U, note_num - 1, 0, 1 if correct_queue else 0,
-                                    "wn_decode_batch: a hand-off between two decode workgroups timed out", check=note_num - 1 >= 4)
+                                    "wn_decode_batch: a hand-off between two decode workgroups timed out", check=note_num - 1 >= 4,
+                                    win=win.tail(1) if win is not None else None)
     return torch.cat([first.view(U, 1).to(torch.int64), codes.to(torch.int64)], 1)
 
 
 def decode_batch_cond(net, rings, prev0, note0, n_steps, step0=0, pos0=0, forced=None, want_probs=False, temperature=None,
-                      seed=0, cond_fg=None, cond_p1=None, schedule=None, top_k=None, top_p=None, streams=None):
+                      seed=0, cond_fg=None, cond_p1=None, schedule=None, top_k=None, top_p=None, streams=None, windows=None,
+                      window_pos=0):
     """One persistent launch of wn_decode_batch_cond (corrected recurrence) for U utterances from explicit state: ``rings``
     (U, ring floats) is advanced in place, ``prev0`` (U, k-1, Q) / ``note0`` (U, Q) are the causal layer's history and the
     first input column.  ``cond_fg`` (U, N, Le, 2 Dp) rows [f | g] and ``cond_p1`` (U, Le, S) are the per-utterance
@@ -486,6 +567,8 @@ def decode_batch_cond(net, rings, prev0, note0, n_steps, step0=0, pos0=0, forced
     ``ae_generate.cond_schedule``; step s is output position pos0 + s.  ``forced`` (U, n_steps): the next input codes.
     ``temperature`` / ``top_k`` / ``top_p`` / ``seed``: scalars or one value per utterance, ``streams`` the random-number stream
     ids (default: the utterance index); anything beyond a scalar temperature and seed goes through wn_decode_batch_samp.
+    ``windows`` / ``window_pos``: position windows shared by the launch, step s samples inside pair ``(window_pos + s) %
+    len(windows)`` (wn_win_decode_batch; independent of ``step0`` and ``pos0``).
     Returns (codes int32 (U, n_steps), probabilities (U, n_steps, Q) or None, note_out, prev_out)."""
     eng = net._engine_for(rings.device)
     pack = _pack_for(net, eng)
@@ -496,6 +579,7 @@ def decode_batch_cond(net, rings, prev0, note0, n_steps, step0=0, pos0=0, forced
     if U > (1024 if pack.mfma else 128):
         raise ValueError("at most 1024 utterances per launch (128 off the matrix-core path)")
     smp = _Sampling(U, temperature, top_k, top_p, seed, streams, dev)
+    win = _windows_of(windows, window_pos, eng.Q)
     le = 1
     shift = qs = None
     if cond_fg is not None or cond_p1 is not None:
@@ -513,14 +597,16 @@ def decode_batch_cond(net, rings, prev0, note0, n_steps, step0=0, pos0=0, forced
             cond_p1[0].numel() if cond_p1 is not None else 0, shift, qs, le, int(pos0))
     return _launch_decode(net, eng, smp, rings, note0, prev0, U, n_steps, step0, 1,
                           "wn_decode_batch_cond: a hand-off between two decode workgroups timed out", forced=forced,
-                          want_probs=want_probs, cond=cond)
+                          want_probs=want_probs, cond=cond, win=win.tail() if win is not None else None)
 
 
-def sample_logits(logits, temperature=1.0, top_k=None, top_p=None, seed=0, step0=0, u=None, want_probs=False, streams=None):
+def sample_logits(logits, temperature=1.0, top_k=None, top_p=None, seed=0, step0=0, u=None, want_probs=False, streams=None,
+                  windows=None, window_pos=0):
     """The decoder's sampler (the same device function, wn_sample_logits) on a matrix of pre-softmax logits ``(n, Q)``,
     Q <= 1024: row i is drawn as "step" ``step0 + i``.  ``temperature`` (<= 0 / None: greedy argmax), ``top_k``, ``top_p`` and
     ``seed`` may each be a scalar or one value per row (``streams``: the rows' random-number stream ids, default 0);
-    ``u`` (n,) replaces the generated uniform numbers.  Returns the codes (int64, on the device), with ``want_probs`` also the
+    ``u`` (n,) replaces the generated uniform numbers.  ``windows`` / ``window_pos``: row i samples inside pair ``(window_pos +
+    i) % len(windows)`` of the table (wn_win_sample_logits), independent of ``step0``.  Returns the codes (int64, on the device), with ``want_probs`` also the
     distributions drawn from ``(n, Q)``.  This is what a one-forward-per-sample generator calls on the forward's logits."""
     if logits.dim() != 2 or not logits.is_cuda:
         raise ValueError("sample_logits: logits must be a (n, Q) device tensor")
@@ -531,6 +617,7 @@ def sample_logits(logits, temperature=1.0, top_k=None, top_p=None, seed=0, step0
     if not 1 <= Q <= 1024:
         raise ValueError("sample_logits: 1 <= Q <= 1024")
     smp = _Sampling(n, temperature, top_k, top_p, seed, streams, x.device, default_stream=0)
+    win = _windows_of(windows, window_pos, Q)
     u_t = None
     if u is not None:
         u_t = torch.as_tensor(u, dtype=torch.float32).to(x.device).contiguous()
@@ -538,8 +625,12 @@ def sample_logits(logits, temperature=1.0, top_k=None, top_p=None, seed=0, step0
             raise ValueError("sample_logits: u must hold one number per row")
     codes = torch.empty(n, dtype=torch.int32, device=x.device)
     probs = torch.empty(n, Q, dtype=torch.float32, device=x.device) if want_probs else None
-    call("wn_sample_logits", ptr(x), n, Q, x.stride(0) if n > 1 else max(Q, x.stride(0)), ptr(smp.table), smp.temperature, smp.seed,
-         int(smp.top_k), float(smp.top_p), int(step0), ptr(u_t), ptr(codes), ptr(probs), _lib.stream())
+    args = (ptr(x), n, Q, x.stride(0) if n > 1 else max(Q, x.stride(0)), ptr(smp.table), smp.temperature, smp.seed, int(smp.top_k),
+            float(smp.top_p), int(step0), ptr(u_t), ptr(codes), ptr(probs))
+    if win is None:
+        call("wn_sample_logits", *args, _lib.stream())
+    else:
+        call("wn_win_sample_logits", *args, *win.tail(), _lib.stream())
     codes = codes.to(torch.int64)
     return (codes, probs) if want_probs else codes
 

@@ -6,7 +6,9 @@ recurrence, the only one defined there).  `--cond-frames N`: the same decoder CO
 tables of N frames with the schedule of a 16000-sample clip (config 4: N = 25), biased, corrected recurrence, from zero queues -
 to be compared with `--bias` (the unconditioned biased decoder of the same shape).
 `--temperature T`: sample instead of the greedy argmax; `--top-k K` / `--top-p P`: truncate the distribution first
-(wn_decode_batch_samp; corrected recurrence, temperature 1 unless given); `--runs N`: repeat the whole measurement."""
+(wn_decode_batch_samp; corrected recurrence, temperature 1 unless given); `--windows S,K`: sample under the position windows of an
+S-stage token stream of K codes per stage (wn_win_decode_batch with fast_generate.stage_windows(S, K); corrected recurrence,
+temperature 1 unless given); `--runs N`: repeat the whole measurement."""
 import os
 import sys
 import time
@@ -33,12 +35,16 @@ def _opt(name, conv, default=None):
 def sampling():
     """generate_codes' sampling arguments from the command line, and whether they need the corrected recurrence"""
     top_k, top_p = _opt("--top-k", int), _opt("--top-p", float)
+    windows = _opt("--windows", lambda v: tuple(int(x) for x in v.split(",")))
     filtered = top_k is not None or top_p is not None
-    T = _opt("--temperature", float, 1.0 if filtered else None)
+    T = _opt("--temperature", float, 1.0 if filtered or windows else None)
     kw = dict(temperature=T, seed=1)
     if filtered:
         kw.update(top_k=top_k, top_p=top_p)
-    return kw, filtered
+    if windows:
+        from music_amd import fast_generate as fg
+        kw.update(windows=fg.stage_windows(*windows))
+    return kw, filtered or bool(windows)
 
 
 def main_cond(le):
@@ -86,7 +92,8 @@ def main():
     n = 16000
     kw, filtered = sampling()
     correct = k != 2 or filtered
-    what = ", ".join("%s %s" % kv for kv in kw.items() if kv[1] is not None and kv[0] != "seed") or "greedy"
+    what = ", ".join("%s %s" % (key, "%d pairs" % len(v) if key == "windows" else v) for key, v in kw.items()
+                     if v is not None and key != "seed") or "greedy"
     for run in range(_opt("--runs", int, 1)):
         for rep in range(2):
             torch.cuda.synchronize()

@@ -19,7 +19,8 @@ encoded in windows of --frames pooled frames (rf - 1 samples of overlap, so ever
 A model with "vq_stages": S > 1 gives S codes per frame.  A piece is still ONE array, frame-major - l0s0, l0s1, .., l1s0, .. - of
 TOKENS s * K + code, so the prior's alphabet ("quantization_channels") is S * K and a position's stage is readable from its
 token; S * K > 1024, the decoder's sampler limit, is refused.  music_amd.ae_generate.split_code_stream turns a sampled stream back
-into the (B, S, Le) codes that decode_codes takes."""
+into the (B, S, Le) codes that decode_codes takes; music_amd.ae_generate.sample_code_stream samples the prior under the decoder's
+position windows, so a token never leaves its position's stage range and the stream always splits."""
 import argparse
 import json
 import os
