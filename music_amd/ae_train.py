@@ -75,7 +75,7 @@ try:
     from . import objective as wobjective
     from .faster_audio_data import audio_data_loader
     from .model1 import wavenet_autoencoder
-    from .train import get_params, load_model
+    from .train import FlatOptimizer, get_params, load_model
 except ImportError:
     from music_amd import dist as wdist
     from music_amd import ema
@@ -83,7 +83,7 @@ except ImportError:
     from music_amd import objective as wobjective
     from music_amd.faster_audio_data import audio_data_loader
     from music_amd.model1 import wavenet_autoencoder
-    from music_amd.train import get_params, load_model
+    from music_amd.train import FlatOptimizer, get_params, load_model
 
 PREFIX = "wavenet_autoencoder"
 
@@ -104,17 +104,7 @@ def _host_guarded(cls):
     """`cls` (a torch optimizer class) with the guard's rule applied on the host before every step (music_amd/guard.py): the step of
     this harness is torch's own per-tensor path, where a read-back per step is already the rule.  With `ema` (ema_decay set) every
     step ends with the shadow's update (music_amd/ema.py), guarded or not."""
-    class Guarded(guard.GuardedOptimizer, cls):
-        def __init__(self, model, max_grad_norm, skip_nonfinite, ema_decay=None, ema_warmup=False, **kw):
-            super().__init__(model.parameters(), **kw)
-            self._model = model
-            self._guard_setup(max_grad_norm, skip_nonfinite)
-            self._ema_setup(model.named_parameters(), ema_decay, ema_warmup)
-
-        def load_state_dict(self, state_dict):
-            super().load_state_dict(state_dict)
-            self._guard_reseed()
-
+    class Guarded(FlatOptimizer, cls):                    # its constructor and load_state_dict; the step stays torch's
         def step(self, closure=None):
             return self._torch_step(closure)
     Guarded.__name__ = Guarded.__qualname__ = "Guarded" + cls.__name__

@@ -5,9 +5,10 @@ reference keeps none.
 ``ShadowParams`` owns the shadow and is updated by ONE ``wn_ema_flat`` launch behind the optimizer's update (include/wavenet_hip.h)
 - not by ``torch._foreach_lerp_`` over 123 tensors, and not on the host: under the guarded step (music_amd/guard.py) only the
 device knows whether a step was taken and which step it was, so the launch reads the guard's ``wn_guard_state``: a skipped step
-leaves the shadow bit for bit, and the warm-up counts the steps TAKEN.  The fused step of the three engines
-(``EngineBase.adam_init(ema_decay=...)``) and the flat optimizers of music_amd/train.py (``get_optimizer(ema_decay=...)``) end
-with that launch; a step on torch's own path ends with the same rule in plain torch (``host_update``).
+leaves the shadow bit for bit, and the warm-up counts the steps TAKEN.  ``guard.flat_step`` ends with that launch - the fused step
+of the engines (``EngineBase.adam_init(ema_decay=...)``) and the flat optimizers of music_amd/train.py
+(``get_optimizer(ema_decay=...)``) both go through it; a step on torch's own path ends with the same rule in plain torch
+(``host_update``, from ``GuardedOptimizer._torch_step``).
 
 Rule (float32; swa_utils.get_ema_avg_fn's lerp, TensorFlow's num_updates warm-up):
     d_eff = min(decay, (1 + T) / (10 + T)) with warm-up, else decay ;  w = 1 - d_eff ;  ema += w * (p - ema)

@@ -724,17 +724,6 @@ class EngineBase:
         return guard.engine_guard_report(self)
 
     def adam_step(self, gscale=1.0):
-        """torch.optim.Adam semantics on the flat parameter buffer."""
-        s = self.adam_state
-        shadow = s.get("ema")
-        if shadow is not None:
-            shadow.check_step()
-        if s.get("guard") is not None:
-            return guard.adam_step_guarded(self, gscale)
-        s["t"] += 1
-        call("wn_adam_flat", ptr(self.flat), ptr(self.flat_grad), ptr(s["m"]), ptr(s["v"]), self.spec.total,
-             s["lr"], s["b1"], s["b2"], s["eps"], 1.0 - s["b1"] ** s["t"], 1.0 - s["b2"] ** s["t"], gscale, _lib.stream())
-        if self.vq_ema:
-            self.vq_ema_step()
-        if shadow is not None:
-            shadow.update(self)
+        """torch.optim.Adam semantics on the flat parameter buffer (guarded with adam_init's options; the codebook's EMA update and
+        the shadow's follow the update: guard.flat_step)."""
+        guard.engine_adam_step(self, gscale)

@@ -2,8 +2,10 @@
 (``wn_grad_guard`` + the ``*_guarded`` updates, include/wavenet_hip.h) - what ``torch.nn.utils.clip_grad_norm_`` plus a finiteness
 check would do between ``backward()`` and ``step()``, without the 123 small launches and without the host reading the norm.
 
-``GradGuard`` owns the device-resident ``wn_guard_state`` block and the scratch of one optimizer; the fused steps of the three
-engines and the flat optimizers of music_amd/train.py go through it.  ``report()`` is the only synchronisation.
+``GradGuard`` owns the device-resident ``wn_guard_state`` block and the scratch of one optimizer.  ``flat_step`` issues every update
+of an engine's flat buffers, plain or guarded, and what follows it (the codebook's EMA update, the EMA shadow's): the fused step of
+the engines (``engine_adam_step``) and the flat optimizers of music_amd/train.py end there.  ``GuardedOptimizer`` is what those
+optimizers and the host-guarded ones of music_amd/ae_train.py share on torch's own path.  ``report()`` is the only synchronisation.
 """
 import math
 import sys
@@ -69,7 +71,26 @@ class GradGuard:
                     skipped=int(s.n_skipped), nonfinite=int(s.nonfinite))
 
 
-# ---------------------------------------------------------------- the fused step of an engine (engine.py, plan_generic.py, model1.py)
+# ---------------------------------------------------------------- the end of a step: every optimizer update on the flat buffers
+def flat_step(eng, entry, gptr, state, plain, guarded, gd=None, shadow=None, gscale=1.0):
+    """THE update of eng.flat and what follows it, on the current stream: `entry`(p, g, *state, n, *plain), or under the GradGuard
+    `gd` its two launches and `entry`_guarded(p, g, *state, n, *guarded, the guard's state block); then the codebook's EMA update
+    of an engine in that mode, then the `shadow`'s (music_amd/ema.py) - both reading the guard's decision.  The flat optimizers of
+    music_amd/train.py and the fused step of the engines end here, so the order is written once.  `gptr`: the flat gradient,
+    `state`: the optimizer's flat state buffers, `gscale`: what the guard measures the gradient with (the update's own is in the tails)."""
+    n = eng.spec.total
+    if gd is None:
+        _lib.call(entry, _lib.ptr(eng.flat), gptr, *state, n, *plain, _lib.stream())
+    else:
+        gd.run(gptr, n, gscale)
+        _lib.call(entry + "_guarded", _lib.ptr(eng.flat), gptr, *state, n, *guarded, gd.state_ptr(), _lib.stream())
+    if getattr(eng, "vq_ema", False):
+        eng.vq_ema_step(gd)
+    if shadow is not None:
+        shadow.update(eng, gd)
+
+
+# ---------------------------------------------------------------- the fused step of an engine (EngineBase.adam_init / adam_step)
 def adam_init_guard(state, device, max_grad_norm, skip_nonfinite):
     """adam_init of an engine: adds the guard to its adam_state when either option is set."""
     state["guard"] = (GradGuard(device, max_grad_norm, skip_nonfinite, (state["b1"], state["b2"]))
@@ -77,20 +98,24 @@ def adam_init_guard(state, device, max_grad_norm, skip_nonfinite):
     return state
 
 
-def adam_step_guarded(eng, gscale):
-    """wn_grad_guard + wn_adam_flat_guarded on the engine's flat buffers (+ wn_ema_flat reading the same decision, with
-    adam_init(ema_decay=...)).  adam_state["t"] counts the steps ISSUED until guard_report() replaces it by the device's count of
-    steps taken."""
+def engine_adam_step(eng, gscale=1.0):
+    """torch.optim.Adam semantics on the engine's flat buffers: wn_adam_flat, or with adam_init's guard wn_grad_guard +
+    wn_adam_flat_guarded, and the tail of flat_step.  adam_state["t"] counts the steps ISSUED; under the guard guard_report()
+    replaces it by the device's count of steps taken."""
     s = eng.adam_state
-    gd = s["guard"]
+    shadow = s.get("ema")
+    if shadow is not None:
+        shadow.check_step()
     s["t"] += 1
-    gd.run(_lib.ptr(eng.flat_grad), eng.spec.total, gscale)
-    _lib.call("wn_adam_flat_guarded", _lib.ptr(eng.flat), _lib.ptr(eng.flat_grad), _lib.ptr(s["m"]), _lib.ptr(s["v"]), eng.spec.total,
-              s["lr"], s["b1"], s["b2"], s["eps"], gscale, gd.state_ptr(), _lib.stream())
-    if getattr(eng, "vq_ema", False):
-        eng.vq_ema_step(gd)
-    if s.get("ema") is not None:
-        s["ema"].update(eng, gd)
+    hyper = (s["lr"], s["b1"], s["b2"], s["eps"])
+    flat_step(eng, "wn_adam_flat", _lib.ptr(eng.flat_grad), (_lib.ptr(s["m"]), _lib.ptr(s["v"])),
+              hyper + (1.0 - s["b1"] ** s["t"], 1.0 - s["b2"] ** s["t"], gscale), hyper + (gscale,), s.get("guard"), shadow, gscale)
+
+
+def adam_step_guarded(eng, gscale):
+    """The guarded form of engine_adam_step, for a caller that holds an engine whose adam_state has a guard."""
+    assert eng.adam_state["guard"] is not None
+    engine_adam_step(eng, gscale)
 
 
 def engine_guard_report(eng):
@@ -120,13 +145,6 @@ class GuardedOptimizer:
 
     ema = None                   # the ShadowParams of music_amd/ema.py when ema_decay is set (_ema_setup), else None
     _model = None                # the module whose parameters these are, where the optimizer was given it
-
-    def _vq_ema_step(self, eng=None, gd=None, taken=True):
-        """A model whose vq codebook follows EMA updates: its engine's wn_vq_ema_update, behind the step's parameter update and in
-        front of the shadow's.  `gd`: the GradGuard whose decision the device reads; `taken`: the host's decision on torch's path."""
-        eng = eng if eng is not None else getattr(self._model, "_engine", None)
-        if taken and eng is not None and getattr(eng, "vq_ema", False):
-            eng.vq_ema_step(gd)
 
     def _guard_setup(self, max_grad_norm, skip_nonfinite):
         self._guard_opts = (max_grad_norm, bool(skip_nonfinite)) if enabled(max_grad_norm, skip_nonfinite) else None
@@ -181,28 +199,31 @@ class GuardedOptimizer:
         """norm / coef / taken / clipped / skipped / nonfinite of the guard (synchronises); None before the first guarded step."""
         return None if self._guard is None else self._guard.report()
 
-    def _torch_step(self, closure=None):
+    def _torch_step(self, closure=None, checked=False):
         """torch's own step; guarded: the same rule on the host first (clip_grad_norm_, and a non-finite gradient is not applied).
-        With `ema`, the shadow's update in plain torch follows a step that was taken."""
+        With `ema`, the shadow's update in plain torch follows a step that was taken (`checked`: the caller has made its
+        check_step() already)."""
         params = [p for grp in self.param_groups for p in grp["params"]]
-        if self.ema is not None:
+        if self.ema is not None and not checked:
             self.ema.check_step()
+        taken, gd = True, None
         if self._guard_opts is None:
             loss = super().step(closure)
-            self._vq_ema_step()
-            if self.ema is not None:
-                self.ema.host_update(params)
-            return loss
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        gd = self._guard_get(params[0].device)
-        self._guard_sync_steps()
-        taken = gd.host_rule(params)
-        if taken:
-            super().step()
-        self._vq_ema_step(taken=taken)
+        else:
+            loss = None
+            if closure is not None:
+                with torch.enable_grad():
+                    loss = closure()
+            gd = self._guard_get(params[0].device)
+            self._guard_sync_steps()
+            taken = gd.host_rule(params)
+            if taken:
+                super().step()
+        # a model whose vq codebook follows EMA updates: its engine's update behind the parameters' and in front of the shadow's, as
+        # in flat_step - but on the HOST's decision, which is why neither reads the guard's state block here
+        eng = getattr(self._model, "_engine", None)
+        if taken and eng is not None and getattr(eng, "vq_ema", False):
+            eng.vq_ema_step()
         if self.ema is not None:
             self.ema.host_update(params, taken, gd)
         return loss

@@ -67,101 +67,6 @@ def get_arguments():
             get_params('./params/dataset_params.json'))
 
 
-class FlatAdam(guard.GuardedOptimizer, optim.Adam):
-    """``torch.optim.Adam`` whose ``step()`` is ONE ``wn_adam_flat`` launch when it can be.
-
-    The module's parameters are views of one flat buffer (music_amd/engine.py) and the gradients autograd hands to them
-    are views of one flat buffer too (``_WaveNetFunction.backward``), so the 123 per-tensor updates of the reference's
-    ``optim.Adam(model.parameters(), lr)`` (wavenet/train.py:39-42) are one elementwise pass.  The optimizer state is
-    torch's own - per parameter ``step`` / ``exp_avg`` / ``exp_avg_sq`` - with the two moment tensors being VIEWS of two flat
-    buffers: ``state_dict()`` / ``load_state_dict()`` interchange with ``torch.optim.Adam``, and any step the fast path
-    does not cover (parameters not on the flat buffer yet, gradients that are not one flat tensor, weight decay /
-    amsgrad / maximize / closures, several parameter groups) falls through to ``torch.optim.Adam.step`` on the same state."""
-
-    def __init__(self, model, lr, max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=False):
-        super().__init__(model.parameters(), lr=lr)
-        self._model = model
-        self._guard_setup(max_grad_norm, skip_nonfinite)
-        self._ema_setup(model.named_parameters(), ema_decay, ema_warmup)
-        self._flat = None            # (engine, m, v, steps): flat moments of that engine's flat parameter buffer
-
-    def _fast_state(self):
-        eng = getattr(self._model, "_engine", None)
-        if eng is None or getattr(eng, "flat", None) is None or len(self.param_groups) != 1:
-            return None
-        g = self.param_groups[0]
-        if g.get("weight_decay", 0) != 0 or g.get("amsgrad") or g.get("maximize") or g.get("capturable") or g.get("differentiable"):
-            return None
-        params = g["params"]
-        named = [p for _, p in self._model.named_parameters()]
-        if len(params) != len(named) or any(a is not b for a, b in zip(params, named)):
-            return None
-        base = eng.flat.data_ptr()
-        if any(p.data_ptr() != base + 4 * eng.spec.off[n] for n, p in zip(eng.param_names, params)):
-            return None                                   # (the module was moved: its parameters left the flat buffer)
-        if self._flat is not None and self._flat[0] is eng:
-            return self._flat
-        # adopt whatever per-parameter state exists (a loaded state_dict, earlier torch steps) into flat moment buffers
-        m, v = torch.zeros_like(eng.flat), torch.zeros_like(eng.flat)
-        steps = []
-        for n, p in zip(eng.param_names, params):
-            o, k = eng.spec.off[n], p.numel()
-            st = self.state[p]
-            if "exp_avg" in st:
-                m[o:o + k].copy_(st["exp_avg"].reshape(-1))
-                v[o:o + k].copy_(st["exp_avg_sq"].reshape(-1))
-            step = st.get("step")
-            step = torch.zeros((), dtype=torch.float32) if step is None else torch.as_tensor(step, dtype=torch.float32).detach().cpu().reshape(())
-            st["step"], st["exp_avg"], st["exp_avg_sq"] = step, m[o:o + k].view(p.shape), v[o:o + k].view(p.shape)
-            steps.append(step)
-        if any(float(s) != float(steps[0]) for s in steps):
-            return None                                   # parameters at different step counts: torch's per-tensor path
-        self._flat = (eng, m, v, steps)
-        return self._flat
-
-    def load_state_dict(self, state_dict):
-        super().load_state_dict(state_dict)
-        self._flat = None                                 # re-adopt the loaded tensors at the next step
-        self._guard_reseed()
-
-    @torch.no_grad()
-    def step(self, closure=None):
-        if self.ema is not None:
-            self.ema.check_step()
-        fast = self._fast_state() if closure is None else None
-        if fast is not None:
-            eng, m, v, steps = fast
-            params = self.param_groups[0]["params"]
-            g0 = params[0].grad
-            ok = g0 is not None and g0.dtype == torch.float32
-            if ok:
-                gbase = g0.data_ptr() - 4 * eng.spec.off[eng.param_names[0]]
-                ok = all(p.grad is not None and p.grad.is_contiguous() and p.grad.data_ptr() == gbase + 4 * eng.spec.off[n]
-                         for n, p in zip(eng.param_names, params))
-            if ok:
-                from music_amd import _lib
-                grp = self.param_groups[0]
-                if self._guard_opts is not None:          # guard + guarded update; the step counters follow the device's (state_dict())
-                    gd = self._guard_get(eng.flat.device)
-                    gd.run(gbase, eng.spec.total)
-                    _lib.call("wn_adam_flat_guarded", eng.flat.data_ptr(), gbase, m.data_ptr(), v.data_ptr(), eng.spec.total,
-                              float(grp["lr"]), grp["betas"][0], grp["betas"][1], grp["eps"], 1.0, gd.state_ptr(), _lib.stream())
-                    self._vq_ema_step(eng, gd)
-                    if self.ema is not None:
-                        self.ema.update(eng, gd)
-                    return None
-                torch._foreach_add_(steps, 1.0)
-                t = float(steps[0])
-                b1, b2 = grp["betas"]
-                _lib.call("wn_adam_flat", eng.flat.data_ptr(), gbase, m.data_ptr(), v.data_ptr(), eng.spec.total,
-                          float(grp["lr"]), b1, b2, grp["eps"], 1.0 - b1 ** t, 1.0 - b2 ** t, 1.0, _lib.stream())
-                self._vq_ema_step(eng)
-                if self.ema is not None:
-                    self.ema.update(eng)
-                return None
-        return self._torch_step(closure)
-
-
 def _flat_layout(opt, model, plain_group):
     """(engine, params, flat gradient base pointer) when `opt` can take its step as ONE launch on the engine's flat buffers: one
     parameter group holding exactly the module's parameters in order, every parameter a view of the flat parameter buffer, every
@@ -190,12 +95,13 @@ def _flat_layout(opt, model, plain_group):
     return eng, params, gbase
 
 
-def _flat_views(opt, eng, params, key, cache):
+def _flat_views(opt, eng, params, key, cache, validate=True):
     """One flat buffer for the per-parameter state tensors `key`, the state entries being VIEWS of it (so `state_dict()` /
     `load_state_dict()` interchange with torch's optimizer).  Existing per-parameter tensors (a loaded state_dict, earlier torch
-    steps) are adopted.  Returns (flat buffer, how many parameters had the entry before)."""
+    steps) are adopted.  Returns (flat buffer, how many parameters had the entry before).  The cached buffer is for this engine and
+    dropped by load_state_dict(); `validate`: it is also checked against the state entries, every step."""
     hit = cache.get(key)
-    if hit is not None and hit[0] is eng and all(opt.state[p].get(key) is v for p, v in zip(params, hit[2])):
+    if hit is not None and hit[0] is eng and (not validate or all(opt.state[p].get(key) is v for p, v in zip(params, hit[2]))):
         return hit[1], len(params)
     flat = torch.zeros_like(eng.flat)
     had, views = 0, []
@@ -213,125 +119,133 @@ def _flat_views(opt, eng, params, key, cache):
     return flat, had
 
 
-class FlatSGD(guard.GuardedOptimizer, optim.SGD):
-    """``torch.optim.SGD(model.parameters(), lr, momentum)`` (wavenet/train.py:28-31) whose ``step()`` is ONE ``wn_sgd_flat``
-    launch when it can be (see FlatAdam): same state (``momentum_buffer`` per parameter, views of one flat buffer), same
-    ``state_dict``; anything the kernel does not cover (dampening, Nesterov, weight decay, maximize, closures, parameters or
-    gradients off the flat buffers, parameters with and without a momentum buffer mixed) falls through to torch's own step."""
+def _step_counters(opt, params, cache, uniform=False, validate=True):
+    """torch's `step` counters (a 0-d fp32 CPU tensor per parameter, made where there is none), bumped in one call on the plain
+    path; under the guard they follow the device's count instead (GuardedOptimizer.state_dict()).  With `uniform`, counters that
+    differ between the parameters give None: looked at where they are readied, and nothing is cached then, so the next step looks
+    again (every change after that - a bump, torch's own step, the guard's count - is the same for all parameters)."""
+    steps = cache.get("step")
+    if steps is None or (validate and any(opt.state[p].get("step") is not t for p, t in zip(params, steps))):
+        steps = []
+        for p in params:
+            st = opt.state[p]
+            step = st.get("step")
+            st["step"] = (torch.zeros((), dtype=torch.float32) if step is None else
+                          torch.as_tensor(step, dtype=torch.float32).detach().cpu().reshape(()).clone())
+            steps.append(st["step"])
+        if uniform and any(float(t) != float(steps[0]) for t in steps):
+            cache.pop("step", None)
+            return None
+        cache["step"] = steps
+    return steps
 
-    def __init__(self, model, lr, momentum, max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=False):
-        super().__init__(model.parameters(), lr=lr, momentum=momentum)
-        self._model, self._cache = model, {}
+
+class FlatOptimizer(guard.GuardedOptimizer):
+    """Mixin in front of a torch optimizer class whose ``step()`` is ONE launch on the module's flat buffers when it can be.
+
+    The module's parameters are views of one flat buffer (music_amd/engine.py) and the gradients autograd hands to them are views
+    of one flat buffer too (``_WaveNetFunction.backward``), so the 123 per-tensor updates of the reference's optimizers
+    (wavenet/train.py:28-42) are one elementwise pass.  The optimizer state is torch's own, its tensors being VIEWS of flat buffers:
+    ``state_dict()`` / ``load_state_dict()`` interchange with torch's class, and any step the fast path does not cover (parameters
+    not on the flat buffer yet, gradients that are not one flat tensor, an option the kernel does not implement, closures, several
+    parameter groups) falls through to torch's own step on the same state.  A class gives `_covers(group)`, whether the kernel
+    implements the group's options, and `_flat_args(eng, params, group)`, which readies the flat state and returns (entry point,
+    state pointers, the plain and the guarded argument tail, the step counters the plain path bumps) or None for torch's path."""
+
+    def __init__(self, model, *, max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=False, **kw):
+        super().__init__(model.parameters(), **kw)
+        self._model, self._cache = model, {}     # _cache: the flat state buffers of _flat_views / _step_counters
         self._guard_setup(max_grad_norm, skip_nonfinite)
         self._ema_setup(model.named_parameters(), ema_decay, ema_warmup)
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        self._cache = {}                                  # re-adopt the loaded tensors at the next step
+        self._guard_reseed()
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        if self.ema is not None:
+            self.ema.check_step()
+        lay = _flat_layout(self, self._model, self._covers) if closure is None else None
+        args = None if lay is None else self._flat_args(lay[0], lay[1], self.param_groups[0])
+        if args is None:
+            return self._torch_step(closure, checked=True)
+        eng, _, gbase = lay
+        entry, state, plain, guarded, steps = args
+        gd = None if self._guard_opts is None else self._guard_get(eng.flat.device)
+        if gd is None and steps:
+            torch._foreach_add_(steps, 1.0)
+        guard.flat_step(eng, entry, gbase, state, plain, guarded, gd, self.ema)
+        return None
+
+
+class FlatAdam(FlatOptimizer, optim.Adam):
+    """``torch.optim.Adam(model.parameters(), lr)`` (wavenet/train.py:39-42) as ONE ``wn_adam_flat`` launch (see FlatOptimizer):
+    torch's own state - per parameter ``step`` / ``exp_avg`` / ``exp_avg_sq``; weight decay / amsgrad / maximize, and parameters at
+    different step counts, fall through to torch."""
+
+    @staticmethod
+    def _covers(g):
+        return not (g.get("weight_decay", 0) != 0 or g.get("amsgrad") or g.get("maximize") or g.get("capturable") or g.get("differentiable"))
+
+    def _flat_args(self, eng, params, grp):
+        # the caches as they are until load_state_dict() or another engine, not checked against the state entries per step: on the
+        # reference's own loop, where this optimizer sits, the three checks (0.04 ms of host time) showed (DESIGN.md section 6)
+        m, _ = _flat_views(self, eng, params, "exp_avg", self._cache, validate=False)
+        v, _ = _flat_views(self, eng, params, "exp_avg_sq", self._cache, validate=False)
+        steps = _step_counters(self, params, self._cache, uniform=True, validate=False)
+        if steps is None:
+            return None                                   # parameters at different step counts: torch's per-tensor path
+        t = float(steps[0])
+        b1, b2 = grp["betas"]
+        hyper = (float(grp["lr"]), b1, b2, grp["eps"])
+        return ("wn_adam_flat", (m.data_ptr(), v.data_ptr()), hyper + (1.0 - b1 ** (t + 1.0), 1.0 - b2 ** (t + 1.0), 1.0), hyper + (1.0,), steps)
+
+
+class FlatSGD(FlatOptimizer, optim.SGD):
+    """``torch.optim.SGD(model.parameters(), lr, momentum)`` (wavenet/train.py:28-31) as ONE ``wn_sgd_flat`` launch (see
+    FlatOptimizer): ``momentum_buffer`` per parameter; dampening, Nesterov, weight decay, maximize, and parameters with and without
+    a momentum buffer mixed, fall through to torch."""
+
+    @staticmethod
+    def _covers(g):
+        return (g.get("dampening", 0) == 0 and not g.get("nesterov") and g.get("weight_decay", 0) == 0 and not g.get("maximize")
+                and not g.get("differentiable"))
 
     def _guard_seed(self):
         # torch's SGD keeps no step counter: existing momentum buffers mean "not the first step" (one step the guard did not see)
         have = any(st.get("momentum_buffer") is not None for st in self.state.values())
         return (1, 1) if have else (0, 0)
 
-    def load_state_dict(self, state_dict):
-        super().load_state_dict(state_dict)
-        self._cache = {}
-        self._guard_reseed()
-
-    @torch.no_grad()
-    def step(self, closure=None):
-        if self.ema is not None:
-            self.ema.check_step()
-        lay = None
-        if closure is None:
-            lay = _flat_layout(self, self._model, lambda g: (g.get("dampening", 0) == 0 and not g.get("nesterov") and g.get("weight_decay", 0) == 0
-                                                           and not g.get("maximize") and not g.get("differentiable")))
-        if lay is not None:
-            eng, params, gbase = lay
-            grp = self.param_groups[0]
-            mom = float(grp["momentum"])
-            buf, first = None, 0
-            if mom != 0.0:
-                have = sum(1 for p in params if self.state[p].get("momentum_buffer") is not None)
-                if have not in (0, len(params)):
-                    return self._torch_step(closure)
-                flat, _ = _flat_views(self, eng, params, "momentum_buffer", self._cache)
-                buf, first = flat.data_ptr(), 1 if have == 0 else 0
-            from music_amd import _lib
-            if self._guard_opts is not None:              # "first step" is the device's: the first step TAKEN
-                gd = self._guard_get(eng.flat.device)
-                gd.run(gbase, eng.spec.total)
-                _lib.call("wn_sgd_flat_guarded", eng.flat.data_ptr(), gbase, buf, eng.spec.total, float(grp["lr"]), mom, 1.0, gd.state_ptr(),
-                          _lib.stream())
-                self._vq_ema_step(eng, gd)
-                if self.ema is not None:
-                    self.ema.update(eng, gd)
+    def _flat_args(self, eng, params, grp):
+        mom = float(grp["momentum"])
+        buf, first = None, 0
+        if mom != 0.0:
+            have = sum(1 for p in params if self.state[p].get("momentum_buffer") is not None)
+            if have not in (0, len(params)):
                 return None
-            _lib.call("wn_sgd_flat", eng.flat.data_ptr(), gbase, buf, eng.spec.total, float(grp["lr"]), mom, 1.0, first, _lib.stream())
-            self._vq_ema_step(eng)
-            if self.ema is not None:
-                self.ema.update(eng)
-            return None
-        return self._torch_step(closure)
+            buf = _flat_views(self, eng, params, "momentum_buffer", self._cache)[0].data_ptr()
+            first = 1 if have == 0 else 0
+        tail = (float(grp["lr"]), mom, 1.0)
+        return "wn_sgd_flat", (buf,), tail + (first,), tail, None     # guarded, "first step" is the device's: the first step TAKEN
 
 
-class FlatRMSprop(guard.GuardedOptimizer, optim.RMSprop):
-    """``torch.optim.RMSprop(model.parameters(), lr, momentum=momentum)`` (wavenet/train.py:32-37) whose ``step()`` is ONE
-    ``wn_rmsprop_flat`` launch when it can be (see FlatAdam): torch's own state (``step``, ``square_avg``, ``momentum_buffer``; the
-    tensors are views of flat buffers), same ``state_dict``; centered / weight decay / maximize / closures fall through to torch."""
+class FlatRMSprop(FlatOptimizer, optim.RMSprop):
+    """``torch.optim.RMSprop(model.parameters(), lr, momentum=momentum)`` (wavenet/train.py:32-37) as ONE ``wn_rmsprop_flat`` launch
+    (see FlatOptimizer): ``step``, ``square_avg``, ``momentum_buffer``; centered / weight decay / maximize fall through to torch."""
 
-    def __init__(self, model, lr, momentum, max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=False):
-        super().__init__(model.parameters(), lr=lr, momentum=momentum)
-        self._model, self._cache = model, {}
-        self._guard_setup(max_grad_norm, skip_nonfinite)
-        self._ema_setup(model.named_parameters(), ema_decay, ema_warmup)
+    @staticmethod
+    def _covers(g):
+        return (not g.get("centered") and g.get("weight_decay", 0) == 0 and not g.get("maximize") and not g.get("capturable")
+                and not g.get("differentiable"))
 
-    def load_state_dict(self, state_dict):
-        super().load_state_dict(state_dict)
-        self._cache = {}
-        self._guard_reseed()
-
-    @torch.no_grad()
-    def step(self, closure=None):
-        if self.ema is not None:
-            self.ema.check_step()
-        lay = None
-        if closure is None:
-            lay = _flat_layout(self, self._model, lambda g: (not g.get("centered") and g.get("weight_decay", 0) == 0 and not g.get("maximize")
-                                                           and not g.get("capturable") and not g.get("differentiable")))
-        if lay is not None:
-            eng, params, gbase = lay
-            grp = self.param_groups[0]
-            mom = float(grp["momentum"])
-            sq, _ = _flat_views(self, eng, params, "square_avg", self._cache)
-            buf = None
-            if mom > 0.0:
-                buf = _flat_views(self, eng, params, "momentum_buffer", self._cache)[0].data_ptr()
-            steps = self._cache.get("step")                   # torch's step counters (a 0-d tensor per parameter), bumped in one call
-            if steps is None or any(self.state[p].get("step") is not t for p, t in zip(params, steps)):
-                steps = []
-                for p in params:
-                    st = self.state[p]
-                    step = st.get("step")
-                    st["step"] = (torch.zeros((), dtype=torch.float32) if step is None else
-                                  torch.as_tensor(step, dtype=torch.float32).detach().cpu().reshape(()).clone())
-                    steps.append(st["step"])
-                self._cache["step"] = steps
-            from music_amd import _lib
-            if self._guard_opts is not None:              # the step counters follow the device's count (state_dict())
-                gd = self._guard_get(eng.flat.device)
-                gd.run(gbase, eng.spec.total)
-                _lib.call("wn_rmsprop_flat_guarded", eng.flat.data_ptr(), gbase, sq.data_ptr(), buf, eng.spec.total, float(grp["lr"]),
-                          float(grp["alpha"]), float(grp["eps"]), mom, 1.0, gd.state_ptr(), _lib.stream())
-                self._vq_ema_step(eng, gd)
-                if self.ema is not None:
-                    self.ema.update(eng, gd)
-                return None
-            torch._foreach_add_(steps, 1.0)
-            _lib.call("wn_rmsprop_flat", eng.flat.data_ptr(), gbase, sq.data_ptr(), buf, eng.spec.total, float(grp["lr"]), float(grp["alpha"]),
-                      float(grp["eps"]), mom, 1.0, _lib.stream())
-            self._vq_ema_step(eng)
-            if self.ema is not None:
-                self.ema.update(eng)
-            return None
-        return self._torch_step(closure)
+    def _flat_args(self, eng, params, grp):
+        mom = float(grp["momentum"])
+        sq, _ = _flat_views(self, eng, params, "square_avg", self._cache)
+        buf = _flat_views(self, eng, params, "momentum_buffer", self._cache)[0].data_ptr() if mom > 0.0 else None
+        tail = (float(grp["lr"]), float(grp["alpha"]), float(grp["eps"]), mom, 1.0)
+        return "wn_rmsprop_flat", (sq.data_ptr(), buf), tail, tail, _step_counters(self, params, self._cache)
 
 
 def get_optimizer(model, optimizer_type, learning_rate, momentum, max_grad_norm=None, skip_nonfinite=False, ema_decay=None,

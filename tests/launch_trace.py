@@ -12,7 +12,11 @@ and the autoencoder's pinned staging stubbed.  A trace is the ordered list of
 
 A pointer is written as [owner key, element offset]: the owner is the first tensor among the engine's attributes, `ws` and `bw`
 (lists, tuples and dicts included, keys sorted) whose memory holds the address; a tensor no owner holds any more (d_tab, d_enf,
-a replaced table) is "tmp<k>" in order of first appearance.  None stays None, ctypes arrays are written out as lists."""
+a replaced table) is "tmp<k>" in order of first appearance.  None stays None, ctypes arrays are written out as lists.  A raw
+address (the data_ptr() integers the flat optimizers and GradGuard pass) inside an owner's memory is written exactly as a pointer is,
+so code may pass either; any other integer of 2^40 or more fails the recording.
+
+A third set, the optimizer steps (OPTIMIZER_CASES, record_optimizer, tests/golden/launch_traces_optimizers.json), is at the end."""
 import ctypes
 import hashlib
 import json
@@ -131,21 +135,27 @@ def _tensors(obj, key, out):
             _tensors(v, "%s.%d" % (key, k), out)
 
 
+def _span(key, t):
+    return key, t.data_ptr(), t.data_ptr() + t.numel() * t.element_size(), t.element_size()
+
+
 def owners(eng, ws):
     out = []
     _tensors(vars(eng), "eng", out)
     _tensors({k: v for k, v in ws.items() if k != "bwd"}, "ws", out)
     _tensors(ws.get("bwd") or {}, "bw", out)
-    return [(key, t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()) for key, t in out if t.numel()]
+    return [_span(key, t) for key, t in out if t.numel()]
 
 
-def canonical(trace, eng, ws):
-    own, tmp = owners(eng, ws), {}
+def canonical(trace, eng, ws, own=None, tmp=None):
+    """`own`: the owners (default: the engine's and the workspace's); `tmp`: the names of tensors no owner holds, carried over where
+    a case is canonicalised in pieces.  A raw address (an int, what data_ptr() gives) inside an owner's memory is named as a Ptr is."""
+    own, tmp = owners(eng, ws) if own is None else own, {} if tmp is None else tmp
 
     def arg(a):
         if isinstance(a, Ptr):
             size = a.t.element_size()
-            for key, lo, hi in own:
+            for key, lo, hi, _ in own:
                 if lo <= a.addr < hi:
                     return [key, (a.addr - lo) // size]
             base = a.t.untyped_storage().data_ptr()
@@ -153,7 +163,11 @@ def canonical(trace, eng, ws):
         if isinstance(a, ctypes.Array):
             return list(a)
         assert a is None or isinstance(a, (int, float, str)), a
-        assert not isinstance(a, int) or abs(a) < 1 << 40, "a raw address among the arguments: %r" % (a,)
+        if isinstance(a, int):
+            for key, lo, hi, size in own:
+                if lo <= a < hi:
+                    return [key, (a - lo) // size]
+            assert abs(a) < 1 << 40, "a raw address among the arguments: %r" % (a,)
         return a
 
     out = []
@@ -344,3 +358,197 @@ def record(name, monkeypatch):
 
 def digest(trace):
     return hashlib.sha256(json.dumps(trace, sort_keys=True).encode()).hexdigest()
+
+
+# ---------------------------------------------------------------- the optimizer steps (tests/golden/launch_traces_optimizers.json)
+# What ends a training step: the flat optimizers of music_amd/train.py and the fused step's adam_step, plain and guarded, with and
+# without an EMA shadow, on a model whose codebook follows EMA updates or not.  The engines are built on the CPU as in
+# test_vq_ema_model_cpu (net._engine = Engine(net, cpu); parameters and gradients are views of eng.flat / eng.flat_grad), the guard is
+# the real GradGuard on device="cpu".  No launch runs, so the recorder plays the device's one part the host later reads back: every
+# wn_grad_guard issued counts as a step TAKEN (the gradients here are finite) in the guard's state block.
+GUARD = dict(max_grad_norm=1.0, skip_nonfinite=True)
+SHADOW = dict(ema_decay=0.99, ema_warmup=True)
+OPT_DIL, OPT_K = [1, 2], 24
+STANDARD = ("flat", "flat", "foreign", "flat", "reload", "flat")
+
+
+def _opt_net(ae=False):
+    """-> (module, its engine on the CPU), the parameters being views of eng.flat"""
+    if ae:
+        from music_amd.model1 import _AutoencoderEngine
+        net = _ae_net(64, 64, conditioning="learned", bottleneck="vq", vq_codes=OPT_K, vq_update="ema")
+        eng = net._engine = _AutoencoderEngine(net, torch.device("cpu"))
+    else:
+        from music_amd.engine import WaveNetEngine
+        from music_amd.model import wavenet
+        torch.manual_seed(0)
+        net = wavenet(2, OPT_DIL, 32, 32, 32, 256, False)
+        eng = net._engine = WaveNetEngine(OPT_DIL, 32, 32, 32, device="cpu")
+    assert [n for n, _ in net.named_parameters()] == eng.param_names
+    for n, p in net.named_parameters():
+        o = eng.spec.off[n]
+        eng.flat[o:o + p.numel()].copy_(p.detach().reshape(-1))
+        p.data = eng.flat[o:o + p.numel()].view(p.shape)
+    eng.flat_grad.fill_(0.01)
+    return net, eng
+
+
+def _flat_grads(net, eng):
+    for n, p in net.named_parameters():
+        o = eng.spec.off[n]
+        p.grad = eng.flat_grad[o:o + p.numel()].view(p.shape)
+
+
+def _optimizer(kind, momentum=0.9, ae=False, **kw):
+    def build():
+        from music_amd import train
+        net, eng = _opt_net(ae)
+        return net, eng, train.get_optimizer(net, kind, 1e-3, momentum, **kw)
+    return build
+
+
+def _fused(ae=False, **kw):
+    def build():
+        net, eng = _opt_net(ae)
+        eng.adam_init(lr=1e-3, **kw)
+        return net, eng, None
+    return build
+
+
+def _mixed_steps(net, eng, opt):
+    """a state dict in which the first parameter's `step` differs, loaded"""
+    sd = opt.state_dict()
+    sd["state"][0]["step"] = sd["state"][0]["step"] + 3
+    opt.load_state_dict(sd)
+
+
+def _some_buffers(net, eng, opt):
+    """only the first parameter holds a momentum_buffer"""
+    p = opt.param_groups[0]["params"][0]
+    opt.state[p]["momentum_buffer"] = torch.zeros_like(p)
+
+
+def _second_group(net, eng, opt):
+    opt.add_param_group({"params": [torch.nn.Parameter(torch.zeros(3))]})
+
+
+def _weight_decay(net, eng, opt):
+    opt.param_groups[0]["weight_decay"] = 1e-2
+
+
+# name -> (builder of (module, engine, optimizer or None), the scripted sequence).  "flat": a step with the gradients on the flat
+# buffer; "foreign": with p.grad = p.grad.clone() (torch's path); "closure": step(closure); "reload": load_state_dict(state_dict());
+# "fused": eng.adam_step(); a function: called with (module, engine, optimizer) between two steps
+OPTIMIZER_CASES = {}
+for _kind in ("adam", "sgd", "rmsprop"):
+    for _g, _gkw in (("plain", {}), ("guarded", GUARD)):
+        for _s, _skw in (("", {}), ("_shadow", SHADOW)):
+            OPTIMIZER_CASES["%s_%s%s" % (_kind, _g, _s)] = (_optimizer(_kind, **_gkw, **_skw), STANDARD)
+        OPTIMIZER_CASES["%s_vq_ema_%s_shadow" % (_kind, _g)] = (_optimizer(_kind, ae=True, **_gkw, **SHADOW), ("flat", "flat"))
+for _g, _gkw in (("plain", {}), ("guarded", GUARD)):
+    for _s, _skw in (("", {}), ("_shadow", SHADOW)):
+        OPTIMIZER_CASES["fused_%s%s" % (_g, _s)] = (_fused(**_gkw, **_skw), ("fused", "fused"))
+    OPTIMIZER_CASES["fused_vq_ema_%s_shadow" % _g] = (_fused(ae=True, **_gkw, **SHADOW), ("fused", "fused"))
+OPTIMIZER_CASES.update({
+    "sgd_momentum0": (_optimizer("sgd", 0.0), ("flat", "flat")),
+    "sgd_momentum0_guarded": (_optimizer("sgd", 0.0, **GUARD), ("flat", "flat")),
+    "rmsprop_momentum0": (_optimizer("rmsprop", 0.0), ("flat", "flat")),
+    "rmsprop_momentum0_guarded": (_optimizer("rmsprop", 0.0, **GUARD), ("flat", "flat")),
+    "adam_closure": (_optimizer("adam", **SHADOW), ("flat", "closure", "flat")),
+    "adam_mixed_steps": (_optimizer("adam"), ("flat", _mixed_steps, "flat", "flat")),
+    "adam_mixed_steps_guarded": (_optimizer("adam", **GUARD), ("flat", _mixed_steps, "flat", "flat")),
+    "sgd_some_momentum_buffers": (_optimizer("sgd"), (_some_buffers, "flat", "flat")),
+    "adam_second_group": (_optimizer("adam"), ("flat", _second_group, "flat")),
+    "sgd_second_group": (_optimizer("sgd"), ("flat", _second_group, "flat")),
+    "adam_weight_decay": (_optimizer("adam"), ("flat", _weight_decay, "flat")),
+    "sgd_weight_decay": (_optimizer("sgd"), ("flat", _weight_decay, "flat")),
+    "rmsprop_weight_decay": (_optimizer("rmsprop"), ("flat", _weight_decay, "flat")),
+})
+del _kind, _g, _gkw, _s, _skw
+
+
+def _optimizer_owners(eng, opt, keep):
+    """The engine's tensors, then the optimizer's state tensors by storage (`opt.<state key>`, numbered where the parameters'
+    tensors do not share one), the guard's state and partials and the shadow's flat buffer.  `keep` holds every tensor ever named,
+    so that no address is handed out twice within a case."""
+    out = []
+    _tensors(vars(eng), "eng", out)
+    out = [_span(key, t) for key, t in out if t.numel()]
+    gd, shadow = (opt._guard, opt.ema) if opt is not None else (eng.adam_state.get("guard"), eng.ema)
+    if opt is not None:
+        seen = {}
+        for p in (p for grp in opt.param_groups for p in grp["params"]):
+            for key, t in sorted(opt.state[p].items()):
+                if torch.is_tensor(t) and t.numel() and t.dim():
+                    st = t.untyped_storage()
+                    if (key, st.data_ptr()) not in seen:
+                        n = sum(k == key for k, _ in seen)
+                        seen[key, st.data_ptr()] = ("opt.%s" % key if n == 0 else "opt.%s.%d" % (key, n), st.data_ptr(), st.data_ptr() + st.nbytes(),
+                                                    t.element_size())
+                    keep.append(t)
+        out += list(seen.values())
+    if gd is not None:
+        out += [_span("guard.state", gd.state), _span("guard.partials", gd.partials)]
+    if shadow is not None and shadow.flat is not None:
+        out.append(_span("shadow.flat", shadow.flat))
+    keep.extend(t for t in (getattr(gd, "state", None), getattr(gd, "partials", None), getattr(shadow, "flat", None)) if t is not None)
+    return out
+
+
+def _optimizer_forms(eng, opt, prev):
+    """after a step: every parameter's `step`, the sorted state keys, per state tensor whether it is a view of ONE flat buffer
+    at the parameter's offset ("1"), a tensor of its own ("0") or None ("-"), one character per parameter, and `fresh`: the keys
+    whose (first) tensor lies in other memory than after the step before (`prev`) - the state was adopted anew"""
+    if opt is None:
+        return {"t": eng.adam_state["t"]}
+    params = [p for grp in opt.param_groups for p in grp["params"]]
+    keys = sorted({k for p in params for k in opt.state[p]})
+    forms = {"keys": keys, "step": [float(opt.state[p]["step"]) if opt.state[p].get("step") is not None else None for p in params],
+             "fresh": []}
+    for key in keys:
+        if key == "step":
+            continue
+        ts = [opt.state[p].get(key) for p in params]
+        base = next((t.untyped_storage().data_ptr() for t in ts if t is not None), None)
+        if prev.get(key) != base:
+            forms["fresh"].append(key)
+        prev[key] = base
+        forms[key] = "".join("-" if t is None else
+                             "1" if n in eng.spec.off and t.untyped_storage().data_ptr() == base and t.storage_offset() == eng.spec.off[n]
+                             and t.untyped_storage().nbytes() == 4 * eng.spec.total else "0"
+                             for n, t in zip(eng.param_names + [None] * len(ts), ts))
+    return forms
+
+
+def record_optimizer(name, monkeypatch):
+    """-> (canonical trace, {}, forms: one entry per item of the sequence) of one case of OPTIMIZER_CASES; a step that launched
+    nothing leaves no trace item, ["step", k] items separate the sequence's."""
+    from music_amd.guard import _TAKEN
+    build, script = OPTIMIZER_CASES[name]
+    for k in SWITCHES:
+        monkeypatch.delenv(k, raising=False)
+    trace = install(monkeypatch)
+    net, eng, opt = build()
+    del trace[:]
+    out, forms, keep, tmp, prev = [], [], [], {}, {}
+    for k, what in enumerate(script):
+        if what == "fused":
+            eng.adam_step()
+        elif what == "reload":
+            opt.load_state_dict(opt.state_dict())
+        elif callable(what):
+            what(net, eng, opt)
+        else:
+            _flat_grads(net, eng)
+            if what == "foreign":
+                for p in net.parameters():
+                    p.grad = p.grad.clone()
+            opt.step(*([lambda: None] if what == "closure" else []))
+        gd = opt._guard if opt is not None else eng.adam_state.get("guard")
+        if gd is not None:                  # the device's part: every guard launch saw a finite gradient, the step was taken
+            gd.state[_TAKEN] += sum(item[0] == "wn_grad_guard" for item in trace)
+        out.append(["step", k])
+        out += canonical(trace, eng, None, _optimizer_owners(eng, opt, keep), tmp)
+        forms.append(_optimizer_forms(eng, opt, prev))
+        del trace[:]
+    return out, {}, {"steps": forms}

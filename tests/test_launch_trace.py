@@ -7,6 +7,11 @@ A second file, tests/golden/launch_traces_epilogue.json (tools/record_launch_tra
 pins the forms of the skip epilogue the first one does not reach - the three-launch forward, one chain, the fused backward and its
 switches, learned conditioning - and the pack maps of the two general engines.
 
+A third file, tests/golden/launch_traces_optimizers.json (--set optimizers), pins what ENDS a step: the launches of the three flat
+optimizers of music_amd/train.py and of the fused step's adam_step - plain and guarded, with and without an EMA shadow and an
+EMA-updated codebook - over short scripted sequences, with the steps that launch nothing (torch's path) and the optimizer's state
+after every step.
+
 The recording itself (what is stubbed, how pointers are named) is tests/launch_trace.py.  No device is touched."""
 import json
 import os
@@ -112,3 +117,88 @@ def test_epilogue_launch_trace_is_the_recorded_one(name, golden_epilogue, monkey
 @pytest.mark.parametrize("name", list(lt.PACK_CASES))
 def test_general_engine_pack_maps_are_the_recorded_ones(name, golden_epilogue, monkeypatch):
     assert lt.record_packs(name, monkeypatch) == golden_epilogue["packs_only"][name]
+
+
+# ---------------------------------------------------------------- the optimizer steps
+GOLDEN_OPTIMIZERS = os.path.join(os.path.dirname(GOLDEN), "launch_traces_optimizers.json")
+
+
+@pytest.fixture(scope="module")
+def golden_optimizers():
+    with open(GOLDEN_OPTIMIZERS) as f:
+        return json.load(f)
+
+
+def test_the_recorded_optimizer_cases_are_the_cases(golden_optimizers):
+    g = golden_optimizers
+    assert len(g["recorded_at"]) == 40 and sorted(g["cases"]) == sorted(lt.OPTIMIZER_CASES)
+    assert os.path.getsize(GOLDEN_OPTIMIZERS) < 1 << 20
+
+
+def test_the_recorded_optimizer_cases_hold_the_forms_they_are_there_for(golden_optimizers):
+    """What the third file pins (tests/golden/launch_traces_optimizers.json, tools/record_launch_trace.py --write --set optimizers at
+    the commit it names): the launches that END a step - the update, plain or behind wn_grad_guard, then the codebook's EMA update,
+    then the shadow's - of the three flat optimizers and of the fused step, and which steps launch nothing (torch's path).  The guard
+    is the real GradGuard on the CPU; the one piece played for the device is its count of steps taken, which the recorder bumps
+    per wn_grad_guard issued (tests/launch_trace.py, record_optimizer)."""
+    cases = golden_optimizers["cases"]
+
+    def steps(name):                                          # the entry points of every item of the case's sequence
+        out = []
+        for item in cases[name]["trace"]:
+            if item[0] == "step":
+                out.append([])
+            else:
+                out[-1].append(item[1])
+        return out
+    forms = lambda name: cases[name]["forms"]["steps"]
+    args = lambda name, entry: [i[3] for i in cases[name]["trace"] if i[0] == "call" and i[1] == entry]
+    for kind, keys in (("adam", ["exp_avg", "exp_avg_sq"]), ("sgd", ["momentum_buffer"]), ("rmsprop", ["momentum_buffer", "square_avg"])):
+        entry = "wn_%s_flat" % kind
+        for g, head in (("plain", [entry]), ("guarded", ["wn_grad_guard", entry + "_guarded"])):
+            for s, tail in (("", []), ("_shadow", ["wn_ema_flat"])):
+                # flat, flat, foreign gradients (torch's path: no launch), flat, load_state_dict(state_dict()), flat
+                assert steps("%s_%s%s" % (kind, g, s)) == [head + tail, head + tail, [], head + tail, [], head + tail], (kind, g, s)
+                f = forms("%s_%s%s" % (kind, g, s))
+                assert all(all(st[k] == "1" * 11 for k in keys) for st in f)                 # views of the flat buffers throughout
+                assert [st["fresh"] for st in f] == [keys, [], [], [], [], keys]              # ... adopted anew after a load, only then
+            assert steps("%s_vq_ema_%s_shadow" % (kind, g)) == [head + ["wn_vq_ema_update", "wn_ema_flat"]] * 2
+        assert all(a[11] is None for a in args(kind + "_vq_ema_plain_shadow", "wn_vq_ema_update"))
+        assert all(a[11] == ["guard.state", 0] for a in args(kind + "_vq_ema_guarded_shadow", "wn_vq_ema_update"))
+        assert steps(kind + "_weight_decay")[1:] == [[], []]
+    # the step counters: bumped by the host on the plain path, the device's count (read back by state_dict()) on the guarded one
+    assert [st["step"][0] for st in forms("adam_plain")] == [1.0, 2.0, 3.0, 4.0, 4.0, 5.0]
+    assert [st["step"][0] for st in forms("adam_guarded")] == [0.0, 0.0, 3.0, 3.0, 4.0, 4.0]
+    assert [st["step"][0] for st in forms("rmsprop_guarded")] == [0.0, 0.0, 3.0, 3.0, 4.0, 4.0]
+    # SGD's first step, and the momentum buffer only with momentum
+    assert [a[7] for a in args("sgd_plain", "wn_sgd_flat")] == [1, 0, 0, 0] and [a[7] for a in args("sgd_momentum0", "wn_sgd_flat")] == [0, 0]
+    assert all(a[2] == ["opt.momentum_buffer", 0] for a in args("sgd_plain", "wn_sgd_flat"))
+    for name, entry, at in (("sgd_momentum0", "wn_sgd_flat", 2), ("sgd_momentum0_guarded", "wn_sgd_flat_guarded", 2),
+                            ("rmsprop_momentum0", "wn_rmsprop_flat", 3), ("rmsprop_momentum0_guarded", "wn_rmsprop_flat_guarded", 3)):
+        assert len(args(name, entry)) == 2 and all(a[at] is None for a in args(name, entry))
+        assert "momentum_buffer" not in forms(name)[-1]["keys"]
+    # torch's path: a closure, parameters at different step counts, some momentum buffers, a second group, weight decay
+    assert steps("adam_closure") == [["wn_adam_flat", "wn_ema_flat"], [], ["wn_adam_flat", "wn_ema_flat"]]
+    assert [a[5] for a in args("adam_closure", "wn_ema_flat")] == [1, 3]           # the update on the host counted
+    assert steps("adam_mixed_steps") == [["wn_adam_flat"], [], [], []] and forms("adam_mixed_steps")[-1]["step"][:2] == [6.0, 3.0]
+    assert steps("sgd_some_momentum_buffers") == [[], [], ["wn_sgd_flat"]]
+    assert [st["momentum_buffer"] for st in forms("sgd_some_momentum_buffers")] == ["0" + "-" * 10, "0" * 11, "1" * 11]
+    assert steps("adam_second_group")[1:] == [[], []] and steps("sgd_second_group")[1:] == [[], []]
+    # the fused step
+    for g, head in (("plain", ["wn_adam_flat"]), ("guarded", ["wn_grad_guard", "wn_adam_flat_guarded"])):
+        assert steps("fused_" + g) == [head] * 2 and steps("fused_%s_shadow" % g) == [head + ["wn_ema_flat"]] * 2
+        assert steps("fused_vq_ema_%s_shadow" % g) == [head + ["wn_vq_ema_update", "wn_ema_flat"]] * 2
+        assert [st["t"] for st in forms("fused_" + g)] == [1, 2]
+
+
+@pytest.mark.parametrize("name", list(lt.OPTIMIZER_CASES))
+def test_optimizer_launch_trace_is_the_recorded_one(name, golden_optimizers, monkeypatch):
+    want = golden_optimizers["cases"][name]
+    trace, packs, forms = lt.record_optimizer(name, monkeypatch)
+    if name in ("adam_mixed_steps", "adam_mixed_steps_guarded"):
+        # `fresh` of these two cases alone: at the recorded commit FlatAdam left its cache unfinished when the parameters' step
+        # counts differ and adopted the moments into new buffers at EVERY such step; its moments now go through _flat_views like
+        # the other two optimizers', which adopts them once.  Same values, same views, no launch either way.
+        want = dict(want, forms={"steps": [dict(st, fresh=None) for st in want["forms"]["steps"]]})
+        forms = {"steps": [dict(st, fresh=None) for st in forms["steps"]]}
+    _same(want, trace, packs, forms)
