@@ -429,6 +429,29 @@ int wn_step_softmax(const float* x, int64_t x_bstride, int x_pitch, float* probs
 int wn_step_nll(const float* x, int64_t x_bstride, int x_pitch, const int64_t* target, float* dx, int64_t dx_bstride, int dx_pitch,
                 float* probs, float* row_nll, int32_t* row_hit, float* loss_part, int w, int q, int batch, float inv_n,
                 wn_stream_t stream);
+/* The WINDOWED objective (ABI 9 still: new entries only): the two entries above under the samplers' position windows ("POSITION-WINDOWED
+ * sampling" below states the table and the rule once; this is that rule applied to the softmax, the NLL and its gradient), so that a
+ * prior over an interleaved code stream is trained and scored on the distribution wn_win_decode_batch draws from.  Layout, the
+ * NULL-able outputs, loss_part, empty calls and refusals are wn_step_nll's / wn_step_softmax's.  win_host: a HOST array of
+ * 2 * win_period int32 lo0, hi0, lo1, hi1, .., read during the call (at most 16 pairs, 0 <= lo < hi <= q; it travels in the kernel
+ * arguments).  win_pos: a DEVICE array of `batch` int64 (one stream position per clip: a loader's clips start anywhere in a piece), or
+ * NULL for zeros.  Column c of clip b sits at stream position p = win_pos0 + win_pos[b] + c and uses pair j = p mod win_period:
+ *   - m, S, p_k and nll = log S + m - x_y are taken over k in [lo_j, hi_j) only; row_hit compares the FIRST index of the maximum
+ *     inside the window with y.
+ *   - Outside the window probs is an exact 0 and dx an exact +0.0; both are written (the backward consumes the whole dx).  What x
+ *     holds outside influences nothing - not a NaN, not +inf, not a value far above every logit inside.
+ *   - A target inside [0, q) but outside its column's window poisons that column as a target outside [0, q) does (loss, the column's
+ *     dx and row_nll NaN, row_hit 0, other columns untouched): a misaligned position is loud, not silently wrong.  A negative
+ *     win_pos[b] cannot be refused before the launch: it poisons every column of clip b the same way and is never used as an index.
+ *   - win_period == 0 (win_host and win_pos may be NULL): wn_step_nll / wn_step_softmax bit for bit - the same kernel is launched.
+ *     A table whose every pair is (0, q) gives those bits too, on every output.
+ * -4 before any launch, the entry and the argument named in wn_last_error: win_period < 0 or > 16; win_period > 0 with NULL win_host;
+ * a pair with lo < 0, hi > q or lo >= hi; win_pos0 < 0; and everything the entries above refuse. */
+int wn_win_step_softmax(const float* x, int64_t x_bstride, int x_pitch, float* probs, int w, int q, int batch, const int32_t* win_host,
+                        int win_period, const int64_t* win_pos, int64_t win_pos0, wn_stream_t stream);
+int wn_win_step_nll(const float* x, int64_t x_bstride, int x_pitch, const int64_t* target, float* dx, int64_t dx_bstride, int dx_pitch,
+                    float* probs, float* row_nll, int32_t* row_hit, float* loss_part, int w, int q, int batch, float inv_n,
+                    const int32_t* win_host, int win_period, const int64_t* win_pos, int64_t win_pos0, wn_stream_t stream);
 /* ---- LEARNED conditioning projections of the autoencoder: the N + 1 1x1 convs of the pooled encoding enc [batch][bw][le]
  * (wavenet_autoencoder/model1.py:178-179, 216-217 draws them afresh per forward; here they are parameters), read from and
  * differentiated into the flat buffers.  Offsets count floats from `flat` (and from `flat_grad`): stage i < n_stages has its weight

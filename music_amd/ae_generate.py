@@ -438,6 +438,23 @@ def sample_code_stream(prior, stages, K, frames, start_tokens, start_pos=0, temp
     return split_code_stream(tokens, stages, K)
 
 
+def prior_score(prior, tokens, stages, K, start_pos=0):
+    """Held-out figures of a prior on token streams ``tokens`` (U, n > receptive_field) whose first token sits at stream position
+    ``start_pos``, under the windows ``sample_code_stream`` draws with: ``objective.score`` of every token behind the first
+    receptive_field ones - per-stream "nll", "bits" (per token, of the distribution that is sampled) and "accuracy"."""
+    try:
+        from . import fast_generate as fg, objective
+    except ImportError:
+        from music_amd import fast_generate as fg, objective
+    rf = prior.receptive_field
+    t = torch.as_tensor(tokens)
+    if t.is_floating_point() or t.dim() != 2 or t.size(1) <= rf:
+        raise ValueError("prior_score: tokens must be (U, n > %d) integer tokens" % rf)
+    t = t.to(next(prior.parameters()).device)
+    return objective.score(prior, t[:, :-1].to(torch.int32), t[:, rf:].to(torch.int64), windows=fg.stage_windows(int(stages), int(K)),
+                           window_pos=int(start_pos) + rf)
+
+
 def _checked_codes(t, B, n, Q, dev, what):
     t = torch.as_tensor(t)
     if t.dim() != 2 or tuple(t.shape) != (B, n):

@@ -300,7 +300,7 @@ class GenericAutoencoderEngine(GeneralPlan):
         ps.reduce_grads()
 
     # ------------------------------------------------------------------ fused training step (wavenet_autoencoder/train.py:146-160)
-    def loss_and_grad(self, x, target, cond=None, objective=None, classes=None, stages=None):
-        """objective: None = self.objective (EngineBase); stages: as in forward"""
+    def loss_and_grad(self, x, target, cond=None, objective=None, classes=None, stages=None, windows=None, window_pos=None):
+        """objective: None = self.objective (EngineBase); stages: as in forward; windows / window_pos: step_nll's (the shared base)"""
         return self._throttled(lambda: self._fused_tail(self.forward(x, cond, want_probs=False, classes=classes, stages=stages)[2], target,
-                                                       objective=objective))
+                                                       objective=objective, windows=windows, window_pos=window_pos))

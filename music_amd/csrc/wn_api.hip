@@ -441,17 +441,63 @@ int wn_step_softmax(const float* x, int64_t x_bstride, int x_pitch, float* probs
     if (batch == 0 || w == 0) return 0;
     WN_REQUIRE("wn_step_softmax", probs);
     return wn_launch_step_nll(x, (long)x_bstride, x_pitch, nullptr, nullptr, 0, 0, probs, nullptr, nullptr, nullptr, w, q, batch, 0.f,
-                              (hipStream_t)stream);
+                              nullptr, (hipStream_t)stream);
+}
+// wn_step_nll's refusals and launch under the entry's name `fn`; win NULL: no windows
+static int step_nll_checked(const char* fn, const float* x, int64_t x_bstride, int x_pitch, const int64_t* target, float* dx,
+                            int64_t dx_bstride, int dx_pitch, float* probs, float* row_nll, int32_t* row_hit, float* loss_part, int w,
+                            int q, int batch, float inv_n, const WnNllWin* win, wn_stream_t stream) {
+    char msg[160];
+    if (dx && dx_pitch < w) {
+        snprintf(msg, sizeof(msg), "%s: argument 'dx_pitch' must be >= w", fn);
+        return wn_set_error_msg(-4, msg);
+    }
+    if (dx && dx_bstride < (int64_t)q * dx_pitch) {
+        snprintf(msg, sizeof(msg), "%s: argument 'dx_bstride' must be >= q * dx_pitch", fn);
+        return wn_set_error_msg(-4, msg);
+    }
+    if (batch > 0 && w > 0) WN_REQUIRE(fn, target, loss_part);
+    return wn_launch_step_nll(x, (long)x_bstride, x_pitch, target, dx, (long)dx_bstride, dx_pitch, probs, row_nll, row_hit, loss_part, w, q,
+                              batch, inv_n, win, (hipStream_t)stream);
 }
 int wn_step_nll(const float* x, int64_t x_bstride, int x_pitch, const int64_t* target, float* dx, int64_t dx_bstride, int dx_pitch,
                 float* probs, float* row_nll, int32_t* row_hit, float* loss_part, int w, int q, int batch, float inv_n,
                 wn_stream_t stream) {
     if (int rc = step_checked("wn_step_nll", x, x_bstride, x_pitch, w, q, batch)) return rc;
-    if (dx && dx_pitch < w) return wn_set_error_msg(-4, "wn_step_nll: argument 'dx_pitch' must be >= w");
-    if (dx && dx_bstride < (int64_t)q * dx_pitch) return wn_set_error_msg(-4, "wn_step_nll: argument 'dx_bstride' must be >= q * dx_pitch");
-    if (batch > 0 && w > 0) WN_REQUIRE("wn_step_nll", target, loss_part);
-    return wn_launch_step_nll(x, (long)x_bstride, x_pitch, target, dx, (long)dx_bstride, dx_pitch, probs, row_nll, row_hit, loss_part, w, q,
-                              batch, inv_n, (hipStream_t)stream);
+    return step_nll_checked("wn_step_nll", x, x_bstride, x_pitch, target, dx, dx_bstride, dx_pitch, probs, row_nll, row_hit, loss_part, w,
+                            q, batch, inv_n, nullptr, stream);
+}
+// the objective's window table (the samplers' checks, win_checked) in its kernel-argument form; q is in range here
+static int nll_win_checked(const char* fn, const int32_t* win_host, int win_period, const int64_t* win_pos, int64_t win_pos0, int q,
+                           WnNllWin& win) {
+    memset(&win, 0, sizeof(win));
+    int pos0 = 0;
+    if (int rc = win_checked(fn, win_host, win_period, win_pos0, q, win.period, pos0, win.lo, win.hi)) return rc;
+    win.pos0 = (unsigned)pos0;
+    win.pow32 = win_period > 0 ? (unsigned)((1ull << 32) % (unsigned)win_period) : 0;
+    win.pos = win_pos;
+    return 0;
+}
+int wn_win_step_softmax(const float* x, int64_t x_bstride, int x_pitch, float* probs, int w, int q, int batch, const int32_t* win_host,
+                        int win_period, const int64_t* win_pos, int64_t win_pos0, wn_stream_t stream) {
+    const char* fn = "wn_win_step_softmax";
+    if (int rc = step_checked(fn, x, x_bstride, x_pitch, w, q, batch)) return rc;
+    WnNllWin win;
+    if (int rc = nll_win_checked(fn, win_host, win_period, win_pos, win_pos0, q, win)) return rc;
+    if (batch == 0 || w == 0) return 0;
+    WN_REQUIRE(fn, probs);
+    return wn_launch_step_nll(x, (long)x_bstride, x_pitch, nullptr, nullptr, 0, 0, probs, nullptr, nullptr, nullptr, w, q, batch, 0.f,
+                              &win, (hipStream_t)stream);
+}
+int wn_win_step_nll(const float* x, int64_t x_bstride, int x_pitch, const int64_t* target, float* dx, int64_t dx_bstride, int dx_pitch,
+                    float* probs, float* row_nll, int32_t* row_hit, float* loss_part, int w, int q, int batch, float inv_n,
+                    const int32_t* win_host, int win_period, const int64_t* win_pos, int64_t win_pos0, wn_stream_t stream) {
+    const char* fn = "wn_win_step_nll";
+    if (int rc = step_checked(fn, x, x_bstride, x_pitch, w, q, batch)) return rc;
+    WnNllWin win;
+    if (int rc = nll_win_checked(fn, win_host, win_period, win_pos, win_pos0, q, win)) return rc;
+    return step_nll_checked(fn, x, x_bstride, x_pitch, target, dx, dx_bstride, dx_pitch, probs, row_nll, row_hit, loss_part, w, q, batch,
+                            inv_n, &win, stream);
 }
 // ---- learned conditioning projections (wn_condproj.hip) ----
 // the refusals both entries share: shapes, offsets and strides first (they need no pointer)

@@ -295,9 +295,14 @@ int wn_launch_vq_lookup(const int32_t* idx, const int32_t* nstage, const float* 
 // S stages (1: wn_vq_ema_update): S blocks of stat, state, work and info[2], S x K codebook rows
 int wn_launch_vq_ema_update(float* flat, long cb_off, const float* stat, float* state, void* work, int32_t* info, int S, int K, int bw,
                             float decay, float eps, float restart, const wn_guard_state* guard, hipStream_t st);
-// per-timestep softmax + negative log-likelihood over the channel axis of [B][Q][pitch] logits (wn_nll.hip); target NULL: softmax only
+#define WN_WIN_MAX 16                                      // pairs of a window table (the samplers' and the objective's)
+// per-timestep softmax + negative log-likelihood over the channel axis of [B][Q][pitch] logits (wn_nll.hip); target NULL: softmax only.
+// win (NULL: none): the window table of the objective, period pairs; column c of clip b is at stream position pos0 + pos[b] + c with
+// pos0 already reduced mod period by the host, pos a DEVICE array [batch] or NULL, pow32 = 2^32 mod period
+struct WnNllWin { int period; unsigned pos0, pow32; const int64_t* pos; int lo[WN_WIN_MAX], hi[WN_WIN_MAX]; };
 int wn_launch_step_nll(const float* x, long x_bs, int x_pitch, const int64_t* target, float* dx, long dx_bs, int dx_pitch, float* probs,
-                       float* row_nll, int32_t* row_hit, float* loss_part, int w, int q, int batch, float inv_n, hipStream_t st);
+                       float* row_nll, int32_t* row_hit, float* loss_part, int w, int q, int batch, float inv_n, const WnNllWin* win,
+                       hipStream_t st);
 // general path (wn_generic.hip): gate and chunk softmax for any shape
 int wn_launch_gate_fwd(const float* fg, long fg_bstride, int dp, int rows, float* z, long z_bstride, int pitch, int t_lo, int t_hi,
                        int batch, hipStream_t st);
@@ -309,7 +314,6 @@ int wn_launch_softmaxq_ce(const float* x, const int64_t* target, float* probs, f
                           float inv_n, hipStream_t st);
 
 #define WN_DEC_MAX_LAYERS 64
-#define WN_WIN_MAX 16                                      // pairs of a sampling-window table
 // one utterance's (or one row's) sampling settings: the layout of wn_sampling (include/wavenet_hip.h), 24 bytes
 struct WnSampling { float temperature; float top_p; int32_t top_k; uint32_t stream; uint64_t seed; };
 static_assert(sizeof(WnSampling) == 24, "wn_sampling is 24 bytes");

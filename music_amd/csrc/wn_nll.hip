@@ -8,29 +8,49 @@
 // registers, the column max / argmax / target logit and the column sum cross the waves through LDS.  x is read once, dx written once.
 // Any W: a clip's base is only 4-byte aligned, so every access is a scalar dword per lane and the last tile of a clip is masked.
 // No float atomics: block i sums its tiles in a fixed order into loss_part[i]; the same bits come back on every launch.
+//
+// WIN (wn_win_step_nll, wn_win_step_softmax): the samplers' window rule as an objective.  A column at stream position p takes the
+// softmax over the rows [lo, hi) of pair p mod period alone: the lane picks its pair once per tile, rows outside it enter the
+// reductions as -inf (their exp is an exact 0, so probs and dx outside are +0.0 without a second predicate) and what x holds there
+// stays behind the window's predicate: it never reaches arithmetic.  WIN = false is the code from before the windows.
+#include <type_traits>
+
 #include "wn_common.h"
 #include "wn_kernels.h"
+
+struct WnNoWin {};
 
 // probabilities go out row-major per time step ([column][q]): a wave turns TR of its rows at a time through a [64][TR + 1] LDS tile
 // of its own and writes segments of TR consecutive floats
 // Q256: q is 256 and the block has 4 waves of 64 rows (120 registers, no scratch: four blocks per CU, so a grid of up to 1024 blocks
 // is resident at once); else q is a run-time value, the block has ceil(q / 64) <= MAXT / 64 waves and rows >= q are masked.
-template <int RPW, int TR, bool Q256, int MAXT>
+template <int RPW, int TR, bool Q256, int MAXT, bool WIN>
 __global__ __launch_bounds__(MAXT) void step_nll_k(
         const float* __restrict__ x, long x_bs, int x_pitch, const int64_t* __restrict__ target, float* __restrict__ dx, long dx_bs,
         int dx_pitch, float* __restrict__ probs, float* __restrict__ row_nll, int32_t* __restrict__ row_hit,
-        float* __restrict__ loss_part, int w, int q_rt, int tiles_per_clip, long ntiles, float inv_n) {
+        float* __restrict__ loss_part, int w, int q_rt, int tiles_per_clip, long ntiles, float inv_n,
+        const std::conditional_t<WIN, WnNllWin, WnNoWin> win) {
     constexpr int MAXW = MAXT / 64;
     constexpr int TP = TR + 1;
     __shared__ float s_max[MAXW][64], s_sum[MAXW][64], s_xy[64];
     __shared__ int s_arg[MAXW][64];
     __shared__ float s_t[MAXW][64 * TP];
+    __shared__ int s_win[WIN ? 2 * WN_WIN_MAX : 1];
     const int q = Q256 ? 256 : q_rt;
     // (the wave index through readfirstlane: row offsets are then wave-uniform, a scalar base + the lane's column per access)
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
     const int k0 = wave * RPW;
     const float nan = __builtin_nanf("");
     float lacc = 0.f;
+    if constexpr (WIN) {
+        // the table from the kernel arguments into LDS, by constant indices (a lane-indexed read of the arguments would move the
+        // table to scratch; a select per pair keeps 32 scalars alive across the tile and spills them)
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int j = 0; j < WN_WIN_MAX; ++j) { s_win[j] = win.lo[j]; s_win[WN_WIN_MAX + j] = win.hi[j]; }
+        }
+        __syncthreads();
+    }
     for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int b = (int)(tile / tiles_per_clip);
         const int c0 = (int)(tile - (long)b * tiles_per_clip) * 64, c = c0 + lane;
@@ -38,13 +58,25 @@ __global__ __launch_bounds__(MAXT) void step_nll_k(
         const long col = (long)b * w + c;
         long y = -1;
         if (cv && target) y = target[col];
-        const bool bad = (unsigned long)y >= (unsigned long)q;
+        bool bad = (unsigned long)y >= (unsigned long)q;
+        int lo = 0, hi = q;
+        if constexpr (WIN) {
+            // the clip's position mod period without a 64-bit division: p = h 2^32 + l, pow32 = 2^32 mod period (from the host).
+            // A negative position poisons the clip's columns and picks no pair.
+            const long pb = win.pos ? win.pos[b] : 0;
+            const unsigned P = (unsigned)win.period;
+            const unsigned base = win.pos0 + (((unsigned)((unsigned long)pb >> 32) % P) * win.pow32 + (unsigned)pb % P) % P;
+            const unsigned jw = (base + (unsigned)c) % P;
+            if (pb >= 0 && cv) { lo = s_win[jw]; hi = s_win[WN_WIN_MAX + jw]; }
+            bad = bad || pb < 0 || y < lo || y >= hi;
+        }
         const float* xr = x + b * x_bs + (long)k0 * x_pitch + c0;       // row k0 of this tile, wave-uniform
         float v[RPW];
 #pragma unroll
         for (int j = 0; j < RPW; ++j) {
             const int k = k0 + j;
-            v[j] = (Q256 || k < q) ? (cv ? xr[lane] : 0.f) : -INFINITY;
+            if constexpr (WIN) v[j] = ((unsigned)(k - lo) < (unsigned)(hi - lo)) ? (cv ? xr[lane] : 0.f) : -INFINITY;      // (hi <= q)
+            else v[j] = (Q256 || k < q) ? (cv ? xr[lane] : 0.f) : -INFINITY;
             xr += x_pitch;
         }
         // this wave's max, its first index, and the target's logit if it is one of these rows
@@ -125,9 +157,26 @@ __global__ __launch_bounds__(MAXT) void step_nll_k(
     }
 }
 
-// target NULL: the softmax alone (wn_step_softmax; nothing but probs is written).  The caller has checked the arguments.
+// target NULL: the softmax alone (wn_step_softmax; nothing but probs is written).  win NULL (or of period 0): the instantiations without
+// windows.  The caller has checked the arguments.
+template <bool WIN, class Win>
+static void step_nll_launch(int grid, dim3 block, hipStream_t st, const float* x, long x_bs, int x_pitch, const int64_t* target, float* dx,
+                            long dx_bs, int dx_pitch, float* probs, float* row_nll, int32_t* row_hit, float* loss_part, int w, int q,
+                            int tiles_per_clip, long ntiles, float inv_n, const Win& win) {
+    if (q == 256)
+        hipLaunchKernelGGL((step_nll_k<64, 8, true, 256, WIN>), dim3(grid), block, 0, st, x, x_bs, x_pitch, target, dx, dx_bs, dx_pitch,
+                           probs, row_nll, row_hit, loss_part, w, q, tiles_per_clip, ntiles, inv_n, win);
+    else if (q <= 512)
+        hipLaunchKernelGGL((step_nll_k<64, 8, false, 512, WIN>), dim3(grid), block, 0, st, x, x_bs, x_pitch, target, dx, dx_bs, dx_pitch,
+                           probs, row_nll, row_hit, loss_part, w, q, tiles_per_clip, ntiles, inv_n, win);
+    else          // (16 waves of 64 rows leave 128 registers a lane: this instantiation alone keeps part of its rows in scratch)
+        hipLaunchKernelGGL((step_nll_k<64, 8, false, 1024, WIN>), dim3(grid), block, 0, st, x, x_bs, x_pitch, target, dx, dx_bs, dx_pitch,
+                           probs, row_nll, row_hit, loss_part, w, q, tiles_per_clip, ntiles, inv_n, win);
+}
+
 int wn_launch_step_nll(const float* x, long x_bs, int x_pitch, const int64_t* target, float* dx, long dx_bs, int dx_pitch, float* probs,
-                       float* row_nll, int32_t* row_hit, float* loss_part, int w, int q, int batch, float inv_n, hipStream_t st) {
+                       float* row_nll, int32_t* row_hit, float* loss_part, int w, int q, int batch, float inv_n, const WnNllWin* win,
+                       hipStream_t st) {
     if (batch <= 0 || w <= 0) {
         if (loss_part) {
             hipError_t e = hipMemsetAsync(loss_part, 0, WN_CE_PARTIALS * sizeof(float), st);
@@ -141,15 +190,12 @@ int wn_launch_step_nll(const float* x, long x_bs, int x_pitch, const int64_t* ta
     const long rounds = (ntiles + WN_CE_PARTIALS - 1) / WN_CE_PARTIALS;
     const int grid = (int)((ntiles + rounds - 1) / rounds);
     const dim3 block(64 * ((q + 63) / 64));
-    if (q == 256)
-        hipLaunchKernelGGL((step_nll_k<64, 8, true, 256>), dim3(grid), block, 0, st, x, x_bs, x_pitch, target, dx, dx_bs, dx_pitch, probs,
-                           row_nll, row_hit, loss_part, w, q, tiles_per_clip, ntiles, inv_n);
-    else if (q <= 512)
-        hipLaunchKernelGGL((step_nll_k<64, 8, false, 512>), dim3(grid), block, 0, st, x, x_bs, x_pitch, target, dx, dx_bs, dx_pitch, probs,
-                           row_nll, row_hit, loss_part, w, q, tiles_per_clip, ntiles, inv_n);
-    else          // (16 waves of 64 rows leave 128 registers a lane: this instantiation alone keeps part of its rows in scratch)
-        hipLaunchKernelGGL((step_nll_k<64, 8, false, 1024>), dim3(grid), block, 0, st, x, x_bs, x_pitch, target, dx, dx_bs, dx_pitch, probs,
-                           row_nll, row_hit, loss_part, w, q, tiles_per_clip, ntiles, inv_n);
+    if (win && win->period > 0)
+        step_nll_launch<true>(grid, block, st, x, x_bs, x_pitch, target, dx, dx_bs, dx_pitch, probs, row_nll, row_hit, loss_part, w, q,
+                              tiles_per_clip, ntiles, inv_n, *win);
+    else
+        step_nll_launch<false>(grid, block, st, x, x_bs, x_pitch, target, dx, dx_bs, dx_pitch, probs, row_nll, row_hit, loss_part, w, q,
+                               tiles_per_clip, ntiles, inv_n, WnNoWin());
     WN_CHECK_LAUNCH();
     return 0;
 }

@@ -4,6 +4,7 @@ the workspace pool, the flat-parameter spec, `EngineBase` (state, timing marks, 
 
 PyTorch is used for device memory and streams only.  Nothing here imports oracle/.
 """
+import ctypes
 import weakref
 from collections import namedtuple
 
@@ -118,6 +119,50 @@ class _Spec:
 
 
 OBJECTIVES = ("reference", "nll")     # what a fused step minimises: the reference's loss, or the true NLL per sample
+
+
+class NllWindows:
+    """The position windows of the "nll" objective (include/wavenet_hip.h, wn_win_step_nll): 1..16 ``(lo, hi)`` pairs with
+    0 <= lo < hi <= Q, the samplers' table (fast_generate.stage_windows); the column at stream position p is scored inside pair
+    ``p % len(windows)``."""
+
+    def __init__(self, windows, Q):
+        try:
+            pairs = [(int(lo), int(hi)) for lo, hi in windows]
+        except (TypeError, ValueError):
+            raise ValueError("windows must be a sequence of (lo, hi) pairs") from None
+        if not 1 <= len(pairs) <= 16:
+            raise ValueError("windows must hold 1..16 (lo, hi) pairs, got %d" % len(pairs))
+        for lo, hi in pairs:
+            if not 0 <= lo < hi <= Q:
+                raise ValueError("every window needs 0 <= lo < hi <= Q = %d, got (%d, %d)" % (Q, lo, hi))
+        self.pairs = pairs
+        self.host = (ctypes.c_int32 * (2 * len(pairs)))(*[v for pr in pairs for v in pr])
+        self.pos = None                  # the per-clip positions of the last tail(), kept alive for the launch
+
+    def tail(self, window_pos, B, device):
+        """The arguments the windowed entries take behind those of wn_step_nll / wn_step_softmax (before the stream): win_host,
+        win_period, win_pos, win_pos0.  window_pos: None (every clip starts at position 0), an int (all clips), or one per clip - a
+        host sequence, or an int64 device tensor, which travels as it is (no host synchronisation)."""
+        pos, pos0 = None, 0
+        if isinstance(window_pos, torch.Tensor) and window_pos.dim() > 0:
+            pos = window_pos.reshape(-1)
+            if pos.dtype != torch.int64:
+                raise ValueError("window_pos as a tensor is int64, one stream position per clip, got %s" % pos.dtype)
+            pos = pos.to(device).contiguous()
+        elif window_pos is not None and not isinstance(window_pos, (int, np.integer, torch.Tensor)):
+            vals = [int(v) for v in window_pos]
+            if any(v < 0 for v in vals):
+                raise ValueError("window_pos (the stream position of a clip's first target) must be >= 0, got %d" % min(vals))
+            pos = torch.tensor(vals, dtype=torch.int64).to(device)
+        elif window_pos is not None:
+            pos0 = int(window_pos)
+            if pos0 < 0:
+                raise ValueError("window_pos (the stream position of a clip's first target) must be >= 0, got %d" % pos0)
+        if pos is not None and pos.numel() != B:
+            raise ValueError("window_pos holds %d positions for %d clips" % (pos.numel(), B))
+        self.pos = pos
+        return ctypes.cast(self.host, ctypes.c_void_p), len(self.pairs), ptr(pos), pos0
 
 
 SlabOp = namedtuple("SlabOp", "so n chunk ns")      # first slab element, elements per slab, wn_wgrad's chunk (or None), slabs
@@ -240,6 +285,9 @@ class EngineBase:
     # the loss of loss_and_grad(..., objective=None): "reference" = chunk softmax + CrossEntropyLoss on the probabilities, as the
     # reference trains; "nll" = the negative log-likelihood under the per-timestep softmax the decoder samples from
     objective = "reference"
+    # the position windows of the "nll" objective: None, or 1..16 (lo, hi) pairs (NllWindows) - step_nll, score_logits, step_probs
+    # and the fused step then run wn_win_step_nll / wn_win_step_softmax, the softmax of a column taken inside its position's pair
+    nll_windows = None
 
     def _init_state(self):
         self._ws = WorkspacePool(self._make_workspace)
@@ -636,18 +684,34 @@ class EngineBase:
             raise ValueError("music_amd: objective must be one of %s, not %r" % (", ".join(OBJECTIVES), objective))
         return objective
 
-    def step_nll(self, ws, target, dlogits=None, probs=None, row_nll=None, row_hit=None):
+    def _resolve_windows(self, windows, window_pos=None):
+        """NllWindows of `windows`, else of self.nll_windows, else None (then window_pos must be unset too)"""
+        windows = self.nll_windows if windows is None else windows
+        if windows is None:
+            if window_pos is not None:
+                raise ValueError("music_amd: window_pos is the position inside a window table: pass windows= (or set nll_windows) with it")
+            return None
+        return windows if isinstance(windows, NllWindows) else NllWindows(windows, self.Q)
+
+    def step_nll(self, ws, target, dlogits=None, probs=None, row_nll=None, row_hit=None, windows=None, window_pos=None):
         """wn_step_nll on the compact logits ws["O"] (pitch W, clip stride Q W): loss partials of the MEAN negative log-likelihood under
         the per-timestep softmax into ws["loss_part"]; d loss / d logits in the logits' own layout, the (B W, Q) probabilities, the
-        per-column nll and hit flags where a tensor is given"""
+        per-column nll and hit flags where a tensor is given.  windows (None: self.nll_windows) / window_pos: the one launch is
+        wn_win_step_nll, column c of clip b scored inside the pair of stream position window_pos[b] + c (NllWindows.tail)."""
         B, W, Q = ws["B"], ws["W"], self.Q
+        win = self._resolve_windows(windows, window_pos)
         if "loss_part" not in ws:
             ws["loss_part"] = torch.zeros(_lib.CE_NUM_PARTIALS, dtype=torch.float32, device=self.device)
-        call("wn_step_nll", ptr(ws["O"]), Q * W, W, ptr(target), ptr(dlogits), Q * W, W, ptr(probs), ptr(row_nll), ptr(row_hit),
-             ptr(ws["loss_part"]), W, Q, B, 1.0 / (B * W), _lib.stream())
+        if win is None:
+            call("wn_step_nll", ptr(ws["O"]), Q * W, W, ptr(target), ptr(dlogits), Q * W, W, ptr(probs), ptr(row_nll), ptr(row_hit),
+                 ptr(ws["loss_part"]), W, Q, B, 1.0 / (B * W), _lib.stream())
+        else:
+            ws["nll_win"] = win                 # (the host table and the positions live as long as the workspace's last launch)
+            call("wn_win_step_nll", ptr(ws["O"]), Q * W, W, ptr(target), ptr(dlogits), Q * W, W, ptr(probs), ptr(row_nll), ptr(row_hit),
+                 ptr(ws["loss_part"]), W, Q, B, 1.0 / (B * W), *win.tail(window_pos, B, self.device), _lib.stream())
         self.mark("step_nll")
 
-    def score_logits(self, ws, target):
+    def score_logits(self, ws, target, windows=None, window_pos=None):
         """(row_nll float32 (B W,), row_hit int32 (B W,)) of the logits a forward left in ws["O"]: nats of every target sample under
         the per-timestep softmax, and whether the first-index argmax is the target.  Forward only: no gradient is formed."""
         n = ws["B"] * ws["W"]
@@ -655,15 +719,20 @@ class EngineBase:
         assert target.numel() == n and target.dtype == torch.int64 and target.is_cuda
         row_nll = torch.empty(n, dtype=torch.float32, device=self.device)
         row_hit = torch.empty(n, dtype=torch.int32, device=self.device)
-        self.step_nll(ws, target, row_nll=row_nll, row_hit=row_hit)
+        self.step_nll(ws, target, row_nll=row_nll, row_hit=row_hit, windows=windows, window_pos=window_pos)
         return row_nll, row_hit
 
-    def step_probs(self, ws):
+    def step_probs(self, ws, windows=None, window_pos=None):
         """(B W, Q) per-timestep probabilities of the logits in ws["O"] (wn_step_softmax): row b W + w is the distribution the
-        decoder draws sample w of clip b from"""
+        decoder draws sample w of clip b from - under windows (wn_win_step_softmax), the one a windowed decode draws from"""
         B, W, Q = ws["B"], ws["W"], self.Q
+        win = self._resolve_windows(windows, window_pos)
         probs = torch.empty(B * W, Q, dtype=torch.float32, device=self.device)
-        call("wn_step_softmax", ptr(ws["O"]), Q * W, W, ptr(probs), W, Q, B, _lib.stream())
+        if win is None:
+            call("wn_step_softmax", ptr(ws["O"]), Q * W, W, ptr(probs), W, Q, B, _lib.stream())
+        else:
+            ws["nll_win"] = win
+            call("wn_win_step_softmax", ptr(ws["O"]), Q * W, W, ptr(probs), W, Q, B, *win.tail(window_pos, B, self.device), _lib.stream())
         return probs
 
     def _throttled(self, step):
@@ -673,11 +742,15 @@ class EngineBase:
         self._throttle.leave()
         return out
 
-    def _fused_tail(self, ws, target, want_probs=False, objective=None):
+    def _fused_tail(self, ws, target, want_probs=False, objective=None, windows=None, window_pos=None):
         """Everything of a fused step behind the forward that left the logits in ws["O"]: softmax + CrossEntropyLoss on the
         probabilities in one kernel (objective "nll": the per-timestep softmax and its negative log-likelihood, step_nll), the
-        backward, the loss as a 0-d device tensor.  Gradients land in self.flat_grad."""
+        backward, the loss as a 0-d device tensor.  Gradients land in self.flat_grad.  windows / window_pos: step_nll's; the
+        reference's loss has no per-column softmax to window."""
         objective = self._resolve_objective(objective)
+        win = self._resolve_windows(windows, window_pos)
+        if win is not None and objective != "nll":
+            raise ValueError('music_amd: position windows (nll_windows) apply to objective "nll" only, not %r' % objective)
         bw = self._bwd_workspace(ws)
         n = ws["B"] * ws["W"]
         target = target.reshape(-1)
@@ -689,7 +762,7 @@ class EngineBase:
             probs = torch.empty(n, self.Q, dtype=torch.float32, device=self.device)
             ws["probs"] = probs
         if objective == "nll":
-            self.step_nll(ws, target, bw["dO"], probs)
+            self.step_nll(ws, target, bw["dO"], probs, windows=win, window_pos=window_pos)
         else:
             self.softmax_ce(ws["O"], target, probs, bw["dO"], ws["loss_part"], n)
         if self.vq:                         # reconstruction loss + vq_loss, under either objective; its upstream scalar is 1

@@ -194,13 +194,13 @@ class GenericWaveNetEngine(GeneralPlan):
         self.pack_weights()
         return self.forward_logits(x)
 
-    def loss_and_grad(self, x, target, want_probs=False, objective=None):
-        """objective: None = self.objective (EngineBase)"""
-        return self._throttled(lambda: self._fused_tail(self._step_forward(x), target, want_probs, objective))
+    def loss_and_grad(self, x, target, want_probs=False, objective=None, windows=None, window_pos=None):
+        """objective: None = self.objective (EngineBase); windows / window_pos: step_nll's"""
+        return self._throttled(lambda: self._fused_tail(self._step_forward(x), target, want_probs, objective, windows, window_pos))
 
-    def loss_and_grad_codes(self, codes, target, scrambled=True, want_probs=False, objective=None):
+    def loss_and_grad_codes(self, codes, target, scrambled=True, want_probs=False, objective=None, windows=None, window_pos=None):
         """the fast engine's entry point on integer codes; here the one-hot is built (wn_onehot) and the dense path runs"""
-        return self.loss_and_grad(self.onehot(codes, scrambled), target, want_probs, objective)
+        return self.loss_and_grad(self.onehot(codes, scrambled), target, want_probs, objective, windows, window_pos)
 
     def onehot(self, codes, scrambled=True):
         """int32 (B,T) codes on the device -> float32 (B,Q,T) (faster_audio_data.py:62-83)."""

@@ -22,10 +22,14 @@ except ImportError:
 class audio_dataset(Dataset):
 
     def __init__(self, audio_path, receptive_field, window_length, cuda_available=False,
-                 quantization_channels=256, labels_path=None, n_classes=None):
+                 quantization_channels=256, labels_path=None, n_classes=None, token_positions=False):
         """labels_path (the optional key "labels_path" of dataset_params.json): a JSON list of integers, one class per item of the
         audio pickle (global class conditioning of the autoencoder); every piece then carries 'audio_class', the label of the item
-        it was cut from.  n_classes: the model's global_classes - a label outside [0, n_classes) raises here."""
+        it was cut from.  n_classes: the model's global_classes - a label outside [0, n_classes) raises here.
+        token_positions (the optional key "token_positions" of dataset_params.json): every piece also carries 'audio_pos', the offset
+        of its FIRST TARGET sample within the pickle item it was cut from - the stream position the windowed objective needs
+        (music_amd/objective.py, "nll_windows"; an item of tools/vq_codes_dataset.py starts at a frame boundary, position 0 = stage 0)."""
+        self.token_positions = bool(token_positions)
         self.audio_path = audio_path
         self.labels_path = labels_path
         self.receptive_field = receptive_field
@@ -58,23 +62,29 @@ class audio_dataset(Dataset):
         assigns nothing new); a first item that short raises NameError, as the reference does."""
         rf, win = self.receptive_field, self.window_length
         pieces = []
-        piece = target = label = None
+        piece = target = label = pos = None
         for n, item in enumerate(data):
             item = torch.from_numpy(item)
+            consumed = 0                         # samples of this item cut off so far
             while len(item) > rf:
                 if len(item) >= rf + win:
                     piece = item[:rf + win - 1]
                     target = item[rf:rf + win].long()
                     label = labels[n] if labels is not None else None
+                    pos = consumed + rf          # where target[0] sits in the item
                     item = item[win:]
+                    consumed += win
                 else:
                     item = item[rf:]
+                    consumed += rf
                 if target is None:
                     raise NameError("name 'target' is not defined")
                 # (a re-appended piece keeps the label of the item its samples came from - the previous item's, where a short item
-                # repeats that one's last piece)
+                # repeats that one's last piece - and, with token_positions, the position of the piece it repeats)
                 pieces.append({'audio_piece': piece, 'audio_target': target} if labels is None else
                               {'audio_piece': piece, 'audio_target': target, 'audio_class': label})
+                if self.token_positions:
+                    pieces[-1]['audio_pos'] = pos
         return pieces
 
     def __len__(self):
@@ -178,11 +188,18 @@ class _Collate:
         if same and torch.cuda.is_available():
             codes = self.stager.to_device([it['audio_piece'].to(torch.int32) for it in items], torch.int32)
             target = self.stager.to_device([it['audio_target'] for it in items], torch.int64)
+            if "audio_pos" in items[0]:
+                pos = self.stager.to_device([torch.tensor([it['audio_pos']], dtype=torch.int64) for it in items], torch.int64).view(-1)
         else:                                    # (torch.stack raises on ragged items, as in the reference; no device: onehot_device raises)
             codes = torch.stack([it['audio_piece'] for it in items]).to(torch.int32)
             target = torch.stack([it['audio_target'] for it in items])
             target = target.cuda(non_blocking=True) if torch.cuda.is_available() else target
+            if "audio_pos" in items[0]:
+                pos = torch.tensor([it['audio_pos'] for it in items], dtype=torch.int64)
+                pos = pos.cuda(non_blocking=True) if torch.cuda.is_available() else pos
         batch = {"audio_piece": onehot_device(codes, self.q, scrambled=self.scrambled), "audio_target": target}
+        if "audio_pos" in items[0]:                  # (token_positions: the clips' stream positions, staged like the targets)
+            batch["audio_pos"] = pos
         if "audio_class" in items[0]:                # (labels_path: this shard's classes, on the host - the engine checks and copies them)
             batch["audio_class"] = torch.tensor([it["audio_class"] for it in items], dtype=torch.int64)
         if self.shard is not None:
@@ -199,7 +216,8 @@ def audio_data_loader(batch_size, shuffle, num_workers, pin_memory, shard=None, 
     batch; all ranks must share the torch seed so they draw the same permutation.  ``one_hot`` (the optional key "one_hot" of
     dataset_params.json): "scrambled" is the reference's reshape-not-transpose layout, "canonical" the true one-hot
     x[b][code[t]][t] = 1 - what a model trained on the true likelihood (music_amd/objective.py) and the decoder see.
-    With ``labels_path`` (audio_dataset) a batch also has "audio_class": int64 (B,) on the HOST, the classes of this process's clips."""
+    With ``labels_path`` (audio_dataset) a batch also has "audio_class": int64 (B,) on the HOST, the classes of this process's clips;
+    with ``token_positions`` "audio_pos": int64 (B,) on the device, the offset of each clip's first target within its item."""
     if one_hot not in ONE_HOT_LAYOUTS:
         raise ValueError("one_hot must be one of %s, not %r" % (", ".join(ONE_HOT_LAYOUTS), one_hot))
     audioDataset = audio_dataset(**kwargs)

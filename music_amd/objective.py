@@ -9,6 +9,10 @@ alternative, for ``wavenet`` and ``wavenet_autoencoder`` alike:
 ``step_probs(net, x)``         (B W, Q) per-timestep probabilities, the distribution the decoder draws from
 ``score(net, x, target)``      per-clip nats, bits and accuracy of a checkpoint on held-out audio, no gradient
 
+All three take ``windows=`` / ``window_pos=``: the samplers' position windows (``fast_generate.stage_windows``) applied to the
+objective (``wn_win_step_nll`` / ``wn_win_step_softmax``), for a prior over a residual quantiser's interleaved token stream - the
+softmax of a column is taken inside the pair of its stream position, which is what ``sample_code_stream`` draws from.
+
 There is no CPU path: the arithmetic runs through libwavenet_hip.so only.
 """
 from contextlib import nullcontext
@@ -19,10 +23,10 @@ import torch
 
 try:
     from . import faster_audio_data
-    from .engine_base import OBJECTIVES, WorkspaceHold
+    from .engine_base import OBJECTIVES, NllWindows, WorkspaceHold
 except ImportError:                      # imported as a bare module
     from music_amd import faster_audio_data
-    from music_amd.engine_base import OBJECTIVES, WorkspaceHold
+    from music_amd.engine_base import OBJECTIVES, NllWindows, WorkspaceHold
 
 
 def _dense_input(wave_sample):
@@ -69,10 +73,11 @@ class _NLLFunction(torch.autograd.Function):
     backward_from_dlogits scaled by the upstream scalar."""
 
     @staticmethod
-    def forward(ctx, net, grad_on, wave_sample, target, classes, stages, *params):
+    def forward(ctx, net, grad_on, wave_sample, target, classes, stages, windows, window_pos, *params):
         eng, ws = _forward_logits(net, wave_sample, classes, stages)
         need = grad_on and any(ctx.needs_input_grad)
-        eng.step_nll(ws, _flat_target(target, ws), eng._bwd_workspace(ws)["dO"] if need else None)
+        eng.step_nll(ws, _flat_target(target, ws), eng._bwd_workspace(ws)["dO"] if need else None, windows=windows,
+                     window_pos=window_pos)
         ctx.eng, ctx.ws, ctx.gen = eng, ws, ws["gen"]
         ctx.hold = WorkspaceHold(ws) if need else None          # see music_amd/model.py
         if getattr(eng, "vq", False):
@@ -102,7 +107,7 @@ class _NLLFunction(torch.autograd.Function):
             o, shp = eng.spec.off[name], eng.spec.shape[name]
             grads.append(g[o:o + int(np.prod(shp))].view(shp))
         din = eng.input_grad(ws) * dloss if ctx.needs_input_grad[2] else None
-        return (None, None, din, None, None, None) + tuple(grads)
+        return (None, None, din, None, None, None, None, None) + tuple(grads)
 
 
 def _params(net):
@@ -110,41 +115,46 @@ def _params(net):
     return [p for _, p in net._named_ref_params()] if hasattr(net, "_named_ref_params") else list(net.parameters())
 
 
-def nll_loss(net, x, target, classes=None, stages=None):
+def nll_loss(net, x, target, classes=None, stages=None, windows=None, window_pos=None):
     """Mean negative log-likelihood (nats per sample) of `target` (B, W) or (B W,) int64 under the per-timestep softmax of
     net's logits for the one-hot x (B, Q, T): a 0-d tensor whose backward() gives the parameter gradients (and the input's, when it
     requires grad).  A target outside [0, Q) makes the loss NaN.  classes: one integer per clip for an autoencoder with global class
     conditioning (required there, refused elsewhere).  stages: the clips' stage counts under quantiser dropout, as the autoencoder's
-    forward takes them (None: all stages - this function draws nothing)."""
+    forward takes them (None: all stages - this function draws nothing).  windows: 1..16 (lo, hi) pairs (None: the engine's
+    nll_windows) - the softmax of column c of clip b is taken inside the pair of stream position window_pos[b] + c; window_pos: None
+    (0), an int, or one per clip (a sequence, or an int64 device tensor: no host synchronisation).  A target outside its window makes
+    the loss NaN."""
     if classes is not None and not hasattr(net, "engine_cond"):
         raise ValueError("music_amd.objective: classes are the autoencoder's (global class conditioning)")
-    out = _NLLFunction.apply(net, torch.is_grad_enabled(), x, target, classes, stages, *_params(net))
+    out = _NLLFunction.apply(net, torch.is_grad_enabled(), x, target, classes, stages, windows, window_pos, *_params(net))
     if isinstance(out, tuple):                                  # a vq autoencoder: the caller adds net.vq_loss
         out, net.vq_loss = out
     return out
 
 
-def step_probs(net, x, classes=None):
+def step_probs(net, x, classes=None, windows=None, window_pos=None):
     """(B W, Q) probabilities: row b W + w is softmax over the Q logits of output column w of clip b - what the decoder samples
-    from (the module's own forward returns the reference's chunk softmax instead)."""
+    from (the module's own forward returns the reference's chunk softmax instead).  windows / window_pos (nll_loss): the
+    distribution a windowed decode draws from, an exact 0 outside the column's window."""
     with torch.no_grad():
         eng, ws = _forward_logits(net, x, classes)
-        return eng.step_probs(ws)
+        return eng.step_probs(ws, windows=windows, window_pos=window_pos)
 
 
-def score(net, x_or_codes, target, scrambled=False, classes=None, stages=None):
+def score(net, x_or_codes, target, scrambled=False, classes=None, stages=None, windows=None, window_pos=None):
     """Held-out figures of net on one batch, forward only.  x_or_codes: the one-hot (B, Q, T) float, or the integer codes (B, T) -
     then the one-hot is laid out canonical, or as the loader scrambles it with `scrambled`.  Returns device tensors of
     shape (B,), float64: "nll" (mean nats per sample of each clip), "bits" (nll / ln 2) and "accuracy" (share of samples whose
     first-index argmax is the target); the per-clip means are taken on the device, nothing is read back.  stages: score a residual vq
-    autoencoder with the first n stages (an int, or one per clip) - the coarser code's figures."""
+    autoencoder with the first n stages (an int, or one per clip) - the coarser code's figures.  windows / window_pos (nll_loss): the
+    figures of the windowed distribution, the honest bits per token of what sample_code_stream draws from."""
     with torch.no_grad():
         x = x_or_codes
         if x.dim() == 2:
             q = getattr(net, "quantization_channels", None) or net.quantization_channel
             x = faster_audio_data.onehot_device(x, q, scrambled)
         eng, ws = _forward_logits(net, x, classes, stages)
-        row_nll, row_hit = eng.score_logits(ws, _flat_target(target, ws))
+        row_nll, row_hit = eng.score_logits(ws, _flat_target(target, ws), windows=windows, window_pos=window_pos)
         B, W = ws["B"], ws["W"]
         nll = row_nll.view(B, W).double().mean(1)
         return {"nll": nll, "bits": nll / math.log(2.0), "accuracy": row_hit.view(B, W).double().mean(1)}
@@ -159,6 +169,35 @@ def objective_option(train_params):
     return objective
 
 
+def nll_windows_option(train_params, dataset_params, quantization_channels=None):
+    """The optional key "nll_windows" of train_params.json: {"stages": S, "codes": K} - fast_generate.stage_windows(S, K), the table
+    of a residual quantiser's token stream (tools/vq_codes_dataset.py) - or an explicit list of [lo, hi] pairs; None when unset.
+    It needs "objective": "nll" (the reference's loss has no per-column softmax to window), "token_positions": true in
+    dataset_params.json (every clip would otherwise be scored as if it started at stream position 0) and hi <= quantization_channels
+    (default: dataset_params')."""
+    spec = train_params.get("nll_windows")
+    if spec is None:
+        return None
+    if objective_option(train_params) != "nll":
+        raise ValueError('train_params.json: "nll_windows" needs "objective": "nll", not %r' % train_params.get("objective", "reference"))
+    if not dataset_params.get("token_positions"):
+        raise ValueError('train_params.json: "nll_windows" needs "token_positions": true in dataset_params.json (the stream position '
+                         'of every clip)')
+    if isinstance(spec, dict):
+        if set(spec) != {"stages", "codes"}:
+            raise ValueError('train_params.json: "nll_windows" as an object is {"stages": S, "codes": K}, got keys %s' % sorted(spec))
+        try:                                 # (here, not at the top: fast_generate imports train, which imports this module)
+            from .fast_generate import stage_windows
+        except ImportError:
+            from music_amd.fast_generate import stage_windows
+        spec = stage_windows(spec["stages"], spec["codes"])
+    q = dataset_params.get("quantization_channels", 256) if quantization_channels is None else quantization_channels
+    try:
+        return NllWindows(spec, int(q)).pairs
+    except ValueError as e:
+        raise ValueError('train_params.json: "nll_windows": %s' % e) from None
+
+
 class Validation:
     """Held-out scoring during training: every `validate_every` steps, `score` over the loader of "valid_audio_path" - under the
     EMA shadow's weights when there is one - and one line in valid_log.log.  make() returns None when the keys are unset: nothing
@@ -169,15 +208,17 @@ class Validation:
         path, every = train_params.get("valid_audio_path"), int(train_params.get("validate_every") or 0)
         if not path or every <= 0:
             return None
-        return cls(path, every, dataset_params, train_params["log_dir"], train_params.get("valid_labels_path"))
+        return cls(path, every, dataset_params, train_params["log_dir"], train_params.get("valid_labels_path"),
+                   nll_windows_option(train_params, dataset_params))
 
-    def __init__(self, audio_path, every, dataset_params, log_dir, labels_path=None):
+    def __init__(self, audio_path, every, dataset_params, log_dir, labels_path=None, windows=None):
         # (the training set's labels name the training pickle's items: the held-out set's come from "valid_labels_path")
         params = {k: v for k, v in dataset_params.items() if k not in ("shard", "labels_path")}
         params.update(audio_path=audio_path, shuffle=False)
         if labels_path:
             params.update(labels_path=labels_path)
         self.every = every
+        self.windows = windows               # ("nll_windows": the held-out figures are those of the windowed distribution)
         self.loader = faster_audio_data.audio_data_loader(**params)
         self.log_path = log_dir + "valid_log.log"
 
@@ -189,6 +230,8 @@ class Validation:
                 if batch["audio_piece"] is None:
                     continue
                 kw = {"classes": batch["audio_class"]} if "audio_class" in batch else {}       # (global class conditioning)
+                if self.windows is not None:
+                    kw.update(windows=self.windows, window_pos=batch["audio_pos"])
                 r = score(net, batch["audio_piece"], batch["audio_target"], **kw)
                 part = torch.stack([r["nll"].sum(), r["bits"].sum(), r["accuracy"].sum()])
                 total = part if total is None else total + part

@@ -372,7 +372,10 @@ def train():
         raise ValueError("Cuda is not avalable,", " can not train model using multi-gpu.")
     # optional keys: "objective": "nll" trains the negative log-likelihood under the per-timestep softmax instead of the reference's
     # loss; "valid_audio_path" + "validate_every" (steps) score held-out audio on rank 0 into valid_log.log (music_amd/objective.py)
+    # "nll_windows" ({"stages": S, "codes": K} or [lo, hi] pairs; with "token_positions": true in dataset_params.json): the position
+    # windows of the samplers applied to that objective - a prior over a residual quantiser's token stream trains on what it samples
     objective = wobjective.objective_option(train_params)
+    nll_windows = wobjective.nll_windows_option(train_params, dataset_params, wavenet_params.get("quantization_channels"))
     validation = wobjective.Validation.make(train_params, dataset_params) if rank == 0 else None
     if world > 1:
         # DataParallel semantics: the JSON batch_size is the GLOBAL batch, split evenly
@@ -451,12 +454,13 @@ def train():
                     piece = piece.cuda(non_blocking=True)
                     target = target.cuda(non_blocking=True)
                 target = target.view(-1)
+            win_kw = {} if nll_windows is None else {"windows": nll_windows, "window_pos": sampled_batch.get("audio_pos")}     # (absent on an empty shard)
             loss = torch.zeros((), device=device)
             if fused:
                 if engine is None:
                     engine = _fused_engine()
                 if piece is not None:
-                    loss = engine.loss_and_grad(piece.contiguous(), target)
+                    loss = engine.loss_and_grad(piece.contiguous(), target, **win_kw)
                 else:
                     engine.flat_grad.zero_()
                 if guarded:                               # the sum alone; 1 / world rides in the guard's and the update's gscale
@@ -468,7 +472,7 @@ def train():
             else:
                 optimizer.zero_grad()
                 if piece is not None and objective == "nll":
-                    loss = wobjective.nll_loss(net, piece, target)
+                    loss = wobjective.nll_loss(net, piece, target, **win_kw)
                     loss.backward()
                 elif piece is not None:
                     logits = net(piece)            # probabilities, named as in the reference (Q1)

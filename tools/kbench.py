@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of single kernels of the hot path at BASELINE config-2 shapes (GPU only).
 
-    python tools/kbench.py [fwd|bwd|epi|dx|skip|decode|ae|guard|ema|nll|cond|vq|vq_ema|gcond|rvq|all] [--reps N] [--precision f16x3,bf16x3]
+    python tools/kbench.py [fwd|bwd|epi|dx|skip|decode|ae|guard|ema|nll|win_nll|cond|vq|vq_ema|gcond|rvq|all] [--reps N] [--precision f16x3,bf16x3]
 
 Prints per-phase / per-layer kernel times measured with HIP events on the launch stream.
 """
@@ -603,13 +603,73 @@ def gcond_bench(reps, alternations=6, E=64, n_cls=8):
     print(json.dumps(res))
 
 
+def win_nll_bench(reps, alternations=6):
+    """`win_nll`: the windowed objective's launch (wn_win_step_nll) against the plain one (wn_step_nll, the yardstick: the kernel from
+    before the windows, measured in the same run) on random logits, with dx and forward-only (row_nll + row_hit), at config 2's shape
+    (8 x 256 x 12930, windows 4 x 64: the q = 256 instantiation) and at a prior's (8 x 1024 x 4096, windows 4 x 256: the q > 512 one).
+    HIP events around `reps * 20` back-to-back launches, the legs alternated `alternations` times on one device: medians and spreads
+    (largest - smallest).  Written to profiles/win_nll_kbench.json."""
+    import ctypes
+    from music_amd import _lib
+    from music_amd._lib import call, ptr
+    from music_amd.fast_generate import stage_windows
+    st = _lib.stream()
+    res = {"what": "wn_win_step_nll against wn_step_nll in one run, %d launches per timing, %d alternations; us" % (reps * 20, alternations)}
+    g = torch.Generator(device="cuda").manual_seed(0)
+    for label, (B, Q, W, stages) in (("config2_8x256x12930_4x64", (B_LOCAL, 256, T - 3070, 4)), ("prior_8x1024x4096_4x256", (8, 1024, 4096, 4))):
+        K = Q // stages
+        n = B * W
+        x = torch.randn(B * Q * W, device="cuda", generator=g)
+        pos = torch.randint(0, 1 << 20, (B,), device="cuda", generator=g)
+        col = pos.view(B, 1) + torch.arange(W, device="cuda").view(1, W)
+        target = ((col % stages) * K + torch.randint(0, K, (B, W), device="cuda", generator=g)).reshape(-1).contiguous()
+        dx = torch.empty_like(x)
+        part = torch.zeros(_lib.CE_NUM_PARTIALS, device="cuda")
+        row_nll = torch.empty(n, dtype=torch.float32, device="cuda")
+        row_hit = torch.empty(n, dtype=torch.int32, device="cuda")
+        host = (ctypes.c_int32 * (2 * stages))(*[v for pr in stage_windows(stages, K) for v in pr])
+        tail = (ctypes.cast(host, ctypes.c_void_p), stages, ptr(pos), 0)
+        head_dx = (ptr(x), Q * W, W, ptr(target), ptr(dx), Q * W, W, None, None, None, ptr(part), W, Q, B, 1.0 / n)
+        head_sc = (ptr(x), Q * W, W, ptr(target), None, 0, 0, None, ptr(row_nll), ptr(row_hit), ptr(part), W, Q, B, 1.0 / n)
+        legs = {
+            "step_nll": lambda: call("wn_step_nll", *head_dx, st),
+            "win_step_nll": lambda: call("wn_win_step_nll", *head_dx, *tail, st),
+            "step_nll_score": lambda: call("wn_step_nll", *head_sc, st),
+            "win_step_nll_score": lambda: call("wn_win_step_nll", *head_sc, *tail, st),
+        }
+
+        def timed(fn):
+            fn()
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            ev[0].record()
+            for _ in range(reps * 20):
+                fn()
+            ev[1].record()
+            torch.cuda.synchronize()
+            return ev[0].elapsed_time(ev[1]) / (reps * 20) * 1e3
+        us = {k: [] for k in legs}
+        for _ in range(alternations):
+            for k, fn in legs.items():
+                us[k].append(timed(fn))
+        assert not bool(torch.isnan(part.sum()))                     # (the targets respect the windows: a poisoned run measures nothing)
+        r = {"shape": [B, Q, W], "windows": [stages, K], "algorithmic_bytes_with_dx": 2 * B * Q * W * 4}
+        for k, vals in us.items():
+            r[k + "_us"], r[k + "_us_spread"] = _median_spread(vals)
+            r[k + "_us_all"] = [round(v, 2) for v in vals]
+        r["win_over_plain"] = round(r["win_step_nll_us"] / r["step_nll_us"], 3)
+        r["win_over_plain_score"] = round(r["win_step_nll_score_us"] / r["step_nll_score_us"], 3)
+        res[label] = r
+    _write_profile("win_nll_kbench.json", res)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", nargs="?", default="all")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--precision", default="f16x3,bf16x3")
     ap.add_argument("--overlap", type=int, default=1)
-    ap.add_argument("--parent", default=None, help="gcond / rvq / rvq_drop: a built checkout of the parent commit, for profiles/<what>_bench_unset.json")
+    ap.add_argument("--parent", default=None, help="gcond / rvq / rvq_drop / win_nll: a built checkout of the parent commit, for profiles/<what>_bench_unset.json")
     args = ap.parse_args()
     if args.what == "gcond":
         if args.parent:
@@ -623,6 +683,10 @@ def main():
         if args.parent:
             bench_unset(os.path.abspath(args.parent), profile="rvq_drop_bench_unset.json", keys="vq_stage_dropout")
         return rvq_drop_bench(args.reps)
+    if args.what == "win_nll":
+        if args.parent:
+            bench_unset(os.path.abspath(args.parent), profile="win_nll_bench_unset.json", keys="nll_windows / token_positions")
+        return win_nll_bench(args.reps)
     if args.what == "vq":
         return vq_bench(args.reps)
     if args.what == "vq_ema":

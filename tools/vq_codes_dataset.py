@@ -20,7 +20,12 @@ A model with "vq_stages": S > 1 gives S codes per frame.  A piece is still ONE a
 TOKENS s * K + code, so the prior's alphabet ("quantization_channels") is S * K and a position's stage is readable from its
 token; S * K > 1024, the decoder's sampler limit, is refused.  music_amd.ae_generate.split_code_stream turns a sampled stream back
 into the (B, S, Le) codes that decode_codes takes; music_amd.ae_generate.sample_code_stream samples the prior under the decoder's
-position windows, so a token never leaves its position's stage range and the stream always splits."""
+position windows, so a token never leaves its position's stage range and the stream always splits.  Train that prior on the
+distribution it is sampled from: `"nll_windows": {"stages": S, "codes": K}` beside `"objective": "nll"` in train_params.json and
+`"token_positions": true` in dataset_params.json (music_amd/objective.py: the softmax, the loss and the validation figures of a
+position are taken over its stage's K tokens only; the loss starts at ln K, not ln(S K)).  Every array written here starts at a
+frame boundary, so position 0 of an item is stage 0 - what the loader's 'audio_pos' counts from; sampling with sample_code_stream is
+unchanged."""
 import argparse
 import json
 import os
