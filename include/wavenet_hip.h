@@ -503,6 +503,29 @@ int wn_gcond_proj_bwd(const float* d_tab, int pair, const float* d_enf, const fl
                       int64_t b_off, int64_t stage_stride, int64_t wf_off, int64_t bf_off, float* d_enc, float* flat_grad,
                       int n_stages, int dd, int ch, int sd, int bw, int le, int batch, const int32_t* cls, int64_t gw_off,
                       int64_t gstage_stride, int64_t gwf_off, int64_t emb_off, int ge, int n_cls, wn_stream_t stream);
+/* ---- the GLOBAL CLASS term ALONE: the tables of a class-conditional WaveNet (WaveNet paper section 2.5), which has no encoding.
+ * wn_gcond_proj_fwd / _bwd without the bracket and with le = 1: one column per clip, constant over the clip's time.
+ *   en_i[b][c] = sum_e G_i[c][e] emb[cls[b]][e]          enf[b][c] likewise with G_f, [batch][sd]
+ * G_i, G_f, the embedding, cls, the table layouts (per clip / clip pairs, ch = dd padded to 32, le = 1) and the offsets are
+ * wn_gcond_proj_fwd's.  The sums run over e ascending from +0 in fp32 FMA: the bits of wn_gcond_proj_fwd with bw = 1, le = 1 and
+ * zero W_i, b_i.
+ * wn_gclass_fwd writes every table it is given (tab, tab_pair: at least one) WHOLE, padding rows as exact zeros, and enf, in ONE launch.
+ * wn_gclass_bwd takes d_tab in the layout `pair` names and d_enf [batch][sd] and writes, in TWO launches,
+ *   dG_i[c][e]  = sum_b d_en_i[b][c] emb[cls[b]][e]        in ascending b                                  (the final stage alike)
+ *   d_emb[m][e] = sum_{b: cls[b] == m, in ascending b} sum_r G[r][e] d[r][b]               over all n_stages * 2 dd + sd rows r
+ * at the parameters' offsets in flat_grad, OVERWRITING them and all n_cls rows of d_emb - a class no clip has gets exactly 0; nothing
+ * else of flat_grad is touched.  A cls[b] outside [0, n_cls) is never used as an index: the forward turns that clip's column of every
+ * table and its row of enf into NaN, the backward its share of dG (d_emb has no row for it).  No float atomics, a fixed order: the
+ * same bits at every launch.  On `stream`, no allocation, nothing retained, legal under stream capture.
+ * batch == 0 returns 0 (NULLs allowed).  -4, function and argument named in wn_last_error: batch < 0; n_stages, dd or sd < 1; ch < dd
+ * or ch not a multiple of 32; a pair table with an odd batch; ge < 1 or ge > WN_GCOND_MAX_CHANNELS; n_cls < 1; a negative gw_off,
+ * gwf_off or emb_off; gstage_stride < 2 dd ge with more than one stage; with work to do, a NULL required pointer. */
+int wn_gclass_fwd(const float* flat, float* tab, float* tab_pair, float* enf, int n_stages, int dd, int ch, int sd, int batch,
+                  const int32_t* cls, int64_t gw_off, int64_t gstage_stride, int64_t gwf_off, int64_t emb_off, int ge, int n_cls,
+                  wn_stream_t stream);
+int wn_gclass_bwd(const float* d_tab, int pair, const float* d_enf, const float* flat, float* flat_grad, int n_stages, int dd, int ch,
+                  int sd, int batch, const int32_t* cls, int64_t gw_off, int64_t gstage_stride, int64_t gwf_off, int64_t emb_off, int ge,
+                  int n_cls, wn_stream_t stream);
 /* ---- VECTOR-QUANTISED bottleneck of the autoencoder (VQ-VAE, van den Oord et al. 2017; the reference has none): every pooled frame
  * e = enc[b][:][l] of enc [batch][bw][le] is replaced by its nearest row of the codebook c [K][bw], which sits at flat + cb_off
  * (its gradient at flat_grad + cb_off; offsets count floats).  C = batch * le frames.  Everything in float32:

@@ -102,6 +102,9 @@ SIGNATURES = {
     "wn_cond_proj_bwd": [_p, _i, _p, _p, _p, _l, _l, _l, _l, _l, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
     "wn_gcond_proj_fwd": [_p, _p, _l, _l, _l, _l, _l, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _l, _l, _l, _l, _i, _i, _p],
     "wn_gcond_proj_bwd": [_p, _i, _p, _p, _p, _l, _l, _l, _l, _l, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _l, _l, _l, _l, _i, _i, _p],
+    # the global class term alone (a class-conditional WaveNet's tables): no encoding, le = 1
+    "wn_gclass_fwd": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _l, _l, _l, _l, _i, _i, _p],
+    "wn_gclass_bwd": [_p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _p, _l, _l, _l, _l, _i, _i, _p],
     "wn_vq_fwd": [_p, _p, _l, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     "wn_vq_bwd": [_p, _p, _p, _p, _l, _f, _f, _p, _p, _i, _i, _i, _i, _p],
     "wn_vq_lookup": [_p, _p, _l, _p, _p, _i, _i, _i, _i, _p],

@@ -403,7 +403,7 @@ def split_code_stream(tokens, stages, K):
 
 
 def sample_code_stream(prior, stages, K, frames, start_tokens, start_pos=0, temperature=None, top_k=None, top_p=None, seed=0,
-                       streams=None):
+                       streams=None, classes=None):
     """New bottleneck codes from a prior over the interleaved token stream (a ``wavenet`` with ``quantization_channels`` >= stages
     * K trained on tools/vq_codes_dataset.py's output): ``start_tokens`` (U, n0 >= receptive_field) are tokens of a real stream
     whose first token sits at stream position ``start_pos``; their last receptive_field tokens (canonical one-hot) prime the
@@ -411,6 +411,8 @@ def sample_code_stream(prior, stages, K, frames, start_tokens, start_pos=0, temp
     recurrence) under ``stage_windows(stages, K)``: the token at stream position p is drawn among stage p mod stages' K tokens
     only, renormalised there, so no token can leave its range.  ``(start_pos + n0) % stages`` must be 0: generation starts on a
     frame boundary.  ``temperature`` / ``top_k`` / ``top_p`` / ``seed`` / ``streams``: as in ``generate_codes_batch``.
+    ``classes``: one class per stream for a class-conditional prior (required there, refused elsewhere): stream u is drawn as
+    class classes[u], under the same stage windows.
     Returns ``split_code_stream`` of the generated tokens: (U, stages, frames) int64 codes in [0, K), what ``decode_codes`` takes."""
     try:
         from . import fast_generate as fg
@@ -434,14 +436,15 @@ def sample_code_stream(prior, stages, K, frames, start_tokens, start_pos=0, temp
     x = torch.nn.functional.one_hot(t[:, -rf:].to(device=dev, dtype=torch.int64), Q).transpose(1, 2).float().contiguous()
     tokens = fg.generate_codes_batch(prior, x, frames * stages, correct_queue=True, temperature=temperature, seed=seed, top_k=top_k,
                                      top_p=top_p, streams=streams, windows=fg.stage_windows(stages, K),
-                                     window_pos=start_pos + t.size(1))
+                                     window_pos=start_pos + t.size(1), classes=classes)
     return split_code_stream(tokens, stages, K)
 
 
-def prior_score(prior, tokens, stages, K, start_pos=0):
+def prior_score(prior, tokens, stages, K, start_pos=0, classes=None):
     """Held-out figures of a prior on token streams ``tokens`` (U, n > receptive_field) whose first token sits at stream position
     ``start_pos``, under the windows ``sample_code_stream`` draws with: ``objective.score`` of every token behind the first
-    receptive_field ones - per-stream "nll", "bits" (per token, of the distribution that is sampled) and "accuracy"."""
+    receptive_field ones - per-stream "nll", "bits" (per token, of the distribution that is sampled) and "accuracy".  ``classes``: one
+    class per stream for a class-conditional prior."""
     try:
         from . import fast_generate as fg, objective
     except ImportError:
@@ -451,8 +454,8 @@ def prior_score(prior, tokens, stages, K, start_pos=0):
     if t.is_floating_point() or t.dim() != 2 or t.size(1) <= rf:
         raise ValueError("prior_score: tokens must be (U, n > %d) integer tokens" % rf)
     t = t.to(next(prior.parameters()).device)
-    return objective.score(prior, t[:, :-1].to(torch.int32), t[:, rf:].to(torch.int64), windows=fg.stage_windows(int(stages), int(K)),
-                           window_pos=int(start_pos) + rf)
+    return objective.score(prior, t[:, :-1].to(torch.int32), t[:, rf:].to(torch.int64), classes=classes,
+                           windows=fg.stage_windows(int(stages), int(K)), window_pos=int(start_pos) + rf)
 
 
 def _checked_codes(t, B, n, Q, dev, what):

@@ -613,6 +613,57 @@ int wn_gcond_proj_bwd(const float* d_tab, int pair, const float* d_enf, const fl
     p.n_stages = n_stages; p.dd = dd; p.ch = ch; p.sd = sd; p.bw = bw; p.le = le; p.batch = batch;
     return wn_launch_gcond_proj_bwd(p, gcond_args(cls, gw_off, gstage_stride, gwf_off, emb_off, ge, n_cls), (hipStream_t)stream);
 }
+// ---- the global class term alone (wn_gcond.hip): the tables of a class-conditional WaveNet ----
+// wn_gcond_proj_*'s refusals that still apply (no bw, no le, no learned offsets); they need no pointer
+static int gclass_checked(const char* fn, int pair, int n_stages, int dd, int ch, int sd, int batch, int64_t gw_off, int64_t gstage_stride,
+                          int64_t gwf_off, int64_t emb_off, int ge, int n_cls) {
+    char msg[200];
+    const char* bad = nullptr;
+    if (batch < 0) bad = "'batch' must be >= 0";
+    else if (n_stages < 1) bad = "'n_stages' must be >= 1";
+    else if (dd < 1) bad = "'dd' must be >= 1";
+    else if (sd < 1) bad = "'sd' must be >= 1";
+    else if (ch < dd || ch % 32 != 0) bad = "'ch' must be a multiple of 32 and >= dd";
+    else if (pair && batch % 2 != 0) bad = "'batch' must be even for a table of clip pairs";
+    else if (ge < 1 || ge > WN_GCOND_MAX_CHANNELS) bad = "'ge' must lie in [1, 512]";
+    else if (n_cls < 1) bad = "'n_cls' must be >= 1";
+    else if (gw_off < 0) bad = "'gw_off' must be >= 0";
+    else if (gwf_off < 0) bad = "'gwf_off' must be >= 0";
+    else if (emb_off < 0) bad = "'emb_off' must be >= 0";
+    else if (n_stages > 1 && gstage_stride < (int64_t)2 * dd * ge) bad = "'gstage_stride' must be >= 2 * dd * ge (the stages' weights overlap)";
+    if (bad) {
+        snprintf(msg, sizeof(msg), "%s: argument %s", fn, bad);
+        return wn_set_error_msg(-4, msg);
+    }
+    return 0;
+}
+int wn_gclass_fwd(const float* flat, float* tab, float* tab_pair, float* enf, int n_stages, int dd, int ch, int sd, int batch,
+                  const int32_t* cls, int64_t gw_off, int64_t gstage_stride, int64_t gwf_off, int64_t emb_off, int ge, int n_cls,
+                  wn_stream_t stream) {
+    if (int rc = gclass_checked("wn_gclass_fwd", tab_pair != nullptr, n_stages, dd, ch, sd, batch, gw_off, gstage_stride, gwf_off, emb_off,
+                                ge, n_cls)) return rc;
+    if (batch == 0) return 0;
+    WN_REQUIRE("wn_gclass_fwd", flat, enf, cls);
+    if (!tab && !tab_pair) return wn_set_error_msg(-4, "wn_gclass_fwd: argument 'tab' or 'tab_pair' must not be NULL");
+    WnCondProj p;
+    memset(&p, 0, sizeof(p));
+    p.flat = flat; p.tab = tab; p.tab_pair = tab_pair; p.enf = enf;
+    p.n_stages = n_stages; p.dd = dd; p.ch = ch; p.sd = sd; p.bw = 1; p.le = 1; p.batch = batch;
+    return wn_launch_gclass_fwd(p, gcond_args(cls, gw_off, gstage_stride, gwf_off, emb_off, ge, n_cls), (hipStream_t)stream);
+}
+int wn_gclass_bwd(const float* d_tab, int pair, const float* d_enf, const float* flat, float* flat_grad, int n_stages, int dd, int ch,
+                  int sd, int batch, const int32_t* cls, int64_t gw_off, int64_t gstage_stride, int64_t gwf_off, int64_t emb_off, int ge,
+                  int n_cls, wn_stream_t stream) {
+    if (int rc = gclass_checked("wn_gclass_bwd", pair, n_stages, dd, ch, sd, batch, gw_off, gstage_stride, gwf_off, emb_off, ge, n_cls))
+        return rc;
+    if (batch == 0) return 0;
+    WN_REQUIRE("wn_gclass_bwd", d_tab, d_enf, flat, flat_grad, cls);
+    WnCondProj p;
+    memset(&p, 0, sizeof(p));
+    p.flat = flat; p.d_tab = d_tab; p.d_pair = pair ? 1 : 0; p.d_enf = d_enf; p.flat_grad = flat_grad;
+    p.n_stages = n_stages; p.dd = dd; p.ch = ch; p.sd = sd; p.bw = 1; p.le = 1; p.batch = batch;
+    return wn_launch_gclass_bwd(p, gcond_args(cls, gw_off, gstage_stride, gwf_off, emb_off, ge, n_cls), (hipStream_t)stream);
+}
 // ---- vector-quantised bottleneck (wn_vq.hip) ----
 static int vq_refused(const char* fn, const char* what) {
     char msg[200];

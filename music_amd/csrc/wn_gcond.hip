@@ -15,6 +15,12 @@
 // the loads each keeps in flight) - and the 16 waves' partials are added through LDS in wave order.  fp32 FMA, a fixed summation
 // order, no atomics: the same bits on every launch.  A class outside [0, n_cls) is never used as an index: the forward's columns of
 // that clip and its share of dG become NaN, d emb (which has no row for it) ignores the clip.
+//
+// The global term ALONE (wn_gclass_fwd / wn_gclass_bwd: a class-conditional WaveNet has no encoding, its tables one column per clip):
+//   forward    tab[.][b] = sum_e G[r][e] emb[cls[b]][e], the padding rows' zeros and enf in one launch: a thread per (table row, clip)
+//              runs cond_gemm_k's second reduction - e ascending from +0, one FMA each - so the bits are that kernel's       (gclass_fwd_k)
+//   dG         dG[r][e]  = sum_b d[r][b] emb[cls[b]][e], b ascending: a thread per (r, e), cond_gemm_k<1>'s dG tile            (gclass_dg_k)
+//   d emb      gcond_demb_k with le = 1
 #include "wn_condproj.h"
 
 namespace {
@@ -91,9 +97,72 @@ __global__ __launch_bounds__(GRC) void gcond_demb_k(WnCondProj p, WnGcond g) {
     }
 }
 
+// The global term alone, le = 1.  Thread (rt, b): row rt of the 2 ch rows of stage rt / (2 ch) - filter half first, as the tables
+// have them - or, behind the stages, row rt - n_stages 2 ch of enf; clips fastest, so that a wave reads few rows of G.
+__global__ __launch_bounds__(256) void gclass_fwd_k(WnCondProj p, WnGcond g, long total) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int b = (int)(idx % p.batch), rt = (int)(idx / p.batch), nt = p.n_stages * 2 * p.ch;
+    int i = p.n_stages, c = rt - nt, half = 0, cc = 0;
+    if (rt < nt) {
+        i = rt / (2 * p.ch);
+        const int rr = rt - i * 2 * p.ch;
+        half = rr / p.ch; cc = rr - half * p.ch;
+        c = half ? cc : p.dd + cc;                            // the reference's row: gate rows [0, dd), filter rows [dd, 2 dd)
+    }
+    float acc = 0.f;
+    if (i == p.n_stages || cc < p.dd) {
+        const float* gr = p.flat + g_row(p, g, i, c);
+        const long er = emb_row(g, b);
+        const float* em = p.flat + (er >= 0 ? er : 0);
+#pragma unroll 8
+        for (int e = 0; e < g.ge; ++e) acc = fmaf(gr[e], er >= 0 ? em[e] : __builtin_nanf(""), acc);
+    }
+    if (i == p.n_stages) { p.enf[(long)b * p.sd + c] = acc; return; }
+    if (p.tab) p.tab[((long)i * p.batch + b) * 2 * p.ch + half * p.ch + cc] = acc;
+    if (p.tab_pair) p.tab_pair[((long)i * (p.batch / 2) + (b >> 1)) * 4 * p.ch + half * 2 * p.ch + (b & 1) * p.ch + cc] = acc;
+}
+
+// dG: thread (r, e), e fastest (the embedding rows and the stores coalesce); clips in ascending order
+__global__ __launch_bounds__(256) void gclass_dg_k(WnCondProj p, WnGcond g, long total) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int e = (int)(idx % g.ge), r = (int)(idx / g.ge);
+    int i, c;
+    row_of(p, r, i, c);
+    const float* src = i == p.n_stages ? p.d_enf + c : p.d_tab + tab_row(p, p.d_pair, i, c);
+    float acc = 0.f;
+    for (int b = 0; b < p.batch; ++b) {
+        const float d = i == p.n_stages ? src[(long)b * p.sd] : src[tab_col(p, p.d_pair, b, 0)];
+        const long er = emb_row(g, b);
+        acc = fmaf(d, er >= 0 ? p.flat[er + e] : __builtin_nanf(""), acc);
+    }
+    p.flat_grad[g_row(p, g, i, c) + e] = acc;
+}
+
 }  // namespace
 
 // The callers (wn_api.hip) have checked the arguments.
+int wn_launch_gclass_fwd(const WnCondProj& p, const WnGcond& g, hipStream_t st) {
+    if (p.batch <= 0) return 0;
+    const long total = ((long)p.n_stages * 2 * p.ch + p.sd) * p.batch, blocks = (total + 255) / 256;
+    if (blocks > 0x7fffffffL) return wn_set_error_msg(-4, "wn_gclass_fwd: the tables have too many elements for one grid");
+    hipLaunchKernelGGL(gclass_fwd_k, dim3((unsigned)blocks), dim3(256), 0, st, p, g, total);
+    WN_CHECK_LAUNCH();
+    return 0;
+}
+
+int wn_launch_gclass_bwd(const WnCondProj& p, const WnGcond& g, hipStream_t st) {
+    if (p.batch <= 0) return 0;
+    const long total = ((long)p.n_stages * 2 * p.dd + p.sd) * g.ge, blocks = (total + 255) / 256;
+    if (blocks > 0x7fffffffL) return wn_set_error_msg(-4, "wn_gclass_bwd: the projections have too many elements for one grid");
+    hipLaunchKernelGGL(gclass_dg_k, dim3((unsigned)blocks), dim3(256), 0, st, p, g, total);
+    WN_CHECK_LAUNCH();
+    hipLaunchKernelGGL(gcond_demb_k, dim3((unsigned)g.n_cls), dim3(GRC), 0, st, p, g);
+    WN_CHECK_LAUNCH();
+    return 0;
+}
+
 int wn_launch_gcond_proj_fwd(const WnCondProj& p, const WnGcond& g, hipStream_t st) {
     if (p.batch <= 0) return 0;
     const long R = (long)p.n_stages * 2 * p.dd + p.sd, C = (long)p.batch * p.le;

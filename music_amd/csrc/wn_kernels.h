@@ -267,6 +267,9 @@ struct WnGcond {
 };
 int wn_launch_gcond_proj_fwd(const WnCondProj& p, const WnGcond& g, hipStream_t st);
 int wn_launch_gcond_proj_bwd(const WnCondProj& p, const WnGcond& g, hipStream_t st);
+// the global term alone (a class-conditional WaveNet): p with le = 1, its encoding, weights and biases unused
+int wn_launch_gclass_fwd(const WnCondProj& p, const WnGcond& g, hipStream_t st);
+int wn_launch_gclass_bwd(const WnCondProj& p, const WnGcond& g, hipStream_t st);
 // vector-quantised bottleneck (wn_vq.hip): the codebook [K][bw] sits at flat + cb_off (its gradient at flat_grad + cb_off)
 #define WN_VQ_PARTIALS 256
 #define WN_RVQ_MAX_S 8

@@ -19,19 +19,20 @@ from . import _lib
 from ._lib import call, ptr
 from .engine_base import SLACK, PAD_BACK, EngineBase, SlabPlan, WorkspaceHold, WorkspacePool, _Spec, _pad  # noqa: F401 (re-exported)
 from .packs import PackSet, causal_mats, epilogue_mats, gated_mats, pack_index, pack_positions, pair_mats  # noqa: F401 (pack_* re-exported)
-from .stack import EpiBias, GatedStack, SkipEpilogue
+from .stack import Cond, EpiBias, GatedStack, SkipEpilogue
 
 
 class WaveNetEngine(EngineBase):
     def __init__(self, dilations, residual_channels, dilation_channels, skip_channels,
                  quantization_channels=256, filter_width=2, use_bias=False,
-                 mode_fwd="f16x3", mode_bwd="bf16x3", device=None):
+                 mode_fwd="f16x3", mode_bwd="bf16x3", device=None, global_classes=0, global_channels=0):
         if filter_width != 2:
             raise NotImplementedError("HIP path implements filter_width == 2 (the reference's only configuration)")
         if quantization_channels != 256:
             raise NotImplementedError("HIP path implements quantization_channels == 256 (chunk softmax width)")
         self.dil = [int(d) for d in dilations]
         self.N = len(self.dil)
+        self.g_n, self.g_E = int(global_classes), int(global_channels)      # class-conditional: classes, embedding width (0, 0: off)
         self.R, self.D, self.S, self.Q = residual_channels, dilation_channels, skip_channels, quantization_channels
         self.fused_loss_ok = True           # model.py: nn.CrossEntropyLoss on the module's output may run as wn_chunk_softmax256_ce (Q = 256 here)
         self.use_bias = bool(use_bias)
@@ -79,7 +80,8 @@ class WaveNetEngine(EngineBase):
         bias = EpiBias([bn % (4 * i + 3) for i in range(self.N)], "post_process_1.bias", "post_process_2.bias", self._bias_ptr,
                        lambda name: ptr(self.gpack, self.gp_bias_off[name]),
                        [self.spec.off[bn % (4 * i + 3)] for i in range(self.N)]) if self.use_bias else None
-        self.epilogue = SkipEpilogue(self, ("skip", "p1", "p2"), ("U", "H", None, "dH"), self.CH, self.S, self.SP, self._fr, self._br,
+        # (class-conditional: h gains the class term as the second product's residual C1 - the three-launch forward, never the fused one)
+        self.epilogue = SkipEpilogue(self, ("skip", "p1", "p2"), ("U", "H", "C1" if self.gcond else None, "dH"), self.CH, self.S, self.SP, self._fr, self._br,
                                      self.mode_fwd, self.mode_bwd, bias=bias, fmark=self.fmark)
 
     def fmark(self, name):
@@ -103,8 +105,10 @@ class WaveNetEngine(EngineBase):
         names.append(("post_process_2.weight", (self.Q, self.S, 1)))
         if self.use_bias:
             names.append(("post_process_2.bias", (self.Q,)))
+        names += self.gclass_names(self.N, self.D, self.S, self.g_n, self.g_E)       # (class-conditional: the global block, last)
         self.spec = _Spec(names)
         self.param_names = [n for n, _ in names]
+        self._plan_gclass(self.g_n, self.g_E)
         dev = self.device
         self.flat = torch.zeros(self.spec.total, dtype=torch.float32, device=dev)
         self.flat_grad = torch.zeros(self.spec.total, dtype=torch.float32, device=dev)
@@ -163,7 +167,7 @@ class WaveNetEngine(EngineBase):
         self.gp_off, self.gp_bias_off = pk.gp_off, pk.gp_bias_off
         self.gpack = torch.zeros(pk.go, dtype=torch.float32, device=dev)
         gidx, ga, gb = pk.gather_maps()
-        assert (gidx >= 0).all()
+        assert (gidx[:self.n_gather] >= 0).all()               # (the global block: wn_gclass_bwd writes its gradients)
         self.gidx = torch.from_numpy(gidx.astype(np.int32)).to(dev)
         if self.pair_ok:
             # pair mode: the stack's weight gradients come out of the 64-channel block kernels as block-diagonal matrices -
@@ -190,6 +194,8 @@ class WaveNetEngine(EngineBase):
         ws["U"] = buf(self.SP)
         ws["H"] = buf(self.SP)
         ws["O"] = torch.zeros(B * self.Q * W + PAD_BACK, dtype=torch.float32, device=dev)
+        if self.gcond:
+            ws["C1"] = buf(self.SP)        # the output stage's class term, expanded over time
         ws["bwd"] = None
         # which backward blocks this workspace is planned for: decided ONCE here (slab layout, (P, Q) buffers, and whether
         # the forward has to store z on each block's whole range for the fallback backward) - a switch flipped later
@@ -238,7 +244,8 @@ class WaveNetEngine(EngineBase):
         # one-launch blocks whose dilation is a multiple of 32 hand dx on WHOLE (chain form of wn_resblock_bwd_pq: the Q rows
         # of an item are the carry of the next item of its chain); decided here, once per workspace, with the slab counts
         Bp = B // 2 if pair else B
-        want = os.environ.get("WN_PQ_CHAIN", "1") == "1"       # 0: every block hands the (P, Q) pair on (round 3's form)
+        # 0: every block hands the (P, Q) pair on (round 3's form); so do conditioned blocks (the chain form takes no table)
+        want = os.environ.get("WN_PQ_CHAIN", "1") == "1" and not self.gcond
         bw["chain"] = [want and bool(bw["pq"] or pair) and _lib.pq_chain_ok(self.off[i + 1], T, Bp, self.dil[i]) for i in range(self.N)]
         sfx = "2_" if pair else ""                            # pair mode: the block-diagonal gradient matrices of B / 2 clip pairs
         for i in range(self.N):
@@ -278,10 +285,45 @@ class WaveNetEngine(EngineBase):
         return ptr(ws["X"], SLACK + i * ws["B"] * self.CH * ws["pitch"])
 
     # ------------------------------------------------------------------ forward
-    def forward_logits(self, x, ws=None, codes=None):
+    def _gclass_tables(self, ws, cls, st):
+        """The clips' conditioning of one forward: every block's table [f; g]_i += G_i emb[c] and the output stage's h += G_f emb[c]
+        (one launch, wn_gclass_fwd), in the forms the autoencoder's decoder runs a table of <= 32 frames in (music_amd/model1.py) -
+        here ONE frame stretched over the block's whole range.  Returns i -> stack.Cond; fills ws["C1"]."""
+        B, T, W, pitch, N, CH = ws["B"], ws["T"], ws["W"], ws["pitch"], self.N, self.CH
+        pair, pair_f, dev = ws["pair"], ws["pair_fwd"], self.device
+        empty = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        # per clip for a 32-channel or unpaired forward, as clip pairs for the pair blocks (forward if pair_f, backward always)
+        tab_c = empty(N, B, 2 * CH) if not pair_f else None
+        tab = empty(N, B // 2, 4 * CH) if pair else tab_c
+        enf = empty(B, self.S)
+        self.gclass_fwd(cls, tab_c, tab if pair else None, enf, CH, st)
+        ws["tab"] = tab
+        CHp, Bp = (64, B // 2) if pair else (CH, B)
+        cpk = cix = None
+        if CHp == 64 and self.mode_fwd == _lib.F16X3:
+            # the conditioning bias on the matrix cores: the bucket of every sample as bytes (one frame: all 0; built once per
+            # workspace) and, per forward, the tables as packed A fragments ([2 CH rows][32 buckets] per block and clip)
+            if "cidx" not in ws:
+                ws["cidx"] = torch.zeros(N, _lib.COND_IDX_PAD + T + 64, dtype=torch.uint8, device=dev)
+                row, k = pack_positions(2 * CHp // 16, 1, False)
+                one = np.where(k < 1, row + k, -1).astype(np.int64)
+                base = np.arange(N * Bp, dtype=np.int64)[:, None] * (2 * CHp)
+                ws["ctab_idx"] = torch.from_numpy(np.where(one[None, :] >= 0, base + one[None, :], -1).astype(np.int32).reshape(-1)).to(dev)
+                ws["ctab_pk"] = torch.empty(N * Bp * 2 * CHp * 32 * 2, dtype=torch.int16, device=dev)
+            if pair_f or not pair:                        # (the backward blocks read the fp32 table; only a 64-channel forward the pack)
+                call("wn_pack_weights", ptr(tab), ptr(ws["ctab_idx"]), ptr(ws["ctab_pk"]), ws["ctab_idx"].numel(), self.mode_fwd, st)
+                cpk, cix = ws["ctab_pk"], ws["cidx"]
+        cpb = 2 * CHp * 32 * 2                          # halfs of one clip's packed table (hi + lo planes)
+        tab_f, n_f = (tab, Bp) if pair_f else (tab_c, B)
+        call("wn_cond_expand", ptr(enf), self.S, 1, self.S, self.rf - 1, T, 1, 1, W, ptr(ws["C1"], SLACK), self.SP * pitch, pitch, B, st)
+        return lambda i: Cond(ptr(tab_f[i]), tab_f.shape[2], 1, 1, T - self.off[i + 1],
+                              ptr(cpk, i * n_f * cpb) if cpk is not None else None, cpb, ptr(cix[i]) if cix is not None else None)
+
+    def forward_logits(self, x, ws=None, codes=None, classes=None):
         """x: (B,Q,T) float32 contiguous on the device.  Runs causal conv, the residual stack, the
         skip product and both post-process convs; leaves the pre-softmax (B,Q,W) in ws['O'].
-        codes = (int32 (B,T) device tensor, scrambled) instead of x: the one-hot is never built."""
+        codes = (int32 (B,T) device tensor, scrambled) instead of x: the one-hot is never built.
+        classes: one integer per clip of a class-conditional model (EngineBase.stage_classes), else None."""
         if x is None:
             B, T = codes[0].shape
             Q = self.Q
@@ -292,9 +334,11 @@ class WaveNetEngine(EngineBase):
         W = T - self.rf + 1
         if W <= 0:
             raise ValueError("wave sample not long enough")          # wavenet/model.py:100-101
+        cls = self.stage_classes(classes, B)
         ws = ws or self._ws.get(B, T)
         st = _lib.stream()
         CH, pitch, mf = self.CH, ws["pitch"], self.mode_fwd
+        ws["cls"] = cls
         self._gen += 1
         ws["gen"] = self._gen
         ws["x_in"] = x
@@ -313,16 +357,20 @@ class WaveNetEngine(EngineBase):
         # forward's z for dWd on the block's whole valid range [off_{i+1}, T) (19 % more z; it saves that path a second
         # copy written by its recompute kernel).
         z_whole = self.z_from_fwd and not ws["ms"] and not ws["pair"]      # (pair: the one-launch backward recomputes z)
-        self.stack.forward(B, T, pitch, ws["X"], ws["Z"], z_whole, st, pair=ws["pair_fwd"])
+        cond = None
+        if cls is not None:
+            cond = self._gclass_tables(ws, cls, st)
+            self.mark("gclass_fwd")
+        self.stack.forward(B, T, pitch, ws["X"], ws["Z"], z_whole, st, cond=cond, pair=ws["pair_fwd"])
         self.mark("stack_fwd")
         self.epilogue.forward(ws, self.epilogue.skip_bias(ws), st, self.epi_fused, int(self.epi_chains))
         self.mark("epilogue_fwd")
         return ws
 
-    def forward(self, x):
+    def forward(self, x, classes=None):
         """wavenet/model.py:86-145 -> probabilities (B*W, Q) (fresh tensor)."""
         self.pack_weights()
-        ws = self.forward_logits(x)
+        ws = self.forward_logits(x, classes=classes)
         B, W = ws["B"], ws["W"]
         probs = torch.empty(B * W, self.Q, dtype=torch.float32, device=self.device)
         call("wn_chunk_softmax256_fwd", ptr(ws["O"]), ptr(probs), B * W, _lib.stream())
@@ -335,17 +383,42 @@ class WaveNetEngine(EngineBase):
         bw = self._bwd_workspace(ws)
         st = _lib.stream()
         # (WN_EPI_BWD_ORDER=0: the skip weight gradient beside the stack, on the side stream)
-        self.epilogue.backward(self.epilogue.begin_backward(ws, bw), st, self.epi_fused_bwd and not self.use_bias,
-                               side_skip=os.environ.get("WN_EPI_BWD_ORDER", "1") != "1")
+        a = self.epilogue.begin_backward(ws, bw)
+        d_enf, after_dh = None, lambda: None
+        if ws.get("cls") is not None:        # the output stage's class term: d enf = the sum of dh over each clip's time
+            d_enf = torch.zeros(ws["B"], self.S, dtype=torch.float32, device=self.device)
+            after_dh = lambda: call("wn_cond_grad", a.dH, a.sb, a.pitch, self.S, self.rf - 1, a.T, 1, 1, a.W, ptr(d_enf), self.S, 1, a.B, st)
+        self.epilogue.backward(a, st, self.epi_fused_bwd and not self.use_bias, side_skip=os.environ.get("WN_EPI_BWD_ORDER", "1") != "1",
+                               after_dh=after_dh)
         self.mark("epilogue_bwd")
-        return self._backward_stack(ws, bw, st)
+        return self._backward_stack(ws, bw, st, d_enf)
 
-    def _backward_stack(self, ws, bw, st):
-        """The residual stack's backward, the causal layer's weight gradient and the slab reduction (second half of backward_from_dlogits)."""
+    def _backward_stack(self, ws, bw, st, d_enf=None):
+        """The residual stack's backward, the causal layer's weight gradient and the slab reduction (second half of backward_from_dlogits).
+        d_enf: the gradient of the output stage's class term (class-conditional), else None."""
         B, T, pitch, CH = ws["B"], ws["T"], ws["pitch"], self.CH
+        N, cls, cond, d_tab = self.N, ws.get("cls"), None, None
+        form = "pq" if bw["pq"] or bw["pair"] else "ms" if bw["ms"] else "rw"
+        if cls is not None:
+            # the block tables' gradients, sums of [df; dg] over each clip's time: inside the one-launch block as bucket sums (one
+            # bucket) reduced behind the stack, else wn_cond_grad on the [df; dg] the block wrote - as the autoencoder's decoder
+            Bp, rows = (B // 2, 4 * CH) if bw["pair"] else (B, 2 * CH)
+            d_tab = torch.zeros(N, Bp, rows, dtype=torch.float32, device=self.device)
+            if form == "pq" and "cslab" not in bw:
+                import ctypes
+                fl = [_lib.load().wn_resblock_bwd_pq_cond_floats(self.off[i + 1], T, Bp) for i in range(N)]
+                bw["cs_off"] = (ctypes.c_int64 * N)(*np.concatenate([[0], np.cumsum(fl)[:-1]]).tolist())
+                bw["cs_tlo"] = (ctypes.c_int * N)(*[self.off[i + 1] for i in range(N)])
+                bw["cslab"] = torch.empty(sum(fl), dtype=torch.float32, device=self.device)
+
+            def cond(i):
+                mc = dict(cidx=ptr(ws["cidx"][i]), cslab=ptr(bw["cslab"], bw["cs_off"][i])) if form == "pq" else {}
+                return Cond(ptr(ws["tab"][i]), rows, 1, 1, T - self.off[i + 1], **mc)
 
         def bias_grads(i, dfg, dy, t_lo, s_):
-            """row sums of [df;dg] and of dy: the gradients of block i's three biases"""
+            """row sums of [df;dg] and of dy: the gradients of block i's three biases (and of its class table)"""
+            if cls is not None:
+                call("wn_cond_grad", dfg, 2 * CH * pitch, pitch, 2 * CH, t_lo, T, 1, 1, T - t_lo, ptr(d_tab[i]), 2 * CH, 1, B, s_)
             if self.use_bias:
                 bo, bn = self.gp_bias_off, "dilation_layer_stack.%d.bias"
                 call("wn_bias_grad", dfg, 2 * CH * pitch, pitch, 0, self.D, t_lo, T, B, ptr(self.gpack, bo[bn % (4 * i)]), s_)
@@ -354,10 +427,13 @@ class WaveNetEngine(EngineBase):
                     call("wn_bias_grad", dy, CH * pitch, pitch, 0, self.R, t_lo, T, B, ptr(self.gpack, bo[bn % (4 * i + 2)]), s_)
         # The per-layer weight-gradient products of the fallback form only feed the slab reduction at the very end, so they run on the
         # side stream next to the data-gradient chain (resblock_bwd -> dx product -> next block); dfg / z scratch is double-buffered for that.
-        form = "pq" if bw["pq"] or bw["pair"] else "ms" if bw["ms"] else "rw"
         self.stack.backward(form, B, T, pitch, ws["X"], ws["Z"], bw, bw["dX"], st, chain=bw["chain"], dfg=bw["dfg"],
-                            zs=None if self.z_from_fwd else bw["zs"], pair=bw["pair"], hook=bias_grads)
+                            zs=None if self.z_from_fwd else bw["zs"], cond=cond, pair=bw["pair"], hook=bias_grads)
+        if cls is not None and form == "pq":
+            call("wn_resblock_bwd_pq_cond_reduce", ptr(bw["cslab"]), bw["cs_off"], bw["cs_tlo"], N, T, Bp, 1, ptr(d_tab), Bp * rows, rows, 1, st)
         self.join_side()              # everything on the side stream (epilogue weight gradients)
+        if cls is not None:           # behind the last table gradient: the global block's own, flat_grad's tail
+            self.gclass_bwd(cls, d_tab, bw["pair"], d_enf, CH, st)
         self.mark("stack_bwd")
         # causal weight gradient: dWc[r][q][tap] = sum dx0[r][t] in[q][t-1+tap]
         dx0 = ptr(bw["dX"][0], SLACK)
@@ -389,24 +465,26 @@ class WaveNetEngine(EngineBase):
         self.backward_from_dlogits(ws)
 
     # ------------------------------------------------------------------ fused training step
-    def loss_and_grad_codes(self, codes, target, scrambled=True, want_probs=False, objective=None, windows=None, window_pos=None):
+    def loss_and_grad_codes(self, codes, target, scrambled=True, want_probs=False, objective=None, windows=None, window_pos=None,
+                            classes=None):
         """loss_and_grad on the integer codes themselves (int32 (B,T) on the device; `scrambled` = the loader's one-hot
         layout, faster_audio_data.py:77-81): same result as loss_and_grad(self.onehot(codes, scrambled), target), but the
         (B,256,T) float tensor is never built, written or read - the causal layer is a gather forward and
         a scatter backward."""
         return self.loss_and_grad(None, target, want_probs, codes=(codes, scrambled), objective=objective, windows=windows,
-                                  window_pos=window_pos)
+                                  window_pos=window_pos, classes=classes)
 
-    def loss_and_grad(self, x, target, want_probs=False, codes=None, objective=None, windows=None, window_pos=None):
+    def loss_and_grad(self, x, target, want_probs=False, codes=None, objective=None, windows=None, window_pos=None, classes=None):
         """forward + CrossEntropyLoss(probs, target) + backward (wavenet/train.py:178-181).
         Returns the loss as a 0-d device tensor; gradients land in self.flat_grad.  objective: None = self.objective
         (EngineBase; "nll" = the negative log-likelihood under the per-timestep softmax instead of the reference's loss).  windows /
-        window_pos: the position windows of "nll" (EngineBase.step_nll; None = self.nll_windows)."""
+        window_pos: the position windows of "nll" (EngineBase.step_nll; None = self.nll_windows).  classes: forward_logits'."""
         def step():
             self.mark("begin")
             self.pack_weights()
             self.mark("pack")
-            return self._fused_tail(self.forward_logits(x, codes=codes), target, want_probs, objective, windows, window_pos)
+            return self._fused_tail(self.forward_logits(x, codes=codes, classes=classes), target, want_probs, objective, windows,
+                                    window_pos)
         return self._throttled(step)
 
     def softmax_ce(self, *args):

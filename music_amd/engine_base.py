@@ -577,6 +577,39 @@ class EngineBase:
             return call("wn_gcond_proj_bwd", *args, *self._gcond_args(cls), st)
         call("wn_cond_proj_bwd", *args, st)
 
+    # ------------------------------------------------------------------ class-conditional WaveNet (the two WaveNet engines)
+    @staticmethod
+    def gclass_names(N, D, S, n, E):
+        """(name, shape) of the global block of a class-conditional WaveNet, in the order it ends the flat buffer"""
+        return ([("gcond_layer_stack.%d.weight" % i, (2 * D, E, 1)) for i in range(N)] + [("connection_gcond.weight", (S, E, 1))] +
+                [("global_embedding.weight", (n, E))]) if n > 0 else []
+
+    def _plan_gclass(self, n, E):
+        """Where wn_gclass_fwd / wn_gclass_bwd find G_i (2 D x E, gate rows first), G_f (S x E) and the embedding (n x E): the tail
+        of flat / flat_grad, behind everything the model has without them (self.D, self.S: the engine's channel counts)."""
+        self.gcond = n > 0
+        if not self.gcond:
+            return
+        o, N = self.spec.off, len(self.dil)
+        self.g_E, self.g_n = E, n
+        gw0, gwf, emb = o["gcond_layer_stack.0.weight"], o["connection_gcond.weight"], o["global_embedding.weight"]
+        gstride = 2 * self.D * E
+        assert all(o["gcond_layer_stack.%d.weight" % i] == gw0 + i * gstride for i in range(N)) and gwf == gw0 + N * gstride \
+            and emb == gwf + self.S * E and emb + n * E == self.spec.total
+        self.gcond_off = (gw0, gstride, gwf, emb)
+        self.n_gcond = self.spec.total - gw0
+
+    def gclass_fwd(self, cls, tab, tab_pair, enf, ch, st):
+        """Every block's table (per clip and / or as clip pairs, padding rows included; one column per clip) and the output stage's
+        enf (B, S) of the clips' classes, in one launch"""
+        call("wn_gclass_fwd", ptr(self.flat), ptr(tab), ptr(tab_pair), ptr(enf), len(self.dil), self.D, ch, self.S, cls.numel(),
+             *self._gcond_args(cls), st)
+
+    def gclass_bwd(self, cls, d_tab, pair, d_enf, ch, st):
+        """dG_i, dG_f and every row of d emb into the tail of flat_grad, from the tables' gradients"""
+        call("wn_gclass_bwd", ptr(d_tab), 1 if pair else 0, ptr(d_enf), ptr(self.flat), ptr(self.flat_grad), len(self.dil), self.D, ch,
+             self.S, cls.numel(), *self._gcond_args(cls), st)
+
     # ------------------------------------------------------------------ the second stream
     def _side_stream(self):
         """THE side stream of this device (_lib.side_stream: high priority = a hardware queue of its own), created at first use."""

@@ -30,9 +30,10 @@ from .plan_generic import GeneralPlan, PackBuilder, Pass
 
 class GenericWaveNetEngine(GeneralPlan):
     def __init__(self, dilations, residual_channels, dilation_channels, skip_channels, quantization_channels=256,
-                 filter_width=2, use_bias=False, mode_fwd="f16x3", mode_bwd="bf16x3", device=None):
+                 filter_width=2, use_bias=False, mode_fwd="f16x3", mode_bwd="bf16x3", device=None, global_classes=0, global_channels=0):
         self.dil = [int(d) for d in dilations]
         self.k = int(filter_width)
+        self.g_n, self.g_E = int(global_classes), int(global_channels)
         self._geometry()
         self.R, self.D, self.S, self.Q = residual_channels, dilation_channels, skip_channels, quantization_channels
         self.use_bias = bool(use_bias)
@@ -63,8 +64,10 @@ class GenericWaveNetEngine(GeneralPlan):
         names.append(("post_process_2.weight", (self.Q, self.S, 1)))
         if self.use_bias:
             names.append(("post_process_2.bias", (self.Q,)))
+        names += self.gclass_names(self.N, self.D, self.S, self.g_n, self.g_E)       # (class-conditional: the global block, last)
         self.spec = _Spec(names)
         self.param_names = [n for n, _ in names]
+        self._plan_gclass(self.g_n, self.g_E)
         self.flat = torch.zeros(self.spec.total, dtype=torch.float32, device=self.device)
         self.flat_grad = torch.zeros(self.spec.total, dtype=torch.float32, device=self.device)
 
@@ -94,7 +97,7 @@ class GenericWaveNetEngine(GeneralPlan):
         pb.conv_1("post_process_1.weight", "p1", S, SP, S, SP)
         pb.conv_1("post_process_2.weight", "p2", Q, QP, S, SP)
         if self.use_bias:
-            pb.bias_rows([n for n in self.param_names if n.endswith(".bias")], {})
+            pb.bias_rows([n for n in self.gathered_param_names if n.endswith(".bias")], {})
         # [f | g] bias rows of every layer in the padded row order of the fg product, gathered from the flat buffer
         self._finish_packs(pb, [[(bn % (4 * i), np.arange(D)), (bn % (4 * i + 1), g_rows)] for i in range(N)], 2 * DP)
 
@@ -107,16 +110,29 @@ class GenericWaveNetEngine(GeneralPlan):
         return ws
 
     # ------------------------------------------------------------------ forward
-    def forward_logits(self, x, ws=None):
+    def forward_logits(self, x, ws=None, classes=None):
+        """classes: one integer per clip of a class-conditional model (EngineBase.stage_classes), else None"""
         B, Q, T = x.shape
         assert Q == self.Q and x.is_contiguous() and x.dtype == torch.float32 and x.is_cuda
         W = T - self.rf + 1
         if W <= 0:
             raise ValueError("wave sample not long enough")          # wavenet/model.py:100-101
+        cls = self.stage_classes(classes, B)
         ws = ws or self._ws.get(B, T)
         N, RP, DP, SP, QP, pitch = self.N, self.RP, self.DP, self.SP, self.QP, ws["pitch"]
         xin_p, xin_bs = self._stage_input(ws, x)
         ps = Pass(self, ws)
+        ws["cls"] = cls
+        cond, cond_f = (lambda i: None), None
+        if cls is not None:
+            # the clips' tables, one column each: [f; g]_i += G_i emb[c] and h += G_f emb[c], constant over time - a table of one
+            # frame stretched over the block's whole valid range (mode 1, q = its length)
+            tab = torch.empty(N, B, 2 * DP, dtype=torch.float32, device=self.device)
+            enf = torch.empty(B, self.S, dtype=torch.float32, device=self.device)
+            self.gclass_fwd(cls, tab, None, enf, DP, ps.st)
+            cond = lambda i: (ptr(tab[i]), 2 * DP, 1, 1, T - self.off[i + 1])
+            cond_f = (ptr(enf), self.S, 1, 1, W)
+            self.mark("gclass_fwd")
         x_ = lambda i: self._lay(ws, "X", i, RP)
         k0, lo, zb = self.k - 1, self.rf - 1, N * DP * pitch
         # causal conv (model.py:104): x0[t] = sum_j Wc_j in[t - (k-1-j)]
@@ -127,7 +143,7 @@ class GenericWaveNetEngine(GeneralPlan):
             # [f; g] = sum_j [Wf_j; Wg_j] x_i[t - (k-1-j) d] (model.py:118-119), gate (:120), x_{i+1} = Wd z + x_i[t] (:121-124)
             ps.gated_fwd("fg%d" % i, "d%d" % i, x_(i), x_(i + 1) if i < N - 1 else None, RP, self.R, self._lay(ws, "FG", i, 2 * DP),
                          ptr(ws["Z"], SLACK + i * DP * pitch), zb, DP, d, self.off[i], self.off[i + 1],
-                         ptr(self.bfg, i * 2 * DP) if self.use_bias else None, self._bias_ptr(bn % (4 * i + 2)))
+                         ptr(self.bfg, i * 2 * DP) if self.use_bias else None, self._bias_ptr(bn % (4 * i + 2)), cond(i))
         self.mark("stack_fwd")
         bias_s = None
         if self.use_bias:
@@ -135,14 +151,14 @@ class GenericWaveNetEngine(GeneralPlan):
             bias_s = ptr(ws["bias_skip"])
         ps.epilogue_fwd("p1", "p2", ptr(ws["Z"], SLACK), zb, N * DP, ptr(ws["U"], SLACK), ptr(ws["H"], SLACK), SP, self.S,
                         ptr(ws["O"]), QP, Q, W, lo, bias_s, self._bias_ptr("post_process_1.bias"),
-                        self._bias_ptr("post_process_2.bias"))                                     # model.py:127-138
+                        self._bias_ptr("post_process_2.bias"), cond_f)                             # model.py:127-138
         self.mark("epilogue_fwd")
         return ws
 
-    def forward(self, x):
+    def forward(self, x, classes=None):
         """wavenet/model.py:86-145 -> probabilities (B*W, Q) (fresh tensor)."""
         self.pack_weights()
-        ws = self.forward_logits(x)
+        ws = self.forward_logits(x, classes=classes)
         B, W = ws["B"], ws["W"]
         probs = torch.empty(B * W, self.Q, dtype=torch.float32, device=self.device)
         self.softmax_fwd(ws["O"], probs, B * W)
@@ -166,10 +182,17 @@ class GenericWaveNetEngine(GeneralPlan):
         self._check_input_unchanged(ws)
         ps = Pass(self, ws, bw)
         bn = "dilation_layer_stack.%d.bias"
-        # ---- epilogue: o = P2 relu(h), h = P1 relu(u), u = sum_i Ws_i z_i
+        cls, cond, cond_f = ws.get("cls"), (lambda i: None), None
+        if cls is not None:                      # the tables' gradients: sums of [df; dg] and of dh over each clip's time
+            B = ws["B"]
+            d_tab = torch.zeros(N, B, 2 * DP, dtype=torch.float32, device=self.device)
+            d_enf = torch.zeros(B, self.S, dtype=torch.float32, device=self.device)
+            cond = lambda i: (ptr(d_tab[i]), 2 * DP, 1, 1, T - self.off[i + 1])
+            cond_f = (ptr(d_enf), self.S, 1, 1, W)
+        # ---- epilogue: o = P2 relu(h), h = P1 relu(u) (+ the class term), u = sum_i Ws_i z_i
         ps.epilogue_bwd("p1", "p2", ptr(bw["dO"]), ptr(bw["dH"], SLACK), ptr(bw["dU"], SLACK), ptr(bw["dZ"], SLACK),
                         ptr(ws["Z"], SLACK), zb, N * DP, ptr(ws["U"], SLACK), ptr(ws["H"], SLACK), SP, self.S, QP, Q, W, lo,
-                        [bn % (4 * i + 3) for i in range(N)], "post_process_1.bias", "post_process_2.bias")
+                        [bn % (4 * i + 3) for i in range(N)], "post_process_1.bias", "post_process_2.bias", cond_f)
         self.mark("epilogue_bwd")
         dX = [ptr(t, SLACK) for t in bw["dX"]]
         for i in range(N - 1, -1, -1):
@@ -177,7 +200,9 @@ class GenericWaveNetEngine(GeneralPlan):
                          dX[(i + 1) % 2] if i < N - 1 else None, dX[i % 2], RP, self.R, self._lay(ws, "FG", i, 2 * DP),
                          ptr(ws["Z"], SLACK + i * DP * pitch), ptr(bw["dZ"], SLACK + i * DP * pitch), zb, DP, self.dil[i],
                          self.off[i], self.off[i + 1], lo, [(bn % (4 * i), 0, self.D), (bn % (4 * i + 1), DP, self.D)],
-                         bn % (4 * i + 2))
+                         bn % (4 * i + 2), cond(i))
+        if cls is not None:                      # behind the last table gradient: the global block's own, flat_grad's tail
+            self.gclass_bwd(cls, d_tab, False, d_enf, DP, ps.st)
         self.mark("stack_bwd")
         xin_p, xin_bs = ws["xin"]
         ps.conv_k_bwd("causal", dX[0], RP * pitch, RP, 1, k0, xin_p, xin_bs, T, QP)
@@ -189,18 +214,20 @@ class GenericWaveNetEngine(GeneralPlan):
         return self._causal_input_grad(ws, [("causalT", self.RP, "dX")])
 
     # ------------------------------------------------------------------ fused training step (wavenet/train.py:178-181)
-    def _step_forward(self, x):
+    def _step_forward(self, x, classes=None):
         self.mark("begin")
         self.pack_weights()
-        return self.forward_logits(x)
+        return self.forward_logits(x, classes=classes)
 
-    def loss_and_grad(self, x, target, want_probs=False, objective=None, windows=None, window_pos=None):
-        """objective: None = self.objective (EngineBase); windows / window_pos: step_nll's"""
-        return self._throttled(lambda: self._fused_tail(self._step_forward(x), target, want_probs, objective, windows, window_pos))
+    def loss_and_grad(self, x, target, want_probs=False, objective=None, windows=None, window_pos=None, classes=None):
+        """objective: None = self.objective (EngineBase); windows / window_pos: step_nll's; classes: as in forward_logits"""
+        return self._throttled(lambda: self._fused_tail(self._step_forward(x, classes), target, want_probs, objective, windows,
+                                                       window_pos))
 
-    def loss_and_grad_codes(self, codes, target, scrambled=True, want_probs=False, objective=None, windows=None, window_pos=None):
+    def loss_and_grad_codes(self, codes, target, scrambled=True, want_probs=False, objective=None, windows=None, window_pos=None,
+                            classes=None):
         """the fast engine's entry point on integer codes; here the one-hot is built (wn_onehot) and the dense path runs"""
-        return self.loss_and_grad(self.onehot(codes, scrambled), target, want_probs, objective, windows, window_pos)
+        return self.loss_and_grad(self.onehot(codes, scrambled), target, want_probs, objective, windows, window_pos, classes)
 
     def onehot(self, codes, scrambled=True):
         """int32 (B,T) codes on the device -> float32 (B,Q,T) (faster_audio_data.py:62-83)."""

@@ -366,6 +366,44 @@ def _first_in_window(probs, win):
     return torch.from_numpy(lo + np.argmax(probs.detach().float().cpu().numpy()[:, lo:hi], axis=1)).to(probs.device)
 
 
+def _check_classes(net, classes):
+    """classes are refused by a model without the mode (or without the notion) and required by one with it, before any launch"""
+    check = getattr(net, "check_classes", None)
+    if check is not None:
+        check(classes)
+    elif classes is not None:
+        raise ValueError("music_amd.fast_generate: this model takes no classes, pass classes=None")
+
+
+def _class_cond(net, eng, classes, U, correct_queue):
+    """The conditioning arguments of a class-conditional WaveNet's decode launch (None with the mode off): the U utterances' tables
+    - cond_fg (U, N, 1, 2 Dp) rows [f | g], cond_p1 (U, 1, S) - built on the device from wn_gclass_fwd's output, under a schedule
+    of one frame that every position reads.  Classes are refused with the mode off and required with it on (EngineBase.stage_classes);
+    corrected recurrence only.  Returns (wn_decode_batch_cond's eight table arguments, the tensors they point into)."""
+    if classes is None and not getattr(eng, "gcond", False):
+        return None, None
+    cls = eng.stage_classes(classes, U)
+    if cls is None:
+        return None, None
+    if not correct_queue:
+        raise ValueError("a class-conditional model decodes on the corrected recurrence only (wn_decode_batch_cond): pass "
+                         "correct_queue=True")
+    pack = _pack_for(net, eng)
+    N, D, S, Dp, dev = eng.N, eng.D, eng.S, pack.Dp, eng.device
+    ch = -(-D // 32) * 32                                         # the table's rows per half: D padded to 32
+    tab = torch.empty(N, U, 2 * ch, dtype=torch.float32, device=dev)
+    enf = torch.empty(U, S, dtype=torch.float32, device=dev)
+    eng.gclass_fwd(cls, tab, None, enf, ch, _lib.stream())
+    cond_fg = torch.zeros(U, N, 1, 2 * Dp, dtype=torch.float32, device=dev)
+    cond_fg[:, :, 0, :D] = tab[:, :, :D].transpose(0, 1)
+    cond_fg[:, :, 0, Dp:Dp + D] = tab[:, :, ch:ch + D].transpose(0, 1)
+    cond_p1 = enf.view(U, 1, S)
+    shift = (ctypes.c_int32 * (N + 1))(*([0] * (N + 1)))          # one frame, the tile rule: every position reads frame 0
+    qs = (ctypes.c_int32 * (N + 1))(*([0] * (N + 1)))
+    cond = (ptr(cond_fg), cond_fg[0].numel(), ptr(cond_p1), S, ctypes.cast(shift, ctypes.c_void_p), ctypes.cast(qs, ctypes.c_void_p), 1, 0)
+    return cond, (cond_fg, cond_p1, shift, qs)
+
+
 def _pack_for(net, eng):
     """The decode weight pack of `eng`, kept on the net (built on first use; refreshed by the launcher)."""
     pack = getattr(net, "_decode_pack", None)
@@ -428,7 +466,7 @@ def _launch_decode(net, eng, smp, rings, note0, prev0, U, n_steps, step0, push_i
 
 
 def _decode(net, state, note0, n_steps, forced=None, want_probs=False, correct_queue=False, temperature=None, seed=0,
-            top_k=None, top_p=None, win=None):
+            top_k=None, top_p=None, win=None, cond=None):
     eng = state.eng
     _check_recurrence(eng, correct_queue)
     smp = _Sampling(1, temperature, top_k, top_p, seed, None, eng.device)
@@ -444,7 +482,7 @@ def _decode(net, state, note0, n_steps, forced=None, want_probs=False, correct_q
     codes, probs, note_out, prev_out = _launch_decode(
         net, eng, smp, state.rings, note0, state.prev, 1, n_steps, state.steps, 1 if correct_queue else 0,
         "wn_decode: a hand-off between the two decode workgroups timed out", check=n_steps >= 4, forced=forced,
-        want_probs=want_probs, sync=sync, win=win)
+        want_probs=want_probs, sync=sync, win=win, cond=cond)
     state.prev = prev_out.view(-1)
     state.steps += n_steps
     return codes[0], probs[0] if want_probs else None, note_out[0]
@@ -461,13 +499,13 @@ def _rings_from_workspace(eng, U, T):
                       for i, d in enumerate(eng.dil)], 1).contiguous()
 
 
-def _init_forward(net, note):
+def _init_forward(net, note, classes=None):
     """The full forward over a ``(1, Q, receptive_field)`` piece: (probabilities (1, Q), the queues it leaves)."""
     assert note.size()[2] == net.receptive_field
     dev = note.device if note.is_cuda else torch.device("cuda")
     x = note.detach().to(dev).float().contiguous()
     with torch.no_grad():
-        probs = net(x)                                            # (1, Q): W == 1
+        probs = net(x) if classes is None else net(x, classes=classes)     # (1, Q): W == 1
     eng, T, K1 = net._engine, x.size(2), _taps(net._engine)
     # the causal layer's queue = the last k-1 input columns
     return probs, DecodeState(eng, _rings_from_workspace(eng, 1, T)[0], x[0, :, T - K1:T].t().contiguous().view(-1), 0)
@@ -489,7 +527,7 @@ def predict_next(net, note, state_queue=None, correct_queue=False):
 
 
 def generate_codes(net, start_piece, note_num, correct_queue=False, temperature=None, seed=0, top_k=None, top_p=None,
-                   windows=None, window_pos=0):
+                   windows=None, window_pos=0, classes=None):
     """The greedy loop of fast_generate.py:162-172 as one init forward + ONE persistent launch.
     Returns the note_num generated codes (int64, on the device).
     ``temperature`` (the reference is greedy only): if given and > 0, every code after the
@@ -499,26 +537,30 @@ def generate_codes(net, start_piece, note_num, correct_queue=False, temperature=
     ``windows`` / ``window_pos``: 1..16 ``(lo, hi)`` pairs and the stream position of the first code returned; the code at
     position p is chosen inside pair ``p % len(windows)`` only, renormalised there (include/wavenet_hip.h,
     wn_win_decode_batch; ``stage_windows`` for a residual quantiser's token stream).  The first code is the first-index argmax
-    of the init forward inside its window.  Corrected recurrence only."""
+    of the init forward inside its window.  Corrected recurrence only.
+    ``classes``: ``[c]``, the class to generate as, for a class-conditional model (required there, refused elsewhere): the init
+    forward runs with it and the launch is the conditioned one (wn_decode_batch_cond).  Corrected recurrence only."""
     win = _windows_of(windows, window_pos, net.quantization_channels)
     _need_corrected_win(win, correct_queue)
+    _check_classes(net, classes)
     with torch.no_grad():
-        if win is None:
+        if win is None and classes is None:
             first, state = predict_next(net, start_piece, None)
         else:
-            probs, state = _init_forward(net, start_piece)
-            first = _first_in_window(probs.view(1, -1), win)
+            probs, state = _init_forward(net, start_piece, classes)
+            first = probs.view(1, -1).argmax(1) if win is None else _first_in_window(probs.view(1, -1), win)
+    cond, keep = _class_cond(net, state.eng, classes, 1, correct_queue)
     if note_num <= 1:
         return first.to(state.eng.device)[:note_num]
     note0 = torch.zeros(net.quantization_channels, dtype=torch.float32, device=state.eng.device)
     note0[int(first[0])] = 1.0
     codes, _, _ = _decode(net, state, note0, note_num - 1, correct_queue=correct_queue, temperature=temperature, seed=seed,
-                          top_k=top_k, top_p=top_p, win=win.tail(1) if win is not None else None)
+                          top_k=top_k, top_p=top_p, win=win.tail(1) if win is not None else None, cond=cond)
     return torch.cat([first.to(codes.device).to(torch.int64), codes.to(torch.int64)])
 
 
 def generate_codes_batch(net, start_pieces, note_num, correct_queue=False, temperature=None, seed=0, top_k=None, top_p=None,
-                         streams=None, windows=None, window_pos=0):
+                         streams=None, windows=None, window_pos=0, classes=None):
     """SURVEY 8f2 (batched utterances; the reference generates one at a time): greedy generation of
     ``note_num`` codes for U independent start pieces ``(U, Q, receptive_field)`` in ONE persistent
     launch - on the matrix-core path eight utterances to a workgroup pair, one pair of MFMA result columns each (else one
@@ -528,8 +570,10 @@ def generate_codes_batch(net, start_pieces, note_num, correct_queue=False, tempe
     over one prompt, N takes of one prompt); ``streams``: the random-number stream id of every utterance (default: its
     index; row u is then the single-utterance launch with ``streams=[u]``, bit for bit when both run the same kernel form,
     see WN_DEC_KS).  Truncation and per-utterance settings run on the corrected recurrence only.
-    ``windows`` / ``window_pos``: as in ``generate_codes``; one table and one position for the whole launch."""
+    ``windows`` / ``window_pos``: as in ``generate_codes``; one table and one position for the whole launch.
+    ``classes``: one class per utterance for a class-conditional model, every utterance with its own tables."""
     assert start_pieces.dim() == 3 and start_pieces.size(2) == net.receptive_field
+    _check_classes(net, classes)
     win = _windows_of(windows, window_pos, net.quantization_channels)
     _need_corrected_win(win, correct_queue)
     U = start_pieces.size(0)
@@ -538,8 +582,9 @@ def generate_codes_batch(net, start_pieces, note_num, correct_queue=False, tempe
     dev = start_pieces.device if start_pieces.is_cuda else torch.device("cuda")
     x = start_pieces.detach().to(dev).float().contiguous()
     with torch.no_grad():
-        probs = net(x)                                            # (U, Q): W == 1
+        probs = net(x) if classes is None else net(x, classes=classes)     # (U, Q): W == 1
     eng = net._engine
+    cond, keep = _class_cond(net, eng, classes, U, correct_queue)
     T, Q, K1 = x.size(2), eng.Q, _taps(eng)
     rings = _rings_from_workspace(eng, U, T)
     first = probs.view(U, Q).argmax(1) if win is None else _first_in_window(probs.view(U, Q), win)
@@ -553,7 +598,7 @@ def generate_codes_batch(net, start_pieces, note_num, correct_queue=False, tempe
     prev0 = x[:, :, T - K1:T].transpose(1, 2).contiguous()         # [U][k-1][Q], oldest column first
     codes, _, _, _ = _launch_decode(net, eng, smp, rings, note0, prev0, U, note_num - 1, 0, 1 if correct_queue else 0,
                                     "wn_decode_batch: a hand-off between two decode workgroups timed out", check=note_num - 1 >= 4,
-                                    win=win.tail(1) if win is not None else None)
+                                    win=win.tail(1) if win is not None else None, cond=cond)
     return torch.cat([first.view(U, 1).to(torch.int64), codes.to(torch.int64)], 1)
 
 
@@ -636,9 +681,10 @@ def sample_logits(logits, temperature=1.0, top_k=None, top_p=None, seed=0, step0
 
 
 def generate(model_path, model_name, generate_path, generate_name, start_piece=None, sr=16000, duration=10, temperature=None,
-             seed=0, top_k=None, top_p=None):
+             seed=0, top_k=None, top_p=None, classes=None):
     """wavenet/fast_generate.py:144-179.  ``temperature`` / ``top_k`` / ``top_p`` / ``seed``: sample instead of the greedy
-    argmax; a filter selects the corrected queue recurrence (the only one truncated sampling runs on)."""
+    argmax; a filter selects the corrected queue recurrence (the only one truncated sampling runs on).  ``classes``: ``[c]``, the
+    class to generate as (a model whose parameters set "global_classes"; corrected recurrence)."""
     if os.path.exists(generate_path) is False:
         os.makedirs(generate_path)
     with open('./params/wavenet_params.json', 'r') as f:
@@ -654,8 +700,9 @@ def generate(model_path, model_name, generate_path, generate_name, start_piece=N
         start_piece[:, Q // 2, :] = 1.0
     # the as-written queue push exists for filter_width 2 only; every other width runs the corrected recurrence
     generated_piece = generate_codes(net, start_piece.cuda(), duration * sr,
-                                     correct_queue=net.filter_width != 2 or top_k is not None or top_p is not None,
-                                     temperature=temperature, seed=seed, top_k=top_k, top_p=top_p)
+                                     correct_queue=(net.filter_width != 2 or top_k is not None or top_p is not None
+                                                    or classes is not None),
+                                     temperature=temperature, seed=seed, top_k=top_k, top_p=top_p, classes=classes)
     print(generated_piece.tolist()[:32], "...")
     audio = mu_law_decode(generated_piece, net.quantization_channels).cpu().numpy()
     from scipy.io import wavfile

@@ -13,11 +13,11 @@ import torch
 import torch.nn as nn
 
 try:
-    from . import _losshook
+    from . import _lib, _losshook
     from .engine import WaveNetEngine, WorkspaceHold
     from .engine_generic import GenericWaveNetEngine
 except ImportError:                      # imported as a bare module (`from model import wavenet`)
-    from music_amd import _losshook
+    from music_amd import _lib, _losshook
     from music_amd.engine import WaveNetEngine, WorkspaceHold
     from music_amd.engine_generic import GenericWaveNetEngine
 
@@ -26,7 +26,7 @@ _Probs = _losshook.Probs                 # the type of the module's output while
 
 class _WaveNetFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, net, grad_on, wave_sample, *params):
+    def forward(ctx, net, grad_on, wave_sample, classes, *params):
         eng = net._engine_for(wave_sample.device)
         x = wave_sample.detach()
         if x.dtype != torch.float32 or not x.is_contiguous():
@@ -35,7 +35,7 @@ class _WaveNetFunction(torch.autograd.Function):
             tag = getattr(wave_sample, "_wn_codes", None)        # one-hot built from codes (engine.forward_logits)
             if tag is not None and wave_sample._version == tag[2]:
                 x._wn_codes = (tag[0], tag[1], x._version, tag[3])
-        probs, ws = eng.forward(x)
+        probs, ws = eng.forward(x, classes=classes) if classes is not None else eng.forward(x)
         ctx.eng, ctx.ws, ctx.gen = eng, ws, ws["gen"]
         ctx.loss_hook = net._last_hook = _losshook.make(eng, ws, grad_on)
         # a forward that some backward may follow keeps its workspace: the next forward of this shape gets another one (several
@@ -67,14 +67,23 @@ class _WaveNetFunction(torch.autograd.Function):
             grads.append(g[o:o + n].view(shp))
         # the input's own gradient, when autograd asks for it (the reference's causal nn.Conv1d provides it, wavenet/model.py:104)
         din = eng.input_grad(ws) if ctx.needs_input_grad[2] else None
-        return (None, None, din) + tuple(grads)
+        return (None, None, din, None) + tuple(grads)
 
 
 class wavenet(nn.Module):
 
     def __init__(self, filter_width, dilations, dilation_channels, residual_channels, skip_channels,
-                 quantization_channels, use_bias):
+                 quantization_channels, use_bias, global_classes=0, global_channels=0):
         super(wavenet, self).__init__()
+        for key, val in (("global_classes", global_classes), ("global_channels", global_channels)):
+            if isinstance(val, bool) or not isinstance(val, int) or val < 0:
+                raise ValueError("music_amd.wavenet: %s must be an integer >= 0, not %r" % (key, val))
+        if (global_classes > 0) != (global_channels > 0):
+            raise ValueError("music_amd.wavenet: global_classes and global_channels must both be 0 (off) or both >= 1, not %r and %r"
+                             % (global_classes, global_channels))
+        if global_channels > _lib.GCOND_MAX_CHANNELS:
+            raise ValueError("music_amd.wavenet: global_channels must lie in [1, %d], not %r" % (_lib.GCOND_MAX_CHANNELS, global_channels))
+        self.global_classes, self.global_channels = global_classes, global_channels
         self.filter_width = filter_width
         self.dilations = dilations
         self.dilation_channels = dilation_channels
@@ -96,6 +105,14 @@ class wavenet(nn.Module):
         self.post_process_1 = nn.Conv1d(skip_channels, skip_channels, 1, bias=use_bias)
         self.post_process_2 = nn.Conv1d(skip_channels, quantization_channels, 1, bias=use_bias)
         self.softmax = nn.Softmax(dim=1)     # the reference's nn.Softmax() resolves to dim 1 on 2-D input
+        if global_classes > 0:
+            # global conditioning on a class per clip (WaveNet paper section 2.5): [f; g]_i += G_i emb[c] in every block and
+            # h += G_f emb[c] in front of post_process_1's ReLU, constant over time.  The G_i (2 D x E, gate rows first, like the
+            # autoencoder's de_gcond_layer_stack), G_f and the embedding are registered - and drawn - BEHIND everything the model has
+            # without them: a seed gives every earlier parameter the same value and flat offset.  No biases of their own.
+            self.gcond_layer_stack = nn.ModuleList(nn.Conv1d(global_channels, 2 * dilation_channels, 1, bias=False) for _ in dilations)
+            self.connection_gcond = nn.Conv1d(global_channels, skip_channels, 1, bias=False)
+            self.global_embedding = nn.Embedding(global_classes, global_channels)
         self._engine = None
         self.precision = ("f16x3", "bf16x3")     # (forward, backward) arithmetic of the MFMA products
         # nn.CrossEntropyLoss()(net(x), target) with its default arguments runs as the engine's fused softmax + CE pass (the output
@@ -110,6 +127,39 @@ class wavenet(nn.Module):
         state["_engine"] = None
         state["_last_hook"] = None
         return state
+
+    def __setstate__(self, state):
+        super(wavenet, self).__setstate__(state)
+        self.__dict__.setdefault("global_classes", 0)        # (a module pickled before the keys existed)
+        self.__dict__.setdefault("global_channels", 0)
+
+    def global_vectors(self, classes):
+        """The (detached) embedding rows (B, E) of `classes`, B integers in [0, global_classes)."""
+        if not self.global_classes:
+            raise ValueError("music_amd.wavenet: global_vectors needs global_classes > 0")
+        w = self.global_embedding.weight.detach()
+        cls = torch.as_tensor(classes, dtype=torch.int64).reshape(-1)
+        if cls.numel() and not (0 <= int(cls.min()) and int(cls.max()) < self.global_classes):
+            raise ValueError("music_amd.wavenet: a class lies outside [0, %d) (global_classes)" % self.global_classes)
+        return w[cls.to(w.device)]
+
+    def load_state_dict(self, state_dict, *args, **kwargs):
+        """A checkpoint loads only into a model of the same mode, class count and embedding width: refused whole, by name."""
+        emb = state_dict.get("global_embedding.weight", state_dict.get("module.global_embedding.weight"))
+        saved = tuple(emb.shape) if emb is not None and emb.dim() == 2 else (0, 0)
+        mine = (getattr(self, "global_classes", 0), getattr(self, "global_channels", 0))
+        if saved != mine:
+            raise RuntimeError("music_amd.wavenet: the checkpoint was saved with global_classes=%d, global_channels=%d but this model "
+                               "was built with global_classes=%d, global_channels=%d (the keys of the model's parameters JSON); "
+                               "nothing was loaded" % (saved + mine))
+        return super(wavenet, self).load_state_dict(state_dict, *args, **kwargs)
+
+    def check_classes(self, classes):
+        """classes are refused with the mode off and required with it on - before an engine is built or anything is launched"""
+        n = getattr(self, "global_classes", 0)
+        if (classes is None) == bool(n):
+            raise ValueError("music_amd.wavenet: global_classes = %d: classes must be %s"
+                             % (n, "None" if classes is not None else "given, one integer in [0, %d) per clip" % n))
 
     def calc_receptive_field(self):
         return (self.filter_width - 1) * (sum(self.dilations) + 1) + 1
@@ -143,7 +193,8 @@ class wavenet(nn.Module):
         eng = (WaveNetEngine if fast else GenericWaveNetEngine)(
             self.dilations, self.residual_channels, self.dilation_channels, self.skip_channels,
             self.quantization_channels, self.filter_width, self.use_bias,
-            mode_fwd=self.precision[0], mode_bwd=self.precision[1], device=device)
+            mode_fwd=self.precision[0], mode_bwd=self.precision[1], device=device,
+            **(dict(global_classes=self.global_classes, global_channels=self.global_channels) if self.global_classes else {}))
         eng.mode_names = tuple(self.precision)
         assert [n for n, _ in named] == eng.param_names, "parameter order differs from the reference layout"
         with torch.no_grad():
@@ -154,14 +205,16 @@ class wavenet(nn.Module):
         self._engine = eng
         return eng
 
-    def forward(self, wave_sample):
+    def forward(self, wave_sample, classes=None):
+        """classes: one integer in [0, global_classes) per clip of a class-conditional model (required there), else None"""
         batch_size, original_channels, seq_len = wave_sample.size()
         output_width = seq_len - self.receptive_field + 1
         if output_width <= 0:
             raise ValueError("wave sample not long enough")
+        self.check_classes(classes)
         params = [p for _, p in self._named_ref_params()]
         self._last_hook = None
-        out = _WaveNetFunction.apply(self, torch.is_grad_enabled(), wave_sample, *params)
+        out = _WaveNetFunction.apply(self, torch.is_grad_enabled(), wave_sample, classes, *params)
         hook, self._last_hook = self._last_hook, None
         return _losshook.wrap(out, hook) if self.fuse_loss else out
 

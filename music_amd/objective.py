@@ -47,6 +47,8 @@ def _forward_logits(net, wave_sample, classes=None, stages=None):
         raise ValueError("music_amd.objective: the input is a (B, Q, T) one-hot, got shape %s" % (tuple(wave_sample.shape),))
     if wave_sample.shape[2] - net.receptive_field + 1 <= 0:
         raise ValueError("wave sample not long enough")
+    if hasattr(net, "check_classes"):
+        net.check_classes(classes)                              # (a class-conditional WaveNet: required there, refused elsewhere)
     eng = net._engine_for(wave_sample.device)
     x = _dense_input(wave_sample)
     if hasattr(net, "engine_cond"):
@@ -57,7 +59,7 @@ def _forward_logits(net, wave_sample, classes=None, stages=None):
         if stages is not None:
             raise ValueError("music_amd.objective: stages are the autoencoder's (quantiser dropout)")
         eng.pack_weights()
-        ws = eng.forward_logits(x)
+        ws = eng.forward_logits(x, classes=classes) if classes is not None else eng.forward_logits(x)
     return eng, ws
 
 
@@ -118,14 +120,12 @@ def _params(net):
 def nll_loss(net, x, target, classes=None, stages=None, windows=None, window_pos=None):
     """Mean negative log-likelihood (nats per sample) of `target` (B, W) or (B W,) int64 under the per-timestep softmax of
     net's logits for the one-hot x (B, Q, T): a 0-d tensor whose backward() gives the parameter gradients (and the input's, when it
-    requires grad).  A target outside [0, Q) makes the loss NaN.  classes: one integer per clip for an autoencoder with global class
-    conditioning (required there, refused elsewhere).  stages: the clips' stage counts under quantiser dropout, as the autoencoder's
+    requires grad).  A target outside [0, Q) makes the loss NaN.  classes: one integer per clip for a model with global class
+    conditioning - an autoencoder or a WaveNet (required there, refused elsewhere).  stages: the clips' stage counts under quantiser dropout, as the autoencoder's
     forward takes them (None: all stages - this function draws nothing).  windows: 1..16 (lo, hi) pairs (None: the engine's
     nll_windows) - the softmax of column c of clip b is taken inside the pair of stream position window_pos[b] + c; window_pos: None
     (0), an int, or one per clip (a sequence, or an int64 device tensor: no host synchronisation).  A target outside its window makes
     the loss NaN."""
-    if classes is not None and not hasattr(net, "engine_cond"):
-        raise ValueError("music_amd.objective: classes are the autoencoder's (global class conditioning)")
     out = _NLLFunction.apply(net, torch.is_grad_enabled(), x, target, classes, stages, windows, window_pos, *_params(net))
     if isinstance(out, tuple):                                  # a vq autoencoder: the caller adds net.vq_loss
         out, net.vq_loss = out

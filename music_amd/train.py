@@ -376,6 +376,22 @@ def train():
     # windows of the samplers applied to that objective - a prior over a residual quantiser's token stream trains on what it samples
     objective = wobjective.objective_option(train_params)
     nll_windows = wobjective.nll_windows_option(train_params, dataset_params, wavenet_params.get("quantization_channels"))
+    # "global_classes" / "global_channels" in the model's JSON: a class-conditional WaveNet.  The clips' classes come from
+    # dataset_params.json's "labels_path" (a JSON list of integers, one per item of the audio pickle; "valid_labels_path" in
+    # train_params.json for the held-out set) - as in music_amd/ae_train.py: the mode without labels is refused, labels without it too
+    n_global = getattr(net, "global_classes", 0)
+    if n_global and not dataset_params.get("labels_path"):
+        raise ValueError('the model\'s parameters set "global_classes": %d, so dataset_params.json must name the clips\' classes with '
+                         '"labels_path" (a JSON list of integers, one per item of the audio pickle)' % n_global)
+    if dataset_params.get("labels_path"):
+        if not n_global:
+            raise ValueError('dataset_params.json has "labels_path" but the model\'s parameters leave "global_classes" at 0: nothing '
+                             'would read the labels')
+        dataset_params = dict(dataset_params, n_classes=n_global)         # a label outside [0, global_classes) raises at load
+        if train_params.get("valid_audio_path") and int(train_params.get("validate_every") or 0) > 0 \
+                and not train_params.get("valid_labels_path"):
+            raise ValueError('train_params.json: validating a model with "global_classes" needs "valid_labels_path", the classes of the '
+                             'items of "valid_audio_path"')
     validation = wobjective.Validation.make(train_params, dataset_params) if rank == 0 else None
     if world > 1:
         # DataParallel semantics: the JSON batch_size is the GLOBAL batch, split evenly
@@ -455,12 +471,13 @@ def train():
                     target = target.cuda(non_blocking=True)
                 target = target.view(-1)
             win_kw = {} if nll_windows is None else {"windows": nll_windows, "window_pos": sampled_batch.get("audio_pos")}     # (absent on an empty shard)
+            cls_kw = {"classes": sampled_batch["audio_class"]} if n_global and "audio_class" in sampled_batch else {}
             loss = torch.zeros((), device=device)
             if fused:
                 if engine is None:
                     engine = _fused_engine()
                 if piece is not None:
-                    loss = engine.loss_and_grad(piece.contiguous(), target, **win_kw)
+                    loss = engine.loss_and_grad(piece.contiguous(), target, **win_kw, **cls_kw)
                 else:
                     engine.flat_grad.zero_()
                 if guarded:                               # the sum alone; 1 / world rides in the guard's and the update's gscale
@@ -472,10 +489,10 @@ def train():
             else:
                 optimizer.zero_grad()
                 if piece is not None and objective == "nll":
-                    loss = wobjective.nll_loss(net, piece, target, **win_kw)
+                    loss = wobjective.nll_loss(net, piece, target, **win_kw, **cls_kw)
                     loss.backward()
                 elif piece is not None:
-                    logits = net(piece)            # probabilities, named as in the reference (Q1)
+                    logits = net(piece, **cls_kw)  # probabilities, named as in the reference (Q1)
                     loss = loss_func(logits, target)
                     loss.backward()
                 wdist.allreduce_gradients(net.parameters(), average=True, scale=dp_scale)

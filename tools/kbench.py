@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of single kernels of the hot path at BASELINE config-2 shapes (GPU only).
 
-    python tools/kbench.py [fwd|bwd|epi|dx|skip|decode|ae|guard|ema|nll|win_nll|cond|vq|vq_ema|gcond|rvq|all] [--reps N] [--precision f16x3,bf16x3]
+    python tools/kbench.py [fwd|bwd|epi|dx|skip|decode|ae|guard|ema|nll|win_nll|cond|vq|vq_ema|gcond|gclass|rvq|all] [--reps N] [--precision f16x3,bf16x3]
 
 Prints per-phase / per-layer kernel times measured with HIP events on the launch stream.
 """
@@ -603,6 +603,93 @@ def gcond_bench(reps, alternations=6, E=64, n_cls=8):
     print(json.dumps(res))
 
 
+def gclass_bench(reps, alternations=6, E=64, n_cls=8):
+    """`gclass`: the class-conditional WaveNet.  (a) wn_gclass_fwd / wn_gclass_bwd alone at config 2's shape (30 blocks, 64 / 256
+    channels, 8 clips) with E = 64 channels, HIP events around max(reps, 100) calls; (b) the fused step (forward, loss, backward, flat
+    Adam) conditioned against unconditioned at config 2's shape (the fast engine: the conditioned one runs the three-launch forward
+    epilogue) and at a prior's (8 x 1024 x 4096, the general plan); everything alternated `alternations` times on one device, medians
+    and spreads (largest - smallest).  Written to profiles/gclass_kbench.json."""
+    import time
+    from music_amd import _lib
+    from music_amd._lib import call, ptr
+    from music_amd.faster_audio_data import onehot_device
+    from music_amd.model import wavenet
+    st = _lib.stream()
+    res = {"alternations": alternations, "E": E, "n_cls": n_cls}
+    rng = np.random.default_rng(0)
+    N, D, CH, S, B = len(CFG["dilations"]), 64, 64, 256, B_LOCAL
+    n = N * 2 * D * E + S * E + n_cls * E
+    flat, grad = torch.randn(n, device="cuda") * 0.1, torch.empty(n, device="cuda")
+    goffs = (0, 2 * D * E, N * 2 * D * E, N * 2 * D * E + S * E, E, n_cls)
+    tab, tabp, enf = torch.randn(N, B, 2 * CH, device="cuda"), torch.randn(N, B // 2, 4 * CH, device="cuda"), torch.randn(B, S, device="cuda")
+    cls = torch.from_numpy((np.arange(B) % n_cls).astype(np.int32)).cuda()
+    legs = {"gclass_fwd": lambda: call("wn_gclass_fwd", ptr(flat), ptr(tab), None, ptr(enf), N, D, CH, S, B, ptr(cls), *goffs, st),
+            "gclass_fwd_both_tables": lambda: call("wn_gclass_fwd", ptr(flat), ptr(tab), ptr(tabp), ptr(enf), N, D, CH, S, B, ptr(cls), *goffs, st),
+            "gclass_bwd": lambda: call("wn_gclass_bwd", ptr(tab), 0, ptr(enf), ptr(flat), ptr(grad), N, D, CH, S, B, ptr(cls), *goffs, st)}
+    res["shape_kernels"] = dict(N=N, D=D, CH=CH, S=S, B=B)
+
+    def launches(fn, k):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        torch.cuda.synchronize()
+        ev[0].record()
+        for _ in range(k):
+            fn()
+        ev[1].record()
+        torch.cuda.synchronize()
+        return ev[0].elapsed_time(ev[1]) / k * 1e3
+    times = {key: [] for key in legs}
+    for fn in legs.values():
+        launches(fn, 20)                                                      # warm
+    for _ in range(alternations):
+        for key, fn in legs.items():
+            times[key].append(launches(fn, max(reps, 100)))
+    for leg, v in times.items():
+        res["wn_%s_us" % leg], res["wn_%s_us_spread" % leg] = _median_spread(v)
+    # ---- the fused step, conditioned against unconditioned
+    shapes = {"config2": (dict(CFG), B_LOCAL, T), "prior_8x1024x4096": (dict(CFG, quantization_channels=1024), 8, 4096)}
+    for tag, (cfg, Bs, Ts) in shapes.items():
+        Q = cfg["quantization_channels"]
+        codes = torch.from_numpy(rng.integers(0, Q, size=(Bs, Ts)).astype(np.int32)).cuda()
+        x = onehot_device(codes, Q, True)
+        engs = {}
+        for mode, kw in (("plain", {}), ("classes", dict(global_classes=n_cls, global_channels=E))):
+            torch.manual_seed(0)
+            net = wavenet(**dict(cfg, **kw)).cuda()
+            eng = net._engine_for(torch.device("cuda", 0))
+            eng.adam_init(lr=1e-4)
+            engs[mode] = eng
+        W = Ts - engs["plain"].rf + 1
+        target = torch.from_numpy(rng.integers(0, Q, size=(Bs * W,)).astype(np.int64)).cuda()
+        classes = torch.arange(Bs, dtype=torch.int64) % n_cls                 # on the host, as the loader hands them on
+
+        def steps(mode, k):
+            eng = engs[mode]
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(k):
+                loss = eng.loss_and_grad(x, target, **({"classes": classes} if mode == "classes" else {}))
+                eng.adam_step()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) / k * 1e3, float(loss)
+        for mode in engs:
+            steps(mode, 5)
+        step_ms = {m: [] for m in engs}
+        for _ in range(alternations):
+            for mode in engs:
+                ms, loss = steps(mode, max(reps, 20))
+                step_ms[mode].append(ms)
+                res["%s_fused_step_loss_%s" % (tag, mode)] = round(loss, 5)
+        for mode, v in step_ms.items():
+            res["%s_fused_step_ms_%s" % (tag, mode)], res["%s_fused_step_ms_%s_spread" % (tag, mode)] = _median_spread(v)
+        res["%s_fused_step_ms_classes_minus_plain" % tag] = round(res["%s_fused_step_ms_classes" % tag] - res["%s_fused_step_ms_plain" % tag], 3)
+        res["%s_fused_step_ms_by_alternation" % tag] = {m: [round(t, 3) for t in v] for m, v in step_ms.items()}
+        res["shape_" + tag] = dict(B=Bs, T=Ts, Q=Q, engine=type(engs["classes"]).__name__, E=E, n_cls=n_cls)
+        del engs, x, target
+        torch.cuda.empty_cache()
+    _write_profile("gclass_kbench.json", res)
+    print(json.dumps(res))
+
+
 def win_nll_bench(reps, alternations=6):
     """`win_nll`: the windowed objective's launch (wn_win_step_nll) against the plain one (wn_step_nll, the yardstick: the kernel from
     before the windows, measured in the same run) on random logits, with dx and forward-only (row_nll + row_hit), at config 2's shape
@@ -669,12 +756,16 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--precision", default="f16x3,bf16x3")
     ap.add_argument("--overlap", type=int, default=1)
-    ap.add_argument("--parent", default=None, help="gcond / rvq / rvq_drop / win_nll: a built checkout of the parent commit, for profiles/<what>_bench_unset.json")
+    ap.add_argument("--parent", default=None, help="gcond / gclass / rvq / rvq_drop / win_nll: a built checkout of the parent commit, for profiles/<what>_bench_unset.json")
     args = ap.parse_args()
     if args.what == "gcond":
         if args.parent:
             bench_unset(os.path.abspath(args.parent))
         return gcond_bench(args.reps)
+    if args.what == "gclass":
+        if args.parent:
+            bench_unset(os.path.abspath(args.parent), profile="gclass_bench_unset.json", keys="global_classes / global_channels of wavenet")
+        return gclass_bench(args.reps)
     if args.what == "rvq":
         if args.parent:
             bench_unset(os.path.abspath(args.parent), profile="rvq_bench_unset.json", keys="vq_stages")

@@ -25,7 +25,11 @@ distribution it is sampled from: `"nll_windows": {"stages": S, "codes": K}` besi
 `"token_positions": true` in dataset_params.json (music_amd/objective.py: the softmax, the loss and the validation figures of a
 position are taken over its stage's K tokens only; the loss starts at ln K, not ln(S K)).  Every array written here starts at a
 frame boundary, so position 0 of an item is stage 0 - what the loader's 'audio_pos' counts from; sampling with sample_code_stream is
-unchanged."""
+unchanged.
+
+--labels (the source corpus' "labels_path": a JSON list of integers, one per piece of --audio) with --labels-out writes the labels
+of the token pickle's items - every item the label of the piece it was encoded from, the pieces --drop-empty leaves out left out
+here too - as the "labels_path" of a class-conditional prior (`wavenet(..., global_classes=n, global_channels=E)`)."""
 import argparse
 import json
 import os
@@ -75,6 +79,18 @@ def encode_pieces(net, pieces, frames=32, batch=8, one_hot="scrambled"):
     return out
 
 
+def item_labels(labels, codes, drop_empty=False):
+    """The labels of the token pickle's items: labels[i] of source piece i for every item written (with drop_empty: the pieces
+    whose code array is empty are left out, as main() leaves them out of the pickle)."""
+    labels = list(labels)
+    if len(labels) != len(codes):
+        raise ValueError("%d labels for %d pieces of audio: the labels file names one class per piece" % (len(labels), len(codes)))
+    for v in labels:
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+            raise ValueError("a label is an integer >= 0, got %r" % (v,))
+    return [int(v) for v, c in zip(labels, codes) if not drop_empty or np.asarray(c).size]
+
+
 def check_alphabet(stages, K):
     """The prior's alphabet is stages * K tokens; the decoder's samplers take at most 1024."""
     from music_amd import _lib
@@ -110,12 +126,21 @@ def main(argv=None):
     ap.add_argument("--one-hot", default="scrambled", choices=("scrambled", "canonical"))
     ap.add_argument("--no-ema", action="store_true")
     ap.add_argument("--drop-empty", action="store_true")
+    ap.add_argument("--labels", help='the "labels_path" of --audio: a JSON list of integers, one per piece')
+    ap.add_argument("--labels-out", help="where the labels of the items of --out go (needs --labels)")
     args = ap.parse_args(argv)
+    if bool(args.labels) != bool(args.labels_out):
+        ap.error("--labels and --labels-out go together")
     with open(args.model_params) as f:
         net, read = load_vq_model(json.load(f), args.checkpoint, not args.no_ema)
     with open(args.audio, "rb") as f:
         pieces = pickle.load(f)
     codes = encode_pieces(net, pieces, args.frames, args.batch, args.one_hot)
+    if args.labels:
+        with open(args.labels) as f:
+            out_labels = item_labels(json.load(f), codes, args.drop_empty)
+        with open(args.labels_out, "w") as f:
+            json.dump(out_labels, f)
     if args.drop_empty:
         codes = [c for c in codes if c.size]
     with open(args.out, "wb") as f:
