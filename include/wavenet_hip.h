@@ -896,6 +896,49 @@ int wn_win_sample_logits(const float* logits, int64_t n, int Q, int64_t ld, cons
                          int top_k, float top_p, int64_t step0, const float* u, int32_t* codes, float* probs,
                          const int32_t* win_host, int win_period, int64_t win_pos0, wn_stream_t stream);
 
+/* CLASSIFIER-FREE GUIDANCE (ABI 9 still: new entries only).  A model trained with its class dropped for a share of the clips is
+ * sampled from an extrapolation of its unconditional logits l_u towards its conditional ones l_c (Ho & Salimans 2021).  A launch
+ * carries a GUIDANCE TABLE, a DEVICE array of n_utt / 2 floats, and its rows are PAIRS: row 2j is the conditional member, row
+ * 2j + 1 the unconditional one, guidance[j] the pair's scale s.  Each member runs the recurrence on its own rings and its own
+ * conditioning tables exactly as in wn_win_decode_batch; only the choice changes.  The rule:
+ *   - Combination: g_i = l_c,i + (s - 1) (l_c,i - l_u,i), element by element in fp32 (the difference rounded, then one fused
+ *     multiply-add).  s = 1 is the conditional model, s > 1 more of the class, s = 0 the unconditional model.
+ *   - s == 1 is a bypass: g IS l_c, bit for bit, whatever l_u holds - NaN and inf included.
+ *   - The pick runs ONCE, on g, by the rule above: window first, then top-k, temperature, top-p, draw.  It uses row 2j's sampling
+ *     settings, stream id and uniform number; row 2j + 1's wn_sampling entry is ignored.  An entry outside the step's window
+ *     influences nothing, in either matrix.
+ *   - Feedback: the ONE code is the next input of both members and goes to both codes_out rows; both members therefore see the
+ *     same input history and their note_out / prev_out rows are equal.  probs_out row 2j receives the distribution drawn from
+ *     (of g) and row 2j + 1 the same values: no row is left unwritten.
+ *   - forced, note0 and prev0 stay per row and the caller passes EQUAL rows for the two members of a pair (the fp32 kernel, which
+ *     runs both members of a pair in one workgroup, reads row 2j's).
+ *   - guidance == NULL: no table, the launch is wn_win_decode_batch / wn_win_sample_logits bit for bit.
+ * The per-launch limits stay per row: 1024 rows on the matrix-core path (512 guided streams), 128 on the fp32 kernel (64).
+ *
+ * wn_cfg_decode_batch: wn_win_decode_batch's arguments up to win_pos0, then guidance.  Returns -4 (wn_last_error names the entry
+ * and the argument) before any launch for a non-NULL guidance with odd n_utt, a non-NULL guidance without conditioning tables
+ * (cond_fg and cond_p1 both NULL), and everything wn_win_decode_batch refuses. */
+int wn_cfg_decode_batch(int filter_width, int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host,
+                        const int64_t* q_off_host, float* queues, const float* w_causal, const float* b_causal,
+                        const float* w_layers, int64_t layer_stride, const float* b_layers, const float* w_p1, const float* b_p1,
+                        const float* w_p2, const float* b_p2, const float* note0, const float* prev0, float* note_out,
+                        float* prev_out, const int32_t* forced, int32_t* codes_out, float* probs_out, int64_t step0,
+                        int n_steps, int push_input, uint64_t* sync, int n_utt, int64_t queues_ustride, float temperature,
+                        uint64_t seed, const uint16_t* pk, int64_t pk_fg0, int64_t pk_d0, int64_t pk_lstride, int64_t pk_skip,
+                        int64_t pk_p1, int64_t pk_p2, const float* cond_fg, int64_t cond_fg_ustride, const float* cond_p1,
+                        int64_t cond_p1_ustride, const int32_t* c_shift_host, const int32_t* c_q_host, int le, int64_t pos0,
+                        const wn_sampling* samp, int top_k, float top_p, const int32_t* win_host, int win_period,
+                        int64_t win_pos0, const float* guidance, wn_stream_t stream);
+/* The guided sampler alone (the decode kernels' device function): wn_win_sample_logits' arguments up to win_pos0 with logits_c in
+ * the place of logits, then logits_u [n][Q] (row stride ld too) and guidance [n], DEVICE arrays - row i is picked from the
+ * combination of the two matrices' rows i under guidance[i], with row i's settings.  guidance == NULL is wn_win_sample_logits on
+ * logits_c (logits_u is not read); a non-NULL guidance with NULL logits_u is refused like every missing pointer (-4, by name).  Everything
+ * wn_win_sample_logits refuses is refused under this entry's name. */
+int wn_cfg_sample_logits(const float* logits_c, int64_t n, int Q, int64_t ld, const wn_sampling* samp, float temperature, uint64_t seed,
+                         int top_k, float top_p, int64_t step0, const float* u, int32_t* codes, float* probs,
+                         const int32_t* win_host, int win_period, int64_t win_pos0, const float* logits_u, const float* guidance,
+                         wn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -142,6 +142,9 @@ SIGNATURES = {
     # position-windowed sampling: the entries above with the window tail (named outside the wn_decode* family on purpose)
     "wn_win_decode_batch": [_i] + _DEC_HEAD + _DEC_BATCH + _DEC_PK + _DEC_COND + _DEC_SAMP + _DEC_WIN + [_p],
     "wn_win_sample_logits": _SAMPLE_LOGITS + _DEC_WIN + [_p],
+    # classifier-free guidance: the windowed entries with the guidance tail (decode: the table; sampler: logits_u, the table)
+    "wn_cfg_decode_batch": [_i] + _DEC_HEAD + _DEC_BATCH + _DEC_PK + _DEC_COND + _DEC_SAMP + _DEC_WIN + [_p, _p],
+    "wn_cfg_sample_logits": _SAMPLE_LOGITS + _DEC_WIN + [_p, _p, _p],
 }
 
 

@@ -403,7 +403,7 @@ def split_code_stream(tokens, stages, K):
 
 
 def sample_code_stream(prior, stages, K, frames, start_tokens, start_pos=0, temperature=None, top_k=None, top_p=None, seed=0,
-                       streams=None, classes=None):
+                       streams=None, classes=None, guidance=None):
     """New bottleneck codes from a prior over the interleaved token stream (a ``wavenet`` with ``quantization_channels`` >= stages
     * K trained on tools/vq_codes_dataset.py's output): ``start_tokens`` (U, n0 >= receptive_field) are tokens of a real stream
     whose first token sits at stream position ``start_pos``; their last receptive_field tokens (canonical one-hot) prime the
@@ -412,7 +412,8 @@ def sample_code_stream(prior, stages, K, frames, start_tokens, start_pos=0, temp
     only, renormalised there, so no token can leave its range.  ``(start_pos + n0) % stages`` must be 0: generation starts on a
     frame boundary.  ``temperature`` / ``top_k`` / ``top_p`` / ``seed`` / ``streams``: as in ``generate_codes_batch``.
     ``classes``: one class per stream for a class-conditional prior (required there, refused elsewhere): stream u is drawn as
-    class classes[u], under the same stage windows.
+    class classes[u], under the same stage windows.  ``guidance``: None, a scale or one per stream - classifier-free guidance
+    of a prior with ``null_class`` (``fast_generate.generate_codes_batch``): the guided logits are windowed like the plain ones.
     Returns ``split_code_stream`` of the generated tokens: (U, stages, frames) int64 codes in [0, K), what ``decode_codes`` takes."""
     try:
         from . import fast_generate as fg
@@ -436,7 +437,7 @@ def sample_code_stream(prior, stages, K, frames, start_tokens, start_pos=0, temp
     x = torch.nn.functional.one_hot(t[:, -rf:].to(device=dev, dtype=torch.int64), Q).transpose(1, 2).float().contiguous()
     tokens = fg.generate_codes_batch(prior, x, frames * stages, correct_queue=True, temperature=temperature, seed=seed, top_k=top_k,
                                      top_p=top_p, streams=streams, windows=fg.stage_windows(stages, K),
-                                     window_pos=start_pos + t.size(1), classes=classes)
+                                     window_pos=start_pos + t.size(1), classes=classes, guidance=guidance)
     return split_code_stream(tokens, stages, K)
 
 

@@ -60,14 +60,15 @@ static_assert(WN_VQ_NUM_PARTIALS == WN_VQ_PARTIALS && WN_VQ_MAX_CODES == WN_DEC_
 static_assert(WN_VQ_MAX_CODES == WN_VQ_MAX_K && WN_VQ_EMA_WORK_BYTES == WN_VQ_EMA_WORK, "vq ema constants out of sync");
 static_assert(WN_RVQ_MAX_STAGES == WN_RVQ_MAX_S, "rvq constants out of sync");
 
-// ---- cached-queue decode: the ONE call path behind the seven exported decode entries (wn_decode .. wn_decode_batch_samp and
-// wn_win_decode_batch) -----------------------------------------------------------------------------------------------------------
+// ---- cached-queue decode: the ONE call path behind the eight exported decode entries (wn_decode .. wn_decode_batch_samp,
+// wn_win_decode_batch and wn_cfg_decode_batch)------------------------------------------------------------------------------------------------------
 // Every entry forwards its arguments (and the defaults of those it does not take) to decode_checked with the checks it applies:
 enum : unsigned {
     DEC_FW = 1,       // takes filter_width: it, Q and the note / history pointers are checked, under the entry's own name
     DEC_COND = 2,     // takes conditioning tables: corrected recurrence only; le, n_layers and the schedule arrays are checked
     DEC_SAMP = 4,     // takes top_k / top_p: the scalar form's filters are checked
     DEC_WIN = 8,      // takes a sampling-window table: its period, pairs and position are checked against Q
+    DEC_CFG = 16,     // takes a guidance table: the rows are (conditional, unconditional) pairs - an even count, with conditioning tables
 };
 
 static int decode_refuse(const char* fn, const char* text) {
@@ -106,7 +107,7 @@ static int decode_checked(const char* fn, unsigned checks, int64_t sync_ustride,
                           int64_t pk_d0, int64_t pk_lstride, int64_t pk_skip, int64_t pk_p1, int64_t pk_p2, const float* cond_fg,
                           int64_t cond_fg_ustride, const float* cond_p1, int64_t cond_p1_ustride, const int32_t* c_shift_host,
                           const int32_t* c_q_host, int le, int64_t pos0, const wn_sampling* samp, int top_k, float top_p,
-                          const int32_t* win_host, int win_period, int64_t win_pos0, wn_stream_t stream) {
+                          const int32_t* win_host, int win_period, int64_t win_pos0, const float* guidance, wn_stream_t stream) {
     const bool layers_ok = n_layers >= 1 && n_layers <= WN_DEC_MAX_LAYERS;
     if ((checks & DEC_SAMP) && !samp) {   // (a table's entries are normalised on the device: out of range = filter off)
         if (!(top_p >= 0.0f)) return decode_refuse(fn, "'top_p' must be a number >= 0 (0 or >= 1: no nucleus filter)");
@@ -141,6 +142,13 @@ static int decode_checked(const char* fn, unsigned checks, int64_t sync_ustride,
         const int rc = win_checked(fn, win_host, win_period, win_pos0, Q, a.win_period, a.win_pos0, a.win_lo, a.win_hi);
         if (rc) return rc;
     }
+    if ((checks & DEC_CFG) && guidance) {
+        if (n_utt > 0 && (n_utt & 1))
+            return decode_refuse(fn, "'guidance' makes the rows (conditional, unconditional) pairs: 'n_utt' must be even");
+        if (!cond_fg && !cond_p1)
+            return decode_refuse(fn, "'guidance' needs the conditioning tables 'cond_fg' / 'cond_p1' (without them both members of a "
+                                     "pair are the same model)");
+    }
     if (n_utt <= 0) return 0;
     if (!layers_ok) return decode_refuse("wn_decode", "1..64 layers supported");
     WN_REQUIRE("wn_decode", dilations_host, q_off_host);              // (host arrays, read right here)
@@ -160,6 +168,7 @@ static int decode_checked(const char* fn, unsigned checks, int64_t sync_ustride,
     a.pk_skip = -1;
     a.cond_fg = cond_fg; a.cond_fg_ustride = cond_fg_ustride; a.cond_p1 = cond_p1; a.cond_p1_ustride = cond_p1_ustride;
     a.le = le; a.pos0 = pos0;
+    a.guidance = (checks & DEC_CFG) ? guidance : nullptr;
     if (cond_fg || cond_p1)
         for (int i = 0; i <= n_layers; ++i) { a.c_shift[i] = c_shift_host[i]; a.c_q[i] = c_q_host[i]; }
     // the matrix-core kernel needs all of pk (chain, skip, post-processing: 64 / 64 / 256 / 256 channels); biases are fine
@@ -173,9 +182,11 @@ static int decode_checked(const char* fn, unsigned checks, int64_t sync_ustride,
 }
 
 // The two sampler entries' one body: the refusals under the entry's name `fn`, then the launch (`win`: the entry takes a table).
+// `logits_u`, `guidance`: the guided entry's second matrix and per-row scales (guidance NULL: the plain sampler on `logits`).
 static int sample_checked(const char* fn, bool win, const float* logits, int64_t n, int Q, int64_t ld, const wn_sampling* samp,
                           float temperature, uint64_t seed, int top_k, float top_p, int64_t step0, const float* u, int32_t* codes,
-                          float* probs, const int32_t* win_host, int win_period, int64_t win_pos0, wn_stream_t stream) {
+                          float* probs, const int32_t* win_host, int win_period, int64_t win_pos0, wn_stream_t stream,
+                          const float* logits_u = nullptr, const float* guidance = nullptr) {
     if (Q < 1 || Q > WN_DEC_MAX_Q) return decode_refuse(fn, "1 <= 'Q' <= 1024 entries per row");
     if (n < 0) return decode_refuse(fn, "'n' (rows) must be >= 0");
     if (ld < Q) return decode_refuse(fn, "'ld' (row stride) must be >= Q");
@@ -191,6 +202,11 @@ static int sample_checked(const char* fn, bool win, const float* logits, int64_t
     }
     if (n == 0) return 0;
     WN_REQUIRE(fn, logits, codes);
+    if (guidance) {
+        WN_REQUIRE(fn, logits_u);
+        return wn_launch_cfg_sample_logits(logits, logits_u, guidance, (long)n, Q, (long)ld, reinterpret_cast<const WnSampling*>(samp),
+                                           temperature, seed, top_k, top_p, (long)step0, u, codes, probs, w, (hipStream_t)stream);
+    }
     return wn_launch_sample_logits(logits, (long)n, Q, (long)ld, reinterpret_cast<const WnSampling*>(samp), temperature, seed, top_k,
                                    top_p, (long)step0, u, codes, probs, w, (hipStream_t)stream);
 }
@@ -1037,7 +1053,7 @@ int wn_decode(int n_layers, int R, int D, int S, int Q, const int32_t* dilations
     return decode_checked("wn_decode", 0, (int64_t)n_layers * D + 2, 2, n_layers, R, D, S, Q, dilations_host, q_off_host, queues,
                           w_causal, b_causal, w_layers, layer_stride, b_layers, w_p1, b_p1, w_p2, b_p2, note0, prev0, note_out,
                           prev_out, forced, codes_out, probs_out, step0, n_steps, push_input, sync, 1, 0, 0.0f, 0,
-                          nullptr, 0, 0, 0, -1, -1, -1, nullptr, 0, nullptr, 0, nullptr, nullptr, 1, 0, nullptr, 0, 1.0f, nullptr, 0, 0, stream);
+                          nullptr, 0, 0, 0, -1, -1, -1, nullptr, 0, nullptr, 0, nullptr, nullptr, 1, 0, nullptr, 0, 1.0f, nullptr, 0, 0, nullptr, stream);
 }
 
 int wn_decode_batch(int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host, const int64_t* q_off_host,
@@ -1051,7 +1067,7 @@ int wn_decode_batch(int n_layers, int R, int D, int S, int Q, const int32_t* dil
                           queues, w_causal, b_causal, w_layers, layer_stride, b_layers, w_p1, b_p1, w_p2, b_p2, note0, prev0,
                           note_out, prev_out, forced, codes_out, probs_out, step0, n_steps, push_input, sync, n_utt, queues_ustride,
                           temperature, seed, nullptr, 0, 0, 0, -1, -1, -1, nullptr, 0, nullptr, 0, nullptr, nullptr, 1, 0,
-                          nullptr, 0, 1.0f, nullptr, 0, 0, stream);
+                          nullptr, 0, 1.0f, nullptr, 0, 0, nullptr, stream);
 }
 
 int wn_decode_batch_pk(int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host, const int64_t* q_off_host,
@@ -1066,7 +1082,7 @@ int wn_decode_batch_pk(int n_layers, int R, int D, int S, int Q, const int32_t* 
                           q_off_host, queues, w_causal, b_causal, w_layers, layer_stride, b_layers, w_p1, b_p1, w_p2, b_p2, note0,
                           prev0, note_out, prev_out, forced, codes_out, probs_out, step0, n_steps, push_input, sync, n_utt,
                           queues_ustride, temperature, seed, pk, pk_fg0, pk_d0, pk_lstride, pk_skip, pk_p1, pk_p2,
-                          nullptr, 0, nullptr, 0, nullptr, nullptr, 1, 0, nullptr, 0, 1.0f, nullptr, 0, 0, stream);
+                          nullptr, 0, nullptr, 0, nullptr, nullptr, 1, 0, nullptr, 0, 1.0f, nullptr, 0, 0, nullptr, stream);
 }
 
 int wn_decode_batch_fw(int filter_width, int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host,
@@ -1081,7 +1097,7 @@ int wn_decode_batch_fw(int filter_width, int n_layers, int R, int D, int S, int 
                           dilations_host, q_off_host, queues, w_causal, b_causal, w_layers, layer_stride, b_layers, w_p1, b_p1, w_p2,
                           b_p2, note0, prev0, note_out, prev_out, forced, codes_out, probs_out, step0, n_steps, push_input, sync,
                           n_utt, queues_ustride, temperature, seed, pk, pk_fg0, pk_d0, pk_lstride, pk_skip, pk_p1, pk_p2,
-                          nullptr, 0, nullptr, 0, nullptr, nullptr, 1, 0, nullptr, 0, 1.0f, nullptr, 0, 0, stream);
+                          nullptr, 0, nullptr, 0, nullptr, nullptr, 1, 0, nullptr, 0, 1.0f, nullptr, 0, 0, nullptr, stream);
 }
 
 int wn_decode_batch_cond(int filter_width, int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host,
@@ -1099,7 +1115,7 @@ int wn_decode_batch_cond(int filter_width, int n_layers, int R, int D, int S, in
                           b_p1, w_p2, b_p2, note0, prev0, note_out, prev_out, forced, codes_out, probs_out, step0, n_steps,
                           push_input, sync, n_utt, queues_ustride, temperature, seed, pk, pk_fg0, pk_d0, pk_lstride, pk_skip, pk_p1,
                           pk_p2, cond_fg, cond_fg_ustride, cond_p1, cond_p1_ustride, c_shift_host, c_q_host, le, pos0,
-                          nullptr, 0, 1.0f, nullptr, 0, 0, stream);
+                          nullptr, 0, 1.0f, nullptr, 0, 0, nullptr, stream);
 }
 
 int wn_decode_batch_samp(int filter_width, int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host,
@@ -1117,7 +1133,7 @@ int wn_decode_batch_samp(int filter_width, int n_layers, int R, int D, int S, in
                           b_layers, w_p1, b_p1, w_p2, b_p2, note0, prev0, note_out, prev_out, forced, codes_out, probs_out, step0,
                           n_steps, push_input, sync, n_utt, queues_ustride, temperature, seed, pk, pk_fg0, pk_d0, pk_lstride, pk_skip,
                           pk_p1, pk_p2, cond_fg, cond_fg_ustride, cond_p1, cond_p1_ustride, c_shift_host, c_q_host, le, pos0, samp,
-                          top_k, top_p, nullptr, 0, 0, stream);
+                          top_k, top_p, nullptr, 0, 0, nullptr, stream);
 }
 
 int wn_win_decode_batch(int filter_width, int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host,
@@ -1136,7 +1152,7 @@ int wn_win_decode_batch(int filter_width, int n_layers, int R, int D, int S, int
                           layer_stride, b_layers, w_p1, b_p1, w_p2, b_p2, note0, prev0, note_out, prev_out, forced, codes_out,
                           probs_out, step0, n_steps, push_input, sync, n_utt, queues_ustride, temperature, seed, pk, pk_fg0, pk_d0,
                           pk_lstride, pk_skip, pk_p1, pk_p2, cond_fg, cond_fg_ustride, cond_p1, cond_p1_ustride, c_shift_host,
-                          c_q_host, le, pos0, samp, top_k, top_p, win_host, win_period, win_pos0, stream);
+                          c_q_host, le, pos0, samp, top_k, top_p, win_host, win_period, win_pos0, nullptr, stream);
 }
 
 int wn_sample_logits(const float* logits, int64_t n, int Q, int64_t ld, const wn_sampling* samp, float temperature, uint64_t seed,
@@ -1150,6 +1166,33 @@ int wn_win_sample_logits(const float* logits, int64_t n, int Q, int64_t ld, cons
                          const int32_t* win_host, int win_period, int64_t win_pos0, wn_stream_t stream) {
     return sample_checked("wn_win_sample_logits", true, logits, n, Q, ld, samp, temperature, seed, top_k, top_p, step0, u, codes, probs,
                           win_host, win_period, win_pos0, stream);
+}
+
+int wn_cfg_decode_batch(int filter_width, int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host,
+                        const int64_t* q_off_host, float* queues, const float* w_causal, const float* b_causal,
+                        const float* w_layers, int64_t layer_stride, const float* b_layers, const float* w_p1, const float* b_p1,
+                        const float* w_p2, const float* b_p2, const float* note0, const float* prev0, float* note_out,
+                        float* prev_out, const int32_t* forced, int32_t* codes_out, float* probs_out, int64_t step0,
+                        int n_steps, int push_input, uint64_t* sync, int n_utt, int64_t queues_ustride, float temperature,
+                        uint64_t seed, const uint16_t* pk, int64_t pk_fg0, int64_t pk_d0, int64_t pk_lstride, int64_t pk_skip,
+                        int64_t pk_p1, int64_t pk_p2, const float* cond_fg, int64_t cond_fg_ustride, const float* cond_p1,
+                        int64_t cond_p1_ustride, const int32_t* c_shift_host, const int32_t* c_q_host, int le, int64_t pos0,
+                        const wn_sampling* samp, int top_k, float top_p, const int32_t* win_host, int win_period,
+                        int64_t win_pos0, const float* guidance, wn_stream_t stream) {
+    return decode_checked("wn_cfg_decode_batch", DEC_FW | DEC_COND | DEC_SAMP | DEC_WIN | DEC_CFG, wn_decode_sync_granules(n_layers, D, S),
+                          filter_width, n_layers, R, D, S, Q, dilations_host, q_off_host, queues, w_causal, b_causal, w_layers,
+                          layer_stride, b_layers, w_p1, b_p1, w_p2, b_p2, note0, prev0, note_out, prev_out, forced, codes_out,
+                          probs_out, step0, n_steps, push_input, sync, n_utt, queues_ustride, temperature, seed, pk, pk_fg0, pk_d0,
+                          pk_lstride, pk_skip, pk_p1, pk_p2, cond_fg, cond_fg_ustride, cond_p1, cond_p1_ustride, c_shift_host,
+                          c_q_host, le, pos0, samp, top_k, top_p, win_host, win_period, win_pos0, guidance, stream);
+}
+
+int wn_cfg_sample_logits(const float* logits_c, int64_t n, int Q, int64_t ld, const wn_sampling* samp, float temperature, uint64_t seed,
+                         int top_k, float top_p, int64_t step0, const float* u, int32_t* codes, float* probs,
+                         const int32_t* win_host, int win_period, int64_t win_pos0, const float* logits_u, const float* guidance,
+                         wn_stream_t stream) {
+    return sample_checked("wn_cfg_sample_logits", true, logits_c, n, Q, ld, samp, temperature, seed, top_k, top_p, step0, u, codes, probs,
+                          win_host, win_period, win_pos0, stream, logits_u, guidance);
 }
 
 }  // extern "C"

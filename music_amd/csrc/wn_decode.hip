@@ -299,6 +299,85 @@ __device__ __forceinline__ int dec_pick_any(const float* logit, int Q, const Dec
     return dec_pick<16>(logit, Q, w, lane, probs_dst, s, u);
 }
 
+// ---- classifier-free guidance -----------------------------------------------------------------------------------------
+// The ONE code of a (conditional, unconditional) pair of rows: the conditional member's logit row lc (LDS, owned by this wave) is
+// combined IN PLACE with the unconditional member's lu,
+//   g_i = l_c,i + (s - 1) (l_c,i - l_u,i)      (fp32: the difference rounded, then ONE fused multiply-add)
+// and the existing rule (dec_pick: window, top-k, temperature, top-p, draw) runs once on g with the conditional member's settings
+// and uniform number.  s (wave-uniform) == 1 is a bypass: g IS l_c, bit for bit, and l_u is never read - NaN and inf in it
+// included.  A lane combines exactly the entries dec_pick has it read (NE l .. NE l + NE-1, below Q), so nothing crosses lanes
+// between the two.  The distribution drawn from goes to BOTH members' rows of probs_out: the entries dec_pick stored through
+// probs_c (all i < Q, every lane its own) are read back by the lane that stored them and repeated in probs_u.
+template <int NE>
+__device__ __forceinline__ void dec_guide(float* lc, const float* lu, float s, int Q, int lane) {
+    if (s != 1.0f) {
+        const float t = s - 1.0f;
+        for (int e = 0; e < NE; ++e) {
+            const int i = lane * NE + e;
+            if (i < Q) { const float c = lc[i]; lc[i] = fmaf(t, c - lu[i], c); }
+        }
+    }
+}
+template <int NE>
+__device__ __forceinline__ void dec_probs_again(float* probs_u, const float* probs_c, int Q, int lane) {
+    for (int e = 0; e < NE; ++e) { const int i = lane * NE + e; if (i < Q) probs_u[i] = probs_c[i]; }
+}
+template <int NE>
+__device__ __forceinline__ int dec_pick_cfg(float* lc, const float* lu, float s, int Q, const DecWin& w, int lane, float* probs_c,
+                                            float* probs_u, const DecSamp& smp, float u) {
+    dec_guide<NE>(lc, lu, s, Q, lane);
+    const int bi = dec_pick<NE>(lc, Q, w, lane, probs_c, smp, u);
+    if (probs_c && probs_u) dec_probs_again<NE>(probs_u, probs_c, Q, lane);
+    return bi;
+}
+__device__ __forceinline__ int dec_pick_cfg_any(float* lc, const float* lu, float s, int Q, const DecWin& w, int lane, float* probs_c,
+                                                float* probs_u, const DecSamp& smp, float u) {
+    if (Q <= 64) return dec_pick_cfg<1>(lc, lu, s, Q, w, lane, probs_c, probs_u, smp, u);
+    if (Q <= 128) return dec_pick_cfg<2>(lc, lu, s, Q, w, lane, probs_c, probs_u, smp, u);
+    if (Q <= 256) return dec_pick_cfg<4>(lc, lu, s, Q, w, lane, probs_c, probs_u, smp, u);
+    if (Q <= 512) return dec_pick_cfg<8>(lc, lu, s, Q, w, lane, probs_c, probs_u, smp, u);
+    return dec_pick_cfg<16>(lc, lu, s, Q, w, lane, probs_c, probs_u, smp, u);
+}
+// the scale of pair j as a scalar register
+__device__ __forceinline__ float dec_scale_of(const float* guidance, size_t j) { return dec_sgpr(guidance[j]); }
+
+// The guided sampler alone (wn_cfg_sample_logits): sample_logits_k with row i picked from the combination of logits_c[i] and
+// logits_u[i] under guidance[i] - the wave stages its conditional row in LDS (lane l the entries it will combine and read) and
+// calls the decode kernels' dec_pick_cfg on it.
+__global__ __launch_bounds__(256) void cfg_sample_logits_k(const float* __restrict__ logits_c, const float* __restrict__ logits_u,
+                                                           const float* __restrict__ guidance, long n, int Q, long ld,
+                                                           const WnSampling* __restrict__ samp, int sample, float inv_temp,
+                                                           unsigned long long seed, int top_k, float top_p, long step0,
+                                                           const float* __restrict__ u, int32_t* __restrict__ codes,
+                                                           float* __restrict__ probs, WnWin win) {
+    __shared__ float s_g[4][WN_DEC_MAX_Q];
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const long row = (long)blockIdx.x * 4 + wv;
+    if (row >= n) return;
+    const DecSamp s = dec_samp_of(samp, samp ? (size_t)row : 0, Q, sample, inv_temp, top_k, top_p, seed);
+    const float ur = u ? u[row] : s.uniform((unsigned long long)(step0 + row));
+    const DecWin w = dec_win_of(win.period, win.lo, win.hi, win.period > 0 ? (int)((win.pos0 + row) % win.period) : 0, Q);
+    float* g = s_g[wv];
+    const int ne = Q <= 64 ? 1 : Q <= 128 ? 2 : Q <= 256 ? 4 : Q <= 512 ? 8 : 16;       // dec_pick_cfg_any's entries per lane
+    for (int e = 0; e < ne; ++e) { const int i = lane * ne + e; if (i < Q) g[i] = logits_c[row * ld + i]; }
+    const int bi = dec_pick_cfg_any(g, logits_u + row * ld, dec_scale_of(guidance, (size_t)row), Q, w, lane,
+                                    probs ? probs + row * (long)Q : nullptr, nullptr, s, ur);
+    if (lane == 0) codes[row] = bi;
+}
+int wn_launch_cfg_sample_logits(const float* logits_c, const float* logits_u, const float* guidance, long n, int Q, long ld,
+                                const WnSampling* samp, float temperature, unsigned long long seed, int top_k, float top_p, long step0,
+                                const float* u, int32_t* codes, float* probs, const WnWin& win, hipStream_t st) {
+    if (n <= 0) return 0;
+    const long blocks = (n + 3) / 4;
+    if (blocks > 0x7fffffffL) return wn_set_error_msg(-4, "wn_cfg_sample_logits: 'n' is too many rows for one launch");
+    hipLaunchKernelGGL(cfg_sample_logits_k, dim3((unsigned)blocks), dim3(256), 0, st, logits_c, logits_u, guidance, n, Q, ld, samp,
+                       temperature > 0.0f ? 1 : 0, temperature > 0.0f ? 1.0f / temperature : 1.0f, seed, top_k, top_p, step0, u, codes,
+                       probs, win);
+    WN_CHECK_LAUNCH();
+    return 0;
+}
+
 // The sampler alone: one wave per row of logits [n][Q] (row stride ld), four rows per workgroup.  Row i is "step" step0 + i
 // of stream samp[i].stream (no table: stream 0); u, when given, replaces the generated uniform numbers.  Row i samples inside
 // pair (win.pos0 + i) mod win.period of the window table (period 0: the whole alphabet).
@@ -332,13 +411,19 @@ int wn_launch_sample_logits(const float* logits, long n, int Q, long ld, const W
 // of global step g; slot g mod L is the oldest: read as tap 0, then overwritten).  For k = 2 this is the loop above,
 // with the same arithmetic in the same order.
 // FW = 2: the filter width fixed at compile time (the arithmetic and schedule of the two-tap loop); FW = 0: any width a.fw
-template <int FW>
+// CFG (a.guidance): one workgroup per PAIR of rows (2b: conditional, 2b + 1: unconditional).  The two members' input columns
+// prev | note are equal by construction (equal start columns, the same code fed back - row 2b's note0 / prev0 / forced serve
+// both), so they are kept once; per sample the network body runs for member 0, then for member 1 - each on its own rings and
+// tables, through the SAME LDS scratch (nothing but prev | note lives across samples), member 0's logits kept in Q more floats -
+// and the workgroup chooses once (dec_pick_cfg).  No hand-off between workgroups.
+template <int FW, bool CFG = false>
 __global__ __launch_bounds__(DEC_THREADS) void decode_k(WnDecodeArgs a) {
     // utterance of a batched launch: per-utterance pointers as LOCALS (the argument struct itself must stay
     // untouched: a modified copy would be moved to scratch and every dil[] / q_off[] lookup with it)
     const int fw = FW ? FW : a.fw;
     const int K1 = fw - 1;                                      // history columns (taps before the current one)
-    const size_t utt = blockIdx.x;
+    constexpr int NM = CFG ? 2 : 1;                             // members (rows) of this workgroup
+    const size_t utt = (size_t)blockIdx.x * NM;
     float* const u_queues = a.queues + utt * a.queues_ustride;
     const float* const u_note0 = a.note0 + utt * a.Q;
     const float* const u_prev0 = a.prev0 ? a.prev0 + utt * (size_t)K1 * a.Q : nullptr;
@@ -360,8 +445,9 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_k(WnDecodeArgs a) {
     float* nxt = z + a.D;                   // [R]
     float* skip = nxt + a.R;                // [S]
     float* h1 = skip + a.S;                 // [S]
-    float* logit = h1 + a.S;                // [Q]
+    float* logit = h1 + a.S;                // [Q] (CFG: [2][Q], the conditional member's row first)
     __shared__ int s_arg;
+    const float gscale = CFG ? dec_scale_of(a.guidance, blockIdx.x) : 1.0f;
     const int tid = threadIdx.x;
 
     const DecSamp smp = dec_samp_of(a, utt, a.Q);               // this utterance's sampling settings, in scalar registers
@@ -373,57 +459,72 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_k(WnDecodeArgs a) {
     for (int step = 0; step < a.n_steps; ++step) {
         const long gstep = a.step0 + step;                      // global step index: ring positions
         const int pos = (int)(a.pos0 + step);                   // output position: conditioning columns
-        // ---- causal layer: cur = sum_j Wc[:, jQ:(j+1)Q] col_j over [prev_0 .. prev_{k-2} | note]
-        dec_matvec(a.w_causal, fw * a.Q, prev /* note follows prev in LDS */, a.R, fw * a.Q, a.b_causal,
-                   [&](int o, float v) { cur[o] = v; });
-        for (int i = tid; i < a.S; i += DEC_THREADS) skip[i] = 0.f;
-        __syncthreads();
-        for (int l = 0; l < a.n_layers; ++l) {
-            const int d = a.dil[l];
-            const long L = (long)K1 * d;
-            float* q = u_queues + a.q_off[l];
-            const int slot = L ? (int)(gstep % L) : 0;          // oldest column == the one replaced now
-            // tap j at slot (g + j d) mod L, staged at old[(k-2-j) R]
-            for (int jj = 0; jj < K1; ++jj) {
-                const float* qj = q + (size_t)((gstep + (long)(K1 - 1 - jj) * d) % L) * a.R;
-                for (int i = tid; i < a.R; i += DEC_THREADS) old[jj * a.R + i] = qj[i];
+        for (int mb = 0; mb < NM; ++mb) {                       // (CFG: the pair's members one after the other; else once)
+            float* const m_queues = CFG ? u_queues + (size_t)mb * a.queues_ustride : u_queues;
+            const float* const m_cfg = CFG && u_cfg ? u_cfg + (size_t)mb * a.cond_fg_ustride : u_cfg;
+            const float* const m_cp1 = CFG && u_cp1 ? u_cp1 + (size_t)mb * a.cond_p1_ustride : u_cp1;
+            float* const m_logit = CFG ? logit + mb * a.Q : logit;
+            // ---- causal layer: cur = sum_j Wc[:, jQ:(j+1)Q] col_j over [prev_0 .. prev_{k-2} | note]
+            dec_matvec(a.w_causal, fw * a.Q, prev /* note follows prev in LDS */, a.R, fw * a.Q, a.b_causal,
+                       [&](int o, float v) { cur[o] = v; });
+            for (int i = tid; i < a.S; i += DEC_THREADS) skip[i] = 0.f;
+            __syncthreads();
+            for (int l = 0; l < a.n_layers; ++l) {
+                const int d = a.dil[l];
+                const long L = (long)K1 * d;
+                float* q = m_queues + a.q_off[l];
+                const int slot = L ? (int)(gstep % L) : 0;          // oldest column == the one replaced now
+                // tap j at slot (g + j d) mod L, staged at old[(k-2-j) R]
+                for (int jj = 0; jj < K1; ++jj) {
+                    const float* qj = q + (size_t)((gstep + (long)(K1 - 1 - jj) * d) % L) * a.R;
+                    for (int i = tid; i < a.R; i += DEC_THREADS) old[jj * a.R + i] = qj[i];
+                }
+                __syncthreads();
+                const float* wl = a.w_layers + (size_t)l * a.layer_stride;
+                const float* bl = a.b_layers ? a.b_layers + (size_t)l * (2 * a.D + a.R + a.S) : nullptr;
+                // [f;g] = Wfg [cur; old]: the decode pack orders k as [tap k-1 weights (cur) | tap k-2 | .. | tap 0]
+                // because cur and the staged columns are adjacent in LDS in that order
+                // conditioning: column idx_l(pos + shift_l) of this block's table under [f; g]
+                const float* cfg = m_cfg ? m_cfg + ((size_t)l * a.le + wn_dec_cond_idx(pos + a.c_shift[l], a.c_q[l], a.le)) * 2 * a.D : nullptr;
+                dec_matvec(wl, fw * a.R, cur, 2 * a.D, fw * a.R, bl, [&](int o, float v) { fg[o] = cfg ? v + cfg[o] : v; });
+                __syncthreads();
+                for (int i = tid; i < a.D; i += DEC_THREADS) z[i] = tanhf(fg[i]) * (1.0f / (1.0f + expf(-fg[a.D + i])));
+                __syncthreads();
+                const float* wd = wl + (size_t)2 * a.D * fw * a.R;
+                const float* wsk = wd + (size_t)a.R * a.D;
+                dec_matvec(wd, a.D, z, a.R, a.D, bl ? bl + 2 * a.D : nullptr, [&](int o, float v) { nxt[o] = v + cur[o]; });
+                dec_matvec(wsk, a.D, z, a.S, a.D, bl ? bl + 2 * a.D + a.R : nullptr, [&](int o, float v) { skip[o] += v; });
+                __syncthreads();
+                for (int i = tid; i < a.R; i += DEC_THREADS) {
+                    if (L) q[(size_t)slot * a.R + i] = a.push_input ? cur[i] : nxt[i];     // Q5: output by default (k = 2 only)
+                    cur[i] = nxt[i];
+                }
+                __syncthreads();
             }
+            // ---- post-processing: relu -> P1 -> relu -> P2 -> softmax -> argmax
+            for (int i = tid; i < a.S; i += DEC_THREADS) skip[i] = fmaxf(skip[i], 0.f);
             __syncthreads();
-            const float* wl = a.w_layers + (size_t)l * a.layer_stride;
-            const float* bl = a.b_layers ? a.b_layers + (size_t)l * (2 * a.D + a.R + a.S) : nullptr;
-            // [f;g] = Wfg [cur; old]: the decode pack orders k as [tap k-1 weights (cur) | tap k-2 | .. | tap 0]
-            // because cur and the staged columns are adjacent in LDS in that order
-            // conditioning: column idx_l(pos + shift_l) of this block's table under [f; g]
-            const float* cfg = u_cfg ? u_cfg + ((size_t)l * a.le + wn_dec_cond_idx(pos + a.c_shift[l], a.c_q[l], a.le)) * 2 * a.D : nullptr;
-            dec_matvec(wl, fw * a.R, cur, 2 * a.D, fw * a.R, bl, [&](int o, float v) { fg[o] = cfg ? v + cfg[o] : v; });
+            const float* cp1 = m_cp1 ? m_cp1 + (size_t)wn_dec_cond_idx(pos + a.c_shift[a.n_layers], a.c_q[a.n_layers], a.le) * a.S : nullptr;
+            dec_matvec(a.w_p1, a.S, skip, a.S, a.S, a.b_p1, [&](int o, float v) { h1[o] = fmaxf(cp1 ? v + cp1[o] : v, 0.f); });
             __syncthreads();
-            for (int i = tid; i < a.D; i += DEC_THREADS) z[i] = tanhf(fg[i]) * (1.0f / (1.0f + expf(-fg[a.D + i])));
-            __syncthreads();
-            const float* wd = wl + (size_t)2 * a.D * fw * a.R;
-            const float* wsk = wd + (size_t)a.R * a.D;
-            dec_matvec(wd, a.D, z, a.R, a.D, bl ? bl + 2 * a.D : nullptr, [&](int o, float v) { nxt[o] = v + cur[o]; });
-            dec_matvec(wsk, a.D, z, a.S, a.D, bl ? bl + 2 * a.D + a.R : nullptr, [&](int o, float v) { skip[o] += v; });
-            __syncthreads();
-            for (int i = tid; i < a.R; i += DEC_THREADS) {
-                if (L) q[(size_t)slot * a.R + i] = a.push_input ? cur[i] : nxt[i];     // Q5: output by default (k = 2 only)
-                cur[i] = nxt[i];
-            }
+            dec_matvec(a.w_p2, a.S, h1, a.Q, a.S, a.b_p2, [&](int o, float v) { m_logit[o] = v; });
             __syncthreads();
         }
-        // ---- post-processing: relu -> P1 -> relu -> P2 -> softmax -> argmax
-        for (int i = tid; i < a.S; i += DEC_THREADS) skip[i] = fmaxf(skip[i], 0.f);
-        __syncthreads();
-        const float* cp1 = u_cp1 ? u_cp1 + (size_t)wn_dec_cond_idx(pos + a.c_shift[a.n_layers], a.c_q[a.n_layers], a.le) * a.S : nullptr;
-        dec_matvec(a.w_p1, a.S, skip, a.S, a.S, a.b_p1, [&](int o, float v) { h1[o] = fmaxf(cp1 ? v + cp1[o] : v, 0.f); });
-        __syncthreads();
-        dec_matvec(a.w_p2, a.S, h1, a.Q, a.S, a.b_p2, [&](int o, float v) { logit[o] = v; });
-        __syncthreads();
         // softmax over the Q logits and first-index argmax of the PROBABILITIES, wave 0
         if (tid < 64) {
             const float ur = smp.uniform((unsigned long long)(a.step0 + step));
             const DecWin win = dec_win_of(a.win_period, a.win_lo, a.win_hi, wj, a.Q);
-            const int bi = (FW == 2 && a.Q == 256) ? dec_pick<4>(logit, 256, win, tid, u_probs_out ? u_probs_out + (size_t)step * a.Q : nullptr, smp, ur)
-                                                   : dec_pick_any(logit, a.Q, win, tid, u_probs_out ? u_probs_out + (size_t)step * a.Q : nullptr, smp, ur);
+            float* const pdst = u_probs_out ? u_probs_out + (size_t)step * a.Q : nullptr;
+            int bi;
+            if (CFG) {      // the pair's one code, from the combined row; both members' outputs receive it
+                float* const pdst1 = pdst ? pdst + (size_t)a.n_steps * a.Q : nullptr;
+                bi = (FW == 2 && a.Q == 256) ? dec_pick_cfg<4>(logit, logit + 256, gscale, 256, win, tid, pdst, pdst1, smp, ur)
+                                             : dec_pick_cfg_any(logit, logit + a.Q, gscale, a.Q, win, tid, pdst, pdst1, smp, ur);
+                if (tid == 0) u_codes_out[a.n_steps + step] = bi;
+            } else {
+                bi = (FW == 2 && a.Q == 256) ? dec_pick<4>(logit, 256, win, tid, pdst, smp, ur)
+                                             : dec_pick_any(logit, a.Q, win, tid, pdst, smp, ur);
+            }
             if (tid == 0) { s_arg = bi; u_codes_out[step] = bi; }
         }
         wj = dec_win_next(a.win_period, wj);
@@ -438,8 +539,10 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_k(WnDecodeArgs a) {
         __syncthreads();
     }
     // hand the input columns back (prev = causal queue, note = next input)
-    for (int i = tid; i < a.Q; i += DEC_THREADS) u_note_out[i] = note[i];
-    for (int i = tid; i < K1 * a.Q; i += DEC_THREADS) u_prev_out[i] = prev[i];
+    for (int mb = 0; mb < NM; ++mb) {
+        for (int i = tid; i < a.Q; i += DEC_THREADS) u_note_out[mb * a.Q + i] = note[i];
+        for (int i = tid; i < K1 * a.Q; i += DEC_THREADS) u_prev_out[(size_t)mb * K1 * a.Q + i] = prev[i];
+    }
 }
 
 // Workgroup barrier that only drains LDS traffic.  __syncthreads() also waits for every outstanding
@@ -603,7 +706,11 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
     // a pair with fewer than eight utterances left (n_utt not a multiple of 8; a single utterance): the spare columns MIRROR the
     // last real one - same inputs, same arithmetic, same addresses, so their stores only repeat identical values
     const size_t ulast = (size_t)(a.n_utt > 0 ? a.n_utt : 1) - 1;
-    auto ux = [&](int uu) { const size_t g = ubase + uu; return g < ulast ? g : ulast; };
+    // guided rows (a.guidance; n_utt even): a column pair (2w, 2w + 1) is a (conditional, unconditional) pair of rows, and a spare
+    // one mirrors the last real PAIR, parity kept - mirroring the last row alone would make it (u, u): a pair that picks from l_u
+    // and stores ANOTHER code into the last pair's codes_out row and code granule
+    const int gpar = a.guidance ? 1 : 0;
+    auto ux = [&](int uu) { const size_t g = ubase + uu; return g < ulast ? g : ulast - (size_t)(~(int)g & gpar); };
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 15, q = lane >> 4;
     const int u = c >> 1, h = c & 1;                       // this lane's utterance of the eight and its half (hi / lo columns)
     extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -1091,14 +1198,21 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
                 gather_rows(lg_of(tid >> 5), Q, nullptr, logit, tag, errp);
                 dec_sync();
                 const DecWin win = dec_win_of(a.win_period, a.win_lo, a.win_hi, wj, Q);
+                int bi = 0;
 #pragma unroll
                 for (int e = 0; e < 2; ++e) {          // wave w chooses for utterances 2w and 2w + 1
                     const int uu = 2 * w + e;
                     const size_t ug = ux(uu);
                     const DecSamp& sp = e ? smp1 : smp0;
-                    const float ur = sp.uniform((unsigned long long)(a.step0 + step));
                     float* pdst = a.probs_out ? a.probs_out + (ug * (size_t)a.n_steps + step) * Q : nullptr;
-                    const int bi = dec_pick<4>(logit + uu * Q, Q, win, lane, pdst, sp, ur);
+                    if (e && a.guidance) {                // the unconditional member of a guided pair: the pair's ONE code and distribution again
+                        if (pdst) dec_probs_again<4>(pdst, a.probs_out + (ux(uu - 1) * (size_t)a.n_steps + step) * Q, Q, lane);
+                    } else {
+                        // (guided: the conditional member's row becomes the combined row, in place - both rows are this wave's)
+                        if (a.guidance) dec_guide<4>(logit + uu * Q, logit + (uu + 1) * Q, dec_scale_of(a.guidance, ug >> 1), Q, lane);
+                        const float ur = sp.uniform((unsigned long long)(a.step0 + step));
+                        bi = dec_pick<4>(logit + uu * Q, Q, win, lane, pdst, sp, ur);
+                    }
                     if (lane == 0) {
                         a.codes_out[ug * a.n_steps + step] = bi;
                         __hip_atomic_store(cg_of(uu), dec_pack((float)bi, tag), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1245,14 +1359,21 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
             post(Q / 256, p2b, h1, nullptr, logit, BIAS && a.b_p2 ? bsk + 2 * S : nullptr);
             dec_sync();
             const DecWin win = dec_win_of(a.win_period, a.win_lo, a.win_hi, wj, Q);
+            int bi = 0;
 #pragma unroll
             for (int e = 0; e < 2; ++e) {          // wave w chooses for utterances 2w and 2w + 1
                 const int uu = 2 * w + e;
                 const size_t ug = ux(uu);
                 const DecSamp& sp = e ? smp1 : smp0;
-                const float ur = sp.uniform((unsigned long long)(a.step0 + step));
                 float* pdst = a.probs_out ? a.probs_out + (ug * (size_t)a.n_steps + step) * Q : nullptr;
-                const int bi = dec_pick<4>(logit + uu * Q, Q, win, lane, pdst, sp, ur);
+                if (e && a.guidance) {                // the unconditional member of a guided pair: the pair's ONE code and distribution again
+                    if (pdst) dec_probs_again<4>(pdst, a.probs_out + (ux(uu - 1) * (size_t)a.n_steps + step) * Q, Q, lane);
+                } else {
+                    // (guided: the conditional member's row becomes the combined row, in place - both rows are this wave's)
+                    if (a.guidance) dec_guide<4>(logit + uu * Q, logit + (uu + 1) * Q, dec_scale_of(a.guidance, ug >> 1), Q, lane);
+                    const float ur = sp.uniform((unsigned long long)(a.step0 + step));
+                    bi = dec_pick<4>(logit + uu * Q, Q, win, lane, pdst, sp, ur);
+                }
                 if (lane == 0) {
                     a.codes_out[ug * a.n_steps + step] = bi;
                     __hip_atomic_store(cg_of(uu), dec_pack((float)bi, tag), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1276,15 +1397,17 @@ long wn_decode_granules(int n_layers, int D, int S) {
 }
 
 // LDS bytes of decode_k: [k-1][Q] history + [Q] note, cur [R] + [k-1][R] queue columns, fg [2D], z [D], nxt [R], skip and
-// post_process_1 [S] each, logits [Q] (k = 2: 3Q + 3R + 3D + 2S + 64 floats, as before)
+// post_process_1 [S] each, logits [Q] (k = 2: 3Q + 3R + 3D + 2S + 64 floats, as before); guided pairs: the second member's logits
+// [Q] on top (everything else is shared or reused by the two members)
 size_t dec_k_lds_bytes(const WnDecodeArgs& a) {
-    return sizeof(float) * (size_t)((a.fw + 1) * (size_t)a.Q + (a.fw + 1) * (size_t)a.R + 3 * (size_t)a.D + 2 * (size_t)a.S + 64);
+    return sizeof(float) * (size_t)((a.fw + 1 + (a.guidance ? 1 : 0)) * (size_t)a.Q + (a.fw + 1) * (size_t)a.R + 3 * (size_t)a.D + 2 * (size_t)a.S + 64);
 }
 
 int wn_launch_decode(const WnDecodeArgs& a, hipStream_t st) {
     if (a.n_steps <= 0) return 0;
     if (a.n_layers > WN_DEC_MAX_LAYERS) return wn_set_error_msg(-4, "decode: too many layers");
     const int nu = a.n_utt > 0 ? a.n_utt : 1;
+    if (a.guidance && (nu & 1)) return wn_set_error_msg(-4, "decode: guided rows come in pairs, 'n_utt' must be even");
     // Matrix-core pair of workgroups (64 / 64 / 256 / 256 channels, with or without biases; the API layer only hands `pk`
     // over at those shapes): eight utterances per pair, a launch with fewer mirrors the last one into the spare columns.
     // The two workgroups of a pair spin on each other's hand-offs, so every pair must be resident at once: 128 pairs =
@@ -1360,14 +1483,18 @@ int wn_launch_decode(const WnDecodeArgs& a, hipStream_t st) {
         const size_t sh = dec_k_lds_bytes(a);
         if (sh + 1024 > 160 * 1024) return wn_set_error_msg(-4, "decode: the fp32 kernel's LDS layout does not fit (too many channels for this filter width)");
         if (sh > 64 * 1024) {                       // (above the default dynamic-LDS limit: raise it once per device)
-            static WnDevOnce done_k2, done_k0;
+            static WnDevOnce done_k2, done_k0, done_g2, done_g0;
             int dev = 0;
             (void)hipGetDevice(&dev);
-            WnDevOnce& once = a.fw == 2 ? done_k2 : done_k0;
-            const void* fn = a.fw == 2 ? reinterpret_cast<const void*>(&decode_k<2>) : reinterpret_cast<const void*>(&decode_k<0>);
+            WnDevOnce& once = a.guidance ? (a.fw == 2 ? done_g2 : done_g0) : (a.fw == 2 ? done_k2 : done_k0);
+            const void* fn = a.guidance ? (a.fw == 2 ? reinterpret_cast<const void*>(&decode_k<2, true>) : reinterpret_cast<const void*>(&decode_k<0, true>))
+                                        : (a.fw == 2 ? reinterpret_cast<const void*>(&decode_k<2>) : reinterpret_cast<const void*>(&decode_k<0>));
             if (once.need(dev)) { (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024); once.done(dev); }
         }
-        if (a.fw == 2) hipLaunchKernelGGL(decode_k<2>, dim3(nu), dim3(DEC_THREADS), sh, st, a);
+        // guided: one workgroup per pair of rows runs both members
+        if (a.guidance && a.fw == 2) hipLaunchKernelGGL((decode_k<2, true>), dim3(nu / 2), dim3(DEC_THREADS), sh, st, a);
+        else if (a.guidance) hipLaunchKernelGGL((decode_k<0, true>), dim3(nu / 2), dim3(DEC_THREADS), sh, st, a);
+        else if (a.fw == 2) hipLaunchKernelGGL(decode_k<2>, dim3(nu), dim3(DEC_THREADS), sh, st, a);
         else hipLaunchKernelGGL(decode_k<0>, dim3(nu), dim3(DEC_THREADS), sh, st, a);
     }
     WN_CHECK_LAUNCH();

@@ -367,6 +367,10 @@ struct WnDecodeArgs {
     // stream position already reduced mod win_period by the host.  Read with scalar loads, like dil[] and c_shift[]
     int win_period, win_pos0;
     int win_lo[WN_WIN_MAX], win_hi[WN_WIN_MAX];
+    // classifier-free guidance (wn_cfg_decode_batch): null, or a DEVICE array of n_utt / 2 scales.  With it the rows are pairs - row 2j
+    // the conditional member, row 2j + 1 the unconditional one - that run the recurrence on their own rings and tables; pair j's ONE
+    // code is picked from g = l_c + (guidance[j] - 1) (l_c - l_u) with row 2j's sampling settings and fed back to both members
+    const float* guidance;
 };
 // column of a conditioning table for output column c (see WnDecodeArgs::c_shift)
 __host__ __device__ inline int wn_dec_cond_idx(int c, int q, int le) {
@@ -384,6 +388,10 @@ struct WnWin { int period, pos0; int lo[WN_WIN_MAX], hi[WN_WIN_MAX]; };
 int wn_launch_sample_logits(const float* logits, long n, int Q, long ld, const WnSampling* samp, float temperature,
                             unsigned long long seed, int top_k, float top_p, long step0, const float* u, int32_t* codes,
                             float* probs, const WnWin& win, hipStream_t st);
+// the guided sampler: row i is picked from logits_c[i] + (guidance[i] - 1) (logits_c[i] - logits_u[i]) (both matrices [n][Q], stride ld)
+int wn_launch_cfg_sample_logits(const float* logits_c, const float* logits_u, const float* guidance, long n, int Q, long ld,
+                                const WnSampling* samp, float temperature, unsigned long long seed, int top_k, float top_p, long step0,
+                                const float* u, int32_t* codes, float* probs, const WnWin& win, hipStream_t st);
 
 // wn_coll.hip
 int wn_coll_loaded();

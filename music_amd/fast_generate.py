@@ -404,6 +404,54 @@ def _class_cond(net, eng, classes, U, correct_queue):
     return cond, (cond_fg, cond_p1, shift, qs)
 
 
+def _guidance_of(net, guidance, U, correct_queue, classes):
+    """``guidance=`` of the generators -> None, or U floats (a scalar serves every utterance).  Classifier-free guidance needs a
+    class-conditional model whose parameters name a ``null_class``, classes, and the corrected recurrence: refused here, before
+    anything is launched."""
+    if guidance is None:
+        return None
+    if not getattr(net, "global_classes", 0) or classes is None:
+        raise ValueError("music_amd.fast_generate: guidance= extrapolates from the unconditional towards the class-conditional "
+                         "distribution: it needs a model with global_classes > 0 and classes=")
+    if getattr(net, "null_class", None) is None:
+        raise ValueError('music_amd.fast_generate: guidance= needs a model with "null_class" (the class that stands for "no class", '
+                         'trained with "class_dropout")')
+    if not correct_queue:
+        raise ValueError("guidance runs on the corrected recurrence only (wn_cfg_decode_batch): pass correct_queue=True")
+    if isinstance(guidance, torch.Tensor):
+        guidance = guidance.detach().cpu().tolist()
+    if isinstance(guidance, np.ndarray):
+        guidance = guidance.tolist()
+    g = [guidance] * U if not isinstance(guidance, (list, tuple)) else list(guidance)
+    if len(g) != U or any(isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or abs(v) == float("inf") for v in g):
+        raise ValueError("guidance must be None, a finite number or %d finite numbers (one per utterance)" % U)
+    return [float(v) for v in g]
+
+
+def _paired(v, U):
+    """a per-utterance setting for the doubled rows of a guided launch (both members of a pair carry the utterance's value)"""
+    if isinstance(v, torch.Tensor):
+        v = v.detach().cpu().tolist()
+    if isinstance(v, np.ndarray):
+        v = v.tolist()
+    if isinstance(v, (list, tuple)):
+        if len(v) != U:
+            raise ValueError("per-utterance sampling settings must have one entry per utterance (%d), got %d" % (U, len(v)))
+        return [e for e in v for _ in (0, 1)]
+    return v
+
+
+def _first_guided(probs, g, win):
+    """The first code of every guided pair from the init forward's probabilities (2U, Q), rows [c, u] interleaved: the first-index
+    argmax of log p_c + (s - 1)(log p_c - log p_u) inside the position's window (the rule of the launch on log-probabilities,
+    which differ from the logits by a constant per row: the argmax is the same), taken on the host in float64."""
+    lp = np.log(np.maximum(probs.detach().double().cpu().numpy(), 1e-300))
+    lo, hi = win.at(win.pos) if win is not None else (0, lp.shape[1])
+    s = np.asarray(g, dtype=np.float64)[:, None]
+    comb = lp[0::2, lo:hi] + (s - 1.0) * (lp[0::2, lo:hi] - lp[1::2, lo:hi])
+    return torch.from_numpy(lo + np.argmax(comb, axis=1)).to(probs.device)
+
+
 def _pack_for(net, eng):
     """The decode weight pack of `eng`, kept on the net (built on first use; refreshed by the launcher)."""
     pack = getattr(net, "_decode_pack", None)
@@ -412,15 +460,22 @@ def _pack_for(net, eng):
     return pack
 
 
+_NO_WIN = (None, 0, 0)                                # wn_win_decode_batch's window arguments of a launch without a table
+
+
 def _decode_call(shape, dil, qoff, queues, weights, io, step0, n_steps, push_input, sync, U, queues_ustride, smp, pk, cond=None,
-                 win=None):
+                 win=None, guide=None):
     """(entry point, its arguments without the stream) of one decode launch: THE place the argument list is written and the
     entry chosen.  Plain values and pointers only (no device work).  ``shape``: (filter_width, N, Rp, Dp, S, Q); ``weights``:
     ``_DecodePack.weights()``; ``io``: note0, prev0, note_out, prev_out, forced, codes, probs; ``pk``: ``_DecodePack.chain()``;
     ``cond``: the eight table arguments of wn_decode_batch_cond when the launch came in through ``decode_batch_cond``;
-    ``win``: the three window arguments (``_Windows.tail``) - only then is the entry wn_win_decode_batch, whatever the sampling."""
+    ``win``: the three window arguments (``_Windows.tail``) - only then is the entry wn_win_decode_batch, whatever the sampling;
+    ``guide``: the device pointer of the guidance table (U / 2 floats) - only then is the entry wn_cfg_decode_batch."""
     args = (*shape, dil, qoff, queues, *weights, *io, step0, n_steps, push_input, sync, U, queues_ustride,
             smp.temperature, smp.seed, *pk)
+    if guide is not None:
+        return "wn_cfg_decode_batch", (args + (_NO_COND if cond is None else tuple(cond)) + smp.tail() +
+                                       (_NO_WIN if win is None else tuple(win)) + (guide,))
     if win is not None:
         return "wn_win_decode_batch", args + (_NO_COND if cond is None else tuple(cond)) + smp.tail() + tuple(win)
     if smp.plain and cond is None:
@@ -432,9 +487,10 @@ def _decode_call(shape, dil, qoff, queues, weights, io, step0, n_steps, push_inp
 
 
 def _launch_decode(net, eng, smp, rings, note0, prev0, U, n_steps, step0, push_input, timeout_msg, check=True, forced=None,
-                   want_probs=False, sync=None, cond=None, win=None):
+                   want_probs=False, sync=None, cond=None, win=None, guide=None):
     """One persistent decode launch of U utterances: ``rings`` ((U, ring floats), or 1-D for one utterance) is advanced in
-    place.  ``win``: the window arguments of the launch's first step (``_Windows.tail``), or None.  ``sync``: the hand-off scratch (default: fresh and zeroed); ``check``: read the error flags back and raise
+    place.  ``win``: the window arguments of the launch's first step (``_Windows.tail``), or None.  ``guide``: the guidance table
+    (U / 2 floats on the device; the rows are then (conditional, unconditional) pairs), or None.  ``sync``: the hand-off scratch (default: fresh and zeroed); ``check``: read the error flags back and raise
     ``timeout_msg`` if one is set.  Returns (codes int32 (U, n_steps), probabilities (U, n_steps, Q) or None, note_out (U, Q),
     prev_out (U, k-1, Q))."""
     global last_error_flags
@@ -455,7 +511,7 @@ def _launch_decode(net, eng, smp, rings, note0, prev0, U, n_steps, step0, push_i
                               ctypes.cast(qoff, ctypes.c_void_p), ptr(qbuf), pack.weights(),
                               (ptr(note0), _ptr_or_none(prev0), ptr(note_out), _ptr_or_none(prev_out), ptr(forced_t), ptr(codes),
                                ptr(probs)), int(step0), n_steps, push_input, ptr(sync), U, rings.size(1) if rings.dim() == 2 else 0,
-                              smp, pack.chain(), cond, win)
+                              smp, pack.chain(), cond, win, ptr(guide) if guide is not None else None)
     call(name, *args, _lib.stream())
     flags = sync.view(U, -1)[:, -1]                          # the error flag word of every utterance
     if cond is not None:
@@ -527,7 +583,7 @@ def predict_next(net, note, state_queue=None, correct_queue=False):
 
 
 def generate_codes(net, start_piece, note_num, correct_queue=False, temperature=None, seed=0, top_k=None, top_p=None,
-                   windows=None, window_pos=0, classes=None):
+                   windows=None, window_pos=0, classes=None, guidance=None):
     """The greedy loop of fast_generate.py:162-172 as one init forward + ONE persistent launch.
     Returns the note_num generated codes (int64, on the device).
     ``temperature`` (the reference is greedy only): if given and > 0, every code after the
@@ -539,7 +595,12 @@ def generate_codes(net, start_piece, note_num, correct_queue=False, temperature=
     wn_win_decode_batch; ``stage_windows`` for a residual quantiser's token stream).  The first code is the first-index argmax
     of the init forward inside its window.  Corrected recurrence only.
     ``classes``: ``[c]``, the class to generate as, for a class-conditional model (required there, refused elsewhere): the init
-    forward runs with it and the launch is the conditioned one (wn_decode_batch_cond).  Corrected recurrence only."""
+    forward runs with it and the launch is the conditioned one (wn_decode_batch_cond).  Corrected recurrence only.
+    ``guidance``: a scale s, classifier-free guidance (``generate_codes_batch``; the one-utterance batch of it)."""
+    if guidance is not None:
+        return generate_codes_batch(net, start_piece, note_num, correct_queue=correct_queue, temperature=temperature, seed=seed,
+                                    top_k=top_k, top_p=top_p, windows=windows, window_pos=window_pos, classes=classes,
+                                    guidance=guidance)[0]
     win = _windows_of(windows, window_pos, net.quantization_channels)
     _need_corrected_win(win, correct_queue)
     _check_classes(net, classes)
@@ -560,7 +621,7 @@ def generate_codes(net, start_piece, note_num, correct_queue=False, temperature=
 
 
 def generate_codes_batch(net, start_pieces, note_num, correct_queue=False, temperature=None, seed=0, top_k=None, top_p=None,
-                         streams=None, windows=None, window_pos=0, classes=None):
+                         streams=None, windows=None, window_pos=0, classes=None, guidance=None):
     """SURVEY 8f2 (batched utterances; the reference generates one at a time): greedy generation of
     ``note_num`` codes for U independent start pieces ``(U, Q, receptive_field)`` in ONE persistent
     launch - on the matrix-core path eight utterances to a workgroup pair, one pair of MFMA result columns each (else one
@@ -571,12 +632,20 @@ def generate_codes_batch(net, start_pieces, note_num, correct_queue=False, tempe
     index; row u is then the single-utterance launch with ``streams=[u]``, bit for bit when both run the same kernel form,
     see WN_DEC_KS).  Truncation and per-utterance settings run on the corrected recurrence only.
     ``windows`` / ``window_pos``: as in ``generate_codes``; one table and one position for the whole launch.
-    ``classes``: one class per utterance for a class-conditional model, every utterance with its own tables."""
+    ``classes``: one class per utterance for a class-conditional model, every utterance with its own tables.
+    ``guidance``: None, a scale s or one per utterance - classifier-free guidance (include/wavenet_hip.h, wn_cfg_decode_batch) on a
+    model with ``null_class``: every utterance is decoded as a PAIR of rows, as its class and as null_class, each on its own queues
+    and tables; the ONE code per step is picked from l_c + (s - 1)(l_c - l_u) with the utterance's settings and fed to both.  s = 1
+    is the conditional model, s > 1 more of the class, s = 0 the unconditional model; half as many utterances fit a launch.
+    Corrected recurrence only; None is the call without the argument, launch for launch."""
     assert start_pieces.dim() == 3 and start_pieces.size(2) == net.receptive_field
     _check_classes(net, classes)
     win = _windows_of(windows, window_pos, net.quantization_channels)
     _need_corrected_win(win, correct_queue)
     U = start_pieces.size(0)
+    guide = _guidance_of(net, guidance, U, correct_queue, classes)
+    if guide is not None:
+        return _generate_guided(net, start_pieces, note_num, guide, temperature, seed, top_k, top_p, streams, win, classes)
     if U > 1024:
         raise ValueError("at most 1024 utterances per launch (128 off the matrix-core path)")
     dev = start_pieces.device if start_pieces.is_cuda else torch.device("cuda")
@@ -602,9 +671,44 @@ def generate_codes_batch(net, start_pieces, note_num, correct_queue=False, tempe
     return torch.cat([first.view(U, 1).to(torch.int64), codes.to(torch.int64)], 1)
 
 
+def _generate_guided(net, start_pieces, note_num, guide, temperature, seed, top_k, top_p, streams, win, classes):
+    """generate_codes_batch under guidance: the rows doubled as [c_u, null_class] interleaved for the init forward and for the
+    class tables, one wn_cfg_decode_batch launch through _launch_decode, the even rows returned."""
+    U = start_pieces.size(0)
+    if 2 * U > 1024:
+        raise ValueError("at most 512 guided utterances per launch (64 off the matrix-core path): every one is a pair of rows")
+    dev = start_pieces.device if start_pieces.is_cuda else torch.device("cuda")
+    cls = classes.detach().cpu().tolist() if isinstance(classes, torch.Tensor) else [int(c) for c in classes]
+    if len(cls) != U:
+        raise ValueError("music_amd: classes must be %d integers, one per clip" % U)
+    cls2 = [v for c in cls for v in (int(c), int(net.null_class))]
+    x = start_pieces.detach().to(dev).float().repeat_interleave(2, 0).contiguous()
+    with torch.no_grad():
+        probs = net(x, classes=cls2)                                # (2U, Q): W == 1
+    eng = net._engine
+    cond, keep = _class_cond(net, eng, cls2, 2 * U, True)
+    T, Q, K1 = x.size(2), eng.Q, _taps(eng)
+    rings = _rings_from_workspace(eng, 2 * U, T)
+    first = _first_guided(probs.view(2 * U, Q), guide, win)
+    if note_num <= 1:
+        return first.view(U, 1)[:, :note_num]
+    _check_recurrence(eng, True)
+    # both members of a pair carry the utterance's settings and stream id (the launch reads the conditional member's)
+    smp = _Sampling(2 * U, _paired(temperature, U), _paired(top_k, U), _paired(top_p, U), _paired(seed, U),
+                    _paired(list(range(U)) if streams is None else streams, U), dev)
+    note0 = torch.zeros(2 * U, Q, dtype=torch.float32, device=dev)
+    note0[torch.arange(2 * U, device=dev), first.repeat_interleave(2)] = 1.0
+    prev0 = x[:, :, T - K1:T].transpose(1, 2).contiguous()
+    gtab = torch.tensor(guide, dtype=torch.float32, device=dev)
+    codes, _, _, _ = _launch_decode(net, eng, smp, rings, note0, prev0, 2 * U, note_num - 1, 0, 1,
+                                    "wn_cfg_decode_batch: a hand-off between two decode workgroups timed out", check=note_num - 1 >= 4,
+                                    win=win.tail(1) if win is not None else None, cond=cond, guide=gtab)
+    return torch.cat([first.view(U, 1).to(torch.int64), codes[0::2].to(torch.int64)], 1)
+
+
 def decode_batch_cond(net, rings, prev0, note0, n_steps, step0=0, pos0=0, forced=None, want_probs=False, temperature=None,
                       seed=0, cond_fg=None, cond_p1=None, schedule=None, top_k=None, top_p=None, streams=None, windows=None,
-                      window_pos=0):
+                      window_pos=0, guidance=None):
     """One persistent launch of wn_decode_batch_cond (corrected recurrence) for U utterances from explicit state: ``rings``
     (U, ring floats) is advanced in place, ``prev0`` (U, k-1, Q) / ``note0`` (U, Q) are the causal layer's history and the
     first input column.  ``cond_fg`` (U, N, Le, 2 Dp) rows [f | g] and ``cond_p1`` (U, Le, S) are the per-utterance
@@ -614,6 +718,8 @@ def decode_batch_cond(net, rings, prev0, note0, n_steps, step0=0, pos0=0, forced
     ids (default: the utterance index); anything beyond a scalar temperature and seed goes through wn_decode_batch_samp.
     ``windows`` / ``window_pos``: position windows shared by the launch, step s samples inside pair ``(window_pos + s) %
     len(windows)`` (wn_win_decode_batch; independent of ``step0`` and ``pos0``).
+    ``guidance``: (U / 2,) scales - the rows are (conditional, unconditional) pairs with equal ``note0`` / ``prev0`` / ``forced``
+    rows, decoded by wn_cfg_decode_batch; every output comes back for all U rows.
     Returns (codes int32 (U, n_steps), probabilities (U, n_steps, Q) or None, note_out, prev_out)."""
     eng = net._engine_for(rings.device)
     pack = _pack_for(net, eng)
@@ -638,21 +744,28 @@ def decode_batch_cond(net, rings, prev0, note0, n_steps, step0=0, pos0=0, forced
         shift = ctypes.cast((ctypes.c_int32 * (N + 1))(*[int(t[0]) for t in schedule]), ctypes.c_void_p)
         qs = ctypes.cast((ctypes.c_int32 * (N + 1))(*[int(t[1]) for t in schedule]), ctypes.c_void_p)
     assert forced is None or tuple(forced.shape) == (U, n_steps)
+    gtab = None
+    if guidance is not None:
+        gtab = torch.as_tensor(guidance, dtype=torch.float32).to(dev).contiguous()
+        if U % 2 or tuple(gtab.shape) != (U // 2,):
+            raise ValueError("decode_batch_cond: guidance must hold one scale per pair of rows (U / 2 = %s of them, U even)" % (U / 2,))
     cond = (ptr(cond_fg), cond_fg[0].numel() if cond_fg is not None else 0, ptr(cond_p1),
             cond_p1[0].numel() if cond_p1 is not None else 0, shift, qs, le, int(pos0))
     return _launch_decode(net, eng, smp, rings, note0, prev0, U, n_steps, step0, 1,
                           "wn_decode_batch_cond: a hand-off between two decode workgroups timed out", forced=forced,
-                          want_probs=want_probs, cond=cond, win=win.tail() if win is not None else None)
+                          want_probs=want_probs, cond=cond, win=win.tail() if win is not None else None, guide=gtab)
 
 
 def sample_logits(logits, temperature=1.0, top_k=None, top_p=None, seed=0, step0=0, u=None, want_probs=False, streams=None,
-                  windows=None, window_pos=0):
+                  windows=None, window_pos=0, guidance=None, logits_u=None):
     """The decoder's sampler (the same device function, wn_sample_logits) on a matrix of pre-softmax logits ``(n, Q)``,
     Q <= 1024: row i is drawn as "step" ``step0 + i``.  ``temperature`` (<= 0 / None: greedy argmax), ``top_k``, ``top_p`` and
     ``seed`` may each be a scalar or one value per row (``streams``: the rows' random-number stream ids, default 0);
     ``u`` (n,) replaces the generated uniform numbers.  ``windows`` / ``window_pos``: row i samples inside pair ``(window_pos +
     i) % len(windows)`` of the table (wn_win_sample_logits), independent of ``step0``.  Returns the codes (int64, on the device), with ``want_probs`` also the
-    distributions drawn from ``(n, Q)``.  This is what a one-forward-per-sample generator calls on the forward's logits."""
+    distributions drawn from ``(n, Q)``.  This is what a one-forward-per-sample generator calls on the forward's logits.
+    ``guidance`` (a scale or one per row) with ``logits_u`` (n, Q): classifier-free guidance - ``logits`` are the conditional
+    model's, ``logits_u`` the unconditional one's, row i is drawn from l_c + (s_i - 1)(l_c - l_u) (wn_cfg_sample_logits)."""
     if logits.dim() != 2 or not logits.is_cuda:
         raise ValueError("sample_logits: logits must be a (n, Q) device tensor")
     x = logits.detach().float()
@@ -670,9 +783,21 @@ def sample_logits(logits, temperature=1.0, top_k=None, top_p=None, seed=0, step0
             raise ValueError("sample_logits: u must hold one number per row")
     codes = torch.empty(n, dtype=torch.int32, device=x.device)
     probs = torch.empty(n, Q, dtype=torch.float32, device=x.device) if want_probs else None
+    if (guidance is None) != (logits_u is None):
+        raise ValueError("sample_logits: guidance= and logits_u= come together (the scales and the unconditional model's logits)")
+    if guidance is not None:
+        if not isinstance(logits_u, torch.Tensor) or tuple(logits_u.shape) != (n, Q) or logits_u.device != x.device:
+            raise ValueError("sample_logits: logits_u must be a (%d, %d) tensor on the device of logits" % (n, Q))
+        x, xu = x.contiguous(), logits_u.detach().float().contiguous()
+        g = torch.as_tensor(guidance, dtype=torch.float32).reshape(-1)
+        g = (g.expand(n) if g.numel() == 1 else g).to(x.device).contiguous()
+        if tuple(g.shape) != (n,) or not bool(torch.isfinite(g).all()):
+            raise ValueError("sample_logits: guidance must be a finite number or one per row")
     args = (ptr(x), n, Q, x.stride(0) if n > 1 else max(Q, x.stride(0)), ptr(smp.table), smp.temperature, smp.seed, int(smp.top_k),
             float(smp.top_p), int(step0), ptr(u_t), ptr(codes), ptr(probs))
-    if win is None:
+    if guidance is not None:
+        call("wn_cfg_sample_logits", *args, *(win.tail() if win is not None else _NO_WIN), ptr(xu), ptr(g), _lib.stream())
+    elif win is None:
         call("wn_sample_logits", *args, _lib.stream())
     else:
         call("wn_win_sample_logits", *args, *win.tail(), _lib.stream())
@@ -681,10 +806,11 @@ def sample_logits(logits, temperature=1.0, top_k=None, top_p=None, seed=0, step0
 
 
 def generate(model_path, model_name, generate_path, generate_name, start_piece=None, sr=16000, duration=10, temperature=None,
-             seed=0, top_k=None, top_p=None, classes=None):
+             seed=0, top_k=None, top_p=None, classes=None, guidance=None):
     """wavenet/fast_generate.py:144-179.  ``temperature`` / ``top_k`` / ``top_p`` / ``seed``: sample instead of the greedy
     argmax; a filter selects the corrected queue recurrence (the only one truncated sampling runs on).  ``classes``: ``[c]``, the
-    class to generate as (a model whose parameters set "global_classes"; corrected recurrence)."""
+    class to generate as (a model whose parameters set "global_classes"; corrected recurrence).  ``guidance``: a classifier-free
+    guidance scale (``generate_codes``; the model's parameters set "null_class")."""
     if os.path.exists(generate_path) is False:
         os.makedirs(generate_path)
     with open('./params/wavenet_params.json', 'r') as f:
@@ -701,8 +827,8 @@ def generate(model_path, model_name, generate_path, generate_name, start_piece=N
     # the as-written queue push exists for filter_width 2 only; every other width runs the corrected recurrence
     generated_piece = generate_codes(net, start_piece.cuda(), duration * sr,
                                      correct_queue=(net.filter_width != 2 or top_k is not None or top_p is not None
-                                                    or classes is not None),
-                                     temperature=temperature, seed=seed, top_k=top_k, top_p=top_p, classes=classes)
+                                                    or classes is not None or guidance is not None),
+                                     temperature=temperature, seed=seed, top_k=top_k, top_p=top_p, classes=classes, guidance=guidance)
     print(generated_piece.tolist()[:32], "...")
     audio = mu_law_decode(generated_piece, net.quantization_channels).cpu().numpy()
     from scipy.io import wavfile

@@ -73,7 +73,7 @@ class _WaveNetFunction(torch.autograd.Function):
 class wavenet(nn.Module):
 
     def __init__(self, filter_width, dilations, dilation_channels, residual_channels, skip_channels,
-                 quantization_channels, use_bias, global_classes=0, global_channels=0):
+                 quantization_channels, use_bias, global_classes=0, global_channels=0, null_class=None):
         super(wavenet, self).__init__()
         for key, val in (("global_classes", global_classes), ("global_channels", global_channels)):
             if isinstance(val, bool) or not isinstance(val, int) or val < 0:
@@ -84,6 +84,13 @@ class wavenet(nn.Module):
         if global_channels > _lib.GCOND_MAX_CHANNELS:
             raise ValueError("music_amd.wavenet: global_channels must lie in [1, %d], not %r" % (_lib.GCOND_MAX_CHANNELS, global_channels))
         self.global_classes, self.global_channels = global_classes, global_channels
+        # classifier-free guidance: the row of the embedding that stands for "no class" (train.py's "class_dropout" trains it,
+        # fast_generate's guidance= decodes against it).  It names an existing row: no parameter, no kernel, no state_dict key
+        if null_class is not None:
+            if isinstance(null_class, bool) or not isinstance(null_class, int) or not global_classes or not 0 <= null_class < global_classes:
+                raise ValueError("music_amd.wavenet: null_class must be an integer in [0, global_classes) of a model with "
+                                 "global_classes > 0, not %r (global_classes = %d)" % (null_class, global_classes))
+        self.null_class = null_class
         self.filter_width = filter_width
         self.dilations = dilations
         self.dilation_channels = dilation_channels
@@ -132,6 +139,7 @@ class wavenet(nn.Module):
         super(wavenet, self).__setstate__(state)
         self.__dict__.setdefault("global_classes", 0)        # (a module pickled before the keys existed)
         self.__dict__.setdefault("global_channels", 0)
+        self.__dict__.setdefault("null_class", None)
 
     def global_vectors(self, classes):
         """The (detached) embedding rows (B, E) of `classes`, B integers in [0, global_classes)."""

@@ -141,6 +141,31 @@ def step_probs(net, x, classes=None, windows=None, window_pos=None):
         return eng.step_probs(ws, windows=windows, window_pos=window_pos)
 
 
+def guided_probs(net, x, classes, guidance, windows=None, window_pos=None):
+    """(B W, Q) float64: the teacher-forced distribution a classifier-free-guided decode draws sample w of clip b from
+    (include/wavenet_hip.h, wn_cfg_decode_batch) - the forward the decoder is held to.  Two ``step_probs`` forwards, as `classes`
+    (p_c) and with every clip as the model's ``null_class`` (p_u); the guided logits l_c + (s - 1)(l_c - l_u) differ from
+    s log p_c - (s - 1) log p_u by a constant per row, so the result is p_c^s / p_u^(s-1) renormalised inside the column's window,
+    computed in float64 logs.  guidance: a scale or one per clip.  An entry either forward gives an exact 0 (outside the window, or
+    under float32's range) has probability 0."""
+    null = getattr(net, "null_class", None)
+    if null is None:
+        raise ValueError('music_amd.objective.guided_probs: the model needs "null_class" (the class that stands for "no class")')
+    B = x.size(0)
+    pc = step_probs(net, x, classes=classes, windows=windows, window_pos=window_pos).double()
+    pu = step_probs(net, x, classes=[int(null)] * B, windows=windows, window_pos=window_pos).double()
+    s = torch.as_tensor(guidance, dtype=torch.float64).reshape(-1)
+    if s.numel() not in (1, B) or not bool(torch.isfinite(s).all()):
+        raise ValueError("music_amd.objective.guided_probs: guidance must be a finite number or one per clip (%d)" % B)
+    s = s.expand(B).to(pc.device).repeat_interleave(pc.size(0) // B).view(-1, 1)
+    inside = (pc > 0) & (pu > 0)
+    one = torch.ones_like(pc)
+    lg = s * torch.log(torch.where(inside, pc, one)) - (s - 1.0) * torch.log(torch.where(inside, pu, one))
+    lg = torch.where(inside, lg, torch.full_like(lg, -float("inf")))
+    e = torch.exp(lg - lg.max(1, keepdim=True).values)
+    return e / e.sum(1, keepdim=True)
+
+
 def score(net, x_or_codes, target, scrambled=False, classes=None, stages=None, windows=None, window_pos=None):
     """Held-out figures of net on one batch, forward only.  x_or_codes: the one-hot (B, Q, T) float, or the integer codes (B, T) -
     then the one-hot is laid out canonical, or as the loader scrambles it with `scrambled`.  Returns device tensors of

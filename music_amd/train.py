@@ -41,6 +41,7 @@ import torch.nn as nn
 import torch.optim as optim
 
 try:
+    from . import class_dropout
     from . import dist as wdist
     from . import ema
     from . import guard
@@ -48,6 +49,7 @@ try:
     from .faster_audio_data import audio_data_loader
     from .model import wavenet
 except ImportError:                                  # run as a script / bare modules from the CWD
+    from music_amd import class_dropout
     from music_amd import dist as wdist
     from music_amd import ema
     from music_amd import guard
@@ -392,6 +394,19 @@ def train():
                 and not train_params.get("valid_labels_path"):
             raise ValueError('train_params.json: validating a model with "global_classes" needs "valid_labels_path", the classes of the '
                              'items of "valid_audio_path"')
+    # "null_class" in the model's JSON + "class_dropout": p (and "class_dropout_seed") here: classifier-free guidance training - each
+    # step a clip's class becomes null_class with probability p (music_amd/class_dropout.py: a counter hash of the global step and the
+    # clip's index in the global batch).  No clip may carry null_class as its label; validation scores the true labels.
+    null_class = getattr(net, "null_class", None)
+    class_drop = class_dropout.options(train_params, null_class)
+    if null_class is not None:
+        for key, path in (("labels_path", dataset_params.get("labels_path")), ("valid_labels_path", train_params.get("valid_labels_path"))):
+            if path:
+                with open(path) as f:
+                    labels = json.load(f)
+                if isinstance(labels, list) and null_class in labels:
+                    raise ValueError('%s %s: item %d carries the label %d, the model\'s "null_class" (the class that stands for "no '
+                                     'class" cannot be a clip\'s own)' % (key, path, labels.index(null_class), null_class))
     validation = wobjective.Validation.make(train_params, dataset_params) if rank == 0 else None
     if world > 1:
         # DataParallel semantics: the JSON batch_size is the GLOBAL batch, split evenly
@@ -472,6 +487,9 @@ def train():
                 target = target.view(-1)
             win_kw = {} if nll_windows is None else {"windows": nll_windows, "window_pos": sampled_batch.get("audio_pos")}     # (absent on an empty shard)
             cls_kw = {"classes": sampled_batch["audio_class"]} if n_global and "audio_class" in sampled_batch else {}
+            if class_drop is not None and cls_kw:
+                cls_kw["classes"] = class_dropout.apply(cls_kw["classes"], null_class, class_drop[1], num_trained,
+                                                        int(sampled_batch.get("first_clip", 0)), class_drop[0])
             loss = torch.zeros((), device=device)
             if fused:
                 if engine is None:

@@ -8,8 +8,14 @@ to be compared with `--bias` (the unconditioned biased decoder of the same shape
 `--temperature T`: sample instead of the greedy argmax; `--top-k K` / `--top-p P`: truncate the distribution first
 (wn_decode_batch_samp; corrected recurrence, temperature 1 unless given); `--windows S,K`: sample under the position windows of an
 S-stage token stream of K codes per stage (wn_win_decode_batch with fast_generate.stage_windows(S, K); corrected recurrence,
-temperature 1 unless given); `--runs N`: repeat the whole measurement."""
+temperature 1 unless given); `--runs N`: repeat the whole measurement.
+`--guidance S`: classifier-free guidance at scale S (wn_cfg_decode_batch) on the class-conditional model of the same shape, and on a
+code prior's shape (10 blocks, 64 / 64 / 256, Q = 1024: the fp32 kernel, two members per workgroup, under stage windows 4 x 256):
+U guided streams against 2 U plain conditioned rows of the same build, U = 1 and 64, alternated six times, medians; `--json PATH`
+writes the figures."""
+import json
 import os
+import statistics
 import sys
 import time
 
@@ -77,9 +83,58 @@ def main_cond(le):
                   % (le, U, n, rep, dt, U * n / dt / 1e3, int(torch.unique(codes).numel())))
 
 
+def main_guided(scale):
+    """U guided streams (2 U rows, one choice per pair) against 2 U plain conditioned rows: what guidance costs beyond its second row"""
+    from music_amd import fast_generate as fg
+    from music_amd.model import wavenet
+    dev = torch.device("cuda", 0)
+    gl = dict(global_classes=4, global_channels=16, null_class=3)
+    shapes = [("config-5 shape (matrix cores)", dict(bench.CFG, use_bias=False, filter_width=2, **gl), None, 16000, 2000),
+              ("prior shape, Q = 1024 (fp32 kernel)", dict(filter_width=2, dilations=[2 ** i for i in range(10)], dilation_channels=64,
+                                                        residual_channels=64, skip_channels=256, quantization_channels=1024,
+                                                        use_bias=False, **gl), fg.stage_windows(4, 256), 2000, 500)]
+    res = {"what": "guided streams against twice as many plain conditioned rows, k samples/s of ROWS (a guided stream counts as two), "
+                   "6 alternations, medians [min, max]", "guidance": scale, "cases": []}
+    for name, cfg, win, n1, n64 in shapes:
+        torch.manual_seed(0)
+        net = wavenet(**cfg).cuda()
+        Q = cfg["quantization_channels"]
+        for U, n in ((1, n1), (64, n64)):
+            def pieces(rows):
+                st = torch.zeros(rows, Q, net.receptive_field, device=dev)
+                st[torch.arange(rows), (Q // 2 + torch.arange(rows)) % Q, :] = 1.0
+                return st
+            kw = dict(correct_queue=True, temperature=1.0, seed=1, windows=win)
+            runs = {"guided": lambda: fg.generate_codes_batch(net, pieces(U), n + 1, classes=[u % 3 for u in range(U)], guidance=scale, **kw),
+                    "plain": lambda: fg.generate_codes_batch(net, pieces(2 * U), n + 1, classes=[u % 3 for u in range(2 * U)], **kw)}
+            t = {"guided": [], "plain": []}
+            for alt in range(7):                            # (the first alternation warms up: not counted)
+                for key in ("guided", "plain"):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    runs[key]()
+                    torch.cuda.synchronize()
+                    if alt:
+                        t[key].append(2 * U * n / (time.perf_counter() - t0) / 1e3)
+            row = {"shape": name, "streams": U, "rows": 2 * U, "steps": n}
+            for key in t:
+                row[key] = {"median": statistics.median(t[key]), "min": min(t[key]), "max": max(t[key])}
+            row["guided_over_plain"] = row["guided"]["median"] / row["plain"]["median"]
+            res["cases"].append(row)
+            print("%s, %d guided stream(s) against %d plain rows x %d samples: %.1f [%.1f, %.1f] against %.1f [%.1f, %.1f] k row-samples/s = %.3fx"
+                  % (name, U, 2 * U, n, row["guided"]["median"], row["guided"]["min"], row["guided"]["max"], row["plain"]["median"],
+                     row["plain"]["min"], row["plain"]["max"], row["guided_over_plain"]))
+    path = _opt("--json", str)
+    if path:
+        with open(path, "w") as f:
+            json.dump(res, f, indent=1)
+
+
 def main():
     if cond_frames():
         return main_cond(cond_frames())
+    if "--guidance" in sys.argv:
+        return main_guided(_opt("--guidance", float))
     from music_amd import fast_generate as fg
     from music_amd.model import wavenet
     torch.manual_seed(0)
