@@ -188,13 +188,10 @@ def _decode_from_encoding(net, enc, cond, W, first, prime, forced, free_step=Fal
         from music_amd import fast_generate as fg
     dev = enc.device
     B, Le = enc.size(0), enc.size(2)
-    Q, rf = net.quantization_channel, net.receptive_field
+    rf = net.receptive_field
     wnet, proj = conditioned_decoder(net, cond)
     deng = wnet._engine_for(dev)
-    if not hasattr(wnet, "_decode_pack") or wnet._decode_pack.eng is not deng:
-        wnet._decode_pack = fg._DecodePack(deng)
-    pack = wnet._decode_pack
-    N, Dd, Dp, S, K1 = len(net.dilations), net.de_dilation_channel, pack.Dp, net.de_skip_channel, net.filter_width - 1
+    N, Dd, Dp = len(net.dilations), net.de_dilation_channel, fg._pack_for(wnet, deng).Dp
     # tables: column e of stage i = proj_i(enc[:, e]); blocks [B][N][Le][f Dp | g Dp] (zero rows beyond Dd), post-processing [B][Le][S]
     cw = torch.stack([p[0] for p in proj[:N]])                        # (N, 2 Dd, Bw), rows [f | g]
     cb = torch.stack([p[1] for p in proj[:N]])
@@ -211,10 +208,8 @@ def _decode_from_encoding(net, enc, cond, W, first, prime, forced, free_step=Fal
         cond_fg[..., Dp:Dp + Dd] += gfg[:, :, None, Dd:]
         cond_p1 += (gvec.to(dev) @ G[N].t())[:, None, :]
     sched = cond_schedule(net, W, Le)
-    rw = fg._ring_width(deng)
-    rings = torch.zeros(B, max(1, sum(K1 * d * rw for d in deng.dil)), dtype=torch.float32, device=dev)
+    rings, prev = fg.zero_state(deng, B)
     note = first
-    prev = torch.zeros(B, K1, Q, dtype=torch.float32, device=dev)
     tabs = dict(cond_fg=cond_fg, cond_p1=cond_p1, schedule=sched)
     n = prime.size(1)
     if n > 0:

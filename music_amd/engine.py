@@ -32,6 +32,7 @@ class WaveNetEngine(EngineBase):
             raise NotImplementedError("HIP path implements quantization_channels == 256 (chunk softmax width)")
         self.dil = [int(d) for d in dilations]
         self.N = len(self.dil)
+        self.k = 2                                       # filter width (EngineBase._build_spec, the decoder)
         self.g_n, self.g_E = int(global_classes), int(global_channels)      # class-conditional: classes, embedding width (0, 0: off)
         self.R, self.D, self.S, self.Q = residual_channels, dilation_channels, skip_channels, quantization_channels
         self.fused_loss_ok = True           # model.py: nn.CrossEntropyLoss on the module's output may run as wn_chunk_softmax256_ce (Q = 256 here)
@@ -88,40 +89,6 @@ class WaveNetEngine(EngineBase):
         """Per-kernel timing marks of the epilogue (tools/kbench.py epi); off unless self.fine_marks."""
         if self.fine_marks:
             self.mark(name)
-
-    # ------------------------------------------------------------------ parameters
-    def _build_spec(self):
-        names = [("causal_layer.weight", (self.R, self.Q, 2))]
-        if self.use_bias:
-            names.append(("causal_layer.bias", (self.R,)))
-        for i in range(self.N):
-            for k, shp in enumerate([(self.D, self.R, 2), (self.D, self.R, 2), (self.R, self.D, 1), (self.S, self.D, 1)]):
-                names.append(("dilation_layer_stack.%d.weight" % (4 * i + k), shp))
-                if self.use_bias:
-                    names.append(("dilation_layer_stack.%d.bias" % (4 * i + k), (shp[0],)))
-        names.append(("post_process_1.weight", (self.S, self.S, 1)))
-        if self.use_bias:
-            names.append(("post_process_1.bias", (self.S,)))
-        names.append(("post_process_2.weight", (self.Q, self.S, 1)))
-        if self.use_bias:
-            names.append(("post_process_2.bias", (self.Q,)))
-        names += self.gclass_names(self.N, self.D, self.S, self.g_n, self.g_E)       # (class-conditional: the global block, last)
-        self.spec = _Spec(names)
-        self.param_names = [n for n, _ in names]
-        self._plan_gclass(self.g_n, self.g_E)
-        dev = self.device
-        self.flat = torch.zeros(self.spec.total, dtype=torch.float32, device=dev)
-        self.flat_grad = torch.zeros(self.spec.total, dtype=torch.float32, device=dev)
-
-    def param_view(self, name, grad=False):
-        o, shp = self.spec.off[name], self.spec.shape[name]
-        n = int(np.prod(shp))
-        return (self.flat_grad if grad else self.flat)[o:o + n].view(shp)
-
-    def load_state_dict_tensors(self, sd):
-        with torch.no_grad():
-            for n in self.param_names:
-                self.param_view(n).copy_(sd[n])
 
     def _bias_ptr(self, name):
         if not self.use_bias:

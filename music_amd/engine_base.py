@@ -121,10 +121,11 @@ class _Spec:
 OBJECTIVES = ("reference", "nll")     # what a fused step minimises: the reference's loss, or the true NLL per sample
 
 
-class NllWindows:
-    """The position windows of the "nll" objective (include/wavenet_hip.h, wn_win_step_nll): 1..16 ``(lo, hi)`` pairs with
-    0 <= lo < hi <= Q, the samplers' table (fast_generate.stage_windows); the column at stream position p is scored inside pair
-    ``p % len(windows)``."""
+class WindowTable:
+    """A table of position windows (include/wavenet_hip.h): 1..16 ``(lo, hi)`` pairs with 0 <= lo < hi <= Q; stream position p is
+    sampled, or scored, inside pair ``p % len(windows)``.  THE place the pairs are parsed and checked and the host array the entry
+    points read is built: the decoder's and the sampler's table (fast_generate._Windows) and the "nll" objective's (NllWindows) are
+    this class with their own ``tail``."""
 
     def __init__(self, windows, Q):
         try:
@@ -138,7 +139,16 @@ class NllWindows:
                 raise ValueError("every window needs 0 <= lo < hi <= Q = %d, got (%d, %d)" % (Q, lo, hi))
         self.pairs = pairs
         self.host = (ctypes.c_int32 * (2 * len(pairs)))(*[v for pr in pairs for v in pr])
-        self.pos = None                  # the per-clip positions of the last tail(), kept alive for the launch
+
+    def at(self, pos):
+        """The pair of stream position ``pos``."""
+        return self.pairs[pos % len(self.pairs)]
+
+
+class NllWindows(WindowTable):
+    """The position windows of the "nll" objective (wn_win_step_nll): the samplers' table (fast_generate.stage_windows); the column
+    at stream position p is scored inside pair ``p % len(windows)``."""
+    pos = None                           # the per-clip positions of the last tail(), kept alive for the launch
 
     def tail(self, window_pos, B, device):
         """The arguments the windowed entries take behind those of wn_step_nll / wn_step_softmax (before the stream): win_host,
@@ -288,6 +298,41 @@ class EngineBase:
     # the position windows of the "nll" objective: None, or 1..16 (lo, hi) pairs (NllWindows) - step_nll, score_logits, step_probs
     # and the fused step then run wn_win_step_nll / wn_win_step_softmax, the softmax of a column taken inside its position's pair
     nll_windows = None
+
+    # ------------------------------------------------------------------ parameters (the WaveNet engines': reference state_dict order)
+    def _build_spec(self):
+        """The flat layout of a WaveNet with filter width self.k, and the zeroed flat parameter / gradient buffers."""
+        k = self.k
+        names = [("causal_layer.weight", (self.R, self.Q, k))]
+        if self.use_bias:
+            names.append(("causal_layer.bias", (self.R,)))
+        for i in range(self.N):
+            for j, shp in enumerate([(self.D, self.R, k), (self.D, self.R, k), (self.R, self.D, 1), (self.S, self.D, 1)]):
+                names.append(("dilation_layer_stack.%d.weight" % (4 * i + j), shp))
+                if self.use_bias:
+                    names.append(("dilation_layer_stack.%d.bias" % (4 * i + j), (shp[0],)))
+        names.append(("post_process_1.weight", (self.S, self.S, 1)))
+        if self.use_bias:
+            names.append(("post_process_1.bias", (self.S,)))
+        names.append(("post_process_2.weight", (self.Q, self.S, 1)))
+        if self.use_bias:
+            names.append(("post_process_2.bias", (self.Q,)))
+        names += self.gclass_names(self.N, self.D, self.S, self.g_n, self.g_E)       # (class-conditional: the global block, last)
+        self.spec = _Spec(names)
+        self.param_names = [n for n, _ in names]
+        self._plan_gclass(self.g_n, self.g_E)
+        self.flat = torch.zeros(self.spec.total, dtype=torch.float32, device=self.device)
+        self.flat_grad = torch.zeros(self.spec.total, dtype=torch.float32, device=self.device)
+
+    def param_view(self, name, grad=False):
+        o, shp = self.spec.off[name], self.spec.shape[name]
+        n = int(np.prod(shp))
+        return (self.flat_grad if grad else self.flat)[o:o + n].view(shp)
+
+    def load_state_dict_tensors(self, sd):
+        with torch.no_grad():
+            for n in self.param_names:
+                self.param_view(n).copy_(sd[n])
 
     def _init_state(self):
         self._ws = WorkspacePool(self._make_workspace)

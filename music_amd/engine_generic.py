@@ -24,7 +24,7 @@ import torch
 
 from . import _lib
 from ._lib import call, ptr
-from .engine_base import SLACK, _Spec, _pad
+from .engine_base import SLACK, _pad
 from .plan_generic import GeneralPlan, PackBuilder, Pass
 
 
@@ -46,40 +46,6 @@ class GenericWaveNetEngine(GeneralPlan):
         self._build_spec()
         self._build_packs()
         self._init_state()
-
-    # ------------------------------------------------------------------ parameters (the fast engine's layout)
-    def _build_spec(self):
-        k = self.k
-        names = [("causal_layer.weight", (self.R, self.Q, k))]
-        if self.use_bias:
-            names.append(("causal_layer.bias", (self.R,)))
-        for i in range(self.N):
-            for j, shp in enumerate([(self.D, self.R, k), (self.D, self.R, k), (self.R, self.D, 1), (self.S, self.D, 1)]):
-                names.append(("dilation_layer_stack.%d.weight" % (4 * i + j), shp))
-                if self.use_bias:
-                    names.append(("dilation_layer_stack.%d.bias" % (4 * i + j), (shp[0],)))
-        names.append(("post_process_1.weight", (self.S, self.S, 1)))
-        if self.use_bias:
-            names.append(("post_process_1.bias", (self.S,)))
-        names.append(("post_process_2.weight", (self.Q, self.S, 1)))
-        if self.use_bias:
-            names.append(("post_process_2.bias", (self.Q,)))
-        names += self.gclass_names(self.N, self.D, self.S, self.g_n, self.g_E)       # (class-conditional: the global block, last)
-        self.spec = _Spec(names)
-        self.param_names = [n for n, _ in names]
-        self._plan_gclass(self.g_n, self.g_E)
-        self.flat = torch.zeros(self.spec.total, dtype=torch.float32, device=self.device)
-        self.flat_grad = torch.zeros(self.spec.total, dtype=torch.float32, device=self.device)
-
-    def param_view(self, name, grad=False):
-        o, shp = self.spec.off[name], self.spec.shape[name]
-        n = int(np.prod(shp))
-        return (self.flat_grad if grad else self.flat)[o:o + n].view(shp)
-
-    def load_state_dict_tensors(self, sd):
-        with torch.no_grad():
-            for n in self.param_names:
-                self.param_view(n).copy_(sd[n])
 
     # ------------------------------------------------------------------ packs and gradient maps
     def _build_packs(self):

@@ -33,6 +33,7 @@ try:
     from ._lib import call, ptr
     from .audio_func import mu_law_decode
     from .engine import SLACK, pack_index
+    from .engine_base import WindowTable
     from .model import wavenet
     from .train import load_model
 except ImportError:
@@ -40,6 +41,7 @@ except ImportError:
     from music_amd._lib import call, ptr
     from music_amd.audio_func import mu_law_decode
     from music_amd.engine import SLACK, pack_index
+    from music_amd.engine_base import WindowTable
     from music_amd.model import wavenet
     from music_amd.train import load_model
 
@@ -52,7 +54,7 @@ def _mfma_decode(eng):
     a switch flipped inside a process must not make them disagree)."""
     v = getattr(eng, "_dec_mfma", None)
     if v is None:
-        k = getattr(eng, "k", 2)
+        k = eng.k
         if k == 2:
             v = bool(os.environ.get("WN_DEC_MFMA", "1") == "1" and eng.R <= 64 and
                      eng.D <= 64 and eng.S in (256, 512) and eng.Q == 256 and eng.mode_fwd == _lib.F16X3 and
@@ -78,7 +80,7 @@ class _DecodePack:
 
     def __init__(self, eng):
         sp, R, D, S, Q, N = eng.spec, eng.R, eng.D, eng.S, eng.Q, eng.N
-        k = self.k = getattr(eng, "k", 2)
+        k = self.k = eng.k
         self.mfma = _mfma_decode(eng)
         Rp = Dp = self.Rp = self.Dp = 64 if self.mfma else None
         if not self.mfma:
@@ -176,7 +178,7 @@ class _DecodePack:
 
 def _taps(eng):
     """k - 1: the previous input columns every layer keeps (filter_width - 1)."""
-    return getattr(eng, "k", 2) - 1
+    return eng.k - 1
 
 
 def _check_recurrence(eng, correct_queue):
@@ -190,14 +192,17 @@ def _ptr_or_none(t):
     return ptr(t) if t is not None and t.numel() else None
 
 
-def _queue_buffer(rings):
-    """filter_width 1 keeps no queues, but the entry point wants a queue buffer: one unused float then."""
-    return rings if rings.numel() else torch.zeros(1, dtype=torch.float32, device=rings.device)
+def _ring_offsets(eng):
+    """Float offset of every block's ring - (k-1) d_i columns of _ring_width floats each -, then the floats of all of them: N + 1
+    values.  THE place the ring layout is computed (DecodeState, the launcher, decode_batch_cond's check, zero_state)."""
+    return np.cumsum([0] + [_taps(eng) * d * _ring_width(eng) for d in eng.dil]).astype(np.int64)
 
 
-def _queue_offsets(eng, rw):
-    """Float offset of every block's ring: (k-1) d_i columns of rw floats each."""
-    return np.cumsum([0] + [_taps(eng) * d * rw for d in eng.dil[:-1]]).astype(np.int64)
+def zero_state(eng, B):
+    """The queues of B utterances that have seen nothing, as ``decode_batch_cond`` takes them: (rings (B, ring floats), prev (B, k-1,
+    Q)), zeros on the engine's device.  (filter_width 1 keeps no queues, but the entry point wants a queue buffer: one unused float.)"""
+    return (torch.zeros(B, max(1, int(_ring_offsets(eng)[-1])), dtype=torch.float32, device=eng.device),
+            torch.zeros(B, _taps(eng), eng.Q, dtype=torch.float32, device=eng.device))
 
 
 class DecodeState(OrderedDict):
@@ -209,7 +214,7 @@ class DecodeState(OrderedDict):
         super().__init__()
         self.eng, self.rings, self.prev, self.steps = eng, rings, prev, steps
         self.rw = _ring_width(eng)                # floats per queue column (64 on the matrix-core kernels, zeros beyond eng.R)
-        self.q_off = _queue_offsets(eng, self.rw)
+        self.q_off = _ring_offsets(eng)
         for k in ["causal_layer"] + ["block_%d" % (i + 1) for i in range(eng.N)]:
             OrderedDict.__setitem__(self, k, None)
 
@@ -245,6 +250,20 @@ class DecodeState(OrderedDict):
         return DecodeState(eng, rings.contiguous(), prev, 0)
 
 
+def _per_row(v, U, spread=False):
+    """A setting that is a scalar or one value per utterance (tensor / ndarray / list / tuple) -> None for a scalar, the list of its U
+    values otherwise.  ``spread``: a scalar comes back U times and a sequence as it is - the caller checks what it holds."""
+    if isinstance(v, torch.Tensor):
+        v = v.detach().cpu().tolist()
+    if isinstance(v, np.ndarray):
+        v = v.tolist()
+    if not isinstance(v, (list, tuple)):
+        return [v] * U if spread else None
+    if len(v) != U and not spread:
+        raise ValueError("per-utterance sampling settings must have one entry per utterance (%d), got %d" % (U, len(v)))
+    return list(v)
+
+
 class _Sampling:
     """The sampling arguments of one decode launch of U utterances (or of ``sample_logits`` over U rows).  ``temperature``,
     ``top_k``, ``top_p`` and ``seed`` may each be a scalar or a length-U sequence / tensor; ``streams`` are the random-number
@@ -253,16 +272,7 @@ class _Sampling:
     ``plain``: nothing here needs ``wn_decode_batch_samp`` (no filter, no table)."""
 
     def __init__(self, U, temperature, top_k, top_p, seed, streams, dev, default_stream=None):
-        def seq(v):
-            if isinstance(v, torch.Tensor):
-                v = v.detach().cpu().tolist()
-            if isinstance(v, np.ndarray):
-                v = v.tolist()
-            if isinstance(v, (list, tuple)):
-                if len(v) != U:
-                    raise ValueError("per-utterance sampling settings must have one entry per utterance (%d), got %d" % (U, len(v)))
-                return list(v)
-            return None
+        seq = lambda v: _per_row(v, U)
         per = {"temperature": seq(temperature), "top_k": seq(top_k), "top_p": seq(top_p), "seed": seq(seed)}
         st = seq(streams)
         if streams is not None and st is None:
@@ -304,10 +314,15 @@ _NO_COND = (None, 0, None, 0, None, None, 1, 0)       # wn_decode_batch_cond's t
 last_error_flags = None        # the error flag word of every utterance of the last decode_batch_cond launch (device tensor)
 
 
+def _corrected_only(correct_queue, what, entry):
+    """THE refusal of the as-written recurrence: `what` exists on the corrected one only, served by `entry`."""
+    if not correct_queue:
+        raise ValueError("%s on the corrected recurrence only (%s): pass correct_queue=True" % (what, entry))
+
+
 def _need_corrected(smp, correct_queue):
-    if not smp.plain and not correct_queue:
-        raise ValueError("top_k / top_p and per-utterance sampling settings run on the corrected recurrence only "
-                         "(wn_decode_batch_samp): pass correct_queue=True")
+    if not smp.plain:
+        _corrected_only(correct_queue, "top_k / top_p and per-utterance sampling settings run", "wn_decode_batch_samp")
 
 
 def stage_windows(stages, K):
@@ -316,29 +331,16 @@ def stage_windows(stages, K):
     return [(s * int(K), (s + 1) * int(K)) for s in range(int(stages))]
 
 
-class _Windows:
-    """The position windows of one launch (include/wavenet_hip.h, wn_win_decode_batch): ``windows``, a sequence of 1..16
-    ``(lo, hi)`` pairs with 0 <= lo < hi <= Q, and ``pos``, the stream position of the launch's first step (row); step s
-    samples inside pair ``(pos + s) % len(windows)``.  ``_windows_of`` gives None for ``windows=None``."""
+class _Windows(WindowTable):
+    """The position windows of one launch (engine_base.WindowTable; include/wavenet_hip.h, wn_win_decode_batch) and ``pos``, the
+    stream position of the launch's first step (row); step s samples inside pair ``(pos + s) % len(windows)``.  ``_windows_of``
+    gives None for ``windows=None``."""
 
     def __init__(self, windows, pos, Q):
-        try:
-            pairs = [(int(lo), int(hi)) for lo, hi in windows]
-        except (TypeError, ValueError):
-            raise ValueError("windows must be a sequence of (lo, hi) pairs") from None
-        if not 1 <= len(pairs) <= 16:
-            raise ValueError("windows must hold 1..16 (lo, hi) pairs, got %d" % len(pairs))
-        for lo, hi in pairs:
-            if not 0 <= lo < hi <= Q:
-                raise ValueError("every window needs 0 <= lo < hi <= Q = %d, got (%d, %d)" % (Q, lo, hi))
+        super().__init__(windows, Q)
         if int(pos) < 0:
             raise ValueError("window_pos (the stream position of the first code) must be >= 0, got %d" % int(pos))
-        self.pairs, self.pos = pairs, int(pos)
-        self.host = (ctypes.c_int32 * (2 * len(pairs)))(*[v for pr in pairs for v in pr])
-
-    def at(self, pos):
-        """The pair of stream position ``pos``."""
-        return self.pairs[pos % len(self.pairs)]
+        self.pos = int(pos)
 
     def tail(self, ahead=0):
         """The arguments wn_win_decode_batch / wn_win_sample_logits take behind the entry they extend (before the stream), for a
@@ -346,17 +348,15 @@ class _Windows:
         return ctypes.cast(self.host, ctypes.c_void_p), len(self.pairs), self.pos + ahead
 
 
-def _windows_of(windows, window_pos, Q):
+def _windows_of(windows, window_pos, Q, correct_queue=True):
+    """``windows=`` / ``window_pos=`` of a generator -> _Windows or None; ``correct_queue``: the recurrence the caller runs on."""
     if windows is None:
         if window_pos:
             raise ValueError("window_pos is the position inside a window table: pass windows= with it")
         return None
-    return _Windows(windows, window_pos, Q)
-
-
-def _need_corrected_win(win, correct_queue):
-    if win is not None and not correct_queue:
-        raise ValueError("position windows run on the corrected recurrence only (wn_win_decode_batch): pass correct_queue=True")
+    win = _Windows(windows, window_pos, Q)
+    _corrected_only(correct_queue, "position windows run", "wn_win_decode_batch")
+    return win
 
 
 def _first_in_window(probs, win):
@@ -385,9 +385,7 @@ def _class_cond(net, eng, classes, U, correct_queue):
     cls = eng.stage_classes(classes, U)
     if cls is None:
         return None, None
-    if not correct_queue:
-        raise ValueError("a class-conditional model decodes on the corrected recurrence only (wn_decode_batch_cond): pass "
-                         "correct_queue=True")
+    _corrected_only(correct_queue, "a class-conditional model decodes", "wn_decode_batch_cond")
     pack = _pack_for(net, eng)
     N, D, S, Dp, dev = eng.N, eng.D, eng.S, pack.Dp, eng.device
     ch = -(-D // 32) * 32                                         # the table's rows per half: D padded to 32
@@ -416,40 +414,34 @@ def _guidance_of(net, guidance, U, correct_queue, classes):
     if getattr(net, "null_class", None) is None:
         raise ValueError('music_amd.fast_generate: guidance= needs a model with "null_class" (the class that stands for "no class", '
                          'trained with "class_dropout")')
-    if not correct_queue:
-        raise ValueError("guidance runs on the corrected recurrence only (wn_cfg_decode_batch): pass correct_queue=True")
-    if isinstance(guidance, torch.Tensor):
-        guidance = guidance.detach().cpu().tolist()
-    if isinstance(guidance, np.ndarray):
-        guidance = guidance.tolist()
-    g = [guidance] * U if not isinstance(guidance, (list, tuple)) else list(guidance)
+    _corrected_only(correct_queue, "guidance runs", "wn_cfg_decode_batch")
+    g = _per_row(guidance, U, spread=True)
     if len(g) != U or any(isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or abs(v) == float("inf") for v in g):
         raise ValueError("guidance must be None, a finite number or %d finite numbers (one per utterance)" % U)
     return [float(v) for v in g]
 
 
-def _paired(v, U):
-    """a per-utterance setting for the doubled rows of a guided launch (both members of a pair carry the utterance's value)"""
-    if isinstance(v, torch.Tensor):
-        v = v.detach().cpu().tolist()
-    if isinstance(v, np.ndarray):
-        v = v.tolist()
-    if isinstance(v, (list, tuple)):
-        if len(v) != U:
-            raise ValueError("per-utterance sampling settings must have one entry per utterance (%d), got %d" % (U, len(v)))
-        return [e for e in v for _ in (0, 1)]
-    return v
-
-
-def _first_guided(probs, g, win):
-    """The first code of every guided pair from the init forward's probabilities (2U, Q), rows [c, u] interleaved: the first-index
-    argmax of log p_c + (s - 1)(log p_c - log p_u) inside the position's window (the rule of the launch on log-probabilities,
-    which differ from the logits by a constant per row: the argmax is the same), taken on the host in float64."""
+def _first_codes(probs, win=None, guide=None):
+    """The first code of every utterance from the init forward's probabilities: the first-index argmax of its row, inside the
+    window of position ``win.pos`` when there is a table (``_first_in_window``).  ``guide`` (U scales): the rows are (2U, Q), [c, u]
+    interleaved, and the code is the first-index argmax of log p_c + (s - 1)(log p_c - log p_u) inside the window (the rule of the
+    launch on log-probabilities, which differ from the logits by a constant per row: the argmax is the same), taken on the host in
+    float64."""
+    if guide is None:
+        return probs.argmax(1) if win is None else _first_in_window(probs, win)
     lp = np.log(np.maximum(probs.detach().double().cpu().numpy(), 1e-300))
     lo, hi = win.at(win.pos) if win is not None else (0, lp.shape[1])
-    s = np.asarray(g, dtype=np.float64)[:, None]
+    s = np.asarray(guide, dtype=np.float64)[:, None]
     comb = lp[0::2, lo:hi] + (s - 1.0) * (lp[0::2, lo:hi] - lp[1::2, lo:hi])
     return torch.from_numpy(lo + np.argmax(comb, axis=1)).to(probs.device)
+
+
+def _note0(first, rows, Q, dev):
+    """The first input column of a launch, (rows U, Q): the one-hot of every utterance's first code, once per row of the utterance."""
+    idx = first.to(dev).repeat_interleave(rows)
+    note0 = torch.zeros(idx.numel(), Q, dtype=torch.float32, device=dev)
+    note0[torch.arange(idx.numel(), device=dev), idx] = 1.0
+    return note0
 
 
 def _pack_for(net, eng):
@@ -498,7 +490,7 @@ def _launch_decode(net, eng, smp, rings, note0, prev0, U, n_steps, step0, push_i
     pack.refresh()
     dev, N, Q, K1 = eng.device, eng.N, eng.Q, pack.k - 1
     dil = (ctypes.c_int32 * N)(*eng.dil)
-    qoff = (ctypes.c_int64 * N)(*[int(v) for v in _queue_offsets(eng, pack.Rp)])
+    qoff = (ctypes.c_int64 * N)(*[int(v) for v in _ring_offsets(eng)[:N]])
     forced_t = forced.to(device=dev, dtype=torch.int32).contiguous() if forced is not None else None
     codes = torch.empty(U, n_steps, dtype=torch.int32, device=dev)
     probs = torch.empty(U, n_steps, Q, dtype=torch.float32, device=dev) if want_probs else None
@@ -506,7 +498,7 @@ def _launch_decode(net, eng, smp, rings, note0, prev0, U, n_steps, step0, push_i
     prev_out = torch.empty(U, K1, Q, dtype=torch.float32, device=dev)
     if sync is None:
         sync = torch.zeros(U * _lib.decode_sync_granules(N, pack.Dp, eng.S), dtype=torch.int64, device=dev)
-    qbuf = _queue_buffer(rings)
+    qbuf = rings if rings.numel() else torch.zeros(1, dtype=torch.float32, device=dev)     # (filter_width 1: zero_state)
     name, args = _decode_call((pack.k, N, pack.Rp, pack.Dp, eng.S, Q), ctypes.cast(dil, ctypes.c_void_p),
                               ctypes.cast(qoff, ctypes.c_void_p), ptr(qbuf), pack.weights(),
                               (ptr(note0), _ptr_or_none(prev0), ptr(note_out), _ptr_or_none(prev_out), ptr(forced_t), ptr(codes),
@@ -555,16 +547,31 @@ def _rings_from_workspace(eng, U, T):
                       for i, d in enumerate(eng.dil)], 1).contiguous()
 
 
+def _prime(net, start_pieces, classes=None, rows=1):
+    """THE prompt stage of every generator: the full forward over the U start pieces ``(U, Q, receptive_field)`` and the state it
+    leaves -> (engine, probabilities (rows U, Q), rings (rows U, ring floats), prev0 (rows U, k-1, Q): the causal layer's queue =
+    the last k-1 input columns, oldest first, the classes of the rows).  ``rows`` = 2 is guidance: every utterance becomes a pair of
+    rows, as its class and as ``net.null_class``, [c_u, null_class] interleaved, for the forward and for the class tables."""
+    assert start_pieces.dim() == 3 and start_pieces.size(2) == net.receptive_field
+    dev = start_pieces.device if start_pieces.is_cuda else torch.device("cuda")
+    x = start_pieces.detach().to(dev).float()
+    if rows == 2:
+        cls = classes.detach().cpu().tolist() if isinstance(classes, torch.Tensor) else [int(c) for c in classes]
+        if len(cls) != x.size(0):
+            raise ValueError("music_amd: classes must be %d integers, one per clip" % x.size(0))
+        classes = [v for c in cls for v in (int(c), int(net.null_class))]
+        x = x.repeat_interleave(2, 0)
+    x = x.contiguous()
+    with torch.no_grad():
+        probs = net(x) if classes is None else net(x, classes=classes)     # (rows U, Q): W == 1
+    eng, n, T = net._engine, x.size(0), x.size(2)
+    return eng, probs.view(n, -1), _rings_from_workspace(eng, n, T), x[:, :, T - _taps(eng):T].transpose(1, 2).contiguous(), classes
+
+
 def _init_forward(net, note, classes=None):
     """The full forward over a ``(1, Q, receptive_field)`` piece: (probabilities (1, Q), the queues it leaves)."""
-    assert note.size()[2] == net.receptive_field
-    dev = note.device if note.is_cuda else torch.device("cuda")
-    x = note.detach().to(dev).float().contiguous()
-    with torch.no_grad():
-        probs = net(x) if classes is None else net(x, classes=classes)     # (1, Q): W == 1
-    eng, T, K1 = net._engine, x.size(2), _taps(net._engine)
-    # the causal layer's queue = the last k-1 input columns
-    return probs, DecodeState(eng, _rings_from_workspace(eng, 1, T)[0], x[0, :, T - K1:T].t().contiguous().view(-1), 0)
+    eng, probs, rings, prev0, _ = _prime(net, note, classes)
+    return probs, DecodeState(eng, rings[0], prev0.view(-1), 0)
 
 
 def predict_next(net, note, state_queue=None, correct_queue=False):
@@ -601,23 +608,19 @@ def generate_codes(net, start_piece, note_num, correct_queue=False, temperature=
         return generate_codes_batch(net, start_piece, note_num, correct_queue=correct_queue, temperature=temperature, seed=seed,
                                     top_k=top_k, top_p=top_p, windows=windows, window_pos=window_pos, classes=classes,
                                     guidance=guidance)[0]
-    win = _windows_of(windows, window_pos, net.quantization_channels)
-    _need_corrected_win(win, correct_queue)
+    win = _windows_of(windows, window_pos, net.quantization_channels, correct_queue)
     _check_classes(net, classes)
-    with torch.no_grad():
-        if win is None and classes is None:
-            first, state = predict_next(net, start_piece, None)
-        else:
-            probs, state = _init_forward(net, start_piece, classes)
-            first = probs.view(1, -1).argmax(1) if win is None else _first_in_window(probs.view(1, -1), win)
-    cond, keep = _class_cond(net, state.eng, classes, 1, correct_queue)
+    probs, state = _init_forward(net, start_piece, classes)
+    # (the plain call picks as predict_next does, with the reference's topk: the argmax, whatever either makes of a tie)
+    first = torch.topk(probs.view(-1), 1)[1] if win is None and classes is None else _first_codes(probs, win)
+    eng = state.eng
+    cond, keep = _class_cond(net, eng, classes, 1, correct_queue)
     if note_num <= 1:
-        return first.to(state.eng.device)[:note_num]
-    note0 = torch.zeros(net.quantization_channels, dtype=torch.float32, device=state.eng.device)
-    note0[int(first[0])] = 1.0
-    codes, _, _ = _decode(net, state, note0, note_num - 1, correct_queue=correct_queue, temperature=temperature, seed=seed,
-                          top_k=top_k, top_p=top_p, win=win.tail(1) if win is not None else None, cond=cond)
-    return torch.cat([first.to(codes.device).to(torch.int64), codes.to(torch.int64)])
+        return first[:note_num]
+    codes, _, _ = _decode(net, state, _note0(first, 1, eng.Q, eng.device)[0], note_num - 1, correct_queue=correct_queue,
+                          temperature=temperature, seed=seed, top_k=top_k, top_p=top_p, win=win.tail(1) if win is not None else None,
+                          cond=cond)
+    return torch.cat([first.to(torch.int64), codes.to(torch.int64)])
 
 
 def generate_codes_batch(net, start_pieces, note_num, correct_queue=False, temperature=None, seed=0, top_k=None, top_p=None,
@@ -640,70 +643,33 @@ def generate_codes_batch(net, start_pieces, note_num, correct_queue=False, tempe
     Corrected recurrence only; None is the call without the argument, launch for launch."""
     assert start_pieces.dim() == 3 and start_pieces.size(2) == net.receptive_field
     _check_classes(net, classes)
-    win = _windows_of(windows, window_pos, net.quantization_channels)
-    _need_corrected_win(win, correct_queue)
+    win = _windows_of(windows, window_pos, net.quantization_channels, correct_queue)
     U = start_pieces.size(0)
     guide = _guidance_of(net, guidance, U, correct_queue, classes)
-    if guide is not None:
-        return _generate_guided(net, start_pieces, note_num, guide, temperature, seed, top_k, top_p, streams, win, classes)
-    if U > 1024:
-        raise ValueError("at most 1024 utterances per launch (128 off the matrix-core path)")
-    dev = start_pieces.device if start_pieces.is_cuda else torch.device("cuda")
-    x = start_pieces.detach().to(dev).float().contiguous()
-    with torch.no_grad():
-        probs = net(x) if classes is None else net(x, classes=classes)     # (U, Q): W == 1
-    eng = net._engine
-    cond, keep = _class_cond(net, eng, classes, U, correct_queue)
-    T, Q, K1 = x.size(2), eng.Q, _taps(eng)
-    rings = _rings_from_workspace(eng, U, T)
-    first = probs.view(U, Q).argmax(1) if win is None else _first_in_window(probs.view(U, Q), win)
+    rows = 1 if guide is None else 2                                # guided: every utterance is a pair of rows [c_u, null_class]
+    if rows * U > 1024:
+        raise ValueError("at most 1024 utterances per launch (128 off the matrix-core path)" if guide is None else
+                         "at most 512 guided utterances per launch (64 off the matrix-core path): every one is a pair of rows")
+    eng, probs, rings, prev0, row_classes = _prime(net, start_pieces, classes, rows)
+    cond, keep = _class_cond(net, eng, row_classes, rows * U, correct_queue)
+    first = _first_codes(probs, win, guide)
     if note_num <= 1:
         return first.view(U, 1)[:, :note_num]
     _check_recurrence(eng, correct_queue)
-    smp = _Sampling(U, temperature, top_k, top_p, seed, streams, dev)
+    dev = eng.device
+    if guide is not None:
+        # both members of a pair carry the utterance's settings and stream id (the launch reads the conditional member's)
+        pair = lambda v: v if _per_row(v, U) is None else [e for e in _per_row(v, U) for _ in (0, 1)]
+        temperature, top_k, top_p, seed = pair(temperature), pair(top_k), pair(top_p), pair(seed)
+        streams = pair(list(range(U)) if streams is None else streams)
+    smp = _Sampling(rows * U, temperature, top_k, top_p, seed, streams, dev)
     _need_corrected(smp, correct_queue)
-    note0 = torch.zeros(U, Q, dtype=torch.float32, device=dev)
-    note0[torch.arange(U, device=dev), first] = 1.0
-    prev0 = x[:, :, T - K1:T].transpose(1, 2).contiguous()         # [U][k-1][Q], oldest column first
-    codes, _, _, _ = _launch_decode(net, eng, smp, rings, note0, prev0, U, note_num - 1, 0, 1 if correct_queue else 0,
-                                    "wn_decode_batch: a hand-off between two decode workgroups timed out", check=note_num - 1 >= 4,
-                                    win=win.tail(1) if win is not None else None, cond=cond)
-    return torch.cat([first.view(U, 1).to(torch.int64), codes.to(torch.int64)], 1)
-
-
-def _generate_guided(net, start_pieces, note_num, guide, temperature, seed, top_k, top_p, streams, win, classes):
-    """generate_codes_batch under guidance: the rows doubled as [c_u, null_class] interleaved for the init forward and for the
-    class tables, one wn_cfg_decode_batch launch through _launch_decode, the even rows returned."""
-    U = start_pieces.size(0)
-    if 2 * U > 1024:
-        raise ValueError("at most 512 guided utterances per launch (64 off the matrix-core path): every one is a pair of rows")
-    dev = start_pieces.device if start_pieces.is_cuda else torch.device("cuda")
-    cls = classes.detach().cpu().tolist() if isinstance(classes, torch.Tensor) else [int(c) for c in classes]
-    if len(cls) != U:
-        raise ValueError("music_amd: classes must be %d integers, one per clip" % U)
-    cls2 = [v for c in cls for v in (int(c), int(net.null_class))]
-    x = start_pieces.detach().to(dev).float().repeat_interleave(2, 0).contiguous()
-    with torch.no_grad():
-        probs = net(x, classes=cls2)                                # (2U, Q): W == 1
-    eng = net._engine
-    cond, keep = _class_cond(net, eng, cls2, 2 * U, True)
-    T, Q, K1 = x.size(2), eng.Q, _taps(eng)
-    rings = _rings_from_workspace(eng, 2 * U, T)
-    first = _first_guided(probs.view(2 * U, Q), guide, win)
-    if note_num <= 1:
-        return first.view(U, 1)[:, :note_num]
-    _check_recurrence(eng, True)
-    # both members of a pair carry the utterance's settings and stream id (the launch reads the conditional member's)
-    smp = _Sampling(2 * U, _paired(temperature, U), _paired(top_k, U), _paired(top_p, U), _paired(seed, U),
-                    _paired(list(range(U)) if streams is None else streams, U), dev)
-    note0 = torch.zeros(2 * U, Q, dtype=torch.float32, device=dev)
-    note0[torch.arange(2 * U, device=dev), first.repeat_interleave(2)] = 1.0
-    prev0 = x[:, :, T - K1:T].transpose(1, 2).contiguous()
-    gtab = torch.tensor(guide, dtype=torch.float32, device=dev)
-    codes, _, _, _ = _launch_decode(net, eng, smp, rings, note0, prev0, 2 * U, note_num - 1, 0, 1,
-                                    "wn_cfg_decode_batch: a hand-off between two decode workgroups timed out", check=note_num - 1 >= 4,
-                                    win=win.tail(1) if win is not None else None, cond=cond, guide=gtab)
-    return torch.cat([first.view(U, 1).to(torch.int64), codes[0::2].to(torch.int64)], 1)
+    codes, _, _, _ = _launch_decode(net, eng, smp, rings, _note0(first, rows, eng.Q, dev), prev0, rows * U, note_num - 1, 0,
+                                    1 if correct_queue else 0, "%s: a hand-off between two decode workgroups timed out"
+                                    % ("wn_decode_batch" if guide is None else "wn_cfg_decode_batch"), check=note_num - 1 >= 4,
+                                    win=win.tail(1) if win is not None else None, cond=cond,
+                                    guide=None if guide is None else torch.tensor(guide, dtype=torch.float32, device=dev))
+    return torch.cat([first.view(U, 1).to(torch.int64), codes[0::rows].to(torch.int64)], 1)
 
 
 def decode_batch_cond(net, rings, prev0, note0, n_steps, step0=0, pos0=0, forced=None, want_probs=False, temperature=None,
@@ -723,8 +689,8 @@ def decode_batch_cond(net, rings, prev0, note0, n_steps, step0=0, pos0=0, forced
     Returns (codes int32 (U, n_steps), probabilities (U, n_steps, Q) or None, note_out, prev_out)."""
     eng = net._engine_for(rings.device)
     pack = _pack_for(net, eng)
-    dev, N, K1, U = eng.device, eng.N, _taps(eng), rings.size(0)
-    n_ring = max(1, sum(K1 * d * pack.Rp for d in eng.dil))
+    dev, N, U = eng.device, eng.N, rings.size(0)
+    n_ring = max(1, int(_ring_offsets(eng)[-1]))
     if rings.dim() != 2 or rings.size(1) != n_ring or not rings.is_contiguous():
         raise ValueError("decode_batch_cond: rings must be (U, %d) contiguous floats" % n_ring)
     if U > (1024 if pack.mfma else 128):

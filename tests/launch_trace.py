@@ -16,7 +16,8 @@ a replaced table) is "tmp<k>" in order of first appearance.  None stays None, ct
 address (the data_ptr() integers the flat optimizers and GradGuard pass) inside an owner's memory is written exactly as a pointer is,
 so code may pass either; any other integer of 2^40 or more fails the recording.
 
-A third set, the optimizer steps (OPTIMIZER_CASES, record_optimizer, tests/golden/launch_traces_optimizers.json), is at the end."""
+A third set, the optimizer steps (OPTIMIZER_CASES, record_optimizer, tests/golden/launch_traces_optimizers.json), and a fourth, the
+generators (DECODE_CASES, record_decode, tests/golden/launch_traces_decode.json), are at the end."""
 import ctypes
 import hashlib
 import json
@@ -552,3 +553,225 @@ def record_optimizer(name, monkeypatch):
         forms.append(_optimizer_forms(eng, opt, prev))
         del trace[:]
     return out, {}, {"steps": forms}
+
+
+# ---------------------------------------------------------------- the generators (tests/golden/launch_traces_decode.json)
+# What music_amd/fast_generate.py and ae_generate.py launch between a prompt and the persistent decode kernel: the init forward, the
+# class tables, the weight pack's refresh and the decode entry with every argument, for each public way in.  Beyond install():
+# wavenet._engine_for builds its engine on the CPU (the module's own choice between the fast and the general one), ctypes.cast hands
+# a host array through (it is then written out by value: dilations, ring offsets, window pairs, schedules), .cuda() is the identity.
+# Owners: the engine, every workspace of its pool ("ws<B>x<T>"), the decode weight pack and the cached hand-off scratch.  The init
+# forward's probabilities are never written here, so the first code is arbitrary: it enters no launch argument.
+DEC_DIL, DEC_U, DEC_N = [1, 2, 4], 3, 12
+DEC_CLASSES = [0, 1, 2]
+
+
+def _halves(Q):
+    return [(0, Q // 2), (Q // 2, Q)]
+
+
+def _dec_net(kind):
+    from music_amd.model import wavenet
+    torch.manual_seed(0)
+    if kind == "general":                                    # filter_width 3, Q = 100: the general plan and the fp32 decode kernel
+        return wavenet(3, DEC_DIL, 40, 48, 96, 100, False)
+    extra = dict(global_classes=4, global_channels=8, null_class=3) if kind == "classes" else {}
+    return wavenet(2, DEC_DIL, 64, 64, 256, 256, kind == "bias", **extra)      # the matrix-core pack
+
+
+def _prompt(net, U):
+    return on_device(torch.zeros(U, net.quantization_channels, net.receptive_field))
+
+
+def _gen(batch, note_nums=(DEC_N,), **kw):
+    def run(fg, net):
+        for n in note_nums:
+            out = (fg.generate_codes_batch if batch else fg.generate_codes)(net, _prompt(net, DEC_U if batch else 1), n, **kw)
+            assert tuple(out.shape) == ((DEC_U, n) if batch else (n,)) and out.dtype == torch.int64
+    return run
+
+
+def _predict(fg, net):
+    Q = net.quantization_channels
+    col = lambda: on_device(torch.zeros(1, Q, 1))
+    _, state = fg.predict_next(net, _prompt(net, 1))
+    corrected = net.filter_width != 2
+    fg.predict_next(net, col(), state, correct_queue=corrected)
+    fg.predict_next(net, col(), state, correct_queue=True)
+    fg.predict_next(net, col(), dict(state.items()), correct_queue=True)       # reference-style tensors: DecodeState.from_tensors
+
+
+def _explicit(U, **kw):
+    """decode_batch_cond from explicit state: zero rings of the pack's ring size, five steps"""
+    def run(fg, net):
+        from music_amd.ae_generate import cond_schedule
+        eng = net._engine_for(torch.device("cpu"))
+        pack, K1, n = fg._pack_for(net, eng), net.filter_width - 1, 5
+        rings = torch.zeros(U, max(1, sum(K1 * d * pack.Rp for d in eng.dil)))
+        a = dict(kw)
+        if a.pop("tables", False):
+            a.update(cond_fg=torch.zeros(U, eng.N, 2, 2 * pack.Dp), cond_p1=torch.zeros(U, 2, eng.S),
+                     schedule=cond_schedule((net.filter_width, eng.dil), n, 2), forced=torch.zeros(U, n, dtype=torch.int64))
+        fg.decode_batch_cond(net, rings, torch.zeros(U, K1, eng.Q), torch.zeros(U, eng.Q), n, step0=2, pos0=1, **a)
+    return run
+
+
+def _sampler(**kw):
+    def run(fg, net):
+        a = dict(kw)
+        if a.pop("with_u", False):
+            a["logits_u"] = on_device(torch.zeros(5, 256))
+        fg.sample_logits(on_device(torch.zeros(5, 256)), **a)
+    return run
+
+
+def _ae_resynthesize(fg, net):
+    from music_amd import ae_generate
+    torch.manual_seed(3)
+    ae_generate.resynthesize(net, torch.zeros(2, 256, net.receptive_field + 99), temperature=0.9, seed=2)
+
+
+def _ae_decode_codes(fg, net):
+    from music_amd import ae_generate
+    ae_generate.decode_codes(net, torch.zeros(2, 2, dtype=torch.int64), 80, temperature=0.9, seed=2)
+
+
+_W256 = dict(correct_queue=True, windows=_halves(256), window_pos=5)
+_TABLES = dict(correct_queue=True, temperature=[0.5, 0.8, 1.0], top_k=[0, 40, 5], seed=[1, 2, 3], streams=[4, 5, 6])
+_CLS1, _CLS = dict(correct_queue=True, classes=[1]), dict(correct_queue=True, classes=DEC_CLASSES)
+# name -> (model of _dec_net, or a builder of the module, or None; run(fast_generate, module))
+DECODE_CASES = {
+    "one": ("fast", _gen(False)),
+    "one_sampled": ("fast", _gen(False, correct_queue=True, temperature=0.9, top_k=20, seed=3)),
+    "one_windows": ("fast", _gen(False, **_W256)),
+    "batch": ("fast", _gen(True)),
+    "batch_tables": ("fast", _gen(True, **_TABLES)),
+    "batch_windows": ("fast", _gen(True, **_W256)),
+    "batch_bias": ("bias", _gen(True)),
+    "classes_one": ("classes", _gen(False, **_CLS1)),
+    "classes_batch": ("classes", _gen(True, **_CLS)),
+    "guided_one": ("classes", _gen(False, guidance=2.0, temperature=0.9, seed=3, **_CLS1, **{k: v for k, v in _W256.items() if k != "correct_queue"})),
+    "guided_batch_scalar": ("classes", _gen(True, guidance=2.0, streams=[4, 5, 6], temperature=0.9, seed=3, classes=DEC_CLASSES, **_W256)),
+    "guided_batch": ("classes", _gen(True, guidance=[0.5, 1.0, 2.5], classes=DEC_CLASSES, windows=_halves(256), window_pos=5, **_TABLES)),
+    "guidance_none_one": ("classes", _gen(False, guidance=None, **_CLS1)),
+    "guidance_none_batch": ("classes", _gen(True, guidance=None, **_CLS)),
+    "general_one": ("general", _gen(False, correct_queue=True)),
+    "general_batch": ("general", _gen(True, correct_queue=True)),
+    "short_one": ("fast", _gen(False, (0, 1))),
+    "short_batch": ("fast", _gen(True, (0, 1))),
+    "short_guided": ("classes", _gen(True, (0, 1), guidance=2.0, **_CLS)),
+    "predict_next": ("fast", _predict),
+    "predict_next_general": ("general", _predict),
+    "explicit": ("fast", _explicit(3)),
+    "explicit_tables": ("fast", _explicit(3, tables=True, want_probs=True, temperature=0.9, top_p=0.8, seed=4)),
+    "explicit_guided": ("fast", _explicit(4, tables=True, guidance=[1.5, 0.5], windows=_halves(256), window_pos=2)),
+    "explicit_general": ("general", _explicit(3)),
+    "sample_logits": (None, _sampler(temperature=0.8, top_k=5, seed=2, step0=3)),
+    "sample_logits_windows": (None, _sampler(temperature=[0.5, 0.6, 0.7, 0.8, 0.9], windows=_halves(256), window_pos=3)),
+    "sample_logits_guided": (None, _sampler(guidance=[0.5, 1.0, 1.5, 2.0, 2.5], with_u=True, windows=_halves(256), window_pos=3)),
+    "ae_resynthesize": (lambda: _ae_net(64, 64), _ae_resynthesize),
+    "ae_decode_codes": (lambda: _ae_net(64, 64, conditioning="learned", bottleneck="vq", vq_codes=OPT_K), _ae_decode_codes),
+}
+
+
+def _cpu_engine_for(self, device=None):
+    """model.wavenet._engine_for on device="cpu": the same choice of engine, the parameters views of its flat buffer"""
+    from music_amd.engine import WaveNetEngine
+    from music_amd.engine_generic import GenericWaveNetEngine
+    if self._engine is None:
+        fast = self.filter_width == 2 and self.quantization_channels == 256 and max(self.residual_channels, self.dilation_channels) <= 64
+        eng = (WaveNetEngine if fast else GenericWaveNetEngine)(
+            self.dilations, self.residual_channels, self.dilation_channels, self.skip_channels, self.quantization_channels, self.filter_width,
+            self.use_bias, mode_fwd=self.precision[0], mode_bwd=self.precision[1], device="cpu",
+            **(dict(global_classes=self.global_classes, global_channels=self.global_channels) if self.global_classes else {}))
+        eng.mode_names = tuple(self.precision)
+        with torch.no_grad():
+            for name, p in self._named_ref_params():
+                view = eng.param_view(name)
+                view.copy_(p.data)
+                p.data = view
+        self._engine = eng
+    return self._engine
+
+
+def _decode_owners(nets):
+    out = []
+    for j, net in enumerate(nets):
+        eng, tag = net._engine, "" if j == 0 else str(j)
+        if eng is None:
+            continue
+        _tensors(vars(eng), "eng" + tag, out)
+        for (B, T), lst in eng._ws._d.items():
+            for k, ws in enumerate(lst):
+                _tensors({key: v for key, v in ws.items() if key != "bwd"}, "ws%s_%dx%d_%d" % (tag, B, T, k), out)
+        pack = getattr(net, "_decode_pack", None)
+        _tensors({k: getattr(pack, k, None) for k in ("buf", "idx", "pk", "pk_idx")} if pack is not None else {}, "pack" + tag, out)
+        _tensors(getattr(net, "_decode_sync", None), "sync" + tag, out)
+    return [_span(key, t) for key, t in out if t.numel()]
+
+
+def _values(trace, own):
+    """What a pointer's name does not say, per launch: shape and dtype of every tensor no owner holds (note0, prev0, the rings, the
+    class tables, the outputs), the bytes of a sampling table (the one uint8 tensor) as a hash, and the floats of a guidance table
+    (the last pointer of the wn_cfg_* entries)."""
+    out = []
+    for n, item in enumerate(trace):
+        if item[0] in ("record", "wait", "mark"):
+            continue
+        name, args = item
+        ptrs = [(j, a) for j, a in enumerate(args) if isinstance(a, Ptr)]
+        vals = {}
+        for j, a in ptrs:
+            if not any(lo <= a.addr < hi for _, lo, hi, _ in own):
+                vals[str(j)] = [list(a.t.shape), str(a.t.dtype)]
+                if a.t.dtype == torch.uint8:
+                    vals[str(j)].append(hashlib.sha256(a.t.numpy().tobytes()).hexdigest())
+        if name.startswith("wn_cfg_"):
+            vals["guidance"] = [float(v) for v in ptrs[-1][1].t.tolist()]
+        if vals:
+            out.append([n, name, vals])
+    return out
+
+
+def _decode_pack_maps(pack):
+    """the decode weight pack's index maps by hash and its offsets by value"""
+    if pack is None:
+        return {}
+    h = lambda t: None if t is None else hashlib.sha256(t.numpy().tobytes()).hexdigest()
+    out = {k: getattr(pack, k, None) for k in ("k", "mfma", "Rp", "Dp", "o_causal", "o_layers", "layer_stride", "o_p1", "o_p2", "o_bias",
+                                               "pk_off", "pk_stride")}
+    return dict(out, idx=h(pack.idx), pk_idx=h(getattr(pack, "pk_idx", None)))
+
+
+def record_decode(name, monkeypatch):
+    """-> (canonical trace, pack-map hashes of the engine and the decode pack, {"values": what the trace cannot name}) of one case."""
+    from music_amd import ae_generate, fast_generate as fg, model, model1  # noqa: F401 (imported so that install() patches them)
+    build, run = DECODE_CASES[name]
+    for k in SWITCHES + ("WN_DEC_MFMA", "WN_DEC_T0"):
+        monkeypatch.delenv(k, raising=False)
+    trace = install(monkeypatch)
+    real_cast = ctypes.cast
+    monkeypatch.setattr(ctypes, "cast", lambda a, t: a if isinstance(a, ctypes.Array) and t is ctypes.c_void_p else real_cast(a, t))
+    monkeypatch.setattr(model.wavenet, "_engine_for", _cpu_engine_for)
+    # the autoencoder's cases: the clips and both modules stay where they are, the engine is built on the CPU
+    made = []
+    monkeypatch.setattr(torch.Tensor, "cuda", lambda self, *a, **k: on_device(self))
+    monkeypatch.setattr(torch.nn.Module, "cuda", lambda self, *a, **k: made.append(self) or self)
+
+    def ae_engine_for(self, device=None):
+        if self._engine is None:
+            self._engine = model1._AutoencoderEngine(self, torch.device("cpu"))
+        return self._engine
+    monkeypatch.setattr(model1.wavenet_autoencoder, "_engine_for", ae_engine_for)
+    net = None if build is None else _dec_net(build) if isinstance(build, str) else build()
+    del trace[:]
+    with np.errstate(all="ignore"), torch.no_grad():
+        run(fg, net)
+    nets = [] if net is None else [net] + [m for m in made if m is not net]
+    own = _decode_owners(nets)
+    packs = {}
+    for j, m in enumerate(nets):
+        if m._engine is not None:
+            packs["engine%d" % j] = pack_maps(m._engine, PACK_KEYS_ALL)
+            packs["decode%d" % j] = _decode_pack_maps(getattr(m, "_decode_pack", None))
+    return canonical(trace, None, None, own), packs, {"values": _values(trace, own)}

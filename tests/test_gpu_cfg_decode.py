@@ -64,17 +64,10 @@ def test_teacher_forced_guided_probabilities_are_the_objectives(name, windows, m
     bars = torch.tensor([PROB_TOL * cr.amp([s]) for s in guide], dtype=torch.float64).view(U, 1, 1)
     assert bool(((want.cpu() - r64).abs() <= bars).all())
     # init forward over the first rf samples, rows doubled as [c, null], then n teacher-forced steps of the guided launch
-    x2 = x.repeat_interleave(2, 0)
-    cls2 = [v for c in classes for v in (c, cfg["null_class"])]
-    with torch.no_grad():
-        net(x2[:, :, :rf].contiguous(), classes=cls2)
-    eng = net._engine
+    eng, _, rings, prev0, cls2 = fg._prime(net, x[:, :, :rf], classes, 2)
     assert fg._mfma_decode(eng) == (name == "mfma")
-    rings = fg._rings_from_workspace(eng, 2 * U, rf)
     cond, keep = fg._class_cond(net, eng, cls2, 2 * U, True)
-    K1 = cfg["filter_width"] - 1
-    prev0 = x2[:, :, rf - K1:rf].transpose(1, 2).contiguous()
-    note0 = x2[:, :, rf].contiguous()
+    note0 = x[:, :, rf].repeat_interleave(2, 0).contiguous()
     forced = torch.cat([codes[:, rf + 1:], torch.zeros(U, 1, dtype=torch.int64)], 1).to(torch.int32).repeat_interleave(2, 0)
     smp = fg._Sampling(2 * U, None, None, None, 0, None, eng.device)
     wtail = fg._windows_of(win, p0, Q).tail(1) if win else None

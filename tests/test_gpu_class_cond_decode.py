@@ -55,14 +55,9 @@ def test_teacher_forced_probabilities_are_the_forwards(name, windows, monkeypatc
                                     x.cpu().double(), torch.tensor(classes), cfg["filter_width"]), win, p0 if win else None).view(U, n + 1, Q)
     assert float((want.cpu().double() - p64).abs().max()) <= PROB_TOL
     # init forward over the first rf samples with the classes, then n teacher-forced steps of the conditioned launch
-    with torch.no_grad():
-        net(x[:, :, :rf].contiguous(), classes=classes)
-    eng = net._engine
+    eng, _, rings, prev0, _ = fg._prime(net, x[:, :, :rf], classes)
     assert fg._mfma_decode(eng) == (name == "mfma")
-    rings = fg._rings_from_workspace(eng, U, rf)
     cond, keep = fg._class_cond(net, eng, classes, U, True)
-    K1 = cfg["filter_width"] - 1
-    prev0 = x[:, :, rf - K1:rf].transpose(1, 2).contiguous()
     note0 = x[:, :, rf].contiguous()
     forced = torch.cat([codes[:, rf + 1:], torch.zeros(U, 1, dtype=torch.int64)], 1).to(torch.int32)
     smp = fg._Sampling(U, None, None, None, 0, None, eng.device)
@@ -79,9 +74,7 @@ def test_teacher_forced_probabilities_are_the_forwards(name, windows, monkeypatc
     # another class: another distribution (the table reaches the launch)
     other = [(c + 1) % cfg["global_classes"] for c in classes]
     cond2, keep2 = fg._class_cond(net, eng, other, U, True)
-    with torch.no_grad():
-        net(x[:, :, :rf].contiguous(), classes=other)
-    rings2 = fg._rings_from_workspace(eng, U, rf)
+    rings2 = fg._prime(net, x[:, :, :rf], other)[2]
     _, probs2, _, _ = fg._launch_decode(net, eng, smp, rings2, note0, prev0, U, n, 0, 1, "decode hand-off timed out", forced=forced,
                                         want_probs=True, cond=cond2, win=wtail)
     assert float((probs2 - probs).abs().max()) > 10 * PROB_TOL

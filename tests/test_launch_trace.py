@@ -12,6 +12,9 @@ optimizers of music_amd/train.py and of the fused step's adam_step - plain and g
 EMA-updated codebook - over short scripted sequences, with the steps that launch nothing (torch's path) and the optimizer's state
 after every step.
 
+A fourth file, tests/golden/launch_traces_decode.json (--set decode), pins the generators: what fast_generate.py and ae_generate.py
+launch between a prompt and the persistent decode kernel, every public way in.
+
 The recording itself (what is stubbed, how pointers are named) is tests/launch_trace.py.  No device is touched."""
 import json
 import os
@@ -202,3 +205,57 @@ def test_optimizer_launch_trace_is_the_recorded_one(name, golden_optimizers, mon
         want = dict(want, forms={"steps": [dict(st, fresh=None) for st in want["forms"]["steps"]]})
         forms = {"steps": [dict(st, fresh=None) for st in forms["steps"]]}
     _same(want, trace, packs, forms)
+
+
+# ---------------------------------------------------------------- the generators
+GOLDEN_DECODE = os.path.join(os.path.dirname(GOLDEN), "launch_traces_decode.json")
+
+
+@pytest.fixture(scope="module")
+def golden_decode():
+    with open(GOLDEN_DECODE) as f:
+        return json.load(f)
+
+
+def test_the_recorded_decode_cases_hold_the_forms_they_are_there_for(golden_decode):
+    """What the fourth file pins (tests/golden/launch_traces_decode.json, tools/record_launch_trace.py --write --set decode at the commit
+    it names): everything music_amd/fast_generate.py and ae_generate.py launch between a prompt and the persistent decode kernel, for
+    every public way in - and what no pointer's name says (the shapes of note0 / prev0 / rings / tables, the sampling table's bytes,
+    the guidance scales) by value, under "forms"."""
+    g = golden_decode
+    assert len(g["recorded_at"]) == 40 and sorted(g["cases"]) == sorted(lt.DECODE_CASES) and os.path.getsize(GOLDEN_DECODE) < 1 << 20
+    entries = lambda name: [i[1] for i in g["cases"][name]["trace"] if i[0] == "call"]
+    args = lambda name: [i[3] for i in g["cases"][name]["trace"] if i[0] == "call"][-1]
+    values = lambda name: g["cases"][name]["forms"]["values"][-1][2]
+    decode = lambda name: [e for e in entries(name) if "decode" in e]
+    assert entries("batch")[-3:] == ["wn_gather_grads", "wn_pack_weights", "wn_decode_batch_fw"] and len(g["cases"]["batch"]["trace"]) == 11
+    assert len(g["cases"]["guided_batch"]["trace"]) == 24
+    for name, entry in (("one", "wn_decode_batch_fw"), ("one_sampled", "wn_decode_batch_samp"), ("one_windows", "wn_win_decode_batch"),
+                        ("batch_tables", "wn_decode_batch_samp"), ("batch_windows", "wn_win_decode_batch"), ("batch_bias", "wn_decode_batch_fw"),
+                        ("classes_one", "wn_decode_batch_cond"), ("classes_batch", "wn_decode_batch_cond"), ("guided_one", "wn_cfg_decode_batch"),
+                        ("guided_batch", "wn_cfg_decode_batch"), ("guided_batch_scalar", "wn_cfg_decode_batch"),
+                        ("general_one", "wn_decode_batch_fw"), ("general_batch", "wn_decode_batch_fw"), ("explicit", "wn_decode_batch_cond"),
+                        ("explicit_tables", "wn_decode_batch_samp"), ("explicit_guided", "wn_cfg_decode_batch"),
+                        ("ae_resynthesize", "wn_decode_batch_cond"), ("ae_decode_codes", "wn_decode_batch_cond")):
+        assert decode(name) and set(decode(name)) == {entry}, name
+    for name in ("guidance_none_one", "guidance_none_batch"):          # None is the call without the argument
+        assert g["cases"][name]["trace"] == g["cases"][name.replace("guidance_none", "classes")]["trace"]
+    for name in ("short_one", "short_batch", "short_guided"):          # note_num 0 and 1: two init forwards, no decode launch
+        assert not decode(name) and entries(name)
+    assert entries("predict_next").count("wn_decode_batch_fw") == 3 and entries("predict_next_general").count("wn_decode_batch_fw") == 3
+    assert [entries(n) for n in ("sample_logits", "sample_logits_windows", "sample_logits_guided")] == [
+        ["wn_sample_logits"], ["wn_win_sample_logits"], ["wn_cfg_sample_logits"]]
+    # one utterance: the cached scratch and no utterance stride; the matrix-core pack, the fp32 kernel's absence of one
+    assert args("one")[28] == ["sync", 0] and args("one")[29:31] == [1, 0] and args("batch")[28][0].startswith("tmp") and args("batch")[29:31] == [3, 448]
+    assert args("batch")[33][0] == "pack.pk" and args("general_batch")[33] is None and args("general_batch")[:6] == [3, 3, 48, 40, 96, 100]
+    # by value: the guidance scales, one per utterance, and the doubled rows; the sampling table only where something is per-utterance
+    assert values("guided_batch")["guidance"] == [0.5, 1.0, 2.5] and values("guided_batch_scalar")["guidance"] == [2.0] * 3
+    assert values("guided_one")["guidance"] == [2.0] and args("guided_batch")[29] == 6 and args("guided_one")[29] == 2
+    hashed = lambda name: [v for v in values(name).values() if isinstance(v, list) and len(v) == 3 and v[1] == "torch.uint8"]
+    assert [v[0] for v in hashed("batch_tables")] == [[72]] and [v[0] for v in hashed("guided_batch")] == [[144]] and not hashed("batch_windows")
+    assert hashed("guided_batch")[0][2] != hashed("guided_batch_scalar")[0][2]
+
+
+@pytest.mark.parametrize("name", list(lt.DECODE_CASES))
+def test_decode_launch_trace_is_the_recorded_one(name, golden_decode, monkeypatch):
+    _same(golden_decode["cases"][name], *lt.record_decode(name, monkeypatch))

@@ -4,8 +4,8 @@ events and marks of one step, recorded with `call` replaced) and the hashes of t
 
     python tools/record_launch_trace.py --write            tests/golden/launch_traces.json (run ONCE, at the commit a host refactor starts from;
                                                            tests/test_launch_trace.py compares every later tree with it)
-    python tools/record_launch_trace.py --write --set epilogue     the cases of another set (SETS below: `epilogue`, or `optimizers`, the
-                                                           optimizer steps) into that set's file, or into --out FILE;
+    python tools/record_launch_trace.py --write --set epilogue     the cases of another set (SETS below: `epilogue`, `optimizers`, the
+                                                           optimizer steps, or `decode`, the generators) into that set's file, or into --out FILE;
                                                            --cases a,b narrows either set
     python tools/record_launch_trace.py --dump DIR         one <case>.json per case with one trace item per line, of THIS checkout: diff two
                                                            checkouts' dumps to see which launch moved (--set all: every set)
@@ -23,7 +23,8 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 # set -> (its file under tests/golden, the name of its traced cases in tests/launch_trace.py, ... of its pack-map-only cases)
 SETS = {"steps": ("launch_traces.json", "TRACE_CASES", None),
         "epilogue": ("launch_traces_epilogue.json", "EPILOGUE_CASES", "PACK_CASES"),
-        "optimizers": ("launch_traces_optimizers.json", "OPTIMIZER_CASES", None)}      # recorded by lt.record_optimizer
+        "optimizers": ("launch_traces_optimizers.json", "OPTIMIZER_CASES", None),      # recorded by lt.record_optimizer
+        "decode": ("launch_traces_decode.json", "DECODE_CASES", None)}                 # the generators, by lt.record_decode
 
 
 def lines(trace):
@@ -44,7 +45,8 @@ def main():
     sets = list(SETS) if a.set == "all" else [a.set]
     want = lambda n: not a.cases or n in a.cases.split(",")
     names = [n for s in sets for n in getattr(lt, SETS[s][1]) if want(n)]
-    record = lambda name, mp: (lt.record_optimizer if name in lt.OPTIMIZER_CASES else lt.record)(name, mp)
+    record = lambda name, mp: (lt.record_optimizer if name in lt.OPTIMIZER_CASES else lt.record_decode if name in lt.DECODE_CASES
+                               else lt.record)(name, mp)
     pack_names = [n for s in sets if SETS[s][2] for n in getattr(lt, SETS[s][2]) if want(n)]
     out, pack_only = {}, {}
     for name in names:
