@@ -713,6 +713,15 @@ int wn_mulaw_decode_q(const int32_t* codes, const float* table, int q, float* au
  * note0 / prev0: dense [Q] current and previous input columns; forced: teacher-forced next codes
  * (NULL = feed back the argmax).  codes_out[n_steps] = argmax of the probabilities (first index on
  * ties); probs_out optional.  dilations_host / q_off_host are HOST arrays.
+ * PARTIALLY FORCED DECODE - the rule of `forced`, here and in every decode entry below that takes it, per utterance u and
+ * step s: forced[u][s] >= 0: the input column after step s is the one-hot of that code (teacher forcing; the entry must be
+ * < Q).  forced[u][s] < 0: the step is FREE - the input column is the code the launch chose at step s, exactly as with
+ * forced == NULL.  Nothing else depends on the entry: codes_out[u][s] and probs_out[u][s] are the model's own pick and
+ * distribution at every step, forced or free (the likelihood of kept tokens is read from probs_out); the uniform number of
+ * step s is that of global step step0 + s whether s is forced or free, so a stream's draws do not move with the mask; the
+ * window, top-k, top-p and guidance rules are untouched (under guidance the two members of a pair carry EQUAL forced rows -
+ * the fp32 kernel reads row 2j's - and a free step feeds the pair's one code to both).  A launch with forced == NULL, or
+ * without a negative entry, computes what it computed before this rule was written down, bit for bit.
  * sync: optional device scratch of (n_layers*D + 2) uint64, used by the two-workgroup matrix-core form
  * (wn_decode_batch_pk; hand-offs through tagged 8-byte granules, the last word is an error flag: non-zero = a
  * bounded spin timed out).  wn_decode / wn_decode_batch run one workgroup of fp32 FMAs per utterance
@@ -728,6 +737,8 @@ int wn_decode(int n_layers, int R, int D, int S, int Q, const int32_t* dilations
  * utterances; the reference generates one at a time): weights shared, everything else per utterance with
  * utterance u at queues + u*queues_ustride, note0/prev0/note_out/prev_out + u*Q, forced/codes_out +
  * u*n_steps, probs_out + u*n_steps*Q, sync + u*(n_layers*D + 2).  All utterances share step0 / n_steps.
+ * forced: wn_decode's rule, per utterance and step (a negative entry frees that step of that utterance only); it holds for
+ * every batched entry below (_pk, _fw, _cond, _samp, wn_win_decode_batch, wn_cfg_decode_batch).
  * temperature > 0: SAMPLE each code from softmax(logits / temperature) (inverse CDF, uniform numbers from
  * a counter-based generator keyed by (seed, step0 + step, u): reproducible); <= 0: greedy argmax. */
 int wn_decode_batch(int n_layers, int R, int D, int S, int Q, const int32_t* dilations_host, const int64_t* q_off_host,
@@ -911,7 +922,8 @@ int wn_win_sample_logits(const float* logits, int64_t n, int Q, int64_t ld, cons
  *     same input history and their note_out / prev_out rows are equal.  probs_out row 2j receives the distribution drawn from
  *     (of g) and row 2j + 1 the same values: no row is left unwritten.
  *   - forced, note0 and prev0 stay per row and the caller passes EQUAL rows for the two members of a pair (the fp32 kernel, which
- *     runs both members of a pair in one workgroup, reads row 2j's).
+ *     runs both members of a pair in one workgroup, reads row 2j's).  A negative forced entry (wn_decode's rule) frees the step for
+ *     the pair: its one code is fed to both members.
  *   - guidance == NULL: no table, the launch is wn_win_decode_batch / wn_win_sample_logits bit for bit.
  * The per-launch limits stay per row: 1024 rows on the matrix-core path (512 guided streams), 128 on the fp32 kernel (64).
  *

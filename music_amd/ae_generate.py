@@ -224,8 +224,30 @@ def _decode_from_encoding(net, enc, cond, W, first, prime, forced, free_step=Fal
     return codes, probs
 
 
+def _region_mask(regions, B, W, teacher_forced=False):
+    """``regions=`` of ``resynthesize`` -> None, or the (B, W) bool mask of the output positions inside a region.  Pure host work."""
+    if regions is None:
+        return None
+    if teacher_forced:
+        raise ValueError("resynthesize: regions= says where the clip's samples are fed: pass it without teacher_forced")
+    is_pair = lambda r: isinstance(r, (tuple, list)) and len(r) == 2 and all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in r)
+    if not isinstance(regions, (tuple, list)):
+        raise ValueError("resynthesize: regions must be a list of (a, b) ranges, or one such list per clip")
+    per_clip = [list(regions)] * B if all(is_pair(r) for r in regions) else list(regions)
+    if len(per_clip) != B or not all(isinstance(rs, (tuple, list)) and all(is_pair(r) for r in rs) for rs in per_clip):
+        raise ValueError("resynthesize: regions must be a list of (a, b) ranges, or one such list per clip (%d clips)" % B)
+    mask = torch.zeros(B, W, dtype=torch.bool)
+    for b, rs in enumerate(per_clip):
+        for a, e in rs:
+            if not 0 <= a <= e <= W:
+                raise ValueError("resynthesize: region (%d, %d) of clip %d lies outside the %d output positions (0 <= a <= b <= %d)"
+                                 % (a, e, b, W, W))
+            mask[b, int(a):int(e)] = True
+    return mask
+
+
 def resynthesize(net, clips, cond=None, teacher_forced=False, want_probs=False, temperature=None, seed=0, top_k=None, top_p=None,
-                 streams=None, classes=None, global_vectors=None, stages=None):
+                 streams=None, classes=None, global_vectors=None, stages=None, regions=None):
     """Encode ``clips`` (B, Q, T) one-hot, T >= receptive_field with at least one pooled frame, and regenerate them from the
     encoding with the cached-queue decoder: the encoder runs ONCE, the conditioning projections are drawn ONCE (or taken
     from ``cond``), the per-clip tables (one column per pooled frame and stage) are built on the device, the queues are
@@ -242,7 +264,14 @@ def resynthesize(net, clips, cond=None, teacher_forced=False, want_probs=False, 
     mix of two rows of ``net.global_vectors``), never both: the clips are decoded AS that class - their own for a reconstruction,
     another for a conversion (the encoder takes no class).
     ``stages`` (a residual vq bottleneck): None, an int n or one int per clip in [1, vq_stages] - every clip is quantised with its
-    first n stages (wn_rvq_fwd_n) and decoded from that coarser encoding; ``net.vq_codes`` then holds -1 in the absent stages."""
+    first n stages (wn_rvq_fwd_n) and decoded from that coarser encoding; ``net.vq_codes`` then holds -1 in the absent stages.
+    ``regions``: None, or a list of ``(a, b)`` ranges of output positions, 0 <= a <= b <= W - shared by all clips, or one such list per
+    clip - to regenerate while the rest of the clip is kept (the decoder sees the whole clip's encoding either way): inside a region
+    the model's own codes are fed, outside it the clip's samples, as teacher forcing, in the ONE conditioned launch over the W
+    positions behind the unchanged priming (a negative ``forced`` entry frees its step: include/wavenet_hip.h, wn_decode).  The codes
+    returned are then the composed stream - the clip's samples outside the regions (the model's at position W - 1, which no sample
+    of the clip follows), the model's inside - and the probabilities are the model's at every position.  ``[(0, W)]`` is the free
+    run, ``[]`` feeds what ``teacher_forced=True`` feeds; not together with ``teacher_forced``."""
     if clips.dim() != 3 or clips.size(1) != net.quantization_channel:
         raise ValueError("resynthesize: clips must be (B, %d, T)" % net.quantization_channel)
     x = clips.detach().cuda().float().contiguous()
@@ -251,6 +280,7 @@ def resynthesize(net, clips, cond=None, teacher_forced=False, want_probs=False, 
     W = T - rf + 1
     if W < 1:
         raise ValueError("wave sample not long enough")
+    inside = _region_mask(regions, B, W, teacher_forced)             # (B, W) bool on the host, or None
     eng_cond = net.engine_cond(cond)                                  # (learned conditioning: None, and a given `cond` is refused)
     cond = eng_cond if eng_cond is not None else net.conditioning_projections()
     gvec = global_term(net, B, classes, global_vectors, "resynthesize")
@@ -263,11 +293,18 @@ def resynthesize(net, clips, cond=None, teacher_forced=False, want_probs=False, 
         net.vq_codes, net.last_encoding_pre = eng.vq_codes_of(ws), ws["enc_pre"]
     codes_in = x.argmax(1).to(torch.int32)                            # (B, T)
     forced = None
-    if teacher_forced:
+    if teacher_forced or inside is not None:
         forced = torch.cat([codes_in[:, rf:], torch.zeros(B, 1, dtype=torch.int32, device=x.device)], 1)
+    if inside is not None:
+        inside = inside.to(x.device)
+        forced = torch.where(inside, torch.full_like(forced, -1), forced)
     codes, probs = _decode_from_encoding(net, enc, cond, W, x[:, :, 0].contiguous(), codes_in[:, 1:rf], forced, want_probs=want_probs,
                                          temperature=temperature, seed=seed, top_k=top_k, top_p=top_p, streams=streams, gvec=gvec)
-    return codes.to(torch.int64), probs, enc
+    codes = codes.to(torch.int64)
+    if inside is not None:
+        inside[:, W - 1] = True                                       # (no sample of the clip follows the last position)
+        codes = torch.where(inside, codes, forced.to(torch.int64))
+    return codes, probs, enc
 
 
 def _vq_engine(net, what):
@@ -397,8 +434,28 @@ def split_code_stream(tokens, stages, K):
     return codes.permute(0, 2, 1).contiguous()
 
 
+def join_code_stream(codes, K):
+    """The inverse of ``split_code_stream``: ``codes`` (B, S, Le) integers in [0, K) -> (B, Le * S) int64 tokens, frame-major (l0s0,
+    l0s1, .., l1s0, ..) with token = s * K + code.  A -1 (an absent stage of ``encode_codes(..., stages=n)``, a code still to be
+    sampled) stays -1.  ``split_code_stream(join_code_stream(c, K), S, K) == c`` on complete codes.  Raises on anything else."""
+    c = torch.as_tensor(codes)
+    K = int(K)
+    if K < 1:
+        raise ValueError("join_code_stream: K must be >= 1")
+    if c.is_floating_point() or c.dtype == torch.bool or c.dim() != 3:
+        raise ValueError("join_code_stream: codes must be (B, stages, Le) integers")
+    c = c.to(torch.int64)
+    wrong = (c < -1) | (c >= K)
+    if bool(wrong.any()):
+        b, s, l = (int(v) for v in wrong.nonzero()[0])
+        raise ValueError("join_code_stream: code %d of clip %d at frame %d, stage %d lies outside [0, %d) (-1: no code)"
+                         % (int(c[b, s, l]), b, l, s, K))
+    tok = c + (torch.arange(c.size(1), dtype=torch.int64, device=c.device) * K)[None, :, None]
+    return torch.where(c >= 0, tok, c).permute(0, 2, 1).reshape(c.size(0), -1).contiguous()
+
+
 def sample_code_stream(prior, stages, K, frames, start_tokens, start_pos=0, temperature=None, top_k=None, top_p=None, seed=0,
-                       streams=None, classes=None, guidance=None):
+                       streams=None, classes=None, guidance=None, keep_codes=None):
     """New bottleneck codes from a prior over the interleaved token stream (a ``wavenet`` with ``quantization_channels`` >= stages
     * K trained on tools/vq_codes_dataset.py's output): ``start_tokens`` (U, n0 >= receptive_field) are tokens of a real stream
     whose first token sits at stream position ``start_pos``; their last receptive_field tokens (canonical one-hot) prime the
@@ -409,6 +466,11 @@ def sample_code_stream(prior, stages, K, frames, start_tokens, start_pos=0, temp
     ``classes``: one class per stream for a class-conditional prior (required there, refused elsewhere): stream u is drawn as
     class classes[u], under the same stage windows.  ``guidance``: None, a scale or one per stream - classifier-free guidance
     of a prior with ``null_class`` (``fast_generate.generate_codes_batch``): the guided logits are windowed like the plain ones.
+    ``keep_codes``: (U, stages, frames) integers, a code in [0, K) where the caller has one and -1 where one is to be sampled - the
+    format of ``encode_codes(..., stages=n)``, sliced to the frames generated here.  The kept codes are fed to the prior at their
+    positions and the others drawn GIVEN them, in the same one launch (``generate_codes_batch(keep=)``: coarse-to-fine when the kept
+    codes are a stage prefix; single frames, everything or nothing are as welcome); the result holds the caller's codes where given.
+    A kept code outside [0, K) is refused before any launch.
     Returns ``split_code_stream`` of the generated tokens: (U, stages, frames) int64 codes in [0, K), what ``decode_codes`` takes."""
     try:
         from . import fast_generate as fg
@@ -428,11 +490,21 @@ def sample_code_stream(prior, stages, K, frames, start_tokens, start_pos=0, temp
                          "%d stages (start_pos >= 0)" % (start_pos, t.size(1), stages))
     if int(t.min()) < 0 or int(t.max()) >= Q:
         raise ValueError("sample_code_stream: start_tokens must hold tokens in [0, %d)" % Q)
+    keep = {}
+    if keep_codes is not None:
+        kc = torch.as_tensor(keep_codes)
+        if kc.is_floating_point() or kc.dtype == torch.bool or tuple(kc.shape) != (t.size(0), stages, frames):
+            raise ValueError("sample_code_stream: keep_codes must be (%d, %d, %d) integers (a code in [0, %d), or -1: to be sampled)"
+                             % (t.size(0), stages, frames, K))
+        try:
+            keep["keep"] = join_code_stream(kc, K)
+        except ValueError as e:
+            raise ValueError("sample_code_stream: keep_codes: %s" % e) from None
     dev = next(prior.parameters()).device
     x = torch.nn.functional.one_hot(t[:, -rf:].to(device=dev, dtype=torch.int64), Q).transpose(1, 2).float().contiguous()
     tokens = fg.generate_codes_batch(prior, x, frames * stages, correct_queue=True, temperature=temperature, seed=seed, top_k=top_k,
                                      top_p=top_p, streams=streams, windows=fg.stage_windows(stages, K),
-                                     window_pos=start_pos + t.size(1), classes=classes, guidance=guidance)
+                                     window_pos=start_pos + t.size(1), classes=classes, guidance=guidance, **keep)
     return split_code_stream(tokens, stages, K)
 
 

@@ -529,8 +529,10 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_k(WnDecodeArgs a) {
         }
         wj = dec_win_next(a.win_period, wj);
         __syncthreads();
-        // next input column: the forced code if given (teacher forcing), else the prediction; the causal queue moves up
-        const int nextc = u_forced ? u_forced[step] : s_arg;
+        // next input column: the forced code where one is given (teacher forcing; a negative entry frees the step), else the
+        // prediction; the causal queue moves up
+        int nextc = s_arg;
+        if (u_forced) { const int fc = u_forced[step]; nextc = fc >= 0 ? fc : nextc; }
         for (int j = 0; j < K1; ++j) {
             for (int i = tid; i < a.Q; i += DEC_THREADS) { prev[j * a.Q + i] = prev[(j + 1) * a.Q + i]; }     // (j = k-2: note)
             __syncthreads();
@@ -1024,9 +1026,13 @@ __global__ __launch_bounds__(DEC_MT) void decode_duo_mfma8_k(WnDecodeArgs a) {
             dec_sync();
             if (step + 1 < a.n_steps) { if (T0) history_ahead(); else load_queues(); }
             if (tid < NU) {
+                // the forced entry is asked for in FRONT of the poll (its round trip hides behind the hand-off); a negative one
+                // frees the step: the column's own code (a spare column mirrors its row's entry through ux() like its code)
+                int fc = -1;
+                if (a.forced) fc = a.forced[ux(tid) * a.n_steps + step];
                 float cv = 0.f;
                 dec_poll(cg_of(tid), tag, cv, cg_of(tid) + 1);
-                s_code[tid] = a.forced ? a.forced[ux(tid) * a.n_steps + step] : (int)cv;
+                s_code[tid] = fc >= 0 ? fc : (int)cv;
             }
             dec_sync();
             for (int i = tid; i < NU * Q; i += 256) prev[i] = note[i];

@@ -332,7 +332,7 @@ struct WnDecodeArgs {
     const float* w_p1; const float* b_p1; const float* w_p2; const float* b_p2;   // [S][S], [Q][S]
     const float* note0; const float* prev0;              // [Q] dense: first input column and the one before it
     float* note_out; float* prev_out;                    // [Q] state handed back
-    const int32_t* forced;                               // [n_steps] teacher-forced next codes, or null (greedy)
+    const int32_t* forced;                               // [n_steps] teacher-forced next codes (< 0: that step is free), or null (greedy)
     int32_t* codes_out; float* probs_out;                // [n_steps], [n_steps][Q] or null
     long step0; int n_steps; int push_input;
     int dbg;                                             // WN_DEC_DBG timing diagnostics (wrong results)

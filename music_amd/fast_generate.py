@@ -436,6 +436,54 @@ def _first_codes(probs, win=None, guide=None):
     return torch.from_numpy(lo + np.argmax(comb, axis=1)).to(probs.device)
 
 
+def check_keep(keep, U, note_num, Q, win=None):
+    """The pure checks of ``keep=`` (no device): ``keep`` is (U, note_num) - or (note_num,) for one utterance - integers, every entry
+    a token in [0, Q) that IS the code at its position, or -1: the sampler's choice.  ``win`` (a ``_Windows`` or None): a kept token at
+    position j must lie inside the window of stream position ``win.pos + j``.  Returns the (U, note_num) int64 host tensor."""
+    k = torch.as_tensor(keep)
+    if k.is_floating_point() or k.is_complex() or k.dtype == torch.bool:
+        raise ValueError("keep must hold integers (a token, or -1 for the sampler's choice), got %s" % k.dtype)
+    if k.dim() == 1 and U == 1:
+        k = k.reshape(1, -1)
+    if tuple(k.shape) != (U, note_num):
+        raise ValueError("keep must be (%d, %d) integers, one per utterance and position, got %s" % (U, note_num, tuple(k.shape)))
+    k = k.detach().to(device="cpu", dtype=torch.int64)
+    wrong = (k < -1) | (k >= Q)
+    if bool(wrong.any()):
+        u, j = (int(v) for v in wrong.nonzero()[0])
+        raise ValueError("keep: token %d of utterance %d at position %d is neither -1 nor a token in [0, %d)" % (int(k[u, j]), u, j, Q))
+    if win is not None:
+        lo = torch.tensor([win.at(win.pos + j)[0] for j in range(note_num)], dtype=torch.int64)
+        hi = torch.tensor([win.at(win.pos + j)[1] for j in range(note_num)], dtype=torch.int64)
+        wrong = (k >= 0) & ((k < lo) | (k >= hi))
+        if bool(wrong.any()):
+            u, j = (int(v) for v in wrong.nonzero()[0])
+            raise ValueError("keep: token %d of utterance %d at position %d (stream position %d) lies outside that position's range "
+                             "[%d, %d)" % (int(k[u, j]), u, j, win.pos + j, int(lo[j]), int(hi[j])))
+    return k
+
+
+def _check_forced(forced, Q, what):
+    """``forced=`` of a launch: entries >= Q are refused where the tensor lives on the host (a device tensor travels as it is: no
+    synchronisation); negative entries free their step (include/wavenet_hip.h, wn_decode)."""
+    if forced is not None and not forced.is_cuda and forced.numel() and int(forced.max()) >= Q:
+        raise ValueError("%s: forced holds a code >= Q = %d (a negative entry frees its step)" % (what, Q))
+
+
+def _keep_of(keep, U, note_num, Q, win, correct_queue):
+    """``keep=`` of a generator -> None, or the checked (U, note_num) int64 host tensor; corrected recurrence only."""
+    if keep is None:
+        return None
+    _corrected_only(correct_queue, "keep= (partially forced decode) runs", "wn_decode_batch")
+    return check_keep(keep, U, int(note_num), Q, win)
+
+
+def _resolved(kept, codes):
+    """The fed stream: the kept code where there is one, else the launch's own (``codes``: a device tensor of ``kept``'s shape)."""
+    k = kept.to(codes.device)
+    return torch.where(k >= 0, k, codes.to(torch.int64))
+
+
 def _note0(first, rows, Q, dev):
     """The first input column of a launch, (rows U, Q): the one-hot of every utterance's first code, once per row of the utterance."""
     idx = first.to(dev).repeat_interleave(rows)
@@ -515,8 +563,11 @@ def _launch_decode(net, eng, smp, rings, note0, prev0, U, n_steps, step0, push_i
 
 def _decode(net, state, note0, n_steps, forced=None, want_probs=False, correct_queue=False, temperature=None, seed=0,
             top_k=None, top_p=None, win=None, cond=None):
+    """One launch of one utterance on ``state``.  ``forced`` (n_steps,): the next input codes; a negative entry frees its step (the
+    launch's own code is fed), an entry >= Q is refused when the tensor is a host tensor."""
     eng = state.eng
     _check_recurrence(eng, correct_queue)
+    _check_forced(forced, eng.Q, "wn_decode")
     smp = _Sampling(1, temperature, top_k, top_p, seed, None, eng.device)
     _need_corrected(smp, correct_queue)
     pack = _pack_for(net, eng)
@@ -590,7 +641,7 @@ def predict_next(net, note, state_queue=None, correct_queue=False):
 
 
 def generate_codes(net, start_piece, note_num, correct_queue=False, temperature=None, seed=0, top_k=None, top_p=None,
-                   windows=None, window_pos=0, classes=None, guidance=None):
+                   windows=None, window_pos=0, classes=None, guidance=None, keep=None):
     """The greedy loop of fast_generate.py:162-172 as one init forward + ONE persistent launch.
     Returns the note_num generated codes (int64, on the device).
     ``temperature`` (the reference is greedy only): if given and > 0, every code after the
@@ -603,28 +654,33 @@ def generate_codes(net, start_piece, note_num, correct_queue=False, temperature=
     of the init forward inside its window.  Corrected recurrence only.
     ``classes``: ``[c]``, the class to generate as, for a class-conditional model (required there, refused elsewhere): the init
     forward runs with it and the launch is the conditioned one (wn_decode_batch_cond).  Corrected recurrence only.
-    ``guidance``: a scale s, classifier-free guidance (``generate_codes_batch``; the one-utterance batch of it)."""
+    ``guidance``: a scale s, classifier-free guidance (``generate_codes_batch``; the one-utterance batch of it).
+    ``keep``: (note_num,) or (1, note_num) integers - partially forced decode (``generate_codes_batch``)."""
     if guidance is not None:
         return generate_codes_batch(net, start_piece, note_num, correct_queue=correct_queue, temperature=temperature, seed=seed,
                                     top_k=top_k, top_p=top_p, windows=windows, window_pos=window_pos, classes=classes,
-                                    guidance=guidance)[0]
+                                    guidance=guidance, **({} if keep is None else {"keep": keep}))[0]
     win = _windows_of(windows, window_pos, net.quantization_channels, correct_queue)
     _check_classes(net, classes)
+    kept = _keep_of(keep, 1, note_num, net.quantization_channels, win, correct_queue)
     probs, state = _init_forward(net, start_piece, classes)
     # (the plain call picks as predict_next does, with the reference's topk: the argmax, whatever either makes of a tie)
     first = torch.topk(probs.view(-1), 1)[1] if win is None and classes is None else _first_codes(probs, win)
     eng = state.eng
-    cond, keep = _class_cond(net, eng, classes, 1, correct_queue)
+    cond, tables = _class_cond(net, eng, classes, 1, correct_queue)
+    if kept is not None and note_num >= 1:
+        first = _resolved(kept[:, 0], first)
     if note_num <= 1:
         return first[:note_num]
     codes, _, _ = _decode(net, state, _note0(first, 1, eng.Q, eng.device)[0], note_num - 1, correct_queue=correct_queue,
                           temperature=temperature, seed=seed, top_k=top_k, top_p=top_p, win=win.tail(1) if win is not None else None,
-                          cond=cond)
-    return torch.cat([first.to(torch.int64), codes.to(torch.int64)])
+                          cond=cond, **({} if kept is None else {"forced": kept[0, 1:].to(torch.int32)}))
+    codes = codes.to(torch.int64)
+    return torch.cat([first.to(torch.int64), codes if kept is None else _resolved(kept[0, 1:], codes)])
 
 
 def generate_codes_batch(net, start_pieces, note_num, correct_queue=False, temperature=None, seed=0, top_k=None, top_p=None,
-                         streams=None, windows=None, window_pos=0, classes=None, guidance=None):
+                         streams=None, windows=None, window_pos=0, classes=None, guidance=None, keep=None):
     """SURVEY 8f2 (batched utterances; the reference generates one at a time): greedy generation of
     ``note_num`` codes for U independent start pieces ``(U, Q, receptive_field)`` in ONE persistent
     launch - on the matrix-core path eight utterances to a workgroup pair, one pair of MFMA result columns each (else one
@@ -640,19 +696,29 @@ def generate_codes_batch(net, start_pieces, note_num, correct_queue=False, tempe
     model with ``null_class``: every utterance is decoded as a PAIR of rows, as its class and as null_class, each on its own queues
     and tables; the ONE code per step is picked from l_c + (s - 1)(l_c - l_u) with the utterance's settings and fed to both.  s = 1
     is the conditional model, s > 1 more of the class, s = 0 the unconditional model; half as many utterances fit a launch.
-    Corrected recurrence only; None is the call without the argument, launch for launch."""
+    Corrected recurrence only; None is the call without the argument, launch for launch.
+    ``keep``: (U, note_num) integers - partially forced decode (include/wavenet_hip.h, wn_decode: a negative ``forced`` entry frees its
+    step).  ``keep[u][j] >= 0`` IS the code returned at position j and what the model is fed there; -1 is the sampler's choice
+    (position 0: the init forward's pick).  The launch still draws at every step - a stream's random numbers do not move with the
+    mask - and the function returns the fed stream, ``where(keep >= 0, keep, codes)``.  Under ``windows`` a kept token outside the
+    window of its position ``window_pos + j`` is a ValueError before any launch (``check_keep``); under ``guidance`` both rows of a
+    pair are fed the utterance's row.  Fill the absent stages of a residual-VQ stream, continue a prompt of any length, regenerate
+    single positions - in the one launch.  Corrected recurrence only; None is the call without the argument."""
     assert start_pieces.dim() == 3 and start_pieces.size(2) == net.receptive_field
     _check_classes(net, classes)
     win = _windows_of(windows, window_pos, net.quantization_channels, correct_queue)
     U = start_pieces.size(0)
+    kept = _keep_of(keep, U, note_num, net.quantization_channels, win, correct_queue)
     guide = _guidance_of(net, guidance, U, correct_queue, classes)
     rows = 1 if guide is None else 2                                # guided: every utterance is a pair of rows [c_u, null_class]
     if rows * U > 1024:
         raise ValueError("at most 1024 utterances per launch (128 off the matrix-core path)" if guide is None else
                          "at most 512 guided utterances per launch (64 off the matrix-core path): every one is a pair of rows")
     eng, probs, rings, prev0, row_classes = _prime(net, start_pieces, classes, rows)
-    cond, keep = _class_cond(net, eng, row_classes, rows * U, correct_queue)
+    cond, tables = _class_cond(net, eng, row_classes, rows * U, correct_queue)
     first = _first_codes(probs, win, guide)
+    if kept is not None and note_num >= 1:
+        first = _resolved(kept[:, 0], first)
     if note_num <= 1:
         return first.view(U, 1)[:, :note_num]
     _check_recurrence(eng, correct_queue)
@@ -668,8 +734,10 @@ def generate_codes_batch(net, start_pieces, note_num, correct_queue=False, tempe
                                     1 if correct_queue else 0, "%s: a hand-off between two decode workgroups timed out"
                                     % ("wn_decode_batch" if guide is None else "wn_cfg_decode_batch"), check=note_num - 1 >= 4,
                                     win=win.tail(1) if win is not None else None, cond=cond,
-                                    guide=None if guide is None else torch.tensor(guide, dtype=torch.float32, device=dev))
-    return torch.cat([first.view(U, 1).to(torch.int64), codes[0::rows].to(torch.int64)], 1)
+                                    guide=None if guide is None else torch.tensor(guide, dtype=torch.float32, device=dev),
+                                    **({} if kept is None else {"forced": kept[:, 1:].to(torch.int32).repeat_interleave(rows, 0)}))
+    codes = codes[0::rows].to(torch.int64)
+    return torch.cat([first.view(U, 1).to(torch.int64), codes if kept is None else _resolved(kept[:, 1:], codes)], 1)
 
 
 def decode_batch_cond(net, rings, prev0, note0, n_steps, step0=0, pos0=0, forced=None, want_probs=False, temperature=None,
@@ -679,7 +747,9 @@ def decode_batch_cond(net, rings, prev0, note0, n_steps, step0=0, pos0=0, forced
     (U, ring floats) is advanced in place, ``prev0`` (U, k-1, Q) / ``note0`` (U, Q) are the causal layer's history and the
     first input column.  ``cond_fg`` (U, N, Le, 2 Dp) rows [f | g] and ``cond_p1`` (U, Le, S) are the per-utterance
     conditioning tables (Dp = the decode pack's dilation width), ``schedule`` the N + 1 (shift, q, Le) triples of
-    ``ae_generate.cond_schedule``; step s is output position pos0 + s.  ``forced`` (U, n_steps): the next input codes.
+    ``ae_generate.cond_schedule``; step s is output position pos0 + s.  ``forced`` (U, n_steps): the next input codes; a
+    negative entry frees its step - the launch's own code is fed, as without ``forced`` (include/wavenet_hip.h, wn_decode) -, an entry
+    >= Q is refused when the tensor is a host tensor (a device tensor travels as it is, no synchronisation).
     ``temperature`` / ``top_k`` / ``top_p`` / ``seed``: scalars or one value per utterance, ``streams`` the random-number stream
     ids (default: the utterance index); anything beyond a scalar temperature and seed goes through wn_decode_batch_samp.
     ``windows`` / ``window_pos``: position windows shared by the launch, step s samples inside pair ``(window_pos + s) %
@@ -710,6 +780,7 @@ def decode_batch_cond(net, rings, prev0, note0, n_steps, step0=0, pos0=0, forced
         shift = ctypes.cast((ctypes.c_int32 * (N + 1))(*[int(t[0]) for t in schedule]), ctypes.c_void_p)
         qs = ctypes.cast((ctypes.c_int32 * (N + 1))(*[int(t[1]) for t in schedule]), ctypes.c_void_p)
     assert forced is None or tuple(forced.shape) == (U, n_steps)
+    _check_forced(forced, eng.Q, "decode_batch_cond")
     gtab = None
     if guidance is not None:
         gtab = torch.as_tensor(guidance, dtype=torch.float32).to(dev).contiguous()

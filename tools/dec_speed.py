@@ -9,6 +9,9 @@ to be compared with `--bias` (the unconditioned biased decoder of the same shape
 (wn_decode_batch_samp; corrected recurrence, temperature 1 unless given); `--windows S,K`: sample under the position windows of an
 S-stage token stream of K codes per stage (wn_win_decode_batch with fast_generate.stage_windows(S, K); corrected recurrence,
 temperature 1 unless given); `--runs N`: repeat the whole measurement.
+`--keep S,n`: partially forced decode over the default shape - a stage-prefix mask, positions with p % S < n are kept (fed a fixed
+token), the others drawn (generate_codes(keep=): one launch; corrected recurrence, temperature 1 unless given) - to be compared with
+`--temperature 1 --corrected` (the free run of the same build on the same recurrence); `--corrected`: the corrected recurrence.
 `--guidance S`: classifier-free guidance at scale S (wn_cfg_decode_batch) on the class-conditional model of the same shape, and on a
 code prior's shape (10 blocks, 64 / 64 / 256, Q = 1024: the fp32 kernel, two members per workgroup, under stage windows 4 x 256):
 U guided streams against 2 U plain conditioned rows of the same build, U = 1 and 64, alternated six times, medians; `--json PATH`
@@ -43,14 +46,23 @@ def sampling():
     top_k, top_p = _opt("--top-k", int), _opt("--top-p", float)
     windows = _opt("--windows", lambda v: tuple(int(x) for x in v.split(",")))
     filtered = top_k is not None or top_p is not None
-    T = _opt("--temperature", float, 1.0 if filtered or windows else None)
+    T = _opt("--temperature", float, 1.0 if filtered or windows or "--keep" in sys.argv else None)
     kw = dict(temperature=T, seed=1)
     if filtered:
         kw.update(top_k=top_k, top_p=top_p)
     if windows:
         from music_amd import fast_generate as fg
         kw.update(windows=fg.stage_windows(*windows))
-    return kw, filtered or bool(windows)
+    return kw, filtered or bool(windows) or "--keep" in sys.argv or "--corrected" in sys.argv
+
+
+def keep_mask(U, n):
+    """`--keep S,n` as generate_codes' keyword: (U, n) tokens - position p holds (128 + p) % 256 where p % S < n, -1 elsewhere"""
+    sn = _opt("--keep", lambda v: tuple(int(x) for x in v.split(",")))
+    if sn is None:
+        return {}
+    p = torch.arange(n)
+    return {"keep": torch.where(p % sn[0] < sn[1], (128 + p) % 256, torch.full_like(p, -1)).repeat(U, 1)}
 
 
 def main_cond(le):
@@ -149,11 +161,13 @@ def main():
     correct = k != 2 or filtered
     what = ", ".join("%s %s" % (key, "%d pairs" % len(v) if key == "windows" else v) for key, v in kw.items()
                      if v is not None and key != "seed") or "greedy"
+    if "--keep" in sys.argv:
+        what += ", keep %s" % _opt("--keep", str)
     for run in range(_opt("--runs", int, 1)):
         for rep in range(2):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            seq = fg.generate_codes(net, start, n, correct_queue=correct, **kw)
+            seq = fg.generate_codes(net, start, n, correct_queue=correct, **kw, **keep_mask(1, n))
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
         print("one stream (%s): %d samples in %.3f s = %.1f k samples/s = %.2f us per sample (%d distinct codes)"
@@ -164,7 +178,7 @@ def main():
                 st[uu, (128 + uu) % 256, :] = 1.0
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            out = fg.generate_codes_batch(net, st, 2001, correct_queue=correct, **kw)
+            out = fg.generate_codes_batch(net, st, 2001, correct_queue=correct, **kw, **keep_mask(U, 2001))
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
             print("%d utterances x 2000 samples (%s): %.3f s = %.2f M samples/s" % (U, what, dt, U * 2000 / dt / 1e6))
