@@ -526,6 +526,37 @@ int wn_gclass_fwd(const float* flat, float* tab, float* tab_pair, float* enf, in
 int wn_gclass_bwd(const float* d_tab, int pair, const float* d_enf, const float* flat, float* flat_grad, int n_stages, int dd, int ch,
                   int sd, int batch, const int32_t* cls, int64_t gw_off, int64_t gstage_stride, int64_t gwf_off, int64_t emb_off, int ge,
                   int n_cls, wn_stream_t stream);
+/* ---- the tables of a PHASE-conditioned WaveNet: a prior over a residual-VQ code stream (S stages, frame-major) is told the stage it
+ * is at, p mod P of the stream position p, by a learned column per phase instead of a token alphabet of S K.  The model owns
+ * T_i [2 dd][period] per block (rows as G_i: gate rows first) at flat + pw_off + i * pstage_stride and T_f [sd][period] at flat + pwf_off
+ * (their gradients at the same offsets of flat_grad; offsets count floats).  Clip b's first target sits at stream position pos[b]
+ * (device, int64, >= 0).  The block kernels read a table of `period` frames in their tile mode, frame (t - t_lo) mod period of stage i's
+ * own t_lo; rot [n_stages + 1] (device, int32, any integer; the last entry is the final stage's) carries each stage's t_lo:
+ *   en_i[b][c][l] = T_i[c][(l + pos[b] + rot[i]) mod period]      enf[b][c][l] likewise with T_f and rot[n_stages], [batch][sd][period]
+ * the mathematical mod on int64, never negative.  The table layouts are wn_cond_proj_fwd's with le = period: per clip
+ * [n_stages][batch][2 ch][period] and / or clip pairs [n_stages][batch/2][4 ch][period], ch = dd padded to 32, rows mapped as documented
+ * there.  add_tab / add_pair / add_enf: all NULL, or the class term in the le = 1 layouts of wn_gclass_fwd (its tab, tab_pair, enf; an
+ * addend for every output given) - every frame is then the correctly rounded fp32 sum (class column + phase column).
+ * wn_phase_tab_fwd writes every table it is given (tab, tab_pair: at least one) WHOLE, padding rows as exact zeros, and enf, in ONE launch.
+ * wn_phase_tab_bwd takes d_tab in the layout `pair` names and d_enf [batch][sd][period] and writes, in ONE launch,
+ *   dT_i[c][s] = sum_b d_en_i[b][c][(s - pos[b] - rot[i]) mod period]       in ascending b from +0              (the final stage alike)
+ * at the tables' offsets in flat_grad, OVERWRITING them; nothing else of flat_grad is touched.  sum_tab / sum_enf: both NULL, or the
+ * outputs of the frame sums sum_l d_en_i[b][c][l] (ascending l from +0; every row of the layout, padding included) in the le = 1
+ * layouts: sum_tab in the layout `pair` names, sum_enf [batch][sd] - what wn_gclass_bwd takes as its d_tab and d_enf.
+ * A negative pos[b] is never used as an index: the forward turns that clip's rows of every table (not the padding) and of enf into NaN,
+ * the backward its share of every dT.  fp32 in a fixed order, no float atomics: the same bits at every launch.  On `stream`, no
+ * allocation, nothing retained, legal under stream capture.
+ * batch == 0 returns 0 (NULLs allowed).  -4, function and argument named in wn_last_error, before any launch: batch < 0; n_stages, dd
+ * or sd < 1; period < 1 or > WN_PHASE_MAX_PERIOD; ch < dd or ch not a multiple of 32; a pair table with an odd batch; a negative pw_off
+ * or pwf_off; pstage_stride < 2 dd period with more than one stage; with work to do, a NULL required pointer (an addend missing for an
+ * output, one of sum_tab / sum_enf without the other). */
+#define WN_PHASE_MAX_PERIOD 16
+int wn_phase_tab_fwd(const float* flat, int64_t pw_off, int64_t pstage_stride, int64_t pwf_off, const int64_t* pos, const int32_t* rot,
+                     const float* add_tab, const float* add_pair, const float* add_enf, float* tab, float* tab_pair, float* enf,
+                     int n_stages, int dd, int ch, int sd, int period, int batch, wn_stream_t stream);
+int wn_phase_tab_bwd(const float* d_tab, int pair, const float* d_enf, float* flat_grad, int64_t pw_off, int64_t pstage_stride,
+                     int64_t pwf_off, const int64_t* pos, const int32_t* rot, float* sum_tab, float* sum_enf, int n_stages, int dd, int ch,
+                     int sd, int period, int batch, wn_stream_t stream);
 /* ---- VECTOR-QUANTISED bottleneck of the autoencoder (VQ-VAE, van den Oord et al. 2017; the reference has none): every pooled frame
  * e = enc[b][:][l] of enc [batch][bw][le] is replaced by its nearest row of the codebook c [K][bw], which sits at flat + cb_off
  * (its gradient at flat_grad + cb_off; offsets count floats).  C = batch * le frames.  Everything in float32:

@@ -20,6 +20,7 @@ VQ_MAX_CODES, VQ_MAX_WIDTH = 1024, 512
 VQ_EMA_WORK_BYTES = 16 + 4 * VQ_MAX_CODES      # include/wavenet_hip.h WN_VQ_EMA_WORK_BYTES
 RVQ_MAX_STAGES = 8             # include/wavenet_hip.h WN_RVQ_MAX_STAGES
 GCOND_MAX_CHANNELS = 512       # include/wavenet_hip.h WN_GCOND_MAX_CHANNELS
+PHASE_MAX_PERIOD = 16          # include/wavenet_hip.h WN_PHASE_MAX_PERIOD
 
 _p = ctypes.c_void_p
 _i = ctypes.c_int
@@ -105,6 +106,9 @@ SIGNATURES = {
     # the global class term alone (a class-conditional WaveNet's tables): no encoding, le = 1
     "wn_gclass_fwd": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _l, _l, _l, _l, _i, _i, _p],
     "wn_gclass_bwd": [_p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _p, _l, _l, _l, _l, _i, _i, _p],
+    # the tables of a phase-conditioned WaveNet: `period` frames per clip, the parameters' columns rotated by the clip's position
+    "wn_phase_tab_fwd": [_p, _l, _l, _l, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
+    "wn_phase_tab_bwd": [_p, _i, _p, _p, _l, _l, _l, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
     "wn_vq_fwd": [_p, _p, _l, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     "wn_vq_bwd": [_p, _p, _p, _p, _l, _f, _f, _p, _p, _i, _i, _i, _i, _p],
     "wn_vq_lookup": [_p, _p, _l, _p, _p, _i, _i, _i, _i, _p],

@@ -409,14 +409,38 @@ def rate_distortion(net, clips, classes=None):
     return rows
 
 
-def split_code_stream(tokens, stages, K):
+LAYOUTS = ("interleaved", "phase")
+
+
+def _layout(layout, what):
+    if layout not in LAYOUTS:
+        raise ValueError('%s: layout must be "interleaved" (token = stage * K + code) or "phase" (token = code), not %r' % (what, layout))
+    return layout == "phase"
+
+
+def _phase_prior(prior, stages, K, what):
+    """True for a phase-conditioned prior over the K-ary stream of `stages` stages (phase_period == stages, quantization_channels ==
+    K), False for a prior over the interleaved S K alphabet; any other combination of phase_period and alphabet is refused by name"""
+    P, Q = int(getattr(prior, "phase_period", 0) or 0), int(prior.quantization_channels)
+    if not P:
+        return False
+    if P != stages or Q != K:
+        raise ValueError("%s: the prior has phase_period = %d and quantization_channels = %d; a phase-conditioned prior of %d stages "
+                         "x %d codes needs phase_period = %d and quantization_channels = %d" % (what, P, Q, stages, K, stages, K))
+    return True
+
+
+def split_code_stream(tokens, stages, K, layout="interleaved"):
     """The interleaved token stream of tools/vq_codes_dataset.py back into codes: ``tokens`` (B, Le * stages) or (Le * stages,)
     integers, frame-major (l0s0, l0s1, .., l1s0, ..) with token = s * K + code, -> (B, stages, Le) int64 codes in [0, K), what
     ``decode_codes`` takes.  Raises on a length that is no multiple of ``stages`` and on a token outside its position's stage range.
     A prior over the S K alphabet sampled freely may emit one; ``sample_code_stream`` samples it under the decoder's position
-    windows (``fast_generate.stage_windows``), which keep every token inside its position's range, so its streams always split."""
+    windows (``fast_generate.stage_windows``), which keep every token inside its position's range, so its streams always split.
+    ``layout="phase"`` (tools/vq_codes_dataset.py --layout phase, a phase-conditioned prior): the tokens ARE the codes, frame-major,
+    every one in [0, K)."""
     t = torch.as_tensor(tokens)
     stages, K = int(stages), int(K)
+    phase = _layout(layout, "split_code_stream")
     if stages < 1 or K < 1:
         raise ValueError("split_code_stream: stages and K must be >= 1")
     if t.is_floating_point() or t.dim() not in (1, 2):
@@ -425,21 +449,23 @@ def split_code_stream(tokens, stages, K):
     if t.size(1) % stages:
         raise ValueError("split_code_stream: %d tokens per clip are not a multiple of %d stages" % (t.size(1), stages))
     t = t.to(torch.int64).reshape(t.size(0), -1, stages)                              # (B, Le, S)
-    codes = t - torch.arange(stages, dtype=torch.int64, device=t.device) * K
+    codes = t if phase else t - torch.arange(stages, dtype=torch.int64, device=t.device) * K
     wrong = (codes < 0) | (codes >= K)
     if bool(wrong.any()):
         b, l, s = (int(v) for v in wrong.nonzero()[0])
         raise ValueError("split_code_stream: token %d of clip %d at frame %d, stage %d lies outside that stage's range [%d, %d)"
-                         % (int(t[b, l, s]), b, l, s, s * K, (s + 1) * K))
+                         % ((int(t[b, l, s]), b, l, s) + ((0, K) if phase else (s * K, (s + 1) * K))))
     return codes.permute(0, 2, 1).contiguous()
 
 
-def join_code_stream(codes, K):
+def join_code_stream(codes, K, layout="interleaved"):
     """The inverse of ``split_code_stream``: ``codes`` (B, S, Le) integers in [0, K) -> (B, Le * S) int64 tokens, frame-major (l0s0,
     l0s1, .., l1s0, ..) with token = s * K + code.  A -1 (an absent stage of ``encode_codes(..., stages=n)``, a code still to be
-    sampled) stays -1.  ``split_code_stream(join_code_stream(c, K), S, K) == c`` on complete codes.  Raises on anything else."""
+    sampled) stays -1.  ``split_code_stream(join_code_stream(c, K), S, K) == c`` on complete codes.  Raises on anything else.
+    ``layout="phase"``: token = code (``split_code_stream``)."""
     c = torch.as_tensor(codes)
     K = int(K)
+    phase = _layout(layout, "join_code_stream")
     if K < 1:
         raise ValueError("join_code_stream: K must be >= 1")
     if c.is_floating_point() or c.dtype == torch.bool or c.dim() != 3:
@@ -450,7 +476,7 @@ def join_code_stream(codes, K):
         b, s, l = (int(v) for v in wrong.nonzero()[0])
         raise ValueError("join_code_stream: code %d of clip %d at frame %d, stage %d lies outside [0, %d) (-1: no code)"
                          % (int(c[b, s, l]), b, l, s, K))
-    tok = c + (torch.arange(c.size(1), dtype=torch.int64, device=c.device) * K)[None, :, None]
+    tok = c if phase else c + (torch.arange(c.size(1), dtype=torch.int64, device=c.device) * K)[None, :, None]
     return torch.where(c >= 0, tok, c).permute(0, 2, 1).reshape(c.size(0), -1).contiguous()
 
 
@@ -471,6 +497,9 @@ def sample_code_stream(prior, stages, K, frames, start_tokens, start_pos=0, temp
     positions and the others drawn GIVEN them, in the same one launch (``generate_codes_batch(keep=)``: coarse-to-fine when the kept
     codes are a stage prefix; single frames, everything or nothing are as welcome); the result holds the caller's codes where given.
     A kept code outside [0, K) is refused before any launch.
+    A phase-conditioned prior (``phase_period == stages`` and ``quantization_channels == K``, trained on the tool's ``--layout phase``
+    stream) is detected: its tokens are the codes themselves, every logit is legal, so it runs without a window table and is told the
+    stage by ``phase_pos = start_pos + n0``; everything else is as above.  Any other (phase_period, alphabet) is refused by name.
     Returns ``split_code_stream`` of the generated tokens: (U, stages, frames) int64 codes in [0, K), what ``decode_codes`` takes."""
     try:
         from . import fast_generate as fg
@@ -480,7 +509,8 @@ def sample_code_stream(prior, stages, K, frames, start_tokens, start_pos=0, temp
     rf, Q = prior.receptive_field, prior.quantization_channels
     if stages < 1 or K < 1 or frames < 1:
         raise ValueError("sample_code_stream: stages, K and frames must be >= 1")
-    if stages * K > Q:
+    phase = _phase_prior(prior, stages, K, "sample_code_stream")
+    if not phase and stages * K > Q:
         raise ValueError("sample_code_stream: %d stages x %d codes = %d tokens, the prior's alphabet holds %d" % (stages, K, stages * K, Q))
     t = torch.as_tensor(start_tokens)
     if t.is_floating_point() or t.dim() != 2 or t.size(1) < rf:
@@ -497,22 +527,23 @@ def sample_code_stream(prior, stages, K, frames, start_tokens, start_pos=0, temp
             raise ValueError("sample_code_stream: keep_codes must be (%d, %d, %d) integers (a code in [0, %d), or -1: to be sampled)"
                              % (t.size(0), stages, frames, K))
         try:
-            keep["keep"] = join_code_stream(kc, K)
+            keep["keep"] = join_code_stream(kc, K, "phase" if phase else "interleaved")
         except ValueError as e:
             raise ValueError("sample_code_stream: keep_codes: %s" % e) from None
     dev = next(prior.parameters()).device
     x = torch.nn.functional.one_hot(t[:, -rf:].to(device=dev, dtype=torch.int64), Q).transpose(1, 2).float().contiguous()
+    where = dict(phase_pos=start_pos + t.size(1)) if phase else dict(windows=fg.stage_windows(stages, K), window_pos=start_pos + t.size(1))
     tokens = fg.generate_codes_batch(prior, x, frames * stages, correct_queue=True, temperature=temperature, seed=seed, top_k=top_k,
-                                     top_p=top_p, streams=streams, windows=fg.stage_windows(stages, K),
-                                     window_pos=start_pos + t.size(1), classes=classes, guidance=guidance, **keep)
-    return split_code_stream(tokens, stages, K)
+                                     top_p=top_p, streams=streams, classes=classes, guidance=guidance, **where, **keep)
+    return split_code_stream(tokens, stages, K, "phase" if phase else "interleaved")
 
 
 def prior_score(prior, tokens, stages, K, start_pos=0, classes=None):
     """Held-out figures of a prior on token streams ``tokens`` (U, n > receptive_field) whose first token sits at stream position
     ``start_pos``, under the windows ``sample_code_stream`` draws with: ``objective.score`` of every token behind the first
     receptive_field ones - per-stream "nll", "bits" (per token, of the distribution that is sampled) and "accuracy".  ``classes``: one
-    class per stream for a class-conditional prior."""
+    class per stream for a class-conditional prior.  A phase-conditioned prior (``sample_code_stream``) is scored without windows,
+    under ``phase_pos = start_pos + receptive_field``."""
     try:
         from . import fast_generate as fg, objective
     except ImportError:
@@ -522,6 +553,10 @@ def prior_score(prior, tokens, stages, K, start_pos=0, classes=None):
     if t.is_floating_point() or t.dim() != 2 or t.size(1) <= rf:
         raise ValueError("prior_score: tokens must be (U, n > %d) integer tokens" % rf)
     t = t.to(next(prior.parameters()).device)
+    if int(start_pos) < 0:
+        raise ValueError("prior_score: start_pos must be >= 0")
+    if _phase_prior(prior, int(stages), int(K), "prior_score"):
+        return objective.score(prior, t[:, :-1].to(torch.int32), t[:, rf:].to(torch.int64), classes=classes, phase_pos=int(start_pos) + rf)
     return objective.score(prior, t[:, :-1].to(torch.int32), t[:, rf:].to(torch.int64), classes=classes,
                            windows=fg.stage_windows(int(stages), int(K)), window_pos=int(start_pos) + rf)
 

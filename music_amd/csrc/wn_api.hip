@@ -680,6 +680,67 @@ int wn_gclass_bwd(const float* d_tab, int pair, const float* d_enf, const float*
     p.n_stages = n_stages; p.dd = dd; p.ch = ch; p.sd = sd; p.bw = 1; p.le = 1; p.batch = batch;
     return wn_launch_gclass_bwd(p, gcond_args(cls, gw_off, gstage_stride, gwf_off, emb_off, ge, n_cls), (hipStream_t)stream);
 }
+// ---- the tables of a phase-conditioned WaveNet (wn_phase.hip) ----
+// the refusals both entries share: shapes, offsets and the stride (they need no pointer)
+static int phase_checked(const char* fn, int pair, int n_stages, int dd, int ch, int sd, int period, int batch, int64_t pw_off,
+                         int64_t pstage_stride, int64_t pwf_off) {
+    char msg[200];
+    const char* bad = nullptr;
+    if (batch < 0) bad = "'batch' must be >= 0";
+    else if (n_stages < 1) bad = "'n_stages' must be >= 1";
+    else if (dd < 1) bad = "'dd' must be >= 1";
+    else if (sd < 1) bad = "'sd' must be >= 1";
+    else if (period < 1 || period > WN_PHASE_MAX_PERIOD) bad = "'period' must lie in [1, 16]";
+    else if (ch < dd || ch % 32 != 0) bad = "'ch' must be a multiple of 32 and >= dd";
+    else if (pair && batch % 2 != 0) bad = "'batch' must be even for a table of clip pairs";
+    else if (pw_off < 0) bad = "'pw_off' must be >= 0";
+    else if (pwf_off < 0) bad = "'pwf_off' must be >= 0";
+    else if (n_stages > 1 && pstage_stride < (int64_t)2 * dd * period) bad = "'pstage_stride' must be >= 2 * dd * period (the stages' tables overlap)";
+    if (bad) {
+        snprintf(msg, sizeof(msg), "%s: argument %s", fn, bad);
+        return wn_set_error_msg(-4, msg);
+    }
+    return 0;
+}
+static WnPhase phase_args(int64_t pw_off, int64_t pstage_stride, int64_t pwf_off, const int64_t* pos, const int32_t* rot, int n_stages,
+                          int dd, int ch, int sd, int period, int batch) {
+    WnPhase p;
+    memset(&p, 0, sizeof(p));
+    p.pw_off = (long)pw_off; p.pstage_stride = (long)pstage_stride; p.pwf_off = (long)pwf_off; p.pos = pos; p.rot = rot;
+    p.n_stages = n_stages; p.dd = dd; p.ch = ch; p.sd = sd; p.period = period; p.batch = batch;
+    return p;
+}
+int wn_phase_tab_fwd(const float* flat, int64_t pw_off, int64_t pstage_stride, int64_t pwf_off, const int64_t* pos, const int32_t* rot,
+                     const float* add_tab, const float* add_pair, const float* add_enf, float* tab, float* tab_pair, float* enf,
+                     int n_stages, int dd, int ch, int sd, int period, int batch, wn_stream_t stream) {
+    const char* fn = "wn_phase_tab_fwd";
+    if (int rc = phase_checked(fn, tab_pair != nullptr, n_stages, dd, ch, sd, period, batch, pw_off, pstage_stride, pwf_off)) return rc;
+    if (batch == 0) return 0;
+    WN_REQUIRE("wn_phase_tab_fwd", flat, pos, rot, enf);
+    if (!tab && !tab_pair) return wn_set_error_msg(-4, "wn_phase_tab_fwd: argument 'tab' or 'tab_pair' must not be NULL");
+    if (add_tab || add_pair || add_enf) {                    // the class term: an addend for every output
+        if (!add_enf) return wn_set_error_msg(-4, "wn_phase_tab_fwd: argument 'add_enf' must not be NULL where an addend is given");
+        if (tab && !add_tab) return wn_set_error_msg(-4, "wn_phase_tab_fwd: argument 'add_tab' must not be NULL where 'tab' and an addend are given");
+        if (tab_pair && !add_pair)
+            return wn_set_error_msg(-4, "wn_phase_tab_fwd: argument 'add_pair' must not be NULL where 'tab_pair' and an addend are given");
+    }
+    WnPhase p = phase_args(pw_off, pstage_stride, pwf_off, pos, rot, n_stages, dd, ch, sd, period, batch);
+    p.flat = flat; p.add_tab = add_tab; p.add_pair = add_pair; p.add_enf = add_enf; p.tab = tab; p.tab_pair = tab_pair; p.enf = enf;
+    return wn_launch_phase_tab_fwd(p, (hipStream_t)stream);
+}
+int wn_phase_tab_bwd(const float* d_tab, int pair, const float* d_enf, float* flat_grad, int64_t pw_off, int64_t pstage_stride,
+                     int64_t pwf_off, const int64_t* pos, const int32_t* rot, float* sum_tab, float* sum_enf, int n_stages, int dd, int ch,
+                     int sd, int period, int batch, wn_stream_t stream) {
+    const char* fn = "wn_phase_tab_bwd";
+    if (int rc = phase_checked(fn, pair, n_stages, dd, ch, sd, period, batch, pw_off, pstage_stride, pwf_off)) return rc;
+    if (batch == 0) return 0;
+    WN_REQUIRE("wn_phase_tab_bwd", d_tab, d_enf, flat_grad, pos, rot);
+    if ((sum_tab != nullptr) != (sum_enf != nullptr))
+        return wn_set_error_msg(-4, "wn_phase_tab_bwd: arguments 'sum_tab' and 'sum_enf' must both be NULL or both be given");
+    WnPhase p = phase_args(pw_off, pstage_stride, pwf_off, pos, rot, n_stages, dd, ch, sd, period, batch);
+    p.d_tab = d_tab; p.d_pair = pair ? 1 : 0; p.d_enf = d_enf; p.flat_grad = flat_grad; p.sum_tab = sum_tab; p.sum_enf = sum_enf;
+    return wn_launch_phase_tab_bwd(p, (hipStream_t)stream);
+}
 // ---- vector-quantised bottleneck (wn_vq.hip) ----
 static int vq_refused(const char* fn, const char* what) {
     char msg[200];

@@ -270,6 +270,20 @@ int wn_launch_gcond_proj_bwd(const WnCondProj& p, const WnGcond& g, hipStream_t 
 // the global term alone (a class-conditional WaveNet): p with le = 1, its encoding, weights and biases unused
 int wn_launch_gclass_fwd(const WnCondProj& p, const WnGcond& g, hipStream_t st);
 int wn_launch_gclass_bwd(const WnCondProj& p, const WnGcond& g, hipStream_t st);
+// the tables of a phase-conditioned WaveNet (wn_phase.hip): stage i's T_i [2 dd][period] sits at pw_off + i * pstage_stride, the
+// final stage's [sd][period] at pwf_off; pos [batch] and rot [n_stages + 1] are device arrays; tables of `period` frames
+struct WnPhase {
+    const float* flat; float* flat_grad;
+    long pw_off, pstage_stride, pwf_off;
+    const int64_t* pos; const int32_t* rot;
+    const float* add_tab; const float* add_pair; const float* add_enf;               // forward: the class term's le = 1 tables, or NULLs
+    float* tab; float* tab_pair; float* enf;                                          // forward outputs (a table may be NULL)
+    const float* d_tab; int d_pair; const float* d_enf;                               // backward
+    float* sum_tab; float* sum_enf;                                                   // backward: the frame sums (le = 1), or NULLs
+    int n_stages, dd, ch, sd, period, batch;
+};
+int wn_launch_phase_tab_fwd(const WnPhase& p, hipStream_t st);
+int wn_launch_phase_tab_bwd(const WnPhase& p, hipStream_t st);
 // vector-quantised bottleneck (wn_vq.hip): the codebook [K][bw] sits at flat + cb_off (its gradient at flat_grad + cb_off)
 #define WN_VQ_PARTIALS 256
 #define WN_RVQ_MAX_S 8

@@ -25,7 +25,7 @@ from .stack import Cond, EpiBias, GatedStack, SkipEpilogue
 class WaveNetEngine(EngineBase):
     def __init__(self, dilations, residual_channels, dilation_channels, skip_channels,
                  quantization_channels=256, filter_width=2, use_bias=False,
-                 mode_fwd="f16x3", mode_bwd="bf16x3", device=None, global_classes=0, global_channels=0):
+                 mode_fwd="f16x3", mode_bwd="bf16x3", device=None, global_classes=0, global_channels=0, phase_period=0):
         if filter_width != 2:
             raise NotImplementedError("HIP path implements filter_width == 2 (the reference's only configuration)")
         if quantization_channels != 256:
@@ -34,6 +34,7 @@ class WaveNetEngine(EngineBase):
         self.N = len(self.dil)
         self.k = 2                                       # filter width (EngineBase._build_spec, the decoder)
         self.g_n, self.g_E = int(global_classes), int(global_channels)      # class-conditional: classes, embedding width (0, 0: off)
+        self.phase = int(phase_period)                   # phase-conditioned: the period P of the stream's stages (0: off)
         self.R, self.D, self.S, self.Q = residual_channels, dilation_channels, skip_channels, quantization_channels
         self.fused_loss_ok = True           # model.py: nn.CrossEntropyLoss on the module's output may run as wn_chunk_softmax256_ce (Q = 256 here)
         self.use_bias = bool(use_bias)
@@ -81,8 +82,8 @@ class WaveNetEngine(EngineBase):
         bias = EpiBias([bn % (4 * i + 3) for i in range(self.N)], "post_process_1.bias", "post_process_2.bias", self._bias_ptr,
                        lambda name: ptr(self.gpack, self.gp_bias_off[name]),
                        [self.spec.off[bn % (4 * i + 3)] for i in range(self.N)]) if self.use_bias else None
-        # (class-conditional: h gains the class term as the second product's residual C1 - the three-launch forward, never the fused one)
-        self.epilogue = SkipEpilogue(self, ("skip", "p1", "p2"), ("U", "H", "C1" if self.gcond else None, "dH"), self.CH, self.S, self.SP, self._fr, self._br,
+        # (class- or phase-conditional: h gains the term as the second product's residual C1 - the three-launch forward, never the fused one)
+        self.epilogue = SkipEpilogue(self, ("skip", "p1", "p2"), ("U", "H", "C1" if self.gcond or self.phase else None, "dH"), self.CH, self.S, self.SP, self._fr, self._br,
                                      self.mode_fwd, self.mode_bwd, bias=bias, fmark=self.fmark)
 
     def fmark(self, name):
@@ -134,7 +135,7 @@ class WaveNetEngine(EngineBase):
         self.gp_off, self.gp_bias_off = pk.gp_off, pk.gp_bias_off
         self.gpack = torch.zeros(pk.go, dtype=torch.float32, device=dev)
         gidx, ga, gb = pk.gather_maps()
-        assert (gidx[:self.n_gather] >= 0).all()               # (the global block: wn_gclass_bwd writes its gradients)
+        assert (gidx[:self.n_gather] >= 0).all()               # (the global block, the phase tables: wn_gclass_bwd / wn_phase_tab_bwd write theirs)
         self.gidx = torch.from_numpy(gidx.astype(np.int32)).to(dev)
         if self.pair_ok:
             # pair mode: the stack's weight gradients come out of the 64-channel block kernels as block-diagonal matrices -
@@ -161,8 +162,8 @@ class WaveNetEngine(EngineBase):
         ws["U"] = buf(self.SP)
         ws["H"] = buf(self.SP)
         ws["O"] = torch.zeros(B * self.Q * W + PAD_BACK, dtype=torch.float32, device=dev)
-        if self.gcond:
-            ws["C1"] = buf(self.SP)        # the output stage's class term, expanded over time
+        if self.gcond or self.phase:
+            ws["C1"] = buf(self.SP)        # the output stage's class / phase term, expanded over time
         ws["bwd"] = None
         # which backward blocks this workspace is planned for: decided ONCE here (slab layout, (P, Q) buffers, and whether
         # the forward has to store z on each block's whole range for the fallback backward) - a switch flipped later
@@ -212,7 +213,7 @@ class WaveNetEngine(EngineBase):
         # of an item are the carry of the next item of its chain); decided here, once per workspace, with the slab counts
         Bp = B // 2 if pair else B
         # 0: every block hands the (P, Q) pair on (round 3's form); so do conditioned blocks (the chain form takes no table)
-        want = os.environ.get("WN_PQ_CHAIN", "1") == "1" and not self.gcond
+        want = os.environ.get("WN_PQ_CHAIN", "1") == "1" and not self.gcond and not self.phase
         bw["chain"] = [want and bool(bw["pq"] or pair) and _lib.pq_chain_ok(self.off[i + 1], T, Bp, self.dil[i]) for i in range(self.N)]
         sfx = "2_" if pair else ""                            # pair mode: the block-diagonal gradient matrices of B / 2 clip pairs
         for i in range(self.N):
@@ -252,18 +253,35 @@ class WaveNetEngine(EngineBase):
         return ptr(ws["X"], SLACK + i * ws["B"] * self.CH * ws["pitch"])
 
     # ------------------------------------------------------------------ forward
-    def _gclass_tables(self, ws, cls, st):
+    def _cond_shape(self, ws, i):
+        """(frames, mode, q) of block i's table (i = N: the output stage's): ONE frame stretched over the stage's whole range (class-
+        conditional), or P frames tiled over it, frame (t - t_lo) mod P (phase-conditioned, with or without classes)"""
+        if self.phase:
+            return self.phase, 2, 1
+        return 1, 1, (ws["T"] - self.off[i + 1] if i < self.N else ws["W"])
+
+    def _gclass_tables(self, ws, cls, st, pos=None):
         """The clips' conditioning of one forward: every block's table [f; g]_i += G_i emb[c] and the output stage's h += G_f emb[c]
         (one launch, wn_gclass_fwd), in the forms the autoencoder's decoder runs a table of <= 32 frames in (music_amd/model1.py) -
-        here ONE frame stretched over the block's whole range.  Returns i -> stack.Cond; fills ws["C1"]."""
+        here ONE frame stretched over the block's whole range.  pos (a phase-conditioned model; cls may then be None): the tables have
+        P frames, the phase tables' columns rotated by the clip's position plus the class column (one more launch, wn_phase_tab_fwd),
+        tiled over the block's range.  Returns i -> stack.Cond; fills ws["C1"]."""
         B, T, W, pitch, N, CH = ws["B"], ws["T"], ws["W"], ws["pitch"], self.N, self.CH
         pair, pair_f, dev = ws["pair"], ws["pair_fwd"], self.device
         empty = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
         # per clip for a 32-channel or unpaired forward, as clip pairs for the pair blocks (forward if pair_f, backward always)
-        tab_c = empty(N, B, 2 * CH) if not pair_f else None
-        tab = empty(N, B // 2, 4 * CH) if pair else tab_c
-        enf = empty(B, self.S)
-        self.gclass_fwd(cls, tab_c, tab if pair else None, enf, CH, st)
+        le = self.phase or 1
+        gc = (None, None, None)                       # the class term's (tab per clip, tab of pairs, enf), one frame
+        if cls is not None:
+            gc = (empty(N, B, 2 * CH) if not pair_f else None, empty(N, B // 2, 4 * CH) if pair else None, empty(B, self.S))
+            self.gclass_fwd(cls, *gc, CH, st)
+        if pos is not None:
+            tab_c = empty(N, B, 2 * CH, le) if not pair_f else None
+            tab = empty(N, B // 2, 4 * CH, le) if pair else tab_c
+            enf = empty(B, self.S, le)
+            self.phase_fwd(pos, tab_c, tab if pair else None, enf, CH, st, gc)
+        else:
+            tab_c, tab, enf = gc[0], gc[1] if pair else gc[0], gc[2]
         ws["tab"] = tab
         CHp, Bp = (64, B // 2) if pair else (CH, B)
         cpk = cix = None
@@ -272,9 +290,12 @@ class WaveNetEngine(EngineBase):
             # workspace) and, per forward, the tables as packed A fragments ([2 CH rows][32 buckets] per block and clip)
             if "cidx" not in ws:
                 ws["cidx"] = torch.zeros(N, _lib.COND_IDX_PAD + T + 64, dtype=torch.uint8, device=dev)
+                for i in range(N if le > 1 else 0):        # (P frames: the bucket of sample t of block i is (t - t_lo) mod P)
+                    L = T - self.off[i + 1]
+                    ws["cidx"][i, _lib.COND_IDX_PAD:_lib.COND_IDX_PAD + L] = (torch.arange(L, device=dev) % le).to(torch.uint8)
                 row, k = pack_positions(2 * CHp // 16, 1, False)
-                one = np.where(k < 1, row + k, -1).astype(np.int64)
-                base = np.arange(N * Bp, dtype=np.int64)[:, None] * (2 * CHp)
+                one = np.where(k < le, row * le + k, -1).astype(np.int64)                   # one [2 CH][le] table
+                base = np.arange(N * Bp, dtype=np.int64)[:, None] * (2 * CHp * le)
                 ws["ctab_idx"] = torch.from_numpy(np.where(one[None, :] >= 0, base + one[None, :], -1).astype(np.int32).reshape(-1)).to(dev)
                 ws["ctab_pk"] = torch.empty(N * Bp * 2 * CHp * 32 * 2, dtype=torch.int16, device=dev)
             if pair_f or not pair:                        # (the backward blocks read the fp32 table; only a 64-channel forward the pack)
@@ -282,15 +303,17 @@ class WaveNetEngine(EngineBase):
                 cpk, cix = ws["ctab_pk"], ws["cidx"]
         cpb = 2 * CHp * 32 * 2                          # halfs of one clip's packed table (hi + lo planes)
         tab_f, n_f = (tab, Bp) if pair_f else (tab_c, B)
-        call("wn_cond_expand", ptr(enf), self.S, 1, self.S, self.rf - 1, T, 1, 1, W, ptr(ws["C1"], SLACK), self.SP * pitch, pitch, B, st)
-        return lambda i: Cond(ptr(tab_f[i]), tab_f.shape[2], 1, 1, T - self.off[i + 1],
+        _, mode_c, q = self._cond_shape(ws, N)
+        call("wn_cond_expand", ptr(enf), self.S * le, le, self.S, self.rf - 1, T, mode_c, le, q, ptr(ws["C1"], SLACK), self.SP * pitch, pitch, B, st)
+        return lambda i: Cond(ptr(tab_f[i]), tab_f.shape[2] * le, *self._cond_shape(ws, i),
                               ptr(cpk, i * n_f * cpb) if cpk is not None else None, cpb, ptr(cix[i]) if cix is not None else None)
 
-    def forward_logits(self, x, ws=None, codes=None, classes=None):
+    def forward_logits(self, x, ws=None, codes=None, classes=None, phase_pos=None):
         """x: (B,Q,T) float32 contiguous on the device.  Runs causal conv, the residual stack, the
         skip product and both post-process convs; leaves the pre-softmax (B,Q,W) in ws['O'].
         codes = (int32 (B,T) device tensor, scrambled) instead of x: the one-hot is never built.
-        classes: one integer per clip of a class-conditional model (EngineBase.stage_classes), else None."""
+        classes: one integer per clip of a class-conditional model (EngineBase.stage_classes), else None.
+        phase_pos: the stream position of every clip's first target of a phase-conditioned model (EngineBase.stage_phase), else None."""
         if x is None:
             B, T = codes[0].shape
             Q = self.Q
@@ -301,11 +324,11 @@ class WaveNetEngine(EngineBase):
         W = T - self.rf + 1
         if W <= 0:
             raise ValueError("wave sample not long enough")          # wavenet/model.py:100-101
-        cls = self.stage_classes(classes, B)
+        cls, pos = self.stage_classes(classes, B), self.stage_phase(phase_pos, B)
         ws = ws or self._ws.get(B, T)
         st = _lib.stream()
         CH, pitch, mf = self.CH, ws["pitch"], self.mode_fwd
-        ws["cls"] = cls
+        ws["cls"], ws["pos"] = cls, pos
         self._gen += 1
         ws["gen"] = self._gen
         ws["x_in"] = x
@@ -325,7 +348,10 @@ class WaveNetEngine(EngineBase):
         # copy written by its recompute kernel).
         z_whole = self.z_from_fwd and not ws["ms"] and not ws["pair"]      # (pair: the one-launch backward recomputes z)
         cond = None
-        if cls is not None:
+        if pos is not None:
+            cond = self._gclass_tables(ws, cls, st, pos)
+            self.mark("phase_fwd")
+        elif cls is not None:
             cond = self._gclass_tables(ws, cls, st)
             self.mark("gclass_fwd")
         self.stack.forward(B, T, pitch, ws["X"], ws["Z"], z_whole, st, cond=cond, pair=ws["pair_fwd"])
@@ -334,10 +360,10 @@ class WaveNetEngine(EngineBase):
         self.mark("epilogue_fwd")
         return ws
 
-    def forward(self, x, classes=None):
+    def forward(self, x, classes=None, phase_pos=None):
         """wavenet/model.py:86-145 -> probabilities (B*W, Q) (fresh tensor)."""
         self.pack_weights()
-        ws = self.forward_logits(x, classes=classes)
+        ws = self.forward_logits(x, classes=classes, phase_pos=phase_pos)
         B, W = ws["B"], ws["W"]
         probs = torch.empty(B * W, self.Q, dtype=torch.float32, device=self.device)
         call("wn_chunk_softmax256_fwd", ptr(ws["O"]), ptr(probs), B * W, _lib.stream())
@@ -352,9 +378,11 @@ class WaveNetEngine(EngineBase):
         # (WN_EPI_BWD_ORDER=0: the skip weight gradient beside the stack, on the side stream)
         a = self.epilogue.begin_backward(ws, bw)
         d_enf, after_dh = None, lambda: None
-        if ws.get("cls") is not None:        # the output stage's class term: d enf = the sum of dh over each clip's time
-            d_enf = torch.zeros(ws["B"], self.S, dtype=torch.float32, device=self.device)
-            after_dh = lambda: call("wn_cond_grad", a.dH, a.sb, a.pitch, self.S, self.rf - 1, a.T, 1, 1, a.W, ptr(d_enf), self.S, 1, a.B, st)
+        if ws.get("cls") is not None or ws.get("pos") is not None:
+            # the output stage's class / phase term: d enf = the sum of dh over each clip's time (over each frame's samples)
+            le, mode_c, q = self._cond_shape(ws, self.N)
+            d_enf = torch.zeros(ws["B"], self.S, *((le,) if self.phase else ()), dtype=torch.float32, device=self.device)
+            after_dh = lambda: call("wn_cond_grad", a.dH, a.sb, a.pitch, self.S, self.rf - 1, a.T, mode_c, le, q, ptr(d_enf), self.S * le, le, a.B, st)
         self.epilogue.backward(a, st, self.epi_fused_bwd and not self.use_bias, side_skip=os.environ.get("WN_EPI_BWD_ORDER", "1") != "1",
                                after_dh=after_dh)
         self.mark("epilogue_bwd")
@@ -364,13 +392,15 @@ class WaveNetEngine(EngineBase):
         """The residual stack's backward, the causal layer's weight gradient and the slab reduction (second half of backward_from_dlogits).
         d_enf: the gradient of the output stage's class term (class-conditional), else None."""
         B, T, pitch, CH = ws["B"], ws["T"], ws["pitch"], self.CH
-        N, cls, cond, d_tab = self.N, ws.get("cls"), None, None
+        N, cls, pos, cond, d_tab = self.N, ws.get("cls"), ws.get("pos"), None, None
         form = "pq" if bw["pq"] or bw["pair"] else "ms" if bw["ms"] else "rw"
-        if cls is not None:
+        le = self.phase or 1
+        conditioned = cls is not None or pos is not None
+        if conditioned:
             # the block tables' gradients, sums of [df; dg] over each clip's time: inside the one-launch block as bucket sums (one
             # bucket) reduced behind the stack, else wn_cond_grad on the [df; dg] the block wrote - as the autoencoder's decoder
             Bp, rows = (B // 2, 4 * CH) if bw["pair"] else (B, 2 * CH)
-            d_tab = torch.zeros(N, Bp, rows, dtype=torch.float32, device=self.device)
+            d_tab = torch.zeros(N, Bp, rows, *((le,) if self.phase else ()), dtype=torch.float32, device=self.device)
             if form == "pq" and "cslab" not in bw:
                 import ctypes
                 fl = [_lib.load().wn_resblock_bwd_pq_cond_floats(self.off[i + 1], T, Bp) for i in range(N)]
@@ -380,12 +410,13 @@ class WaveNetEngine(EngineBase):
 
             def cond(i):
                 mc = dict(cidx=ptr(ws["cidx"][i]), cslab=ptr(bw["cslab"], bw["cs_off"][i])) if form == "pq" else {}
-                return Cond(ptr(ws["tab"][i]), rows, 1, 1, T - self.off[i + 1], **mc)
+                return Cond(ptr(ws["tab"][i]), rows * le, *self._cond_shape(ws, i), **mc)
 
         def bias_grads(i, dfg, dy, t_lo, s_):
             """row sums of [df;dg] and of dy: the gradients of block i's three biases (and of its class table)"""
-            if cls is not None:
-                call("wn_cond_grad", dfg, 2 * CH * pitch, pitch, 2 * CH, t_lo, T, 1, 1, T - t_lo, ptr(d_tab[i]), 2 * CH, 1, B, s_)
+            if conditioned:
+                _, mode_c, q = self._cond_shape(ws, i)
+                call("wn_cond_grad", dfg, 2 * CH * pitch, pitch, 2 * CH, t_lo, T, mode_c, le, q, ptr(d_tab[i]), 2 * CH * le, le, B, s_)
             if self.use_bias:
                 bo, bn = self.gp_bias_off, "dilation_layer_stack.%d.bias"
                 call("wn_bias_grad", dfg, 2 * CH * pitch, pitch, 0, self.D, t_lo, T, B, ptr(self.gpack, bo[bn % (4 * i)]), s_)
@@ -396,9 +427,15 @@ class WaveNetEngine(EngineBase):
         # side stream next to the data-gradient chain (resblock_bwd -> dx product -> next block); dfg / z scratch is double-buffered for that.
         self.stack.backward(form, B, T, pitch, ws["X"], ws["Z"], bw, bw["dX"], st, chain=bw["chain"], dfg=bw["dfg"],
                             zs=None if self.z_from_fwd else bw["zs"], cond=cond, pair=bw["pair"], hook=bias_grads)
-        if cls is not None and form == "pq":
-            call("wn_resblock_bwd_pq_cond_reduce", ptr(bw["cslab"]), bw["cs_off"], bw["cs_tlo"], N, T, Bp, 1, ptr(d_tab), Bp * rows, rows, 1, st)
+        if conditioned and form == "pq":
+            call("wn_resblock_bwd_pq_cond_reduce", ptr(bw["cslab"]), bw["cs_off"], bw["cs_tlo"], N, T, Bp, le, ptr(d_tab), Bp * rows * le,
+                 rows * le, le, st)
         self.join_side()              # everything on the side stream (epilogue weight gradients)
+        if pos is not None:           # behind the last table gradient: the phase tables' own, flat_grad's tail, and the sums over the
+            sums = (torch.empty(N, Bp, rows, dtype=torch.float32, device=self.device),                 # frames: the class term's
+                    torch.empty(B, self.S, dtype=torch.float32, device=self.device)) if cls is not None else (None, None)
+            self.phase_bwd(pos, d_tab, bw["pair"], d_enf, CH, st, sums)
+            d_tab, d_enf = sums
         if cls is not None:           # behind the last table gradient: the global block's own, flat_grad's tail
             self.gclass_bwd(cls, d_tab, bw["pair"], d_enf, CH, st)
         self.mark("stack_bwd")
@@ -433,25 +470,26 @@ class WaveNetEngine(EngineBase):
 
     # ------------------------------------------------------------------ fused training step
     def loss_and_grad_codes(self, codes, target, scrambled=True, want_probs=False, objective=None, windows=None, window_pos=None,
-                            classes=None):
+                            classes=None, phase_pos=None):
         """loss_and_grad on the integer codes themselves (int32 (B,T) on the device; `scrambled` = the loader's one-hot
         layout, faster_audio_data.py:77-81): same result as loss_and_grad(self.onehot(codes, scrambled), target), but the
         (B,256,T) float tensor is never built, written or read - the causal layer is a gather forward and
         a scatter backward."""
         return self.loss_and_grad(None, target, want_probs, codes=(codes, scrambled), objective=objective, windows=windows,
-                                  window_pos=window_pos, classes=classes)
+                                  window_pos=window_pos, classes=classes, phase_pos=phase_pos)
 
-    def loss_and_grad(self, x, target, want_probs=False, codes=None, objective=None, windows=None, window_pos=None, classes=None):
+    def loss_and_grad(self, x, target, want_probs=False, codes=None, objective=None, windows=None, window_pos=None, classes=None,
+                      phase_pos=None):
         """forward + CrossEntropyLoss(probs, target) + backward (wavenet/train.py:178-181).
         Returns the loss as a 0-d device tensor; gradients land in self.flat_grad.  objective: None = self.objective
         (EngineBase; "nll" = the negative log-likelihood under the per-timestep softmax instead of the reference's loss).  windows /
-        window_pos: the position windows of "nll" (EngineBase.step_nll; None = self.nll_windows).  classes: forward_logits'."""
+        window_pos: the position windows of "nll" (EngineBase.step_nll; None = self.nll_windows).  classes, phase_pos: forward_logits'."""
         def step():
             self.mark("begin")
             self.pack_weights()
             self.mark("pack")
-            return self._fused_tail(self.forward_logits(x, codes=codes, classes=classes), target, want_probs, objective, windows,
-                                    window_pos)
+            return self._fused_tail(self.forward_logits(x, codes=codes, classes=classes, phase_pos=phase_pos), target, want_probs, objective,
+                                    windows, window_pos)
         return self._throttled(step)
 
     def softmax_ce(self, *args):

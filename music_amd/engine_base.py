@@ -318,8 +318,10 @@ class EngineBase:
         if self.use_bias:
             names.append(("post_process_2.bias", (self.Q,)))
         names += self.gclass_names(self.N, self.D, self.S, self.g_n, self.g_E)       # (class-conditional: the global block, last)
+        names += self.phase_names(self.N, self.D, self.S, getattr(self, "phase", 0))  # (phase-conditioned: the N + 1 tables behind it)
         self.spec = _Spec(names)
         self.param_names = [n for n, _ in names]
+        self._plan_phase(getattr(self, "phase", 0))
         self._plan_gclass(self.g_n, self.g_E)
         self.flat = torch.zeros(self.spec.total, dtype=torch.float32, device=self.device)
         self.flat_grad = torch.zeros(self.spec.total, dtype=torch.float32, device=self.device)
@@ -387,18 +389,21 @@ class EngineBase:
     vq_ema = False               # net.vq_update == "ema": wn_vq_bwd_stats in place of wn_vq_bwd, wn_vq_ema_update behind the optimizer
     gcond = False                # net.global_classes > 0: the global block [G_0 .. G_N-1 | G_f | embedding] ends the flat buffer, behind the codebook
     n_gcond = 0                  # its floats: wn_gcond_proj_bwd writes that tail of flat_grad (and the projections' in front of the codebook)
+    phase = 0                    # net.phase_period (the WaveNet engines): the N + 1 phase tables end the flat buffer, behind the global block
+    n_phase = 0                  # their floats: wn_phase_tab_bwd writes that tail of flat_grad
 
     @property
     def n_gather(self):
         """Leading elements of flat_grad that the gather of the gradient pack fills."""
-        return self.spec.total - self.n_cond - self.n_vq - self.n_gcond
+        return self.spec.total - self.n_cond - self.n_vq - self.n_gcond - self.n_phase
 
     @property
     def gathered_param_names(self):
-        """The parameters whose gradients come out of the gradient pack: all but the learned projections' 2 (N + 1), the codebook and
-        the global block's N + 2, the last ones."""
+        """The parameters whose gradients come out of the gradient pack: all but the learned projections' 2 (N + 1), the codebook,
+        the global block's N + 2 and the phase tables' N + 1, the last ones."""
         N = len(self.dil)
-        return self.param_names[:len(self.param_names) - (2 * (N + 1) if self.learned else 0) - (1 if self.vq else 0) - (N + 2 if self.gcond else 0)]
+        return self.param_names[:len(self.param_names) - (2 * (N + 1) if self.learned else 0) - (1 if self.vq else 0)
+                                - (N + 2 if self.gcond else 0) - (N + 1 if self.phase else 0)]
 
     def _plan_cond(self, net):
         """Learned mode: where wn_cond_proj_fwd / wn_cond_proj_bwd find the projections in the flat buffers; the vq bottleneck's
@@ -637,12 +642,13 @@ class EngineBase:
             return
         o, N = self.spec.off, len(self.dil)
         self.g_E, self.g_n = E, n
+        n_phase = getattr(self, "n_phase", 0)                 # (the phase tables, behind the global block)
         gw0, gwf, emb = o["gcond_layer_stack.0.weight"], o["connection_gcond.weight"], o["global_embedding.weight"]
         gstride = 2 * self.D * E
         assert all(o["gcond_layer_stack.%d.weight" % i] == gw0 + i * gstride for i in range(N)) and gwf == gw0 + N * gstride \
-            and emb == gwf + self.S * E and emb + n * E == self.spec.total
+            and emb == gwf + self.S * E and emb + n * E == self.spec.total - n_phase
         self.gcond_off = (gw0, gstride, gwf, emb)
-        self.n_gcond = self.spec.total - gw0
+        self.n_gcond = self.spec.total - n_phase - gw0
 
     def gclass_fwd(self, cls, tab, tab_pair, enf, ch, st):
         """Every block's table (per clip and / or as clip pairs, padding rows included; one column per clip) and the output stage's
@@ -654,6 +660,64 @@ class EngineBase:
         """dG_i, dG_f and every row of d emb into the tail of flat_grad, from the tables' gradients"""
         call("wn_gclass_bwd", ptr(d_tab), 1 if pair else 0, ptr(d_enf), ptr(self.flat), ptr(self.flat_grad), len(self.dil), self.D, ch,
              self.S, cls.numel(), *self._gcond_args(cls), st)
+
+    # ------------------------------------------------------------------ phase-conditioned WaveNet (the two WaveNet engines)
+    @staticmethod
+    def phase_names(N, D, S, P):
+        """(name, shape) of the phase tables of a phase-conditioned WaveNet, in the order they end the flat buffer"""
+        return ([("phase_layer_stack.%d" % i, (2 * D, P)) for i in range(N)] + [("connection_phase", (S, P))]) if P > 0 else []
+
+    def _plan_phase(self, P):
+        """Where wn_phase_tab_fwd / wn_phase_tab_bwd find T_i (2 D x P, gate rows first) and T_f (S x P): the tail of flat / flat_grad,
+        behind the global block; and the stages' rotations.  Output column c of a clip whose first target sits at stream position
+        pos predicts position pos + c and sits at absolute time rf - 1 + c; block i's table is read at frame (t - t_lo_i) mod P, so its
+        frame l is the parameter's column (l + pos + t_lo_i - (rf - 1)) mod P: rot[i] = (off[i + 1] - (rf - 1)) mod P, 0 for the
+        output stage, whose table is expanded from rf - 1."""
+        self.phase = int(P)
+        if not self.phase:
+            return
+        o, N = self.spec.off, len(self.dil)
+        pw0, pwf = o["phase_layer_stack.0"], o["connection_phase"]
+        pstride = 2 * self.D * P
+        assert all(o["phase_layer_stack.%d" % i] == pw0 + i * pstride for i in range(N)) and pwf == pw0 + N * pstride \
+            and pwf + self.S * P == self.spec.total
+        self.phase_off = (pw0, pstride, pwf)
+        self.n_phase = self.spec.total - pw0
+        self.phase_rot = torch.tensor([(self.off[i + 1] - (self.rf - 1)) % P for i in range(N)] + [0], dtype=torch.int32, device=self.device)
+
+    def stage_phase(self, phase_pos, B):
+        """`phase_pos` of forward / loss_and_grad -> what the workspace keeps as ws["pos"]: None with the mode off (a given value is
+        refused), else the (B,) int64 vector of the clips' stream positions on the device - ONE copy per step.  One int for all clips,
+        one per clip, or a device tensor; values still on the host are checked here, before anything is launched (a device tensor's
+        negative entries are the kernel's to turn into NaN)."""
+        if not self.phase:
+            if phase_pos is not None:
+                raise ValueError("music_amd: phase_period is 0: this model takes no phase_pos, pass phase_pos=None")
+            return None
+        if phase_pos is None:
+            raise ValueError("music_amd: phase_period = %d: pass phase_pos, the stream position of every clip's first target "
+                             "(one integer >= 0 per clip)" % self.phase)
+        if isinstance(phase_pos, (int, np.integer)) and not isinstance(phase_pos, bool):
+            phase_pos = [int(phase_pos)] * B
+        pos = phase_pos if torch.is_tensor(phase_pos) else torch.as_tensor(list(phase_pos))
+        if pos.dim() != 1 or pos.numel() != B or pos.is_floating_point() or pos.is_complex() or pos.dtype == torch.bool:
+            raise ValueError("music_amd: phase_pos must be %d integers, one per clip, not %s of shape %s" % (B, pos.dtype, tuple(pos.shape)))
+        if pos.device.type == "cpu" and B and int(pos.min()) < 0:
+            raise ValueError("music_amd: a phase_pos is negative (%d): stream positions are >= 0" % int(pos.min()))
+        return pos.to(device=self.device, dtype=torch.int64, non_blocking=True).contiguous()
+
+    def phase_fwd(self, pos, tab, tab_pair, enf, ch, st, add=(None, None, None), rot=None):
+        """Every block's table of P frames (per clip and / or as clip pairs, padding rows included) and the output stage's enf
+        (B, S, P) of the clips' positions, in one launch; add = wn_gclass_fwd's (tab, tab_pair, enf): the class term, added per frame;
+        rot: the stages' rotations (default: the forward's, self.phase_rot; the decoder's tables take zeros)"""
+        call("wn_phase_tab_fwd", ptr(self.flat), *self.phase_off, ptr(pos), ptr(self.phase_rot if rot is None else rot), *(ptr(a) for a in add), ptr(tab),
+             ptr(tab_pair), ptr(enf), len(self.dil), self.D, ch, self.S, self.phase, pos.numel(), st)
+
+    def phase_bwd(self, pos, d_tab, pair, d_enf, ch, st, sums=(None, None)):
+        """dT_i and dT_f into the tail of flat_grad, from the tables' gradients; sums = (sum_tab, sum_enf): their sums over the
+        frames, what wn_gclass_bwd takes as the class term's gradients"""
+        call("wn_phase_tab_bwd", ptr(d_tab), 1 if pair else 0, ptr(d_enf), ptr(self.flat_grad), *self.phase_off, ptr(pos),
+             ptr(self.phase_rot), *(ptr(a) for a in sums), len(self.dil), self.D, ch, self.S, self.phase, pos.numel(), st)
 
     # ------------------------------------------------------------------ the second stream
     def _side_stream(self):

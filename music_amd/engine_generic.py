@@ -30,10 +30,12 @@ from .plan_generic import GeneralPlan, PackBuilder, Pass
 
 class GenericWaveNetEngine(GeneralPlan):
     def __init__(self, dilations, residual_channels, dilation_channels, skip_channels, quantization_channels=256,
-                 filter_width=2, use_bias=False, mode_fwd="f16x3", mode_bwd="bf16x3", device=None, global_classes=0, global_channels=0):
+                 filter_width=2, use_bias=False, mode_fwd="f16x3", mode_bwd="bf16x3", device=None, global_classes=0, global_channels=0,
+                 phase_period=0):
         self.dil = [int(d) for d in dilations]
         self.k = int(filter_width)
         self.g_n, self.g_E = int(global_classes), int(global_channels)
+        self.phase = int(phase_period)                     # phase-conditioned: the period P of the stream's stages (0: off)
         self._geometry()
         self.R, self.D, self.S, self.Q = residual_channels, dilation_channels, skip_channels, quantization_channels
         self.use_bias = bool(use_bias)
@@ -76,21 +78,35 @@ class GenericWaveNetEngine(GeneralPlan):
         return ws
 
     # ------------------------------------------------------------------ forward
-    def forward_logits(self, x, ws=None, classes=None):
-        """classes: one integer per clip of a class-conditional model (EngineBase.stage_classes), else None"""
+    def forward_logits(self, x, ws=None, classes=None, phase_pos=None):
+        """classes: one integer per clip of a class-conditional model (EngineBase.stage_classes), else None; phase_pos: the stream
+        position of every clip's first target of a phase-conditioned model (EngineBase.stage_phase), else None"""
         B, Q, T = x.shape
         assert Q == self.Q and x.is_contiguous() and x.dtype == torch.float32 and x.is_cuda
         W = T - self.rf + 1
         if W <= 0:
             raise ValueError("wave sample not long enough")          # wavenet/model.py:100-101
-        cls = self.stage_classes(classes, B)
+        cls, pos = self.stage_classes(classes, B), self.stage_phase(phase_pos, B)
         ws = ws or self._ws.get(B, T)
         N, RP, DP, SP, QP, pitch = self.N, self.RP, self.DP, self.SP, self.QP, ws["pitch"]
         xin_p, xin_bs = self._stage_input(ws, x)
         ps = Pass(self, ws)
-        ws["cls"] = cls
+        ws["cls"], ws["pos"] = cls, pos
         cond, cond_f = (lambda i: None), None
-        if cls is not None:
+        if pos is not None:
+            # a table of P frames per clip in the tile mode (frame (t - t_lo) mod P): the phase tables' columns rotated by the clip's
+            # position (wn_phase_tab_fwd), plus the class term's column where there are classes
+            P, add = self.phase, (None, None, None)
+            empty = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=self.device)
+            if cls is not None:
+                add = (empty(N, B, 2 * DP), None, empty(B, self.S))
+                self.gclass_fwd(cls, add[0], None, add[2], DP, ps.st)
+            tab, enf = empty(N, B, 2 * DP, P), empty(B, self.S, P)
+            self.phase_fwd(pos, tab, None, enf, DP, ps.st, add)
+            cond = lambda i: (ptr(tab[i]), 2 * DP, P, 2, 1)
+            cond_f = (ptr(enf), self.S, P, 2, 1)
+            self.mark("phase_fwd")
+        elif cls is not None:
             # the clips' tables, one column each: [f; g]_i += G_i emb[c] and h += G_f emb[c], constant over time - a table of one
             # frame stretched over the block's whole valid range (mode 1, q = its length)
             tab = torch.empty(N, B, 2 * DP, dtype=torch.float32, device=self.device)
@@ -121,10 +137,10 @@ class GenericWaveNetEngine(GeneralPlan):
         self.mark("epilogue_fwd")
         return ws
 
-    def forward(self, x, classes=None):
+    def forward(self, x, classes=None, phase_pos=None):
         """wavenet/model.py:86-145 -> probabilities (B*W, Q) (fresh tensor)."""
         self.pack_weights()
-        ws = self.forward_logits(x, classes=classes)
+        ws = self.forward_logits(x, classes=classes, phase_pos=phase_pos)
         B, W = ws["B"], ws["W"]
         probs = torch.empty(B * W, self.Q, dtype=torch.float32, device=self.device)
         self.softmax_fwd(ws["O"], probs, B * W)
@@ -148,9 +164,15 @@ class GenericWaveNetEngine(GeneralPlan):
         self._check_input_unchanged(ws)
         ps = Pass(self, ws, bw)
         bn = "dilation_layer_stack.%d.bias"
-        cls, cond, cond_f = ws.get("cls"), (lambda i: None), None
-        if cls is not None:                      # the tables' gradients: sums of [df; dg] and of dh over each clip's time
-            B = ws["B"]
+        cls, pos, cond, cond_f = ws.get("cls"), ws.get("pos"), (lambda i: None), None
+        B = ws["B"]
+        if pos is not None:                      # the P-frame tables' gradients: sums of [df; dg] and of dh over each frame's samples
+            P = self.phase
+            d_tab = torch.zeros(N, B, 2 * DP, P, dtype=torch.float32, device=self.device)
+            d_enf = torch.zeros(B, self.S, P, dtype=torch.float32, device=self.device)
+            cond = lambda i: (ptr(d_tab[i]), 2 * DP, P, 2, 1)
+            cond_f = (ptr(d_enf), self.S, P, 2, 1)
+        elif cls is not None:                    # the tables' gradients: sums of [df; dg] and of dh over each clip's time
             d_tab = torch.zeros(N, B, 2 * DP, dtype=torch.float32, device=self.device)
             d_enf = torch.zeros(B, self.S, dtype=torch.float32, device=self.device)
             cond = lambda i: (ptr(d_tab[i]), 2 * DP, 1, 1, T - self.off[i + 1])
@@ -167,6 +189,11 @@ class GenericWaveNetEngine(GeneralPlan):
                          ptr(ws["Z"], SLACK + i * DP * pitch), ptr(bw["dZ"], SLACK + i * DP * pitch), zb, DP, self.dil[i],
                          self.off[i], self.off[i + 1], lo, [(bn % (4 * i), 0, self.D), (bn % (4 * i + 1), DP, self.D)],
                          bn % (4 * i + 2), cond(i))
+        if pos is not None:                      # behind the last table gradient: the phase tables' own, flat_grad's tail ...
+            sums = (torch.empty(N, B, 2 * DP, dtype=torch.float32, device=self.device),
+                    torch.empty(B, self.S, dtype=torch.float32, device=self.device)) if cls is not None else (None, None)
+            self.phase_bwd(pos, d_tab, False, d_enf, DP, ps.st, sums)
+            d_tab, d_enf = sums                  # (... and the sums over the frames: the class term's gradients)
         if cls is not None:                      # behind the last table gradient: the global block's own, flat_grad's tail
             self.gclass_bwd(cls, d_tab, False, d_enf, DP, ps.st)
         self.mark("stack_bwd")
@@ -180,20 +207,20 @@ class GenericWaveNetEngine(GeneralPlan):
         return self._causal_input_grad(ws, [("causalT", self.RP, "dX")])
 
     # ------------------------------------------------------------------ fused training step (wavenet/train.py:178-181)
-    def _step_forward(self, x, classes=None):
+    def _step_forward(self, x, classes=None, phase_pos=None):
         self.mark("begin")
         self.pack_weights()
-        return self.forward_logits(x, classes=classes)
+        return self.forward_logits(x, classes=classes, phase_pos=phase_pos)
 
-    def loss_and_grad(self, x, target, want_probs=False, objective=None, windows=None, window_pos=None, classes=None):
-        """objective: None = self.objective (EngineBase); windows / window_pos: step_nll's; classes: as in forward_logits"""
-        return self._throttled(lambda: self._fused_tail(self._step_forward(x, classes), target, want_probs, objective, windows,
+    def loss_and_grad(self, x, target, want_probs=False, objective=None, windows=None, window_pos=None, classes=None, phase_pos=None):
+        """objective: None = self.objective (EngineBase); windows / window_pos: step_nll's; classes, phase_pos: as in forward_logits"""
+        return self._throttled(lambda: self._fused_tail(self._step_forward(x, classes, phase_pos), target, want_probs, objective, windows,
                                                        window_pos))
 
     def loss_and_grad_codes(self, codes, target, scrambled=True, want_probs=False, objective=None, windows=None, window_pos=None,
-                            classes=None):
+                            classes=None, phase_pos=None):
         """the fast engine's entry point on integer codes; here the one-hot is built (wn_onehot) and the dense path runs"""
-        return self.loss_and_grad(self.onehot(codes, scrambled), target, want_probs, objective, windows, window_pos, classes)
+        return self.loss_and_grad(self.onehot(codes, scrambled), target, want_probs, objective, windows, window_pos, classes, phase_pos)
 
     def onehot(self, codes, scrambled=True):
         """int32 (B,T) codes on the device -> float32 (B,Q,T) (faster_audio_data.py:62-83)."""

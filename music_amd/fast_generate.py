@@ -375,11 +375,57 @@ def _check_classes(net, classes):
         raise ValueError("music_amd.fast_generate: this model takes no classes, pass classes=None")
 
 
-def _class_cond(net, eng, classes, U, correct_queue):
+def _check_phase(net, phase_pos):
+    """phase_pos is refused by a model without the mode (or without the notion) and required by one with it, before any launch; the
+    generators take ONE stream position for the launch, as they take one window_pos"""
+    check = getattr(net, "check_phase", None)
+    if check is not None:
+        check(phase_pos)
+    elif phase_pos is not None:
+        raise ValueError("music_amd.fast_generate: this model takes no phase_pos, pass phase_pos=None")
+    if phase_pos is not None and (isinstance(phase_pos, bool) or not isinstance(phase_pos, (int, np.integer))):
+        raise ValueError("music_amd.fast_generate: phase_pos is one integer >= 0, the stream position of the first token the launch "
+                         "chooses, not %r" % (phase_pos,))
+
+
+def _phase_cond(net, eng, cls, U, pos0):
+    """The decode tables of a phase-conditioned WaveNet: cond_fg (U, N, P, 2 Dp) rows [f | g] and cond_p1 (U, P, S), frame l = the
+    phase tables' column l (plus the utterance's class column where there are classes: wn_gclass_fwd, then wn_phase_tab_fwd at position
+    0 without rotation), under a schedule with c_shift = 0, c_q = 0 (the tile rule: column c mod P) and le = P.  pos0: the stream
+    position of the launch's first step - priming steps may lie in front of stream position 0, where the entry would read column 0;
+    the tile rule is periodic, so the launch is given pos0 mod P (the mathematical one: a multiple of P added), never negative."""
+    pack = _pack_for(net, eng)
+    N, D, S, Dp, P, dev = eng.N, eng.D, eng.S, pack.Dp, eng.phase, eng.device
+    ch = -(-D // 32) * 32
+    empty = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+    st, add = _lib.stream(), (None, None, None)
+    if cls is not None:
+        add = (empty(N, U, 2 * ch), None, empty(U, S))
+        eng.gclass_fwd(cls, add[0], None, add[2], ch, st)
+    tab, enf = empty(N, U, 2 * ch, P), empty(U, S, P)
+    zero_pos, zero_rot = torch.zeros(U, dtype=torch.int64, device=dev), torch.zeros(N + 1, dtype=torch.int32, device=dev)
+    eng.phase_fwd(zero_pos, tab, None, enf, ch, st, add, rot=zero_rot)
+    cond_fg = torch.zeros(U, N, P, 2 * Dp, dtype=torch.float32, device=dev)
+    cond_fg[:, :, :, :D] = tab[:, :, :D].permute(1, 0, 3, 2)
+    cond_fg[:, :, :, Dp:Dp + D] = tab[:, :, ch:ch + D].permute(1, 0, 3, 2)
+    cond_p1 = enf.transpose(1, 2).contiguous()
+    shift = (ctypes.c_int32 * (N + 1))(*([0] * (N + 1)))
+    qs = (ctypes.c_int32 * (N + 1))(*([0] * (N + 1)))
+    cond = (ptr(cond_fg), cond_fg[0].numel(), ptr(cond_p1), cond_p1[0].numel(), ctypes.cast(shift, ctypes.c_void_p),
+            ctypes.cast(qs, ctypes.c_void_p), P, int(pos0) % P)
+    return cond, (cond_fg, cond_p1, shift, qs)
+
+
+def _class_cond(net, eng, classes, U, correct_queue, phase_pos0=None):
     """The conditioning arguments of a class-conditional WaveNet's decode launch (None with the mode off): the U utterances' tables
     - cond_fg (U, N, 1, 2 Dp) rows [f | g], cond_p1 (U, 1, S) - built on the device from wn_gclass_fwd's output, under a schedule
     of one frame that every position reads.  Classes are refused with the mode off and required with it on (EngineBase.stage_classes);
-    corrected recurrence only.  Returns (wn_decode_batch_cond's eight table arguments, the tensors they point into)."""
+    corrected recurrence only.  phase_pos0: the stream position of the launch's first step for a phase-conditioned model, whose tables
+    have P frames (``_phase_cond``, with or without classes).  Returns (wn_decode_batch_cond's eight table arguments, the tensors
+    they point into)."""
+    if getattr(eng, "phase", 0):
+        _corrected_only(correct_queue, "a phase-conditioned model decodes", "wn_decode_batch_cond")
+        return _phase_cond(net, eng, eng.stage_classes(classes, U), U, phase_pos0)
     if classes is None and not getattr(eng, "gcond", False):
         return None, None
     cls = eng.stage_classes(classes, U)
@@ -598,11 +644,12 @@ def _rings_from_workspace(eng, U, T):
                       for i, d in enumerate(eng.dil)], 1).contiguous()
 
 
-def _prime(net, start_pieces, classes=None, rows=1):
+def _prime(net, start_pieces, classes=None, rows=1, phase_pos=None):
     """THE prompt stage of every generator: the full forward over the U start pieces ``(U, Q, receptive_field)`` and the state it
     leaves -> (engine, probabilities (rows U, Q), rings (rows U, ring floats), prev0 (rows U, k-1, Q): the causal layer's queue =
     the last k-1 input columns, oldest first, the classes of the rows).  ``rows`` = 2 is guidance: every utterance becomes a pair of
-    rows, as its class and as ``net.null_class``, [c_u, null_class] interleaved, for the forward and for the class tables."""
+    rows, as its class and as ``net.null_class``, [c_u, null_class] interleaved, for the forward and for the class tables.
+    ``phase_pos``: the stream position of the code the forward predicts (a phase-conditioned model), the same for every row."""
     assert start_pieces.dim() == 3 and start_pieces.size(2) == net.receptive_field
     dev = start_pieces.device if start_pieces.is_cuda else torch.device("cuda")
     x = start_pieces.detach().to(dev).float()
@@ -614,14 +661,15 @@ def _prime(net, start_pieces, classes=None, rows=1):
         x = x.repeat_interleave(2, 0)
     x = x.contiguous()
     with torch.no_grad():
-        probs = net(x) if classes is None else net(x, classes=classes)     # (rows U, Q): W == 1
+        kw = {} if phase_pos is None else {"phase_pos": int(phase_pos)}
+        probs = net(x, **kw) if classes is None else net(x, classes=classes, **kw)     # (rows U, Q): W == 1
     eng, n, T = net._engine, x.size(0), x.size(2)
     return eng, probs.view(n, -1), _rings_from_workspace(eng, n, T), x[:, :, T - _taps(eng):T].transpose(1, 2).contiguous(), classes
 
 
-def _init_forward(net, note, classes=None):
+def _init_forward(net, note, classes=None, phase_pos=None):
     """The full forward over a ``(1, Q, receptive_field)`` piece: (probabilities (1, Q), the queues it leaves)."""
-    eng, probs, rings, prev0, _ = _prime(net, note, classes)
+    eng, probs, rings, prev0, _ = _prime(net, note, classes, phase_pos=phase_pos)
     return probs, DecodeState(eng, rings[0], prev0.view(-1), 0)
 
 
@@ -641,7 +689,7 @@ def predict_next(net, note, state_queue=None, correct_queue=False):
 
 
 def generate_codes(net, start_piece, note_num, correct_queue=False, temperature=None, seed=0, top_k=None, top_p=None,
-                   windows=None, window_pos=0, classes=None, guidance=None, keep=None):
+                   windows=None, window_pos=0, classes=None, guidance=None, keep=None, phase_pos=None):
     """The greedy loop of fast_generate.py:162-172 as one init forward + ONE persistent launch.
     Returns the note_num generated codes (int64, on the device).
     ``temperature`` (the reference is greedy only): if given and > 0, every code after the
@@ -655,19 +703,26 @@ def generate_codes(net, start_piece, note_num, correct_queue=False, temperature=
     ``classes``: ``[c]``, the class to generate as, for a class-conditional model (required there, refused elsewhere): the init
     forward runs with it and the launch is the conditioned one (wn_decode_batch_cond).  Corrected recurrence only.
     ``guidance``: a scale s, classifier-free guidance (``generate_codes_batch``; the one-utterance batch of it).
-    ``keep``: (note_num,) or (1, note_num) integers - partially forced decode (``generate_codes_batch``)."""
+    ``keep``: (note_num,) or (1, note_num) integers - partially forced decode (``generate_codes_batch``).
+    ``phase_pos``: the stream position of the first code returned, for a phase-conditioned model (required there, refused
+    elsewhere; ``window_pos``'s convention): the code at position p is conditioned on phase p mod phase_period.  The start piece's
+    positions lie in front of it, mod the period - also where that is in front of stream position 0.  Corrected recurrence only."""
     if guidance is not None:
         return generate_codes_batch(net, start_piece, note_num, correct_queue=correct_queue, temperature=temperature, seed=seed,
                                     top_k=top_k, top_p=top_p, windows=windows, window_pos=window_pos, classes=classes,
-                                    guidance=guidance, **({} if keep is None else {"keep": keep}))[0]
+                                    guidance=guidance, **({} if keep is None else {"keep": keep}),
+                                    **({} if phase_pos is None else {"phase_pos": phase_pos}))[0]
     win = _windows_of(windows, window_pos, net.quantization_channels, correct_queue)
     _check_classes(net, classes)
+    _check_phase(net, phase_pos)
+    if phase_pos is not None:
+        _corrected_only(correct_queue, "a phase-conditioned model decodes", "wn_decode_batch_cond")
     kept = _keep_of(keep, 1, note_num, net.quantization_channels, win, correct_queue)
-    probs, state = _init_forward(net, start_piece, classes)
+    probs, state = _init_forward(net, start_piece, classes, phase_pos)
     # (the plain call picks as predict_next does, with the reference's topk: the argmax, whatever either makes of a tie)
-    first = torch.topk(probs.view(-1), 1)[1] if win is None and classes is None else _first_codes(probs, win)
+    first = torch.topk(probs.view(-1), 1)[1] if win is None and classes is None and phase_pos is None else _first_codes(probs, win)
     eng = state.eng
-    cond, tables = _class_cond(net, eng, classes, 1, correct_queue)
+    cond, tables = _class_cond(net, eng, classes, 1, correct_queue, None if phase_pos is None else phase_pos + 1)
     if kept is not None and note_num >= 1:
         first = _resolved(kept[:, 0], first)
     if note_num <= 1:
@@ -680,7 +735,7 @@ def generate_codes(net, start_piece, note_num, correct_queue=False, temperature=
 
 
 def generate_codes_batch(net, start_pieces, note_num, correct_queue=False, temperature=None, seed=0, top_k=None, top_p=None,
-                         streams=None, windows=None, window_pos=0, classes=None, guidance=None, keep=None):
+                         streams=None, windows=None, window_pos=0, classes=None, guidance=None, keep=None, phase_pos=None):
     """SURVEY 8f2 (batched utterances; the reference generates one at a time): greedy generation of
     ``note_num`` codes for U independent start pieces ``(U, Q, receptive_field)`` in ONE persistent
     launch - on the matrix-core path eight utterances to a workgroup pair, one pair of MFMA result columns each (else one
@@ -703,9 +758,14 @@ def generate_codes_batch(net, start_pieces, note_num, correct_queue=False, tempe
     mask - and the function returns the fed stream, ``where(keep >= 0, keep, codes)``.  Under ``windows`` a kept token outside the
     window of its position ``window_pos + j`` is a ValueError before any launch (``check_keep``); under ``guidance`` both rows of a
     pair are fed the utterance's row.  Fill the absent stages of a residual-VQ stream, continue a prompt of any length, regenerate
-    single positions - in the one launch.  Corrected recurrence only; None is the call without the argument."""
+    single positions - in the one launch.  Corrected recurrence only; None is the call without the argument.
+    ``phase_pos``: as in ``generate_codes``; one position for the whole launch.  Under ``guidance`` the unconditional member's table
+    is the null class's column plus the phase column."""
     assert start_pieces.dim() == 3 and start_pieces.size(2) == net.receptive_field
     _check_classes(net, classes)
+    _check_phase(net, phase_pos)
+    if phase_pos is not None:
+        _corrected_only(correct_queue, "a phase-conditioned model decodes", "wn_decode_batch_cond")
     win = _windows_of(windows, window_pos, net.quantization_channels, correct_queue)
     U = start_pieces.size(0)
     kept = _keep_of(keep, U, note_num, net.quantization_channels, win, correct_queue)
@@ -714,8 +774,8 @@ def generate_codes_batch(net, start_pieces, note_num, correct_queue=False, tempe
     if rows * U > 1024:
         raise ValueError("at most 1024 utterances per launch (128 off the matrix-core path)" if guide is None else
                          "at most 512 guided utterances per launch (64 off the matrix-core path): every one is a pair of rows")
-    eng, probs, rings, prev0, row_classes = _prime(net, start_pieces, classes, rows)
-    cond, tables = _class_cond(net, eng, row_classes, rows * U, correct_queue)
+    eng, probs, rings, prev0, row_classes = _prime(net, start_pieces, classes, rows, phase_pos)
+    cond, tables = _class_cond(net, eng, row_classes, rows * U, correct_queue, None if phase_pos is None else phase_pos + 1)
     first = _first_codes(probs, win, guide)
     if kept is not None and note_num >= 1:
         first = _resolved(kept[:, 0], first)
@@ -742,7 +802,7 @@ def generate_codes_batch(net, start_pieces, note_num, correct_queue=False, tempe
 
 def decode_batch_cond(net, rings, prev0, note0, n_steps, step0=0, pos0=0, forced=None, want_probs=False, temperature=None,
                       seed=0, cond_fg=None, cond_p1=None, schedule=None, top_k=None, top_p=None, streams=None, windows=None,
-                      window_pos=0, guidance=None):
+                      window_pos=0, guidance=None, phase_pos=None, classes=None):
     """One persistent launch of wn_decode_batch_cond (corrected recurrence) for U utterances from explicit state: ``rings``
     (U, ring floats) is advanced in place, ``prev0`` (U, k-1, Q) / ``note0`` (U, Q) are the causal layer's history and the
     first input column.  ``cond_fg`` (U, N, Le, 2 Dp) rows [f | g] and ``cond_p1`` (U, Le, S) are the per-utterance
@@ -756,6 +816,10 @@ def decode_batch_cond(net, rings, prev0, note0, n_steps, step0=0, pos0=0, forced
     len(windows)`` (wn_win_decode_batch; independent of ``step0`` and ``pos0``).
     ``guidance``: (U / 2,) scales - the rows are (conditional, unconditional) pairs with equal ``note0`` / ``prev0`` / ``forced``
     rows, decoded by wn_cfg_decode_batch; every output comes back for all U rows.
+    ``phase_pos``: for a phase-conditioned model (required there, refused elsewhere) the stream position of output position 0 - step
+    s chooses the token at stream position phase_pos + pos0 + s - with ``classes``, one per row, where the model has classes too; the
+    tables are built here (``cond_fg`` / ``cond_p1`` / ``schedule`` stay None).  Priming steps (pos0 < 0) may lie in front of stream
+    position 0: the phase is periodic.
     Returns (codes int32 (U, n_steps), probabilities (U, n_steps, Q) or None, note_out, prev_out)."""
     eng = net._engine_for(rings.device)
     pack = _pack_for(net, eng)
@@ -767,6 +831,9 @@ def decode_batch_cond(net, rings, prev0, note0, n_steps, step0=0, pos0=0, forced
         raise ValueError("at most 1024 utterances per launch (128 off the matrix-core path)")
     smp = _Sampling(U, temperature, top_k, top_p, seed, streams, dev)
     win = _windows_of(windows, window_pos, eng.Q)
+    _check_phase(net, phase_pos)
+    if phase_pos is None and classes is not None:
+        raise ValueError("decode_batch_cond: classes= comes with phase_pos= (a class-conditional model's own tables are the caller's)")
     le = 1
     shift = qs = None
     if cond_fg is not None or cond_p1 is not None:
@@ -788,6 +855,11 @@ def decode_batch_cond(net, rings, prev0, note0, n_steps, step0=0, pos0=0, forced
             raise ValueError("decode_batch_cond: guidance must hold one scale per pair of rows (U / 2 = %s of them, U even)" % (U / 2,))
     cond = (ptr(cond_fg), cond_fg[0].numel() if cond_fg is not None else 0, ptr(cond_p1),
             cond_p1[0].numel() if cond_p1 is not None else 0, shift, qs, le, int(pos0))
+    if phase_pos is not None:
+        if cond_fg is not None or cond_p1 is not None or schedule is not None:
+            raise ValueError("decode_batch_cond: with phase_pos= the tables are the model's own: pass no cond_fg, cond_p1 or schedule")
+        _check_classes(net, classes)
+        cond, tables = _class_cond(net, eng, classes, U, True, int(phase_pos) + int(pos0))
     return _launch_decode(net, eng, smp, rings, note0, prev0, U, n_steps, step0, 1,
                           "wn_decode_batch_cond: a hand-off between two decode workgroups timed out", forced=forced,
                           want_probs=want_probs, cond=cond, win=win.tail() if win is not None else None, guide=gtab)
@@ -843,11 +915,12 @@ def sample_logits(logits, temperature=1.0, top_k=None, top_p=None, seed=0, step0
 
 
 def generate(model_path, model_name, generate_path, generate_name, start_piece=None, sr=16000, duration=10, temperature=None,
-             seed=0, top_k=None, top_p=None, classes=None, guidance=None):
+             seed=0, top_k=None, top_p=None, classes=None, guidance=None, phase_pos=None):
     """wavenet/fast_generate.py:144-179.  ``temperature`` / ``top_k`` / ``top_p`` / ``seed``: sample instead of the greedy
     argmax; a filter selects the corrected queue recurrence (the only one truncated sampling runs on).  ``classes``: ``[c]``, the
     class to generate as (a model whose parameters set "global_classes"; corrected recurrence).  ``guidance``: a classifier-free
-    guidance scale (``generate_codes``; the model's parameters set "null_class")."""
+    guidance scale (``generate_codes``; the model's parameters set "null_class").  ``phase_pos``: the stream position of the first
+    code generated (a model whose parameters set "phase_period"; corrected recurrence)."""
     if os.path.exists(generate_path) is False:
         os.makedirs(generate_path)
     with open('./params/wavenet_params.json', 'r') as f:
@@ -864,8 +937,9 @@ def generate(model_path, model_name, generate_path, generate_name, start_piece=N
     # the as-written queue push exists for filter_width 2 only; every other width runs the corrected recurrence
     generated_piece = generate_codes(net, start_piece.cuda(), duration * sr,
                                      correct_queue=(net.filter_width != 2 or top_k is not None or top_p is not None
-                                                    or classes is not None or guidance is not None),
-                                     temperature=temperature, seed=seed, top_k=top_k, top_p=top_p, classes=classes, guidance=guidance)
+                                                    or classes is not None or guidance is not None or phase_pos is not None),
+                                     temperature=temperature, seed=seed, top_k=top_k, top_p=top_p, classes=classes, guidance=guidance,
+                                     **({} if phase_pos is None else {"phase_pos": phase_pos}))
     print(generated_piece.tolist()[:32], "...")
     audio = mu_law_decode(generated_piece, net.quantization_channels).cpu().numpy()
     from scipy.io import wavfile

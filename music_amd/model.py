@@ -9,6 +9,8 @@ probabilities ``(B*(T-rf+1), Q)`` with the reference's CHUNK softmax semantics, 
 The arithmetic runs only through libwavenet_hip.so (music_amd/engine.py).  There is no CPU
 implementation: calling ``forward`` without a ROCm device raises.
 """
+import math
+
 import torch
 import torch.nn as nn
 
@@ -26,7 +28,7 @@ _Probs = _losshook.Probs                 # the type of the module's output while
 
 class _WaveNetFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, net, grad_on, wave_sample, classes, *params):
+    def forward(ctx, net, grad_on, wave_sample, classes, phase_pos, *params):
         eng = net._engine_for(wave_sample.device)
         x = wave_sample.detach()
         if x.dtype != torch.float32 or not x.is_contiguous():
@@ -35,7 +37,10 @@ class _WaveNetFunction(torch.autograd.Function):
             tag = getattr(wave_sample, "_wn_codes", None)        # one-hot built from codes (engine.forward_logits)
             if tag is not None and wave_sample._version == tag[2]:
                 x._wn_codes = (tag[0], tag[1], x._version, tag[3])
-        probs, ws = eng.forward(x, classes=classes) if classes is not None else eng.forward(x)
+        kw = {} if classes is None else {"classes": classes}
+        if phase_pos is not None:
+            kw["phase_pos"] = phase_pos
+        probs, ws = eng.forward(x, **kw)
         ctx.eng, ctx.ws, ctx.gen = eng, ws, ws["gen"]
         ctx.loss_hook = net._last_hook = _losshook.make(eng, ws, grad_on)
         # a forward that some backward may follow keeps its workspace: the next forward of this shape gets another one (several
@@ -67,14 +72,19 @@ class _WaveNetFunction(torch.autograd.Function):
             grads.append(g[o:o + n].view(shp))
         # the input's own gradient, when autograd asks for it (the reference's causal nn.Conv1d provides it, wavenet/model.py:104)
         din = eng.input_grad(ws) if ctx.needs_input_grad[2] else None
-        return (None, None, din, None) + tuple(grads)
+        return (None, None, din, None, None) + tuple(grads)
 
 
 class wavenet(nn.Module):
 
     def __init__(self, filter_width, dilations, dilation_channels, residual_channels, skip_channels,
-                 quantization_channels, use_bias, global_classes=0, global_channels=0, null_class=None):
+                 quantization_channels, use_bias, global_classes=0, global_channels=0, null_class=None, phase_period=0):
         super(wavenet, self).__init__()
+        phase_period = 0 if phase_period is None else phase_period
+        if isinstance(phase_period, bool) or not isinstance(phase_period, int) or not 0 <= phase_period <= _lib.PHASE_MAX_PERIOD:
+            raise ValueError("music_amd.wavenet: phase_period must be an integer in [1, %d] (0 or absent: off), not %r"
+                             % (_lib.PHASE_MAX_PERIOD, phase_period))
+        self.phase_period = phase_period
         for key, val in (("global_classes", global_classes), ("global_channels", global_channels)):
             if isinstance(val, bool) or not isinstance(val, int) or val < 0:
                 raise ValueError("music_amd.wavenet: %s must be an integer >= 0, not %r" % (key, val))
@@ -120,6 +130,19 @@ class wavenet(nn.Module):
             self.gcond_layer_stack = nn.ModuleList(nn.Conv1d(global_channels, 2 * dilation_channels, 1, bias=False) for _ in dilations)
             self.connection_gcond = nn.Conv1d(global_channels, skip_channels, 1, bias=False)
             self.global_embedding = nn.Embedding(global_classes, global_channels)
+        if phase_period > 0:
+            # phase conditioning (a prior over a residual quantiser's frame-major code stream: the stage is position mod P): a learned
+            # column per phase, [f; g]_i(column) += phase_layer_stack.i[:, p mod P] in every block and h += connection_phase[:, p mod P]
+            # in front of post_process_1's ReLU, p the stream position the column's output predicts.  Tables of shape (2 D, P), gate
+            # rows first like gcond_layer_stack, and (S, P); registered - and drawn - BEHIND everything else, the global block
+            # included.  Init: gcond_layer_stack's rule, nn.Conv1d's default (kaiming uniform with a = sqrt(5)) at fan-in P, which is
+            # U(-1 / sqrt(P), 1 / sqrt(P)).  No biases.
+            def table(rows):
+                t = torch.empty(rows, phase_period)
+                nn.init.kaiming_uniform_(t, a=math.sqrt(5))
+                return nn.Parameter(t)
+            self.phase_layer_stack = nn.ParameterList([table(2 * dilation_channels) for _ in dilations])
+            self.connection_phase = table(skip_channels)
         self._engine = None
         self.precision = ("f16x3", "bf16x3")     # (forward, backward) arithmetic of the MFMA products
         # nn.CrossEntropyLoss()(net(x), target) with its default arguments runs as the engine's fused softmax + CE pass (the output
@@ -140,6 +163,20 @@ class wavenet(nn.Module):
         self.__dict__.setdefault("global_classes", 0)        # (a module pickled before the keys existed)
         self.__dict__.setdefault("global_channels", 0)
         self.__dict__.setdefault("null_class", None)
+        self.__dict__.setdefault("phase_period", 0)
+
+    def named_parameters(self, *args, **kwargs):
+        """torch lists a module's own parameters in front of its children's; connection_phase, the one parameter this module owns
+        directly, is the model's LAST (parameters(), the optimizers, the EMA shadow and the engine's flat buffer follow this order)"""
+        last = self._parameters.get("connection_phase")
+        tail = []
+        for name, p in super(wavenet, self).named_parameters(*args, **kwargs):
+            if last is not None and p is last:
+                tail.append((name, p))
+            else:
+                yield name, p
+        for item in tail:
+            yield item
 
     def global_vectors(self, classes):
         """The (detached) embedding rows (B, E) of `classes`, B integers in [0, global_classes)."""
@@ -160,7 +197,25 @@ class wavenet(nn.Module):
             raise RuntimeError("music_amd.wavenet: the checkpoint was saved with global_classes=%d, global_channels=%d but this model "
                                "was built with global_classes=%d, global_channels=%d (the keys of the model's parameters JSON); "
                                "nothing was loaded" % (saved + mine))
+        ph = state_dict.get("connection_phase", state_dict.get("module.connection_phase"))
+        saved_p, mine_p = int(ph.shape[1]) if ph is not None and ph.dim() == 2 else 0, getattr(self, "phase_period", 0)
+        if saved_p != mine_p:
+            raise RuntimeError("music_amd.wavenet: the checkpoint was saved with phase_period=%d (%s) but this model was built with "
+                               "phase_period=%d (%s) (the key of the model's parameters JSON); nothing was loaded"
+                               % (saved_p, "phase-conditioned" if saved_p else "off", mine_p, "phase-conditioned" if mine_p else "off"))
         return super(wavenet, self).load_state_dict(state_dict, *args, **kwargs)
+
+    def check_phase(self, phase_pos):
+        """phase_pos is refused with the mode off and required with it on - before an engine is built or anything is launched; a
+        negative entry that is still on the host is refused here too"""
+        P = getattr(self, "phase_period", 0)
+        if (phase_pos is None) == bool(P):
+            raise ValueError("music_amd.wavenet: phase_period = %d: phase_pos must be %s"
+                             % (P, "None" if phase_pos is not None else "given, the stream position (>= 0) of every clip's first target"))
+        if phase_pos is not None and not (torch.is_tensor(phase_pos) and phase_pos.device.type != "cpu"):
+            vals = torch.as_tensor(phase_pos).reshape(-1)
+            if vals.numel() and not vals.is_floating_point() and int(vals.min()) < 0:
+                raise ValueError("music_amd.wavenet: a phase_pos is negative (%d): stream positions are >= 0" % int(vals.min()))
 
     def check_classes(self, classes):
         """classes are refused with the mode off and required with it on - before an engine is built or anything is launched"""
@@ -202,7 +257,8 @@ class wavenet(nn.Module):
             self.dilations, self.residual_channels, self.dilation_channels, self.skip_channels,
             self.quantization_channels, self.filter_width, self.use_bias,
             mode_fwd=self.precision[0], mode_bwd=self.precision[1], device=device,
-            **(dict(global_classes=self.global_classes, global_channels=self.global_channels) if self.global_classes else {}))
+            **(dict(global_classes=self.global_classes, global_channels=self.global_channels) if self.global_classes else {}),
+            **(dict(phase_period=self.phase_period) if getattr(self, "phase_period", 0) else {}))
         eng.mode_names = tuple(self.precision)
         assert [n for n, _ in named] == eng.param_names, "parameter order differs from the reference layout"
         with torch.no_grad():
@@ -213,16 +269,19 @@ class wavenet(nn.Module):
         self._engine = eng
         return eng
 
-    def forward(self, wave_sample, classes=None):
-        """classes: one integer in [0, global_classes) per clip of a class-conditional model (required there), else None"""
+    def forward(self, wave_sample, classes=None, phase_pos=None):
+        """classes: one integer in [0, global_classes) per clip of a class-conditional model (required there), else None;
+        phase_pos: the stream position of every clip's first target of a phase-conditioned model (one int for all clips, one per
+        clip, or an int64 device tensor; required there), else None"""
         batch_size, original_channels, seq_len = wave_sample.size()
         output_width = seq_len - self.receptive_field + 1
         if output_width <= 0:
             raise ValueError("wave sample not long enough")
         self.check_classes(classes)
+        self.check_phase(phase_pos)
         params = [p for _, p in self._named_ref_params()]
         self._last_hook = None
-        out = _WaveNetFunction.apply(self, torch.is_grad_enabled(), wave_sample, classes, *params)
+        out = _WaveNetFunction.apply(self, torch.is_grad_enabled(), wave_sample, classes, phase_pos, *params)
         hook, self._last_hook = self._last_hook, None
         return _losshook.wrap(out, hook) if self.fuse_loss else out
 

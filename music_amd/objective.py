@@ -40,7 +40,7 @@ def _dense_input(wave_sample):
     return x
 
 
-def _forward_logits(net, wave_sample, classes=None, stages=None):
+def _forward_logits(net, wave_sample, classes=None, stages=None, phase_pos=None):
     """The module's forward up to the pre-softmax logits: (engine, workspace with the logits in ws["O"]).  The autoencoder draws its
     per-forward conditioning convs from the global RNG, as its own forward does (learned ones are parameters: nothing is drawn)."""
     if wave_sample.dim() != 3:
@@ -49,6 +49,10 @@ def _forward_logits(net, wave_sample, classes=None, stages=None):
         raise ValueError("wave sample not long enough")
     if hasattr(net, "check_classes"):
         net.check_classes(classes)                              # (a class-conditional WaveNet: required there, refused elsewhere)
+    if hasattr(net, "check_phase"):
+        net.check_phase(phase_pos)                              # (a phase-conditioned WaveNet: likewise)
+    elif phase_pos is not None:
+        raise ValueError("music_amd.objective: phase_pos is a phase-conditioned WaveNet's (phase_period)")
     eng = net._engine_for(wave_sample.device)
     x = _dense_input(wave_sample)
     if hasattr(net, "engine_cond"):
@@ -59,7 +63,10 @@ def _forward_logits(net, wave_sample, classes=None, stages=None):
         if stages is not None:
             raise ValueError("music_amd.objective: stages are the autoencoder's (quantiser dropout)")
         eng.pack_weights()
-        ws = eng.forward_logits(x, classes=classes) if classes is not None else eng.forward_logits(x)
+        kw = {} if classes is None else {"classes": classes}
+        if phase_pos is not None:
+            kw["phase_pos"] = phase_pos
+        ws = eng.forward_logits(x, **kw)
     return eng, ws
 
 
@@ -75,8 +82,8 @@ class _NLLFunction(torch.autograd.Function):
     backward_from_dlogits scaled by the upstream scalar."""
 
     @staticmethod
-    def forward(ctx, net, grad_on, wave_sample, target, classes, stages, windows, window_pos, *params):
-        eng, ws = _forward_logits(net, wave_sample, classes, stages)
+    def forward(ctx, net, grad_on, wave_sample, target, classes, stages, windows, window_pos, phase_pos, *params):
+        eng, ws = _forward_logits(net, wave_sample, classes, stages, phase_pos)
         need = grad_on and any(ctx.needs_input_grad)
         eng.step_nll(ws, _flat_target(target, ws), eng._bwd_workspace(ws)["dO"] if need else None, windows=windows,
                      window_pos=window_pos)
@@ -109,7 +116,7 @@ class _NLLFunction(torch.autograd.Function):
             o, shp = eng.spec.off[name], eng.spec.shape[name]
             grads.append(g[o:o + int(np.prod(shp))].view(shp))
         din = eng.input_grad(ws) * dloss if ctx.needs_input_grad[2] else None
-        return (None, None, din, None, None, None, None, None) + tuple(grads)
+        return (None, None, din, None, None, None, None, None, None) + tuple(grads)
 
 
 def _params(net):
@@ -117,7 +124,7 @@ def _params(net):
     return [p for _, p in net._named_ref_params()] if hasattr(net, "_named_ref_params") else list(net.parameters())
 
 
-def nll_loss(net, x, target, classes=None, stages=None, windows=None, window_pos=None):
+def nll_loss(net, x, target, classes=None, stages=None, windows=None, window_pos=None, phase_pos=None):
     """Mean negative log-likelihood (nats per sample) of `target` (B, W) or (B W,) int64 under the per-timestep softmax of
     net's logits for the one-hot x (B, Q, T): a 0-d tensor whose backward() gives the parameter gradients (and the input's, when it
     requires grad).  A target outside [0, Q) makes the loss NaN.  classes: one integer per clip for a model with global class
@@ -125,23 +132,24 @@ def nll_loss(net, x, target, classes=None, stages=None, windows=None, window_pos
     forward takes them (None: all stages - this function draws nothing).  windows: 1..16 (lo, hi) pairs (None: the engine's
     nll_windows) - the softmax of column c of clip b is taken inside the pair of stream position window_pos[b] + c; window_pos: None
     (0), an int, or one per clip (a sequence, or an int64 device tensor: no host synchronisation).  A target outside its window makes
-    the loss NaN."""
-    out = _NLLFunction.apply(net, torch.is_grad_enabled(), x, target, classes, stages, windows, window_pos, *_params(net))
+    the loss NaN.  phase_pos: the stream position of every clip's first target for a phase-conditioned WaveNet (required there,
+    refused elsewhere): one int, one per clip, or an int64 device tensor."""
+    out = _NLLFunction.apply(net, torch.is_grad_enabled(), x, target, classes, stages, windows, window_pos, phase_pos, *_params(net))
     if isinstance(out, tuple):                                  # a vq autoencoder: the caller adds net.vq_loss
         out, net.vq_loss = out
     return out
 
 
-def step_probs(net, x, classes=None, windows=None, window_pos=None):
+def step_probs(net, x, classes=None, windows=None, window_pos=None, phase_pos=None):
     """(B W, Q) probabilities: row b W + w is softmax over the Q logits of output column w of clip b - what the decoder samples
     from (the module's own forward returns the reference's chunk softmax instead).  windows / window_pos (nll_loss): the
-    distribution a windowed decode draws from, an exact 0 outside the column's window."""
+    distribution a windowed decode draws from, an exact 0 outside the column's window.  phase_pos: nll_loss's."""
     with torch.no_grad():
-        eng, ws = _forward_logits(net, x, classes)
+        eng, ws = _forward_logits(net, x, classes, phase_pos=phase_pos)
         return eng.step_probs(ws, windows=windows, window_pos=window_pos)
 
 
-def guided_probs(net, x, classes, guidance, windows=None, window_pos=None):
+def guided_probs(net, x, classes, guidance, windows=None, window_pos=None, phase_pos=None):
     """(B W, Q) float64: the teacher-forced distribution a classifier-free-guided decode draws sample w of clip b from
     (include/wavenet_hip.h, wn_cfg_decode_batch) - the forward the decoder is held to.  Two ``step_probs`` forwards, as `classes`
     (p_c) and with every clip as the model's ``null_class`` (p_u); the guided logits l_c + (s - 1)(l_c - l_u) differ from
@@ -152,8 +160,8 @@ def guided_probs(net, x, classes, guidance, windows=None, window_pos=None):
     if null is None:
         raise ValueError('music_amd.objective.guided_probs: the model needs "null_class" (the class that stands for "no class")')
     B = x.size(0)
-    pc = step_probs(net, x, classes=classes, windows=windows, window_pos=window_pos).double()
-    pu = step_probs(net, x, classes=[int(null)] * B, windows=windows, window_pos=window_pos).double()
+    pc = step_probs(net, x, classes=classes, windows=windows, window_pos=window_pos, phase_pos=phase_pos).double()
+    pu = step_probs(net, x, classes=[int(null)] * B, windows=windows, window_pos=window_pos, phase_pos=phase_pos).double()
     s = torch.as_tensor(guidance, dtype=torch.float64).reshape(-1)
     if s.numel() not in (1, B) or not bool(torch.isfinite(s).all()):
         raise ValueError("music_amd.objective.guided_probs: guidance must be a finite number or one per clip (%d)" % B)
@@ -166,7 +174,7 @@ def guided_probs(net, x, classes, guidance, windows=None, window_pos=None):
     return e / e.sum(1, keepdim=True)
 
 
-def score(net, x_or_codes, target, scrambled=False, classes=None, stages=None, windows=None, window_pos=None):
+def score(net, x_or_codes, target, scrambled=False, classes=None, stages=None, windows=None, window_pos=None, phase_pos=None):
     """Held-out figures of net on one batch, forward only.  x_or_codes: the one-hot (B, Q, T) float, or the integer codes (B, T) -
     then the one-hot is laid out canonical, or as the loader scrambles it with `scrambled`.  Returns device tensors of
     shape (B,), float64: "nll" (mean nats per sample of each clip), "bits" (nll / ln 2) and "accuracy" (share of samples whose
@@ -178,7 +186,7 @@ def score(net, x_or_codes, target, scrambled=False, classes=None, stages=None, w
         if x.dim() == 2:
             q = getattr(net, "quantization_channels", None) or net.quantization_channel
             x = faster_audio_data.onehot_device(x, q, scrambled)
-        eng, ws = _forward_logits(net, x, classes, stages)
+        eng, ws = _forward_logits(net, x, classes, stages, phase_pos)
         row_nll, row_hit = eng.score_logits(ws, _flat_target(target, ws), windows=windows, window_pos=window_pos)
         B, W = ws["B"], ws["W"]
         nll = row_nll.view(B, W).double().mean(1)
@@ -257,6 +265,8 @@ class Validation:
                 kw = {"classes": batch["audio_class"]} if "audio_class" in batch else {}       # (global class conditioning)
                 if self.windows is not None:
                     kw.update(windows=self.windows, window_pos=batch["audio_pos"])
+                if getattr(net, "phase_period", 0):                                            # (a phase-conditioned prior)
+                    kw.update(phase_pos=batch["audio_pos"])
                 r = score(net, batch["audio_piece"], batch["audio_target"], **kw)
                 part = torch.stack([r["nll"].sum(), r["bits"].sum(), r["accuracy"].sum()])
                 total = part if total is None else total + part

@@ -394,6 +394,13 @@ def train():
                 and not train_params.get("valid_labels_path"):
             raise ValueError('train_params.json: validating a model with "global_classes" needs "valid_labels_path", the classes of the '
                              'items of "valid_audio_path"')
+    # "phase_period": P in the model's JSON: a phase-conditioned WaveNet, a prior over a frame-major code stream of P stages.  Every
+    # clip's stream position comes from the loader's "audio_pos", so the dataset must hand the positions out - refused here, at start,
+    # the way "nll_windows" without them is
+    phase_period = getattr(net, "phase_period", 0)
+    if phase_period and not dataset_params.get("token_positions"):
+        raise ValueError('the model\'s parameters set "phase_period": %d, which needs "token_positions": true in dataset_params.json (the '
+                         'stream position of every clip)' % phase_period)
     # "null_class" in the model's JSON + "class_dropout": p (and "class_dropout_seed") here: classifier-free guidance training - each
     # step a clip's class becomes null_class with probability p (music_amd/class_dropout.py: a counter hash of the global step and the
     # clip's index in the global batch).  No clip may carry null_class as its label; validation scores the true labels.
@@ -487,7 +494,9 @@ def train():
                 target = target.view(-1)
             win_kw = {} if nll_windows is None else {"windows": nll_windows, "window_pos": sampled_batch.get("audio_pos")}     # (absent on an empty shard)
             cls_kw = {"classes": sampled_batch["audio_class"]} if n_global and "audio_class" in sampled_batch else {}
-            if class_drop is not None and cls_kw:
+            if phase_period and piece is not None:        # (a phase-conditioned prior: the clips' stream positions)
+                cls_kw["phase_pos"] = sampled_batch["audio_pos"]
+            if class_drop is not None and "classes" in cls_kw:
                 cls_kw["classes"] = class_dropout.apply(cls_kw["classes"], null_class, class_drop[1], num_trained,
                                                         int(sampled_batch.get("first_clip", 0)), class_drop[0])
             loss = torch.zeros((), device=device)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of single kernels of the hot path at BASELINE config-2 shapes (GPU only).
 
-    python tools/kbench.py [fwd|bwd|epi|dx|skip|decode|ae|guard|ema|nll|win_nll|cond|vq|vq_ema|gcond|gclass|rvq|all] [--reps N] [--precision f16x3,bf16x3]
+    python tools/kbench.py [fwd|bwd|epi|dx|skip|decode|ae|guard|ema|nll|win_nll|cond|vq|vq_ema|gcond|gclass|phase|rvq|all] [--reps N] [--precision f16x3,bf16x3]
 
 Prints per-phase / per-layer kernel times measured with HIP events on the launch stream.
 """
@@ -690,6 +690,103 @@ def gclass_bench(reps, alternations=6, E=64, n_cls=8):
     print(json.dumps(res))
 
 
+def phase_bench(reps, alternations=6, P=4):
+    """`phase`: the phase-conditioned WaveNet.  (a) wn_phase_tab_fwd / wn_phase_tab_bwd alone at a prior's shape (8 clips, 30 blocks,
+    64 / 256 channels, P = 4; the forward with one and with both table layouts, the backward without and with the frame sums), HIP
+    events around max(reps, 100) calls; (b) the fused step (forward, loss, backward, flat Adam) with phase_period = 4 against the plain
+    model at a prior's 8 x 512 x 4096 (the general plan) and at config 2's shape (the fast plan: the conditioned one runs the
+    three-launch forward epilogue); everything alternated `alternations` times on one device, medians and spreads (largest -
+    smallest).  Written to profiles/phase_kbench.json."""
+    import time
+    from music_amd import _lib
+    from music_amd._lib import call, ptr
+    from music_amd.faster_audio_data import onehot_device
+    from music_amd.model import wavenet
+    st = _lib.stream()
+    res = {"alternations": alternations, "P": P}
+    rng = np.random.default_rng(0)
+    N, D, CH, S, B = len(CFG["dilations"]), 64, 64, 256, 8
+    n = (N * 2 * D + S) * P
+    flat, grad = torch.randn(n, device="cuda") * 0.1, torch.empty(n, device="cuda")
+    offs = (0, 2 * D * P, N * 2 * D * P)
+    tab, tabp, enf = torch.randn(N, B, 2 * CH, P, device="cuda"), torch.randn(N, B // 2, 4 * CH, P, device="cuda"), torch.randn(B, S, P, device="cuda")
+    s_tab, s_enf = torch.empty(N, B, 2 * CH, device="cuda"), torch.empty(B, S, device="cuda")
+    pos = torch.from_numpy(rng.integers(0, 1 << 40, size=B).astype(np.int64)).cuda()
+    rot = torch.from_numpy(rng.integers(0, P, size=N + 1).astype(np.int32)).cuda()
+    dims = (N, D, CH, S, P, B)
+    head = (ptr(flat),) + offs + (ptr(pos), ptr(rot))
+    legs = {"phase_tab_fwd": lambda: call("wn_phase_tab_fwd", *head, None, None, None, ptr(tab), None, ptr(enf), *dims, st),
+            "phase_tab_fwd_both_tables": lambda: call("wn_phase_tab_fwd", *head, None, None, None, ptr(tab), ptr(tabp), ptr(enf), *dims, st),
+            "phase_tab_fwd_class_addends": lambda: call("wn_phase_tab_fwd", *head, ptr(s_tab), None, ptr(s_enf), ptr(tab), None, ptr(enf), *dims, st),
+            "phase_tab_bwd": lambda: call("wn_phase_tab_bwd", ptr(tab), 0, ptr(enf), ptr(grad), *offs, ptr(pos), ptr(rot), None, None, *dims, st),
+            "phase_tab_bwd_frame_sums": lambda: call("wn_phase_tab_bwd", ptr(tab), 0, ptr(enf), ptr(grad), *offs, ptr(pos), ptr(rot), ptr(s_tab),
+                                                     ptr(s_enf), *dims, st)}
+    s_tab.normal_()
+    s_enf.normal_()
+    res["shape_kernels"] = dict(N=N, D=D, CH=CH, S=S, B=B, P=P)
+
+    def launches(fn, k):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        torch.cuda.synchronize()
+        ev[0].record()
+        for _ in range(k):
+            fn()
+        ev[1].record()
+        torch.cuda.synchronize()
+        return ev[0].elapsed_time(ev[1]) / k * 1e3
+    times = {key: [] for key in legs}
+    for fn in legs.values():
+        launches(fn, 20)                                                      # warm
+    for _ in range(alternations):
+        for key, fn in legs.items():
+            times[key].append(launches(fn, max(reps, 100)))
+    for leg, v in times.items():
+        res["wn_%s_us" % leg], res["wn_%s_us_spread" % leg] = _median_spread(v)
+    # ---- the fused step, phase-conditioned against plain
+    shapes = {"prior_8x512x4096": (dict(CFG, quantization_channels=512), 8, 4096), "config2": (dict(CFG), B_LOCAL, T)}
+    for tag, (cfg, Bs, Ts) in shapes.items():
+        Q = cfg["quantization_channels"]
+        codes = torch.from_numpy(rng.integers(0, Q, size=(Bs, Ts)).astype(np.int32)).cuda()
+        x = onehot_device(codes, Q, True)
+        engs = {}
+        for mode, kw in (("plain", {}), ("phase", dict(phase_period=P))):
+            torch.manual_seed(0)
+            net = wavenet(**dict(cfg, **kw)).cuda()
+            eng = net._engine_for(torch.device("cuda", 0))
+            eng.adam_init(lr=1e-4)
+            engs[mode] = eng
+        W = Ts - engs["plain"].rf + 1
+        target = torch.from_numpy(rng.integers(0, Q, size=(Bs * W,)).astype(np.int64)).cuda()
+        ppos = torch.from_numpy(rng.integers(0, 1 << 20, size=Bs).astype(np.int64)).cuda()       # on the device, as the loader hands them on
+
+        def steps(mode, k):
+            eng = engs[mode]
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(k):
+                loss = eng.loss_and_grad(x, target, **({"phase_pos": ppos} if mode == "phase" else {}))
+                eng.adam_step()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) / k * 1e3, float(loss)
+        for mode in engs:
+            steps(mode, 5)
+        step_ms = {m: [] for m in engs}
+        for _ in range(alternations):
+            for mode in engs:
+                ms, loss = steps(mode, max(reps, 20))
+                step_ms[mode].append(ms)
+                res["%s_fused_step_loss_%s" % (tag, mode)] = round(loss, 5)
+        for mode, v in step_ms.items():
+            res["%s_fused_step_ms_%s" % (tag, mode)], res["%s_fused_step_ms_%s_spread" % (tag, mode)] = _median_spread(v)
+        res["%s_fused_step_ms_phase_minus_plain" % tag] = round(res["%s_fused_step_ms_phase" % tag] - res["%s_fused_step_ms_plain" % tag], 3)
+        res["%s_fused_step_ms_by_alternation" % tag] = {m: [round(t, 3) for t in v] for m, v in step_ms.items()}
+        res["shape_" + tag] = dict(B=Bs, T=Ts, Q=Q, engine=type(engs["phase"]).__name__, P=P)
+        del engs, x, target
+        torch.cuda.empty_cache()
+    _write_profile("phase_kbench.json", res)
+    print(json.dumps(res))
+
+
 def win_nll_bench(reps, alternations=6):
     """`win_nll`: the windowed objective's launch (wn_win_step_nll) against the plain one (wn_step_nll, the yardstick: the kernel from
     before the windows, measured in the same run) on random logits, with dx and forward-only (row_nll + row_hit), at config 2's shape
@@ -756,7 +853,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--precision", default="f16x3,bf16x3")
     ap.add_argument("--overlap", type=int, default=1)
-    ap.add_argument("--parent", default=None, help="gcond / gclass / rvq / rvq_drop / win_nll: a built checkout of the parent commit, for profiles/<what>_bench_unset.json")
+    ap.add_argument("--parent", default=None, help="gcond / gclass / phase / rvq / rvq_drop / win_nll: a built checkout of the parent commit, for profiles/<what>_bench_unset.json")
     args = ap.parse_args()
     if args.what == "gcond":
         if args.parent:
@@ -766,6 +863,10 @@ def main():
         if args.parent:
             bench_unset(os.path.abspath(args.parent), profile="gclass_bench_unset.json", keys="global_classes / global_channels of wavenet")
         return gclass_bench(args.reps)
+    if args.what == "phase":
+        if args.parent:
+            bench_unset(os.path.abspath(args.parent), profile="phase_bench_unset.json", keys="phase_period of wavenet")
+        return phase_bench(args.reps)
     if args.what == "rvq":
         if args.parent:
             bench_unset(os.path.abspath(args.parent), profile="rvq_bench_unset.json", keys="vq_stages")

@@ -27,6 +27,12 @@ position are taken over its stage's K tokens only; the loss starts at ln K, not 
 frame boundary, so position 0 of an item is stage 0 - what the loader's 'audio_pos' counts from; sampling with sample_code_stream is
 unchanged.
 
+--layout phase writes the K-ary stream instead: the same frame-major order, every token the CODE itself, so the prior's alphabet
+stays K whatever S is, and the refusal becomes K > 1024.  Such a stream is for a phase-conditioned prior - `wavenet(...,
+quantization_channels=K, phase_period=S)` with `"token_positions": true` in dataset_params.json - which is told the stage of a
+position, p mod S, as conditioning (music_amd/model.py); split_code_stream / join_code_stream take `layout="phase"` for it, and
+sample_code_stream / prior_score detect such a prior.  --labels is unchanged.
+
 --labels (the source corpus' "labels_path": a JSON list of integers, one per piece of --audio) with --labels-out writes the labels
 of the token pickle's items - every item the label of the piece it was encoded from, the pieces --drop-empty leaves out left out
 here too - as the "labels_path" of a class-conditional prior (`wavenet(..., global_classes=n, global_channels=E)`)."""
@@ -42,17 +48,17 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
 
-def encode_pieces(net, pieces, frames=32, batch=8, one_hot="scrambled"):
+def encode_pieces(net, pieces, frames=32, batch=8, one_hot="scrambled", layout="interleaved"):
     """pieces: list of 1-D integer arrays of mu-law codes -> list of 1-D int32 arrays, the bottleneck codes of every piece (one
     array per piece, empty where a piece pools to no frame).  `one_hot`: the layout the autoencoder was trained on (the loader's
-    default is "scrambled")."""
+    default is "scrambled").  `layout`: "interleaved" (token = s * K + code) or "phase" (token = code)."""
     from music_amd import faster_audio_data
     from music_amd.ae_generate import encode_codes
     if one_hot not in ("scrambled", "canonical"):
         raise ValueError('one_hot must be "scrambled" or "canonical", not %r' % (one_hot,))
     Q, rf, pool = net.quantization_channel, net.receptive_field, net.en_pool_kernel_size
     S, K = getattr(net, "vq_stages", 1), net.vq_num_codes
-    check_alphabet(S, K)
+    check_alphabet(S, K, layout)
     dev = next(net.parameters()).device
     out = []
     for piece in pieces:
@@ -74,7 +80,7 @@ def encode_pieces(net, pieces, frames=32, batch=8, one_hot="scrambled"):
             got = encode_codes(net, x).cpu().numpy().astype(np.int32).reshape(len(group), S, -1)
             assert got.shape == (len(group), S, nf)
             for row, f0 in zip(got, group):
-                codes[f0:f0 + nf] = row.T + np.arange(S, dtype=np.int32) * K
+                codes[f0:f0 + nf] = row.T + (np.arange(S, dtype=np.int32) * K if layout == "interleaved" else 0)
         out.append(codes.reshape(-1))
     return out
 
@@ -91,13 +97,21 @@ def item_labels(labels, codes, drop_empty=False):
     return [int(v) for v, c in zip(labels, codes) if not drop_empty or np.asarray(c).size]
 
 
-def check_alphabet(stages, K):
-    """The prior's alphabet is stages * K tokens; the decoder's samplers take at most 1024."""
+def check_alphabet(stages, K, layout="interleaved"):
+    """The prior's alphabet is stages * K tokens (layout "phase": K, the stage being conditioning); the decoder's samplers take at
+    most 1024."""
     from music_amd import _lib
+    if layout not in ("interleaved", "phase"):
+        raise ValueError('layout must be "interleaved" or "phase", not %r' % (layout,))
+    if layout == "phase":
+        if K > _lib.VQ_MAX_CODES:
+            raise ValueError('"vq_codes" = %d: a prior over the code stream would need more than the %d classes the decoder\'s samplers '
+                             "take - use a smaller codebook" % (K, _lib.VQ_MAX_CODES))
+        return
     if stages * K > _lib.VQ_MAX_CODES:
         raise ValueError('"vq_stages" x "vq_codes" = %d x %d = %d tokens: a prior over the interleaved stream would need more than the '
-                         "%d classes the decoder's samplers take - use fewer stages or a smaller codebook"
-                         % (stages, K, stages * K, _lib.VQ_MAX_CODES))
+                         "%d classes the decoder's samplers take - use fewer stages, a smaller codebook, or --layout phase (a "
+                         "phase-conditioned prior over the K-ary stream)" % (stages, K, stages * K, _lib.VQ_MAX_CODES))
 
 
 def load_vq_model(model_params, checkpoint, use_ema=True):
@@ -126,6 +140,8 @@ def main(argv=None):
     ap.add_argument("--one-hot", default="scrambled", choices=("scrambled", "canonical"))
     ap.add_argument("--no-ema", action="store_true")
     ap.add_argument("--drop-empty", action="store_true")
+    ap.add_argument("--layout", default="interleaved", choices=("interleaved", "phase"),
+                    help="interleaved: token = stage * K + code (alphabet S K); phase: token = code (alphabet K, for a prior with phase_period = S)")
     ap.add_argument("--labels", help='the "labels_path" of --audio: a JSON list of integers, one per piece')
     ap.add_argument("--labels-out", help="where the labels of the items of --out go (needs --labels)")
     args = ap.parse_args(argv)
@@ -135,7 +151,7 @@ def main(argv=None):
         net, read = load_vq_model(json.load(f), args.checkpoint, not args.no_ema)
     with open(args.audio, "rb") as f:
         pieces = pickle.load(f)
-    codes = encode_pieces(net, pieces, args.frames, args.batch, args.one_hot)
+    codes = encode_pieces(net, pieces, args.frames, args.batch, args.one_hot, args.layout)
     if args.labels:
         with open(args.labels) as f:
             out_labels = item_labels(json.load(f), codes, args.drop_empty)
