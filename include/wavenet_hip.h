@@ -452,6 +452,35 @@ int wn_win_step_softmax(const float* x, int64_t x_bstride, int x_pitch, float* p
 int wn_win_step_nll(const float* x, int64_t x_bstride, int x_pitch, const int64_t* target, float* dx, int64_t dx_bstride, int dx_pitch,
                     float* probs, float* row_nll, int32_t* row_hit, float* loss_part, int w, int q, int batch, float inv_n,
                     const int32_t* win_host, int win_period, const int64_t* win_pos, int64_t win_pos0, wn_stream_t stream);
+/* The MASKED, WEIGHTED and SMOOTHED objective (ABI 9 still: a new entry only): wn_win_step_nll without inv_n, as a weighted mean over
+ * the columns that carry a target - the objective's side of "an absent token contributes nothing" (wn_onehot, the partially forced
+ * decode).  Layout, the NULL-able outputs, loss_part and the windows (win_period == 0: none, rows [0, q)) are wn_win_step_nll's.
+ *   weight: DEVICE, [batch * w] floats, or NULL for ones.  ignore_index: a target value that marks an absent column.  smoothing: the
+ *   label smoothing e in [0, 1).  den: DEVICE, 2 floats, written by the call.
+ * Column col = b * w + c, its window [lo, hi) of n = hi - lo rows, y = target[col]:
+ *   W = 0 if y == ignore_index, else weight ? weight[col] : 1.
+ *   den[0] = sum of W over all columns, accumulated in double in a fixed order by a launch of its own in front of the main kernel on
+ *     `stream` (no host read-back); den[1] = (float)(1.0 / that sum), or 0 for a sum of 0.  A counted weight that is negative or not
+ *     finite makes both NaN, and with them the loss and the dx of every counted column; it cannot be refused before the launch.
+ *   W == 0 exactly: the column is SKIPPED by a predicate, not by a multiply.  Its target is compared with ignore_index and otherwise
+ *     has no effect (garbage is fine); its logits reach no arithmetic that leaves the column - NaN, +-inf or 1e30 there change no
+ *     output bit elsewhere; its dx is an exact +0.0 in all q rows, its row_nll 0.0, its row_hit 0.  probs is still its softmax.
+ *   W != 0, with m, S, p_k as in wn_win_step_nll:
+ *     l = log S + m - (1 - e) x_y - (e / n) sum_{k in [lo, hi)} x_k
+ *     dx = (W den[1]) (p_k - (1 - e) [k == y] - e / n) inside the window, +0.0 outside
+ *     loss_part sums to den[1] * sum of W l;  row_nll is the UNSMOOTHED log S + m - x_y, row_hit as before.
+ *     A target outside [0, q) or outside its window poisons the column, a negative win_pos[b] its clip, as in wn_win_step_nll.
+ *   smoothing == 0 is a bypass: the sum of x_k is not formed (a -inf logit inside a window gives no 0 * inf).
+ *   Every column skipped: the loss is 0, every dx +0.0, den = {0, 0}.
+ *   weight == NULL, no target equal to ignore_index, smoothing == 0: every output equals wn_win_step_nll with
+ *     inv_n = (float)(1.0 / (double)(batch * w)) bit for bit (with win_period == 0: wn_step_nll).
+ * No float atomics, the same bits at every launch; legal under stream capture, allocates and retains nothing.  batch == 0 or w == 0:
+ * returns 0 and zeroes loss_part and den where given.  -4, entry and argument named in wn_last_error: everything wn_win_step_nll
+ * refuses; smoothing NaN, < 0 or >= 1; with work to do, a NULL den. */
+int wn_wstep_nll(const float* x, int64_t x_bstride, int x_pitch, const int64_t* target, float* dx, int64_t dx_bstride, int dx_pitch,
+                 float* probs, float* row_nll, int32_t* row_hit, float* loss_part, int w, int q, int batch, const int32_t* win_host,
+                 int win_period, const int64_t* win_pos, int64_t win_pos0, const float* weight, int64_t ignore_index, float smoothing,
+                 float* den, wn_stream_t stream);
 /* ---- LEARNED conditioning projections of the autoencoder: the N + 1 1x1 convs of the pooled encoding enc [batch][bw][le]
  * (wavenet_autoencoder/model1.py:178-179, 216-217 draws them afresh per forward; here they are parameters), read from and
  * differentiated into the flat buffers.  Offsets count floats from `flat` (and from `flat_grad`): stage i < n_stages has its weight

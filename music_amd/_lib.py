@@ -99,6 +99,8 @@ SIGNATURES = {
     # the windowed objective: the two entries above with the host window table, its period, per-clip device positions, the first position
     "wn_win_step_softmax": [_p, _l, _i, _p, _i, _i, _i, _p, _i, _p, _l, _p],
     "wn_win_step_nll": [_p, _l, _i, _p, _p, _l, _i, _p, _p, _p, _p, _i, _i, _i, _f, _p, _i, _p, _l, _p],
+    # the masked / weighted / smoothed objective: wn_win_step_nll without inv_n, then weight, ignore_index, smoothing, den
+    "wn_wstep_nll": [_p, _l, _i, _p, _p, _l, _i, _p, _p, _p, _p, _i, _i, _i, _p, _i, _p, _l, _p, _l, _f, _p, _p],
     "wn_cond_proj_fwd": [_p, _p, _l, _l, _l, _l, _l, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
     "wn_cond_proj_bwd": [_p, _i, _p, _p, _p, _l, _l, _l, _l, _l, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
     "wn_gcond_proj_fwd": [_p, _p, _l, _l, _l, _l, _l, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _l, _l, _l, _l, _i, _i, _p],

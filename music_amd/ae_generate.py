@@ -538,12 +538,14 @@ def sample_code_stream(prior, stages, K, frames, start_tokens, start_pos=0, temp
     return split_code_stream(tokens, stages, K, "phase" if phase else "interleaved")
 
 
-def prior_score(prior, tokens, stages, K, start_pos=0, classes=None):
+def prior_score(prior, tokens, stages, K, start_pos=0, classes=None, weights=None, ignore_index=None, label_smoothing=0.0):
     """Held-out figures of a prior on token streams ``tokens`` (U, n > receptive_field) whose first token sits at stream position
     ``start_pos``, under the windows ``sample_code_stream`` draws with: ``objective.score`` of every token behind the first
     receptive_field ones - per-stream "nll", "bits" (per token, of the distribution that is sampled) and "accuracy".  ``classes``: one
     class per stream for a class-conditional prior.  A phase-conditioned prior (``sample_code_stream``) is scored without windows,
-    under ``phase_pos = start_pos + receptive_field``."""
+    under ``phase_pos = start_pos + receptive_field``.  ``weights`` ((U, n - receptive_field), one per scored token) /
+    ``ignore_index`` / ``label_smoothing``: ``objective.score``'s - the figures become weighted means over the tokens that count (a
+    dropped stage's -1 under ``ignore_index=-1`` does not), with "tokens", their sum of weights per stream."""
     try:
         from . import fast_generate as fg, objective
     except ImportError:
@@ -555,9 +557,11 @@ def prior_score(prior, tokens, stages, K, start_pos=0, classes=None):
     t = t.to(next(prior.parameters()).device)
     if int(start_pos) < 0:
         raise ValueError("prior_score: start_pos must be >= 0")
+    wnll = dict(weights=weights, ignore_index=ignore_index, label_smoothing=label_smoothing)
     if _phase_prior(prior, int(stages), int(K), "prior_score"):
-        return objective.score(prior, t[:, :-1].to(torch.int32), t[:, rf:].to(torch.int64), classes=classes, phase_pos=int(start_pos) + rf)
-    return objective.score(prior, t[:, :-1].to(torch.int32), t[:, rf:].to(torch.int64), classes=classes,
+        return objective.score(prior, t[:, :-1].to(torch.int32), t[:, rf:].to(torch.int64), classes=classes, phase_pos=int(start_pos) + rf,
+                               **wnll)
+    return objective.score(prior, t[:, :-1].to(torch.int32), t[:, rf:].to(torch.int64), classes=classes, **wnll,
                            windows=fg.stage_windows(int(stages), int(K)), window_pos=int(start_pos) + rf)
 
 

@@ -300,7 +300,10 @@ class GenericAutoencoderEngine(GeneralPlan):
         ps.reduce_grads()
 
     # ------------------------------------------------------------------ fused training step (wavenet_autoencoder/train.py:146-160)
-    def loss_and_grad(self, x, target, cond=None, objective=None, classes=None, stages=None, windows=None, window_pos=None):
-        """objective: None = self.objective (EngineBase); stages: as in forward; windows / window_pos: step_nll's (the shared base)"""
+    def loss_and_grad(self, x, target, cond=None, objective=None, classes=None, stages=None, windows=None, window_pos=None,
+                      weights=None, ignore_index=None, label_smoothing=0.0):
+        """objective: None = self.objective (EngineBase); stages: as in forward; windows / window_pos, weights / ignore_index /
+        label_smoothing: step_nll's (the shared base)"""
         return self._throttled(lambda: self._fused_tail(self.forward(x, cond, want_probs=False, classes=classes, stages=stages)[2], target,
-                                                       objective=objective, windows=windows, window_pos=window_pos))
+                                                       objective=objective, windows=windows, window_pos=window_pos,
+                                                       weights=weights, ignore_index=ignore_index, label_smoothing=label_smoothing))

@@ -197,6 +197,7 @@ def train():
         raise ValueError("Cuda is not avalable,", " can not train model using multi-gpu.")
     # optional keys "objective", "valid_audio_path", "validate_every": as in music_amd/train.py (music_amd/objective.py)
     objective = wobjective.objective_option(train_params)
+    wnll = wobjective.wnll_option(train_params, dataset_params)       # "ignore_token", "label_smoothing", "nll_stage_weights": likewise
     n_global = getattr(net, "global_classes", 0)
     if n_global and not dataset_params.get("labels_path"):
         raise ValueError('model_params.json sets "global_classes": %d, so dataset_params.json must name the clips\' classes with '
@@ -278,6 +279,8 @@ def train():
             dp_scale = float(sampled_batch.get("dp_scale", 1.0))      # ragged last batch, see faster_audio_data._Collate
             if piece is not None:
                 target = target.view(-1)
+                if wnll is not None:                          # (keys of objective "nll" alone: refused at start otherwise)
+                    kw.update(wobjective.wnll_kwargs(wnll, sampled_batch, target.numel() // piece.shape[0], device))
             if vq_init_pending and piece is not None:
                 # the codebook starts as K frames of the first batch's encoding in front of the quantiser (every replica from the
                 # same frames: rank 0's, broadcast)

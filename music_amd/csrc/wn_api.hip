@@ -457,12 +457,12 @@ int wn_step_softmax(const float* x, int64_t x_bstride, int x_pitch, float* probs
     if (batch == 0 || w == 0) return 0;
     WN_REQUIRE("wn_step_softmax", probs);
     return wn_launch_step_nll(x, (long)x_bstride, x_pitch, nullptr, nullptr, 0, 0, probs, nullptr, nullptr, nullptr, w, q, batch, 0.f,
-                              nullptr, (hipStream_t)stream);
+                              nullptr, nullptr, (hipStream_t)stream);
 }
-// wn_step_nll's refusals and launch under the entry's name `fn`; win NULL: no windows
+// wn_step_nll's refusals and launch under the entry's name `fn`; win NULL: no windows; wt NULL: no weights (else inv_n is unused)
 static int step_nll_checked(const char* fn, const float* x, int64_t x_bstride, int x_pitch, const int64_t* target, float* dx,
                             int64_t dx_bstride, int dx_pitch, float* probs, float* row_nll, int32_t* row_hit, float* loss_part, int w,
-                            int q, int batch, float inv_n, const WnNllWin* win, wn_stream_t stream) {
+                            int q, int batch, float inv_n, const WnNllWin* win, const WnNllWt* wt, wn_stream_t stream) {
     char msg[160];
     if (dx && dx_pitch < w) {
         snprintf(msg, sizeof(msg), "%s: argument 'dx_pitch' must be >= w", fn);
@@ -474,14 +474,14 @@ static int step_nll_checked(const char* fn, const float* x, int64_t x_bstride, i
     }
     if (batch > 0 && w > 0) WN_REQUIRE(fn, target, loss_part);
     return wn_launch_step_nll(x, (long)x_bstride, x_pitch, target, dx, (long)dx_bstride, dx_pitch, probs, row_nll, row_hit, loss_part, w, q,
-                              batch, inv_n, win, (hipStream_t)stream);
+                              batch, inv_n, win, wt, (hipStream_t)stream);
 }
 int wn_step_nll(const float* x, int64_t x_bstride, int x_pitch, const int64_t* target, float* dx, int64_t dx_bstride, int dx_pitch,
                 float* probs, float* row_nll, int32_t* row_hit, float* loss_part, int w, int q, int batch, float inv_n,
                 wn_stream_t stream) {
     if (int rc = step_checked("wn_step_nll", x, x_bstride, x_pitch, w, q, batch)) return rc;
     return step_nll_checked("wn_step_nll", x, x_bstride, x_pitch, target, dx, dx_bstride, dx_pitch, probs, row_nll, row_hit, loss_part, w,
-                            q, batch, inv_n, nullptr, stream);
+                            q, batch, inv_n, nullptr, nullptr, stream);
 }
 // the objective's window table (the samplers' checks, win_checked) in its kernel-argument form; q is in range here
 static int nll_win_checked(const char* fn, const int32_t* win_host, int win_period, const int64_t* win_pos, int64_t win_pos0, int q,
@@ -503,7 +503,7 @@ int wn_win_step_softmax(const float* x, int64_t x_bstride, int x_pitch, float* p
     if (batch == 0 || w == 0) return 0;
     WN_REQUIRE(fn, probs);
     return wn_launch_step_nll(x, (long)x_bstride, x_pitch, nullptr, nullptr, 0, 0, probs, nullptr, nullptr, nullptr, w, q, batch, 0.f,
-                              &win, (hipStream_t)stream);
+                              &win, nullptr, (hipStream_t)stream);
 }
 int wn_win_step_nll(const float* x, int64_t x_bstride, int x_pitch, const int64_t* target, float* dx, int64_t dx_bstride, int dx_pitch,
                     float* probs, float* row_nll, int32_t* row_hit, float* loss_part, int w, int q, int batch, float inv_n,
@@ -513,7 +513,21 @@ int wn_win_step_nll(const float* x, int64_t x_bstride, int x_pitch, const int64_
     WnNllWin win;
     if (int rc = nll_win_checked(fn, win_host, win_period, win_pos, win_pos0, q, win)) return rc;
     return step_nll_checked(fn, x, x_bstride, x_pitch, target, dx, dx_bstride, dx_pitch, probs, row_nll, row_hit, loss_part, w, q, batch,
-                            inv_n, &win, stream);
+                            inv_n, &win, nullptr, stream);
+}
+int wn_wstep_nll(const float* x, int64_t x_bstride, int x_pitch, const int64_t* target, float* dx, int64_t dx_bstride, int dx_pitch,
+                 float* probs, float* row_nll, int32_t* row_hit, float* loss_part, int w, int q, int batch, const int32_t* win_host,
+                 int win_period, const int64_t* win_pos, int64_t win_pos0, const float* weight, int64_t ignore_index, float smoothing,
+                 float* den, wn_stream_t stream) {
+    const char* fn = "wn_wstep_nll";
+    if (int rc = step_checked(fn, x, x_bstride, x_pitch, w, q, batch)) return rc;
+    WnNllWin win;
+    if (int rc = nll_win_checked(fn, win_host, win_period, win_pos, win_pos0, q, win)) return rc;
+    if (!(smoothing >= 0.f && smoothing < 1.f)) return wn_set_error_msg(-4, "wn_wstep_nll: argument 'smoothing' must lie in [0, 1)");
+    if (batch > 0 && w > 0) WN_REQUIRE(fn, den);
+    const WnNllWt wt = {weight, ignore_index, smoothing, den};
+    return step_nll_checked(fn, x, x_bstride, x_pitch, target, dx, dx_bstride, dx_pitch, probs, row_nll, row_hit, loss_part, w, q, batch,
+                            0.f, &win, &wt, stream);
 }
 // ---- learned conditioning projections (wn_condproj.hip) ----
 // the refusals both entries share: shapes, offsets and strides first (they need no pointer)

@@ -317,9 +317,11 @@ int wn_launch_vq_ema_update(float* flat, long cb_off, const float* stat, float* 
 // win (NULL: none): the window table of the objective, period pairs; column c of clip b is at stream position pos0 + pos[b] + c with
 // pos0 already reduced mod period by the host, pos a DEVICE array [batch] or NULL, pow32 = 2^32 mod period
 struct WnNllWin { int period; unsigned pos0, pow32; const int64_t* pos; int lo[WN_WIN_MAX], hi[WN_WIN_MAX]; };
+// wt (NULL: none): wn_wstep_nll's per-column weights (DEVICE, or NULL for ones), ignored target, smoothing and den (DEVICE, 2 floats)
+struct WnNllWt { const float* weight; int64_t ignore; float smoothing; float* den; };
 int wn_launch_step_nll(const float* x, long x_bs, int x_pitch, const int64_t* target, float* dx, long dx_bs, int dx_pitch, float* probs,
                        float* row_nll, int32_t* row_hit, float* loss_part, int w, int q, int batch, float inv_n, const WnNllWin* win,
-                       hipStream_t st);
+                       const WnNllWt* wt, hipStream_t st);
 // general path (wn_generic.hip): gate and chunk softmax for any shape
 int wn_launch_gate_fwd(const float* fg, long fg_bstride, int dp, int rows, float* z, long z_bstride, int pitch, int t_lo, int t_hi,
                        int batch, hipStream_t st);

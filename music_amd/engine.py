@@ -470,26 +470,28 @@ class WaveNetEngine(EngineBase):
 
     # ------------------------------------------------------------------ fused training step
     def loss_and_grad_codes(self, codes, target, scrambled=True, want_probs=False, objective=None, windows=None, window_pos=None,
-                            classes=None, phase_pos=None):
+                            classes=None, phase_pos=None, weights=None, ignore_index=None, label_smoothing=0.0):
         """loss_and_grad on the integer codes themselves (int32 (B,T) on the device; `scrambled` = the loader's one-hot
         layout, faster_audio_data.py:77-81): same result as loss_and_grad(self.onehot(codes, scrambled), target), but the
         (B,256,T) float tensor is never built, written or read - the causal layer is a gather forward and
         a scatter backward."""
         return self.loss_and_grad(None, target, want_probs, codes=(codes, scrambled), objective=objective, windows=windows,
-                                  window_pos=window_pos, classes=classes, phase_pos=phase_pos)
+                                  window_pos=window_pos, classes=classes, phase_pos=phase_pos, weights=weights, ignore_index=ignore_index,
+                                  label_smoothing=label_smoothing)
 
     def loss_and_grad(self, x, target, want_probs=False, codes=None, objective=None, windows=None, window_pos=None, classes=None,
-                      phase_pos=None):
+                      phase_pos=None, weights=None, ignore_index=None, label_smoothing=0.0):
         """forward + CrossEntropyLoss(probs, target) + backward (wavenet/train.py:178-181).
         Returns the loss as a 0-d device tensor; gradients land in self.flat_grad.  objective: None = self.objective
         (EngineBase; "nll" = the negative log-likelihood under the per-timestep softmax instead of the reference's loss).  windows /
-        window_pos: the position windows of "nll" (EngineBase.step_nll; None = self.nll_windows).  classes, phase_pos: forward_logits'."""
+        window_pos: the position windows of "nll" (EngineBase.step_nll; None = self.nll_windows).  classes, phase_pos: forward_logits'.
+        weights / ignore_index / label_smoothing: step_nll's masked, weighted and smoothed "nll"."""
         def step():
             self.mark("begin")
             self.pack_weights()
             self.mark("pack")
             return self._fused_tail(self.forward_logits(x, codes=codes, classes=classes, phase_pos=phase_pos), target, want_probs, objective,
-                                    windows, window_pos)
+                                    windows, window_pos, weights=weights, ignore_index=ignore_index, label_smoothing=label_smoothing)
         return self._throttled(step)
 
     def softmax_ce(self, *args):

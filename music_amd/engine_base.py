@@ -835,16 +835,47 @@ class EngineBase:
             return None
         return windows if isinstance(windows, NllWindows) else NllWindows(windows, self.Q)
 
-    def step_nll(self, ws, target, dlogits=None, probs=None, row_nll=None, row_hit=None, windows=None, window_pos=None):
+    def _resolve_wnll(self, ws, weights=None, ignore_index=None, label_smoothing=0.0):
+        """None with all three at their defaults (today's launch), else wn_wstep_nll's tail: (weight tensor or None, ignore_index,
+        smoothing).  weights: (B, W) or (B W,) floats on the device or the host, one per target; ignore_index: the target value
+        of an absent column (None: no target is absent); label_smoothing in [0, 1)."""
+        eps = float(label_smoothing)
+        if not 0.0 <= eps < 1.0:
+            raise ValueError("music_amd: label_smoothing must lie in [0, 1), got %r" % (label_smoothing,))
+        if weights is None and ignore_index is None and eps == 0.0:
+            return None
+        if weights is not None:
+            weights = torch.as_tensor(weights).reshape(-1)
+            if weights.numel() != ws["B"] * ws["W"]:
+                raise ValueError("music_amd: %d weights for %d clips of %d targets" % (weights.numel(), ws["B"], ws["W"]))
+            if not weights.is_floating_point():
+                raise ValueError("music_amd: weights are floats, one per target, got %s" % weights.dtype)
+            weights = weights.to(device=self.device, dtype=torch.float32).contiguous()
+        # (no ignore_index: the one value no stream can hold - it lies outside [0, Q) for every Q)
+        return weights, -(1 << 63) if ignore_index is None else int(ignore_index), eps
+
+    def step_nll(self, ws, target, dlogits=None, probs=None, row_nll=None, row_hit=None, windows=None, window_pos=None, weights=None,
+                 ignore_index=None, label_smoothing=0.0):
         """wn_step_nll on the compact logits ws["O"] (pitch W, clip stride Q W): loss partials of the MEAN negative log-likelihood under
         the per-timestep softmax into ws["loss_part"]; d loss / d logits in the logits' own layout, the (B W, Q) probabilities, the
         per-column nll and hit flags where a tensor is given.  windows (None: self.nll_windows) / window_pos: the one launch is
-        wn_win_step_nll, column c of clip b scored inside the pair of stream position window_pos[b] + c (NllWindows.tail)."""
+        wn_win_step_nll, column c of clip b scored inside the pair of stream position window_pos[b] + c (NllWindows.tail).
+        weights / ignore_index / label_smoothing (_resolve_wnll), any of them set: the launch is wn_wstep_nll - the weighted mean over
+        the columns that carry a target, a column of weight 0 or with target == ignore_index skipped; ws["nll_den"] then holds the sum
+        of the weights and its reciprocal on the device."""
         B, W, Q = ws["B"], ws["W"], self.Q
         win = self._resolve_windows(windows, window_pos)
+        wt = self._resolve_wnll(ws, weights, ignore_index, label_smoothing)
         if "loss_part" not in ws:
             ws["loss_part"] = torch.zeros(_lib.CE_NUM_PARTIALS, dtype=torch.float32, device=self.device)
-        if win is None:
+        if wt is not None:
+            if "nll_den" not in ws:
+                ws["nll_den"] = torch.zeros(2, dtype=torch.float32, device=self.device)
+            ws["nll_win"], ws["nll_weight"] = win, wt[0]      # (alive as long as the workspace's last launch)
+            tail = (None, 0, None, 0) if win is None else win.tail(window_pos, B, self.device)
+            call("wn_wstep_nll", ptr(ws["O"]), Q * W, W, ptr(target), ptr(dlogits), Q * W, W, ptr(probs), ptr(row_nll), ptr(row_hit),
+                 ptr(ws["loss_part"]), W, Q, B, *tail, ptr(wt[0]), wt[1], wt[2], ptr(ws["nll_den"]), _lib.stream())
+        elif win is None:
             call("wn_step_nll", ptr(ws["O"]), Q * W, W, ptr(target), ptr(dlogits), Q * W, W, ptr(probs), ptr(row_nll), ptr(row_hit),
                  ptr(ws["loss_part"]), W, Q, B, 1.0 / (B * W), _lib.stream())
         else:
@@ -853,15 +884,17 @@ class EngineBase:
                  ptr(ws["loss_part"]), W, Q, B, 1.0 / (B * W), *win.tail(window_pos, B, self.device), _lib.stream())
         self.mark("step_nll")
 
-    def score_logits(self, ws, target, windows=None, window_pos=None):
+    def score_logits(self, ws, target, windows=None, window_pos=None, weights=None, ignore_index=None, label_smoothing=0.0):
         """(row_nll float32 (B W,), row_hit int32 (B W,)) of the logits a forward left in ws["O"]: nats of every target sample under
-        the per-timestep softmax, and whether the first-index argmax is the target.  Forward only: no gradient is formed."""
+        the per-timestep softmax, and whether the first-index argmax is the target.  Forward only: no gradient is formed.  weights /
+        ignore_index (step_nll): a skipped column reports 0 and 0; row_nll is unsmoothed under any label_smoothing."""
         n = ws["B"] * ws["W"]
         target = target.reshape(-1)
         assert target.numel() == n and target.dtype == torch.int64 and target.is_cuda
         row_nll = torch.empty(n, dtype=torch.float32, device=self.device)
         row_hit = torch.empty(n, dtype=torch.int32, device=self.device)
-        self.step_nll(ws, target, row_nll=row_nll, row_hit=row_hit, windows=windows, window_pos=window_pos)
+        self.step_nll(ws, target, row_nll=row_nll, row_hit=row_hit, windows=windows, window_pos=window_pos, weights=weights,
+                      ignore_index=ignore_index, label_smoothing=label_smoothing)
         return row_nll, row_hit
 
     def step_probs(self, ws, windows=None, window_pos=None):
@@ -884,15 +917,18 @@ class EngineBase:
         self._throttle.leave()
         return out
 
-    def _fused_tail(self, ws, target, want_probs=False, objective=None, windows=None, window_pos=None):
+    def _fused_tail(self, ws, target, want_probs=False, objective=None, windows=None, window_pos=None, weights=None, ignore_index=None,
+                    label_smoothing=0.0):
         """Everything of a fused step behind the forward that left the logits in ws["O"]: softmax + CrossEntropyLoss on the
         probabilities in one kernel (objective "nll": the per-timestep softmax and its negative log-likelihood, step_nll), the
         backward, the loss as a 0-d device tensor.  Gradients land in self.flat_grad.  windows / window_pos: step_nll's; the
-        reference's loss has no per-column softmax to window."""
+        reference's loss has no per-column softmax to window.  weights / ignore_index / label_smoothing: step_nll's, "nll" only too."""
         objective = self._resolve_objective(objective)
         win = self._resolve_windows(windows, window_pos)
         if win is not None and objective != "nll":
             raise ValueError('music_amd: position windows (nll_windows) apply to objective "nll" only, not %r' % objective)
+        if objective != "nll" and self._resolve_wnll(ws, weights, ignore_index, label_smoothing) is not None:
+            raise ValueError('music_amd: weights, ignore_index and label_smoothing apply to objective "nll" only, not %r' % objective)
         bw = self._bwd_workspace(ws)
         n = ws["B"] * ws["W"]
         target = target.reshape(-1)
@@ -904,7 +940,8 @@ class EngineBase:
             probs = torch.empty(n, self.Q, dtype=torch.float32, device=self.device)
             ws["probs"] = probs
         if objective == "nll":
-            self.step_nll(ws, target, bw["dO"], probs, windows=win, window_pos=window_pos)
+            self.step_nll(ws, target, bw["dO"], probs, windows=win, window_pos=window_pos, weights=weights, ignore_index=ignore_index,
+                          label_smoothing=label_smoothing)
         else:
             self.softmax_ce(ws["O"], target, probs, bw["dO"], ws["loss_part"], n)
         if self.vq:                         # reconstruction loss + vq_loss, under either objective; its upstream scalar is 1

@@ -212,15 +212,19 @@ class GenericWaveNetEngine(GeneralPlan):
         self.pack_weights()
         return self.forward_logits(x, classes=classes, phase_pos=phase_pos)
 
-    def loss_and_grad(self, x, target, want_probs=False, objective=None, windows=None, window_pos=None, classes=None, phase_pos=None):
-        """objective: None = self.objective (EngineBase); windows / window_pos: step_nll's; classes, phase_pos: as in forward_logits"""
+    def loss_and_grad(self, x, target, want_probs=False, objective=None, windows=None, window_pos=None, classes=None, phase_pos=None,
+                      weights=None, ignore_index=None, label_smoothing=0.0):
+        """objective: None = self.objective (EngineBase); windows / window_pos, weights / ignore_index / label_smoothing: step_nll's;
+        classes, phase_pos: as in forward_logits"""
         return self._throttled(lambda: self._fused_tail(self._step_forward(x, classes, phase_pos), target, want_probs, objective, windows,
-                                                       window_pos))
+                                                       window_pos, weights=weights, ignore_index=ignore_index,
+                                                       label_smoothing=label_smoothing))
 
     def loss_and_grad_codes(self, codes, target, scrambled=True, want_probs=False, objective=None, windows=None, window_pos=None,
-                            classes=None, phase_pos=None):
+                            classes=None, phase_pos=None, weights=None, ignore_index=None, label_smoothing=0.0):
         """the fast engine's entry point on integer codes; here the one-hot is built (wn_onehot) and the dense path runs"""
-        return self.loss_and_grad(self.onehot(codes, scrambled), target, want_probs, objective, windows, window_pos, classes, phase_pos)
+        return self.loss_and_grad(self.onehot(codes, scrambled), target, want_probs, objective, windows, window_pos, classes, phase_pos,
+                                  weights=weights, ignore_index=ignore_index, label_smoothing=label_smoothing)
 
     def onehot(self, codes, scrambled=True):
         """int32 (B,T) codes on the device -> float32 (B,Q,T) (faster_audio_data.py:62-83)."""

@@ -429,14 +429,17 @@ class _AutoencoderEngine(EngineBase):
         ws["bwd"] = bw
         return bw
 
-    def loss_and_grad(self, x, target, cond=None, objective=None, classes=None, stages=None, windows=None, window_pos=None):
+    def loss_and_grad(self, x, target, cond=None, objective=None, classes=None, stages=None, windows=None, window_pos=None,
+                      weights=None, ignore_index=None, label_smoothing=0.0):
         """Fused training step body (the autoencoder counterpart of engine.loss_and_grad): forward to the logits, ONE
         kernel for chunk softmax + CrossEntropyLoss on the probabilities (wavenet_autoencoder/train.py:146-160) + both
         backward steps, then the backward.  Returns the loss (0-d device tensor); gradients land in self.flat_grad.
         objective: None = self.objective (EngineBase).  stages: as in forward (the backward then runs wn_rvq_bwd_n / _bwd_stats_n).
-        windows / window_pos: step_nll's, here only because the step tail lives in the shared base."""
+        windows / window_pos, weights / ignore_index / label_smoothing: step_nll's, here only because the step tail lives in the shared
+        base."""
         return self._throttled(lambda: self._fused_tail(self.forward(x, cond, want_probs=False, classes=classes, stages=stages)[2], target,
-                                                       objective=objective, windows=windows, window_pos=window_pos))
+                                                       objective=objective, windows=windows, window_pos=window_pos,
+                                                       weights=weights, ignore_index=ignore_index, label_smoothing=label_smoothing))
 
     def backward_from_dlogits(self, ws):
         self.backward(ws, None)

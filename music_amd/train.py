@@ -378,6 +378,10 @@ def train():
     # windows of the samplers applied to that objective - a prior over a residual quantiser's token stream trains on what it samples
     objective = wobjective.objective_option(train_params)
     nll_windows = wobjective.nll_windows_option(train_params, dataset_params, wavenet_params.get("quantization_channels"))
+    # "ignore_token", "label_smoothing", "nll_stage_weights": the masked, weighted and smoothed "nll" (objective.wnll_option) - targets of
+    # the ignored value (a dropped stage's -1, padding) are skipped, the loss is the weighted mean over the rest.  Under data
+    # parallelism every rank normalises by its own sum of weights and the ranks are averaged as before: no collective is added
+    wnll = wobjective.wnll_option(train_params, dataset_params)
     # "global_classes" / "global_channels" in the model's JSON: a class-conditional WaveNet.  The clips' classes come from
     # dataset_params.json's "labels_path" (a JSON list of integers, one per item of the audio pickle; "valid_labels_path" in
     # train_params.json for the held-out set) - as in music_amd/ae_train.py: the mode without labels is refused, labels without it too
@@ -494,6 +498,8 @@ def train():
                 target = target.view(-1)
             win_kw = {} if nll_windows is None else {"windows": nll_windows, "window_pos": sampled_batch.get("audio_pos")}     # (absent on an empty shard)
             cls_kw = {"classes": sampled_batch["audio_class"]} if n_global and "audio_class" in sampled_batch else {}
+            if wnll is not None and piece is not None:
+                cls_kw.update(wobjective.wnll_kwargs(wnll, sampled_batch, target.numel() // piece.shape[0], device))
             if phase_period and piece is not None:        # (a phase-conditioned prior: the clips' stream positions)
                 cls_kw["phase_pos"] = sampled_batch["audio_pos"]
             if class_drop is not None and "classes" in cls_kw:

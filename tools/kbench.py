@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of single kernels of the hot path at BASELINE config-2 shapes (GPU only).
 
-    python tools/kbench.py [fwd|bwd|epi|dx|skip|decode|ae|guard|ema|nll|win_nll|cond|vq|vq_ema|gcond|gclass|phase|rvq|all] [--reps N] [--precision f16x3,bf16x3]
+    python tools/kbench.py [fwd|bwd|epi|dx|skip|decode|ae|guard|ema|nll|win_nll|wnll|cond|vq|vq_ema|gcond|gclass|phase|rvq|all] [--reps N] [--precision f16x3,bf16x3]
 
 Prints per-phase / per-layer kernel times measured with HIP events on the launch stream.
 """
@@ -847,13 +847,75 @@ def win_nll_bench(reps, alternations=6):
     print(json.dumps(res))
 
 
+def wnll_bench(reps, alternations=6):
+    """`wnll`: the masked / weighted / smoothed objective's entry (wn_wstep_nll: the denominator's launch and the main kernel, both
+    inside the timing) against wn_win_step_nll, the entry from before, on identical logits with dx, at a prior's shape (8 x 512 x 4096,
+    windows 4 x 128: the q <= 512 instantiation) and at config 2's (8 x 256 x 12930, windows 4 x 64: the q = 256 one).  Variants:
+    unmasked (the degenerate call: the same arithmetic as the old entry), half the columns ignored, smoothing 0.1.  HIP events around
+    `reps * 20` back-to-back calls, the legs alternated `alternations` times on one device: medians and spreads (largest - smallest).
+    Written to profiles/wnll_kbench.json."""
+    import ctypes
+    from music_amd import _lib
+    from music_amd._lib import call, ptr
+    from music_amd.fast_generate import stage_windows
+    st = _lib.stream()
+    calls = reps * 20
+    res = {"what": "wn_wstep_nll (nll_den_k + step_nll_k) against wn_win_step_nll in one run, %d back-to-back calls per timing, "
+                   "%d alternations; us per call" % (calls, alternations)}
+    g = torch.Generator(device="cuda").manual_seed(0)
+    for label, (B, Q, W, stages) in (("prior_8x512x4096_4x128", (8, 512, 4096, 4)), ("config2_8x256x12930_4x64", (B_LOCAL, 256, T - 3070, 4))):
+        K = Q // stages
+        n = B * W
+        x = torch.randn(B * Q * W, device="cuda", generator=g)
+        pos = torch.randint(0, 1 << 20, (B,), device="cuda", generator=g)
+        col = pos.view(B, 1) + torch.arange(W, device="cuda").view(1, W)
+        target = ((col % stages) * K + torch.randint(0, K, (B, W), device="cuda", generator=g)).reshape(-1).contiguous()
+        half = torch.where(torch.rand(n, device="cuda", generator=g) < 0.5, target, torch.full_like(target, -1))
+        dx = torch.empty_like(x)
+        part = torch.zeros(_lib.CE_NUM_PARTIALS, device="cuda")
+        den = torch.zeros(2, device="cuda")
+        host = (ctypes.c_int32 * (2 * stages))(*[v for pr in stage_windows(stages, K) for v in pr])
+        tail = (ctypes.cast(host, ctypes.c_void_p), stages, ptr(pos), 0)
+        head = lambda t: (ptr(x), Q * W, W, ptr(t), ptr(dx), Q * W, W, None, None, None, ptr(part), W, Q, B)
+        legs = {
+            "win_step_nll": lambda: call("wn_win_step_nll", *head(target), 1.0 / n, *tail, st),
+            "wstep_nll_unmasked": lambda: call("wn_wstep_nll", *head(target), *tail, None, -1, 0.0, ptr(den), st),
+            "wstep_nll_half_masked": lambda: call("wn_wstep_nll", *head(half), *tail, None, -1, 0.0, ptr(den), st),
+            "wstep_nll_smoothing": lambda: call("wn_wstep_nll", *head(target), *tail, None, -1, 0.1, ptr(den), st),
+        }
+
+        def timed(fn):
+            fn()
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            ev[0].record()
+            for _ in range(calls):
+                fn()
+            ev[1].record()
+            torch.cuda.synchronize()
+            return ev[0].elapsed_time(ev[1]) / calls * 1e3
+        us = {k: [] for k in legs}
+        for _ in range(alternations):
+            for k, fn in legs.items():
+                us[k].append(timed(fn))
+        assert not bool(torch.isnan(part.sum()))                     # (the targets respect the windows: a poisoned run measures nothing)
+        r = {"shape": [B, Q, W], "windows": [stages, K], "algorithmic_bytes": 2 * B * Q * W * 4, "extra_bytes_per_column": 4}
+        for k, vals in us.items():
+            r[k + "_us"], r[k + "_us_spread"] = _median_spread(vals)
+            r[k + "_us_all"] = [round(v, 2) for v in vals]
+        for k in list(legs)[1:]:
+            r[k + "_over_old"] = round(r[k + "_us"] / r["win_step_nll_us"], 3)
+        res[label] = r
+    _write_profile("wnll_kbench.json", res)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", nargs="?", default="all")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--precision", default="f16x3,bf16x3")
     ap.add_argument("--overlap", type=int, default=1)
-    ap.add_argument("--parent", default=None, help="gcond / gclass / phase / rvq / rvq_drop / win_nll: a built checkout of the parent commit, for profiles/<what>_bench_unset.json")
+    ap.add_argument("--parent", default=None, help="gcond / gclass / phase / rvq / rvq_drop / win_nll / wnll: a built checkout of the parent commit, for profiles/<what>_bench_unset.json")
     args = ap.parse_args()
     if args.what == "gcond":
         if args.parent:
@@ -879,6 +941,10 @@ def main():
         if args.parent:
             bench_unset(os.path.abspath(args.parent), profile="win_nll_bench_unset.json", keys="nll_windows / token_positions")
         return win_nll_bench(args.reps)
+    if args.what == "wnll":
+        if args.parent:
+            bench_unset(os.path.abspath(args.parent), profile="wnll_bench_unset.json", keys="ignore_token / label_smoothing / nll_stage_weights")
+        return wnll_bench(args.reps)
     if args.what == "vq":
         return vq_bench(args.reps)
     if args.what == "vq_ema":
